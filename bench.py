@@ -22,7 +22,9 @@ With N > 1 both ways of sharing the matrix are timed, K steps each:
 `value` is the faster of the two (named in config.parallelism); both are in `partitionings`.
 `--workload C5 --gpus N` times BASELINE configs[4] as written instead: the matrix kept sharded by rows (no
 all-gather) and fed to the distributed spectral step, both phases reported.
-The K-step block is timed `--repeats` times (5): the line carries the median block, all blocks and the spread.
+Exactly K steps are timed, in `--repeats` blocks (5): `ms_per_step` is the median block's time per step, the
+blocks give the spread.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see matrix_outputs).
 After the timed region the last output is held against the compiled reference's sampled entries where a digest
 exists (C3, C2): `parity_checked`.
 `roofline` is stated against the limit that binds the dominant kernel: LDS atomics at random addresses (peak
@@ -45,6 +47,10 @@ if ROOT not in sys.path:
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PROFILE_ROUND = "r04"   # profiles/<round>_*.json: the counter-derived inputs of the roofline record
 LIVE_COUNTERS_BUDGET_S = 240.0  # all rocprofv3 --pmc child passes of a default run together
+DUMP_BYTES_MAX = 64 << 20       # --dump-outputs: all arrays of one run together
+DUMP_FULL_BYTES = 32 << 20      # a matrix up to this size is written whole (C1, C2), a larger one as a sample
+DUMP_SAMPLE = 1 << 21           # sampled entries (values, rows, columns: 3 x 16 MB)
+DUMP_SEED = 20240601
 
 
 def _pmc_pass(counters, program, out_dir, timeout):
@@ -196,13 +202,68 @@ def cpu_baseline(p, n_cells, mfl, rates, threads, budget_updates):
             "host_cpus": os.cpu_count()}
 
 
+def block_sizes(steps, repeats):
+    """The K timed steps cut into `repeats` blocks (at most K), as even as possible: together exactly K steps."""
+    n = max(1, min(repeats, steps))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+def matrix_outputs(rows, row_begin, n_cells, reduce=None):
+    """What --dump-outputs writes of the similarity matrix, given this rank's rows [row_begin, row_begin + len(rows))
+    as a CUDA float64 tensor. A matrix of at most DUMP_FULL_BYTES whole; a larger one as a fixed sample of entries
+    (DUMP_SEED: the same (row, column) pairs in every run of the same workload) and the fp64 sum of every row. With
+    the matrix sharded by rows, `reduce` sums a tensor over the ranks: each entry and row sum comes from one rank."""
+    import numpy as np
+    import torch
+    n_rows = rows.shape[0]
+    if reduce is None and n_rows == n_cells and n_cells * n_cells * 8 <= DUMP_FULL_BYTES:
+        return {"similarity_matrix": rows.cpu().numpy()}
+    rng = np.random.default_rng(DUMP_SEED)
+    i = rng.integers(0, n_cells, DUMP_SAMPLE)
+    j = rng.integers(0, n_cells, DUMP_SAMPLE)
+    mine = np.nonzero((i >= row_begin) & (i < row_begin + n_rows))[0]
+    sample = torch.zeros(DUMP_SAMPLE, dtype=torch.float64, device=rows.device)
+    if len(mine):
+        at = lambda a: torch.from_numpy(a).to(rows.device)
+        sample[at(mine)] = rows[at(i[mine] - row_begin), at(j[mine])]
+    row_sums = torch.zeros(n_cells, dtype=torch.float64, device=rows.device)
+    row_sums[row_begin:row_begin + n_rows] = rows.sum(dim=1)
+    if reduce is not None:
+        sample, row_sums = reduce(sample), reduce(row_sums)
+    return {"similarity_matrix_sample": sample.cpu().numpy(),
+            "similarity_matrix_sample_rows": i.astype(np.float64),
+            "similarity_matrix_sample_cols": j.astype(np.float64),
+            "similarity_matrix_row_sums": row_sums.cpu().numpy()}
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: every array as directory/<name>.npy (float32 / float64, DUMP_BYTES_MAX in all).
+    Returns {name: shape} for the result line."""
+    import numpy as np
+    arrays = {name: np.ascontiguousarray(a) for name, a in arrays.items()}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise ValueError("--dump-outputs: %d bytes, more than %d" % (total, DUMP_BYTES_MAX))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in sorted(arrays.items())}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps in all (K)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the K-step block is timed this many times; the line reports the median block and the spread")
+                    help="the K timed steps are timed in this many blocks (at most K); the line reports the median "
+                         "block's time per step and the spread")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; the "
+                         "whole matrix up to C2's size, else a fixed seeded sample of entries and the row sums)")
     ap.add_argument("--workload", default="C3", choices=["C1", "C2", "C3", "C5"])
     ap.add_argument("--clustered", action="store_true", help="gap_max=300 variant (~2.8 loci/read)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -231,7 +292,10 @@ def parse_args(argv=None):
                     help="keep the PACKED pileup resident and leave the packing out of the step "
                          "(steady state of repeated accumulations; default: the step starts from the raw "
                          "flat pileup in HBM and includes the device-side packing)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -376,13 +440,14 @@ def main():
         plan.accumulate(acc, *rates, *my_tiles, overwrite=True)
         local_updates, local_pairs = plan.last_counts()
         sync()
-        # EXACTLY K steps between barrier + synchronize on both sides, `--repeats` times over; the reported block
-        # is the median one (max over ranks of each block first), the others give the spread
+        # EXACTLY K timed steps in all, in `--repeats` blocks, each between barrier + synchronize on both sides; the
+        # reported step is the median block's (max over ranks of each block first), the others give the spread
+        sizes = block_sizes(args.steps, args.repeats)
         blocks = []
-        for _ in range(max(1, args.repeats)):
+        for size in sizes:
             sync()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(size):
                 step()
             sync()
             blocks.append(time.perf_counter() - t0)
@@ -390,8 +455,8 @@ def main():
         bt = torch.tensor(blocks, dtype=torch.float64, device=red_dev)
         if dist_on:
             dist.all_reduce(bt, op=dist.ReduceOp.MAX)
-        blocks = sorted(float(v) for v in bt)
-        elapsed = blocks[len(blocks) // 2]
+        blocks = sorted(float(v) / size for v, size in zip(bt, sizes))  # seconds per step of each block
+        elapsed = blocks[len(blocks) // 2] * args.steps
 
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         own = by_chromosome or rank == 0
@@ -442,14 +507,28 @@ def main():
 
         for _ in range(args.warmup):
             step()
+        sizes = block_sizes(args.steps, args.repeats)  # exactly K timed steps in all
         blocks = []
-        for _ in range(max(1, args.repeats)):
+        for size in sizes:
             sync()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(size):
                 step()
             sync()
             blocks.append(time.perf_counter() - t0)
+        dumped = None
+        if args.dump_outputs:  # the last timed step's row blocks and eigenpairs, before the phase timings redo them
+
+            def reduce(t):
+                t = t.to(red_dev)
+                dist.all_reduce(t, op=dist.ReduceOp.SUM)
+                return t
+            arrays = matrix_outputs(state["rows"], state["lo"], n_cells, reduce)
+            if rank == 0:
+                vals, vecs, _ = state["eig"]
+                arrays["spectral_eigenvalues"] = np.asarray(vals, dtype=np.float64)
+                arrays["spectral_eigenvectors"] = vecs.cpu().numpy()
+                dumped = write_outputs(args.dump_outputs, arrays)
         phases = {}
         for name, fn in (("matrix_sharded_rows_ms", matrix_step), ("spectral_sharded_ms", spectral_step)):
             ts = []
@@ -466,8 +545,8 @@ def main():
         if world > 1:
             dist.all_reduce(bt, op=dist.ReduceOp.MAX)
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
-        blocks = sorted(float(v) for v in bt[:-2])
-        elapsed = blocks[len(blocks) // 2]
+        blocks = sorted(float(v) / size for v, size in zip(bt[:-2], sizes))  # seconds per step of each block
+        elapsed = blocks[len(blocks) // 2] * args.steps
         if rank == 0:
             vals, _, info = state["eig"]
             step_s = elapsed / args.steps
@@ -485,12 +564,12 @@ def main():
                            "parallelism": "row blocks/%d: tiles touching own rows + scalar max all-reduce; spectral: "
                                           "row-block products + all-reduce of N x 32 fp64" % world,
                            "backend": backend_name, "world_size": world, "rccl_world_size": pg_world},
-                "block_ms": [b / args.steps * 1e3 for b in blocks],
-                "spread": (blocks[-1] - blocks[0]) / elapsed if elapsed else None,
+                "block_ms": [b * 1e3 for b in blocks],
+                "spread": (blocks[-1] - blocks[0]) / step_s if step_s else None,
                 "phase_ms": {"matrix_sharded_rows": float(bt[-2].item()), "spectral_sharded": float(bt[-1].item())},
                 "spectral": {"smallest_eigenvalues": [float(v) for v in vals[:4]], **info},
                 "first_prepare_s": prepare_s, "step_includes_packing": not args.packed_resident,
-                "roofline": None, "cpu_baseline": None,
+                "roofline": None, "cpu_baseline": None, "dumped_outputs": dumped,
             })
 
     backend_name = "none" if not dist_on else ("RCCL (nccl)" if args.backend == "nccl" else args.backend)
@@ -532,6 +611,9 @@ def main():
 
     # parity of the LAST TIMED OUTPUT (outside the timed region): `out` still holds what the last timed step of
     # the last partitioning wrote; held against the compiled reference's sampled entries where a digest exists
+    # (and written by --dump-outputs: every rank holds the whole matrix)
+    dumped = write_outputs(args.dump_outputs, matrix_outputs(out, 0, n_cells)) \
+        if args.dump_outputs and rank == 0 else None
     parity = None
     digest = reference_digest(args.workload, args.clustered, int(p.n_entries), rates, mfl, threads) if rank == 0 else None
     if digest is not None:
@@ -685,8 +767,8 @@ def main():
                 "replicated_ms_per_step": phase.get("pack_ms") if world > 1 and not by_chromosome else None},
             # the K-step block, timed `repeats` times: value / ms_per_step are the median block's
             "repeats": len(best["blocks"]),
-            "block_ms_per_step": [b / args.steps * 1e3 for b in best["blocks"]],
-            "spread": (best["blocks"][-1] - best["blocks"][0]) / elapsed if elapsed else None,
+            "block_ms_per_step": [b * 1e3 for b in best["blocks"]],
+            "spread": (best["blocks"][-1] - best["blocks"][0]) / step_s if step_s else None,
             "parity_checked": bool(parity and parity["ok"]),
             "parity": parity,
             "partitionings": {("chromosomes+all-reduce" if m["by_chromosome"] else
@@ -703,6 +785,7 @@ def main():
             "first_prepare_s": best["prepare_s"],
             "scale_log2": plan.scale_log2,
             "roofline": roofline,
+            "dumped_outputs": dumped,
         }
         if not args.no_cpu_baseline and world == 1:
             # the drop-in call itself: host buffers in, host matrix out (H2D, pack, accumulate, normalise,

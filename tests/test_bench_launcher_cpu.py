@@ -39,3 +39,36 @@ def test_bench_default_workload_is_the_headline_configuration():
     import bench
     args = bench.parse_args([])
     assert args.workload == "C3" and args.gpus == 1  # BASELINE.json configs[2]: 8000 cells x 100K loci
+
+
+def test_bench_steps_are_the_timed_steps():
+    sys.path.insert(0, ROOT)
+    import bench
+    for steps in (1, 2, 3, 7, 20):
+        for repeats in (1, 5, 30):
+            sizes = bench.block_sizes(steps, repeats)
+            assert sum(sizes) == steps and len(sizes) == min(steps, repeats) and max(sizes) - min(sizes) <= 1
+
+
+def test_bench_dumped_matrix_sample_is_fixed_and_independent_of_sharding(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    n = 700
+    m = torch.arange(n * n, dtype=torch.float64).reshape(n, n)
+    assert list(bench.matrix_outputs(m, 0, n)) == ["similarity_matrix"]
+    monkeypatch.setattr(bench, "DUMP_FULL_BYTES", 1024)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 5000)
+    whole = bench.matrix_outputs(m, 0, n)
+    i, j = (whole["similarity_matrix_sample_" + k].astype(np.int64) for k in ("rows", "cols"))
+    assert np.array_equal(whole["similarity_matrix_sample"], m.numpy()[i, j])
+    assert np.array_equal(whole["similarity_matrix_row_sums"], m.sum(dim=1).numpy())
+    # the matrix kept sharded by rows: each rank fills its own rows, the sum over the ranks is the whole
+    parts = [bench.matrix_outputs(m[lo:hi], lo, n, reduce=lambda t: t) for lo, hi in ((0, 256), (256, n))]
+    for k, v in whole.items():
+        summed = k in ("similarity_matrix_sample", "similarity_matrix_row_sums")
+        assert np.array_equal(parts[0][k] + parts[1][k] if summed else parts[0][k], v), k
+    shapes = bench.write_outputs(str(tmp_path / "out"), whole)
+    assert shapes["similarity_matrix_sample"] == [5000]
+    assert np.array_equal(np.load(tmp_path / "out" / "similarity_matrix_sample.npy"), whole["similarity_matrix_sample"])
