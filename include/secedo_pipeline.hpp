@@ -8,11 +8,23 @@
 //   void smallest_eigenpairs(similarity, n_values, n_vectors, &eigenvalues, &eigenvectors)
 //        replaces laplacian() + arma::eig_sym in spectral_clustering() (spectral_clustering.cpp:127-138);
 //        eigenvectors column-major n x n_vectors (arma::mat layout)
+//   uint32_t spectral_clustering(similarity, clustering, termination, out_dir, marker, use_arma_kmeans, &cluster)
+//        reference: spectral_clustering.cpp:117-299; clustering and termination as the strings the reference
+//        parses (parse_clustering_type / parse_termination), so that no reference header is needed
+//   void divide_cluster(pds, max_read_length, id_to_group, id_to_pos, pos_to_id, mutation_rate, homozygous_rate,
+//                       seq_error_rate, num_threads, out_dir, normalization, termination, clustering_type,
+//                       use_arma_kmeans, use_expectation_maximization, min_cluster_size, cell_proportion, marker,
+//                       &clusters, &cluster_idx)
+//        reference: spectral_clustering.cpp:311-434
+// The last two need libsecedo_cluster.so (include/secedo_cluster.h) at link time. num_threads and out_dir are
+// accepted and unused: the GPU path needs no thread count and writes no files (the optional `levels` output
+// carries what the reference logs and writes per level).
 //
 // A failure of the library throws std::runtime_error with the library's message; the reference has no
 // error path at these places (it asserts, or reads out of bounds).
 #pragma once
 
+#include "secedo_cluster.h"
 #include "secedo_em.h"
 #include "secedo_simmat.h"
 #include "secedo_spectral.h"
@@ -91,6 +103,54 @@ void smallest_eigenpairs(const MatdT &similarity, uint32_t n_values, uint32_t n_
         throw std::runtime_error("secedo_spectral: the eigensolver did not converge (residual "
                                  + std::to_string(info.max_residual_vectors) + " after "
                                  + std::to_string(info.cycles) + " cycles)");
+}
+
+// MatdT as for smallest_eigenpairs. Returns the number of clusters (1 = stop), cluster[n] the labels.
+// An unknown clustering type throws std::invalid_argument, as parse_clustering_type does.
+template <class MatdT>
+uint32_t spectral_clustering(const MatdT &similarity, const std::string &clustering, const std::string &termination,
+                             const std::string & /*out_dir*/, const std::string & /*marker*/, bool use_arma_kmeans,
+                             std::vector<double> *cluster, secedo_cluster_decision *decision = nullptr) {
+    const int type = secedo_cluster_type_from_string(clustering.c_str());
+    if (type < 0) throw std::invalid_argument(clustering);
+    const uint32_t n = similarity.rows();
+    cluster->assign(n, 0.0);
+    uint32_t num_clusters = 0;
+    const int rc = secedo_spectral_clustering(0, similarity.data(), n, type,
+                                              secedo_termination_from_string(termination.c_str()), use_arma_kmeans,
+                                              cluster->data(), &num_clusters, decision, nullptr);
+    if (rc != SECEDO_OK) throw std::runtime_error(std::string("secedo_cluster: ") + secedo_cluster_last_error());
+    return num_clusters;
+}
+
+// PosDataT as for flatten (group ids in group_ids_bases). clusters[id] and *cluster_idx in/out as in the reference.
+template <class PosDataT>
+void divide_cluster(const std::vector<std::vector<PosDataT>> &pds, uint32_t max_read_length,
+                    const std::vector<uint16_t> &id_to_group, const std::vector<uint32_t> &id_to_pos,
+                    const std::vector<uint32_t> &pos_to_id, double mutation_rate, double homozygous_rate,
+                    double seq_error_rate, const uint32_t /*num_threads*/, const std::string & /*out_dir*/,
+                    const std::string &normalization, const std::string &termination_str,
+                    const std::string &clustering_type_str, bool use_arma_kmeans, bool use_expectation_maximization,
+                    uint32_t min_cluster_size, uint8_t cell_proportion, const std::string marker,
+                    std::vector<uint16_t> *clusters, uint16_t *cluster_idx,
+                    std::vector<secedo_cluster_level> *levels = nullptr) {
+    const int norm = secedo_simmat_normalization_from_string(normalization.c_str());
+    if (norm < 0) throw std::logic_error("Invalid normalization: " + normalization);
+    const int type = secedo_cluster_type_from_string(clustering_type_str.c_str());
+    if (type < 0) throw std::invalid_argument(clustering_type_str);
+    const FlatPileupHost flat = flatten(pds);
+    std::vector<secedo_cluster_level> records(4 * pos_to_id.size() + 16);
+    uint32_t n_records = 0;
+    const int rc = secedo_divide_cluster(
+            0, flat.chr_locus_off.data(), static_cast<uint32_t>(flat.chr_locus_off.size() - 1), flat.locus_pos.data(),
+            flat.locus_entry_off.data(), flat.read_ids.data(), flat.id_base.data(), nullptr, max_read_length,
+            id_to_group.data(), static_cast<uint32_t>(id_to_group.size()), id_to_pos.data(),
+            static_cast<uint32_t>(id_to_pos.size()), pos_to_id.data(), static_cast<uint32_t>(pos_to_id.size()),
+            mutation_rate, homozygous_rate, seq_error_rate, norm, secedo_termination_from_string(termination_str.c_str()),
+            type, use_arma_kmeans, use_expectation_maximization, min_cluster_size, cell_proportion, marker.c_str(),
+            clusters->data(), cluster_idx, records.data(), static_cast<uint32_t>(records.size()), &n_records);
+    if (rc != SECEDO_OK) throw std::runtime_error(std::string("secedo_cluster: ") + secedo_cluster_last_error());
+    if (levels) levels->assign(records.begin(), records.begin() + n_records);
 }
 
 }  // namespace secedo_amd

@@ -8,7 +8,8 @@
  * of which the reference uses the 20 smallest eigenvalues (:141-143, a CSV for inspection) and the
  * eigenvectors of the 7 smallest (columns 0..6: :166, :171-172, :221, :235-237). The dense O(N^3)
  * decomposition is replaced by a block Krylov iteration on the matrix where it already lies (HBM):
- * the normalised Laplacian is never formed, the GMM / k-means that follow stay on the host.
+ * the normalised Laplacian is never formed. The GMM / k-means that follow run on the device as well:
+ * include/secedo_cluster.h (libsecedo_cluster.so), which also drives the divide_cluster recursion.
  *
  * L = I - D^-1/2 A D^-1/2 with D = diag(row sums of A), 1/sqrt(0) := 0 as in the reference (:40-41).
  * Eigenvalues ascending (eig_sym order). An eigenvector's sign is arbitrary in LAPACK; here the

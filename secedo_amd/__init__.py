@@ -11,3 +11,4 @@ from .filter import Filter, NO_POS, filter_resident  # noqa: F401,E402
 from .pileup_reader import get_grouping, read_pileup  # noqa: F401,E402
 from .spectral import laplacian, smallest_eigenpairs  # noqa: F401,E402
 from .em import expectation_maximization  # noqa: F401,E402
+from .cluster import divide_cluster, divide_cluster_resident, spectral_clustering  # noqa: F401,E402
