@@ -16,7 +16,10 @@
 //                       use_arma_kmeans, use_expectation_maximization, min_cluster_size, cell_proportion, marker,
 //                       &clusters, &cluster_idx)
 //        reference: spectral_clustering.cpp:311-434
-// The last two need libsecedo_cluster.so (include/secedo_cluster.h) at link time. num_threads and out_dir are
+//   void variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir)
+//        reference: variant_calling.cpp:323-461; writes the same files (needs libsecedo_variant.so,
+//        include/secedo_variant.h, at link time)
+// divide_cluster and spectral_clustering need libsecedo_cluster.so (include/secedo_cluster.h) at link time. num_threads and out_dir are
 // accepted and unused: the GPU path needs no thread count and writes no files (the optional `levels` output
 // carries what the reference logs and writes per level).
 //
@@ -28,8 +31,10 @@
 #include "secedo_em.h"
 #include "secedo_simmat.h"
 #include "secedo_spectral.h"
+#include "secedo_variant.h"
 
 #include <cstdint>
+#include <filesystem>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -151,6 +156,22 @@ void divide_cluster(const std::vector<std::vector<PosDataT>> &pds, uint32_t max_
             clusters->data(), cluster_idx, records.data(), static_cast<uint32_t>(records.size()), &n_records);
     if (rc != SECEDO_OK) throw std::runtime_error(std::string("secedo_cluster: ") + secedo_cluster_last_error());
     if (levels) levels->assign(records.begin(), records.begin() + n_records);
+}
+
+// variant_calling (variant_calling.cpp:323-461): cluster_<i>.vcf, common.vcf, variant and scores under out_dir.
+// Nothing is written for empty clusters, as in the reference.
+template <class PosDataT>
+void variant_calling(const std::vector<std::vector<PosDataT>> &pos_data, const std::vector<uint16_t> &clusters,
+                     const std::string &reference_genome, const std::string &map_file, double hetero_prior,
+                     double theta, const std::filesystem::path &out_dir) {
+    if (clusters.empty()) return;
+    const FlatPileupHost flat = flatten(pos_data);
+    const int rc = secedo_variant_calling(
+            0, flat.chr_locus_off.data(), static_cast<uint32_t>(flat.chr_locus_off.size() - 1), flat.locus_pos.data(),
+            flat.locus_entry_off.data(), flat.id_base.data(), nullptr, clusters.data(),
+            static_cast<uint32_t>(clusters.size()), reference_genome.c_str(), map_file.c_str(), hetero_prior, theta,
+            out_dir.c_str(), nullptr);
+    if (rc != SECEDO_OK) throw std::runtime_error(secedo_variant_last_error());
 }
 
 }  // namespace secedo_amd

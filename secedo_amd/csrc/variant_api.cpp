@@ -1,0 +1,821 @@
+// variant_api.cpp -- host side of include/secedo_variant.h: the reference genome (FASTA + Varsim map), the
+// per-locus gather of the reference genotype, the constant tables, the launches of variant_kernels.hip and the
+// VCF / scores text of the reference's variant_calling() (variant_calling.cpp:81-461).
+//
+// The FASTA is memory-mapped and read through a small restatement of the std::ifstream calls the reference
+// makes (getline, peek, get, putback), so that its quirks carry over: a contig header directly after another
+// is read as sequence, a FASTA with fewer contigs than the pileup has chromosomes leaves the last contig in
+// place (:161-163), and a missing paternal contig reads as empty.
+#include "secedo_variant.h"
+#include "secedo_simmat.h"
+#include "variant_kernels.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <ctime>
+#include <filesystem>
+#include <string>
+#include <string_view>
+#include <unordered_map>
+#include <vector>
+
+namespace {
+
+using secedo::variant::Logs;
+
+thread_local std::string g_error;
+
+int fail(int code, const std::string &msg) {
+    g_error = msg;
+    return code;
+}
+
+#define VC_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) return fail(SECEDO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+#define VC_CALL(expr)                 \
+    do {                              \
+        int rc_ = (expr);             \
+        if (rc_ != SECEDO_OK) return rc_; \
+    } while (0)
+
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point &t0) {
+    const Clock::time_point t1 = Clock::now();
+    const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+    return ms;
+}
+
+constexpr char kIntToChar[6] = {'A', 'C', 'G', 'T', 'N', 'N'};
+
+// CharToInt (util/util.hpp:17-22): A/a 0, C/c 1, G/g 2, T/t/U/u 3, anything else 5
+uint8_t char_to_int(char c) {
+    switch (c) {
+        case 'A': case 'a': return 0;
+        case 'C': case 'c': return 1;
+        case 'G': case 'g': return 2;
+        case 'T': case 't': case 'U': case 'u': return 3;
+        default: return 5;
+    }
+}
+
+std::string id_to_chromosome(uint32_t chr_id) {
+    if (chr_id < 22) return std::to_string(chr_id + 1);
+    return chr_id == 22 ? "X" : "Y";
+}
+
+struct Buf {
+    void *p = nullptr;
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
+    hipError_t alloc(size_t bytes) {
+        release();
+        return hipMalloc(&p, std::max<size_t>(bytes, 8));
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    template <class T>
+    T *as() const { return static_cast<T *>(p); }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// The reference genome
+
+// A read-only mapping of a file with the std::istream calls get_next_chromosome makes. `fail` is the stream's
+// failbit: once set, every call fails, as the reference's stream does.
+struct Fasta {
+    const char *p = nullptr;
+    size_t n = 0, pos = 0;
+    bool fail = false;
+    int fd = -1;
+
+    ~Fasta() {
+        if (p && n) munmap(const_cast<char *>(p), n);
+        if (fd >= 0) close(fd);
+    }
+    bool open(const char *path) {
+        fd = ::open(path, O_RDONLY);
+        if (fd < 0) return false;
+        struct stat st;
+        if (fstat(fd, &st) != 0) return false;
+        n = static_cast<size_t>(st.st_size);
+        if (n) {
+            void *m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) return false;
+            madvise(m, n, MADV_SEQUENTIAL);
+            p = static_cast<const char *>(m);
+        }
+        return true;
+    }
+    bool getline(std::string_view *line) {
+        if (fail || pos >= n) {
+            fail = true;
+            return false;
+        }
+        const char *nl = static_cast<const char *>(memchr(p + pos, '\n', n - pos));
+        const size_t end = nl ? static_cast<size_t>(nl - p) : n;
+        *line = std::string_view(p + pos, end - pos);
+        pos = nl ? end + 1 : n;
+        return true;
+    }
+    int peek() const { return (fail || pos >= n) ? EOF : static_cast<unsigned char>(p[pos]); }
+    int get() {
+        if (fail || pos >= n) {
+            fail = true;
+            return EOF;
+        }
+        return static_cast<unsigned char>(p[pos++]);
+    }
+    void putback() {
+        if (!fail && pos > 0) --pos;
+    }
+};
+
+struct ChrMap {
+    uint32_t start_pos;
+    uint32_t len;
+    char tr;
+    uint8_t chromosome_id;
+};
+
+struct MapEntry {
+    std::string name;
+    ChrMap m;
+};
+
+// split(s, '\t') of util.cpp: std::getline segments, so a trailing delimiter adds no empty field
+std::vector<std::string> split(const std::string &s, char c) {
+    std::vector<std::string> out;
+    size_t b = 0;
+    while (b < s.size()) {
+        size_t e = s.find(c, b);
+        if (e == std::string::npos) e = s.size();
+        out.emplace_back(s, b, e - b);
+        b = e + 1;
+    }
+    return out;
+}
+
+bool parse_ulong(const std::string &s, unsigned long *v) {  // std::stoul, which throws where this fails
+    const char *b = s.c_str();
+    char *end;
+    errno = 0;
+    *v = strtoul(b, &end, 10);
+    return end != b && errno == 0;
+}
+
+// chromosome_to_id (util.cpp:143-160)
+bool chromosome_to_id(const std::string &chromosome, uint8_t *id) {
+    char *p;
+    const uint32_t converted = static_cast<uint32_t>(strtol(chromosome.c_str(), &p, 10));
+    if (*p) {
+        if (chromosome != "X" && chromosome != "Y") return false;
+        *id = chromosome == "X" ? 22 : 23;
+        return true;
+    }
+    if (converted > 22) return false;
+    *id = static_cast<uint8_t>(converted - 1);
+    return true;
+}
+
+// read_map (:81-115), entries in file order
+int read_map(const char *map_file, std::vector<MapEntry> *out) {
+    out->clear();
+    if (!map_file || !*map_file) return SECEDO_OK;
+    FILE *f = fopen(map_file, "rb");
+    if (!f) return fail(SECEDO_E_INVALID_ARG, std::string("Map file: ") + map_file + " does not exist.");
+    std::string text;
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    fclose(f);
+    size_t b = 0;
+    while (b < text.size()) {
+        size_t e = text.find('\n', b);
+        if (e == std::string::npos) e = text.size();
+        const std::string line = text.substr(b, e - b);
+        b = e + 1;
+        if (line.empty() || line[0] == '#') continue;
+        const std::vector<std::string> cols = split(line, '\t');
+        if (cols.size() != 8)
+            return fail(SECEDO_E_INVALID_ARG, std::string("Invalid map file: ") + map_file + ". Has " +
+                                                      std::to_string(cols.size()) + " columns, expected 8.");
+        // the chromosome-name guard of :102 (c < '1' && c > '9' && ...) is never true: no line is skipped there
+        if (cols[6] == "SEQ") continue;
+        unsigned long start, len;
+        if (!parse_ulong(cols[2], &start) || !parse_ulong(cols[0], &len))
+            return fail(SECEDO_E_INVALID_ARG, std::string("Invalid map file: ") + map_file + ". Bad line: " + line);
+        MapEntry m;
+        m.name = cols[1];
+        m.m.start_pos = static_cast<uint32_t>(start) - 1;
+        m.m.len = static_cast<uint32_t>(len);
+        m.m.tr = cols[6] == "INS" ? 'I' : 'D';
+        if (!chromosome_to_id(cols[3], &m.m.chromosome_id))
+            return fail(SECEDO_E_INVALID_ARG, "Invalid chromosome: " + cols[3] + ". Must be 1..22, X, Y");
+        out->push_back(std::move(m));
+    }
+    return SECEDO_OK;
+}
+
+// apply_map (:117-141). A start position past the contig's end, where the reference reads out of bounds, is
+// an error.
+int apply_map(const std::vector<ChrMap> &map, const std::vector<uint8_t> &chr_data, std::vector<uint8_t> *out) {
+    uint64_t i = 0;
+    out->clear();
+    out->reserve(chr_data.size());
+    for (const ChrMap &m : map) {
+        if (i < m.start_pos) {
+            if (m.start_pos > chr_data.size())
+                return fail(SECEDO_E_INVALID_ARG, "map entry at " + std::to_string(m.start_pos) +
+                                                          " lies past the contig's end (" +
+                                                          std::to_string(chr_data.size()) + ")");
+            out->insert(out->end(), chr_data.begin() + i, chr_data.begin() + m.start_pos);
+            i = m.start_pos;
+        }
+        if (m.tr == 'D') out->insert(out->end(), m.len, 5);
+        else i += m.len;
+    }
+    if (i < chr_data.size()) out->insert(out->end(), chr_data.begin() + i, chr_data.end());
+    return SECEDO_OK;
+}
+
+using Map = std::unordered_map<std::string, std::vector<ChrMap>>;
+
+Map group_map(const std::vector<MapEntry> &entries) {
+    Map m;
+    for (const MapEntry &e : entries) m[e.name].push_back(e.m);
+    return m;
+}
+
+// read_contig (:143-153)
+void read_contig(Fasta &f, std::vector<uint8_t> *chr_data) {
+    std::string_view line;
+    while (f.getline(&line)) {
+        const size_t at = chr_data->size();
+        chr_data->resize(at + line.size());
+        uint8_t *d = chr_data->data() + at;
+        for (size_t k = 0; k < line.size(); ++k) d[k] = char_to_int(line[k]);
+        if (f.peek() == '>') break;
+    }
+}
+
+// check_is_diploid (:281-286): the first whitespace-delimited word contains "maternal"
+bool check_is_diploid(const Fasta &f) {
+    size_t b = 0;
+    while (b < f.n && isspace(static_cast<unsigned char>(f.p[b]))) ++b;
+    size_t e = b;
+    while (e < f.n && !isspace(static_cast<unsigned char>(f.p[e]))) ++e;
+    return std::string_view(f.p + b, e - b).find("maternal") != std::string_view::npos;
+}
+
+// get_next_chromosome (:155-224)
+int get_next_chromosome(Fasta &f, const Map &map, bool is_diploid, std::vector<uint8_t> *chr_data,
+                        std::vector<uint8_t> *tmp1, std::vector<uint8_t> *tmp2) {
+    std::string_view header;
+    if (!f.getline(&header)) return SECEDO_OK;  // fewer contigs: the previous one stays
+    if (header.empty()) return fail(SECEDO_E_INVALID_ARG, "reference genome: empty line where a contig header is expected");
+    const char chromosome = header.size() > 1 ? header[1] : '\0';
+    std::string chr_name(header.substr(1));
+    tmp1->clear();
+    read_contig(f, tmp1);
+    auto it = map.find(chr_name);
+    if (it != map.end()) VC_CALL(apply_map(it->second, *tmp1, chr_data));
+    else std::swap(*tmp1, *chr_data);
+
+    const int ch1 = f.get();
+    const int ch2 = f.peek();
+    if (ch1 != EOF) f.putback();
+    if (!is_diploid || (chromosome == 'X' && ch2 == 'Y') || chromosome == 'Y') {
+        for (uint8_t &x : *chr_data) x |= static_cast<uint8_t>(x << 3);
+        return SECEDO_OK;
+    }
+    std::string_view second;
+    if (f.getline(&second) && !second.empty()) chr_name.assign(second.substr(1));  // else the line is unchanged
+    tmp1->clear();
+    read_contig(f, tmp1);
+    it = map.find(chr_name);
+    if (it != map.end()) VC_CALL(apply_map(it->second, *tmp1, tmp2));
+    else std::swap(*tmp1, *tmp2);
+    if (chr_data->size() != tmp2->size())
+        return fail(SECEDO_E_INVALID_ARG, "Invalid reference genome. Maternal and paternal chromosome sizes don't "
+                                          "match (" + std::to_string(chr_data->size()) + " vs " +
+                                          std::to_string(tmp2->size()) + ")");
+    for (size_t i = 0; i < chr_data->size(); ++i) (*chr_data)[i] = static_cast<uint8_t>(((*chr_data)[i] << 3) | (*tmp2)[i]);
+    return SECEDO_OK;
+}
+
+int open_fasta(const char *path, Fasta *f) {
+    if (!path || !std::filesystem::exists(path))
+        return fail(SECEDO_E_INVALID_ARG, std::string("Reference genome ") + (path ? path : "(null)") + " does not exist");
+    if (!f->open(path)) return fail(SECEDO_E_INVALID_ARG, std::string("cannot read ") + path);
+    return SECEDO_OK;
+}
+
+// The host half of variant_calling before the locus loop: locus_ref and chr_locus_end (see the header).
+int reference_genotypes(const char *fasta, const char *map_file, const uint32_t *chr_locus_off, uint32_t n_chr,
+                        const uint32_t *locus_pos, uint8_t *locus_ref, uint32_t *chr_locus_end, double *fasta_ms) {
+    Clock::time_point t0 = Clock::now();
+    Fasta f;
+    VC_CALL(open_fasta(fasta, &f));
+    std::vector<MapEntry> entries;
+    VC_CALL(read_map(map_file, &entries));
+    const Map map = group_map(entries);
+    const bool diploid = check_is_diploid(f);
+    std::vector<uint8_t> chr, tmp1, tmp2;
+    double parse = 0;
+    for (uint32_t c = 0; c < n_chr; ++c) {
+        Clock::time_point t1 = Clock::now();
+        VC_CALL(get_next_chromosome(f, map, diploid, &chr, &tmp1, &tmp2));
+        parse += ms_since(t1);
+        const uint32_t b = chr_locus_off[c], e = chr_locus_off[c + 1];
+        uint32_t l = b;
+        for (; l < e; ++l) {
+            const uint32_t p = locus_pos[l] - 1;  // uint32: position 0 wraps and ends the chromosome
+            if (p >= chr.size()) break;
+            locus_ref[l] = chr[p];
+        }
+        chr_locus_end[c] = l;
+        for (; l < e; ++l) locus_ref[l] = 0;
+    }
+    if (fasta_ms) *fasta_ms = parse + (n_chr == 0 ? ms_since(t0) : 0.0);
+    return SECEDO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Device side
+
+int set_device(int device_id) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(SECEDO_E_NO_DEVICE, "no HIP device");
+    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_INVALID_ARG, "device id out of range");
+    VC_TRY(hipSetDevice(device_id));
+    return SECEDO_OK;
+}
+
+Logs host_logs(double hetero_prior, double theta) {
+    return Logs{std::log(theta / 3), std::log(1 - theta), std::log(0.5 - theta / 3), std::log(hetero_prior)};
+}
+
+// likely_homozygous' threshold, std::round(cov * theta + std::sqrt(cov * theta * (1 - theta))), for every u16 cov
+std::vector<double> threshold_table(double theta) {
+    std::vector<double> t(secedo::variant::kThresholds);
+    for (uint32_t cov = 0; cov < t.size(); ++cov) t[cov] = std::round(cov * theta + std::sqrt(cov * theta * (1 - theta)));
+    return t;
+}
+
+// Global atomics by default: on the whole-pileup bench the LDS copy (64 KiB per workgroup, two workgroups per CU)
+// took 25.1 ms against 20.0 ms, on C3 1.22 ms against 1.21 ms.
+constexpr bool kLdsDefault = false;
+
+struct Calls {
+    std::vector<secedo_variant_record> records;
+    uint32_t total = 0;
+    double kernel_ms = 0;
+};
+
+// Both passes on a resident pileup; records downloaded when they fit `capacity`.
+int run_calls(const uint32_t *d_chr_locus_off, uint32_t n_chr, const uint64_t *d_locus_entry_off,
+              const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci, const uint16_t *d_clusters,
+              uint32_t n_groups, const uint8_t *d_locus_ref, const uint32_t *chr_locus_end, double hetero_prior,
+              double theta, uint32_t capacity, uint32_t *d_mismatch, uint32_t *d_loci, Calls *out, hipStream_t s) {
+    namespace V = secedo::variant;
+    const uint32_t ranges = V::num_ranges(n_loci);
+    const std::vector<double> thr = threshold_table(theta);
+    const size_t scan_bytes = V::scan_workspace(n_loci);
+    Buf b_thr, b_end, b_cnt, b_off, b_flag, b_err, b_scan, b_rec;
+    VC_TRY(b_thr.alloc(thr.size() * sizeof(double)));
+    VC_TRY(b_end.alloc((size_t)n_chr * 4));
+    VC_TRY(b_cnt.alloc(((size_t)ranges + 1) * 4));
+    VC_TRY(b_off.alloc(((size_t)ranges + 1) * 4));
+    VC_TRY(b_flag.alloc(n_loci));
+    VC_TRY(b_err.alloc(4));
+    VC_TRY(b_scan.alloc(scan_bytes));
+    VC_TRY(hipMemcpyAsync(b_thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_chr) VC_TRY(hipMemcpyAsync(b_end.p, chr_locus_end, (size_t)n_chr * 4, hipMemcpyHostToDevice, s));
+
+    V::CallsIn in{d_chr_locus_off, b_end.as<uint32_t>(), n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci,
+                  d_clusters, n_groups, d_locus_ref, b_thr.as<double>(), host_logs(hetero_prior, theta)};
+    hipEvent_t e0, e1, e2, e3;
+    VC_TRY(hipEventCreate(&e0));
+    VC_TRY(hipEventCreate(&e1));
+    VC_TRY(hipEventCreate(&e2));
+    VC_TRY(hipEventCreate(&e3));
+    struct Ev {
+        hipEvent_t *e[4];
+        ~Ev() { for (hipEvent_t *x : e) (void)hipEventDestroy(*x); }
+    } ev{{&e0, &e1, &e2, &e3}};
+    // the counted-entry counters: LDS-privatised or global atomics (env SECEDO_VARIANT_COUNTERS=lds|global; the
+    // default is the faster on the measured workloads, see DESIGN)
+    const char *mode = getenv("SECEDO_VARIANT_COUNTERS");
+    const bool lds = mode ? strcmp(mode, "global") != 0 : kLdsDefault;
+    int dev = 0, cus = 0;
+    VC_TRY(hipGetDevice(&dev));
+    VC_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const uint32_t max_blocks = static_cast<uint32_t>(std::max(cus, 1)) * (lds ? 2u : 8u);
+    VC_TRY(hipEventRecord(e0, s));
+    VC_TRY(V::count_calls(in, d_mismatch, d_loci, b_cnt.as<uint32_t>(), b_off.as<uint32_t>(), b_flag.as<uint8_t>(),
+                          b_err.as<uint32_t>(), b_scan.p, scan_bytes, lds, max_blocks, s));
+    VC_TRY(hipEventRecord(e1, s));
+    uint32_t head[2] = {0, 0};
+    VC_TRY(hipMemcpyAsync(&head[0], b_off.as<uint32_t>() + ranges, 4, hipMemcpyDeviceToHost, s));
+    VC_TRY(hipMemcpyAsync(&head[1], b_err.p, 4, hipMemcpyDeviceToHost, s));
+    VC_TRY(hipStreamSynchronize(s));
+    if (head[1]) return fail(SECEDO_E_INVALID_ARG, "a group id of the pileup is >= the length of clusters");
+    out->total = head[0];
+    float k1 = 0, k2 = 0;
+    VC_TRY(hipEventElapsedTime(&k1, e0, e1));
+    out->kernel_ms = k1;
+    if (out->total > capacity) return SECEDO_OK;
+    VC_TRY(b_rec.alloc((size_t)out->total * sizeof(secedo_variant_record)));
+    VC_TRY(hipEventRecord(e2, s));
+    VC_TRY(V::write_calls(in, b_off.as<uint32_t>(), b_flag.as<uint8_t>(), b_rec.as<secedo_variant_record>(), s));
+    VC_TRY(hipEventRecord(e3, s));
+    out->records.resize(out->total);
+    if (out->total)
+        VC_TRY(hipMemcpyAsync(out->records.data(), b_rec.p, (size_t)out->total * sizeof(secedo_variant_record),
+                              hipMemcpyDeviceToHost, s));
+    VC_TRY(hipStreamSynchronize(s));
+    VC_TRY(hipEventElapsedTime(&k2, e2, e3));
+    out->kernel_ms += k2;
+    return SECEDO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The files
+
+const char *const kInfoFormat = "\t.\t.\tVARIANT_OVERALL_TYPE=SNP\tGT\t";
+
+bool is_homozygous(uint32_t g) { return (g & 7) == (g >> 3); }
+
+void append_counts(std::string &o, const uint16_t c[4]) {
+    for (int j = 0; j < 4; ++j) {
+        o += std::to_string(c[j]);
+        o += ' ';
+    }
+    o += '\n';
+}
+
+void append_head(std::string &o, const std::string &chr, uint32_t pos, char ref, const std::string &alt) {
+    o += chr;
+    o += '\t';
+    o += std::to_string(pos);
+    o += "\t.\t";
+    o += ref;
+    o += '\t';
+    o += alt;
+    o += kInfoFormat;
+}
+
+// write_vcf_line (:288-321) for a record the device already found to be written; get_differing_bases (:247-279)
+void append_vcf_line(std::string &o, const std::string &chr, uint32_t pos, uint32_t ref, uint32_t g,
+                     const uint16_t c[4]) {
+    if (is_homozygous(ref)) {
+        std::string alt(1, kIntToChar[g & 7]);
+        const char *gt = "1/1";
+        if (!is_homozygous(g)) {
+            alt += kIntToChar[g >> 3];
+            gt = "0/1";
+        }
+        append_head(o, chr, pos, kIntToChar[ref & 7], alt);
+        o += gt;
+        o += '\t';
+        append_counts(o, c);
+        return;
+    }
+    char r1 = kIntToChar[ref & 7], r2 = kIntToChar[ref >> 3];
+    if (r1 > r2) std::swap(r1, r2);
+    char g1 = kIntToChar[g & 7], g2 = kIntToChar[g >> 3];
+    if (g1 > g2) std::swap(g1, g2);
+    std::pair<char, char> pairs[2];
+    int n = 0;
+    if (g1 == r1 && g2 == r2) n = 0;
+    else if (g1 == r1) pairs[n++] = {r2, g2};
+    else if (g2 == r2) pairs[n++] = {r1, g1};
+    else {
+        pairs[n++] = {r1, g1};
+        pairs[n++] = {r2, g2};
+    }
+    for (int k = 0; k < n; ++k) {
+        append_head(o, chr, pos, pairs[k].first, std::string(1, pairs[k].second));
+        o += "1/1\t";
+        append_counts(o, c);
+    }
+}
+
+int write_file(const std::filesystem::path &path, const std::string &text) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return fail(SECEDO_E_INVALID_ARG, "cannot write " + path.string());
+    const size_t w = text.empty() ? 0 : fwrite(text.data(), 1, text.size(), f);
+    const bool closed = fclose(f) == 0;
+    const bool ok = w == text.size() && closed;
+    return ok ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, "cannot write " + path.string());
+}
+
+// write_vcf_preamble (:226-241)
+std::string preamble(const std::string &reference, uint32_t cluster) {
+    std::time_t now = std::chrono::system_clock::to_time_t(std::chrono::system_clock::now());
+    std::string o = "##fileformat=VCFv4.2\n##fileDate=";
+    o += std::ctime(&now);
+    o += "##source=SVC (Somatic Variant Caller)\n##reference=" + reference + "\n##cluster=" +
+         std::to_string(cluster) + "\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tcluster-" +
+         std::to_string(cluster) + "\n";
+    return o;
+}
+
+int write_outputs(const std::filesystem::path &out_dir, const std::string &reference, uint32_t num_clusters,
+                  const std::vector<secedo_variant_record> &records, const uint32_t *chr_locus_off, uint32_t n_chr,
+                  const uint32_t *locus_pos, const uint8_t *locus_ref, const std::vector<uint32_t> &mismatch,
+                  const std::vector<uint32_t> &loci) {
+    std::vector<std::string> vcfs(num_clusters);
+    for (uint32_t i = 0; i < num_clusters; ++i) vcfs[i] = preamble(reference, i);
+    std::string common;
+    uint32_t chr = 0;
+    std::string chr_name = id_to_chromosome(0);
+    for (const secedo_variant_record &r : records) {
+        while (chr + 1 < n_chr && r.locus >= chr_locus_off[chr + 1]) chr_name = id_to_chromosome(++chr);
+        const uint32_t pos = locus_pos[r.locus], ref = locus_ref[r.locus];
+        if (r.kind == SECEDO_VARIANT_POOLED) {  // :395-406
+            const uint32_t new_base = r.genotype & 7;
+            const uint32_t ref_base = (ref & 7) == new_base ? (ref >> 3) & 7 : ref & 7;
+            append_head(common, chr_name, pos, kIntToChar[ref_base], std::string(1, kIntToChar[new_base]));
+            common += "1/1\t";
+            append_counts(common, r.counts);
+        } else if (r.kind == SECEDO_VARIANT_COMMON) {
+            append_vcf_line(common, chr_name, pos, ref, r.genotype, r.counts);
+        } else {
+            append_vcf_line(vcfs[r.cluster], chr_name, pos, ref, r.genotype, r.counts);
+        }
+    }
+    for (uint32_t i = 0; i < num_clusters; ++i)
+        VC_CALL(write_file(out_dir / ("cluster_" + std::to_string(i) + ".vcf"), vcfs[i]));
+    VC_CALL(write_file(out_dir / "common.vcf", common));
+    VC_CALL(write_file(out_dir / "variant", ""));
+    // write_vec(scores): default ostream formatting (%g, 6 digits); 0.0 / 0 prints as -nan on x86-64
+    std::string scores;
+    char buf[64];
+    for (size_t i = 0; i < loci.size(); ++i) {
+        if (i) scores += ',';
+        if (loci[i] == 0) {
+            scores += "-nan";
+        } else {
+            snprintf(buf, sizeof buf, "%g", static_cast<double>(mismatch[i]) / loci[i]);
+            scores += buf;
+        }
+    }
+    scores += '\n';
+    return write_file(out_dir / "scores", scores);
+}
+
+// variant_calling on a resident pileup with the host copies of its chromosome offsets and positions.
+int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_locus_off, uint32_t n_chr,
+            const uint32_t *locus_pos, const uint64_t *d_locus_entry_off, const uint16_t *d_id_base16,
+            const uint32_t *d_id_base32, uint32_t n_loci, const uint16_t *clusters, uint32_t n,
+            const char *reference_genome, const char *map_file, double hetero_prior, double theta,
+            const char *out_dir, secedo_variant_times *times, hipStream_t s, double pre_device_ms) {
+    secedo_variant_times t{};
+    Clock::time_point t0 = Clock::now();
+    std::vector<uint8_t> locus_ref(n_loci);
+    std::vector<uint32_t> chr_end(n_chr);
+    VC_CALL(reference_genotypes(reference_genome, map_file, chr_locus_off, n_chr, locus_pos, locus_ref.data(),
+                                chr_end.data(), &t.fasta_ms));
+    t.gather_ms = ms_since(t0) - t.fasta_ms;
+    const uint32_t num_clusters = static_cast<uint32_t>(*std::max_element(clusters, clusters + n)) + 1;
+
+    Buf b_ref, b_cl, b_mm, b_loci;
+    VC_TRY(b_ref.alloc(n_loci));
+    VC_TRY(b_cl.alloc((size_t)n * 2));
+    VC_TRY(b_mm.alloc((size_t)n * 4));
+    VC_TRY(b_loci.alloc((size_t)n * 4));
+    if (n_loci) VC_TRY(hipMemcpyAsync(b_ref.p, locus_ref.data(), n_loci, hipMemcpyHostToDevice, s));
+    VC_TRY(hipMemcpyAsync(b_cl.p, clusters, (size_t)n * 2, hipMemcpyHostToDevice, s));
+    Calls calls;
+    VC_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, b_cl.as<uint16_t>(),
+                      n, b_ref.as<uint8_t>(), chr_end.data(), hetero_prior, theta, UINT32_MAX, b_mm.as<uint32_t>(),
+                      b_loci.as<uint32_t>(), &calls, s));
+    std::vector<uint32_t> mismatch(n), loci(n);
+    VC_TRY(hipMemcpyAsync(mismatch.data(), b_mm.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    VC_TRY(hipMemcpyAsync(loci.data(), b_loci.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    VC_TRY(hipStreamSynchronize(s));
+    t.device_ms = ms_since(t0) + pre_device_ms;
+    t.kernel_ms = calls.kernel_ms;
+    VC_CALL(write_outputs(out_dir, reference_genome, num_clusters, calls.records, chr_locus_off, n_chr, locus_pos,
+                          locus_ref.data(), mismatch, loci));
+    t.write_ms = ms_since(t0);
+    if (times) *times = t;
+    return SECEDO_OK;
+}
+
+// The steps before the reference's locus loop (:330-337): nothing for no cells; out_dir is created before the
+// reference genome is checked.
+int begin_calling(uint32_t n, const char *reference_genome, const char *out_dir, bool *done) {
+    *done = n == 0;
+    if (*done) return SECEDO_OK;
+    if (!out_dir || !reference_genome) return fail(SECEDO_E_INVALID_ARG, "null path");
+    std::error_code ec;
+    std::filesystem::create_directories(out_dir, ec);
+    if (ec) return fail(SECEDO_E_INVALID_ARG, std::string("cannot create ") + out_dir + ": " + ec.message());
+    if (!std::filesystem::exists(reference_genome))
+        return fail(SECEDO_E_INVALID_ARG, std::string("Reference genome ") + reference_genome + " does not exist");
+    return SECEDO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *secedo_variant_last_error(void) { return g_error.c_str(); }
+
+int secedo_variant_reference_genotypes(const char *fasta, const char *map_file, const uint32_t *chr_locus_off,
+                                       uint32_t n_chr, const uint32_t *locus_pos, uint32_t n_loci,
+                                       uint8_t *locus_ref, uint32_t *chr_locus_end, double *fasta_ms) {
+    if (!chr_locus_off || (n_chr && !chr_locus_end) || (n_loci && (!locus_pos || !locus_ref)))
+        return fail(SECEDO_E_INVALID_ARG, "null argument");
+    if (chr_locus_off[0] != 0 || chr_locus_off[n_chr] != n_loci)
+        return fail(SECEDO_E_INVALID_ARG, "chr_locus_off must run from 0 to n_loci");
+    return reference_genotypes(fasta, map_file, chr_locus_off, n_chr, locus_pos, locus_ref, chr_locus_end, fasta_ms);
+}
+
+int secedo_variant_is_diploid(const char *fasta) {
+    Fasta f;
+    VC_CALL(open_fasta(fasta, &f));
+    return check_is_diploid(f) ? 1 : 0;
+}
+
+int secedo_variant_read_chromosome(const char *fasta, const char *map_file, uint32_t index, uint8_t *out,
+                                   uint64_t capacity, uint64_t *length) {
+    Fasta f;
+    VC_CALL(open_fasta(fasta, &f));
+    std::vector<MapEntry> entries;
+    VC_CALL(read_map(map_file, &entries));
+    const Map map = group_map(entries);
+    const bool diploid = check_is_diploid(f);
+    std::vector<uint8_t> chr, tmp1, tmp2;
+    for (uint32_t c = 0; c <= index; ++c) VC_CALL(get_next_chromosome(f, map, diploid, &chr, &tmp1, &tmp2));
+    *length = chr.size();
+    if (chr.size() > capacity) return fail(SECEDO_E_LIMIT, "contig longer than capacity");
+    if (!chr.empty()) memcpy(out, chr.data(), chr.size());
+    return SECEDO_OK;
+}
+
+int secedo_variant_read_map(const char *map_file, char *names, uint32_t name_len, uint32_t *start_pos,
+                            uint32_t *len, char *tr, uint8_t *chromosome_id, uint32_t capacity,
+                            uint32_t *n_entries) {
+    std::vector<MapEntry> entries;
+    VC_CALL(read_map(map_file, &entries));
+    *n_entries = static_cast<uint32_t>(entries.size());
+    if (entries.size() > capacity) return fail(SECEDO_E_LIMIT, "more map entries than capacity");
+    for (size_t i = 0; i < entries.size(); ++i) {
+        if (name_len) {
+            const size_t k = std::min<size_t>(entries[i].name.size(), name_len - 1);
+            memcpy(names + i * name_len, entries[i].name.data(), k);
+            names[i * name_len + k] = '\0';
+        }
+        start_pos[i] = entries[i].m.start_pos;
+        len[i] = entries[i].m.len;
+        tr[i] = entries[i].m.tr;
+        chromosome_id[i] = entries[i].m.chromosome_id;
+    }
+    return SECEDO_OK;
+}
+
+int secedo_variant_apply_map(const uint32_t *start_pos, const uint32_t *len, const char *tr, uint32_t n_map,
+                             const uint8_t *chr_data, uint64_t n, uint8_t *out, uint64_t capacity,
+                             uint64_t *out_len) {
+    std::vector<ChrMap> map(n_map);
+    for (uint32_t i = 0; i < n_map; ++i) map[i] = ChrMap{start_pos[i], len[i], tr[i], 0};
+    std::vector<uint8_t> in(chr_data, chr_data + n), res;
+    VC_CALL(apply_map(map, in, &res));
+    *out_len = res.size();
+    if (res.size() > capacity) return fail(SECEDO_E_LIMIT, "result longer than capacity");
+    if (!res.empty()) memcpy(out, res.data(), res.size());
+    return SECEDO_OK;
+}
+
+int secedo_variant_calls_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                                const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+                                const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci,
+                                uint64_t n_entries, const uint16_t *d_clusters, uint32_t n_clusters_entries,
+                                const uint8_t *d_locus_ref, const uint32_t *chr_locus_end, double hetero_prior,
+                                double theta, secedo_variant_record *records, uint32_t capacity,
+                                uint32_t *n_records, uint32_t *d_mismatch, uint32_t *d_loci, double *kernel_ms,
+                                void *stream) {
+    (void)d_locus_pos;
+    (void)n_entries;
+    VC_CALL(set_device(device_id));
+    if (!n_records || (!!d_id_base16 == !!d_id_base32) || (capacity && !records))
+        return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
+    Calls calls;
+    VC_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, d_clusters,
+                      n_clusters_entries, d_locus_ref, chr_locus_end, hetero_prior, theta, capacity, d_mismatch,
+                      d_loci, &calls, static_cast<hipStream_t>(stream)));
+    *n_records = calls.total;
+    if (kernel_ms) *kernel_ms = calls.kernel_ms;
+    if (calls.total > capacity)
+        return fail(SECEDO_E_LIMIT, std::to_string(calls.total) + " records, capacity " + std::to_string(capacity));
+    if (calls.total) memcpy(records, calls.records.data(), calls.records.size() * sizeof(secedo_variant_record));
+    return SECEDO_OK;
+}
+
+int secedo_variant_genotypes_device(int device_id, const uint16_t *counts, uint32_t n,
+                                    int likely_homozygous_total, double hetero_prior, double theta,
+                                    uint8_t *homozygous, uint8_t *genotype) {
+    VC_CALL(set_device(device_id));
+    if (n == 0) return SECEDO_OK;
+    const std::vector<double> thr = threshold_table(theta);
+    Buf b_c, b_t, b_h, b_g;
+    VC_TRY(b_c.alloc((size_t)n * 8));
+    VC_TRY(b_t.alloc(thr.size() * sizeof(double)));
+    VC_TRY(b_h.alloc(n));
+    VC_TRY(b_g.alloc(n));
+    VC_TRY(hipMemcpy(b_c.p, counts, (size_t)n * 8, hipMemcpyHostToDevice));
+    VC_TRY(hipMemcpy(b_t.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice));
+    VC_TRY(secedo::variant::genotypes(b_c.as<uint16_t>(), n, likely_homozygous_total, b_t.as<double>(),
+                                      host_logs(hetero_prior, theta), b_h.as<uint8_t>(), b_g.as<uint8_t>(), 0));
+    VC_TRY(hipMemcpy(homozygous, b_h.p, n, hipMemcpyDeviceToHost));
+    VC_TRY(hipMemcpy(genotype, b_g.p, n, hipMemcpyDeviceToHost));
+    return SECEDO_OK;
+}
+
+int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
+                           const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint16_t *id_base16,
+                           const uint32_t *id_base32, const uint16_t *clusters, uint32_t n,
+                           const char *reference_genome, const char *map_file, double hetero_prior, double theta,
+                           const char *out_dir, secedo_variant_times *times) {
+    bool done;
+    VC_CALL(begin_calling(n, reference_genome, out_dir, &done));
+    if (done) return SECEDO_OK;
+    if (!chr_locus_off || !clusters || (!!id_base16 == !!id_base32 && chr_locus_off[n_chr] > 0))
+        return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
+    VC_CALL(set_device(device_id));
+    Clock::time_point t0 = Clock::now();
+    const uint32_t n_loci = chr_locus_off[n_chr];
+    const uint64_t n_entries = locus_entry_off[n_loci];
+    const size_t idb_bytes = (size_t)n_entries * (id_base16 ? 2 : 4);
+    hipStream_t s;
+    VC_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    struct StreamGuard {
+        hipStream_t s;
+        ~StreamGuard() { (void)hipStreamDestroy(s); }
+    } guard{s};
+    Buf b_chr, b_off, b_idb;
+    VC_TRY(b_chr.alloc(((size_t)n_chr + 1) * 4));
+    VC_TRY(b_off.alloc(((size_t)n_loci + 1) * 8));
+    VC_TRY(b_idb.alloc(idb_bytes));
+    VC_TRY(hipMemcpyAsync(b_chr.p, chr_locus_off, ((size_t)n_chr + 1) * 4, hipMemcpyHostToDevice, s));
+    VC_TRY(hipMemcpyAsync(b_off.p, locus_entry_off, ((size_t)n_loci + 1) * 8, hipMemcpyHostToDevice, s));
+    if (idb_bytes)
+        VC_TRY(hipMemcpyAsync(b_idb.p, id_base16 ? (const void *)id_base16 : (const void *)id_base32, idb_bytes,
+                              hipMemcpyHostToDevice, s));
+    const double upload_ms = ms_since(t0);
+    return calling(device_id, b_chr.as<uint32_t>(), chr_locus_off, n_chr, locus_pos, b_off.as<uint64_t>(),
+                   id_base16 ? b_idb.as<uint16_t>() : nullptr, id_base16 ? nullptr : b_idb.as<uint32_t>(), n_loci,
+                   clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times, s, upload_ms);
+}
+
+int secedo_variant_calling_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                                  const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+                                  const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci,
+                                  uint64_t n_entries, const uint16_t *clusters, uint32_t n,
+                                  const char *reference_genome, const char *map_file, double hetero_prior,
+                                  double theta, const char *out_dir, secedo_variant_times *times, void *stream) {
+    (void)n_entries;
+    bool done;
+    VC_CALL(begin_calling(n, reference_genome, out_dir, &done));
+    if (done) return SECEDO_OK;
+    if (!clusters || (!!d_id_base16 == !!d_id_base32 && n_loci > 0))
+        return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
+    VC_CALL(set_device(device_id));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Clock::time_point t0 = Clock::now();
+    std::vector<uint32_t> chr_off((size_t)n_chr + 1), pos(n_loci);
+    VC_TRY(hipMemcpyAsync(chr_off.data(), d_chr_locus_off, ((size_t)n_chr + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (n_loci) VC_TRY(hipMemcpyAsync(pos.data(), d_locus_pos, (size_t)n_loci * 4, hipMemcpyDeviceToHost, s));
+    VC_TRY(hipStreamSynchronize(s));
+    if (chr_off[0] != 0 || chr_off[n_chr] != n_loci)
+        return fail(SECEDO_E_INVALID_ARG, "chr_locus_off must run from 0 to n_loci");
+    const double download_ms = ms_since(t0);
+    return calling(device_id, d_chr_locus_off, chr_off.data(), n_chr, pos.data(), d_locus_entry_off, d_id_base16,
+                   d_id_base32, n_loci, clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times,
+                   s, download_ms);
+}
+
+}  // extern "C"

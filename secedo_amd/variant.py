@@ -1,0 +1,264 @@
+"""Variant calling after the clustering (include/secedo_variant.h, libsecedo_variant.so).
+
+Host-side mirror of the reference's ``variant_calling(pos_data, clusters, reference_genome, map_file,
+hetero_prior, theta, out_dir)`` (variant_calling.cpp:323-461): the per-locus genotype calls and the per-cell
+counters run on the GPU (secedo_amd/csrc/variant_kernels.hip); the FASTA / map reading and the VCF text are
+host code in the library. ``reference_genotypes`` and the FASTA / map helpers need no GPU. No CPU fallback for
+the calls.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from .pileup import FlatPileup, flatten
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libsecedo_variant.so")
+
+NO_GENOTYPE = 255
+KINDS = ("pooled", "common", "cluster")
+
+_vp = C.c_void_p
+_u32p = C.POINTER(C.c_uint32)
+_u64p = C.POINTER(C.c_uint64)
+_f64p = C.POINTER(C.c_double)
+
+
+class Record(C.Structure):
+    _fields_ = [("locus", C.c_uint32), ("cluster", C.c_uint16), ("genotype", C.c_uint8), ("kind", C.c_uint8),
+                ("counts", C.c_uint16 * 4)]
+
+
+class Times(C.Structure):
+    _fields_ = [("fasta_ms", C.c_double), ("gather_ms", C.c_double), ("device_ms", C.c_double),
+                ("write_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
+RECORD_DTYPE = np.dtype([("locus", np.uint32), ("cluster", np.uint16), ("genotype", np.uint8), ("kind", np.uint8),
+                         ("counts", np.uint16, (4,))])
+
+SIGNATURES = {
+    "secedo_variant_last_error": (C.c_char_p, []),
+    "secedo_variant_reference_genotypes": (C.c_int, [C.c_char_p, C.c_char_p, _vp, C.c_uint32, _vp, C.c_uint32, _vp,
+                                                     _vp, _f64p]),
+    "secedo_variant_is_diploid": (C.c_int, [C.c_char_p]),
+    "secedo_variant_read_chromosome": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
+    "secedo_variant_read_map": (C.c_int, [C.c_char_p, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _u32p]),
+    "secedo_variant_apply_map": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _u64p]),
+    "secedo_variant_calls_device": (C.c_int, [C.c_int, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64,
+                                              _vp, C.c_uint32, _vp, _vp, C.c_double, C.c_double, _vp, C.c_uint32,
+                                              _u32p, _vp, _vp, _f64p, _vp]),
+    "secedo_variant_genotypes_device": (C.c_int, [C.c_int, _vp, C.c_uint32, C.c_int, C.c_double, C.c_double, _vp,
+                                                  _vp]),
+    "secedo_variant_calling": (C.c_int, [C.c_int, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_char_p,
+                                         C.c_char_p, C.c_double, C.c_double, C.c_char_p, C.POINTER(Times)]),
+    "secedo_variant_calling_device": (C.c_int, [C.c_int, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32,
+                                                C.c_uint64, _vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_double,
+                                                C.c_double, C.c_char_p, C.POINTER(Times), _vp]),
+}
+
+_vl = None
+
+
+def lib():
+    global _vl
+    if _vl is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError("%s is missing: build it with `make -C secedo_amd/csrc` (there is no fallback "
+                              "implementation)" % LIB_PATH)
+        try:
+            import torch  # noqa: F401  -- one HIP runtime per process: torch's, as in _lib.py
+        except ImportError:
+            pass
+        l = C.CDLL(LIB_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            f = getattr(l, name)
+            f.restype = res
+            f.argtypes = args
+        _vl = l
+    return _vl
+
+
+def check(rc):
+    if rc == _lib.OK:
+        return
+    raise _lib.SecedoError(rc, lib().secedo_variant_last_error().decode(errors="replace"))
+
+
+def _b(s):
+    return None if s is None else os.fsencode(str(s))
+
+
+def _flat(pos_data):
+    p = pos_data if isinstance(pos_data, FlatPileup) else flatten(pos_data)
+    idb = np.ascontiguousarray(p.id_base)
+    if p.n_entries == 0 or int(idb.max()) <= 0xFFFF:
+        return p, np.ascontiguousarray(idb, dtype=np.uint16), None
+    return p, None, np.ascontiguousarray(idb, dtype=np.uint32)
+
+
+def reference_genotypes(reference_genome, chr_locus_off, locus_pos, map_file=""):
+    """The reference genotype of every locus (maternal << 3 | paternal, N = 5) and each chromosome's end (the
+    first locus with position - 1 >= its contig's length). No GPU. -> (locus_ref u8[L], chr_locus_end u32[C])."""
+    off = np.ascontiguousarray(chr_locus_off, dtype=np.uint32)
+    pos = np.ascontiguousarray(locus_pos, dtype=np.uint32)
+    ref = np.zeros(max(len(pos), 1), dtype=np.uint8)
+    end = np.zeros(max(len(off) - 1, 1), dtype=np.uint32)
+    check(lib().secedo_variant_reference_genotypes(_b(reference_genome), _b(map_file), _lib.ptr(off), len(off) - 1,
+                                                   _lib.ptr(pos), len(pos), _lib.ptr(ref), _lib.ptr(end), None))
+    return ref[:len(pos)], end[:len(off) - 1]
+
+
+def is_diploid(fasta) -> bool:
+    rc = lib().secedo_variant_is_diploid(_b(fasta))
+    if rc < 0:
+        check(rc)
+    return bool(rc)
+
+
+def read_chromosome(fasta, index, map_file=""):
+    """What get_next_chromosome leaves in chr_data after its (index + 1)-th call -> u8 genotype codes."""
+    n = C.c_uint64(0)
+    rc = lib().secedo_variant_read_chromosome(_b(fasta), _b(map_file), index, None, 0, C.byref(n))
+    if rc not in (_lib.OK, _lib.E_LIMIT):
+        check(rc)
+    out = np.zeros(max(n.value, 1), dtype=np.uint8)
+    check(lib().secedo_variant_read_chromosome(_b(fasta), _b(map_file), index, _lib.ptr(out), len(out), C.byref(n)))
+    return out[:n.value]
+
+
+def read_map(map_file):
+    """read_map -> {contig name: [(start_pos, len, tr, chromosome_id), ...]} in file order."""
+    n = C.c_uint32(0)
+    rc = lib().secedo_variant_read_map(_b(map_file), None, 0, None, None, None, None, 0, C.byref(n))
+    if rc not in (_lib.OK, _lib.E_LIMIT):
+        check(rc)
+    k, width = max(n.value, 1), 256
+    names = C.create_string_buffer(k * width)
+    start, length = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+    tr, chrom = C.create_string_buffer(k), np.zeros(k, np.uint8)
+    check(lib().secedo_variant_read_map(_b(map_file), names, width, _lib.ptr(start), _lib.ptr(length), tr,
+                                        _lib.ptr(chrom), k, C.byref(n)))
+    out = {}
+    for i in range(n.value):
+        name = names.raw[i * width:(i + 1) * width].split(b"\0", 1)[0].decode()
+        out.setdefault(name, []).append((int(start[i]), int(length[i]), tr.raw[i:i + 1].decode(), int(chrom[i])))
+    return out
+
+
+def apply_map(map_entries, chr_data):
+    """apply_map on one contig: map_entries = [(start_pos, len, tr), ...] -> u8 array."""
+    m = list(map_entries)
+    start = np.asarray([e[0] for e in m] or [0], dtype=np.uint32)
+    length = np.asarray([e[1] for e in m] or [0], dtype=np.uint32)
+    tr = C.create_string_buffer("".join(e[2] for e in m).encode() or b"\0")
+    data = np.ascontiguousarray(chr_data, dtype=np.uint8)
+    n = C.c_uint64(0)
+    cap = int(len(data) + sum(e[1] for e in m if e[2] == "D")) + 1
+    out = np.zeros(cap, dtype=np.uint8)
+    check(lib().secedo_variant_apply_map(_lib.ptr(start), _lib.ptr(length), tr, len(m), _lib.ptr(data), len(data),
+                                         _lib.ptr(out), cap, C.byref(n)))
+    return out[:n.value]
+
+
+def genotypes_device(counts, likely_homozygous_total, hetero_prior, theta, device=0):
+    """likely_homozygous(counts[i], theta) and most_likely_genotype(counts[i], ..., likely_homozygous_total,
+    hetero_prior, theta) as the kernel evaluates them; counts: (n, 4) -> (homozygous u8[n], genotype u8[n])."""
+    c = np.ascontiguousarray(counts, dtype=np.uint16).reshape(-1, 4)
+    n = c.shape[0]
+    h, g = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+    check(lib().secedo_variant_genotypes_device(device, _lib.ptr(c), n, int(bool(likely_homozygous_total)),
+                                                hetero_prior, theta, _lib.ptr(h), _lib.ptr(g)))
+    return h[:n], g[:n]
+
+
+def _dev(a, t, dev):
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.size == 0:
+        a = np.zeros(1, dtype=a.dtype)
+    return torch.from_numpy(a.view(t)).to(dev)
+
+
+def _stream(device):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def variant_calls(pos_data, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01, capacity=None,
+                  device=0, with_kernel_ms=False):
+    """The device calls alone -> (records as a RECORD_DTYPE array in write order, mismatch u32[n], loci u32[n]).
+    `capacity` (default: enough) bounds the records; SecedoError(E_LIMIT) when more are needed, its
+    `required` attribute the count."""
+    import torch
+    p, b16, b32 = _flat(pos_data)
+    cl = np.ascontiguousarray(clusters, dtype=np.uint16)
+    ref, end = reference_genotypes(reference_genome, p.chr_locus_off, p.locus_pos, map_file)
+    dev = "cuda:%d" % device
+    d_chr = _dev(p.chr_locus_off, np.int32, dev)
+    d_pos = _dev(p.locus_pos, np.int32, dev)
+    d_off = _dev(p.locus_entry_off, np.int64, dev)
+    d_idb = _dev(b16, np.int16, dev) if b16 is not None else _dev(b32, np.int32, dev)
+    d_cl = _dev(cl, np.int16, dev)
+    d_ref = _dev(ref, np.uint8, dev)
+    n = len(cl)
+    d_mm = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    d_loci = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    cap = int(p.n_entries) * 2 + p.n_loci + 16 if capacity is None else int(capacity)
+    recs = (Record * max(cap, 1))()
+    n_rec, kms = C.c_uint32(0), C.c_double(0)
+    idb = C.c_void_p(d_idb.data_ptr())
+    rc = lib().secedo_variant_calls_device(
+        device, C.c_void_p(d_chr.data_ptr()), p.n_chr, C.c_void_p(d_pos.data_ptr()), C.c_void_p(d_off.data_ptr()),
+        idb if b16 is not None else None, None if b16 is not None else idb, p.n_loci, p.n_entries,
+        C.c_void_p(d_cl.data_ptr()), n, C.c_void_p(d_ref.data_ptr()), _lib.ptr(end), hetero_prior, theta, recs, cap,
+        C.byref(n_rec), C.c_void_p(d_mm.data_ptr()), C.c_void_p(d_loci.data_ptr()), C.byref(kms), _stream(device))
+    if rc == _lib.E_LIMIT:
+        err = _lib.SecedoError(rc, lib().secedo_variant_last_error().decode(errors="replace"))
+        err.required = int(n_rec.value)
+        raise err
+    check(rc)
+    out = np.frombuffer(recs, dtype=RECORD_DTYPE, count=n_rec.value).copy()
+    mm = d_mm.cpu().numpy().view(np.uint32)[:n].copy()
+    lo = d_loci.cpu().numpy().view(np.uint32)[:n].copy()
+    if with_kernel_ms:
+        return out, mm, lo, kms.value
+    return out, mm, lo
+
+
+def _times(t):
+    return dict(fasta_ms=t.fasta_ms, gather_ms=t.gather_ms, device_ms=t.device_ms, write_ms=t.write_ms,
+                kernel_ms=t.kernel_ms)
+
+
+def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
+                    out_dir="variant_calling", device=0):
+    """variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir): writes
+    cluster_<i>.vcf, common.vcf, variant and scores under out_dir as the reference does. -> step times (ms)."""
+    p, b16, b32 = _flat(pos_data)
+    cl = np.ascontiguousarray(clusters, dtype=np.uint16)
+    t = Times()
+    check(lib().secedo_variant_calling(device, _lib.ptr(p.chr_locus_off), p.n_chr, _lib.ptr(p.locus_pos),
+                                       _lib.ptr(p.locus_entry_off), _lib.ptr(b16), _lib.ptr(b32), _lib.ptr(cl),
+                                       len(cl), _b(reference_genome), _b(map_file), hetero_prior, theta, _b(out_dir),
+                                       C.byref(t)))
+    return _times(t)
+
+
+def variant_calling_resident(plan, res, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
+                             out_dir="variant_calling"):
+    """variant_calling on the pileup `res` resident in HBM (SimilarityMatrixPlan.upload, as divide_cluster_resident
+    takes it), in the plan's current stream. -> step times (ms)."""
+    cl = np.ascontiguousarray(clusters, dtype=np.uint16)
+    idb = C.c_void_p(res["idb"].data_ptr())
+    t = Times()
+    check(lib().secedo_variant_calling_device(
+        plan.device, C.c_void_p(res["chr"].data_ptr()), res["n_chr"], C.c_void_p(res["pos"].data_ptr()),
+        C.c_void_p(res["off"].data_ptr()), idb if res["idb_is16"] else None, None if res["idb_is16"] else idb,
+        res["n_loci"], res["n_entries"], _lib.ptr(cl), len(cl), _b(reference_genome), _b(map_file), hetero_prior,
+        theta, _b(out_dir), C.byref(t), plan._stream()))
+    return _times(t)

@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""bench_variant_calling.py -- the variant calling (include/secedo_variant.h) on the GPU, one JSON line per
+workload:
+
+    C3      the C3 pileup of synth_pileup (8000 cells, 100K loci, 22 chromosomes) with positions renumbered 1, 4,
+            7, ... per chromosome so that the FASTA stays small, clusters of a ((A1, A2), B) clone tree
+            (labels 2, 3, 4 as divide_cluster numbers them, 1 % of the cells unassigned = 0)
+    whole   a whole-pileup-sized synthetic: 24 chromosomes, 10 M loci, coverage 30 (300 M entries), one locus
+            every 100 bp (a 1 Gbp diploid FASTA, 60 bases per line), the same clone-tree clusters, 2 % of the
+            loci with a planted clone-specific variant
+
+Each line: the two kernels (device events), the end-to-end call split into FASTA parse / gather / device (uploads,
+kernels, downloads) / write, and the achieved bytes/s of the kernels against the HBM peak (8 TB/s spec, 6.3
+TB/s measured with a float4 copy). The bytes counted are the compulsory ones: id_base, the entry offsets, one cluster
+id and one counter update per entry, the reference genotype and flag per locus. Every workload runs once
+untimed first. Run every step under a time limit (timeout -k 10 ...)."""
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from secedo_amd import variant  # noqa: E402
+from secedo_amd.pileup import FlatPileup  # noqa: E402
+
+HBM_PEAK = 8.0e12
+HBM_MEASURED = 6.29e12
+
+
+def clone_clusters(n, seed=1):
+    rng = np.random.default_rng(seed)
+    cl = np.where(np.arange(n) < 0.6 * n, 2, np.where(np.arange(n) < 0.8 * n, 3, 4)).astype(np.uint16)
+    cl[rng.random(n) < 0.01] = 0
+    return cl
+
+
+def write_fasta(path, lengths, seed):
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    with open(path, "wb") as f:
+        for c, n in enumerate(lengths):
+            name = str(c + 1) if c < 22 else ("X" if c == 22 else "Y")
+            mat = acgt[rng.integers(0, 4, n)]
+            pat = mat.copy()
+            flip = rng.random(n) < 0.001
+            pat[flip] = acgt[rng.integers(0, 4, int(flip.sum()))]
+            for tag, seq in (("maternal", mat), ("paternal", pat)):
+                f.write((">%s_%s\n" % (name, tag)).encode())
+                full = n // 60
+                rows = np.concatenate([seq[:full * 60].reshape(full, 60), np.full((full, 1), 10, np.uint8)], axis=1)
+                body = np.concatenate([rows.reshape(-1), seq[full * 60:], np.full(1 if n % 60 else 0, 10, np.uint8)])
+                f.write(body.tobytes())
+
+
+def compulsory_bytes(p, n_groups, idb_bytes):
+    e, l = p.n_entries, p.n_loci
+    return e * (idb_bytes + 2 + 4) + (l + 1) * 8 + 2 * l + 2 * n_groups * 4
+
+
+def run(name, p, clusters, fasta, reps=3):
+    out = tempfile.mkdtemp(prefix="vc_bench_")
+    try:
+        variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out)  # warm-up
+        runs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            t = variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out)
+            t["total_ms"] = (time.perf_counter() - t0) * 1e3
+            runs.append(t)
+        med = {k: round(float(np.median([r[k] for r in runs])), 3) for k in runs[0]}
+        n_lines = sum(1 for f in os.listdir(out) if f.endswith(".vcf")
+                      for line in open(os.path.join(out, f)) if line[0] != "#")
+        recs, _, _, kms = variant.variant_calls(p, clusters, fasta, with_kernel_ms=True)
+        modes = {}
+        for mode in ("lds", "global"):  # the counted-entry counters: LDS-privatised vs global atomics
+            os.environ["SECEDO_VARIANT_COUNTERS"] = mode
+            variant.variant_calls(p, clusters, fasta)
+            modes[mode] = round(float(np.median([variant.variant_calls(p, clusters, fasta, with_kernel_ms=True)[3]
+                                                 for _ in range(reps)])), 3)
+        del os.environ["SECEDO_VARIANT_COUNTERS"]
+    finally:
+        shutil.rmtree(out, ignore_errors=True)
+    idb_bytes = 2 if p.n_entries == 0 or int(p.id_base.max()) <= 0xFFFF else 4
+    by = compulsory_bytes(p, len(clusters), idb_bytes)
+    print(json.dumps(dict(workload=name, cells=len(clusters), loci=p.n_loci, entries=p.n_entries,
+                          chromosomes=p.n_chr, fasta_bytes=os.path.getsize(fasta), records=len(recs),
+                          vcf_lines=n_lines, **med, kernel_ms_calls=round(kms, 3),
+                          kernel_ms_lds_counters=modes["lds"], kernel_ms_global_counters=modes["global"], compulsory_bytes=by,
+                          achieved_bytes_per_s=by / (med["kernel_ms"] * 1e-3),
+                          fraction_of_hbm_peak=by / (med["kernel_ms"] * 1e-3) / HBM_PEAK,
+                          fraction_of_hbm_measured=by / (med["kernel_ms"] * 1e-3) / HBM_MEASURED)), flush=True)
+
+
+def c3(tmp):
+    from secedo_amd.synth import synth_config
+    p0 = synth_config("C3")
+    pos = np.zeros(p0.n_loci, dtype=np.uint32)
+    lengths = []
+    for c in range(p0.n_chr):
+        b, e = int(p0.chr_locus_off[c]), int(p0.chr_locus_off[c + 1])
+        pos[b:e] = 1 + 3 * np.arange(e - b, dtype=np.uint32)
+        lengths.append(3 * (e - b) + 10)
+    p = FlatPileup(p0.chr_locus_off, pos, p0.locus_entry_off, p0.read_ids, p0.id_base)
+    fasta = os.path.join(tmp, "c3.fa")
+    write_fasta(fasta, lengths, 3)
+    n_cells = int(p.id_base.max() >> 2) + 1
+    run("C3", p, clone_clusters(max(n_cells, 8000)), fasta)
+
+
+def whole(tmp, n_loci=10_000_000, n_chr=24, cov=30, n_cells=8000, spacing=100):
+    rng = np.random.default_rng(7)
+    per = n_loci // n_chr
+    n_loci = per * n_chr
+    chr_off = (np.arange(n_chr + 1) * per).astype(np.uint32)
+    pos = np.tile(1 + spacing * np.arange(per, dtype=np.uint32), n_chr)
+    lengths = [spacing * per + 10] * n_chr
+    fasta = os.path.join(tmp, "whole.fa")
+    write_fasta(fasta, lengths, 5)
+    cl = clone_clusters(n_cells)
+    counts = rng.poisson(cov, n_loci).astype(np.uint64)
+    off = np.zeros(n_loci + 1, dtype=np.uint64)
+    np.cumsum(counts, out=off[1:])
+    e = int(off[-1])
+    cells = rng.integers(0, n_cells, e, dtype=np.uint32)
+    bases = rng.integers(0, 4, n_loci, dtype=np.uint32)  # the locus' base (not the FASTA's: many calls)
+    locus_of = np.repeat(np.arange(n_loci, dtype=np.uint32), counts.astype(np.int64))
+    b = bases[locus_of]
+    planted = rng.random(n_loci) < 0.02
+    clone_b = (cl[cells] == 2) & planted[locus_of]
+    b = np.where(clone_b, (b + 1) & 3, b)
+    err = rng.random(e, dtype=np.float32) < 0.01
+    b = np.where(err, rng.integers(0, 4, e, dtype=np.uint32), b)
+    idb = (cells << 2) | b.astype(np.uint32)
+    del locus_of, b, err, clone_b
+    p = FlatPileup(chr_off, pos, off, np.arange(e, dtype=np.uint32), idb)
+    run("whole", p, cl, fasta, reps=2)
+
+
+def main(which):
+    tmp = tempfile.mkdtemp(prefix="vc_bench_data_")
+    try:
+        if "C3" in which:
+            c3(tmp)
+        if "whole" in which:
+            whole(tmp)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:] or ["C3", "whole"])
