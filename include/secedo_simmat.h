@@ -247,12 +247,22 @@ int secedo_simmat_last_counts(secedo_simmat_t *handle, uint64_t *updates, uint64
  * on the stream it ran on. Synchronises on the end event. */
 int secedo_simmat_last_accumulate_ms(secedo_simmat_t *handle, float *ms);
 /* ... and of its dominant kernel by itself when the sparse-loci kernels ran (accumulate_counts, from the start
- * of the accumulate to the launch that follows it); SECEDO_E_STATE otherwise. */
+ * of the accumulate to the launch that follows it; it includes the correction of the tiles when that ran as its
+ * epilogue, secedo_simmat_last_correction_fused); SECEDO_E_STATE otherwise. */
 int secedo_simmat_last_pair_kernel_ms(secedo_simmat_t *handle, float *ms);
-/* Which pair kernel the prepared pileup runs: "accumulate_counts" (sparse loci: count tile, followed by
- * correct_tiles), "accumulate_masks" (clustered loci: window masks staged, followed by wide_pairs when reads reach
+/* Which pair kernel the prepared pileup runs: "accumulate_counts" (sparse loci: count tile, corrected in its own
+ * epilogue or by correct_tiles after it), "accumulate_masks" (clustered loci: window masks staged, followed by wide_pairs when reads reach
  * beyond their windows) or "accumulate_tiles" (deep pileups, and the A/B switches). Static string. */
 const char *secedo_simmat_pair_kernel(const secedo_simmat_t *handle);
+/* 1 when the last accumulate() corrected its tiles in the epilogue of accumulate_counts (one workgroup per tile),
+ * 0 when correct_tiles ran after it or another pair kernel ran. */
+int secedo_simmat_last_correction_fused(const secedo_simmat_t *handle);
+/* Debugging aid: the sparse-loci path's lists of the flagged entries of the prepared pileup, copied to host memory
+ * (synchronises the device). n_flagged: their number; grp (num_blocks * (num_loci + 1) words): flagged entries
+ * before each (cell block, locus) group; rec (4 words each) and idx: their records and packed-entry indices. Any of
+ * grp, rec, idx may be null. SECEDO_E_STATE when the lists have not been built. */
+int secedo_simmat_debug_flag_lists(secedo_simmat_t *handle, uint64_t *n_flagged, uint32_t *grp, uint32_t *rec,
+                                   uint32_t *idx);
 
 /* log-likelihood ratio D(x_s, x_d) = log P(x_s,x_d | different) - log P(x_s,x_d | same) as the
  * matrix path adds it (host-only, no device): what the reference's nested sums return

@@ -560,7 +560,7 @@ __global__ __launch_bounds__(TPB_SCAN) void k_flag_scan(const uint32_t *block_su
     }
     if (threadIdx.x == 0u) {
         *m_idx_end = carry;  // m_idx[E]
-        sc->n_multi_id = carry;
+        if (sc) sc->n_multi_id = carry;  // (null: the flagged entries' lists, pack_flag_lists)
     }
 }
 // m_idx = exclusive scan of the flags (entry e is an M entry iff m_idx[e + 1] != m_idx[e]) and the list of the M
@@ -609,6 +609,82 @@ __global__ __launch_bounds__(TPB) void k_compact_m(Raw in, const uint8_t *multi,
         const uint32_t e = e0 + (uint32_t)i;
         if (e >= n) break;  // (the padding holds no flags)
         if ((words[i >> 2] >> ((i & 3) * 8)) & 1u) m_entry[j++] = e;
+    }
+}
+// The same count -> scan -> compact chain numbers the FLAGGED entries of the packed pileup (C_TAIL | C_MULTI in
+// entry32: the read was never flushed, or has further kept entries) for the correction of the sparse-loci pair
+// kernel (pack_flag_lists). Here a workgroup's thread takes the words tid + k * TPB of its kFlagBlock entries (coalesced
+// loads), so a wave's 64 entries of a round are consecutive: a 64-entry chunk, whose flags are one ballot.
+__global__ __launch_bounds__(TPB) void k_pflag_count(const uint32_t *entry32, uint32_t n, uint32_t *block_sum) {
+    __shared__ uint32_t part[TPB / 64];
+    const uint32_t b0 = blockIdx.x * kFlagBlock + threadIdx.x;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t e = b0 + (uint32_t)k * TPB;
+        c += (e < n && (entry32[e] & (kC_Tail | kC_Multi)) != 0u) ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        for (int w = 1; w < TPB / 64; ++w) c += part[w];
+        block_sum[blockIdx.x] = c;
+    }
+}
+// rec / idx: the flagged entries' records and indices, compact; per 64-entry chunk the flagged entries before it
+// (chunk_pre) and its flags (chunk_mask) -- what k_pflag_groups needs of an exclusive scan over all entries, in 1/21
+// of the bytes
+__global__ __launch_bounds__(TPB) void k_pflag_compact(const uint32_t *entry32, const uint4 *entry, uint32_t n,
+                                                      const uint32_t *block_off, uint4 *rec, uint32_t *idx,
+                                                      uint32_t *chunk_pre, unsigned long long *chunk_mask) {
+    constexpr int WAVES = TPB / 64;
+    static_assert(16 * WAVES == 64, "one wave scans the (round, wave) counts");
+    __shared__ uint32_t cnt[16 * WAVES];  // flagged entries per (round k, wave), in entry order
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t b0 = blockIdx.x * kFlagBlock + threadIdx.x;
+    unsigned long long m[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t e = b0 + (uint32_t)k * TPB;
+        m[k] = __ballot(e < n && (entry32[e] & (kC_Tail | kC_Multi)) != 0u);
+        if (lane == 0u) cnt[k * WAVES + wv] = (uint32_t)__popcll(m[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64u) {
+        const uint32_t v = cnt[threadIdx.x];
+        uint32_t incl = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if (lane >= (uint32_t)off) incl += up;
+        }
+        cnt[threadIdx.x] = incl - v;
+    }
+    __syncthreads();
+    const uint32_t base = block_off[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t e = b0 + (uint32_t)k * TPB;
+        const uint32_t before = base + cnt[k * WAVES + wv];
+        if (lane == 0u) {
+            const uint32_t chunk = (blockIdx.x * kFlagBlock + (uint32_t)k * TPB) / 64u + wv;
+            chunk_pre[chunk] = before;
+            chunk_mask[chunk] = m[k];
+        }
+        if ((m[k] >> lane) & 1ull) {
+            const uint32_t j = before + (uint32_t)__popcll(m[k] & ((1ull << lane) - 1ull));
+            rec[j] = entry[e];
+            idx[j] = e;
+        }
+    }
+}
+// grp[i] = flagged entries before entry blk_off[i]: the flagged entries before each (block, locus) group. (An offset
+// at the end of the last whole chunk reads the total behind the chunks, chunk_pre[n_chunks], and no mask.)
+__global__ __launch_bounds__(TPB) void k_pflag_groups(const uint32_t *blk_off, size_t n_off, const uint32_t *chunk_pre,
+                                                     const unsigned long long *chunk_mask, uint32_t *grp) {
+    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n_off; i += (size_t)gridDim.x * TPB) {
+        const uint32_t d = blk_off[i], c = d >> 6, r = d & 63u;
+        grp[i] = chunk_pre[c] + (r ? (uint32_t)__popcll(chunk_mask[c] & ((1ull << r) - 1ull)) : 0u);
     }
 }
 __global__ void k_m_fields(Raw in, const uint32_t *eloc, const uint32_t *dense, const uint32_t *last,
@@ -2370,6 +2446,32 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
     }
     if (err.empty() && retry != kNoRetry) *need_host = true;  // cannot happen: three attempts cover both requests
     return err;
+}
+
+
+// flag_list_scratch: block sums and offsets (nb each), chunk_pre (64 nb + 1), chunk_mask (64 nb, 8-byte aligned)
+static uint32_t flag_blocks(uint32_t n_entries) { return std::max<uint32_t>(1u, (n_entries + kFlagBlock - 1) / kFlagBlock); }
+
+size_t flag_list_scratch_bytes(uint32_t n_entries) {
+    const size_t nb = flag_blocks(n_entries);
+    return (2 * nb + 64 * nb + 2) * 4 + 64 * nb * 8;
+}
+
+hipError_t pack_flag_lists(const uint32_t *entry32, const uint4 *entry, uint32_t n_entries, const uint32_t *blk_off,
+                           size_t n_off, void *scratch, uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream) {
+    const uint32_t nb = flag_blocks(n_entries);
+    uint32_t *block_sum = static_cast<uint32_t *>(scratch), *block_off = block_sum + nb, *chunk_pre = block_off + nb;
+    unsigned long long *chunk_mask = reinterpret_cast<unsigned long long *>(chunk_pre + 64 * (size_t)nb + 2);
+    hipLaunchKernelGGL(k_pflag_count, dim3(nb), dim3(TPB), 0, stream, entry32, n_entries, block_sum);
+    hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, block_sum, nb, block_off,
+                       chunk_pre + 64 * (size_t)nb, static_cast<Scalars *>(nullptr));
+    hipLaunchKernelGGL(k_pflag_compact, dim3(nb), dim3(TPB), 0, stream, entry32, entry, n_entries, block_off, rec, idx,
+                       chunk_pre, chunk_mask);
+    if (n_off) {
+        const uint32_t blocks = (uint32_t)std::min<size_t>((n_off + TPB - 1) / TPB, 256 * 32);
+        hipLaunchKernelGGL(k_pflag_groups, dim3(blocks), dim3(TPB), 0, stream, blk_off, n_off, chunk_pre, chunk_mask, grp);
+    }
+    return hipGetLastError();
 }
 
 }  // namespace secedo

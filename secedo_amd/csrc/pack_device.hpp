@@ -10,6 +10,7 @@
 #include "pack_host.hpp"
 
 #include <hip/hip_runtime_api.h>
+#include <hip/hip_vector_types.h>
 
 #include <cstdint>
 #include <string>
@@ -89,5 +90,14 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells,
                                uint32_t block_cells, StageGeometry (*geometry)(uint32_t),
                                bool allow_count_tile, hipStream_t stream, DevicePacked *out,
                                bool *need_host);
+
+// The flagged entries of a packed pileup (kC_Tail | kC_Multi in entry32), compacted in packed-entry order -- which
+// is (cell block, locus) order -- for the correction of the sparse-loci pair kernel: grp[n_off] = flagged entries
+// before each group offset blk_off[] (the last one is the end of the entries: grp[n_off - 1] is their number),
+// rec[] / idx[] = the flagged entries' records and indices (room for n_entries each). scratch:
+// flag_list_scratch_bytes(n_entries). Four kernels on `stream`, nothing read back.
+size_t flag_list_scratch_bytes(uint32_t n_entries);
+hipError_t pack_flag_lists(const uint32_t *entry32, const uint4 *entry, uint32_t n_entries, const uint32_t *blk_off,
+                           size_t n_off, void *scratch, uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream);
 
 }  // namespace secedo

@@ -184,6 +184,7 @@ struct secedo_simmat {
     bool timed_mid = false;
     bool timed = false;
     secedo::SideStream side;  // the flagged entries' lists are built beside accumulate_counts (created on first use)
+    bool last_fused = false;  // the last accumulate corrected its tiles in accumulate_counts' epilogue
 };
 
 namespace {
@@ -686,6 +687,22 @@ int secedo_simmat_prepare(secedo_simmat_t *h, uint32_t num_cells, uint32_t max_f
     h->timed = false;
     h->flags_ready = false;
     h->wide_known = false;
+    // The sparse-loci path's lists of the flagged entries, as the last step of the packing and on its stream: the
+    // pair kernel's epilogue reads them (SECEDO_FLAGS_FROM_PACK=0: built by the first accumulate instead,
+    // build_flagged_lists, for A/B runs)
+    static const bool from_pack = [] { const char *e = std::getenv("SECEDO_FLAGS_FROM_PACK"); return !(e && std::atoi(e) == 0); }();
+    if (from_pack && pk.count_tile && !pk.stage_masks && secedo::counts_path_enabled() && pk.num_entries) {
+        const uint32_t ne = (uint32_t)pk.num_entries;
+        const size_t n_off = (size_t)pk.num_blocks * (pk.num_loci + 1);
+        HIP_TRY(h->flag_tmp.ensure(secedo::flag_list_scratch_bytes(ne)));
+        HIP_TRY(h->flag_rec.ensure((size_t)ne * 16));
+        HIP_TRY(h->flag_idx.ensure((size_t)ne * 4));
+        HIP_TRY(h->flag_grp.ensure(std::max<size_t>(n_off, 1) * 4));
+        HIP_TRY(secedo::pack_flag_lists(pk.entry32.as<uint32_t>(), pk.entry.as<uint4>(), ne, pk.blk_off.as<uint32_t>(),
+                                        n_off, h->flag_tmp.p, h->flag_grp.as<uint32_t>(), h->flag_rec.as<uint4>(),
+                                        h->flag_idx.as<uint32_t>(), s));
+        h->flags_ready = true;
+    }
     return SECEDO_OK;
 }
 
@@ -1034,14 +1051,24 @@ static int accumulate_impl(secedo_simmat_t *h, double eps, double hr, double the
     const secedo::SideStream *side = nullptr;
     secedo::SideStream side_call;
     FlagBuild build;
+    h->last_fused = false;
     if (h->pk.count_tile && !h->pk.stage_masks && secedo::counts_path_enabled()) {
-        // accumulate_counts + correct_tiles. The compact list of flagged entries, once per prepare, is read by
-        // the second kernel only: it is built on a stream of the handle's own while the pair kernel runs
+        // accumulate_counts, and correct_tiles or the pair kernel's own epilogue: the epilogue when every tile of the
+        // launch has one workgroup and correct_tiles would have one per tile too (SECEDO_CORRECT_FUSED=0: never)
+        static const bool fused_env = [] {
+            const char *e = std::getenv("SECEDO_CORRECT_FUSED");
+            return !(e && std::atoi(e) == 0);
+        }();
+        a.fused = fused_env && h->plan_workgroups == n_tiles
+                  && (secedo::counts_split(n_tiles) == 1u || (overwrite && list != nullptr));
+        h->last_fused = a.fused;
+        // The compact list of flagged entries, once per prepare, comes with the packing. Otherwise it is built here,
+        // and when correct_tiles reads it it is built on a stream of the handle's own while the pair kernel runs
         static const bool serial = [] {
             const char *e = std::getenv("SECEDO_CORRECT_SERIAL");
             return e && std::atoi(e) != 0;
         }();
-        if (!serial) {
+        if (!serial && !a.fused) {
             if (!h->side.stream) {
                 HIP_TRY(hipStreamCreateWithFlags(&h->side.stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&h->side.fork, hipEventDisableTiming));
@@ -1360,6 +1387,24 @@ const char *secedo_simmat_pair_kernel(const secedo_simmat_t *h) {
         if (!(e && std::atoi(e) == 0)) return "accumulate_masks";
     }
     return "accumulate_tiles";
+}
+
+int secedo_simmat_last_correction_fused(const secedo_simmat_t *h) { return h && h->last_fused ? 1 : 0; }
+
+int secedo_simmat_debug_flag_lists(secedo_simmat_t *h, uint64_t *n_flagged, uint32_t *grp, uint32_t *rec,
+                                   uint32_t *idx) {
+    if (!h || !n_flagged) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    if (!h->prepared || !h->flags_ready) return fail(SECEDO_E_STATE, "the flagged entries' lists have not been built");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n_off = (size_t)h->pk.num_blocks * (h->pk.num_loci + 1);
+    uint32_t n = 0;  // (the last group offset is the end of the entries)
+    if (n_off) HIP_TRY(hipMemcpy(&n, h->flag_grp.as<uint32_t>() + n_off - 1, 4, hipMemcpyDeviceToHost));
+    *n_flagged = n;
+    if (grp && n_off) HIP_TRY(hipMemcpy(grp, h->flag_grp.p, n_off * 4, hipMemcpyDeviceToHost));
+    if (rec && n) HIP_TRY(hipMemcpy(rec, h->flag_rec.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (idx && n) HIP_TRY(hipMemcpy(idx, h->flag_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return SECEDO_OK;
 }
 
 int secedo_simmat_last_pair_kernel_ms(secedo_simmat_t *h, float *ms) {

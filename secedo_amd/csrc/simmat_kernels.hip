@@ -740,6 +740,9 @@ constexpr uint32_t IT_REC_MASK = 0x1FFu;  // cell (7 bits) | base (2 bits)
 // C++ form the compiler builds, per slot, saveexec + a branch around the (out-of-line) body + s_or exec + the test
 // of the wave-uniform `diag` flag with its branch: five scalar / branch instructions for three vector ones and
 // the ds_add -- 0.63e9 scalar instructions per C3 launch through the ONE scalar unit of a CU, 2.3e8 branches.
+template <int B, int THREADS, int NCNT>
+__device__ __forceinline__ void correct_epilogue(const AccumulateArgs &a, unsigned char *lds, uint32_t t_local,
+                                                 const uint32_t (&cnt)[NCNT]);
 template <int B, int THREADS, int CAPJ, int CAPL, int GROUP, bool SLOT_ASM>
 __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArgs a) {
     static_assert(CAPJ <= 16384, "14 bits of column index in an item");
@@ -1179,8 +1182,18 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
 #endif
     __syncthreads();
 
-    // flush: the tile goes to the workgroup's own slab with plain coalesced stores (reduce_slabs adds up)
-    {
+    // flush: the tile goes to the workgroup's own slab with plain coalesced stores (correct_tiles adds up) -- or, when
+    // the tile is this workgroup's alone, into registers for the epilogue below
+    constexpr int NCNT = (B * B) / THREADS;
+    static_assert(NCNT * THREADS == B * B && NCNT <= 16, "the count tile in whole words per thread");
+    uint32_t cnt[NCNT];
+    if (a.fused) {
+#pragma unroll
+        for (int k = 0; k < NCNT; ++k) {
+            const uint32_t i = tid + (uint32_t)k * THREADS;
+            cnt[k] = tile32[(i / B) * ROW_WORDS + (i % B)];  // dense rows, as the slab holds them
+        }
+    } else {
         uint32_t *out = reinterpret_cast<uint32_t *>(a.slab) + (size_t)blockIdx.x * B * B;
         for (uint32_t i = tid; i < B * B; i += THREADS) out[i] = tile32[(i / B) * ROW_WORDS + (i % B)];  // dense rows
     }
@@ -1197,6 +1210,10 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
             atomicAdd(&a.counters[0], u);
             atomicAdd(&a.counters[1], u);
         }
+    }
+    if (a.fused) {
+        __syncthreads();  // (red[] has been read and the count tile is in registers: the LDS is free)
+        correct_epilogue<B, THREADS, NCNT>(a, lds_raw, t_local, cnt);
     }
 }
 
@@ -1945,36 +1962,62 @@ struct CorrectArgs {
 // 2. reduce_slabs: the count tiles of the tile's accumulate_counts workgroups, converted with the two
 //    single-locus ratios (exact integer arithmetic), plus the LDS tile, added to acc[tile] with plain coalesced
 //    read-modify-writes: nothing else touches the tile during the launch.
+//
+// When every tile of a launch has one accumulate_counts workgroup (counts_split == 1 and a workgroup plan of one
+// chunk per tile: C3, C5), that workgroup does both itself after its last locus range (AccumulateArgs::fused,
+// correct_epilogue): its count tile goes to registers instead of the slab, and the pair phase's LDS holds the int64
+// tile. correct_tiles remains for launches of few tiles (a tile shared by several workgroups) and for
+// SECEDO_CORRECT_FUSED=0. Both run correct_setup + correct_tile below.
+__host__ __device__ inline CorrectArgs correct_args(const AccumulateArgs &args) {  // (split, overwrite, max_bits: 0)
+    CorrectArgs c = {};
+    c.blk_off = args.blk_off;
+    c.stride = args.stride;
+    c.flag_grp = args.flag_grp;
+    c.flag_rec = args.flag_rec;
+    c.flag_idx = args.flag_idx;
+    c.slow = args.slow;
+    c.lut = args.lut;
+    c.tile_row = args.tile_row;
+    c.tile_col = args.tile_col;
+    c.tile_begin = args.tile_begin;
+    c.tile_ids = args.tile_ids;
+    c.slab = args.slab;
+    c.tile_wg_begin = args.tile_wg_begin;
+    c.acc = args.acc;
+    c.counters = args.counters;
+    c.max_scale = args.max_scale;
+    return c;
+}
+
+// corr = 0 (B * B); scorr = the correction D(x_s,x_d) - x_s D(1,0) - x_d D(0,1) itself for few shared loci (the
+// usual case)
 template <int B, int THREADS>
-__global__ __launch_bounds__(THREADS) void correct_tiles(const CorrectArgs a) {
-    extern __shared__ unsigned long long corr[];  // B * B
-    __shared__ long long part[2 * (THREADS / 64)];
-    // the correction D(x_s,x_d) - x_s D(1,0) - x_d D(0,1) itself for few shared loci (the usual case)
-    __shared__ long long scorr[SLUT_DIM * SLUT_DIM];
-    constexpr int U = 6;  // flagged entries p per thread in flight: their loads are issued together
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t S = a.split, t_local = blockIdx.x / S, part_id = blockIdx.x % S;
-    const uint32_t t = a.tile_ids ? a.tile_ids[t_local] : a.tile_begin + t_local;
-    const uint32_t I = a.tile_row[t], J = a.tile_col[t];
-    const bool diag = I == J;
+__device__ __forceinline__ void correct_setup(const long long *lut, long long d10, long long d01,
+                                              unsigned long long *corr, long long *scorr) {
+    const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < (uint32_t)(B * B); i += THREADS) corr[i] = 0ull;
-    const long long d10 = a.lut[1 * LUT_DIM + 0], d01 = a.lut[0 * LUT_DIM + 1];
     if (tid < (uint32_t)(SLUT_DIM * SLUT_DIM)) {
         const uint32_t xs = tid / SLUT_DIM, xd = tid % SLUT_DIM;
-        scorr[tid] = a.lut[xs * LUT_DIM + xd] - (long long)xs * d10 - (long long)xd * d01;
+        scorr[tid] = lut[xs * LUT_DIM + xd] - (long long)xs * d10 - (long long)xd * d01;
     }
     __syncthreads();
-    // The usual launch -- one count tile per matrix tile, one workgroup per tile -- asks for its count tile NOW: the
-    // 16 words per thread land while the flagged entries are paired (the flush below then starts with its data at
-    // hand instead of with a round trip to HBM).
-    constexpr int PRE = (B * B) / THREADS;
-    const bool prefetched = S == 1u && a.tile_wg_begin[t_local + 1] - a.tile_wg_begin[t_local] == 1u && PRE <= 16;
-    uint32_t pre[PRE <= 16 ? PRE : 1];
-    if (prefetched) {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.slab) + (size_t)a.tile_wg_begin[t_local] * B * B;
-#pragma unroll
-        for (int k = 0; k < (PRE <= 16 ? PRE : 1); ++k) pre[k] = __builtin_nontemporal_load(&src[tid + (uint32_t)k * THREADS]);
-    }
+}
+
+// The tile's flagged pairs into corr, then the tile into acc (steps 1 and 2 above), for part part_id of a.split.
+// t: the tile (global index), d10 / d01: D(1,0) and D(0,1).
+// The count tiles: IN_CORR -- already converted into corr (the fused epilogue) --, or pre[k] holds the tile's only
+// count tile at cell tid + k * THREADS (dense rows) when `prefetched`, or they are read from the slab. part:
+// 2 * THREADS / 64 words of LDS.
+template <int B, int THREADS, int NPRE, bool IN_CORR>
+__device__ __forceinline__ void correct_tile(const CorrectArgs &a, unsigned long long *corr, const long long *scorr,
+                                             long long *part, uint32_t t_local, uint32_t part_id, uint32_t t,
+                                             long long d10, long long d01, const uint32_t (&pre)[NPRE],
+                                             bool prefetched) {
+    constexpr int U = 6;  // flagged entries p per thread in flight: their loads are issued together
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t S = a.split;
+    const uint32_t I = a.tile_row[t], J = a.tile_col[t];
+    const bool diag = I == J;
     long long upd_delta = 0, pair_delta = 0;  // per lane
 #ifdef SECEDO_STAMPS
     unsigned long long dg_tests = 0, dg_tail = 0, dg_joint = 0, dg_later = 0;
@@ -2149,12 +2192,12 @@ __global__ __launch_bounds__(THREADS) void correct_tiles(const CorrectArgs a) {
                 // (cell c0 + f * THREADS = tid + (batch * F + f) * THREADS: the word pre[batch * F + f])
                 uint32_t v = 0;
 #pragma unroll
-                for (int k = 0; k < (PRE <= 16 ? PRE : 1); ++k) v = (k == batch * F + f) ? pre[k] : v;
+                for (int k = 0; k < NPRE; ++k) v = (k == batch * F + f) ? pre[k] : v;
                 n_same[f] = v & 0xFFFFu;
                 n_diff[f] = v >> 16;
             }
         }
-        for (uint32_t w = prefetched ? w1 : w0; w < w1; ++w) {
+        for (uint32_t w = (prefetched || IN_CORR) ? w1 : w0; w < w1; ++w) {
 #pragma unroll
             for (int f = 0; f < F; ++f) {
                 const uint32_t c = c0 + f * THREADS;
@@ -2213,6 +2256,62 @@ __global__ __launch_bounds__(THREADS) void correct_tiles(const CorrectArgs a) {
         atomicAdd(&a.counters[92], (unsigned long long)dg_qiter);
     }
 #endif
+}
+
+
+template <int B, int THREADS>
+__global__ __launch_bounds__(THREADS) void correct_tiles(const CorrectArgs a) {
+    extern __shared__ unsigned long long corr[];  // B * B
+    __shared__ long long part[2 * (THREADS / 64)];
+    __shared__ long long scorr[SLUT_DIM * SLUT_DIM];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t S = a.split, t_local = blockIdx.x / S, part_id = blockIdx.x % S;
+    const uint32_t t = a.tile_ids ? a.tile_ids[t_local] : a.tile_begin + t_local;
+    const long long d10 = a.lut[1 * LUT_DIM + 0], d01 = a.lut[0 * LUT_DIM + 1];
+    correct_setup<B, THREADS>(a.lut, d10, d01, corr, scorr);
+    // The usual launch -- one count tile per matrix tile, one workgroup per tile -- asks for its count tile NOW: the
+    // 16 words per thread land while the flagged entries are paired (the flush below then starts with its data at
+    // hand instead of with a round trip to HBM).
+    constexpr int PRE = (B * B) / THREADS, NPRE = PRE <= 16 ? PRE : 1;
+    const bool prefetched = S == 1u && a.tile_wg_begin[t_local + 1] - a.tile_wg_begin[t_local] == 1u && PRE <= 16;
+    uint32_t pre[NPRE];
+    if (prefetched) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.slab) + (size_t)a.tile_wg_begin[t_local] * B * B;
+#pragma unroll
+        for (int k = 0; k < NPRE; ++k) pre[k] = __builtin_nontemporal_load(&src[tid + (uint32_t)k * THREADS]);
+    }
+    correct_tile<B, THREADS, NPRE, false>(a, corr, scorr, part, t_local, part_id, t, d10, d01, pre, prefetched);
+}
+
+// accumulate_counts' epilogue when its workgroup is the tile's only one (AccumulateArgs::fused): correct_tiles' work
+// on the tile in the pair phase's LDS. corr starts as the count tile's own terms, same * D(1,0) + diff * D(0,1) --
+// the sum correct_tiles forms at the end; in exact (wrapping) int64 arithmetic the order of the additions does not
+// change a bit --, so the counts (cnt[k]: cell tid + k * THREADS, dense rows) need no registers while the flagged
+// entries are paired.
+template <int B, int THREADS, int NCNT>
+__device__ __forceinline__ void correct_epilogue(const AccumulateArgs &a, unsigned char *lds, uint32_t t_local,
+                                                 const uint32_t (&cnt)[NCNT]) {
+    unsigned long long *corr = reinterpret_cast<unsigned long long *>(lds);
+    long long *scorr = reinterpret_cast<long long *>(lds + (size_t)B * B * 8);
+    long long *part = scorr + SLUT_DIM * SLUT_DIM;
+    const uint32_t tid = threadIdx.x;
+    const long long d10 = a.lut[1 * LUT_DIM + 0], d01 = a.lut[0 * LUT_DIM + 1];
+#pragma unroll
+    for (int k = 0; k < NCNT; ++k)
+        corr[tid + (uint32_t)k * THREADS] = (unsigned long long)((long long)(cnt[k] & 0xFFFFu) * d10
+                                                                 + (long long)(cnt[k] >> 16) * d01);
+    if (tid < (uint32_t)(SLUT_DIM * SLUT_DIM)) {
+        const uint32_t xs = tid / SLUT_DIM, xd = tid % SLUT_DIM;
+        scorr[tid] = a.lut[xs * LUT_DIM + xd] - (long long)xs * d10 - (long long)xd * d01;
+    }
+    __syncthreads();
+    CorrectArgs c = correct_args(a);
+    c.split = 1u;
+    c.overwrite = a.overwrite ? 1u : 0u;
+    c.max_bits = a.max_bits;
+    const uint32_t none[1] = {0u};
+    const uint32_t t = a.tile_ids ? a.tile_ids[t_local] : a.tile_begin + t_local;
+    correct_tile<B, THREADS, 1, true>(c, corr, scorr, part, t_local, 0u, t, d10, d01, none, false);
 }
 
 // acc[tile] += sum over the tile's workgroups of their slab (count slabs are converted with the two
@@ -2423,8 +2522,11 @@ hipError_t launch_counts_v(const AccumulateArgs &args, uint32_t grid, hipStream_
         if (e != hipSuccess) return e;
         configured_device = dev;
     }
+    // (the fused epilogue's corr, scorr and part in the same LDS)
+    static_assert((size_t)B * B * 8 + ((size_t)SLUT_DIM * SLUT_DIM + 2 * (THREADS / 64)) * 8 <= lds, "LDS of the epilogue");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, args);
     if (mid && (e = hipEventRecord(mid, stream)) != hipSuccess) return e;
+    if (args.fused) return hipGetLastError();  // the correction was the pair kernel's epilogue
     if (side && side->deferred && (e = side->deferred(side->deferred_ctx)) != hipSuccess) return e;
     return launch_correct<B>(args, stream, side);
 }
@@ -2449,22 +2551,7 @@ hipError_t launch_correct(const AccumulateArgs &args, hipStream_t stream, const 
     if (side && side->stream) {
         if ((e = hipStreamWaitEvent(stream, side->join, 0)) != hipSuccess) return e;
     }
-    CorrectArgs c;
-    c.blk_off = args.blk_off;
-    c.stride = args.stride;
-    c.flag_grp = args.flag_grp;
-    c.flag_rec = args.flag_rec;
-    c.flag_idx = args.flag_idx;
-    c.slow = args.slow;
-    c.lut = args.lut;
-    c.tile_row = args.tile_row;
-    c.tile_col = args.tile_col;
-    c.tile_begin = args.tile_begin;
-    c.tile_ids = args.tile_ids;
-    c.slab = args.slab;
-    c.tile_wg_begin = args.tile_wg_begin;
-    c.acc = args.acc;
-    c.counters = args.counters;
+    CorrectArgs c = correct_args(args);
     constexpr int CT = B == 128 ? 1024 : 256;
     constexpr size_t corr_lds = (size_t)B * B * 8;
     auto corr = &correct_tiles<B, CT>;
@@ -2481,7 +2568,6 @@ hipError_t launch_correct(const AccumulateArgs &args, hipStream_t stream, const 
     if (args.overwrite && args.tile_ids) c.split = 1;
     c.overwrite = (args.overwrite && c.split == 1u) ? 1u : 0u;
     c.max_bits = c.split == 1u ? args.max_bits : nullptr;
-    c.max_scale = args.max_scale;
     if (args.overwrite && c.split > 1u) {
         e = hipMemsetAsync(args.acc + (size_t)args.tile_begin * B * B, 0, (size_t)args.n_tiles * B * B * 8, stream);
         if (e != hipSuccess) return e;

@@ -88,6 +88,10 @@ struct AccumulateArgs {
     // the stored tiles by atomicMax, as launch_tile_max leaves it (zeroed by the caller)
     unsigned long long *max_bits = nullptr;
     double max_scale = 0.0;
+    // counts path, every tile of the launch with one accumulate_counts workgroup (and correct_tiles with one per tile):
+    // that workgroup corrects and stores its tile itself, no slab, no correct_tiles (the flagged entries' lists must
+    // be complete when the launch starts)
+    bool fused = false;
 };
 
 // true when the count-tile variants run accumulate_counts + correct_tiles (the default; SECEDO_PAIR_MODE=0

@@ -79,7 +79,7 @@ def sharded_accumulate(plan, acc, mutation_rate, homozygous_rate, seq_error_rate
 def sharded_accumulate_overlapped(plan, acc, mutation_rate, homozygous_rate, seq_error_rate, rank, world,
                                   chunks=4, group=None, comm_stream=None):
     """sharded_accumulate with the exchange hidden behind the accumulation: the rank's tile range is worked off
-    in `chunks` launches, and as soon as a chunk's tiles are final (correct_tiles has stored them) its
+    in `chunks` launches, and as soon as a chunk's tiles are final (stored by the launch's last kernel) its
     all-gather is issued on a second stream while the next chunk accumulates; the calling stream waits for the
     last exchange at the end. Tiles keep their place in `acc` (position = tile index), so chunk k of rank r is
     the k-th part of r's slice and the gather of chunk k writes `world` separate slices of `acc` (all_gather
