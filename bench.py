@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the similarity-matrix hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C5|C1] [--clustered]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C5|C1] [--clustered] [--full]
 
 One step = one pass of the hot path over the synthetic pileup already resident in HBM: device packing
 of the raw flat pileup (read assembly, flush schedule, tiles), zero the accumulator, accumulate the
@@ -21,15 +21,20 @@ With N > 1 both ways of sharing the matrix are timed, K steps each:
     (sum) of the accumulator.
 `value` is the faster of the two (named in config.parallelism); both are in `partitionings`.
 `--workload C5 --gpus N` times BASELINE configs[4] as written instead: the matrix kept sharded by rows (no
-all-gather) and fed to the distributed spectral step, both phases reported.
+all-gather) and fed to the distributed spectral step (each phase timed on its own as well under --full).
 Exactly K steps are timed, in `--repeats` blocks (5): `ms_per_step` is the median block's time per step, the
 blocks give the spread.
 `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see matrix_outputs).
-After the timed region the last output is held against the compiled reference's sampled entries where a digest
-exists (C3, C2): `parity_checked`.
-`roofline` is stated against the limit that binds the dominant kernel: LDS atomics at random addresses (peak
-measured by tools/lds_atomic_bench on the same box); the HBM figures (measured traffic, and SURVEY 8d's
-algorithmic-bytes accounting under `b_alg`) are beside it.
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump, print the line.
+`--full` measures the rest after the dump, and the line then carries it (a plain run leaves these fields null):
+  * the last output held against the compiled reference's sampled entries where a digest exists (C3, C2):
+    `parity_checked`, `parity`;
+  * phase times of one step and the per-launch kernel time: `phase_ms`, `config.replicated_ms_per_step`;
+  * `roofline`, stated against the limit that binds the dominant kernel: LDS atomics at random addresses (peak
+    measured by tools/lds_atomic_bench on the same GPU); the HBM figures (measured traffic, and SURVEY 8d's
+    algorithmic-bytes accounting under `b_alg`) are beside it; the traffic and SQ counters come from rocprofv3
+    --pmc child runs of this script (one GPU, unless --no-cpu-baseline or --no-live-counters), else from profiles/;
+  * one GPU, unless --no-cpu-baseline: the one-shot host call, the C++ drop-in call and `cpu_baseline`.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -266,9 +271,15 @@ def parse_args(argv=None):
                          "whole matrix up to C2's size, else a fixed seeded sample of entries and the row sums)")
     ap.add_argument("--workload", default="C3", choices=["C1", "C2", "C3", "C5"])
     ap.add_argument("--clustered", action="store_true", help="gap_max=300 variant (~2.8 loci/read)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the in-run parity "
+                         "against the compiled reference, phase and per-launch kernel times, the roofline (with its "
+                         "counter passes), the host-side calls and the CPU baseline (minutes on C3)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: leave out the host-side calls, the CPU baseline and the live counter passes")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="take roofline.traffic and the SQ counters from profiles/ instead of measuring them in this run")
+                    help="--full: take roofline.traffic and the SQ counters from profiles/ instead of measuring them in "
+                         "this run")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend (nccl = RCCL over xGMI; gloo only to rehearse the N > 1 "
                          "flow on a box with fewer GPUs than ranks)")
@@ -529,23 +540,23 @@ def main():
                 arrays["spectral_eigenvalues"] = np.asarray(vals, dtype=np.float64)
                 arrays["spectral_eigenvectors"] = vecs.cpu().numpy()
                 dumped = write_outputs(args.dump_outputs, arrays)
-        phases = {}
-        for name, fn in (("matrix_sharded_rows_ms", matrix_step), ("spectral_sharded_ms", spectral_step)):
-            ts = []
-            for _ in range(3):
-                sync()
-                t0 = time.perf_counter()
-                fn()
-                sync()
-                ts.append((time.perf_counter() - t0) * 1e3)
-            phases[name] = sorted(ts)[1]
-        bt = torch.tensor(blocks + [phases["matrix_sharded_rows_ms"], phases["spectral_sharded_ms"]],
-                          dtype=torch.float64, device=red_dev)
+        phases = []
+        if args.full:  # the two phases of the step, each on its own: median of three
+            for fn in (matrix_step, spectral_step):
+                ts = []
+                for _ in range(3):
+                    sync()
+                    t0 = time.perf_counter()
+                    fn()
+                    sync()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                phases.append(sorted(ts)[1])
+        bt = torch.tensor(blocks + phases, dtype=torch.float64, device=red_dev)
         cnt = torch.tensor([own_updates, own_pairs, len(ids)], dtype=torch.int64, device=red_dev)
         if world > 1:
             dist.all_reduce(bt, op=dist.ReduceOp.MAX)
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
-        blocks = sorted(float(v) / size for v, size in zip(bt[:-2], sizes))  # seconds per step of each block
+        blocks = sorted(float(v) / size for v, size in zip(bt[:len(sizes)], sizes))  # seconds per step of each block
         elapsed = blocks[len(blocks) // 2] * args.steps
         if rank == 0:
             vals, _, info = state["eig"]
@@ -555,7 +566,7 @@ def main():
                 "metric": "cell-pair x locus updates/sec (similarity matrix)", "value": updates / step_s,
                 "unit": "updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-                "dtype": "int64", "data": "synthetic (SYNTH-v1, seed 42)",
+                "dtype": "int64", "data": "synthetic (SYNTH-v1, seed 42)", "full": args.full,
                 "config": {"workload": "%s: %d cells x %d loci, matrix kept sharded by rows (no all-gather) + distributed "
                                        "spectral step (BASELINE configs[4])" % (args.workload, n_cells, n_loci),
                            "updates_per_step": updates, "read_pairs_per_step": int(cnt[1].item()),
@@ -566,7 +577,8 @@ def main():
                            "backend": backend_name, "world_size": world, "rccl_world_size": pg_world},
                 "block_ms": [b * 1e3 for b in blocks],
                 "spread": (blocks[-1] - blocks[0]) / step_s if step_s else None,
-                "phase_ms": {"matrix_sharded_rows": float(bt[-2].item()), "spectral_sharded": float(bt[-1].item())},
+                "phase_ms": {"matrix_sharded_rows": float(bt[-2].item()), "spectral_sharded": float(bt[-1].item())}
+                if args.full else None,
                 "spectral": {"smallest_eigenvalues": [float(v) for v in vals[:4]], **info},
                 "first_prepare_s": prepare_s, "step_includes_packing": not args.packed_resident,
                 "roofline": None, "cpu_baseline": None, "dumped_outputs": dumped,
@@ -609,65 +621,73 @@ def main():
     by_chromosome, block_cells, my_tiles = best["by_chromosome"], best["block_cells"], best["my_tiles"]
     elapsed, updates = best["elapsed"], best["updates"]
 
-    # parity of the LAST TIMED OUTPUT (outside the timed region): `out` still holds what the last timed step of
-    # the last partitioning wrote; held against the compiled reference's sampled entries where a digest exists
-    # (and written by --dump-outputs: every rank holds the whole matrix)
+    # --dump-outputs: the LAST TIMED OUTPUT (outside the timed region): `out` still holds what the last timed step of
+    # the last partitioning wrote (every rank holds the whole matrix)
     dumped = write_outputs(args.dump_outputs, matrix_outputs(out, 0, n_cells)) \
         if args.dump_outputs and rank == 0 else None
-    parity = None
-    digest = reference_digest(args.workload, args.clustered, int(p.n_entries), rates, mfl, threads) if rank == 0 else None
-    if digest is not None:
-        ii = torch.from_numpy(digest["sample_i"].astype(np.int64)).to(out.device)
-        jj = torch.from_numpy(digest["sample_j"].astype(np.int64)).to(out.device)
-        err = np.abs(out[ii, jj].cpu().numpy() - digest["sample_v"])
-        ref_max = float(digest["max_abs"])
-        parity = {"checked": True, "against": "compiled reference (oracle/_ref), tests/golden/%s%s_reference_digest.npz"
-                                              % (args.workload.lower(), "_clustered" if args.clustered else ""),
-                  "samples": int(len(err)), "normwise_err": float(err.max() / ref_max), "tolerance": 1e-9,
-                  "max_abs_matches": bool(abs(float(out.abs().max()) - ref_max) <= 1e-9 * ref_max),
-                  "symmetric": bool(torch.equal(out, out.T)), "zero_diagonal": not bool(torch.any(torch.diagonal(out)))}
-        parity["ok"] = bool(parity["normwise_err"] <= 1e-9 and parity["max_abs_matches"] and parity["symmetric"]
-                            and parity["zero_diagonal"])
 
-    # phase times of one step of the reported partitioning, events on the launch stream (torch's current one)
-    phase = {}
+    def full_fields():
+        """--full only: what the headline does not need, measured after the timed region and the dump. Returns the
+        line's added fields on rank 0 (None on the others): the in-run parity, the phase and per-launch kernel times,
+        the roofline (with its counter passes and microbenchmark) and, unless --no-cpu-baseline, the host calls and
+        the CPU baseline."""
+        # parity of the last timed output, held against the compiled reference's sampled entries where a digest exists
+        # (before the phase times below write `out` again)
+        parity = None
+        digest = reference_digest(args.workload, args.clustered, int(p.n_entries), rates, mfl, threads) if rank == 0 else None
+        if digest is not None:
+            ii = torch.from_numpy(digest["sample_i"].astype(np.int64)).to(out.device)
+            jj = torch.from_numpy(digest["sample_j"].astype(np.int64)).to(out.device)
+            err = np.abs(out[ii, jj].cpu().numpy() - digest["sample_v"])
+            ref_max = float(digest["max_abs"])
+            parity = {"checked": True, "against": "compiled reference (oracle/_ref), tests/golden/%s%s_reference_digest.npz"
+                                                  % (args.workload.lower(), "_clustered" if args.clustered else ""),
+                      "samples": int(len(err)), "normwise_err": float(err.max() / ref_max), "tolerance": 1e-9,
+                      "max_abs_matches": bool(abs(float(out.abs().max()) - ref_max) <= 1e-9 * ref_max),
+                      "symmetric": bool(torch.equal(out, out.T)), "zero_diagonal": not bool(torch.any(torch.diagonal(out)))}
+            parity["ok"] = bool(parity["normwise_err"] <= 1e-9 and parity["max_abs_matches"] and parity["symmetric"]
+                                and parity["zero_diagonal"])
 
-    def repack():
-        plan.prepare_resident(resident, n_cells, mfl, threads, block_cells)
+        # phase times of one step of the reported partitioning, events on the launch stream (torch's current one)
+        phase = {}
 
-    def refinalize():
-        plan.finalize(acc, norm, out)
+        def repack():
+            plan.prepare_resident(resident, n_cells, mfl, threads, block_cells)
 
-    for name, fn in (("pack_ms", repack), ("finalize_ms", refinalize)):
-        ts = []
-        if name == "finalize_ms":
-            plan.accumulate(acc, *rates, *my_tiles, overwrite=True)
-        for _ in range(5):
+        def refinalize():
+            plan.finalize(acc, norm, out)
+
+        for name, fn in (("pack_ms", repack), ("finalize_ms", refinalize)):
+            ts = []
+            if name == "finalize_ms":
+                plan.accumulate(acc, *rates, *my_tiles, overwrite=True)
+            for _ in range(5):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b))
+            phase[name] = sorted(ts)[len(ts) // 2]
+        # per-launch kernel time over K launches with events on the launch stream
+        lo, hi = my_tiles
+        evs, pair_samples = [], []
+        for _ in range(min(args.steps, 10)):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            fn()
+            plan.accumulate(acc, *rates, lo, hi, overwrite=True)
             b.record()
-            torch.cuda.synchronize()
-            ts.append(a.elapsed_time(b))
-        phase[name] = sorted(ts)[len(ts) // 2]
-    # per-launch kernel time over K launches with events on the launch stream
-    lo, hi = my_tiles
-    evs, pair_samples = [], []
-    for _ in range(min(args.steps, 10)):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        plan.accumulate(acc, *rates, lo, hi, overwrite=True)
-        b.record()
-        evs.append((a, b))
-        pm = plan.last_pair_kernel_ms()  # the pair kernel alone in this launch (HIP events of the library)
-        if pm:
-            pair_samples.append(pm)
-    torch.cuda.synchronize()
-    ev_ms = sorted(a.elapsed_time(b) for a, b in evs)
-    kern_ms = ev_ms[len(ev_ms) // 2]
-    pair_ms = sorted(pair_samples)[len(pair_samples) // 2] if pair_samples else None
+            evs.append((a, b))
+            pm = plan.last_pair_kernel_ms()  # the pair kernel alone in this launch (HIP events of the library)
+            if pm:
+                pair_samples.append(pm)
+        torch.cuda.synchronize()
+        ev_ms = sorted(a.elapsed_time(b) for a, b in evs)
+        kern_ms = ev_ms[len(ev_ms) // 2]
+        pair_ms = sorted(pair_samples)[len(pair_samples) // 2] if pair_samples else None
+        if rank != 0:
+            return None
 
-    if rank == 0:
         # counter-derived inputs: HBM bytes per launch (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over
         # this same command, calibrated as the microarch guide prescribes) and the SQ counters of the pair kernel
         key = args.workload if world == 1 else ""
@@ -685,7 +705,7 @@ def main():
                 counters = rec
         counters_live = False
         if world == 1 and not args.no_cpu_baseline and not args.no_live_counters:
-            # (the full default command only: four child runs of about ten seconds each)
+            # (--full with the CPU baseline only: four child runs of about ten seconds each)
             live_t, live_c = live_counters(args, plan.pair_kernel, pair_ms if pair_ms else kern_ms)
             if live_t and live_c:
                 traffic_rec, counters, counters_live = live_t, live_c, True
@@ -695,7 +715,6 @@ def main():
         b_alg = (16 * local_updates + 6 * E + 4 * L + 16 * N * N if by_chromosome
                  else 16 * local_updates + 6 * E / world + 4 * L + 16 * N * N / world)
         b_alg_step = 16 * updates + 6 * best["kept_entries"] + 4 * n_loci + 16 * N * N  # the whole job
-        step_s = elapsed / args.steps
         dom_ms = pair_ms if pair_ms else kern_ms
         dom_name = plan.pair_kernel if pair_ms else plan.pair_kernel + " (+ its reduction kernels: the accumulate phase)"
         peak, peak_src, peak_rec = lds_atomic_peak()
@@ -737,6 +756,47 @@ def main():
                 roofline["lds_pipe_busy_frac"] = counters["SQ_LDS_IDX_ACTIVE"] / (256.0 * cyc)
             roofline["counters_source"] = (counters.get("source") if counters_live
                                            else "profiles/%s_counters.json" % PROFILE_ROUND)
+        fields = {
+            "parity_checked": bool(parity and parity["ok"]),
+            "parity": parity,
+            # tiles mode: every rank packs the whole pileup, only the pair accumulation is divided
+            "replicated_ms_per_step": phase["pack_ms"] if world > 1 and not by_chromosome else None,
+            "phase_ms": {"pack": phase["pack_ms"], "accumulate": kern_ms, "finalize": phase["finalize_ms"]},
+            "roofline": roofline,
+        }
+        if not args.no_cpu_baseline and world == 1:
+            # the drop-in call itself: host buffers in, host matrix out (H2D, pack, accumulate, normalise,
+            # D2H) -- PCIe-inclusive, never `value`
+            # (the library keeps the call's device buffers for the next call: first and repeated call)
+            t0 = time.perf_counter()
+            secedo_amd.compute_similarity_matrix(p, n_cells, mfl, None, *rates, threads, "", norm)
+            fields["one_shot_first_call_s"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            secedo_amd.compute_similarity_matrix(p, n_cells, mfl, None, *rates, threads, "", norm)
+            fields["one_shot_host_call_s"] = time.perf_counter() - t0
+            # ... and through the C++ shim with the reference's signature (include/secedo_simmat.hpp) from a
+            # vector<vector<PosData>>, as the reference's caller holds the pileup: flatten + H2D + step +
+            # D2H straight into the returned matrix. A child process (tests/cpp/shim_test.cpp, built by make).
+            shim = os.path.join(ROOT, "secedo_amd", "csrc", "build", "shim_test")
+            if os.path.exists(shim) and n_cells <= 16383:
+                try:
+                    r = subprocess.run([shim, "--synth", str(n_cells), str(n_loci), str(n_chr),
+                                        str(300 if args.clustered else gap), repr(prob), "2"],
+                                       capture_output=True, text=True, timeout=600)
+                    fields["cpp_dropin_call"] = json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 \
+                        else {"error": r.stderr[-300:]}
+                except (subprocess.SubprocessError, ValueError, IndexError) as e:
+                    fields["cpp_dropin_call"] = {"error": str(e)[:300]}
+            fields["cpu_baseline"] = cpu_baseline(p, n_cells, mfl, rates, threads, 5e8)
+            if digest is not None and "reference_seconds" in digest.files:
+                # the WHOLE workload through the compiled reference, once, in the build container (8 vCPUs), when
+                # the digest above was made (oracle/gen_golden.py): not a measurement of this run
+                fields["cpu_baseline"]["reference_full_workload_s_in_build_container"] = float(digest["reference_seconds"])
+        return fields
+
+    step_s = elapsed / args.steps
+    extra = full_fields() if args.full else None
+    if rank == 0:
         line = {
             "metric": "cell-pair x locus updates/sec (similarity matrix)",
             "value": updates * args.steps / elapsed,
@@ -750,6 +810,7 @@ def main():
             "vs_baseline": None,
             "dtype": "int64",
             "data": "synthetic (SYNTH-v1, seed 42)",
+            "full": args.full,
             "config": {"workload": "%s: %d cells x %d loci%s" % (
                 args.workload, n_cells, n_loci, " clustered" if args.clustered else ""),
                 "entries": int(p.n_entries), "kept_entries": best["kept_entries"], "reads": best["reads"],
@@ -763,14 +824,13 @@ def main():
                                                                                 "the accumulation" % args.chunks
                                                                          if best["overlapped"] else "")),
                 "backend": backend_name, "world_size": world, "rccl_world_size": pg_world,
-                # tiles mode: every rank packs the whole pileup, only the pair accumulation is divided
-                "replicated_ms_per_step": phase.get("pack_ms") if world > 1 and not by_chromosome else None},
+                "replicated_ms_per_step": None},
             # the K-step block, timed `repeats` times: value / ms_per_step are the median block's
             "repeats": len(best["blocks"]),
             "block_ms_per_step": [b * 1e3 for b in best["blocks"]],
             "spread": (best["blocks"][-1] - best["blocks"][0]) / step_s if step_s else None,
-            "parity_checked": bool(parity and parity["ok"]),
-            "parity": parity,
+            "parity_checked": None,  # --full: held against the compiled reference in the run
+            "parity": None,
             "partitionings": {("chromosomes+all-reduce" if m["by_chromosome"] else
                                "tiles+all-gather in %d chunks behind the accumulation" % args.chunks if m["overlapped"]
                                else "tiles+all-gather"):
@@ -781,40 +841,15 @@ def main():
             "dense_equivalent_cell_pair_locus_slots_per_s": n_cells * (n_cells - 1) / 2 * n_loci / step_s,
             "step_includes_packing": not args.packed_resident,
             "packing": "device" if plan.used_device_packing else "host",
-            "phase_ms": {"pack": phase["pack_ms"], "accumulate": kern_ms, "finalize": phase["finalize_ms"]},
+            "phase_ms": None,  # --full
             "first_prepare_s": best["prepare_s"],
             "scale_log2": plan.scale_log2,
-            "roofline": roofline,
+            "roofline": None,  # --full
             "dumped_outputs": dumped,
         }
-        if not args.no_cpu_baseline and world == 1:
-            # the drop-in call itself: host buffers in, host matrix out (H2D, pack, accumulate, normalise,
-            # D2H) -- PCIe-inclusive, never `value`
-            # (the library keeps the call's device buffers for the next call: first and repeated call)
-            t0 = time.perf_counter()
-            secedo_amd.compute_similarity_matrix(p, n_cells, mfl, None, *rates, threads, "", norm)
-            line["one_shot_first_call_s"] = time.perf_counter() - t0
-            t0 = time.perf_counter()
-            secedo_amd.compute_similarity_matrix(p, n_cells, mfl, None, *rates, threads, "", norm)
-            line["one_shot_host_call_s"] = time.perf_counter() - t0
-            # ... and through the C++ shim with the reference's signature (include/secedo_simmat.hpp) from a
-            # vector<vector<PosData>>, as the reference's caller holds the pileup: flatten + H2D + step +
-            # D2H straight into the returned matrix. A child process (tests/cpp/shim_test.cpp, built by make).
-            shim = os.path.join(ROOT, "secedo_amd", "csrc", "build", "shim_test")
-            if os.path.exists(shim) and n_cells <= 16383:
-                try:
-                    r = subprocess.run([shim, "--synth", str(n_cells), str(n_loci), str(n_chr),
-                                        str(300 if args.clustered else gap), repr(prob), "2"],
-                                       capture_output=True, text=True, timeout=600)
-                    line["cpp_dropin_call"] = json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 \
-                        else {"error": r.stderr[-300:]}
-                except (subprocess.SubprocessError, ValueError, IndexError) as e:
-                    line["cpp_dropin_call"] = {"error": str(e)[:300]}
-            line["cpu_baseline"] = cpu_baseline(p, n_cells, mfl, rates, threads, 5e8)
-            if digest is not None and "reference_seconds" in digest.files:
-                # the WHOLE workload through the compiled reference, once, in the build container (8 vCPUs), when
-                # the digest above was made (oracle/gen_golden.py): not a measurement of this run
-                line["cpu_baseline"]["reference_full_workload_s_in_build_container"] = float(digest["reference_seconds"])
+        if extra:
+            line["config"]["replicated_ms_per_step"] = extra.pop("replicated_ms_per_step")
+            line.update(extra)
         emit(line)
     if dist_on:
         dist.barrier()

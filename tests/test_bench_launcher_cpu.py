@@ -41,6 +41,13 @@ def test_bench_default_workload_is_the_headline_configuration():
     assert args.workload == "C3" and args.gpus == 1  # BASELINE.json configs[2]: 8000 cells x 100K loci
 
 
+def test_bench_extras_only_under_full():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False  # a plain run: the headline line only
+    assert bench.parse_args(["--full", "--no-live-counters"]).full is True
+
+
 def test_bench_steps_are_the_timed_steps():
     sys.path.insert(0, ROOT)
     import bench

@@ -4,17 +4,17 @@ set -e
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT/gpurun_out/refresh
 rm -rf $R; mkdir -p $R
-python bench.py --steps 20 --warmup 3 > $R/C2_bench.json 2> $R/C2_bench.err
+python bench.py --full --steps 20 --warmup 3 > $R/C2_bench.json 2> $R/C2_bench.err
 echo "C2 bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_C2 -- python bench.py --steps 20 --warmup 3 > $R/prof_C2.log 2>&1
 cp $(find $R/prof_C2 -name "*kernel_stats.csv" | head -1) $R/C2_kernel_stats.csv
 python tools/kstats.py $R/prof_C2 > $R/C2_kernel_stats_readable.txt
 echo "C2 kernel stats done"
-python bench.py --workload C3 --steps 5 --warmup 2 --no-cpu-baseline > $R/C3_bench.json 2> $R/C3_bench.err
-python bench.py --workload C5 --steps 3 --warmup 1 --no-cpu-baseline > $R/C5_bench.json 2> $R/C5_bench.err
-python bench.py --workload C2 --clustered --steps 10 --warmup 2 --no-cpu-baseline > $R/C2_clustered_bench.json 2> $R/C2c.err
-python bench.py --workload C2 --packed-resident --steps 20 --warmup 3 --no-cpu-baseline > $R/C2_resident_bench.json 2> $R/C2r.err
-python bench.py --workload C3 --packed-resident --steps 5 --warmup 2 --no-cpu-baseline > $R/C3_resident_bench.json 2> $R/C3r.err
+python bench.py --full --workload C3 --steps 5 --warmup 2 --no-cpu-baseline > $R/C3_bench.json 2> $R/C3_bench.err
+python bench.py --full --workload C5 --steps 3 --warmup 1 --no-cpu-baseline > $R/C5_bench.json 2> $R/C5_bench.err
+python bench.py --full --workload C2 --clustered --steps 10 --warmup 2 --no-cpu-baseline > $R/C2_clustered_bench.json 2> $R/C2c.err
+python bench.py --full --workload C2 --packed-resident --steps 20 --warmup 3 --no-cpu-baseline > $R/C2_resident_bench.json 2> $R/C2r.err
+python bench.py --full --workload C3 --packed-resident --steps 5 --warmup 2 --no-cpu-baseline > $R/C3_resident_bench.json 2> $R/C3r.err
 echo "benches done"
 for wl in C2 C3; do
   steps=10; [[ $wl == C3 ]] && steps=3

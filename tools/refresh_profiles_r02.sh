@@ -9,7 +9,7 @@ set -e
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT/gpurun_out/r02
 rm -rf $R; mkdir -p $R
-python bench.py > $R/C3_bench.json 2> $R/C3_bench.err
+python bench.py --full > $R/C3_bench.json 2> $R/C3_bench.err
 echo "C3 bench done"; cat $R/C3_bench.json | head -c 600; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_C3 -- python bench.py --no-cpu-baseline > $R/prof_C3.log 2>&1
 cp $(find $R/prof_C3 -name "*kernel_stats.csv" | head -1) $R/C3_kernel_stats.csv

@@ -17,7 +17,7 @@ tools/lds_atomic_bench.bin --json > $R/lds_atomic_peak.json
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $R/pmc_ldsbench -- tools/lds_atomic_bench.bin --json > /dev/null 2>&1
 python tools/pmc_table.py $R/pmc_ldsbench > $R/lds_atomic_bench_pmc.txt
 rm -rf $R/pmc_ldsbench
-SECEDO_BENCH_NO_CHILD= python bench.py > $R/C3_bench.json 2> $R/C3_bench.err
+SECEDO_BENCH_NO_CHILD= python bench.py --full > $R/C3_bench.json 2> $R/C3_bench.err
 echo "C3 bench done"; head -c 400 $R/C3_bench.json; echo
 stats() {  # name, bench args...
   local name=$1; shift
@@ -41,8 +41,8 @@ tools/pmc.sh r04_c "SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INSTS_BRANCH SQ_TH
 cat $R/pmc_C3_a.txt $R/pmc_C3_b.txt $R/pmc_C3_c.txt > $R/pmc_C3.txt
 echo "pmc done"
 # clustered loci
-SECEDO_BENCH_NO_CHILD= python bench.py --clustered --no-cpu-baseline > $R/C3_clustered_bench.json 2> $R/C3_clustered_bench.err
-SECEDO_BENCH_NO_CHILD= python bench.py --workload C2 --clustered --no-cpu-baseline > $R/C2_clustered_bench.json 2> $R/C2_clustered_bench.err
+SECEDO_BENCH_NO_CHILD= python bench.py --full --clustered --no-cpu-baseline > $R/C3_clustered_bench.json 2> $R/C3_clustered_bench.err
+SECEDO_BENCH_NO_CHILD= python bench.py --full --workload C2 --clustered --no-cpu-baseline > $R/C2_clustered_bench.json 2> $R/C2_clustered_bench.err
 stats C3_clustered --clustered --steps 5
 stats C2_clustered --workload C2 --clustered
 tools/pmc.sh r04_ca "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" --clustered $P > $R/pmc_C3_clustered_a.txt
@@ -50,10 +50,10 @@ tools/pmc.sh r04_cb "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTI
 cat $R/pmc_C3_clustered_a.txt $R/pmc_C3_clustered_b.txt > $R/pmc_C3_clustered.txt
 python tools/counters_json.py $R > $R/counters.json
 cat $R/counters.json
-SECEDO_BENCH_NO_CHILD= python bench.py --workload C2 --no-cpu-baseline > $R/C2_bench.json 2> $R/C2_bench.err
-SECEDO_BENCH_NO_CHILD= python bench.py --workload C5 --no-cpu-baseline --steps 5 > $R/C5_bench.json 2> $R/C5_bench.err
+SECEDO_BENCH_NO_CHILD= python bench.py --full --workload C2 --no-cpu-baseline > $R/C2_bench.json 2> $R/C2_bench.err
+SECEDO_BENCH_NO_CHILD= python bench.py --full --workload C5 --no-cpu-baseline --steps 5 > $R/C5_bench.json 2> $R/C5_bench.err
 # the N > 1 step under a world-size-1 RCCL group (every collective issued), and the one-shot C++ call on 1 / 2 / 4 lanes
-SECEDO_BENCH_NO_CHILD= python bench.py --group --no-cpu-baseline > $R/C3_group_rccl_world1_bench.json 2> $R/C3_group.err
+SECEDO_BENCH_NO_CHILD= python bench.py --full --group --no-cpu-baseline > $R/C3_group_rccl_world1_bench.json 2> $R/C3_group.err
 for g in "" "--gpus 0,0" "--gpus 0,0,0,0"; do
   tag=$(echo "lanes$g" | tr -d ' ,-' | sed 's/gpus//')
   SECEDO_ONE_SHOT_TRACE=1 secedo_amd/csrc/build/shim_test $g --synth 8000 100000 22 30000 0.03 2 > $R/shim_C3_$tag.json 2> $R/shim_C3_$tag.trace
