@@ -1,0 +1,95 @@
+/*
+ * secedo_bam.h -- C-ABI of the pileup creation from aligned reads: the reference's pileup_bams()
+ * (pileup.cpp:49-348, pileup.hpp:29-38). Library libsecedo_bam.so.
+ *
+ * The host memory-maps each BAM, inflates its BGZF blocks with zlib in a thread pool (CRC32 and ISIZE
+ * checked), walks the records and uploads the byte run of the requested chromosome. The per-record decode,
+ * the read-name numbering, the per-position base counts, the locus rule and the entry placement run on the
+ * GPU (secedo_amd/csrc/bam_kernels.hip, which lists the restated semantics). The outputs equal the
+ * reference's run with num_threads = 1: .bin and .map byte for byte, .txt wherever a locus has at most 16
+ * entries. Error codes are those of secedo_simmat.h; secedo_bam_last_error() holds the message.
+ */
+#ifndef SECEDO_BAM_H
+#define SECEDO_BAM_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SECEDO_BAM_MAX_FILES 16384u /* cell_base = cell << 2 | base is a u16 */
+
+/* Header and record summary of one BAM file (host only, no GPU). */
+typedef struct secedo_bam_scan_info {
+    uint32_t n_ref;          /* entries of the @SQ dictionary */
+    uint32_t sorted;         /* 1 if (RefID, Position) never decreases (RefID -1 sorts last) */
+    uint64_t n_records;      /* all records, unmapped ones included */
+    uint64_t n_unmapped;     /* records with RefID -1 */
+    uint64_t n_blocks;       /* BGZF blocks, the empty EOF block included */
+    uint64_t inflated_bytes; /* total ISIZE */
+    uint32_t l_text;         /* length of the SAM header text */
+    uint32_t reserved;
+} secedo_bam_scan_info;
+
+/* Per-step wall times of one call, in ms (inflated_bytes in bytes). */
+typedef struct secedo_bam_times {
+    double inflate_ms;     /* BGZF inflate + CRC32 check, all files */
+    double inflated_bytes;
+    double walk_ms;        /* header parse, record walk, the chromosome's runs concatenated, global ordering */
+    double upload_ms;      /* record bytes and offsets to HBM */
+    double device_ms;      /* every launch and read-back of the device passes */
+    double write_ms;       /* .bin, .map, .txt */
+    double total_ms;
+} secedo_bam_times;
+
+/* Sizes of the last result (see secedo_bam_fetch). */
+typedef struct secedo_bam_result_info {
+    uint64_t n_loci;
+    uint64_t n_entries;
+    uint32_t n_chr;
+    uint32_t num_cells;       /* as secedo_pileup_read reports it on the written .bin (max over chromosomes) */
+    uint32_t max_read_length; /* idem: longest span of one read id between its kept loci */
+    uint32_t reserved;
+} secedo_bam_result_info;
+
+const char *secedo_bam_last_error(void);
+
+/* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
+ * num_threads: inflate pool size, capped at 16 (0 = 1). */
+int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_bam_scan_info *info, uint64_t *records_per_ref,
+                    uint32_t capacity);
+
+/* The reference's pileup_bams() for one chromosome. out_pileup: path prefix of <out>.bin, <out>.map and
+ * <out>.txt (the .txt is created empty unless write_text_file, like the reference), or NULL to write nothing.
+ * The result stays on the device until the next call on this thread; get it with secedo_bam_fetch.
+ * times may be NULL. Synchronous. */
+int secedo_pileup_bams(const char *const *bam_files, uint32_t n_files, const char *out_pileup, int write_text_file,
+                       uint32_t chromosome_id, uint32_t max_coverage, uint32_t min_base_quality,
+                       uint32_t min_map_quality, uint32_t min_alignment_score, uint32_t num_threads,
+                       uint16_t min_different, secedo_bam_result_info *info, secedo_bam_times *times);
+
+/* Several chromosomes in one pass over the files (each file is inflated once); chromosome c of the result is
+ * chromosome_ids[c], its read ids numbered from 0 as in its own pileup_bams() call. id_to_group (host, may be
+ * NULL for the identity) maps cell ids to groups as secedo_pileup_read does: id_base16 = group << 2 | base, a
+ * cell >= n_ids is SECEDO_E_INVALID_ARG. */
+int secedo_pileup_bams_device(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                              uint32_t n_chr, uint32_t max_coverage, uint32_t min_base_quality,
+                              uint32_t min_map_quality, uint32_t min_alignment_score, uint32_t num_threads,
+                              uint16_t min_different, const uint16_t *id_to_group, uint32_t n_ids,
+                              secedo_bam_result_info *info, secedo_bam_times *times);
+
+/* Copies the last result into host or device buffers (any may be NULL): chr_locus_off[n_chr + 1],
+ * locus_pos[n_loci], locus_entry_off[n_loci + 1], read_ids[n_entries], id_base16[n_entries].
+ * The flat layout secedo_simmat_set_pileup_device takes. Synchronous. */
+int secedo_bam_fetch(uint32_t *chr_locus_off, uint32_t *locus_pos, uint64_t *locus_entry_off, uint32_t *read_ids,
+                     uint16_t *id_base16);
+
+/* Frees the device memory of the last result. */
+void secedo_bam_release(void);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* SECEDO_BAM_H */

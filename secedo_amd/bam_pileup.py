@@ -1,0 +1,178 @@
+"""Pileup creation from BAM files (include/secedo_bam.h, libsecedo_bam.so).
+
+Host-side mirror of the reference's ``pileup_bams(bam_files, out_pileup, write_text_file, chromosome_id,
+max_coverage, min_base_quality, min_map_quality, min_alignment_score, num_threads, min_different)``
+(pileup.cpp:235-348). The host inflates the BGZF blocks and walks the records; the per-record decode, the read
+name numbering, the base counts, the locus rule and the entry placement run on the GPU
+(secedo_amd/csrc/bam_kernels.hip). ``bam_scan`` needs no GPU. No CPU fallback for the pileup itself.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .pileup import FlatPileup
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libsecedo_bam.so")
+
+MAX_FILES = 16384
+
+
+class ScanInfo(C.Structure):
+    _fields_ = [("n_ref", C.c_uint32), ("sorted", C.c_uint32), ("n_records", C.c_uint64),
+                ("n_unmapped", C.c_uint64), ("n_blocks", C.c_uint64), ("inflated_bytes", C.c_uint64),
+                ("l_text", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Times(C.Structure):
+    _fields_ = [("inflate_ms", C.c_double), ("inflated_bytes", C.c_double), ("walk_ms", C.c_double),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("write_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+class ResultInfo(C.Structure):
+    _fields_ = [("n_loci", C.c_uint64), ("n_entries", C.c_uint64), ("n_chr", C.c_uint32),
+                ("num_cells", C.c_uint32), ("max_read_length", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_vp = C.c_void_p
+_u32 = C.c_uint32
+_files_t = C.POINTER(C.c_char_p)
+
+SIGNATURES = {
+    "secedo_bam_last_error": (C.c_char_p, []),
+    "secedo_bam_scan": (C.c_int, [C.c_char_p, _u32, C.POINTER(ScanInfo), _vp, _u32]),
+    "secedo_pileup_bams": (C.c_int, [_files_t, _u32, C.c_char_p, C.c_int, _u32, _u32, _u32, _u32, _u32, _u32,
+                                     C.c_uint16, C.POINTER(ResultInfo), C.POINTER(Times)]),
+    "secedo_pileup_bams_device": (C.c_int, [_files_t, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, C.c_uint16,
+                                            _vp, _u32, C.POINTER(ResultInfo), C.POINTER(Times)]),
+    "secedo_bam_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "secedo_bam_release": (None, []),
+}
+
+_bl = None
+
+
+def lib():
+    global _bl
+    if _bl is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError("%s is missing: build it with `make -C secedo_amd/csrc` (there is no fallback "
+                              "implementation)" % LIB_PATH)
+        try:
+            import torch  # noqa: F401  -- one HIP runtime per process: torch's, as in _lib.py
+        except ImportError:
+            pass
+        l = C.CDLL(LIB_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            f = getattr(l, name)
+            f.restype = res
+            f.argtypes = args
+        _bl = l
+    return _bl
+
+
+def check(rc):
+    if rc == _lib.OK:
+        return
+    raise _lib.SecedoError(rc, lib().secedo_bam_last_error().decode(errors="replace"))
+
+
+def _files(bam_files):
+    names = [os.fsencode(str(f)) for f in bam_files]
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    return arr, len(names)
+
+
+def bam_scan(path, num_threads: int = 1, max_refs: int = 4096) -> dict:
+    """Header and record summary of one BAM file, no GPU: n_ref, sorted, n_records, n_unmapped, n_blocks,
+    inflated_bytes, l_text and records_per_ref (one count per @SQ entry)."""
+    info = ScanInfo()
+    per = np.zeros(max_refs, dtype=np.uint64)
+    check(lib().secedo_bam_scan(os.fsencode(str(path)), num_threads, C.byref(info), _lib.ptr(per), max_refs))
+    out = {k: int(getattr(info, k)) for k, _ in ScanInfo._fields_ if k != "reserved"}
+    out["sorted"] = bool(info.sorted)
+    out["records_per_ref"] = per[:min(info.n_ref, max_refs)].copy()
+    return out
+
+
+def _times(t: Times) -> dict:
+    return {k: float(getattr(t, k)) for k, _ in Times._fields_}
+
+
+def _fetch_host(info: ResultInfo) -> FlatPileup:
+    chr_off = np.zeros(info.n_chr + 1, dtype=np.uint32)
+    pos = np.zeros(max(info.n_loci, 1), dtype=np.uint32)
+    off = np.zeros(info.n_loci + 1, dtype=np.uint64)
+    rid = np.zeros(max(info.n_entries, 1), dtype=np.uint32)
+    idb = np.zeros(max(info.n_entries, 1), dtype=np.uint16)
+    check(lib().secedo_bam_fetch(_lib.ptr(chr_off), _lib.ptr(pos), _lib.ptr(off), _lib.ptr(rid), _lib.ptr(idb)))
+    lib().secedo_bam_release()
+    return FlatPileup(chr_off, pos[:info.n_loci], off, rid[:info.n_entries],
+                      idb[:info.n_entries].astype(np.uint32))
+
+
+def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_file: bool, chromosome_id: int,
+                max_coverage: int, min_base_quality: int, min_map_quality: int, min_alignment_score: int,
+                num_threads: int, min_different: int, times: Optional[dict] = None) -> FlatPileup:
+    """The reference's pileup_bams() -> a one-chromosome FlatPileup (id_base = cell << 2 | base). Writes
+    <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms."""
+    arr, n = _files(bam_files)
+    info, t = ResultInfo(), Times()
+    check(lib().secedo_pileup_bams(arr, n, None if out_pileup is None else os.fsencode(str(out_pileup)),
+                                   int(bool(write_text_file)), chromosome_id, max_coverage, min_base_quality,
+                                   min_map_quality, min_alignment_score, num_threads, min_different, C.byref(info),
+                                   C.byref(t)))
+    if times is not None:
+        times.update(_times(t))
+    return _fetch_host(info)
+
+
+def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequence[int], max_coverage: int = 100,
+                         min_base_quality: int = 30, min_map_quality: int = 30, min_alignment_score: int = 0,
+                         num_threads: int = 8, min_different: int = 3, id_to_group=None, group_id_to_pos=None,
+                         times: Optional[dict] = None):
+    """Several chromosomes in one pass over the files, straight into HBM on ``plan``'s device.
+
+    -> (res, num_cells, max_read_length): ``res`` is the resident pileup dict of SimilarityMatrixPlan.upload,
+    which filter_resident, divide_cluster_resident and variant_calling_resident take; num_cells and
+    max_read_length are what read_pileup would report on the written .bin files (maxima over chromosomes)."""
+    import torch
+
+    ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
+    arr, n = _files(bam_files)
+    i2g = None if id_to_group is None else np.ascontiguousarray(id_to_group, dtype=np.uint16)
+    info, t = ResultInfo(), Times()
+    dev = "cuda:%d" % plan.device
+    with torch.cuda.device(plan.device):
+        check(lib().secedo_pileup_bams_device(arr, n, _lib.ptr(ids), len(ids), max_coverage, min_base_quality,
+                                              min_map_quality, min_alignment_score, num_threads, min_different,
+                                              _lib.ptr(i2g) if i2g is not None else None,
+                                              0 if i2g is None else len(i2g), C.byref(info), C.byref(t)))
+        L, E = int(info.n_loci), int(info.n_entries)
+        chr_t = torch.from_numpy(np.zeros(len(ids) + 1, dtype=np.int32)).to(dev)
+        pos_t = torch.empty(max(L, 1), dtype=torch.int32, device=dev)
+        off_t = torch.empty(L + 1, dtype=torch.int64, device=dev)
+        rid_t = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+        idb_t = torch.empty(max(E, 1), dtype=torch.int16, device=dev)
+        torch.cuda.synchronize(dev)
+        check(lib().secedo_bam_fetch(C.c_void_p(chr_t.data_ptr()), C.c_void_p(pos_t.data_ptr()),
+                                     C.c_void_p(off_t.data_ptr()), C.c_void_p(rid_t.data_ptr()),
+                                     C.c_void_p(idb_t.data_ptr())))
+        lib().secedo_bam_release()
+    if times is not None:
+        times.update(_times(t))
+    num_cells = int(info.num_cells)
+    if group_id_to_pos is None:
+        n_groups = int(i2g.max()) + 1 if i2g is not None and len(i2g) else num_cells
+        group_id_to_pos = np.arange(n_groups, dtype=np.uint32)
+    g2p = np.ascontiguousarray(group_id_to_pos, dtype=np.uint32)
+    res = dict(chr=chr_t, pos=pos_t, off=off_t, rid=rid_t, idb=idb_t, idb_is16=True,
+               g2p=torch.from_numpy(g2p.view(np.int32)).to(dev), n_chr=len(ids), n_loci=L, n_entries=E,
+               n_groups=len(g2p))
+    return res, num_cells, int(info.max_read_length)

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""bench_pileup_bams.py -- the pileup creation from BAM files (include/secedo_bam.h) on one GPU, one JSON line.
+
+The set is written once into --dir with tests/bam_writer.uniform_cell_bam (numpy-built records, 16 worker
+processes): --cells cells x --pairs read pairs of 2 x 100 bp on a --mbp Mbp chromosome, a planted variant every
+100 bp carried by the odd cells, so that those loci survive min_different = 3. The line holds the step times of
+the file-writing call (host inflate with its GB/s of inflated bytes, record walk, upload, device passes, file
+writes, end to end) and of the resident call, medians of --repeat runs after one untimed run.
+
+Kernel times come from a run of its own:
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_pileup_bams.py --dir D \
+        --repeat 1 --resident-only
+    python tools/bench_pileup_bams.py --merge LINE.json OUT   # adds per-kernel ms and bytes/s vs HBM peak
+Run every step under a time limit (timeout -k 10 ...)."""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+import time
+from multiprocessing import Pool
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK = 8.0e12
+HBM_MEASURED = 6.29e12
+
+
+_GENOME = {}
+
+
+def _one(args):
+    from tests import bam_writer as bw
+    path, cell, mbp, pairs, seed = args
+    if (mbp, seed) not in _GENOME:  # once per worker process
+        rng = np.random.default_rng(seed)
+        L = int(mbp * 1_000_000)
+        genome = rng.integers(0, 4, L).astype(np.int64)
+        mask = np.zeros(L, dtype=bool)
+        mask[50::100] = True
+        _GENOME[(mbp, seed)] = (genome, (genome + 1) % 4, mask)
+    genome, alt, mask = _GENOME[(mbp, seed)]
+    return bw.uniform_cell_bam(path, cell, genome, alt, mask, pairs, seed=seed)
+
+
+def write_set(d, cells, pairs, mbp, seed=7):
+    os.makedirs(d, exist_ok=True)
+    paths = [os.path.join(d, "cell%05d_x.bam" % c) for c in range(cells)]
+    stamp = os.path.join(d, "set.json")
+    want = dict(cells=cells, pairs=pairs, mbp=mbp, seed=seed)
+    if os.path.exists(stamp) and json.load(open(stamp)) == want:
+        return paths, 0.0
+    t0 = time.time()
+    with Pool(16) as pool:
+        pool.map(_one, [(p, c, mbp, pairs, seed) for c, p in enumerate(paths)], chunksize=4)
+    json.dump(want, open(stamp, "w"))
+    return paths, time.time() - t0
+
+
+def merge(line_path, prof_dir):
+    line = json.loads(open(line_path).read().strip().splitlines()[-1])
+    f = sorted(glob.glob(os.path.join(prof_dir, "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)[-1]
+    kernels, total = {}, 0.0
+    for r in csv.DictReader(open(f)):
+        name = r["Name"]
+        if "secedo::bam" not in name and "rocprim" not in name:
+            continue
+        short = name.replace("secedo::bam::(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        if "rocprim" in name:
+            short = "rocprim_" + ("radix_sort" if "radix_sort" in name else "scan" if "scan" in name else "other")
+        ms = float(r["TotalDurationNs"]) / 1e6
+        k = kernels.setdefault(short, dict(calls=0, ms=0.0))
+        k["calls"] += int(r["Calls"])
+        k["ms"] = round(k["ms"] + ms, 3)
+        total += ms
+    calls = kernels["k_decode"]["calls"]  # pileup calls in the profiled run (one decode launch each)
+    line["kernels"] = kernels
+    line["profiled_calls"] = calls
+    line["kernel_ms_per_call"] = round(total / calls, 3)
+    # compulsory bytes of one call: the uploaded records read by decode, count and emit, the counts written and
+    # read per window position (16 B each way), the entries written
+    by = 3 * line["record_bytes"] + 32 * line["window_positions"] + 6 * line["entries"]
+    line["compulsory_bytes"] = by
+    line["achieved_bytes_per_s"] = by / (line["kernel_ms_per_call"] * 1e-3)
+    line["fraction_of_hbm_peak"] = line["achieved_bytes_per_s"] / HBM_PEAK
+    line["fraction_of_hbm_measured"] = line["achieved_bytes_per_s"] / HBM_MEASURED
+    print(json.dumps(line))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dir", default="/tmp/secedo_bam_bench")
+    ap.add_argument("--cells", type=int, default=2000)
+    ap.add_argument("--pairs", type=int, default=2000)
+    ap.add_argument("--mbp", type=float, default=10.0)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--resident-only", action="store_true")
+    ap.add_argument("--merge", nargs=2, metavar=("LINE", "PROF_DIR"))
+    a = ap.parse_args()
+    if a.merge:
+        merge(*a.merge)
+        return
+    paths, gen_s = write_set(a.dir, a.cells, a.pairs, a.mbp)
+    import secedo_amd
+    from secedo_amd import bam_pileup
+
+    med = lambda xs: float(np.median(xs))
+    out = os.path.join(a.dir, "out")
+    line = dict(workload="uniform", cells=a.cells, pairs=a.pairs, mbp=a.mbp, threads=a.threads,
+                set_write_s=round(gen_s, 1), bam_bytes=sum(os.path.getsize(p) for p in paths))
+    if not a.resident_only:
+        runs = []
+        for k in range(a.repeat + 1):
+            t = {}
+            p = bam_pileup.pileup_bams(paths, out, True, 0, 100, 30, 30, 0, a.threads, 3, times=t)
+            if k:
+                runs.append(t)
+        for key in ("inflate_ms", "walk_ms", "upload_ms", "device_ms", "write_ms", "total_ms"):
+            line[key] = round(med([r[key] for r in runs]), 2)
+        line["inflated_bytes"] = runs[0]["inflated_bytes"]
+        line["inflate_GBps"] = line["inflated_bytes"] / (line["inflate_ms"] * 1e-3) / 1e9
+        line.update(loci=p.n_loci, entries=p.n_entries)
+    with secedo_amd.SimilarityMatrixPlan(0) as plan:
+        rt = []
+        for k in range(a.repeat + 1):
+            t = {}
+            res, cells, max_len = bam_pileup.pileup_bams_resident(plan, paths, [0], 100, 30, 30, 0, a.threads, 3,
+                                                                  times=t)
+            if k:
+                rt.append(t)
+    line["resident_total_ms"] = round(med([r["total_ms"] for r in rt]), 2)
+    line["resident_device_ms"] = round(med([r["device_ms"] for r in rt]), 2)
+    line.update(loci=res["n_loci"], entries=res["n_entries"], num_cells=cells, max_read_length=max_len)
+    n_rec = a.cells * a.pairs * 2
+    line["records"] = n_rec
+    line["record_bytes"] = n_rec * 211  # uniform_cell_bam's fixed record size
+    line["window_positions"] = int(a.mbp * 1_000_000)
+    print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
