@@ -149,7 +149,7 @@ struct secedo_simmat {
     uint32_t num_tiles = 0;
     DevBuf tile_row, tile_col, lut, counters, max_bits, slow_args, slab, plan_wg_tile, plan_wg_begin;
     uint32_t plan_tile_begin = 0xFFFFFFFFu, plan_tile_end = 0, plan_ranges = 0, plan_blocks = 0, plan_workgroups = 0;
-    DevBuf flag_tmp, flag_pre, flag_grp, flag_rec, flag_idx;  // sparse-loci path: the flagged entries, compact
+    DevBuf flag_tmp, flag_grp, flag_rec, flag_idx;            // sparse-loci path: the flagged entries, compact
     bool flags_ready = false;                                 // ... of the current packed pileup
     bool wide_known = false;                                  // clustered loci: the reads that reach beyond their windows ...
     uint32_t n_wide = 0;                                      // ... their entries, listed per cell block
@@ -183,7 +183,6 @@ struct secedo_simmat {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_mid = nullptr;
     bool timed_mid = false;
     bool timed = false;
-    secedo::SideStream side;  // the flagged entries' lists are built beside accumulate_counts (created on first use)
     bool last_fused = false;  // the last accumulate corrected its tiles in accumulate_counts' epilogue
 };
 
@@ -452,9 +451,6 @@ void secedo_simmat_destroy(secedo_simmat_t *h) {
     if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
     if (h->ev_end) (void)hipEventDestroy(h->ev_end);
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
-    if (h->side.fork) (void)hipEventDestroy(h->side.fork);
-    if (h->side.join) (void)hipEventDestroy(h->side.join);
-    if (h->side.stream) (void)hipStreamDestroy(h->side.stream);
     h->uploads.destroy();
     delete h;
 }
@@ -688,10 +684,8 @@ int secedo_simmat_prepare(secedo_simmat_t *h, uint32_t num_cells, uint32_t max_f
     h->flags_ready = false;
     h->wide_known = false;
     // The sparse-loci path's lists of the flagged entries, as the last step of the packing and on its stream: the
-    // pair kernel's epilogue reads them (SECEDO_FLAGS_FROM_PACK=0: built by the first accumulate instead,
-    // build_flagged_lists, for A/B runs)
-    static const bool from_pack = [] { const char *e = std::getenv("SECEDO_FLAGS_FROM_PACK"); return !(e && std::atoi(e) == 0); }();
-    if (from_pack && pk.count_tile && !pk.stage_masks && secedo::counts_path_enabled() && pk.num_entries) {
+    // pair kernel's epilogue and correct_tiles read them
+    if (pk.count_tile && !pk.stage_masks && pk.num_entries) {
         const uint32_t ne = (uint32_t)pk.num_entries;
         const size_t n_off = (size_t)pk.num_blocks * (pk.num_loci + 1);
         HIP_TRY(h->flag_tmp.ensure(secedo::flag_list_scratch_bytes(ne)));
@@ -760,35 +754,122 @@ int secedo_simmat_zero_acc(secedo_simmat_t *h, int64_t *d_acc, void *stream) {
     return SECEDO_OK;
 }
 
-
-// The compact lists of the flagged entries (build_flagged_lists), issued on `stream`: the launch stream itself, or
-// the handle's side stream -- then behind the fork event and followed by the join event.
-struct FlagBuild {
-    secedo_simmat *h = nullptr;
-    const uint32_t *entry32 = nullptr, *blk_off = nullptr;
-    const uint4 *entry = nullptr;
-    uint32_t ne = 0;
-    size_t n_off = 0;
-    hipStream_t stream = nullptr;
-    bool done = false;
-    static hipError_t run(void *ctx) {
-        FlagBuild *b = static_cast<FlagBuild *>(ctx);
-        secedo_simmat *h = b->h;
-        const bool on_side = h->side.stream && b->stream == h->side.stream;
-        hipError_t e = hipSuccess;
-        if (on_side && (e = hipStreamWaitEvent(b->stream, h->side.fork, 0)) != hipSuccess) return e;
-        e = secedo::build_flagged_lists(b->entry32, b->entry, b->ne, b->blk_off, b->n_off, h->flag_tmp.p, h->flag_tmp.bytes,
-                                        h->flag_pre.as<uint32_t>(), h->flag_grp.as<uint32_t>(), h->flag_rec.as<uint4>(),
-                                        h->flag_idx.as<uint32_t>(), b->stream);
-        if (e == hipSuccess && on_side) e = hipEventRecord(h->side.join, b->stream);
-        b->done = true;
-        return e;
-    }
-};
-
 // capacity of the list of read pairs beyond the table per launch (16 bytes each; allocated only for a pileup with a
 // read of more than 128 kept entries)
 constexpr uint32_t kBeyondCap = 1u << 20;
+
+// Workgroups: every tile is cut into chunks of locus ranges so that the launch fills the 256 CUs
+// in whole rounds of about equally loaded workgroups (a diagonal tile holds half the pairs of an
+// off-diagonal one and gets half the chunks). Cached per tile range.
+static int plan_workgroups(secedo_simmat_t *h, uint32_t tile_begin, uint32_t tile_end, const uint32_t *list,
+                           uint64_t list_hash, hipStream_t s) {
+    const uint32_t n_tiles = tile_end - tile_begin;
+    if (h->plan_tile_begin != tile_begin || h->plan_tile_end != tile_end || h->plan_ranges != h->pk.num_ranges
+        || h->plan_blocks != h->pk.num_blocks || h->plan_list_hash != list_hash) {
+        // workgroups resident per CU (LDS-limited): 1 (128-cell tiles), 2 (64-cell tiles with staged masks,
+        // 512 threads), 4 (the other 64-cell variants)
+        // (the 64-cell count tile runs accumulate_counts with 512 threads and 59 KiB of LDS: two per CU)
+        const uint32_t wgs_per_round = h->pk.block_cells == 128 ? 256u : (h->pk.stage_masks || h->pk.count_tile) ? 512u : 1024u;
+        uint32_t rounds = 1;
+        if (const char *env = std::getenv("SECEDO_ROUNDS")) rounds = std::max(1, std::atoi(env));
+        // weight of a tile = the time it takes: per row-side entry a fixed part (the batch set-up) and a
+        // part per column entry of the same locus (the pairs; half of them in a diagonal tile). Fitted to
+        // the per-workgroup times on C2: the fixed part is worth 5.7 pairs.
+        const uint32_t Bc = h->pk.block_cells;
+        auto cells_of = [&](uint32_t blk) { return (double)std::min(Bc, h->pk.num_cells - blk * Bc); };
+        const double per_cell_locus = h->pk.num_loci ? (double)h->pk.num_entries / h->pk.num_cells / h->pk.num_loci : 0.0;
+        std::vector<double> weight(n_tiles);
+        double total_weight = 0;
+        for (uint32_t k = 0; k < n_tiles; ++k) {
+            const uint32_t t = list ? list[k] : tile_begin + k;
+            const uint32_t I = h->host_tile_row[t], J = h->host_tile_col[t];
+            const double depth = per_cell_locus * cells_of(J) * (I == J ? 0.5 : 1.0);  // column entries per locus
+            weight[k] = cells_of(I) * (5.7 + depth);
+            total_weight += weight[k];
+        }
+        // whole rounds of workgroups, shared out so that the slowest chunk is as fast as possible: every
+        // tile starts with one chunk and the next one always goes to the tile whose chunks are heaviest
+        const uint64_t slots = static_cast<uint64_t>(wgs_per_round) * std::max<uint64_t>(rounds, (n_tiles + wgs_per_round - 1) / wgs_per_round);
+        const uint32_t max_chunks = std::max(1u, h->pk.num_ranges);
+        std::vector<uint32_t> chunks(n_tiles, 1u);
+        if (total_weight > 0 && n_tiles < slots && n_tiles <= 2 * wgs_per_round) {  // more tiles: one workgroup each
+            std::priority_queue<std::pair<double, uint32_t>> heaviest;  // (weight per chunk, tile)
+            for (uint32_t k = 0; k < n_tiles; ++k) heaviest.push({weight[k], k});
+            for (uint64_t given = n_tiles; given < slots && !heaviest.empty();) {
+                const uint32_t k = heaviest.top().second;
+                heaviest.pop();
+                if (chunks[k] >= max_chunks) continue;  // one range per chunk at least
+                ++chunks[k];
+                ++given;
+                heaviest.push({weight[k] / chunks[k], k});
+            }
+        }
+        std::vector<uint32_t> wg_begin(n_tiles + 1, 0);
+        std::vector<uint32_t> wg_tile;
+        for (uint32_t t = 0; t < n_tiles; ++t) {
+            wg_begin[t + 1] = wg_begin[t] + chunks[t];
+            for (uint32_t k = 0; k < chunks[t]; ++k) wg_tile.push_back(t);
+        }
+        // (a larger plan than any before: the buffers grow, and hipFree waits for the device; otherwise the new plan
+        // follows the launches that read the old one in stream order)
+        HIP_TRY(h->plan_wg_tile.ensure(wg_tile.size() * 4));
+        HIP_TRY(h->plan_wg_begin.ensure(wg_begin.size() * 4));
+        HIP_TRY(h->uploads.put(h->plan_wg_tile.p, wg_tile.data(), wg_tile.size() * 4, s));
+        HIP_TRY(h->uploads.put(h->plan_wg_begin.p, wg_begin.data(), wg_begin.size() * 4, s));
+        h->plan_workgroups = wg_begin[n_tiles];
+        h->plan_tile_begin = tile_begin;
+        h->plan_tile_end = tile_end;
+        h->plan_list_hash = list_hash;
+        h->plan_ranges = h->pk.num_ranges;
+        h->plan_blocks = h->pk.num_blocks;
+    }
+    return SECEDO_OK;
+}
+
+// The read pairs of a launch that share more than 128 loci, as the kernels noted them: the call waits for the launch
+// here (only a pileup with a read of more than 128 kept entries comes this way), evaluates the distinct (x_s, x_d) as
+// the reference does and adds the terms
+static int add_beyond_terms(secedo_simmat_t *h, double eps, double hr, double theta, int64_t *d_acc, hipStream_t s) {
+    uint32_t n_noted = 0;
+    HIP_TRY(hipMemcpyAsync(&n_noted, h->beyond_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (n_noted > kBeyondCap)
+        return fail(SECEDO_E_LIMIT, std::to_string(n_noted) + " read pairs of this launch share more than 128 loci (at most "
+                                    + std::to_string(kBeyondCap) + " per launch: accumulate fewer tiles at a time, or set "
+                                    "SECEDO_LLR_EXACT=1 for the formula in exact arithmetic)");
+    if (n_noted) {
+        std::vector<uint32_t> noted((size_t)n_noted * 4);
+        HIP_TRY(hipMemcpy(noted.data(), h->beyond_list.p, noted.size() * 4, hipMemcpyDeviceToHost));
+        const uint32_t Bc = h->pk.block_cells, nb = h->pk.num_blocks;
+        std::vector<unsigned long long> index(n_noted);
+        std::vector<long long> value(n_noted);
+        for (uint32_t k = 0; k < n_noted; ++k) {
+            uint32_t ca = noted[(size_t)k * 4], cb = noted[(size_t)k * 4 + 1];
+            const uint32_t xs = noted[(size_t)k * 4 + 2], xd = noted[(size_t)k * 4 + 3];
+            if (ca / Bc > cb / Bc) std::swap(ca, cb);  // the tile's row block is the smaller one
+            const uint32_t I = ca / Bc, J = cb / Bc;
+            const uint64_t tile = (uint64_t)I * nb - (uint64_t)I * (I - 1) / 2 + (J - I);  // row-major upper triangle
+            if (ca >= h->pk.num_cells || cb >= h->pk.num_cells || tile >= h->num_tiles || h->host_tile_row[tile] != I
+                || h->host_tile_col[tile] != J)
+                return fail(SECEDO_E_STATE, "a noted read pair lies outside the matrix");
+            const double d = secedo::reference_llr_any(eps, hr, theta, xs, xd, std::max(1u, h->num_threads));
+            if (!std::isfinite(d) || std::fabs(std::ldexp(d, h->scale_log2)) >= 0x1p62)
+                return fail(SECEDO_E_INVALID_ARG, "a read pair sharing " + std::to_string(xs + xd) + " loci has a non-finite "
+                                                  "log-likelihood ratio in the reference's arithmetic (it would write "
+                                                  "inf / NaN into the matrix); SECEDO_LLR_EXACT=1 selects the exact formula");
+            index[k] = tile * Bc * Bc + (uint64_t)(ca % Bc) * Bc + (cb % Bc);
+            value[k] = std::llround(std::ldexp(d, h->scale_log2));
+        }
+        HIP_TRY(h->beyond_index.ensure((size_t)n_noted * 8));
+        HIP_TRY(h->beyond_value.ensure((size_t)n_noted * 8));
+        HIP_TRY(hipMemcpyAsync(h->beyond_index.p, index.data(), (size_t)n_noted * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(h->beyond_value.p, value.data(), (size_t)n_noted * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(secedo::launch_add_terms(d_acc, h->beyond_index.as<unsigned long long>(), h->beyond_value.as<long long>(),
+                                         n_noted, s));
+        HIP_TRY(hipStreamSynchronize(s));  // (the sources are this frame's vectors)
+    }
+    return SECEDO_OK;
+}
 
 // tiles [tile_begin, tile_end) when list == nullptr, else the n_list tiles of `list` (global indices)
 // overwrite: acc[tiles of the launch] = result instead of +=
@@ -926,68 +1007,7 @@ static int accumulate_impl(secedo_simmat_t *h, double eps, double hr, double the
         }
         a.tile_ids = h->tile_ids.as<uint32_t>();
     }
-    // Workgroups: every tile is cut into chunks of locus ranges so that the launch fills the 256 CUs
-    // in whole rounds of about equally loaded workgroups (a diagonal tile holds half the pairs of an
-    // off-diagonal one and gets half the chunks). Cached per tile range.
-    if (h->plan_tile_begin != tile_begin || h->plan_tile_end != tile_end || h->plan_ranges != h->pk.num_ranges
-        || h->plan_blocks != h->pk.num_blocks || h->plan_list_hash != list_hash) {
-        // workgroups resident per CU (LDS-limited): 1 (128-cell tiles), 2 (64-cell tiles with staged masks,
-        // 512 threads), 4 (the other 64-cell variants)
-        // (the 64-cell count tile runs accumulate_counts with 512 threads and 59 KiB of LDS: two per CU)
-        const uint32_t wgs_per_round = h->pk.block_cells == 128 ? 256u : (h->pk.stage_masks || h->pk.count_tile) ? 512u : 1024u;
-        uint32_t rounds = 1;
-        if (const char *env = std::getenv("SECEDO_ROUNDS")) rounds = std::max(1, std::atoi(env));
-        // weight of a tile = the time it takes: per row-side entry a fixed part (the batch set-up) and a
-        // part per column entry of the same locus (the pairs; half of them in a diagonal tile). Fitted to
-        // the per-workgroup times on C2: the fixed part is worth 5.7 pairs.
-        const uint32_t Bc = h->pk.block_cells;
-        auto cells_of = [&](uint32_t blk) { return (double)std::min(Bc, h->pk.num_cells - blk * Bc); };
-        const double per_cell_locus = h->pk.num_loci ? (double)h->pk.num_entries / h->pk.num_cells / h->pk.num_loci : 0.0;
-        std::vector<double> weight(n_tiles);
-        double total_weight = 0;
-        for (uint32_t k = 0; k < n_tiles; ++k) {
-            const uint32_t t = list ? list[k] : tile_begin + k;
-            const uint32_t I = h->host_tile_row[t], J = h->host_tile_col[t];
-            const double depth = per_cell_locus * cells_of(J) * (I == J ? 0.5 : 1.0);  // column entries per locus
-            weight[k] = cells_of(I) * (5.7 + depth);
-            total_weight += weight[k];
-        }
-        // whole rounds of workgroups, shared out so that the slowest chunk is as fast as possible: every
-        // tile starts with one chunk and the next one always goes to the tile whose chunks are heaviest
-        const uint64_t slots = static_cast<uint64_t>(wgs_per_round) * std::max<uint64_t>(rounds, (n_tiles + wgs_per_round - 1) / wgs_per_round);
-        const uint32_t max_chunks = std::max(1u, h->pk.num_ranges);
-        std::vector<uint32_t> chunks(n_tiles, 1u);
-        if (total_weight > 0 && n_tiles < slots && n_tiles <= 2 * wgs_per_round) {  // more tiles: one workgroup each
-            std::priority_queue<std::pair<double, uint32_t>> heaviest;  // (weight per chunk, tile)
-            for (uint32_t k = 0; k < n_tiles; ++k) heaviest.push({weight[k], k});
-            for (uint64_t given = n_tiles; given < slots && !heaviest.empty();) {
-                const uint32_t k = heaviest.top().second;
-                heaviest.pop();
-                if (chunks[k] >= max_chunks) continue;  // one range per chunk at least
-                ++chunks[k];
-                ++given;
-                heaviest.push({weight[k] / chunks[k], k});
-            }
-        }
-        std::vector<uint32_t> wg_begin(n_tiles + 1, 0);
-        std::vector<uint32_t> wg_tile;
-        for (uint32_t t = 0; t < n_tiles; ++t) {
-            wg_begin[t + 1] = wg_begin[t] + chunks[t];
-            for (uint32_t k = 0; k < chunks[t]; ++k) wg_tile.push_back(t);
-        }
-        // (a larger plan than any before: the buffers grow, and hipFree waits for the device; otherwise the new plan
-        // follows the launches that read the old one in stream order)
-        HIP_TRY(h->plan_wg_tile.ensure(wg_tile.size() * 4));
-        HIP_TRY(h->plan_wg_begin.ensure(wg_begin.size() * 4));
-        HIP_TRY(h->uploads.put(h->plan_wg_tile.p, wg_tile.data(), wg_tile.size() * 4, s));
-        HIP_TRY(h->uploads.put(h->plan_wg_begin.p, wg_begin.data(), wg_begin.size() * 4, s));
-        h->plan_workgroups = wg_begin[n_tiles];
-        h->plan_tile_begin = tile_begin;
-        h->plan_tile_end = tile_end;
-        h->plan_list_hash = list_hash;
-        h->plan_ranges = h->pk.num_ranges;
-        h->plan_blocks = h->pk.num_blocks;
-    }
+    if (const int rc = plan_workgroups(h, tile_begin, tile_end, list, list_hash, s); rc != SECEDO_OK) return rc;
     a.n_tiles = n_tiles;
     a.n_workgroups = h->plan_workgroups;
     a.wg_tile = h->plan_wg_tile.as<uint32_t>();
@@ -1000,7 +1020,7 @@ static int accumulate_impl(secedo_simmat_t *h, double eps, double hr, double the
     a.overwrite = overwrite;
     // the maximum finalize needs, on the way (assign_finalize: all tiles, stored, one workgroup per tile)
     if (max_done && !beyond && overwrite && !list && tile_begin == 0 && tile_end == h->num_tiles && h->pk.count_tile
-        && !h->pk.stage_masks && secedo::counts_path_enabled() && secedo::counts_split(n_tiles) == 1) {
+        && !h->pk.stage_masks && secedo::counts_split(n_tiles) == 1) {
         HIP_TRY(hipMemsetAsync(h->max_bits.p, 0, sizeof(unsigned long long), s));
         a.max_bits = h->max_bits.as<unsigned long long>();
         a.max_scale = std::ldexp(1.0, -h->scale_log2);
@@ -1048,13 +1068,13 @@ static int accumulate_impl(secedo_simmat_t *h, double eps, double hr, double the
 
     HIP_TRY(hipMemsetAsync(h->counters.p, 0, 96 * sizeof(unsigned long long), s));
     if (beyond) HIP_TRY(hipMemsetAsync(h->beyond_count.p, 0, sizeof(uint32_t), s));
-    const secedo::SideStream *side = nullptr;
-    secedo::SideStream side_call;
-    FlagBuild build;
     h->last_fused = false;
-    if (h->pk.count_tile && !h->pk.stage_masks && secedo::counts_path_enabled()) {
-        // accumulate_counts, and correct_tiles or the pair kernel's own epilogue: the epilogue when every tile of the
-        // launch has one workgroup and correct_tiles would have one per tile too (SECEDO_CORRECT_FUSED=0: never)
+    if (h->pk.count_tile && !h->pk.stage_masks) {
+        // accumulate_counts, and correct_tiles or the pair kernel's own epilogue; both read the flagged entries' lists,
+        // which prepare builds with the packing
+        if (!h->flags_ready) return fail(SECEDO_E_STATE, "the flagged entries' lists were not built");
+        // the epilogue when every tile of the launch has one workgroup and correct_tiles would have one per tile too
+        // (SECEDO_CORRECT_FUSED=0: never)
         static const bool fused_env = [] {
             const char *e = std::getenv("SECEDO_CORRECT_FUSED");
             return !(e && std::atoi(e) == 0);
@@ -1062,114 +1082,23 @@ static int accumulate_impl(secedo_simmat_t *h, double eps, double hr, double the
         a.fused = fused_env && h->plan_workgroups == n_tiles
                   && (secedo::counts_split(n_tiles) == 1u || (overwrite && list != nullptr));
         h->last_fused = a.fused;
-        // The compact list of flagged entries, once per prepare, comes with the packing. Otherwise it is built here,
-        // and when correct_tiles reads it it is built on a stream of the handle's own while the pair kernel runs
-        static const bool serial = [] {
-            const char *e = std::getenv("SECEDO_CORRECT_SERIAL");
-            return e && std::atoi(e) != 0;
-        }();
-        if (!serial && !a.fused) {
-            if (!h->side.stream) {
-                HIP_TRY(hipStreamCreateWithFlags(&h->side.stream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&h->side.fork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&h->side.join, hipEventDisableTiming));
-            }
-            side = &h->side;
-        }
-        if (!h->flags_ready) {
-            const uint32_t ne = (uint32_t)h->pk.num_entries;
-            const size_t scan_bytes = secedo::flagged_scan_bytes(ne);
-            HIP_TRY(h->flag_tmp.ensure(std::max<size_t>(scan_bytes, 16)));
-            HIP_TRY(h->flag_pre.ensure(((size_t)ne + 1) * 4));
-            HIP_TRY(h->flag_rec.ensure(std::max<size_t>(ne, 1) * 16));
-            HIP_TRY(h->flag_idx.ensure(std::max<size_t>(ne, 1) * 4));
-            const size_t n_off = (size_t)h->pk.num_blocks * a.stride;
-            HIP_TRY(h->flag_grp.ensure(std::max<size_t>(n_off, 1) * 4));
-            build.h = h;
-            build.entry32 = a.entry32;
-            build.entry = a.entry;
-            build.blk_off = a.blk_off;
-            build.ne = ne;
-            build.n_off = n_off;
-            if (side) {
-                // the lists depend on the packed pileup (complete on `s` by now) and are read by correct_tiles
-                // only: the host enqueues their kernels behind the pair kernel's launch, on the side stream
-                HIP_TRY(hipEventRecord(side->fork, s));
-                build.stream = side->stream;
-                side_call = *side;
-                side_call.deferred = &FlagBuild::run;
-                side_call.deferred_ctx = &build;
-                side = &side_call;
-            } else {
-                build.stream = s;
-                if (FlagBuild::run(&build) != hipSuccess) return fail(SECEDO_E_HIP, "building the flagged entries' lists failed");
-            }
-            // (flags_ready is set once the lists' kernels have been ISSUED without an error, below: a launch that
-            // fails in between must not leave the next accumulate reading lists nobody built -- ADVICE r03)
-        }
         a.flag_grp = h->flag_grp.as<uint32_t>();
         a.flag_rec = h->flag_rec.as<uint4>();
         a.flag_idx = h->flag_idx.as<uint32_t>();
-        {
-            const double per_block_locus = h->pk.num_loci && h->pk.num_blocks
-                    ? (double)h->pk.num_entries / h->pk.num_loci / h->pk.num_blocks : 0.0;
-            a.group_hint = per_block_locus < 2.5 ? 2 : per_block_locus < 3.2 ? 3 : 4;
-        }
+        const double per_block_locus = h->pk.num_loci && h->pk.num_blocks
+                ? (double)h->pk.num_entries / h->pk.num_loci / h->pk.num_blocks : 0.0;
+        a.group_hint = per_block_locus < 2.5 ? 2 : per_block_locus < 3.2 ? 3 : 4;
     }
     HIP_TRY(hipEventRecord(h->ev_begin, s));
     // 16-bit pair counters per cell pair are safe when no cell pair can collect 65536 pairs
     const bool count_tile = h->pk.count_tile;
     HIP_TRY(h->slab.ensure(secedo::accumulate_slab_bytes(h->pk.block_cells, count_tile, a.n_workgroups)));
     a.slab = h->slab.p;
-    h->timed_mid = count_tile && !h->pk.stage_masks && secedo::counts_path_enabled();
-    HIP_TRY(secedo::launch_accumulate(a, h->pk.block_cells, h->pk.stage_masks, count_tile, n_tiles, s, side,
+    h->timed_mid = count_tile && !h->pk.stage_masks;
+    HIP_TRY(secedo::launch_accumulate(a, h->pk.block_cells, h->pk.stage_masks, count_tile, n_tiles, s,
                                       h->timed_mid ? h->ev_mid : nullptr));
-    if (build.h && build.stream != s && !build.done) {  // no tile in the launch: nobody issued the lists yet
-        if (FlagBuild::run(&build) != hipSuccess) return fail(SECEDO_E_HIP, "building the flagged entries' lists failed");
-        HIP_TRY(hipStreamWaitEvent(s, h->side.join, 0));
-    }
-    if (build.h && build.done) h->flags_ready = true;
     if (beyond) {
-        // the pairs the kernels noted: the call waits for the launch here (only a pileup with a read of more than 128
-        // kept entries comes this way), evaluates the distinct (x_s, x_d) as the reference does and adds the terms
-        uint32_t n_noted = 0;
-        HIP_TRY(hipMemcpyAsync(&n_noted, h->beyond_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (n_noted > kBeyondCap)
-            return fail(SECEDO_E_LIMIT, std::to_string(n_noted) + " read pairs of this launch share more than 128 loci (at most "
-                                        + std::to_string(kBeyondCap) + " per launch: accumulate fewer tiles at a time, or set "
-                                        "SECEDO_LLR_EXACT=1 for the formula in exact arithmetic)");
-        if (n_noted) {
-            std::vector<uint32_t> noted((size_t)n_noted * 4);
-            HIP_TRY(hipMemcpy(noted.data(), h->beyond_list.p, noted.size() * 4, hipMemcpyDeviceToHost));
-            const uint32_t Bc = h->pk.block_cells, nb = h->pk.num_blocks;
-            std::vector<unsigned long long> index(n_noted);
-            std::vector<long long> value(n_noted);
-            for (uint32_t k = 0; k < n_noted; ++k) {
-                uint32_t ca = noted[(size_t)k * 4], cb = noted[(size_t)k * 4 + 1];
-                const uint32_t xs = noted[(size_t)k * 4 + 2], xd = noted[(size_t)k * 4 + 3];
-                if (ca / Bc > cb / Bc) std::swap(ca, cb);  // the tile's row block is the smaller one
-                const uint32_t I = ca / Bc, J = cb / Bc;
-                const uint64_t tile = (uint64_t)I * nb - (uint64_t)I * (I - 1) / 2 + (J - I);  // row-major upper triangle
-                if (ca >= h->pk.num_cells || cb >= h->pk.num_cells || tile >= h->num_tiles || h->host_tile_row[tile] != I
-                    || h->host_tile_col[tile] != J)
-                    return fail(SECEDO_E_STATE, "a noted read pair lies outside the matrix");
-                const double d = secedo::reference_llr_any(eps, hr, theta, xs, xd, std::max(1u, h->num_threads));
-                if (!std::isfinite(d) || std::fabs(std::ldexp(d, h->scale_log2)) >= 0x1p62)
-                    return fail(SECEDO_E_INVALID_ARG, "a read pair sharing " + std::to_string(xs + xd) + " loci has a non-finite "
-                                                      "log-likelihood ratio in the reference's arithmetic (it would write "
-                                                      "inf / NaN into the matrix); SECEDO_LLR_EXACT=1 selects the exact formula");
-                index[k] = tile * Bc * Bc + (uint64_t)(ca % Bc) * Bc + (cb % Bc);
-                value[k] = std::llround(std::ldexp(d, h->scale_log2));
-            }
-            HIP_TRY(h->beyond_index.ensure((size_t)n_noted * 8));
-            HIP_TRY(h->beyond_value.ensure((size_t)n_noted * 8));
-            HIP_TRY(hipMemcpyAsync(h->beyond_index.p, index.data(), (size_t)n_noted * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(h->beyond_value.p, value.data(), (size_t)n_noted * 8, hipMemcpyHostToDevice, s));
-            HIP_TRY(secedo::launch_add_terms(d_acc, h->beyond_index.as<unsigned long long>(), h->beyond_value.as<long long>(),
-                                             n_noted, s));
-            HIP_TRY(hipStreamSynchronize(s));  // (the sources are this frame's vectors)
-        }
+        if (const int rc = add_beyond_terms(h, eps, hr, theta, d_acc, s); rc != SECEDO_OK) return rc;
     }
     h->timed_mid = h->timed_mid && n_tiles > 0;
     HIP_TRY(hipEventRecord(h->ev_end, s));
@@ -1381,7 +1310,7 @@ int secedo_simmat_last_accumulate_ms(secedo_simmat_t *h, float *ms) {
 
 const char *secedo_simmat_pair_kernel(const secedo_simmat_t *h) {
     if (!h || !h->prepared) return "";
-    if (h->pk.count_tile && !h->pk.stage_masks && secedo::counts_path_enabled()) return "accumulate_counts";
+    if (h->pk.count_tile && !h->pk.stage_masks) return "accumulate_counts";
     if (h->pk.stage_masks && h->pk.block_cells == 64 && h->pk.num_blocks <= 1024u) {
         const char *e = std::getenv("SECEDO_MASKS_KERNEL");
         if (!(e && std::atoi(e) == 0)) return "accumulate_masks";

@@ -12,10 +12,8 @@
 #include "simmat_kernels.hpp"
 
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 namespace secedo {
@@ -139,10 +137,10 @@ __device__ __noinline__ long long pair_value_full(const SlowPathArgs *sp, uint32
 
 // Capacity of the per-wave list of deferred joint pairs (see accumulate_tiles): 192 where the LDS
 // budget allows, else 0 (the batch is rescanned for its joint pairs instead).
-template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS, bool COUNTS>
+template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS>
 constexpr int joint_list_cap() {
     if (MASKS) return 0;
-    constexpr size_t fixed = (size_t)B * B * (COUNTS ? 4 : 8) + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2 + 16
+    constexpr size_t fixed = (size_t)B * B * 8 + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2 + 16
             + (size_t)(THREADS / 64) * ((size_t)HCAP + 64 * 8);
     return fixed + (size_t)(THREADS / 64) * 192 * 10 <= 160 * 1024 ? 192 : 0;
 }
@@ -150,11 +148,6 @@ constexpr int joint_list_cap() {
 // MASKS:  the 8-locus window masks are staged too, so joint (x_s, x_d) terms of multi-locus read
 //         pairs are evaluated from LDS (clustered loci); otherwise such pairs go through the full
 //         entries in HBM (they are rare when loci are sparse).
-// COUNTS: the tile holds two 16-bit pair counters per cell pair (matching | mismatching single-
-//         locus pairs, one ds_add_u32 each) instead of an int64 sum; the workgroup converts them
-//         to fixed point when it flushes (exact integer arithmetic, so the result is bit-identical
-//         to the int64 tile). Needs < 65536 pairs per cell pair, which the host guarantees from
-//         the pileup's pair bound; joint terms bypass the tile (global atomics).
 // HCAP:   size of the per-wave strip in which a batch's pairs are flattened over the lanes (below);
 //         deeper batches are flattened HCAP pairs at a time.
 //
@@ -164,14 +157,13 @@ constexpr int joint_list_cap() {
 // the batch's pairs are FLATTENED: a wave prefix sum over c gives every entry a slice [P, P + c) of
 // the batch's T pairs, the slice is filled with the owning lane's number in a per-wave LDS strip,
 // and pair p is then handled by lane p % 64 -- every lane busy until the batch's last 64 pairs.
-template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS, bool COUNTS>
+template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS>
 __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs a) {
-    static_assert(!(MASKS && COUNTS), "the count tile is for the sparse-loci variant");
-    constexpr size_t TILE_BYTES = (size_t)B * B * (COUNTS ? 4 : 8);
+    constexpr size_t TILE_BYTES = (size_t)B * B * 8;
     constexpr int WAVES = THREADS / 64;
     constexpr int JPT = (CAPJ + THREADS - 1) / THREADS;      // staged column entries per thread
     constexpr int OPT = (CAPL + 1 + THREADS - 1) / THREADS;  // staged offsets per thread
-    constexpr int MCAP = joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP, MASKS, COUNTS>();
+    constexpr int MCAP = joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP, MASKS>();
     constexpr size_t WAVE_BYTES = (size_t)HCAP + 64 * 8 + (MASKS ? 64 * 4 : 0) + (size_t)MCAP * 10;
 
     // LDS: [ tile | sJ CAPJ u16 | sOff CAPL+2 u16 | sJm CAPJ u32, sLut (MASKS) | s_next | per wave:
@@ -179,7 +171,6 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
     //        mlist MCAP x {g1, g2}, mcell MCAP u16 (sparse-loci variants: deferred joint pairs) ]
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     unsigned long long *tile64 = reinterpret_cast<unsigned long long *>(lds_raw);
-    uint32_t *tile32 = reinterpret_cast<uint32_t *>(lds_raw);
     uint16_t *sJ = reinterpret_cast<uint16_t *>(lds_raw + TILE_BYTES);
     uint16_t *sOff = sJ + CAPJ;
     uint32_t *sJm = reinterpret_cast<uint32_t *>(sOff + CAPL + 2);
@@ -231,11 +222,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
         row_end = __builtin_amdgcn_readfirstlane(row_end);
     }
 
-    if (COUNTS) {
-        for (uint32_t i = tid; i < B * B; i += THREADS) tile32[i] = 0u;
-    } else {
-        for (uint32_t i = tid; i < B * B; i += THREADS) tile64[i] = 0ull;
-    }
+    for (uint32_t i = tid; i < B * B; i += THREADS) tile64[i] = 0ull;
     if (MASKS) {
         for (uint32_t i = tid; i < SLUT_DIM * SLUT_DIM; i += THREADS)
             sLut[i] = a.lut[(i / SLUT_DIM) * LUT_DIM + (i % SLUT_DIM)];
@@ -263,7 +250,6 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
             const uint2 g = mlist[q];
             const long long v = pair_value_full(a.slow, g.x, g.y);
             if (v == NO_PAIR) ++skipped_list;
-            else if (COUNTS) atomicAdd(&dst[mcell[q]], (unsigned long long)v);
             else atomicAdd(&tile64[mcell[q]], (unsigned long long)v);
         }
         __builtin_amdgcn_wave_barrier();
@@ -302,14 +288,8 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                 v = pair_value_full(a.slow, g1, g2);
                 owner_here = (v != NO_PAIR);
             }
-            if (owner_here) {
-                if (COUNTS) atomicAdd(&dst[cell], (unsigned long long)v);
-                else atomicAdd(&tile64[cell], (unsigned long long)v);
-            } else {
-                ++skipped;
-            }
-        } else if (COUNTS) {
-            atomicAdd(&tile32[cell], differ ? 0x10000u : 1u);
+            if (owner_here) atomicAdd(&tile64[cell], (unsigned long long)v);
+            else ++skipped;
         } else {
             atomicAdd(&tile64[cell], (unsigned long long)(differ ? d01 : d10));
         }
@@ -509,8 +489,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                                 }
                                 if ((a.debug & 1u) == 0u && ok && (both & C_MULTI) == 0u) {
                                     const bool differ = (x & (3u << C_BASE_SHIFT)) != 0u;
-                                    if (COUNTS) atomicAdd(&tile32[cell], differ ? 0x10000u : 1u);
-                                    else atomicAdd(&tile64[cell], (unsigned long long)(differ ? d01 : d10));
+                                    atomicAdd(&tile64[cell], (unsigned long long)(differ ? d01 : d10));
                                 }
                             }
                         };
@@ -542,7 +521,6 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                                     const long long v = pair_value_full(a.slow, ib + cur * 64u + o, jb + jc);
                                     const uint32_t cell = (ro.x >> 16) + (w & C_CELL);
                                     if (v == NO_PAIR) ++skipped;
-                                    else if (COUNTS) atomicAdd(&dst[cell], (unsigned long long)v);
                                     else atomicAdd(&tile64[cell], (unsigned long long)v);
                                 }
                             }
@@ -626,11 +604,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
 
     // flush: the workgroup's tile goes to its own slab with plain coalesced stores; reduce_slabs adds
     // the slabs of a tile into the accumulator (joint terms and deep ranges went there directly)
-    if (COUNTS) {
-        uint4 *out = reinterpret_cast<uint4 *>(reinterpret_cast<uint32_t *>(a.slab) + (size_t)blockIdx.x * B * B);
-        const uint4 *src = reinterpret_cast<const uint4 *>(tile32);
-        for (uint32_t i = tid; i < B * B / 4; i += THREADS) out[i] = src[i];
-    } else {
+    {
         uint4 *out = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned long long *>(a.slab) + (size_t)blockIdx.x * B * B);
         const uint4 *src = reinterpret_cast<const uint4 *>(tile64);
         for (uint32_t i = tid; i < B * B / 2; i += THREADS) out[i] = src[i];
@@ -735,18 +709,20 @@ constexpr uint32_t IT_REC_MASK = 0x1FFu;  // cell (7 bits) | base (2 bits)
 //   C3 (3.8 entries per cell block and locus): - / 3.31 / 3.13 / 3.02 for GROUP 1 / 2 / 3 / 4
 //   C5 (1.3):                                 31.4 / 30.6 / 31.6 / -
 // (with seven vector instructions per slot, before col32, the empty slots of GROUP 4 cost more than the trips
-// through the ring: 4.87 / 4.49 / 4.38 / 5.62 on C3.) 4 by default, 2 below 2.5 entries per block and locus.
-// SLOT_ASM: the pair slot as five hand-placed instructions between one s_and_saveexec and one s_mov exec. From the
-// C++ form the compiler builds, per slot, saveexec + a branch around the (out-of-line) body + s_or exec + the test
-// of the wave-uniform `diag` flag with its branch: five scalar / branch instructions for three vector ones and
-// the ds_add -- 0.63e9 scalar instructions per C3 launch through the ONE scalar unit of a CU, 2.3e8 branches.
+// through the ring: 4.87 / 4.49 / 4.38 / 5.62 on C3.) 4 by default, 2 below 2.5 entries per block and locus,
+// 3 below 3.2 (AccumulateArgs::group_hint); GROUP 1, 5, 6 and 8 were measured, dropped and then deleted.
+// Off the diagonal the pair slot is five hand-placed instructions between one s_and_saveexec and one s_mov exec.
+// From the C++ form (pair_slot, which diagonal tiles keep) the compiler builds, per slot, saveexec + a branch around
+// the (out-of-line) body + s_or exec + the test of the wave-uniform `diag` flag with its branch: five scalar / branch
+// instructions for three vector ones and the ds_add -- 0.63e9 scalar instructions per C3 launch through the ONE
+// scalar unit of a CU, 2.3e8 branches.
 template <int B, int THREADS, int NCNT>
 __device__ __forceinline__ void correct_epilogue(const AccumulateArgs &a, unsigned char *lds, uint32_t t_local,
                                                  const uint32_t (&cnt)[NCNT]);
-template <int B, int THREADS, int CAPJ, int CAPL, int GROUP, bool SLOT_ASM>
+template <int B, int THREADS, int CAPJ, int CAPL, int GROUP>
 __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArgs a) {
     static_assert(CAPJ <= 16384, "14 bits of column index in an item");
-    static_assert(GROUP >= 1 && GROUP <= 8, "group size");
+    static_assert(GROUP >= 2 && GROUP <= 4, "group size");
     // Rows of the LDS tile are B + 1 words apart: the lanes of a wave that share a locus add to the SAME column
     // (their common column entry) in DIFFERENT rows, and with a row stride of B words all of them would hit one
     // bank (bank = column mod 32): 3-4 lanes deep at every locus, on top of the random collisions.
@@ -893,7 +869,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                 atomicAdd(reinterpret_cast<uint32_t *>(lds_raw + addr),
                           (w >> 16) != (rec9 >> C_BASE_SHIFT) ? 0x10000u : 1u);
         };
-        // SLOT_ASM, tiles off the diagonal (all but one in num_blocks): exec = in; same base? (third byte of w
+        // the slot by hand, tiles off the diagonal (all but one in num_blocks): exec = in; same base? (third byte of w
         // against the row entry's base); address = row + low half of w; 1 or 0x10000; ds_add; exec back. (The
         // s_nop covers the SDWA compare's write of vcc before v_cndmask reads it, as in the compiler's own
         // sequence. lgkmcnt: the compiler does not see this ds_add; LDS returns in order, so its counted waits
@@ -936,7 +912,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
             for (int u = 0; u < GROUP; ++u) in[u] = __ballot(c > (uint32_t)u);
             const unsigned long long more = __ballot(c > (uint32_t)GROUP);
             // (the wave-uniform `diag` flag is tested once per group, not once per slot)
-            if (SLOT_ASM && !DIAG && (GROUP == 4 || GROUP == 2)) {
+            if (!DIAG && (GROUP == 4 || GROUP == 2)) {
                 // The slots of a group as ONE block (round 4): the compares, addresses and values of all slots under
                 // the group's exec -- a lane that does not take part computes garbage nobody adds --, each compare
                 // into a scalar pair of its own, and only the ds_add under the slot's lanes. Per slot that is one
@@ -998,7 +974,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                                  : "memory");
                     (void)a2; (void)a3; (void)v2; (void)v3; (void)q2; (void)q3;
                 }
-            } else if (SLOT_ASM && !DIAG) {
+            } else if (!DIAG) {
                 const uint32_t rbase = rec9 >> C_BASE_SHIFT, row_addr = lds_base + row_byte;
 #pragma unroll
                 for (int u = 0; u < GROUP; ++u) pair_slot_asm(rbase, row_addr, w[u], in[u]);
@@ -1270,7 +1246,7 @@ static_assert((C_TAIL << 15) == MX_TAIL && (C_WIDE << 15) == MX_DEAD, "flag posi
 template <int B, int THREADS, int CAPJ, int CAPL, int GROUP>
 __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs a) {
     static_assert(CAPJ <= 4096, "12 bits of column index in an item");
-        static_assert(GROUP >= 1 && GROUP <= 4, "group size");
+    static_assert(GROUP == 3, "pair_group3_asm pairs three slots");
     // rows of the int64 tile are B + 1 words apart: lanes that share a locus hold the same column entry and
     // different rows, and with a row stride of 512 bytes they all met in one pair of banks (52 % of the LDS
     // cycles were conflict cycles on C3 clustered, 22 % since); the flush takes the skew out again
@@ -1333,7 +1309,6 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
     }
 
     unsigned long long *dst = reinterpret_cast<unsigned long long *>(a.acc) + (size_t)t * B * B;
-    const bool slot_asm = a.masks_slot_asm != 0u;   // (SECEDO_MASKS_SLOT_ASM=0: the compiler's slot, for A/B runs)
     unsigned long long n_updates = 0, n_pairs = 0;  // per lane
     uint32_t upd_lane = 0, add_lane = 0;            // this lane's incidences / owned incidences in the range
     uint32_t ring_head = 0, ring_tail = 0;          // wave-uniform, free-running
@@ -1512,8 +1487,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
     };
     auto pair_dispatch = [&](uint32_t item, uint32_t x1, uint32_t y1, const uint2 (&w2)[GROUP], uint32_t c) {
         if (DIAG) pair_group(std::true_type{}, item, x1, y1, w2, c);
-        else if (GROUP == 3 && slot_asm) pair_group3_asm(item, x1, y1, w2, c);
-        else pair_group(std::false_type{}, item, x1, y1, w2, c);
+        else pair_group3_asm(item, x1, y1, w2, c);
     };
     // `more`: the lanes whose item goes on, `adv` column entries further
     auto ring_push = [&](unsigned long long more, uint32_t item, uint32_t x1, uint32_t y1, uint32_t adv) {
@@ -1852,33 +1826,6 @@ __global__ __launch_bounds__(256) void wide_pairs(const WideArgs a) {
         atomicAdd(&a.counters[0], u);
         atomicAdd(&a.counters[1], q);
     }
-}
-
-// ---- the flagged entries (tail: the read was never flushed; multi: the read has further kept entries), compacted
-// in the order of the packed entries, i.e. by (cell block, locus): pre[d] = flagged entries before entry d, so
-// the flagged entries of the group (b, l) are [pre[blk_off[b][l]], pre[blk_off[b][l + 1]]) of the compact list
-struct FlaggedOp {  // input of the prefix sum
-    const uint32_t *entry32;
-    uint32_t n;
-    __device__ __forceinline__ uint32_t operator()(uint32_t d) const {
-        return (d < n && (entry32[d] & (C_TAIL | C_MULTI)) != 0u) ? 1u : 0u;
-    }
-};
-__global__ __launch_bounds__(256) void flagged_compact(const uint32_t *entry32, const uint4 *entry, uint32_t n,
-                                                      const uint32_t *pre, uint4 *rec, uint32_t *idx) {
-    for (uint32_t d = blockIdx.x * 256 + threadIdx.x; d < n; d += gridDim.x * 256)
-        if (entry32[d] & (C_TAIL | C_MULTI)) {
-            const uint32_t i = pre[d];
-            rec[i] = entry[d];
-            idx[i] = d;
-        }
-}
-
-// ... and per (block, locus) group the number of flagged entries before it
-__global__ __launch_bounds__(256) void flagged_groups(const uint32_t *blk_off, size_t n_off, const uint32_t *pre,
-                                                     uint32_t *grp) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_off; i += (size_t)gridDim.x * 256)
-        grp[i] = pre[blk_off[i]];
 }
 
 // x_s, x_d over all loci two multi-locus reads share, packed (values, not out-parameters: those would live
@@ -2314,9 +2261,9 @@ __device__ __forceinline__ void correct_epilogue(const AccumulateArgs &a, unsign
     correct_tile<B, THREADS, 1, true>(c, corr, scorr, part, t_local, 0u, t, d10, d01, none, false);
 }
 
-// acc[tile] += sum over the tile's workgroups of their slab (count slabs are converted with the two
-// single-locus ratios: exact integer arithmetic). One thread per cell pair of a tile.
-template <int B, bool COUNTS>
+// acc[tile] += sum over the tile's workgroups of their int64 slab. One thread per cell pair of a tile. (`lut` is
+// unused since the count slabs went; without it the compiler numbers the kernel's scalar registers differently.)
+template <int B>
 __global__ __launch_bounds__(256) void reduce_slabs(const void *slab, const uint32_t *tile_wg_begin,
                                                    uint32_t tile_begin, const uint32_t *tile_ids,
                                                    const long long *lut, long long *acc) {
@@ -2326,20 +2273,8 @@ __global__ __launch_bounds__(256) void reduce_slabs(const void *slab, const uint
     const uint32_t cell = (blockIdx.x % (B * B / 256)) * 256 + threadIdx.x;
     const uint32_t w0 = tile_wg_begin[t_local], w1 = tile_wg_begin[t_local + 1];
     long long sum = 0;
-    if (COUNTS) {
-        const long long d10 = lut[1 * LUT_DIM + 0], d01 = lut[0 * LUT_DIM + 1];
-        const uint32_t *p = reinterpret_cast<const uint32_t *>(slab) + cell;
-        uint32_t same = 0, diff = 0;
-        for (uint32_t w = w0; w < w1; ++w) {
-            const uint32_t v = p[(size_t)w * B * B];
-            same += v & 0xFFFFu;
-            diff += v >> 16;
-        }
-        sum = (long long)same * d10 + (long long)diff * d01;
-    } else {
-        const long long *p = reinterpret_cast<const long long *>(slab) + cell;
-        for (uint32_t w = w0; w < w1; ++w) sum += p[(size_t)w * B * B];
-    }
+    const long long *p = reinterpret_cast<const long long *>(slab) + cell;
+    for (uint32_t w = w0; w < w1; ++w) sum += p[(size_t)w * B * B];
     long long *dst = &acc[(size_t)(tile_ids ? tile_ids[t_local] : tile_begin + t_local) * B * B + cell];
     if (sum) *dst += sum;
 }
@@ -2430,15 +2365,15 @@ __global__ __launch_bounds__(256) void write_matrix(const long long *acc, const 
     }
 }
 
-template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS, bool COUNTS>
+template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS>
 hipError_t launch_acc(const AccumulateArgs &args, uint32_t grid, hipStream_t stream) {
-    constexpr size_t lds = (size_t)B * B * (COUNTS ? 4 : 8) + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2
+    constexpr size_t lds = (size_t)B * B * 8 + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2
             + (MASKS ? (size_t)CAPJ * 4 + SLUT_DIM * SLUT_DIM * 8 : 0) + 16
             + (size_t)(THREADS / 64) * ((size_t)HCAP + 64 * 8 + (MASKS ? 64 * 4 : 0)
-                                        + (size_t)joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP, MASKS, COUNTS>() * 10);
+                                        + (size_t)joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP, MASKS>() * 10);
     static_assert(lds <= 160 * 1024, "LDS budget");
     static_assert((CAPL + 2) % 4 == 0 && CAPJ % 8 == 0 && HCAP % 16 == 0, "alignment of the LDS carve-up");
-    auto kern = &accumulate_tiles<B, THREADS, CAPJ, CAPL, HCAP, MASKS, COUNTS>;
+    auto kern = &accumulate_tiles<B, THREADS, CAPJ, CAPL, HCAP, MASKS>;
     static thread_local int configured_device = -1;  // the attribute is per device and sticky
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -2450,14 +2385,14 @@ hipError_t launch_acc(const AccumulateArgs &args, uint32_t grid, hipStream_t str
         configured_device = dev;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, args);
-    hipLaunchKernelGGL((reduce_slabs<B, COUNTS>), dim3(args.n_tiles * (B * B / 256)), dim3(256), 0, stream,
+    hipLaunchKernelGGL((reduce_slabs<B>), dim3(args.n_tiles * (B * B / 256)), dim3(256), 0, stream,
                        args.slab, args.tile_wg_begin, args.tile_begin, args.tile_ids, args.lut,
                        reinterpret_cast<long long *>(args.acc));
     return hipGetLastError();
 }
 
 template <int B>
-hipError_t launch_correct(const AccumulateArgs &args, hipStream_t stream, const SideStream *side);
+hipError_t launch_correct(const AccumulateArgs &args, hipStream_t stream);
 
 template <int B, int THREADS, int CAPJ, int CAPL, int GROUP>
 hipError_t launch_masks(const AccumulateArgs &args, uint32_t grid, hipStream_t stream) {
@@ -2476,11 +2411,8 @@ hipError_t launch_masks(const AccumulateArgs &args, uint32_t grid, hipStream_t s
         if (e != hipSuccess) return e;
         configured_device = dev;
     }
-    static const bool slot_asm = [] { const char *v = std::getenv("SECEDO_MASKS_SLOT_ASM"); return !(v && std::atoi(v) == 0); }();
-    AccumulateArgs with_flag = args;
-    with_flag.masks_slot_asm = slot_asm ? 1u : 0u;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, with_flag);
-    hipLaunchKernelGGL((reduce_slabs<B, false>), dim3(args.n_tiles * (B * B / 256)), dim3(256), 0, stream, args.slab,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, args);
+    hipLaunchKernelGGL((reduce_slabs<B>), dim3(args.n_tiles * (B * B / 256)), dim3(256), 0, stream, args.slab,
                        args.tile_wg_begin, args.tile_begin, args.tile_ids, args.lut,
                        reinterpret_cast<long long *>(args.acc));
     if (args.wide_list) {  // the pairs of reads that reach beyond their windows
@@ -2504,14 +2436,13 @@ hipError_t launch_masks(const AccumulateArgs &args, uint32_t grid, hipStream_t s
     return hipGetLastError();
 }
 
-template <int B, int THREADS, int CAPJ, int CAPL, int GROUP, bool SLOT_ASM>
-hipError_t launch_counts_v(const AccumulateArgs &args, uint32_t grid, hipStream_t stream, const SideStream *side,
-                           hipEvent_t mid) {
+template <int B, int THREADS, int CAPJ, int CAPL, int GROUP>
+hipError_t launch_counts(const AccumulateArgs &args, uint32_t grid, hipStream_t stream, hipEvent_t mid) {
     constexpr size_t lds = ((size_t)B * (B + 1) * 4 + 15) / 16 * 16 + (size_t)CAPJ * 4 + ((size_t)CAPL + 2) * 2
             + (size_t)(THREADS / 64) * (size_t)COUNTS_RING * 4;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static_assert((CAPL + 2) % 4 == 0 && CAPJ % 8 == 0, "alignment of the LDS carve-up");
-    auto kern = &accumulate_counts<B, THREADS, CAPJ, CAPL, GROUP, SLOT_ASM>;
+    auto kern = &accumulate_counts<B, THREADS, CAPJ, CAPL, GROUP>;
     static thread_local int configured_device = -1;  // the attribute is per device and sticky
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -2527,30 +2458,16 @@ hipError_t launch_counts_v(const AccumulateArgs &args, uint32_t grid, hipStream_
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, args);
     if (mid && (e = hipEventRecord(mid, stream)) != hipSuccess) return e;
     if (args.fused) return hipGetLastError();  // the correction was the pair kernel's epilogue
-    if (side && side->deferred && (e = side->deferred(side->deferred_ctx)) != hipSuccess) return e;
-    return launch_correct<B>(args, stream, side);
-}
-
-// (SECEDO_SLOT_ASM=0: the compiler's pair slot, for A/B measurements)
-template <int B, int THREADS, int CAPJ, int CAPL, int GROUP>
-hipError_t launch_counts(const AccumulateArgs &args, uint32_t grid, hipStream_t stream, const SideStream *side,
-                         hipEvent_t mid) {
-    static const bool slot_asm = [] { const char *e = std::getenv("SECEDO_SLOT_ASM"); return !(e && std::atoi(e) == 0); }();
-    return slot_asm ? launch_counts_v<B, THREADS, CAPJ, CAPL, GROUP, true>(args, grid, stream, side, mid)
-                    : launch_counts_v<B, THREADS, CAPJ, CAPL, GROUP, false>(args, grid, stream, side, mid);
+    return launch_correct<B>(args, stream);
 }
 
 // The second kernel of the sparse-loci path, after the pair kernel.
 template <int B>
-hipError_t launch_correct(const AccumulateArgs &args, hipStream_t stream, const SideStream *side) {
+hipError_t launch_correct(const AccumulateArgs &args, hipStream_t stream) {
     hipError_t e = hipSuccess;
     int dev = 0;
     if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
     // What the flags of the reads mean, and the count tiles' way into the accumulator: one workgroup per tile.
-    // The flagged entries' lists may still be in the making on the side stream (build_flagged_lists).
-    if (side && side->stream) {
-        if ((e = hipStreamWaitEvent(stream, side->join, 0)) != hipSuccess) return e;
-    }
     CorrectArgs c = correct_args(args);
     constexpr int CT = B == 128 ? 1024 : 256;
     constexpr size_t corr_lds = (size_t)B * B * 8;
@@ -2586,48 +2503,10 @@ __global__ __launch_bounds__(256) void zero_tiles(long long *acc, const uint32_t
     }
 }
 
-int pair_mode() {
-    static const int mode = [] {
-        const char *e = std::getenv("SECEDO_PAIR_MODE");
-        return e ? std::atoi(e) : 1;
-    }();
-    return mode;
-}
-
 }  // namespace
-
-bool counts_path_enabled() { return pair_mode() != 0; }
 
 // (few tiles: several workgroups each, as many as fit one round of the chip's 256 CUs)
 uint32_t counts_split(uint32_t n_tiles) { return std::max(1u, std::min(8u, 256u / std::max(n_tiles, 1u))); }
-
-size_t flagged_scan_bytes(uint32_t n_entries) {
-    size_t bytes = 0;
-    hipcub::CountingInputIterator<uint32_t> ids(0u);
-    hipcub::TransformInputIterator<uint32_t, FlaggedOp, hipcub::CountingInputIterator<uint32_t>> in(
-            ids, FlaggedOp{nullptr, 0});
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, static_cast<uint32_t *>(nullptr), (int)n_entries + 1);
-    return bytes;
-}
-
-hipError_t build_flagged_lists(const uint32_t *entry32, const uint4 *entry, uint32_t n_entries,
-                               const uint32_t *blk_off, size_t n_off, void *scan_tmp, size_t scan_tmp_bytes,
-                               uint32_t *pre, uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream) {
-    hipcub::CountingInputIterator<uint32_t> ids(0u);
-    hipcub::TransformInputIterator<uint32_t, FlaggedOp, hipcub::CountingInputIterator<uint32_t>> in(
-            ids, FlaggedOp{entry32, n_entries});
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_tmp_bytes, in, pre, (int)n_entries + 1, stream);
-    if (e != hipSuccess) return e;
-    if (n_entries) {
-        const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)n_entries + 255) / 256, 256 * 32);
-        hipLaunchKernelGGL(flagged_compact, dim3(blocks), dim3(256), 0, stream, entry32, entry, n_entries, pre, rec, idx);
-    }
-    if (n_off) {
-        const uint32_t blocks = (uint32_t)std::min<size_t>((n_off + 255) / 256, 256 * 32);
-        hipLaunchKernelGGL(flagged_groups, dim3(blocks), dim3(256), 0, stream, blk_off, n_off, pre, grp);
-    }
-    return hipGetLastError();
-}
 
 hipError_t masks_words(const uint32_t *entry32, const uint32_t *mask32, uint32_t n_entries, uint32_t *y, uint32_t *xcol,
                        uint32_t *xrow, hipStream_t stream) {
@@ -2664,11 +2543,10 @@ StageGeometry stage_geometry(uint32_t block_cells) {
 }
 
 hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, bool stage_masks,
-                             bool count_tile, uint32_t n_tiles, hipStream_t stream, const SideStream *side,
-                             hipEvent_t mid) {
+                             bool count_tile, uint32_t n_tiles, hipStream_t stream, hipEvent_t mid) {
     if (n_tiles == 0) return hipSuccess;
     const uint32_t grid = args.n_workgroups;
-    const bool counts_path = count_tile && !stage_masks && pair_mode() != 0;
+    const bool counts_path = count_tile && !stage_masks;
     if (args.overwrite && !counts_path) {  // (accumulate_counts + correct_tiles store the tiles themselves)
         const uint32_t tile_elems = block_cells * block_cells;
         if (args.tile_ids) {
@@ -2682,35 +2560,19 @@ hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, b
     }
     if (block_cells == 128) {
         // the 128 KiB int64 tile leaves no room for the window masks: joint terms go through HBM
-        if (count_tile && pair_mode() != 0) {
-            static const int g = [] { const char *e = std::getenv("SECEDO_GROUP"); return e ? std::atoi(e) : 0; }();
-            if (g == 1) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 1>(args, grid, stream, side, mid);
-            if (g == 5) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 5>(args, grid, stream, side, mid);
-            if (g == 6) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 6>(args, grid, stream, side, mid);
-            if (g == 8) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 8>(args, grid, stream, side, mid);
-            if (g == 3) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 3>(args, grid, stream, side, mid);
-            if (g == 4) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 4>(args, grid, stream, side, mid);
-            if (g == 2 || (g == 0 && args.group_hint == 2))
-                return launch_counts<128, 1024, kCapJ128C, kCapL128C, 2>(args, grid, stream, side, mid);
-            if (g == 0 && args.group_hint == 3)
-                return launch_counts<128, 1024, kCapJ128C, kCapL128C, 3>(args, grid, stream, side, mid);
-            return launch_counts<128, 1024, kCapJ128C, kCapL128C, 4>(args, grid, stream, side, mid);
+        if (count_tile) {
+            if (args.group_hint == 2) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 2>(args, grid, stream, mid);
+            if (args.group_hint == 3) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 3>(args, grid, stream, mid);
+            return launch_counts<128, 1024, kCapJ128C, kCapL128C, 4>(args, grid, stream, mid);
         }
-        if (count_tile) return launch_acc<128, 1024, kCapJ128C, kCapL128C, 1024, false, true>(args, grid, stream);
-        return launch_acc<128, 1024, kCapJ128, kCapL128, 512, false, false>(args, grid, stream);
+        return launch_acc<128, 1024, kCapJ128, kCapL128, 512, false>(args, grid, stream);
     }
-    if (stage_masks && args.masks_kernel) {
-        // column entries per item and pass: C2 clustered (9 entries per cell block and locus) 1.160 / 1.143 / 1.111 ms
-        // of accumulate with 4 / 2 / 3
-        static const int g = [] { const char *e = std::getenv("SECEDO_MASKS_GROUP"); return e ? std::atoi(e) : 3; }();
-        if (g == 2) return launch_masks<64, 512, kCapJ64M, kCapL64M, 2>(args, grid, stream);
-        if (g == 4) return launch_masks<64, 512, kCapJ64M, kCapL64M, 4>(args, grid, stream);
-        return launch_masks<64, 512, kCapJ64M, kCapL64M, 3>(args, grid, stream);
-    }
-    if (stage_masks) return launch_acc<64, 512, kCapJ64M, kCapL64M, 1024, true, false>(args, grid, stream);
-    if (count_tile && pair_mode() != 0) return launch_counts<64, 512, kCapJ64C, kCapL64C, 4>(args, grid, stream, side, mid);
-    if (count_tile) return launch_acc<64, 256, kCapJ64C, kCapL64C, 1024, false, true>(args, grid, stream);
-    return launch_acc<64, 256, kCapJ64, kCapL64, 1024, false, false>(args, grid, stream);
+    // accumulate_masks pairs an item with 3 column entries per pass: C2 clustered (9 entries per cell block and locus)
+    // 1.160 / 1.143 / 1.111 ms of accumulate with 4 / 2 / 3 (measured, dropped and then deleted)
+    if (stage_masks && args.masks_kernel) return launch_masks<64, 512, kCapJ64M, kCapL64M, 3>(args, grid, stream);
+    if (stage_masks) return launch_acc<64, 512, kCapJ64M, kCapL64M, 1024, true>(args, grid, stream);
+    if (count_tile) return launch_counts<64, 512, kCapJ64C, kCapL64C, 4>(args, grid, stream, mid);
+    return launch_acc<64, 256, kCapJ64, kCapL64, 1024, false>(args, grid, stream);
 }
 
 __global__ void k_add_terms(long long *acc, const unsigned long long *index, const long long *value, uint32_t n) {

@@ -73,14 +73,13 @@ struct AccumulateArgs {
     int64_t *acc;              // tile-major: [tile][B*B]
     void *slab;                // one B*B tile (u32 counts or int64) per workgroup of the launch
     unsigned long long *counters;  // [0] incidences examined, [1] read pairs accumulated
-    // the sparse-loci path (accumulate_counts + correct_tiles): the flagged entries, compact (build_flagged_lists)
+    // the sparse-loci path (accumulate_counts + correct_tiles): the flagged entries, compact (pack_flag_lists)
     const uint32_t *flag_grp = nullptr;     // num_blocks * stride: flagged entries before each (block, locus) group
     const uint4 *flag_rec = nullptr;        // their full entries ...
     const uint32_t *flag_idx = nullptr;     // ... and entry indices
     int group_hint = 4;                     // GROUP of accumulate_counts by the entries per (cell block, locus)
     bool overwrite = false;                 // acc[tiles of the launch] = result (no need to zero them first)
     bool masks_kernel = false;              // staged masks: accumulate_masks (+ wide_pairs) instead of accumulate_tiles
-    uint32_t masks_slot_asm = 1;            // accumulate_masks: the hand-written pair slots (SECEDO_MASKS_SLOT_ASM=0: off)
     const uint32_t *mk_y = nullptr, *mk_xcol = nullptr, *mk_xrow = nullptr;  // ... the entries' words (masks_words)
     const uint32_t *wide_off = nullptr;     // num_blocks + 1: the C_WIDE entries per cell block ...
     const uint32_t *wide_list = nullptr;    // ... their entry indices (null: none)
@@ -94,20 +93,8 @@ struct AccumulateArgs {
     bool fused = false;
 };
 
-// true when the count-tile variants run accumulate_counts + correct_tiles (the default; SECEDO_PAIR_MODE=0
-// selects the flattening kernel accumulate_tiles instead, for A/B measurements)
-bool counts_path_enabled();
 // workgroups per tile of correct_tiles for a launch of n_tiles
 uint32_t counts_split(uint32_t n_tiles);
-// The entries whose read is flagged (never flushed, or covering further loci), compacted in entry order --
-// which is (cell block, locus) order -- for correct_tiles: pre[n_entries + 1] (exclusive prefix of the flag,
-// scratch), grp[n_off] = pre at the n_off group offsets blk_off[], rec[] / idx[] = the flagged entries' records
-// and indices (room for n_entries each). scan_tmp: at least flagged_scan_bytes(n_entries). Depends on the packed
-// pileup only.
-size_t flagged_scan_bytes(uint32_t n_entries);
-hipError_t build_flagged_lists(const uint32_t *entry32, const uint4 *entry, uint32_t n_entries,
-                               const uint32_t *blk_off, size_t n_off, void *scan_tmp, size_t scan_tmp_bytes,
-                               uint32_t *pre, uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream);
 
 StageGeometry stage_geometry(uint32_t block_cells);
 // The entries flagged C_WIDE (their read reaches beyond the 8-locus windows), listed per cell block for
@@ -125,23 +112,14 @@ hipError_t wide_fill(const uint32_t *entry32, const uint32_t *blk_off, uint32_t 
 // workspace of one accumulate launch: a tile per workgroup (plain-store flush, then reduce_slabs)
 size_t accumulate_slab_bytes(uint32_t block_cells, bool count_tile, uint32_t n_workgroups);
 
-// stage_masks / count_tile: the kernel variants, see accumulate_tiles. count_tile requires fewer
-// than 65536 pairs per cell pair (PackedPileup::pair_bound) and !stage_masks; stage_masks exists
-// for 64-cell tiles only. The accumulator must be zeroed by the caller: the flush is additive.
-// side: the stream (with two events) the flagged entries' lists are built on beside the pair kernel, or null
-struct SideStream {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    // work for the side stream that the launch issues right AFTER the pair kernel (so that the host's enqueueing of
-    // it does not delay that kernel) and whose `join` the second kernel waits for; null: nothing pending
-    hipError_t (*deferred)(void *ctx) = nullptr;
-    void *deferred_ctx = nullptr;
-};
+// stage_masks / count_tile: the kernel variants. count_tile (accumulate_counts + correct_tiles, or its fused
+// epilogue) requires fewer than 65536 pairs per cell pair (PackedPileup::pair_bound), !stage_masks and the flagged
+// entries' lists in AccumulateArgs; stage_masks (accumulate_masks, or accumulate_tiles with MASKS) exists for 64-cell
+// tiles only; neither: accumulate_tiles with the int64 tile. Unless args.overwrite the accumulator is added to.
 // mid: when non-null, recorded on `stream` between the pair kernel and what follows it (the duration of the
 // dominant kernel by itself: secedo_simmat_last_pair_kernel_ms)
 hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, bool stage_masks,
-                             bool count_tile, uint32_t n_tiles, hipStream_t stream, const SideStream *side = nullptr,
-                             hipEvent_t mid = nullptr);
+                             bool count_tile, uint32_t n_tiles, hipStream_t stream, hipEvent_t mid = nullptr);
 
 // mode 0..2 = SECEDO_NORM_*, 3 = raw D
 hipError_t launch_finalize(const int64_t *acc, const uint16_t *tile_row, const uint16_t *tile_col, uint32_t n_tiles,

@@ -1,7 +1,7 @@
-"""The sparse-loci path with the correction as accumulate_counts' epilogue and the flagged entries' lists built by the
-packing (the defaults) against accumulate_counts + correct_tiles with the lists built by the first accumulate
-(SECEDO_CORRECT_FUSED=0 SECEDO_FLAGS_FROM_PACK=0). Both switches are read once per process: each side runs in a child
-process. Accumulators, matrices and work counters must be bit-identical, and so must the flagged entries' lists."""
+"""The sparse-loci path with the correction as accumulate_counts' epilogue (the default) against accumulate_counts +
+correct_tiles (SECEDO_CORRECT_FUSED=0). The switch is read once per process: each side runs in a child process. Both
+sides read the flagged entries' lists the packing built. Accumulators, matrices and work counters must be
+bit-identical, and so must the flagged entries' lists."""
 import os
 import subprocess
 import sys
@@ -74,8 +74,6 @@ for name, expr, n, mfl, block, packing in CASES:
         acc.fill_(-5)
         plan.accumulate(acc, *RATES, overwrite=True)                      # assign
         r["assign"] = (digest(acc), plan.last_counts(), fused(plan))
-        if lists is None:
-            lists = flag_lists(plan)
         grp, rec, idx = lists
         out[name + "/grp"], out[name + "/rec"], out[name + "/idx"] = grp, rec, idx
         plan.accumulate(acc, *RATES)                                      # += onto a non-zero accumulator
@@ -117,9 +115,9 @@ def _run(tmp_path, tag, env):
 
 
 @pytest.mark.gpu
-def test_fused_correction_matches_correct_tiles(tmp_path):
-    new = _run(tmp_path, "fused", {"SECEDO_CORRECT_FUSED": "1", "SECEDO_FLAGS_FROM_PACK": "1"})
-    old = _run(tmp_path, "separate", {"SECEDO_CORRECT_FUSED": "0", "SECEDO_FLAGS_FROM_PACK": "0"})
+def test_fused_correction_matches_correct_tiles_on_the_packed_lists(tmp_path):
+    new = _run(tmp_path, "fused", {})
+    old = _run(tmp_path, "separate", {"SECEDO_CORRECT_FUSED": "0"})
     assert set(new) == set(old)
     for key in sorted(new):
         if key.endswith("/fused") or key.endswith("/lists_after_prepare"):
@@ -127,8 +125,8 @@ def test_fused_correction_matches_correct_tiles(tmp_path):
         assert np.array_equal(new[key], old[key]), key
     tails, multis = [], []
     for name, *_ in CASES:
-        # the packing built the lists; the first accumulate did on the old path
-        assert new[name + "/lists_after_prepare"][0] and not old[name + "/lists_after_prepare"][0], name
+        # the packing built the lists on both sides
+        assert new[name + "/lists_after_prepare"][0] and old[name + "/lists_after_prepare"][0], name
         # which launches ran the epilogue: every launch with one workgroup per tile, never a launch of few tiles
         for op in ("assign", "accumulate", "assign_list", "assign_finalize_ADD_MIN"):
             assert new[name + "/" + op + "/fused"][0] == 1, (name, op)
