@@ -143,6 +143,47 @@ int secedo_divide_cluster(int device_id, const uint32_t *chr_locus_off, uint32_t
                           const char *marker, uint16_t *clusters, uint16_t *cluster_idx,
                           secedo_cluster_level *records, uint32_t capacity, uint32_t *n_records);
 
+/* The same two recursions writing the reference's output files into out_dir (created when missing), per level
+ * (spectral_clustering.cpp:141-143, :236-279, :336-417):
+ *   <out_dir>/significant_positions<marker>   every level, before the coverage stop: id_to_chromosome(slot) TAB
+ *                                             position per kept locus, slot order
+ *   out_dir + "sim_mat_eigenvalues" + marker + ".csv"        every level that built a matrix
+ *   out_dir + "sim_mat_eigenvectors_norm" + marker + ".csv"  SPECTRAL2 / SPECTRAL6 with >= 2 eigenvectors:
+ *                                             columns 0..min(col_idx, k - 1) (col_idx 2 resp. 6), each row divided
+ *                                             by its norm when non-zero, space separated
+ *   <out_dir>/spectral_clustering<marker>      num_clusters > 1: per cell NO_POS (16383) when its group is outside
+ *                                             the sub-cluster, else uint16(cluster[pos]), comma separated
+ *   <out_dir>/expectation_maximization<marker> the same on the post-EM values, when EM ran (SECEDO_EM_RUN)
+ *   <out_dir>/clustering                       after every split: the clusters of all cells so far
+ * (the two eigen files are a plain concatenation of out_dir and the name, as in the reference). Departures: the
+ * eigenvalue file holds the min(20, n) recorded eigenvalues (the reference's cols(0, min(20, n_cols - 1)) of a
+ * column vector writes all n, against its own comment); numbers are written with %.17g, not Armadillo's layout;
+ * no expectation_maximization file when EM is SECEDO_EM_SKIPPED (the reference reads past its vector there);
+ * n_chr > 24 is SECEDO_E_INVALID_ARG, as slots are named by chromosome id. */
+int secedo_divide_cluster_files_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                                       const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+                                       const uint32_t *d_read_ids, const uint16_t *d_id_base16,
+                                       const uint32_t *d_id_base32, uint32_t n_loci, uint64_t n_entries,
+                                       uint32_t max_read_length, const uint16_t *id_to_group, uint32_t n_cells,
+                                       const uint32_t *id_to_pos, uint32_t n_groups, const uint32_t *pos_to_id,
+                                       uint32_t n_pos, double mutation_rate, double homozygous_rate,
+                                       double seq_error_rate, int normalization, int termination, int clustering_type,
+                                       int use_arma_kmeans, int use_expectation_maximization,
+                                       uint32_t min_cluster_size, uint32_t cell_proportion, const char *marker,
+                                       uint16_t *clusters, uint16_t *cluster_idx, secedo_cluster_level *records,
+                                       uint32_t capacity, uint32_t *n_records, void *stream, const char *out_dir);
+
+int secedo_divide_cluster_files(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
+                                const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint32_t *read_ids,
+                                const uint16_t *id_base16, const uint32_t *id_base32, uint32_t max_read_length,
+                                const uint16_t *id_to_group, uint32_t n_cells, const uint32_t *id_to_pos,
+                                uint32_t n_groups, const uint32_t *pos_to_id, uint32_t n_pos, double mutation_rate,
+                                double homozygous_rate, double seq_error_rate, int normalization, int termination,
+                                int clustering_type, int use_arma_kmeans, int use_expectation_maximization,
+                                uint32_t min_cluster_size, uint32_t cell_proportion, const char *marker,
+                                uint16_t *clusters, uint16_t *cluster_idx, secedo_cluster_level *records,
+                                uint32_t capacity, uint32_t *n_records, const char *out_dir);
+
 #ifdef __cplusplus
 }
 #endif

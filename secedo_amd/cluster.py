@@ -72,6 +72,10 @@ SIGNATURES = {
                                         C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
                                         C.c_uint32, C.c_char_p, _vp, _u16p, C.POINTER(Level), C.c_uint32, _u32p]),
 }
+# the same two recursions writing the reference's output files: one more argument, out_dir, at the end
+SIGNATURES["secedo_divide_cluster_files_device"] = (C.c_int, SIGNATURES["secedo_divide_cluster_device"][1] +
+                                                    [C.c_char_p])
+SIGNATURES["secedo_divide_cluster_files"] = (C.c_int, SIGNATURES["secedo_divide_cluster"][1] + [C.c_char_p])
 
 _cl = None
 
@@ -232,12 +236,13 @@ def divide_cluster(pds, max_read_length, id_to_group, id_to_pos, pos_to_id, muta
                    seq_error_rate, num_threads=1, out_dir="", normalization="ADD_MIN", termination_name="BIC",
                    clustering_type_name="SPECTRAL6", use_arma_kmeans=False, use_expectation_maximization=False,
                    min_cluster_size=500, cell_proportion=4, marker="", clusters=None, cluster_idx=1, device=0,
-                   with_times=False):
+                   with_times=False, *, write_files=False):
     """divide_cluster(...) (spectral_clustering.cpp:311-434) in the reference's argument order, the pileup uploaded
-    once. `num_threads` and `out_dir` are accepted and unused (no files are written: the records carry what
-    the reference logs; with_times adds each level's step times). -> (clusters as uint16 ndarray per cell id,
-    cluster_idx, list of level records)."""
-    del num_threads, out_dir
+    once. `num_threads` is accepted and unused; `out_dir` is ignored unless write_files is set, when the reference's
+    output files are written there (include/secedo_cluster.h lists them). The records carry what the reference
+    logs; with_times adds each level's step times. -> (clusters as uint16 ndarray per cell id, cluster_idx, list of
+    level records)."""
+    del num_threads
     p = pds if isinstance(pds, FlatPileup) else flatten(pds)
     g, i2p, p2i, cl = _id_maps(id_to_group, id_to_pos, pos_to_id, clusters)
     idb = np.ascontiguousarray(p.id_base)
@@ -254,12 +259,15 @@ def divide_cluster(pds, max_read_length, id_to_group, id_to_pos, pos_to_id, muta
     cap = 4 * len(p2i) + 16
     recs = (Level * cap)()
     n_rec, idx = C.c_uint32(0), C.c_uint16(cluster_idx)
-    check(lib().secedo_divide_cluster(
+    fn, extra = lib().secedo_divide_cluster, ()
+    if write_files:
+        fn, extra = lib().secedo_divide_cluster_files, (os.fsencode(str(out_dir)),)
+    check(fn(
         device, _lib.ptr(chr_off), len(chr_off) - 1, _lib.ptr(pos), _lib.ptr(off), _lib.ptr(rid), _lib.ptr(b16),
         _lib.ptr(b32), max_read_length, _lib.ptr(g), len(g), _lib.ptr(i2p), len(i2p), _lib.ptr(p2i), len(p2i),
         mutation_rate, homozygous_rate, seq_error_rate, _norm(normalization), term, t, int(bool(use_arma_kmeans)),
         int(bool(use_expectation_maximization)), min_cluster_size, cell_proportion, marker.encode(),
-        _lib.ptr(cl), C.byref(idx), recs, cap, C.byref(n_rec)))
+        _lib.ptr(cl), C.byref(idx), recs, cap, C.byref(n_rec), *extra))
     return cl, int(idx.value), _records(recs, n_rec.value, with_times)
 
 
@@ -267,21 +275,25 @@ def divide_cluster_resident(plan, res, max_read_length, id_to_group, id_to_pos, 
                             homozygous_rate, seq_error_rate, normalization="ADD_MIN", termination_name="BIC",
                             clustering_type_name="SPECTRAL6", use_arma_kmeans=False,
                             use_expectation_maximization=False, min_cluster_size=500, cell_proportion=4, marker="",
-                            clusters=None, cluster_idx=1, with_times=False):
+                            clusters=None, cluster_idx=1, with_times=False, out_dir=None):
     """divide_cluster on a pileup already resident in HBM (`res` from SimilarityMatrixPlan.upload, on
-    plan.device, in the plan's current stream) -> (clusters, cluster_idx, records)."""
+    plan.device, in the plan's current stream) -> (clusters, cluster_idx, records). With an out_dir the reference's
+    output files are written there (include/secedo_cluster.h lists them)."""
     g, i2p, p2i, cl = _id_maps(id_to_group, id_to_pos, pos_to_id, clusters)
     t, term = clustering_type(clustering_type_name), termination(termination_name)
     idb = C.c_void_p(res["idb"].data_ptr())
     cap = 4 * len(p2i) + 16
     recs = (Level * cap)()
     n_rec, idx = C.c_uint32(0), C.c_uint16(cluster_idx)
-    check(lib().secedo_divide_cluster_device(
+    fn, extra = lib().secedo_divide_cluster_device, ()
+    if out_dir is not None:
+        fn, extra = lib().secedo_divide_cluster_files_device, (os.fsencode(str(out_dir)),)
+    check(fn(
         plan.device, C.c_void_p(res["chr"].data_ptr()), res["n_chr"], C.c_void_p(res["pos"].data_ptr()),
         C.c_void_p(res["off"].data_ptr()), C.c_void_p(res["rid"].data_ptr()), idb if res["idb_is16"] else None,
         None if res["idb_is16"] else idb, res["n_loci"], res["n_entries"], max_read_length, _lib.ptr(g), len(g),
         _lib.ptr(i2p), len(i2p), _lib.ptr(p2i), len(p2i), mutation_rate, homozygous_rate, seq_error_rate,
         _norm(normalization), term, t, int(bool(use_arma_kmeans)), int(bool(use_expectation_maximization)),
         min_cluster_size, cell_proportion, marker.encode(), _lib.ptr(cl), C.byref(idx), recs, cap, C.byref(n_rec),
-        plan._stream()))
+        plan._stream(), *extra))
     return cl, int(idx.value), _records(recs, n_rec.value, with_times)

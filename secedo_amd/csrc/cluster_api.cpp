@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <filesystem>
 #include <string>
 #include <vector>
 
@@ -170,7 +171,112 @@ struct Params {
     hipStream_t stream;
     secedo_cluster_level *records;
     uint32_t capacity, n_records;
+    // the reference's output files (spectral_clustering.cpp:141-143, :236-279, :336-417) when `write` is set
+    bool write;
+    std::string out_dir;
+    const uint16_t *id_to_group;  // host
 };
+
+// --- the files divide_cluster writes -------------------------------------------------------------------------
+
+std::string id_to_chromosome(uint32_t c) {
+    if (c < 22) return std::to_string(c + 1);
+    return c == 22 ? "X" : "Y";
+}
+
+std::string in_dir(const std::string &dir, const std::string &name) {
+    return (std::filesystem::path(dir) / name).string();
+}
+
+int open_out(const std::string &path, FILE **f) {
+    *f = std::fopen(path.c_str(), "w");
+    return *f ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, "cannot write " + path);
+}
+
+// write_vec (util.hpp:49-60): comma-joined values and a newline; an empty vector leaves an empty file
+int write_vec(const std::string &path, const std::vector<uint16_t> &v) {
+    FILE *f;
+    if (int rc = open_out(path, &f)) return rc;
+    for (size_t i = 0; i < v.size(); ++i) std::fprintf(f, i + 1 < v.size() ? "%u," : "%u\n", (unsigned)v[i]);
+    std::fclose(f);
+    return SECEDO_OK;
+}
+
+template <class T>
+int download(std::vector<T> *out, const void *d, size_t n, hipStream_t s) {
+    out->resize(n);
+    if (n) CL_TRY(hipMemcpyAsync(out->data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    CL_TRY(hipStreamSynchronize(s));
+    return SECEDO_OK;
+}
+
+// significant_positions<marker>: id_to_chromosome(slot) TAB position per kept locus, slot order
+int write_positions(const Params &P, const std::string &marker, const uint32_t *d_chr, const uint32_t *d_pos,
+                    uint64_t kept_loci) {
+    std::vector<uint32_t> chr, pos;
+    if (int rc = download(&chr, d_chr, P.n_chr + 1, P.stream)) return rc;
+    if (int rc = download(&pos, d_pos, kept_loci, P.stream)) return rc;
+    FILE *f;
+    if (int rc = open_out(in_dir(P.out_dir, "significant_positions" + marker), &f)) return rc;
+    for (uint32_t c = 0; c < P.n_chr; ++c) {
+        const std::string name = id_to_chromosome(c);
+        for (uint32_t i = chr[c]; i < chr[c + 1]; ++i) std::fprintf(f, "%s\t%u\n", name.c_str(), pos[i]);
+    }
+    std::fclose(f);
+    return SECEDO_OK;
+}
+
+// sim_mat_eigenvalues<marker>.csv: the recorded eigenvalues, one per line (the reference's path is a plain
+// concatenation of out_dir and the name)
+int write_eigenvalues(const Params &P, const std::string &marker, const double *vals, uint32_t n) {
+    FILE *f;
+    if (int rc = open_out(P.out_dir + "sim_mat_eigenvalues" + marker + ".csv", &f)) return rc;
+    for (uint32_t i = 0; i < n; ++i) std::fprintf(f, "%.17g\n", vals[i]);
+    std::fclose(f);
+    return SECEDO_OK;
+}
+
+// sim_mat_eigenvectors_norm<marker>.csv: eigenvector columns 0..min(col_idx, k - 1), rows scaled to unit norm
+// when non-zero (:240-249); d_ev column-major n x k
+int write_eigenvectors(const Params &P, const std::string &marker, const double *d_ev, uint32_t n, uint32_t k) {
+    std::vector<double> ev;
+    if (int rc = download(&ev, d_ev, (size_t)n * k, P.stream)) return rc;
+    const uint32_t col_idx = P.type == SECEDO_CLUSTER_SPECTRAL2 ? 2 : 6;
+    const uint32_t cols = std::min(col_idx, k - 1) + 1;
+    FILE *f;
+    if (int rc = open_out(P.out_dir + "sim_mat_eigenvectors_norm" + marker + ".csv", &f)) return rc;
+    std::vector<double> row(cols);
+    for (uint32_t i = 0; i < n; ++i) {
+        double sq = 0;
+        for (uint32_t c = 0; c < cols; ++c) {
+            row[c] = ev[(size_t)c * n + i];
+            sq += row[c] * row[c];
+        }
+        const double norm = std::sqrt(sq);
+        for (uint32_t c = 0; c < cols; ++c) {
+            const double v = norm > 0 ? row[c] / norm : row[c];
+            std::fprintf(f, c + 1 < cols ? "%.17g " : "%.17g\n", v);
+        }
+    }
+    std::fclose(f);
+    return SECEDO_OK;
+}
+
+// spectral_clustering<marker> / expectation_maximization<marker>: per cell, NO_POS when its group is outside the
+// sub-cluster, else uint16(cluster[pos]) (:356-371)
+int write_id_to_cluster(const Params &P, const std::string &name, const uint32_t *d_i2p, const double *d_cluster,
+                        uint32_t n_sub) {
+    std::vector<uint32_t> i2p;
+    std::vector<double> cl;
+    if (int rc = download(&i2p, d_i2p, P.n_groups, P.stream)) return rc;
+    if (int rc = download(&cl, d_cluster, n_sub, P.stream)) return rc;
+    std::vector<uint16_t> out(P.n_cells);
+    for (uint32_t c = 0; c < P.n_cells; ++c) {
+        const uint32_t pos = i2p[P.id_to_group[c]];
+        out[c] = pos == kNoPos ? (uint16_t)kNoPos : (uint16_t)cl[pos];
+    }
+    return write_vec(in_dir(P.out_dir, name), out);
+}
 
 // One level of divide_cluster. d_i2p[n_groups], d_p2i[n_sub] on the device; max_group = largest id in d_p2i.
 int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_sub, uint32_t max_group,
@@ -202,6 +308,10 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
     rec.step_ms[0] = ms_since(t0);  // secedo_filter_device synchronises the stream
     rec.kept_loci = kept_loci;
     rec.coverage = coverage;
+    if (P.write) {
+        if (int rc = write_positions(P, marker, f_chr.as<uint32_t>(), f_pos.as<uint32_t>(), kept_loci)) return rc;
+        t0 = Clock::now();
+    }
     if (coverage < 9) {
         rec.stop_reason = SECEDO_STOP_COVERAGE;
         return SECEDO_OK;
@@ -236,6 +346,12 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
         rec.n_eigenvalues = n_values;
     }
     rec.step_ms[2] = ms_since(t0);
+    if (P.write && n_sub > 0) {
+        if (int rc = write_eigenvalues(P, marker, rec.eigenvalues, n_values)) return rc;
+        if (P.type != SECEDO_CLUSTER_FIEDLER && k >= 2)
+            if (int rc = write_eigenvectors(P, marker, ev.as<double>(), n_sub, k)) return rc;
+        t0 = Clock::now();
+    }
     sim.release();
     uint32_t num_clusters = 1;
     CL_CALL(decide(ev.as<double>(), n_sub, k, P.type, P.termination, d_cluster.as<double>(), &num_clusters,
@@ -246,6 +362,11 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
     if (num_clusters == 1) {
         rec.stop_reason = SECEDO_STOP_ONE_CLUSTER;
         return SECEDO_OK;
+    }
+    if (P.write) {
+        if (int rc = write_id_to_cluster(P, "spectral_clustering" + marker, d_i2p, d_cluster.as<double>(), n_sub))
+            return rc;
+        t0 = Clock::now();
     }
 
     if (P.use_em && num_clusters == 2) {
@@ -265,6 +386,11 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
     }
     CL_TRY(hipStreamSynchronize(P.stream));
     rec.step_ms[4] = ms_since(t0);
+    if (P.write && rec.em_state == SECEDO_EM_RUN) {
+        if (int rc = write_id_to_cluster(P, "expectation_maximization" + marker, d_i2p, d_cluster.as<double>(), n_sub))
+            return rc;
+        t0 = Clock::now();
+    }
     f_chr.release();
     f_pos.release();
     f_off.release();
@@ -283,6 +409,11 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
     CL_TRY(hipMemcpyAsync(info, c_info.p, sizeof(info), hipMemcpyDeviceToHost, P.stream));
     CL_TRY(hipStreamSynchronize(P.stream));
     rec.step_ms[5] = ms_since(t0);
+    if (P.write) {
+        std::vector<uint16_t> cells;
+        if (int rc = download(&cells, P.d_clusters, P.n_cells, P.stream)) return rc;
+        if (int rc = write_vec(in_dir(P.out_dir, "clustering"), cells)) return rc;
+    }
     d_cluster.release();
     *cluster_idx = (uint16_t)(*cluster_idx + num_clusters);
     rec.stop_reason = SECEDO_STOP_SPLIT;
@@ -393,17 +524,16 @@ int secedo_cluster_gmm_device(int device_id, const double *d_points, uint32_t n,
     return SECEDO_OK;
 }
 
-int secedo_divide_cluster_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
-                                 const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
-                                 const uint32_t *d_read_ids, const uint16_t *d_id_base16, const uint32_t *d_id_base32,
-                                 uint32_t n_loci, uint64_t n_entries, uint32_t max_read_length,
-                                 const uint16_t *id_to_group, uint32_t n_cells, const uint32_t *id_to_pos,
-                                 uint32_t n_groups, const uint32_t *pos_to_id, uint32_t n_pos, double mutation_rate,
-                                 double homozygous_rate, double seq_error_rate, int normalization, int termination,
-                                 int clustering_type, int use_arma_kmeans, int use_expectation_maximization,
-                                 uint32_t min_cluster_size, uint32_t cell_proportion, const char *marker,
-                                 uint16_t *clusters, uint16_t *cluster_idx, secedo_cluster_level *records,
-                                 uint32_t capacity, uint32_t *n_records, void *stream) {
+static int divide_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                         const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off, const uint32_t *d_read_ids,
+                         const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci, uint64_t n_entries,
+                         uint32_t max_read_length, const uint16_t *id_to_group, uint32_t n_cells,
+                         const uint32_t *id_to_pos, uint32_t n_groups, const uint32_t *pos_to_id, uint32_t n_pos,
+                         double mutation_rate, double homozygous_rate, double seq_error_rate, int normalization,
+                         int termination, int clustering_type, int use_arma_kmeans, int use_expectation_maximization,
+                         uint32_t min_cluster_size, uint32_t cell_proportion, const char *marker, uint16_t *clusters,
+                         uint16_t *cluster_idx, secedo_cluster_level *records, uint32_t capacity,
+                         uint32_t *n_records, void *stream, const char *out_dir) {
     (void)cell_proportion;  // Filter filter(seq_error_rate) (:336)
     if (int rc = check_options(clustering_type, termination, use_arma_kmeans)) return rc;
     if (normalization < SECEDO_NORM_ADD_MIN || normalization > SECEDO_NORM_SCALE_MAX_1)
@@ -428,7 +558,14 @@ int secedo_divide_cluster_device(int device_id, const uint32_t *d_chr_locus_off,
     if (n_pos >= kNoPos) return fail(SECEDO_E_INVALID_ARG, "a sub-cluster holds at most 16382 cells (NO_POS)");
     for (uint32_t c = 0; c < n_cells; ++c)
         if (id_to_group[c] >= n_groups) return fail(SECEDO_E_INVALID_ARG, "id_to_group names a group past id_to_pos");
+    if (out_dir && n_chr > 24)
+        return fail(SECEDO_E_INVALID_ARG, "more than 24 chromosome slots: significant_positions names slots by chromosome");
     if (int rc = check_device(device_id)) return rc;
+    if (out_dir && *out_dir) {
+        std::error_code ec;
+        std::filesystem::create_directories(out_dir, ec);
+        if (ec) return fail(SECEDO_E_INVALID_ARG, std::string("cannot create ") + out_dir + ": " + ec.message());
+    }
 
     Params P{};
     P.device_id = device_id;
@@ -455,6 +592,9 @@ int secedo_divide_cluster_device(int device_id, const uint32_t *d_chr_locus_off,
     P.stream = static_cast<hipStream_t>(stream);
     P.records = records;
     P.capacity = capacity;
+    P.write = out_dir != nullptr;
+    P.out_dir = out_dir ? out_dir : "";
+    P.id_to_group = id_to_group;
 
     Buf d_g, d_i2p, d_p2i, d_cl;
     CL_TRY(d_g.alloc((size_t)n_cells * 2));
@@ -484,15 +624,15 @@ int secedo_divide_cluster_device(int device_id, const uint32_t *d_chr_locus_off,
     return SECEDO_OK;
 }
 
-int secedo_divide_cluster(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr, const uint32_t *locus_pos,
-                          const uint64_t *locus_entry_off, const uint32_t *read_ids, const uint16_t *id_base16,
-                          const uint32_t *id_base32, uint32_t max_read_length, const uint16_t *id_to_group,
-                          uint32_t n_cells, const uint32_t *id_to_pos, uint32_t n_groups, const uint32_t *pos_to_id,
-                          uint32_t n_pos, double mutation_rate, double homozygous_rate, double seq_error_rate,
-                          int normalization, int termination, int clustering_type, int use_arma_kmeans,
-                          int use_expectation_maximization, uint32_t min_cluster_size, uint32_t cell_proportion,
-                          const char *marker, uint16_t *clusters, uint16_t *cluster_idx,
-                          secedo_cluster_level *records, uint32_t capacity, uint32_t *n_records) {
+static int divide_host(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr, const uint32_t *locus_pos,
+                       const uint64_t *locus_entry_off, const uint32_t *read_ids, const uint16_t *id_base16,
+                       const uint32_t *id_base32, uint32_t max_read_length, const uint16_t *id_to_group,
+                       uint32_t n_cells, const uint32_t *id_to_pos, uint32_t n_groups, const uint32_t *pos_to_id,
+                       uint32_t n_pos, double mutation_rate, double homozygous_rate, double seq_error_rate,
+                       int normalization, int termination, int clustering_type, int use_arma_kmeans,
+                       int use_expectation_maximization, uint32_t min_cluster_size, uint32_t cell_proportion,
+                       const char *marker, uint16_t *clusters, uint16_t *cluster_idx, secedo_cluster_level *records,
+                       uint32_t capacity, uint32_t *n_records, const char *out_dir) {
     if (int rc = check_options(clustering_type, termination, use_arma_kmeans)) return rc;
     if (n_pos == 0) return fail(SECEDO_E_INVALID_ARG, "no cells: pos_to_id is empty");
     if (!chr_locus_off || (!locus_pos && n_chr) || !locus_entry_off)
@@ -522,13 +662,81 @@ int secedo_divide_cluster(int device_id, const uint32_t *chr_locus_off, uint32_t
         if (id_base16) CL_TRY(hipMemcpy(idb.p, id_base16, (size_t)E * 2, hipMemcpyHostToDevice));
         else CL_TRY(hipMemcpy(idb.p, id_base32, (size_t)E * 4, hipMemcpyHostToDevice));
     }
-    return secedo_divide_cluster_device(device_id, chr.as<uint32_t>(), n_chr, pos.as<uint32_t>(), off.as<uint64_t>(),
-                                        rid.as<uint32_t>(), id_base16 ? idb.as<uint16_t>() : nullptr,
-                                        id_base16 ? nullptr : idb.as<uint32_t>(), L, E, max_read_length, id_to_group,
-                                        n_cells, id_to_pos, n_groups, pos_to_id, n_pos, mutation_rate, homozygous_rate,
-                                        seq_error_rate, normalization, termination, clustering_type, use_arma_kmeans,
-                                        use_expectation_maximization, min_cluster_size, cell_proportion, marker,
-                                        clusters, cluster_idx, records, capacity, n_records, nullptr);
+    return divide_device(device_id, chr.as<uint32_t>(), n_chr, pos.as<uint32_t>(), off.as<uint64_t>(),
+                         rid.as<uint32_t>(), id_base16 ? idb.as<uint16_t>() : nullptr,
+                         id_base16 ? nullptr : idb.as<uint32_t>(), L, E, max_read_length, id_to_group, n_cells,
+                         id_to_pos, n_groups, pos_to_id, n_pos, mutation_rate, homozygous_rate, seq_error_rate,
+                         normalization, termination, clustering_type, use_arma_kmeans, use_expectation_maximization,
+                         min_cluster_size, cell_proportion, marker, clusters, cluster_idx, records, capacity,
+                         n_records, nullptr, out_dir);
+}
+
+#define DEVICE_ARGS                                                                                                  \
+    device_id, d_chr_locus_off, n_chr, d_locus_pos, d_locus_entry_off, d_read_ids, d_id_base16, d_id_base32, n_loci, \
+        n_entries, max_read_length, id_to_group, n_cells, id_to_pos, n_groups, pos_to_id, n_pos, mutation_rate,      \
+        homozygous_rate, seq_error_rate, normalization, termination, clustering_type, use_arma_kmeans,               \
+        use_expectation_maximization, min_cluster_size, cell_proportion, marker, clusters, cluster_idx, records,     \
+        capacity, n_records, stream
+#define HOST_ARGS                                                                                                     \
+    device_id, chr_locus_off, n_chr, locus_pos, locus_entry_off, read_ids, id_base16, id_base32, max_read_length,     \
+        id_to_group, n_cells, id_to_pos, n_groups, pos_to_id, n_pos, mutation_rate, homozygous_rate, seq_error_rate, \
+        normalization, termination, clustering_type, use_arma_kmeans, use_expectation_maximization, min_cluster_size, \
+        cell_proportion, marker, clusters, cluster_idx, records, capacity, n_records
+
+int secedo_divide_cluster_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                                 const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+                                 const uint32_t *d_read_ids, const uint16_t *d_id_base16, const uint32_t *d_id_base32,
+                                 uint32_t n_loci, uint64_t n_entries, uint32_t max_read_length,
+                                 const uint16_t *id_to_group, uint32_t n_cells, const uint32_t *id_to_pos,
+                                 uint32_t n_groups, const uint32_t *pos_to_id, uint32_t n_pos, double mutation_rate,
+                                 double homozygous_rate, double seq_error_rate, int normalization, int termination,
+                                 int clustering_type, int use_arma_kmeans, int use_expectation_maximization,
+                                 uint32_t min_cluster_size, uint32_t cell_proportion, const char *marker,
+                                 uint16_t *clusters, uint16_t *cluster_idx, secedo_cluster_level *records,
+                                 uint32_t capacity, uint32_t *n_records, void *stream) {
+    return divide_device(DEVICE_ARGS, nullptr);
+}
+
+int secedo_divide_cluster_files_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                                       const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+                                       const uint32_t *d_read_ids, const uint16_t *d_id_base16,
+                                       const uint32_t *d_id_base32, uint32_t n_loci, uint64_t n_entries,
+                                       uint32_t max_read_length, const uint16_t *id_to_group, uint32_t n_cells,
+                                       const uint32_t *id_to_pos, uint32_t n_groups, const uint32_t *pos_to_id,
+                                       uint32_t n_pos, double mutation_rate, double homozygous_rate,
+                                       double seq_error_rate, int normalization, int termination, int clustering_type,
+                                       int use_arma_kmeans, int use_expectation_maximization,
+                                       uint32_t min_cluster_size, uint32_t cell_proportion, const char *marker,
+                                       uint16_t *clusters, uint16_t *cluster_idx, secedo_cluster_level *records,
+                                       uint32_t capacity, uint32_t *n_records, void *stream, const char *out_dir) {
+    if (!out_dir) return fail(SECEDO_E_INVALID_ARG, "null out_dir");
+    return divide_device(DEVICE_ARGS, out_dir);
+}
+
+int secedo_divide_cluster(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr, const uint32_t *locus_pos,
+                          const uint64_t *locus_entry_off, const uint32_t *read_ids, const uint16_t *id_base16,
+                          const uint32_t *id_base32, uint32_t max_read_length, const uint16_t *id_to_group,
+                          uint32_t n_cells, const uint32_t *id_to_pos, uint32_t n_groups, const uint32_t *pos_to_id,
+                          uint32_t n_pos, double mutation_rate, double homozygous_rate, double seq_error_rate,
+                          int normalization, int termination, int clustering_type, int use_arma_kmeans,
+                          int use_expectation_maximization, uint32_t min_cluster_size, uint32_t cell_proportion,
+                          const char *marker, uint16_t *clusters, uint16_t *cluster_idx,
+                          secedo_cluster_level *records, uint32_t capacity, uint32_t *n_records) {
+    return divide_host(HOST_ARGS, nullptr);
+}
+
+int secedo_divide_cluster_files(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
+                                const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint32_t *read_ids,
+                                const uint16_t *id_base16, const uint32_t *id_base32, uint32_t max_read_length,
+                                const uint16_t *id_to_group, uint32_t n_cells, const uint32_t *id_to_pos,
+                                uint32_t n_groups, const uint32_t *pos_to_id, uint32_t n_pos, double mutation_rate,
+                                double homozygous_rate, double seq_error_rate, int normalization, int termination,
+                                int clustering_type, int use_arma_kmeans, int use_expectation_maximization,
+                                uint32_t min_cluster_size, uint32_t cell_proportion, const char *marker,
+                                uint16_t *clusters, uint16_t *cluster_idx, secedo_cluster_level *records,
+                                uint32_t capacity, uint32_t *n_records, const char *out_dir) {
+    if (!out_dir) return fail(SECEDO_E_INVALID_ARG, "null out_dir");
+    return divide_host(HOST_ARGS, out_dir);
 }
 
 }  // extern "C"
