@@ -8,6 +8,13 @@
  * GPU (secedo_amd/csrc/bam_kernels.hip, which lists the restated semantics). The outputs equal the
  * reference's run with num_threads = 1: .bin and .map byte for byte, .txt wherever a locus has at most 16
  * entries. Error codes are those of secedo_simmat.h; secedo_bam_last_error() holds the message.
+ *
+ * Tag mode (secedo_pileup_bams_cells[_device]) reads multiplexed BAMs, one cell per value of a barcode tag (10x's
+ * CB:Z): the cell of a record is the index of its Z-typed tag value in the barcode list, records of other values are
+ * dropped. Its output equals the per-file call on the per-cell split files (record order Position, input file,
+ * record); secedo_bam_barcodes lists the values found. Inflated bytes per file are bounded: a large file is inflated
+ * and walked in ranges of BGZF blocks (about 512 MiB inflated; the environment variable SECEDO_BAM_BATCH_BYTES
+ * overrides it, outputs do not depend on it).
  */
 #ifndef SECEDO_BAM_H
 #define SECEDO_BAM_H
@@ -78,6 +85,36 @@ int secedo_pileup_bams_device(const char *const *bam_files, uint32_t n_files, co
                               uint32_t min_map_quality, uint32_t min_alignment_score, uint32_t num_threads,
                               uint16_t min_different, const uint16_t *id_to_group, uint32_t n_ids,
                               secedo_bam_result_info *info, secedo_bam_times *times);
+
+/* Tag mode: bam_files are multiplexed BAMs; the cell of a record is the index in barcodes[0..n_barcodes) of the
+ * value of its first aux field named tag (two characters [A-Za-z][A-Za-z0-9]) when that field is Z-typed. Records
+ * without it, with another type or an unlisted value take no read id, pass no checks of the device passes and give
+ * nothing; the host's structural checks still cover every record of the chromosome. The result equals
+ * secedo_pileup_bams / secedo_pileup_bams_device on n_barcodes files C_c holding the records of barcode c in
+ * (Position, input file, record) order. Error messages name the input file and its record index. An empty list, a
+ * duplicate or a bad tag: SECEDO_E_INVALID_ARG; more than SECEDO_BAM_MAX_FILES barcodes: SECEDO_E_LIMIT. */
+int secedo_pileup_bams_cells(const char *const *bam_files, uint32_t n_files, const char *out_pileup,
+                             int write_text_file, uint32_t chromosome_id, uint32_t max_coverage,
+                             uint32_t min_base_quality, uint32_t min_map_quality, uint32_t min_alignment_score,
+                             uint32_t num_threads, uint16_t min_different, const char tag[2],
+                             const char *const *barcodes, uint32_t n_barcodes, secedo_bam_result_info *info,
+                             secedo_bam_times *times);
+int secedo_pileup_bams_cells_device(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                                    uint32_t n_chr, uint32_t max_coverage, uint32_t min_base_quality,
+                                    uint32_t min_map_quality, uint32_t min_alignment_score, uint32_t num_threads,
+                                    uint16_t min_different, const uint16_t *id_to_group, uint32_t n_ids,
+                                    const char tag[2], const char *const *barcodes, uint32_t n_barcodes,
+                                    secedo_bam_result_info *info, secedo_bam_times *times);
+
+/* The distinct Z-typed values of tag (first occurrence per record) over the records of the requested chromosomes,
+ * sorted bytewise, with their record counts: *n_barcodes values of *bytes bytes in all. The result stays until the
+ * next call on this thread; get it with secedo_bam_barcodes_fetch. Synchronous. */
+int secedo_bam_barcodes(const char *const *bam_files, uint32_t n_files, const char tag[2],
+                        const uint32_t *chromosome_ids, uint32_t n_chr, uint32_t num_threads, uint32_t *n_barcodes,
+                        uint64_t *bytes);
+/* Host buffers, any may be NULL: values[bytes] packed without separators, value_off[n_barcodes + 1],
+ * counts[n_barcodes]. */
+int secedo_bam_barcodes_fetch(char *values, uint64_t *value_off, uint64_t *counts);
 
 /* Copies the last result into host or device buffers (any may be NULL): chr_locus_off[n_chr + 1],
  * locus_pos[n_loci], locus_entry_off[n_loci + 1], read_ids[n_entries], id_base16[n_entries].

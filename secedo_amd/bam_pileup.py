@@ -5,6 +5,10 @@ max_coverage, min_base_quality, min_map_quality, min_alignment_score, num_thread
 (pileup.cpp:235-348). The host inflates the BGZF blocks and walks the records; the per-record decode, the read
 name numbering, the base counts, the locus rule and the entry placement run on the GPU
 (secedo_amd/csrc/bam_kernels.hip). ``bam_scan`` needs no GPU. No CPU fallback for the pileup itself.
+
+Multiplexed BAMs (one file, many cells named by a barcode tag such as 10x's ``CB:Z``): ``cell_tag`` and ``cells``
+on ``pileup_bams`` / ``pileup_bams_resident`` make cell c the records whose tag value is ``cells[c]``;
+``bam_barcodes`` lists the values found and their record counts.
 """
 from __future__ import annotations
 
@@ -51,6 +55,15 @@ SIGNATURES = {
                                      C.c_uint16, C.POINTER(ResultInfo), C.POINTER(Times)]),
     "secedo_pileup_bams_device": (C.c_int, [_files_t, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32, C.c_uint16,
                                             _vp, _u32, C.POINTER(ResultInfo), C.POINTER(Times)]),
+    "secedo_pileup_bams_cells": (C.c_int, [_files_t, _u32, C.c_char_p, C.c_int, _u32, _u32, _u32, _u32, _u32, _u32,
+                                           C.c_uint16, C.c_char_p, _files_t, _u32, C.POINTER(ResultInfo),
+                                           C.POINTER(Times)]),
+    "secedo_pileup_bams_cells_device": (C.c_int, [_files_t, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _u32,
+                                                  C.c_uint16, _vp, _u32, C.c_char_p, _files_t, _u32,
+                                                  C.POINTER(ResultInfo), C.POINTER(Times)]),
+    "secedo_bam_barcodes": (C.c_int, [_files_t, _u32, C.c_char_p, _vp, _u32, _u32, C.POINTER(_u32),
+                                      C.POINTER(C.c_uint64)]),
+    "secedo_bam_barcodes_fetch": (C.c_int, [_vp, _vp, _vp]),
     "secedo_bam_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "secedo_bam_release": (None, []),
 }
@@ -89,6 +102,53 @@ def _files(bam_files):
     return arr, len(names)
 
 
+def _encode(value) -> bytes:
+    return value if isinstance(value, bytes) else str(value).encode("utf-8", "surrogateescape")
+
+
+def _tag(cell_tag) -> bytes:
+    """The two tag characters (the library checks them); anything not two characters long is refused here."""
+    t = _encode(cell_tag)
+    if len(t) != 2:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "a tag is two characters [A-Za-z][A-Za-z0-9], got %r" % cell_tag)
+    return t
+
+
+def _cells(cell_tag, cells):
+    """-> (tag bytes, barcode array, count) of tag mode, or (None, None, 0) without cell_tag."""
+    if cell_tag is None:
+        if cells is not None:
+            raise _lib.SecedoError(_lib.E_INVALID_ARG, "cells needs cell_tag")
+        return None, None, 0
+    if cells is None:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "cell_tag needs the barcode list cells")
+    vals = [_encode(c) for c in cells]
+    return _tag(cell_tag), (C.c_char_p * max(len(vals), 1))(*vals), len(vals)
+
+
+def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], num_threads: int = 1):
+    """The distinct Z-typed values of ``tag`` over the records of the given chromosomes of ``files``, sorted
+    bytewise -> (values [str], counts np.uint64: records per value). Needs the GPU."""
+    arr, n = _files(files)
+    ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
+    n_val, n_bytes = C.c_uint32(0), C.c_uint64(0)
+    t = _tag(tag)
+    try:
+        import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
+    except ImportError:
+        pass
+    check(lib().secedo_bam_barcodes(arr, n, t, _lib.ptr(ids) if len(ids) else None, len(ids), num_threads,
+                                    C.byref(n_val), C.byref(n_bytes)))
+    k = int(n_val.value)
+    buf = C.create_string_buffer(max(int(n_bytes.value), 1))
+    off = np.zeros(k + 1, dtype=np.uint64)
+    counts = np.zeros(max(k, 1), dtype=np.uint64)
+    check(lib().secedo_bam_barcodes_fetch(C.cast(buf, C.c_void_p), _lib.ptr(off), _lib.ptr(counts)))
+    raw = buf.raw
+    values = [raw[int(off[i]):int(off[i + 1])].decode("utf-8", "surrogateescape") for i in range(k)]
+    return values, counts[:k].copy()
+
+
 def bam_scan(path, num_threads: int = 1, max_refs: int = 4096) -> dict:
     """Header and record summary of one BAM file, no GPU: n_ref, sorted, n_records, n_unmapped, n_blocks,
     inflated_bytes, l_text and records_per_ref (one count per @SQ entry)."""
@@ -119,15 +179,25 @@ def _fetch_host(info: ResultInfo) -> FlatPileup:
 
 def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_file: bool, chromosome_id: int,
                 max_coverage: int, min_base_quality: int, min_map_quality: int, min_alignment_score: int,
-                num_threads: int, min_different: int, times: Optional[dict] = None) -> FlatPileup:
+                num_threads: int, min_different: int, times: Optional[dict] = None, *, cell_tag=None,
+                cells=None) -> FlatPileup:
     """The reference's pileup_bams() -> a one-chromosome FlatPileup (id_base = cell << 2 | base). Writes
-    <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms."""
+    <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms.
+
+    With ``cell_tag`` (e.g. "CB") the files are multiplexed: cell c is the records whose Z-typed ``cell_tag`` value
+    is ``cells[c]``; the result equals this call on the per-cell split files."""
     arr, n = _files(bam_files)
+    tag, bcs, n_bcs = _cells(cell_tag, cells)
     info, t = ResultInfo(), Times()
-    check(lib().secedo_pileup_bams(arr, n, None if out_pileup is None else os.fsencode(str(out_pileup)),
-                                   int(bool(write_text_file)), chromosome_id, max_coverage, min_base_quality,
-                                   min_map_quality, min_alignment_score, num_threads, min_different, C.byref(info),
-                                   C.byref(t)))
+    out = None if out_pileup is None else os.fsencode(str(out_pileup))
+    if tag is None:
+        check(lib().secedo_pileup_bams(arr, n, out, int(bool(write_text_file)), chromosome_id, max_coverage,
+                                       min_base_quality, min_map_quality, min_alignment_score, num_threads,
+                                       min_different, C.byref(info), C.byref(t)))
+    else:
+        check(lib().secedo_pileup_bams_cells(arr, n, out, int(bool(write_text_file)), chromosome_id, max_coverage,
+                                             min_base_quality, min_map_quality, min_alignment_score, num_threads,
+                                             min_different, tag, bcs, n_bcs, C.byref(info), C.byref(t)))
     if times is not None:
         times.update(_times(t))
     return _fetch_host(info)
@@ -136,24 +206,32 @@ def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_
 def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequence[int], max_coverage: int = 100,
                          min_base_quality: int = 30, min_map_quality: int = 30, min_alignment_score: int = 0,
                          num_threads: int = 8, min_different: int = 3, id_to_group=None, group_id_to_pos=None,
-                         times: Optional[dict] = None):
+                         times: Optional[dict] = None, *, cell_tag=None, cells=None):
     """Several chromosomes in one pass over the files, straight into HBM on ``plan``'s device.
 
     -> (res, num_cells, max_read_length): ``res`` is the resident pileup dict of SimilarityMatrixPlan.upload,
     which filter_resident, divide_cluster_resident and variant_calling_resident take; num_cells and
-    max_read_length are what read_pileup would report on the written .bin files (maxima over chromosomes)."""
+    max_read_length are what read_pileup would report on the written .bin files (maxima over chromosomes).
+    ``cell_tag`` / ``cells``: multiplexed files, as in pileup_bams; id_to_group then maps barcode indices."""
     import torch
 
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
     arr, n = _files(bam_files)
+    tag, bcs, n_bcs = _cells(cell_tag, cells)
     i2g = None if id_to_group is None else np.ascontiguousarray(id_to_group, dtype=np.uint16)
     info, t = ResultInfo(), Times()
     dev = "cuda:%d" % plan.device
     with torch.cuda.device(plan.device):
-        check(lib().secedo_pileup_bams_device(arr, n, _lib.ptr(ids), len(ids), max_coverage, min_base_quality,
-                                              min_map_quality, min_alignment_score, num_threads, min_different,
-                                              _lib.ptr(i2g) if i2g is not None else None,
-                                              0 if i2g is None else len(i2g), C.byref(info), C.byref(t)))
+        i2g_p, n_i2g = (_lib.ptr(i2g), len(i2g)) if i2g is not None else (None, 0)
+        if tag is None:
+            check(lib().secedo_pileup_bams_device(arr, n, _lib.ptr(ids), len(ids), max_coverage, min_base_quality,
+                                                  min_map_quality, min_alignment_score, num_threads, min_different,
+                                                  i2g_p, n_i2g, C.byref(info), C.byref(t)))
+        else:
+            check(lib().secedo_pileup_bams_cells_device(arr, n, _lib.ptr(ids), len(ids), max_coverage,
+                                                        min_base_quality, min_map_quality, min_alignment_score,
+                                                        num_threads, min_different, i2g_p, n_i2g, tag, bcs, n_bcs,
+                                                        C.byref(info), C.byref(t)))
         L, E = int(info.n_loci), int(info.n_entries)
         chr_t = torch.from_numpy(np.zeros(len(ids) + 1, dtype=np.int32)).to(dev)
         pos_t = torch.empty(max(L, 1), dtype=torch.int32, device=dev)

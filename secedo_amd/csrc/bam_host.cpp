@@ -4,8 +4,13 @@
 //
 // Each file is memory-mapped; its BGZF blocks (BSIZE from the BC extra field) are inflated with zlib raw inflate
 // in a pool of at most 16 threads, CRC32 and ISIZE checked. Files are inflated in batches of about 512 MiB of
-// inflated data; of each file only the byte run of the requested chromosomes' records is kept. No .bai is needed:
-// the run is found by walking block_size, so with or without an index the result is the same.
+// inflated data (SECEDO_BAM_BATCH_BYTES overrides it); a file alone in its batch is inflated and walked in ranges
+// of BGZF blocks of that size, a record cut at a range's end carried into the next, so one large multiplexed BAM
+// never sits inflated in RAM. Of each file only the byte run of the requested chromosomes' records is kept. No .bai
+// is needed: the run is found by walking block_size, so with or without an index the result is the same.
+//
+// Tag mode (secedo_pileup_bams_cells) uploads the chromosome's records in input order and builds the global order
+// on the device (bam_kernels.hip rule 3b); secedo_bam_barcodes counts the distinct tag values.
 #include "secedo_bam.h"
 #include "secedo_simmat.h"
 #include "bam_kernels.hpp"
@@ -21,9 +26,12 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <map>
 #include <climits>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -58,6 +66,17 @@ double ms_since(Clock::time_point t0) {
 
 constexpr uint32_t kMaxThreads = 16;
 constexpr uint64_t kBatchBytes = 512ull << 20;
+
+// inflated bytes per batch of files and per block range of one file; SECEDO_BAM_BATCH_BYTES overrides it (tests:
+// outputs do not depend on it), read at every call
+uint64_t batch_bytes() {
+    const char *e = std::getenv("SECEDO_BAM_BATCH_BYTES");
+    if (e && *e) {
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v > 0) return v;
+    }
+    return kBatchBytes;
+}
 
 inline uint32_t rd32(const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
 inline uint16_t rd16(const uint8_t *p) { uint16_t v; std::memcpy(&v, p, 2); return v; }
@@ -191,51 +210,88 @@ struct Header {
     uint64_t first_record = 0;
 };
 
-int parse_header(const Inflated &f, Header *h) {
-    const std::vector<uint8_t> &d = f.data;
-    if (d.size() < 12 || std::memcmp(d.data(), "BAM\1", 4) != 0)
-        return fail(SECEDO_E_INVALID_ARG, f.path + ": not a BAM file (magic)");
-    h->l_text = rd32(&d[4]);
+constexpr int kNeedMore = 1;  // parse_header / walk_range: the bytes end inside the header or a record
+
+// final: d ends the file, so a cut header is an error; else kNeedMore
+int parse_header(const std::string &path, const uint8_t *d, uint64_t n, bool final, Header *h) {
+    if ((n >= 4 && std::memcmp(d, "BAM\1", 4) != 0) || (final && n < 12))
+        return fail(SECEDO_E_INVALID_ARG, path + ": not a BAM file (magic)");
+    if (n < 12) return kNeedMore;
+    h->l_text = rd32(d + 4);
     uint64_t o = 8 + uint64_t(h->l_text);
-    if (o + 4 > d.size()) return fail(SECEDO_E_INVALID_ARG, f.path + ": truncated header");
-    h->n_ref = rd32(&d[o]);
+    if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated header") : kNeedMore;
+    h->n_ref = rd32(d + o);
     o += 4;
     for (uint32_t r = 0; r < h->n_ref; ++r) {
-        if (o + 4 > d.size()) return fail(SECEDO_E_INVALID_ARG, f.path + ": truncated reference list");
-        o += 4 + uint64_t(rd32(&d[o]));
-        if (o + 4 > d.size()) return fail(SECEDO_E_INVALID_ARG, f.path + ": truncated reference list");
+        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
+        o += 4 + uint64_t(rd32(d + o));
+        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
         o += 4;
     }
     h->first_record = o;
     return SECEDO_OK;
 }
 
-// One pass over the records: structure and sortedness checked; on_record(index, offset, refID, pos).
-template <class F>
-int walk_records(const Inflated &f, const Header &h, uint64_t *n_records, F on_record) {
-    const std::vector<uint8_t> &d = f.data;
-    uint64_t o = h.first_record, idx = 0;
+int parse_header(const Inflated &f, Header *h) {
+    return parse_header(f.path, f.data.data(), f.data.size(), true, h);
+}
+
+// The record walk of one file, carried across its block ranges.
+struct WalkState {
+    bool have_header = false;
+    Header h;
+    uint64_t idx = 0;
     int64_t prev_ref = -1, prev_pos = 0;
-    while (o < d.size()) {
-        const std::string where = f.path + ": record " + std::to_string(idx);
-        if (d.size() - o < 4 + 32) return fail(SECEDO_E_INVALID_ARG, where + " is truncated");
-        const uint32_t bs = rd32(&d[o]);
-        const uint8_t *c = &d[o + 4];
-        if (bs < 32 || bs > d.size() - o - 4) return fail(SECEDO_E_INVALID_ARG, where + " has a bad block_size");
+};
+
+// Walks the header (first) and the complete records of d[0, n), the file's inflated bytes that follow what earlier
+// calls consumed; *used = bytes consumed, the rest starts the next range. final: d ends the file, so a cut record is
+// an error. Structure and sortedness checked; on_record(index, record, refID, pos).
+template <class F>
+int walk_range(const std::string &path, const uint8_t *d, uint64_t n, bool final, WalkState *st, uint64_t *used,
+               F on_record) {
+    uint64_t o = 0;
+    *used = 0;
+    if (!st->have_header) {
+        const int rc = parse_header(path, d, n, final, &st->h);
+        if (rc == kNeedMore) return SECEDO_OK;
+        BAM_CALL(rc);
+        st->have_header = true;
+        o = st->h.first_record;
+    }
+    for (;; ++st->idx) {
+        *used = o;
+        if (o >= n) return SECEDO_OK;
+        const std::string where = path + ": record " + std::to_string(st->idx);
+        if (n - o < 4 + 32) return final ? fail(SECEDO_E_INVALID_ARG, where + " is truncated") : SECEDO_OK;
+        const uint32_t bs = rd32(d + o);
+        const uint8_t *c = d + o + 4;
+        if (bs < 32) return fail(SECEDO_E_INVALID_ARG, where + " has a bad block_size");
+        if (bs > n - o - 4) return final ? fail(SECEDO_E_INVALID_ARG, where + " has a bad block_size") : SECEDO_OK;
         const uint64_t need = 32 + uint64_t(c[8]) + 4ull * rd16(c + 12) + (uint64_t(rd32(c + 16)) + 1) / 2 +
                               uint64_t(rd32(c + 16));
         if (need > bs) return fail(SECEDO_E_INVALID_ARG, where + " is longer than its block_size");
         const int32_t ref = int32_t(rd32(c)), pos = int32_t(rd32(c + 4));
         const int64_t key_ref = ref < 0 ? INT64_MAX : ref;
-        if (idx > 0 && (key_ref < prev_ref || (key_ref == prev_ref && ref >= 0 && pos < prev_pos)))
+        if (st->idx > 0 && (key_ref < st->prev_ref || (key_ref == st->prev_ref && ref >= 0 && pos < st->prev_pos)))
             return fail(SECEDO_E_INVALID_ARG, where + ": input is not coordinate-sorted");
-        prev_ref = key_ref;
-        prev_pos = pos;
-        BAM_CALL(on_record(idx, o, ref, pos));
+        st->prev_ref = key_ref;
+        st->prev_pos = pos;
+        BAM_CALL(on_record(st->idx, d + o, ref, pos));
         o += 4 + uint64_t(bs);
-        ++idx;
     }
-    *n_records = idx;
+}
+
+// One pass over the records of a whole inflated file.
+template <class F>
+int walk_records(const Inflated &f, const Header &h, uint64_t *n_records, F on_record) {
+    WalkState st;
+    st.have_header = true;
+    st.h = h;
+    uint64_t used = 0;
+    BAM_CALL(walk_range(f.path, f.data.data() + h.first_record, f.data.size() - h.first_record, true, &st, &used,
+                        on_record));
+    *n_records = st.idx;
     return SECEDO_OK;
 }
 
@@ -254,6 +310,36 @@ int check_cigar(const uint8_t *rec, const std::string &where) {
     return SECEDO_OK;
 }
 
+// The value of the first aux field named by the tag, which the device's census found Z-typed (FindTag's walk).
+std::string first_z_value(const uint8_t *p, uint64_t len, const char *tag) {
+    uint64_t o = 0;
+    while (o + 3 <= len) {
+        const uint8_t type = p[o + 2];
+        o += 3;
+        if (p[o - 3] == uint8_t(tag[0]) && p[o - 2] == uint8_t(tag[1])) {
+            const uint64_t b = o;
+            while (o < len && p[o]) ++o;
+            return std::string(reinterpret_cast<const char *>(p + b), o - b);
+        }
+        uint64_t skip = 0;
+        switch (type) {
+            case 'A': case 'c': case 'C': skip = 1; break;
+            case 's': case 'S': skip = 2; break;
+            case 'f': case 'i': case 'I': skip = 4; break;
+            case 'Z': case 'H': while (o + skip < len && p[o + skip]) ++skip; ++skip; break;
+            case 'B': {
+                const uint8_t at = p[o];
+                const uint64_t es = (at == 'c' || at == 'C') ? 1 : (at == 's' || at == 'S') ? 2 : 4;
+                skip = 5 + uint64_t(rd32(p + o + 1)) * es;
+                break;
+            }
+            default: return std::string();
+        }
+        o += skip;
+    }
+    return std::string();
+}
+
 // the chromosome's records of every file, in the global order
 struct ChrInput {
     uint32_t chromosome;
@@ -264,9 +350,88 @@ struct ChrInput {
     std::vector<std::vector<uint64_t>> ridx;  // record index in the file (messages)
 };
 
+// Per file: its records of each requested chromosome, appended as the walk meets them (one range after another).
+struct FileSink {
+    const std::string &path;
+    size_t f;
+    std::vector<ChrInput> &chrs;
+    std::vector<std::vector<uint8_t> *> runs;  // [chr] this file's run
+    std::vector<int> started, done;
+    FileSink(const std::string &p, size_t file, std::vector<ChrInput> &c, std::vector<std::vector<std::vector<uint8_t>>> &r)
+        : path(p), f(file), chrs(c), runs(c.size()), started(c.size(), 0), done(c.size(), 0) {
+        for (size_t k = 0; k < c.size(); ++k) runs[k] = &r[k][file];
+    }
+    int operator()(uint64_t idx, const uint8_t *rec, int32_t ref, int32_t pos) {
+        for (size_t c = 0; c < chrs.size(); ++c) {
+            ChrInput &ci = chrs[c];
+            if (done[c]) continue;
+            if (ref < 0 || uint32_t(ref) != ci.chromosome) {
+                if (started[c]) done[c] = 1;  // the reader stops at another RefID
+                continue;
+            }
+            const std::string where = path + ": record " + std::to_string(idx);
+            if (pos < 0) return fail(SECEDO_E_INVALID_ARG, where + " has a negative position");
+            BAM_CALL(check_cigar(rec, where));
+            started[c] = 1;
+            std::vector<uint8_t> &run = *runs[c];
+            ci.roff[f].push_back(run.size());
+            ci.rpos[f].push_back(pos);
+            ci.ridx[f].push_back(idx);
+            run.insert(run.end(), rec, rec + 4 + rd32(rec));
+        }
+        return SECEDO_OK;
+    }
+};
+
+// One file larger than a batch, inflated and walked in ranges of BGZF blocks of about `batch` inflated bytes; a
+// record cut at a range's end is carried to the front of the next range. Host memory: one range plus the runs kept.
+int load_file_ranges(const std::string &path, size_t f, uint32_t threads, uint64_t batch, std::vector<ChrInput> *chrs,
+                     std::vector<std::vector<std::vector<uint8_t>>> *runs, secedo_bam_times *t) {
+    Mapped m;
+    BAM_CALL(map_file(path, &m));
+    std::vector<Block> blocks;
+    uint64_t total = 0;
+    BAM_CALL(list_blocks(path, m, &blocks, &total));
+    WalkState st;
+    FileSink sink(path, f, *chrs, *runs);
+    std::vector<uint8_t> buf;
+    uint64_t carry = 0;
+    size_t b0 = 0;
+    do {
+        size_t b1 = b0;
+        uint64_t bytes = 0;
+        while (b1 < blocks.size() && (b1 == b0 || bytes + blocks[b1].isize <= batch)) bytes += blocks[b1++].isize;
+        Clock::time_point t0 = Clock::now();
+        buf.resize(carry + bytes);
+        std::vector<std::string> errs(b1 - b0);
+        const uint64_t out0 = b1 > b0 ? blocks[b0].out : 0;
+        parallel_for(threads, b1 - b0, [&](uint64_t k) {
+            const Block &b = blocks[b0 + k];
+            errs[k] = inflate_block(b, buf.data() + carry + (b.out - out0));
+        });
+        for (size_t k = 0; k < errs.size(); ++k)
+            if (!errs[k].empty())
+                return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(b0 + k) + ": " + errs[k]);
+        if (t) {
+            t->inflate_ms += ms_since(t0);
+            t->inflated_bytes += double(bytes);
+        }
+        t0 = Clock::now();
+        uint64_t used = 0;
+        BAM_CALL(walk_range(path, buf.data(), buf.size(), b1 == blocks.size(), &st, &used, sink));
+        carry = buf.size() - used;
+        if (used) std::memmove(buf.data(), buf.data() + used, carry);
+        buf.resize(carry);
+        if (t) t->walk_ms += ms_since(t0);
+        b0 = b1;
+    } while (b0 < blocks.size());
+    return SECEDO_OK;
+}
+
 int load_inputs(const std::vector<std::string> &files, uint32_t threads, std::vector<ChrInput> *chrs,
                 secedo_bam_times *t) {
     const size_t n_files = files.size();
+    const uint64_t batch = batch_bytes();
     for (auto &c : *chrs) {
         c.file_base.assign(n_files, 0);
         c.roff.assign(n_files, {});
@@ -276,13 +441,18 @@ int load_inputs(const std::vector<std::string> &files, uint32_t threads, std::ve
     std::vector<std::vector<std::vector<uint8_t>>> runs(chrs->size(), std::vector<std::vector<uint8_t>>(n_files));
     size_t f0 = 0;
     while (f0 < n_files) {
-        // a batch of files of at most kBatchBytes on disk (BGZF inflates 3-4x), at least one file
+        // a batch of files of at most `batch` bytes on disk (BGZF inflates 3-4x), at least one file
         size_t f1 = f0;
         uint64_t disk = 0;
-        while (f1 < n_files && (f1 == f0 || disk < kBatchBytes / 4)) {
+        while (f1 < n_files && (f1 == f0 || disk < batch / 4)) {
             struct stat st;
             disk += stat(files[f1].c_str(), &st) == 0 ? uint64_t(st.st_size) : 0;
             ++f1;
+        }
+        if (f1 == f0 + 1) {  // one file: walked in block ranges (one range when it inflates to at most `batch`)
+            BAM_CALL(load_file_ranges(files[f0], f0, threads, batch, chrs, &runs, t));
+            f0 = f1;
+            continue;
         }
         std::vector<Inflated> inf;
         Clock::time_point t0 = Clock::now();
@@ -295,38 +465,12 @@ int load_inputs(const std::vector<std::string> &files, uint32_t threads, std::ve
         std::vector<int> rcs(inf.size(), SECEDO_OK);
         std::vector<std::string> errs(inf.size());
         parallel_for(threads, inf.size(), [&](uint64_t k) {
-            const size_t f = f0 + k;
-            Header h;
-            int rc = parse_header(inf[k], &h);
-            std::vector<uint64_t> first(chrs->size(), UINT64_MAX), last(chrs->size(), 0);
-            std::vector<int> done(chrs->size(), 0);
-            uint64_t n = 0;
-            if (rc == SECEDO_OK)
-                rc = walk_records(inf[k], h, &n, [&](uint64_t idx, uint64_t o, int32_t ref, int32_t pos) {
-                    for (size_t c = 0; c < chrs->size(); ++c) {
-                        ChrInput &ci = (*chrs)[c];
-                        if (done[c]) continue;
-                        if (ref < 0 || uint32_t(ref) != ci.chromosome) {
-                            if (first[c] != UINT64_MAX) done[c] = 1;  // the reader stops at another RefID
-                            continue;
-                        }
-                        const std::string where = files[f] + ": record " + std::to_string(idx);
-                        if (pos < 0) return fail(SECEDO_E_INVALID_ARG, where + " has a negative position");
-                        BAM_CALL(check_cigar(&inf[k].data[o], where));
-                        if (first[c] == UINT64_MAX) first[c] = o;
-                        last[c] = o + 4 + rd32(&inf[k].data[o]);
-                        ci.roff[f].push_back(o - first[c]);
-                        ci.rpos[f].push_back(pos);
-                        ci.ridx[f].push_back(idx);
-                    }
-                    return SECEDO_OK;
-                });
-            if (rc == SECEDO_OK)
-                for (size_t c = 0; c < chrs->size(); ++c)
-                    if (first[c] != UINT64_MAX)
-                        runs[c][f].assign(inf[k].data.begin() + first[c], inf[k].data.begin() + last[c]);
-            rcs[k] = rc;
+            WalkState st;
+            FileSink sink(files[f0 + k], f0 + k, *chrs, runs);
+            uint64_t used = 0;
+            rcs[k] = walk_range(files[f0 + k], inf[k].data.data(), inf[k].data.size(), true, &st, &used, sink);
             errs[k] = g_error;
+            std::vector<uint8_t>().swap(inf[k].data);
         });
         for (size_t k = 0; k < inf.size(); ++k)
             if (rcs[k] != SECEDO_OK) return fail(rcs[k], errs[k]);
@@ -400,9 +544,142 @@ struct ChrOut {
     std::vector<uint64_t> ord_off;  // per ordinal: byte offset in ChrInput::bytes
 };
 
-// The device passes of one chromosome, appended to `res`.
-int run_chromosome(const ChrInput &ci, const Params &prm, const uint16_t *d_i2g, uint32_t n_groups, bool want_map,
-                   hipStream_t s, Result *res, ChrOut *co, secedo_bam_times *t) {
+// The listed barcodes of tag mode on the device: packed values, their hashes sorted, the cell of each.
+struct DevCells {
+    Dev<uint8_t> bytes;
+    Dev<uint32_t> off, cell;
+    Dev<uint64_t> hash;
+    CellList list{};
+};
+
+int upload_cells(const char tag[2], const std::vector<std::string> &values, hipStream_t s, DevCells *dc) {
+    const uint32_t n = uint32_t(values.size());
+    std::vector<uint8_t> bytes;
+    std::vector<uint32_t> off{0};
+    for (const auto &v : values) {
+        bytes.insert(bytes.end(), v.begin(), v.end());
+        off.push_back(uint32_t(bytes.size()));
+    }
+    Dev<uint64_t> h;
+    Dev<uint32_t> idx;
+    BAM_TRY(dc->bytes.alloc(bytes.size()));
+    BAM_TRY(dc->off.alloc(n + 1));
+    BAM_TRY(dc->hash.alloc(n));
+    BAM_TRY(dc->cell.alloc(n));
+    BAM_TRY(h.alloc(n));
+    BAM_TRY(idx.alloc(n));
+    if (!bytes.empty()) BAM_TRY(hipMemcpyAsync(dc->bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+    BAM_TRY(hipMemcpyAsync(dc->off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
+    BAM_TRY(list_hash(dc->bytes.p, dc->off.p, n, h.p, idx.p, s));
+    const size_t tb = sort_pairs_bytes(n);
+    Dev<uint8_t> tmp;
+    BAM_TRY(tmp.alloc(tb));
+    BAM_TRY(sort_pairs(tmp.p, tb, h.p, dc->hash.p, idx.p, dc->cell.p, n, s));
+    BAM_TRY(hipStreamSynchronize(s));
+    dc->list = CellList{dc->bytes.p, dc->off.p, dc->hash.p, dc->cell.p, n, uint8_t(tag[0]), uint8_t(tag[1])};
+    return SECEDO_OK;
+}
+
+// The chromosome's records in input order (file, record): byte offsets in ci.bytes, input file, record index.
+void input_order(const ChrInput &ci, std::vector<uint64_t> *off, std::vector<uint32_t> *file,
+                 std::vector<uint64_t> *idx) {
+    for (size_t f = 0; f < ci.roff.size(); ++f)
+        for (size_t k = 0; k < ci.roff[f].size(); ++k) {
+            off->push_back(ci.file_base[f] + ci.roff[f][k]);
+            if (file) file->push_back(uint32_t(f));
+            if (idx) idx->push_back(ci.ridx[f][k]);
+        }
+}
+
+// Selected (key, input ordinal) pairs of d_key / d_sel (n records), sorted by key: -> *n_sel, d_ks, d_vs.
+int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
+                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs) {
+    Dev<uint32_t> scan, vc;
+    Dev<uint64_t> kc;
+    Dev<uint8_t> tmp;
+    size_t tb = scan_bytes(uint64_t(n) + 1);
+    BAM_TRY(tmp.alloc(tb));
+    BAM_TRY(scan.alloc(n + 1));
+    BAM_TRY(hipMemsetAsync(d_sel.p + n, 0, 4, s));
+    BAM_TRY(exclusive_sum(tmp.p, tb, d_sel.p, scan.p, uint64_t(n) + 1, s));
+    *n_sel = 0;
+    BAM_TRY(hipMemcpyAsync(n_sel, scan.p + n, 4, hipMemcpyDeviceToHost, s));
+    BAM_TRY(hipStreamSynchronize(s));
+    const uint32_t m = *n_sel;
+    BAM_TRY(kc.alloc(m));
+    BAM_TRY(vc.alloc(m));
+    BAM_TRY(d_ks->alloc(m));
+    BAM_TRY(d_vs->alloc(m));
+    BAM_TRY(compact_keys(d_key.p, d_sel.p, scan.p, n, kc.p, vc.p, s));
+    tb = sort_pairs_bytes(m);
+    BAM_TRY(tmp.alloc(tb));
+    BAM_TRY(sort_pairs(tmp.p, tb, kc.p, d_ks->p, vc.p, d_vs->p, m, s));  // radix sort: stable
+    BAM_TRY(hipStreamSynchronize(s));
+    return SECEDO_OK;
+}
+
+// Where the records of the global order come from, for error messages and the .map.
+struct Order {
+    uint32_t n = 0, last_chunk = 0;
+    int32_t min_pos = INT32_MAX;
+    std::vector<uint64_t> ord_off;  // per-file mode: per ordinal byte offset, input file, record index
+    std::vector<uint16_t> ord_file;
+    std::vector<uint64_t> ord_idx;
+    std::vector<uint32_t> in_file;  // tag mode: per input ordinal; d_ord maps an ordinal to its input ordinal
+    std::vector<uint64_t> in_idx;
+    Dev<uint32_t> d_ord;
+};
+
+// Tag mode: the records in input order go up, the device selects the listed cells and sorts them into the global
+// order (chunk, cell, Position, file, record) -> d_off / d_cell of the selected records.
+int order_by_cell(const ChrInput &ci, const CellList &L, hipStream_t s, Dev<uint8_t> *d_bytes, Dev<uint64_t> *d_off,
+                  Dev<uint16_t> *d_cell, Order *ord, secedo_bam_times *t) {
+    Clock::time_point t0 = Clock::now();
+    std::vector<uint64_t> in_off;
+    input_order(ci, &in_off, &ord->in_file, &ord->in_idx);
+    if (in_off.size() >= (1ull << 32)) return fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome");
+    const uint32_t n_in = uint32_t(in_off.size());
+    if (t) t->walk_ms += ms_since(t0);
+    t0 = Clock::now();
+    Dev<uint64_t> d_in_off;
+    BAM_TRY(d_bytes->alloc(ci.bytes.size()));
+    BAM_TRY(d_in_off.alloc(n_in));
+    if (!ci.bytes.empty())
+        BAM_TRY(hipMemcpyAsync(d_bytes->p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
+    if (n_in) BAM_TRY(hipMemcpyAsync(d_in_off.p, in_off.data(), n_in * 8ull, hipMemcpyHostToDevice, s));
+    BAM_TRY(hipStreamSynchronize(s));
+    if (t) t->upload_ms += ms_since(t0);
+    t0 = Clock::now();
+    Dev<uint64_t> key, ks;
+    Dev<uint32_t> sel, vs;
+    BAM_TRY(key.alloc(n_in));
+    BAM_TRY(sel.alloc(n_in + 1));
+    BAM_TRY(cells(d_bytes->p, d_in_off.p, n_in, L, key.p, sel.p, s));
+    uint32_t n = 0;
+    BAM_CALL(compact_and_sort(key, sel, n_in, s, &n, &ks, &vs));
+    key.reset();
+    sel.reset();
+    BAM_TRY(d_off->alloc(n));
+    BAM_TRY(d_cell->alloc(n));
+    BAM_TRY(ord->d_ord.alloc(n));
+    BAM_TRY(order_records(ks.p, vs.p, d_in_off.p, n, d_off->p, d_cell->p, ord->d_ord.p, s));
+    ord->n = n;
+    if (n) {
+        uint64_t k0 = 0, k1 = 0;
+        BAM_TRY(hipMemcpyAsync(&k0, ks.p, 8, hipMemcpyDeviceToHost, s));
+        BAM_TRY(hipMemcpyAsync(&k1, ks.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+        BAM_TRY(hipStreamSynchronize(s));
+        ord->min_pos = int32_t(uint32_t(k0 >> 46) * kChunk);  // the first window starts at or before it
+        ord->last_chunk = uint32_t(k1 >> 46);
+    }
+    BAM_TRY(hipStreamSynchronize(s));
+    if (t) t->device_ms += ms_since(t0);
+    return SECEDO_OK;
+}
+
+// Per-file mode: the global order (chunk of Position, file, record) built on the host, then uploaded.
+int order_by_file(const ChrInput &ci, hipStream_t s, Dev<uint8_t> *d_bytes, Dev<uint64_t> *d_off,
+                  Dev<uint16_t> *d_file, Order *ord, secedo_bam_times *t) {
     const size_t n_files = ci.roff.size();
     Clock::time_point t0 = Clock::now();
     // global order: chunk of Position, file, record
@@ -418,9 +695,9 @@ int run_chromosome(const ChrInput &ci, const Params &prm, const uint16_t *d_i2g,
     if (n64 >= (1ull << 32)) return fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome");
     const uint32_t n = uint32_t(n64);
     const uint32_t last_chunk = max_pos < 0 ? 0 : uint32_t(max_pos) / kChunk;
-    std::vector<uint64_t> ord_off;
-    std::vector<uint16_t> ord_file;
-    std::vector<uint64_t> ord_idx;
+    std::vector<uint64_t> &ord_off = ord->ord_off;
+    std::vector<uint16_t> &ord_file = ord->ord_file;
+    std::vector<uint64_t> &ord_idx = ord->ord_idx;
     ord_off.reserve(n);
     ord_file.reserve(n);
     ord_idx.reserve(n);
@@ -436,21 +713,35 @@ int run_chromosome(const ChrInput &ci, const Params &prm, const uint16_t *d_i2g,
     }
     if (t) t->walk_ms += ms_since(t0);
     t0 = Clock::now();
-    Dev<uint8_t> d_bytes;
-    Dev<uint64_t> d_off;
-    Dev<uint16_t> d_file;
-    BAM_TRY(d_bytes.alloc(ci.bytes.size()));
-    BAM_TRY(d_off.alloc(n));
-    BAM_TRY(d_file.alloc(n));
+    BAM_TRY(d_bytes->alloc(ci.bytes.size()));
+    BAM_TRY(d_off->alloc(n));
+    BAM_TRY(d_file->alloc(n));
     if (!ci.bytes.empty())
-        BAM_TRY(hipMemcpyAsync(d_bytes.p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
+        BAM_TRY(hipMemcpyAsync(d_bytes->p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
     if (n) {
-        BAM_TRY(hipMemcpyAsync(d_off.p, ord_off.data(), n * 8ull, hipMemcpyHostToDevice, s));
-        BAM_TRY(hipMemcpyAsync(d_file.p, ord_file.data(), n * 2ull, hipMemcpyHostToDevice, s));
+        BAM_TRY(hipMemcpyAsync(d_off->p, ord_off.data(), n * 8ull, hipMemcpyHostToDevice, s));
+        BAM_TRY(hipMemcpyAsync(d_file->p, ord_file.data(), n * 2ull, hipMemcpyHostToDevice, s));
     }
     BAM_TRY(hipStreamSynchronize(s));
     if (t) t->upload_ms += ms_since(t0);
-    t0 = Clock::now();
+    ord->n = n;
+    ord->min_pos = min_pos;
+    ord->last_chunk = last_chunk;
+    return SECEDO_OK;
+}
+
+// The device passes of one chromosome, appended to `res`. cells: tag mode's list, or null for per-file mode.
+int run_chromosome(const ChrInput &ci, const Params &prm, const CellList *cells, const uint16_t *d_i2g,
+                   uint32_t n_groups, bool want_map, hipStream_t s, Result *res, ChrOut *co, secedo_bam_times *t) {
+    Order ord;
+    Dev<uint8_t> d_bytes;
+    Dev<uint64_t> d_off;
+    Dev<uint16_t> d_file;
+    if (cells) BAM_CALL(order_by_cell(ci, *cells, s, &d_bytes, &d_off, &d_file, &ord, t));
+    else BAM_CALL(order_by_file(ci, s, &d_bytes, &d_off, &d_file, &ord, t));
+    const uint32_t n = ord.n, last_chunk = ord.last_chunk;
+    const int32_t min_pos = ord.min_pos;
+    Clock::time_point t0 = Clock::now();
 
     const Records rs{d_bytes.p, d_off.p, d_file.p, n};
     Dev<uint64_t> key, key2;
@@ -480,8 +771,18 @@ int run_chromosome(const ChrInput &ci, const Params &prm, const uint16_t *d_i2g,
                                      "walks past the end of its CIGAR", "has a D op over a base",
                                      "reads past its quality string", "has a negative position"};
         const uint32_t o = uint32_t(h_err >> 8), code = uint32_t(h_err & 0xFF);
-        return fail(SECEDO_E_INVALID_ARG, "file " + std::to_string(ord_file[o]) + ", record " +
-                                              std::to_string(ord_idx[o]) + ": " + (code < 7 ? what[code] : "?"));
+        uint64_t file = 0, idx = 0;
+        if (cells) {  // the input file and record of ordinal o
+            uint32_t i = 0;
+            BAM_TRY(hipMemcpy(&i, ord.d_ord.p + o, 4, hipMemcpyDeviceToHost));
+            file = ord.in_file[i];
+            idx = ord.in_idx[i];
+        } else {
+            file = ord.ord_file[o];
+            idx = ord.ord_idx[o];
+        }
+        return fail(SECEDO_E_INVALID_ARG, "file " + std::to_string(file) + ", record " + std::to_string(idx) + ": " +
+                                              (code < 7 ? what[code] : "?"));
     }
     // name numbering
     Dev<uint8_t> tmp;
@@ -513,7 +814,12 @@ int run_chromosome(const ChrInput &ci, const Params &prm, const uint16_t *d_i2g,
             BAM_TRY(hipStreamSynchronize(s));
         }
         for (uint32_t o = 0; o < n; ++o) co->first[o] = uint8_t(fl[o]);
-        co->ord_off = ord_off;
+        if (cells) {
+            co->ord_off.resize(n);
+            if (n) BAM_TRY(hipMemcpy(co->ord_off.data(), d_off.p, n * 8ull, hipMemcpyDeviceToHost));
+        } else {
+            co->ord_off = ord.ord_off;
+        }
     }
     flag.reset();
     scan.reset();
@@ -687,20 +993,54 @@ int write_files(const std::string &prefix, bool text, uint32_t chromosome_id, co
     return (fclose(ft) == 0 && ok) ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, "Could not write " + prefix);
 }
 
+// tag: two characters [A-Za-z][A-Za-z0-9] (SAM spec 1.5)
+int check_tag(const char *tag) {
+    if (!tag) return fail(SECEDO_E_INVALID_ARG, "null tag");
+    const auto alpha = [](char c) { return (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z'); };
+    if (!alpha(tag[0]) || !(alpha(tag[1]) || (tag[1] >= '0' && tag[1] <= '9')))
+        return fail(SECEDO_E_INVALID_ARG, "a tag is two characters [A-Za-z][A-Za-z0-9]");
+    return SECEDO_OK;
+}
+
+// the barcode list of tag mode: non-empty, at most SECEDO_BAM_MAX_FILES, no value twice
+int check_cells(const char *tag, const char *const *barcodes, uint32_t n, std::vector<std::string> *values) {
+    BAM_CALL(check_tag(tag));
+    if (n == 0 || !barcodes) return fail(SECEDO_E_INVALID_ARG, "an empty barcode list");
+    if (n > SECEDO_BAM_MAX_FILES)
+        return fail(SECEDO_E_LIMIT, "more than 16384 barcodes: cell ids do not fit cell << 2 | base in 16 bits");
+    std::set<std::string> seen;
+    for (uint32_t c = 0; c < n; ++c) {
+        if (!barcodes[c]) return fail(SECEDO_E_INVALID_ARG, "null barcode");
+        values->emplace_back(barcodes[c]);
+        if (!seen.insert(values->back()).second)
+            return fail(SECEDO_E_INVALID_ARG, "barcode " + values->back() + " is listed twice");
+    }
+    return SECEDO_OK;
+}
+
+int check_files(const char *const *bam_files, uint32_t n_files, std::vector<std::string> *files) {
+    for (uint32_t f = 0; f < n_files; ++f) {
+        if (!bam_files[f]) return fail(SECEDO_E_INVALID_ARG, "null file name");
+        files->emplace_back(bam_files[f]);
+    }
+    return SECEDO_OK;
+}
+
+// tag null: per-file mode (cell = file index); else tag mode with the listed barcodes
 int run(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids, uint32_t n_chr,
         const char *out_pileup, bool text, const Params &base, uint32_t num_threads, const uint16_t *id_to_group,
-        uint32_t n_ids, secedo_bam_result_info *info, secedo_bam_times *times) {
+        uint32_t n_ids, const char *tag, const char *const *barcodes, uint32_t n_barcodes,
+        secedo_bam_result_info *info, secedo_bam_times *times) {
     const Clock::time_point t_all = Clock::now();
     secedo_bam_times tl{};
     if (!info || (n_files && !bam_files) || (n_chr && !chromosome_ids))
         return fail(SECEDO_E_INVALID_ARG, "null argument");
-    if (n_files > SECEDO_BAM_MAX_FILES)
+    std::vector<std::string> values;
+    if (tag) BAM_CALL(check_cells(tag, barcodes, n_barcodes, &values));
+    else if (n_files > SECEDO_BAM_MAX_FILES)
         return fail(SECEDO_E_LIMIT, "more than 16384 BAM files: cell ids do not fit cell << 2 | base in 16 bits");
     std::vector<std::string> files;
-    for (uint32_t f = 0; f < n_files; ++f) {
-        if (!bam_files[f]) return fail(SECEDO_E_INVALID_ARG, "null file name");
-        files.emplace_back(bam_files[f]);
-    }
+    BAM_CALL(check_files(bam_files, n_files, &files));
     delete g_result;
     g_result = new Result();
     Result *res = g_result;
@@ -718,6 +1058,8 @@ int run(const char *const *bam_files, uint32_t n_files, const uint32_t *chromoso
         BAM_TRY(d_i2g.alloc(n_ids));
         if (n_ids) BAM_TRY(hipMemcpy(d_i2g.p, id_to_group, n_ids * 2ull, hipMemcpyHostToDevice));
     }
+    DevCells dc;
+    if (tag) BAM_CALL(upload_cells(tag, values, s, &dc));
     BAM_TRY(res->off.grow(1, 0, s));
     BAM_TRY(hipMemsetAsync(res->off.p, 0, 8, s));
     for (uint32_t c = 0; c < n_chr; ++c) {
@@ -725,8 +1067,8 @@ int run(const char *const *bam_files, uint32_t n_files, const uint32_t *chromoso
         p.chromosome = chromosome_ids[c];
         ChrOut co;
         const uint64_t l0 = res->n_loci, e0 = res->n_entries;
-        BAM_CALL(run_chromosome(chrs[c], p, id_to_group ? d_i2g.p : nullptr, n_ids, out_pileup != nullptr, s, res,
-                                &co, &tl));
+        BAM_CALL(run_chromosome(chrs[c], p, tag ? &dc.list : nullptr, id_to_group ? d_i2g.p : nullptr, n_ids,
+                                out_pileup != nullptr, s, res, &co, &tl));
         res->chr_locus_off.push_back(uint32_t(res->n_loci));
         if (out_pileup) {
             const Clock::time_point t0 = Clock::now();
@@ -757,6 +1099,97 @@ int run(const char *const *bam_files, uint32_t n_files, const uint32_t *chromoso
     return SECEDO_OK;
 }
 
+// the distinct tag values over the requested chromosomes, sorted bytewise, and their record counts
+struct Barcodes {
+    std::vector<std::string> values;
+    std::vector<uint64_t> counts;
+};
+
+thread_local Barcodes *g_barcodes = nullptr;
+
+// one chromosome's distinct values (device: hash, sort, exact split of equal-hash runs) added to `acc`
+int count_values(const ChrInput &ci, const char *tag, hipStream_t s, std::map<std::string, uint64_t> *acc) {
+    std::vector<uint64_t> in_off;
+    input_order(ci, &in_off, nullptr, nullptr);
+    if (in_off.size() >= (1ull << 32)) return fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome");
+    const uint32_t n_in = uint32_t(in_off.size());
+    if (n_in == 0) return SECEDO_OK;
+    Dev<uint8_t> d_bytes, tmp;
+    Dev<uint64_t> d_in_off, key, ks, voff;
+    Dev<uint32_t> sel, vs, run, cnt, vlen;
+    BAM_TRY(d_bytes.alloc(ci.bytes.size()));
+    BAM_TRY(d_in_off.alloc(n_in));
+    BAM_TRY(hipMemcpyAsync(d_bytes.p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
+    BAM_TRY(hipMemcpyAsync(d_in_off.p, in_off.data(), n_in * 8ull, hipMemcpyHostToDevice, s));
+    BAM_TRY(key.alloc(n_in));
+    BAM_TRY(sel.alloc(n_in + 1));
+    const uint8_t t0 = uint8_t(tag[0]), t1 = uint8_t(tag[1]);
+    BAM_TRY(tag_keys(d_bytes.p, d_in_off.p, n_in, t0, t1, key.p, sel.p, s));
+    uint32_t n = 0;
+    BAM_CALL(compact_and_sort(key, sel, n_in, s, &n, &ks, &vs));
+    if (n == 0) return SECEDO_OK;
+    const size_t tb = scan_bytes(n);
+    BAM_TRY(tmp.alloc(tb));
+    BAM_TRY(run.alloc(n));
+    BAM_TRY(cnt.alloc(n));
+    BAM_TRY(hipMemsetAsync(cnt.p, 0, n * 4ull, s));
+    BAM_TRY(tag_count(d_bytes.p, d_in_off.p, t0, t1, ks.p, vs.p, run.p, n, cnt.p, tmp.p, tb, s));
+    std::vector<uint32_t> h_cnt(n), h_val(n);
+    BAM_TRY(hipMemcpyAsync(h_cnt.data(), cnt.p, n * 4ull, hipMemcpyDeviceToHost, s));
+    BAM_TRY(hipMemcpyAsync(h_val.data(), vs.p, n * 4ull, hipMemcpyDeviceToHost, s));
+    BAM_TRY(hipStreamSynchronize(s));
+    for (uint32_t j = 0; j < n; ++j) {
+        if (!h_cnt[j]) continue;
+        // the value of the record that first showed it: the first aux field named by the tag, Z-typed (the device
+        // pass found it there)
+        const uint8_t *rec = ci.bytes.data() + in_off[h_val[j]];
+        const uint32_t bs = rd32(rec);
+        const uint8_t *c = rec + 4;
+        const uint64_t aux = 32 + uint64_t(c[8]) + 4ull * rd16(c + 12) + (uint64_t(rd32(c + 16)) + 1) / 2 +
+                             uint64_t(rd32(c + 16));
+        const std::string v = first_z_value(c + aux, bs - aux, tag);
+        (*acc)[v] += h_cnt[j];
+    }
+    return SECEDO_OK;
+}
+
+int barcodes(const char *const *bam_files, uint32_t n_files, const char *tag, const uint32_t *chromosome_ids,
+             uint32_t n_chr, uint32_t num_threads, uint32_t *n_values, uint64_t *bytes) {
+    if (!n_values || !bytes || (n_files && !bam_files) || (n_chr && !chromosome_ids))
+        return fail(SECEDO_E_INVALID_ARG, "null argument");
+    BAM_CALL(check_tag(tag));
+    std::vector<std::string> files;
+    BAM_CALL(check_files(bam_files, n_files, &files));
+    delete g_barcodes;
+    g_barcodes = nullptr;
+    std::vector<ChrInput> chrs(n_chr);
+    for (uint32_t c = 0; c < n_chr; ++c) chrs[c].chromosome = chromosome_ids[c];
+    BAM_CALL(load_inputs(files, num_threads ? num_threads : 1, &chrs, nullptr));
+    hipStream_t s;
+    BAM_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    struct StreamGuard {
+        hipStream_t s;
+        ~StreamGuard() { (void)hipStreamDestroy(s); }
+    } guard{s};
+    std::map<std::string, uint64_t> acc;
+    for (uint32_t c = 0; c < n_chr; ++c) {
+        BAM_CALL(count_values(chrs[c], tag, s, &acc));
+        std::vector<uint8_t>().swap(chrs[c].bytes);
+    }
+    if (acc.size() > UINT32_MAX) return fail(SECEDO_E_LIMIT, "more than 2^32 distinct values");
+    Barcodes *b = new Barcodes();
+    uint64_t total = 0;
+    for (const auto &kv : acc) {
+        b->values.push_back(kv.first);
+        b->counts.push_back(kv.second);
+        total += kv.first.size();
+    }
+    g_barcodes = b;
+    *n_values = uint32_t(b->values.size());
+    *bytes = total;
+    return SECEDO_OK;
+}
+
 Params make_params(uint32_t max_coverage, uint32_t min_base_quality, uint32_t min_map_quality,
                    uint32_t min_alignment_score, uint16_t min_different) {
     Params p{};
@@ -784,7 +1217,7 @@ int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_bam_scan_info
     std::vector<uint64_t> per(h.n_ref, 0);
     uint64_t n = 0, unmapped = 0;
     int sorted = 1;
-    int rc = walk_records(inf[0], h, &n, [&](uint64_t, uint64_t, int32_t ref, int32_t) {
+    int rc = walk_records(inf[0], h, &n, [&](uint64_t, const uint8_t *, int32_t ref, int32_t) {
         if (ref < 0) ++unmapped;
         else if (uint32_t(ref) < h.n_ref) ++per[ref];
         return SECEDO_OK;
@@ -825,7 +1258,7 @@ int secedo_pileup_bams(const char *const *bam_files, uint32_t n_files, const cha
                        uint16_t min_different, secedo_bam_result_info *info, secedo_bam_times *times) {
     const Params p = make_params(max_coverage, min_base_quality, min_map_quality, min_alignment_score, min_different);
     return run(bam_files, n_files, &chromosome_id, 1, out_pileup, write_text_file != 0, p, num_threads, nullptr, 0,
-               info, times);
+               nullptr, nullptr, 0, info, times);
 }
 
 int secedo_pileup_bams_device(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
@@ -834,8 +1267,52 @@ int secedo_pileup_bams_device(const char *const *bam_files, uint32_t n_files, co
                               uint16_t min_different, const uint16_t *id_to_group, uint32_t n_ids,
                               secedo_bam_result_info *info, secedo_bam_times *times) {
     const Params p = make_params(max_coverage, min_base_quality, min_map_quality, min_alignment_score, min_different);
-    return run(bam_files, n_files, chromosome_ids, n_chr, nullptr, false, p, num_threads, id_to_group, n_ids, info,
-               times);
+    return run(bam_files, n_files, chromosome_ids, n_chr, nullptr, false, p, num_threads, id_to_group, n_ids,
+               nullptr, nullptr, 0, info, times);
+}
+
+int secedo_pileup_bams_cells(const char *const *bam_files, uint32_t n_files, const char *out_pileup,
+                             int write_text_file, uint32_t chromosome_id, uint32_t max_coverage,
+                             uint32_t min_base_quality, uint32_t min_map_quality, uint32_t min_alignment_score,
+                             uint32_t num_threads, uint16_t min_different, const char tag[2],
+                             const char *const *barcodes, uint32_t n_barcodes, secedo_bam_result_info *info,
+                             secedo_bam_times *times) {
+    const Params p = make_params(max_coverage, min_base_quality, min_map_quality, min_alignment_score, min_different);
+    if (!tag) return fail(SECEDO_E_INVALID_ARG, "null tag");
+    return run(bam_files, n_files, &chromosome_id, 1, out_pileup, write_text_file != 0, p, num_threads, nullptr, 0,
+               tag, barcodes, n_barcodes, info, times);
+}
+
+int secedo_pileup_bams_cells_device(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                                    uint32_t n_chr, uint32_t max_coverage, uint32_t min_base_quality,
+                                    uint32_t min_map_quality, uint32_t min_alignment_score, uint32_t num_threads,
+                                    uint16_t min_different, const uint16_t *id_to_group, uint32_t n_ids,
+                                    const char tag[2], const char *const *barcodes, uint32_t n_barcodes,
+                                    secedo_bam_result_info *info, secedo_bam_times *times) {
+    const Params p = make_params(max_coverage, min_base_quality, min_map_quality, min_alignment_score, min_different);
+    if (!tag) return fail(SECEDO_E_INVALID_ARG, "null tag");
+    return run(bam_files, n_files, chromosome_ids, n_chr, nullptr, false, p, num_threads, id_to_group, n_ids, tag,
+               barcodes, n_barcodes, info, times);
+}
+
+int secedo_bam_barcodes(const char *const *bam_files, uint32_t n_files, const char tag[2],
+                        const uint32_t *chromosome_ids, uint32_t n_chr, uint32_t num_threads, uint32_t *n_barcodes,
+                        uint64_t *bytes) {
+    return barcodes(bam_files, n_files, tag, chromosome_ids, n_chr, num_threads, n_barcodes, bytes);
+}
+
+int secedo_bam_barcodes_fetch(char *values, uint64_t *value_off, uint64_t *counts) {
+    const Barcodes *b = g_barcodes;
+    if (!b) return fail(SECEDO_E_STATE, "no secedo_bam_barcodes result on this thread");
+    uint64_t o = 0;
+    for (size_t k = 0; k < b->values.size(); ++k) {
+        if (values) std::memcpy(values + o, b->values[k].data(), b->values[k].size());
+        if (value_off) value_off[k] = o;
+        if (counts) counts[k] = b->counts[k];
+        o += b->values[k].size();
+    }
+    if (value_off) value_off[b->values.size()] = o;
+    return SECEDO_OK;
 }
 
 int secedo_bam_fetch(uint32_t *chr_locus_off, uint32_t *locus_pos, uint64_t *locus_entry_off, uint32_t *read_ids,

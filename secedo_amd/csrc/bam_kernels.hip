@@ -9,6 +9,13 @@
 //     (file % 100, MAX_OPEN_FILES): files 0 and 100 share one. Every selected record takes an id before its
 //     base loop, filtered or not.
 //  3. Cell id = global file index, cell_base = cell << 2 | base (the host refuses more than 16384 files).
+//  3b. Tag mode (secedo_pileup_bams_cells): the cell is the index of the record's barcode in the list, the barcode
+//     being the value of the first aux field named by the tag (FindTag) when it is Z-typed. A record without the
+//     tag, with a tag of another type or with an unlisted value is not selected: it takes no read id, is not
+//     checked against rule 6 and gives nothing. The global order of rules 2 and 8 becomes (chunk of Position,
+//     cell, Position, input file, record), which is per-file mode on the per-cell split files; the name maps are
+//     per slot cell % 100. The host's structural checks (sortedness, CIGAR against SEQ, negative position) still
+//     cover every record of the chromosome. At most 16384 barcodes.
 //  4. Base walk (:94-155) over BamTools' AlignedBases (BuildCharData): M/I/=/X copy the bases, D gives '-',
 //     N gives 'N', P gives '*', S/H give nothing. Only leading H/S ops are skipped; I advances `offset`; an I
 //     as the last op ends the read; the quality index is i + offset - del_offset (a leading soft clip is not
@@ -29,6 +36,13 @@
 //  8. Entry order in a locus: (chunk of the record's Position, file, record) = the global ordinal; one record
 //     gives at most one base per position. When the counter wrapped, the stored entries are the last
 //     (arrivals mod 2^16) arrivals: slots 0..c-1 were overwritten by the last cycle.
+//
+// Tag mode first runs the front passes: cells (one thread per uploaded record, input order: FindTag walk, hash of the
+// value, lower bound in the hash-sorted list, exact byte compare over the run of equal hashes) -> compaction of the
+// selected records (scan) -> stable hipcub sort by chunk << 46 | cell << 32 | Position with the input ordinal as
+// value -> order (byte offset, cell and input ordinal per global ordinal), which is the Records the chain below
+// takes. The barcode census (secedo_bam_barcodes) hashes every Z-typed value, sorts, and splits each run of equal
+// hashes by exact compare into distinct values with their record counts.
 //
 // Passes: decode (one thread per record) -> hipcub sort by (slot-name hash, ordinal) -> first_occurrence with
 // an exact byte compare inside each run of equal hashes -> exclusive scan of first-occurrence flags = ids.
@@ -87,28 +101,24 @@ __device__ __forceinline__ uint32_t op_len(const Rec &r, uint32_t i) { return ld
 __device__ __forceinline__ bool copies_bases(uint32_t t) { return t == kOpM || t == kOpI || t == kOpEq || t == kOpX; }
 __device__ __forceinline__ bool writes_char(uint32_t t) { return copies_bases(t) || t == kOpD || t == kOpN || t == kOpP; }
 
-// GetTag("AS", uint32_t&) from 0 (BamAlignment::FindTag / SkipToNextTag / TagTypeHelper<uint32_t>)
-__device__ uint32_t alignment_score(const Rec &r) {
+// BamAlignment::FindTag / SkipToNextTag: the first aux field named t0 t1. Returns its value (null when absent or
+// when the walk gives up on an unknown storage type), *type its storage type, *avail the aux bytes from the value on.
+__device__ const uint8_t *find_tag(const Rec &r, uint8_t t0, uint8_t t1, uint8_t *type, uint32_t *avail) {
     const uint8_t *p = r.aux;
     const uint32_t len = r.l_aux;
     uint32_t parsed = 0;
     while (parsed < len) {
-        if (parsed + 3 > len) return 0;
-        const uint8_t t0 = p[0], t1 = p[1], type = p[2];
+        if (parsed + 3 > len) return nullptr;
+        const uint8_t a = p[0], b = p[1], ty = p[2];
         p += 3;
         parsed += 3;
-        if (t0 == 'A' && t1 == 'S') {
-            uint32_t n = 0;
-            if (type == 'A' || type == 'C') n = 1;
-            else if (type == 'S') n = 2;
-            else if (type == 'I') n = 4;
-            if (n == 0 || parsed + n > len) return 0;
-            uint32_t v = 0;
-            for (uint32_t k = 0; k < n; ++k) v |= uint32_t(p[k]) << (8 * k);
-            return v;
+        if (a == t0 && b == t1) {
+            *type = ty;
+            *avail = len - parsed;
+            return p;
         }
         uint32_t skip;
-        switch (type) {
+        switch (ty) {
             case 'A': case 'c': case 'C': skip = 1; break;
             case 's': case 'S': skip = 2; break;
             case 'f': case 'i': case 'I': skip = 4; break;
@@ -119,25 +129,73 @@ __device__ uint32_t alignment_score(const Rec &r) {
                 break;
             }
             case 'B': {
-                if (parsed + 5 > len) return 0;
+                if (parsed + 5 > len) return nullptr;
                 const uint8_t at = p[0];
                 const uint32_t cnt = ld32(p + 1);
                 uint32_t es = 0;
                 if (at == 'c' || at == 'C') es = 1;
                 else if (at == 's' || at == 'S') es = 2;
                 else if (at == 'i' || at == 'I' || at == 'f') es = 4;
-                else return 0;
+                else return nullptr;
                 skip = 5 + cnt * es;
                 break;
             }
-            default: return 0;  // unknown storage type: FindTag gives up
+            default: return nullptr;  // unknown storage type: FindTag gives up
         }
-        if (parsed + skip >= len) return 0;  // the next tag would start at the terminating NUL
+        if (parsed + skip >= len) return nullptr;  // the next tag would start at the terminating NUL
         p += skip;
         parsed += skip;
-        if (*p == 0) return 0;
+        if (*p == 0) return nullptr;
     }
-    return 0;
+    return nullptr;
+}
+
+// GetTag("AS", uint32_t&) from 0 (TagTypeHelper<uint32_t>: only A/C/S/I are read)
+__device__ uint32_t alignment_score(const Rec &r) {
+    uint8_t type = 0;
+    uint32_t avail = 0;
+    const uint8_t *p = find_tag(r, 'A', 'S', &type, &avail);
+    if (!p) return 0;
+    uint32_t n = 0;
+    if (type == 'A' || type == 'C') n = 1;
+    else if (type == 'S') n = 2;
+    else if (type == 'I') n = 4;
+    if (n == 0 || n > avail) return 0;
+    uint32_t v = 0;
+    for (uint32_t k = 0; k < n; ++k) v |= uint32_t(p[k]) << (8 * k);
+    return v;
+}
+
+// The Z-typed value of tag t0 t1 (its bytes up to the NUL or the record's end), or null when the record has no such
+// tag or it is not Z-typed (rule 3b).
+__device__ const uint8_t *tag_value(const Rec &r, uint8_t t0, uint8_t t1, uint32_t *len) {
+    uint8_t type = 0;
+    uint32_t avail = 0;
+    const uint8_t *p = find_tag(r, t0, t1, &type, &avail);
+    if (!p || type != 'Z') return nullptr;
+    uint32_t k = 0;
+    while (k < avail && p[k]) ++k;
+    *len = k;
+    return p;
+}
+
+__device__ __forceinline__ uint64_t value_hash(const uint8_t *v, uint32_t len) {
+    uint64_t h = 1469598103934665603ull;
+    for (uint32_t k = 0; k < len; ++k) {
+        h ^= v[k];
+        h *= 1099511628211ull;
+    }
+    h ^= uint64_t(len) * 0x9E3779B97F4A7C15ull;
+    h ^= h >> 29;
+    h *= 0xBF58476D1CE4E5B9ull;
+    return h ^ (h >> 32);
+}
+
+__device__ __forceinline__ bool same_bytes(const uint8_t *a, uint32_t la, const uint8_t *b, uint32_t lb) {
+    if (la != lb) return false;
+    for (uint32_t k = 0; k < la; ++k)
+        if (a[k] != b[k]) return false;
+    return true;
 }
 
 // CharToInt of a 4-bit SEQ code ("=ACMGRSVTWYHKDBN"): A 0, C 1, G 2, T 3, else 5
@@ -426,6 +484,103 @@ __global__ void __launch_bounds__(kBlock) k_span(const uint32_t *minpos, const u
     atomicMax(max_len, maxpos[id] - minpos[id]);
 }
 
+// --- tag mode (rule 3b): the cell of a record from its barcode tag, and the global order built on the device ---
+
+// a listed barcode's hash and index, to be sorted by hash
+__global__ void __launch_bounds__(kBlock) k_list_hash(const uint8_t *bytes, const uint32_t *off, uint32_t n,
+                                                      uint64_t *hash, uint32_t *idx) {
+    const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= n) return;
+    hash[c] = value_hash(bytes + off[c], off[c + 1] - off[c]);
+    idx[c] = c;
+}
+
+// the listed cell of a barcode value, or ~0: lower bound in the hash-sorted table, then an exact compare over the run
+// of equal hashes, so a collision never merges two cells
+__device__ uint32_t find_cell(const CellList &L, const uint8_t *v, uint32_t len) {
+    const uint64_t h = value_hash(v, len);
+    uint32_t lo = 0, hi = L.n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (L.hash[mid] < h) lo = mid + 1;
+        else hi = mid;
+    }
+    for (uint32_t k = lo; k < L.n && L.hash[k] == h; ++k) {
+        const uint32_t c = L.cell[k];
+        if (same_bytes(v, len, L.bytes + L.off[c], L.off[c + 1] - L.off[c])) return c;
+    }
+    return ~0u;
+}
+
+// one thread per uploaded record (input order): sel = 1 and key = chunk << 46 | cell << 32 | Position for a record
+// of a listed cell
+__global__ void __launch_bounds__(kBlock) k_cells(const uint8_t *bytes, const uint64_t *in_off, uint32_t n,
+                                                  CellList L, uint64_t *key, uint32_t *sel) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o >= n) return;
+    const Rec r = parse(bytes + in_off[o]);
+    uint32_t len = 0, cell = ~0u;
+    const uint8_t *v = tag_value(r, L.t0, L.t1, &len);
+    if (v) cell = find_cell(L, v, len);
+    const uint32_t pos = uint32_t(r.pos);  // >= 0: the host refuses negative positions
+    key[o] = cell == ~0u ? 0 : (uint64_t(pos / kChunk) << 46 | uint64_t(cell) << 32 | pos);
+    sel[o] = cell == ~0u ? 0 : 1;
+}
+
+// one thread per record with a Z-typed tag value: sel = 1, key = the value's hash
+__global__ void __launch_bounds__(kBlock) k_tag_keys(const uint8_t *bytes, const uint64_t *in_off, uint32_t n,
+                                                     uint8_t t0, uint8_t t1, uint64_t *key, uint32_t *sel) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o >= n) return;
+    const Rec r = parse(bytes + in_off[o]);
+    uint32_t len = 0;
+    const uint8_t *v = tag_value(r, t0, t1, &len);
+    key[o] = v ? value_hash(v, len) : 0;
+    sel[o] = v ? 1 : 0;
+}
+
+// the selected (key, input ordinal) pairs, in input order
+__global__ void __launch_bounds__(kBlock) k_compact_keys(const uint64_t *key, const uint32_t *sel,
+                                                         const uint32_t *scan, uint32_t n, uint64_t *key_out,
+                                                         uint32_t *val_out) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o >= n || !sel[o]) return;
+    key_out[scan[o]] = key[o];
+    val_out[scan[o]] = o;
+}
+
+// the Records of the global order: byte offset, cell and input ordinal of ordinal j
+__global__ void __launch_bounds__(kBlock) k_order(const uint64_t *key, const uint32_t *val, const uint64_t *in_off,
+                                                  uint32_t n, uint64_t *off, uint16_t *cell, uint32_t *ord) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t o = val[j];
+    off[j] = in_off[o];
+    cell[j] = uint16_t((key[j] >> 32) & 0x3FFF);
+    ord[j] = o;
+}
+
+// distinct values: within a run of equal hashes (sorted, input order inside) the first position holding the same
+// value counts the record
+__global__ void __launch_bounds__(kBlock) k_tag_count(const uint8_t *bytes, const uint64_t *in_off, uint8_t t0,
+                                                      uint8_t t1, const uint32_t *val, const uint32_t *run, uint32_t n,
+                                                      uint32_t *cnt) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    uint32_t len = 0;
+    const uint8_t *v = tag_value(parse(bytes + in_off[val[j]]), t0, t1, &len);
+    uint32_t first = j;
+    for (uint32_t q = run[j]; q < j; ++q) {
+        uint32_t lq = 0;
+        const uint8_t *w = tag_value(parse(bytes + in_off[val[q]]), t0, t1, &lq);
+        if (same_bytes(v, len, w, lq)) {
+            first = q;
+            break;
+        }
+    }
+    atomicAdd(&cnt[first], 1u);
+}
+
 inline uint32_t grid(uint64_t n) { return uint32_t((n + kBlock - 1) / kBlock); }
 
 struct MaxOp {
@@ -515,6 +670,54 @@ hipError_t read_stats(const uint32_t *d_pos, const uint64_t *d_off, const uint32
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || n_ids == 0) return e;
     k_span<<<grid(n_ids), kBlock, 0, s>>>(d_minpos, d_maxpos, n_ids, d_max_len);
+    return hipGetLastError();
+}
+
+hipError_t list_hash(const uint8_t *d_bytes, const uint32_t *d_off, uint32_t n, uint64_t *d_hash, uint32_t *d_idx,
+                     hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_list_hash<<<grid(n), kBlock, 0, s>>>(d_bytes, d_off, n, d_hash, d_idx);
+    return hipGetLastError();
+}
+
+hipError_t cells(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const CellList &L, uint64_t *d_key,
+                 uint32_t *d_sel, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_cells<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, n, L, d_key, d_sel);
+    return hipGetLastError();
+}
+
+hipError_t tag_keys(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, uint8_t t0, uint8_t t1,
+                    uint64_t *d_key, uint32_t *d_sel, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_tag_keys<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, n, t0, t1, d_key, d_sel);
+    return hipGetLastError();
+}
+
+hipError_t compact_keys(const uint64_t *d_key, const uint32_t *d_sel, const uint32_t *d_scan, uint32_t n,
+                        uint64_t *d_key_out, uint32_t *d_val_out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_compact_keys<<<grid(n), kBlock, 0, s>>>(d_key, d_sel, d_scan, n, d_key_out, d_val_out);
+    return hipGetLastError();
+}
+
+hipError_t order_records(const uint64_t *d_key_sorted, const uint32_t *d_val_sorted, const uint64_t *d_in_off,
+                         uint32_t n, uint64_t *d_off, uint16_t *d_cell, uint32_t *d_ord, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_order<<<grid(n), kBlock, 0, s>>>(d_key_sorted, d_val_sorted, d_in_off, n, d_off, d_cell, d_ord);
+    return hipGetLastError();
+}
+
+hipError_t tag_count(const uint8_t *d_bytes, const uint64_t *d_in_off, uint8_t t0, uint8_t t1,
+                     const uint64_t *d_key_sorted, const uint32_t *d_val_sorted, uint32_t *d_run, uint32_t n,
+                     uint32_t *d_cnt, void *tmp, size_t tmp_bytes, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_run_head<<<grid(n), kBlock, 0, s>>>(d_key_sorted, d_run, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = hipcub::DeviceScan::InclusiveScan(tmp, tmp_bytes, d_run, d_run, MaxOp(), n, s);
+    if (e != hipSuccess) return e;
+    k_tag_count<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, t0, t1, d_val_sorted, d_run, n, d_cnt);
     return hipGetLastError();
 }
 

@@ -39,9 +39,40 @@ struct Params {
 struct Records {
     const uint8_t *bytes;   // uploaded records (block_size field first), host-validated structure
     const uint64_t *off;    // [n] byte offset of record ordinal r, in global order (chunk, file, record)
-    const uint16_t *file;   // [n] file index (cell id) of record r
+    const uint16_t *file;   // [n] file index (cell id) of record r; in tag mode its cell (rule 3b)
     uint32_t n;
 };
+
+// the barcode list of tag mode (rule 3b): packed values (off[n + 1]), their hashes sorted and the cell of each
+struct CellList {
+    const uint8_t *bytes;
+    const uint32_t *off;   // [n + 1] by cell
+    const uint64_t *hash;  // [n] sorted
+    const uint32_t *cell;  // [n] cell of hash[k]
+    uint32_t n;
+    uint8_t t0, t1;        // the tag
+};
+
+// hash[c], idx[c] = c of each listed value (to be sorted by hash into CellList)
+hipError_t list_hash(const uint8_t *d_bytes, const uint32_t *d_off, uint32_t n, uint64_t *d_hash, uint32_t *d_idx,
+                     hipStream_t s);
+// cells: per uploaded record (input order) d_sel = 1 for a listed barcode, d_key = chunk << 46 | cell << 32 | Position
+hipError_t cells(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const CellList &L, uint64_t *d_key,
+                 uint32_t *d_sel, hipStream_t s);
+// tag_keys: d_sel = 1 for a Z-typed value of tag t0 t1, d_key = its hash
+hipError_t tag_keys(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, uint8_t t0, uint8_t t1,
+                    uint64_t *d_key, uint32_t *d_sel, hipStream_t s);
+// selected (key, input ordinal) pairs at d_scan (exclusive sum of d_sel)
+hipError_t compact_keys(const uint64_t *d_key, const uint32_t *d_sel, const uint32_t *d_scan, uint32_t n,
+                        uint64_t *d_key_out, uint32_t *d_val_out, hipStream_t s);
+// Records of the sorted order: d_off[j] = d_in_off[val[j]], d_cell[j] = the key's cell, d_ord[j] = val[j]
+hipError_t order_records(const uint64_t *d_key_sorted, const uint32_t *d_val_sorted, const uint64_t *d_in_off,
+                         uint32_t n, uint64_t *d_off, uint16_t *d_cell, uint32_t *d_ord, hipStream_t s);
+// distinct values of hash-sorted (key, input ordinal) pairs: d_cnt[j] (zeroed by the caller) = records of the value
+// first seen at sorted position j, 0 elsewhere. d_run: workspace [n]; tmp: scan_bytes(n)
+hipError_t tag_count(const uint8_t *d_bytes, const uint64_t *d_in_off, uint8_t t0, uint8_t t1,
+                     const uint64_t *d_key_sorted, const uint32_t *d_val_sorted, uint32_t *d_run, uint32_t n,
+                     uint32_t *d_cnt, void *tmp, size_t tmp_bytes, hipStream_t s);
 
 // decode: per record the read filter, the name key, the walk's error checks and the end of its touched span.
 // d_err: u64 min of (ordinal << 8 | code), initialised to ~0 by the caller.

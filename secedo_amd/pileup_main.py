@@ -5,6 +5,12 @@ Flags as in the reference: -i (a BAM file or a directory searched recursively fo
 --num_threads (here only the size of the host inflate pool, capped at 16). Writes
 <o>_<chromosome>.pileup.{bin,map,txt} per chromosome and, for a directory input, the cell map
 <o>_<chromosomes>.map. The default chromosome list is the real one (1..22, X, Y).
+
+Multiplexed BAMs (--cell_tag TG, e.g. CB for 10x data): every BAM under -i holds many cells, the cell of a record
+being its Z-typed TG value. --cells FILE lists the barcodes (one per line; empty and '#' lines skipped, so a 10x
+barcodes.tsv works); without it the cells are every value with at least --min_cell_records records over the requested
+chromosomes, sorted bytewise, so that every <o>_<chromosome>.pileup.bin shares one numbering. The cell map
+<o>_<chromosomes>.map then holds barcode<TAB>index, for a file input too.
 """
 from __future__ import annotations
 
@@ -29,7 +35,48 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--min_map_score", type=int, default=0)
     ap.add_argument("--max_coverage", type=int, default=100)
     ap.add_argument("--min_different", type=int, default=3)
+    ap.add_argument("--cell_tag", default=None, help="Multiplexed input: the aux tag naming a record's cell (e.g. CB)")
+    ap.add_argument("--cells", default=None, help="With --cell_tag: file of barcodes, one per line")
+    ap.add_argument("--min_cell_records", type=int, default=None,
+                    help="With --cell_tag and without --cells: cells are the values with at least this many records "
+                         "(default 1)")
     return ap.parse_args(argv)
+
+
+MAX_CELLS = 16384
+
+
+def valid_tag(tag: str) -> bool:
+    return len(tag) == 2 and tag[0].isascii() and tag[0].isalpha() and tag[1].isascii() and tag[1].isalnum()
+
+
+def read_cells(path: str) -> List[str]:
+    """Barcodes of a --cells file: the first tab-separated field of each line; empty lines and lines starting
+    with '#' are skipped."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            out.append(line.split("\t")[0])
+    return out
+
+
+def check_tag_flags(a: argparse.Namespace) -> None:
+    """The tag-mode flags, checked before any BAM is read (and before torch is imported)."""
+    if a.cell_tag is None:
+        if a.cells is not None or a.min_cell_records is not None:
+            raise SystemExit("--cells and --min_cell_records need --cell_tag")
+        return
+    if not valid_tag(a.cell_tag):
+        raise SystemExit("Invalid --cell_tag %r: two characters [A-Za-z][A-Za-z0-9]" % a.cell_tag)
+    if a.cells is not None and a.min_cell_records is not None:
+        raise SystemExit("--cells and --min_cell_records exclude each other")
+    if a.cells is not None and not os.path.isfile(a.cells):
+        raise SystemExit("--cells file %s does not exist" % a.cells)
+    if a.min_cell_records is not None and a.min_cell_records < 1:
+        raise SystemExit("--min_cell_records must be at least 1")
 
 
 def chromosome_to_id(chromosome: str) -> int:
@@ -68,23 +115,46 @@ def cell_map_lines(files: List[str]) -> List[str]:
 
 def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
+    check_tag_flags(a)
+    if a.cell_tag is not None and not os.path.exists(a.i):
+        raise SystemExit("Input %s does not exist" % a.i)
     files = input_files(a.i)
-    if os.path.isdir(a.i):
-        if not files:
-            print("No BAM files found in %s. Done." % a.i)
-            return 0
+    if os.path.isdir(a.i) and not files:
+        print("No BAM files found in %s. Done." % a.i)
+        return 0
+    if os.path.isdir(a.i) and a.cell_tag is None:
         with open(a.o + "_" + a.chromosomes + ".map", "w") as f:
             f.writelines(cell_map_lines(files))
     if os.path.isdir(a.o):
         raise SystemExit("-o <output_dir> must be a file prefix, not a directory")
     chromosomes = a.chromosomes.split(",")
     ids = [chromosome_to_id(c) for c in chromosomes]
+    cells = None
+    if a.cell_tag is not None:
+        if a.cells is not None:
+            cells = read_cells(a.cells)
+            if not cells:
+                raise SystemExit("--cells file %s lists no barcode" % a.cells)
+        else:
+            from .bam_pileup import bam_barcodes
+
+            values, counts = bam_barcodes(files, a.cell_tag, ids, pool_size(a.num_threads))
+            n = 1 if a.min_cell_records is None else a.min_cell_records
+            cells = [v for v, c in zip(values, counts) if int(c) >= n]
+            if not cells:
+                raise SystemExit("No %s:Z value has %d or more records" % (a.cell_tag, n))
+        if len(cells) > MAX_CELLS:
+            raise SystemExit("%d cells: at most %d are supported; pass --cells or a larger --min_cell_records"
+                             % (len(cells), MAX_CELLS))
+        with open(a.o + "_" + a.chromosomes + ".map", "w") as f:
+            f.writelines("%s\t%d\n" % (c, i) for i, c in enumerate(cells))
     from .bam_pileup import pileup_bams
 
+    tag_kw = {} if a.cell_tag is None else dict(cell_tag=a.cell_tag, cells=cells)
     for chromosome, cid in zip(chromosomes, ids):
         out = a.o + "_" + chromosome + ".pileup"
         p = pileup_bams(files, out, True, cid, a.max_coverage, a.min_base_quality, a.min_map_quality,
-                        a.min_map_score, pool_size(a.num_threads), a.min_different)
+                        a.min_map_score, pool_size(a.num_threads), a.min_different, **tag_kw)
         print("Written %d positions to %s.txt/.bin" % (p.n_loci, out))
     return 0
 

@@ -7,6 +7,11 @@ processes): --cells cells x --pairs read pairs of 2 x 100 bp on a --mbp Mbp chro
 the file-writing call (host inflate with its GB/s of inflated bytes, record walk, upload, device passes, file
 writes, end to end) and of the resident call, medians of --repeat runs after one untimed run.
 
+--multiplexed also writes the same set as one tagged BAM (every record gets CB:Z:C<cell>-1, all cells merged in
+position order) and adds the tag-mode call (pileup_bams with cell_tag="CB") beside the per-file call: its step
+times, and whether its .bin and .map equal the per-file call's. Its device time includes the front passes (cells,
+compaction, sort, order); the rocprofv3 merge below lists them as front_ms.
+
 Kernel times come from a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_pileup_bams.py --dir D \
         --repeat 1 --resident-only
@@ -15,10 +20,13 @@ Run every step under a time limit (timeout -k 10 ...)."""
 import argparse
 import csv
 import glob
+import gzip
 import json
 import os
+import struct
 import sys
 import time
+import zlib
 from multiprocessing import Pool
 
 import numpy as np
@@ -61,6 +69,53 @@ def write_set(d, cells, pairs, mbp, seed=7):
     return paths, time.time() - t0
 
 
+TAG_LEN = 3 + 9  # "CBZ" + "C%05d-1" + NUL
+
+
+def _bgzf_block(chunk):
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    cdata = c.compress(chunk) + c.flush()
+    return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(cdata) + 25) + cdata +
+            struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+
+
+def write_multiplexed(d, paths, seed_stamp):
+    """The cells of write_set as one coordinate-sorted BAM, each record tagged CB:Z:C<cell>-1 -> (path, barcodes)."""
+    path = os.path.join(d, "multiplexed.bam")
+    barcodes = ["C%05d-1" % c for c in range(len(paths))]
+    stamp = os.path.join(d, "multiplexed.json")
+    if os.path.exists(stamp) and os.path.exists(path) and json.load(open(stamp)) == seed_stamp:
+        return path, barcodes, 0.0
+    t0 = time.time()
+    parts, header = [], None
+    for c, p in enumerate(paths):
+        raw = gzip.decompress(open(p, "rb").read())
+        l_text = struct.unpack_from("<i", raw, 4)[0]
+        o = 8 + l_text + 4 + 4 + 2 + 4  # one reference named "1"
+        header = raw[:o]
+        rec = np.frombuffer(raw, dtype=np.uint8, offset=o).reshape(-1, 211)  # uniform_cell_bam's fixed size
+        out = np.empty((rec.shape[0], 211 + TAG_LEN), dtype=np.uint8)
+        out[:, :211] = rec
+        out[:, :4] = (rec[:, :4].copy().view("<i4") + TAG_LEN).view(np.uint8)
+        out[:, 211:] = np.frombuffer(b"CBZ" + barcodes[c].encode() + b"\0", dtype=np.uint8)
+        parts.append(out)
+    allr = np.concatenate(parts)
+    del parts
+    pos = allr[:, 8:12].copy().view("<i4").ravel()
+    allr = allr[np.argsort(pos, kind="stable")]
+    data = header + allr.tobytes()
+    del allr
+    chunks = [data[i:i + 0xFF00] for i in range(0, len(data), 0xFF00)]
+    with Pool(16) as pool:
+        blocks = pool.map(_bgzf_block, chunks, chunksize=64)
+    with open(path, "wb") as f:
+        for b in blocks:
+            f.write(b)
+        f.write(_bgzf_block(b""))
+    json.dump(seed_stamp, open(stamp, "w"))
+    return path, barcodes, time.time() - t0
+
+
 def merge(line_path, prof_dir):
     line = json.loads(open(line_path).read().strip().splitlines()[-1])
     f = sorted(glob.glob(os.path.join(prof_dir, "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)[-1]
@@ -79,6 +134,9 @@ def merge(line_path, prof_dir):
         total += ms
     calls = kernels["k_decode"]["calls"]  # pileup calls in the profiled run (one decode launch each)
     line["kernels"] = kernels
+    front = [k for k in ("k_cells", "k_compact_keys", "k_order") if k in kernels]
+    if front:  # tag mode's front passes (their radix sort is inside rocprim_radix_sort)
+        line["front_ms"] = round(sum(kernels[k]["ms"] for k in front) / calls, 3)
     line["profiled_calls"] = calls
     line["kernel_ms_per_call"] = round(total / calls, 3)
     # compulsory bytes of one call: the uploaded records read by decode, count and emit, the counts written and
@@ -100,6 +158,9 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--resident-only", action="store_true")
+    ap.add_argument("--multiplexed", action="store_true", help="Also the tag-mode call on the set as one BAM")
+    ap.add_argument("--multiplexed-only", action="store_true",
+                    help="Only the tag-mode resident call (for a rocprofv3 run of its own)")
     ap.add_argument("--merge", nargs=2, metavar=("LINE", "PROF_DIR"))
     a = ap.parse_args()
     if a.merge:
@@ -108,6 +169,21 @@ def main():
     paths, gen_s = write_set(a.dir, a.cells, a.pairs, a.mbp)
     import secedo_amd
     from secedo_amd import bam_pileup
+
+    print("set ready (%.1f s)" % gen_s, file=sys.stderr, flush=True)
+    if a.multiplexed or a.multiplexed_only:
+        mpath, barcodes, mux_s = write_multiplexed(a.dir, paths, dict(cells=a.cells, pairs=a.pairs, mbp=a.mbp))
+        print("multiplexed BAM ready (%.1f s)" % mux_s, file=sys.stderr, flush=True)
+    if a.multiplexed_only:
+        with secedo_amd.SimilarityMatrixPlan(0) as plan:
+            for k in range(a.repeat + 1):
+                t = {}
+                res, cells, max_len = bam_pileup.pileup_bams_resident(plan, [mpath], [0], 100, 30, 30, 0, a.threads,
+                                                                      3, times=t, cell_tag="CB", cells=barcodes)
+        print(json.dumps(dict(workload="uniform_multiplexed", cells=a.cells, pairs=a.pairs, records=a.cells * a.pairs * 2,
+                              record_bytes=a.cells * a.pairs * 2 * 211, window_positions=int(a.mbp * 1_000_000),
+                              entries=res["n_entries"], total_ms=t["total_ms"], device_ms=t["device_ms"])), flush=True)
+        return
 
     med = lambda xs: float(np.median(xs))
     out = os.path.join(a.dir, "out")
@@ -125,6 +201,22 @@ def main():
         line["inflated_bytes"] = runs[0]["inflated_bytes"]
         line["inflate_GBps"] = line["inflated_bytes"] / (line["inflate_ms"] * 1e-3) / 1e9
         line.update(loci=p.n_loci, entries=p.n_entries)
+        if a.multiplexed:
+            mout = os.path.join(a.dir, "mout")
+            mr = []
+            for k in range(a.repeat + 1):
+                t = {}
+                bam_pileup.pileup_bams([mpath], mout, True, 0, 100, 30, 30, 0, a.threads, 3, times=t, cell_tag="CB",
+                                       cells=barcodes)
+                if k:
+                    mr.append(t)
+            m = dict(set_write_s=round(mux_s, 1), bam_bytes=os.path.getsize(mpath),
+                     inflated_bytes=mr[0]["inflated_bytes"])
+            for key in ("inflate_ms", "walk_ms", "upload_ms", "device_ms", "write_ms", "total_ms"):
+                m[key] = round(med([r[key] for r in mr]), 2)
+            m["bin_equal"] = open(mout + ".bin", "rb").read() == open(out + ".bin", "rb").read()
+            m["map_equal"] = open(mout + ".map", "rb").read() == open(out + ".map", "rb").read()
+            line["multiplexed"] = m
     with secedo_amd.SimilarityMatrixPlan(0) as plan:
         rt = []
         for k in range(a.repeat + 1):
