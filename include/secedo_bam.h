@@ -15,6 +15,24 @@
  * record); secedo_bam_barcodes lists the values found. Inflated bytes per file are bounded: a large file is inflated
  * and walked in ranges of BGZF blocks (about 512 MiB inflated; the environment variable SECEDO_BAM_BATCH_BYTES
  * overrides it, outputs do not depend on it).
+ *
+ * SAM input: every file list may mix BAM and coordinate-sorted SAM text files. The type is decided by content:
+ * BGZF magic is BAM, a plain gzip file (no BGZF extra field) is SECEDO_E_INVALID_ARG ("decompress it to SAM or
+ * convert it to BAM"), anything else is SAM. A SAM file gives exactly what the BAM `samtools view -b` writes from
+ * it gives, in every call. The host parses the header (the leading '@' lines; every @SQ needs SN and LN, SN unique;
+ * @SQ order = RefID = chromosome_id) and cuts the alignment lines into ranges of about SECEDO_BAM_BATCH_BYTES that
+ * end at a '\n'; the GPU (secedo_amd/csrc/sam_kernels.hip, which lists the rules) splits the lines, validates them
+ * and encodes the BAM records, following htslib's sam_parse1. Departures and limits:
+ *  - an RNAME or RNEXT that no @SQ line names is an error (htslib warns and treats the record as unmapped);
+ *  - an '@' line after the first alignment line, and an empty line other than the file's last, are errors;
+ *  - f aux values are converted to float32 without correct rounding of the last bit (no pass reads them);
+ *  - no line-length limit below 4 GiB (a range grows to hold its longest line); more than 65535 CIGAR ops or a
+ *    record of 2^31 bytes or more is SECEDO_E_LIMIT;
+ *  - .sam.gz, standard input and CRAM are not read.
+ * Errors in a SAM file name the file index, its path and the 1-based line (record k of a file with h header lines
+ * is line h + k + 1): parse errors, the host's structural checks and the device passes' rule-6 errors; of several
+ * bad lines the first is reported. For SAM, secedo_bam_times.inflate_ms is the text read and walk_ms includes the
+ * device parse. secedo_bam_scan reads BAM only.
  */
 #ifndef SECEDO_BAM_H
 #define SECEDO_BAM_H

@@ -1,10 +1,14 @@
-"""Pileup creation from BAM files (include/secedo_bam.h, libsecedo_bam.so).
+"""Pileup creation from BAM or SAM files (include/secedo_bam.h, libsecedo_bam.so).
 
 Host-side mirror of the reference's ``pileup_bams(bam_files, out_pileup, write_text_file, chromosome_id,
 max_coverage, min_base_quality, min_map_quality, min_alignment_score, num_threads, min_different)``
 (pileup.cpp:235-348). The host inflates the BGZF blocks and walks the records; the per-record decode, the read
 name numbering, the base counts, the locus rule and the entry placement run on the GPU
 (secedo_amd/csrc/bam_kernels.hip). ``bam_scan`` needs no GPU. No CPU fallback for the pileup itself.
+
+Every file list may hold BAM and coordinate-sorted SAM files, told apart by content (BGZF magic: BAM; plain gzip is
+refused; anything else: SAM text). A SAM file's lines are parsed on the GPU (secedo_amd/csrc/sam_kernels.hip) into the
+records of the BAM that ``samtools view -b`` writes from it, so results equal that BAM's; errors name its line.
 
 Multiplexed BAMs (one file, many cells named by a barcode tag such as 10x's ``CB:Z``): ``cell_tag`` and ``cells``
 on ``pileup_bams`` / ``pileup_bams_resident`` make cell c the records whose tag value is ``cells[c]``;
@@ -127,8 +131,8 @@ def _cells(cell_tag, cells):
 
 
 def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], num_threads: int = 1):
-    """The distinct Z-typed values of ``tag`` over the records of the given chromosomes of ``files``, sorted
-    bytewise -> (values [str], counts np.uint64: records per value). Needs the GPU."""
+    """The distinct Z-typed values of ``tag`` over the records of the given chromosomes of ``files`` (BAM or SAM),
+    sorted bytewise -> (values [str], counts np.uint64: records per value). Needs the GPU."""
     arr, n = _files(files)
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
     n_val, n_bytes = C.c_uint32(0), C.c_uint64(0)
@@ -181,8 +185,8 @@ def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_
                 max_coverage: int, min_base_quality: int, min_map_quality: int, min_alignment_score: int,
                 num_threads: int, min_different: int, times: Optional[dict] = None, *, cell_tag=None,
                 cells=None) -> FlatPileup:
-    """The reference's pileup_bams() -> a one-chromosome FlatPileup (id_base = cell << 2 | base). Writes
-    <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms.
+    """The reference's pileup_bams() on BAM or SAM files -> a one-chromosome FlatPileup (id_base = cell << 2 |
+    base). Writes <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms.
 
     With ``cell_tag`` (e.g. "CB") the files are multiplexed: cell c is the records whose Z-typed ``cell_tag`` value
     is ``cells[c]``; the result equals this call on the per-cell split files."""
@@ -207,7 +211,7 @@ def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequenc
                          min_base_quality: int = 30, min_map_quality: int = 30, min_alignment_score: int = 0,
                          num_threads: int = 8, min_different: int = 3, id_to_group=None, group_id_to_pos=None,
                          times: Optional[dict] = None, *, cell_tag=None, cells=None):
-    """Several chromosomes in one pass over the files, straight into HBM on ``plan``'s device.
+    """Several chromosomes in one pass over the BAM or SAM files, straight into HBM on ``plan``'s device.
 
     -> (res, num_cells, max_read_length): ``res`` is the resident pileup dict of SimilarityMatrixPlan.upload,
     which filter_resident, divide_cluster_resident and variant_calling_resident take; num_cells and

@@ -14,6 +14,7 @@
 #include "secedo_bam.h"
 #include "secedo_simmat.h"
 #include "bam_kernels.hpp"
+#include "sam_kernels.hpp"
 
 #include <hip/hip_runtime.h>
 #include <zlib.h>
@@ -340,6 +341,40 @@ std::string first_z_value(const uint8_t *p, uint64_t len, const char *tag) {
     return std::string();
 }
 
+template <class T>
+struct Dev {
+    T *p = nullptr;
+    size_t n = 0;
+    Dev() = default;
+    Dev(const Dev &) = delete;
+    Dev &operator=(const Dev &) = delete;
+    ~Dev() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    hipError_t alloc(size_t count) {
+        reset();
+        n = count;
+        return hipMalloc(&p, std::max<size_t>(1, count) * sizeof(T));
+    }
+    // keep the first `keep` elements, grow to at least `count`
+    hipError_t grow(size_t count, size_t keep, hipStream_t s) {
+        if (count <= n && p) return hipSuccess;
+        size_t cap = std::max<size_t>(count, 2 * n);
+        T *q = nullptr;
+        hipError_t e = hipMalloc(&q, std::max<size_t>(1, cap) * sizeof(T));
+        if (e != hipSuccess) return e;
+        if (keep) e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (p) (void)hipFree(p);
+        p = q;
+        n = cap;
+        return e;
+    }
+};
+
 // the chromosome's records of every file, in the global order
 struct ChrInput {
     uint32_t chromosome;
@@ -348,7 +383,15 @@ struct ChrInput {
     std::vector<std::vector<uint64_t>> roff;  // per file: record offsets (relative to its run)
     std::vector<std::vector<int32_t>> rpos;
     std::vector<std::vector<uint64_t>> ridx;  // record index in the file (messages)
+    std::vector<std::string> paths;            // [n_files] (messages)
+    std::vector<uint64_t> line0;               // [n_files] SAM: the line of record 0 (1-based); BAM: 0
 };
+
+// where a record is, for messages: "path: record k" (BAM), "file f (path), line l" (SAM)
+std::string record_where(const std::string &path, size_t f, uint64_t line0, uint64_t idx) {
+    if (!line0) return path + ": record " + std::to_string(idx);
+    return "file " + std::to_string(f) + " (" + path + "), line " + std::to_string(line0 + idx);
+}
 
 // Per file: its records of each requested chromosome, appended as the walk meets them (one range after another).
 struct FileSink {
@@ -357,6 +400,7 @@ struct FileSink {
     std::vector<ChrInput> &chrs;
     std::vector<std::vector<uint8_t> *> runs;  // [chr] this file's run
     std::vector<int> started, done;
+    uint64_t line0 = 0;  // SAM: the line of record 0
     FileSink(const std::string &p, size_t file, std::vector<ChrInput> &c, std::vector<std::vector<std::vector<uint8_t>>> &r)
         : path(p), f(file), chrs(c), runs(c.size()), started(c.size(), 0), done(c.size(), 0) {
         for (size_t k = 0; k < c.size(); ++k) runs[k] = &r[k][file];
@@ -369,7 +413,7 @@ struct FileSink {
                 if (started[c]) done[c] = 1;  // the reader stops at another RefID
                 continue;
             }
-            const std::string where = path + ": record " + std::to_string(idx);
+            const std::string where = record_where(path, f, line0, idx);
             if (pos < 0) return fail(SECEDO_E_INVALID_ARG, where + " has a negative position");
             BAM_CALL(check_cigar(rec, where));
             started[c] = 1;
@@ -428,6 +472,268 @@ int load_file_ranges(const std::string &path, size_t f, uint32_t threads, uint64
     return SECEDO_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// SAM text input: the header is parsed here, the alignment lines on the device (sam_kernels.hip) into the BAM records
+// the walk above collects. The file type comes from its first bytes: BGZF is BAM, plain gzip is refused, anything
+// else is SAM.
+
+// *sam = the file is SAM text; plain gzip (no BGZF extra field) is an error
+int sniff(const std::string &path, bool *sam) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return fail(SECEDO_E_INVALID_ARG, "Could not open " + path);
+    uint8_t b[512];
+    const ssize_t n = pread(fd, b, sizeof(b), 0);
+    close(fd);
+    if (n < 0) return fail(SECEDO_E_INVALID_ARG, "Could not read " + path);
+    *sam = !(n >= 2 && b[0] == 31 && b[1] == 139);
+    if (*sam) return SECEDO_OK;
+    bool bgzf = false;
+    if (n >= 12 && b[2] == 8 && (b[3] & 4)) {
+        const uint32_t end = std::min<uint32_t>(12 + rd16(b + 10), uint32_t(n));
+        for (uint32_t x = 12; x + 4 <= end; x += 4 + rd16(b + x + 2))
+            if (b[x] == 'B' && b[x + 1] == 'C') bgzf = true;
+    }
+    if (!bgzf)
+        return fail(SECEDO_E_INVALID_ARG, path + ": a gzip file that is not BGZF; decompress it to SAM or convert "
+                                                 "it to BAM (samtools view -b)");
+    return SECEDO_OK;
+}
+
+struct SamHeader {
+    std::vector<std::string> names;  // @SQ SN values by RefID
+    uint64_t lines = 0, body = 0;    // header lines, byte offset of the first alignment line
+};
+
+// the leading '@' lines: @SQ SN and LN required, SN unique
+int parse_sam_header(const std::string &path, size_t f, const Mapped &m, SamHeader *h) {
+    std::set<std::string> seen;
+    uint64_t o = 0;
+    while (o < m.n && m.p[o] == '@') {
+        const uint8_t *nl = static_cast<const uint8_t *>(std::memchr(m.p + o, '\n', m.n - o));
+        const uint64_t e = nl ? uint64_t(nl - m.p) : m.n;
+        ++h->lines;
+        const std::string line(reinterpret_cast<const char *>(m.p + o), e - o);
+        o = nl ? e + 1 : m.n;
+        if (line.compare(0, 3, "@SQ") != 0 || (line.size() > 3 && line[3] != '\t')) continue;
+        const std::string where = "file " + std::to_string(f) + " (" + path + "), line " + std::to_string(h->lines);
+        std::string sn;
+        bool has_sn = false, has_ln = false;
+        for (size_t a = 4; a <= line.size();) {
+            size_t b = line.find('\t', a);
+            if (b == std::string::npos) b = line.size();
+            const std::string fld = line.substr(a, b - a);
+            if (fld.compare(0, 3, "SN:") == 0 && !has_sn) {
+                sn = fld.substr(3);
+                has_sn = true;
+            } else if (fld.compare(0, 3, "LN:") == 0 && !has_ln) {
+                const std::string v = fld.substr(3);
+                if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != std::string::npos ||
+                    std::stoull(v) < 1 || std::stoull(v) > 2147483647ull)
+                    return fail(SECEDO_E_INVALID_ARG, where + ": @SQ LN is not an integer in [1, 2^31 - 1]");
+                has_ln = true;
+            }
+            a = b + 1;
+        }
+        if (!has_sn || !has_ln) return fail(SECEDO_E_INVALID_ARG, where + ": @SQ without SN or LN");
+        if (!seen.insert(sn).second) return fail(SECEDO_E_INVALID_ARG, where + ": @SQ SN:" + sn + " is listed twice");
+        h->names.push_back(sn);
+    }
+    h->body = o;
+    return SECEDO_OK;
+}
+
+// device buffers of the SAM passes, kept over the ranges and files of one call
+struct SamWork {
+    hipStream_t s = nullptr;
+    Dev<uint8_t> text, out, names, sel, tmp;
+    Dev<uint32_t> cnt, scan, start, name_off, name_id;
+    Dev<uint64_t> name_hash, size, off;
+    Dev<int32_t> ref, pos;
+    Dev<unsigned long long> err;
+    std::vector<uint8_t> h_text, h_out;
+    std::vector<int32_t> h_ref, h_pos;
+    ~SamWork() {
+        if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
+    }
+};
+
+const char *sam_what(uint32_t code) {
+    static const char *what[kSamCodes] = {
+        "",
+        "does not have 11 non-empty tab-separated mandatory fields",
+        "has a QNAME longer than 254 characters",
+        "has a FLAG that is not an integer in [0, 65535]",
+        "has an RNAME that no @SQ line names",
+        "has a POS that is not an integer in [0, 2^31 - 1]",
+        "has a MAPQ that is not an integer in [0, 255]",
+        "has a malformed CIGAR",
+        "has an RNEXT that is not '*', '=' or an @SQ name",
+        "has a PNEXT that is not an integer in [0, 2^31 - 1]",
+        "has a TLEN that is not an integer in [-(2^31 - 1), 2^31 - 1]",
+        "has a QUAL that is not '*', not as long as SEQ or not in '!'..'~'",
+        "has CIGAR and SEQ lengths that differ",
+        "has a malformed optional field",
+        "is a header line after the first alignment line",
+        "is empty",
+        "has more than 65535 CIGAR ops",
+        "gives a record of 2^31 bytes or more",
+    };
+    return code < kSamCodes ? what[code] : "?";
+}
+
+// One SAM file: header on the host, then ranges of about `batch` bytes ending at a '\n', each uploaded, parsed on the
+// device, and its records of the requested chromosomes downloaded into the file's runs (FileSink, as a BAM's walk).
+int load_sam_file(const std::string &path, size_t f, uint64_t batch, SamWork *w, std::vector<ChrInput> *chrs,
+                  std::vector<std::vector<std::vector<uint8_t>>> *runs, secedo_bam_times *t) {
+    Clock::time_point t0 = Clock::now();
+    Mapped m;
+    BAM_CALL(map_file(path, &m));
+    SamHeader h;
+    BAM_CALL(parse_sam_header(path, f, m, &h));
+    const uint64_t line0 = h.lines + 1;
+    for (auto &ci : *chrs) ci.line0[f] = line0;
+    if (t) t->inflate_ms += ms_since(t0);
+    t0 = Clock::now();
+    if (!w->s) BAM_TRY(hipStreamCreateWithFlags(&w->s, hipStreamNonBlocking));
+    hipStream_t s = w->s;
+    // the @SQ names: packed, hashed and sorted here; the selected RefIDs
+    const uint32_t n_ref = uint32_t(h.names.size());
+    std::vector<uint8_t> names, sel(std::max<uint32_t>(n_ref, 1), 0);
+    std::vector<uint32_t> name_off{0}, name_id(n_ref);
+    std::vector<std::pair<uint64_t, uint32_t>> hs(n_ref);
+    for (uint32_t r = 0; r < n_ref; ++r) {
+        names.insert(names.end(), h.names[r].begin(), h.names[r].end());
+        name_off.push_back(uint32_t(names.size()));
+        hs[r] = {sam_name_hash(reinterpret_cast<const uint8_t *>(h.names[r].data()), uint32_t(h.names[r].size())),
+                 r};
+    }
+    std::sort(hs.begin(), hs.end());
+    std::vector<uint64_t> name_hash(n_ref);
+    for (uint32_t r = 0; r < n_ref; ++r) name_hash[r] = hs[r].first, name_id[r] = hs[r].second;
+    for (const auto &ci : *chrs)
+        if (ci.chromosome < n_ref) sel[ci.chromosome] = 1;
+    BAM_TRY(w->names.grow(names.size(), 0, s));
+    BAM_TRY(w->name_off.grow(n_ref + 1, 0, s));
+    BAM_TRY(w->name_hash.grow(n_ref, 0, s));
+    BAM_TRY(w->name_id.grow(n_ref, 0, s));
+    BAM_TRY(w->sel.grow(sel.size(), 0, s));
+    BAM_TRY(w->err.grow(1, 0, s));
+    if (!names.empty()) BAM_TRY(hipMemcpyAsync(w->names.p, names.data(), names.size(), hipMemcpyHostToDevice, s));
+    BAM_TRY(hipMemcpyAsync(w->name_off.p, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice, s));
+    if (n_ref) {
+        BAM_TRY(hipMemcpyAsync(w->name_hash.p, name_hash.data(), n_ref * 8ull, hipMemcpyHostToDevice, s));
+        BAM_TRY(hipMemcpyAsync(w->name_id.p, name_id.data(), n_ref * 4ull, hipMemcpyHostToDevice, s));
+    }
+    BAM_TRY(hipMemcpyAsync(w->sel.p, sel.data(), sel.size(), hipMemcpyHostToDevice, s));
+    const SamRefs refs{w->names.p, w->name_off.p, w->name_hash.p, w->name_id.p, w->sel.p, n_ref};
+    if (t) t->upload_ms += ms_since(t0);
+
+    FileSink sink(path, f, *chrs, *runs);
+    sink.line0 = line0;
+    bool have_prev = false;
+    int64_t prev_ref = -1, prev_pos = 0;
+    uint64_t line_base = 0;  // lines of the body before the range
+    for (uint64_t r0 = h.body; r0 < m.n;) {
+        uint64_t r1 = std::min<uint64_t>(m.n, r0 + std::max<uint64_t>(batch, 1));
+        if (r1 < m.n) {
+            const uint8_t *nl = static_cast<const uint8_t *>(std::memchr(m.p + r1 - 1, '\n', m.n - (r1 - 1)));
+            r1 = nl ? uint64_t(nl - m.p) + 1 : m.n;
+        }
+        const uint64_t len = r1 - r0;
+        if (len >= (1ull << 32) - 64)
+            return fail(SECEDO_E_LIMIT, "file " + std::to_string(f) + " (" + path +
+                                            "): a range of SAM lines of 4 GiB or more (a line that long)");
+        const bool ends_file = r1 == m.n, trailing = m.p[r1 - 1] == '\n';
+        // text read
+        t0 = Clock::now();
+        w->h_text.assign(m.p + r0, m.p + r1);
+        if (t) {
+            t->inflate_ms += ms_since(t0);
+            t->inflated_bytes += double(len);
+        }
+        // upload, zero-padded to whole 16-byte vectors plus one
+        t0 = Clock::now();
+        const uint64_t n16 = (len + 15) / 16, padded = n16 * 16 + 16;
+        BAM_TRY(w->text.grow(padded, 0, s));
+        BAM_TRY(hipMemcpyAsync(w->text.p, w->h_text.data(), len, hipMemcpyHostToDevice, s));
+        BAM_TRY(hipMemsetAsync(w->text.p + len, 0, padded - len, s));
+        BAM_TRY(hipStreamSynchronize(s));
+        if (t) t->upload_ms += ms_since(t0);
+        // device parse
+        t0 = Clock::now();
+        BAM_TRY(w->cnt.grow(n16 + 1, 0, s));
+        BAM_TRY(w->scan.grow(n16 + 1, 0, s));
+        size_t tb = scan_bytes(n16 + 1);
+        BAM_TRY(w->tmp.grow(tb, 0, s));
+        BAM_TRY(sam_newline_count(w->text.p, n16, w->cnt.p, s));
+        BAM_TRY(hipMemsetAsync(w->cnt.p + n16, 0, 4, s));
+        BAM_TRY(exclusive_sum(w->tmp.p, tb, w->cnt.p, w->scan.p, n16 + 1, s));
+        uint32_t n_nl = 0;
+        BAM_TRY(hipMemcpyAsync(&n_nl, w->scan.p + n16, 4, hipMemcpyDeviceToHost, s));
+        BAM_TRY(hipStreamSynchronize(s));
+        const uint32_t n_lines = n_nl + (trailing ? 0 : 1);
+        BAM_TRY(w->start.grow(uint64_t(n_lines) + 1, 0, s));
+        BAM_TRY(w->size.grow(uint64_t(n_lines) + 1, 0, s));
+        BAM_TRY(w->off.grow(uint64_t(n_lines) + 1, 0, s));
+        BAM_TRY(w->ref.grow(n_lines, 0, s));
+        BAM_TRY(w->pos.grow(n_lines, 0, s));
+        BAM_TRY(sam_line_starts(w->text.p, n16, w->scan.p, n_lines, uint32_t(len), !trailing, w->start.p, s));
+        BAM_TRY(hipMemsetAsync(w->err.p, 0xFF, 8, s));
+        BAM_TRY(sam_size(w->text.p, w->start.p, n_lines, line_base, ends_file, refs, w->size.p, w->ref.p, w->pos.p,
+                         w->err.p, s));
+        BAM_TRY(hipMemsetAsync(w->size.p + n_lines, 0, 8, s));
+        tb = scan_bytes(uint64_t(n_lines) + 1);
+        BAM_TRY(w->tmp.grow(tb, 0, s));
+        BAM_TRY(exclusive_sum64(w->tmp.p, tb, w->size.p, w->off.p, uint64_t(n_lines) + 1, s));
+        uint64_t total = 0;
+        unsigned long long err = 0;
+        BAM_TRY(hipMemcpyAsync(&total, w->off.p + n_lines, 8, hipMemcpyDeviceToHost, s));
+        BAM_TRY(hipMemcpyAsync(&err, w->err.p, 8, hipMemcpyDeviceToHost, s));
+        BAM_TRY(hipStreamSynchronize(s));
+        // lines below the first bad one are encoded and walked: a structural error there comes first
+        const uint32_t limit = err == ~0ull ? n_lines : uint32_t((err >> 8) - line_base);
+        BAM_TRY(w->out.grow(total, 0, s));
+        BAM_TRY(sam_encode(w->text.p, w->start.p, limit, refs, w->off.p, w->out.p, s));
+        w->h_ref.resize(limit);
+        w->h_pos.resize(limit);
+        w->h_out.resize(total);
+        if (limit) {
+            BAM_TRY(hipMemcpyAsync(w->h_ref.data(), w->ref.p, limit * 4ull, hipMemcpyDeviceToHost, s));
+            BAM_TRY(hipMemcpyAsync(w->h_pos.data(), w->pos.p, limit * 4ull, hipMemcpyDeviceToHost, s));
+        }
+        if (total) BAM_TRY(hipMemcpyAsync(w->h_out.data(), w->out.p, total, hipMemcpyDeviceToHost, s));
+        BAM_TRY(hipStreamSynchronize(s));
+        // sortedness over every line, the selected records into the runs
+        uint64_t o = 0;
+        for (uint32_t k = 0; k < limit; ++k) {
+            const int32_t ref = w->h_ref[k], pos = w->h_pos[k];
+            if (ref == kSamNoRecord) continue;
+            const uint64_t idx = line_base + k;
+            const int64_t key_ref = ref < 0 ? INT64_MAX : ref;
+            if (have_prev && (key_ref < prev_ref || (key_ref == prev_ref && ref >= 0 && pos < prev_pos)))
+                return fail(SECEDO_E_INVALID_ARG,
+                            record_where(path, f, line0, idx) + ": input is not coordinate-sorted");
+            have_prev = true;
+            prev_ref = key_ref;
+            prev_pos = pos;
+            if (ref >= 0 && uint32_t(ref) < n_ref && sel[ref]) {
+                const uint8_t *rec = w->h_out.data() + o;
+                BAM_CALL(sink(idx, rec, ref, pos));
+                o += 4 + uint64_t(rd32(rec));
+            }
+        }
+        if (err != ~0ull) {
+            const uint32_t code = uint32_t(err & 0xFF);
+            return fail(code == kSamManyOps || code == kSamTooLong ? SECEDO_E_LIMIT : SECEDO_E_INVALID_ARG,
+                        record_where(path, f, line0, err >> 8) + " " + sam_what(code));
+        }
+        if (t) t->walk_ms += ms_since(t0);
+        line_base += n_lines;
+        r0 = r1;
+    }
+    return SECEDO_OK;
+}
+
 int load_inputs(const std::vector<std::string> &files, uint32_t threads, std::vector<ChrInput> *chrs,
                 secedo_bam_times *t) {
     const size_t n_files = files.size();
@@ -437,14 +743,28 @@ int load_inputs(const std::vector<std::string> &files, uint32_t threads, std::ve
         c.roff.assign(n_files, {});
         c.rpos.assign(n_files, {});
         c.ridx.assign(n_files, {});
+        c.paths = files;
+        c.line0.assign(n_files, 0);
     }
+    std::vector<char> sam(n_files, 0);
+    for (size_t f = 0; f < n_files; ++f) {
+        bool is_sam = false;
+        BAM_CALL(sniff(files[f], &is_sam));
+        sam[f] = is_sam;
+    }
+    SamWork sam_work;
     std::vector<std::vector<std::vector<uint8_t>>> runs(chrs->size(), std::vector<std::vector<uint8_t>>(n_files));
     size_t f0 = 0;
     while (f0 < n_files) {
-        // a batch of files of at most `batch` bytes on disk (BGZF inflates 3-4x), at least one file
+        if (sam[f0]) {  // SAM text: parsed on the device in ranges of about `batch` bytes
+            BAM_CALL(load_sam_file(files[f0], f0, batch, &sam_work, chrs, &runs, t));
+            ++f0;
+            continue;
+        }
+        // a batch of BAM files of at most `batch` bytes on disk (BGZF inflates 3-4x), at least one file
         size_t f1 = f0;
         uint64_t disk = 0;
-        while (f1 < n_files && (f1 == f0 || disk < batch / 4)) {
+        while (f1 < n_files && !sam[f1] && (f1 == f0 || disk < batch / 4)) {
             struct stat st;
             disk += stat(files[f1].c_str(), &st) == 0 ? uint64_t(st.st_size) : 0;
             ++f1;
@@ -492,40 +812,6 @@ int load_inputs(const std::vector<std::string> &files, uint32_t threads, std::ve
     if (t) t->walk_ms += ms_since(t0);
     return SECEDO_OK;
 }
-
-template <class T>
-struct Dev {
-    T *p = nullptr;
-    size_t n = 0;
-    Dev() = default;
-    Dev(const Dev &) = delete;
-    Dev &operator=(const Dev &) = delete;
-    ~Dev() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t alloc(size_t count) {
-        reset();
-        n = count;
-        return hipMalloc(&p, std::max<size_t>(1, count) * sizeof(T));
-    }
-    // keep the first `keep` elements, grow to at least `count`
-    hipError_t grow(size_t count, size_t keep, hipStream_t s) {
-        if (count <= n && p) return hipSuccess;
-        size_t cap = std::max<size_t>(count, 2 * n);
-        T *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(1, cap) * sizeof(T));
-        if (e != hipSuccess) return e;
-        if (keep) e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (p) (void)hipFree(p);
-        p = q;
-        n = cap;
-        return e;
-    }
-};
 
 struct Result {
     std::vector<uint32_t> chr_locus_off{0};
@@ -781,8 +1067,9 @@ int run_chromosome(const ChrInput &ci, const Params &prm, const CellList *cells,
             file = ord.ord_file[o];
             idx = ord.ord_idx[o];
         }
-        return fail(SECEDO_E_INVALID_ARG, "file " + std::to_string(file) + ", record " + std::to_string(idx) + ": " +
-                                              (code < 7 ? what[code] : "?"));
+        const std::string where = ci.line0[file] ? record_where(ci.paths[file], file, ci.line0[file], idx)
+                                                 : "file " + std::to_string(file) + ", record " + std::to_string(idx);
+        return fail(SECEDO_E_INVALID_ARG, where + ": " + (code < 7 ? what[code] : "?"));
     }
     // name numbering
     Dev<uint8_t> tmp;

@@ -1,6 +1,7 @@
 """``python -m secedo_amd.pileup_main``: the reference's ``pileup`` executable (pileup_main.cpp) on the GPU path.
 
-Flags as in the reference: -i (a BAM file or a directory searched recursively for *.bam), -o (file prefix),
+Flags as in the reference: -i (a BAM or SAM file, or a directory searched recursively for *.bam, or for *.sam when it
+holds no BAM), -o (file prefix),
 --chromosomes, --min_base_quality, --min_map_quality, --min_map_score, --max_coverage, --min_different,
 --num_threads (here only the size of the host inflate pool, capped at 16). Writes
 <o>_<chromosome>.pileup.{bin,map,txt} per chromosome and, for a directory input, the cell map
@@ -11,6 +12,9 @@ being its Z-typed TG value. --cells FILE lists the barcodes (one per line; empty
 barcodes.tsv works); without it the cells are every value with at least --min_cell_records records over the requested
 chromosomes, sorted bytewise, so that every <o>_<chromosome>.pileup.bin shares one numbering. The cell map
 <o>_<chromosomes>.map then holds barcode<TAB>index, for a file input too.
+
+SAM text input (coordinate-sorted, as aligners write it) goes the same way: its lines are parsed on the GPU into the
+BAM records the BAM route reads, so a SAM file gives what the BAM `samtools view -b` writes from it would give.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ MAX_POOL = 16
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(prog="python -m secedo_amd.pileup_main", description=__doc__.splitlines()[0])
-    ap.add_argument("-i", required=True, help="Input BAM file, or a directory containing BAM files")
+    ap.add_argument("-i", required=True, help="Input BAM or SAM file, or a directory containing BAM files (or SAM files when it holds no BAM)")
     ap.add_argument("-o", default="./", help="File prefix of the output: <o>_<chromosome>.pileup.bin etc.")
     ap.add_argument("--num_threads", type=int, default=8, help="Host inflate threads (at most 16 are used)")
     ap.add_argument("--chromosomes", default=DEFAULT_CHROMOSOMES, help="Comma-separated chromosomes (1..22, X, Y)")
@@ -94,13 +98,18 @@ def pool_size(num_threads: int) -> int:
     return max(1, min(int(num_threads), MAX_POOL))
 
 
-def input_files(path: str) -> List[str]:
-    if not os.path.isdir(path):
-        return [path]
+def _find(path: str, ext: str) -> List[str]:
     found = []
     for root, _dirs, names in os.walk(path):
-        found.extend(os.path.join(root, n) for n in names if os.path.splitext(n)[1] == ".bam")
+        found.extend(os.path.join(root, n) for n in names if os.path.splitext(n)[1] == ext)
     return sorted(found)
+
+
+def input_files(path: str) -> List[str]:
+    """A file as given; a directory's *.bam files, or its *.sam files when it holds no BAM."""
+    if not os.path.isdir(path):
+        return [path]
+    return _find(path, ".bam") or _find(path, ".sam")
 
 
 def cell_map_lines(files: List[str]) -> List[str]:
@@ -120,7 +129,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise SystemExit("Input %s does not exist" % a.i)
     files = input_files(a.i)
     if os.path.isdir(a.i) and not files:
-        print("No BAM files found in %s. Done." % a.i)
+        print("No BAM or SAM files found in %s. Done." % a.i)
         return 0
     if os.path.isdir(a.i) and a.cell_tag is None:
         with open(a.o + "_" + a.chromosomes + ".map", "w") as f:

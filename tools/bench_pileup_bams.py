@@ -12,6 +12,11 @@ position order) and adds the tag-mode call (pileup_bams with cell_tag="CB") besi
 times, and whether its .bin and .map equal the per-file call's. Its device time includes the front passes (cells,
 compaction, sort, order); the rocprofv3 merge below lists them as front_ms.
 
+--sam also writes the set as SAM text (one .sam per cell; with --multiplexed also the tagged set as one .sam, lines
+in the multiplexed BAM's order) and times the SAM route beside the BAM route in the same process: its step times
+(inflate_ms is the text read, walk_ms includes the device parse), and whether its .bin and .map equal the BAM
+route's. --sam-only runs just the SAM calls once each, for a rocprofv3 run of its own; --merge-sam LINE.json OUT then
+adds the SAM kernels' times and their text GB/s against HBM peak.
 Kernel times come from a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_pileup_bams.py --dir D \
         --repeat 1 --resident-only
@@ -116,6 +121,92 @@ def write_multiplexed(d, paths, seed_stamp):
     return path, barcodes, time.time() - t0
 
 
+SEQ_LETTERS = np.frombuffer(b"=ACMGRSVTWYHKDBN", dtype=np.uint8)
+
+
+def _sam_cell(args):
+    """uniform_cell_bam's records (fixed 211-byte layout, a 17-character name stored without its NUL) as SAM lines
+    -> (header text, lines, line offsets, positions). A mate position before the chromosome start (no pass reads
+    it) becomes PNEXT 0. tag: appended to every line (the multiplexed set's CB:Z field)"""
+    path, tag = args
+    raw = gzip.decompress(open(path, "rb").read())
+    l_text = struct.unpack_from("<i", raw, 4)[0]
+    text = raw[8:8 + l_text]
+    rec = np.frombuffer(raw, dtype=np.uint8, offset=8 + l_text + 4 + 4 + 2 + 4).reshape(-1, 211)
+    n = rec.shape[0]
+    pos = rec[:, 8:12].copy().view("<i4").ravel()
+    flag = rec[:, 18:20].copy().view("<u2").ravel()
+    npos = rec[:, 28:32].copy().view("<i4").ravel()
+    seq = np.empty((n, 100), dtype=np.uint8)
+    seq[:, 0::2] = SEQ_LETTERS[rec[:, 57:107] >> 4]
+    seq[:, 1::2] = SEQ_LETTERS[rec[:, 57:107] & 15]
+    qual = rec[:, 107:207] + 33
+    score = rec[:, 210]
+    suffix = (b"\t" + tag if tag else b"") + b"\n"
+    lines = [b"%s\t%d\t1\t%d\t60\t100M\t=\t%d\t0\t%s\t%s\tAS:i:%d%s" % (
+        rec[k, 36:53].tobytes(), flag[k], pos[k] + 1, max(npos[k] + 1, 0), seq[k].tobytes(), qual[k].tobytes(), score[k],
+        suffix) for k in range(n)]
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in lines], out=off[1:])
+    return text, b"".join(lines), off, pos
+
+
+def _sam_file(args):
+    bam, sam = args
+    text, body, _, _ = _sam_cell((bam, None))
+    with open(sam, "wb") as f:
+        f.write(text + body)
+
+
+def write_sam_set(d, paths, seed_stamp, multiplexed):
+    """The cells of write_set as SAM files under <d>/sam, and with multiplexed the tagged set as one SAM whose lines
+    follow the multiplexed BAM's order -> (sam paths, multiplexed sam path or None, seconds)"""
+    sd = os.path.join(d, "sam")
+    os.makedirs(sd, exist_ok=True)
+    sams = [os.path.join(sd, os.path.basename(p)[:-4] + ".sam") for p in paths]
+    mpath = os.path.join(d, "multiplexed.sam") if multiplexed else None
+    stamp = os.path.join(sd, "set.json")
+    want = dict(seed_stamp, multiplexed=multiplexed)
+    if os.path.exists(stamp) and json.load(open(stamp)) == want:
+        return sams, mpath, 0.0
+    t0 = time.time()
+    with Pool(16) as pool:
+        pool.map(_sam_file, list(zip(paths, sams)), chunksize=4)
+        if multiplexed:
+            parts = pool.map(_sam_cell, [(p, b"CB:Z:C%05d-1" % c) for c, p in enumerate(paths)], chunksize=4)
+            pos = np.concatenate([x[3] for x in parts])
+            cell = np.concatenate([np.full(len(x[3]), c, dtype=np.int64) for c, x in enumerate(parts)])
+            k = np.concatenate([np.arange(len(x[3])) for x in parts])
+            order = np.argsort(pos, kind="stable")  # the multiplexed BAM's record order
+            with open(mpath, "wb") as f:
+                f.write(parts[0][0])
+                for i in order:
+                    c, j = cell[i], k[i]
+                    f.write(parts[c][1][parts[c][2][j]:parts[c][2][j + 1]])
+            del parts
+    json.dump(want, open(stamp, "w"))
+    return sams, mpath, time.time() - t0
+
+
+def merge_sam(line_path, prof_dir):
+    """The SAM kernels of a --sam-only rocprofv3 run: ms per call and text GB/s against HBM peak"""
+    line = json.loads(open(line_path).read().strip().splitlines()[-1])
+    f = sorted(glob.glob(os.path.join(prof_dir, "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)[-1]
+    kernels = {}
+    for r in csv.DictReader(open(f)):
+        if "k_sam_" not in r["Name"]:
+            continue
+        short = r["Name"].replace("secedo::bam::(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        kernels[short] = dict(calls=int(r["Calls"]), ms=round(float(r["TotalDurationNs"]) / 1e6, 3))
+    total = sum(k["ms"] for k in kernels.values())
+    text = line["sam_text_bytes"] + line.get("sam_multiplexed_text_bytes", 0)
+    line["sam_kernels"] = kernels
+    line["sam_kernel_ms"] = round(total, 3)
+    line["sam_text_GBps"] = text / (total * 1e-3) / 1e9
+    line["sam_fraction_of_hbm_peak"] = text / (total * 1e-3) / HBM_PEAK
+    print(json.dumps(line))
+
+
 def merge(line_path, prof_dir):
     line = json.loads(open(line_path).read().strip().splitlines()[-1])
     f = sorted(glob.glob(os.path.join(prof_dir, "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)[-1]
@@ -161,10 +252,16 @@ def main():
     ap.add_argument("--multiplexed", action="store_true", help="Also the tag-mode call on the set as one BAM")
     ap.add_argument("--multiplexed-only", action="store_true",
                     help="Only the tag-mode resident call (for a rocprofv3 run of its own)")
+    ap.add_argument("--sam", action="store_true", help="Also the SAM route on the set written as SAM")
+    ap.add_argument("--sam-only", action="store_true", help="Only the SAM calls, once each (for rocprofv3)")
     ap.add_argument("--merge", nargs=2, metavar=("LINE", "PROF_DIR"))
+    ap.add_argument("--merge-sam", nargs=2, metavar=("LINE", "PROF_DIR"))
     a = ap.parse_args()
     if a.merge:
         merge(*a.merge)
+        return
+    if a.merge_sam:
+        merge_sam(*a.merge_sam)
         return
     paths, gen_s = write_set(a.dir, a.cells, a.pairs, a.mbp)
     import secedo_amd
@@ -174,6 +271,21 @@ def main():
     if a.multiplexed or a.multiplexed_only:
         mpath, barcodes, mux_s = write_multiplexed(a.dir, paths, dict(cells=a.cells, pairs=a.pairs, mbp=a.mbp))
         print("multiplexed BAM ready (%.1f s)" % mux_s, file=sys.stderr, flush=True)
+    if a.sam or a.sam_only:
+        sams, msam, sam_s = write_sam_set(a.dir, paths, dict(cells=a.cells, pairs=a.pairs, mbp=a.mbp),
+                                          a.multiplexed)
+        print("SAM set ready (%.1f s)" % sam_s, file=sys.stderr, flush=True)
+    if a.sam_only:
+        t = {}
+        p = bam_pileup.pileup_bams(sams, None, False, 0, 100, 30, 30, 0, a.threads, 3, times=t)
+        line = dict(workload="uniform_sam", cells=a.cells, sam_text_bytes=t["inflated_bytes"], loci=p.n_loci)
+        if msam:
+            t = {}
+            bam_pileup.pileup_bams([msam], None, False, 0, 100, 30, 30, 0, a.threads, 3, times=t, cell_tag="CB",
+                                   cells=barcodes)
+            line["sam_multiplexed_text_bytes"] = t["inflated_bytes"]
+        print(json.dumps(line), flush=True)
+        return
     if a.multiplexed_only:
         with secedo_amd.SimilarityMatrixPlan(0) as plan:
             for k in range(a.repeat + 1):
@@ -217,6 +329,9 @@ def main():
             m["bin_equal"] = open(mout + ".bin", "rb").read() == open(out + ".bin", "rb").read()
             m["map_equal"] = open(mout + ".map", "rb").read() == open(out + ".map", "rb").read()
             line["multiplexed"] = m
+        if a.sam:
+            line["sam"] = sam_route(a, sams, [msam] if msam else None, barcodes if msam else None, out,
+                                    mout if msam else None, sam_s, med)
     with secedo_amd.SimilarityMatrixPlan(0) as plan:
         rt = []
         for k in range(a.repeat + 1):
@@ -232,7 +347,52 @@ def main():
     line["records"] = n_rec
     line["record_bytes"] = n_rec * 211  # uniform_cell_bam's fixed record size
     line["window_positions"] = int(a.mbp * 1_000_000)
+    if "sam" in line:
+        print_table(line)
     print(json.dumps(line), flush=True)
+
+
+STEPS = ("inflate_ms", "walk_ms", "upload_ms", "device_ms", "write_ms", "total_ms")
+
+
+def sam_route(a, sams, msam, barcodes, out, mout, sam_s, med):
+    """The SAM route's step times (medians of --repeat runs after one untimed run), its outputs against the BAM
+    route's (out / mout), and a table of both routes on stderr"""
+    from secedo_amd import bam_pileup
+
+    def timed(files, prefix, **kw):
+        runs = []
+        for k in range(a.repeat + 1):
+            t = {}
+            bam_pileup.pileup_bams(files, prefix, True, 0, 100, 30, 30, 0, a.threads, 3, times=t, **kw)
+            if k:
+                runs.append(t)
+        r = {key: round(med([x[key] for x in runs]), 2) for key in STEPS}
+        r["text_bytes"] = runs[0]["inflated_bytes"]
+        r["text_read_GBps"] = r["text_bytes"] / (r["inflate_ms"] * 1e-3) / 1e9
+        for ext in (".bin", ".map"):
+            r[ext[1:] + "_equal"] = open(prefix + ext, "rb").read() == open(out_of[prefix] + ext, "rb").read()
+        return r
+
+    sout = os.path.join(a.dir, "sout")
+    out_of = {sout: out}
+    res = dict(set_write_s=round(sam_s, 1), per_file=timed(sams, sout))
+    if msam:
+        smout = os.path.join(a.dir, "smout")
+        out_of[smout] = mout
+        res["multiplexed"] = timed(msam, smout, cell_tag="CB", cells=barcodes)
+    return res
+
+
+def print_table(line):
+    rows = [("BAM per-file", line), ("SAM per-file", line["sam"]["per_file"])]
+    if "multiplexed" in line:
+        rows.append(("BAM multiplexed", line["multiplexed"]))
+    if "multiplexed" in line["sam"]:
+        rows.append(("SAM multiplexed", line["sam"]["multiplexed"]))
+    print("%-16s" % "ms" + "".join("%11s" % k[:-3] for k in STEPS), file=sys.stderr)
+    for name, r in rows:
+        print("%-16s" % name + "".join("%11.1f" % r[k] for k in STEPS), file=sys.stderr)
 
 
 if __name__ == "__main__":
