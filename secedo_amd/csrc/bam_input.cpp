@@ -1,0 +1,789 @@
+// bam_input.cpp -- the input side of include/secedo_bam.h: BGZF inflate, the BAM header and record walk, the SAM
+// header and the driver of the device parse (sam_kernels.hip), and secedo_bam_scan. Its product is one ChrInput per
+// requested chromosome (bam_host.hpp), which bam_pileup.cpp turns into the pileup.
+//
+// Each file is memory-mapped; its BGZF blocks (BSIZE from the BC extra field) are inflated with zlib raw inflate
+// in a pool of at most 16 threads, CRC32 and ISIZE checked. Files are inflated in batches of about 512 MiB of
+// inflated data (SECEDO_BAM_BATCH_BYTES overrides it); a file alone in its batch is inflated and walked in ranges
+// of BGZF blocks of that size, a record cut at a range's end carried into the next, so one large multiplexed BAM
+// never sits inflated in RAM. Of each file only the byte run of the requested chromosomes' records is kept. No .bai
+// is needed: the run is found by walking block_size, so with or without an index the result is the same.
+#include "bam_host.hpp"
+#include "bam_kernels.hpp"  // the scan wrappers
+#include "sam_kernels.hpp"
+
+#include <zlib.h>
+
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <climits>
+#include <cstdlib>
+#include <set>
+#include <thread>
+
+namespace {
+
+using namespace secedo::bam;
+using namespace secedo::bam_host;
+
+constexpr uint32_t kMaxThreads = 16;
+constexpr uint64_t kBatchBytes = 512ull << 20;
+
+// inflated bytes per batch of files and per block range of one file; SECEDO_BAM_BATCH_BYTES overrides it (tests:
+// outputs do not depend on it), read at every call
+uint64_t batch_bytes() {
+    const char *e = std::getenv("SECEDO_BAM_BATCH_BYTES");
+    if (e && *e) {
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v > 0) return v;
+    }
+    return kBatchBytes;
+}
+
+template <class F>
+void parallel_for(uint32_t threads, uint64_t n, F f) {
+    threads = std::max<uint32_t>(1, std::min<uint64_t>(std::min(threads, kMaxThreads), n));
+    std::atomic<uint64_t> next{0};
+    auto work = [&] {
+        for (uint64_t i; (i = next.fetch_add(1)) < n;) f(i);
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto &t : pool) t.join();
+}
+
+struct Mapped {
+    const uint8_t *p = nullptr;
+    size_t n = 0;
+    ~Mapped() {
+        if (p && n) munmap(const_cast<uint8_t *>(p), n);
+    }
+};
+
+int map_file(const std::string &path, Mapped *m) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return fail(SECEDO_E_INVALID_ARG, "Could not open " + path);
+    struct stat st;
+    if (fstat(fd, &st) != 0) {
+        close(fd);
+        return fail(SECEDO_E_INVALID_ARG, "Could not stat " + path);
+    }
+    m->n = size_t(st.st_size);
+    if (m->n) {
+        void *p = mmap(nullptr, m->n, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (p == MAP_FAILED) {
+            close(fd);
+            return fail(SECEDO_E_INVALID_ARG, "Could not map " + path);
+        }
+        m->p = static_cast<const uint8_t *>(p);
+    }
+    close(fd);
+    return SECEDO_OK;
+}
+
+struct Block {
+    const uint8_t *cdata;
+    uint32_t clen, crc, isize;
+    uint64_t out;  // offset in the file's inflated buffer
+};
+
+// BGZF block list of one mapped file
+int list_blocks(const std::string &path, const Mapped &m, std::vector<Block> *blocks, uint64_t *total) {
+    uint64_t off = 0, out = 0;
+    while (off < m.n) {
+        const uint8_t *b = m.p + off;
+        if (m.n - off < 18 || b[0] != 31 || b[1] != 139 || b[2] != 8 || !(b[3] & 4))
+            return fail(SECEDO_E_INVALID_ARG, path + ": not a BGZF block at byte " + std::to_string(off));
+        const uint32_t xlen = rd16(b + 10);
+        uint32_t bsize = UINT32_MAX;
+        for (uint32_t x = 12; x + 4 <= 12 + xlen && 12 + xlen <= m.n - off;) {
+            const uint32_t slen = rd16(b + x + 2);
+            if (b[x] == 'B' && b[x + 1] == 'C' && slen == 2) bsize = rd16(b + x + 4);
+            x += 4 + slen;
+        }
+        if (bsize == UINT32_MAX || uint64_t(bsize) + 1 > m.n - off || bsize + 1 < 12 + xlen + 8)
+            return fail(SECEDO_E_INVALID_ARG, path + ": bad BGZF block size at byte " + std::to_string(off));
+        const uint32_t len = bsize + 1;
+        Block blk{b + 12 + xlen, len - xlen - 20, rd32(b + len - 8), rd32(b + len - 4), out};
+        if (blk.isize > 65536) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF ISIZE above 64 KiB");
+        blocks->push_back(blk);
+        out += blk.isize;
+        off += len;
+    }
+    *total = out;
+    return SECEDO_OK;
+}
+
+// 0 on success, else a message
+std::string inflate_block(const Block &b, uint8_t *dst) {
+    z_stream z{};
+    if (inflateInit2(&z, -15) != Z_OK) return "inflateInit2 failed";
+    z.next_in = const_cast<Bytef *>(b.cdata);
+    z.avail_in = b.clen;
+    z.next_out = dst;
+    z.avail_out = b.isize;
+    const int rc = inflate(&z, Z_FINISH);
+    const uint64_t got = z.total_out;
+    inflateEnd(&z);
+    if (rc != Z_STREAM_END || got != b.isize) return "inflate failed or ISIZE mismatch";
+    if (uint32_t(crc32(crc32(0, nullptr, 0), dst, b.isize)) != b.crc) return "CRC32 mismatch";
+    return std::string();
+}
+
+// a file mapped and its BGZF blocks listed; *total = its inflated size
+int open_bgzf(const std::string &path, Mapped *m, std::vector<Block> *blocks, uint64_t *total) {
+    SECEDO_CALL(map_file(path, m));
+    return list_blocks(path, *m, blocks, total);
+}
+
+struct InflateJob {
+    const std::string *path;
+    const Block *block;
+    uint64_t index;  // of the block in its file (messages)
+    uint8_t *dst;
+};
+
+// the jobs in one pool; the first failed job in list order is the error
+int inflate_blocks(const std::vector<InflateJob> &jobs, uint32_t threads) {
+    std::vector<std::string> errs(jobs.size());
+    parallel_for(threads, jobs.size(), [&](uint64_t k) { errs[k] = inflate_block(*jobs[k].block, jobs[k].dst); });
+    for (size_t k = 0; k < jobs.size(); ++k)
+        if (!errs[k].empty())
+            return fail(SECEDO_E_INVALID_ARG,
+                        *jobs[k].path + ": BGZF block " + std::to_string(jobs[k].index) + ": " + errs[k]);
+    return SECEDO_OK;
+}
+
+struct Inflated {
+    std::string path;
+    std::vector<uint8_t> data;
+    uint64_t n_blocks = 0;
+};
+
+// inflate a batch of files: all their blocks in one pool
+int inflate_files(const std::vector<std::string> &paths, uint32_t threads, std::vector<Inflated> *out) {
+    std::vector<Mapped> maps(paths.size());
+    std::vector<std::vector<Block>> blocks(paths.size());
+    std::vector<InflateJob> jobs;
+    out->resize(paths.size());
+    for (size_t f = 0; f < paths.size(); ++f) {
+        uint64_t total = 0;
+        SECEDO_CALL(open_bgzf(paths[f], &maps[f], &blocks[f], &total));
+        (*out)[f].path = paths[f];
+        (*out)[f].data.resize(total);
+        (*out)[f].n_blocks = blocks[f].size();
+        for (size_t b = 0; b < blocks[f].size(); ++b)
+            jobs.push_back({&paths[f], &blocks[f][b], b, (*out)[f].data.data() + blocks[f][b].out});
+    }
+    return inflate_blocks(jobs, threads);
+}
+
+struct Header {
+    uint32_t l_text = 0, n_ref = 0;
+    uint64_t first_record = 0;
+};
+
+constexpr int kNeedMore = 1;  // parse_header / walk_range: the bytes end inside the header or a record
+
+// final: d ends the file, so a cut header is an error; else kNeedMore
+int parse_header(const std::string &path, const uint8_t *d, uint64_t n, bool final, Header *h) {
+    if ((n >= 4 && std::memcmp(d, "BAM\1", 4) != 0) || (final && n < 12))
+        return fail(SECEDO_E_INVALID_ARG, path + ": not a BAM file (magic)");
+    if (n < 12) return kNeedMore;
+    h->l_text = rd32(d + 4);
+    uint64_t o = 8 + uint64_t(h->l_text);
+    if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated header") : kNeedMore;
+    h->n_ref = rd32(d + o);
+    o += 4;
+    for (uint32_t r = 0; r < h->n_ref; ++r) {
+        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
+        o += 4 + uint64_t(rd32(d + o));
+        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
+        o += 4;
+    }
+    h->first_record = o;
+    return SECEDO_OK;
+}
+
+// (RefID, Position) of one record after another: coordinate order puts the unmapped (RefID < 0) last
+struct SortCheck {
+    bool any = false;
+    int64_t prev_ref = -1, prev_pos = 0;
+    // false: the record sorts before the one before it
+    bool check(int32_t ref, int32_t pos) {
+        const int64_t key_ref = ref < 0 ? INT64_MAX : ref;
+        const bool ok = !any || !(key_ref < prev_ref || (key_ref == prev_ref && ref >= 0 && pos < prev_pos));
+        any = true;
+        prev_ref = key_ref;
+        prev_pos = pos;
+        return ok;
+    }
+};
+
+// The record walk of one file, carried across its block ranges.
+struct WalkState {
+    bool have_header = false;
+    Header h;
+    uint64_t idx = 0;
+    SortCheck order;
+    bool require_sorted = true;  // false (secedo_bam_scan): an unsorted file is walked to its end, `sorted` says so
+    bool sorted = true;
+};
+
+// Walks the header (first) and the complete records of d[0, n), the file's inflated bytes that follow what earlier
+// calls consumed; *used = bytes consumed, the rest starts the next range. final: d ends the file, so a cut record is
+// an error. Structure and sortedness checked; on_record(index, record, refID, pos).
+template <class F>
+int walk_range(const std::string &path, const uint8_t *d, uint64_t n, bool final, WalkState *st, uint64_t *used,
+               F on_record) {
+    uint64_t o = 0;
+    *used = 0;
+    if (!st->have_header) {
+        const int rc = parse_header(path, d, n, final, &st->h);
+        if (rc == kNeedMore) return SECEDO_OK;
+        SECEDO_CALL(rc);
+        st->have_header = true;
+        o = st->h.first_record;
+    }
+    for (;; ++st->idx) {
+        *used = o;
+        if (o >= n) return SECEDO_OK;
+        const std::string where = record_where(path, 0, 0, st->idx);
+        if (n - o < 4 + 32) return final ? fail(SECEDO_E_INVALID_ARG, where + " is truncated") : SECEDO_OK;
+        const uint32_t bs = rd32(d + o);
+        const uint8_t *c = d + o + 4;
+        if (bs < 32) return fail(SECEDO_E_INVALID_ARG, where + " has a bad block_size");
+        if (bs > n - o - 4) return final ? fail(SECEDO_E_INVALID_ARG, where + " has a bad block_size") : SECEDO_OK;
+        if (rec_aux_off(c) > bs) return fail(SECEDO_E_INVALID_ARG, where + " is longer than its block_size");
+        const int32_t ref = int32_t(rd32(c)), pos = int32_t(rd32(c + 4));
+        if (!st->order.check(ref, pos)) {
+            if (st->require_sorted) return fail(SECEDO_E_INVALID_ARG, where + ": input is not coordinate-sorted");
+            st->sorted = false;
+        }
+        SECEDO_CALL(on_record(st->idx, d + o, ref, pos));
+        o += 4 + uint64_t(bs);
+    }
+}
+
+// CIGAR ops and SEQ length agree (BuildCharData's substr would otherwise truncate)
+int check_cigar(const uint8_t *rec, const std::string &where) {
+    const uint8_t *c = rec + 4;
+    const uint32_t l_name = rec_l_name(c), n_cigar = rec_n_cigar(c), l_seq = rec_l_seq(c);
+    uint64_t query = 0;
+    for (uint32_t k = 0; k < n_cigar; ++k) {
+        const uint32_t v = rd32(c + 32 + l_name + 4 * k), t = v & 15;
+        if (t > 8) return fail(SECEDO_E_INVALID_ARG, where + ": invalid CIGAR op code " + std::to_string(t));
+        if (t == 0 || t == 1 || t == 4 || t == 7 || t == 8) query += v >> 4;
+    }
+    if (l_seq > 0 && n_cigar > 0 && query != l_seq)
+        return fail(SECEDO_E_INVALID_ARG, where + ": CIGAR and SEQ lengths differ");
+    return SECEDO_OK;
+}
+
+using Runs = std::vector<std::vector<std::vector<uint8_t>>>;  // [chr][file] the file's records of the chromosome
+
+// Per file: its records of each requested chromosome, appended as the walk meets them (one range after another).
+struct FileSink {
+    Inputs &in;
+    size_t f;
+    std::vector<std::vector<uint8_t> *> runs;  // [chr] this file's run
+    std::vector<int> started, done;
+    FileSink(Inputs &inputs, size_t file, Runs &r)
+        : in(inputs), f(file), runs(inputs.chrs.size()), started(inputs.chrs.size(), 0), done(inputs.chrs.size(), 0) {
+        for (size_t k = 0; k < runs.size(); ++k) runs[k] = &r[k][file];
+    }
+    int operator()(uint64_t idx, const uint8_t *rec, int32_t ref, int32_t pos) {
+        for (size_t c = 0; c < in.chrs.size(); ++c) {
+            ChrInput &ci = in.chrs[c];
+            if (done[c]) continue;
+            if (ref < 0 || uint32_t(ref) != ci.chromosome) {
+                if (started[c]) done[c] = 1;  // the reader stops at another RefID
+                continue;
+            }
+            const std::string where = record_where(in.paths[f], f, in.line0[f], idx);
+            if (pos < 0) return fail(SECEDO_E_INVALID_ARG, where + " has a negative position");
+            SECEDO_CALL(check_cigar(rec, where));
+            started[c] = 1;
+            std::vector<uint8_t> &run = *runs[c];
+            ci.roff[f].push_back(run.size());
+            ci.rpos[f].push_back(pos);
+            ci.ridx[f].push_back(idx);
+            run.insert(run.end(), rec, rec + 4 + rd32(rec));
+        }
+        return SECEDO_OK;
+    }
+};
+
+// One file larger than a batch, inflated and walked in ranges of BGZF blocks of about `batch` inflated bytes; a
+// record cut at a range's end is carried to the front of the next range. Host memory: one range plus the runs kept.
+int load_file_ranges(size_t f, uint32_t threads, uint64_t batch, Inputs *in, Runs *runs, secedo_bam_times *t) {
+    const std::string &path = in->paths[f];
+    Mapped m;
+    std::vector<Block> blocks;
+    uint64_t total = 0;
+    SECEDO_CALL(open_bgzf(path, &m, &blocks, &total));
+    WalkState st;
+    FileSink sink(*in, f, *runs);
+    std::vector<uint8_t> buf;
+    std::vector<InflateJob> jobs;
+    uint64_t carry = 0;
+    size_t b0 = 0;
+    do {
+        size_t b1 = b0;
+        uint64_t bytes = 0;
+        while (b1 < blocks.size() && (b1 == b0 || bytes + blocks[b1].isize <= batch)) bytes += blocks[b1++].isize;
+        Clock::time_point t0 = Clock::now();
+        buf.resize(carry + bytes);
+        jobs.clear();
+        for (size_t b = b0; b < b1; ++b)
+            jobs.push_back({&path, &blocks[b], b, buf.data() + carry + (blocks[b].out - blocks[b0].out)});
+        SECEDO_CALL(inflate_blocks(jobs, threads));
+        if (t) {
+            t->inflate_ms += ms_since(t0);
+            t->inflated_bytes += double(bytes);
+        }
+        t0 = Clock::now();
+        uint64_t used = 0;
+        SECEDO_CALL(walk_range(path, buf.data(), buf.size(), b1 == blocks.size(), &st, &used, sink));
+        carry = buf.size() - used;
+        if (used) std::memmove(buf.data(), buf.data() + used, carry);
+        buf.resize(carry);
+        if (t) t->walk_ms += ms_since(t0);
+        b0 = b1;
+    } while (b0 < blocks.size());
+    return SECEDO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// SAM text input: the header is parsed here, the alignment lines on the device (sam_kernels.hip) into the BAM records
+// the walk above collects. The file type comes from its first bytes: BGZF is BAM, plain gzip is refused, anything
+// else is SAM.
+
+// *sam = the file is SAM text; plain gzip (no BGZF extra field) is an error
+int sniff(const std::string &path, bool *sam) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return fail(SECEDO_E_INVALID_ARG, "Could not open " + path);
+    uint8_t b[512];
+    const ssize_t n = pread(fd, b, sizeof(b), 0);
+    close(fd);
+    if (n < 0) return fail(SECEDO_E_INVALID_ARG, "Could not read " + path);
+    *sam = !(n >= 2 && b[0] == 31 && b[1] == 139);
+    if (*sam) return SECEDO_OK;
+    bool bgzf = false;
+    if (n >= 12 && b[2] == 8 && (b[3] & 4)) {
+        const uint32_t end = std::min<uint32_t>(12 + rd16(b + 10), uint32_t(n));
+        for (uint32_t x = 12; x + 4 <= end; x += 4 + rd16(b + x + 2))
+            if (b[x] == 'B' && b[x + 1] == 'C') bgzf = true;
+    }
+    if (!bgzf)
+        return fail(SECEDO_E_INVALID_ARG, path + ": a gzip file that is not BGZF; decompress it to SAM or convert "
+                                                 "it to BAM (samtools view -b)");
+    return SECEDO_OK;
+}
+
+struct SamHeader {
+    std::vector<std::string> names;  // @SQ SN values by RefID
+    uint64_t lines = 0, body = 0;    // header lines, byte offset of the first alignment line
+};
+
+// the leading '@' lines: @SQ SN and LN required, SN unique
+int parse_sam_header(const std::string &path, size_t f, const Mapped &m, SamHeader *h) {
+    std::set<std::string> seen;
+    uint64_t o = 0;
+    while (o < m.n && m.p[o] == '@') {
+        const uint8_t *nl = static_cast<const uint8_t *>(std::memchr(m.p + o, '\n', m.n - o));
+        const uint64_t e = nl ? uint64_t(nl - m.p) : m.n;
+        ++h->lines;
+        const std::string line(reinterpret_cast<const char *>(m.p + o), e - o);
+        o = nl ? e + 1 : m.n;
+        if (line.compare(0, 3, "@SQ") != 0 || (line.size() > 3 && line[3] != '\t')) continue;
+        const std::string where = record_where(path, f, h->lines, 0);  // the header line itself
+        std::string sn;
+        bool has_sn = false, has_ln = false;
+        for (size_t a = 4; a <= line.size();) {
+            size_t b = line.find('\t', a);
+            if (b == std::string::npos) b = line.size();
+            const std::string fld = line.substr(a, b - a);
+            if (fld.compare(0, 3, "SN:") == 0 && !has_sn) {
+                sn = fld.substr(3);
+                has_sn = true;
+            } else if (fld.compare(0, 3, "LN:") == 0 && !has_ln) {
+                const std::string v = fld.substr(3);
+                if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != std::string::npos ||
+                    std::stoull(v) < 1 || std::stoull(v) > 2147483647ull)
+                    return fail(SECEDO_E_INVALID_ARG, where + ": @SQ LN is not an integer in [1, 2^31 - 1]");
+                has_ln = true;
+            }
+            a = b + 1;
+        }
+        if (!has_sn || !has_ln) return fail(SECEDO_E_INVALID_ARG, where + ": @SQ without SN or LN");
+        if (!seen.insert(sn).second) return fail(SECEDO_E_INVALID_ARG, where + ": @SQ SN:" + sn + " is listed twice");
+        h->names.push_back(sn);
+    }
+    h->body = o;
+    return SECEDO_OK;
+}
+
+// device buffers of the SAM passes, kept over the ranges and files of one call
+struct SamWork {
+    hipStream_t s = nullptr;
+    Dev<uint8_t> text, out, names, sel, tmp;
+    Dev<uint32_t> cnt, scan, start, name_off, name_id;
+    Dev<uint64_t> name_hash, size, off;
+    Dev<int32_t> ref, pos;
+    Dev<unsigned long long> err;
+    std::vector<uint8_t> h_text, h_out;
+    std::vector<int32_t> h_ref, h_pos;
+    ~SamWork() {
+        if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
+    }
+};
+
+const char *sam_what(uint32_t code) {
+    static const char *what[kSamCodes] = {
+        "",
+        "does not have 11 non-empty tab-separated mandatory fields",
+        "has a QNAME longer than 254 characters",
+        "has a FLAG that is not an integer in [0, 65535]",
+        "has an RNAME that no @SQ line names",
+        "has a POS that is not an integer in [0, 2^31 - 1]",
+        "has a MAPQ that is not an integer in [0, 255]",
+        "has a malformed CIGAR",
+        "has an RNEXT that is not '*', '=' or an @SQ name",
+        "has a PNEXT that is not an integer in [0, 2^31 - 1]",
+        "has a TLEN that is not an integer in [-(2^31 - 1), 2^31 - 1]",
+        "has a QUAL that is not '*', not as long as SEQ or not in '!'..'~'",
+        "has CIGAR and SEQ lengths that differ",
+        "has a malformed optional field",
+        "is a header line after the first alignment line",
+        "is empty",
+        "has more than 65535 CIGAR ops",
+        "gives a record of 2^31 bytes or more",
+    };
+    return code < kSamCodes ? what[code] : "?";
+}
+
+// The @SQ names on the device: packed, hashed and sorted here; *sel marks the requested RefIDs.
+int upload_sam_refs(const SamHeader &h, const std::vector<ChrInput> &chrs, SamWork *w, std::vector<uint8_t> *sel,
+                    SamRefs *refs) {
+    hipStream_t s = w->s;
+    const uint32_t n_ref = uint32_t(h.names.size());
+    std::vector<uint8_t> names;
+    sel->assign(std::max<uint32_t>(n_ref, 1), 0);
+    std::vector<uint32_t> name_off{0}, name_id(n_ref);
+    std::vector<std::pair<uint64_t, uint32_t>> hs(n_ref);
+    for (uint32_t r = 0; r < n_ref; ++r) {
+        names.insert(names.end(), h.names[r].begin(), h.names[r].end());
+        name_off.push_back(uint32_t(names.size()));
+        hs[r] = {sam_name_hash(reinterpret_cast<const uint8_t *>(h.names[r].data()), uint32_t(h.names[r].size())),
+                 r};
+    }
+    std::sort(hs.begin(), hs.end());
+    std::vector<uint64_t> name_hash(n_ref);
+    for (uint32_t r = 0; r < n_ref; ++r) name_hash[r] = hs[r].first, name_id[r] = hs[r].second;
+    for (const auto &ci : chrs)
+        if (ci.chromosome < n_ref) (*sel)[ci.chromosome] = 1;
+    SECEDO_TRY(w->names.grow(names.size(), 0, s));
+    SECEDO_TRY(w->name_off.grow(n_ref + 1, 0, s));
+    SECEDO_TRY(w->name_hash.grow(n_ref, 0, s));
+    SECEDO_TRY(w->name_id.grow(n_ref, 0, s));
+    SECEDO_TRY(w->sel.grow(sel->size(), 0, s));
+    SECEDO_TRY(w->err.grow(1, 0, s));
+    if (!names.empty()) SECEDO_TRY(hipMemcpyAsync(w->names.p, names.data(), names.size(), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(w->name_off.p, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice, s));
+    if (n_ref) {
+        SECEDO_TRY(hipMemcpyAsync(w->name_hash.p, name_hash.data(), n_ref * 8ull, hipMemcpyHostToDevice, s));
+        SECEDO_TRY(hipMemcpyAsync(w->name_id.p, name_id.data(), n_ref * 4ull, hipMemcpyHostToDevice, s));
+    }
+    SECEDO_TRY(hipMemcpyAsync(w->sel.p, sel->data(), sel->size(), hipMemcpyHostToDevice, s));
+    *refs = SamRefs{w->names.p, w->name_off.p, w->name_hash.p, w->name_id.p, w->sel.p, n_ref};
+    return SECEDO_OK;
+}
+
+// one range of SAM lines as the device parse sees it and leaves it
+struct SamRange {
+    uint64_t len = 0;        // bytes of text, uploaded to w->text and zero-padded to n16 + 1 vectors of 16
+    uint64_t n16 = 0;
+    uint64_t line_base = 0;  // lines of the body before the range
+    bool ends_file = false, trailing = false;  // the range ends the file; its last byte is '\n'
+    // out: the lines, those below the first bad one (parsed into w->h_ref / h_pos / h_out), the lowest error
+    uint32_t n_lines = 0, limit = 0;
+    unsigned long long err = ~0ull;
+};
+
+// The device parse of one uploaded range: line starts, the size of each line's record, the records themselves; RefID
+// and Position of each line and the records of the selected chromosomes come back to the host.
+int parse_sam_range(SamWork *w, const SamRefs &refs, SamRange *r) {
+    hipStream_t s = w->s;
+    const uint64_t n16 = r->n16;
+    SECEDO_TRY(w->cnt.grow(n16 + 1, 0, s));
+    SECEDO_TRY(w->scan.grow(n16 + 1, 0, s));
+    size_t tb = scan_bytes(n16 + 1);
+    SECEDO_TRY(w->tmp.grow(tb, 0, s));
+    SECEDO_TRY(sam_newline_count(w->text.p, n16, w->cnt.p, s));
+    SECEDO_TRY(hipMemsetAsync(w->cnt.p + n16, 0, 4, s));
+    SECEDO_TRY(exclusive_sum(w->tmp.p, tb, w->cnt.p, w->scan.p, n16 + 1, s));
+    uint32_t n_nl = 0;
+    SECEDO_TRY(hipMemcpyAsync(&n_nl, w->scan.p + n16, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    const uint32_t n_lines = n_nl + (r->trailing ? 0 : 1);
+    SECEDO_TRY(w->start.grow(uint64_t(n_lines) + 1, 0, s));
+    SECEDO_TRY(w->size.grow(uint64_t(n_lines) + 1, 0, s));
+    SECEDO_TRY(w->off.grow(uint64_t(n_lines) + 1, 0, s));
+    SECEDO_TRY(w->ref.grow(n_lines, 0, s));
+    SECEDO_TRY(w->pos.grow(n_lines, 0, s));
+    SECEDO_TRY(sam_line_starts(w->text.p, n16, w->scan.p, n_lines, uint32_t(r->len), !r->trailing, w->start.p, s));
+    SECEDO_TRY(hipMemsetAsync(w->err.p, 0xFF, 8, s));
+    SECEDO_TRY(sam_size(w->text.p, w->start.p, n_lines, r->line_base, r->ends_file, refs, w->size.p, w->ref.p,
+                        w->pos.p, w->err.p, s));
+    SECEDO_TRY(hipMemsetAsync(w->size.p + n_lines, 0, 8, s));
+    tb = scan_bytes(uint64_t(n_lines) + 1);
+    SECEDO_TRY(w->tmp.grow(tb, 0, s));
+    SECEDO_TRY(exclusive_sum64(w->tmp.p, tb, w->size.p, w->off.p, uint64_t(n_lines) + 1, s));
+    uint64_t total = 0;
+    unsigned long long err = 0;
+    SECEDO_TRY(hipMemcpyAsync(&total, w->off.p + n_lines, 8, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(&err, w->err.p, 8, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    // lines below the first bad one are encoded and walked: a structural error there comes first
+    const uint32_t limit = err == ~0ull ? n_lines : uint32_t((err >> 8) - r->line_base);
+    SECEDO_TRY(w->out.grow(total, 0, s));
+    SECEDO_TRY(sam_encode(w->text.p, w->start.p, limit, refs, w->off.p, w->out.p, s));
+    w->h_ref.resize(limit);
+    w->h_pos.resize(limit);
+    w->h_out.resize(total);
+    if (limit) {
+        SECEDO_TRY(hipMemcpyAsync(w->h_ref.data(), w->ref.p, limit * 4ull, hipMemcpyDeviceToHost, s));
+        SECEDO_TRY(hipMemcpyAsync(w->h_pos.data(), w->pos.p, limit * 4ull, hipMemcpyDeviceToHost, s));
+    }
+    if (total) SECEDO_TRY(hipMemcpyAsync(w->h_out.data(), w->out.p, total, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    r->n_lines = n_lines;
+    r->limit = limit;
+    r->err = err;
+    return SECEDO_OK;
+}
+
+// The host pass over a parsed range: sortedness over every line, the selected records into the runs, then the
+// range's parse error if it has one.
+int collect_sam_range(const SamWork &w, const SamRange &r, const std::vector<uint8_t> &sel, SortCheck *order,
+                      FileSink *sink) {
+    const std::string &path = sink->in.paths[sink->f];
+    const uint64_t line0 = sink->in.line0[sink->f];
+    uint64_t o = 0;
+    for (uint32_t k = 0; k < r.limit; ++k) {
+        const int32_t ref = w.h_ref[k], pos = w.h_pos[k];
+        if (ref == kSamNoRecord) continue;
+        const uint64_t idx = r.line_base + k;
+        if (!order->check(ref, pos))
+            return fail(SECEDO_E_INVALID_ARG,
+                        record_where(path, sink->f, line0, idx) + ": input is not coordinate-sorted");
+        if (ref >= 0 && size_t(ref) < sel.size() && sel[ref]) {
+            const uint8_t *rec = w.h_out.data() + o;
+            SECEDO_CALL((*sink)(idx, rec, ref, pos));
+            o += 4 + uint64_t(rd32(rec));
+        }
+    }
+    if (r.err != ~0ull) {
+        const uint32_t code = uint32_t(r.err & 0xFF);
+        return fail(code == kSamManyOps || code == kSamTooLong ? SECEDO_E_LIMIT : SECEDO_E_INVALID_ARG,
+                    record_where(path, sink->f, line0, r.err >> 8) + " " + sam_what(code));
+    }
+    return SECEDO_OK;
+}
+
+// One SAM file: header on the host, then ranges of about `batch` bytes ending at a '\n', each uploaded, parsed on the
+// device, and its records of the requested chromosomes downloaded into the file's runs (FileSink, as a BAM's walk).
+int load_sam_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs, secedo_bam_times *t) {
+    const std::string &path = in->paths[f];
+    Clock::time_point t0 = Clock::now();
+    Mapped m;
+    SECEDO_CALL(map_file(path, &m));
+    SamHeader h;
+    SECEDO_CALL(parse_sam_header(path, f, m, &h));
+    in->line0[f] = h.lines + 1;
+    if (t) t->inflate_ms += ms_since(t0);
+    t0 = Clock::now();
+    if (!w->s) SECEDO_TRY(hipStreamCreateWithFlags(&w->s, hipStreamNonBlocking));
+    hipStream_t s = w->s;
+    std::vector<uint8_t> sel;
+    SamRefs refs{};
+    SECEDO_CALL(upload_sam_refs(h, in->chrs, w, &sel, &refs));
+    if (t) t->upload_ms += ms_since(t0);
+
+    FileSink sink(*in, f, *runs);
+    SortCheck order;
+    SamRange r;
+    for (uint64_t r0 = h.body; r0 < m.n;) {
+        uint64_t r1 = std::min<uint64_t>(m.n, r0 + std::max<uint64_t>(batch, 1));
+        if (r1 < m.n) {
+            const uint8_t *nl = static_cast<const uint8_t *>(std::memchr(m.p + r1 - 1, '\n', m.n - (r1 - 1)));
+            r1 = nl ? uint64_t(nl - m.p) + 1 : m.n;
+        }
+        r.len = r1 - r0;
+        if (r.len >= (1ull << 32) - 64)
+            return fail(SECEDO_E_LIMIT, "file " + std::to_string(f) + " (" + path +
+                                            "): a range of SAM lines of 4 GiB or more (a line that long)");
+        r.ends_file = r1 == m.n;
+        r.trailing = m.p[r1 - 1] == '\n';
+        // text read
+        t0 = Clock::now();
+        w->h_text.assign(m.p + r0, m.p + r1);
+        if (t) {
+            t->inflate_ms += ms_since(t0);
+            t->inflated_bytes += double(r.len);
+        }
+        // upload, zero-padded to whole 16-byte vectors plus one
+        t0 = Clock::now();
+        r.n16 = (r.len + 15) / 16;
+        const uint64_t padded = r.n16 * 16 + 16;
+        SECEDO_TRY(w->text.grow(padded, 0, s));
+        SECEDO_TRY(hipMemcpyAsync(w->text.p, w->h_text.data(), r.len, hipMemcpyHostToDevice, s));
+        SECEDO_TRY(hipMemsetAsync(w->text.p + r.len, 0, padded - r.len, s));
+        SECEDO_TRY(hipStreamSynchronize(s));
+        if (t) t->upload_ms += ms_since(t0);
+        // device parse, then the host pass
+        t0 = Clock::now();
+        SECEDO_CALL(parse_sam_range(w, refs, &r));
+        SECEDO_CALL(collect_sam_range(*w, r, sel, &order, &sink));
+        if (t) t->walk_ms += ms_since(t0);
+        r.line_base += r.n_lines;
+        r0 = r1;
+    }
+    return SECEDO_OK;
+}
+
+}  // namespace
+
+namespace secedo {
+namespace bam_host {
+
+std::string record_where(const std::string &path, size_t f, uint64_t line0, uint64_t idx, Stage stage) {
+    if (line0) return "file " + std::to_string(f) + " (" + path + "), line " + std::to_string(line0 + idx);
+    if (stage == Stage::kLoad) return path + ": record " + std::to_string(idx);
+    return "file " + std::to_string(f) + ", record " + std::to_string(idx);
+}
+
+int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosome_ids, uint32_t n_chr,
+                uint32_t threads, Inputs *in, secedo_bam_times *t) {
+    const size_t n_files = files.size();
+    const uint64_t batch = batch_bytes();
+    in->paths = files;
+    in->line0.assign(n_files, 0);
+    in->chrs.resize(n_chr);
+    for (uint32_t c = 0; c < n_chr; ++c) {
+        ChrInput &ci = in->chrs[c];
+        ci.chromosome = chromosome_ids[c];
+        ci.file_base.assign(n_files, 0);
+        ci.roff.assign(n_files, {});
+        ci.rpos.assign(n_files, {});
+        ci.ridx.assign(n_files, {});
+    }
+    std::vector<char> sam(n_files, 0);
+    for (size_t f = 0; f < n_files; ++f) {
+        bool is_sam = false;
+        SECEDO_CALL(sniff(files[f], &is_sam));
+        sam[f] = is_sam;
+    }
+    SamWork sam_work;
+    Runs runs(n_chr, std::vector<std::vector<uint8_t>>(n_files));
+    size_t f0 = 0;
+    while (f0 < n_files) {
+        if (sam[f0]) {  // SAM text: parsed on the device in ranges of about `batch` bytes
+            SECEDO_CALL(load_sam_file(f0, batch, &sam_work, in, &runs, t));
+            ++f0;
+            continue;
+        }
+        // a batch of BAM files of at most `batch` bytes on disk (BGZF inflates 3-4x), at least one file
+        size_t f1 = f0;
+        uint64_t disk = 0;
+        while (f1 < n_files && !sam[f1] && (f1 == f0 || disk < batch / 4)) {
+            struct stat st;
+            disk += stat(files[f1].c_str(), &st) == 0 ? uint64_t(st.st_size) : 0;
+            ++f1;
+        }
+        if (f1 == f0 + 1) {  // one file: walked in block ranges (one range when it inflates to at most `batch`)
+            SECEDO_CALL(load_file_ranges(f0, threads, batch, in, &runs, t));
+            f0 = f1;
+            continue;
+        }
+        std::vector<Inflated> inf;
+        Clock::time_point t0 = Clock::now();
+        SECEDO_CALL(inflate_files(std::vector<std::string>(files.begin() + f0, files.begin() + f1), threads, &inf));
+        if (t) {
+            t->inflate_ms += ms_since(t0);
+            for (auto &x : inf) t->inflated_bytes += double(x.data.size());
+        }
+        t0 = Clock::now();
+        // g_error is per thread: each worker's message comes back to this one
+        std::vector<int> rcs(inf.size(), SECEDO_OK);
+        std::vector<std::string> errs(inf.size());
+        parallel_for(threads, inf.size(), [&](uint64_t k) {
+            WalkState st;
+            FileSink sink(*in, f0 + k, runs);
+            uint64_t used = 0;
+            rcs[k] = walk_range(files[f0 + k], inf[k].data.data(), inf[k].data.size(), true, &st, &used, sink);
+            errs[k] = g_error;
+            std::vector<uint8_t>().swap(inf[k].data);
+        });
+        for (size_t k = 0; k < inf.size(); ++k)
+            if (rcs[k] != SECEDO_OK) return fail(rcs[k], errs[k]);
+        if (t) t->walk_ms += ms_since(t0);
+        f0 = f1;
+    }
+    const Clock::time_point t0 = Clock::now();
+    for (size_t c = 0; c < in->chrs.size(); ++c) {
+        ChrInput &ci = in->chrs[c];
+        uint64_t total = 0;
+        for (size_t f = 0; f < n_files; ++f) total += runs[c][f].size();
+        ci.bytes.reserve(total);
+        for (size_t f = 0; f < n_files; ++f) {
+            ci.file_base[f] = ci.bytes.size();
+            ci.bytes.insert(ci.bytes.end(), runs[c][f].begin(), runs[c][f].end());
+            std::vector<uint8_t>().swap(runs[c][f]);
+        }
+    }
+    if (t) t->walk_ms += ms_since(t0);
+    return SECEDO_OK;
+}
+
+}  // namespace bam_host
+}  // namespace secedo
+
+extern "C" int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_bam_scan_info *info,
+                               uint64_t *records_per_ref, uint32_t capacity) {
+    if (!path || !info) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    std::vector<Inflated> inf;
+    SECEDO_CALL(inflate_files({std::string(path)}, num_threads ? num_threads : 1, &inf));
+    const std::vector<uint8_t> &d = inf[0].data;
+    WalkState st;
+    st.require_sorted = false;  // counted to the end either way; st.sorted says which it was
+    SECEDO_CALL(parse_header(inf[0].path, d.data(), d.size(), true, &st.h));
+    st.have_header = true;
+    const Header &h = st.h;
+    std::vector<uint64_t> per(h.n_ref, 0);
+    uint64_t unmapped = 0, used = 0;
+    const auto count = [&](uint64_t, const uint8_t *, int32_t ref, int32_t) {
+        if (ref < 0) ++unmapped;
+        else if (uint32_t(ref) < h.n_ref) ++per[ref];
+        return SECEDO_OK;
+    };
+    SECEDO_CALL(walk_range(inf[0].path, d.data() + h.first_record, d.size() - h.first_record, true, &st, &used, count));
+    info->n_ref = h.n_ref;
+    info->sorted = st.sorted ? 1 : 0;
+    info->n_records = st.idx;
+    info->n_unmapped = unmapped;
+    info->n_blocks = inf[0].n_blocks;
+    info->inflated_bytes = d.size();
+    info->l_text = h.l_text;
+    info->reserved = 0;
+    if (records_per_ref)
+        for (uint32_t r = 0; r < std::min(capacity, h.n_ref); ++r) records_per_ref[r] = per[r];
+    return SECEDO_OK;
+}

@@ -25,6 +25,7 @@ enum Err : uint32_t {
     kErrDeletion = 4,     // a D op over a character other than '-' (:134)
     kErrQuality = 5,      // the quality index i + offset - del_offset is past the quality string (:137)
     kErrPosition = 6,     // negative Position
+    kErrCodes
 };
 
 struct Params {

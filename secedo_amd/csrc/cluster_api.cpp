@@ -13,11 +13,11 @@
 #include "secedo_simmat.h"
 #include "secedo_spectral.h"
 #include "cluster_kernels.hpp"
+#include "host_util.hpp"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -30,26 +30,12 @@ namespace {
 using secedo::cluster::Decision;
 using secedo::cluster::kNoPos;
 using secedo::cluster::ModelResult;
-
-thread_local std::string g_error;
+using namespace secedo::host;
 
 // Host threads secedo_simmat_prepare may use when a level's pileup needs the host packing path (a read split at
 // a flush; the device path ignores it). The reference's num_threads has no counterpart in this C-ABI, which
 // takes no thread count: a fixed, moderate width.
 constexpr uint32_t kPrepareThreads = 8;
-
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point &t0) {
-    const Clock::time_point t1 = Clock::now();
-    const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-    return ms;
-}
-
-int fail(int code, const std::string &msg) {
-    g_error = msg;
-    return code;
-}
 
 // a wrapped libsecedo_simmat call failed: forward its message
 int forward(int code, const char *what) {
@@ -57,44 +43,18 @@ int forward(int code, const char *what) {
     return fail(code, std::string(what) + ": " + (m ? m : ""));
 }
 
-#define CL_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(SECEDO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 #define CL_CALL(expr)                                  \
     do {                                               \
         int rc_ = (expr);                              \
         if (rc_ != SECEDO_OK) return forward(rc_, #expr); \
     } while (0)
 
-struct Buf {
-    void *p = nullptr;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-    hipError_t alloc(size_t bytes) {
-        release();
-        return hipMalloc(&p, std::max<size_t>(bytes, 8));
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    template <typename T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-
 int check_device(int device_id) {
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the clustering step has no CPU fallback");
     if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_NO_DEVICE, "device id out of range");
-    CL_TRY(hipSetDevice(device_id));
+    SECEDO_TRY(hipSetDevice(device_id));
     return SECEDO_OK;
 }
 
@@ -126,20 +86,20 @@ int decide(const double *d_ev, uint32_t n, uint32_t k, int type, int termination
     std::memset(&dec, 0, sizeof(dec));
     dec.n_vectors = k;
     if (k < 2) {  // "Perfect decomposition, all cells in same cluster" (:160-163)
-        if (n) CL_TRY(hipMemsetAsync(d_cluster, 0, (size_t)n * sizeof(double), stream));
-        CL_TRY(hipStreamSynchronize(stream));
+        if (n) SECEDO_TRY(hipMemsetAsync(d_cluster, 0, (size_t)n * sizeof(double), stream));
+        SECEDO_TRY(hipStreamSynchronize(stream));
         dec.num_clusters = 1;
         if (num_clusters) *num_clusters = 1;
         if (out) *out = dec;
         return SECEDO_OK;
     }
     Buf scratch, d_dec;
-    CL_TRY(scratch.alloc(secedo::cluster::decide_scratch_bytes(n)));
-    CL_TRY(d_dec.alloc(sizeof(Decision)));
-    CL_TRY(secedo::cluster::decide(d_ev, n, k, type, termination, d_cluster, d_dec.as<Decision>(), scratch.p, stream));
+    SECEDO_TRY(scratch.alloc(secedo::cluster::decide_scratch_bytes(n)));
+    SECEDO_TRY(d_dec.alloc(sizeof(Decision)));
+    SECEDO_TRY(secedo::cluster::decide(d_ev, n, k, type, termination, d_cluster, d_dec.as<Decision>(), scratch.p, stream));
     Decision h;
-    CL_TRY(hipMemcpyAsync(&h, d_dec.p, sizeof(Decision), hipMemcpyDeviceToHost, stream));
-    CL_TRY(hipStreamSynchronize(stream));
+    SECEDO_TRY(hipMemcpyAsync(&h, d_dec.p, sizeof(Decision), hipMemcpyDeviceToHost, stream));
+    SECEDO_TRY(hipStreamSynchronize(stream));
     for (uint32_t i = 0; i < SECEDO_CLUSTER_MAX; ++i) {
         copy_model(h.kmeans[i], &dec.kmeans[i]);
         copy_model(h.gmm[i], &dec.gmm[i]);
@@ -205,8 +165,8 @@ int write_vec(const std::string &path, const std::vector<uint16_t> &v) {
 template <class T>
 int download(std::vector<T> *out, const void *d, size_t n, hipStream_t s) {
     out->resize(n);
-    if (n) CL_TRY(hipMemcpyAsync(out->data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    CL_TRY(hipStreamSynchronize(s));
+    if (n) SECEDO_TRY(hipMemcpyAsync(out->data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
     return SECEDO_OK;
 }
 
@@ -294,18 +254,18 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
     // Filter filter(seq_error_rate): cell_proportion is the default 4 whatever the caller passed (:336)
     Buf f_chr, f_pos, f_off, f_rid, f_idb;
     const uint64_t L = P.n_loci, E = P.n_entries;
-    CL_TRY(f_chr.alloc((size_t)(P.n_chr + 1) * 4));
-    CL_TRY(f_pos.alloc((size_t)std::max<uint64_t>(L, 1) * 4));
-    CL_TRY(f_off.alloc((size_t)(L + 1) * 8));
-    CL_TRY(f_rid.alloc((size_t)std::max<uint64_t>(E, 1) * 4));
-    CL_TRY(f_idb.alloc((size_t)std::max<uint64_t>(E, 1) * (P.d_b16 ? 2 : 4)));
+    SECEDO_TRY(f_chr.alloc((size_t)(P.n_chr + 1) * 4));
+    SECEDO_TRY(f_pos.alloc((size_t)std::max<uint64_t>(L, 1) * 4));
+    SECEDO_TRY(f_off.alloc((size_t)(L + 1) * 8));
+    SECEDO_TRY(f_rid.alloc((size_t)std::max<uint64_t>(E, 1) * 4));
+    SECEDO_TRY(f_idb.alloc((size_t)std::max<uint64_t>(E, 1) * (P.d_b16 ? 2 : 4)));
     uint64_t kept_loci = 0, kept_entries = 0;
     double coverage = 0;
     CL_CALL(secedo_filter_device(P.d_chr, P.n_chr, P.d_pos, P.d_off, P.d_rid, P.d_b16, P.d_b32, d_i2p, P.n_groups,
                                  P.n_loci, P.n_entries, P.seq_error_rate, 4, f_chr.as<uint32_t>(), f_pos.as<uint32_t>(),
                                  f_off.as<uint64_t>(), f_rid.as<uint32_t>(), f_idb.p, &kept_loci, &kept_entries,
                                  &coverage, P.stream));
-    rec.step_ms[0] = ms_since(t0);  // secedo_filter_device synchronises the stream
+    rec.step_ms[0] = ms_lap(t0);  // secedo_filter_device synchronises the stream
     rec.kept_loci = kept_loci;
     rec.coverage = coverage;
     if (P.write) {
@@ -319,7 +279,7 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
 
     // computeSimilarityMatrix on the filtered pileup, n_sub cells
     Buf sim, ev, d_cluster;
-    CL_TRY(sim.alloc((size_t)n_sub * n_sub * 8));
+    SECEDO_TRY(sim.alloc((size_t)n_sub * n_sub * 8));
     {
         const uint16_t *b16 = P.d_b16 ? f_idb.as<uint16_t>() : nullptr;
         const uint32_t *b32 = P.d_b16 ? nullptr : f_idb.as<uint32_t>();
@@ -328,36 +288,36 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
                                                 (uint32_t)kept_loci, kept_entries));
         CL_CALL(secedo_simmat_prepare(P.handle, n_sub, P.max_read_length, kPrepareThreads, 0, P.stream));
         Buf acc;
-        CL_TRY(acc.alloc((size_t)secedo_simmat_acc_elems(P.handle) * 8));
+        SECEDO_TRY(acc.alloc((size_t)secedo_simmat_acc_elems(P.handle) * 8));
         CL_CALL(secedo_simmat_assign_finalize(P.handle, P.mutation_rate, P.homozygous_rate, P.seq_error_rate,
                                               P.normalization, acc.as<int64_t>(), sim.as<double>(), P.stream));
-        CL_TRY(hipStreamSynchronize(P.stream));
-        rec.step_ms[1] = ms_since(t0);
+        SECEDO_TRY(hipStreamSynchronize(P.stream));
+        rec.step_ms[1] = ms_lap(t0);
     }
     // laplacian + eig_sym: the 20 smallest eigenvalues, the eigenvectors of the 7 smallest
     const uint32_t n_values = std::min<uint32_t>(SECEDO_CLUSTER_EIGENVALUES, n_sub);
     const uint32_t k = std::min<uint32_t>(7, n_sub);
-    CL_TRY(ev.alloc((size_t)n_sub * std::max<uint32_t>(k, 1) * 8));
-    CL_TRY(d_cluster.alloc((size_t)std::max<uint32_t>(n_sub, 1) * 8));
+    SECEDO_TRY(ev.alloc((size_t)n_sub * std::max<uint32_t>(k, 1) * 8));
+    SECEDO_TRY(d_cluster.alloc((size_t)std::max<uint32_t>(n_sub, 1) * 8));
     if (n_sub > 0) {
         secedo_spectral_info info;
         CL_CALL(secedo_spectral_eigs_device(P.device_id, sim.as<double>(), n_sub, n_values, k, 0, 0, rec.eigenvalues,
                                             ev.as<double>(), &info, P.stream));
         rec.n_eigenvalues = n_values;
     }
-    rec.step_ms[2] = ms_since(t0);
+    rec.step_ms[2] = ms_lap(t0);
     if (P.write && n_sub > 0) {
         if (int rc = write_eigenvalues(P, marker, rec.eigenvalues, n_values)) return rc;
         if (P.type != SECEDO_CLUSTER_FIEDLER && k >= 2)
             if (int rc = write_eigenvectors(P, marker, ev.as<double>(), n_sub, k)) return rc;
         t0 = Clock::now();
     }
-    sim.release();
+    sim.reset();
     uint32_t num_clusters = 1;
     CL_CALL(decide(ev.as<double>(), n_sub, k, P.type, P.termination, d_cluster.as<double>(), &num_clusters,
                    &rec.decision, P.stream));
-    rec.step_ms[3] = ms_since(t0);  // decide() synchronises the stream
-    ev.release();
+    rec.step_ms[3] = ms_lap(t0);  // decide() synchronises the stream
+    ev.reset();
     rec.num_clusters = num_clusters;
     if (num_clusters == 1) {
         rec.stop_reason = SECEDO_STOP_ONE_CLUSTER;
@@ -384,37 +344,37 @@ int level(Params &P, const uint32_t *d_i2p, const uint32_t *d_p2i, uint32_t n_su
             rec.em_iterations = iters;
         }
     }
-    CL_TRY(hipStreamSynchronize(P.stream));
-    rec.step_ms[4] = ms_since(t0);
+    SECEDO_TRY(hipStreamSynchronize(P.stream));
+    rec.step_ms[4] = ms_lap(t0);
     if (P.write && rec.em_state == SECEDO_EM_RUN) {
         if (int rc = write_id_to_cluster(P, "expectation_maximization" + marker, d_i2p, d_cluster.as<double>(), n_sub))
             return rc;
         t0 = Clock::now();
     }
-    f_chr.release();
-    f_pos.release();
-    f_off.release();
-    f_rid.release();
-    f_idb.release();
+    f_chr.reset();
+    f_pos.reset();
+    f_off.reset();
+    f_rid.reset();
+    f_idb.reset();
 
     // partition (:379-416) and the labels of the cells
     Buf c_i2p, c_p2i, c_info;
-    CL_TRY(c_i2p.alloc((size_t)num_clusters * P.n_groups * 4));
-    CL_TRY(c_p2i.alloc((size_t)num_clusters * std::max<uint32_t>(n_sub, 1) * 4));
-    CL_TRY(c_info.alloc(2 * SECEDO_CLUSTER_MAX * 4));
-    CL_TRY(secedo::cluster::partition(d_cluster.as<double>(), n_sub, num_clusters, d_p2i, P.n_groups, c_i2p.as<uint32_t>(),
+    SECEDO_TRY(c_i2p.alloc((size_t)num_clusters * P.n_groups * 4));
+    SECEDO_TRY(c_p2i.alloc((size_t)num_clusters * std::max<uint32_t>(n_sub, 1) * 4));
+    SECEDO_TRY(c_info.alloc(2 * SECEDO_CLUSTER_MAX * 4));
+    SECEDO_TRY(secedo::cluster::partition(d_cluster.as<double>(), n_sub, num_clusters, d_p2i, P.n_groups, c_i2p.as<uint32_t>(),
                                       c_p2i.as<uint32_t>(), c_info.as<uint32_t>(), P.d_id_to_group, P.n_cells, d_i2p,
                                       *cluster_idx, P.d_clusters, P.stream));
     uint32_t info[2 * SECEDO_CLUSTER_MAX];
-    CL_TRY(hipMemcpyAsync(info, c_info.p, sizeof(info), hipMemcpyDeviceToHost, P.stream));
-    CL_TRY(hipStreamSynchronize(P.stream));
-    rec.step_ms[5] = ms_since(t0);
+    SECEDO_TRY(hipMemcpyAsync(info, c_info.p, sizeof(info), hipMemcpyDeviceToHost, P.stream));
+    SECEDO_TRY(hipStreamSynchronize(P.stream));
+    rec.step_ms[5] = ms_lap(t0);
     if (P.write) {
         std::vector<uint16_t> cells;
         if (int rc = download(&cells, P.d_clusters, P.n_cells, P.stream)) return rc;
         if (int rc = write_vec(in_dir(P.out_dir, "clustering"), cells)) return rc;
     }
-    d_cluster.release();
+    d_cluster.reset();
     *cluster_idx = (uint16_t)(*cluster_idx + num_clusters);
     rec.stop_reason = SECEDO_STOP_SPLIT;
     for (uint32_t c = 0; c < num_clusters; ++c) {
@@ -471,20 +431,20 @@ int secedo_spectral_clustering(int device_id, const double *similarity, uint32_t
     if (int rc = check_device(device_id)) return rc;
     const uint32_t n_values = std::min<uint32_t>(SECEDO_CLUSTER_EIGENVALUES, n), k = std::min<uint32_t>(7, n);
     Buf a, ev, c;
-    CL_TRY(a.alloc((size_t)n * n * 8));
-    CL_TRY(ev.alloc((size_t)n * k * 8));
-    CL_TRY(c.alloc((size_t)n * 8));
-    CL_TRY(hipMemcpy(a.p, similarity, (size_t)n * n * 8, hipMemcpyHostToDevice));
+    SECEDO_TRY(a.alloc((size_t)n * n * 8));
+    SECEDO_TRY(ev.alloc((size_t)n * k * 8));
+    SECEDO_TRY(c.alloc((size_t)n * 8));
+    SECEDO_TRY(hipMemcpy(a.p, similarity, (size_t)n * n * 8, hipMemcpyHostToDevice));
     double vals[SECEDO_CLUSTER_EIGENVALUES];
     secedo_spectral_info info;
     CL_CALL(secedo_spectral_eigs_device(device_id, a.as<double>(), n, n_values, k, 0, 0, vals, ev.as<double>(), &info,
                                         nullptr));
     if (eigenvalues) std::memcpy(eigenvalues, vals, n_values * sizeof(double));
-    a.release();
+    a.reset();
     if (int rc = decide(ev.as<double>(), n, k, clustering_type, termination, c.as<double>(), num_clusters, decision,
                         nullptr))
         return rc;
-    CL_TRY(hipMemcpy(cluster, c.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    SECEDO_TRY(hipMemcpy(cluster, c.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return SECEDO_OK;
 }
 
@@ -497,11 +457,11 @@ int secedo_cluster_kmeans_device(int device_id, const double *d_points, uint32_t
     if (int rc = check_device(device_id)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     Buf r;
-    CL_TRY(r.alloc(sizeof(ModelResult)));
-    CL_TRY(secedo::cluster::kmeans(d_points, n, dims, K, max_iter, d_labels, r.as<ModelResult>(), s));
+    SECEDO_TRY(r.alloc(sizeof(ModelResult)));
+    SECEDO_TRY(secedo::cluster::kmeans(d_points, n, dims, K, max_iter, d_labels, r.as<ModelResult>(), s));
     ModelResult h;
-    CL_TRY(hipMemcpyAsync(&h, r.p, sizeof(h), hipMemcpyDeviceToHost, s));
-    CL_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(hipMemcpyAsync(&h, r.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
     copy_model(h, model);
     return SECEDO_OK;
 }
@@ -515,11 +475,11 @@ int secedo_cluster_gmm_device(int device_id, const double *d_points, uint32_t n,
     if (int rc = check_device(device_id)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     Buf r;
-    CL_TRY(r.alloc(sizeof(ModelResult)));
-    CL_TRY(secedo::cluster::gmm(d_points, n, dims, K, r.as<ModelResult>(), s));
+    SECEDO_TRY(r.alloc(sizeof(ModelResult)));
+    SECEDO_TRY(secedo::cluster::gmm(d_points, n, dims, K, r.as<ModelResult>(), s));
     ModelResult h;
-    CL_TRY(hipMemcpyAsync(&h, r.p, sizeof(h), hipMemcpyDeviceToHost, s));
-    CL_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(hipMemcpyAsync(&h, r.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
     copy_model(h, model);
     return SECEDO_OK;
 }
@@ -597,14 +557,14 @@ static int divide_device(int device_id, const uint32_t *d_chr_locus_off, uint32_
     P.id_to_group = id_to_group;
 
     Buf d_g, d_i2p, d_p2i, d_cl;
-    CL_TRY(d_g.alloc((size_t)n_cells * 2));
-    CL_TRY(d_i2p.alloc((size_t)n_groups * 4));
-    CL_TRY(d_p2i.alloc((size_t)n_pos * 4));
-    CL_TRY(d_cl.alloc((size_t)n_cells * 2));
-    CL_TRY(hipMemcpyAsync(d_g.p, id_to_group, (size_t)n_cells * 2, hipMemcpyHostToDevice, P.stream));
-    CL_TRY(hipMemcpyAsync(d_i2p.p, id_to_pos, (size_t)n_groups * 4, hipMemcpyHostToDevice, P.stream));
-    CL_TRY(hipMemcpyAsync(d_p2i.p, pos_to_id, (size_t)n_pos * 4, hipMemcpyHostToDevice, P.stream));
-    CL_TRY(hipMemcpyAsync(d_cl.p, clusters, (size_t)n_cells * 2, hipMemcpyHostToDevice, P.stream));
+    SECEDO_TRY(d_g.alloc((size_t)n_cells * 2));
+    SECEDO_TRY(d_i2p.alloc((size_t)n_groups * 4));
+    SECEDO_TRY(d_p2i.alloc((size_t)n_pos * 4));
+    SECEDO_TRY(d_cl.alloc((size_t)n_cells * 2));
+    SECEDO_TRY(hipMemcpyAsync(d_g.p, id_to_group, (size_t)n_cells * 2, hipMemcpyHostToDevice, P.stream));
+    SECEDO_TRY(hipMemcpyAsync(d_i2p.p, id_to_pos, (size_t)n_groups * 4, hipMemcpyHostToDevice, P.stream));
+    SECEDO_TRY(hipMemcpyAsync(d_p2i.p, pos_to_id, (size_t)n_pos * 4, hipMemcpyHostToDevice, P.stream));
+    SECEDO_TRY(hipMemcpyAsync(d_cl.p, clusters, (size_t)n_cells * 2, hipMemcpyHostToDevice, P.stream));
     P.d_id_to_group = d_g.as<uint16_t>();
     P.d_clusters = d_cl.as<uint16_t>();
 
@@ -616,8 +576,8 @@ static int divide_device(int device_id, const uint32_t *d_chr_locus_off, uint32_
     secedo_simmat_destroy(h);
     *n_records = P.n_records;
     if (rc) return rc;
-    CL_TRY(hipMemcpyAsync(clusters, d_cl.p, (size_t)n_cells * 2, hipMemcpyDeviceToHost, P.stream));
-    CL_TRY(hipStreamSynchronize(P.stream));
+    SECEDO_TRY(hipMemcpyAsync(clusters, d_cl.p, (size_t)n_cells * 2, hipMemcpyDeviceToHost, P.stream));
+    SECEDO_TRY(hipStreamSynchronize(P.stream));
     *cluster_idx = idx;
     if (P.n_records > capacity)
         return fail(SECEDO_E_LIMIT, "more levels (" + std::to_string(P.n_records) + ") than record capacity");
@@ -649,18 +609,18 @@ static int divide_host(int device_id, const uint32_t *chr_locus_off, uint32_t n_
     const uint32_t L = chr_locus_off[n_chr];
     const uint64_t E = locus_entry_off[L];
     Buf chr, pos, off, rid, idb;
-    CL_TRY(chr.alloc((size_t)(n_chr + 1) * 4));
-    CL_TRY(pos.alloc((size_t)std::max<uint32_t>(L, 1) * 4));
-    CL_TRY(off.alloc((size_t)(L + 1) * 8));
-    CL_TRY(rid.alloc((size_t)std::max<uint64_t>(E, 1) * 4));
-    CL_TRY(idb.alloc((size_t)std::max<uint64_t>(E, 1) * (id_base16 ? 2 : 4)));
-    CL_TRY(hipMemcpy(chr.p, chr_locus_off, (size_t)(n_chr + 1) * 4, hipMemcpyHostToDevice));
-    if (L) CL_TRY(hipMemcpy(pos.p, locus_pos, (size_t)L * 4, hipMemcpyHostToDevice));
-    CL_TRY(hipMemcpy(off.p, locus_entry_off, (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
+    SECEDO_TRY(chr.alloc((size_t)(n_chr + 1) * 4));
+    SECEDO_TRY(pos.alloc((size_t)std::max<uint32_t>(L, 1) * 4));
+    SECEDO_TRY(off.alloc((size_t)(L + 1) * 8));
+    SECEDO_TRY(rid.alloc((size_t)std::max<uint64_t>(E, 1) * 4));
+    SECEDO_TRY(idb.alloc((size_t)std::max<uint64_t>(E, 1) * (id_base16 ? 2 : 4)));
+    SECEDO_TRY(hipMemcpy(chr.p, chr_locus_off, (size_t)(n_chr + 1) * 4, hipMemcpyHostToDevice));
+    if (L) SECEDO_TRY(hipMemcpy(pos.p, locus_pos, (size_t)L * 4, hipMemcpyHostToDevice));
+    SECEDO_TRY(hipMemcpy(off.p, locus_entry_off, (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
     if (E) {
-        CL_TRY(hipMemcpy(rid.p, read_ids, (size_t)E * 4, hipMemcpyHostToDevice));
-        if (id_base16) CL_TRY(hipMemcpy(idb.p, id_base16, (size_t)E * 2, hipMemcpyHostToDevice));
-        else CL_TRY(hipMemcpy(idb.p, id_base32, (size_t)E * 4, hipMemcpyHostToDevice));
+        SECEDO_TRY(hipMemcpy(rid.p, read_ids, (size_t)E * 4, hipMemcpyHostToDevice));
+        if (id_base16) SECEDO_TRY(hipMemcpy(idb.p, id_base16, (size_t)E * 2, hipMemcpyHostToDevice));
+        else SECEDO_TRY(hipMemcpy(idb.p, id_base32, (size_t)E * 4, hipMemcpyHostToDevice));
     }
     return divide_device(device_id, chr.as<uint32_t>(), n_chr, pos.as<uint32_t>(), off.as<uint64_t>(),
                          rid.as<uint32_t>(), id_base16 ? idb.as<uint16_t>() : nullptr,

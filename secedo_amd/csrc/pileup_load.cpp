@@ -9,12 +9,12 @@
 // list ended the file before it, and a kept cell id past id_to_group reports the first one in file order.
 #include "secedo_pileup.h"
 #include "secedo_simmat.h"
+#include "host_util.hpp"
 #include "pileup_device.hpp"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -23,30 +23,11 @@
 namespace {
 
 using namespace secedo::pileup;
+using namespace secedo::host;
 
-thread_local std::string g_error;
-
-int fail(int code, const std::string &msg) {
-    g_error = msg;
-    return code;
-}
-
-#define PL_TRY(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(SECEDO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-#define PL_CALL(expr)                     \
-    do {                                  \
-        int rc_ = (expr);                 \
-        if (rc_ != SECEDO_OK) return rc_; \
-    } while (0)
-
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-}
+// buffers that grow chunk after chunk (the result keeps its prefix): by half, from 1024 elements
+template <class T>
+using Grown = Dev<T, 150, 1024>;
 
 constexpr uint64_t kDefaultStaging = 64ull << 20;
 constexpr uint64_t kMaxStaging = 1ull << 30;
@@ -54,53 +35,11 @@ constexpr uint64_t kMaxRecord = 6 + 6 * 65535ull;  // the longest record: covera
 
 inline uint16_t rd16(const uint8_t *p) { uint16_t v; std::memcpy(&v, p, 2); return v; }
 
-template <class T>
-struct Dev {
-    T *p = nullptr;
-    uint64_t n = 0;
-    Dev() = default;
-    Dev(const Dev &) = delete;
-    Dev &operator=(const Dev &) = delete;
-    ~Dev() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t alloc(uint64_t count) {
-        release();
-        hipError_t e = hipMalloc(&p, std::max<uint64_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        else p = nullptr;
-        return e;
-    }
-    // at least `count` elements, the first `keep` preserved (stream-ordered copy)
-    hipError_t reserve(uint64_t count, uint64_t keep, hipStream_t s) {
-        if (count <= n && p) return hipSuccess;
-        const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(count, n + n / 2), 1024);
-        T *q = nullptr;
-        hipError_t e = hipMalloc(&q, cap * sizeof(T));
-        if (e != hipSuccess) return e;
-        if (keep && p) {
-            e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) {
-                (void)hipFree(q);
-                return e;
-            }
-        }
-        release();
-        p = q;
-        n = cap;
-        return hipSuccess;
-    }
-};
-
 struct Result {
     std::vector<uint32_t> chr_locus_off{0};
-    Dev<uint32_t> pos, rid;
-    Dev<uint64_t> off;
-    Dev<uint16_t> idb;
+    Grown<uint32_t> pos, rid;
+    Grown<uint64_t> off;
+    Grown<uint16_t> idb;
     uint64_t n_loci = 0, n_entries = 0;
 };
 
@@ -189,13 +128,6 @@ struct Reader {
     }
 };
 
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-
 struct EventGuard {
     hipEvent_t e[3] = {nullptr, nullptr, nullptr};
     ~EventGuard() {
@@ -214,8 +146,9 @@ struct PinnedSmall {
 struct Ctx {
     hipStream_t s;
     hipEvent_t ev[3];
-    Dev<uint16_t> bytes;
-    Dev<uint32_t> rec, pos, cov, mval, mscan, keep, lidx, positions;
+    Grown<uint16_t> bytes;
+    Grown<uint32_t> positions;
+    Dev<uint32_t> rec, pos, cov, mval, mscan, keep, lidx;
     Dev<uint64_t> cnt, eoff;
     Dev<uint8_t> tmp;
     uint64_t scratch_n = 0;
@@ -256,15 +189,15 @@ int load_file(Ctx &x, Result &r, const char *path, const uint32_t *positions, ui
     rd.staging = staging;
     rd.cap = staging + kMaxRecord;
     rd.max_coverage = x.max_coverage;
-    PL_TRY(g_staging.ensure(rd.cap));
+    SECEDO_TRY(g_staging.ensure(rd.cap));
     const hipStream_t s = x.s;
-    PL_TRY(x.positions.reserve(std::max<uint64_t>(n_positions, 1), 0, s));
-    if (n_positions) PL_TRY(hipMemcpyAsync(x.positions.p, positions, n_positions * 4, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(x.positions.grow(std::max<uint64_t>(n_positions, 1), 0, s));
+    if (n_positions) SECEDO_TRY(hipMemcpyAsync(x.positions.p, positions, n_positions * 4, hipMemcpyHostToDevice, s));
     FileState init{};
     init.err_key = kNoError;
     *x.h_state = init;
-    PL_TRY(hipMemcpyAsync(x.d_state, x.h_state, sizeof(FileState), hipMemcpyHostToDevice, s));
-    PL_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(hipMemcpyAsync(x.d_state, x.h_state, sizeof(FileState), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
 
     const uint64_t l0 = r.n_loci, e0 = r.n_entries;
     uint64_t rec_base = 0;
@@ -277,23 +210,23 @@ int load_file(Ctx &x, Result &r, const char *path, const uint32_t *positions, ui
         const bool launched = c.n > 0;
         if (launched) {
             if (r.n_loci + c.n >= (1ull << 32)) return fail(SECEDO_E_LIMIT, "more than 2^32 - 1 loci");
-            PL_TRY(ensure_scratch(x, c.n));
-            PL_TRY(r.pos.reserve(r.n_loci + c.n, r.n_loci, s));
-            PL_TRY(r.off.reserve(r.n_loci + c.n + 1, r.n_loci, s));
-            PL_TRY(r.rid.reserve(r.n_entries + c.upper_entries, r.n_entries, s));
-            PL_TRY(r.idb.reserve(r.n_entries + c.upper_entries, r.n_entries, s));
-            PL_TRY(x.bytes.reserve((c.complete + 1) / 2, 0, s));
-            PL_TRY(hipEventRecord(x.ev[0], s));
-            PL_TRY(hipMemcpyAsync(x.bytes.p, c.buf, c.complete, hipMemcpyHostToDevice, s));
-            PL_TRY(hipMemcpyAsync(x.rec.p, c.rec, (size_t)c.n * 4, hipMemcpyHostToDevice, s));
-            PL_TRY(hipEventRecord(x.ev[1], s));
+            SECEDO_TRY(ensure_scratch(x, c.n));
+            SECEDO_TRY(r.pos.grow(r.n_loci + c.n, r.n_loci, s));
+            SECEDO_TRY(r.off.grow(r.n_loci + c.n + 1, r.n_loci, s));
+            SECEDO_TRY(r.rid.grow(r.n_entries + c.upper_entries, r.n_entries, s));
+            SECEDO_TRY(r.idb.grow(r.n_entries + c.upper_entries, r.n_entries, s));
+            SECEDO_TRY(x.bytes.grow((c.complete + 1) / 2, 0, s));
+            SECEDO_TRY(hipEventRecord(x.ev[0], s));
+            SECEDO_TRY(hipMemcpyAsync(x.bytes.p, c.buf, c.complete, hipMemcpyHostToDevice, s));
+            SECEDO_TRY(hipMemcpyAsync(x.rec.p, c.rec, (size_t)c.n * 4, hipMemcpyHostToDevice, s));
+            SECEDO_TRY(hipEventRecord(x.ev[1], s));
             Chunk dc{x.bytes.p, x.rec.p, c.n, rec_base};
             ChunkScratch w{x.pos.p, x.cov.p, x.mval.p, x.mscan.p, x.keep.p, x.lidx.p, x.cnt.p, x.eoff.p, x.tmp.p,
                            (size_t)x.tmp.n};
-            PL_TRY(decode_chunk(dc, w, x.max_coverage, x.positions.p, n_positions, carry, r.n_loci, r.n_entries, x.i2g,
+            SECEDO_TRY(decode_chunk(dc, w, x.max_coverage, x.positions.p, n_positions, carry, r.n_loci, r.n_entries, x.i2g,
                                 x.n_ids, r.pos.p, r.off.p, r.rid.p, r.idb.p, x.d_state, x.d_tail, s));
-            PL_TRY(hipEventRecord(x.ev[2], s));
-            PL_TRY(hipMemcpyAsync(x.h_tail, x.d_tail, sizeof(ChunkTail), hipMemcpyDeviceToHost, s));
+            SECEDO_TRY(hipEventRecord(x.ev[2], s));
+            SECEDO_TRY(hipMemcpyAsync(x.h_tail, x.d_tail, sizeof(ChunkTail), hipMemcpyDeviceToHost, s));
         }
         // the next chunk: the cut record first, then new bytes; read and walked while the device works
         HostChunk &nx = chunk[1 - cur];
@@ -302,7 +235,7 @@ int load_file(Ctx &x, Result &r, const char *path, const uint32_t *positions, ui
         nx.n = 0;
         rd.fill(nx);
         if (launched) {
-            PL_TRY(hipStreamSynchronize(s));
+            SECEDO_TRY(hipStreamSynchronize(s));
             x.upload_ms += elapsed(x.ev[0], x.ev[1]);
             x.device_ms += elapsed(x.ev[1], x.ev[2]);
             r.n_loci += x.h_tail->loci;
@@ -315,8 +248,8 @@ int load_file(Ctx &x, Result &r, const char *path, const uint32_t *positions, ui
     }
     *read_ms += rd.read_ms;
     *walk_ms += rd.walk_ms;
-    PL_TRY(hipMemcpyAsync(x.h_state, x.d_state, sizeof(FileState), hipMemcpyDeviceToHost, s));
-    PL_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(hipMemcpyAsync(x.h_state, x.d_state, sizeof(FileState), hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
     const FileState st = *x.h_state;
     if (st.err_key != kNoError)
         return fail(SECEDO_E_INVALID_ARG, "Cell id " + std::to_string(st.err_key & 0x3FFFu) +
@@ -334,31 +267,31 @@ int load_file(Ctx &x, Result &r, const char *path, const uint32_t *positions, ui
         return SECEDO_OK;
     }
     // the file's own last offset, so the span passes see off[l0 + n_loci]
-    PL_TRY(r.off.reserve(r.n_loci + 1, r.n_loci, s));
+    SECEDO_TRY(r.off.grow(r.n_loci + 1, r.n_loci, s));
     uint64_t end = r.n_entries;
-    PL_TRY(hipMemcpy(r.off.p + r.n_loci, &end, 8, hipMemcpyHostToDevice));
-    PL_TRY(hipEventRecord(x.ev[1], s));
+    SECEDO_TRY(hipMemcpy(r.off.p + r.n_loci, &end, 8, hipMemcpyHostToDevice));
+    SECEDO_TRY(hipEventRecord(x.ev[1], s));
     const uint64_t table = (uint64_t)st.max_rid + 1;
     if (table <= 4 * n_entries + 1024 && table <= 0xFFFFFFFFull) {
         Dev<uint32_t> first, last;
-        PL_TRY(first.alloc(table));
-        PL_TRY(last.alloc(table));
-        PL_TRY(spans_dense(r.pos.p, r.off.p, r.rid.p, l0, (uint32_t)n_loci, first.p, last.p, (uint32_t)table,
+        SECEDO_TRY(first.alloc(table));
+        SECEDO_TRY(last.alloc(table));
+        SECEDO_TRY(spans_dense(r.pos.p, r.off.p, r.rid.p, l0, (uint32_t)n_loci, first.p, last.p, (uint32_t)table,
                            x.d_state, s));
-        PL_TRY(hipEventRecord(x.ev[2], s));
-        PL_TRY(hipMemcpyAsync(x.h_state, x.d_state, sizeof(FileState), hipMemcpyDeviceToHost, s));
-        PL_TRY(hipStreamSynchronize(s));
+        SECEDO_TRY(hipEventRecord(x.ev[2], s));
+        SECEDO_TRY(hipMemcpyAsync(x.h_state, x.d_state, sizeof(FileState), hipMemcpyDeviceToHost, s));
+        SECEDO_TRY(hipStreamSynchronize(s));
     } else {
         Dev<uint64_t> keys;
         Dev<uint8_t> tmp;
-        PL_TRY(keys.alloc(2 * n_entries));
+        SECEDO_TRY(keys.alloc(2 * n_entries));
         const size_t tb = sort_bytes(n_entries);
-        PL_TRY(tmp.alloc(tb));
-        PL_TRY(spans_sparse(r.pos.p, r.off.p, r.rid.p, l0, (uint32_t)n_loci, e0, n_entries, keys.p, tmp.p, tb,
+        SECEDO_TRY(tmp.alloc(tb));
+        SECEDO_TRY(spans_sparse(r.pos.p, r.off.p, r.rid.p, l0, (uint32_t)n_loci, e0, n_entries, keys.p, tmp.p, tb,
                             x.d_state, s));
-        PL_TRY(hipEventRecord(x.ev[2], s));
-        PL_TRY(hipMemcpyAsync(x.h_state, x.d_state, sizeof(FileState), hipMemcpyDeviceToHost, s));
-        PL_TRY(hipStreamSynchronize(s));
+        SECEDO_TRY(hipEventRecord(x.ev[2], s));
+        SECEDO_TRY(hipMemcpyAsync(x.h_state, x.d_state, sizeof(FileState), hipMemcpyDeviceToHost, s));
+        SECEDO_TRY(hipStreamSynchronize(s));
     }
     x.device_ms += elapsed(x.ev[1], x.ev[2]);
     *max_len = x.h_state->max_span;
@@ -398,24 +331,24 @@ int secedo_pileup_load_device(const char *const *bin_files, uint32_t n_files, co
     Result &r = *g_result;
     r.chr_locus_off.assign(n_slots + 1, 0);
     StreamGuard sg;
-    PL_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    SECEDO_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
     EventGuard eg;
-    for (hipEvent_t &e : eg.e) PL_TRY(hipEventCreate(&e));
+    for (hipEvent_t &e : eg.e) SECEDO_TRY(hipEventCreate(&e));
     Ctx x{};
     x.s = sg.s;
     std::copy(eg.e, eg.e + 3, x.ev);
     x.n_ids = n_ids;
     x.max_coverage = max_coverage;
     Dev<uint16_t> d_i2g;
-    PL_TRY(d_i2g.alloc(n_ids));
-    if (n_ids) PL_TRY(hipMemcpy(d_i2g.p, id_to_group, n_ids * 2ull, hipMemcpyHostToDevice));
+    SECEDO_TRY(d_i2g.alloc(n_ids));
+    if (n_ids) SECEDO_TRY(hipMemcpy(d_i2g.p, id_to_group, n_ids * 2ull, hipMemcpyHostToDevice));
     x.i2g = d_i2g.p;
     Dev<uint8_t> d_small;
-    PL_TRY(d_small.alloc(sizeof(FileState) + sizeof(ChunkTail)));
+    SECEDO_TRY(d_small.alloc(sizeof(FileState) + sizeof(ChunkTail)));
     x.d_state = reinterpret_cast<FileState *>(d_small.p);
     x.d_tail = reinterpret_cast<ChunkTail *>(d_small.p + sizeof(FileState));
     PinnedSmall h_small;
-    PL_TRY(hipHostMalloc(&h_small.p, sizeof(FileState) + sizeof(ChunkTail), hipHostMallocDefault));
+    SECEDO_TRY(hipHostMalloc(&h_small.p, sizeof(FileState) + sizeof(ChunkTail), hipHostMallocDefault));
     x.h_state = reinterpret_cast<FileState *>(h_small.p);
     x.h_tail = reinterpret_cast<ChunkTail *>(static_cast<uint8_t *>(h_small.p) + sizeof(FileState));
 
@@ -425,17 +358,17 @@ int secedo_pileup_load_device(const char *const *bin_files, uint32_t n_files, co
         if (i >= 0) {
             const uint32_t *p = positions ? positions[i] : nullptr;
             const uint64_t np = (p && n_positions) ? n_positions[i] : 0;
-            PL_CALL(load_file(x, r, bin_files[i], p, np, compute_max_read_len != 0, staging, &num_cells[i],
+            SECEDO_CALL(load_file(x, r, bin_files[i], p, np, compute_max_read_len != 0, staging, &num_cells[i],
                               &max_read_length[i], &read_ms, &walk_ms));
         }
         r.chr_locus_off[slot + 1] = (uint32_t)r.n_loci;
     }
-    PL_TRY(r.pos.reserve(std::max<uint64_t>(r.n_loci, 1), r.n_loci, x.s));
-    PL_TRY(r.off.reserve(r.n_loci + 1, r.n_loci, x.s));
-    PL_TRY(r.rid.reserve(std::max<uint64_t>(r.n_entries, 1), r.n_entries, x.s));
-    PL_TRY(r.idb.reserve(std::max<uint64_t>(r.n_entries, 1), r.n_entries, x.s));
+    SECEDO_TRY(r.pos.grow(std::max<uint64_t>(r.n_loci, 1), r.n_loci, x.s));
+    SECEDO_TRY(r.off.grow(r.n_loci + 1, r.n_loci, x.s));
+    SECEDO_TRY(r.rid.grow(std::max<uint64_t>(r.n_entries, 1), r.n_entries, x.s));
+    SECEDO_TRY(r.idb.grow(std::max<uint64_t>(r.n_entries, 1), r.n_entries, x.s));
     const uint64_t end = r.n_entries;
-    PL_TRY(hipMemcpy(r.off.p + r.n_loci, &end, 8, hipMemcpyHostToDevice));
+    SECEDO_TRY(hipMemcpy(r.off.p + r.n_loci, &end, 8, hipMemcpyHostToDevice));
     info->n_loci = r.n_loci;
     info->n_entries = r.n_entries;
     if (times) {
@@ -453,11 +386,11 @@ int secedo_pileup_load_fetch(uint32_t *chr_locus_off, uint32_t *locus_pos, uint6
     const Result *r = g_result;
     if (!r) return fail(SECEDO_E_STATE, "no pileup load result on this thread");
     if (chr_locus_off)
-        PL_TRY(hipMemcpy(chr_locus_off, r->chr_locus_off.data(), r->chr_locus_off.size() * 4, hipMemcpyDefault));
-    if (locus_pos && r->n_loci) PL_TRY(hipMemcpy(locus_pos, r->pos.p, r->n_loci * 4, hipMemcpyDefault));
-    if (locus_entry_off) PL_TRY(hipMemcpy(locus_entry_off, r->off.p, (r->n_loci + 1) * 8, hipMemcpyDefault));
-    if (read_ids && r->n_entries) PL_TRY(hipMemcpy(read_ids, r->rid.p, r->n_entries * 4, hipMemcpyDefault));
-    if (id_base16 && r->n_entries) PL_TRY(hipMemcpy(id_base16, r->idb.p, r->n_entries * 2, hipMemcpyDefault));
+        SECEDO_TRY(hipMemcpy(chr_locus_off, r->chr_locus_off.data(), r->chr_locus_off.size() * 4, hipMemcpyDefault));
+    if (locus_pos && r->n_loci) SECEDO_TRY(hipMemcpy(locus_pos, r->pos.p, r->n_loci * 4, hipMemcpyDefault));
+    if (locus_entry_off) SECEDO_TRY(hipMemcpy(locus_entry_off, r->off.p, (r->n_loci + 1) * 8, hipMemcpyDefault));
+    if (read_ids && r->n_entries) SECEDO_TRY(hipMemcpy(read_ids, r->rid.p, r->n_entries * 4, hipMemcpyDefault));
+    if (id_base16 && r->n_entries) SECEDO_TRY(hipMemcpy(id_base16, r->idb.p, r->n_entries * 2, hipMemcpyDefault));
     return SECEDO_OK;
 }
 

@@ -20,6 +20,7 @@
 // they save (N = 8000: 0.36 s against 0.18 s) -- it is not in the code.
 #include "secedo_simmat.h"
 #include "secedo_spectral.h"
+#include "host_util.hpp"
 #include "spectral_kernels.hpp"
 #include "sym_eig.hpp"
 
@@ -40,6 +41,7 @@ int api_fail(int code, const std::string &msg);  // simmat_api.cpp: sets secedo_
 
 namespace {
 
+using secedo::host::Buf;
 using secedo::spectral::kBlockWidth;
 constexpr uint32_t BW = kBlockWidth;
 // Krylov blocks per restart cycle, set per solve (cycle_blocks): a larger space needs fewer matrix passes in
@@ -54,15 +56,6 @@ uint32_t cycle_blocks(uint32_t n) {
     }
     return n < 2000u ? 6u : n < 12000u ? 7u : 8u;
 }
-
-struct Buf {
-    void *p = nullptr;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    double *d() const { return static_cast<double *>(p); }
-};
 
 #define SP_TRY(expr)                                                                                      \
     do {                                                                                                  \
@@ -111,7 +104,7 @@ struct Solver {
         SP_TRY(alive_dev.alloc((size_t)(kCycleBlocks + 1) * BW * 4));
         return SECEDO_OK;
     }
-    double *block(uint32_t b) const { return Q.d() + b * blk_stride; }
+    double *block(uint32_t b) const { return Q.as<double>() + b * blk_stride; }
     // sum over the ranks of a device buffer, in place (nothing to do for a rank that holds all rows)
     int reduce_ranks(double *buf, size_t count) {
         if (!allreduce) return SECEDO_OK;
@@ -123,26 +116,26 @@ struct Solver {
     int scales() {
         using namespace secedo::spectral;
         SP_TRY(hipMemsetAsync(sums.p, 0, (size_t)n * 8, stream));
-        SP_TRY(row_sums(A, n, row_begin, n_rows, sums.d(), stream));
-        const int rc = reduce_ranks(sums.d(), n);
+        SP_TRY(row_sums(A, n, row_begin, n_rows, sums.as<double>(), stream));
+        const int rc = reduce_ranks(sums.as<double>(), n);
         if (rc) return rc;
-        SP_TRY(scale_from_sums(n, sums.d(), s.d(), root.d(), stream));
+        SP_TRY(scale_from_sums(n, sums.as<double>(), s.as<double>(), root.as<double>(), stream));
         return SECEDO_OK;
     }
     // y = T x
     int product(const double *x, double *y) {
         using namespace secedo::spectral;
         // (one rank: the segments' sum and the finishing step in one kernel)
-        SP_TRY(product_partial(A, n, row_begin, n_rows, s.d(), x, Z.d(), P.d(), allreduce ? Ypart.d() : nullptr,
+        SP_TRY(product_partial(A, n, row_begin, n_rows, s.as<double>(), x, Z.as<double>(), P.as<double>(), allreduce ? Ypart.as<double>() : nullptr,
                                allreduce ? nullptr : y, stream));
         if (!allreduce) return SECEDO_OK;
-        const int rc = reduce_ranks(Ypart.d(), blk_stride);
+        const int rc = reduce_ranks(Ypart.as<double>(), blk_stride);
         if (rc) return rc;
-        SP_TRY(product_finish(n, s.d(), x, Ypart.d(), y, stream));
+        SP_TRY(product_finish(n, s.as<double>(), x, Ypart.as<double>(), y, stream));
         return SECEDO_OK;
     }
     int upload_small(const std::vector<double> &m) {
-        SP_TRY(hipMemcpyAsync(M.d(), m.data(), m.size() * 8, hipMemcpyHostToDevice, stream));
+        SP_TRY(hipMemcpyAsync(M.as<double>(), m.data(), m.size() * 8, hipMemcpyHostToDevice, stream));
         return SECEDO_OK;
     }
     // Q[blk] = orthonormalised src (Cholesky QR, twice, through Wtmp; src keeps its contents). Nothing comes back to the
@@ -151,15 +144,15 @@ struct Solver {
     int orthonormalise(double *src, uint32_t blk) {
         using namespace secedo::spectral;
         double *dst = block(blk);
-        double *R = static_cast<double *>(Rblk.p) + (size_t)blk * BW * BW;
-        uint32_t *alive = static_cast<uint32_t *>(alive_dev.p) + (size_t)blk * BW;
-        SP_TRY(gram(n, src, blk_stride, 1, src, Gp.d(), G.d(), stream));
-        SP_TRY(cholesky_drop(G.d(), nullptr, M.d(), Rfirst.d(), nullptr, stream));
-        double *tmp = Wtmp.d();
-        SP_TRY(block_combine(n, src, blk_stride, 1, M.d(), 1.0, 0.0, tmp, stream));
-        SP_TRY(gram(n, tmp, blk_stride, 1, tmp, Gp.d(), G.d(), stream));
-        SP_TRY(cholesky_drop(G.d(), Rfirst.d(), M.d(), R, alive, stream));
-        SP_TRY(block_combine(n, tmp, blk_stride, 1, M.d(), 1.0, 0.0, dst, stream));
+        double *R = Rblk.as<double>() + (size_t)blk * BW * BW;
+        uint32_t *alive = alive_dev.as<uint32_t>() + (size_t)blk * BW;
+        SP_TRY(gram(n, src, blk_stride, 1, src, Gp.as<double>(), G.as<double>(), stream));
+        SP_TRY(cholesky_drop(G.as<double>(), nullptr, M.as<double>(), Rfirst.as<double>(), nullptr, stream));
+        double *tmp = Wtmp.as<double>();
+        SP_TRY(block_combine(n, src, blk_stride, 1, M.as<double>(), 1.0, 0.0, tmp, stream));
+        SP_TRY(gram(n, tmp, blk_stride, 1, tmp, Gp.as<double>(), G.as<double>(), stream));
+        SP_TRY(cholesky_drop(G.as<double>(), Rfirst.as<double>(), M.as<double>(), R, alive, stream));
+        SP_TRY(block_combine(n, tmp, blk_stride, 1, M.as<double>(), 1.0, 0.0, dst, stream));
         return SECEDO_OK;
     }
 };
@@ -192,10 +185,10 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
     int rc = sv.setup(d_rows, row_begin, n_rows, n, allreduce, allreduce_ctx, stream);
     if (rc) return rc;
     if ((rc = sv.scales())) return rc;
-    SP_TRY(init_block(n, sv.root.d(), sv.W.d(), stream));
+    SP_TRY(init_block(n, sv.root.as<double>(), sv.W.as<double>(), stream));
     std::vector<double> R_last((size_t)BW * BW);
     std::vector<uint32_t> basis_alive((size_t)(kCycleBlocks + 1) * BW, 1);
-    if ((rc = sv.orthonormalise(sv.W.d(), 0))) return rc;
+    if ((rc = sv.orthonormalise(sv.W.as<double>(), 0))) return rc;
 
     const uint32_t m = kCycleBlocks * BW;
     // Thick restart (large n): the 64 best Ritz vectors are kept as blocks 0 and 1 and the last Krylov
@@ -222,22 +215,22 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
         std::fill(H.begin(), H.end(), 0.0);
         for (uint32_t r = 0; r < kept * BW; ++r) H[(size_t)r * m + r] = theta_kept[r];
         for (uint32_t j = kept; j < kCycleBlocks; ++j) {
-            if ((rc = sv.product(sv.block(j), sv.W.d()))) return rc;
+            if ((rc = sv.product(sv.block(j), sv.W.as<double>()))) return rc;
             ++inf.block_products;
             for (int pass = 0; pass < 2; ++pass) {  // classical Gram-Schmidt, twice
                 // the coefficients stay on the device; the host needs them only for the projection H
-                double *coef = sv.Gall.d() + (size_t)(j * 2 + pass) * kCycleBlocks * BW * BW;
-                SP_TRY(gram(n, sv.Q.d(), sv.blk_stride, j + 1, sv.W.d(), sv.Gp.d(), coef, stream));
-                SP_TRY(block_combine(n, sv.Q.d(), sv.blk_stride, j + 1, coef, -1.0, 1.0, sv.W.d(), stream));
+                double *coef = sv.Gall.as<double>() + (size_t)(j * 2 + pass) * kCycleBlocks * BW * BW;
+                SP_TRY(gram(n, sv.Q.as<double>(), sv.blk_stride, j + 1, sv.W.as<double>(), sv.Gp.as<double>(), coef, stream));
+                SP_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, j + 1, coef, -1.0, 1.0, sv.W.as<double>(), stream));
             }
-            if ((rc = sv.orthonormalise(sv.W.d(), j + 1))) return rc;
+            if ((rc = sv.orthonormalise(sv.W.as<double>(), j + 1))) return rc;
         }
         // The one read-back of the cycle: H[blk, j] = sum of the two passes' coefficients of step j, who
         // survived the orthonormalisations, and the R of the last step (for the residuals).
         g.resize((size_t)kCycleBlocks * 2 * kCycleBlocks * BW * BW);
-        SP_TRY(hipMemcpyAsync(g.data(), sv.Gall.d(), g.size() * 8, hipMemcpyDeviceToHost, stream));
+        SP_TRY(hipMemcpyAsync(g.data(), sv.Gall.as<double>(), g.size() * 8, hipMemcpyDeviceToHost, stream));
         SP_TRY(hipMemcpyAsync(basis_alive.data(), sv.alive_dev.p, basis_alive.size() * 4, hipMemcpyDeviceToHost, stream));
-        SP_TRY(hipMemcpyAsync(R_last.data(), static_cast<const double *>(sv.Rblk.p) + (size_t)kCycleBlocks * BW * BW,
+        SP_TRY(hipMemcpyAsync(R_last.data(), sv.Rblk.as<const double>() + (size_t)kCycleBlocks * BW * BW,
                               R_last.size() * 8, hipMemcpyDeviceToHost, stream));
         SP_TRY(hipStreamSynchronize(stream));
         for (uint32_t j = kept; j < kCycleBlocks; ++j)
@@ -295,28 +288,28 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
                     for (uint32_t k = 0; k < BW; ++k)
                         coeff[((size_t)blk * BW + a) * BW + k] = U[(size_t)(blk * BW + a) * ucols + q * BW + k];
             if ((rc = sv.upload_small(coeff))) return rc;
-            SP_TRY(block_combine(n, sv.Q.d(), sv.blk_stride, kCycleBlocks, sv.M.d(), 1.0, 0.0,
-                                 q == 0 ? sv.W.d() : sv.W2.d(), stream));
+            SP_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, kCycleBlocks, sv.M.as<double>(), 1.0, 0.0,
+                                 q == 0 ? sv.W.as<double>() : sv.W2.as<double>(), stream));
         }
         if (last) {
             for (uint32_t k = 0; k < n_values; ++k) eigenvalues[k] = 2.0 * (1.0 - theta[top[k]]);
-            SP_TRY(write_vectors(n, sv.W.d(), n_vectors, d_eigenvectors, stream));
+            SP_TRY(write_vectors(n, sv.W.as<double>(), n_vectors, d_eigenvectors, stream));
             SP_TRY(hipStreamSynchronize(stream));
             break;
         }
-        if ((rc = sv.orthonormalise(sv.W.d(), 0))) return rc;
+        if ((rc = sv.orthonormalise(sv.W.as<double>(), 0))) return rc;
         kept = 0;
         if (keep == 2u) {
             // second Ritz block: orthogonal to the first up to rounding; cleaned like every other block
             for (int pass = 0; pass < 2; ++pass) {
-                SP_TRY(gram(n, sv.Q.d(), sv.blk_stride, 1, sv.W2.d(), sv.Gp.d(), sv.Gall.d(), stream));
-                SP_TRY(block_combine(n, sv.Q.d(), sv.blk_stride, 1, sv.Gall.d(), -1.0, 1.0, sv.W2.d(), stream));
+                SP_TRY(gram(n, sv.Q.as<double>(), sv.blk_stride, 1, sv.W2.as<double>(), sv.Gp.as<double>(), sv.Gall.as<double>(), stream));
+                SP_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, 1, sv.Gall.as<double>(), -1.0, 1.0, sv.W2.as<double>(), stream));
             }
-            if ((rc = sv.orthonormalise(sv.W2.d(), 1))) return rc;
+            if ((rc = sv.orthonormalise(sv.W2.as<double>(), 1))) return rc;
             // the last Krylov block (and who is alive in it) continues as block 2
             SP_TRY(hipMemcpyAsync(sv.block(2), sv.block(kCycleBlocks), sv.blk_stride * 8, hipMemcpyDeviceToDevice, stream));
-            SP_TRY(hipMemcpyAsync(static_cast<uint32_t *>(sv.alive_dev.p) + 2 * BW,
-                                  static_cast<const uint32_t *>(sv.alive_dev.p) + (size_t)kCycleBlocks * BW, BW * 4,
+            SP_TRY(hipMemcpyAsync(sv.alive_dev.as<uint32_t>() + 2 * BW,
+                                  sv.alive_dev.as<const uint32_t>() + (size_t)kCycleBlocks * BW, BW * 4,
                                   hipMemcpyDeviceToDevice, stream));
             kept = 2;
             for (uint32_t r = 0; r < ucols; ++r) theta_kept[r] = theta[m - 1 - r];
@@ -338,9 +331,9 @@ int secedo_laplacian_device(const double *d_similarity, uint32_t n, double *d_ou
     SP_TRY(s.alloc((size_t)n * 8));
     SP_TRY(root.alloc((size_t)n * 8));
     SP_TRY(sums.alloc((size_t)n * 8));
-    SP_TRY(secedo::spectral::row_sums(d_similarity, n, 0, n, sums.d(), st));
-    SP_TRY(secedo::spectral::scale_from_sums(n, sums.d(), s.d(), root.d(), st));
-    SP_TRY(secedo::spectral::laplacian(d_similarity, s.d(), n, d_out, st));
+    SP_TRY(secedo::spectral::row_sums(d_similarity, n, 0, n, sums.as<double>(), st));
+    SP_TRY(secedo::spectral::scale_from_sums(n, sums.as<double>(), s.as<double>(), root.as<double>(), st));
+    SP_TRY(secedo::spectral::laplacian(d_similarity, s.as<double>(), n, d_out, st));
     SP_TRY(hipStreamSynchronize(st));  // the scratch is freed on return
     return SECEDO_OK;
 }
@@ -375,7 +368,7 @@ int secedo_spectral_eigs(int device_id, const double *similarity, uint32_t n, ui
     SP_TRY(a.alloc((size_t)n * n * 8));
     SP_TRY(v.alloc((size_t)n * std::max<uint32_t>(n_vectors, 1) * 8));
     SP_TRY(hipMemcpy(a.p, similarity, (size_t)n * n * 8, hipMemcpyHostToDevice));
-    const int rc = solve(device_id, a.d(), 0, n, n, n_values, n_vectors, tol, max_cycles, eigenvalues, v.d(), info,
+    const int rc = solve(device_id, a.as<double>(), 0, n, n, n_values, n_vectors, tol, max_cycles, eigenvalues, v.as<double>(), info,
                          nullptr, nullptr, nullptr);
     if (rc) return rc;
     if (n_vectors) SP_TRY(hipMemcpy(eigenvectors, v.p, (size_t)n * n_vectors * 8, hipMemcpyDeviceToHost));

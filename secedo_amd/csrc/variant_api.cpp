@@ -8,6 +8,7 @@
 // place (:161-163), and a missing paternal contig reads as empty.
 #include "secedo_variant.h"
 #include "secedo_simmat.h"
+#include "host_util.hpp"
 #include "variant_kernels.hpp"
 
 #include <hip/hip_runtime.h>
@@ -18,7 +19,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,33 +33,7 @@
 namespace {
 
 using secedo::variant::Logs;
-
-thread_local std::string g_error;
-
-int fail(int code, const std::string &msg) {
-    g_error = msg;
-    return code;
-}
-
-#define VC_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(SECEDO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-#define VC_CALL(expr)                 \
-    do {                              \
-        int rc_ = (expr);             \
-        if (rc_ != SECEDO_OK) return rc_; \
-    } while (0)
-
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point &t0) {
-    const Clock::time_point t1 = Clock::now();
-    const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-    return ms;
-}
+using namespace secedo::host;
 
 constexpr char kIntToChar[6] = {'A', 'C', 'G', 'T', 'N', 'N'};
 
@@ -78,24 +52,6 @@ std::string id_to_chromosome(uint32_t chr_id) {
     if (chr_id < 22) return std::to_string(chr_id + 1);
     return chr_id == 22 ? "X" : "Y";
 }
-
-struct Buf {
-    void *p = nullptr;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-    hipError_t alloc(size_t bytes) {
-        release();
-        return hipMalloc(&p, std::max<size_t>(bytes, 8));
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    template <class T>
-    T *as() const { return static_cast<T *>(p); }
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // The reference genome
@@ -298,7 +254,7 @@ int get_next_chromosome(Fasta &f, const Map &map, bool is_diploid, std::vector<u
     tmp1->clear();
     read_contig(f, tmp1);
     auto it = map.find(chr_name);
-    if (it != map.end()) VC_CALL(apply_map(it->second, *tmp1, chr_data));
+    if (it != map.end()) SECEDO_CALL(apply_map(it->second, *tmp1, chr_data));
     else std::swap(*tmp1, *chr_data);
 
     const int ch1 = f.get();
@@ -313,7 +269,7 @@ int get_next_chromosome(Fasta &f, const Map &map, bool is_diploid, std::vector<u
     tmp1->clear();
     read_contig(f, tmp1);
     it = map.find(chr_name);
-    if (it != map.end()) VC_CALL(apply_map(it->second, *tmp1, tmp2));
+    if (it != map.end()) SECEDO_CALL(apply_map(it->second, *tmp1, tmp2));
     else std::swap(*tmp1, *tmp2);
     if (chr_data->size() != tmp2->size())
         return fail(SECEDO_E_INVALID_ARG, "Invalid reference genome. Maternal and paternal chromosome sizes don't "
@@ -335,17 +291,17 @@ int reference_genotypes(const char *fasta, const char *map_file, const uint32_t 
                         const uint32_t *locus_pos, uint8_t *locus_ref, uint32_t *chr_locus_end, double *fasta_ms) {
     Clock::time_point t0 = Clock::now();
     Fasta f;
-    VC_CALL(open_fasta(fasta, &f));
+    SECEDO_CALL(open_fasta(fasta, &f));
     std::vector<MapEntry> entries;
-    VC_CALL(read_map(map_file, &entries));
+    SECEDO_CALL(read_map(map_file, &entries));
     const Map map = group_map(entries);
     const bool diploid = check_is_diploid(f);
     std::vector<uint8_t> chr, tmp1, tmp2;
     double parse = 0;
     for (uint32_t c = 0; c < n_chr; ++c) {
         Clock::time_point t1 = Clock::now();
-        VC_CALL(get_next_chromosome(f, map, diploid, &chr, &tmp1, &tmp2));
-        parse += ms_since(t1);
+        SECEDO_CALL(get_next_chromosome(f, map, diploid, &chr, &tmp1, &tmp2));
+        parse += ms_lap(t1);
         const uint32_t b = chr_locus_off[c], e = chr_locus_off[c + 1];
         uint32_t l = b;
         for (; l < e; ++l) {
@@ -356,7 +312,7 @@ int reference_genotypes(const char *fasta, const char *map_file, const uint32_t 
         chr_locus_end[c] = l;
         for (; l < e; ++l) locus_ref[l] = 0;
     }
-    if (fasta_ms) *fasta_ms = parse + (n_chr == 0 ? ms_since(t0) : 0.0);
+    if (fasta_ms) *fasta_ms = parse + (n_chr == 0 ? ms_lap(t0) : 0.0);
     return SECEDO_OK;
 }
 
@@ -367,7 +323,7 @@ int set_device(int device_id) {
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(SECEDO_E_NO_DEVICE, "no HIP device");
     if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_INVALID_ARG, "device id out of range");
-    VC_TRY(hipSetDevice(device_id));
+    SECEDO_TRY(hipSetDevice(device_id));
     return SECEDO_OK;
 }
 
@@ -402,23 +358,23 @@ int run_calls(const uint32_t *d_chr_locus_off, uint32_t n_chr, const uint64_t *d
     const std::vector<double> thr = threshold_table(theta);
     const size_t scan_bytes = V::scan_workspace(n_loci);
     Buf b_thr, b_end, b_cnt, b_off, b_flag, b_err, b_scan, b_rec;
-    VC_TRY(b_thr.alloc(thr.size() * sizeof(double)));
-    VC_TRY(b_end.alloc((size_t)n_chr * 4));
-    VC_TRY(b_cnt.alloc(((size_t)ranges + 1) * 4));
-    VC_TRY(b_off.alloc(((size_t)ranges + 1) * 4));
-    VC_TRY(b_flag.alloc(n_loci));
-    VC_TRY(b_err.alloc(4));
-    VC_TRY(b_scan.alloc(scan_bytes));
-    VC_TRY(hipMemcpyAsync(b_thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    if (n_chr) VC_TRY(hipMemcpyAsync(b_end.p, chr_locus_end, (size_t)n_chr * 4, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(b_thr.alloc(thr.size() * sizeof(double)));
+    SECEDO_TRY(b_end.alloc((size_t)n_chr * 4));
+    SECEDO_TRY(b_cnt.alloc(((size_t)ranges + 1) * 4));
+    SECEDO_TRY(b_off.alloc(((size_t)ranges + 1) * 4));
+    SECEDO_TRY(b_flag.alloc(n_loci));
+    SECEDO_TRY(b_err.alloc(4));
+    SECEDO_TRY(b_scan.alloc(scan_bytes));
+    SECEDO_TRY(hipMemcpyAsync(b_thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_chr) SECEDO_TRY(hipMemcpyAsync(b_end.p, chr_locus_end, (size_t)n_chr * 4, hipMemcpyHostToDevice, s));
 
     V::CallsIn in{d_chr_locus_off, b_end.as<uint32_t>(), n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci,
                   d_clusters, n_groups, d_locus_ref, b_thr.as<double>(), host_logs(hetero_prior, theta)};
     hipEvent_t e0, e1, e2, e3;
-    VC_TRY(hipEventCreate(&e0));
-    VC_TRY(hipEventCreate(&e1));
-    VC_TRY(hipEventCreate(&e2));
-    VC_TRY(hipEventCreate(&e3));
+    SECEDO_TRY(hipEventCreate(&e0));
+    SECEDO_TRY(hipEventCreate(&e1));
+    SECEDO_TRY(hipEventCreate(&e2));
+    SECEDO_TRY(hipEventCreate(&e3));
     struct Ev {
         hipEvent_t *e[4];
         ~Ev() { for (hipEvent_t *x : e) (void)hipEventDestroy(*x); }
@@ -428,33 +384,33 @@ int run_calls(const uint32_t *d_chr_locus_off, uint32_t n_chr, const uint64_t *d
     const char *mode = getenv("SECEDO_VARIANT_COUNTERS");
     const bool lds = mode ? strcmp(mode, "global") != 0 : kLdsDefault;
     int dev = 0, cus = 0;
-    VC_TRY(hipGetDevice(&dev));
-    VC_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    SECEDO_TRY(hipGetDevice(&dev));
+    SECEDO_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const uint32_t max_blocks = static_cast<uint32_t>(std::max(cus, 1)) * (lds ? 2u : 8u);
-    VC_TRY(hipEventRecord(e0, s));
-    VC_TRY(V::count_calls(in, d_mismatch, d_loci, b_cnt.as<uint32_t>(), b_off.as<uint32_t>(), b_flag.as<uint8_t>(),
+    SECEDO_TRY(hipEventRecord(e0, s));
+    SECEDO_TRY(V::count_calls(in, d_mismatch, d_loci, b_cnt.as<uint32_t>(), b_off.as<uint32_t>(), b_flag.as<uint8_t>(),
                           b_err.as<uint32_t>(), b_scan.p, scan_bytes, lds, max_blocks, s));
-    VC_TRY(hipEventRecord(e1, s));
+    SECEDO_TRY(hipEventRecord(e1, s));
     uint32_t head[2] = {0, 0};
-    VC_TRY(hipMemcpyAsync(&head[0], b_off.as<uint32_t>() + ranges, 4, hipMemcpyDeviceToHost, s));
-    VC_TRY(hipMemcpyAsync(&head[1], b_err.p, 4, hipMemcpyDeviceToHost, s));
-    VC_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(hipMemcpyAsync(&head[0], b_off.as<uint32_t>() + ranges, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(&head[1], b_err.p, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
     if (head[1]) return fail(SECEDO_E_INVALID_ARG, "a group id of the pileup is >= the length of clusters");
     out->total = head[0];
     float k1 = 0, k2 = 0;
-    VC_TRY(hipEventElapsedTime(&k1, e0, e1));
+    SECEDO_TRY(hipEventElapsedTime(&k1, e0, e1));
     out->kernel_ms = k1;
     if (out->total > capacity) return SECEDO_OK;
-    VC_TRY(b_rec.alloc((size_t)out->total * sizeof(secedo_variant_record)));
-    VC_TRY(hipEventRecord(e2, s));
-    VC_TRY(V::write_calls(in, b_off.as<uint32_t>(), b_flag.as<uint8_t>(), b_rec.as<secedo_variant_record>(), s));
-    VC_TRY(hipEventRecord(e3, s));
+    SECEDO_TRY(b_rec.alloc((size_t)out->total * sizeof(secedo_variant_record)));
+    SECEDO_TRY(hipEventRecord(e2, s));
+    SECEDO_TRY(V::write_calls(in, b_off.as<uint32_t>(), b_flag.as<uint8_t>(), b_rec.as<secedo_variant_record>(), s));
+    SECEDO_TRY(hipEventRecord(e3, s));
     out->records.resize(out->total);
     if (out->total)
-        VC_TRY(hipMemcpyAsync(out->records.data(), b_rec.p, (size_t)out->total * sizeof(secedo_variant_record),
+        SECEDO_TRY(hipMemcpyAsync(out->records.data(), b_rec.p, (size_t)out->total * sizeof(secedo_variant_record),
                               hipMemcpyDeviceToHost, s));
-    VC_TRY(hipStreamSynchronize(s));
-    VC_TRY(hipEventElapsedTime(&k2, e2, e3));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(hipEventElapsedTime(&k2, e2, e3));
     out->kernel_ms += k2;
     return SECEDO_OK;
 }
@@ -566,9 +522,9 @@ int write_outputs(const std::filesystem::path &out_dir, const std::string &refer
         }
     }
     for (uint32_t i = 0; i < num_clusters; ++i)
-        VC_CALL(write_file(out_dir / ("cluster_" + std::to_string(i) + ".vcf"), vcfs[i]));
-    VC_CALL(write_file(out_dir / "common.vcf", common));
-    VC_CALL(write_file(out_dir / "variant", ""));
+        SECEDO_CALL(write_file(out_dir / ("cluster_" + std::to_string(i) + ".vcf"), vcfs[i]));
+    SECEDO_CALL(write_file(out_dir / "common.vcf", common));
+    SECEDO_CALL(write_file(out_dir / "variant", ""));
     // write_vec(scores): default ostream formatting (%g, 6 digits); 0.0 / 0 prints as -nan on x86-64
     std::string scores;
     char buf[64];
@@ -595,31 +551,31 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
     Clock::time_point t0 = Clock::now();
     std::vector<uint8_t> locus_ref(n_loci);
     std::vector<uint32_t> chr_end(n_chr);
-    VC_CALL(reference_genotypes(reference_genome, map_file, chr_locus_off, n_chr, locus_pos, locus_ref.data(),
+    SECEDO_CALL(reference_genotypes(reference_genome, map_file, chr_locus_off, n_chr, locus_pos, locus_ref.data(),
                                 chr_end.data(), &t.fasta_ms));
-    t.gather_ms = ms_since(t0) - t.fasta_ms;
+    t.gather_ms = ms_lap(t0) - t.fasta_ms;
     const uint32_t num_clusters = static_cast<uint32_t>(*std::max_element(clusters, clusters + n)) + 1;
 
     Buf b_ref, b_cl, b_mm, b_loci;
-    VC_TRY(b_ref.alloc(n_loci));
-    VC_TRY(b_cl.alloc((size_t)n * 2));
-    VC_TRY(b_mm.alloc((size_t)n * 4));
-    VC_TRY(b_loci.alloc((size_t)n * 4));
-    if (n_loci) VC_TRY(hipMemcpyAsync(b_ref.p, locus_ref.data(), n_loci, hipMemcpyHostToDevice, s));
-    VC_TRY(hipMemcpyAsync(b_cl.p, clusters, (size_t)n * 2, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(b_ref.alloc(n_loci));
+    SECEDO_TRY(b_cl.alloc((size_t)n * 2));
+    SECEDO_TRY(b_mm.alloc((size_t)n * 4));
+    SECEDO_TRY(b_loci.alloc((size_t)n * 4));
+    if (n_loci) SECEDO_TRY(hipMemcpyAsync(b_ref.p, locus_ref.data(), n_loci, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(b_cl.p, clusters, (size_t)n * 2, hipMemcpyHostToDevice, s));
     Calls calls;
-    VC_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, b_cl.as<uint16_t>(),
+    SECEDO_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, b_cl.as<uint16_t>(),
                       n, b_ref.as<uint8_t>(), chr_end.data(), hetero_prior, theta, UINT32_MAX, b_mm.as<uint32_t>(),
                       b_loci.as<uint32_t>(), &calls, s));
     std::vector<uint32_t> mismatch(n), loci(n);
-    VC_TRY(hipMemcpyAsync(mismatch.data(), b_mm.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    VC_TRY(hipMemcpyAsync(loci.data(), b_loci.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    VC_TRY(hipStreamSynchronize(s));
-    t.device_ms = ms_since(t0) + pre_device_ms;
+    SECEDO_TRY(hipMemcpyAsync(mismatch.data(), b_mm.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(loci.data(), b_loci.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    t.device_ms = ms_lap(t0) + pre_device_ms;
     t.kernel_ms = calls.kernel_ms;
-    VC_CALL(write_outputs(out_dir, reference_genome, num_clusters, calls.records, chr_locus_off, n_chr, locus_pos,
+    SECEDO_CALL(write_outputs(out_dir, reference_genome, num_clusters, calls.records, chr_locus_off, n_chr, locus_pos,
                           locus_ref.data(), mismatch, loci));
-    t.write_ms = ms_since(t0);
+    t.write_ms = ms_lap(t0);
     if (times) *times = t;
     return SECEDO_OK;
 }
@@ -656,20 +612,20 @@ int secedo_variant_reference_genotypes(const char *fasta, const char *map_file, 
 
 int secedo_variant_is_diploid(const char *fasta) {
     Fasta f;
-    VC_CALL(open_fasta(fasta, &f));
+    SECEDO_CALL(open_fasta(fasta, &f));
     return check_is_diploid(f) ? 1 : 0;
 }
 
 int secedo_variant_read_chromosome(const char *fasta, const char *map_file, uint32_t index, uint8_t *out,
                                    uint64_t capacity, uint64_t *length) {
     Fasta f;
-    VC_CALL(open_fasta(fasta, &f));
+    SECEDO_CALL(open_fasta(fasta, &f));
     std::vector<MapEntry> entries;
-    VC_CALL(read_map(map_file, &entries));
+    SECEDO_CALL(read_map(map_file, &entries));
     const Map map = group_map(entries);
     const bool diploid = check_is_diploid(f);
     std::vector<uint8_t> chr, tmp1, tmp2;
-    for (uint32_t c = 0; c <= index; ++c) VC_CALL(get_next_chromosome(f, map, diploid, &chr, &tmp1, &tmp2));
+    for (uint32_t c = 0; c <= index; ++c) SECEDO_CALL(get_next_chromosome(f, map, diploid, &chr, &tmp1, &tmp2));
     *length = chr.size();
     if (chr.size() > capacity) return fail(SECEDO_E_LIMIT, "contig longer than capacity");
     if (!chr.empty()) memcpy(out, chr.data(), chr.size());
@@ -680,7 +636,7 @@ int secedo_variant_read_map(const char *map_file, char *names, uint32_t name_len
                             uint32_t *len, char *tr, uint8_t *chromosome_id, uint32_t capacity,
                             uint32_t *n_entries) {
     std::vector<MapEntry> entries;
-    VC_CALL(read_map(map_file, &entries));
+    SECEDO_CALL(read_map(map_file, &entries));
     *n_entries = static_cast<uint32_t>(entries.size());
     if (entries.size() > capacity) return fail(SECEDO_E_LIMIT, "more map entries than capacity");
     for (size_t i = 0; i < entries.size(); ++i) {
@@ -703,7 +659,7 @@ int secedo_variant_apply_map(const uint32_t *start_pos, const uint32_t *len, con
     std::vector<ChrMap> map(n_map);
     for (uint32_t i = 0; i < n_map; ++i) map[i] = ChrMap{start_pos[i], len[i], tr[i], 0};
     std::vector<uint8_t> in(chr_data, chr_data + n), res;
-    VC_CALL(apply_map(map, in, &res));
+    SECEDO_CALL(apply_map(map, in, &res));
     *out_len = res.size();
     if (res.size() > capacity) return fail(SECEDO_E_LIMIT, "result longer than capacity");
     if (!res.empty()) memcpy(out, res.data(), res.size());
@@ -720,11 +676,11 @@ int secedo_variant_calls_device(int device_id, const uint32_t *d_chr_locus_off, 
                                 void *stream) {
     (void)d_locus_pos;
     (void)n_entries;
-    VC_CALL(set_device(device_id));
+    SECEDO_CALL(set_device(device_id));
     if (!n_records || (!!d_id_base16 == !!d_id_base32) || (capacity && !records))
         return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
     Calls calls;
-    VC_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, d_clusters,
+    SECEDO_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, d_clusters,
                       n_clusters_entries, d_locus_ref, chr_locus_end, hetero_prior, theta, capacity, d_mismatch,
                       d_loci, &calls, static_cast<hipStream_t>(stream)));
     *n_records = calls.total;
@@ -738,20 +694,20 @@ int secedo_variant_calls_device(int device_id, const uint32_t *d_chr_locus_off, 
 int secedo_variant_genotypes_device(int device_id, const uint16_t *counts, uint32_t n,
                                     int likely_homozygous_total, double hetero_prior, double theta,
                                     uint8_t *homozygous, uint8_t *genotype) {
-    VC_CALL(set_device(device_id));
+    SECEDO_CALL(set_device(device_id));
     if (n == 0) return SECEDO_OK;
     const std::vector<double> thr = threshold_table(theta);
     Buf b_c, b_t, b_h, b_g;
-    VC_TRY(b_c.alloc((size_t)n * 8));
-    VC_TRY(b_t.alloc(thr.size() * sizeof(double)));
-    VC_TRY(b_h.alloc(n));
-    VC_TRY(b_g.alloc(n));
-    VC_TRY(hipMemcpy(b_c.p, counts, (size_t)n * 8, hipMemcpyHostToDevice));
-    VC_TRY(hipMemcpy(b_t.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice));
-    VC_TRY(secedo::variant::genotypes(b_c.as<uint16_t>(), n, likely_homozygous_total, b_t.as<double>(),
+    SECEDO_TRY(b_c.alloc((size_t)n * 8));
+    SECEDO_TRY(b_t.alloc(thr.size() * sizeof(double)));
+    SECEDO_TRY(b_h.alloc(n));
+    SECEDO_TRY(b_g.alloc(n));
+    SECEDO_TRY(hipMemcpy(b_c.p, counts, (size_t)n * 8, hipMemcpyHostToDevice));
+    SECEDO_TRY(hipMemcpy(b_t.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice));
+    SECEDO_TRY(secedo::variant::genotypes(b_c.as<uint16_t>(), n, likely_homozygous_total, b_t.as<double>(),
                                       host_logs(hetero_prior, theta), b_h.as<uint8_t>(), b_g.as<uint8_t>(), 0));
-    VC_TRY(hipMemcpy(homozygous, b_h.p, n, hipMemcpyDeviceToHost));
-    VC_TRY(hipMemcpy(genotype, b_g.p, n, hipMemcpyDeviceToHost));
+    SECEDO_TRY(hipMemcpy(homozygous, b_h.p, n, hipMemcpyDeviceToHost));
+    SECEDO_TRY(hipMemcpy(genotype, b_g.p, n, hipMemcpyDeviceToHost));
     return SECEDO_OK;
 }
 
@@ -761,31 +717,28 @@ int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_
                            const char *reference_genome, const char *map_file, double hetero_prior, double theta,
                            const char *out_dir, secedo_variant_times *times) {
     bool done;
-    VC_CALL(begin_calling(n, reference_genome, out_dir, &done));
+    SECEDO_CALL(begin_calling(n, reference_genome, out_dir, &done));
     if (done) return SECEDO_OK;
     if (!chr_locus_off || !clusters || (!!id_base16 == !!id_base32 && chr_locus_off[n_chr] > 0))
         return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
-    VC_CALL(set_device(device_id));
+    SECEDO_CALL(set_device(device_id));
     Clock::time_point t0 = Clock::now();
     const uint32_t n_loci = chr_locus_off[n_chr];
     const uint64_t n_entries = locus_entry_off[n_loci];
     const size_t idb_bytes = (size_t)n_entries * (id_base16 ? 2 : 4);
-    hipStream_t s;
-    VC_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard {
-        hipStream_t s;
-        ~StreamGuard() { (void)hipStreamDestroy(s); }
-    } guard{s};
+    StreamGuard guard;
+    SECEDO_TRY(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    const hipStream_t s = guard.s;
     Buf b_chr, b_off, b_idb;
-    VC_TRY(b_chr.alloc(((size_t)n_chr + 1) * 4));
-    VC_TRY(b_off.alloc(((size_t)n_loci + 1) * 8));
-    VC_TRY(b_idb.alloc(idb_bytes));
-    VC_TRY(hipMemcpyAsync(b_chr.p, chr_locus_off, ((size_t)n_chr + 1) * 4, hipMemcpyHostToDevice, s));
-    VC_TRY(hipMemcpyAsync(b_off.p, locus_entry_off, ((size_t)n_loci + 1) * 8, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(b_chr.alloc(((size_t)n_chr + 1) * 4));
+    SECEDO_TRY(b_off.alloc(((size_t)n_loci + 1) * 8));
+    SECEDO_TRY(b_idb.alloc(idb_bytes));
+    SECEDO_TRY(hipMemcpyAsync(b_chr.p, chr_locus_off, ((size_t)n_chr + 1) * 4, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(b_off.p, locus_entry_off, ((size_t)n_loci + 1) * 8, hipMemcpyHostToDevice, s));
     if (idb_bytes)
-        VC_TRY(hipMemcpyAsync(b_idb.p, id_base16 ? (const void *)id_base16 : (const void *)id_base32, idb_bytes,
+        SECEDO_TRY(hipMemcpyAsync(b_idb.p, id_base16 ? (const void *)id_base16 : (const void *)id_base32, idb_bytes,
                               hipMemcpyHostToDevice, s));
-    const double upload_ms = ms_since(t0);
+    const double upload_ms = ms_lap(t0);
     return calling(device_id, b_chr.as<uint32_t>(), chr_locus_off, n_chr, locus_pos, b_off.as<uint64_t>(),
                    id_base16 ? b_idb.as<uint16_t>() : nullptr, id_base16 ? nullptr : b_idb.as<uint32_t>(), n_loci,
                    clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times, s, upload_ms);
@@ -799,20 +752,20 @@ int secedo_variant_calling_device(int device_id, const uint32_t *d_chr_locus_off
                                   double theta, const char *out_dir, secedo_variant_times *times, void *stream) {
     (void)n_entries;
     bool done;
-    VC_CALL(begin_calling(n, reference_genome, out_dir, &done));
+    SECEDO_CALL(begin_calling(n, reference_genome, out_dir, &done));
     if (done) return SECEDO_OK;
     if (!clusters || (!!d_id_base16 == !!d_id_base32 && n_loci > 0))
         return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
-    VC_CALL(set_device(device_id));
+    SECEDO_CALL(set_device(device_id));
     hipStream_t s = static_cast<hipStream_t>(stream);
     Clock::time_point t0 = Clock::now();
     std::vector<uint32_t> chr_off((size_t)n_chr + 1), pos(n_loci);
-    VC_TRY(hipMemcpyAsync(chr_off.data(), d_chr_locus_off, ((size_t)n_chr + 1) * 4, hipMemcpyDeviceToHost, s));
-    if (n_loci) VC_TRY(hipMemcpyAsync(pos.data(), d_locus_pos, (size_t)n_loci * 4, hipMemcpyDeviceToHost, s));
-    VC_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(hipMemcpyAsync(chr_off.data(), d_chr_locus_off, ((size_t)n_chr + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (n_loci) SECEDO_TRY(hipMemcpyAsync(pos.data(), d_locus_pos, (size_t)n_loci * 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
     if (chr_off[0] != 0 || chr_off[n_chr] != n_loci)
         return fail(SECEDO_E_INVALID_ARG, "chr_locus_off must run from 0 to n_loci");
-    const double download_ms = ms_since(t0);
+    const double download_ms = ms_lap(t0);
     return calling(device_id, d_chr_locus_off, chr_off.data(), n_chr, pos.data(), d_locus_entry_off, d_id_base16,
                    d_id_base32, n_loci, clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times,
                    s, download_ms);

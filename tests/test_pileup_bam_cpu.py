@@ -2,7 +2,9 @@
 (tests/pileup_bam_ref.py) against every case of the reference's tests/test_pileup.cpp on its own fixtures, the
 host-only BAM scan of libsecedo_bam.so on the fixtures and on tests/bam_writer.py output, and the argument
 handling of the pileup CLI."""
+import gzip
 import os
+import struct
 
 import numpy as np
 import pytest
@@ -111,6 +113,31 @@ def test_scan_unsorted_and_corrupt(tmp_path):
     bw.write_bam(path, [("1", 100)], recs)
     s = bam_pileup.bam_scan(path)
     assert not s["sorted"] and s["n_records"] == 2
+    # a larger unsorted file (three references, an unmapped record first, more than one block): every count is
+    # what the same records give in sorted order
+    srt = bw.synthetic_set(tmp_path, n_cells=1, pairs_per_cell=400, n_refs=3, seed=5)[0]
+    raw = gzip.decompress(open(srt, "rb").read())
+    offs, o = [], 8 + struct.unpack_from("<i", raw, 4)[0]
+    for _ in range(struct.unpack_from("<i", raw, o)[0]):
+        o += 8 + struct.unpack_from("<i", raw, o + 4)[0]
+    o += 4
+    first = o
+    while o < len(raw):
+        offs.append(o)
+        o += 4 + struct.unpack_from("<i", raw, o)[0]
+    body = b"".join(raw[a:b] for a, b in reversed(list(zip(offs, offs[1:] + [len(raw)]))))
+    rev = str(tmp_path / "rev.bam")
+    open(rev, "wb").write(bw.bgzf(raw[:first] + body))
+    want, got = bam_pileup.bam_scan(srt), bam_pileup.bam_scan(rev)
+    assert want["sorted"] and not got["sorted"] and got["n_unmapped"] == 1 and got["n_blocks"] > 3
+    for k in ("n_ref", "n_records", "n_unmapped", "inflated_bytes", "l_text"):
+        assert got[k] == want[k], k
+    assert list(got["records_per_ref"]) == list(want["records_per_ref"])
+    # unsorted and cut inside its last record: refused
+    cut = str(tmp_path / "cut.bam")
+    open(cut, "wb").write(bw.bgzf((raw[:first] + body)[:-7]))
+    with pytest.raises(secedo_amd.SecedoError):
+        bam_pileup.bam_scan(cut)
     data = bytearray(open(path, "rb").read())
     data[30] ^= 0xFF  # inside the first block's deflate data
     bad = str(tmp_path / "bad.bam")
