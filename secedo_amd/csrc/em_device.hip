@@ -12,6 +12,7 @@
 // HBM-bound: 6 B per entry for the centres + 4 B per entry for the sums per iteration.
 #include "secedo_em.h"
 #include "secedo_simmat.h"
+#include "host_util.hpp"
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -24,28 +25,10 @@
 #include <string>
 #include <vector>
 
-namespace secedo {
-int api_fail(int code, const std::string &msg);  // simmat_api.cpp
-}
-
 namespace {
 
-#define EM_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess)                                                                         \
-            return secedo::api_fail(SECEDO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-struct Buf {
-    void *p = nullptr;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <class T>
-    T *as() const { return static_cast<T *>(p); }
-};
+using secedo::host::Buf;
+using secedo::host::fail;  // the library's one error string: secedo_simmat_last_error()
 
 // Scratch of one refinement: one allocation, carved up. The reference refines once per sub-cluster of
 // its recursion (spectral_clustering.cpp:425-426), and hipMalloc + hipFree of nine buffers cost more than
@@ -245,24 +228,24 @@ int bits_for(uint32_t max_value) {
 int refine(int device_id, const uint64_t *d_off, uint32_t n_loci, uint64_t n_entries, const uint16_t *d_b16,
            const uint32_t *d_b32, const uint32_t *d_id_to_pos, uint32_t n_groups, double theta, double *d_prob,
            uint32_t n_cells, uint32_t max_iterations, uint32_t *iterations, hipStream_t stream) {
-    if (!d_prob || (!d_off && n_loci)) return secedo::api_fail(SECEDO_E_INVALID_ARG, "null argument");
+    if (!d_prob || (!d_off && n_loci)) return fail(SECEDO_E_INVALID_ARG, "null argument");
     if ((d_b16 != nullptr) == (d_b32 != nullptr) && n_entries)
-        return secedo::api_fail(SECEDO_E_INVALID_ARG, "exactly one of id_base16 / id_base32 must be given");
-    if (n_cells == 0) return secedo::api_fail(SECEDO_E_INVALID_ARG, "prob_cluster_b is empty");
+        return fail(SECEDO_E_INVALID_ARG, "exactly one of id_base16 / id_base32 must be given");
+    if (n_cells == 0) return fail(SECEDO_E_INVALID_ARG, "prob_cluster_b is empty");
     if (n_entries >= (1ull << 31) || n_loci >= (1u << 30))
-        return secedo::api_fail(SECEDO_E_LIMIT, "pileup too large for the EM refinement (2^31 entries, 2^30 loci)");
+        return fail(SECEDO_E_LIMIT, "pileup too large for the EM refinement (2^31 entries, 2^30 loci)");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return secedo::api_fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the EM refinement has no CPU fallback");
-    if (device_id < 0 || device_id >= n_dev) return secedo::api_fail(SECEDO_E_NO_DEVICE, "device id out of range");
-    EM_TRY(hipSetDevice(device_id));
+        return fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the EM refinement has no CPU fallback");
+    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_NO_DEVICE, "device id out of range");
+    SECEDO_TRY(hipSetDevice(device_id));
     if (max_iterations == 0) max_iterations = 1000;
     const uint32_t E = (uint32_t)n_entries;
 
     // sizes first (the sort's temporary storage is a query), then one allocation carved up
     size_t sort_tmp = 0;
     if (E)
-        EM_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+        SECEDO_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                                   (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)E, 0,
                                                   bits_for(n_cells - 1), stream));
     size_t total = 0;
@@ -276,7 +259,7 @@ int refine(int device_id, const uint64_t *d_off, uint32_t n_loci, uint64_t n_ent
                  o_centres = carve((size_t)std::max(n_loci, 1u) * 8 * sizeof(double)),
                  o_ll = carve((size_t)n_cells * 2 * sizeof(double)), o_flags = carve(sizeof(Flags));
     ArenaLease lease(device_id);
-    EM_TRY(lease.a->ensure(total));
+    SECEDO_TRY(lease.a->ensure(total));
     unsigned char *base = static_cast<unsigned char *>(lease.a->p);
     uint32_t *key_a = reinterpret_cast<uint32_t *>(base + o_key_a), *key_b = reinterpret_cast<uint32_t *>(base + o_key_b);
     uint32_t *val_a = reinterpret_cast<uint32_t *>(base + o_val_a), *val_b = reinterpret_cast<uint32_t *>(base + o_val_b);
@@ -284,34 +267,34 @@ int refine(int device_id, const uint64_t *d_off, uint32_t n_loci, uint64_t n_ent
     double *centres = reinterpret_cast<double *>(base + o_centres);
     Flags *flags = reinterpret_cast<Flags *>(base + o_flags);
     double *ll_a = reinterpret_cast<double *>(base + o_ll), *ll_b = ll_a + n_cells;
-    EM_TRY(hipMemsetAsync(flags, 0, sizeof(Flags), stream));
-    EM_TRY(hipMemsetAsync(ll_a, 0, (size_t)n_cells * 2 * sizeof(double), stream));  // :130-131
+    SECEDO_TRY(hipMemsetAsync(flags, 0, sizeof(Flags), stream));
+    SECEDO_TRY(hipMemsetAsync(ll_a, 0, (size_t)n_cells * 2 * sizeof(double), stream));  // :130-131
     const uint32_t locus_grid = std::max(1u, std::min((n_loci + 3u) / 4u, 16384u));
     const uint32_t *sorted_val = val_a;
     if (E) {
         hipLaunchKernelGGL(k_em_keys, dim3(locus_grid), dim3(256), 0, stream, d_off, n_loci, d_b16, d_b32, d_id_to_pos,
                            n_groups, n_cells, key_a, val_a, flags);
-        EM_TRY(hipcub::DeviceRadixSort::SortPairs(base + o_cub, sort_tmp, key_a, key_b, val_a, val_b, (int)E, 0,
+        SECEDO_TRY(hipcub::DeviceRadixSort::SortPairs(base + o_cub, sort_tmp, key_a, key_b, val_a, val_b, (int)E, 0,
                                                   bits_for(n_cells - 1), stream));
         sorted_val = val_b;
     }
     hipLaunchKernelGGL(k_em_cell_offsets, dim3((n_cells + 256) / 256), dim3(256), 0, stream, key_b, E, n_cells, cell_off);
     Flags h{};
-    EM_TRY(hipMemcpyAsync(&h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
-    EM_TRY(hipStreamSynchronize(stream));
+    SECEDO_TRY(hipMemcpyAsync(&h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
+    SECEDO_TRY(hipStreamSynchronize(stream));
     if (h.error == 1)
-        return secedo::api_fail(SECEDO_E_INVALID_ARG,
+        return fail(SECEDO_E_INVALID_ARG,
                                 "a group id is >= n_cells: the reference indexes prob_cluster_b with the group id "
                                 "(expectation_maximization.cpp:24) and would read out of bounds");
     if (h.error == 2)
-        return secedo::api_fail(SECEDO_E_INVALID_ARG, "a group id is outside id_to_pos or maps outside prob_cluster_b");
+        return fail(SECEDO_E_INVALID_ARG, "a group id is outside id_to_pos or maps outside prob_cluster_b");
 
     // Iterations are launched four at a time: a kernel returns at once when an earlier E-step of its
     // batch has settled, so the host reads the flags (a synchronisation, ~40 us) once per batch.
     uint32_t it = 0;
     for (;;) {
         if (it == max_iterations)
-            return secedo::api_fail(SECEDO_E_LIMIT, "the EM refinement did not settle within max_iterations");
+            return fail(SECEDO_E_LIMIT, "the EM refinement did not settle within max_iterations");
         const uint32_t batch = std::min(4u, max_iterations - it);
         for (uint32_t k = 0; k < batch; ++k) {
             if (n_loci)
@@ -321,12 +304,12 @@ int refine(int device_id, const uint64_t *d_off, uint32_t n_loci, uint64_t n_ent
                                n_cells, centres, ll_a, ll_b, flags);
             hipLaunchKernelGGL(k_em_estep, dim3(1), dim3(1024), 0, stream, n_cells, ll_a, ll_b, d_prob, flags);
         }
-        EM_TRY(hipMemcpyAsync(&h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
-        EM_TRY(hipStreamSynchronize(stream));
+        SECEDO_TRY(hipMemcpyAsync(&h, flags, sizeof(h), hipMemcpyDeviceToHost, stream));
+        SECEDO_TRY(hipStreamSynchronize(stream));
         it = h.iterations;
         if (h.done) break;
     }
-    EM_TRY(hipGetLastError());
+    SECEDO_TRY(hipGetLastError());
     if (iterations) *iterations = it;
     return SECEDO_OK;
 }
@@ -354,30 +337,30 @@ int secedo_em_refine_device(int device_id, const uint64_t *d_locus_entry_off, ui
 int secedo_em_refine(int device_id, const uint64_t *locus_entry_off, uint32_t n_loci, const uint16_t *id_base16,
                      const uint32_t *id_base32, const uint32_t *id_to_pos, uint32_t n_groups, double theta,
                      double *prob_cluster_b, uint32_t n_cells, uint32_t max_iterations, uint32_t *iterations) {
-    if (!prob_cluster_b || (!locus_entry_off && n_loci)) return secedo::api_fail(SECEDO_E_INVALID_ARG, "null argument");
+    if (!prob_cluster_b || (!locus_entry_off && n_loci)) return fail(SECEDO_E_INVALID_ARG, "null argument");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return secedo::api_fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the EM refinement has no CPU fallback");
-    if (device_id < 0 || device_id >= n_dev) return secedo::api_fail(SECEDO_E_NO_DEVICE, "device id out of range");
-    EM_TRY(hipSetDevice(device_id));
+        return fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the EM refinement has no CPU fallback");
+    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_NO_DEVICE, "device id out of range");
+    SECEDO_TRY(hipSetDevice(device_id));
     const uint64_t E = n_loci ? locus_entry_off[n_loci] : 0;
     if (E && (id_base16 != nullptr) == (id_base32 != nullptr))
-        return secedo::api_fail(SECEDO_E_INVALID_ARG, "exactly one of id_base16 / id_base32 must be given");
+        return fail(SECEDO_E_INVALID_ARG, "exactly one of id_base16 / id_base32 must be given");
     Buf off, b, i2p, prob;
-    EM_TRY(off.alloc(((size_t)n_loci + 1) * 8));
-    EM_TRY(b.alloc(E * (id_base16 ? 2 : 4)));
-    EM_TRY(i2p.alloc((size_t)n_groups * 4));
-    EM_TRY(prob.alloc((size_t)n_cells * 8));
-    if (n_loci) EM_TRY(hipMemcpy(off.p, locus_entry_off, ((size_t)n_loci + 1) * 8, hipMemcpyHostToDevice));
-    if (E) EM_TRY(hipMemcpy(b.p, id_base16 ? (const void *)id_base16 : (const void *)id_base32,
+    SECEDO_TRY(off.alloc(((size_t)n_loci + 1) * 8));
+    SECEDO_TRY(b.alloc(E * (id_base16 ? 2 : 4)));
+    SECEDO_TRY(i2p.alloc((size_t)n_groups * 4));
+    SECEDO_TRY(prob.alloc((size_t)n_cells * 8));
+    if (n_loci) SECEDO_TRY(hipMemcpy(off.p, locus_entry_off, ((size_t)n_loci + 1) * 8, hipMemcpyHostToDevice));
+    if (E) SECEDO_TRY(hipMemcpy(b.p, id_base16 ? (const void *)id_base16 : (const void *)id_base32,
                             E * (id_base16 ? 2 : 4), hipMemcpyHostToDevice));
-    if (n_groups) EM_TRY(hipMemcpy(i2p.p, id_to_pos, (size_t)n_groups * 4, hipMemcpyHostToDevice));
-    if (n_cells) EM_TRY(hipMemcpy(prob.p, prob_cluster_b, (size_t)n_cells * 8, hipMemcpyHostToDevice));
+    if (n_groups) SECEDO_TRY(hipMemcpy(i2p.p, id_to_pos, (size_t)n_groups * 4, hipMemcpyHostToDevice));
+    if (n_cells) SECEDO_TRY(hipMemcpy(prob.p, prob_cluster_b, (size_t)n_cells * 8, hipMemcpyHostToDevice));
     const int rc = refine(device_id, off.as<uint64_t>(), n_loci, E, id_base16 ? b.as<uint16_t>() : nullptr,
                           id_base16 ? nullptr : b.as<uint32_t>(), i2p.as<uint32_t>(), n_groups, theta,
                           prob.as<double>(), n_cells, max_iterations, iterations, nullptr);
     if (rc) return rc;
-    EM_TRY(hipMemcpy(prob_cluster_b, prob.p, (size_t)n_cells * 8, hipMemcpyDeviceToHost));
+    SECEDO_TRY(hipMemcpy(prob_cluster_b, prob.p, (size_t)n_cells * 8, hipMemcpyDeviceToHost));
     return SECEDO_OK;
 }
 

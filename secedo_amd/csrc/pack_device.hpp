@@ -33,7 +33,7 @@ struct DeviceFlatPileup {
     uint64_t n_entries = 0;
 };
 
-// Growable device allocation owned by the caller (simmat_api.cpp's handle)
+// Growable device allocation owned by the caller (the handle of simmat_handle.hpp)
 int poison_level();  // SECEDO_POISON, a debugging aid (pack_device.hip)
 
 struct DeviceArena {
@@ -41,6 +41,12 @@ struct DeviceArena {
     size_t bytes = 0;
     ~DeviceArena();
     hipError_t ensure(size_t n);
+    template <class T>
+    __attribute__((visibility("hidden"))) hipError_t upload(const std::vector<T> &v) {  // synchronous
+        hipError_t e = ensure(v.size() * sizeof(T));
+        if (e != hipSuccess || v.empty()) return e;
+        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
     template <class T>
     T *as() const { return static_cast<T *>(p); }
 };

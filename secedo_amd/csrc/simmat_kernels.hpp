@@ -41,7 +41,7 @@ struct SlowPathArgs {
     int scale_log2;
     // Read pairs that share more than 128 loci (beyond the table): with a list here the kernels add NOTHING for the
     // joint term of such a pair and note {cell, cell, x_s, x_d} instead; the host evaluates the term as the reference
-    // does and adds it afterwards (simmat_api.cpp). nullptr: the closed form on the device (SECEDO_LLR_EXACT).
+    // does and adds it afterwards (simmat_accumulate.cpp). nullptr: the closed form on the device (SECEDO_LLR_EXACT).
     uint4 *beyond_list = nullptr;
     uint32_t *beyond_count = nullptr;   // entries noted (may exceed the capacity: then the list is incomplete)
     uint32_t beyond_cap = 0;

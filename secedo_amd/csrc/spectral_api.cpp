@@ -27,7 +27,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -35,13 +34,9 @@
 #include <string>
 #include <vector>
 
-namespace secedo {
-int api_fail(int code, const std::string &msg);  // simmat_api.cpp: sets secedo_simmat_last_error()
-}
-
 namespace {
 
-using secedo::host::Buf;
+using namespace secedo::host;  // fail() sets the library's one error string: secedo_simmat_last_error()
 using secedo::spectral::kBlockWidth;
 constexpr uint32_t BW = kBlockWidth;
 // Krylov blocks per restart cycle, set per solve (cycle_blocks): a larger space needs fewer matrix passes in
@@ -56,13 +51,6 @@ uint32_t cycle_blocks(uint32_t n) {
     }
     return n < 2000u ? 6u : n < 12000u ? 7u : 8u;
 }
-
-#define SP_TRY(expr)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess)                                                                            \
-            return secedo::api_fail(SECEDO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));    \
-    } while (0)
 
 struct Solver {
     uint32_t n = 0, row_begin = 0, n_rows = 0;
@@ -84,24 +72,24 @@ struct Solver {
         allreduce = fn;
         allreduce_ctx = ctx;
         blk_stride = (size_t)n * BW;
-        SP_TRY(sums.alloc((size_t)n * 8));
-        SP_TRY(Ypart.alloc(blk_stride * 8));
-        SP_TRY(s.alloc((size_t)n * 8));
-        SP_TRY(root.alloc((size_t)n * 8));
-        SP_TRY(Q.alloc((kCycleBlocks + 1) * blk_stride * 8));
-        SP_TRY(W.alloc(blk_stride * 8));
-        SP_TRY(W2.alloc(blk_stride * 8));
-        SP_TRY(Wtmp.alloc(blk_stride * 8));
-        SP_TRY(Z.alloc(((size_t)pad16(n) + 64) * BW * 8));
-        SP_TRY(P.alloc((size_t)product_segments(n, n_rows) * pad16(n) * BW * 8));
-        SP_TRY(Gp.alloc((size_t)gram_chunks(n) * (kCycleBlocks + 1) * BW * BW * 8));
-        SP_TRY(G.alloc((size_t)(kCycleBlocks + 1) * BW * BW * 8));
-        SP_TRY(M.alloc((size_t)(kCycleBlocks + 1) * BW * BW * 8));
+        SECEDO_TRY(sums.alloc((size_t)n * 8));
+        SECEDO_TRY(Ypart.alloc(blk_stride * 8));
+        SECEDO_TRY(s.alloc((size_t)n * 8));
+        SECEDO_TRY(root.alloc((size_t)n * 8));
+        SECEDO_TRY(Q.alloc((kCycleBlocks + 1) * blk_stride * 8));
+        SECEDO_TRY(W.alloc(blk_stride * 8));
+        SECEDO_TRY(W2.alloc(blk_stride * 8));
+        SECEDO_TRY(Wtmp.alloc(blk_stride * 8));
+        SECEDO_TRY(Z.alloc(((size_t)pad16(n) + 64) * BW * 8));
+        SECEDO_TRY(P.alloc((size_t)product_segments(n, n_rows) * pad16(n) * BW * 8));
+        SECEDO_TRY(Gp.alloc((size_t)gram_chunks(n) * (kCycleBlocks + 1) * BW * BW * 8));
+        SECEDO_TRY(G.alloc((size_t)(kCycleBlocks + 1) * BW * BW * 8));
+        SECEDO_TRY(M.alloc((size_t)(kCycleBlocks + 1) * BW * BW * 8));
         // Gram-Schmidt coefficients of a whole cycle (6 steps x 2 passes x up to 6 blocks): read back once
-        SP_TRY(Gall.alloc((size_t)kCycleBlocks * 2 * kCycleBlocks * BW * BW * 8));
-        SP_TRY(Rfirst.alloc((size_t)BW * BW * 8));
-        SP_TRY(Rblk.alloc((size_t)(kCycleBlocks + 1) * BW * BW * 8));
-        SP_TRY(alive_dev.alloc((size_t)(kCycleBlocks + 1) * BW * 4));
+        SECEDO_TRY(Gall.alloc((size_t)kCycleBlocks * 2 * kCycleBlocks * BW * BW * 8));
+        SECEDO_TRY(Rfirst.alloc((size_t)BW * BW * 8));
+        SECEDO_TRY(Rblk.alloc((size_t)(kCycleBlocks + 1) * BW * BW * 8));
+        SECEDO_TRY(alive_dev.alloc((size_t)(kCycleBlocks + 1) * BW * 4));
         return SECEDO_OK;
     }
     double *block(uint32_t b) const { return Q.as<double>() + b * blk_stride; }
@@ -109,33 +97,33 @@ struct Solver {
     int reduce_ranks(double *buf, size_t count) {
         if (!allreduce) return SECEDO_OK;
         if (allreduce(allreduce_ctx, buf, count, stream) != 0)
-            return secedo::api_fail(SECEDO_E_STATE, "the all-reduce callback of the spectral step failed");
+            return fail(SECEDO_E_STATE, "the all-reduce callback of the spectral step failed");
         return SECEDO_OK;
     }
     // D^-1/2 from the row sums of the whole matrix
     int scales() {
         using namespace secedo::spectral;
-        SP_TRY(hipMemsetAsync(sums.p, 0, (size_t)n * 8, stream));
-        SP_TRY(row_sums(A, n, row_begin, n_rows, sums.as<double>(), stream));
+        SECEDO_TRY(hipMemsetAsync(sums.p, 0, (size_t)n * 8, stream));
+        SECEDO_TRY(row_sums(A, n, row_begin, n_rows, sums.as<double>(), stream));
         const int rc = reduce_ranks(sums.as<double>(), n);
         if (rc) return rc;
-        SP_TRY(scale_from_sums(n, sums.as<double>(), s.as<double>(), root.as<double>(), stream));
+        SECEDO_TRY(scale_from_sums(n, sums.as<double>(), s.as<double>(), root.as<double>(), stream));
         return SECEDO_OK;
     }
     // y = T x
     int product(const double *x, double *y) {
         using namespace secedo::spectral;
         // (one rank: the segments' sum and the finishing step in one kernel)
-        SP_TRY(product_partial(A, n, row_begin, n_rows, s.as<double>(), x, Z.as<double>(), P.as<double>(), allreduce ? Ypart.as<double>() : nullptr,
+        SECEDO_TRY(product_partial(A, n, row_begin, n_rows, s.as<double>(), x, Z.as<double>(), P.as<double>(), allreduce ? Ypart.as<double>() : nullptr,
                                allreduce ? nullptr : y, stream));
         if (!allreduce) return SECEDO_OK;
         const int rc = reduce_ranks(Ypart.as<double>(), blk_stride);
         if (rc) return rc;
-        SP_TRY(product_finish(n, s.as<double>(), x, Ypart.as<double>(), y, stream));
+        SECEDO_TRY(product_finish(n, s.as<double>(), x, Ypart.as<double>(), y, stream));
         return SECEDO_OK;
     }
     int upload_small(const std::vector<double> &m) {
-        SP_TRY(hipMemcpyAsync(M.as<double>(), m.data(), m.size() * 8, hipMemcpyHostToDevice, stream));
+        SECEDO_TRY(hipMemcpyAsync(M.as<double>(), m.data(), m.size() * 8, hipMemcpyHostToDevice, stream));
         return SECEDO_OK;
     }
     // Q[blk] = orthonormalised src (Cholesky QR, twice, through Wtmp; src keeps its contents). Nothing comes back to the
@@ -146,13 +134,13 @@ struct Solver {
         double *dst = block(blk);
         double *R = Rblk.as<double>() + (size_t)blk * BW * BW;
         uint32_t *alive = alive_dev.as<uint32_t>() + (size_t)blk * BW;
-        SP_TRY(gram(n, src, blk_stride, 1, src, Gp.as<double>(), G.as<double>(), stream));
-        SP_TRY(cholesky_drop(G.as<double>(), nullptr, M.as<double>(), Rfirst.as<double>(), nullptr, stream));
+        SECEDO_TRY(gram(n, src, blk_stride, 1, src, Gp.as<double>(), G.as<double>(), stream));
+        SECEDO_TRY(cholesky_drop(G.as<double>(), nullptr, M.as<double>(), Rfirst.as<double>(), nullptr, stream));
         double *tmp = Wtmp.as<double>();
-        SP_TRY(block_combine(n, src, blk_stride, 1, M.as<double>(), 1.0, 0.0, tmp, stream));
-        SP_TRY(gram(n, tmp, blk_stride, 1, tmp, Gp.as<double>(), G.as<double>(), stream));
-        SP_TRY(cholesky_drop(G.as<double>(), Rfirst.as<double>(), M.as<double>(), R, alive, stream));
-        SP_TRY(block_combine(n, tmp, blk_stride, 1, M.as<double>(), 1.0, 0.0, dst, stream));
+        SECEDO_TRY(block_combine(n, src, blk_stride, 1, M.as<double>(), 1.0, 0.0, tmp, stream));
+        SECEDO_TRY(gram(n, tmp, blk_stride, 1, tmp, Gp.as<double>(), G.as<double>(), stream));
+        SECEDO_TRY(cholesky_drop(G.as<double>(), Rfirst.as<double>(), M.as<double>(), R, alive, stream));
+        SECEDO_TRY(block_combine(n, tmp, blk_stride, 1, M.as<double>(), 1.0, 0.0, dst, stream));
         return SECEDO_OK;
     }
 };
@@ -161,21 +149,21 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
           uint32_t n_vectors, double tol, uint32_t max_cycles, double *eigenvalues, double *d_eigenvectors,
           secedo_spectral_info *info, secedo_allreduce_sum_fn allreduce, void *allreduce_ctx, hipStream_t stream) {
     using namespace secedo::spectral;
-    if ((!d_rows && n_rows) || !eigenvalues) return secedo::api_fail(SECEDO_E_INVALID_ARG, "null argument");
-    if ((uint64_t)row_begin + n_rows > n) return secedo::api_fail(SECEDO_E_INVALID_ARG, "row block outside the matrix");
+    if ((!d_rows && n_rows) || !eigenvalues) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    if ((uint64_t)row_begin + n_rows > n) return fail(SECEDO_E_INVALID_ARG, "row block outside the matrix");
     if (!allreduce && n_rows != n)
-        return secedo::api_fail(SECEDO_E_INVALID_ARG, "a row block needs the all-reduce callback of the other ranks");
-    if (n == 0) return secedo::api_fail(SECEDO_E_INVALID_ARG, "the similarity matrix is empty");
+        return fail(SECEDO_E_INVALID_ARG, "a row block needs the all-reduce callback of the other ranks");
+    if (n == 0) return fail(SECEDO_E_INVALID_ARG, "the similarity matrix is empty");
     if (n_values == 0 || n_values > std::min<uint32_t>(n, SECEDO_SPECTRAL_MAX_VALUES))
-        return secedo::api_fail(SECEDO_E_INVALID_ARG, "n_values must be in [1, min(n, 32)]");
-    if (n_vectors > n_values) return secedo::api_fail(SECEDO_E_INVALID_ARG, "n_vectors must not exceed n_values");
-    if (n_vectors && !d_eigenvectors) return secedo::api_fail(SECEDO_E_INVALID_ARG, "d_eigenvectors is null");
-    if ((uint64_t)n * n >= (1ull << 40)) return secedo::api_fail(SECEDO_E_LIMIT, "matrix too large");
+        return fail(SECEDO_E_INVALID_ARG, "n_values must be in [1, min(n, 32)]");
+    if (n_vectors > n_values) return fail(SECEDO_E_INVALID_ARG, "n_vectors must not exceed n_values");
+    if (n_vectors && !d_eigenvectors) return fail(SECEDO_E_INVALID_ARG, "d_eigenvectors is null");
+    if ((uint64_t)n * n >= (1ull << 40)) return fail(SECEDO_E_LIMIT, "matrix too large");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return secedo::api_fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the spectral step has no CPU fallback");
-    if (device_id < 0 || device_id >= n_dev) return secedo::api_fail(SECEDO_E_NO_DEVICE, "device id out of range");
-    SP_TRY(hipSetDevice(device_id));
+        return fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the spectral step has no CPU fallback");
+    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_NO_DEVICE, "device id out of range");
+    SECEDO_TRY(hipSetDevice(device_id));
     if (tol <= 0.0) tol = 1e-9;
     if (max_cycles == 0) max_cycles = 60;
     const double tol_values = std::max(tol, 1e-6);
@@ -185,7 +173,7 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
     int rc = sv.setup(d_rows, row_begin, n_rows, n, allreduce, allreduce_ctx, stream);
     if (rc) return rc;
     if ((rc = sv.scales())) return rc;
-    SP_TRY(init_block(n, sv.root.as<double>(), sv.W.as<double>(), stream));
+    SECEDO_TRY(init_block(n, sv.root.as<double>(), sv.W.as<double>(), stream));
     std::vector<double> R_last((size_t)BW * BW);
     std::vector<uint32_t> basis_alive((size_t)(kCycleBlocks + 1) * BW, 1);
     if ((rc = sv.orthonormalise(sv.W.as<double>(), 0))) return rc;
@@ -210,7 +198,7 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
     std::vector<uint32_t> top(BW);
     std::vector<double> res(BW, 0.0);
     double rr_seconds = 0.0;
-    const auto t_solve = std::chrono::steady_clock::now();
+    const Clock::time_point t_solve = Clock::now();
     for (uint32_t cycle = 0; cycle < max_cycles; ++cycle) {
         std::fill(H.begin(), H.end(), 0.0);
         for (uint32_t r = 0; r < kept * BW; ++r) H[(size_t)r * m + r] = theta_kept[r];
@@ -220,19 +208,19 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
             for (int pass = 0; pass < 2; ++pass) {  // classical Gram-Schmidt, twice
                 // the coefficients stay on the device; the host needs them only for the projection H
                 double *coef = sv.Gall.as<double>() + (size_t)(j * 2 + pass) * kCycleBlocks * BW * BW;
-                SP_TRY(gram(n, sv.Q.as<double>(), sv.blk_stride, j + 1, sv.W.as<double>(), sv.Gp.as<double>(), coef, stream));
-                SP_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, j + 1, coef, -1.0, 1.0, sv.W.as<double>(), stream));
+                SECEDO_TRY(gram(n, sv.Q.as<double>(), sv.blk_stride, j + 1, sv.W.as<double>(), sv.Gp.as<double>(), coef, stream));
+                SECEDO_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, j + 1, coef, -1.0, 1.0, sv.W.as<double>(), stream));
             }
             if ((rc = sv.orthonormalise(sv.W.as<double>(), j + 1))) return rc;
         }
         // The one read-back of the cycle: H[blk, j] = sum of the two passes' coefficients of step j, who
         // survived the orthonormalisations, and the R of the last step (for the residuals).
         g.resize((size_t)kCycleBlocks * 2 * kCycleBlocks * BW * BW);
-        SP_TRY(hipMemcpyAsync(g.data(), sv.Gall.as<double>(), g.size() * 8, hipMemcpyDeviceToHost, stream));
-        SP_TRY(hipMemcpyAsync(basis_alive.data(), sv.alive_dev.p, basis_alive.size() * 4, hipMemcpyDeviceToHost, stream));
-        SP_TRY(hipMemcpyAsync(R_last.data(), sv.Rblk.as<const double>() + (size_t)kCycleBlocks * BW * BW,
+        SECEDO_TRY(hipMemcpyAsync(g.data(), sv.Gall.as<double>(), g.size() * 8, hipMemcpyDeviceToHost, stream));
+        SECEDO_TRY(hipMemcpyAsync(basis_alive.data(), sv.alive_dev.p, basis_alive.size() * 4, hipMemcpyDeviceToHost, stream));
+        SECEDO_TRY(hipMemcpyAsync(R_last.data(), sv.Rblk.as<const double>() + (size_t)kCycleBlocks * BW * BW,
                               R_last.size() * 8, hipMemcpyDeviceToHost, stream));
-        SP_TRY(hipStreamSynchronize(stream));
+        SECEDO_TRY(hipStreamSynchronize(stream));
         for (uint32_t j = kept; j < kCycleBlocks; ++j)
             for (int pass = 0; pass < 2; ++pass)
                 for (uint32_t blk = 0; blk <= j; ++blk)
@@ -247,10 +235,10 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
         // a dropped basis column is a zero vector: keep its (zero) Ritz value below the spectrum of T
         for (uint32_t r = 0; r < m; ++r)
             if (!basis_alive[r]) H[(size_t)r * m + r] = -1.0;
-        const auto t_rr = std::chrono::steady_clock::now();
+        const Clock::time_point t_rr = Clock::now();
         if (!secedo::sym_eig_top((int)m, H, (int)ucols, theta, U, true))  // U: m x ucols, column k = k-th largest; only those values
-            return secedo::api_fail(SECEDO_E_LIMIT, "the projected eigenproblem did not converge");
-        rr_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_rr).count();
+            return fail(SECEDO_E_LIMIT, "the projected eigenproblem did not converge");
+        rr_seconds += 1e-3 * ms_since(t_rr);
         // the largest tau first; residual of a Ritz pair = || R_last u_last || (T V_j = sum_blk V_blk H_blk,j
         // + V_{j+1} R_j, so T y - theta y = V_6 R_5 u_last for y = V u)
         for (uint32_t k = 0; k < BW; ++k) top[k] = m - 1 - k;
@@ -276,7 +264,7 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
             std::fprintf(stderr, "[spectral] cycle %u:", cycle);
             for (uint32_t k = 0; k < n_values; ++k) std::fprintf(stderr, " %.1e", res[k]);
             std::fprintf(stderr, " | %.1f ms so far, %.1f ms of it in the projected eigenproblem\n",
-                         1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_solve).count(),
+                         ms_since(t_solve),
                          1e3 * rr_seconds);
         }
         // Ritz vectors of the best pairs: Y_q = V U[:, q-th 32 columns] (before any block is overwritten)
@@ -288,13 +276,13 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
                     for (uint32_t k = 0; k < BW; ++k)
                         coeff[((size_t)blk * BW + a) * BW + k] = U[(size_t)(blk * BW + a) * ucols + q * BW + k];
             if ((rc = sv.upload_small(coeff))) return rc;
-            SP_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, kCycleBlocks, sv.M.as<double>(), 1.0, 0.0,
+            SECEDO_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, kCycleBlocks, sv.M.as<double>(), 1.0, 0.0,
                                  q == 0 ? sv.W.as<double>() : sv.W2.as<double>(), stream));
         }
         if (last) {
             for (uint32_t k = 0; k < n_values; ++k) eigenvalues[k] = 2.0 * (1.0 - theta[top[k]]);
-            SP_TRY(write_vectors(n, sv.W.as<double>(), n_vectors, d_eigenvectors, stream));
-            SP_TRY(hipStreamSynchronize(stream));
+            SECEDO_TRY(write_vectors(n, sv.W.as<double>(), n_vectors, d_eigenvectors, stream));
+            SECEDO_TRY(hipStreamSynchronize(stream));
             break;
         }
         if ((rc = sv.orthonormalise(sv.W.as<double>(), 0))) return rc;
@@ -302,13 +290,13 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
         if (keep == 2u) {
             // second Ritz block: orthogonal to the first up to rounding; cleaned like every other block
             for (int pass = 0; pass < 2; ++pass) {
-                SP_TRY(gram(n, sv.Q.as<double>(), sv.blk_stride, 1, sv.W2.as<double>(), sv.Gp.as<double>(), sv.Gall.as<double>(), stream));
-                SP_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, 1, sv.Gall.as<double>(), -1.0, 1.0, sv.W2.as<double>(), stream));
+                SECEDO_TRY(gram(n, sv.Q.as<double>(), sv.blk_stride, 1, sv.W2.as<double>(), sv.Gp.as<double>(), sv.Gall.as<double>(), stream));
+                SECEDO_TRY(block_combine(n, sv.Q.as<double>(), sv.blk_stride, 1, sv.Gall.as<double>(), -1.0, 1.0, sv.W2.as<double>(), stream));
             }
             if ((rc = sv.orthonormalise(sv.W2.as<double>(), 1))) return rc;
             // the last Krylov block (and who is alive in it) continues as block 2
-            SP_TRY(hipMemcpyAsync(sv.block(2), sv.block(kCycleBlocks), sv.blk_stride * 8, hipMemcpyDeviceToDevice, stream));
-            SP_TRY(hipMemcpyAsync(sv.alive_dev.as<uint32_t>() + 2 * BW,
+            SECEDO_TRY(hipMemcpyAsync(sv.block(2), sv.block(kCycleBlocks), sv.blk_stride * 8, hipMemcpyDeviceToDevice, stream));
+            SECEDO_TRY(hipMemcpyAsync(sv.alive_dev.as<uint32_t>() + 2 * BW,
                                   sv.alive_dev.as<const uint32_t>() + (size_t)kCycleBlocks * BW, BW * 4,
                                   hipMemcpyDeviceToDevice, stream));
             kept = 2;
@@ -324,17 +312,17 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
 extern "C" {
 
 int secedo_laplacian_device(const double *d_similarity, uint32_t n, double *d_out, void *stream) {
-    if (!d_similarity || !d_out) return secedo::api_fail(SECEDO_E_INVALID_ARG, "null argument");
+    if (!d_similarity || !d_out) return fail(SECEDO_E_INVALID_ARG, "null argument");
     if (n == 0) return SECEDO_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     Buf s, root, sums;
-    SP_TRY(s.alloc((size_t)n * 8));
-    SP_TRY(root.alloc((size_t)n * 8));
-    SP_TRY(sums.alloc((size_t)n * 8));
-    SP_TRY(secedo::spectral::row_sums(d_similarity, n, 0, n, sums.as<double>(), st));
-    SP_TRY(secedo::spectral::scale_from_sums(n, sums.as<double>(), s.as<double>(), root.as<double>(), st));
-    SP_TRY(secedo::spectral::laplacian(d_similarity, s.as<double>(), n, d_out, st));
-    SP_TRY(hipStreamSynchronize(st));  // the scratch is freed on return
+    SECEDO_TRY(s.alloc((size_t)n * 8));
+    SECEDO_TRY(root.alloc((size_t)n * 8));
+    SECEDO_TRY(sums.alloc((size_t)n * 8));
+    SECEDO_TRY(secedo::spectral::row_sums(d_similarity, n, 0, n, sums.as<double>(), st));
+    SECEDO_TRY(secedo::spectral::scale_from_sums(n, sums.as<double>(), s.as<double>(), root.as<double>(), st));
+    SECEDO_TRY(secedo::spectral::laplacian(d_similarity, s.as<double>(), n, d_out, st));
+    SECEDO_TRY(hipStreamSynchronize(st));  // the scratch is freed on return
     return SECEDO_OK;
 }
 
@@ -357,21 +345,21 @@ int secedo_spectral_eigs_rows_device(int device_id, const double *d_rows, uint32
 int secedo_spectral_eigs(int device_id, const double *similarity, uint32_t n, uint32_t n_values,
                          uint32_t n_vectors, double tol, uint32_t max_cycles, double *eigenvalues,
                          double *eigenvectors, secedo_spectral_info *info) {
-    if (!similarity) return secedo::api_fail(SECEDO_E_INVALID_ARG, "similarity is null");
-    if (n_vectors && !eigenvectors) return secedo::api_fail(SECEDO_E_INVALID_ARG, "eigenvectors is null");
+    if (!similarity) return fail(SECEDO_E_INVALID_ARG, "similarity is null");
+    if (n_vectors && !eigenvectors) return fail(SECEDO_E_INVALID_ARG, "eigenvectors is null");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return secedo::api_fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the spectral step has no CPU fallback");
-    if (device_id < 0 || device_id >= n_dev) return secedo::api_fail(SECEDO_E_NO_DEVICE, "device id out of range");
-    SP_TRY(hipSetDevice(device_id));
+        return fail(SECEDO_E_NO_DEVICE, "no HIP device is visible: the spectral step has no CPU fallback");
+    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_NO_DEVICE, "device id out of range");
+    SECEDO_TRY(hipSetDevice(device_id));
     Buf a, v;
-    SP_TRY(a.alloc((size_t)n * n * 8));
-    SP_TRY(v.alloc((size_t)n * std::max<uint32_t>(n_vectors, 1) * 8));
-    SP_TRY(hipMemcpy(a.p, similarity, (size_t)n * n * 8, hipMemcpyHostToDevice));
+    SECEDO_TRY(a.alloc((size_t)n * n * 8));
+    SECEDO_TRY(v.alloc((size_t)n * std::max<uint32_t>(n_vectors, 1) * 8));
+    SECEDO_TRY(hipMemcpy(a.p, similarity, (size_t)n * n * 8, hipMemcpyHostToDevice));
     const int rc = solve(device_id, a.as<double>(), 0, n, n, n_values, n_vectors, tol, max_cycles, eigenvalues, v.as<double>(), info,
                          nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (n_vectors) SP_TRY(hipMemcpy(eigenvectors, v.p, (size_t)n * n_vectors * 8, hipMemcpyDeviceToHost));
+    if (n_vectors) SECEDO_TRY(hipMemcpy(eigenvectors, v.p, (size_t)n * n_vectors * 8, hipMemcpyDeviceToHost));
     return SECEDO_OK;
 }
 
