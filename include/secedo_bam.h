@@ -16,9 +16,11 @@
  * and walked in ranges of BGZF blocks (about 512 MiB inflated; the environment variable SECEDO_BAM_BATCH_BYTES
  * overrides it, outputs do not depend on it).
  *
- * SAM input: every file list may mix BAM and coordinate-sorted SAM text files. The type is decided by content:
- * BGZF magic is BAM, a plain gzip file (no BGZF extra field) is SECEDO_E_INVALID_ARG ("decompress it to SAM or
- * convert it to BAM"), anything else is SAM. A SAM file gives exactly what the BAM `samtools view -b` writes from
+ * SAM input: every file list may mix BAM, coordinate-sorted SAM text files and BGZF-compressed SAM (what `bgzip`
+ * writes, usually named .sam.gz). The type is decided by content, never by name: a plain gzip file (no BGZF extra
+ * field) is SECEDO_E_INVALID_ARG ("decompress it to SAM or convert it to BAM"); of a BGZF file the first member
+ * with ISIZE > 0 is inflated on the host, and it is BAM if that starts with "BAM\1", else BGZF SAM; anything else
+ * is SAM. A SAM file gives exactly what the BAM `samtools view -b` writes from
  * it gives, in every call. The host parses the header (the leading '@' lines; every @SQ needs SN and LN, SN unique;
  * @SQ order = RefID = chromosome_id) and cuts the alignment lines into ranges of about SECEDO_BAM_BATCH_BYTES that
  * end at a '\n'; the GPU (secedo_amd/csrc/sam_kernels.hip, which lists the rules) splits the lines, validates them
@@ -28,11 +30,21 @@
  *  - f aux values are converted to float32 without correct rounding of the last bit (no pass reads them);
  *  - no line-length limit below 4 GiB (a range grows to hold its longest line); more than 65535 CIGAR ops or a
  *    record of 2^31 bytes or more is SECEDO_E_LIMIT;
- *  - .sam.gz, standard input and CRAM are not read.
+ *  - a .sam.gz that is plain gzip, standard input and CRAM are not read.
+ * BGZF SAM gives exactly what its inflated text gives as a plain SAM file, in every call, error messages (file
+ * index, path, 1-based line of the inflated text) included. The host lists the blocks and inflates the leading ones
+ * with zlib only until the '@' lines end; all other blocks are uploaded compressed and inflated on the GPU
+ * (secedo_amd/csrc/bgzf_kernels.hip: full RFC 1951, ISIZE and CRC32 checked on the device) in ranges of about
+ * SECEDO_BAM_BATCH_BYTES inflated bytes, each range's text up to its last '\n' going to the SAM passes and the rest
+ * to the front of the next range, device to device; the inflated text never reaches the host. A block that does not
+ * inflate is SECEDO_E_INVALID_ARG in the BAM route's words ("<path>: BGZF block <k>: inflate failed or ISIZE
+ * mismatch" or "... CRC32 mismatch"), the first such block in file order, ahead of any parse error below it. For
+ * BGZF SAM, inflate_ms is the header's host inflate plus the device inflate, upload_ms includes the compressed
+ * bytes, and inflated_bytes is the inflated size. BAM files are still inflated on the host.
  * Errors in a SAM file name the file index, its path and the 1-based line (record k of a file with h header lines
  * is line h + k + 1): parse errors, the host's structural checks and the device passes' rule-6 errors; of several
  * bad lines the first is reported. For SAM, secedo_bam_times.inflate_ms is the text read and walk_ms includes the
- * device parse. secedo_bam_scan reads BAM only.
+ * device parse. secedo_bam_scan reads BAM only and stays on the host.
  */
 #ifndef SECEDO_BAM_H
 #define SECEDO_BAM_H
@@ -140,8 +152,15 @@ int secedo_bam_barcodes_fetch(char *values, uint64_t *value_off, uint64_t *count
 int secedo_bam_fetch(uint32_t *chr_locus_off, uint32_t *locus_pos, uint64_t *locus_entry_off, uint32_t *read_ids,
                      uint16_t *id_base16);
 
-/* Frees the device memory of the last result. */
+/* Frees the device memory of the last result (that of secedo_bgzf_inflate too). */
 void secedo_bam_release(void);
+
+/* Inflates any BGZF file (BAM, bgzipped SAM, ...) on the GPU, in ranges of about SECEDO_BAM_BATCH_BYTES, ISIZE and
+ * CRC32 of every member checked there; *bytes = the inflated size. A bad member is SECEDO_E_INVALID_ARG as above.
+ * The bytes stay on the device until the next call on this thread or secedo_bam_release. Synchronous. */
+int secedo_bgzf_inflate(const char *path, uint64_t *bytes);
+/* Copies them into dst[bytes], host or device memory. Synchronous. */
+int secedo_bgzf_inflate_fetch(uint8_t *dst);
 
 #ifdef __cplusplus
 }

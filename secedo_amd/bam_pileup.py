@@ -6,9 +6,11 @@ max_coverage, min_base_quality, min_map_quality, min_alignment_score, num_thread
 name numbering, the base counts, the locus rule and the entry placement run on the GPU
 (secedo_amd/csrc/bam_kernels.hip). ``bam_scan`` needs no GPU. No CPU fallback for the pileup itself.
 
-Every file list may hold BAM and coordinate-sorted SAM files, told apart by content (BGZF magic: BAM; plain gzip is
-refused; anything else: SAM text). A SAM file's lines are parsed on the GPU (secedo_amd/csrc/sam_kernels.hip) into the
-records of the BAM that ``samtools view -b`` writes from it, so results equal that BAM's; errors name its line.
+Every file list may hold BAM, coordinate-sorted SAM and BGZF-compressed SAM (``bgzip``'s .sam.gz) files, told apart by
+content (BGZF whose text starts with ``BAM\\1``: BAM; other BGZF: compressed SAM; plain gzip is refused; anything else:
+SAM text). A SAM file's lines are parsed on the GPU (secedo_amd/csrc/sam_kernels.hip) into the records of the BAM that
+``samtools view -b`` writes from it, so results equal that BAM's; errors name its line. A BGZF SAM file is inflated on
+the GPU too (secedo_amd/csrc/bgzf_kernels.hip) and gives what its text gives; ``bgzf_inflate`` is that inflate alone.
 
 Multiplexed BAMs (one file, many cells named by a barcode tag such as 10x's ``CB:Z``): ``cell_tag`` and ``cells``
 on ``pileup_bams`` / ``pileup_bams_resident`` make cell c the records whose tag value is ``cells[c]``;
@@ -70,6 +72,8 @@ SIGNATURES = {
     "secedo_bam_barcodes_fetch": (C.c_int, [_vp, _vp, _vp]),
     "secedo_bam_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "secedo_bam_release": (None, []),
+    "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
+    "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
 
 _bl = None
@@ -151,6 +155,21 @@ def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], 
     raw = buf.raw
     values = [raw[int(off[i]):int(off[i + 1])].decode("utf-8", "surrogateescape") for i in range(k)]
     return values, counts[:k].copy()
+
+
+def bgzf_inflate(path) -> np.ndarray:
+    """The inflated bytes of a BGZF file (BAM, bgzipped SAM, ...) -> np.uint8. Every member is inflated on the GPU,
+    its ISIZE and CRC32 checked there; a bad member raises SecedoError naming its block. Needs the GPU."""
+    try:
+        import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
+    except ImportError:
+        pass
+    n = C.c_uint64(0)
+    check(lib().secedo_bgzf_inflate(os.fsencode(str(path)), C.byref(n)))
+    out = np.zeros(int(n.value), dtype=np.uint8)
+    check(lib().secedo_bgzf_inflate_fetch(_lib.ptr(out) if len(out) else None))
+    lib().secedo_bam_release()
+    return out
 
 
 def bam_scan(path, num_threads: int = 1, max_refs: int = 4096) -> dict:

@@ -56,5 +56,8 @@ std::string record_where(const std::string &path, size_t f, uint64_t line0, uint
 int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosome_ids, uint32_t n_chr,
                 uint32_t threads, Inputs *in, secedo_bam_times *t);
 
+// Frees the device memory of the last secedo_bgzf_inflate result of this thread (secedo_bam_release calls it).
+void release_inflated();
+
 }  // namespace bam_host
 }  // namespace secedo

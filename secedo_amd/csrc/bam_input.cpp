@@ -1,6 +1,7 @@
 // bam_input.cpp -- the input side of include/secedo_bam.h: BGZF inflate, the BAM header and record walk, the SAM
-// header and the driver of the device parse (sam_kernels.hip), and secedo_bam_scan. Its product is one ChrInput per
-// requested chromosome (bam_host.hpp), which bam_pileup.cpp turns into the pileup.
+// header and the driver of the device parse (sam_kernels.hip), BGZF-compressed SAM through the device inflate
+// (bgzf_kernels.hip), secedo_bgzf_inflate and secedo_bam_scan. Its product is one ChrInput per requested chromosome
+// (bam_host.hpp), which bam_pileup.cpp turns into the pileup.
 //
 // Each file is memory-mapped; its BGZF blocks (BSIZE from the BC extra field) are inflated with zlib raw inflate
 // in a pool of at most 16 threads, CRC32 and ISIZE checked. Files are inflated in batches of about 512 MiB of
@@ -10,6 +11,8 @@
 // is needed: the run is found by walking block_size, so with or without an index the result is the same.
 #include "bam_host.hpp"
 #include "bam_kernels.hpp"  // the scan wrappers
+#include "bgzf_inflate.hpp"  // the status codes
+#include "bgzf_kernels.hpp"
 #include "sam_kernels.hpp"
 
 #include <zlib.h>
@@ -23,6 +26,7 @@
 #include <atomic>
 #include <climits>
 #include <cstdlib>
+#include <memory>
 #include <set>
 #include <thread>
 
@@ -93,25 +97,34 @@ struct Block {
     uint64_t out;  // offset in the file's inflated buffer
 };
 
+// the BGZF block at byte off < m.n of a mapped file (its `out` left 0); *len = its bytes in the file
+int read_block(const std::string &path, const Mapped &m, uint64_t off, Block *blk, uint32_t *len) {
+    const uint8_t *b = m.p + off;
+    if (m.n - off < 18 || b[0] != 31 || b[1] != 139 || b[2] != 8 || !(b[3] & 4))
+        return fail(SECEDO_E_INVALID_ARG, path + ": not a BGZF block at byte " + std::to_string(off));
+    const uint32_t xlen = rd16(b + 10);
+    uint32_t bsize = UINT32_MAX;
+    for (uint32_t x = 12; x + 4 <= 12 + xlen && 12 + xlen <= m.n - off;) {
+        const uint32_t slen = rd16(b + x + 2);
+        if (b[x] == 'B' && b[x + 1] == 'C' && slen == 2) bsize = rd16(b + x + 4);
+        x += 4 + slen;
+    }
+    if (bsize == UINT32_MAX || uint64_t(bsize) + 1 > m.n - off || bsize + 1 < 12 + xlen + 8)
+        return fail(SECEDO_E_INVALID_ARG, path + ": bad BGZF block size at byte " + std::to_string(off));
+    *len = bsize + 1;
+    *blk = Block{b + 12 + xlen, *len - xlen - 20, rd32(b + *len - 8), rd32(b + *len - 4), 0};
+    if (blk->isize > 65536) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF ISIZE above 64 KiB");
+    return SECEDO_OK;
+}
+
 // BGZF block list of one mapped file
 int list_blocks(const std::string &path, const Mapped &m, std::vector<Block> *blocks, uint64_t *total) {
     uint64_t off = 0, out = 0;
     while (off < m.n) {
-        const uint8_t *b = m.p + off;
-        if (m.n - off < 18 || b[0] != 31 || b[1] != 139 || b[2] != 8 || !(b[3] & 4))
-            return fail(SECEDO_E_INVALID_ARG, path + ": not a BGZF block at byte " + std::to_string(off));
-        const uint32_t xlen = rd16(b + 10);
-        uint32_t bsize = UINT32_MAX;
-        for (uint32_t x = 12; x + 4 <= 12 + xlen && 12 + xlen <= m.n - off;) {
-            const uint32_t slen = rd16(b + x + 2);
-            if (b[x] == 'B' && b[x + 1] == 'C' && slen == 2) bsize = rd16(b + x + 4);
-            x += 4 + slen;
-        }
-        if (bsize == UINT32_MAX || uint64_t(bsize) + 1 > m.n - off || bsize + 1 < 12 + xlen + 8)
-            return fail(SECEDO_E_INVALID_ARG, path + ": bad BGZF block size at byte " + std::to_string(off));
-        const uint32_t len = bsize + 1;
-        Block blk{b + 12 + xlen, len - xlen - 20, rd32(b + len - 8), rd32(b + len - 4), out};
-        if (blk.isize > 65536) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF ISIZE above 64 KiB");
+        Block blk;
+        uint32_t len = 0;
+        SECEDO_CALL(read_block(path, m, off, &blk, &len));
+        blk.out = out;
         blocks->push_back(blk);
         out += blk.isize;
         off += len;
@@ -362,19 +375,42 @@ int load_file_ranges(size_t f, uint32_t threads, uint64_t batch, Inputs *in, Run
 
 // ---------------------------------------------------------------------------------------------------------------
 // SAM text input: the header is parsed here, the alignment lines on the device (sam_kernels.hip) into the BAM records
-// the walk above collects. The file type comes from its first bytes: BGZF is BAM, plain gzip is refused, anything
-// else is SAM.
+// the walk above collects. The file type comes from its content, never its name: plain gzip is refused; BGZF whose
+// first non-empty member starts with "BAM\1" is BAM, other BGZF is compressed SAM; anything else is SAM.
 
-// *sam = the file is SAM text; plain gzip (no BGZF extra field) is an error
-int sniff(const std::string &path, bool *sam) {
+enum Kind : char { kBam = 0, kSam = 1, kSamGz = 2 };
+
+// BGZF: the first member with ISIZE > 0 inflated here decides between BAM and SAM text. A file with no such member,
+// or one that does not inflate, stays with the BAM route, which reports it.
+int sniff_bgzf(const std::string &path, Kind *kind) {
+    *kind = kBam;
+    Mapped m;
+    SECEDO_CALL(map_file(path, &m));
+    for (uint64_t off = 0; off < m.n;) {
+        Block blk;
+        uint32_t len = 0;
+        if (read_block(path, m, off, &blk, &len) != SECEDO_OK) return SECEDO_OK;
+        if (blk.isize) {
+            std::vector<uint8_t> d(blk.isize);
+            if (inflate_block(blk, d.data()).empty() && !(d.size() >= 4 && std::memcmp(d.data(), "BAM\1", 4) == 0))
+                *kind = kSamGz;
+            return SECEDO_OK;
+        }
+        off += len;
+    }
+    return SECEDO_OK;
+}
+
+// *kind = what the file is; plain gzip (no BGZF extra field) is an error
+int sniff(const std::string &path, Kind *kind) {
     const int fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) return fail(SECEDO_E_INVALID_ARG, "Could not open " + path);
     uint8_t b[512];
     const ssize_t n = pread(fd, b, sizeof(b), 0);
     close(fd);
     if (n < 0) return fail(SECEDO_E_INVALID_ARG, "Could not read " + path);
-    *sam = !(n >= 2 && b[0] == 31 && b[1] == 139);
-    if (*sam) return SECEDO_OK;
+    *kind = kSam;
+    if (!(n >= 2 && b[0] == 31 && b[1] == 139)) return SECEDO_OK;
     bool bgzf = false;
     if (n >= 12 && b[2] == 8 && (b[3] & 4)) {
         const uint32_t end = std::min<uint32_t>(12 + rd16(b + 10), uint32_t(n));
@@ -384,7 +420,7 @@ int sniff(const std::string &path, bool *sam) {
     if (!bgzf)
         return fail(SECEDO_E_INVALID_ARG, path + ": a gzip file that is not BGZF; decompress it to SAM or convert "
                                                  "it to BAM (samtools view -b)");
-    return SECEDO_OK;
+    return sniff_bgzf(path, kind);
 }
 
 struct SamHeader {
@@ -393,15 +429,15 @@ struct SamHeader {
 };
 
 // the leading '@' lines: @SQ SN and LN required, SN unique
-int parse_sam_header(const std::string &path, size_t f, const Mapped &m, SamHeader *h) {
+int parse_sam_header(const std::string &path, size_t f, const uint8_t *p, uint64_t n, SamHeader *h) {
     std::set<std::string> seen;
     uint64_t o = 0;
-    while (o < m.n && m.p[o] == '@') {
-        const uint8_t *nl = static_cast<const uint8_t *>(std::memchr(m.p + o, '\n', m.n - o));
-        const uint64_t e = nl ? uint64_t(nl - m.p) : m.n;
+    while (o < n && p[o] == '@') {
+        const uint8_t *nl = static_cast<const uint8_t *>(std::memchr(p + o, '\n', n - o));
+        const uint64_t e = nl ? uint64_t(nl - p) : n;
         ++h->lines;
-        const std::string line(reinterpret_cast<const char *>(m.p + o), e - o);
-        o = nl ? e + 1 : m.n;
+        const std::string line(reinterpret_cast<const char *>(p + o), e - o);
+        o = nl ? e + 1 : n;
         if (line.compare(0, 3, "@SQ") != 0 || (line.size() > 3 && line[3] != '\t')) continue;
         const std::string where = record_where(path, f, h->lines, 0);  // the header line itself
         std::string sn;
@@ -430,6 +466,54 @@ int parse_sam_header(const std::string &path, size_t f, const Mapped &m, SamHead
     return SECEDO_OK;
 }
 
+// device buffers of the BGZF inflate, kept over the ranges and files of one call
+struct GzWork {
+    Dev<uint8_t> in;
+    Dev<BgzfDesc> desc;
+    Dev<uint32_t> status;
+    std::vector<BgzfDesc> h_desc;
+    std::vector<uint32_t> h_status;
+};
+
+// Blocks [b0, b1) of a mapped BGZF file inflated on the device: block b lands at d_out + out_base + (its inflated
+// offset - that of b0). The compressed bytes go up as they lie in the file, in one copy; ISIZE and CRC32 are checked
+// on the device, and the first block in file order that fails is the error, in the words of the host inflate.
+int inflate_range_device(const std::string &path, const Mapped &m, const std::vector<Block> &blocks, size_t b0,
+                         size_t b1, GzWork *g, uint8_t *d_out, uint64_t out_base, hipStream_t s,
+                         secedo_bam_times *t) {
+    if (b0 >= b1) return SECEDO_OK;
+    Clock::time_point t0 = Clock::now();
+    // the payloads of the range and kBgzfInSlack bytes on either side (the first payload lies 18 bytes into the file)
+    const uint8_t *lo = blocks[b0].cdata - kBgzfInSlack;
+    const uint8_t *pay_end = blocks[b1 - 1].cdata + blocks[b1 - 1].clen;
+    const uint8_t *hi = std::min(m.p + m.n, pay_end + kBgzfInSlack);
+    const uint64_t n_blocks = b1 - b0;
+    if (n_blocks > UINT32_MAX) return fail(SECEDO_E_LIMIT, path + ": too many BGZF blocks in one range");
+    g->h_desc.resize(n_blocks);
+    for (size_t b = b0; b < b1; ++b)
+        g->h_desc[b - b0] = BgzfDesc{uint64_t(blocks[b].cdata - lo), out_base + (blocks[b].out - blocks[b0].out),
+                                     blocks[b].clen, blocks[b].isize, blocks[b].crc, 0};
+    SECEDO_TRY(g->in.grow(uint64_t(pay_end - lo) + kBgzfInSlack, 0, s));
+    SECEDO_TRY(g->desc.grow(n_blocks, 0, s));
+    SECEDO_TRY(g->status.grow(n_blocks, 0, s));
+    SECEDO_TRY(hipMemcpyAsync(g->in.p, lo, size_t(hi - lo), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(g->desc.p, g->h_desc.data(), n_blocks * sizeof(BgzfDesc), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    if (t) t->upload_ms += ms_lap(t0);
+    SECEDO_TRY(bgzf_inflate(g->in.p, g->desc.p, uint32_t(n_blocks), d_out, g->status.p, s));
+    g->h_status.resize(n_blocks);
+    SECEDO_TRY(hipMemcpyAsync(g->h_status.data(), g->status.p, n_blocks * 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    if (t) t->inflate_ms += ms_lap(t0);
+    for (size_t k = 0; k < n_blocks; ++k)
+        if (g->h_status[k] != secedo::bgzf::kOk)
+            return fail(SECEDO_E_INVALID_ARG,
+                        path + ": BGZF block " + std::to_string(b0 + k) + ": " +
+                            (g->h_status[k] == secedo::bgzf::kCrcMismatch ? "CRC32 mismatch"
+                                                                          : "inflate failed or ISIZE mismatch"));
+    return SECEDO_OK;
+}
+
 // device buffers of the SAM passes, kept over the ranges and files of one call
 struct SamWork {
     hipStream_t s = nullptr;
@@ -438,6 +522,8 @@ struct SamWork {
     Dev<uint64_t> name_hash, size, off;
     Dev<int32_t> ref, pos;
     Dev<unsigned long long> err;
+    GzWork gz;           // BGZF SAM: the device inflate in front of the parse
+    Dev<uint8_t> carry;  // and the cut tail of a range on its way to the front of the next
     std::vector<uint8_t> h_text, h_out;
     std::vector<int32_t> h_ref, h_pos;
     ~SamWork() {
@@ -606,7 +692,7 @@ int load_sam_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs, 
     Mapped m;
     SECEDO_CALL(map_file(path, &m));
     SamHeader h;
-    SECEDO_CALL(parse_sam_header(path, f, m, &h));
+    SECEDO_CALL(parse_sam_header(path, f, m.p, m.n, &h));
     in->line0[f] = h.lines + 1;
     if (t) t->inflate_ms += ms_since(t0);
     t0 = Clock::now();
@@ -659,10 +745,123 @@ int load_sam_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs, 
     return SECEDO_OK;
 }
 
+// One BGZF-compressed SAM file: what load_sam_file gives on its inflated text. The host lists the blocks and inflates
+// the leading ones with zlib until the '@' lines end; every block after those is inflated on the device, in ranges of
+// about `batch` inflated bytes, into the text buffer behind the carry (the bytes after the last '\n' of the range
+// before). [0, last '\n'] of each range goes to the parse; the inflated text never reaches the host.
+int load_samgz_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs, secedo_bam_times *t) {
+    const std::string &path = in->paths[f];
+    Clock::time_point t0 = Clock::now();
+    Mapped m;
+    std::vector<Block> blocks;
+    uint64_t total = 0;
+    SECEDO_CALL(open_bgzf(path, &m, &blocks, &total));
+    // the header: blocks inflated here until a line starts with something else than '@', or the file ends
+    std::vector<uint8_t> head;
+    size_t hb = 0;
+    for (uint64_t o = 0;;) {  // o: a line start, every line before it an '@' line
+        const uint8_t *nl = nullptr;
+        if (o < head.size()) {
+            if (head[o] != '@') break;
+            nl = static_cast<const uint8_t *>(std::memchr(head.data() + o, '\n', head.size() - o));
+        }
+        if (nl) {
+            o = uint64_t(nl - head.data()) + 1;
+            continue;
+        }
+        if (hb == blocks.size()) break;
+        const size_t at = head.size();
+        head.resize(at + blocks[hb].isize);
+        const std::string err = inflate_block(blocks[hb], head.data() + at);
+        if (!err.empty()) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(hb) + ": " + err);
+        ++hb;
+    }
+    SamHeader h;
+    SECEDO_CALL(parse_sam_header(path, f, head.data(), head.size(), &h));
+    in->line0[f] = h.lines + 1;
+    if (t) {
+        t->inflate_ms += ms_since(t0);
+        t->inflated_bytes += double(head.size());
+    }
+    t0 = Clock::now();
+    if (!w->s) SECEDO_TRY(hipStreamCreateWithFlags(&w->s, hipStreamNonBlocking));
+    hipStream_t s = w->s;
+    std::vector<uint8_t> sel;
+    SamRefs refs{};
+    SECEDO_CALL(upload_sam_refs(h, in->chrs, w, &sel, &refs));
+    // what the header's blocks hold of the body is the first carry
+    uint64_t carry = head.size() - h.body;
+    SECEDO_TRY(w->text.grow(carry + 32, 0, s));
+    if (carry) SECEDO_TRY(hipMemcpyAsync(w->text.p, head.data() + h.body, carry, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    if (t) t->upload_ms += ms_since(t0);
+
+    FileSink sink(*in, f, *runs);
+    SortCheck order;
+    SamRange r;
+    for (size_t b0 = hb;;) {
+        size_t b1 = b0;
+        uint64_t bytes = 0;
+        while (b1 < blocks.size() && (b1 == b0 || bytes + blocks[b1].isize <= batch)) bytes += blocks[b1++].isize;
+        if (b1 < blocks.size() && blocks[b1].out == total) b1 = blocks.size();  // only empty blocks follow
+        const bool ends = b1 == blocks.size();
+        const uint64_t len = carry + bytes;
+        if (len >= (1ull << 32) - 64)
+            return fail(SECEDO_E_LIMIT, "file " + std::to_string(f) + " (" + path +
+                                            "): a range of SAM lines of 4 GiB or more (a line that long)");
+        const uint64_t padded = (len + 15) / 16 * 16 + 16;
+        SECEDO_TRY(w->text.grow(padded, carry, s));
+        SECEDO_CALL(inflate_range_device(path, m, blocks, b0, b1, &w->gz, w->text.p, carry, s, t));
+        if (t) t->inflated_bytes += double(bytes);
+        b0 = b1;
+        t0 = Clock::now();
+        unsigned long long last = 0;  // one past the last '\n'
+        if (len) {
+            SECEDO_TRY(w->err.grow(1, 0, s));
+            SECEDO_TRY(bgzf_last_newline(w->text.p, len, w->err.p, s));
+            SECEDO_TRY(hipMemcpyAsync(&last, w->err.p, 8, hipMemcpyDeviceToHost, s));
+            SECEDO_TRY(hipStreamSynchronize(s));
+        }
+        const uint64_t cut = ends ? len : last;  // the range handed on; the rest is carried
+        carry = len - cut;
+        if (cut) {
+            if (carry) {
+                SECEDO_TRY(w->carry.grow(carry, 0, s));
+                SECEDO_TRY(hipMemcpyAsync(w->carry.p, w->text.p + cut, carry, hipMemcpyDeviceToDevice, s));
+            }
+            r.len = cut;
+            r.n16 = (cut + 15) / 16;
+            r.ends_file = ends;
+            r.trailing = last == cut;
+            // zero-padded to whole 16-byte vectors plus one, as an uploaded range is
+            SECEDO_TRY(hipMemsetAsync(w->text.p + cut, 0, r.n16 * 16 + 16 - cut, s));
+            SECEDO_CALL(parse_sam_range(w, refs, &r));
+            SECEDO_CALL(collect_sam_range(*w, r, sel, &order, &sink));
+            r.line_base += r.n_lines;
+            if (carry) SECEDO_TRY(hipMemcpyAsync(w->text.p, w->carry.p, carry, hipMemcpyDeviceToDevice, s));
+        }
+        if (t) t->walk_ms += ms_since(t0);
+        if (ends) break;
+    }
+    return SECEDO_OK;
+}
+
+// the inflated bytes of the last secedo_bgzf_inflate on this thread
+struct InflatedFile {
+    Dev<uint8_t> data;
+    uint64_t n = 0;
+};
+thread_local InflatedFile *g_inflated = nullptr;
+
 }  // namespace
 
 namespace secedo {
 namespace bam_host {
+
+void release_inflated() {
+    delete g_inflated;
+    g_inflated = nullptr;
+}
 
 std::string record_where(const std::string &path, size_t f, uint64_t line0, uint64_t idx, Stage stage) {
     if (line0) return "file " + std::to_string(f) + " (" + path + "), line " + std::to_string(line0 + idx);
@@ -685,18 +884,19 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
         ci.rpos.assign(n_files, {});
         ci.ridx.assign(n_files, {});
     }
-    std::vector<char> sam(n_files, 0);
+    std::vector<char> sam(n_files, kBam);  // the Kind of each file
     for (size_t f = 0; f < n_files; ++f) {
-        bool is_sam = false;
-        SECEDO_CALL(sniff(files[f], &is_sam));
-        sam[f] = is_sam;
+        Kind kind = kBam;
+        SECEDO_CALL(sniff(files[f], &kind));
+        sam[f] = kind;
     }
     SamWork sam_work;
     Runs runs(n_chr, std::vector<std::vector<uint8_t>>(n_files));
     size_t f0 = 0;
     while (f0 < n_files) {
         if (sam[f0]) {  // SAM text: parsed on the device in ranges of about `batch` bytes
-            SECEDO_CALL(load_sam_file(f0, batch, &sam_work, in, &runs, t));
+            if (sam[f0] == kSamGz) SECEDO_CALL(load_samgz_file(f0, batch, &sam_work, in, &runs, t));
+            else SECEDO_CALL(load_sam_file(f0, batch, &sam_work, in, &runs, t));
             ++f0;
             continue;
         }
@@ -785,5 +985,38 @@ extern "C" int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_ba
     info->reserved = 0;
     if (records_per_ref)
         for (uint32_t r = 0; r < std::min(capacity, h.n_ref); ++r) records_per_ref[r] = per[r];
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bgzf_inflate(const char *path, uint64_t *bytes) {
+    if (!path || !bytes) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    secedo::bam_host::release_inflated();
+    Mapped m;
+    std::vector<Block> blocks;
+    uint64_t total = 0;
+    SECEDO_CALL(open_bgzf(path, &m, &blocks, &total));
+    std::unique_ptr<InflatedFile> res(new InflatedFile);
+    StreamGuard sg;
+    SECEDO_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    SECEDO_TRY(res->data.alloc(total));
+    res->n = total;
+    GzWork g;
+    const uint64_t batch = batch_bytes();
+    for (size_t b0 = 0; b0 < blocks.size();) {
+        size_t b1 = b0;
+        uint64_t n = 0;
+        while (b1 < blocks.size() && (b1 == b0 || n + blocks[b1].isize <= batch)) n += blocks[b1++].isize;
+        SECEDO_CALL(inflate_range_device(path, m, blocks, b0, b1, &g, res->data.p, blocks[b0].out, sg.s, nullptr));
+        b0 = b1;
+    }
+    *bytes = total;
+    g_inflated = res.release();
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bgzf_inflate_fetch(uint8_t *dst) {
+    const InflatedFile *r = g_inflated;
+    if (!r) return fail(SECEDO_E_STATE, "no secedo_bgzf_inflate result on this thread");
+    if (dst && r->n) SECEDO_TRY(hipMemcpy(dst, r->data.p, r->n, hipMemcpyDefault));
     return SECEDO_OK;
 }

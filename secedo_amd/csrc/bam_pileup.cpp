@@ -859,6 +859,7 @@ int secedo_bam_fetch(uint32_t *chr_locus_off, uint32_t *locus_pos, uint64_t *loc
 void secedo_bam_release(void) {
     delete g_result;
     g_result = nullptr;
+    release_inflated();
 }
 
 }  // extern "C"

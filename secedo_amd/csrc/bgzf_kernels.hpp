@@ -1,0 +1,33 @@
+// bgzf_kernels.hpp -- launch wrappers of bgzf_kernels.hip (gfx950): BGZF members inflated in HBM, CRC32 and ISIZE
+// checked there, and the last '\n' of a text range. See bgzf_kernels.hip for the kernel's layout.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace secedo {
+namespace bam {
+
+// one BGZF member: its raw-DEFLATE payload at d_in + in_off (clen bytes) inflates to d_out + out_off (isize bytes)
+struct BgzfDesc {
+    uint64_t in_off, out_off;
+    uint32_t clen, isize, crc, reserved;
+};
+
+// bytes the kernel may read beyond a payload's ends (whole 16-byte vectors): d_in needs that much room before the
+// first payload and after the last one
+constexpr uint32_t kBgzfInSlack = 16;
+constexpr uint32_t kBgzfMaxIsize = 65536;
+
+// d_status[k] = secedo::bgzf::Status of member k (0 = inflated, ISIZE and CRC32 right). Members must not overlap in
+// d_out; isize <= kBgzfMaxIsize.
+hipError_t bgzf_inflate(const uint8_t *d_in, const BgzfDesc *d_desc, uint32_t n_members, uint8_t *d_out,
+                        uint32_t *d_status, hipStream_t s);
+
+// *d_end = 1 + the index of the last '\n' of d_text[0, n), 0 when there is none (d_end is set by the call)
+hipError_t bgzf_last_newline(const uint8_t *d_text, uint64_t n, unsigned long long *d_end, hipStream_t s);
+
+}  // namespace bam
+}  // namespace secedo

@@ -1,7 +1,7 @@
 """``python -m secedo_amd.pileup_main``: the reference's ``pileup`` executable (pileup_main.cpp) on the GPU path.
 
-Flags as in the reference: -i (a BAM or SAM file, or a directory searched recursively for *.bam, or for *.sam when it
-holds no BAM), -o (file prefix),
+Flags as in the reference: -i (a BAM, SAM or bgzipped SAM file, or a directory searched recursively for *.bam, or for
+*.sam when it holds no BAM, or for *.sam.gz when it holds neither), -o (file prefix),
 --chromosomes, --min_base_quality, --min_map_quality, --min_map_score, --max_coverage, --min_different,
 --num_threads (here only the size of the host inflate pool, capped at 16). Writes
 <o>_<chromosome>.pileup.{bin,map,txt} per chromosome and, for a directory input, the cell map
@@ -15,6 +15,8 @@ chromosomes, sorted bytewise, so that every <o>_<chromosome>.pileup.bin shares o
 
 SAM text input (coordinate-sorted, as aligners write it) goes the same way: its lines are parsed on the GPU into the
 BAM records the BAM route reads, so a SAM file gives what the BAM `samtools view -b` writes from it would give.
+A .sam.gz written by `bgzip` (BGZF) is inflated on the GPU in front of that parse and gives what its text gives; a
+.sam.gz written by plain `gzip` is refused. Files are told apart by content, the names only serve the directory search.
 """
 from __future__ import annotations
 
@@ -29,7 +31,8 @@ MAX_POOL = 16
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(prog="python -m secedo_amd.pileup_main", description=__doc__.splitlines()[0])
-    ap.add_argument("-i", required=True, help="Input BAM or SAM file, or a directory containing BAM files (or SAM files when it holds no BAM)")
+    ap.add_argument("-i", required=True, help="Input BAM, SAM or bgzipped SAM (.sam.gz) file, or a directory containing BAM files (or SAM files "
+                                       "when it holds no BAM, or .sam.gz files when it holds neither)")
     ap.add_argument("-o", default="./", help="File prefix of the output: <o>_<chromosome>.pileup.bin etc.")
     ap.add_argument("--num_threads", type=int, default=8, help="Host inflate threads (at most 16 are used)")
     ap.add_argument("--chromosomes", default=DEFAULT_CHROMOSOMES, help="Comma-separated chromosomes (1..22, X, Y)")
@@ -101,22 +104,30 @@ def pool_size(num_threads: int) -> int:
 def _find(path: str, ext: str) -> List[str]:
     found = []
     for root, _dirs, names in os.walk(path):
-        found.extend(os.path.join(root, n) for n in names if os.path.splitext(n)[1] == ext)
+        found.extend(os.path.join(root, n) for n in names if _split(n)[1] == ext)
     return sorted(found)
 
 
+def _split(name: str):
+    """os.path.splitext, with .sam.gz as one extension."""
+    if name.endswith(".sam.gz"):
+        return name[:-len(".sam.gz")], ".sam.gz"
+    return os.path.splitext(name)
+
+
 def input_files(path: str) -> List[str]:
-    """A file as given; a directory's *.bam files, or its *.sam files when it holds no BAM."""
+    """A file as given; a directory's *.bam files, or its *.sam files when it holds no BAM, or its *.sam.gz files
+    when it holds neither."""
     if not os.path.isdir(path):
         return [path]
-    return _find(path, ".bam") or _find(path, ".sam")
+    return _find(path, ".bam") or _find(path, ".sam") or _find(path, ".sam.gz")
 
 
 def cell_map_lines(files: List[str]) -> List[str]:
     """The cell map: file name without extension, cut at its last '_', then the cell index."""
     out = []
     for i, f in enumerate(files):
-        stem = os.path.splitext(os.path.basename(f))[0]
+        stem = _split(os.path.basename(f))[0]
         cut = stem.rfind("_")
         out.append("%s\t%d\n" % (stem[:cut] if cut >= 0 else stem, i))
     return out

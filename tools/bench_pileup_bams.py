@@ -17,6 +17,9 @@ in the multiplexed BAM's order) and times the SAM route beside the BAM route in 
 (inflate_ms is the text read, walk_ms includes the device parse), and whether its .bin and .map equal the BAM
 route's. --sam-only runs just the SAM calls once each, for a rocprofv3 run of its own; --merge-sam LINE.json OUT then
 adds the SAM kernels' times and their text GB/s against HBM peak.
+--sam-gz (with --sam) also writes every SAM file as BGZF (<name>.sam.gz, zlib level 6, 65280-byte members) and times
+that route: upload_ms then covers the compressed bytes and inflate_ms the device inflate (k_bgzf_inflate), whose
+inflate_GBps stands beside the BAM route's host zlib pool on the same kind of bytes.
 Kernel times come from a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_pileup_bams.py --dir D \
         --repeat 1 --resident-only
@@ -253,6 +256,8 @@ def main():
     ap.add_argument("--multiplexed-only", action="store_true",
                     help="Only the tag-mode resident call (for a rocprofv3 run of its own)")
     ap.add_argument("--sam", action="store_true", help="Also the SAM route on the set written as SAM")
+    ap.add_argument("--sam-gz", action="store_true",
+                    help="With --sam: also the set as BGZF-compressed SAM (.sam.gz), inflated on the GPU")
     ap.add_argument("--sam-only", action="store_true", help="Only the SAM calls, once each (for rocprofv3)")
     ap.add_argument("--merge", nargs=2, metavar=("LINE", "PROF_DIR"))
     ap.add_argument("--merge-sam", nargs=2, metavar=("LINE", "PROF_DIR"))
@@ -332,6 +337,15 @@ def main():
         if a.sam:
             line["sam"] = sam_route(a, sams, [msam] if msam else None, barcodes if msam else None, out,
                                     mout if msam else None, sam_s, med)
+            if a.sam_gz:
+                t0 = time.time()
+                gzs, mgz = write_sam_gz_set(sams, msam)
+                line["sam_gz"] = sam_route(a, gzs, [mgz] if mgz else None, barcodes if mgz else None, out,
+                                           mout if mgz else None, time.time() - t0, med, prefix="g")
+                line["sam_gz"]["gz_bytes"] = sum(os.path.getsize(p) for p in gzs)
+                # the device inflate against the host zlib pool on BGZF bytes (the BAM route's inflate_GBps above)
+                r = line["sam_gz"]["per_file"]
+                r["inflate_GBps"] = r["text_bytes"] / (r["inflate_ms"] * 1e-3) / 1e9
     with secedo_amd.SimilarityMatrixPlan(0) as plan:
         rt = []
         for k in range(a.repeat + 1):
@@ -355,7 +369,30 @@ def main():
 STEPS = ("inflate_ms", "walk_ms", "upload_ms", "device_ms", "write_ms", "total_ms")
 
 
-def sam_route(a, sams, msam, barcodes, out, mout, sam_s, med):
+def _bgzip(args):
+    """src -> dst as BGZF: members of 65280 bytes at zlib level 6, then the empty EOF member (what bgzip writes)"""
+    src, dst = args
+    data = open(src, "rb").read()
+    with open(dst, "wb") as f:
+        for o in list(range(0, len(data), 0xFF00)) + [len(data)]:
+            piece = data[o:o + 0xFF00]
+            c = zlib.compressobj(6, zlib.DEFLATED, -15)
+            payload = c.compress(piece) + c.flush()
+            f.write(struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(payload) + 25) +
+                    payload + struct.pack("<II", zlib.crc32(piece), len(piece)))
+    return dst
+
+
+def write_sam_gz_set(sams, msam):
+    """Each SAM file of the set beside it as <name>.sam.gz -> (paths, multiplexed path or None)"""
+    jobs = [(s, s + ".gz") for s in sams] + ([(msam, msam + ".gz")] if msam else [])
+    jobs = [j for j in jobs if not os.path.exists(j[1])]
+    with Pool(16) as pool:
+        pool.map(_bgzip, jobs, chunksize=4)
+    return [s + ".gz" for s in sams], (msam + ".gz" if msam else None)
+
+
+def sam_route(a, sams, msam, barcodes, out, mout, sam_s, med, prefix="s"):
     """The SAM route's step times (medians of --repeat runs after one untimed run), its outputs against the BAM
     route's (out / mout), and a table of both routes on stderr"""
     from secedo_amd import bam_pileup
@@ -374,11 +411,11 @@ def sam_route(a, sams, msam, barcodes, out, mout, sam_s, med):
             r[ext[1:] + "_equal"] = open(prefix + ext, "rb").read() == open(out_of[prefix] + ext, "rb").read()
         return r
 
-    sout = os.path.join(a.dir, "sout")
+    sout = os.path.join(a.dir, prefix + "out")
     out_of = {sout: out}
     res = dict(set_write_s=round(sam_s, 1), per_file=timed(sams, sout))
     if msam:
-        smout = os.path.join(a.dir, "smout")
+        smout = os.path.join(a.dir, prefix + "mout")
         out_of[smout] = mout
         res["multiplexed"] = timed(msam, smout, cell_tag="CB", cells=barcodes)
     return res
@@ -390,6 +427,10 @@ def print_table(line):
         rows.append(("BAM multiplexed", line["multiplexed"]))
     if "multiplexed" in line["sam"]:
         rows.append(("SAM multiplexed", line["sam"]["multiplexed"]))
+    if "sam_gz" in line:
+        rows.append(("SAM.gz per-file", line["sam_gz"]["per_file"]))
+        if "multiplexed" in line["sam_gz"]:
+            rows.append(("SAM.gz multiplex", line["sam_gz"]["multiplexed"]))
     print("%-16s" % "ms" + "".join("%11s" % k[:-3] for k in STEPS), file=sys.stderr)
     for name, r in rows:
         print("%-16s" % name + "".join("%11.1f" % r[k] for k in STEPS), file=sys.stderr)
