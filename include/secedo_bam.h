@@ -40,11 +40,24 @@
  * inflate is SECEDO_E_INVALID_ARG in the BAM route's words ("<path>: BGZF block <k>: inflate failed or ISIZE
  * mismatch" or "... CRC32 mismatch"), the first such block in file order, ahead of any parse error below it. For
  * BGZF SAM, inflate_ms is the header's host inflate plus the device inflate, upload_ms includes the compressed
- * bytes, and inflated_bytes is the inflated size. BAM files are still inflated on the host.
+ * bytes, and inflated_bytes is the inflated size. BAM files are still inflated on the host by default.
  * Errors in a SAM file name the file index, its path and the 1-based line (record k of a file with h header lines
  * is line h + k + 1): parse errors, the host's structural checks and the device passes' rule-6 errors; of several
  * bad lines the first is reported. For SAM, secedo_bam_times.inflate_ms is the text read and walk_ms includes the
  * device parse. secedo_bam_scan reads BAM only and stays on the host.
+ *
+ * The device route for BAM (opt-in: secedo_bam_set_inflate(SECEDO_BAM_INFLATE_DEVICE), or SECEDO_BAM_INFLATE=device in
+ * the environment): BAM files take the way of BGZF SAM. The host inflates a file's leading members only until its
+ * header and reference list are complete; every other member goes up compressed and is inflated on the GPU, many small
+ * files to one launch, a large file in ranges of about SECEDO_BAM_BATCH_BYTES. The record walk (block_size chain,
+ * structure, sortedness, the first run of each requested chromosome, the CIGAR checks) runs on the GPU too
+ * (secedo_amd/csrc/bam_walk_kernels.hip), and only the records of the requested chromosomes come back. For valid input
+ * every call returns exactly what the host route returns. A file with one defect gives the host route's code and
+ * message. Of several defects the lowest file index is reported; within a file a member that does not inflate
+ * ("<path>: BGZF block <k>: ...") comes before any record error in or after that member's bytes, and of record errors
+ * the lowest record. The route fills secedo_bam_times as BGZF SAM does: inflate_ms is the header's host inflate plus
+ * the device inflate, upload_ms the staging and upload of the compressed bytes, walk_ms the device walk and the
+ * read-back of the records.
  */
 #ifndef SECEDO_BAM_H
 #define SECEDO_BAM_H
@@ -90,7 +103,33 @@ typedef struct secedo_bam_result_info {
     uint32_t reserved;
 } secedo_bam_result_info;
 
+/* What the last pileup, barcode or scan call on this thread did with its BGZF members. */
+typedef struct secedo_bam_route_info {
+    uint64_t host_blocks;             /* members inflated on the host (device route: the headers' members) */
+    uint64_t device_blocks;           /* members inflated on the device */
+    uint64_t device_records;          /* BAM records walked on the device */
+    uint64_t segments;                /* segments of the device walk */
+    uint64_t rewalked_segments;       /* of those, the ones whose guessed start was no record start */
+    uint64_t uploaded_bytes;          /* compressed bytes uploaded */
+    uint64_t downloaded_record_bytes; /* record bytes of the requested chromosomes downloaded (device route) */
+    uint64_t batches;                 /* device inflate launches */
+} secedo_bam_route_info;
+
+#define SECEDO_BAM_INFLATE_HOST 0   /* the default: zlib in a host pool, host record walk */
+#define SECEDO_BAM_INFLATE_DEVICE 1 /* BAM members inflated and records walked on the GPU */
+
 const char *secedo_bam_last_error(void);
+
+/* The route BAM files take, per process, read at every call. Until it is set, the environment variable
+ * SECEDO_BAM_INFLATE (host or device; unset or empty: host) decides; any other value of it makes every call that
+ * reads BAM, and secedo_bam_get_inflate, fail with SECEDO_E_INVALID_ARG. */
+int secedo_bam_set_inflate(int mode);
+int secedo_bam_get_inflate(int *mode);
+int secedo_bam_route_stats(secedo_bam_route_info *out);
+
+/* secedo_bam_scan with the inflate and the record walk on the GPU: the same info and counts. Needs the GPU. */
+int secedo_bam_scan_device(const char *path, uint32_t num_threads, secedo_bam_scan_info *info,
+                           uint64_t *records_per_ref, uint32_t capacity);
 
 /* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
  * num_threads: inflate pool size, capped at 16 (0 = 1). */

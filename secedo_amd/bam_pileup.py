@@ -50,6 +50,14 @@ class ResultInfo(C.Structure):
                 ("num_cells", C.c_uint32), ("max_read_length", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class RouteInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("host_blocks", "device_blocks", "device_records", "segments",
+                                          "rewalked_segments", "uploaded_bytes", "downloaded_record_bytes",
+                                          "batches")]
+
+
+INFLATE_MODES = {"host": 0, "device": 1}
+
 _vp = C.c_void_p
 _u32 = C.c_uint32
 _files_t = C.POINTER(C.c_char_p)
@@ -72,6 +80,10 @@ SIGNATURES = {
     "secedo_bam_barcodes_fetch": (C.c_int, [_vp, _vp, _vp]),
     "secedo_bam_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "secedo_bam_release": (None, []),
+    "secedo_bam_set_inflate": (C.c_int, [C.c_int]),
+    "secedo_bam_get_inflate": (C.c_int, [C.POINTER(C.c_int)]),
+    "secedo_bam_route_stats": (C.c_int, [C.POINTER(RouteInfo)]),
+    "secedo_bam_scan_device": (C.c_int, [C.c_char_p, _u32, C.POINTER(ScanInfo), _vp, _u32]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
@@ -134,9 +146,50 @@ def _cells(cell_tag, cells):
     return _tag(cell_tag), (C.c_char_p * max(len(vals), 1))(*vals), len(vals)
 
 
-def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], num_threads: int = 1):
+class _route:
+    """The BAM route of the calls inside the block: ``inflate`` is "host" (zlib pool and record walk on the host),
+    "device" (BGZF inflate and record walk on the GPU) or None for the process setting (secedo_bam_set_inflate, else
+    the environment variable SECEDO_BAM_INFLATE). The setting is per process; the block restores what it found."""
+
+    def __init__(self, inflate):
+        if inflate is not None and inflate not in INFLATE_MODES:
+            raise _lib.SecedoError(_lib.E_INVALID_ARG, "inflate is 'host' or 'device', got %r" % (inflate,))
+        self.inflate = inflate
+
+    def __enter__(self):
+        if self.inflate is not None:
+            before = C.c_int(0)
+            check(lib().secedo_bam_get_inflate(C.byref(before)))
+            self.before = before.value
+            check(lib().secedo_bam_set_inflate(INFLATE_MODES[self.inflate]))
+
+    def __exit__(self, *exc):
+        if self.inflate is not None:
+            check(lib().secedo_bam_set_inflate(self.before))
+        return False
+
+
+def set_inflate(inflate: str) -> None:
+    """Sets the process-wide BAM route: "host" or "device" (see ``pileup_bams``'s ``inflate``)."""
+    if inflate not in INFLATE_MODES:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "inflate is 'host' or 'device', got %r" % (inflate,))
+    check(lib().secedo_bam_set_inflate(INFLATE_MODES[inflate]))
+
+
+def bam_route_stats() -> dict:
+    """What the last pileup, barcode or scan call on this thread did: members inflated on the host and on the device,
+    records walked on the device, walk segments and how many of them were re-walked, compressed bytes uploaded, record
+    bytes downloaded, device inflate launches."""
+    info = RouteInfo()
+    check(lib().secedo_bam_route_stats(C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in RouteInfo._fields_}
+
+
+def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], num_threads: int = 1, *,
+                 inflate=None):
     """The distinct Z-typed values of ``tag`` over the records of the given chromosomes of ``files`` (BAM or SAM),
-    sorted bytewise -> (values [str], counts np.uint64: records per value). Needs the GPU."""
+    sorted bytewise -> (values [str], counts np.uint64: records per value). Needs the GPU. ``inflate``: the BAM
+    route, as in ``pileup_bams``."""
     arr, n = _files(files)
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
     n_val, n_bytes = C.c_uint32(0), C.c_uint64(0)
@@ -145,8 +198,9 @@ def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], 
         import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
     except ImportError:
         pass
-    check(lib().secedo_bam_barcodes(arr, n, t, _lib.ptr(ids) if len(ids) else None, len(ids), num_threads,
-                                    C.byref(n_val), C.byref(n_bytes)))
+    with _route(inflate):
+        check(lib().secedo_bam_barcodes(arr, n, t, _lib.ptr(ids) if len(ids) else None, len(ids), num_threads,
+                                        C.byref(n_val), C.byref(n_bytes)))
     k = int(n_val.value)
     buf = C.create_string_buffer(max(int(n_bytes.value), 1))
     off = np.zeros(k + 1, dtype=np.uint64)
@@ -172,12 +226,19 @@ def bgzf_inflate(path) -> np.ndarray:
     return out
 
 
-def bam_scan(path, num_threads: int = 1, max_refs: int = 4096) -> dict:
-    """Header and record summary of one BAM file, no GPU: n_ref, sorted, n_records, n_unmapped, n_blocks,
-    inflated_bytes, l_text and records_per_ref (one count per @SQ entry)."""
+def bam_scan(path, num_threads: int = 1, max_refs: int = 4096, device: bool = False) -> dict:
+    """Header and record summary of one BAM file: n_ref, sorted, n_records, n_unmapped, n_blocks, inflated_bytes,
+    l_text and records_per_ref (one count per @SQ entry). No GPU, unless ``device``: then the members are inflated
+    and the records walked on the GPU, with the same result."""
     info = ScanInfo()
     per = np.zeros(max_refs, dtype=np.uint64)
-    check(lib().secedo_bam_scan(os.fsencode(str(path)), num_threads, C.byref(info), _lib.ptr(per), max_refs))
+    if device:
+        try:
+            import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
+        except ImportError:
+            pass
+    scan = lib().secedo_bam_scan_device if device else lib().secedo_bam_scan
+    check(scan(os.fsencode(str(path)), num_threads, C.byref(info), _lib.ptr(per), max_refs))
     out = {k: int(getattr(info, k)) for k, _ in ScanInfo._fields_ if k != "reserved"}
     out["sorted"] = bool(info.sorted)
     out["records_per_ref"] = per[:min(info.n_ref, max_refs)].copy()
@@ -203,24 +264,30 @@ def _fetch_host(info: ResultInfo) -> FlatPileup:
 def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_file: bool, chromosome_id: int,
                 max_coverage: int, min_base_quality: int, min_map_quality: int, min_alignment_score: int,
                 num_threads: int, min_different: int, times: Optional[dict] = None, *, cell_tag=None,
-                cells=None) -> FlatPileup:
+                cells=None, inflate=None) -> FlatPileup:
     """The reference's pileup_bams() on BAM or SAM files -> a one-chromosome FlatPileup (id_base = cell << 2 |
     base). Writes <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms.
 
     With ``cell_tag`` (e.g. "CB") the files are multiplexed: cell c is the records whose Z-typed ``cell_tag`` value
-    is ``cells[c]``; the result equals this call on the per-cell split files."""
+    is ``cells[c]``; the result equals this call on the per-cell split files.
+
+    ``inflate``: the route BAM files take. "host" (the default setting) inflates them with zlib in a host pool and
+    walks the records on the host; "device" uploads the compressed bytes, inflates them and walks the records on the
+    GPU, and gives the same result; None keeps the process setting (``set_inflate``, SECEDO_BAM_INFLATE)."""
     arr, n = _files(bam_files)
     tag, bcs, n_bcs = _cells(cell_tag, cells)
     info, t = ResultInfo(), Times()
     out = None if out_pileup is None else os.fsencode(str(out_pileup))
-    if tag is None:
-        check(lib().secedo_pileup_bams(arr, n, out, int(bool(write_text_file)), chromosome_id, max_coverage,
-                                       min_base_quality, min_map_quality, min_alignment_score, num_threads,
-                                       min_different, C.byref(info), C.byref(t)))
-    else:
-        check(lib().secedo_pileup_bams_cells(arr, n, out, int(bool(write_text_file)), chromosome_id, max_coverage,
-                                             min_base_quality, min_map_quality, min_alignment_score, num_threads,
-                                             min_different, tag, bcs, n_bcs, C.byref(info), C.byref(t)))
+    with _route(inflate):
+        if tag is None:
+            check(lib().secedo_pileup_bams(arr, n, out, int(bool(write_text_file)), chromosome_id, max_coverage,
+                                           min_base_quality, min_map_quality, min_alignment_score, num_threads,
+                                           min_different, C.byref(info), C.byref(t)))
+        else:
+            check(lib().secedo_pileup_bams_cells(arr, n, out, int(bool(write_text_file)), chromosome_id,
+                                                 max_coverage, min_base_quality, min_map_quality,
+                                                 min_alignment_score, num_threads, min_different, tag, bcs, n_bcs,
+                                                 C.byref(info), C.byref(t)))
     if times is not None:
         times.update(_times(t))
     return _fetch_host(info)
@@ -229,13 +296,14 @@ def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_
 def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequence[int], max_coverage: int = 100,
                          min_base_quality: int = 30, min_map_quality: int = 30, min_alignment_score: int = 0,
                          num_threads: int = 8, min_different: int = 3, id_to_group=None, group_id_to_pos=None,
-                         times: Optional[dict] = None, *, cell_tag=None, cells=None):
+                         times: Optional[dict] = None, *, cell_tag=None, cells=None, inflate=None):
     """Several chromosomes in one pass over the BAM or SAM files, straight into HBM on ``plan``'s device.
 
     -> (res, num_cells, max_read_length): ``res`` is the resident pileup dict of SimilarityMatrixPlan.upload,
     which filter_resident, divide_cluster_resident and variant_calling_resident take; num_cells and
     max_read_length are what read_pileup would report on the written .bin files (maxima over chromosomes).
-    ``cell_tag`` / ``cells``: multiplexed files, as in pileup_bams; id_to_group then maps barcode indices."""
+    ``cell_tag`` / ``cells``: multiplexed files, as in pileup_bams; id_to_group then maps barcode indices.
+    ``inflate``: the BAM route, as in pileup_bams."""
     import torch
 
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
@@ -244,7 +312,7 @@ def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequenc
     i2g = None if id_to_group is None else np.ascontiguousarray(id_to_group, dtype=np.uint16)
     info, t = ResultInfo(), Times()
     dev = "cuda:%d" % plan.device
-    with torch.cuda.device(plan.device):
+    with torch.cuda.device(plan.device), _route(inflate):
         i2g_p, n_i2g = (_lib.ptr(i2g), len(i2g)) if i2g is not None else (None, 0)
         if tag is None:
             check(lib().secedo_pileup_bams_device(arr, n, _lib.ptr(ids), len(ids), max_coverage, min_base_quality,

@@ -9,6 +9,8 @@
 // of BGZF blocks of that size, a record cut at a range's end carried into the next, so one large multiplexed BAM
 // never sits inflated in RAM. Of each file only the byte run of the requested chromosomes' records is kept. No .bai
 // is needed: the run is found by walking block_size, so with or without an index the result is the same.
+// The opt-in device route for BAM (secedo_bam_set_inflate) branches off in load_inputs to bam_device_input.cpp; the
+// BGZF listing, the zlib inflate of one block and the header parse below are what the two routes share.
 #include "bam_host.hpp"
 #include "bam_kernels.hpp"  // the scan wrappers
 #include "bgzf_inflate.hpp"  // the status codes
@@ -30,16 +32,14 @@
 #include <set>
 #include <thread>
 
+// ---- shared with bam_device_input.cpp (declared in bam_host.hpp)
+namespace secedo {
+namespace bam_host {
+
 namespace {
-
-using namespace secedo::bam;
-using namespace secedo::bam_host;
-
-constexpr uint32_t kMaxThreads = 16;
 constexpr uint64_t kBatchBytes = 512ull << 20;
+}
 
-// inflated bytes per batch of files and per block range of one file; SECEDO_BAM_BATCH_BYTES overrides it (tests:
-// outputs do not depend on it), read at every call
 uint64_t batch_bytes() {
     const char *e = std::getenv("SECEDO_BAM_BATCH_BYTES");
     if (e && *e) {
@@ -48,27 +48,6 @@ uint64_t batch_bytes() {
     }
     return kBatchBytes;
 }
-
-template <class F>
-void parallel_for(uint32_t threads, uint64_t n, F f) {
-    threads = std::max<uint32_t>(1, std::min<uint64_t>(std::min(threads, kMaxThreads), n));
-    std::atomic<uint64_t> next{0};
-    auto work = [&] {
-        for (uint64_t i; (i = next.fetch_add(1)) < n;) f(i);
-    };
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < threads; ++t) pool.emplace_back(work);
-    work();
-    for (auto &t : pool) t.join();
-}
-
-struct Mapped {
-    const uint8_t *p = nullptr;
-    size_t n = 0;
-    ~Mapped() {
-        if (p && n) munmap(const_cast<uint8_t *>(p), n);
-    }
-};
 
 int map_file(const std::string &path, Mapped *m) {
     const int fd = open(path.c_str(), O_RDONLY);
@@ -90,12 +69,6 @@ int map_file(const std::string &path, Mapped *m) {
     close(fd);
     return SECEDO_OK;
 }
-
-struct Block {
-    const uint8_t *cdata;
-    uint32_t clen, crc, isize;
-    uint64_t out;  // offset in the file's inflated buffer
-};
 
 // the BGZF block at byte off < m.n of a mapped file (its `out` left 0); *len = its bytes in the file
 int read_block(const std::string &path, const Mapped &m, uint64_t off, Block *blk, uint32_t *len) {
@@ -155,6 +128,34 @@ int open_bgzf(const std::string &path, Mapped *m, std::vector<Block> *blocks, ui
     return list_blocks(path, *m, blocks, total);
 }
 
+// final: d ends the file, so a cut header is an error; else kNeedMore
+int parse_header(const std::string &path, const uint8_t *d, uint64_t n, bool final, Header *h) {
+    if ((n >= 4 && std::memcmp(d, "BAM\1", 4) != 0) || (final && n < 12))
+        return fail(SECEDO_E_INVALID_ARG, path + ": not a BAM file (magic)");
+    if (n < 12) return kNeedMore;
+    h->l_text = rd32(d + 4);
+    uint64_t o = 8 + uint64_t(h->l_text);
+    if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated header") : kNeedMore;
+    h->n_ref = rd32(d + o);
+    o += 4;
+    for (uint32_t r = 0; r < h->n_ref; ++r) {
+        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
+        o += 4 + uint64_t(rd32(d + o));
+        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
+        o += 4;
+    }
+    h->first_record = o;
+    return SECEDO_OK;
+}
+
+}  // namespace bam_host
+}  // namespace secedo
+
+namespace {
+
+using namespace secedo::bam;
+using namespace secedo::bam_host;
+
 struct InflateJob {
     const std::string *path;
     const Block *block;
@@ -166,6 +167,7 @@ struct InflateJob {
 int inflate_blocks(const std::vector<InflateJob> &jobs, uint32_t threads) {
     std::vector<std::string> errs(jobs.size());
     parallel_for(threads, jobs.size(), [&](uint64_t k) { errs[k] = inflate_block(*jobs[k].block, jobs[k].dst); });
+    route().host_blocks += jobs.size();
     for (size_t k = 0; k < jobs.size(); ++k)
         if (!errs[k].empty())
             return fail(SECEDO_E_INVALID_ARG,
@@ -195,33 +197,6 @@ int inflate_files(const std::vector<std::string> &paths, uint32_t threads, std::
             jobs.push_back({&paths[f], &blocks[f][b], b, (*out)[f].data.data() + blocks[f][b].out});
     }
     return inflate_blocks(jobs, threads);
-}
-
-struct Header {
-    uint32_t l_text = 0, n_ref = 0;
-    uint64_t first_record = 0;
-};
-
-constexpr int kNeedMore = 1;  // parse_header / walk_range: the bytes end inside the header or a record
-
-// final: d ends the file, so a cut header is an error; else kNeedMore
-int parse_header(const std::string &path, const uint8_t *d, uint64_t n, bool final, Header *h) {
-    if ((n >= 4 && std::memcmp(d, "BAM\1", 4) != 0) || (final && n < 12))
-        return fail(SECEDO_E_INVALID_ARG, path + ": not a BAM file (magic)");
-    if (n < 12) return kNeedMore;
-    h->l_text = rd32(d + 4);
-    uint64_t o = 8 + uint64_t(h->l_text);
-    if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated header") : kNeedMore;
-    h->n_ref = rd32(d + o);
-    o += 4;
-    for (uint32_t r = 0; r < h->n_ref; ++r) {
-        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
-        o += 4 + uint64_t(rd32(d + o));
-        if (o + 4 > n) return final ? fail(SECEDO_E_INVALID_ARG, path + ": truncated reference list") : kNeedMore;
-        o += 4;
-    }
-    h->first_record = o;
-    return SECEDO_OK;
 }
 
 // (RefID, Position) of one record after another: coordinate order puts the unmapped (RefID < 0) last
@@ -298,8 +273,6 @@ int check_cigar(const uint8_t *rec, const std::string &where) {
         return fail(SECEDO_E_INVALID_ARG, where + ": CIGAR and SEQ lengths differ");
     return SECEDO_OK;
 }
-
-using Runs = std::vector<std::vector<std::vector<uint8_t>>>;  // [chr][file] the file's records of the chromosome
 
 // Per file: its records of each requested chromosome, appended as the walk meets them (one range after another).
 struct FileSink {
@@ -505,6 +478,9 @@ int inflate_range_device(const std::string &path, const Mapped &m, const std::ve
     SECEDO_TRY(hipMemcpyAsync(g->h_status.data(), g->status.p, n_blocks * 4, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     if (t) t->inflate_ms += ms_lap(t0);
+    route().device_blocks += n_blocks;
+    route().uploaded_bytes += uint64_t(hi - lo);
+    route().batches += 1;
     for (size_t k = 0; k < n_blocks; ++k)
         if (g->h_status[k] != secedo::bgzf::kOk)
             return fail(SECEDO_E_INVALID_ARG,
@@ -776,6 +752,7 @@ int load_samgz_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs
         if (!err.empty()) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(hb) + ": " + err);
         ++hb;
     }
+    route().host_blocks += hb;
     SamHeader h;
     SECEDO_CALL(parse_sam_header(path, f, head.data(), head.size(), &h));
     in->line0[f] = h.lines + 1;
@@ -858,6 +835,27 @@ thread_local InflatedFile *g_inflated = nullptr;
 namespace secedo {
 namespace bam_host {
 
+secedo_bam_route_info &route() {
+    static thread_local secedo_bam_route_info r{};
+    return r;
+}
+
+namespace {
+std::atomic<int> g_inflate_mode{-1};  // -1: not set by secedo_bam_set_inflate, the environment decides
+}
+
+int inflate_route(bool *device) {
+    int mode = g_inflate_mode.load();
+    if (mode < 0) {
+        const char *e = std::getenv("SECEDO_BAM_INFLATE");
+        if (!e || !*e || std::strcmp(e, "host") == 0) mode = SECEDO_BAM_INFLATE_HOST;
+        else if (std::strcmp(e, "device") == 0) mode = SECEDO_BAM_INFLATE_DEVICE;
+        else return fail(SECEDO_E_INVALID_ARG, std::string("SECEDO_BAM_INFLATE=") + e + ": expected host or device");
+    }
+    *device = mode == SECEDO_BAM_INFLATE_DEVICE;
+    return SECEDO_OK;
+}
+
 void release_inflated() {
     delete g_inflated;
     g_inflated = nullptr;
@@ -873,6 +871,11 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
                 uint32_t threads, Inputs *in, secedo_bam_times *t) {
     const size_t n_files = files.size();
     const uint64_t batch = batch_bytes();
+    route() = secedo_bam_route_info{};
+    bool device = false;
+    SECEDO_CALL(inflate_route(&device));
+    std::unique_ptr<BamDevWork, void (*)(BamDevWork *)> dev_work(device ? new_bam_dev_work() : nullptr,
+                                                                 delete_bam_dev_work);
     in->paths = files;
     in->line0.assign(n_files, 0);
     in->chrs.resize(n_chr);
@@ -907,6 +910,11 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
             struct stat st;
             disk += stat(files[f1].c_str(), &st) == 0 ? uint64_t(st.st_size) : 0;
             ++f1;
+        }
+        if (device) {  // the opt-in route: device inflate, device walk (bam_device_input.cpp)
+            SECEDO_CALL(load_bams_device(f0, f1, threads, batch, dev_work.get(), in, &runs, t));
+            f0 = f1;
+            continue;
         }
         if (f1 == f0 + 1) {  // one file: walked in block ranges (one range when it inflates to at most `batch`)
             SECEDO_CALL(load_file_ranges(f0, threads, batch, in, &runs, t));
@@ -959,6 +967,7 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
 extern "C" int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_bam_scan_info *info,
                                uint64_t *records_per_ref, uint32_t capacity) {
     if (!path || !info) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    route() = secedo_bam_route_info{};
     std::vector<Inflated> inf;
     SECEDO_CALL(inflate_files({std::string(path)}, num_threads ? num_threads : 1, &inf));
     const std::vector<uint8_t> &d = inf[0].data;
@@ -985,6 +994,28 @@ extern "C" int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_ba
     info->reserved = 0;
     if (records_per_ref)
         for (uint32_t r = 0; r < std::min(capacity, h.n_ref); ++r) records_per_ref[r] = per[r];
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bam_set_inflate(int mode) {
+    if (mode != SECEDO_BAM_INFLATE_HOST && mode != SECEDO_BAM_INFLATE_DEVICE)
+        return fail(SECEDO_E_INVALID_ARG, "secedo_bam_set_inflate: mode " + std::to_string(mode) +
+                                              " is neither SECEDO_BAM_INFLATE_HOST nor SECEDO_BAM_INFLATE_DEVICE");
+    secedo::bam_host::g_inflate_mode.store(mode);
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bam_get_inflate(int *mode) {
+    if (!mode) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    bool device = false;
+    SECEDO_CALL(inflate_route(&device));
+    *mode = device ? SECEDO_BAM_INFLATE_DEVICE : SECEDO_BAM_INFLATE_HOST;
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bam_route_stats(secedo_bam_route_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = route();
     return SECEDO_OK;
 }
 

@@ -47,6 +47,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--min_cell_records", type=int, default=None,
                     help="With --cell_tag and without --cells: cells are the values with at least this many records "
                          "(default 1)")
+    ap.add_argument("--inflate", choices=("host", "device"), default=None,
+                    help="Where BAM files are inflated and their records walked: host (zlib pool) or device (GPU); "
+                         "the outputs are the same. Default: the environment variable SECEDO_BAM_INFLATE, else host")
     return ap.parse_args(argv)
 
 
@@ -158,7 +161,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         else:
             from .bam_pileup import bam_barcodes
 
-            values, counts = bam_barcodes(files, a.cell_tag, ids, pool_size(a.num_threads))
+            values, counts = bam_barcodes(files, a.cell_tag, ids, pool_size(a.num_threads), inflate=a.inflate)
             n = 1 if a.min_cell_records is None else a.min_cell_records
             cells = [v for v, c in zip(values, counts) if int(c) >= n]
             if not cells:
@@ -171,6 +174,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .bam_pileup import pileup_bams
 
     tag_kw = {} if a.cell_tag is None else dict(cell_tag=a.cell_tag, cells=cells)
+    tag_kw["inflate"] = a.inflate
     for chromosome, cid in zip(chromosomes, ids):
         out = a.o + "_" + chromosome + ".pileup"
         p = pileup_bams(files, out, True, cid, a.max_coverage, a.min_base_quality, a.min_map_quality,

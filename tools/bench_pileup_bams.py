@@ -20,6 +20,10 @@ adds the SAM kernels' times and their text GB/s against HBM peak.
 --sam-gz (with --sam) also writes every SAM file as BGZF (<name>.sam.gz, zlib level 6, 65280-byte members) and times
 that route: upload_ms then covers the compressed bytes and inflate_ms the device inflate (k_bgzf_inflate), whose
 inflate_GBps stands beside the BAM route's host zlib pool on the same kind of bytes.
+--device-inflate also runs the BAM calls (the per-file one, and with --multiplexed the tag-mode one) with
+inflate="device": the BGZF members inflated and the records walked on the GPU. Both routes are timed in the same run;
+the line gets the device route's step times, its route stats (bam_route_stats) and whether its files equal the host
+route's.
 Kernel times come from a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_pileup_bams.py --dir D \
         --repeat 1 --resident-only
@@ -259,6 +263,9 @@ def main():
     ap.add_argument("--sam-gz", action="store_true",
                     help="With --sam: also the set as BGZF-compressed SAM (.sam.gz), inflated on the GPU")
     ap.add_argument("--sam-only", action="store_true", help="Only the SAM calls, once each (for rocprofv3)")
+    ap.add_argument("--device-inflate", action="store_true",
+                    help="Also the BAM calls with inflate='device' (BGZF inflate and record walk on the GPU), in the "
+                         "same run as the host route: step times, route stats, outputs compared")
     ap.add_argument("--merge", nargs=2, metavar=("LINE", "PROF_DIR"))
     ap.add_argument("--merge-sam", nargs=2, metavar=("LINE", "PROF_DIR"))
     a = ap.parse_args()
@@ -334,6 +341,11 @@ def main():
             m["bin_equal"] = open(mout + ".bin", "rb").read() == open(out + ".bin", "rb").read()
             m["map_equal"] = open(mout + ".map", "rb").read() == open(out + ".map", "rb").read()
             line["multiplexed"] = m
+        if a.device_inflate:
+            line["device_inflate"] = device_route(a, paths, out, med)
+            if a.multiplexed:
+                line["multiplexed"]["device_inflate"] = device_route(a, [mpath], mout, med, cell_tag="CB",
+                                                                     cells=barcodes)
         if a.sam:
             line["sam"] = sam_route(a, sams, [msam] if msam else None, barcodes if msam else None, out,
                                     mout if msam else None, sam_s, med)
@@ -361,7 +373,7 @@ def main():
     line["records"] = n_rec
     line["record_bytes"] = n_rec * 211  # uniform_cell_bam's fixed record size
     line["window_positions"] = int(a.mbp * 1_000_000)
-    if "sam" in line:
+    if "sam" in line or "device_inflate" in line:
         print_table(line)
     print(json.dumps(line), flush=True)
 
@@ -390,6 +402,27 @@ def write_sam_gz_set(sams, msam):
     with Pool(16) as pool:
         pool.map(_bgzip, jobs, chunksize=4)
     return [s + ".gz" for s in sams], (msam + ".gz" if msam else None)
+
+
+def device_route(a, files, host_out, med, **kw):
+    """The BAM files through inflate='device': step times (medians of --repeat runs after one untimed run), the route
+    stats of the last run, and its outputs against the host route's (host_out)"""
+    from secedo_amd import bam_pileup
+
+    prefix = host_out + "_dev"
+    runs = []
+    for k in range(a.repeat + 1):
+        t = {}
+        bam_pileup.pileup_bams(files, prefix, True, 0, 100, 30, 30, 0, a.threads, 3, times=t, inflate="device", **kw)
+        if k:
+            runs.append(t)
+    r = {key: round(med([x[key] for x in runs]), 2) for key in STEPS}
+    r["inflated_bytes"] = runs[0]["inflated_bytes"]
+    r["inflate_GBps"] = r["inflated_bytes"] / (r["inflate_ms"] * 1e-3) / 1e9
+    r["route_stats"] = bam_pileup.bam_route_stats()
+    for ext in (".bin", ".map", ".txt"):
+        r[ext[1:] + "_equal"] = open(prefix + ext, "rb").read() == open(host_out + ext, "rb").read()
+    return r
 
 
 def sam_route(a, sams, msam, barcodes, out, mout, sam_s, med, prefix="s"):
@@ -422,10 +455,16 @@ def sam_route(a, sams, msam, barcodes, out, mout, sam_s, med, prefix="s"):
 
 
 def print_table(line):
-    rows = [("BAM per-file", line), ("SAM per-file", line["sam"]["per_file"])]
+    rows = [("BAM per-file", line)]
+    if "device_inflate" in line:
+        rows.append(("BAM dev-inflate", line["device_inflate"]))
+    if "sam" in line:
+        rows.append(("SAM per-file", line["sam"]["per_file"]))
     if "multiplexed" in line:
         rows.append(("BAM multiplexed", line["multiplexed"]))
-    if "multiplexed" in line["sam"]:
+        if "device_inflate" in line["multiplexed"]:
+            rows.append(("BAM mux dev-inf", line["multiplexed"]["device_inflate"]))
+    if "sam" in line and "multiplexed" in line["sam"]:
         rows.append(("SAM multiplexed", line["sam"]["multiplexed"]))
     if "sam_gz" in line:
         rows.append(("SAM.gz per-file", line["sam_gz"]["per_file"]))
