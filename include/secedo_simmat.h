@@ -257,6 +257,13 @@ const char *secedo_simmat_pair_kernel(const secedo_simmat_t *handle);
 /* 1 when the last accumulate() corrected its tiles in the epilogue of accumulate_counts (one workgroup per tile),
  * 0 when correct_tiles ran after it or another pair kernel ran. */
 int secedo_simmat_last_correction_fused(const secedo_simmat_t *handle);
+/* 1 when the last accumulate() ran the instance of accumulate_counts that stages one 32-bit word per locus (128-cell
+ * count tile, no locus range of the packing longer than 4094 loci), 0 when it ran the instance with 16-bit offsets
+ * (ranges of up to 8190 loci) or another pair kernel. */
+int secedo_simmat_last_locus_words(const secedo_simmat_t *handle);
+/* Debugging aid: the workgroups the last accumulate() planned for its pair kernel (more than its tiles when a launch
+ * of few tiles gives a tile to several workgroups; 0 before the first accumulate). */
+uint32_t secedo_simmat_last_workgroups(const secedo_simmat_t *handle);
 /* Debugging aid: the sparse-loci path's lists of the flagged entries of the prepared pileup, copied to host memory
  * (synchronises the device). n_flagged: their number; grp (num_blocks * (num_loci + 1) words): flagged entries
  * before each (cell block, locus) group; rec (4 words each) and idx: their records and packed-entry indices. Any of

@@ -87,6 +87,7 @@ struct Scalars {
     uint32_t n_multi_id;        // entries whose read id occurs more than once in its chromosome (k_compact_m)
     uint32_t reads_total;       // reads of the whole pileup (k_arank_m)
     uint32_t n_wide;            // kept entries whose read reaches beyond their 8-locus windows (k_m_records / k_records)
+    uint32_t max_range_span;    // loci of the longest locus range (k_ranges_compact; accumulate_counts' instance)
     unsigned long long id_space;  // sum over chromosomes of (largest - smallest read id + 1)
     unsigned long long multi_entries;
     unsigned long long pair_bound;
@@ -1468,20 +1469,35 @@ __global__ __launch_bounds__(TPB) void k_ranges_compact(const uint32_t *seg_ends
     const uint32_t cap_loci = use_counts ? caps.loci_counts : caps.loci_plain;
     const uint32_t *seg_ends = seg_ends_both + (use_counts ? variant_stride : 0);
     const uint32_t *seg_count = seg_count_both + (use_counts ? variant_stride : 0);
-    __shared__ uint32_t s_base;
+    __shared__ uint32_t s_base, s_span;
     if (threadIdx.x == 0) {
         s_base = 0;
+        s_span = 0;
         range_off[0] = 0;
     }
     __syncthreads();
+    uint32_t span = 0;  // the longest range this thread copies (a segment's first range begins with the segment)
     for (uint32_t seg = 0; seg < n_seg; ++seg) {
         const uint32_t base = s_base, cnt = seg_count[seg];
-        for (uint32_t i = threadIdx.x; i < cnt; i += TPB) range_off[1 + base + i] = seg_ends[(size_t)seg * cap_loci + i];
+        const uint32_t *ends = seg_ends + (size_t)seg * cap_loci;
+        for (uint32_t i = threadIdx.x; i < cnt; i += TPB) {
+            // (the range's begin is the neighbouring lane's end: one load per thread, all loads before the store)
+            const uint32_t e = ends[i];
+            uint32_t begin = __shfl_up(e, 1);
+            if ((threadIdx.x & 63u) == 0) begin = i ? ends[i - 1] : seg * cap_loci;
+            range_off[1 + base + i] = e;
+            span = max(span, e - begin);
+        }
         __syncthreads();
         if (threadIdx.x == 0) s_base = base + cnt;
         __syncthreads();
     }
-    if (threadIdx.x == 0) sc->num_ranges = s_base;
+    atomicMax(&s_span, span);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sc->num_ranges = s_base;
+        sc->max_range_span = s_span;
+    }
 }
 
 // per locus: its chromosome and its index inside its locus range (k_records looks both up per entry)
@@ -2395,6 +2411,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     pk.cap_entries = pk.count_tile ? caps.entries_counts : caps.entries_plain;
     pk.cap_loci = pk.count_tile ? caps.loci_counts : caps.loci_plain;
     pk.num_ranges = hsc.num_ranges;
+    pk.max_range_span = hsc.max_range_span;
     pk.n_wide = hsc.n_wide;
     HIP_OK(hipGetLastError());
     return std::string();

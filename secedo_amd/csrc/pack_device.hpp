@@ -69,6 +69,11 @@ struct DevicePacked {
     bool stage_masks = false;
     bool count_tile = false;
     uint32_t cap_entries = 0, cap_loci = 0;
+    // loci of the longest locus range (unknown: as long as cap_loci allows). A pack_attempt that returns early leaves
+    // the previous call's value: it only picks accumulate_counts' instance, which tests every range's span against
+    // its own capacity before it stages it (a range too long for it is paired from HBM), so a stale value costs
+    // speed, never results
+    uint32_t max_range_span = 0xFFFFFFFFu;
     uint64_t id_space_hint = 0;  // size of the read-id space of the previous call (0: unknown): saves a read-back
     // the single-entry fast path pays when most reads have one entry: a call that finds more than half of the
     // entries in multi-entry reads finishes without it, and the handle's next calls do not try (every 16th does)

@@ -326,6 +326,8 @@ int choose_correction(secedo_simmat *h, const TileSet &t, bool overwrite, secedo
     const double per_block_locus = h->pk.num_loci && h->pk.num_blocks
             ? (double)h->pk.num_entries / h->pk.num_loci / h->pk.num_blocks : 0.0;
     a->group_hint = per_block_locus < 2.5 ? 2 : per_block_locus < 3.2 ? 3 : 4;
+    // the instance with a staged word per locus holds half the loci of a range: by the longest range the packing cut
+    a->short_ranges = h->pk.block_cells == 128 && h->pk.max_range_span <= secedo::kCapL128W;
     return SECEDO_OK;
 }
 
@@ -371,6 +373,7 @@ int accumulate_impl(secedo_simmat *h, double eps, double hr, double theta, TileS
     SECEDO_TRY(hipMemsetAsync(h->counters.p, 0, 96 * sizeof(unsigned long long), s));
     if (beyond) SECEDO_TRY(hipMemsetAsync(h->beyond_count.p, 0, sizeof(uint32_t), s));
     h->last_fused = false;
+    h->last_locus_words = false;
     if (h->pk.count_tile && !h->pk.stage_masks) SECEDO_CALL(choose_correction(h, t, overwrite, &a));
     SECEDO_TRY(hipEventRecord(h->ev_begin, s));
     // 16-bit pair counters per cell pair are safe when no cell pair can collect 65536 pairs
@@ -379,7 +382,7 @@ int accumulate_impl(secedo_simmat *h, double eps, double hr, double theta, TileS
     a.slab = h->slab.p;
     h->timed_mid = count_tile && !h->pk.stage_masks;
     SECEDO_TRY(secedo::launch_accumulate(a, h->pk.block_cells, h->pk.stage_masks, count_tile, n_tiles, s,
-                                         h->timed_mid ? h->ev_mid : nullptr));
+                                         h->timed_mid ? h->ev_mid : nullptr, &h->last_locus_words));
     if (beyond) SECEDO_CALL(add_beyond_terms(h, eps, hr, theta, d_acc, s));
     h->timed_mid = h->timed_mid && n_tiles > 0;
     SECEDO_TRY(hipEventRecord(h->ev_end, s));

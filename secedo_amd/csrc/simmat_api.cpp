@@ -102,6 +102,9 @@ int adopt_host_packing(secedo::PackedPileup &from, secedo::DevicePacked *pk) {
     pk->cap_entries = from.cap_entries;
     pk->cap_loci = from.cap_loci;
     pk->num_ranges = static_cast<uint32_t>(from.range_off.size()) - 1;
+    pk->max_range_span = 0;
+    for (size_t r = 0; r + 1 < from.range_off.size(); ++r)
+        pk->max_range_span = std::max(pk->max_range_span, from.range_off[r + 1] - from.range_off[r]);
     return SECEDO_OK;
 }
 
@@ -548,6 +551,10 @@ const char *secedo_simmat_pair_kernel(const secedo_simmat_t *h) {
 }
 
 int secedo_simmat_last_correction_fused(const secedo_simmat_t *h) { return h && h->last_fused ? 1 : 0; }
+
+int secedo_simmat_last_locus_words(const secedo_simmat_t *h) { return h && h->last_locus_words ? 1 : 0; }
+
+uint32_t secedo_simmat_last_workgroups(const secedo_simmat_t *h) { return h ? h->plan_workgroups : 0; }
 
 int secedo_simmat_debug_flag_lists(secedo_simmat_t *h, uint64_t *n_flagged, uint32_t *grp, uint32_t *rec,
                                    uint32_t *idx) {

@@ -217,6 +217,7 @@ struct secedo_simmat {
     bool timed_mid = false;
     bool timed = false;
     bool last_fused = false;  // the last accumulate corrected its tiles in accumulate_counts' epilogue
+    bool last_locus_words = false;  // ... ran accumulate_counts' instance with a staged word per locus
 };
 
 namespace secedo {

@@ -684,7 +684,12 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
 // incidence of two different cells as a single-locus pair, whatever the reads' flags:
 //
 //   * ITEMS. A thread keeps its JPT row-side entries of the range in registers, each packed with what its
-//     pairs need: {cell | base (9 bits), first column entry j (14), column entries c (8)}.
+//     pairs need: {cell | base (9 bits), first column entry j (14), column entries c (8)}. Two instances (WORDS):
+//     the loci of a staged range are 16-bit offsets into the column entries (ranges of up to 8190 loci; an item
+//     reads two of them and subtracts), or -- when no range of the packing spans more than 4094 loci, which the
+//     packing reports (DevicePacked::max_range_span) -- one 32-bit word per locus that already is {j, c} in the
+//     item's layout: an item off the diagonal is one LDS read and one and-or. Diagonal tiles (the entries AFTER this
+//     one: j of its own) and the wide path (c beyond its 8 bits) take the end of a locus from the next locus' word.
 //   * GROUPS OF FOUR. A wave takes 64 items and pairs each with its first four column entries: four LDS
 //     reads in flight at once, straight-line code, no loop, no flag test, no branch. 79 % of the slots
 //     hold a pair when loci are sparse (c ~ Poisson(3.8)).
@@ -719,7 +724,14 @@ constexpr uint32_t IT_REC_MASK = 0x1FFu;  // cell (7 bits) | base (2 bits)
 template <int B, int THREADS, int NCNT>
 __device__ __forceinline__ void correct_epilogue(const AccumulateArgs &a, unsigned char *lds, uint32_t t_local,
                                                  const uint32_t (&cnt)[NCNT]);
-template <int B, int THREADS, int CAPJ, int CAPL, int GROUP>
+// first column entry of a staged locus (of the slot behind the last locus: the end of the range's column side): the
+// 16-bit offset itself, or with WORDS the j field of the locus' word (the array begins where the offsets would)
+template <bool WORDS>
+__device__ __forceinline__ uint32_t counts_off_at(const uint16_t *sOff, uint32_t l) {
+    if constexpr (WORDS) return (reinterpret_cast<const uint32_t *>(sOff)[l] >> IT_J_SHIFT) & IT_J_MASK;
+    else return sOff[l];
+}
+template <int B, int THREADS, int CAPJ, int CAPL, int GROUP, bool WORDS>
 __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArgs a) {
     static_assert(CAPJ <= 16384, "14 bits of column index in an item");
     static_assert(GROUP >= 2 && GROUP <= 4, "group size");
@@ -734,12 +746,19 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
     constexpr int RING = COUNTS_RING;
 
     // LDS: [ tile | sJ CAPJ u32 (col32_of: column byte offset | base << 16, made of entry32 when a range is staged: a
-    // copy of the entries in that form cost the packing a 4-byte store per entry) | sOff CAPL+2 u16 | per wave: ring ]
+    // copy of the entries in that form cost the packing a 4-byte store per entry) | per locus, CAPL+2 of them: sOff u16,
+    // or with WORDS a u32 word in the same place | per wave: ring ]
+    // WORDS: a staged locus is the word an item takes from it -- {first column entry << IT_J_SHIFT, column entries
+    // (at most 255) << IT_C_SHIFT} -- and an item is one LDS read and one v_and_or, where the u16 offsets cost it two
+    // reads, a subtraction, a compare, a select and the shifts. At 4 bytes a locus the array holds half the loci in
+    // the same LDS: the instance of launches whose ranges all span at most CAPL loci (AccumulateArgs::short_ranges).
+    // (The words are reached through sOff and counts_off_at: with a second pointer into the array and a lambda over both,
+    // the instances WITHOUT words came out with column-entry staging stores that no longer paired into ds_write2st64.)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     uint32_t *tile32 = reinterpret_cast<uint32_t *>(lds_raw);
     uint32_t *sJ = reinterpret_cast<uint32_t *>(lds_raw + TILE_BYTES);
     uint16_t *sOff = reinterpret_cast<uint16_t *>(sJ + CAPJ);
-    uint32_t *ring = reinterpret_cast<uint32_t *>(sOff + CAPL + 2) + (threadIdx.x >> 6) * RING;
+    uint32_t *ring = reinterpret_cast<uint32_t *>(sOff + (CAPL + 2) * (WORDS ? 2 : 1)) + (threadIdx.x >> 6) * RING;
 
     const uint32_t t_local = a.wg_tile[blockIdx.x];
     const uint32_t t = a.tile_ids ? a.tile_ids[t_local] : a.tile_begin + t_local;
@@ -787,6 +806,10 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
 
     // the next range, in flight in registers while the current one is paired
     uint32_t pJ[JPT], pI[JPT], pO[OPT];
+    // WORDS: the offset behind each of pO, for the locus' number of column entries (the same cache lines loaded
+    // again, one place on: no lane exchange, no word through LDS for the wave's last lane, and with half the
+    // offsets per thread as many registers as pO alone has otherwise)
+    uint32_t pO1[WORDS ? OPT : 1];
     uint32_t n_la = 0, n_lb = 0, n_ib = 0, n_ie = 0, n_jb = 0, n_je = 0, n_dsh = 0;
     bool n_staged = false;
     uint32_t q_la = 0, q_lb = 0;  // locus span of the range `ahead` holds the offsets of
@@ -825,6 +848,11 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
 #pragma unroll
             for (int k = 0; k < OPT; ++k)
                 pO[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(ro, (int)(tid * 4u), k * THREADS * 4, 0);
+            if (WORDS) {
+#pragma unroll
+                for (int k = 0; k < OPT; ++k)
+                    pO1[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(ro, (int)(tid * 4u + 4u), k * THREADS * 4, 0);
+            }
         }
     };
     // the row side of the range prefetch() described; issued later, when the registers of the current
@@ -1021,8 +1049,18 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
 #pragma unroll
                 for (int k = 0; k < JPT; ++k)  // the column side's form of an entry: col32_of(cell in block, base)
                     sJ[tid + k * THREADS] = ((pJ[k] & C_CELL) << 2) | ((pJ[k] << (16 - C_BASE_SHIFT)) & 0x30000u);
+                if (WORDS) {
+                    // (c is clamped to its field: 255 is wide all the same, and the wide path takes the true number
+                    // from two neighbouring words. The slot behind the last locus has the zero of the buffer load for
+                    // pO1: its c is 255 and nobody reads it; slots further on hold garbage nobody reads.)
 #pragma unroll
-                for (int k = 0; k < OPT; ++k) sOff[tid + k * THREADS] = (uint16_t)(pO[k] - jb);
+                    for (int k = 0; k < OPT; ++k)
+                        reinterpret_cast<uint32_t *>(sOff)[tid + k * THREADS] = (((pO[k] - jb) & IT_J_MASK) << IT_J_SHIFT)
+                                                | (min(pO1[k] - pO[k], 255u) << IT_C_SHIFT);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < OPT; ++k) sOff[tid + k * THREADS] = (uint16_t)(pO[k] - jb);
+                }
             }
             __syncthreads();
             STAMP(s2);
@@ -1034,19 +1072,36 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                 // sJ[j0 .. j0 + c); in a diagonal tile the entries after this one (each pair once)
                 uint32_t item[JPT];
                 uint32_t any_wide = 0;
+                if (WORDS && !DIAG) {
+                    // the locus' word is the item but for the row entry's cell and base. (A slot past the row side has
+                    // the zero of the buffer load, locus 0: no item. Its word is read all the same, and all reads are
+                    // issued before the first is used: with the read inside the conditional the compiler branches
+                    // around each and waits for each by itself -- the step 1.5 % slower than with the u16 offsets.)
+                    uint32_t word[JPT];
 #pragma unroll
-                for (int k = 0; k < JPT; ++k) {
-                    const uint32_t i = tid + k * THREADS;
-                    const uint32_t rec = pI[k];
-                    const uint32_t lrel = rec >> 16;
-                    uint32_t j0 = sOff[lrel];
-                    const uint32_t j1 = sOff[lrel + 1];
-                    if (DIAG) j0 = i + dsh + 1u;
-                    const uint32_t c = (i < nI && j1 > j0) ? j1 - j0 : 0u;
-                    any_wide |= c;
-                    // (j0 can be CAPJ when c is 0: the last entry of a full diagonal range; c >= 256 spills into
-                    // nothing: the item is rebuilt below)
-                    item[k] = (rec & IT_REC_MASK) | ((j0 & IT_J_MASK) << IT_J_SHIFT) | (c << IT_C_SHIFT);
+                    for (int k = 0; k < JPT; ++k) word[k] = reinterpret_cast<const uint32_t *>(sOff)[pI[k] >> 16];
+#pragma unroll
+                    for (int k = 0; k < JPT; ++k) {
+                        item[k] = tid + k * THREADS < nI ? (pI[k] & IT_REC_MASK) | word[k] : 0u;
+                        any_wide |= item[k];
+                    }
+                    any_wide >>= IT_C_SHIFT;
+                } else {
+                    // (diagonal tiles: the end of the locus' column entries is the next locus' first)
+#pragma unroll
+                    for (int k = 0; k < JPT; ++k) {
+                        const uint32_t i = tid + k * THREADS;
+                        const uint32_t rec = pI[k];
+                        const uint32_t lrel = rec >> 16;
+                        uint32_t j0 = counts_off_at<WORDS>(sOff, lrel);
+                        const uint32_t j1 = counts_off_at<WORDS>(sOff, lrel + 1);
+                        if (DIAG) j0 = i + dsh + 1u;
+                        const uint32_t c = (i < nI && j1 > j0) ? j1 - j0 : 0u;
+                        any_wide |= c;
+                        // (j0 can be CAPJ when c is 0: the last entry of a full diagonal range; c >= 256 spills into
+                        // nothing: the item is rebuilt below)
+                        item[k] = (rec & IT_REC_MASK) | ((j0 & IT_J_MASK) << IT_J_SHIFT) | (c << IT_C_SHIFT);
+                    }
                 }
                 // wide entries (deep loci; none when loci are sparse: one test for the thread's JPT items): the
                 // whole wave pairs one row entry with 64 column entries at a time, right here
@@ -1056,8 +1111,8 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                         const uint32_t i = tid + k * THREADS;
                         const uint32_t rec = pI[k];
                         const uint32_t lrel = rec >> 16;
-                        uint32_t j0 = sOff[lrel];
-                        const uint32_t j1 = sOff[lrel + 1];
+                        uint32_t j0 = counts_off_at<WORDS>(sOff, lrel);
+                        const uint32_t j1 = counts_off_at<WORDS>(sOff, lrel + 1);
                         if (DIAG) j0 = i + dsh + 1u;
                         const uint32_t c = (i < nI && j1 > j0) ? j1 - j0 : 0u;
                         unsigned long long todo = __ballot(c >= IT_WIDE);
@@ -2436,13 +2491,13 @@ hipError_t launch_masks(const AccumulateArgs &args, uint32_t grid, hipStream_t s
     return hipGetLastError();
 }
 
-template <int B, int THREADS, int CAPJ, int CAPL, int GROUP>
+template <int B, int THREADS, int CAPJ, int CAPL, int GROUP, bool WORDS = false>
 hipError_t launch_counts(const AccumulateArgs &args, uint32_t grid, hipStream_t stream, hipEvent_t mid) {
-    constexpr size_t lds = ((size_t)B * (B + 1) * 4 + 15) / 16 * 16 + (size_t)CAPJ * 4 + ((size_t)CAPL + 2) * 2
-            + (size_t)(THREADS / 64) * (size_t)COUNTS_RING * 4;
+    constexpr size_t lds = ((size_t)B * (B + 1) * 4 + 15) / 16 * 16 + (size_t)CAPJ * 4
+            + ((size_t)CAPL + 2) * (WORDS ? 4 : 2) + (size_t)(THREADS / 64) * (size_t)COUNTS_RING * 4;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static_assert((CAPL + 2) % 4 == 0 && CAPJ % 8 == 0, "alignment of the LDS carve-up");
-    auto kern = &accumulate_counts<B, THREADS, CAPJ, CAPL, GROUP>;
+    auto kern = &accumulate_counts<B, THREADS, CAPJ, CAPL, GROUP, WORDS>;
     static thread_local int configured_device = -1;  // the attribute is per device and sticky
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -2543,7 +2598,9 @@ StageGeometry stage_geometry(uint32_t block_cells) {
 }
 
 hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, bool stage_masks,
-                             bool count_tile, uint32_t n_tiles, hipStream_t stream, hipEvent_t mid) {
+                             bool count_tile, uint32_t n_tiles, hipStream_t stream, hipEvent_t mid,
+                             bool *locus_words) {
+    if (locus_words) *locus_words = false;
     if (n_tiles == 0) return hipSuccess;
     const uint32_t grid = args.n_workgroups;
     const bool counts_path = count_tile && !stage_masks;
@@ -2560,6 +2617,14 @@ hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, b
     }
     if (block_cells == 128) {
         // the 128 KiB int64 tile leaves no room for the window masks: joint terms go through HBM
+        if (count_tile && args.short_ranges) {  // a staged word per locus: half the loci per range in the same LDS
+            if (locus_words) *locus_words = true;
+            if (args.group_hint == 2)
+                return launch_counts<128, 1024, kCapJ128C, kCapL128W, 2, true>(args, grid, stream, mid);
+            if (args.group_hint == 3)
+                return launch_counts<128, 1024, kCapJ128C, kCapL128W, 3, true>(args, grid, stream, mid);
+            return launch_counts<128, 1024, kCapJ128C, kCapL128W, 4, true>(args, grid, stream, mid);
+        }
         if (count_tile) {
             if (args.group_hint == 2) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 2>(args, grid, stream, mid);
             if (args.group_hint == 3) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 3>(args, grid, stream, mid);

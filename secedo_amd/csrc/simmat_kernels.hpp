@@ -25,6 +25,9 @@ constexpr uint32_t kCapJ128 = 4096, kCapL128 = 2046, kCapJ128M = 4096, kCapL128M
 // (pack_device.hip): 6144 2.60 ms, 8192 2.34, 10240 2.33, 12288 2.24 (a range's two barriers, its staging and
 // its prefetch are paid per range; 14336 needs the rings halved and 116 VGPRs: 2.5)
 constexpr uint32_t kCapJ128C = 12288, kCapL128C = 8190;
+// accumulate_counts' instance with a staged 32-bit word per locus, in the LDS of kCapL128C 16-bit offsets: the
+// kernel of launches whose locus ranges all span at most this many loci (the ranges are cut for kCapL128C all the same)
+constexpr uint32_t kCapL128W = 4094;
 constexpr double kMasksThreshold = 0.05;  // stage the masks when > 5 % of the entries are multi-locus
 
 // Everything only the rare paths touch lives in HBM behind one pointer, so that the kernel's
@@ -78,6 +81,7 @@ struct AccumulateArgs {
     const uint4 *flag_rec = nullptr;        // their full entries ...
     const uint32_t *flag_idx = nullptr;     // ... and entry indices
     int group_hint = 4;                     // GROUP of accumulate_counts by the entries per (cell block, locus)
+    bool short_ranges = false;              // no locus range spans more than kCapL128W loci (128-cell count tile)
     bool overwrite = false;                 // acc[tiles of the launch] = result (no need to zero them first)
     bool masks_kernel = false;              // staged masks: accumulate_masks (+ wide_pairs) instead of accumulate_tiles
     const uint32_t *mk_y = nullptr, *mk_xcol = nullptr, *mk_xrow = nullptr;  // ... the entries' words (masks_words)
@@ -117,9 +121,11 @@ size_t accumulate_slab_bytes(uint32_t block_cells, bool count_tile, uint32_t n_w
 // entries' lists in AccumulateArgs; stage_masks (accumulate_masks, or accumulate_tiles with MASKS) exists for 64-cell
 // tiles only; neither: accumulate_tiles with the int64 tile. Unless args.overwrite the accumulator is added to.
 // mid: when non-null, recorded on `stream` between the pair kernel and what follows it (the duration of the
-// dominant kernel by itself: secedo_simmat_last_pair_kernel_ms)
+// dominant kernel by itself: secedo_simmat_last_pair_kernel_ms). locus_words: when non-null, whether the launch
+// took accumulate_counts' instance with a staged word per locus (set where the instance is picked)
 hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, bool stage_masks,
-                             bool count_tile, uint32_t n_tiles, hipStream_t stream, hipEvent_t mid = nullptr);
+                             bool count_tile, uint32_t n_tiles, hipStream_t stream, hipEvent_t mid = nullptr,
+                             bool *locus_words = nullptr);
 
 // mode 0..2 = SECEDO_NORM_*, 3 = raw D
 hipError_t launch_finalize(const int64_t *acc, const uint16_t *tile_row, const uint16_t *tile_col, uint32_t n_tiles,
