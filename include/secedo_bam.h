@@ -58,6 +58,24 @@
  * the lowest record. The route fills secedo_bam_times as BGZF SAM does: inflate_ms is the header's host inflate plus
  * the device inflate, upload_ms the staging and upload of the compressed bytes, walk_ms the device walk and the
  * read-back of the records.
+ *
+ * Reading through the .bai index (opt-in: secedo_bam_set_index, or SECEDO_BAM_INDEX=auto|require in the environment;
+ * the default is off, and then no index file is opened). The index file is <path>.bai, else <path without .bam>.bai;
+ * its modification time is not consulted. Of an indexed BAM only the members of the header and of the requested
+ * chromosomes' spans are inflated and walked, on either route: per reference the index gives where its records start
+ * and end (bam_index.hpp); spans whose members touch or overlap are read as one; the members of a span are found by
+ * following BSIZE from its first, so the file is never listed in full. For a coordinate-sorted BAM with a matching
+ * index every call returns exactly what it returns with the index off. AUTO reads a BAM without an index file, or with
+ * one that fails the file-level checks (magic, n_ref against the BAM header, and for the start and the end of every
+ * reference: coffset below the file size, a BGZF member at it, uoffset within its ISIZE, start <= end), in full; REQUIRE makes that SECEDO_E_INVALID_ARG, naming the
+ * BAM and the reason. An index that passes those checks and still does not fit the file is SECEDO_E_INVALID_ARG in
+ * both modes ("<bam>: index does not match the file (...); re-index it or use --index off"): the record at a
+ * chromosome's start has another RefID, the record chain from a span's start breaks or does not land on its end, the
+ * pseudo-bin's count differs from the records between start and end, or the record at the end offset, where the
+ * span's last member holds it, still has the chromosome's RefID. The whole-file ordinals of an indexed file are
+ * unknown: messages say "indexed record k" (k counts from the first record of the file's first span) and "BGZF
+ * block at byte <coffset>". A defect outside every span is not seen. SAM, BGZF SAM and secedo_bam_scan[_device]
+ * never use an index.
  */
 #ifndef SECEDO_BAM_H
 #define SECEDO_BAM_H
@@ -118,7 +136,36 @@ typedef struct secedo_bam_route_info {
 #define SECEDO_BAM_INFLATE_HOST 0   /* the default: zlib in a host pool, host record walk */
 #define SECEDO_BAM_INFLATE_DEVICE 1 /* BAM members inflated and records walked on the GPU */
 
+/* What the last pileup or barcode call on this thread did with the .bai indexes of its BAM files. */
+typedef struct secedo_bam_index_info {
+    uint64_t files_indexed;   /* BAM files read through their index */
+    uint64_t files_full;      /* BAM files read in full under AUTO: no index file, or a rejected one */
+    uint64_t rejected;        /* of those, the ones whose index file failed the file-level checks */
+    uint64_t spans;           /* spans read (member runs of the requested chromosomes, merged where they touch) */
+    uint64_t members;         /* BGZF members of those spans */
+    uint64_t members_skipped; /* members known to be skipped; needs the member listing, so 0 for an indexed file */
+} secedo_bam_index_info;
+
+#define SECEDO_BAM_INDEX_OFF 0     /* the default: no index file is opened, every member is read */
+#define SECEDO_BAM_INDEX_AUTO 1    /* a BAM with a usable .bai is read through it, any other in full */
+#define SECEDO_BAM_INDEX_REQUIRE 2 /* a BAM without a usable .bai is SECEDO_E_INVALID_ARG */
+
 const char *secedo_bam_last_error(void);
+
+/* Whether BAM files are read through their .bai index, per process, read at every call. Until it is set, the
+ * environment variable SECEDO_BAM_INDEX (off, auto or require; unset or empty: off) decides; any other value of it
+ * makes every call that reads BAM, and secedo_bam_get_index, fail with SECEDO_E_INVALID_ARG. */
+int secedo_bam_set_index(int mode);
+int secedo_bam_get_index(int *mode);
+int secedo_bam_index_stats(secedo_bam_index_info *out);
+
+/* Host only, no GPU: what the index beside bam_path (<path>.bai, else <path without .bam>.bai) says of each
+ * reference r < min(capacity, *n_ref): the virtual offsets (coffset << 16 | uoffset) where its records start and
+ * end, both 0 for a reference without records, and its record count from the pseudo-bin, UINT64_MAX where the index
+ * has none. The file-level checks against the BAM are made; a missing or rejected index is SECEDO_E_INVALID_ARG.
+ * Any array may be NULL. */
+int secedo_bam_index_ranges(const char *bam_path, uint32_t *n_ref, uint64_t *beg, uint64_t *end, uint64_t *count,
+                            uint32_t capacity);
 
 /* The route BAM files take, per process, read at every call. Until it is set, the environment variable
  * SECEDO_BAM_INFLATE (host or device; unset or empty: host) decides; any other value of it makes every call that

@@ -56,7 +56,13 @@ class RouteInfo(C.Structure):
                                           "batches")]
 
 
+class IndexInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("files_indexed", "files_full", "rejected", "spans", "members",
+                                          "members_skipped")]
+
+
 INFLATE_MODES = {"host": 0, "device": 1}
+INDEX_MODES = {"off": 0, "auto": 1, "require": 2}
 
 _vp = C.c_void_p
 _u32 = C.c_uint32
@@ -83,6 +89,10 @@ SIGNATURES = {
     "secedo_bam_set_inflate": (C.c_int, [C.c_int]),
     "secedo_bam_get_inflate": (C.c_int, [C.POINTER(C.c_int)]),
     "secedo_bam_route_stats": (C.c_int, [C.POINTER(RouteInfo)]),
+    "secedo_bam_set_index": (C.c_int, [C.c_int]),
+    "secedo_bam_get_index": (C.c_int, [C.POINTER(C.c_int)]),
+    "secedo_bam_index_stats": (C.c_int, [C.POINTER(IndexInfo)]),
+    "secedo_bam_index_ranges": (C.c_int, [C.c_char_p, C.POINTER(_u32), _vp, _vp, _vp, _u32]),
     "secedo_bam_scan_device": (C.c_int, [C.c_char_p, _u32, C.POINTER(ScanInfo), _vp, _u32]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
@@ -149,12 +159,17 @@ def _cells(cell_tag, cells):
 class _route:
     """The BAM route of the calls inside the block: ``inflate`` is "host" (zlib pool and record walk on the host),
     "device" (BGZF inflate and record walk on the GPU) or None for the process setting (secedo_bam_set_inflate, else
-    the environment variable SECEDO_BAM_INFLATE). The setting is per process; the block restores what it found."""
+    the environment variable SECEDO_BAM_INFLATE). ``index`` likewise: "off", "auto" or "require" (``pileup_bams``), or
+    None for the process setting (secedo_bam_set_index, else SECEDO_BAM_INDEX). The settings are per process; the block
+    restores what it found."""
 
-    def __init__(self, inflate):
+    def __init__(self, inflate, index=None):
         if inflate is not None and inflate not in INFLATE_MODES:
             raise _lib.SecedoError(_lib.E_INVALID_ARG, "inflate is 'host' or 'device', got %r" % (inflate,))
+        if index is not None and index not in INDEX_MODES:
+            raise _lib.SecedoError(_lib.E_INVALID_ARG, "index is 'off', 'auto' or 'require', got %r" % (index,))
         self.inflate = inflate
+        self.index = index
 
     def __enter__(self):
         if self.inflate is not None:
@@ -162,8 +177,15 @@ class _route:
             check(lib().secedo_bam_get_inflate(C.byref(before)))
             self.before = before.value
             check(lib().secedo_bam_set_inflate(INFLATE_MODES[self.inflate]))
+        if self.index is not None:
+            before = C.c_int(0)
+            check(lib().secedo_bam_get_index(C.byref(before)))
+            self.index_before = before.value
+            check(lib().secedo_bam_set_index(INDEX_MODES[self.index]))
 
     def __exit__(self, *exc):
+        if self.index is not None:
+            check(lib().secedo_bam_set_index(self.index_before))
         if self.inflate is not None:
             check(lib().secedo_bam_set_inflate(self.before))
         return False
@@ -176,6 +198,37 @@ def set_inflate(inflate: str) -> None:
     check(lib().secedo_bam_set_inflate(INFLATE_MODES[inflate]))
 
 
+def set_index(index: str) -> None:
+    """Sets the process-wide use of .bai indexes: "off", "auto" or "require" (see ``pileup_bams``'s ``index``)."""
+    if index not in INDEX_MODES:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "index is 'off', 'auto' or 'require', got %r" % (index,))
+    check(lib().secedo_bam_set_index(INDEX_MODES[index]))
+
+
+def bam_index_stats() -> dict:
+    """What the last pileup or barcode call on this thread did with the indexes of its BAM files: files_indexed,
+    files_full (read in full under "auto"), rejected (of those, index files that failed the file-level checks), spans
+    and members read through an index, members_skipped (0 for an indexed file: it is never listed in full)."""
+    info = IndexInfo()
+    check(lib().secedo_bam_index_stats(C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in IndexInfo._fields_}
+
+
+def bam_index_ranges(path, max_refs: int = 4096) -> dict:
+    """What the .bai beside the BAM ``path`` (<path>.bai, else <path without .bam>.bai) says of each reference ->
+    dict(start, end: np.uint64 virtual offsets (coffset << 16 | uoffset), both 0 for a reference without records;
+    count: np.int64 records from the pseudo-bin, -1 where the index has none). The file-level checks against the BAM
+    are made; a missing or rejected index raises SecedoError. No GPU."""
+    n = C.c_uint32(0)
+    beg = np.zeros(max_refs, dtype=np.uint64)
+    end = np.zeros(max_refs, dtype=np.uint64)
+    cnt = np.zeros(max_refs, dtype=np.uint64)
+    check(lib().secedo_bam_index_ranges(os.fsencode(str(path)), C.byref(n), _lib.ptr(beg), _lib.ptr(end),
+                                        _lib.ptr(cnt), max_refs))
+    k = min(int(n.value), max_refs)
+    return dict(start=beg[:k].copy(), end=end[:k].copy(), count=cnt[:k].view(np.int64).copy())
+
+
 def bam_route_stats() -> dict:
     """What the last pileup, barcode or scan call on this thread did: members inflated on the host and on the device,
     records walked on the device, walk segments and how many of them were re-walked, compressed bytes uploaded, record
@@ -186,10 +239,10 @@ def bam_route_stats() -> dict:
 
 
 def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], num_threads: int = 1, *,
-                 inflate=None):
+                 inflate=None, index=None):
     """The distinct Z-typed values of ``tag`` over the records of the given chromosomes of ``files`` (BAM or SAM),
     sorted bytewise -> (values [str], counts np.uint64: records per value). Needs the GPU. ``inflate``: the BAM
-    route, as in ``pileup_bams``."""
+    route, and ``index``: the use of .bai indexes, both as in ``pileup_bams``."""
     arr, n = _files(files)
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
     n_val, n_bytes = C.c_uint32(0), C.c_uint64(0)
@@ -198,7 +251,7 @@ def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], 
         import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
     except ImportError:
         pass
-    with _route(inflate):
+    with _route(inflate, index):
         check(lib().secedo_bam_barcodes(arr, n, t, _lib.ptr(ids) if len(ids) else None, len(ids), num_threads,
                                         C.byref(n_val), C.byref(n_bytes)))
     k = int(n_val.value)
@@ -264,7 +317,7 @@ def _fetch_host(info: ResultInfo) -> FlatPileup:
 def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_file: bool, chromosome_id: int,
                 max_coverage: int, min_base_quality: int, min_map_quality: int, min_alignment_score: int,
                 num_threads: int, min_different: int, times: Optional[dict] = None, *, cell_tag=None,
-                cells=None, inflate=None) -> FlatPileup:
+                cells=None, inflate=None, index=None) -> FlatPileup:
     """The reference's pileup_bams() on BAM or SAM files -> a one-chromosome FlatPileup (id_base = cell << 2 |
     base). Writes <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms.
 
@@ -273,12 +326,19 @@ def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_
 
     ``inflate``: the route BAM files take. "host" (the default setting) inflates them with zlib in a host pool and
     walks the records on the host; "device" uploads the compressed bytes, inflates them and walks the records on the
-    GPU, and gives the same result; None keeps the process setting (``set_inflate``, SECEDO_BAM_INFLATE)."""
+    GPU, and gives the same result; None keeps the process setting (``set_inflate``, SECEDO_BAM_INFLATE).
+
+    ``index``: whether BAM files are read through their .bai index (<path>.bai, else <path without .bam>.bai). "off"
+    (the default setting) opens no index and reads every BGZF member; "auto" reads of a BAM with a usable index only
+    the members that hold the chromosome's records, and any other BAM in full; "require" raises for a BAM without a
+    usable index. For coordinate-sorted BAMs with a matching index the result is the same; an index that does not
+    match its BAM raises. None keeps the process setting (``set_index``, SECEDO_BAM_INDEX). ``bam_index_stats()`` says
+    what the call did."""
     arr, n = _files(bam_files)
     tag, bcs, n_bcs = _cells(cell_tag, cells)
     info, t = ResultInfo(), Times()
     out = None if out_pileup is None else os.fsencode(str(out_pileup))
-    with _route(inflate):
+    with _route(inflate, index):
         if tag is None:
             check(lib().secedo_pileup_bams(arr, n, out, int(bool(write_text_file)), chromosome_id, max_coverage,
                                            min_base_quality, min_map_quality, min_alignment_score, num_threads,
@@ -296,14 +356,14 @@ def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_
 def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequence[int], max_coverage: int = 100,
                          min_base_quality: int = 30, min_map_quality: int = 30, min_alignment_score: int = 0,
                          num_threads: int = 8, min_different: int = 3, id_to_group=None, group_id_to_pos=None,
-                         times: Optional[dict] = None, *, cell_tag=None, cells=None, inflate=None):
+                         times: Optional[dict] = None, *, cell_tag=None, cells=None, inflate=None, index=None):
     """Several chromosomes in one pass over the BAM or SAM files, straight into HBM on ``plan``'s device.
 
     -> (res, num_cells, max_read_length): ``res`` is the resident pileup dict of SimilarityMatrixPlan.upload,
     which filter_resident, divide_cluster_resident and variant_calling_resident take; num_cells and
     max_read_length are what read_pileup would report on the written .bin files (maxima over chromosomes).
     ``cell_tag`` / ``cells``: multiplexed files, as in pileup_bams; id_to_group then maps barcode indices.
-    ``inflate``: the BAM route, as in pileup_bams."""
+    ``inflate``: the BAM route, and ``index``: the use of .bai indexes, both as in pileup_bams."""
     import torch
 
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
@@ -312,7 +372,7 @@ def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequenc
     i2g = None if id_to_group is None else np.ascontiguousarray(id_to_group, dtype=np.uint16)
     info, t = ResultInfo(), Times()
     dev = "cuda:%d" % plan.device
-    with torch.cuda.device(plan.device), _route(inflate):
+    with torch.cuda.device(plan.device), _route(inflate, index):
         i2g_p, n_i2g = (_lib.ptr(i2g), len(i2g)) if i2g is not None else (None, 0)
         if tag is None:
             check(lib().secedo_pileup_bams_device(arr, n, _lib.ptr(ids), len(ids), max_coverage, min_base_quality,

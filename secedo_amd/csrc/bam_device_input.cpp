@@ -9,6 +9,12 @@
 // their members, one launch inflates them into one buffer, and the walk has one chain per file. A file that inflates
 // to more than a batch goes alone, in ranges of members of about a batch; the cut record at a range's end is carried
 // to the front of the next range, device to device. The stream is synchronised a fixed number of times per batch.
+//
+// A file read through its index (bam_host.hpp's IndexPlan) has one chain per span instead of one per file: the chain
+// enters at the span's first record inside its first member and its bytes end at the span's limit. The spans of a
+// file go one after another, span k of every file of the call in the same batches (the first spans together with the
+// files read in full), so many small files still share one upload, one inflate launch and one walk; the file's walk state (record count, last record, runs) passes from span
+// to span as it passes from range to range. A span larger than a batch goes alone, in ranges of members.
 #include "bam_host.hpp"
 #include "bam_kernels.hpp"  // the scan wrappers
 #include "bam_walk_kernels.hpp"
@@ -41,6 +47,10 @@ struct DevFile {
     int32_t prev_ref = 0, prev_pos = 0;
     std::vector<uint32_t> run_first, run_last;  // per requested chromosome (bam_walk.hpp's started / done rule)
     bool sorted = true;
+    // read through its index: the plan, and of the span under way what the ranges so far found per requested chromosome
+    const IndexPlan *plan = nullptr;
+    std::vector<uint64_t> sp_count;
+    std::vector<char> sp_start;
     uint64_t device_bytes() const { return carry.size() + (hb < blocks.size() ? total - blocks[hb].out : 0); }
 };
 
@@ -49,7 +59,11 @@ struct Piece {
     DevFile *df;
     size_t b0, b1;
     bool final;
-    uint32_t first_member = 0;  // of the batch
+    uint32_t first_member = 0;   // of the batch
+    const Span *span = nullptr;  // an indexed file: b0, b1 count the span's members
+    bool first_range() const { return span ? b0 == 0 : b0 == df->hb; }
+    const std::vector<Block> &blocks() const { return span ? span->blocks : df->blocks; }
+    const Mapped &mapped() const { return span ? df->plan->m : df->m; }
 };
 
 }  // namespace
@@ -66,6 +80,8 @@ struct BamDevWork {
     Dev<bw::SegJoin> join;
     Dev<WalkFile> files;
     Dev<WalkRun> runs;
+    Dev<SpanCheck> checks;
+    std::vector<SpanCheck> h_checks;
     Dev<int32_t> r_ref, r_pos, sel_pos;
     Dev<uint64_t> size, size_scan, sel_off, sel_idx, totals;
     Dev<unsigned long long> per_ref;
@@ -138,7 +154,10 @@ int file_error(const BamDevWork &w, const Piece &p, const WalkFile &F) {
     const std::string &path = p.df->path;
     if (e != ~0ull) {
         const uint32_t code = uint32_t(e & 0xFF);
-        const std::string where = record_where(path, 0, 0, e >> 8);
+        const std::string where = record_where(path, 0, 0, e >> 8, Stage::kLoad, p.span != nullptr);
+        if (p.span && (code == bw::kErrTruncated || code == bw::kErrBlockSize))  // as the host walk of a span
+            return index_mismatch(path, "the record chain breaks: indexed record " + std::to_string(e >> 8) +
+                                            (code == bw::kErrTruncated ? " is truncated" : " has a bad block_size"));
         std::string what;
         if (code == bw::kErrTruncated) what = " is truncated";
         else if (code == bw::kErrBlockSize) what = " has a bad block_size";
@@ -152,7 +171,8 @@ int file_error(const BamDevWork &w, const Piece &p, const WalkFile &F) {
     if (F.bad != ~0ull) {
         const uint64_t k = p.b0 + ((F.bad >> 8) - p.first_member);
         return fail(SECEDO_E_INVALID_ARG,
-                    path + ": BGZF block " + std::to_string(k) + ": " +
+                    path + ": BGZF block " +
+                        (p.span ? "at byte " + std::to_string(p.span->blocks[k].coff) : std::to_string(k)) + ": " +
                         (uint32_t(F.bad & 0xFF) == secedo::bgzf::kCrcMismatch ? "CRC32 mismatch"
                                                                                : "inflate failed or ISIZE mismatch"));
     }
@@ -176,14 +196,16 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
     w->h_segs.clear();
     w->h_files.assign(n_files, WalkFile{});
     w->h_runs.assign(size_t(n_files) * n_chr, WalkRun{});
+    w->h_checks.assign(size_t(n_files) * n_chr, SpanCheck{});
+    bool any_span = false;
     uint64_t in_pos = kBgzfInSlack, out_pos = 0, n_list = 0;
     for (uint32_t k = 0; k < n_files; ++k) {
         Piece &p = pieces[k];
         DevFile &df = *p.df;
         WalkFile &F = w->h_files[k];
         p.first_member = uint32_t(w->h_desc.size());
-        const bool first_range = p.b0 == df.hb;
-        const uint64_t carry = first_range ? df.carry.size() : df.dev_carry;
+        const bool first_range = p.first_range();
+        const uint64_t carry = !first_range ? df.dev_carry : p.span ? 0 : df.carry.size();
         if (first_range && carry) {
             F.carry_src = in_pos;
             F.carry_len = uint32_t(carry);
@@ -193,16 +215,17 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
         const uint64_t data_start = out_pos;
         uint64_t o = data_start + carry;
         if (p.b0 < p.b1) {
-            const std::vector<Block> &bl = df.blocks;
+            const std::vector<Block> &bl = p.blocks();
             const uint8_t *lo = bl[p.b0].cdata - kBgzfInSlack;  // a member's header is 18 bytes: inside the file
             const uint8_t *pay_end = bl[p.b1 - 1].cdata + bl[p.b1 - 1].clen;
-            const uint8_t *hi = std::min(df.m.p + df.m.n, pay_end + kBgzfInSlack);
+            const uint8_t *hi = std::min(p.mapped().p + p.mapped().n, pay_end + kBgzfInSlack);
             for (uint64_t c = 0; c < uint64_t(hi - lo); c += 4u << 20)
                 copies.push_back({in_pos + c, lo + c, std::min<uint64_t>(4u << 20, uint64_t(hi - lo) - c)});
             for (size_t b = p.b0; b < p.b1; ++b) {
                 w->h_desc.push_back(BgzfDesc{in_pos + uint64_t(bl[b].cdata - lo), o, bl[b].clen, bl[b].isize,
                                              bl[b].crc, 0});
-                const uint64_t start = b == p.b0 ? data_start : o;
+                // a span is entered at its first record, a known record start
+                const uint64_t start = b != p.b0 ? o : data_start + (p.span && first_range ? p.span->entry : 0);
                 o += bl[b].isize;
                 w->h_segs.push_back(bw::Seg{uint32_t(start), uint32_t(o), k, uint32_t(n_list)});
                 n_list += bw::list_cap(uint32_t(o - start));
@@ -212,12 +235,28 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
         }
         F.first_seg = p.first_member;
         F.data_end = F.limit = uint32_t(o);
+        if (p.span) {  // the span's offsets as offsets of the buffer; its last range ends at its limit
+            const Span &sp = *p.span;
+            const long long base = (long long)(data_start + carry) - (long long)sp.blocks[p.b0].out;
+            if (p.final) F.data_end = F.limit = uint32_t(base + (long long)sp.limit);
+            for (size_t c = 0; c < sp.chrs.size(); ++c) {
+                const size_t u = std::find(w->chr_ids.begin(), w->chr_ids.end(), sp.chrs[c].chromosome) -
+                                 w->chr_ids.begin();
+                SpanCheck &ck = w->h_checks[size_t(k) * n_chr + u];
+                ck.beg = base + (long long)sp.chrs[c].beg;
+                ck.end = base + (long long)sp.chrs[c].end;
+                ck.ref = int32_t(sp.chrs[c].chromosome);
+                ck.flags = kSpanOn | (c == 0 && first_range ? kSpanEntry : 0) |
+                           (c + 1 == sp.chrs.size() && p.final && sp.limit + 8 <= sp.bytes ? kSpanTail : 0);
+            }
+            any_span = true;
+        }
         F.final = p.final;
         F.has_prev = df.has_prev;
         F.rec_base = df.rec_base;
         F.prev_ref = df.prev_ref;
         F.prev_pos = df.prev_pos;
-        F.stop_off = uint32_t(o);
+        F.stop_off = F.data_end;
         F.bad = F.err = F.unsorted = ~0ull;
         for (uint32_t u = 0; u < n_chr; ++u) {
             w->h_runs[size_t(k) * n_chr + u].first = df.run_first[u];
@@ -253,7 +292,7 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
     parallel_for(threads, copies.size(),
                  [&](uint64_t c) { std::memcpy(w->h_in + copies[c].dst, copies[c].src, copies[c].n); });
     SECEDO_TRY(w->in.grow(in_pos, 0, s));
-    SECEDO_TRY(w->buf.grow(buf_bytes, pieces[0].b0 == pieces[0].df->hb ? 0 : pieces[0].df->dev_carry, s));
+    SECEDO_TRY(w->buf.grow(buf_bytes, pieces[0].first_range() ? 0 : pieces[0].df->dev_carry, s));
     SECEDO_TRY(w->desc.grow(n_members, 0, s));
     SECEDO_TRY(w->status.grow(n_members, 0, s));
     SECEDO_TRY(w->segs.grow(n_seg, 0, s));
@@ -266,6 +305,11 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
     SECEDO_TRY(w->files.grow(n_files, 0, s));
     SECEDO_TRY(w->runs.grow(w->h_runs.size(), 0, s));
     SECEDO_TRY(w->totals.grow(2, 0, s));
+    if (any_span) {
+        SECEDO_TRY(w->checks.grow(w->h_checks.size(), 0, s));
+        SECEDO_TRY(hipMemcpyAsync(w->checks.p, w->h_checks.data(), w->h_checks.size() * sizeof(SpanCheck),
+                                  hipMemcpyHostToDevice, s));
+    }
     SECEDO_TRY(hipMemcpyAsync(w->in.p, w->h_in, in_pos, hipMemcpyHostToDevice, s));
     if (n_members)
         SECEDO_TRY(hipMemcpyAsync(w->desc.p, w->h_desc.data(), n_members * sizeof(BgzfDesc), hipMemcpyHostToDevice, s));
@@ -306,6 +350,11 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
     const WalkRecords wr{n_rec,    w->r_off.p, w->r_file.p,   w->r_ref.p,
                          w->r_pos.p, w->sel.p,   w->size.p,     w->sel_scan.p, w->size_scan.p};
     SECEDO_TRY(walk_records(wb, wr, w->chr.p, n_chr, w->runs.p, w->scan ? w->per_ref.p : nullptr, w->n_ref, s));
+    if (any_span) {
+        SECEDO_TRY(walk_span_check(wb, wr, n_chr, w->checks.p, s));
+        SECEDO_TRY(hipMemcpyAsync(w->h_checks.data(), w->checks.p, w->h_checks.size() * sizeof(SpanCheck),
+                                  hipMemcpyDeviceToHost, s));
+    }
     tb = scan_bytes(uint64_t(n_rec) + 1);
     SECEDO_TRY(w->tmp.grow(tb, 0, s));
     SECEDO_TRY(exclusive_sum(w->tmp.p, tb, w->sel.p, w->sel_scan.p, uint64_t(n_rec) + 1, s));
@@ -326,7 +375,33 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
         route().device_records += w->h_files[k].n_rec;
         route().rewalked_segments += w->h_files[k].rewalked;
     }
-    for (uint32_t k = 0; k < n_files; ++k) SECEDO_CALL(file_error(*w, pieces[k], w->h_files[k]));
+    // per file in order: the RefID at a span's entry, then the walk's own errors, then what the index says of the span
+    for (uint32_t k = 0; k < n_files; ++k) {
+        const Piece &p = pieces[k];
+        if (p.span) {
+            index_info().members += p.b1 - p.b0;
+            index_info().spans += p.first_range() ? 1 : 0;
+            const Span &sp = *p.span;
+            const size_t u0 = std::find(w->chr_ids.begin(), w->chr_ids.end(), sp.chrs[0].chromosome) -
+                              w->chr_ids.begin();
+            if (w->h_checks[size_t(k) * n_chr + u0].entry_bad) return check_span_chr(p.df->path, sp.chrs[0], false, 0);
+        }
+        SECEDO_CALL(file_error(*w, p, w->h_files[k]));
+        if (!p.span) continue;
+        DevFile &df = *p.df;
+        for (uint32_t u = 0; u < n_chr; ++u) {
+            const SpanCheck &ck = w->h_checks[size_t(k) * n_chr + u];
+            if (!(ck.flags & kSpanOn)) continue;
+            df.sp_count[u] += ck.count;
+            if (ck.start) df.sp_start[u] = ck.start == 1;
+        }
+        if (!p.final) continue;
+        for (const SpanChr &sc : p.span->chrs) {
+            const size_t u = std::find(w->chr_ids.begin(), w->chr_ids.end(), sc.chromosome) - w->chr_ids.begin();
+            SECEDO_CALL(check_span_chr(df.path, sc, df.sp_start[u] != 0, df.sp_count[u]));
+            if (w->h_checks[size_t(k) * n_chr + u].tail_bad) return span_tail_mismatch(df.path, sc);
+        }
+    }
     // ---- the taken records
     const uint64_t n_sel = totals[0], sel_bytes = totals[1];
     // what came back must be consistent before it is used as an index
@@ -397,15 +472,15 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
 }
 
 // One file that inflates to more than a batch: ranges of members of about `batch` inflated bytes.
-int run_ranges(BamDevWork *w, DevFile *df, uint32_t threads, uint64_t batch, Inputs *in, Runs *runs,
+int run_ranges(BamDevWork *w, DevFile *df, const Span *span, uint32_t threads, uint64_t batch, Inputs *in, Runs *runs,
                secedo_bam_times *t) {
-    const std::vector<Block> &bl = df->blocks;
-    for (size_t b0 = df->hb;;) {
+    const std::vector<Block> &bl = span ? span->blocks : df->blocks;
+    for (size_t b0 = span ? 0 : df->hb;;) {
         size_t b1 = b0;
         uint64_t bytes = 0;
         while (b1 < bl.size() && (b1 == b0 || bytes + bl[b1].isize <= batch)) bytes += bl[b1++].isize;
-        if (b1 < bl.size() && bl[b1].out == df->total) b1 = bl.size();  // only empty members follow
-        std::vector<Piece> one{Piece{df, b0, b1, b1 == bl.size()}};
+        if (!span && b1 < bl.size() && bl[b1].out == df->total) b1 = bl.size();  // only empty members follow
+        std::vector<Piece> one{Piece{df, b0, b1, b1 == bl.size(), 0, span}};
         SECEDO_CALL(run_batch(w, one, threads, in, runs, t));
         if (b1 == bl.size()) return SECEDO_OK;
         b0 = b1;
@@ -415,9 +490,11 @@ int run_ranges(BamDevWork *w, DevFile *df, uint32_t threads, uint64_t batch, Inp
 }  // namespace
 
 int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, BamDevWork *w, Inputs *in, Runs *runs,
-                     secedo_bam_times *t) {
+                     secedo_bam_times *t, std::vector<IndexPlan> *plans) {
     SECEDO_CALL(start_work(w, in->chrs));
     std::vector<std::unique_ptr<DevFile>> open;
+    std::vector<std::unique_ptr<DevFile>> indexed;  // kept over their spans
+    const size_t n_chr = w->chr_ids.size();
     std::vector<Piece> pieces;
     uint64_t bytes = 0;
     const auto flush = [&]() -> int {
@@ -430,6 +507,17 @@ int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, Bam
     };
     for (size_t f = f0; f < f1; ++f) {
         const Clock::time_point t0 = Clock::now();
+        if (plans && (*plans)[f].indexed) {  // its header is read; its spans follow below
+            std::unique_ptr<DevFile> df(new DevFile());
+            df->f = f;
+            df->path = in->paths[f];
+            df->plan = &(*plans)[f];
+            df->h = df->plan->h;
+            df->run_first.assign(n_chr, bw::kNoRun);
+            df->run_last.assign(n_chr, bw::kNoRun);
+            indexed.push_back(std::move(df));
+            continue;
+        }
         std::unique_ptr<DevFile> df(new DevFile());
         const int rc = open_file(f, in->paths[f], w->chr_ids.size(), df.get());
         if (t) t->inflate_ms += ms_since(t0);
@@ -442,7 +530,7 @@ int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, Bam
         const uint64_t n = df->device_bytes();
         if (n > batch || n > kMaxBatchBytes / 2) {
             SECEDO_CALL(flush());
-            SECEDO_CALL(run_ranges(w, df.get(), threads, batch, in, runs, t));
+            SECEDO_CALL(run_ranges(w, df.get(), nullptr, threads, batch, in, runs, t));
             continue;
         }
         if (!pieces.empty() && bytes + n > batch) SECEDO_CALL(flush());
@@ -450,7 +538,29 @@ int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, Bam
         open.push_back(std::move(df));
         bytes += n;
     }
-    return flush();
+    // span k of every indexed file, k = 0, 1, ...; the first spans share the batch of the files read in full
+    for (size_t k = 0;; ++k) {
+        bool any = false;
+        for (const auto &df : indexed) {
+            if (k >= df->plan->spans.size()) continue;
+            any = true;
+            const Span *sp = &df->plan->spans[k];
+            df->sp_count.assign(n_chr, 0);
+            df->sp_start.assign(n_chr, 0);
+            df->dev_carry = 0;
+            if (sp->bytes > batch || sp->bytes > kMaxBatchBytes / 2) {
+                SECEDO_CALL(flush());
+                SECEDO_CALL(run_ranges(w, df.get(), sp, threads, batch, in, runs, t));
+                continue;
+            }
+            if (!pieces.empty() && bytes + sp->bytes > batch) SECEDO_CALL(flush());
+            pieces.push_back(Piece{df.get(), 0, sp->blocks.size(), true, 0, sp});
+            bytes += sp->bytes;
+        }
+        SECEDO_CALL(flush());
+        if (!any) break;
+    }
+    return SECEDO_OK;
 }
 
 }  // namespace bam_host
@@ -470,7 +580,8 @@ extern "C" int secedo_bam_scan_device(const char *path, uint32_t num_threads, se
     w->n_ref = df.h.n_ref;
     SECEDO_TRY(w->per_ref.grow(uint64_t(w->n_ref) + 1, 0, w->s));
     SECEDO_TRY(hipMemsetAsync(w->per_ref.p, 0, (uint64_t(w->n_ref) + 1) * 8, w->s));
-    SECEDO_CALL(run_ranges(w.get(), &df, num_threads ? num_threads : 1, batch_bytes(), nullptr, nullptr, nullptr));
+    SECEDO_CALL(run_ranges(w.get(), &df, nullptr, num_threads ? num_threads : 1, batch_bytes(), nullptr, nullptr,
+                           nullptr));
     std::vector<unsigned long long> per(uint64_t(w->n_ref) + 1);
     SECEDO_TRY(hipMemcpyAsync(per.data(), w->per_ref.p, per.size() * 8, hipMemcpyDeviceToHost, w->s));
     SECEDO_TRY(hipStreamSynchronize(w->s));

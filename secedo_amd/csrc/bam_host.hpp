@@ -44,6 +44,7 @@ struct ChrInput {
 struct Inputs {
     std::vector<std::string> paths;  // [n_files] (messages)
     std::vector<uint64_t> line0;     // [n_files] SAM: the line of record 0 (1-based); BAM: 0
+    std::vector<char> indexed;       // [n_files] BAM read through its index: record 0 is the first span's first
     std::vector<ChrInput> chrs;      // [n_chr]
 };
 
@@ -52,8 +53,10 @@ struct Inputs {
 //   BAM while loading:       "path: record idx"
 //   BAM in the device stage: "file f, record idx"
 // Known wart: the two BAM wordings name the same record differently. Both are kept as callers know them.
+// indexed: the file was read through its index, its whole-file ordinals are unknown: "indexed record idx" in both.
 enum class Stage { kLoad, kDevice };
-std::string record_where(const std::string &path, size_t f, uint64_t line0, uint64_t idx, Stage stage = Stage::kLoad);
+std::string record_where(const std::string &path, size_t f, uint64_t line0, uint64_t idx, Stage stage = Stage::kLoad,
+                         bool indexed = false);
 
 // Reads the files (BAM or SAM, told apart by their first bytes) and keeps the records of the requested chromosomes.
 // t: stage times are added to it; may be null.
@@ -89,6 +92,11 @@ struct Mapped {
     Mapped(const Mapped &) = delete;
     Mapped &operator=(const Mapped &) = delete;
     Mapped(Mapped &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    Mapped &operator=(Mapped &&o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
     ~Mapped() {
         if (p && n) munmap(const_cast<uint8_t *>(p), n);
     }
@@ -97,8 +105,12 @@ struct Mapped {
 struct Block {
     const uint8_t *cdata;
     uint32_t clen, crc, isize;
-    uint64_t out;  // offset in the file's inflated buffer
+    uint64_t out;  // offset in the file's inflated buffer (of an indexed file: in its span's)
+    uint64_t coff = 0;  // its byte in the file
 };
+
+// the BGZF block at byte off < m.n of a mapped file (its `out` left 0); *len = its bytes in the file
+int read_block(const std::string &path, const Mapped &m, uint64_t off, Block *blk, uint32_t *len);
 
 // a file mapped and its BGZF blocks listed; *total = its inflated size
 int open_bgzf(const std::string &path, Mapped *m, std::vector<Block> *blocks, uint64_t *total);
@@ -115,6 +127,48 @@ constexpr int kNeedMore = 1;  // parse_header / walk_range: the bytes end inside
 // final: d ends the file, so a cut header is an error; else kNeedMore
 int parse_header(const std::string &path, const uint8_t *d, uint64_t n, bool final, Header *h);
 
+// ---- reading through the .bai index (secedo_bam_set_index, SECEDO_BAM_INDEX; bam_index.hpp parses the file)
+
+// one requested chromosome inside a span; offsets count the span's inflated bytes from its first member's first byte
+struct SpanChr {
+    uint32_t chromosome;
+    uint64_t beg, end;  // its records start at beg and end in front of end
+    uint64_t count;     // the pseudo-bin's record count, or bamindex::kNoCount
+};
+
+// A run of members that holds the records of one or more requested chromosomes, entered at a known record start.
+struct Span {
+    std::vector<Block> blocks;  // its members in file order, `out` from 0
+    uint64_t entry = 0;         // the first record starts here (the start's uoffset)
+    uint64_t limit = 0;         // no record of the span starts at or past this
+    uint64_t bytes = 0;         // inflated bytes of its members
+    uint64_t beg_v = 0;         // the virtual offset of the entry (messages)
+    std::vector<SpanChr> chrs;  // in file order; chrs[0].beg == entry, chrs.back().end == limit
+};
+
+// What the index says of one BAM for the requested chromosomes.
+struct IndexPlan {
+    bool indexed = false;  // false: the file is read in full
+    Mapped m;
+    std::vector<Block> head;     // the members that hold the header and the reference list
+    Header h;
+    std::vector<Span> spans;     // in file order
+};
+
+// The index mode of this call: SECEDO_BAM_INDEX_OFF / AUTO / REQUIRE (secedo_bam_set_index, else SECEDO_BAM_INDEX).
+int index_mode(int *mode);
+// Plans the read of one BAM under AUTO or REQUIRE: its header members are inflated here, its index is read and
+// checked, the members of its spans are found by following BSIZE. AUTO without a usable index: plan->indexed stays
+// false and the stats count the file as read in full.
+int plan_index(const std::string &path, const std::vector<uint32_t> &chromosomes, int mode, IndexPlan *plan);
+// "<path>: index does not match the file (<why>); re-index it or use --index off"
+int index_mismatch(const std::string &path, const std::string &why);
+// The checks made after a span was read, the same words from both routes. got_count: records that start in
+// [c.beg, c.end); start_ok: one starts at c.beg with the chromosome's RefID.
+int check_span_chr(const std::string &path, const SpanChr &c, bool start_ok, uint64_t got_count);
+int span_tail_mismatch(const std::string &path, const SpanChr &c);
+secedo_bam_index_info &index_info();
+
 // Process-wide BAM route (secedo_bam_set_inflate, SECEDO_BAM_INFLATE), read at every call: *device = the device
 // route. An unknown value of the variable is SECEDO_E_INVALID_ARG.
 int inflate_route(bool *device);
@@ -129,8 +183,9 @@ using Runs = std::vector<std::vector<std::vector<uint8_t>>>;  // [chr][file] the
 struct BamDevWork;
 BamDevWork *new_bam_dev_work();
 void delete_bam_dev_work(BamDevWork *w);
+// (*plans)[f] (plans may be null: no index in use) says which of them go through their index.
 int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, BamDevWork *w, Inputs *in, Runs *runs,
-                     secedo_bam_times *t);
+                     secedo_bam_times *t, std::vector<IndexPlan> *plans = nullptr);
 
 // Frees the device memory of the last secedo_bgzf_inflate result of this thread (secedo_bam_release calls it).
 void release_inflated();

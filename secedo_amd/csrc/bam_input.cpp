@@ -8,10 +8,13 @@
 // inflated data (SECEDO_BAM_BATCH_BYTES overrides it); a file alone in its batch is inflated and walked in ranges
 // of BGZF blocks of that size, a record cut at a range's end carried into the next, so one large multiplexed BAM
 // never sits inflated in RAM. Of each file only the byte run of the requested chromosomes' records is kept. No .bai
-// is needed: the run is found by walking block_size, so with or without an index the result is the same.
+// is needed: the run is found by walking block_size. Where one is asked for (secedo_bam_set_index), bam_index.hpp
+// reads it, plan_index below turns it into spans of members, and only those are inflated and walked, on either route;
+// with or without an index the result is the same.
 // The opt-in device route for BAM (secedo_bam_set_inflate) branches off in load_inputs to bam_device_input.cpp; the
 // BGZF listing, the zlib inflate of one block and the header parse below are what the two routes share.
 #include "bam_host.hpp"
+#include "bam_index.hpp"
 #include "bam_kernels.hpp"  // the scan wrappers
 #include "bgzf_inflate.hpp"  // the status codes
 #include "bgzf_kernels.hpp"
@@ -72,21 +75,15 @@ int map_file(const std::string &path, Mapped *m) {
 
 // the BGZF block at byte off < m.n of a mapped file (its `out` left 0); *len = its bytes in the file
 int read_block(const std::string &path, const Mapped &m, uint64_t off, Block *blk, uint32_t *len) {
-    const uint8_t *b = m.p + off;
-    if (m.n - off < 18 || b[0] != 31 || b[1] != 139 || b[2] != 8 || !(b[3] & 4))
+    uint32_t isize = 0, xlen = 0;
+    const bamindex::Member what = bamindex::member_header(m.p, m.n, off, len, &isize, &xlen);
+    if (what == bamindex::kNoMember)
         return fail(SECEDO_E_INVALID_ARG, path + ": not a BGZF block at byte " + std::to_string(off));
-    const uint32_t xlen = rd16(b + 10);
-    uint32_t bsize = UINT32_MAX;
-    for (uint32_t x = 12; x + 4 <= 12 + xlen && 12 + xlen <= m.n - off;) {
-        const uint32_t slen = rd16(b + x + 2);
-        if (b[x] == 'B' && b[x + 1] == 'C' && slen == 2) bsize = rd16(b + x + 4);
-        x += 4 + slen;
-    }
-    if (bsize == UINT32_MAX || uint64_t(bsize) + 1 > m.n - off || bsize + 1 < 12 + xlen + 8)
+    if (what == bamindex::kBadBsize)
         return fail(SECEDO_E_INVALID_ARG, path + ": bad BGZF block size at byte " + std::to_string(off));
-    *len = bsize + 1;
-    *blk = Block{b + 12 + xlen, *len - xlen - 20, rd32(b + *len - 8), rd32(b + *len - 4), 0};
-    if (blk->isize > 65536) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF ISIZE above 64 KiB");
+    if (what == bamindex::kBigIsize) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF ISIZE above 64 KiB");
+    const uint8_t *b = m.p + off;
+    *blk = Block{b + 12 + xlen, *len - xlen - 20, rd32(b + *len - 8), isize, 0, off};
     return SECEDO_OK;
 }
 
@@ -161,7 +158,13 @@ struct InflateJob {
     const Block *block;
     uint64_t index;  // of the block in its file (messages)
     uint8_t *dst;
+    bool by_byte = false;  // an indexed file: the ordinal is unknown, the message names the block's byte
 };
+
+std::string block_where(const std::string &path, const InflateJob &j) {
+    if (j.by_byte) return path + ": BGZF block at byte " + std::to_string(j.block->coff);
+    return path + ": BGZF block " + std::to_string(j.index);
+}
 
 // the jobs in one pool; the first failed job in list order is the error
 int inflate_blocks(const std::vector<InflateJob> &jobs, uint32_t threads) {
@@ -170,8 +173,7 @@ int inflate_blocks(const std::vector<InflateJob> &jobs, uint32_t threads) {
     route().host_blocks += jobs.size();
     for (size_t k = 0; k < jobs.size(); ++k)
         if (!errs[k].empty())
-            return fail(SECEDO_E_INVALID_ARG,
-                        *jobs[k].path + ": BGZF block " + std::to_string(jobs[k].index) + ": " + errs[k]);
+            return fail(SECEDO_E_INVALID_ARG, block_where(*jobs[k].path, jobs[k]) + ": " + errs[k]);
     return SECEDO_OK;
 }
 
@@ -222,6 +224,7 @@ struct WalkState {
     SortCheck order;
     bool require_sorted = true;  // false (secedo_bam_scan): an unsorted file is walked to its end, `sorted` says so
     bool sorted = true;
+    bool span = false;  // the bytes are a span of an indexed file: a chain that breaks means the index does not fit
 };
 
 // Walks the header (first) and the complete records of d[0, n), the file's inflated bytes that follow what earlier
@@ -242,12 +245,17 @@ int walk_range(const std::string &path, const uint8_t *d, uint64_t n, bool final
     for (;; ++st->idx) {
         *used = o;
         if (o >= n) return SECEDO_OK;
-        const std::string where = record_where(path, 0, 0, st->idx);
-        if (n - o < 4 + 32) return final ? fail(SECEDO_E_INVALID_ARG, where + " is truncated") : SECEDO_OK;
+        const std::string where = record_where(path, 0, 0, st->idx, Stage::kLoad, st->span);
+        const auto broken = [&](const char *what) {
+            if (st->span) return index_mismatch(path, "the record chain breaks: indexed record " +
+                                                          std::to_string(st->idx) + what);
+            return fail(SECEDO_E_INVALID_ARG, where + what);
+        };
+        if (n - o < 4 + 32) return final ? broken(" is truncated") : SECEDO_OK;
         const uint32_t bs = rd32(d + o);
         const uint8_t *c = d + o + 4;
-        if (bs < 32) return fail(SECEDO_E_INVALID_ARG, where + " has a bad block_size");
-        if (bs > n - o - 4) return final ? fail(SECEDO_E_INVALID_ARG, where + " has a bad block_size") : SECEDO_OK;
+        if (bs < 32) return broken(" has a bad block_size");
+        if (bs > n - o - 4) return final ? broken(" has a bad block_size") : SECEDO_OK;
         if (rec_aux_off(c) > bs) return fail(SECEDO_E_INVALID_ARG, where + " is longer than its block_size");
         const int32_t ref = int32_t(rd32(c)), pos = int32_t(rd32(c + 4));
         if (!st->order.check(ref, pos)) {
@@ -292,7 +300,7 @@ struct FileSink {
                 if (started[c]) done[c] = 1;  // the reader stops at another RefID
                 continue;
             }
-            const std::string where = record_where(in.paths[f], f, in.line0[f], idx);
+            const std::string where = record_where(in.paths[f], f, in.line0[f], idx, Stage::kLoad, in.indexed[f] != 0);
             if (pos < 0) return fail(SECEDO_E_INVALID_ARG, where + " has a negative position");
             SECEDO_CALL(check_cigar(rec, where));
             started[c] = 1;
@@ -343,6 +351,77 @@ int load_file_ranges(size_t f, uint32_t threads, uint64_t batch, Inputs *in, Run
         if (t) t->walk_ms += ms_since(t0);
         b0 = b1;
     } while (b0 < blocks.size());
+    return SECEDO_OK;
+}
+
+// One indexed file: only the members of its spans are inflated, through the pool, in ranges of about `batch` inflated
+// bytes as above; a span is entered at its first record and walked to its limit. The sortedness check and the runs
+// carry across the spans of the file.
+int load_file_spans(size_t f, const IndexPlan &plan, uint32_t threads, uint64_t batch, Inputs *in, Runs *runs,
+                    secedo_bam_times *t) {
+    const std::string &path = in->paths[f];
+    WalkState st;
+    st.have_header = true;
+    st.h = plan.h;
+    st.span = true;
+    FileSink sink(*in, f, *runs);
+    std::vector<uint8_t> buf;
+    std::vector<InflateJob> jobs;
+    for (const Span &sp : plan.spans) {
+        const std::vector<Block> &blocks = sp.blocks;
+        std::vector<uint64_t> got(sp.chrs.size(), 0);
+        std::vector<char> start_ok(sp.chrs.size(), 0);
+        index_info().spans += 1;
+        index_info().members += blocks.size();
+        uint64_t carry = 0;
+        buf.clear();
+        for (size_t b0 = 0; b0 < blocks.size();) {
+            size_t b1 = b0;
+            uint64_t bytes = 0;
+            while (b1 < blocks.size() && (b1 == b0 || bytes + blocks[b1].isize <= batch)) bytes += blocks[b1++].isize;
+            const bool final = b1 == blocks.size();
+            Clock::time_point t0 = Clock::now();
+            buf.resize(carry + bytes);
+            jobs.clear();
+            for (size_t b = b0; b < b1; ++b)
+                jobs.push_back({&path, &blocks[b], b, buf.data() + carry + (blocks[b].out - blocks[b0].out), true});
+            SECEDO_CALL(inflate_blocks(jobs, threads));
+            if (t) {
+                t->inflate_ms += ms_since(t0);
+                t->inflated_bytes += double(bytes);
+            }
+            t0 = Clock::now();
+            const uint64_t lin0 = blocks[b0].out - carry;  // the span offset of buf[0]
+            const uint64_t n = final ? sp.limit - lin0 : buf.size();
+            const uint64_t o0 = b0 == 0 ? sp.entry : 0;
+            if (b0 == 0 && o0 + 8 <= n && rd32(buf.data() + o0 + 4) != sp.chrs[0].chromosome)
+                return check_span_chr(path, sp.chrs[0], false, 0);
+            const uint8_t *d = buf.data() + o0;
+            const auto on_record = [&](uint64_t idx, const uint8_t *rec, int32_t ref, int32_t pos) {
+                const uint64_t lin = lin0 + o0 + uint64_t(rec - d);
+                for (size_t c = 0; c < sp.chrs.size(); ++c) {
+                    const SpanChr &sc = sp.chrs[c];
+                    if (lin == sc.beg) start_ok[c] = ref >= 0 && uint32_t(ref) == sc.chromosome;
+                    if (sc.beg <= lin && lin < sc.end) ++got[c];
+                }
+                return sink(idx, rec, ref, pos);
+            };
+            uint64_t used = 0;
+            SECEDO_CALL(walk_range(path, d, n - o0, final, &st, &used, on_record));
+            used += o0;
+            if (final) {
+                for (size_t c = 0; c < sp.chrs.size(); ++c)
+                    SECEDO_CALL(check_span_chr(path, sp.chrs[c], start_ok[c] != 0, got[c]));
+                if (sp.limit + 8 <= sp.bytes && rd32(buf.data() + n + 4) == sp.chrs.back().chromosome)
+                    return span_tail_mismatch(path, sp.chrs.back());
+            }
+            carry = buf.size() - used;
+            if (used) std::memmove(buf.data(), buf.data() + used, carry);
+            buf.resize(carry);
+            if (t) t->walk_ms += ms_since(t0);
+            b0 = b1;
+        }
+    }
     return SECEDO_OK;
 }
 
@@ -844,6 +923,179 @@ namespace {
 std::atomic<int> g_inflate_mode{-1};  // -1: not set by secedo_bam_set_inflate, the environment decides
 }
 
+namespace {
+std::atomic<int> g_index_mode{-1};  // -1: not set by secedo_bam_set_index, the environment decides
+}
+
+int index_mode(int *mode) {
+    int m = g_index_mode.load();
+    if (m < 0) {
+        const char *e = std::getenv("SECEDO_BAM_INDEX");
+        if (!e || !*e || std::strcmp(e, "off") == 0) m = SECEDO_BAM_INDEX_OFF;
+        else if (std::strcmp(e, "auto") == 0) m = SECEDO_BAM_INDEX_AUTO;
+        else if (std::strcmp(e, "require") == 0) m = SECEDO_BAM_INDEX_REQUIRE;
+        else return fail(SECEDO_E_INVALID_ARG, std::string("SECEDO_BAM_INDEX=") + e + ": expected off, auto or require");
+    }
+    *mode = m;
+    return SECEDO_OK;
+}
+
+secedo_bam_index_info &index_info() {
+    static thread_local secedo_bam_index_info r{};
+    return r;
+}
+
+int index_mismatch(const std::string &path, const std::string &why) {
+    return fail(SECEDO_E_INVALID_ARG,
+                path + ": index does not match the file (" + why + "); re-index it or use --index off");
+}
+
+int check_span_chr(const std::string &path, const SpanChr &c, bool start_ok, uint64_t got_count) {
+    const std::string ref = "reference " + std::to_string(c.chromosome);
+    if (!start_ok) return index_mismatch(path, "no record of " + ref + " starts where the index says its records start");
+    if (c.count != bamindex::kNoCount && c.count != got_count)
+        return index_mismatch(path, ref + " has " + std::to_string(got_count) +
+                                        " records between its start and end, the index counts " +
+                                        std::to_string(c.count));
+    return SECEDO_OK;
+}
+
+int span_tail_mismatch(const std::string &path, const SpanChr &c) {
+    return index_mismatch(path, "the record at the end of reference " + std::to_string(c.chromosome) +
+                                    " still has its RefID");
+}
+
+namespace {
+
+// the index beside a BAM, parsed and checked against it: empty, or why it cannot be used (*found: a file was there)
+std::string read_index(const std::string &path, const Mapped &m, uint32_t n_ref, std::vector<bamindex::RefRange> *refs,
+                       bool *found) {
+    *found = false;
+    const std::string name = bamindex::find(path);
+    if (name.empty()) return "no index file " + path + ".bai";
+    *found = true;
+    std::vector<uint8_t> bytes;
+    if (!bamindex::read_file(name, &bytes)) return "could not read " + name;
+    std::string why = bamindex::parse(bytes.data(), bytes.size(), refs);
+    if (why.empty()) why = bamindex::check(*refs, n_ref, m.p, m.n);
+    return why.empty() ? why : name + ": " + why;
+}
+
+// the header's members of a mapped BAM inflated and the header parsed
+int read_header(const std::string &path, IndexPlan *plan) {
+    std::vector<uint8_t> head;
+    uint64_t off = 0;
+    for (;;) {
+        const int rc = parse_header(path, head.data(), head.size(), off >= plan->m.n, &plan->h);
+        if (rc == SECEDO_OK) break;
+        if (rc != kNeedMore) return rc;
+        Block blk;
+        uint32_t len = 0;
+        SECEDO_CALL(read_block(path, plan->m, off, &blk, &len));
+        blk.out = head.size();
+        head.resize(head.size() + blk.isize);
+        const std::string err = inflate_block(blk, head.data() + blk.out);
+        if (!err.empty())
+            return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(plan->head.size()) + ": " + err);
+        plan->head.push_back(blk);
+        off += len;
+    }
+    return SECEDO_OK;
+}
+
+}  // namespace
+
+int plan_index(const std::string &path, const std::vector<uint32_t> &chromosomes, int mode, IndexPlan *plan) {
+    const auto full = [&](const std::string &why, bool rejected) {
+        if (mode == SECEDO_BAM_INDEX_REQUIRE) return fail(SECEDO_E_INVALID_ARG, path + ": no usable index: " + why);
+        index_info().files_full += 1;
+        index_info().rejected += rejected ? 1 : 0;
+        *plan = IndexPlan();
+        return int(SECEDO_OK);
+    };
+    // a file whose header does not parse: AUTO reads it in full, which reports it in the words of the full read;
+    // REQUIRE says that no index can be used and why
+    if (map_file(path, &plan->m) != SECEDO_OK || read_header(path, plan) != SECEDO_OK) {
+        const std::string why = g_error;
+        return full(why, false);
+    }
+    std::vector<bamindex::RefRange> refs;
+    bool found = false;
+    const std::string why = read_index(path, plan->m, plan->h.n_ref, &refs, &found);
+    if (!why.empty()) return full(why, found);
+
+    // the requested chromosomes that have records, each once, in file order
+    struct Want {
+        uint32_t chromosome;
+        bamindex::RefRange r;
+    };
+    std::vector<Want> want;
+    for (const uint32_t c : chromosomes) {
+        if (c >= refs.size() || refs[c].empty() || refs[c].beg == refs[c].end) continue;
+        if (std::none_of(want.begin(), want.end(), [&](const Want &w) { return w.chromosome == c; }))
+            want.push_back(Want{c, refs[c]});
+    }
+    std::sort(want.begin(), want.end(), [](const Want &a, const Want &b) { return a.r.beg < b.r.beg; });
+    const Mapped &m = plan->m;
+    for (size_t a = 0; a < want.size();) {
+        // spans whose member ranges touch or overlap are one
+        uint64_t end_v = want[a].r.end;
+        size_t b = a + 1;
+        while (b < want.size() && bamindex::coffset(want[b].r.beg) <= bamindex::coffset(end_v))
+            end_v = std::max(end_v, want[b++].r.end);
+        Span sp;
+        sp.beg_v = want[a].r.beg;
+        const uint64_t end_coff = bamindex::coffset(end_v);
+        const std::string lead = "the members from " + bamindex::voffset_str(sp.beg_v) + " do not lead to " +
+                                 bamindex::voffset_str(end_v);
+        for (uint64_t off = bamindex::coffset(sp.beg_v);;) {
+            if (off == end_coff && bamindex::uoffset(end_v) == 0) break;
+            if (off > end_coff || off >= m.n) return index_mismatch(path, lead);
+            Block blk;
+            uint32_t len = 0;
+            SECEDO_CALL(read_block(path, m, off, &blk, &len));
+            blk.out = sp.bytes;
+            sp.bytes += blk.isize;
+            sp.blocks.push_back(blk);
+            if (off == end_coff) break;
+            off += len;
+        }
+        // a virtual offset as an offset of the span's inflated bytes; its member is one of the span's, or the
+        // one behind its last (uoffset 0)
+        const auto linear = [&](uint64_t v, uint64_t *lin) {
+            const uint64_t coff = bamindex::coffset(v);
+            const auto it = std::lower_bound(sp.blocks.begin(), sp.blocks.end(), coff,
+                                             [](const Block &x, uint64_t c) { return x.coff < c; });
+            if (it != sp.blocks.end() && it->coff == coff) {
+                if (bamindex::uoffset(v) > it->isize) return false;
+                *lin = it->out + bamindex::uoffset(v);
+                return true;
+            }
+            *lin = sp.bytes;
+            return coff == end_coff && bamindex::uoffset(v) == 0;
+        };
+        for (size_t k = a; k < b; ++k) {
+            SpanChr sc{want[k].chromosome, 0, 0, want[k].r.count};
+            if (!linear(want[k].r.beg, &sc.beg) || !linear(want[k].r.end, &sc.end) || sc.beg > sc.end)
+                return index_mismatch(path, "reference " + std::to_string(sc.chromosome) + " at " +
+                                                bamindex::voffset_str(want[k].r.beg) + " .. " +
+                                                bamindex::voffset_str(want[k].r.end) +
+                                                " is not inside the members of its span");
+            sp.limit = std::max(sp.limit, sc.end);
+            sp.chrs.push_back(sc);
+        }
+        sp.entry = sp.chrs[0].beg;
+        if (sp.chrs.back().end != sp.limit)  // a reference that ends behind the next one's end: not a sorted file's
+            return index_mismatch(path, "the references of the span at " + bamindex::voffset_str(sp.beg_v) + " nest");
+        plan->spans.push_back(std::move(sp));
+        a = b;
+    }
+    plan->indexed = true;
+    index_info().files_indexed += 1;
+    route().host_blocks += plan->head.size();
+    return SECEDO_OK;
+}
+
 int inflate_route(bool *device) {
     int mode = g_inflate_mode.load();
     if (mode < 0) {
@@ -861,10 +1113,11 @@ void release_inflated() {
     g_inflated = nullptr;
 }
 
-std::string record_where(const std::string &path, size_t f, uint64_t line0, uint64_t idx, Stage stage) {
+std::string record_where(const std::string &path, size_t f, uint64_t line0, uint64_t idx, Stage stage, bool indexed) {
     if (line0) return "file " + std::to_string(f) + " (" + path + "), line " + std::to_string(line0 + idx);
-    if (stage == Stage::kLoad) return path + ": record " + std::to_string(idx);
-    return "file " + std::to_string(f) + ", record " + std::to_string(idx);
+    const std::string record = (indexed ? "indexed record " : "record ") + std::to_string(idx);
+    if (stage == Stage::kLoad) return path + ": " + record;
+    return "file " + std::to_string(f) + ", " + record;
 }
 
 int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosome_ids, uint32_t n_chr,
@@ -876,8 +1129,12 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
     SECEDO_CALL(inflate_route(&device));
     std::unique_ptr<BamDevWork, void (*)(BamDevWork *)> dev_work(device ? new_bam_dev_work() : nullptr,
                                                                  delete_bam_dev_work);
+    int imode = SECEDO_BAM_INDEX_OFF;
+    SECEDO_CALL(index_mode(&imode));
+    index_info() = secedo_bam_index_info{};
     in->paths = files;
     in->line0.assign(n_files, 0);
+    in->indexed.assign(n_files, 0);
     in->chrs.resize(n_chr);
     for (uint32_t c = 0; c < n_chr; ++c) {
         ChrInput &ci = in->chrs[c];
@@ -893,6 +1150,14 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
         SECEDO_CALL(sniff(files[f], &kind));
         sam[f] = kind;
     }
+    // the index of every BAM, where one is asked for: which members of it are read
+    std::vector<IndexPlan> plans(imode == SECEDO_BAM_INDEX_OFF ? 0 : n_files);
+    for (size_t f = 0; f < plans.size(); ++f) {
+        if (sam[f]) continue;
+        SECEDO_CALL(plan_index(files[f], std::vector<uint32_t>(chromosome_ids, chromosome_ids + n_chr), imode,
+                               &plans[f]));
+        in->indexed[f] = plans[f].indexed;
+    }
     SamWork sam_work;
     Runs runs(n_chr, std::vector<std::vector<uint8_t>>(n_files));
     size_t f0 = 0;
@@ -906,13 +1171,20 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
         // a batch of BAM files of at most `batch` bytes on disk (BGZF inflates 3-4x), at least one file
         size_t f1 = f0;
         uint64_t disk = 0;
-        while (f1 < n_files && !sam[f1] && (f1 == f0 || disk < batch / 4)) {
+        if (!device && in->indexed[f0]) {  // through its index: only its spans' members
+            SECEDO_CALL(load_file_spans(f0, plans[f0], threads, batch, in, &runs, t));
+            plans[f0] = IndexPlan();
+            ++f0;
+            continue;
+        }
+        while (f1 < n_files && !sam[f1] && (f1 == f0 || disk < batch / 4) && (device || !in->indexed[f1])) {
             struct stat st;
             disk += stat(files[f1].c_str(), &st) == 0 ? uint64_t(st.st_size) : 0;
             ++f1;
         }
         if (device) {  // the opt-in route: device inflate, device walk (bam_device_input.cpp)
-            SECEDO_CALL(load_bams_device(f0, f1, threads, batch, dev_work.get(), in, &runs, t));
+            SECEDO_CALL(load_bams_device(f0, f1, threads, batch, dev_work.get(), in, &runs, t,
+                                         plans.empty() ? nullptr : &plans));
             f0 = f1;
             continue;
         }
@@ -1010,6 +1282,45 @@ extern "C" int secedo_bam_get_inflate(int *mode) {
     bool device = false;
     SECEDO_CALL(inflate_route(&device));
     *mode = device ? SECEDO_BAM_INFLATE_DEVICE : SECEDO_BAM_INFLATE_HOST;
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bam_set_index(int mode) {
+    if (mode != SECEDO_BAM_INDEX_OFF && mode != SECEDO_BAM_INDEX_AUTO && mode != SECEDO_BAM_INDEX_REQUIRE)
+        return fail(SECEDO_E_INVALID_ARG, "secedo_bam_set_index: mode " + std::to_string(mode) +
+                                              " is none of SECEDO_BAM_INDEX_OFF, _AUTO and _REQUIRE");
+    secedo::bam_host::g_index_mode.store(mode);
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bam_get_index(int *mode) {
+    if (!mode) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    return index_mode(mode);
+}
+
+extern "C" int secedo_bam_index_stats(secedo_bam_index_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = index_info();
+    return SECEDO_OK;
+}
+
+extern "C" int secedo_bam_index_ranges(const char *bam_path, uint32_t *n_ref, uint64_t *beg, uint64_t *end,
+                                       uint64_t *count, uint32_t capacity) {
+    if (!bam_path || !n_ref) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    const std::string path(bam_path);
+    IndexPlan plan;
+    SECEDO_CALL(map_file(path, &plan.m));
+    SECEDO_CALL(read_header(path, &plan));
+    std::vector<secedo::bamindex::RefRange> refs;
+    bool found = false;
+    const std::string why = read_index(path, plan.m, plan.h.n_ref, &refs, &found);
+    if (!why.empty()) return fail(SECEDO_E_INVALID_ARG, path + ": no usable index: " + why);
+    *n_ref = uint32_t(refs.size());
+    for (uint32_t r = 0; r < std::min<uint64_t>(capacity, refs.size()); ++r) {
+        if (beg) beg[r] = refs[r].beg;
+        if (end) end[r] = refs[r].end;
+        if (count) count[r] = refs[r].count;
+    }
     return SECEDO_OK;
 }
 

@@ -292,7 +292,8 @@ int decode_error(const Inputs &in, const Order &ord, bool tag_mode, unsigned lon
         idx = ord.ord_idx[o];
     }
     return fail(SECEDO_E_INVALID_ARG,
-                record_where(in.paths[file], file, in.line0[file], idx, Stage::kDevice) + ": " + decode_what(code));
+                record_where(in.paths[file], file, in.line0[file], idx, Stage::kDevice, in.indexed[file] != 0) + ": " +
+                    decode_what(code));
 }
 
 // Phase 1: the decode pass over the ordered records, then the numbering of read names (cd->id, cd->n_ids); for the

@@ -15,6 +15,9 @@
 //                                  block_size, records per RefID (scan).
 //   5. k_order, k_run_ends, k_select   sortedness against the record in front, the first run of each requested
 //                                  chromosome (started / done), the negative-position and CIGAR checks on its records.
+//   5b. k_span_check               indexed files: per span and requested chromosome, the RefID at the entry, the record
+//                                  at the chromosome's start, the records between its start and end, the RefID at
+//                                  the span's end (one thread each, binary searches over the file's record offsets).
 //   6. k_runs, k_gather            after the scans: the runs' extents, and the taken records' bytes copied by 16
 //                                  lanes a record in 16-byte vectors.
 // Errors are the minimum of (record of the file << 8 | code) per file. LDS: 4 KiB per wave in pass 2 only, so the
@@ -249,6 +252,38 @@ __global__ void __launch_bounds__(kBlock) k_select(WalkBatch b, WalkRecords r, c
     if (l_seq > 0 && n_cigar > 0 && query != l_seq) note(F, local, kErrCigarSeq);
 }
 
+// index of the first of the ascending offsets off[0, n) that is >= o
+__device__ __forceinline__ uint32_t first_at_or_past(const uint32_t *off, uint32_t n, long long o) {
+    if (o <= 0) return 0;
+    if (o > (long long)UINT32_MAX) return n;
+    return lower_bound(off, n, uint32_t(o));
+}
+
+// One thread per (file, requested chromosome) of a batch: the index's word on a span against what the walk found.
+// Runs after k_records (r.off and r.ref of the file's records, ascending by offset) and k_join (F.n_rec, F.stop_off).
+__global__ void __launch_bounds__(kBlock) k_span_check(WalkBatch b, WalkRecords r, uint32_t n_chr,
+                                                       SpanCheck *__restrict__ checks) {
+    const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (t >= uint64_t(b.n_files) * n_chr) return;
+    SpanCheck c = checks[t];
+    if (!(c.flags & kSpanOn)) return;
+    const WalkFile &F = b.files[t / n_chr];
+    const uint32_t n = uint32_t(F.n_rec);
+    const uint32_t first = b.seg_base[F.first_seg];
+    const uint32_t *off = r.off + first;
+    const long long enter = b.segs[F.first_seg].start;
+    c.entry_bad = c.tail_bad = c.start = 0;
+    if ((c.flags & kSpanEntry) && c.beg >= enter && c.beg + 8 <= (long long)F.limit)
+        c.entry_bad = int32_t(ld32(b.buf + c.beg + 4)) != c.ref;
+    const uint32_t i0 = n ? first_at_or_past(off, n, c.beg) : 0, i1 = n ? first_at_or_past(off, n, c.end) : 0;
+    c.count = i1 - i0;
+    if (c.beg >= enter && c.beg < (long long)F.stop_off)
+        c.start = (i0 < n && off[i0] == c.beg && r.ref[first + i0] == c.ref) ? 1 : 2;
+    if ((c.flags & kSpanTail) && F.limit == F.data_end && c.end >= enter && c.end + 8 <= (long long)b.buf_bytes)
+        c.tail_bad = int32_t(ld32(b.buf + c.end + 4)) == c.ref;
+    checks[t] = c;
+}
+
 __global__ void __launch_bounds__(kBlock) k_runs(WalkBatch b, WalkRecords r, uint32_t n_chr, WalkRun *runs,
                                                  uint64_t *totals) {
     const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
@@ -321,6 +356,13 @@ hipError_t walk_records(const WalkBatch &b, const WalkRecords &r, const uint32_t
         if (n_chr) hipLaunchKernelGGL(k_run_ends, dim3(grid(r.n)), dim3(kBlock), 0, s, b, r, d_chr, n_chr, d_runs);
     }
     hipLaunchKernelGGL(k_select, dim3(grid(uint64_t(r.n) + 1)), dim3(kBlock), 0, s, b, r, d_chr, n_chr, d_runs);
+    return hipGetLastError();
+}
+
+hipError_t walk_span_check(const WalkBatch &b, const WalkRecords &r, uint32_t n_chr, SpanCheck *d_checks,
+                           hipStream_t s) {
+    const uint64_t n = uint64_t(b.n_files) * n_chr;
+    if (n) hipLaunchKernelGGL(k_span_check, dim3(grid(n)), dim3(kBlock), 0, s, b, r, n_chr, d_checks);
     return hipGetLastError();
 }
 

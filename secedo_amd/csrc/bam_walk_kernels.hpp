@@ -45,6 +45,26 @@ struct WalkRun {
     uint64_t b0, b1;       // out: its bytes among the gathered ones
 };
 
+// One requested chromosome u of file f of a batch whose bytes are a span of an indexed file (or a range of one),
+// entry f * n_chr + u: what the index says of it, as offsets of the batch's buffer, against the records the walk found.
+// The offsets are signed: a chromosome may start or end in another range of the span.
+constexpr uint32_t kSpanOn = 1;     // the chromosome lies in this span
+constexpr uint32_t kSpanEntry = 2;  // beg is where the walk enters the span: the RefID there is read before the walk's
+                                    // results are believed (when those 8 bytes lie below the file's limit)
+constexpr uint32_t kSpanTail = 4;   // end is the span's limit and the 8 bytes at it are inflated: the RefID there
+struct SpanCheck {
+    // in
+    long long beg, end;
+    uint32_t flags;
+    int32_t ref;
+    // out
+    uint32_t start;      // 0: beg is no record start of this range's; 1: the record there has RefID ref; 2: none has
+    uint32_t entry_bad;  // kSpanEntry: the RefID at beg is not ref
+    uint32_t tail_bad;   // kSpanTail: the RefID at end is ref
+    uint32_t reserved;
+    uint64_t count;      // records of this range that start in [beg, end)
+};
+
 // the arrays of one batch
 struct WalkBatch {
     uint8_t *buf;               // inflated bytes; buf_bytes (a multiple of 16) are allocated
@@ -80,6 +100,9 @@ hipError_t walk_segments(const WalkBatch &b, hipStream_t s);
 // records per RefID < n_ref, d_per_ref[n_ref] = the unmapped ones. Then the run ends and the selection with its checks.
 hipError_t walk_records(const WalkBatch &b, const WalkRecords &r, const uint32_t *d_chr, uint32_t n_chr,
                         WalkRun *d_runs, unsigned long long *d_per_ref, uint32_t n_ref, hipStream_t s);
+// after walk_records: the consistency pass over the spans of indexed files, d_checks[n_files * n_chr]
+hipError_t walk_span_check(const WalkBatch &b, const WalkRecords &r, uint32_t n_chr, SpanCheck *d_checks,
+                           hipStream_t s);
 // after the scans of sel and size: the runs' extents; d_totals[0] = records taken, [1] = their bytes
 hipError_t walk_runs(const WalkBatch &b, const WalkRecords &r, uint32_t n_chr, WalkRun *d_runs, uint64_t *d_totals,
                      hipStream_t s);

@@ -50,6 +50,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--inflate", choices=("host", "device"), default=None,
                     help="Where BAM files are inflated and their records walked: host (zlib pool) or device (GPU); "
                          "the outputs are the same. Default: the environment variable SECEDO_BAM_INFLATE, else host")
+    ap.add_argument("--index", choices=("off", "auto", "require"), default=None,
+                    help="Read BAM files through their .bai index (<file>.bai, else <file without .bam>.bai): auto "
+                         "reads of an indexed BAM only the members that hold the requested chromosome and any other "
+                         "BAM in full, require fails for a BAM without a usable index, off opens no index; the outputs "
+                         "are the same. Default: the environment variable SECEDO_BAM_INDEX, else off")
     return ap.parse_args(argv)
 
 
@@ -161,7 +166,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         else:
             from .bam_pileup import bam_barcodes
 
-            values, counts = bam_barcodes(files, a.cell_tag, ids, pool_size(a.num_threads), inflate=a.inflate)
+            values, counts = bam_barcodes(files, a.cell_tag, ids, pool_size(a.num_threads), inflate=a.inflate,
+                                          index=a.index)
             n = 1 if a.min_cell_records is None else a.min_cell_records
             cells = [v for v, c in zip(values, counts) if int(c) >= n]
             if not cells:
@@ -175,6 +181,7 @@ def main(argv: Optional[List[str]] = None) -> int:
 
     tag_kw = {} if a.cell_tag is None else dict(cell_tag=a.cell_tag, cells=cells)
     tag_kw["inflate"] = a.inflate
+    tag_kw["index"] = a.index
     for chromosome, cid in zip(chromosomes, ids):
         out = a.o + "_" + chromosome + ".pileup"
         p = pileup_bams(files, out, True, cid, a.max_coverage, a.min_base_quality, a.min_map_quality,

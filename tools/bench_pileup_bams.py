@@ -266,6 +266,12 @@ def main():
     ap.add_argument("--device-inflate", action="store_true",
                     help="Also the BAM calls with inflate='device' (BGZF inflate and record walk on the GPU), in the "
                          "same run as the host route: step times, route stats, outputs compared")
+    ap.add_argument("--refs", type=int, default=0,
+                    help="The indexed shape: every cell file holds its records on each of N chromosomes and one is "
+                         "requested (with --index)")
+    ap.add_argument("--index", action="store_true",
+                    help="With --refs N: the set gets .bai files, and index='off' and index='auto' are timed in the same "
+                         "run, on the host route and, with --device-inflate, on the device route")
     ap.add_argument("--merge", nargs=2, metavar=("LINE", "PROF_DIR"))
     ap.add_argument("--merge-sam", nargs=2, metavar=("LINE", "PROF_DIR"))
     a = ap.parse_args()
@@ -274,6 +280,11 @@ def main():
         return
     if a.merge_sam:
         merge_sam(*a.merge_sam)
+        return
+    if a.refs or a.index:
+        if not (a.refs and a.index):
+            raise SystemExit("--refs N and --index go together")
+        index_shape(a)
         return
     paths, gen_s = write_set(a.dir, a.cells, a.pairs, a.mbp)
     import secedo_amd
@@ -379,6 +390,83 @@ def main():
 
 
 STEPS = ("inflate_ms", "walk_ms", "upload_ms", "device_ms", "write_ms", "total_ms")
+
+
+def _refs_cell(args):
+    """One cell of write_set copied onto n_refs chromosomes, with a .bai: per chromosome one chunk from its first
+    record to behind its last, and the pseudo-bin with the record count."""
+    from tests import bai_writer as bi
+    from tests import bam_writer as bw
+    src, dst, n_refs, mbp = args
+    raw = bi.inflate(open(src, "rb").read())
+    first = bi.record_spans(raw[:4096 + 8 + struct.unpack_from("<i", raw, 4)[0]])[0][0]
+    size = 4 + struct.unpack_from("<i", raw, first)[0]  # uniform_cell_bam's records have one size
+    recs = np.frombuffer(raw, dtype=np.uint8, offset=first).reshape(-1, size)
+    L = int(mbp * 1_000_000)
+    text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%d\tLN:%d\n" % (r + 1, L) for r in range(n_refs))
+    head = bytearray(b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", n_refs))
+    for r in range(n_refs):
+        name = b"%d\0" % (r + 1)
+        head += struct.pack("<i", len(name)) + name + struct.pack("<i", L)
+    body = []
+    for r in range(n_refs):
+        c = recs.copy()
+        c[:, 4:8] = np.frombuffer(struct.pack("<i", r), dtype=np.uint8)    # RefID
+        c[:, 24:28] = np.frombuffer(struct.pack("<i", r), dtype=np.uint8)  # next RefID
+        body.append(c.tobytes())
+    data = bw.bgzf(bytes(head) + b"".join(body))
+    open(dst, "wb").write(data)
+    table = bi.member_table(data)
+    per = len(recs) * size
+    out = bytearray(b"BAI\1" + struct.pack("<i", n_refs))
+    for r in range(n_refs):
+        beg = bi.voffset(table, len(head) + r * per)
+        end = bi.voffset(table, len(head) + (r + 1) * per)
+        out += struct.pack("<i", 2) + struct.pack("<IiQQ", 4681, 1, beg, end)
+        out += struct.pack("<IiQQQQ", bi.PSEUDO_BIN, 2, beg, end, len(recs), 0) + struct.pack("<i", 0)
+    open(dst + ".bai", "wb").write(bytes(out))
+    return len(table)
+
+
+def index_shape(a):
+    """--refs N --index: N chromosomes per file, the middle one requested; index='off' against index='auto'."""
+    paths, gen_s = write_set(a.dir, a.cells, a.pairs, a.mbp)
+    d = os.path.join(a.dir, "refs%d" % a.refs)
+    os.makedirs(d, exist_ok=True)
+    rpaths = [os.path.join(d, os.path.basename(p)) for p in paths]
+    stamp = os.path.join(d, "set.json")
+    want = dict(cells=a.cells, pairs=a.pairs, mbp=a.mbp, refs=a.refs)
+    if not (os.path.exists(stamp) and json.load(open(stamp)) == want):
+        with Pool(16) as pool:
+            members = sum(pool.map(_refs_cell, [(s, t, a.refs, a.mbp) for s, t in zip(paths, rpaths)], chunksize=4))
+        json.dump(dict(want, members=members), open(stamp, "w"))
+    from secedo_amd import bam_pileup
+
+    med = lambda xs: float(np.median(xs))  # noqa: E731
+    line = dict(workload="uniform_refs", cells=a.cells, pairs=a.pairs, mbp=a.mbp, refs=a.refs, threads=a.threads,
+                requested=a.refs // 2, members=json.load(open(stamp)).get("members"),
+                bam_bytes=sum(os.path.getsize(p) for p in rpaths))
+    outs = {}
+    for route in ("host", "device") if a.device_inflate else ("host",):
+        for mode in ("off", "auto"):
+            out = os.path.join(a.dir, "rout_%s_%s" % (route, mode))
+            runs = []
+            for k in range(a.repeat + 1):
+                t = {}
+                p = bam_pileup.pileup_bams(rpaths, out, True, a.refs // 2, 100, 30, 30, 0, a.threads, 3, times=t,
+                                           inflate=route, index=mode)
+                if k:
+                    runs.append(t)
+            r = {key: round(med([x[key] for x in runs]), 2) for key in STEPS}
+            r["inflated_bytes"] = runs[0]["inflated_bytes"]
+            rs = bam_pileup.bam_route_stats()
+            r["members_read"] = rs["host_blocks"] + rs["device_blocks"]
+            r["index_stats"] = bam_pileup.bam_index_stats()
+            r["loci"] = p.n_loci
+            outs[route, mode] = [open(out + ext, "rb").read() for ext in (".bin", ".map", ".txt")]
+            line["%s_%s" % (route, mode)] = r
+        line["%s_outputs_equal" % route] = outs[route, "auto"] == outs[route, "off"]
+    print(json.dumps(line), flush=True)
 
 
 def _bgzip(args):
