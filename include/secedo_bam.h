@@ -178,6 +178,37 @@ int secedo_bam_route_stats(secedo_bam_route_info *out);
 int secedo_bam_scan_device(const char *path, uint32_t num_threads, secedo_bam_scan_info *info,
                            uint64_t *records_per_ref, uint32_t capacity);
 
+/* What secedo_bam_index_build wrote, summed over the files whose index was finished. */
+typedef struct secedo_bam_build_info {
+    uint64_t files;       /* indexes written */
+    uint64_t records;     /* records of those files */
+    uint64_t chunks;      /* chunks written, the pseudo-bins' two not counted */
+    uint64_t bins;        /* bins written, the pseudo-bins not counted */
+    uint64_t windows;     /* entries of the linear indexes (n_intv summed) */
+    uint64_t index_bytes; /* bytes of the index files */
+    uint64_t joined_runs; /* range boundaries of a file across which a run of one (RefID, bin, flag 0x4) went on */
+    uint64_t reserved;
+} secedo_bam_build_info;
+
+/* Writes a .bai index (SAM spec 5.2) for each of n_files coordinate-sorted BAM files in one pass over them, to
+ * out_paths[f], or to <bam>.bai where out_paths or out_paths[f] is NULL. Always the device route, whatever
+ * secedo_bam_set_inflate says: the members are inflated and the records walked on the GPU as for
+ * secedo_bam_scan_device, many small files to a batch, and an index pass (secedo_amd/csrc/bam_index_kernels.hip) finds
+ * there each record's end (pos + the CIGAR's reference length, at least pos + 1), its bin (reg2bin of that, the
+ * record's own bin field is not read), the heads of the runs of one (RefID, bin) and the first record over each 16 kb
+ * window; only those come back. No index is read. What is written is fixed: bins ascending, a bin's chunks (maximal
+ * runs of consecutive records of one bin) in file order, the pseudo-bin 37450 for every reference with records, the
+ * linear index up to the last touched window with htslib's backward fill, n_no_coor. Virtual offsets name the first
+ * member that holds a byte at or past the inflated offset, the end of the data the EOF member, else the file size.
+ * Errors are SECEDO_E_INVALID_ARG and name the file and, where there is one, the record: input that is not
+ * coordinate-sorted, a SAM, BGZF SAM or plain-gzip file, a member that does not inflate or a broken record chain (in
+ * secedo_bam_scan_device's words), a reference longer than 2^29 or a record that ends past 2^29 (BAI cannot hold it),
+ * an output that exists while overwrite is 0. An index is written to a temporary name beside its target and renamed, so
+ * a failed file leaves nothing; the files in front of it in the list keep their finished indexes, and *info counts
+ * those. Sets secedo_bam_route_stats. Synchronous. num_threads: the staging pool, capped at 16 (0 = 1). */
+int secedo_bam_index_build(const char *const *bam_files, uint32_t n_files, const char *const *out_paths, int overwrite,
+                           uint32_t num_threads, secedo_bam_build_info *info);
+
 /* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
  * num_threads: inflate pool size, capped at 16 (0 = 1). */
 int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_bam_scan_info *info, uint64_t *records_per_ref,

@@ -13,6 +13,6 @@ from .spectral import laplacian, smallest_eigenpairs  # noqa: F401,E402
 from .em import expectation_maximization  # noqa: F401,E402
 from .cluster import divide_cluster, divide_cluster_resident, spectral_clustering  # noqa: F401,E402
 from .variant import reference_genotypes, variant_calling, variant_calling_resident, variant_calls  # noqa: F401,E402
-from .bam_pileup import (bam_barcodes, bam_index_ranges, bam_index_stats, bam_route_stats, bam_scan,  # noqa: F401,E402
-                         bgzf_inflate, pileup_bams, pileup_bams_resident, set_index)
+from .bam_pileup import (bam_barcodes, bam_index_build, bam_index_ranges, bam_index_stats, bam_route_stats,  # noqa: F401,E402
+                         bam_scan, bgzf_inflate, pileup_bams, pileup_bams_resident, set_index)
 from .pileup_load import read_pileups_resident  # noqa: F401,E402

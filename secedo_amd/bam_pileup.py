@@ -61,6 +61,11 @@ class IndexInfo(C.Structure):
                                           "members_skipped")]
 
 
+class BuildInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("files", "records", "chunks", "bins", "windows", "index_bytes",
+                                          "joined_runs", "reserved")]
+
+
 INFLATE_MODES = {"host": 0, "device": 1}
 INDEX_MODES = {"off": 0, "auto": 1, "require": 2}
 
@@ -94,6 +99,7 @@ SIGNATURES = {
     "secedo_bam_index_stats": (C.c_int, [C.POINTER(IndexInfo)]),
     "secedo_bam_index_ranges": (C.c_int, [C.c_char_p, C.POINTER(_u32), _vp, _vp, _vp, _u32]),
     "secedo_bam_scan_device": (C.c_int, [C.c_char_p, _u32, C.POINTER(ScanInfo), _vp, _u32]),
+    "secedo_bam_index_build": (C.c_int, [_files_t, _u32, _files_t, C.c_int, _u32, C.POINTER(BuildInfo)]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
@@ -227,6 +233,42 @@ def bam_index_ranges(path, max_refs: int = 4096) -> dict:
                                         _lib.ptr(cnt), max_refs))
     k = min(int(n.value), max_refs)
     return dict(start=beg[:k].copy(), end=end[:k].copy(), count=cnt[:k].view(np.int64).copy())
+
+
+def index_file_of(path) -> Optional[str]:
+    """The index file the readers would open for the BAM ``path``: <path>.bai, else <path without .bam>.bai; None
+    when neither exists."""
+    path = os.fspath(path)
+    names = [path + ".bai"] + ([path[:-4] + ".bai"] if len(path) > 4 and path.endswith(".bam") else [])
+    return next((n for n in names if os.path.exists(n)), None)
+
+
+def bam_index_build(files: Sequence[str], out_paths: Optional[Sequence[Optional[str]]] = None,
+                    overwrite: bool = False, num_threads: int = 1) -> dict:
+    """Writes a .bai index for each of the coordinate-sorted BAM ``files`` in one pass on the GPU: the members are
+    inflated and the records walked there (the device route, whatever ``set_inflate`` says), many small files to a
+    batch, and per record its end on the reference, its bin, the (RefID, bin) runs and the 16 kb windows are found
+    there too (secedo_amd/csrc/bam_index_kernels.hip). ``out_paths[f]`` names the index of file f; None, or a None
+    entry, means ``<bam>.bai``. An existing output raises unless ``overwrite``. -> dict(files, records, chunks, bins,
+    windows, index_bytes, joined_runs) over the indexes written. A file that cannot be indexed (not coordinate-sorted,
+    SAM, a corrupt member, a reference or record past 2^29) raises SecedoError naming it and leaves nothing behind;
+    the files in front of it in the list keep their indexes. ``bam_route_stats()`` says what the call did."""
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    arr, n = _files(files)
+    outs = None
+    if out_paths is not None:
+        if len(out_paths) != n:
+            raise _lib.SecedoError(_lib.E_INVALID_ARG, "out_paths needs one entry per file (%d), got %d"
+                                   % (n, len(out_paths)))
+        outs = (C.c_char_p * max(n, 1))(*[None if o is None else os.fsencode(str(o)) for o in out_paths])
+    try:
+        import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
+    except ImportError:
+        pass
+    info = BuildInfo()
+    check(lib().secedo_bam_index_build(arr, n, outs, int(bool(overwrite)), num_threads, C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in BuildInfo._fields_ if k != "reserved"}
 
 
 def bam_route_stats() -> dict:

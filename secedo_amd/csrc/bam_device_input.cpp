@@ -15,12 +15,22 @@
 // file go one after another, span k of every file of the call in the same batches (the first spans together with the
 // files read in full), so many small files still share one upload, one inflate launch and one walk; the file's walk state (record count, last record, runs) passes from span
 // to span as it passes from range to range. A span larger than a batch goes alone, in ranges of members.
+//
+// secedo_bam_index_build (at the end of the file) sends files through the same batches and ranges with no chromosome
+// requested, and after each batch's walk the index pass of bam_index_kernels.hip over its records: the heads of the
+// (RefID, bin) runs and the touched windows come back with file-linear offsets, the file's member table turns them into
+// virtual offsets, and bam_index_build.hpp's builder of the file takes them.
 #include "bam_host.hpp"
+#include "bam_index_build.hpp"
+#include "bam_index_kernels.hpp"
 #include "bam_kernels.hpp"  // the scan wrappers
 #include "bam_walk_kernels.hpp"
 #include "bgzf_inflate.hpp"  // the status codes
 
+#include <unistd.h>
+
 #include <climits>
+#include <cstdio>
 #include <memory>
 
 namespace secedo {
@@ -51,6 +61,12 @@ struct DevFile {
     const IndexPlan *plan = nullptr;
     std::vector<uint64_t> sp_count;
     std::vector<char> sp_start;
+    // secedo_bam_index_build: the reference lengths are kept, and what the index takes from batch to batch
+    bool want_refs = false;
+    std::vector<uint32_t> l_ref;
+    std::vector<bamindexbuild::Member> members;
+    std::unique_ptr<bamindexbuild::Builder> builder;
+    std::string out_path;
     uint64_t device_bytes() const { return carry.size() + (hb < blocks.size() ? total - blocks[hb].out : 0); }
 };
 
@@ -88,6 +104,17 @@ struct BamDevWork {
     std::vector<uint32_t> chr_ids;  // the requested chromosomes, each once
     uint32_t n_ref = 0;             // scan: per_ref counts n_ref RefIDs and the unmapped records
     bool scan = false;              // scan: unsorted input is no error, nothing is taken
+    // index build: the index pass follows the walk of every batch; `failed` = the piece whose error a batch returned
+    bool index = false;
+    uint32_t failed = UINT32_MAX;
+    Dev<IndexFile> ix_files;
+    Dev<uint32_t> ix_meta, ix_head, ix_head_scan;
+    Dev<uint64_t> ix_key, ix_key_max, ix_n_win, ix_n_win_scan;
+    Dev<IndexHead> ix_heads;
+    Dev<IndexWin> ix_wins;
+    std::vector<IndexFile> h_ix_files;
+    std::vector<IndexHead> h_heads;
+    std::vector<IndexWin> h_wins;
     std::vector<BgzfDesc> h_desc;
     std::vector<bw::Seg> h_segs;
     std::vector<WalkFile> h_files;
@@ -139,6 +166,14 @@ int open_file(size_t f, const std::string &path, size_t n_chr, DevFile *df) {
         ++df->hb;
     }
     df->carry.assign(head.begin() + df->h.first_record, head.end());
+    if (df->want_refs) {  // parse_header has checked the list
+        uint64_t o = 12 + uint64_t(df->h.l_text);
+        for (uint32_t r = 0; r < df->h.n_ref; ++r) {
+            o += 4 + uint64_t(rd32(head.data() + o));
+            df->l_ref.push_back(rd32(head.data() + o));
+            o += 4;
+        }
+    }
     df->run_first.assign(n_chr, bw::kNoRun);
     df->run_last.assign(n_chr, bw::kNoRun);
     route().host_blocks += df->hb;
@@ -179,6 +214,83 @@ int file_error(const BamDevWork &w, const Piece &p, const WalkFile &F) {
     return SECEDO_OK;
 }
 
+// The index pass over the records of a walked batch whose files passed the walk's checks: its own errors first, in
+// file order, then the heads and windows to each file's builder. A builder is touched only by a batch without errors.
+int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch &wb, const WalkRecords &wr) {
+    hipStream_t s = w->s;
+    const uint32_t n_files = uint32_t(pieces.size()), n = wr.n;
+    SECEDO_TRY(w->ix_files.grow(n_files, 0, s));
+    SECEDO_TRY(w->ix_meta.grow(n, 0, s));
+    SECEDO_TRY(w->ix_key.grow(n, 0, s));
+    SECEDO_TRY(w->ix_key_max.grow(n, 0, s));
+    SECEDO_TRY(w->ix_head.grow(uint64_t(n) + 1, 0, s));
+    SECEDO_TRY(w->ix_head_scan.grow(uint64_t(n) + 1, 0, s));
+    SECEDO_TRY(w->ix_n_win.grow(uint64_t(n) + 1, 0, s));
+    SECEDO_TRY(w->ix_n_win_scan.grow(uint64_t(n) + 1, 0, s));
+    const size_t tb = std::max(scan_bytes(uint64_t(n) + 1), index_scan_bytes(n));
+    SECEDO_TRY(w->tmp.grow(tb, 0, s));
+    SECEDO_TRY(hipMemcpyAsync(w->ix_files.p, w->h_ix_files.data(), n_files * sizeof(IndexFile), hipMemcpyHostToDevice,
+                              s));
+    const IndexRecords x{w->ix_meta.p,      w->ix_key.p,   w->ix_key_max.p,  w->ix_head.p,
+                         w->ix_head_scan.p, w->ix_n_win.p, w->ix_n_win_scan.p};
+    SECEDO_TRY(index_records(wb, wr, x, w->ix_files.p, w->tmp.p, tb, s));
+    SECEDO_TRY(index_flags(wb, wr, x, s));
+    SECEDO_TRY(exclusive_sum(w->tmp.p, tb, x.head, x.head_scan, uint64_t(n) + 1, s));
+    SECEDO_TRY(exclusive_sum64(w->tmp.p, tb, x.n_win, x.n_win_scan, uint64_t(n) + 1, s));
+    uint32_t n_heads = 0;
+    uint64_t n_wins = 0;
+    SECEDO_TRY(hipMemcpyAsync(&n_heads, x.head_scan + n, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(&n_wins, x.n_win_scan + n, 8, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(w->h_ix_files.data(), w->ix_files.p, n_files * sizeof(IndexFile), hipMemcpyDeviceToHost,
+                              s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    for (uint32_t k = 0; k < n_files; ++k) {
+        const unsigned long long e = w->h_ix_files[k].err;
+        if (e == ~0ull) continue;
+        w->failed = k;
+        const std::string where = record_where(pieces[k].df->path, 0, 0, e >> 8, Stage::kLoad);
+        const uint32_t code = uint32_t(e & 0xFF);
+        return fail(SECEDO_E_INVALID_ARG,
+                    where + (code == kIndexErrRef   ? " has a RefID outside the reference list"
+                             : code == kIndexErrEnd ? " ends past position 2^29: a BAI index cannot hold it"
+                                                    : " is longer than its block_size"));
+    }
+    // a record starts at most one run, and is the first over at most the 2^15 windows of its reference
+    if (n_heads > n || n_wins > (uint64_t(n) << 15))
+        return fail(SECEDO_E_STATE, pieces[0].df->path + ": the device index pass returned inconsistent results");
+    SECEDO_TRY(w->ix_heads.grow(n_heads, 0, s));
+    SECEDO_TRY(w->ix_wins.grow(n_wins, 0, s));
+    SECEDO_TRY(index_emit(wb, wr, x, w->ix_files.p, w->ix_heads.p, w->ix_wins.p, s));
+    w->h_heads.resize(n_heads);
+    w->h_wins.resize(n_wins);
+    if (n_heads)
+        SECEDO_TRY(hipMemcpyAsync(w->h_heads.data(), w->ix_heads.p, n_heads * sizeof(IndexHead), hipMemcpyDeviceToHost,
+                                  s));
+    if (n_wins)
+        SECEDO_TRY(hipMemcpyAsync(w->h_wins.data(), w->ix_wins.p, n_wins * sizeof(IndexWin), hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    const auto bad = [&](const DevFile &df, const std::string &why) {
+        return fail(SECEDO_E_STATE, df.path + ": the device index pass returned inconsistent results (" + why + ")");
+    };
+    for (const IndexHead &h : w->h_heads) {
+        if (h.file >= n_files) return bad(*pieces[0].df, "a file outside the batch");
+        DevFile &df = *pieces[h.file].df;
+        if (h.lin > df.total) return bad(df, "an offset past the file's bytes");
+        const std::string why = df.builder->add_head(bamindexbuild::Head{
+            h.ref, h.bin, h.unmapped, bamindexbuild::voffset(df.members, df.total, df.m.n, h.lin), h.ord});
+        if (!why.empty()) return bad(df, why);
+    }
+    for (const IndexWin &v : w->h_wins) {
+        if (v.file >= n_files) return bad(*pieces[0].df, "a file outside the batch");
+        DevFile &df = *pieces[v.file].df;
+        if (v.lin > df.total) return bad(df, "an offset past the file's bytes");
+        const std::string why = df.builder->add_window(
+            bamindexbuild::Window{v.ref, v.w, bamindexbuild::voffset(df.members, df.total, df.m.n, v.lin)});
+        if (!why.empty()) return bad(df, why);
+    }
+    return SECEDO_OK;
+}
+
 // One batch through the device: inflate, walk, the taken records back into runs / in (both may be null: scan).
 int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Inputs *in, Runs *runs,
               secedo_bam_times *t) {
@@ -198,6 +310,15 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
     w->h_runs.assign(size_t(n_files) * n_chr, WalkRun{});
     w->h_checks.assign(size_t(n_files) * n_chr, SpanCheck{});
     bool any_span = false;
+    if (w->index) {
+        w->failed = UINT32_MAX;
+        w->h_ix_files.assign(n_files, IndexFile{});
+        uint64_t seg = 0;
+        for (uint32_t k = 0; k < n_files; ++k) {
+            w->h_ix_files[k] = IndexFile{0, seg, pieces[k].df->h.n_ref, 0, ~0ull};
+            seg += uint64_t(pieces[k].df->h.n_ref) + 1;
+        }
+    }
     uint64_t in_pos = kBgzfInSlack, out_pos = 0, n_list = 0;
     for (uint32_t k = 0; k < n_files; ++k) {
         Piece &p = pieces[k];
@@ -235,6 +356,9 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
         }
         F.first_seg = p.first_member;
         F.data_end = F.limit = uint32_t(o);
+        if (w->index)  // the byte behind the carry is the first of member b0 (of the file's end, if none is left)
+            w->h_ix_files[k].delta = (long long)(p.b0 < df.blocks.size() ? df.blocks[p.b0].out : df.total) -
+                                     (long long)(data_start + carry);
         if (p.span) {  // the span's offsets as offsets of the buffer; its last range ends at its limit
             const Span &sp = *p.span;
             const long long base = (long long)(data_start + carry) - (long long)sp.blocks[p.b0].out;
@@ -386,7 +510,10 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
                               w->chr_ids.begin();
             if (w->h_checks[size_t(k) * n_chr + u0].entry_bad) return check_span_chr(p.df->path, sp.chrs[0], false, 0);
         }
-        SECEDO_CALL(file_error(*w, p, w->h_files[k]));
+        if (const int rc = file_error(*w, p, w->h_files[k])) {
+            w->failed = k;
+            return rc;
+        }
         if (!p.span) continue;
         DevFile &df = *p.df;
         for (uint32_t u = 0; u < n_chr; ++u) {
@@ -416,6 +543,7 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
         sane = sane && run.j0 <= run.j1 && run.j1 <= n_sel && run.b0 <= run.b1 && run.b1 <= sel_bytes;
     if (!sane || sum_rec != n_rec)
         return fail(SECEDO_E_STATE, pieces[0].df->path + ": the device walk returned inconsistent results");
+    if (w->index) SECEDO_CALL(index_batch(w, pieces, wb, wr));
     if (n_sel) {
         SECEDO_TRY(w->out.grow(sel_bytes, 0, s));
         SECEDO_TRY(w->sel_off.grow(n_sel, 0, s));
@@ -596,4 +724,130 @@ extern "C" int secedo_bam_scan_device(const char *path, uint32_t num_threads, se
     if (records_per_ref)
         for (uint32_t r = 0; r < std::min(capacity, df.h.n_ref); ++r) records_per_ref[r] = per[r];
     return SECEDO_OK;
+}
+
+// ---- secedo_bam_index_build
+
+namespace secedo {
+namespace bam_host {
+namespace {
+
+bool exists(const std::string &path) { return access(path.c_str(), F_OK) == 0; }
+
+// The bytes to a temporary name beside `path`, then renamed onto it: a failure leaves nothing.
+int write_renamed(const std::string &path, const std::vector<uint8_t> &bytes) {
+    const std::string tmp = path + ".tmp." + std::to_string((long long)getpid());
+    FILE *f = std::fopen(tmp.c_str(), "wb");
+    if (!f) return fail(SECEDO_E_INVALID_ARG, "Could not create " + tmp);
+    const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (std::fclose(f) != 0 || !ok || std::rename(tmp.c_str(), path.c_str()) != 0) {
+        std::remove(tmp.c_str());
+        return fail(SECEDO_E_INVALID_ARG, "Could not write " + path);
+    }
+    return SECEDO_OK;
+}
+
+// The file's index from its builder, once its last range is through.
+int finish_index(DevFile *df, secedo_bam_build_info *info) {
+    std::vector<uint8_t> bytes;
+    bamindexbuild::Stats st;
+    const std::string why = df->builder->finish(bamindexbuild::voffset(df->members, df->total, df->m.n, df->total),
+                                                df->rec_base, &bytes, &st);
+    if (!why.empty())
+        return fail(SECEDO_E_STATE, df->path + ": the device index pass returned inconsistent results (" + why + ")");
+    SECEDO_CALL(write_renamed(df->out_path, bytes));
+    info->files += 1;
+    info->records += df->rec_base;
+    info->chunks += st.chunks;
+    info->bins += st.bins;
+    info->windows += st.windows;
+    info->index_bytes += bytes.size();
+    info->joined_runs += st.joined;
+    return SECEDO_OK;
+}
+
+// What must hold of a file before any of it goes to the device.
+int open_for_index(size_t f, const std::string &path, const std::string &out, int overwrite, DevFile *df) {
+    SECEDO_CALL(require_bam(path, "cannot be indexed"));
+    if (!overwrite && exists(out))
+        return fail(SECEDO_E_INVALID_ARG, path + ": the index " + out + " exists; pass overwrite to replace it");
+    df->want_refs = true;
+    df->out_path = out;
+    SECEDO_CALL(open_file(f, path, 0, df));
+    for (uint32_t r = 0; r < df->h.n_ref; ++r)
+        if (df->l_ref[r] > bamindexbuild::kMaxEnd)
+            return fail(SECEDO_E_INVALID_ARG, path + ": reference " + std::to_string(r) + " is " +
+                                                  std::to_string(df->l_ref[r]) +
+                                                  " long, past 2^29: a BAI index cannot hold it");
+    df->members.reserve(df->blocks.size());
+    for (const Block &b : df->blocks) df->members.push_back(bamindexbuild::Member{b.coff, b.out, b.isize});
+    df->builder.reset(new bamindexbuild::Builder(df->h.n_ref));
+    return SECEDO_OK;
+}
+
+int index_build(const char *const *bam_files, uint32_t n_files, const char *const *out_paths, int overwrite,
+                uint32_t threads, secedo_bam_build_info *info) {
+    std::unique_ptr<BamDevWork> w(new BamDevWork());
+    w->index = true;
+    SECEDO_CALL(start_work(w.get(), {}));
+    const uint64_t batch = batch_bytes();
+    std::vector<std::unique_ptr<DevFile>> open;
+    std::vector<Piece> pieces;
+    uint64_t bytes = 0;
+    // The batch of small files: if one of them fails, the files in front of it go through again without it and keep
+    // their indexes, and the failed file's error is the call's.
+    const auto flush = [&]() -> int {
+        if (pieces.empty()) return SECEDO_OK;
+        int rc = run_batch(w.get(), pieces, threads, nullptr, nullptr, nullptr);
+        size_t n_good = pieces.size();
+        std::string msg;
+        if (rc != SECEDO_OK) {
+            if (w->failed == UINT32_MAX) return rc;
+            msg = g_error;
+            n_good = w->failed;
+            pieces.resize(n_good);
+            if (n_good) SECEDO_CALL(run_batch(w.get(), pieces, threads, nullptr, nullptr, nullptr));
+        }
+        for (size_t k = 0; k < n_good; ++k) SECEDO_CALL(finish_index(pieces[k].df, info));
+        pieces.clear();
+        open.clear();
+        bytes = 0;
+        return rc == SECEDO_OK ? rc : fail(rc, msg);
+    };
+    for (uint32_t f = 0; f < n_files; ++f) {
+        if (!bam_files[f]) return fail(SECEDO_E_INVALID_ARG, "null file name");
+        const std::string path = bam_files[f];
+        const std::string out = out_paths && out_paths[f] ? std::string(out_paths[f]) : path + ".bai";
+        std::unique_ptr<DevFile> df(new DevFile());
+        const int rc = open_for_index(f, path, out, overwrite, df.get());
+        if (rc != SECEDO_OK) {  // the files in front of it come first
+            const std::string msg = g_error;
+            SECEDO_CALL(flush());
+            return fail(rc, msg);
+        }
+        const uint64_t n = df->device_bytes();
+        if (n > batch || n > kMaxBatchBytes / 2) {
+            SECEDO_CALL(flush());
+            SECEDO_CALL(run_ranges(w.get(), df.get(), nullptr, threads, batch, nullptr, nullptr, nullptr));
+            SECEDO_CALL(finish_index(df.get(), info));
+            continue;
+        }
+        if (!pieces.empty() && bytes + n > batch) SECEDO_CALL(flush());
+        pieces.push_back(Piece{df.get(), df->hb, df->blocks.size(), true});
+        open.push_back(std::move(df));
+        bytes += n;
+    }
+    return flush();
+}
+
+}  // namespace
+}  // namespace bam_host
+}  // namespace secedo
+
+extern "C" int secedo_bam_index_build(const char *const *bam_files, uint32_t n_files, const char *const *out_paths,
+                                      int overwrite, uint32_t num_threads, secedo_bam_build_info *info) {
+    if (!bam_files || !info) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *info = secedo_bam_build_info{};
+    route() = secedo_bam_route_info{};
+    return index_build(bam_files, n_files, out_paths, overwrite, num_threads ? num_threads : 1, info);
 }

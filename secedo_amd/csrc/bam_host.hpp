@@ -187,6 +187,10 @@ void delete_bam_dev_work(BamDevWork *w);
 int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, BamDevWork *w, Inputs *in, Runs *runs,
                      secedo_bam_times *t, std::vector<IndexPlan> *plans = nullptr);
 
+// The file is BAM by content, as load_inputs tells it: a SAM or BGZF SAM file is SECEDO_E_INVALID_ARG ("<path>: a SAM
+// file <what>; ..."), a plain-gzip file is refused in load_inputs' words.
+int require_bam(const std::string &path, const std::string &what);
+
 // Frees the device memory of the last secedo_bgzf_inflate result of this thread (secedo_bam_release calls it).
 void release_inflated();
 

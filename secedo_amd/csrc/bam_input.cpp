@@ -919,6 +919,15 @@ secedo_bam_route_info &route() {
     return r;
 }
 
+int require_bam(const std::string &path, const std::string &what) {
+    Kind kind = kBam;
+    SECEDO_CALL(sniff(path, &kind));
+    if (kind != kBam)
+        return fail(SECEDO_E_INVALID_ARG, path + ": " + (kind == kSam ? "a SAM file" : "a BGZF-compressed SAM file") +
+                                              " " + what + "; convert it to BAM (samtools view -b)");
+    return SECEDO_OK;
+}
+
 namespace {
 std::atomic<int> g_inflate_mode{-1};  // -1: not set by secedo_bam_set_inflate, the environment decides
 }

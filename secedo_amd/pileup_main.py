@@ -17,6 +17,10 @@ SAM text input (coordinate-sorted, as aligners write it) goes the same way: its 
 BAM records the BAM route reads, so a SAM file gives what the BAM `samtools view -b` writes from it would give.
 A .sam.gz written by `bgzip` (BGZF) is inflated on the GPU in front of that parse and gives what its text gives; a
 .sam.gz written by plain `gzip` is refused. Files are told apart by content, the names only serve the directory search.
+
+--build_index writes, before the run, <bam>.bai for every input BAM that has no index file where --index looks
+(<bam>.bai, <bam without .bam>.bai), all of them in one pass on the GPU (``secedo_amd.bam_index_build``), and never
+touches an index file that exists; the run then goes on as --index says.
 """
 from __future__ import annotations
 
@@ -55,6 +59,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                          "reads of an indexed BAM only the members that hold the requested chromosome and any other "
                          "BAM in full, require fails for a BAM without a usable index, off opens no index; the outputs "
                          "are the same. Default: the environment variable SECEDO_BAM_INDEX, else off")
+    ap.add_argument("--build_index", action="store_true",
+                    help="Before the run, write <bam>.bai on the GPU for every input BAM without an index file; an "
+                         "existing index file is never touched. The run then proceeds as --index says")
     return ap.parse_args(argv)
 
 
@@ -92,6 +99,39 @@ def check_tag_flags(a: argparse.Namespace) -> None:
         raise SystemExit("--cells file %s does not exist" % a.cells)
     if a.min_cell_records is not None and a.min_cell_records < 1:
         raise SystemExit("--min_cell_records must be at least 1")
+
+
+def check_index_flags(a: argparse.Namespace) -> None:
+    """--build_index against --index and the input, checked before any BAM is read (and before torch is imported)."""
+    if not a.build_index:
+        return
+    if a.index == "off":
+        raise SystemExit("--build_index with --index off: the indexes would not be read; use --index auto or require")
+    if not os.path.exists(a.i):
+        raise SystemExit("Input %s does not exist" % a.i)
+
+
+def is_bam(path: str) -> bool:
+    """By content, as the library tells: gzip whose first inflated bytes are the BAM magic."""
+    import zlib
+    try:
+        with open(path, "rb") as f:
+            head = f.read(1 << 16)
+        return head[:2] == b"\x1f\x8b" and zlib.decompressobj(31).decompress(head, 4) == b"BAM\1"
+    except (OSError, zlib.error):
+        return False
+
+
+def build_missing_indexes(files: List[str], num_threads: int) -> List[str]:
+    """<bam>.bai for every BAM of ``files`` without an index file at either place the reader looks -> those BAMs."""
+    from .bam_pileup import bam_index_build, index_file_of
+
+    todo = [f for f in files if is_bam(f) and index_file_of(f) is None]
+    if todo:
+        info = bam_index_build(todo, num_threads=num_threads)
+        print("Indexed %d of %d input files (%d records, %d index bytes)"
+              % (info["files"], len(files), info["records"], info["index_bytes"]))
+    return todo
 
 
 def chromosome_to_id(chromosome: str) -> int:
@@ -144,6 +184,7 @@ def cell_map_lines(files: List[str]) -> List[str]:
 def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
     check_tag_flags(a)
+    check_index_flags(a)
     if a.cell_tag is not None and not os.path.exists(a.i):
         raise SystemExit("Input %s does not exist" % a.i)
     files = input_files(a.i)
@@ -157,6 +198,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise SystemExit("-o <output_dir> must be a file prefix, not a directory")
     chromosomes = a.chromosomes.split(",")
     ids = [chromosome_to_id(c) for c in chromosomes]
+    if a.build_index:
+        build_missing_indexes(files, pool_size(a.num_threads))
     cells = None
     if a.cell_tag is not None:
         if a.cells is not None:
