@@ -1,12 +1,14 @@
 """GPU parity of the EM refinement (include/secedo_em.h) against oracle/em_oracle.c and the vectors of the
 compiled reference. Floating point: the per-locus and per-cell sums are formed in a different order
 than the reference's sequential loops, so probabilities agree to 1e-9 (observed ~1e-13), the number
-of iterations exactly."""
+of iterations exactly. For the cases of tests/em_cases.py that equality is owed, not observed: tests/test_em_cpu.py
+asserts that none of their iterations comes within 1e-6 of the 1e-2 edge that ends the refinement."""
 import numpy as np
 import pytest
 
 import secedo_amd
 from oracle import bindings as ob
+from tests import em_cases
 from tests.test_em_cpu import CASES, THETA
 
 pytestmark = pytest.mark.gpu
@@ -96,3 +98,51 @@ def test_scratch_pool_release_and_concurrent_callers():
     _lib.lib().secedo_simmat_release_cache()
     for got, it in results + [secedo_amd.expectation_maximization(p, i2p, 1, 1e-3, prob.copy())]:
         assert it == it_ref and np.max(np.abs(got - ref)) <= TOL
+
+
+# ---- the kernels' edges (tests/em_cases.py; the conditions that make the iteration count exact are asserted in
+# tests/test_em_cpu.py) ----
+
+def _refine(name, **kw):
+    p, i2p, theta, prob = em_cases.CASES[name]
+    return secedo_amd.expectation_maximization(p, i2p, 1, theta, prob.copy(), **kw)
+
+
+@pytest.mark.parametrize("name", list(em_cases.CASES))
+def test_hip_matches_oracle_on_edge_cases(name):
+    """Exact 0 / 1 probabilities (a centre without weight, a prior of 0), locus depths around one, two and four
+    waves, cells without entries, n_cells around the E-step's 1024 lanes, n_cells = 1, permuted id_to_pos with
+    16- and 32-bit ids."""
+    want, it_ref = em_cases.oracle(name)
+    got, it = _refine(name)
+    print(name, "iterations", it, "oracle", it_ref, "max |gpu - oracle|", np.max(np.abs(got - want)))
+    assert not np.any(np.isnan(got))
+    assert np.max(np.abs(got - want)) <= TOL
+    assert it == it_ref
+
+
+@pytest.mark.parametrize("name", em_cases.BOUNDARY)
+def test_iteration_limit_at_and_below_the_oracle_count(name):
+    want, it_ref = em_cases.oracle(name)
+    got, it = _refine(name, max_iterations=it_ref)
+    assert it == it_ref and np.max(np.abs(got - want)) <= TOL
+    if it_ref > 1:
+        with pytest.raises(secedo_amd.SecedoError):
+            _refine(name, max_iterations=it_ref - 1)
+
+
+@pytest.mark.parametrize("kind", em_cases.STARTS)
+def test_resident_entry_is_bit_identical_to_the_host_entry(kind):
+    """secedo_amd.em.refine_resident, the entry divide_cluster uses, on tensors put into HBM here."""
+    import torch
+    from secedo_amd.em import refine_resident
+    name = "boundary_n66_" + kind
+    p, i2p, theta, prob = em_cases.CASES[name]
+    assert int(p.id_base.max()) <= 0xFFFF
+    up = lambda a, view: torch.from_numpy(np.array(a).view(view)).to("cuda:0")  # noqa: E731
+    d_prob = torch.from_numpy(prob.copy()).to("cuda:0")
+    it = refine_resident(up(p.locus_entry_off, np.int64), p.n_loci, p.n_entries,
+                         up(p.id_base.astype(np.uint16), np.int16), up(i2p, np.int32), theta, d_prob)
+    got, it_host = _refine(name)
+    assert it == it_host == em_cases.oracle(name)[1]
+    assert np.array_equal(d_prob.cpu().numpy(), got)
