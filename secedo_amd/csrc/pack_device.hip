@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 namespace secedo {
 
@@ -111,8 +112,11 @@ __global__ void k_publish(const Scalars *sc, const unsigned long long *totals, M
     }
 }
 
+// behind: launches that do not touch the scalars and whose results the caller wants whatever the scalars say. They
+// are enqueued behind the publishing kernel and in front of the wait: the host has the scalars as early as without
+// them, and the GPU has work while the host acts on them.
 hipError_t read_scalars(DevicePacked &pk, hipStream_t stream, const Scalars *sc, const unsigned long long *totals,
-                        Scalars *out, unsigned long long *out_totals) {
+                        Scalars *out, unsigned long long *out_totals, const std::function<void()> &behind = nullptr) {
     static const bool plain = [] {
         const char *e = std::getenv("SECEDO_PACK_READBACK");
         return e && std::strcmp(e, "memcpy") == 0;
@@ -132,6 +136,7 @@ hipError_t read_scalars(DevicePacked &pk, hipStream_t stream, const Scalars *sc,
         const unsigned long long seq = ++pk.mailbox_seq;
         hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, stream, sc, totals, box, seq);
         if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (behind) behind();
         // poll; every few thousand polls ask the runtime whether the stream died or drained without
         // the word arriving (then the plain copy below reports what happened)
         bool arrived = false;
@@ -154,6 +159,8 @@ hipError_t read_scalars(DevicePacked &pk, hipStream_t stream, const Scalars *sc,
             if (out_totals) *out_totals = box->totals;
             return hipSuccess;
         }
+    } else if (behind) {
+        behind();
     }
     if (out_totals) {
         *out_totals = 0;
@@ -679,6 +686,44 @@ __global__ __launch_bounds__(TPB) void k_pflag_compact(const uint32_t *entry32, 
         }
     }
 }
+// The same lists where k_entry_records has left the chunks' flags (chunk_mask, one ballot per 64 entries) and the
+// blocks' sums behind it: this pass reads 8 bytes per 64 entries where k_pflag_compact reads entry32 a third time,
+// and the count pass is gone. A wave takes the chunks wave + k * WAVES of its block, in k_pflag_compact's numbering.
+__global__ __launch_bounds__(TPB) void k_pflag_compact_masks(const unsigned long long *chunk_mask, const uint4 *entry,
+                                                            const uint32_t *block_off, uint4 *rec, uint32_t *idx,
+                                                            uint32_t *chunk_pre) {
+    constexpr int WAVES = TPB / 64;
+    constexpr uint32_t CHUNKS = kFlagBlock / 64u;
+    static_assert(CHUNKS == 64, "one wave scans the chunks' counts");
+    __shared__ unsigned long long mask[CHUNKS];
+    __shared__ uint32_t pre[CHUNKS];  // flagged entries of the block before the chunk
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t chunk0 = blockIdx.x * CHUNKS;
+    if (threadIdx.x < 64u) {
+        const unsigned long long m = chunk_mask[chunk0 + threadIdx.x];
+        const uint32_t v = (uint32_t)__popcll(m);
+        uint32_t incl = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if (lane >= (uint32_t)off) incl += up;
+        }
+        mask[threadIdx.x] = m;
+        pre[threadIdx.x] = incl - v;
+        chunk_pre[chunk0 + threadIdx.x] = block_off[blockIdx.x] + incl - v;
+    }
+    __syncthreads();
+    const uint32_t base = block_off[blockIdx.x];
+#pragma unroll 4
+    for (uint32_t c = wv; c < CHUNKS; c += WAVES) {
+        const unsigned long long m = mask[c];
+        if ((m >> lane) & 1ull) {  // (no flag lies behind the last entry: k_entry_records' ballots)
+            const uint32_t e = (chunk0 + c) * 64u + lane;
+            const uint32_t j = base + pre[c] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            rec[j] = entry[e];
+            idx[j] = e;
+        }
+    }
+}
 // grp[i] = flagged entries before entry blk_off[i]: the flagged entries before each (block, locus) group. (An offset
 // at the end of the last whole chunk reads the total behind the chunks, chunk_pre[n_chunks], and no mask.)
 __global__ __launch_bounds__(TPB) void k_pflag_groups(const uint32_t *blk_off, size_t n_off, const uint32_t *chunk_pre,
@@ -688,6 +733,41 @@ __global__ __launch_bounds__(TPB) void k_pflag_groups(const uint32_t *blk_off, s
         grp[i] = chunk_pre[c] + (r ? (uint32_t)__popcll(chunk_mask[c] & ((1ull << r) - 1ull)) : 0u);
     }
 }
+// flag_list_scratch: block sums and offsets (nb each), chunk_pre (64 nb + 1), chunk_mask (64 nb, 8-byte aligned)
+uint32_t flag_blocks(uint32_t n_entries) { return std::max<uint32_t>(1u, (n_entries + kFlagBlock - 1) / kFlagBlock); }
+struct FlagScratch {
+    uint32_t nb;
+    uint32_t *block_sum, *block_off, *chunk_pre;
+    unsigned long long *chunk_mask;
+    FlagScratch(void *scratch, uint32_t n_entries) : nb(flag_blocks(n_entries)) {
+        block_sum = block_off = chunk_pre = nullptr;
+        chunk_mask = nullptr;
+        if (!scratch) return;
+        block_sum = static_cast<uint32_t *>(scratch);
+        block_off = block_sum + nb;
+        chunk_pre = block_off + nb;
+        chunk_mask = reinterpret_cast<unsigned long long *>(chunk_pre + 64 * (size_t)nb + 2);
+    }
+    static size_t bytes(uint32_t n_entries) {
+        const size_t nb = flag_blocks(n_entries);
+        return (2 * nb + 64 * nb + 2) * 4 + 64 * nb * 8;
+    }
+};
+void flag_groups(const FlagScratch &fs, const uint32_t *blk_off, size_t n_off, uint32_t *grp, hipStream_t stream) {
+    if (!n_off) return;
+    const uint32_t blocks = (uint32_t)std::min<size_t>((n_off + TPB - 1) / TPB, 256 * 32);
+    hipLaunchKernelGGL(k_pflag_groups, dim3(blocks), dim3(TPB), 0, stream, blk_off, n_off, fs.chunk_pre, fs.chunk_mask, grp);
+}
+// the lists behind a k_entry_records that has written fs.chunk_mask and fs.block_sum
+void flag_lists_from_masks(const FlagScratch &fs, const uint4 *entry, const uint32_t *blk_off, size_t n_off,
+                           uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream) {
+    hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, fs.block_sum, fs.nb, fs.block_off,
+                       fs.chunk_pre + 64 * (size_t)fs.nb, static_cast<Scalars *>(nullptr));
+    hipLaunchKernelGGL(k_pflag_compact_masks, dim3(fs.nb), dim3(TPB), 0, stream, fs.chunk_mask, entry, fs.block_off, rec,
+                       idx, fs.chunk_pre);
+    flag_groups(fs, blk_off, n_off, grp, stream);
+}
+
 __global__ void k_m_fields(Raw in, const uint32_t *eloc, const uint32_t *dense, const uint32_t *last,
                            const uint32_t *m_idx, const uint32_t *m_entry, uint32_t n_m, uint32_t *rid_m,
                            uint32_t *idb_m, uint32_t *eloc_m, uint32_t *winner_m, uint32_t *count_m) {
@@ -1098,9 +1178,14 @@ __global__ void k_keys2(Raw in, const uint32_t *sval, const unsigned long long *
 // Single-entry fast path (m_idx != null): ONLY the S entries are counted, and their slots are made here -- (block,
 // cell) from the group map, validated as k_keys2 does for the M entries -- with nothing of the read assembly:
 // k_keys2 adds the kept M entries afterwards, and k_bin_place knows an S entry's tail flag from its index.
-// (Measured and dropped: this pass on a stream of its own beside stages 1b-4. The kernels there are not idle
-// time but memory-side work -- the id-space scan went from 104 to 169 us next to it -- and the step gained
-// nothing.)
+// (Measured and dropped, twice: this pass on a stream of its own beside the M entries' read assembly, which it does
+// not depend on. Round 15, launched right behind read-back 1b for an assumed block size, C3 under the profiler: the
+// pass took 196 us instead of 158, k_m_fields started 47 us later (the host's fork and launch), the assembly's
+// fourteen kernels took 77 us longer and k_read_info ended 109 us later -- and with it the flush chain on the side
+// stream, at 643 us instead of 524, which k_bin_place waits for: k_keys2 started 40 us earlier, k_bin_place and
+// everything behind it not at all. The chain (118 us, serial, behind k_read_info) hides behind this pass in the
+// serial order and is the critical path beside it. Round 3 had found the same with a 104 us id-space scan as the
+// neighbour.)
 // A workgroup takes TL consecutive loci at a time (TL a power of two, <= 64, nb * (TL + 1) words of LDS) and counts
 // their entries -- one contiguous stretch of the pileup -- into hist[block][locus in tile], a thread per entry,
 // four entries of a thread in flight; the locus of an entry comes from the tile's offsets in LDS (a search over 65
@@ -1655,8 +1740,9 @@ struct RecordTables {  // by value: what a record needs beside the group's own e
     uint32_t *entry32, *mask32, *entry_read;
 };
 
-// rec: the M entry's m_rec word group, loaded by the caller (all zero for an S entry)
-__device__ __forceinline__ void emit_record(const RecordTables &t, uint32_t d, uint32_t k, uint4 rec, uint32_t cib,
+// rec: the M entry's m_rec word group, loaded by the caller (all zero for an S entry). Returns whether the entry is
+// flagged (kC_Tail | kC_Multi): what the flagged entries' lists are made of
+__device__ __forceinline__ bool emit_record(const RecordTables &t, uint32_t d, uint32_t k, uint4 rec, uint32_t cib,
                                             uint32_t cell, uint32_t l, uint32_t lrel) {
     uint32_t base, meta, masks = 0, bases = 0, r = 0;
     bool multi = false, wide = false, tail;
@@ -1684,19 +1770,28 @@ __device__ __forceinline__ void emit_record(const RecordTables &t, uint32_t d, u
     if (t.mask32)
         t.mask32[d] = (masks & 0xFFu) | (((masks >> 16) & 0xFFu) << 8) | ((bases & 0xFFu) << 16)
                 | (((bases >> 16) & 0xFFu) << 24);
+    return multi || tail;
 }
 
 constexpr int TPB_REC = 512;
 __global__ __launch_bounds__(TPB_REC) void k_entry_records(const unsigned long long *grouped, const uint32_t *blk_off,
                                                           uint32_t n, uint32_t nb, uint32_t L, uint32_t B,
                                                           uint32_t lbits, RecordTables t,
-                                                          unsigned long long *per_cell_sq, Scalars *sc) {
+                                                          unsigned long long *per_cell_sq, Scalars *sc,
+                                                          unsigned long long *chunk_mask, uint32_t *block_sum) {
     constexpr uint32_t SLOTS = 512;
     __shared__ unsigned long long sq[SLOTS];
     __shared__ uint32_t blk_start[1025];  // first entry of every cell block (nb <= 1024), and the end
     __shared__ uint32_t first_cell;
-    const uint32_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const uint32_t d0 = blockIdx.x * per_block, d1 = min(n, d0 + per_block);
+    __shared__ uint32_t n_flagged;  // of this workgroup's entries
+    // A workgroup takes one block of kFlagBlock entries (the grid is their number), so that a wave's 64 entries of a
+    // round are one 64-entry chunk of the flagged entries' lists: where chunk_mask is given, the chunks' flags (one
+    // ballot each, zero behind the last entry) and the block's count leave from here, and the lists need no further
+    // pass over entry32 (k_flag_scan, k_pflag_compact_masks, k_pflag_groups).
+    constexpr int U = 4;
+    static_assert(kFlagBlock % (TPB_REC * U) == 0, "whole rounds per block of the lists");
+    const uint32_t d0 = blockIdx.x * kFlagBlock, d1 = min(n, d0 + kFlagBlock);  // (the last block starts below n < 2^31)
+    if (threadIdx.x == 0) n_flagged = 0;
     for (uint32_t i = threadIdx.x; i < SLOTS; i += TPB_REC) sq[i] = 0;
     for (uint32_t i = threadIdx.x; i <= nb; i += TPB_REC) blk_start[i] = i < nb ? blk_off[(size_t)i * (L + 1)] : n;
     __syncthreads();
@@ -1720,8 +1815,9 @@ __global__ __launch_bounds__(TPB_REC) void k_entry_records(const unsigned long l
     // the stores, 20 for the block search. Staging the slice's per-locus words in LDS -- the slots are in (block,
     // locus) order, a slice covers 2000 consecutive loci -- was measured SLOWER, 197 against 176 us: two more
     // dependent reads and two barriers in front of every slice.)
-    constexpr int U = 4;
-    for (uint32_t base = d0; base < d1; base += TPB_REC * U) {
+    uint32_t wave_flagged = 0;
+    for (uint32_t base = d0; base < d0 + kFlagBlock; base += TPB_REC * U) {
+        if (base >= d1 && !chunk_mask) break;
         unsigned long long mine[U];
         uint32_t blk[U], linfo[U], same[U];
         uint4 rec[U];
@@ -1760,17 +1856,26 @@ __global__ __launch_bounds__(TPB_REC) void k_entry_records(const unsigned long l
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t p = base + (uint32_t)u * TPB_REC + threadIdx.x;
-            if (p >= d1) continue;
-            const uint32_t k = (uint32_t)mine[u], cib = (uint32_t)(mine[u] >> 32) & ((1u << kCibBits) - 1u);
-            const uint32_t l = (uint32_t)(mine[u] >> (32 + kCibBits)) & lmask;
-            const uint32_t cell = blk[u] * B + cib;
-            emit_record(t, p, k, rec[u], cib, cell, l, linfo[u] & 0xFFFFu);
-            const uint32_t rel = cell - first_cell;
-            if (rel < SLOTS) atomicAdd(&sq[rel], (unsigned long long)same[u]);
-            else atomicAdd(&per_cell_sq[cell], (unsigned long long)same[u]);
+            bool flagged = false;
+            if (p < d1) {
+                const uint32_t k = (uint32_t)mine[u], cib = (uint32_t)(mine[u] >> 32) & ((1u << kCibBits) - 1u);
+                const uint32_t l = (uint32_t)(mine[u] >> (32 + kCibBits)) & lmask;
+                const uint32_t cell = blk[u] * B + cib;
+                flagged = emit_record(t, p, k, rec[u], cib, cell, l, linfo[u] & 0xFFFFu);
+                const uint32_t rel = cell - first_cell;
+                if (rel < SLOTS) atomicAdd(&sq[rel], (unsigned long long)same[u]);
+                else atomicAdd(&per_cell_sq[cell], (unsigned long long)same[u]);
+            }
+            if (chunk_mask) {  // (uniform; p - lane is a multiple of 64: d0, TPB_REC and the wave's offset are)
+                const unsigned long long m = __ballot(flagged);
+                wave_flagged += (uint32_t)__popcll(m);
+                if ((threadIdx.x & 63u) == 0u) chunk_mask[p >> 6] = m;
+            }
         }
     }
+    if (chunk_mask && (threadIdx.x & 63u) == 0u && wave_flagged) atomicAdd(&n_flagged, wave_flagged);
     __syncthreads();
+    if (block_sum && threadIdx.x == 0) block_sum[blockIdx.x] = n_flagged;
     if (d0 < n)
         for (uint32_t i = threadIdx.x; i < SLOTS; i += TPB_REC)
             if (sq[i]) atomicAdd(&per_cell_sq[first_cell + i], sq[i]);
@@ -1827,7 +1932,7 @@ int bits_for(unsigned long long max_value) {
 // too long for it sets *retry and the caller runs the attempt again with the radix sorts.
 std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_t mfl, uint32_t num_threads,
                          uint32_t block_cells, StageGeometry (*geometry)(uint32_t), bool allow_count_tile,
-                         bool force_radix, bool no_assumptions, hipStream_t stream, DevicePacked *out,
+                         bool force_radix, bool no_assumptions, bool overlap, hipStream_t stream, DevicePacked *out,
                          bool *need_host, int *retry) {
     *retry = kNoRetry;
     const uint32_t E = static_cast<uint32_t>(in.n_entries);
@@ -2349,6 +2454,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     // the locus ranges were cut for both sets of limits on the side stream (after the flush chain): pick
     HIP_OK(hipStreamWaitEvent(stream, pk.ev_join, 0));
     side_join.joined = true;
+    bool lists_launched = false;
     if (force_radix) {
         hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, stream, seg_ends, seg_count, variant_stride, n_seg,
                            caps, pk.range_off.as<uint32_t>(), per_cell_sq, n_kept ? nb * B : 0u, -1, sc);
@@ -2376,15 +2482,31 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
                                       pk.stage_masks ? pk.mask32.as<uint32_t>() : nullptr,
                                       pk.entry_read.as<uint32_t>()};
             const unsigned long long *grouped = key_b;
-            hipLaunchKernelGGL(k_entry_records, dim3(std::min<uint32_t>(1u << 16, (n_kept + 4095) / 4096)), dim3(TPB_REC),
-                               0, stream, grouped, blk_off, n_kept, nb, L, B, lbits, tables, per_cell_sq, sc);
+            // The flagged entries' lists are wanted wherever the count tile is taken, and they do not depend on what
+            // read-back 3 decides (the records carry the absolute locus, k_fix_locus_rel touches the upper half of
+            // entry32 only): the records pass leaves the chunks' flags, and the list chain goes behind the publishing
+            // kernel of read-back 3 (below). If the pair bound forbids the count tile the lists are not used.
+            const bool lists_here = overlap && caps.allow_counts && !pk.stage_masks && pk.flag_lists.scratch;
+            const FlagScratch fs(pk.flag_lists.scratch, n_kept);
+            hipLaunchKernelGGL(k_entry_records, dim3((n_kept + kFlagBlock - 1) / kFlagBlock), dim3(TPB_REC), 0, stream,
+                               grouped, blk_off, n_kept, nb, L, B, lbits, tables, per_cell_sq, sc,
+                               lists_here ? fs.chunk_mask : nullptr, lists_here ? fs.block_sum : nullptr);
+            lists_launched = lists_here;
         }
         hipLaunchKernelGGL(k_pair_bound, dim3(1), dim3(TPB), 0, stream, per_cell_sq, n_kept ? nb * B : 0u, caps,
                            (uint32_t)assumed, sc);
     }
-    // read-back 3: errors of the group mapping, pair bound (-> tile variant), number of ranges
+    // read-back 3: errors of the group mapping, pair bound (-> tile variant), number of ranges. The list chain goes
+    // behind its publishing kernel: the GPU works through the lists while the host reads the scalars, returns to its
+    // caller and launches the pair kernel. (In front of the publishing kernel the host learned the scalars 50 us
+    // later and the GPU then stood idle for as long as the host needs from there to the pair kernel's launch: 74 us
+    // under the profiler on C3, and C2, whose lists take 15 us, lost 20 us against the lists behind the read-back.)
     trace.mark("records launched");
-    HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));
+    HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr, [&] {
+        if (lists_launched)
+            flag_lists_from_masks(FlagScratch(pk.flag_lists.scratch, n_kept), pk.entry.as<uint4>(), blk_off, n_off,
+                                  pk.flag_lists.grp, pk.flag_lists.rec, pk.flag_lists.idx, stream);
+    }));
     trace.mark("read-back 3 arrived");
     if (!force_radix && hsc.caps_wrong && !hsc.regroup && hsc.error == 0) {
         hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, stream, seg_ends, seg_count, variant_stride, n_seg,
@@ -2413,6 +2535,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     pk.num_ranges = hsc.num_ranges;
     pk.max_range_span = hsc.max_range_span;
     pk.n_wide = hsc.n_wide;
+    pk.flag_lists_built = lists_launched;
     HIP_OK(hipGetLastError());
     return std::string();
 }
@@ -2424,6 +2547,7 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
                                StageGeometry (*geometry)(uint32_t), bool allow_count_tile,
                                hipStream_t stream, DevicePacked *out, bool *need_host) {
     *need_host = false;
+    out->flag_lists_built = false;
     if ((in.id_base16 != nullptr) == (in.id_base32 != nullptr))
         return "exactly one of id_base16 / id_base32 must be given";
     if (num_threads == 0) return "num_threads must be positive";
@@ -2439,6 +2563,10 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
     }
     bool force_radix = false;
     if (const char *env = std::getenv("SECEDO_PACK_GROUPING")) force_radix = std::string(env) == "radix";
+    // SECEDO_PACK_OVERLAP=0: the serial order -- the flagged entries' lists made by the caller from entry32
+    // (pack_flag_lists) behind read-back 3, not from k_entry_records' ballots beside it
+    bool overlap = true;
+    if (const char *env = std::getenv("SECEDO_PACK_OVERLAP")) overlap = std::atoi(env) != 0;
     // an attempt can ask to be repeated: with the radix sorts (a group too long for the counting scheme),
     // or as it was but without assuming the previous call's sizes
     int retry = kNoRetry;
@@ -2456,7 +2584,7 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
                 if (a.p && hipMemset(a.p, 0xA5, a.bytes) != hipSuccess) return "poison: memset failed";
         }
         err = pack_attempt(in, num_cells, mfl, num_threads, block_cells, geometry, allow_count_tile, force_radix,
-                           no_assumptions, stream, out, need_host, &retry);
+                           no_assumptions, overlap, stream, out, need_host, &retry);
         if (!err.empty() || retry == kNoRetry) break;
         if (retry == kRetryRadix) force_radix = true;
         if (retry == kRetrySameScheme) no_assumptions = true;
@@ -2466,28 +2594,17 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
 }
 
 
-// flag_list_scratch: block sums and offsets (nb each), chunk_pre (64 nb + 1), chunk_mask (64 nb, 8-byte aligned)
-static uint32_t flag_blocks(uint32_t n_entries) { return std::max<uint32_t>(1u, (n_entries + kFlagBlock - 1) / kFlagBlock); }
-
-size_t flag_list_scratch_bytes(uint32_t n_entries) {
-    const size_t nb = flag_blocks(n_entries);
-    return (2 * nb + 64 * nb + 2) * 4 + 64 * nb * 8;
-}
+size_t flag_list_scratch_bytes(uint32_t n_entries) { return FlagScratch::bytes(n_entries); }
 
 hipError_t pack_flag_lists(const uint32_t *entry32, const uint4 *entry, uint32_t n_entries, const uint32_t *blk_off,
                            size_t n_off, void *scratch, uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream) {
-    const uint32_t nb = flag_blocks(n_entries);
-    uint32_t *block_sum = static_cast<uint32_t *>(scratch), *block_off = block_sum + nb, *chunk_pre = block_off + nb;
-    unsigned long long *chunk_mask = reinterpret_cast<unsigned long long *>(chunk_pre + 64 * (size_t)nb + 2);
-    hipLaunchKernelGGL(k_pflag_count, dim3(nb), dim3(TPB), 0, stream, entry32, n_entries, block_sum);
-    hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, block_sum, nb, block_off,
-                       chunk_pre + 64 * (size_t)nb, static_cast<Scalars *>(nullptr));
-    hipLaunchKernelGGL(k_pflag_compact, dim3(nb), dim3(TPB), 0, stream, entry32, entry, n_entries, block_off, rec, idx,
-                       chunk_pre, chunk_mask);
-    if (n_off) {
-        const uint32_t blocks = (uint32_t)std::min<size_t>((n_off + TPB - 1) / TPB, 256 * 32);
-        hipLaunchKernelGGL(k_pflag_groups, dim3(blocks), dim3(TPB), 0, stream, blk_off, n_off, chunk_pre, chunk_mask, grp);
-    }
+    const FlagScratch fs(scratch, n_entries);
+    hipLaunchKernelGGL(k_pflag_count, dim3(fs.nb), dim3(TPB), 0, stream, entry32, n_entries, fs.block_sum);
+    hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, fs.block_sum, fs.nb, fs.block_off,
+                       fs.chunk_pre + 64 * (size_t)fs.nb, static_cast<Scalars *>(nullptr));
+    hipLaunchKernelGGL(k_pflag_compact, dim3(fs.nb), dim3(TPB), 0, stream, entry32, entry, n_entries, fs.block_off, rec, idx,
+                       fs.chunk_pre, fs.chunk_mask);
+    flag_groups(fs, blk_off, n_off, grp, stream);
     return hipGetLastError();
 }
 

@@ -83,6 +83,21 @@ struct DevicePacked {
     // (completed counts + flush chain); created on first use
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_offsets = nullptr, ev_flush = nullptr;
+    // The flagged entries' lists (see pack_flag_lists) in the caller's buffers. Where the packing's own records pass
+    // has the flags in registers (counting route, count tile allowed, no staged masks) it builds the lists itself,
+    // behind the publishing kernel of its last read-back and in front of the host's wait for it, and says so in
+    // flag_lists_built; everywhere else the
+    // caller builds them with pack_flag_lists. The caller sizes the buffers for the RAW pileup's entries and the
+    // worst-case number of group offsets before the call (growing one in mid-pipeline would synchronise):
+    // scratch flag_list_scratch_bytes(n_entries), rec 16 and idx 4 bytes per entry, grp 4 bytes per offset of
+    // ceil(num_cells / 64) blocks. scratch == nullptr: the packing leaves the lists to the caller.
+    struct FlagListBuffers {
+        void *scratch = nullptr;
+        uint32_t *grp = nullptr;
+        uint4 *rec = nullptr;
+        uint32_t *idx = nullptr;
+    } flag_lists;
+    bool flag_lists_built = false;  // ... of the packing that has just returned
     // pinned host words the packing's scalar read-backs arrive in (polled; see read_scalars)
     void *mailbox = nullptr;
     unsigned long long mailbox_seq = 0;
@@ -106,7 +121,9 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells,
 // is (cell block, locus) order -- for the correction of the sparse-loci pair kernel: grp[n_off] = flagged entries
 // before each group offset blk_off[] (the last one is the end of the entries: grp[n_off - 1] is their number),
 // rec[] / idx[] = the flagged entries' records and indices (room for n_entries each). scratch:
-// flag_list_scratch_bytes(n_entries). Four kernels on `stream`, nothing read back.
+// flag_list_scratch_bytes(n_entries). Four kernels on `stream`, nothing read back. (For the packings that did not
+// build the lists themselves, DevicePacked::flag_lists_built: host packing, the radix route, staged masks decided
+// otherwise.)
 size_t flag_list_scratch_bytes(uint32_t n_entries);
 hipError_t pack_flag_lists(const uint32_t *entry32, const uint4 *entry, uint32_t n_entries, const uint32_t *blk_off,
                            size_t n_off, void *scratch, uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream);

@@ -97,6 +97,7 @@ int adopt_host_packing(secedo::PackedPileup &from, secedo::DevicePacked *pk) {
     pk->multi_entries = from.multi_entries;
     pk->max_read_entries = from.max_read_entries;
     pk->n_wide = from.n_wide;
+    pk->flag_lists_built = false;
     pk->stage_masks = from.stage_masks;
     pk->count_tile = from.count_tile;
     pk->cap_entries = from.cap_entries;
@@ -117,6 +118,26 @@ struct PrepareArgs {
 // Packs on the device (after the upload of a pileup that came as host pointers); *need_host: the host has to
 int pack_on_device(secedo_simmat *h, const PrepareArgs &p, hipStream_t s, bool *need_host) {
     if (h->have_host) SECEDO_TRY(upload_flat_pileup(h->view, h->raw, &h->dview));  // raw pileup to HBM
+    // the flagged entries' lists are built inside the packing where its records pass knows the flags: their buffers,
+    // sized for what the packing can keep at most (an ensure in mid-pipeline would synchronise). Whether the lists
+    // are wanted is known at read-back 2 only, so a pileup that ends on the masks kernel holds them for nothing: 20
+    // bytes per raw entry and the scratch, 0.5 GB on C3 clustered beside its 8 GB of matrix -- released again in
+    // build_flag_lists where the packed pileup stages masks, and not sized again while the handle's previous pileup
+    // did (the first sparse pileup after a clustered one gets its lists from pack_flag_lists)
+    h->pk.flag_lists = secedo::DevicePacked::FlagListBuffers();
+    const bool was_clustered = h->pk.stage_masks && h->pk.num_entries;
+    if (p.allow_count_tile && !was_clustered && h->dview.n_entries && h->dview.n_entries < (1ull << 31)) {
+        const uint32_t ne = (uint32_t)h->dview.n_entries;
+        const size_t n_off_max = (size_t)((p.num_cells + 63) / 64) * ((size_t)h->dview.n_loci + 1);
+        SECEDO_TRY(h->flag_tmp.ensure(secedo::flag_list_scratch_bytes(ne)));
+        SECEDO_TRY(h->flag_rec.ensure((size_t)ne * 16));
+        SECEDO_TRY(h->flag_idx.ensure((size_t)ne * 4));
+        SECEDO_TRY(h->flag_grp.ensure(std::max<size_t>(n_off_max, 1) * 4));
+        h->pk.flag_lists.scratch = h->flag_tmp.p;
+        h->pk.flag_lists.grp = h->flag_grp.as<uint32_t>();
+        h->pk.flag_lists.rec = h->flag_rec.as<uint4>();
+        h->pk.flag_lists.idx = h->flag_idx.as<uint32_t>();
+    }
     const std::string err = secedo::pack_pileup_device(h->dview, p.num_cells, p.max_fragment_length, p.num_threads,
                                                        p.block_cells, &secedo::stage_geometry, p.allow_count_tile, s,
                                                        &h->pk, need_host);
@@ -173,7 +194,17 @@ int build_tile_table(secedo_simmat *h) {
 // pair kernel's epilogue and correct_tiles read them
 int build_flag_lists(secedo_simmat *h, hipStream_t s) {
     const secedo::DevicePacked &pk = h->pk;
-    if (!(pk.count_tile && !pk.stage_masks && pk.num_entries)) return SECEDO_OK;
+    if (!(pk.count_tile && !pk.stage_masks && pk.num_entries)) {
+        if (pk.stage_masks) {  // clustered loci: no lists, and the next packing of this handle will hardly want them
+            for (secedo_simmat::DevBuf *b : {&h->flag_tmp, &h->flag_rec, &h->flag_idx, &h->flag_grp}) b->release();
+            h->pk.flag_lists = secedo::DevicePacked::FlagListBuffers();
+        }
+        return SECEDO_OK;
+    }
+    if (h->used_device_packing && pk.flag_lists_built) {  // the packing's records pass made them
+        h->flags_ready = true;
+        return SECEDO_OK;
+    }
     const uint32_t ne = (uint32_t)pk.num_entries;
     const size_t n_off = (size_t)pk.num_blocks * (pk.num_loci + 1);
     SECEDO_TRY(h->flag_tmp.ensure(secedo::flag_list_scratch_bytes(ne)));
