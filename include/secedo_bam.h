@@ -150,7 +150,44 @@ typedef struct secedo_bam_index_info {
 #define SECEDO_BAM_INDEX_AUTO 1    /* a BAM with a usable .bai is read through it, any other in full */
 #define SECEDO_BAM_INDEX_REQUIRE 2 /* a BAM without a usable .bai is SECEDO_E_INVALID_ARG */
 
+/* What the last pileup or barcode call on this thread selected by rules 3c and 3d of secedo_amd/csrc/bam_kernels.hip,
+ * summed over its chromosomes. All zero when the read filter and the duplicate removal were off: no pass ran. */
+typedef struct secedo_bam_select_info {
+    uint64_t records;             /* records that reached the flag filter (tag mode: those of listed barcodes;
+                                     secedo_bam_barcodes: those with a Z-typed value); 0 with the filter off */
+    uint64_t dropped_require;     /* dropped by (flag & require) != require; tested first, a record is counted once */
+    uint64_t dropped_exclude;     /* dropped by (flag & exclude) != 0 */
+    uint64_t templates;           /* templates (records of one cell with one name) formed by the duplicate removal */
+    uint64_t large_templates;     /* of those, the ones of three or more records: never duplicates */
+    uint64_t duplicate_templates; /* templates dropped as duplicates */
+    uint64_t duplicate_records;   /* their records */
+    uint64_t reserved;
+} secedo_bam_select_info;
+
+#define SECEDO_BAM_DUPLICATES_KEEP 0   /* the default */
+#define SECEDO_BAM_DUPLICATES_REMOVE 1 /* per cell and chromosome, keep the best template of each 5'-end key */
+
 const char *secedo_bam_last_error(void);
+
+/* Record selection by SAM flag, per process, read at every pileup and barcode call (secedo_bam_index_build and the
+ * scans ignore it): a record is used iff (flag & require) == require && (flag & exclude) == 0. A dropped record takes
+ * no read id, writes no .map line, passes none of the device checks (so a record that is not a proper pair is no
+ * error once it is excluded) and gives no base: the outputs equal those of the same call with the filter off on the
+ * files without the dropped records. The host's structural checks still cover every record. Masks above 0xFFFF or
+ * sharing a bit are SECEDO_E_INVALID_ARG. Until it is set, the environment variables SECEDO_BAM_REQUIRE_FLAGS and
+ * SECEDO_BAM_EXCLUDE_FLAGS (decimal or 0x hex; unset or empty: 0) decide. The default 0, 0 runs no pass. */
+int secedo_bam_set_read_filter(uint32_t require, uint32_t exclude);
+int secedo_bam_get_read_filter(uint32_t *require, uint32_t *exclude);
+
+/* Duplicate removal among the records the filter kept, per process, read at every pileup call (secedo_bam_barcodes
+ * ignores it): SECEDO_BAM_DUPLICATES_KEEP or _REMOVE; until it is set, SECEDO_BAM_DUPLICATES (keep or remove; unset or
+ * empty: keep) decides. Per chromosome and cell (file, or barcode in tag mode), the records of one read name form a
+ * template; singles with the same unclipped 5' end and strand, and pairs with the same two, are duplicates of each
+ * other, and all but the one with the highest sum of base qualities >= 15 (ties: the earliest in the global order) are
+ * dropped like filtered records. Templates of three or more records are left alone. Bit-identical between runs. */
+int secedo_bam_set_duplicates(int mode);
+int secedo_bam_get_duplicates(int *mode);
+int secedo_bam_select_stats(secedo_bam_select_info *out);
 
 /* Whether BAM files are read through their .bai index, per process, read at every call. Until it is set, the
  * environment variable SECEDO_BAM_INDEX (off, auto or require; unset or empty: off) decides; any other value of it

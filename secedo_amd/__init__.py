@@ -14,5 +14,6 @@ from .em import expectation_maximization  # noqa: F401,E402
 from .cluster import divide_cluster, divide_cluster_resident, spectral_clustering  # noqa: F401,E402
 from .variant import reference_genotypes, variant_calling, variant_calling_resident, variant_calls  # noqa: F401,E402
 from .bam_pileup import (bam_barcodes, bam_index_build, bam_index_ranges, bam_index_stats, bam_route_stats,  # noqa: F401,E402
-                         bam_scan, bgzf_inflate, pileup_bams, pileup_bams_resident, set_index)
+                         bam_scan, bam_select_stats, bgzf_inflate, pileup_bams, pileup_bams_resident, set_index)
+from .sam_flags import FLAG_NAMES, parse_flags  # noqa: F401,E402
 from .pileup_load import read_pileups_resident  # noqa: F401,E402

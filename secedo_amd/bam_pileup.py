@@ -26,6 +26,7 @@ import numpy as np
 
 from . import _lib
 from .pileup import FlatPileup
+from .sam_flags import parse_filter
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libsecedo_bam.so")
@@ -66,6 +67,11 @@ class BuildInfo(C.Structure):
                                           "joined_runs", "reserved")]
 
 
+class SelectInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "dropped_require", "dropped_exclude", "templates",
+                                          "large_templates", "duplicate_templates", "duplicate_records", "reserved")]
+
+
 INFLATE_MODES = {"host": 0, "device": 1}
 INDEX_MODES = {"off": 0, "auto": 1, "require": 2}
 
@@ -97,6 +103,11 @@ SIGNATURES = {
     "secedo_bam_set_index": (C.c_int, [C.c_int]),
     "secedo_bam_get_index": (C.c_int, [C.POINTER(C.c_int)]),
     "secedo_bam_index_stats": (C.c_int, [C.POINTER(IndexInfo)]),
+    "secedo_bam_set_read_filter": (C.c_int, [_u32, _u32]),
+    "secedo_bam_get_read_filter": (C.c_int, [C.POINTER(_u32), C.POINTER(_u32)]),
+    "secedo_bam_set_duplicates": (C.c_int, [C.c_int]),
+    "secedo_bam_get_duplicates": (C.c_int, [C.POINTER(C.c_int)]),
+    "secedo_bam_select_stats": (C.c_int, [C.POINTER(SelectInfo)]),
     "secedo_bam_index_ranges": (C.c_int, [C.c_char_p, C.POINTER(_u32), _vp, _vp, _vp, _u32]),
     "secedo_bam_scan_device": (C.c_int, [C.c_char_p, _u32, C.POINTER(ScanInfo), _vp, _u32]),
     "secedo_bam_index_build": (C.c_int, [_files_t, _u32, _files_t, C.c_int, _u32, C.POINTER(BuildInfo)]),
@@ -197,6 +208,51 @@ class _route:
         return False
 
 
+class _select:
+    """The record selection of the calls inside the block: ``require_flags`` / ``exclude_flags`` (an int, or a string:
+    decimal, 0x hex or samtools' names, see sam_flags.py) and ``remove_duplicates`` (bool). None keeps the process
+    setting of each (secedo_bam_set_read_filter / secedo_bam_set_duplicates, else the environment); giving one of the
+    two masks sets both, the other to 0. The settings are per process; the block restores what it found."""
+
+    def __init__(self, require_flags=None, exclude_flags=None, remove_duplicates=None):
+        self.filter = None
+        if require_flags is not None or exclude_flags is not None:
+            try:
+                self.filter = parse_filter(require_flags, exclude_flags)
+            except ValueError as e:
+                raise _lib.SecedoError(_lib.E_INVALID_ARG, str(e))
+        self.dup = None if remove_duplicates is None else int(bool(remove_duplicates))
+
+    def __enter__(self):
+        if self.filter is not None:
+            rq, ex = _u32(0), _u32(0)
+            check(lib().secedo_bam_get_read_filter(C.byref(rq), C.byref(ex)))
+            self.filter_before = (rq.value, ex.value)
+            check(lib().secedo_bam_set_read_filter(*self.filter))
+        if self.dup is not None:
+            before = C.c_int(0)
+            check(lib().secedo_bam_get_duplicates(C.byref(before)))
+            self.dup_before = before.value
+            check(lib().secedo_bam_set_duplicates(self.dup))
+
+    def __exit__(self, *exc):
+        if self.dup is not None:
+            check(lib().secedo_bam_set_duplicates(self.dup_before))
+        if self.filter is not None:
+            check(lib().secedo_bam_set_read_filter(*self.filter_before))
+        return False
+
+
+def bam_select_stats() -> dict:
+    """What the last pileup or barcode call on this thread selected, summed over its chromosomes: records that reached
+    the flag filter, dropped_require, dropped_exclude (a record is counted once, ``require`` first), templates formed
+    by the duplicate removal, large_templates (three or more records, left alone), duplicate_templates and
+    duplicate_records dropped. All zero when neither option was on: no pass ran."""
+    info = SelectInfo()
+    check(lib().secedo_bam_select_stats(C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in SelectInfo._fields_ if k != "reserved"}
+
+
 def set_inflate(inflate: str) -> None:
     """Sets the process-wide BAM route: "host" or "device" (see ``pileup_bams``'s ``inflate``)."""
     if inflate not in INFLATE_MODES:
@@ -281,10 +337,11 @@ def bam_route_stats() -> dict:
 
 
 def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], num_threads: int = 1, *,
-                 inflate=None, index=None):
+                 inflate=None, index=None, require_flags=None, exclude_flags=None):
     """The distinct Z-typed values of ``tag`` over the records of the given chromosomes of ``files`` (BAM or SAM),
     sorted bytewise -> (values [str], counts np.uint64: records per value). Needs the GPU. ``inflate``: the BAM
-    route, and ``index``: the use of .bai indexes, both as in ``pileup_bams``."""
+    route, and ``index``: the use of .bai indexes, both as in ``pileup_bams``. ``require_flags`` / ``exclude_flags``:
+    only records that pass the flag filter are counted, as in ``pileup_bams``."""
     arr, n = _files(files)
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
     n_val, n_bytes = C.c_uint32(0), C.c_uint64(0)
@@ -293,7 +350,7 @@ def bam_barcodes(files: Sequence[str], tag: str, chromosome_ids: Sequence[int], 
         import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
     except ImportError:
         pass
-    with _route(inflate, index):
+    with _route(inflate, index), _select(require_flags, exclude_flags):
         check(lib().secedo_bam_barcodes(arr, n, t, _lib.ptr(ids) if len(ids) else None, len(ids), num_threads,
                                         C.byref(n_val), C.byref(n_bytes)))
     k = int(n_val.value)
@@ -359,7 +416,8 @@ def _fetch_host(info: ResultInfo) -> FlatPileup:
 def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_file: bool, chromosome_id: int,
                 max_coverage: int, min_base_quality: int, min_map_quality: int, min_alignment_score: int,
                 num_threads: int, min_different: int, times: Optional[dict] = None, *, cell_tag=None,
-                cells=None, inflate=None, index=None) -> FlatPileup:
+                cells=None, inflate=None, index=None, require_flags=None, exclude_flags=None,
+                remove_duplicates=None) -> FlatPileup:
     """The reference's pileup_bams() on BAM or SAM files -> a one-chromosome FlatPileup (id_base = cell << 2 |
     base). Writes <out_pileup>.bin/.map/.txt unless out_pileup is None. ``times`` (a dict) receives the step times in ms.
 
@@ -375,12 +433,20 @@ def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_
     the members that hold the chromosome's records, and any other BAM in full; "require" raises for a BAM without a
     usable index. For coordinate-sorted BAMs with a matching index the result is the same; an index that does not
     match its BAM raises. None keeps the process setting (``set_index``, SECEDO_BAM_INDEX). ``bam_index_stats()`` says
-    what the call did."""
+    what the call did.
+
+    ``require_flags`` / ``exclude_flags``: a record is used iff (flag & require) == require and (flag & exclude) == 0,
+    as samtools' -f / -F. Each is an int or a string (decimal, 0x hex, or a comma list of samtools' names such as
+    "SECONDARY,SUPPLEMENTARY,DUP,QCFAIL,UNMAP"). ``remove_duplicates``: among the records the filter kept, per cell, templates
+    (records of one read name) with the same unclipped 5' ends and strands are duplicates; the one with the highest
+    sum of base qualities >= 15 stays (ties: the earliest). Dropped records take no read id and pass no check, so the
+    result equals this call with the options off on the files without them. The defaults (None) keep the process
+    settings, which are off unless the environment sets them. ``bam_select_stats()`` says what the call dropped."""
     arr, n = _files(bam_files)
     tag, bcs, n_bcs = _cells(cell_tag, cells)
     info, t = ResultInfo(), Times()
     out = None if out_pileup is None else os.fsencode(str(out_pileup))
-    with _route(inflate, index):
+    with _route(inflate, index), _select(require_flags, exclude_flags, remove_duplicates):
         if tag is None:
             check(lib().secedo_pileup_bams(arr, n, out, int(bool(write_text_file)), chromosome_id, max_coverage,
                                            min_base_quality, min_map_quality, min_alignment_score, num_threads,
@@ -398,14 +464,16 @@ def pileup_bams(bam_files: Sequence[str], out_pileup: Optional[str], write_text_
 def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequence[int], max_coverage: int = 100,
                          min_base_quality: int = 30, min_map_quality: int = 30, min_alignment_score: int = 0,
                          num_threads: int = 8, min_different: int = 3, id_to_group=None, group_id_to_pos=None,
-                         times: Optional[dict] = None, *, cell_tag=None, cells=None, inflate=None, index=None):
+                         times: Optional[dict] = None, *, cell_tag=None, cells=None, inflate=None, index=None,
+                         require_flags=None, exclude_flags=None, remove_duplicates=None):
     """Several chromosomes in one pass over the BAM or SAM files, straight into HBM on ``plan``'s device.
 
     -> (res, num_cells, max_read_length): ``res`` is the resident pileup dict of SimilarityMatrixPlan.upload,
     which filter_resident, divide_cluster_resident and variant_calling_resident take; num_cells and
     max_read_length are what read_pileup would report on the written .bin files (maxima over chromosomes).
     ``cell_tag`` / ``cells``: multiplexed files, as in pileup_bams; id_to_group then maps barcode indices.
-    ``inflate``: the BAM route, and ``index``: the use of .bai indexes, both as in pileup_bams."""
+    ``inflate``: the BAM route, and ``index``: the use of .bai indexes, both as in pileup_bams; ``require_flags``,
+    ``exclude_flags`` and ``remove_duplicates`` likewise (duplicates are found per chromosome)."""
     import torch
 
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
@@ -414,7 +482,8 @@ def pileup_bams_resident(plan, bam_files: Sequence[str], chromosome_ids: Sequenc
     i2g = None if id_to_group is None else np.ascontiguousarray(id_to_group, dtype=np.uint16)
     info, t = ResultInfo(), Times()
     dev = "cuda:%d" % plan.device
-    with torch.cuda.device(plan.device), _route(inflate, index):
+    with torch.cuda.device(plan.device), _route(inflate, index), \
+            _select(require_flags, exclude_flags, remove_duplicates):
         i2g_p, n_i2g = (_lib.ptr(i2g), len(i2g)) if i2g is not None else (None, 0)
         if tag is None:
             check(lib().secedo_pileup_bams_device(arr, n, _lib.ptr(ids), len(ids), max_coverage, min_base_quality,

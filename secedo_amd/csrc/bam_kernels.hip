@@ -16,6 +16,26 @@
 //     cell, Position, input file, record), which is per-file mode on the per-cell split files; the name maps are
 //     per slot cell % 100. The host's structural checks (sortedness, CIGAR against SEQ, negative position) still
 //     cover every record of the chromosome. At most 16384 barcodes.
+//  3c. Flag filter (opt-in: secedo_bam_set_read_filter; not in the reference). After the structural walk and, in tag
+//     mode, after the barcode selection of 3b, a record is kept iff (flag & require) == require && (flag & exclude)
+//     == 0, both u16 masks, default 0 = off. require & exclude != 0 is SECEDO_E_INVALID_ARG: nothing could pass. The
+//     structural walk is unchanged: block-size chain, sortedness, negative position and the CIGAR checks still cover
+//     every record.
+//  3d. Duplicate removal (opt-in: secedo_bam_set_duplicates; not in the reference), over the records 3c kept, per cell
+//     and over the whole chromosome (not per chunk: mates in different chunks still pair).
+//     5' end of a record: e = (u, strand), strand = flag 0x10, u a signed 64-bit value: forward u = Position - (total
+//     length of the leading S and H ops), reverse u = Position + reflen - 1 + (total length of the trailing S and H
+//     ops), reflen = the sum of the M, D, N, = and X lengths, Position the 0-based BAM field.
+//     Template: the records of one cell (file index, or barcode index in tag mode: files 0 and 100 share a name map
+//     for ids but are different cells here) with the same read name, compared as exact bytes. One record: a single;
+//     two: a pair; three or more: never a duplicate, never makes another one a duplicate, counted in the stats.
+//     Key: (cell, e) of a single; (cell, e_lo, e_hi) of a pair, its ends ordered by (u, strand); a single's key never
+//     equals a pair's. Score: the sum over the template's records of the quality bytes >= 15 and != 0xFF.
+//     Among templates with equal keys the highest score is kept, on a tie the template that holds the record with the
+//     smallest global ordinal; all records of every other template are dropped.
+//     A record dropped by 3c or 3d is "not selected" in 3b's sense: no read id, no .map line, no check of rule 6 or
+//     any other decode error, no base; rule 7's last chunk is counted over the survivors. So the outputs equal those
+//     of the same call with the options off on the input without the dropped records, byte for byte.
 //  4. Base walk (:94-155) over BamTools' AlignedBases (BuildCharData): M/I/=/X copy the bases, D gives '-',
 //     N gives 'N', P gives '*', S/H give nothing. Only leading H/S ops are skipped; I advances `offset`; an I
 //     as the last op ends the read; the quality index is i + offset - del_offset (a leading soft clip is not
@@ -43,6 +63,19 @@
 // value -> order (byte offset, cell and input ordinal per global ordinal), which is the Records the chain below
 // takes. The barcode census (secedo_bam_barcodes) hashes every Z-typed value, sorts, and splits each run of equal
 // hashes by exact compare into distinct values with their record counts.
+//
+// Rules 3c and 3d are front passes too, from one Records to a compacted Records that the chain below takes unchanged;
+// with both off nothing is launched or allocated. 3c: in tag mode the flag test is part of `cells` (ANDed into its
+// selection in front of the compaction that mode already does); in per-file mode flag_test -> scan -> compact_records.
+// 3d: ends_and_scores (16 lanes per record: the quality and name bytes strided over the lanes and summed by shuffles,
+// the CIGAR words read by all lanes at one address) -> hipcub sort by hash(cell, name) with the ordinal -> templates
+// (run heads, then the first record of the run with the same cell and name bytes is the template's leader: a collision
+// splits the run exactly; the other records add their count, score and ordinal to the leader) -> the leaders of singles
+// and pairs compacted and sorted by hash(key) -> mark_duplicates (the first leader of the run with exactly the same
+// key heads the group, its best rank score << 32 | ~leader is an atomicMax; every template that is not its group's
+// best clears the keep flag of its records) -> scan -> compact_records. The atomics are integer sums and maxima,
+// whose results do not depend on their order, and every thread stops at its run's head unless hashes collide, so a
+// group of any length costs each of its members one compare. Device counters (Sel) feed secedo_bam_select_stats.
 //
 // Passes: decode (one thread per record) -> hipcub sort by (slot-name hash, ordinal) -> first_occurrence with
 // an exact byte compare inside each run of equal hashes -> exclusive scan of first-occurrence flags = ids.
@@ -484,6 +517,16 @@ __global__ void __launch_bounds__(kBlock) k_span(const uint32_t *minpos, const u
     atomicMax(max_len, maxpos[id] - minpos[id]);
 }
 
+__device__ __forceinline__ bool flag_require(uint32_t flag, uint32_t require) { return (flag & require) == require; }
+__device__ __forceinline__ bool flag_exclude(uint32_t flag, uint32_t exclude) { return (flag & exclude) == 0; }
+
+// Block-wide count of `yes` into *slot (one atomic per block; a sum of integers, so the order does not matter).
+// Every thread of the block calls it.
+__device__ __forceinline__ void block_count(bool yes, unsigned long long *slot) {
+    const int c = __syncthreads_count(yes ? 1 : 0);
+    if (threadIdx.x == 0 && c) atomicAdd(slot, (unsigned long long)c);
+}
+
 // --- tag mode (rule 3b): the cell of a record from its barcode tag, and the global order built on the device ---
 
 // a listed barcode's hash and index, to be sorted by hash
@@ -513,30 +556,54 @@ __device__ uint32_t find_cell(const CellList &L, const uint8_t *v, uint32_t len)
 }
 
 // one thread per uploaded record (input order): sel = 1 and key = chunk << 46 | cell << 32 | Position for a record
-// of a listed cell
+// of a listed cell that passes the flag filter of rule 3c (stat: null when the filter is off, else the counts of
+// k_flag_test over the records of listed cells)
 __global__ void __launch_bounds__(kBlock) k_cells(const uint8_t *bytes, const uint64_t *in_off, uint32_t n,
-                                                  CellList L, uint64_t *key, uint32_t *sel) {
+                                                  CellList L, uint32_t require, uint32_t exclude, uint64_t *key,
+                                                  uint32_t *sel, unsigned long long *stat) {
     const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
-    if (o >= n) return;
-    const Rec r = parse(bytes + in_off[o]);
-    uint32_t len = 0, cell = ~0u;
-    const uint8_t *v = tag_value(r, L.t0, L.t1, &len);
-    if (v) cell = find_cell(L, v, len);
-    const uint32_t pos = uint32_t(r.pos);  // >= 0: the host refuses negative positions
-    key[o] = cell == ~0u ? 0 : (uint64_t(pos / kChunk) << 46 | uint64_t(cell) << 32 | pos);
-    sel[o] = cell == ~0u ? 0 : 1;
+    bool listed = false, req = false, exc = false;
+    if (o < n) {
+        const Rec r = parse(bytes + in_off[o]);
+        uint32_t len = 0, cell = ~0u;
+        const uint8_t *v = tag_value(r, L.t0, L.t1, &len);
+        if (v) cell = find_cell(L, v, len);
+        listed = cell != ~0u;
+        req = listed && !flag_require(r.flag, require);
+        exc = listed && !req && !flag_exclude(r.flag, exclude);
+        const bool ok = listed && !req && !exc;
+        const uint32_t pos = uint32_t(r.pos);  // >= 0: the host refuses negative positions
+        key[o] = ok ? (uint64_t(pos / kChunk) << 46 | uint64_t(cell) << 32 | pos) : 0;
+        sel[o] = ok ? 1 : 0;
+    }
+    if (!stat) return;  // uniform over the grid
+    block_count(listed, stat + kSelRecords);
+    block_count(req, stat + kSelRequire);
+    block_count(exc, stat + kSelExclude);
 }
 
-// one thread per record with a Z-typed tag value: sel = 1, key = the value's hash
+// one thread per record with a Z-typed tag value that passes the flag filter of rule 3c: sel = 1, key = the value's
+// hash
 __global__ void __launch_bounds__(kBlock) k_tag_keys(const uint8_t *bytes, const uint64_t *in_off, uint32_t n,
-                                                     uint8_t t0, uint8_t t1, uint64_t *key, uint32_t *sel) {
+                                                     uint8_t t0, uint8_t t1, uint32_t require, uint32_t exclude,
+                                                     uint64_t *key, uint32_t *sel, unsigned long long *stat) {
     const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
-    if (o >= n) return;
-    const Rec r = parse(bytes + in_off[o]);
-    uint32_t len = 0;
-    const uint8_t *v = tag_value(r, t0, t1, &len);
-    key[o] = v ? value_hash(v, len) : 0;
-    sel[o] = v ? 1 : 0;
+    bool tagged = false, req = false, exc = false;
+    if (o < n) {
+        const Rec r = parse(bytes + in_off[o]);
+        uint32_t len = 0;
+        const uint8_t *v = tag_value(r, t0, t1, &len);
+        tagged = v != nullptr;
+        req = tagged && !flag_require(r.flag, require);
+        exc = tagged && !req && !flag_exclude(r.flag, exclude);
+        const bool ok = tagged && !req && !exc;
+        key[o] = ok ? value_hash(v, len) : 0;
+        sel[o] = ok ? 1 : 0;
+    }
+    if (!stat) return;  // uniform over the grid
+    block_count(tagged, stat + kSelRecords);
+    block_count(req, stat + kSelRequire);
+    block_count(exc, stat + kSelExclude);
 }
 
 // the selected (key, input ordinal) pairs, in input order
@@ -579,6 +646,233 @@ __global__ void __launch_bounds__(kBlock) k_tag_count(const uint8_t *bytes, cons
         }
     }
     atomicAdd(&cnt[first], 1u);
+}
+
+// --- rules 3c and 3d: the flag filter and the duplicate removal, front passes over the Records of the global order ---
+
+// rule 3c per record of the global order: keep[o], and stat[kSelRecords / kSelRequire / kSelExclude]
+__global__ void __launch_bounds__(kBlock) k_flag_test(Records rs, uint32_t require, uint32_t exclude, uint32_t *keep,
+                                                      unsigned long long *stat) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    const bool in = o < rs.n;
+    bool req = false, exc = false;
+    if (in) {
+        const uint32_t flag = ld16(rs.bytes + rs.off[o] + 4 + 14);
+        req = !flag_require(flag, require);
+        exc = !req && !flag_exclude(flag, exclude);
+        keep[o] = (req || exc) ? 0 : 1;
+    }
+    block_count(in, stat + kSelRecords);
+    block_count(req, stat + kSelRequire);
+    block_count(exc, stat + kSelExclude);
+}
+
+// the survivors of keep (scan = its exclusive sum) in the same order; ord_out = the ordinal each had before (through
+// ord when an earlier compaction or tag mode's sort already renumbered them)
+__global__ void __launch_bounds__(kBlock) k_compact_records(const uint64_t *off, const uint16_t *file,
+                                                            const uint32_t *ord, const uint32_t *keep,
+                                                            const uint32_t *scan, uint32_t n, uint64_t *off_out,
+                                                            uint16_t *file_out, uint32_t *ord_out) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o >= n || !keep[o]) return;
+    const uint32_t at = scan[o];
+    off_out[at] = off[o];
+    file_out[at] = file[o];
+    ord_out[at] = ord ? ord[o] : o;
+}
+
+constexpr uint32_t kSub = 16;                 // lanes per record in k_ends
+constexpr uint64_t kEndBias = 1ull << 62;     // u + kEndBias > 0: an end (u, strand) orders as (u + bias) << 1 | strand
+constexpr uint64_t kNoEnd = ~0ull;            // e_hi of a single: no pair has it
+constexpr uint64_t kNamePrime = 0x9E3779B97F4A7C15ull;
+
+__device__ __forceinline__ uint64_t mix64(uint64_t h) {
+    h ^= h >> 29;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 32;
+    h *= 0x94D049BB133111EBull;
+    return h ^ (h >> 29);
+}
+
+// Rule 3d per record, kSub lanes per record: the lanes stride over the quality bytes and the name bytes (coalesced
+// within the group) and are summed by shuffles; the CIGAR words are read by every lane at the same address.
+// -> end[o] = its 5' end, score[o] = its quality sum, key[o] = hash of (cell, name), val[o] = o.
+__global__ void __launch_bounds__(kBlock) k_ends(Records rs, uint64_t *key, uint32_t *val, uint64_t *end,
+                                                 uint32_t *score) {
+    const uint32_t o = uint32_t((uint64_t(blockIdx.x) * kBlock + threadIdx.x) / kSub), lane = threadIdx.x % kSub;
+    if (o >= rs.n) return;  // whole groups leave together: kBlock is a multiple of kSub
+    const Rec r = parse(rs.bytes + rs.off[o]);
+    uint32_t sum = 0;
+    for (uint32_t k = lane; k < r.l_seq; k += kSub) {
+        const uint32_t q = r.qual[k];
+        if (q >= 15 && q != 0xFF) sum += q;
+    }
+    uint32_t len = r.l_name;  // the name ends at its first NUL
+    for (uint32_t k = lane; k < r.l_name; k += kSub)
+        if (r.name[k] == 0) {
+            len = k;
+            break;
+        }
+    for (uint32_t d = kSub / 2; d; d >>= 1) {
+        sum += __shfl_xor(sum, d, kSub);
+        len = min(len, uint32_t(__shfl_xor(len, d, kSub)));
+    }
+    uint64_t h = 0, pw = 1;
+    for (uint32_t k = 0; k < lane; ++k) pw *= kNamePrime;
+    uint64_t step = 1;
+    for (uint32_t k = 0; k < kSub; ++k) step *= kNamePrime;
+    for (uint32_t k = lane; k < len; k += kSub) {
+        h += (uint64_t(r.name[k]) + 1) * pw;
+        pw *= step;
+    }
+    for (uint32_t d = kSub / 2; d; d >>= 1) h += __shfl_xor(h, d, kSub);
+    if (lane) return;
+    // leading and trailing S/H runs, and the reference length
+    uint64_t lead = 0, trail = 0, reflen = 0;
+    bool in_lead = true;
+    for (uint32_t c = 0; c < r.n_cigar; ++c) {
+        const uint32_t t = op_type(r, c), l = op_len(r, c);
+        if (t == kOpS || t == kOpH) {
+            if (in_lead) lead += l;
+            else trail += l;
+        } else {
+            in_lead = false;
+            trail = 0;
+            if (t == kOpM || t == kOpD || t == kOpN || t == kOpEq || t == kOpX) reflen += l;
+        }
+    }
+    const bool rev = (r.flag & 0x10) != 0;
+    const int64_t u = rev ? int64_t(r.pos) + int64_t(reflen) - 1 + int64_t(trail) : int64_t(r.pos) - int64_t(lead);
+    end[o] = (uint64_t(u) + kEndBias) << 1 | (rev ? 1 : 0);
+    score[o] = sum;
+    key[o] = mix64(h ^ mix64(uint64_t(rs.file[o]) << 32 | len));
+    val[o] = o;
+}
+
+// same cell and same name bytes
+__device__ bool same_template(const Records &rs, uint32_t a, uint32_t b) {
+    if (rs.file[a] != rs.file[b]) return false;
+    const Rec x = parse(rs.bytes + rs.off[a]), y = parse(rs.bytes + rs.off[b]);
+    for (uint32_t k = 0;; ++k) {
+        const uint8_t cx = k < x.l_name ? x.name[k] : 0, cy = k < y.l_name ? y.name[k] : 0;
+        if (cx != cy) return false;
+        if (cx == 0) return true;
+    }
+}
+
+// Template assembly over the hash-sorted (key, ordinal) pairs: rep[o] = the lowest ordinal of o's template (the first
+// record of the run of equal hashes that compares equal; without a collision that is the run's head). The other
+// records add themselves to their leader: extra[rep] counts them, tscore[rep] sums the scores, mate[rep] = max of
+// their ordinals (the one mate of a pair). Integer sums and maxima: any order of the atomics gives the same values.
+__global__ void __launch_bounds__(kBlock) k_tmpl_rep(Records rs, const uint32_t *val, const uint32_t *run,
+                                                     const uint32_t *score, uint32_t *rep, uint32_t *extra,
+                                                     uint32_t *tscore, uint32_t *mate) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= rs.n) return;
+    const uint32_t o = val[j];
+    uint32_t first = o;
+    for (uint32_t q = run[j]; q < j; ++q)  // equal keys are in ordinal order (stable sort)
+        if (same_template(rs, val[q], o)) {
+            first = val[q];
+            break;
+        }
+    rep[o] = first;
+    atomicAdd(&tscore[first], score[o]);
+    if (first != o) {
+        atomicAdd(&extra[first], 1u);
+        atomicMax(&mate[first], o);
+    }
+}
+
+struct DupKey {
+    uint64_t lo, hi;  // the ends in order; hi = kNoEnd for a single
+};
+
+__device__ __forceinline__ DupKey dup_key(const uint64_t *end, const uint32_t *extra, const uint32_t *mate,
+                                          uint32_t o) {
+    DupKey k{end[o], kNoEnd};
+    if (extra[o] == 1) {
+        const uint64_t e2 = end[mate[o]];
+        k.hi = max(k.lo, e2);
+        k.lo = min(k.lo, e2);
+    }
+    return k;
+}
+
+// per record: sel[o] = 1 for the leader of a single or a pair, gkey[o] = hash of its key (cell, e_lo, e_hi);
+// stat[kSelTemplates / kSelLarge]
+__global__ void __launch_bounds__(kBlock) k_tmpl_key(Records rs, const uint32_t *rep, const uint32_t *extra,
+                                                     const uint32_t *mate, const uint64_t *end, uint64_t *gkey,
+                                                     uint32_t *sel, unsigned long long *stat) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    const bool leader = o < rs.n && rep[o] == o;
+    const bool large = leader && extra[o] >= 2;
+    if (o < rs.n) {
+        const bool ok = leader && !large;
+        uint64_t h = 0;
+        if (ok) {
+            const DupKey k = dup_key(end, extra, mate, o);
+            h = mix64(mix64(k.lo ^ uint64_t(rs.file[o]) << 48) + mix64(k.hi) * kNamePrime);
+        }
+        gkey[o] = h;
+        sel[o] = ok ? 1 : 0;
+    }
+    block_count(leader, stat + kSelTemplates);
+    block_count(large, stat + kSelLarge);
+}
+
+// what a template competes with inside its key: the higher score wins, then the lower leading ordinal
+__device__ __forceinline__ unsigned long long dup_rank(const uint32_t *tscore, uint32_t o) {
+    return (unsigned long long)tscore[o] << 32 | (~o & 0xFFFFFFFFu);
+}
+
+// Grouping over the hash-sorted (gkey, leader ordinal) pairs: grp[o] = the lowest leader of the run of equal hashes
+// with exactly o's key, and best[grp] = max of the ranks of that key's templates (atomicMax on exact integers: the
+// maximum is the same in any order). A run may be of any length; without a collision every thread stops at its head.
+__global__ void __launch_bounds__(kBlock) k_group(Records rs, const uint32_t *val, const uint32_t *run, uint32_t m,
+                                                  const uint32_t *extra, const uint32_t *mate, const uint64_t *end,
+                                                  const uint32_t *tscore, uint32_t *grp, unsigned long long *best) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t o = val[j];
+    const DupKey k = dup_key(end, extra, mate, o);
+    uint32_t g = o;
+    for (uint32_t q = run[j]; q < j; ++q) {
+        const uint32_t p = val[q];
+        if (rs.file[p] != rs.file[o]) continue;
+        const DupKey kp = dup_key(end, extra, mate, p);
+        if (kp.lo == k.lo && kp.hi == k.hi) {
+            g = p;
+            break;
+        }
+    }
+    grp[o] = g;
+    atomicMax(&best[g], dup_rank(tscore, o));
+}
+
+// every template but its key's best is a duplicate: keep = 0 for its records (keep is 1 everywhere on entry);
+// stat[kSelDupTemplates / kSelDupRecords]
+__global__ void __launch_bounds__(kBlock) k_dup_mark(const uint32_t *val, uint32_t m, const uint32_t *grp,
+                                                     const unsigned long long *best, const uint32_t *extra,
+                                                     const uint32_t *mate, const uint32_t *tscore, uint32_t *keep,
+                                                     unsigned long long *stat) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    bool dup = false, pair = false;
+    if (j < m) {
+        const uint32_t o = val[j];
+        dup = best[grp[o]] != dup_rank(tscore, o);
+        pair = dup && extra[o] == 1;
+        if (dup) keep[o] = 0;
+        if (pair) keep[mate[o]] = 0;
+    }
+    block_count(dup, stat + kSelDupTemplates);
+    block_count(dup, stat + kSelDupRecords);
+    block_count(pair, stat + kSelDupRecords);
+}
+
+__global__ void __launch_bounds__(kBlock) k_fill(uint32_t *p, uint32_t v, uint32_t n) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) p[i] = v;
 }
 
 inline uint32_t grid(uint64_t n) { return uint32_t((n + kBlock - 1) / kBlock); }
@@ -680,17 +974,18 @@ hipError_t list_hash(const uint8_t *d_bytes, const uint32_t *d_off, uint32_t n, 
     return hipGetLastError();
 }
 
-hipError_t cells(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const CellList &L, uint64_t *d_key,
-                 uint32_t *d_sel, hipStream_t s) {
+hipError_t cells(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const CellList &L, uint32_t require,
+                 uint32_t exclude, uint64_t *d_key, uint32_t *d_sel, unsigned long long *d_stat, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    k_cells<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, n, L, d_key, d_sel);
+    k_cells<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, n, L, require, exclude, d_key, d_sel, d_stat);
     return hipGetLastError();
 }
 
 hipError_t tag_keys(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, uint8_t t0, uint8_t t1,
-                    uint64_t *d_key, uint32_t *d_sel, hipStream_t s) {
+                    uint32_t require, uint32_t exclude, uint64_t *d_key, uint32_t *d_sel, unsigned long long *d_stat,
+                    hipStream_t s) {
     if (n == 0) return hipSuccess;
-    k_tag_keys<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, n, t0, t1, d_key, d_sel);
+    k_tag_keys<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, n, t0, t1, require, exclude, d_key, d_sel, d_stat);
     return hipGetLastError();
 }
 
@@ -718,6 +1013,65 @@ hipError_t tag_count(const uint8_t *d_bytes, const uint64_t *d_in_off, uint8_t t
     e = hipcub::DeviceScan::InclusiveScan(tmp, tmp_bytes, d_run, d_run, MaxOp(), n, s);
     if (e != hipSuccess) return e;
     k_tag_count<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, t0, t1, d_val_sorted, d_run, n, d_cnt);
+    return hipGetLastError();
+}
+
+hipError_t flag_test(const Records &r, uint32_t require, uint32_t exclude, uint32_t *d_keep,
+                     unsigned long long *d_stat, hipStream_t s) {
+    if (r.n == 0) return hipSuccess;
+    k_flag_test<<<grid(r.n), kBlock, 0, s>>>(r, require, exclude, d_keep, d_stat);
+    return hipGetLastError();
+}
+
+hipError_t compact_records(const Records &r, const uint32_t *d_ord, const uint32_t *d_keep, const uint32_t *d_scan,
+                           uint64_t *d_off_out, uint16_t *d_file_out, uint32_t *d_ord_out, hipStream_t s) {
+    if (r.n == 0) return hipSuccess;
+    k_compact_records<<<grid(r.n), kBlock, 0, s>>>(r.off, r.file, d_ord, d_keep, d_scan, r.n, d_off_out, d_file_out,
+                                                   d_ord_out);
+    return hipGetLastError();
+}
+
+hipError_t ends_and_scores(const Records &r, uint64_t *d_key, uint32_t *d_val, uint64_t *d_end, uint32_t *d_score,
+                           hipStream_t s) {
+    if (r.n == 0) return hipSuccess;
+    k_ends<<<grid(uint64_t(r.n) * kSub), kBlock, 0, s>>>(r, d_key, d_val, d_end, d_score);
+    return hipGetLastError();
+}
+
+hipError_t templates(const Records &r, const uint64_t *d_key_sorted, const uint32_t *d_val_sorted,
+                     const uint32_t *d_score, const uint64_t *d_end, uint32_t *d_run, uint32_t *d_rep,
+                     uint32_t *d_extra, uint32_t *d_tscore, uint32_t *d_mate, uint64_t *d_gkey, uint32_t *d_sel,
+                     unsigned long long *d_stat, void *tmp, size_t tmp_bytes, hipStream_t s) {
+    if (r.n == 0) return hipSuccess;
+    k_run_head<<<grid(r.n), kBlock, 0, s>>>(d_key_sorted, d_run, r.n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = hipcub::DeviceScan::InclusiveScan(tmp, tmp_bytes, d_run, d_run, MaxOp(), r.n, s);
+    if (e != hipSuccess) return e;
+    k_tmpl_rep<<<grid(r.n), kBlock, 0, s>>>(r, d_val_sorted, d_run, d_score, d_rep, d_extra, d_tscore, d_mate);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_tmpl_key<<<grid(r.n), kBlock, 0, s>>>(r, d_rep, d_extra, d_mate, d_end, d_gkey, d_sel, d_stat);
+    return hipGetLastError();
+}
+
+hipError_t mark_duplicates(const Records &r, const uint64_t *d_gkey_sorted, const uint32_t *d_val_sorted, uint32_t m,
+                           const uint32_t *d_extra, const uint32_t *d_mate, const uint64_t *d_end,
+                           const uint32_t *d_tscore, uint32_t *d_run, uint32_t *d_grp, unsigned long long *d_best,
+                           uint32_t *d_keep, unsigned long long *d_stat, void *tmp, size_t tmp_bytes, hipStream_t s) {
+    if (r.n == 0) return hipSuccess;
+    k_fill<<<grid(r.n), kBlock, 0, s>>>(d_keep, 1u, r.n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || m == 0) return e;
+    k_run_head<<<grid(m), kBlock, 0, s>>>(d_gkey_sorted, d_run, m);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = hipcub::DeviceScan::InclusiveScan(tmp, tmp_bytes, d_run, d_run, MaxOp(), m, s);
+    if (e != hipSuccess) return e;
+    k_group<<<grid(m), kBlock, 0, s>>>(r, d_val_sorted, d_run, m, d_extra, d_mate, d_end, d_tscore, d_grp, d_best);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_dup_mark<<<grid(m), kBlock, 0, s>>>(d_val_sorted, m, d_grp, d_best, d_extra, d_mate, d_tscore, d_keep, d_stat);
     return hipGetLastError();
 }
 

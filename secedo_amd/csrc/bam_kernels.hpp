@@ -57,12 +57,16 @@ struct CellList {
 // hash[c], idx[c] = c of each listed value (to be sorted by hash into CellList)
 hipError_t list_hash(const uint8_t *d_bytes, const uint32_t *d_off, uint32_t n, uint64_t *d_hash, uint32_t *d_idx,
                      hipStream_t s);
-// cells: per uploaded record (input order) d_sel = 1 for a listed barcode, d_key = chunk << 46 | cell << 32 | Position
-hipError_t cells(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const CellList &L, uint64_t *d_key,
-                 uint32_t *d_sel, hipStream_t s);
-// tag_keys: d_sel = 1 for a Z-typed value of tag t0 t1, d_key = its hash
+// cells: per uploaded record (input order) d_sel = 1 for a listed barcode whose flag passes rule 3c (require,
+// exclude; 0, 0 = off), d_key = chunk << 46 | cell << 32 | Position. d_stat: null, or Sel counters (zeroed by the
+// caller) that take kSelRecords (records of listed barcodes), kSelRequire and kSelExclude.
+hipError_t cells(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const CellList &L, uint32_t require,
+                 uint32_t exclude, uint64_t *d_key, uint32_t *d_sel, unsigned long long *d_stat, hipStream_t s);
+// tag_keys: d_sel = 1 for a Z-typed value of tag t0 t1 on a record that passes rule 3c, d_key = its hash; d_stat as
+// for cells, over the records with a Z-typed value
 hipError_t tag_keys(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, uint8_t t0, uint8_t t1,
-                    uint64_t *d_key, uint32_t *d_sel, hipStream_t s);
+                    uint32_t require, uint32_t exclude, uint64_t *d_key, uint32_t *d_sel, unsigned long long *d_stat,
+                    hipStream_t s);
 // selected (key, input ordinal) pairs at d_scan (exclusive sum of d_sel)
 hipError_t compact_keys(const uint64_t *d_key, const uint32_t *d_sel, const uint32_t *d_scan, uint32_t n,
                         uint64_t *d_key_out, uint32_t *d_val_out, hipStream_t s);
@@ -74,6 +78,37 @@ hipError_t order_records(const uint64_t *d_key_sorted, const uint32_t *d_val_sor
 hipError_t tag_count(const uint8_t *d_bytes, const uint64_t *d_in_off, uint8_t t0, uint8_t t1,
                      const uint64_t *d_key_sorted, const uint32_t *d_val_sorted, uint32_t *d_run, uint32_t n,
                      uint32_t *d_cnt, void *tmp, size_t tmp_bytes, hipStream_t s);
+
+// --- rules 3c and 3d: front passes from one Records to a compacted Records ---
+
+// slots of the device counters behind secedo_bam_select_info
+enum Sel : uint32_t {
+    kSelRecords = 0, kSelRequire, kSelExclude, kSelTemplates, kSelLarge, kSelDupTemplates, kSelDupRecords, kSelSlots
+};
+
+// rule 3c: d_keep[o] = 1 iff (flag & require) == require && (flag & exclude) == 0; counts into d_stat
+hipError_t flag_test(const Records &r, uint32_t require, uint32_t exclude, uint32_t *d_keep,
+                     unsigned long long *d_stat, hipStream_t s);
+// the records with d_keep at d_scan (its exclusive sum), order kept; d_ord_out = d_ord[o], or o where d_ord is null
+hipError_t compact_records(const Records &r, const uint32_t *d_ord, const uint32_t *d_keep, const uint32_t *d_scan,
+                           uint64_t *d_off_out, uint16_t *d_file_out, uint32_t *d_ord_out, hipStream_t s);
+// rule 3d per record: d_end = (u + 2^62) << 1 | strand of its 5' end, d_score = its quality sum, d_key = hash of
+// (cell, name), d_val = ordinal; to be sorted by key
+hipError_t ends_and_scores(const Records &r, uint64_t *d_key, uint32_t *d_val, uint64_t *d_end, uint32_t *d_score,
+                           hipStream_t s);
+// templates from the sorted pairs: d_rep[o] = lowest ordinal of o's template; per leader d_extra (records besides
+// it), d_tscore (summed score), d_mate (a pair's other record), all three zeroed by the caller; d_sel[o] = 1 for the
+// leader of a single or a pair and d_gkey[o] = hash of its key. d_run: workspace [n]; tmp: scan_bytes(n)
+hipError_t templates(const Records &r, const uint64_t *d_key_sorted, const uint32_t *d_val_sorted,
+                     const uint32_t *d_score, const uint64_t *d_end, uint32_t *d_run, uint32_t *d_rep,
+                     uint32_t *d_extra, uint32_t *d_tscore, uint32_t *d_mate, uint64_t *d_gkey, uint32_t *d_sel,
+                     unsigned long long *d_stat, void *tmp, size_t tmp_bytes, hipStream_t s);
+// the m selected leaders sorted by gkey (value = leader ordinal): d_keep[o] = 0 for every record of a template that
+// is not the best of its exact key, 1 elsewhere. d_best [n] zeroed by the caller; d_run, d_grp: workspace [n]
+hipError_t mark_duplicates(const Records &r, const uint64_t *d_gkey_sorted, const uint32_t *d_val_sorted, uint32_t m,
+                           const uint32_t *d_extra, const uint32_t *d_mate, const uint64_t *d_end,
+                           const uint32_t *d_tscore, uint32_t *d_run, uint32_t *d_grp, unsigned long long *d_best,
+                           uint32_t *d_keep, unsigned long long *d_stat, void *tmp, size_t tmp_bytes, hipStream_t s);
 
 // decode: per record the read filter, the name key, the walk's error checks and the end of its touched span.
 // d_err: u64 min of (ordinal << 8 | code), initialised to ~0 by the caller.

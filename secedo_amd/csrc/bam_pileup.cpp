@@ -8,7 +8,9 @@
 #include "bam_kernels.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
+#include <cstdlib>
 #include <cstdio>
 #include <map>
 #include <set>
@@ -58,6 +60,99 @@ struct Result {
 };
 
 thread_local Result *g_result = nullptr;
+
+// Rules 3c and 3d (bam_kernels.hip): the process-wide settings, read at every call, and what the last call did.
+std::atomic<int64_t> g_read_filter{-1};  // require << 16 | exclude; -1: not set, the environment decides
+std::atomic<int> g_duplicates{-1};       // -1: not set by secedo_bam_set_duplicates, the environment decides
+thread_local secedo_bam_select_info g_select{};
+
+struct Select {
+    uint32_t require = 0, exclude = 0;
+    bool dedup = false;
+    bool filter() const { return (require | exclude) != 0; }
+};
+
+int check_read_filter(const std::string &who, uint64_t require, uint64_t exclude) {
+    if (require > 0xFFFF || exclude > 0xFFFF)
+        return fail(SECEDO_E_INVALID_ARG, who + ": a SAM flag mask is at most 0xFFFF");
+    if (require & exclude)
+        return fail(SECEDO_E_INVALID_ARG, who + ": require " + std::to_string(require) + " and exclude " +
+                                              std::to_string(exclude) + " share a bit, no record could pass");
+    return SECEDO_OK;
+}
+
+// a flag mask of the environment: decimal or 0x hex
+int env_flags(const char *name, uint64_t *v) {
+    *v = 0;
+    const char *e = std::getenv(name);
+    if (!e || !*e) return SECEDO_OK;
+    char *end = nullptr;
+    const unsigned long long x = std::strtoull(e, &end, 0);
+    if (end == e || *end || *e == '-' || x > 0xFFFF)
+        return fail(SECEDO_E_INVALID_ARG, std::string(name) + "=" + e + ": expected a flag mask, decimal or 0x hex, at most 0xFFFF");
+    *v = x;
+    return SECEDO_OK;
+}
+
+int read_filter(uint32_t *require, uint32_t *exclude) {
+    const int64_t f = g_read_filter.load();
+    uint64_t rq = 0, ex = 0;
+    if (f < 0) {
+        SECEDO_CALL(env_flags("SECEDO_BAM_REQUIRE_FLAGS", &rq));
+        SECEDO_CALL(env_flags("SECEDO_BAM_EXCLUDE_FLAGS", &ex));
+        SECEDO_CALL(check_read_filter("SECEDO_BAM_REQUIRE_FLAGS / SECEDO_BAM_EXCLUDE_FLAGS", rq, ex));
+    } else {
+        rq = uint64_t(f) >> 16;
+        ex = uint64_t(f) & 0xFFFF;
+    }
+    *require = uint32_t(rq);
+    *exclude = uint32_t(ex);
+    return SECEDO_OK;
+}
+
+int duplicates_mode(int *mode) {
+    int m = g_duplicates.load();
+    if (m < 0) {
+        const char *e = std::getenv("SECEDO_BAM_DUPLICATES");
+        if (!e || !*e || std::strcmp(e, "keep") == 0) m = SECEDO_BAM_DUPLICATES_KEEP;
+        else if (std::strcmp(e, "remove") == 0) m = SECEDO_BAM_DUPLICATES_REMOVE;
+        else return fail(SECEDO_E_INVALID_ARG, std::string("SECEDO_BAM_DUPLICATES=") + e + ": expected keep or remove");
+    }
+    *mode = m;
+    return SECEDO_OK;
+}
+
+int current_select(Select *sel) {
+    SECEDO_CALL(read_filter(&sel->require, &sel->exclude));
+    int mode = SECEDO_BAM_DUPLICATES_KEEP;
+    SECEDO_CALL(duplicates_mode(&mode));
+    sel->dedup = mode == SECEDO_BAM_DUPLICATES_REMOVE;
+    return SECEDO_OK;
+}
+
+// The device counters of the front passes (bam::Sel slots), added to g_select when a chromosome's passes are done.
+struct SelStat {
+    Dev<unsigned long long> d;
+    int init(hipStream_t s) {
+        SECEDO_TRY(d.alloc(kSelSlots));
+        SECEDO_TRY(hipMemsetAsync(d.p, 0, kSelSlots * 8, s));
+        return SECEDO_OK;
+    }
+    int add_to_stats(hipStream_t s) {
+        if (!d.p) return SECEDO_OK;
+        unsigned long long h[kSelSlots];
+        SECEDO_TRY(hipMemcpyAsync(h, d.p, sizeof h, hipMemcpyDeviceToHost, s));
+        SECEDO_TRY(hipStreamSynchronize(s));
+        g_select.records += h[kSelRecords];
+        g_select.dropped_require += h[kSelRequire];
+        g_select.dropped_exclude += h[kSelExclude];
+        g_select.templates += h[kSelTemplates];
+        g_select.large_templates += h[kSelLarge];
+        g_select.duplicate_templates += h[kSelDupTemplates];
+        g_select.duplicate_records += h[kSelDupRecords];
+        return SECEDO_OK;
+    }
+};
 
 struct ChrOut {
     std::vector<uint8_t> first;  // per ordinal: first occurrence of its name (host files only)
@@ -110,7 +205,7 @@ struct Order {
     std::vector<uint64_t> ord_idx;
     std::vector<uint32_t> in_file;  // tag mode: per input ordinal; d_ord maps an ordinal to its input ordinal
     std::vector<uint64_t> in_idx;
-    Dev<uint32_t> d_ord;
+    Dev<uint32_t> d_ord;  // per-file mode: null until rule 3c or 3d dropped a record, then the ordinal each had before
 };
 
 int check_record_count(uint64_t n) {
@@ -171,8 +266,9 @@ int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t 
 
 // Tag mode: the records in input order go up, the device selects the listed cells and sorts them into the global
 // order (chunk, cell, Position, file, record) -> d_off / d_cell of the selected records.
-int order_by_cell(const ChrInput &ci, const CellList &L, hipStream_t s, Dev<uint8_t> *d_bytes, Dev<uint64_t> *d_off,
-                  Dev<uint16_t> *d_cell, Order *ord, secedo_bam_times *t) {
+int order_by_cell(const ChrInput &ci, const CellList &L, const Select &sl, unsigned long long *d_stat, hipStream_t s,
+                  Dev<uint8_t> *d_bytes, Dev<uint64_t> *d_off, Dev<uint16_t> *d_cell, Order *ord,
+                  secedo_bam_times *t) {
     std::vector<uint64_t> in_off;
     Dev<uint64_t> d_in_off;
     SECEDO_CALL(upload_input_order(ci, s, &in_off, ord, d_bytes, &d_in_off, t));
@@ -182,7 +278,7 @@ int order_by_cell(const ChrInput &ci, const CellList &L, hipStream_t s, Dev<uint
     Dev<uint32_t> sel, vs;
     SECEDO_TRY(key.alloc(n_in));
     SECEDO_TRY(sel.alloc(n_in + 1));
-    SECEDO_TRY(cells(d_bytes->p, d_in_off.p, n_in, L, key.p, sel.p, s));
+    SECEDO_TRY(cells(d_bytes->p, d_in_off.p, n_in, L, sl.require, sl.exclude, key.p, sel.p, d_stat, s));
     uint32_t n = 0;
     SECEDO_CALL(compact_and_sort(key, sel, n_in, s, &n, &ks, &vs));
     key.reset();
@@ -288,8 +384,10 @@ int decode_error(const Inputs &in, const Order &ord, bool tag_mode, unsigned lon
         file = ord.in_file[i];
         idx = ord.in_idx[i];
     } else {
-        file = ord.ord_file[o];
-        idx = ord.ord_idx[o];
+        uint32_t i = o;  // the ordinal it had before rules 3c and 3d dropped records
+        if (ord.d_ord.p) SECEDO_TRY(hipMemcpy(&i, ord.d_ord.p + o, 4, hipMemcpyDeviceToHost));
+        file = ord.ord_file[i];
+        idx = ord.ord_idx[i];
     }
     return fail(SECEDO_E_INVALID_ARG,
                 record_where(in.paths[file], file, in.line0[file], idx, Stage::kDevice, in.indexed[file] != 0) + ": " +
@@ -352,7 +450,7 @@ int decode_and_number(const Inputs &in, const Params &prm, bool tag_mode, bool w
             SECEDO_TRY(hipStreamSynchronize(s));
         }
         for (uint32_t o = 0; o < n; ++o) co->first[o] = uint8_t(fl[o]);
-        if (tag_mode) {
+        if (tag_mode || cd->ord.d_ord.p) {
             co->ord_off.resize(n);
             if (n) SECEDO_TRY(hipMemcpy(co->ord_off.data(), cd->off.p, n * 8ull, hipMemcpyDeviceToHost));
         } else {
@@ -476,14 +574,123 @@ int max_read_length(const ChrDev &cd, uint64_t locus_base, hipStream_t s, Result
     return SECEDO_OK;
 }
 
+// The records with keep[o] != 0 (keep: [n + 1]) become the chromosome's Records, in the same order; Order follows:
+// d_ord names the ordinal each survivor had before, the chunks are those of the first and the last survivor.
+int compact_chr(const ChrInput &ci, Dev<uint32_t> &keep, hipStream_t s, ChrDev *cd) {
+    const uint32_t n = cd->ord.n;
+    Dev<uint32_t> scan, ord2;
+    Dev<uint64_t> off2;
+    Dev<uint16_t> file2;
+    Dev<uint8_t> tmp;
+    const size_t tb = scan_bytes(uint64_t(n) + 1);
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(scan.alloc(n + 1));
+    SECEDO_TRY(hipMemsetAsync(keep.p + n, 0, 4, s));
+    SECEDO_TRY(exclusive_sum(tmp.p, tb, keep.p, scan.p, uint64_t(n) + 1, s));
+    uint32_t m = 0;
+    SECEDO_TRY(hipMemcpyAsync(&m, scan.p + n, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    if (m == n) return SECEDO_OK;
+    SECEDO_TRY(off2.alloc(m));
+    SECEDO_TRY(file2.alloc(m));
+    SECEDO_TRY(ord2.alloc(m));
+    SECEDO_TRY(compact_records(cd->records(), cd->ord.d_ord.p, keep.p, scan.p, off2.p, file2.p, ord2.p, s));
+    uint64_t ends[2] = {0, 0};
+    if (m) {
+        SECEDO_TRY(hipMemcpyAsync(&ends[0], off2.p, 8, hipMemcpyDeviceToHost, s));
+        SECEDO_TRY(hipMemcpyAsync(&ends[1], off2.p + m - 1, 8, hipMemcpyDeviceToHost, s));
+    }
+    SECEDO_TRY(hipStreamSynchronize(s));
+    std::swap(cd->off.p, off2.p), std::swap(cd->off.n, off2.n);
+    std::swap(cd->file.p, file2.p), std::swap(cd->file.n, file2.n);
+    std::swap(cd->ord.d_ord.p, ord2.p), std::swap(cd->ord.d_ord.n, ord2.n);
+    cd->ord.n = m;
+    cd->ord.min_pos = INT32_MAX;
+    cd->ord.last_chunk = 0;
+    if (m) {  // the order starts with the chunk: the first survivor is in the first chunk, the last in the last
+        const auto chunk_of = [&](uint64_t off) { return rd32(ci.bytes.data() + off + 4 + 4) / kChunk; };
+        cd->ord.min_pos = int32_t(chunk_of(ends[0]) * kChunk);  // the first window starts at or before it
+        cd->ord.last_chunk = chunk_of(ends[1]);
+    }
+    return SECEDO_OK;
+}
+
+// Rule 3c in per-file mode (tag mode folds it into the cells pass): flag test, scan, compaction.
+int filter_flags(const ChrInput &ci, const Select &sl, unsigned long long *d_stat, hipStream_t s, ChrDev *cd) {
+    const uint32_t n = cd->ord.n;
+    if (n == 0) return SECEDO_OK;
+    Dev<uint32_t> keep;
+    SECEDO_TRY(keep.alloc(n + 1));
+    SECEDO_TRY(flag_test(cd->records(), sl.require, sl.exclude, keep.p, d_stat, s));
+    return compact_chr(ci, keep, s, cd);
+}
+
+// Rule 3d: ends and scores -> templates by (cell, name) -> groups by key -> the drop flags -> compaction.
+int remove_duplicates(const ChrInput &ci, unsigned long long *d_stat, hipStream_t s, ChrDev *cd) {
+    const uint32_t n = cd->ord.n;
+    if (n == 0) return SECEDO_OK;
+    const Records rs = cd->records();
+    Dev<uint64_t> key, key2, end, gkey, gks;
+    Dev<uint32_t> val, val2, score, run, rep, extra, tscore, mate, sel, vs, grp, keep;
+    Dev<unsigned long long> best;
+    Dev<uint8_t> tmp;
+    const size_t tb = std::max(sort_pairs_bytes(n), scan_bytes(uint64_t(n) + 1));
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(key.alloc(n));
+    SECEDO_TRY(key2.alloc(n));
+    SECEDO_TRY(val.alloc(n));
+    SECEDO_TRY(val2.alloc(n));
+    SECEDO_TRY(end.alloc(n));
+    SECEDO_TRY(score.alloc(n));
+    SECEDO_TRY(ends_and_scores(rs, key.p, val.p, end.p, score.p, s));
+    SECEDO_TRY(sort_pairs(tmp.p, tb, key.p, key2.p, val.p, val2.p, n, s));  // radix sort: stable
+    SECEDO_TRY(run.alloc(n));
+    SECEDO_TRY(rep.alloc(n));
+    SECEDO_TRY(extra.alloc(n));
+    SECEDO_TRY(tscore.alloc(n));
+    SECEDO_TRY(mate.alloc(n));
+    SECEDO_TRY(gkey.alloc(n));
+    SECEDO_TRY(sel.alloc(n + 1));
+    SECEDO_TRY(hipMemsetAsync(extra.p, 0, n * 4ull, s));
+    SECEDO_TRY(hipMemsetAsync(tscore.p, 0, n * 4ull, s));
+    SECEDO_TRY(hipMemsetAsync(mate.p, 0, n * 4ull, s));
+    SECEDO_TRY(templates(rs, key2.p, val2.p, score.p, end.p, run.p, rep.p, extra.p, tscore.p, mate.p, gkey.p, sel.p,
+                         d_stat, tmp.p, tb, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    key.reset();
+    key2.reset();
+    val.reset();
+    val2.reset();
+    score.reset();
+    rep.reset();
+    uint32_t m = 0;
+    SECEDO_CALL(compact_and_sort(gkey, sel, n, s, &m, &gks, &vs));
+    gkey.reset();
+    sel.reset();
+    SECEDO_TRY(grp.alloc(n));
+    SECEDO_TRY(best.alloc(n));
+    SECEDO_TRY(keep.alloc(n + 1));
+    SECEDO_TRY(hipMemsetAsync(best.p, 0, n * 8ull, s));
+    SECEDO_TRY(mark_duplicates(rs, gks.p, vs.p, m, extra.p, mate.p, end.p, tscore.p, run.p, grp.p, best.p, keep.p,
+                               d_stat, tmp.p, tb, s));
+    return compact_chr(ci, keep, s, cd);
+}
+
 // The device passes of one chromosome, appended to `res`. cells: tag mode's list, or null for per-file mode.
-int run_chromosome(const Inputs &in, const ChrInput &ci, const Params &prm, const CellList *cells,
+int run_chromosome(const Inputs &in, const ChrInput &ci, const Params &prm, const CellList *cells, const Select &sl,
                    const uint16_t *d_i2g, uint32_t n_groups, bool want_map, hipStream_t s, Result *res, ChrOut *co,
                    secedo_bam_times *t) {
     ChrDev cd;
-    if (cells) SECEDO_CALL(order_by_cell(ci, *cells, s, &cd.bytes, &cd.off, &cd.file, &cd.ord, t));
+    SelStat stat;  // stays unallocated with rules 3c and 3d off
+    if (sl.filter() || sl.dedup) SECEDO_CALL(stat.init(s));
+    if (cells)
+        SECEDO_CALL(order_by_cell(ci, *cells, sl, sl.filter() ? stat.d.p : nullptr, s, &cd.bytes, &cd.off, &cd.file,
+                                  &cd.ord, t));
     else SECEDO_CALL(order_by_file(ci, s, &cd.bytes, &cd.off, &cd.file, &cd.ord, t));
     const Clock::time_point t0 = Clock::now();
+    if (sl.filter() && !cells) SECEDO_CALL(filter_flags(ci, sl, stat.d.p, s, &cd));
+    if (sl.dedup) SECEDO_CALL(remove_duplicates(ci, stat.d.p, s, &cd));
+    SECEDO_CALL(stat.add_to_stats(s));
     const uint64_t locus_base = res->n_loci;
     SECEDO_CALL(decode_and_number(in, prm, cells != nullptr, want_map, s, &cd, co));
     if (cd.ord.n) SECEDO_CALL(pile_windows(cd, prm, d_i2g, n_groups, s, res));
@@ -641,6 +848,9 @@ int run(const Request &rq, secedo_bam_result_info *info, secedo_bam_times *times
         return fail(SECEDO_E_LIMIT, "more than 16384 BAM files: cell ids do not fit cell << 2 | base in 16 bits");
     std::vector<std::string> files;
     SECEDO_CALL(check_files(rq.bam_files, rq.n_files, &files));
+    g_select = secedo_bam_select_info{};
+    Select sl;
+    SECEDO_CALL(current_select(&sl));
     delete g_result;
     g_result = new Result();
     Result *res = g_result;
@@ -663,7 +873,7 @@ int run(const Request &rq, secedo_bam_result_info *info, secedo_bam_times *times
         p.chromosome = rq.chromosome_ids[c];
         ChrOut co;
         const uint64_t l0 = res->n_loci, e0 = res->n_entries;
-        SECEDO_CALL(run_chromosome(in, in.chrs[c], p, rq.tag ? &dc.list : nullptr,
+        SECEDO_CALL(run_chromosome(in, in.chrs[c], p, rq.tag ? &dc.list : nullptr, sl,
                                    rq.id_to_group ? d_i2g.p : nullptr, rq.n_ids, rq.out_pileup != nullptr, s, res,
                                    &co, &tl));
         res->chr_locus_off.push_back(uint32_t(res->n_loci));
@@ -694,7 +904,8 @@ struct Barcodes {
 thread_local Barcodes *g_barcodes = nullptr;
 
 // one chromosome's distinct values (device: hash, sort, exact split of equal-hash runs) added to `acc`
-int count_values(const ChrInput &ci, const char *tag, hipStream_t s, std::map<std::string, uint64_t> *acc) {
+int count_values(const ChrInput &ci, const char *tag, const Select &sl, hipStream_t s,
+                 std::map<std::string, uint64_t> *acc) {
     std::vector<uint64_t> in_off;
     Dev<uint8_t> d_bytes, tmp;
     Dev<uint64_t> d_in_off, key, ks, voff;
@@ -705,9 +916,12 @@ int count_values(const ChrInput &ci, const char *tag, hipStream_t s, std::map<st
     SECEDO_TRY(key.alloc(n_in));
     SECEDO_TRY(sel.alloc(n_in + 1));
     const uint8_t t0 = uint8_t(tag[0]), t1 = uint8_t(tag[1]);
-    SECEDO_TRY(tag_keys(d_bytes.p, d_in_off.p, n_in, t0, t1, key.p, sel.p, s));
+    SelStat stat;
+    if (sl.filter()) SECEDO_CALL(stat.init(s));
+    SECEDO_TRY(tag_keys(d_bytes.p, d_in_off.p, n_in, t0, t1, sl.require, sl.exclude, key.p, sel.p, stat.d.p, s));
     uint32_t n = 0;
     SECEDO_CALL(compact_and_sort(key, sel, n_in, s, &n, &ks, &vs));
+    SECEDO_CALL(stat.add_to_stats(s));
     if (n == 0) return SECEDO_OK;
     const size_t tb = scan_bytes(n);
     SECEDO_TRY(tmp.alloc(tb));
@@ -738,6 +952,36 @@ int count_values(const ChrInput &ci, const char *tag, hipStream_t s, std::map<st
 extern "C" {
 
 const char *secedo_bam_last_error(void) { return g_error.c_str(); }
+
+int secedo_bam_set_read_filter(uint32_t require, uint32_t exclude) {
+    SECEDO_CALL(check_read_filter("secedo_bam_set_read_filter", require, exclude));
+    g_read_filter.store(int64_t(require) << 16 | exclude);
+    return SECEDO_OK;
+}
+
+int secedo_bam_get_read_filter(uint32_t *require, uint32_t *exclude) {
+    if (!require || !exclude) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    return read_filter(require, exclude);
+}
+
+int secedo_bam_set_duplicates(int mode) {
+    if (mode != SECEDO_BAM_DUPLICATES_KEEP && mode != SECEDO_BAM_DUPLICATES_REMOVE)
+        return fail(SECEDO_E_INVALID_ARG, "secedo_bam_set_duplicates: mode " + std::to_string(mode) +
+                                              " is neither SECEDO_BAM_DUPLICATES_KEEP nor SECEDO_BAM_DUPLICATES_REMOVE");
+    g_duplicates.store(mode);
+    return SECEDO_OK;
+}
+
+int secedo_bam_get_duplicates(int *mode) {
+    if (!mode) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    return duplicates_mode(mode);
+}
+
+int secedo_bam_select_stats(secedo_bam_select_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = g_select;
+    return SECEDO_OK;
+}
 
 int secedo_pileup_bams(const char *const *bam_files, uint32_t n_files, const char *out_pileup, int write_text_file,
                        uint32_t chromosome_id, uint32_t max_coverage, uint32_t min_base_quality,
@@ -807,13 +1051,16 @@ int secedo_bam_barcodes(const char *const *bam_files, uint32_t n_files, const ch
     SECEDO_CALL(check_files(bam_files, n_files, &files));
     delete g_barcodes;
     g_barcodes = nullptr;
+    g_select = secedo_bam_select_info{};
+    Select sl;
+    SECEDO_CALL(current_select(&sl));  // the census honours rule 3c only
     Inputs in;
     SECEDO_CALL(load_inputs(files, chromosome_ids, n_chr, num_threads ? num_threads : 1, &in, nullptr));
     StreamGuard guard;
     SECEDO_TRY(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
     std::map<std::string, uint64_t> acc;
     for (uint32_t c = 0; c < n_chr; ++c) {
-        SECEDO_CALL(count_values(in.chrs[c], tag, guard.s, &acc));
+        SECEDO_CALL(count_values(in.chrs[c], tag, sl, guard.s, &acc));
         std::vector<uint8_t>().swap(in.chrs[c].bytes);
     }
     if (acc.size() > UINT32_MAX) return fail(SECEDO_E_LIMIT, "more than 2^32 distinct values");

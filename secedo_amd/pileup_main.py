@@ -21,6 +21,13 @@ A .sam.gz written by `bgzip` (BGZF) is inflated on the GPU in front of that pars
 --build_index writes, before the run, <bam>.bai for every input BAM that has no index file where --index looks
 (<bam>.bai, <bam without .bam>.bai), all of them in one pass on the GPU (``secedo_amd.bam_index_build``), and never
 touches an index file that exists; the run then goes on as --index says.
+
+--require_flags / --exclude_flags select records by SAM flag as samtools' -f / -F do (a decimal or 0x hex mask, or a
+comma list of samtools' names: PAIRED, PROPER_PAIR, UNMAP, MUNMAP, REVERSE, MREVERSE, READ1, READ2, SECONDARY, QCFAIL,
+DUP, SUPPLEMENTARY), and --remove_duplicates drops, per cell, all but the best template of each set with the same
+unclipped 5' ends. Dropped records are not checked: with --require_flags 3 --exclude_flags 0xF04 a BAM straight from
+the aligner runs without a samtools pass in front. Without --cells, --min_cell_records counts the records that pass
+the flag filter.
 """
 from __future__ import annotations
 
@@ -62,6 +69,15 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--build_index", action="store_true",
                     help="Before the run, write <bam>.bai on the GPU for every input BAM without an index file; an "
                          "existing index file is never touched. The run then proceeds as --index says")
+    ap.add_argument("--require_flags", default=None,
+                    help="Use only records with all of these SAM flag bits: decimal, 0x hex or samtools' names "
+                         "separated by commas (samtools -f). Default: SECEDO_BAM_REQUIRE_FLAGS, else 0")
+    ap.add_argument("--exclude_flags", default=None,
+                    help="Skip records with any of these SAM flag bits, e.g. SECONDARY,SUPPLEMENTARY,DUP,QCFAIL,UNMAP or "
+                         "0xF04 (samtools -F). Default: SECEDO_BAM_EXCLUDE_FLAGS, else 0")
+    ap.add_argument("--remove_duplicates", action="store_true", default=None,
+                    help="Per cell, keep only the best template among those with the same unclipped 5' ends and "
+                         "strands. Default: SECEDO_BAM_DUPLICATES, else keep")
     return ap.parse_args(argv)
 
 
@@ -99,6 +115,19 @@ def check_tag_flags(a: argparse.Namespace) -> None:
         raise SystemExit("--cells file %s does not exist" % a.cells)
     if a.min_cell_records is not None and a.min_cell_records < 1:
         raise SystemExit("--min_cell_records must be at least 1")
+
+
+def check_select_flags(a: argparse.Namespace) -> None:
+    """--require_flags / --exclude_flags, checked before any BAM is read (and before torch is imported); they are
+    replaced by their masks."""
+    from .sam_flags import parse_filter
+
+    if a.require_flags is None and a.exclude_flags is None:
+        return
+    try:
+        a.require_flags, a.exclude_flags = parse_filter(a.require_flags, a.exclude_flags)
+    except ValueError as e:
+        raise SystemExit("Invalid --require_flags / --exclude_flags: %s" % e)
 
 
 def check_index_flags(a: argparse.Namespace) -> None:
@@ -185,6 +214,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
     check_tag_flags(a)
     check_index_flags(a)
+    check_select_flags(a)
     if a.cell_tag is not None and not os.path.exists(a.i):
         raise SystemExit("Input %s does not exist" % a.i)
     files = input_files(a.i)
@@ -210,7 +240,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             from .bam_pileup import bam_barcodes
 
             values, counts = bam_barcodes(files, a.cell_tag, ids, pool_size(a.num_threads), inflate=a.inflate,
-                                          index=a.index)
+                                          index=a.index, require_flags=a.require_flags,
+                                          exclude_flags=a.exclude_flags)
             n = 1 if a.min_cell_records is None else a.min_cell_records
             cells = [v for v, c in zip(values, counts) if int(c) >= n]
             if not cells:
@@ -220,16 +251,23 @@ def main(argv: Optional[List[str]] = None) -> int:
                              % (len(cells), MAX_CELLS))
         with open(a.o + "_" + a.chromosomes + ".map", "w") as f:
             f.writelines("%s\t%d\n" % (c, i) for i, c in enumerate(cells))
-    from .bam_pileup import pileup_bams
+    from .bam_pileup import bam_select_stats, pileup_bams
 
     tag_kw = {} if a.cell_tag is None else dict(cell_tag=a.cell_tag, cells=cells)
     tag_kw["inflate"] = a.inflate
     tag_kw["index"] = a.index
+    tag_kw.update(require_flags=a.require_flags, exclude_flags=a.exclude_flags, remove_duplicates=a.remove_duplicates)
     for chromosome, cid in zip(chromosomes, ids):
         out = a.o + "_" + chromosome + ".pileup"
         p = pileup_bams(files, out, True, cid, a.max_coverage, a.min_base_quality, a.min_map_quality,
                         a.min_map_score, pool_size(a.num_threads), a.min_different, **tag_kw)
         print("Written %d positions to %s.txt/.bin" % (p.n_loci, out))
+        st = bam_select_stats()
+        if any(st.values()) and a.log_level.lower() in ("trace", "debug", "info"):
+            print("Chromosome %s: %d records filtered by flag (%d dropped by --require_flags, %d by --exclude_flags); "
+                  "%d templates, %d of three or more records, %d duplicate templates (%d records) dropped"
+                  % (chromosome, st["records"], st["dropped_require"], st["dropped_exclude"], st["templates"],
+                     st["large_templates"], st["duplicate_templates"], st["duplicate_records"]))
     return 0
 
 

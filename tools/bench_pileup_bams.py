@@ -24,6 +24,9 @@ inflate_GBps stands beside the BAM route's host zlib pool on the same kind of by
 inflate="device": the BGZF members inflated and the records walked on the GPU. Both routes are timed in the same run;
 the line gets the device route's step times, its route stats (bam_route_stats) and whether its files equal the host
 route's.
+--require-flags / --exclude-flags / --remove-duplicates run the resident call with the record selection on (the flag
+filter's front pass, the duplicate removal's); the line then holds bam_select_stats() of the last call, and
+resident_device_ms_runs always lists the timed calls one by one, which gives the run-to-run spread.
 Kernel times come from a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_pileup_bams.py --dir D \
         --repeat 1 --resident-only
@@ -235,6 +238,10 @@ def merge(line_path, prof_dir):
     front = [k for k in ("k_cells", "k_compact_keys", "k_order") if k in kernels]
     if front:  # tag mode's front passes (their radix sort is inside rocprim_radix_sort)
         line["front_ms"] = round(sum(kernels[k]["ms"] for k in front) / calls, 3)
+    sel = [k for k in ("k_flag_test", "k_compact_records", "k_ends", "k_tmpl_rep", "k_tmpl_key", "k_group",
+                       "k_dup_mark", "k_fill") if k in kernels]
+    if sel:  # the record selection's front passes (their two radix sorts are inside rocprim_radix_sort)
+        line["select_front_ms"] = round(sum(kernels[k]["ms"] for k in sel) / calls, 3)
     line["profiled_calls"] = calls
     line["kernel_ms_per_call"] = round(total / calls, 3)
     # compulsory bytes of one call: the uploaded records read by decode, count and emit, the counts written and
@@ -272,6 +279,9 @@ def main():
     ap.add_argument("--index", action="store_true",
                     help="With --refs N: the set gets .bai files, and index='off' and index='auto' are timed in the same "
                          "run, on the host route and, with --device-inflate, on the device route")
+    ap.add_argument("--require-flags", default=None, help="The resident call with require_flags (e.g. 3)")
+    ap.add_argument("--exclude-flags", default=None, help="The resident call with exclude_flags (e.g. 0xF04)")
+    ap.add_argument("--remove-duplicates", action="store_true", help="The resident call with remove_duplicates")
     ap.add_argument("--merge", nargs=2, metavar=("LINE", "PROF_DIR"))
     ap.add_argument("--merge-sam", nargs=2, metavar=("LINE", "PROF_DIR"))
     a = ap.parse_args()
@@ -369,16 +379,24 @@ def main():
                 # the device inflate against the host zlib pool on BGZF bytes (the BAM route's inflate_GBps above)
                 r = line["sam_gz"]["per_file"]
                 r["inflate_GBps"] = r["text_bytes"] / (r["inflate_ms"] * 1e-3) / 1e9
+    select = {}
+    if a.require_flags is not None or a.exclude_flags is not None:
+        select.update(require_flags=a.require_flags, exclude_flags=a.exclude_flags)
+    if a.remove_duplicates:
+        select["remove_duplicates"] = True
     with secedo_amd.SimilarityMatrixPlan(0) as plan:
         rt = []
         for k in range(a.repeat + 1):
             t = {}
             res, cells, max_len = bam_pileup.pileup_bams_resident(plan, paths, [0], 100, 30, 30, 0, a.threads, 3,
-                                                                  times=t)
+                                                                  times=t, **select)
             if k:
                 rt.append(t)
     line["resident_total_ms"] = round(med([r["total_ms"] for r in rt]), 2)
     line["resident_device_ms"] = round(med([r["device_ms"] for r in rt]), 2)
+    line["resident_device_ms_runs"] = [round(r["device_ms"], 2) for r in rt]
+    if select:
+        line["select"] = dict({k: str(v) for k, v in select.items()}, **bam_pileup.bam_select_stats())
     line.update(loci=res["n_loci"], entries=res["n_entries"], num_cells=cells, max_read_length=max_len)
     n_rec = a.cells * a.pairs * 2
     line["records"] = n_rec
