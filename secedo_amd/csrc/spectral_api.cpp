@@ -173,6 +173,22 @@ int solve(int device_id, const double *d_rows, uint32_t row_begin, uint32_t n_ro
     int rc = sv.setup(d_rows, row_begin, n_rows, n, allreduce, allreduce_ctx, stream);
     if (rc) return rc;
     if ((rc = sv.scales())) return rc;
+    if (n == 1) {
+        // A single cell: L = [1 - s^2 a_00], and a_00 is the (summed) row sum itself. Closed form: the iteration
+        // normalises its one basis vector to within an ulp of 1, and the Rayleigh quotient inherits that ulp.
+        double sum = 0.0;
+        const double one = 1.0;
+        SECEDO_TRY(hipMemcpyAsync(&sum, sv.sums.p, 8, hipMemcpyDeviceToHost, stream));
+        if (n_vectors) SECEDO_TRY(hipMemcpyAsync(d_eigenvectors, &one, 8, hipMemcpyHostToDevice, stream));
+        SECEDO_TRY(hipStreamSynchronize(stream));
+        const double s1 = sum == 0.0 ? 0.0 : 1.0 / std::sqrt(sum);
+        eigenvalues[0] = 1.0 - s1 * s1 * sum;
+        if (info) {
+            std::memset(info, 0, sizeof(*info));
+            info->converged = 1u;
+        }
+        return SECEDO_OK;
+    }
     SECEDO_TRY(init_block(n, sv.root.as<double>(), sv.W.as<double>(), stream));
     std::vector<double> R_last((size_t)BW * BW);
     std::vector<uint32_t> basis_alive((size_t)(kCycleBlocks + 1) * BW, 1);

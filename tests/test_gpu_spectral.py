@@ -185,3 +185,85 @@ def test_reference_two_and_three_cluster_inputs():
     spread = max(np.linalg.norm(emb[expect == g] - centres[g], axis=1).max() for g in range(3))
     sep = min(np.linalg.norm(centres[g] - centres[h]) for g in range(3) for h in range(g))
     assert spread < 0.25 * sep
+
+
+# ---- the solver at the edges of its kernels' blocks and at the options no other test calls ----
+
+@pytest.mark.parametrize("n", [1, 63, 65, 127, 128, 129, 192])
+def test_eigenpairs_match_lapack_at_block_edges(n):
+    """Around the 64-row stage and the 128-column workgroup of the product and the 128-row Gram chunk; a single cell
+    has the Laplacian [1]: eigenvalue 1 and the vector [1], exactly."""
+    a, _ = planted(n, 2, 50 + n)
+    vals, vecs, _ = check_against_lapack(a, 20, 7)
+    if n == 1:
+        assert vals.tolist() == [1.0] and vecs.tolist() == [[1.0]]
+
+
+@pytest.mark.parametrize("n_values,n_vectors", [(1, 1), (32, 7), (32, 32)])
+def test_one_and_thirty_two_values(n_values, n_vectors):
+    a, _ = planted(100, 3, 61)
+    vals, vecs, _ = check_against_lapack(a, n_values, n_vectors)
+    assert len(vals) == n_values and vecs.shape == (100, n_vectors)
+
+
+def test_no_vectors_through_the_raw_abi_gives_the_same_values():
+    """n_vectors == 0 with a null vector pointer: the eigenvalues of the call that asks for vectors, bit for bit."""
+    import ctypes as C
+
+    import torch
+    from secedo_amd import _lib
+    a, _ = planted(100, 3, 62)
+    dev = torch.from_numpy(a).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def eigs(n_vectors, vec_ptr):
+        vals, info = np.full(20, np.nan), _lib.SpectralInfo()
+        _lib.check(_lib.lib().secedo_spectral_eigs_device(0, dev.data_ptr(), 100, 20, n_vectors, 0.0, 0, _lib.ptr(vals),
+                                                          vec_ptr, C.byref(info), stream))
+        return vals, info
+
+    vecs = torch.empty((7, 100), dtype=torch.float64, device="cuda")
+    with_vectors, info7 = eigs(7, vecs.data_ptr())
+    without, info0 = eigs(0, None)
+    assert info7.converged and info0.converged and info0.max_residual_vectors == 0.0
+    assert np.array_equal(without.view(np.uint64), with_vectors.view(np.uint64))
+    w, _ = so.eig_sym(so.laplacian_fast(a))
+    assert np.max(np.abs(without - w[:20])) <= 1e-8
+    with pytest.raises(secedo_amd.SecedoError):  # vectors asked for, nowhere to put them
+        eigs(7, None)
+
+
+def test_one_cycle_returns_unconverged_pairs_with_an_honest_residual():
+    """max_cycles = 1: not converging is not an error; the best pairs found come back orthonormal, and the residual
+    the solver reports (from the last coupling block) covers the true residual of every returned pair."""
+    a, _ = planted(1000, 3, 63)
+    vals, vecs, info = secedo_amd.smallest_eigenpairs(a, 20, 7, max_cycles=1)
+    assert not info["converged"] and info["cycles"] == 1
+    assert np.isfinite(info["max_residual_vectors"]) and np.isfinite(info["max_residual_values"])
+    assert info["max_residual_values"] >= info["max_residual_vectors"] > 0.0
+    assert np.all(np.isfinite(vals)) and np.max(np.abs(vecs.T @ vecs - np.eye(7))) <= 1e-10
+    lap = so.laplacian_fast(a)
+    true = np.linalg.norm(lap @ vecs - vecs * vals[:7], axis=0)
+    print("max_cycles=1 at n=1000: true residuals %s, reported max %.3e" % (
+        np.array2string(true, precision=2), info["max_residual_vectors"]))
+    assert np.all(true <= info["max_residual_vectors"] + 1e-10)
+    # and the same call with cycles to spare converges
+    assert secedo_amd.smallest_eigenpairs(a, 20, 7)[2]["converged"]
+
+
+@pytest.mark.parametrize("blocks", [3, 7, 8, 12])
+def test_blocks_per_cycle_switch(blocks, monkeypatch):
+    monkeypatch.setenv("SECEDO_SPECTRAL_BLOCKS", str(blocks))
+    a, _ = planted(300, 3, 64, isolated=(11,))
+    vals, vecs, info = check_against_lapack(a, 20, 7)
+    assert info["block_products"] % blocks == 0 and info["block_products"] == blocks * info["cycles"]
+
+
+@pytest.mark.parametrize("n,k,seed", [(230, 2, 65), (700, 3, 66)])
+def test_production_setting_of_large_matrices_on_small_ones(n, k, seed, monkeypatch):
+    """8 blocks per cycle with the thick restart: what runs from 12000 rows on, on matrices of milliseconds."""
+    monkeypatch.setenv("SECEDO_SPECTRAL_BLOCKS", "8")
+    monkeypatch.setenv("SECEDO_SPECTRAL_KEEP", "2")
+    a, _ = planted(n, k, seed, isolated=(3,))
+    vals, vecs, info = check_against_lapack(a, 20, 7)
+    assert info["max_residual_vectors"] <= 1e-9
