@@ -146,6 +146,11 @@ int secedo_simmat_set_pileup_device(secedo_simmat_t *handle, const uint32_t *d_c
 int secedo_simmat_set_packing(secedo_simmat_t *handle, int mode);
 /* 1 if the last prepare() packed on the GPU, else 0. */
 int secedo_simmat_used_device_packing(const secedo_simmat_t *handle);
+/* 1 if the last prepare() packed on the GPU and took the single-entry path to the end: the reads with one entry
+ * (found by their ids occurring once) skip the read assembly, which only the entries of repeated ids go through.
+ * 0 where that path is not tried (sparse id space, radix grouping) or was given up because more than half of the
+ * entries belong to repeated ids. The packed pileup is the same either way; tests use this to know what they ran. */
+int secedo_simmat_used_single_entry_path(const secedo_simmat_t *handle);
 
 /* Read assembly, flush schedule, tile packing (see above). Work is enqueued on `stream` with a few
  * stream synchronisations for scalar read-backs; host packing is synchronous.

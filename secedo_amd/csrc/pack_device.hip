@@ -239,21 +239,48 @@ __global__ __launch_bounds__(TPB) void k_entry_locus(Raw in, uint32_t *entry_loc
     }
 }
 
+// first entry of chromosome c (c <= n_chr: the last one is the number of entries). Empty chromosomes share a start
+// with their successor, trailing empty ones start at the end
+__device__ __forceinline__ uint32_t chr_first_entry(const Raw &in, uint32_t c) {
+    return (uint32_t)in.locus_entry_off[in.chr_locus_off[c]];
+}
+
 // per chromosome the largest and the smallest read id (the latter as max of ~id, so that zero-filled
 // memory is the neutral element). A workgroup owns a contiguous chunk of entries and cuts it at the
 // chromosome boundaries: one pair of atomics per (workgroup, chromosome) -- same-address atomics
 // are slow.
-__global__ __launch_bounds__(TPB) void k_id_range(Raw in, const uint32_t *entry_locus, uint32_t *id_max,
-                                                 uint32_t *id_negmin, int vec) {
+// It also checks that the positions increase strictly inside a chromosome (the reference asserts it,
+// similarity_matrix.cpp:398): a thread per locus, in front of the ids -- the single-entry path launches no
+// k_entry_locus, which checks the same.
+__global__ __launch_bounds__(TPB) void k_id_range(Raw in, uint32_t *id_max, uint32_t *id_negmin, int vec, Scalars *sc) {
     __shared__ uint32_t s_hi[TPB / 64], s_neg[TPB / 64];
+    __shared__ uint32_t s_chr;
+    for (uint32_t l = blockIdx.x * TPB + threadIdx.x; l + 1 < in.n_loci; l += gridDim.x * TPB) {
+        if (in.locus_pos[l + 1] <= in.locus_pos[l]) {
+            // allowed only across a chromosome boundary
+            const uint32_t c = last_le<uint32_t>(in.chr_locus_off, in.n_chr + 1, l);
+            if (l + 1 < in.chr_locus_off[c + 1]) sc->error = 3;
+        }
+    }
     const uint32_t E = in.n_entries;
     const uint32_t chunk = (E + gridDim.x - 1) / gridDim.x;
     uint32_t cur = min(E, blockIdx.x * chunk);
     const uint32_t e1 = min(E, cur + chunk);
     if (cur >= e1) return;
-    // (the locus of the first entry from k_entry_locus' table: a binary search over the loci here is 16
-    // dependent reads in front of every workgroup's chunk and was most of this kernel's time)
-    uint32_t c = last_le<uint32_t>(in.chr_locus_off, in.n_chr + 1, entry_locus[cur]);
+    // The chromosome of the chunk's first entry: the last one that starts at or before it. Every thread looks at the
+    // chromosomes tid, tid + TPB, ...: two dependent reads per thread whatever their number. (A binary search over
+    // the loci was 16 dependent reads in front of every workgroup's chunk and most of this kernel's time; until
+    // round 17 the entry's locus came from k_entry_locus' table.)
+    if (threadIdx.x == 0) s_chr = 0;
+    __syncthreads();
+    {
+        uint32_t best = 0;
+        for (uint32_t i = threadIdx.x; i < in.n_chr; i += TPB)
+            if (chr_first_entry(in, i) <= cur) best = i;  // (ascending: the last hit is the largest)
+        if (best) atomicMax(&s_chr, best);
+    }
+    __syncthreads();
+    uint32_t c = s_chr;
     while (cur < e1) {
         // entries of chromosome c end where its last locus ends (skip chromosomes without entries)
         uint32_t c_end = (uint32_t)in.locus_entry_off[in.chr_locus_off[c + 1]];
@@ -326,9 +353,14 @@ __global__ __launch_bounds__(TPB) void k_id_range(Raw in, const uint32_t *entry_
 }
 
 // dense numbering of (chromosome, read id): id_base[c] + id - smallest id of c
-__global__ void k_id_bases(uint32_t n_chr, const uint32_t *id_max, const uint32_t *id_negmin, uint32_t *id_base,
-                           unsigned long long assumed_space, Scalars *sc) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// (the other lanes: the chromosomes' first entries, chr_entry[0 .. n_chr], for the kernels that find an entry's
+// chromosome from its index)
+__global__ void k_id_bases(Raw in, const uint32_t *id_max, const uint32_t *id_negmin, uint32_t *id_base,
+                           uint32_t *chr_entry, unsigned long long assumed_space, Scalars *sc) {
+    const uint32_t n_chr = in.n_chr;
+    if (blockIdx.x != 0) return;
+    for (uint32_t c = threadIdx.x; c <= n_chr; c += blockDim.x) chr_entry[c] = chr_first_entry(in, c);
+    if (threadIdx.x != 0) return;
     unsigned long long sum = 0;
     uint32_t top = 0;
     for (uint32_t c = 0; c < n_chr; ++c) {
@@ -367,18 +399,22 @@ __global__ void k_sorted_locus(Raw in, const uint32_t *sval, const uint32_t *ent
         sloc[s] = sloc_pack(entry_locus[sval[s]], in.id_base(sval[s]));
 }
 
-// The dense id of an entry: its chromosome (a search over the chromosomes' first loci), then two per-chromosome words.
+// The dense id of an entry: its chromosome, then two per-chromosome words. The chromosome is a search over the
+// chromosomes' first loci with the entry's locus as the key (`first` = chr_locus_off: the general path, which has the
+// entry -> locus table), or over their first ENTRIES with the entry's index (`first` = chr_entry, k_id_bases: the
+// single-entry path, which has no such table -- the same search, no per-entry read in front of it). Empty chromosomes
+// share a start with their successor and last_le picks the last of them, the one that holds the key.
 // From LDS when the tables fit: from global memory the search is a chain of log2(C) dependent loads in front of
 // whatever the kernel does with the id (k_id_store: 156 -> 117 us on C3).
 constexpr uint32_t kChrLds = 1024;
 struct ChrTables {
     uint32_t first[kChrLds + 1], base[kChrLds], min_id[kChrLds];
 };
-__device__ __forceinline__ bool chr_tables_load(const Raw &in, const uint32_t *id_base, const uint32_t *id_negmin,
-                                                ChrTables &t) {  // (all threads; ends with a barrier)
+__device__ __forceinline__ bool chr_tables_load(const Raw &in, const uint32_t *first, const uint32_t *id_base,
+                                                const uint32_t *id_negmin, ChrTables &t) {  // (all threads; ends with a barrier)
     const bool in_lds = in.n_chr <= kChrLds;
     if (in_lds) {
-        for (uint32_t i = threadIdx.x; i <= in.n_chr; i += blockDim.x) t.first[i] = in.chr_locus_off[i];
+        for (uint32_t i = threadIdx.x; i <= in.n_chr; i += blockDim.x) t.first[i] = first[i];
         for (uint32_t i = threadIdx.x; i < in.n_chr; i += blockDim.x) {
             t.base[i] = id_base[i];
             t.min_id[i] = ~id_negmin[i];
@@ -387,14 +423,32 @@ __device__ __forceinline__ bool chr_tables_load(const Raw &in, const uint32_t *i
     __syncthreads();
     return in_lds;
 }
-__device__ __forceinline__ uint32_t dense_id(const Raw &in, const uint32_t *id_base, const uint32_t *id_negmin,
-                                             const ChrTables &t, bool in_lds, uint32_t locus, uint32_t id) {
-    if (in_lds) {
-        const uint32_t c = last_le<uint32_t>(t.first, in.n_chr + 1, locus);
-        return t.base[c] + (id - t.min_id[c]);
+__device__ __forceinline__ uint32_t chr_of(const Raw &in, const uint32_t *first, const ChrTables &t, bool in_lds,
+                                           uint32_t key) {
+    return last_le<uint32_t>(in_lds ? t.first : first, in.n_chr + 1, key);
+}
+__device__ __forceinline__ uint32_t dense_of(const uint32_t *id_base, const uint32_t *id_negmin, const ChrTables &t,
+                                             bool in_lds, uint32_t c, uint32_t id) {
+    return in_lds ? t.base[c] + (id - t.min_id[c]) : id_base[c] + (id - ~id_negmin[c]);
+}
+__device__ __forceinline__ uint32_t dense_id(const Raw &in, const uint32_t *first, const uint32_t *id_base,
+                                             const uint32_t *id_negmin, const ChrTables &t, bool in_lds, uint32_t key,
+                                             uint32_t id) {
+    return dense_of(id_base, id_negmin, t, in_lds, chr_of(in, first, t, in_lds, key), id);
+}
+// ... of four consecutive entries e0 .. e0 + 3 by their indices: one search where the first and the last are in the
+// same chromosome (all but the quads that straddle a boundary)
+__device__ __forceinline__ void dense_id_quad(const Raw &in, const uint32_t *chr_entry, const uint32_t *id_base,
+                                              const uint32_t *id_negmin, const ChrTables &t, bool in_lds, uint32_t e0,
+                                              const uint32_t (&id)[4], uint32_t (&d)[4]) {
+    const uint32_t c0 = chr_of(in, chr_entry, t, in_lds, e0);
+    const uint32_t next = in_lds ? t.first[c0 + 1] : chr_entry[c0 + 1];  // (c0 < n_chr: e0 is an entry)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const uint32_t e = min(e0 + (uint32_t)u, in.n_entries - 1u);  // (the last quad may reach beyond the entries)
+        const uint32_t c = e < next ? c0 : chr_of(in, chr_entry, t, in_lds, e);
+        d[u] = dense_of(id_base, id_negmin, t, in_lds, c, id[u]);
     }
-    const uint32_t c = last_le<uint32_t>(in.chr_locus_off, in.n_chr + 1, locus);
-    return id_base[c] + (id - ~id_negmin[c]);
 }
 
 // counting path, entries by (chromosome, read id) through the dense numbering
@@ -402,9 +456,9 @@ __global__ void k_id_hist(Raw in, const uint32_t *entry_locus, const uint32_t *i
                           const Scalars *sc, uint32_t *dense, uint32_t *hist) {
     if (sc->id_exceeded) return;  // the table is too small: the caller starts over (k_id_rank)
     __shared__ ChrTables tables;
-    const bool in_lds = chr_tables_load(in, id_base, id_negmin, tables);
+    const bool in_lds = chr_tables_load(in, in.chr_locus_off, id_base, id_negmin, tables);
     for (uint32_t e = blockIdx.x * TPB + threadIdx.x; e < in.n_entries; e += gridDim.x * TPB) {
-        const uint32_t d = dense_id(in, id_base, id_negmin, tables, in_lds, entry_locus[e], in.read_ids[e]);
+        const uint32_t d = dense_id(in, in.chr_locus_off, id_base, id_negmin, tables, in_lds, entry_locus[e], in.read_ids[e]);
         dense[e] = d;
         atomicAdd(&hist[d], 1u);
     }
@@ -463,57 +517,47 @@ __global__ void k_id_rank(Raw in, const uint32_t *dense, const uint32_t *id_off,
 constexpr uint32_t kFlagBlock = 4096;      // entries per workgroup of the numbering passes
 // (a thread takes four consecutive entries, 16 bytes per lane and stream; `vec`: the caller's read-id array is 16-byte
 // aligned -- the tables of this file are)
-__global__ void k_id_store(Raw in, const uint32_t *entry_locus, const uint32_t *id_base, const uint32_t *id_negmin,
-                           const Scalars *sc, uint32_t *dense, uint32_t *last, int vec) {
+// (The dense id is made twice, here and in k_id_check, from the entry's id and index: until round 17 this kernel read
+// an entry -> locus table for the chromosome and stored the dense id for k_id_check, 4 bytes per entry each way.)
+__device__ __forceinline__ void load_id_quad(const Raw &in, uint32_t q, int vec, uint32_t (&id)[4]) {
+    const uint32_t n = in.n_entries, e0 = q * 4u;
+    if (vec && e0 + 4u <= n) {
+        const uint4 iv = reinterpret_cast<const uint4 *>(in.read_ids)[q];
+        id[0] = iv.x, id[1] = iv.y, id[2] = iv.z, id[3] = iv.w;
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) id[u] = in.read_ids[min(e0 + (uint32_t)u, n - 1u)];
+    }
+}
+__global__ void k_id_store(Raw in, const uint32_t *chr_entry, const uint32_t *id_base, const uint32_t *id_negmin,
+                           const Scalars *sc, uint32_t *last, int vec) {
     if (sc->id_exceeded) return;  // the table is too small: no flags, no M entries; the caller starts over
     __shared__ ChrTables tables;
-    const bool in_lds = chr_tables_load(in, id_base, id_negmin, tables);
+    const bool in_lds = chr_tables_load(in, chr_entry, id_base, id_negmin, tables);
     const uint32_t n = in.n_entries, stride = gridDim.x * TPB;
     for (uint32_t q = blockIdx.x * TPB + threadIdx.x; q < (n + 3u) / 4u; q += stride) {
         const uint32_t e0 = q * 4u;
-        uint32_t l[4], id[4], d[4];
-        if (vec && e0 + 4u <= n) {
-            const uint4 lv = reinterpret_cast<const uint4 *>(entry_locus)[q];
-            const uint4 iv = reinterpret_cast<const uint4 *>(in.read_ids)[q];
-            l[0] = lv.x, l[1] = lv.y, l[2] = lv.z, l[3] = lv.w;
-            id[0] = iv.x, id[1] = iv.y, id[2] = iv.z, id[3] = iv.w;
-        } else {
+        uint32_t id[4], d[4];
+        load_id_quad(in, q, vec, id);
+        dense_id_quad(in, chr_entry, id_base, id_negmin, tables, in_lds, e0, id, d);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t e = min(e0 + (uint32_t)u, n - 1u);
-                l[u] = entry_locus[e];
-                id[u] = in.read_ids[e];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) d[u] = dense_id(in, id_base, id_negmin, tables, in_lds, l[u], id[u]);
-        if (e0 + 4u <= n) {
-            reinterpret_cast<uint4 *>(dense)[q] = make_uint4(d[0], d[1], d[2], d[3]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) last[d[u]] = e0 + (uint32_t)u + 1u;
-        } else {
-            for (uint32_t u = 0; e0 + u < n; ++u) {
-                dense[e0 + u] = d[u];
-                last[d[u]] = e0 + u + 1u;
-            }
-        }
+        for (int u = 0; u < 4; ++u)
+            if (e0 + (uint32_t)u < n) last[d[u]] = e0 + (uint32_t)u + 1u;
     }
 }
-__global__ void k_id_check(uint32_t n, const Scalars *sc, const uint32_t *dense, const uint32_t *last, uint8_t *multi) {
+__global__ void k_id_check(Raw in, const uint32_t *chr_entry, const uint32_t *id_base, const uint32_t *id_negmin,
+                           const Scalars *sc, const uint32_t *last, uint8_t *multi, int vec) {
     if (sc->id_exceeded) return;
-    const uint32_t stride = gridDim.x * TPB;
+    __shared__ ChrTables tables;
+    const bool in_lds = chr_tables_load(in, chr_entry, id_base, id_negmin, tables);
+    const uint32_t n = in.n_entries, stride = gridDim.x * TPB;
     for (uint32_t q = blockIdx.x * TPB + threadIdx.x; q < (n + 3u) / 4u; q += stride) {
         const uint32_t e0 = q * 4u;
-        uint32_t d[4], w[4];
-        if (e0 + 4u <= n) {
-            const uint4 dv = reinterpret_cast<const uint4 *>(dense)[q];
-            d[0] = dv.x, d[1] = dv.y, d[2] = dv.z, d[3] = dv.w;
-        } else {
+        uint32_t id[4], d[4], w[4];
+        load_id_quad(in, q, vec, id);
+        dense_id_quad(in, chr_entry, id_base, id_negmin, tables, in_lds, e0, id, d);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) d[u] = dense[min(e0 + (uint32_t)u, n - 1u)];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) w[u] = last[d[u]];
+        for (int u = 0; u < 4; ++u) w[u] = e0 + (uint32_t)u < n ? last[d[u]] : 0u;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t e = e0 + (uint32_t)u;
@@ -542,7 +586,7 @@ __global__ __launch_bounds__(TPB) void k_flag_count(const uint8_t *multi, uint32
 // exclusive offsets of the blocks (one workgroup; 3000 blocks on C3), the number of M entries
 constexpr int TPB_SCAN = 1024;
 __global__ __launch_bounds__(TPB_SCAN) void k_flag_scan(const uint32_t *block_sum, uint32_t n_blocks, uint32_t *block_off,
-                                                       uint32_t *m_idx_end, Scalars *sc) {
+                                                       uint32_t *total_out, Scalars *sc) {
     constexpr int TPB = TPB_SCAN;  // (this kernel's own)
     __shared__ uint32_t part[TPB / 64];
     __shared__ uint32_t carry;
@@ -567,23 +611,38 @@ __global__ __launch_bounds__(TPB_SCAN) void k_flag_scan(const uint32_t *block_su
         __syncthreads();
     }
     if (threadIdx.x == 0u) {
-        *m_idx_end = carry;  // m_idx[E]
+        *total_out = carry;  // the prefix of the closing chunk
         if (sc) sc->n_multi_id = carry;  // (null: the flagged entries' lists, pack_flag_lists)
     }
 }
-// m_idx = exclusive scan of the flags (entry e is an M entry iff m_idx[e + 1] != m_idx[e]) and the list of the M
-// entries; k_m_fields, once their number is known, copies them out as a compacted pileup of their own and finds
-// which of them holds its id's slot (the head its read is walked from)
+// The numbering of the M entries, in the form the flagged entries' lists have below: per 64-entry chunk its flags
+// (chunk_mask) and the M entries before it (chunk_pre) -- 12 bytes per 64 entries where the exclusive scan of the flags
+// as an array (until round 17) was 4 bytes per entry, written here and read back by k_bin_hist for every entry to
+// learn one bit. m_index(e) = M entries before entry e, for e <= E: both tables carry a closing chunk (no flags, all
+// M entries before it) behind the last block, which is where E falls when it is a multiple of kFlagBlock.
+struct MIndex {
+    const uint32_t *chunk_pre;
+    const unsigned long long *chunk_mask;
+    __device__ __forceinline__ uint32_t operator()(uint32_t e) const {
+        const uint32_t c = e >> 6, r = e & 63u;
+        return chunk_pre[c] + (uint32_t)__popcll(chunk_mask[c] & ((1ull << r) - 1ull));
+    }
+};
+// ... and the list of the M entries; k_m_fields, once their number is known, copies them out as a compacted pileup of
+// their own and finds which of them holds its id's slot (the head its read is walked from). A thread takes 16
+// consecutive flags, so four neighbouring lanes hold a chunk. (k_flag_scan writes the closing chunk's prefix.)
 __global__ __launch_bounds__(TPB) void k_compact_m(Raw in, const uint8_t *multi, const uint32_t *block_off,
-                                                  uint32_t *m_idx, uint32_t *m_entry) {
+                                                  uint32_t *chunk_pre, unsigned long long *chunk_mask,
+                                                  uint32_t *m_entry) {
     __shared__ uint32_t part[TPB / 64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint32_t e0 = blockIdx.x * kFlagBlock + threadIdx.x * 16u;
     const uint4 w = reinterpret_cast<const uint4 *>(multi + (size_t)blockIdx.x * kFlagBlock)[threadIdx.x];
     const uint32_t words[4] = {w.x, w.y, w.z, w.w};
-    uint32_t mine = 0;
+    uint32_t bits = 0;  // this thread's 16 flags
 #pragma unroll
-    for (int i = 0; i < 4; ++i) mine += (words[i] * 0x01010101u) >> 24;
+    for (int i = 0; i < 16; ++i) bits |= ((words[i >> 2] >> ((i & 3) * 8)) & 1u) << i;
+    const uint32_t mine = (uint32_t)__popc(bits);
     uint32_t incl = mine;
     for (int off = 1; off < 64; off <<= 1) {
         const uint32_t up = __shfl_up(incl, off);
@@ -593,31 +652,16 @@ __global__ __launch_bounds__(TPB) void k_compact_m(Raw in, const uint8_t *multi,
     __syncthreads();
     uint32_t j = block_off[blockIdx.x] + incl - mine;
     for (uint32_t w2 = 0; w2 < wv; ++w2) j += part[w2];
-    const uint32_t n = in.n_entries;
-    // m_idx leaves through LDS: a thread's 16 consecutive words, stored from registers, were 16 stores of 64 lanes
-    // 64 bytes apart (250 us on C3); rows of 17 words keep the transposing writes off one bank
-    __shared__ uint32_t tile[TPB * 17];
-    {
-        uint32_t jj = j;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            tile[threadIdx.x * 17u + (uint32_t)i] = jj;
-            jj += (words[i >> 2] >> ((i & 3) * 8)) & 1u;
-        }
+    unsigned long long m = (unsigned long long)bits << ((lane & 3u) * 16u);
+    m |= __shfl_xor(m, 1);
+    m |= __shfl_xor(m, 2);
+    if ((lane & 3u) == 0u) {  // (the padding behind the last entry holds no flags)
+        const uint32_t chunk = blockIdx.x * (kFlagBlock / 64u) + (threadIdx.x >> 2);
+        chunk_pre[chunk] = j;
+        chunk_mask[chunk] = m;
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const uint32_t i = (uint32_t)k * TPB + threadIdx.x;  // position in the block
-        const uint32_t e = blockIdx.x * kFlagBlock + i;
-        if (e < n) m_idx[e] = tile[(i >> 4) * 17u + (i & 15u)];
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const uint32_t e = e0 + (uint32_t)i;
-        if (e >= n) break;  // (the padding holds no flags)
-        if ((words[i >> 2] >> ((i & 3) * 8)) & 1u) m_entry[j++] = e;
-    }
+    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0u) chunk_mask[gridDim.x * (kFlagBlock / 64u)] = 0ull;
+    for (uint32_t b = bits; b; b &= b - 1u) m_entry[j++] = e0 + (uint32_t)__ffs((int)b) - 1u;
 }
 // The same count -> scan -> compact chain numbers the FLAGGED entries of the packed pileup (C_TAIL | C_MULTI in
 // entry32: the read was never flushed, or has further kept entries) for the correction of the sparse-loci pair
@@ -768,15 +812,22 @@ void flag_lists_from_masks(const FlagScratch &fs, const uint4 *entry, const uint
     flag_groups(fs, blk_off, n_off, grp, stream);
 }
 
-__global__ void k_m_fields(Raw in, const uint32_t *eloc, const uint32_t *dense, const uint32_t *last,
-                           const uint32_t *m_idx, const uint32_t *m_entry, uint32_t n_m, uint32_t *rid_m,
+// (the dense id once more, as in k_id_check; the locus of an M entry by a search over the loci's first entries -- the
+// M entries are ascending, so neighbouring threads search neighbouring places --: the only entries whose locus the
+// single-entry path ever looks up)
+__global__ void k_m_fields(Raw in, const uint32_t *chr_entry, const uint32_t *id_base, const uint32_t *id_negmin,
+                           const uint32_t *last, MIndex m_index, const uint32_t *m_entry, uint32_t n_m, uint32_t *rid_m,
                            uint32_t *idb_m, uint32_t *eloc_m, uint32_t *winner_m, uint32_t *count_m) {
+    __shared__ ChrTables tables;
+    const bool in_lds = chr_tables_load(in, chr_entry, id_base, id_negmin, tables);
     for (uint32_t j = blockIdx.x * TPB + threadIdx.x; j < n_m; j += gridDim.x * TPB) {
         const uint32_t e = m_entry[j];
-        rid_m[j] = in.read_ids[e];
+        const uint32_t id = in.read_ids[e];
+        rid_m[j] = id;
         idb_m[j] = in.id_base(e);
-        eloc_m[j] = eloc[e];
-        const uint32_t w = m_idx[last[dense[e]] - 1u];  // the M index of the entry that stands for this entry's id
+        eloc_m[j] = last_le<uint64_t>(in.locus_entry_off, in.n_loci + 1, (uint64_t)e);
+        const uint32_t d = dense_id(in, chr_entry, id_base, id_negmin, tables, in_lds, e, id);
+        const uint32_t w = m_index(last[d] - 1u);  // the M index of the entry that stands for this entry's id
         winner_m[j] = w;
         atomicAdd(&count_m[w], 1u);
     }
@@ -832,13 +883,14 @@ constexpr uint32_t kSingleTail = 4u;       // in the low word of a grouped S ent
 // them again at the appearance-rank scan (every S entry is the first and only entry of its read) and at
 // the binning.
 // Appearance rank of a pileup entry = marked entries before it. Single-entry fast path: every S entry is
-// marked, so rank(e) = e - (unmarked M entries before e) = e - unm[m_idx[e]], with unm the exclusive prefix of
+// marked, so rank(e) = e - (unmarked M entries before e) = e - unm[m_index(e)], with unm the exclusive prefix of
 // (1 - mark) over the M entries only -- a scan over 5 % of the pileup (C3) instead of one over all of it.
 // Otherwise the ranks are an array (the scan over the marks).
 struct Ranks {
-    const uint32_t *m_idx, *unm;  // fast path (unm != null)
-    const uint32_t *arank;        // or the array
-    __device__ __forceinline__ uint32_t operator()(uint32_t e) const { return unm ? e - unm[m_idx[e]] : arank[e]; }
+    MIndex m_index;
+    const uint32_t *unm;    // fast path (unm != null)
+    const uint32_t *arank;  // or the array
+    __device__ __forceinline__ uint32_t operator()(uint32_t e) const { return unm ? e - unm[m_index(e)] : arank[e]; }
 };
 struct UnmarkedM {  // input of the scan that gives unm
     const uint32_t *mark_m;
@@ -1175,7 +1227,7 @@ __global__ void k_keys2(Raw in, const uint32_t *sval, const unsigned long long *
 // counting path, kept entries by (cell block, locus). The entries of a locus are adjacent in the
 // pileup, so a wave counts a locus' entries per cell block in LDS -- global atomics would all hit the
 // handful of addresses of the loci in flight.
-// Single-entry fast path (m_idx != null): ONLY the S entries are counted, and their slots are made here -- (block,
+// Single-entry fast path (m_mask != null: the M entries' flags, 64 entries a word): ONLY the S entries are counted, and their slots are made here -- (block,
 // cell) from the group map, validated as k_keys2 does for the M entries -- with nothing of the read assembly:
 // k_keys2 adds the kept M entries afterwards, and k_bin_place knows an S entry's tail flag from its index.
 // (Measured and dropped, twice: this pass on a stream of its own beside the M entries' read assembly, which it does
@@ -1207,7 +1259,7 @@ __device__ __forceinline__ uint32_t tile_locus(const uint32_t *s_off, uint32_t l
 }
 
 __global__ __launch_bounds__(TPB) void k_bin_hist(Raw in, uint32_t nb, uint32_t TL, unsigned long long *__restrict__ entry_kc,
-                                                 const uint32_t *__restrict__ m_idx, uint32_t num_cells,
+                                                 const unsigned long long *__restrict__ m_mask, uint32_t num_cells,
                                                  uint32_t B_log2, uint32_t *__restrict__ blk_cnt, Scalars *sc,
                                                  uint32_t g2p_lds) {
     extern __shared__ uint32_t lds_hist[];  // nb * (TL + 1); then (g2p_lds) the group -> cell map as 16-bit words
@@ -1231,21 +1283,23 @@ __global__ __launch_bounds__(TPB) void k_bin_hist(Raw in, uint32_t nb, uint32_t 
         for (uint32_t base = eb + threadIdx.x; base < ee; base += TPB * U) {
             uint32_t slot[U];  // block of the entry, or none
             constexpr uint32_t kNone = 0xFFFFFFFFu;
-            if (m_idx) {
-                uint32_t m0[U], m1[U], ib[U], cell[U];
+            if (m_mask) {
+                unsigned long long mw[U];  // the flags of the entry's 64-entry chunk (a wave's entries touch two)
+                uint32_t ib[U], cell[U];
+                bool is_m[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const uint32_t e = base + (uint32_t)u * TPB;
                     const bool in_tile = e < ee;
-                    m0[u] = in_tile ? m_idx[e] : 0u;
-                    m1[u] = in_tile ? m_idx[e + 1] : 1u;  // (outside the tile: as an M entry, skipped)
+                    mw[u] = in_tile ? m_mask[e >> 6] : ~0ull;  // (outside the tile: as an M entry, skipped)
                     ib[u] = in_tile ? in.id_base(e) : 0u;
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const uint32_t group = ib[u] >> 2;
                     cell[u] = 0;
-                    if (m1[u] == m0[u]) {
+                    is_m[u] = (mw[u] >> ((base + (uint32_t)u * TPB) & 63u)) & 1ull;
+                    if (!is_m[u]) {
                         if (group >= in.n_groups) sc->error = 1;
                         else cell[u] = g2p_lds ? (uint32_t)s_g2p[group] : in.g2p[group];
                     }
@@ -1253,7 +1307,7 @@ __global__ __launch_bounds__(TPB) void k_bin_hist(Raw in, uint32_t nb, uint32_t 
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     slot[u] = kNone;
-                    if (m1[u] != m0[u]) continue;  // an M entry: k_keys2
+                    if (is_m[u]) continue;  // an M entry: k_keys2
                     const uint32_t e = base + (uint32_t)u * TPB;
                     uint32_t c = cell[u];
                     if (c >= num_cells) {
@@ -1941,7 +1995,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     // worst-case block count (64-cell blocks) for buffers sized before the tile size is chosen
     const size_t n_off_max = (size_t)((num_cells + 63) / 64) * ((size_t)L + 1);
     enum { KEY_A, KEY_B, VAL_A, VAL_B, ELOC, WORK_A, WORK_B, RUNS, CUB, TMP, MISC, BIN, ENTRY_KC,
-           M_IDX, M_ENTRY, RID_M, IDB_M, ELOC_M, DENSE_M, MARK_M, ARANK_M, DUPF, SEGS };
+           M_CHUNKS, M_ENTRY, RID_M, IDB_M, ELOC_M, DENSE_M, MARK_M, ARANK_M, DUPF, SEGS };
     auto &S = pk.scratch;
     // the counting scheme for read ids needs a table over the id space
     const size_t id_space_cap = std::min<size_t>((size_t)kIdSpaceFactor * E + 1024, (size_t)1 << 30);
@@ -1951,8 +2005,8 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
 
     // ---- buffers (sized up front: a re-allocation in mid-pipeline would synchronise) -----------
     // MISC: Scalars | id_max[C] | id_negmin[C] | id_base[C+1] | rbeg[C+1] | flushed[C] | cnt[L] |
-    //       locus_chr[L] | locus_rel[L] | flush_loci[L] | flush_count[C] | tail_begin[C]
-    HIP_OK(S[MISC].ensure(sizeof(Scalars) + sizeof(uint32_t) * ((size_t)7 * C + 4 + (size_t)4 * L) + 64));
+    //       locus_chr[L] | locus_rel[L] | flush_loci[L] | flush_count[C] | tail_begin[C] | chr_entry[C+1]
+    HIP_OK(S[MISC].ensure(sizeof(Scalars) + sizeof(uint32_t) * ((size_t)8 * C + 8 + (size_t)4 * L) + 64));
     Scalars *sc = S[MISC].as<Scalars>();
     uint32_t *id_max = reinterpret_cast<uint32_t *>(sc + 1);
     uint32_t *id_negmin = id_max + C;
@@ -1963,6 +2017,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     uint32_t *locus_chr = cnt + L, *locus_rel = locus_chr + L;
     uint32_t *flush_loci = locus_rel + L, *flush_count = flush_loci + L;
     uint32_t *tail_begin = flush_count + C;
+    uint32_t *chr_entry = tail_begin + C;  // first entry of every chromosome, and the number of entries (k_id_bases)
     // KEY_A: sort keys in, later mark[E+1] | arank[E+1], later the per-(block, locus) counts
     // (marks and appearance ranks, 2 (E + 1) words, with the (block, locus) counts behind them: the ranks are
     // still read when the counts are written, k_bin_hist)
@@ -1971,8 +2026,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     HIP_OK(S[KEY_B].ensure((size_t)E * 8));
     HIP_OK(S[VAL_A].ensure(std::max<size_t>(E, 64) * 4));
     HIP_OK(S[VAL_B].ensure((size_t)E * 4));
-    // ELOC: entry -> locus (the pileup's entries: the binning passes read it to the end)
-    HIP_OK(S[ELOC].ensure((size_t)E * 4 + 16));
+    // (ELOC, entry -> locus: sized where k_entry_locus is launched -- the single-entry path has no such table)
     HIP_OK(S[WORK_A].ensure(((size_t)E + 1) * 4));
     HIP_OK(S[WORK_B].ensure(((size_t)2 * E + 2) * 4));
     // RUNS: run_start[R+1] | run_rank[R] | starts_by_rank[R], R <= E
@@ -1985,7 +2039,6 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     HIP_OK(S[BIN].ensure((size_t)E * 24 + ((size_t)num_cells + 130) * 8 + 64));
     unsigned long long *key_a = S[KEY_A].as<unsigned long long>(), *key_b = S[KEY_B].as<unsigned long long>();
     uint32_t *val_a = S[VAL_A].as<uint32_t>(), *val_b = S[VAL_B].as<uint32_t>();
-    uint32_t *eloc = S[ELOC].as<uint32_t>();
     {
         size_t need = 0, most = 0;
         HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, key_a, key_b, val_a, val_b, (int)E, 0, 64, stream));
@@ -2027,15 +2080,15 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     // ---- 1: entries grouped by (chromosome, read id), pileup order inside a read ---------------
     const HostTrace trace;
     trace.mark("begin");
-    hipLaunchKernelGGL(k_entry_locus, dim3(blocks_for((uint64_t)L * 64)), dim3(TPB), 0, stream, raw, eloc, sc);
-    hipLaunchKernelGGL(k_id_range, dim3(std::min<uint32_t>(256, (E + 4095) / 4096)), dim3(TPB), 0, stream, raw,
-                       eloc, id_max, id_negmin, (reinterpret_cast<uintptr_t>(raw.read_ids) & 15u) == 0 ? 1 : 0);
+    const int ids_aligned = (reinterpret_cast<uintptr_t>(raw.read_ids) & 15u) == 0 ? 1 : 0;
+    hipLaunchKernelGGL(k_id_range, dim3(std::min<uint32_t>(256, (E + 4095) / 4096)), dim3(TPB), 0, stream, raw, id_max,
+                       id_negmin, ids_aligned, sc);
     // The size of the id space decides between the counting scheme and the radix sort and sizes the
     // histogram. A handle that has packed before assumes the size of the previous call and does not wait
     // (k_id_bases raises Scalars::id_exceeded if that was too small: the attempt is then void and
     // repeated with the read-back).
     const bool assume = !force_radix && !no_assumptions && pk.id_space_hint && pk.id_space_hint <= id_space_cap;
-    hipLaunchKernelGGL(k_id_bases, dim3(1), dim3(64), 0, stream, C, id_max, id_negmin, id_base,
+    hipLaunchKernelGGL(k_id_bases, dim3(1), dim3(64), 0, stream, raw, id_max, id_negmin, id_base, chr_entry,
                        (unsigned long long)(assume ? pk.id_space_hint : 0), sc);
     Scalars hsc;
     std::memset(&hsc, 0, sizeof(hsc));
@@ -2051,7 +2104,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     uint32_t *work_a = S[WORK_A].as<uint32_t>(), *work_b = S[WORK_B].as<uint32_t>();
     // The single-entry fast path (counting scheme only; SECEDO_PACK_SPLIT=0 turns it off): `sub` is the pileup
     // the read assembly of stages 1-4 sees -- the whole one, or the compacted entries of the ids that occur more
-    // than once (n_m of them; m_entry maps them back, m_idx is the exclusive scan of their flags).
+    // than once (n_m of them; m_entry maps them back, m_index numbers them: the M entries before an entry).
     static const bool split_allowed = [] {
         const char *e = std::getenv("SECEDO_PACK_SPLIT");
         return !(e && std::atoi(e) == 0);
@@ -2061,26 +2114,46 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
         pk.calls_without_split = 0;
     }
     bool split_singles = counting && split_allowed && pk.split_pays;
+    // The entry -> locus table serves the general counting path and the radix route. The single-entry path has none
+    // (the chromosome of an entry follows from its index, the locus is wanted of the M entries only: k_m_fields), so
+    // the table is made here where the route is not tried, and behind read-back 1b where it is given up.
+    uint32_t *eloc = nullptr;
+    auto make_entry_locus = [&]() -> std::string {
+        HIP_OK(S[ELOC].ensure((size_t)E * 4 + 16));
+        eloc = S[ELOC].as<uint32_t>();
+        hipLaunchKernelGGL(k_entry_locus, dim3(blocks_for((uint64_t)L * 64)), dim3(TPB), 0, stream, raw, eloc, sc);
+        return std::string();
+    };
+    if (!split_singles) {
+        const std::string err = make_entry_locus();
+        if (!err.empty()) return err;
+    }
     Raw sub = raw;
-    const uint32_t *sub_eloc = eloc;
+    const uint32_t *sub_eloc = nullptr;
     uint32_t n_m = E;
-    uint32_t *m_idx = nullptr, *m_entry = nullptr;
+    MIndex m_index{nullptr, nullptr};
+    uint32_t *m_entry = nullptr;
     if (counting) {
         uint32_t *hist = work_a, *id_off = work_b, *grouped = val_a;
-        uint32_t *dense = S[KEY_A].as<uint32_t>();  // the radix path's unsorted keys live here
+        uint32_t *dense = S[KEY_A].as<uint32_t>();  // (general path; the radix path's unsorted keys live here)
         if (!split_singles) HIP_OK(hipMemsetAsync(hist, 0, (id_space + 1) * 4, stream));
         if (split_singles) {
             // which ids repeat (k_id_store, k_id_check), the entries of those as a compacted pileup of their own
             const size_t padded = ((size_t)E + kFlagBlock - 1) / kFlagBlock * kFlagBlock + 16;
             const uint32_t n_flag_blocks = (uint32_t)((padded - 16) / kFlagBlock);
-            HIP_OK(S[M_IDX].ensure(((size_t)E + 2) * 4));
-            m_idx = S[M_IDX].as<uint32_t>();
+            // the M entries' numbering: a mask and a prefix per 64-entry chunk, and the closing chunk
+            const size_t n_chunks = (size_t)n_flag_blocks * (kFlagBlock / 64) + 1;
+            HIP_OK(S[M_CHUNKS].ensure(n_chunks * 12 + 16));
+            unsigned long long *chunk_mask = S[M_CHUNKS].as<unsigned long long>();
+            uint32_t *chunk_pre = reinterpret_cast<uint32_t *>(chunk_mask + n_chunks);
+            m_index = MIndex{chunk_pre, chunk_mask};
             HIP_OK(S[MARK_M].ensure(std::max(((size_t)E + 2) * 4, padded)));
             uint8_t *multi = S[MARK_M].as<uint8_t>();  // (the marks of the M entries come later: k_dup_mark)
             HIP_OK(hipMemsetAsync(multi, 0, padded, stream));
-            hipLaunchKernelGGL(k_id_store, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, raw, eloc, id_base, id_negmin,
-                               sc, dense, hist, (reinterpret_cast<uintptr_t>(raw.read_ids) & 15u) == 0 ? 1 : 0);
-            hipLaunchKernelGGL(k_id_check, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, E, sc, dense, hist, multi);
+            hipLaunchKernelGGL(k_id_store, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, raw, chr_entry, id_base,
+                               id_negmin, sc, hist, ids_aligned);
+            hipLaunchKernelGGL(k_id_check, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, raw, chr_entry, id_base,
+                               id_negmin, sc, hist, multi, ids_aligned);
             for (int a : {M_ENTRY, RID_M, IDB_M, ELOC_M, ARANK_M}) HIP_OK(S[a].ensure((size_t)E * 4 + 16));
             // (the reads of the M entries, at most half of all entries:
             // count[n_m+1] | goff[n_m+1] | winner | begin | len | members)
@@ -2088,9 +2161,10 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
             m_entry = S[M_ENTRY].as<uint32_t>();
             uint32_t *block_sum = grouped, *block_off = grouped + n_flag_blocks + 1;  // (VAL_A: 2 words per 4096 entries)
             hipLaunchKernelGGL(k_flag_count, dim3(n_flag_blocks), dim3(TPB), 0, stream, multi, block_sum);
-            hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, block_sum, n_flag_blocks, block_off, m_idx + E,
-                               sc);
-            hipLaunchKernelGGL(k_compact_m, dim3(n_flag_blocks), dim3(TPB), 0, stream, raw, multi, block_off, m_idx, m_entry);
+            hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, block_sum, n_flag_blocks, block_off,
+                               chunk_pre + (n_chunks - 1), sc);
+            hipLaunchKernelGGL(k_compact_m, dim3(n_flag_blocks), dim3(TPB), 0, stream, raw, multi, block_off, chunk_pre,
+                               chunk_mask, m_entry);
             // read-back 1b: how many entries take the general path (sizes every launch over them)
             HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));
             if (hsc.error == 3) return "positions must be strictly increasing within a chromosome";
@@ -2105,10 +2179,12 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
                 pk.split_pays = false;
                 pk.calls_without_split = 0;
                 n_m = E;
-                m_idx = nullptr;
+                m_index = MIndex{nullptr, nullptr};
                 m_entry = nullptr;
-                // (the id slots hold entry numbers, the general path wants counts)
+                // (the id slots hold entry numbers, the general path wants counts -- and the entry -> locus table)
                 HIP_OK(hipMemsetAsync(hist, 0, (id_space + 1) * 4, stream));
+                const std::string err = make_entry_locus();
+                if (!err.empty()) return err;
             }
         }
         if (split_singles) {
@@ -2123,9 +2199,9 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
                 uint32_t *count_m = S[DENSE_M].as<uint32_t>(), *goff = count_m + n_m + 1, *winner_m = goff + n_m + 1;
                 uint32_t *g_begin = winner_m + n_m, *g_len = g_begin + n_m, *members = g_len + n_m;
                 HIP_OK(hipMemsetAsync(count_m, 0, ((size_t)n_m + 1) * 4, stream));
-                hipLaunchKernelGGL(k_m_fields, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, raw, eloc, dense, hist, m_idx, m_entry,
-                                   n_m, S[RID_M].as<uint32_t>(), S[IDB_M].as<uint32_t>(), S[ELOC_M].as<uint32_t>(), winner_m,
-                                   count_m);
+                hipLaunchKernelGGL(k_m_fields, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, raw, chr_entry, id_base, id_negmin,
+                                   hist, m_index, m_entry, n_m, S[RID_M].as<uint32_t>(), S[IDB_M].as<uint32_t>(),
+                                   S[ELOC_M].as<uint32_t>(), winner_m, count_m);
                 cub_cap = S[CUB].bytes;
                 HIP_OK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, count_m, goff, (int)n_m + 1, stream));
                 hipLaunchKernelGGL(k_group_scatter, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, winner_m, n_m, goff, count_m,
@@ -2153,6 +2229,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     }
     const unsigned long long *skey = key_b;
     const uint32_t *sval = val_b;
+    pk.used_single_entry = split_singles;
 
     // ---- 2-4: duplicate rule, reads = runs of equal key, per-read lists, appearance ranks ------
     // (the number of reads R stays on the device until read-back 2; buffers indexed by read are laid
@@ -2182,7 +2259,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     // side stream, next to the grouping of the kept entries.
     // (`sub` / n_m: the entries that go through the read assembly -- all of them, or with the single-entry
     // fast path those of the ids that occur more than once; marks and ranks are always those of the whole pileup)
-    const Ranks ranks{split_singles ? m_idx : nullptr, split_singles ? arank : nullptr, arank};
+    const Ranks ranks{m_index, split_singles ? arank : nullptr, arank};
     auto build_reads = [&]() -> std::string {
         uint32_t *mark_sub = split_singles ? S[MARK_M].as<uint32_t>() : mark;
         if (n_m) {
@@ -2384,7 +2461,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
         const size_t g2p_bytes = ((size_t)in.n_groups * 2 + 15) / 16 * 16;
         const bool g2p_lds = g2p_allowed && num_cells <= 0xFFFFu && lds + g2p_bytes <= 49152;
         hipLaunchKernelGGL(k_bin_hist, dim3(g2p_lds ? std::min<uint32_t>(locus_grid, 1024) : locus_grid), dim3(TPB),
-                           lds + (g2p_lds ? g2p_bytes : 0), stream, raw, nb, TL, entry_kc, m_idx, num_cells, B_log2, blk_cnt,
+                           lds + (g2p_lds ? g2p_bytes : 0), stream, raw, nb, TL, entry_kc, m_index.chunk_mask, num_cells, B_log2, blk_cnt,
                            sc, g2p_lds ? 1u : 0u);
     }
     if (n_m)
@@ -2548,6 +2625,7 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
                                hipStream_t stream, DevicePacked *out, bool *need_host) {
     *need_host = false;
     out->flag_lists_built = false;
+    out->used_single_entry = false;
     if ((in.id_base16 != nullptr) == (in.id_base32 != nullptr))
         return "exactly one of id_base16 / id_base32 must be given";
     if (num_threads == 0) return "num_threads must be positive";

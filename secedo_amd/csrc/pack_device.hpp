@@ -79,6 +79,8 @@ struct DevicePacked {
     // entries in multi-entry reads finishes without it, and the handle's next calls do not try (every 16th does)
     bool split_pays = true;
     uint32_t calls_without_split = 0;
+    // ... and whether the packing that has just returned took it to the end (secedo_simmat_used_single_entry_path)
+    bool used_single_entry = false;
     // side stream for the branch of the pipeline nothing else waits for until the final gather
     // (completed counts + flush chain); created on first use
     hipStream_t side = nullptr;

@@ -393,6 +393,9 @@ int secedo_simmat_set_packing(secedo_simmat_t *h, int mode) {
 }
 
 int secedo_simmat_used_device_packing(const secedo_simmat_t *h) { return h ? h->used_device_packing : 0; }
+int secedo_simmat_used_single_entry_path(const secedo_simmat_t *h) {
+    return h && h->used_device_packing && h->pk.used_single_entry ? 1 : 0;
+}
 
 int secedo_simmat_prepare(secedo_simmat_t *h, uint32_t num_cells, uint32_t max_fragment_length,
                           uint32_t num_threads, uint32_t block_cells, void *stream) {

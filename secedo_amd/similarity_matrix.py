@@ -152,6 +152,11 @@ class SimilarityMatrixPlan:
     def used_device_packing(self) -> bool:
         return bool(_lib.lib().secedo_simmat_used_device_packing(self._h))
 
+    @property
+    def used_single_entry_path(self) -> bool:
+        """The last prepare packed on the GPU and its single-entry path ran to the end (secedo_simmat.h)."""
+        return bool(_lib.lib().secedo_simmat_used_single_entry_path(self._h))
+
     def upload(self, pos_data, group_id_to_pos=None, num_cells=None):
         """Raw flat pileup -> HBM (torch tensors); returns the resident pileup for prepare_resident."""
         p = _as_flat(pos_data)
