@@ -257,7 +257,7 @@ int secedo_simmat_last_accumulate_ms(secedo_simmat_t *handle, float *ms);
 int secedo_simmat_last_pair_kernel_ms(secedo_simmat_t *handle, float *ms);
 /* Which pair kernel the prepared pileup runs: "accumulate_counts" (sparse loci: count tile, corrected in its own
  * epilogue or by correct_tiles after it), "accumulate_masks" (clustered loci: window masks staged, followed by wide_pairs when reads reach
- * beyond their windows) or "accumulate_tiles" (deep pileups, and the A/B switches). Static string. */
+ * beyond their windows) or "accumulate_tiles" (deep pileups). Static string. */
 const char *secedo_simmat_pair_kernel(const secedo_simmat_t *handle);
 /* 1 when the last accumulate() corrected its tiles in the epilogue of accumulate_counts (one workgroup per tile),
  * 0 when correct_tiles ran after it or another pair kernel ran. */

@@ -275,11 +275,10 @@ secedo::AccumulateArgs base_args(const secedo_simmat *h, const TileSet &t, int64
 }
 
 // accumulate_masks pairs from the 8-locus windows alone; the entries of reads that reach beyond them are
-// listed per cell block once per prepare for its second kernel (SECEDO_MASKS_KERNEL=0: accumulate_tiles)
+// listed per cell block once per prepare for its second kernel
 int prepare_masks_lists(secedo_simmat *h, hipStream_t s, secedo::AccumulateArgs *a) {
-    const bool allowed = masks_kernel_allowed(h);
     const size_t ne = (size_t)h->pk.num_entries;
-    if (allowed && !h->wide_known) {
+    if (!h->wide_known) {
         // how many there are came with the packing's last read-back (DevicePacked::n_wide): count per block, scan
         // and fill are enqueued behind each other, nothing waits for the device here
         const uint32_t nb = h->pk.num_blocks;
@@ -297,13 +296,10 @@ int prepare_masks_lists(secedo_simmat *h, hipStream_t s, secedo::AccumulateArgs 
                                        h->mk_words.as<uint32_t>() + ne, h->mk_words.as<uint32_t>() + 2 * ne, s));
         h->wide_known = true;
     }
-    if (allowed) {
-        a->mk_y = h->mk_words.as<uint32_t>();
-        a->mk_xcol = a->mk_y + ne;
-        a->mk_xrow = a->mk_y + 2 * ne;
-    }
-    a->masks_kernel = allowed;
-    if (allowed && h->n_wide) {
+    a->mk_y = h->mk_words.as<uint32_t>();
+    a->mk_xcol = a->mk_y + ne;
+    a->mk_xrow = a->mk_y + 2 * ne;
+    if (h->n_wide) {
         a->wide_off = h->wide_tab.as<uint32_t>() + h->pk.num_blocks;
         a->wide_list = h->wide_list.as<uint32_t>();
     }
@@ -399,13 +395,6 @@ int list_tiles(const uint32_t *tile_ids, uint32_t n_tile_ids, TileSet *t) {
 }
 
 }  // namespace
-
-bool secedo::host::masks_kernel_allowed(const secedo_simmat *h) {
-    static const bool allowed_env = env_enabled("SECEDO_MASKS_KERNEL");
-    // (the list's scan is one workgroup: beyond 1024 cell blocks -- more than num_cells allows today -- the pileup
-    // keeps to accumulate_tiles instead of failing the call)
-    return allowed_env && h->pk.stage_masks && h->pk.block_cells == 64 && h->pk.num_blocks <= 1024u;
-}
 
 extern "C" {
 

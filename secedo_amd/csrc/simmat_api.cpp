@@ -581,7 +581,7 @@ int secedo_simmat_last_accumulate_ms(secedo_simmat_t *h, float *ms) {
 const char *secedo_simmat_pair_kernel(const secedo_simmat_t *h) {
     if (!h || !h->prepared) return "";
     if (h->pk.count_tile && !h->pk.stage_masks) return "accumulate_counts";
-    return masks_kernel_allowed(h) ? "accumulate_masks" : "accumulate_tiles";
+    return h->pk.stage_masks && h->pk.block_cells == 64 ? "accumulate_masks" : "accumulate_tiles";
 }
 
 int secedo_simmat_last_correction_fused(const secedo_simmat_t *h) { return h && h->last_fused ? 1 : 0; }

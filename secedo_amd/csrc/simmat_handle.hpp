@@ -254,9 +254,6 @@ int set_pileup_view(secedo_simmat *h, const FlatPileupView &view);
 int finalize_mode(secedo_simmat *h, int mode, const int64_t *d_acc, uint32_t row_begin, uint32_t row_end,
                   double *d_out, void *stream, bool keep_max = false);  // simmat_api.cpp
 
-// accumulate_masks may run on this packed pileup (SECEDO_MASKS_KERNEL=0: never; read once per process)
-bool masks_kernel_allowed(const secedo_simmat *h);  // simmat_accumulate.cpp
-
 // ---- simmat_one_shot.cpp
 constexpr int kMaxLanes = 16;
 // d_src (device) -> dst (pageable host memory) through page-locked ring `ring` with `threads` copying threads

@@ -135,56 +135,25 @@ __device__ __noinline__ long long pair_value_full(const SlowPathArgs *sp, uint32
     return slow_pair(sp, entry_read[g1], entry_read[g2], A1.w, A1.x & 0xFFFFu, A2.x & 0xFFFFu);
 }
 
-// Capacity of the per-wave list of deferred joint pairs (see accumulate_tiles): 192 where the LDS
-// budget allows, else 0 (the batch is rescanned for its joint pairs instead).
-template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS>
-constexpr int joint_list_cap() {
-    if (MASKS) return 0;
-    constexpr size_t fixed = (size_t)B * B * 8 + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2 + 16
-            + (size_t)(THREADS / 64) * ((size_t)HCAP + 64 * 8);
-    return fixed + (size_t)(THREADS / 64) * 192 * 10 <= 160 * 1024 ? 192 : 0;
-}
+// ------------------------------------------------------------------------------------------------
+// What the three pair kernels (accumulate_tiles, accumulate_counts, accumulate_masks) share: a workgroup owns one
+// tile for a share of its row-side entries and walks the locus ranges that share touches. (All of it is inlined
+// into the kernels: the by-value argument block stays in SGPRs, see SlowPathArgs.)
+// ------------------------------------------------------------------------------------------------
 
-// MASKS:  the 8-locus window masks are staged too, so joint (x_s, x_d) terms of multi-locus read
-//         pairs are evaluated from LDS (clustered loci); otherwise such pairs go through the full
-//         entries in HBM (they are rare when loci are sparse).
-// HCAP:   size of the per-wave strip in which a batch's pairs are flattened over the lanes (below);
-//         deeper batches are flattened HCAP pairs at a time.
-//
-// Work distribution. A workgroup walks its locus ranges; per range the column side (block J) is
-// staged in LDS. Each wave then pulls batches of 64 consecutive row-side entries (block I). A lane's
-// entry pairs with the c = j1 - j0 column entries of its locus, and c varies from lane to lane, so
-// the batch's pairs are FLATTENED: a wave prefix sum over c gives every entry a slice [P, P + c) of
-// the batch's T pairs, the slice is filled with the owning lane's number in a per-wave LDS strip,
-// and pair p is then handled by lane p % 64 -- every lane busy until the batch's last 64 pairs.
-template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS>
-__global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs a) {
-    constexpr size_t TILE_BYTES = (size_t)B * B * 8;
-    constexpr int WAVES = THREADS / 64;
-    constexpr int JPT = (CAPJ + THREADS - 1) / THREADS;      // staged column entries per thread
-    constexpr int OPT = (CAPL + 1 + THREADS - 1) / THREADS;  // staged offsets per thread
-    constexpr int MCAP = joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP, MASKS>();
-    constexpr size_t WAVE_BYTES = (size_t)HCAP + 64 * 8 + (MASKS ? 64 * 4 : 0) + (size_t)MCAP * 10;
-
-    // LDS: [ tile | sJ CAPJ u16 | sOff CAPL+2 u16 | sJm CAPJ u32, sLut (MASKS) | s_next | per wave:
-    //        owner HCAP u8, wrec 64 x {entry, j0 - P}, wm 64 u32 (MASKS),
-    //        mlist MCAP x {g1, g2}, mcell MCAP u16 (sparse-loci variants: deferred joint pairs) ]
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    unsigned long long *tile64 = reinterpret_cast<unsigned long long *>(lds_raw);
-    uint16_t *sJ = reinterpret_cast<uint16_t *>(lds_raw + TILE_BYTES);
-    uint16_t *sOff = sJ + CAPJ;
-    uint32_t *sJm = reinterpret_cast<uint32_t *>(sOff + CAPL + 2);
-    long long *sLut = reinterpret_cast<long long *>(sJm + (MASKS ? CAPJ : 0));
-    uint32_t *s_next = reinterpret_cast<uint32_t *>(sLut + (MASKS ? SLUT_DIM * SLUT_DIM : 0));
-    unsigned char *wave_base = reinterpret_cast<unsigned char *>(s_next + 4) + (threadIdx.x >> 6) * WAVE_BYTES;
-    unsigned char *owner = wave_base;
-    uint2 *wrec = reinterpret_cast<uint2 *>(wave_base + HCAP);
-    uint32_t *wm = reinterpret_cast<uint32_t *>(wave_base + HCAP + 64 * 8);
-    uint2 *mlist = reinterpret_cast<uint2 *>(wave_base + HCAP + 64 * 8);  // MASKS has no list
-    uint16_t *mcell = reinterpret_cast<uint16_t *>(wave_base + HCAP + 64 * 8 + (size_t)MCAP * 8);
-
-    // workgroup -> (tile, chunk of the tile's locus ranges); diagonal tiles hold half the pairs and
-    // get half the chunks, so that all workgroups of a launch carry about the same work
+// workgroup -> (tile, chunk of the tile's locus ranges); diagonal tiles hold half the pairs and
+// get half the chunks, so that all workgroups of a launch carry about the same work
+struct TileChunk {
+    uint32_t t;                   // the tile, in the matrix
+    bool diag;
+    uint32_t lane;                // of the thread (taken here, where the kernels took it: three instances came out
+                                  // with other register counts when the cursor computed it for itself)
+    const uint32_t *offI, *offJ;  // entry offsets per locus of the row and the column block
+    uint32_t r_begin, r_end;      // the chunk's locus ranges ...
+    uint32_t row_begin, row_end;  // ... and its row-side entries in the first and the last of them
+};
+template <int THREADS>
+__device__ __forceinline__ TileChunk tile_chunk(const AccumulateArgs &a) {
     const uint32_t t_local = a.wg_tile[blockIdx.x];
     const uint32_t t = a.tile_ids ? a.tile_ids[t_local] : a.tile_begin + t_local;
     const uint32_t chunk = blockIdx.x - a.tile_wg_begin[t_local];
@@ -221,12 +190,163 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
         row_begin = __builtin_amdgcn_readfirstlane(row_begin);
         row_end = __builtin_amdgcn_readfirstlane(row_end);
     }
+    return TileChunk{t, diag, lane, offI, offJ, r_begin, r_end, row_begin, row_end};
+}
+
+// Range boundaries run ahead of the pairing so that their two dependent reads (locus span -> entry
+// offsets of the two blocks) are never waited for. One register holds them all, a value per lane:
+// lanes 0-3 the offsets of the next range (row begin, row end, column begin, column end), lanes 4-5
+// the locus span of the range after it; it is loaded while the current range is paired.
+struct RangeCursor {
+    uint32_t q_la = 0, q_lb = 0;  // locus span of the range `ahead` holds the offsets of
+    uint32_t ahead = 0;
+    // the range advance() stepped to: its loci [la, lb), this chunk's part [ib, ie) of its row side (dsh entries
+    // behind the range's first), its column side [jb, je)
+    uint32_t la = 0, lb = 0, ib = 0, ie = 0, jb = 0, je = 0, dsh = 0;
+
+    __device__ __forceinline__ void fetch_ahead(const AccumulateArgs &a, const TileChunk &c, uint32_t r) {
+        const uint32_t lane = c.lane;  // r: the range with span (q_la, q_lb)
+        const uint32_t *src = lane == 0u ? c.offI + q_la : lane == 1u ? c.offI + q_lb : lane == 2u ? c.offJ + q_la
+                            : lane == 3u ? c.offJ + q_lb : a.range_off + (r + lane - 3u);  // lanes 4, 5: r + 1, r + 2
+        ahead = 0u;
+        if (lane < 4u || (lane < 6u && r + 1u < c.r_end)) ahead = *src;
+    }
+    // before the first advance(): the span of the chunk's first range, and its offsets on their way
+    __device__ __forceinline__ void prime(const AccumulateArgs &a, const TileChunk &c) {
+        q_la = __builtin_amdgcn_readfirstlane(a.range_off[c.r_begin]);
+        q_lb = __builtin_amdgcn_readfirstlane(a.range_off[c.r_begin + 1u]);
+        fetch_ahead(a, c, c.r_begin);
+    }
+    // step to range r (whose offsets `ahead` holds) and send for the offsets of r + 1
+    __device__ __forceinline__ void advance(const AccumulateArgs &a, const TileChunk &c, uint32_t r) {
+        la = q_la;
+        lb = q_lb;
+        const uint32_t range_ib = __builtin_amdgcn_readlane(ahead, 0);
+        ib = max(range_ib, c.row_begin);  // this chunk's part of the range's row side
+        ie = max(ib, min((uint32_t)__builtin_amdgcn_readlane(ahead, 1), c.row_end));
+        dsh = ib - range_ib;
+        jb = __builtin_amdgcn_readlane(ahead, 2);
+        je = __builtin_amdgcn_readlane(ahead, 3);
+        q_la = __builtin_amdgcn_readlane(ahead, 4);
+        q_lb = __builtin_amdgcn_readlane(ahead, 5);
+        if (r + 1u < c.r_end) fetch_ahead(a, c, r + 1u);
+    }
+};
+
+// Work counters: wave reduction, then one atomic pair per workgroup -- thousands of same-address atomics at the
+// end of a launch queue up in the memory system and delay the workgroups still running. red: 2 * WAVES words of
+// LDS nobody uses any more (the staging area is free by then).
+template <int WAVES>
+__device__ __forceinline__ void add_work_counters(unsigned long long *counters, unsigned long long *red,
+                                                  unsigned long long n_updates, unsigned long long n_pairs) {
+    const uint32_t tid = threadIdx.x;
+    for (int off = 32; off > 0; off >>= 1) {
+        n_updates += __shfl_down(n_updates, off);
+        n_pairs += __shfl_down(n_pairs, off);
+    }
+    if ((tid & 63u) == 0u) {
+        red[(tid >> 6) * 2] = n_updates;
+        red[(tid >> 6) * 2 + 1] = n_pairs;
+    }
+    __syncthreads();
+    if (tid == 0u) {
+        unsigned long long u = 0, q = 0;
+        for (int w = 0; w < WAVES; ++w) {
+            u += red[w * 2];
+            q += red[w * 2 + 1];
+        }
+        if (u | q) {
+            atomicAdd(&counters[0], u);
+            atomicAdd(&counters[1], q);
+        }
+    }
+}
+
+// A locus range that does not fit the staging buffers (a single very deep locus), rows [ib, ie) of it: paired
+// straight from HBM/L2 with the compact entries, straight into the tile's accumulator `dst` in HBM; the full
+// entries are read (and exist) only for pairs of two multi-locus reads. SKIP_WIDE (accumulate_masks): pairs with
+// a read that reaches beyond its windows are wide_pairs'. upd / skipped: this lane's incidences, and those of
+// them another locus owns.
+template <int B, int THREADS, bool SKIP_WIDE>
+__device__ __forceinline__ void pair_range_from_hbm(const AccumulateArgs &a, const TileChunk &c, uint32_t la, uint32_t ib,
+                                                    uint32_t ie, unsigned long long *dst, long long d10, long long d01,
+                                                    uint32_t &upd, uint32_t &skipped) {
+    for (uint32_t e1 = ib + threadIdx.x; e1 < ie; e1 += THREADS) {
+        const uint32_t r1 = a.entry32[e1];
+        const uint32_t l = la + (r1 >> 16);
+        const uint32_t j0 = c.diag ? e1 + 1 : c.offJ[l];
+        const uint32_t j1 = c.offJ[l + 1];
+        const uint32_t row = (r1 & C_CELL) * B;
+        for (uint32_t e2 = j0; e2 < j1; ++e2) {
+            const uint32_t r2 = a.entry32[e2];
+            const uint32_t x = r1 ^ r2, both = r1 & r2;
+            if (c.diag && (x & C_CELL) == 0u) continue;       // same cell (:215)
+            if (both & C_TAIL) continue;                      // both never flushed (:407-408)
+            if (SKIP_WIDE && ((r1 | r2) & C_WIDE)) continue;  // wide_pairs
+            ++upd;
+            long long v = (x & (3u << C_BASE_SHIFT)) ? d01 : d10;
+            if (both & C_MULTI) {
+                v = pair_value_full(a.slow, e1, e2);
+                if (v == NO_PAIR) {
+                    ++skipped;
+                    continue;
+                }
+            }
+            atomicAdd(&dst[row + (r2 & C_CELL)], (unsigned long long)v);
+        }
+    }
+}
+
+// Capacity of the per-wave list of deferred joint pairs (see accumulate_tiles): 192 where the LDS
+// budget allows, else 0 (the batch is rescanned for its joint pairs instead).
+template <int B, int THREADS, int CAPJ, int CAPL, int HCAP>
+constexpr int joint_list_cap() {
+    constexpr size_t fixed = (size_t)B * B * 8 + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2 + 16
+            + (size_t)(THREADS / 64) * ((size_t)HCAP + 64 * 8);
+    return fixed + (size_t)(THREADS / 64) * 192 * 10 <= 160 * 1024 ? 192 : 0;
+}
+
+// The deep-pileup kernel (a cell pair may collect 65536 pairs or more: int64 tile, no count tile). Joint (x_s, x_d)
+// terms of multi-locus read pairs go through the full entries in HBM (they are rare when loci are sparse; clustered
+// loci run accumulate_masks).
+// HCAP:   size of the per-wave strip in which a batch's pairs are flattened over the lanes (below);
+//         deeper batches are flattened HCAP pairs at a time.
+//
+// Work distribution. A workgroup walks its locus ranges; per range the column side (block J) is
+// staged in LDS. Each wave then pulls batches of 64 consecutive row-side entries (block I). A lane's
+// entry pairs with the c = j1 - j0 column entries of its locus, and c varies from lane to lane, so
+// the batch's pairs are FLATTENED: a wave prefix sum over c gives every entry a slice [P, P + c) of
+// the batch's T pairs, the slice is filled with the owning lane's number in a per-wave LDS strip,
+// and pair p is then handled by lane p % 64 -- every lane busy until the batch's last 64 pairs.
+template <int B, int THREADS, int CAPJ, int CAPL, int HCAP>
+__global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs a) {
+    constexpr size_t TILE_BYTES = (size_t)B * B * 8;
+    constexpr int WAVES = THREADS / 64;
+    constexpr int JPT = (CAPJ + THREADS - 1) / THREADS;      // staged column entries per thread
+    constexpr int OPT = (CAPL + 1 + THREADS - 1) / THREADS;  // staged offsets per thread
+    constexpr int MCAP = joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP>();
+    constexpr size_t WAVE_BYTES = (size_t)HCAP + 64 * 8 + (size_t)MCAP * 10;
+
+    // LDS: [ tile | sJ CAPJ u16 | sOff CAPL+2 u16 | s_next | per wave:
+    //        owner HCAP u8, wrec 64 x {entry, j0 - P}, mlist MCAP x {g1, g2}, mcell MCAP u16 (deferred joint pairs) ]
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    unsigned long long *tile64 = reinterpret_cast<unsigned long long *>(lds_raw);
+    uint16_t *sJ = reinterpret_cast<uint16_t *>(lds_raw + TILE_BYTES);
+    uint16_t *sOff = sJ + CAPJ;
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(sOff + CAPL + 2);
+    unsigned char *wave_base = reinterpret_cast<unsigned char *>(s_next + 4) + (threadIdx.x >> 6) * WAVE_BYTES;
+    unsigned char *owner = wave_base;
+    uint2 *wrec = reinterpret_cast<uint2 *>(wave_base + HCAP);
+    uint2 *mlist = reinterpret_cast<uint2 *>(wave_base + HCAP + 64 * 8);
+    uint16_t *mcell = reinterpret_cast<uint16_t *>(wave_base + HCAP + 64 * 8 + (size_t)MCAP * 8);
+
+    const TileChunk tc = tile_chunk<THREADS>(a);
+    const uint32_t t = tc.t, r_begin = tc.r_begin, r_end = tc.r_end;
+    const bool diag = tc.diag;
+    const uint32_t tid = threadIdx.x, lane = tc.lane;
+    const uint32_t *offJ = tc.offJ;
 
     for (uint32_t i = tid; i < B * B; i += THREADS) tile64[i] = 0ull;
-    if (MASKS) {
-        for (uint32_t i = tid; i < SLUT_DIM * SLUT_DIM; i += THREADS)
-            sLut[i] = a.lut[(i / SLUT_DIM) * LUT_DIM + (i % SLUT_DIM)];
-    }
 
     const long long d10 = a.lut[1 * LUT_DIM + 0], d01 = a.lut[0 * LUT_DIM + 1];
     unsigned long long *dst = reinterpret_cast<unsigned long long *>(a.acc) + (size_t)t * B * B;
@@ -259,36 +379,19 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
     // inside a diagonal tile pairs of the same cell are skipped (:215); elsewhere cells differ
     const uint32_t cell_test = diag ? C_CELL : 0u;
 
-    // one (read pair, shared locus) incidence: row-side entry `rec` (mask m1, global index g1)
-    // against column-side entry `w` (staged index jc, global index g2)
-    auto pair = [&](uint32_t rec, uint32_t m1, uint32_t w, uint32_t jc, uint32_t g1, uint32_t g2) {
+    // one (read pair, shared locus) incidence: row-side entry `rec` (global index g1) against
+    // column-side entry `w` (global index g2)
+    auto pair = [&](uint32_t rec, uint32_t w, uint32_t g1, uint32_t g2) {
         const uint32_t x = rec ^ w, both = rec & w;
         // reads that were both never flushed do not pair (:407-408)
         if ((both & C_TAIL) != 0u || ((x & cell_test) == 0u && diag)) return;
         ++upd;
         const bool differ = (x & (3u << C_BASE_SHIFT)) != 0u;
         const uint32_t cell = (rec & C_CELL) * B + (w & C_CELL);
-        if (__builtin_expect((both & C_MULTI) != 0u, MASKS ? 1 : 0)) {
+        if (__builtin_expect((both & C_MULTI) != 0u, 0)) {
             // both reads cover further loci: joint (x_s, x_d) term, owned by their first shared locus
-            long long v = differ ? d01 : d10;
-            bool owner_here = true;
-            if (MASKS && ((rec | w) & C_WIDE) == 0u) {
-                const uint32_t m2 = sJm[jc];
-                owner_here = (m1 & m2 & 0xFFu) == 0u;
-                const uint32_t shared = ((m1 & m2) >> 8) & 0xFFu;
-                if (shared) {
-                    const uint32_t y = m1 ^ m2;
-                    const uint32_t diff = ((y >> 16) | (y >> 24)) & shared;
-                    const uint32_t nd = __popc(diff);
-                    const uint32_t xd = nd + (differ ? 1u : 0u);
-                    const uint32_t xs = __popc(shared) - nd + (differ ? 0u : 1u);
-                    v = sLut[xs * SLUT_DIM + xd];
-                }
-            } else {
-                v = pair_value_full(a.slow, g1, g2);
-                owner_here = (v != NO_PAIR);
-            }
-            if (owner_here) atomicAdd(&tile64[cell], (unsigned long long)v);
+            const long long v = pair_value_full(a.slow, g1, g2);
+            if (v != NO_PAIR) atomicAdd(&tile64[cell], (unsigned long long)v);
             else ++skipped;
         } else {
             atomicAdd(&tile64[cell], (unsigned long long)(differ ? d01 : d10));
@@ -296,68 +399,37 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
     };
 
     // the next range's column side, in flight in registers while the current range is paired
-    uint32_t pJ[JPT], pM[MASKS ? JPT : 1], pO[OPT];
-    uint32_t pRec = 0, pM1 = 0;  // this wave's first row-side batch of the next range
-    uint32_t n_la = 0, n_lb = 0, n_ib = 0, n_ie = 0, n_jb = 0, n_je = 0, n_dsh = 0;
+    uint32_t pJ[JPT], pO[OPT];
+    uint32_t pRec = 0;  // this wave's first row-side batch of the next range
+    RangeCursor nx;
     bool n_staged = false;
-
-    // Range boundaries run ahead of the pairing so that their two dependent reads (locus span -> entry
-    // offsets of the two blocks) are never waited for. One register holds them all, a value per lane:
-    // lanes 0-3 the offsets of the next range (row begin, row end, column begin, column end), lanes 4-5
-    // the locus span of the range after it; it is loaded while the current range is paired.
-    uint32_t q_la = 0, q_lb = 0;  // locus span of the range `ahead` holds the offsets of
-    uint32_t ahead = 0;
-    auto fetch_ahead = [&](uint32_t r) {  // r: the range with span (q_la, q_lb)
-        const uint32_t *src = lane == 0u ? offI + q_la : lane == 1u ? offI + q_lb : lane == 2u ? offJ + q_la
-                            : lane == 3u ? offJ + q_lb : a.range_off + (r + lane - 3u);  // lanes 4, 5: r + 1, r + 2
-        ahead = 0u;
-        if (lane < 4u || (lane < 6u && r + 1u < r_end)) ahead = *src;
-    };
     auto prefetch = [&](uint32_t r) {
-        n_la = q_la;
-        n_lb = q_lb;
-        const uint32_t range_ib = __builtin_amdgcn_readlane(ahead, 0);
-        n_ib = max(range_ib, row_begin);  // this chunk's part of the range's row side
-        n_ie = max(n_ib, min((uint32_t)__builtin_amdgcn_readlane(ahead, 1), row_end));
-        n_dsh = n_ib - range_ib;
-        n_jb = __builtin_amdgcn_readlane(ahead, 2);
-        n_je = __builtin_amdgcn_readlane(ahead, 3);
-        q_la = __builtin_amdgcn_readlane(ahead, 4);
-        q_lb = __builtin_amdgcn_readlane(ahead, 5);
-        if (r + 1u < r_end) fetch_ahead(r + 1u);
-        n_staged = (n_je - n_jb) <= (uint32_t)CAPJ && (n_lb - n_la) <= (uint32_t)CAPL;
+        nx.advance(a, tc, r);
+        n_staged = (nx.je - nx.jb) <= (uint32_t)CAPJ && (nx.lb - nx.la) <= (uint32_t)CAPL;
         if (n_staged) {
 #pragma unroll
             for (int k = 0; k < JPT; ++k) {
                 const uint32_t i = tid + k * THREADS;
-                if (i < n_je - n_jb) {
-                    pJ[k] = a.entry32[n_jb + i];
-                    if (MASKS) pM[k] = a.mask32[n_jb + i];
-                }
+                if (i < nx.je - nx.jb) pJ[k] = a.entry32[nx.jb + i];
             }
 #pragma unroll
             for (int k = 0; k < OPT; ++k) {
                 const uint32_t i = tid + k * THREADS;
-                if (i <= n_lb - n_la) pO[k] = offJ[n_la + i];
+                if (i <= nx.lb - nx.la) pO[k] = offJ[nx.la + i];
             }
             pRec = 0;
-            pM1 = 0;
-            if (tid < n_ie - n_ib) {  // batch (tid >> 6), entry tid: batches 0..WAVES-1 are pre-assigned
-                pRec = a.entry32[n_ib + tid];
-                if (MASKS) pM1 = a.mask32[n_ib + tid];
-            }
+            if (tid < nx.ie - nx.ib)  // batch (tid >> 6), entry tid: batches 0..WAVES-1 are pre-assigned
+                pRec = a.entry32[nx.ib + tid];
         }
     };
 
     if (r_begin < r_end) {
-        q_la = __builtin_amdgcn_readfirstlane(a.range_off[r_begin]);
-        q_lb = __builtin_amdgcn_readfirstlane(a.range_off[r_begin + 1u]);
-        fetch_ahead(r_begin);
+        nx.prime(a, tc);
         prefetch(r_begin);
     }
     STAMP(t_pro);
     for (uint32_t r = r_begin; r < r_end; ++r) {
-        const uint32_t la = n_la, lb = n_lb, ib = n_ib, ie = n_ie, jb = n_jb, je = n_je, dsh = n_dsh;
+        const uint32_t la = nx.la, lb = nx.lb, ib = nx.ib, ie = nx.ie, jb = nx.jb, je = nx.je, dsh = nx.dsh;
         const bool staged = n_staged;
         STAMP(tb0);
         __syncthreads();  // every wave is done with the previous range (first time: with zeroing)
@@ -366,10 +438,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
 #pragma unroll
             for (int k = 0; k < JPT; ++k) {
                 const uint32_t i = tid + k * THREADS;
-                if (i < je - jb) {
-                    sJ[i] = (uint16_t)pJ[k];
-                    if (MASKS) sJm[i] = pM[k];
-                }
+                if (i < je - jb) sJ[i] = (uint16_t)pJ[k];
             }
 #pragma unroll
             for (int k = 0; k < OPT; ++k) {
@@ -378,7 +447,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
             }
         }
         if (tid == 0) *s_next = WAVES;  // batches 0..WAVES-1 are pre-assigned, one per wave
-        const uint32_t first_rec = pRec, first_m1 = pM1;
+        const uint32_t first_rec = pRec;
         __syncthreads();
         STAMP(tb2);
         if (r + 1 < r_end) prefetch(r + 1);
@@ -396,17 +465,15 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
         if (staged) {
             const uint32_t n_batch = (nI + 63u) / 64u;
             uint32_t cur = tid >> 6;
-            uint32_t rec = first_rec, m1 = first_m1;  // loaded while the previous range was paired
+            uint32_t rec = first_rec;  // loaded while the previous range was paired
             while (cur < n_batch) {
                 STAMP(t0);
                 uint32_t nxt = 0;
                 if (lane == 0) nxt = atomicAdd(s_next, 1u);
                 nxt = __builtin_amdgcn_readfirstlane(nxt);
-                uint32_t rec_n = 0, m1_n = 0;
-                if (nxt < n_batch && nxt * 64u + lane < nI) {  // next batch's records in flight
+                uint32_t rec_n = 0;
+                if (nxt < n_batch && nxt * 64u + lane < nI)  // next batch's records in flight
                     rec_n = a.entry32[ib + nxt * 64u + lane];
-                    if (MASKS) m1_n = a.mask32[ib + nxt * 64u + lane];
-                }
                 const uint32_t i = cur * 64u + lane;
                 uint32_t j0 = 0, c = 0;
                 if (i < nI) {
@@ -419,7 +486,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                 const uint32_t pin = wave_inclusive_scan(c);
                 const uint32_t total = __builtin_amdgcn_readlane(pin, 63);
                 const uint32_t pex = pin - c;
-                if (a.debug & 8u) { cur = nxt; rec = rec_n; m1 = m1_n; continue; }
+                if (a.debug & 8u) { cur = nxt; rec = rec_n; continue; }
                 STAMP(t1);
                 if (total <= (uint32_t)HCAP) {
                     // flatten: pair p of the batch belongs to lane owner[p]
@@ -428,7 +495,6 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                     // what a pair needs of its row-side entry: the entry's low 16 bits, its tile row
                     // (element index) in the high 16, and j0 - P so that column index = that + p
                     wrec[lane] = make_uint2((rec & 0xFFFFu) | (((rec & C_CELL) * B) << 16), j0 - pex);
-                    if (MASKS) wm[lane] = m1;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     STAMP(t2);
@@ -438,110 +504,100 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                     st_batches += 1;
                     st_trips += (total + 127u) / 128u;
 #endif
-                    if (!MASKS) {
-                        // sparse-loci variants: single-locus pairs only in the hot loop; the (rare)
-                        // pairs of two multi-locus reads are picked up by the second loop
-                        // Uniform trip count, two pairs per lane and trip (independent LDS read
-                        // chains), lanes past the end clamped and masked: keeps the loop free of
-                        // exec-mask bookkeeping.
-                        uint32_t multi_seen = 0;
-                        const uint32_t last = total - 1u;
-                        // One trip = PPL pairs per lane (independent LDS read chains; 4 is no faster than
-                        // 2). Full trips need no bounds handling; the last trip clamps and masks, and
-                        // takes one pair per lane when 64 or fewer pairs are left.
-                        auto trip = [&](uint32_t base, auto ppl_c, auto tail_c) {
-                            constexpr int PPL = decltype(ppl_c)::value;
-                            constexpr bool TAIL = decltype(tail_c)::value;
-                            if (MCAP > 0 && n_list > (uint32_t)(MCAP - 128)) flush_list();
-                            uint32_t pp[PPL], oo[PPL], ww[PPL];
-                            uint2 rr[PPL];
+                    // single-locus pairs only in the hot loop; the (rare)
+                    // pairs of two multi-locus reads are picked up by the second loop
+                    // Uniform trip count, two pairs per lane and trip (independent LDS read
+                    // chains), lanes past the end clamped and masked: keeps the loop free of
+                    // exec-mask bookkeeping.
+                    uint32_t multi_seen = 0;
+                    const uint32_t last = total - 1u;
+                    // One trip = PPL pairs per lane (independent LDS read chains; 4 is no faster than
+                    // 2). Full trips need no bounds handling; the last trip clamps and masks, and
+                    // takes one pair per lane when 64 or fewer pairs are left.
+                    auto trip = [&](uint32_t base, auto ppl_c, auto tail_c) {
+                        constexpr int PPL = decltype(ppl_c)::value;
+                        constexpr bool TAIL = decltype(tail_c)::value;
+                        if (MCAP > 0 && n_list > (uint32_t)(MCAP - 128)) flush_list();
+                        uint32_t pp[PPL], oo[PPL], ww[PPL];
+                        uint2 rr[PPL];
 #pragma unroll
-                            for (int u = 0; u < PPL; ++u) pp[u] = base + lane + 64u * u;
+                        for (int u = 0; u < PPL; ++u) pp[u] = base + lane + 64u * u;
 #pragma unroll
-                            for (int u = 0; u < PPL; ++u) oo[u] = owner[TAIL ? min(pp[u], last) : pp[u]];
+                        for (int u = 0; u < PPL; ++u) oo[u] = owner[TAIL ? min(pp[u], last) : pp[u]];
 #pragma unroll
-                            for (int u = 0; u < PPL; ++u) rr[u] = wrec[oo[u]];
+                        for (int u = 0; u < PPL; ++u) rr[u] = wrec[oo[u]];
 #pragma unroll
-                            for (int u = 0; u < PPL; ++u) ww[u] = sJ[rr[u].y + (TAIL ? min(pp[u], last) : pp[u])];
+                        for (int u = 0; u < PPL; ++u) ww[u] = sJ[rr[u].y + (TAIL ? min(pp[u], last) : pp[u])];
 #pragma unroll
-                            for (int u = 0; u < PPL; ++u) {
-                                const uint32_t x = rr[u].x ^ ww[u], both = rr[u].x & ww[u];
-                                // reads both never flushed do not pair (:407-408); inside a diagonal
-                                // tile equal cells do not pair (:215)
-                                const bool ok = (!TAIL || pp[u] < total) && (both & C_TAIL) == 0u
-                                        && ((x & cell_test) != 0u || !diag);
-                                upd += ok ? 1u : 0u;
-                                const uint32_t cell = (rr[u].x >> 16) + (ww[u] & C_CELL);
-                                if (MCAP > 0) {
-                                    const bool joint = ok && (both & C_MULTI) != 0u;
-                                    const unsigned long long bal = __ballot(joint);
-                                    if (bal) {
-                                        if (joint) {
-                                            const uint32_t slot = n_list + __builtin_amdgcn_mbcnt_hi(
-                                                    (uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                                            mlist[slot] = make_uint2(ib + cur * 64u + oo[u], jb + rr[u].y + pp[u]);
-                                            mcell[slot] = (uint16_t)cell;
-                                        }
-                                        n_list += (uint32_t)__popcll(bal);
+                        for (int u = 0; u < PPL; ++u) {
+                            const uint32_t x = rr[u].x ^ ww[u], both = rr[u].x & ww[u];
+                            // reads both never flushed do not pair (:407-408); inside a diagonal
+                            // tile equal cells do not pair (:215)
+                            const bool ok = (!TAIL || pp[u] < total) && (both & C_TAIL) == 0u
+                                    && ((x & cell_test) != 0u || !diag);
+                            upd += ok ? 1u : 0u;
+                            const uint32_t cell = (rr[u].x >> 16) + (ww[u] & C_CELL);
+                            if (MCAP > 0) {
+                                const bool joint = ok && (both & C_MULTI) != 0u;
+                                const unsigned long long bal = __ballot(joint);
+                                if (bal) {
+                                    if (joint) {
+                                        const uint32_t slot = n_list + __builtin_amdgcn_mbcnt_hi(
+                                                (uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                                        mlist[slot] = make_uint2(ib + cur * 64u + oo[u], jb + rr[u].y + pp[u]);
+                                        mcell[slot] = (uint16_t)cell;
                                     }
-                                } else {
-                                    multi_seen |= ok ? both : 0u;
+                                    n_list += (uint32_t)__popcll(bal);
                                 }
-                                if ((a.debug & 1u) == 0u && ok && (both & C_MULTI) == 0u) {
-                                    const bool differ = (x & (3u << C_BASE_SHIFT)) != 0u;
-                                    atomicAdd(&tile64[cell], (unsigned long long)(differ ? d01 : d10));
-                                }
+                            } else {
+                                multi_seen |= ok ? both : 0u;
                             }
-                        };
-                        using two = std::integral_constant<int, 2>;
-                        using one = std::integral_constant<int, 1>;
-                        if (!(a.debug & 2u)) {
-                            uint32_t base = 0;
-                            for (; base + 128u <= total; base += 128u) trip(base, two{}, std::false_type{});
-                            if (base < total) {
-                                if (total - base <= 64u) trip(base, one{}, std::true_type{});
-                                else trip(base, two{}, std::true_type{});
+                            if ((a.debug & 1u) == 0u && ok && (both & C_MULTI) == 0u) {
+                                const bool differ = (x & (3u << C_BASE_SHIFT)) != 0u;
+                                atomicAdd(&tile64[cell], (unsigned long long)(differ ? d01 : d10));
                             }
                         }
-                        STAMP(t3);
+                    };
+                    using two = std::integral_constant<int, 2>;
+                    using one = std::integral_constant<int, 1>;
+                    if (!(a.debug & 2u)) {
+                        uint32_t base = 0;
+                        for (; base + 128u <= total; base += 128u) trip(base, two{}, std::false_type{});
+                        if (base < total) {
+                            if (total - base <= 64u) trip(base, one{}, std::true_type{});
+                            else trip(base, two{}, std::true_type{});
+                        }
+                    }
+                    STAMP(t3);
 #ifdef SECEDO_STAMPS
-                        st_trip += t3 - t2;
-                        st_t3 = t3;
+                    st_trip += t3 - t2;
+                    st_t3 = t3;
 #endif
-                        const bool any_multi = MCAP == 0 && (multi_seen & C_MULTI) != 0u;
-                        if (MCAP == 0 && __ballot(any_multi)) {
-                            for (uint32_t p = lane; p < total; p += 64u) {
-                                const uint32_t o = owner[p];
-                                const uint2 ro = wrec[o];
-                                const uint32_t jc = ro.y + p;
-                                const uint32_t w = sJ[jc];
-                                const uint32_t x = ro.x ^ w, both = ro.x & w;
-                                const bool ok = (both & C_TAIL) == 0u && ((x & cell_test) != 0u || !diag);
-                                if (ok && (both & C_MULTI) != 0u) {
-                                    const long long v = pair_value_full(a.slow, ib + cur * 64u + o, jb + jc);
-                                    const uint32_t cell = (ro.x >> 16) + (w & C_CELL);
-                                    if (v == NO_PAIR) ++skipped;
-                                    else atomicAdd(&tile64[cell], (unsigned long long)v);
-                                }
-                            }
-                        }
-                    } else {
+                    const bool any_multi = MCAP == 0 && (multi_seen & C_MULTI) != 0u;
+                    if (MCAP == 0 && __ballot(any_multi)) {
                         for (uint32_t p = lane; p < total; p += 64u) {
                             const uint32_t o = owner[p];
                             const uint2 ro = wrec[o];
                             const uint32_t jc = ro.y + p;
-                            pair(ro.x, wm[o], sJ[jc], jc, ib + cur * 64u + o, jb + jc);
+                            const uint32_t w = sJ[jc];
+                            const uint32_t x = ro.x ^ w, both = ro.x & w;
+                            const bool ok = (both & C_TAIL) == 0u && ((x & cell_test) != 0u || !diag);
+                            if (ok && (both & C_MULTI) != 0u) {
+                                const long long v = pair_value_full(a.slow, ib + cur * 64u + o, jb + jc);
+                                const uint32_t cell = (ro.x >> 16) + (w & C_CELL);
+                                if (v == NO_PAIR) ++skipped;
+                                else atomicAdd(&tile64[cell], (unsigned long long)v);
+                            }
                         }
                     }
                     __builtin_amdgcn_wave_barrier();  // the strip is reused by the next batch
 #ifdef SECEDO_STAMPS
-                    if (!MASKS) { STAMP(t4); st_post += t4 - st_t3; }
+                    { STAMP(t4); st_post += t4 - st_t3; }
 #endif
                 } else {
                     // a very deep batch (more than HCAP pairs): the same flattening, HCAP pairs at a
                     // time -- pair p belongs to lane owner[p - win] -- with the general pair routine
                     wrec[lane] = make_uint2(rec & 0xFFFFu, j0 - pex);
-                    if (MASKS) wm[lane] = m1;
                     for (uint32_t win = 0; win < total; win += (uint32_t)HCAP) {
                         const uint32_t wlen = min((uint32_t)HCAP, total - win);
                         const uint32_t f0 = max(pex, win), f1 = min(pin, win + (uint32_t)HCAP);
@@ -552,42 +608,16 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                             const uint32_t o = owner[q];
                             const uint2 ro = wrec[o];
                             const uint32_t jc = ro.y + win + q;
-                            pair(ro.x, MASKS ? wm[o] : 0u, sJ[jc], jc, ib + cur * 64u + o, jb + jc);
+                            pair(ro.x, sJ[jc], ib + cur * 64u + o, jb + jc);
                         }
                         __builtin_amdgcn_wave_barrier();  // the strip is reused by the next window
                     }
                 }
                 cur = nxt;
                 rec = rec_n;
-                m1 = m1_n;
             }
         } else {
-            // a locus range that does not fit the staging buffers (a single very deep locus):
-            // pair it straight from HBM/L2 with the compact entries, straight into HBM; the full
-            // entries are read (and exist) only for pairs of two multi-locus reads
-            for (uint32_t e1 = ib + tid; e1 < ie; e1 += THREADS) {
-                const uint32_t r1 = a.entry32[e1];
-                const uint32_t l = la + (r1 >> 16);
-                const uint32_t j0 = diag ? e1 + 1 : offJ[l];
-                const uint32_t j1 = offJ[l + 1];
-                const uint32_t row = (r1 & C_CELL) * B;
-                for (uint32_t e2 = j0; e2 < j1; ++e2) {
-                    const uint32_t r2 = a.entry32[e2];
-                    const uint32_t x = r1 ^ r2, both = r1 & r2;
-                    if (diag && (x & C_CELL) == 0u) continue;  // same cell (:215)
-                    if (both & C_TAIL) continue;               // both never flushed (:407-408)
-                    ++upd;
-                    long long v = (x & (3u << C_BASE_SHIFT)) ? d01 : d10;
-                    if (both & C_MULTI) {
-                        v = pair_value_full(a.slow, e1, e2);
-                        if (v == NO_PAIR) {
-                            ++skipped;
-                            continue;
-                        }
-                    }
-                    atomicAdd(&dst[row + (r2 & C_CELL)], (unsigned long long)v);
-                }
-            }
+            pair_range_from_hbm<B, THREADS, false>(a, tc, la, ib, ie, dst, d10, d01, upd, skipped);
         }
 #ifdef SECEDO_STAMPS
         { STAMP(te); st_loop += te - tb3; }
@@ -630,31 +660,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_tiles(const AccumulateArgs
                 | ((unsigned long long)r_end << 44);
     }
 #endif
-    // work counters: wave reduction, one atomic per wave
-    n_pairs -= skipped_list;
-    for (int off = 32; off > 0; off >>= 1) {
-        n_updates += __shfl_down(n_updates, off);
-        n_pairs += __shfl_down(n_pairs, off);
-    }
-    // ... and one per workgroup: thousands of same-address atomics at the end of a launch queue up in
-    // the memory system and delay the workgroups still running (the staging area is free by now)
-    unsigned long long *red = reinterpret_cast<unsigned long long *>(sJ);
-    if (lane == 0u) {
-        red[(tid >> 6) * 2] = n_updates;
-        red[(tid >> 6) * 2 + 1] = n_pairs;
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        unsigned long long u = 0, q = 0;
-        for (int w = 0; w < WAVES; ++w) {
-            u += red[w * 2];
-            q += red[w * 2 + 1];
-        }
-        if (u | q) {
-            atomicAdd(&a.counters[0], u);
-            atomicAdd(&a.counters[1], q);
-        }
-    }
+    add_work_counters<WAVES>(a.counters, reinterpret_cast<unsigned long long *>(sJ), n_updates, n_pairs - skipped_list);
 #ifdef SECEDO_STAMPS
     if (tid == 0u) {  // wave 0 of every workgroup stands for its workgroup
         atomicAdd(&a.counters[2], st_setup);
@@ -760,6 +766,10 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
     uint16_t *sOff = reinterpret_cast<uint16_t *>(sJ + CAPJ);
     uint32_t *ring = reinterpret_cast<uint32_t *>(sOff + (CAPL + 2) * (WORDS ? 2 : 1)) + (threadIdx.x >> 6) * RING;
 
+    // tile_chunk(), word for word, in the kernel's own locals: through the function five of the seven instances came
+    // out with two SGPR spills fewer and the tile's index recomputed in the fused epilogue (profiles/r18_pair_kernel_codegen.txt) -- harmless
+    // as far as anyone can tell, but this is the kernel whose code is to stay what was measured. A change to the chunk
+    // rule is made in both places.
     const uint32_t t_local = a.wg_tile[blockIdx.x];
     const uint32_t t = a.tile_ids ? a.tile_ids[t_local] : a.tile_begin + t_local;
     const uint32_t chunk = blockIdx.x - a.tile_wg_begin[t_local];
@@ -773,7 +783,6 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
     // which have the same number of column entries each, land in different waves and the waves' pair counts
     // even out -- was measured slower: 3.29 against 2.88 ms on C3. The barrier wait did not shrink (it is not
     // the pair counts that differ), and the lanes of a wave lose the shared LDS reads of a common locus.)
-    // chunks: equal shares of the tile's row-side entries (see accumulate_tiles)
     uint32_t r_begin = 0, r_end = a.num_ranges;
     uint32_t row_begin = 0u, row_end = 0xFFFFFFFFu;
     if (n_chunks_t > 1u) {
@@ -798,6 +807,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
         row_begin = __builtin_amdgcn_readfirstlane(row_begin);
         row_end = __builtin_amdgcn_readfirstlane(row_end);
     }
+    const TileChunk tc{t, diag, lane, offI, offJ, r_begin, r_end, row_begin, row_end};
     for (uint32_t i = tid; i < B * ROW_WORDS; i += THREADS) tile32[i] = 0u;
 
     unsigned long long n_updates = 0;  // lane 0 of each wave carries the wave's count
@@ -810,38 +820,20 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
     // again, one place on: no lane exchange, no word through LDS for the wave's last lane, and with half the
     // offsets per thread as many registers as pO alone has otherwise)
     uint32_t pO1[WORDS ? OPT : 1];
-    uint32_t n_la = 0, n_lb = 0, n_ib = 0, n_ie = 0, n_jb = 0, n_je = 0, n_dsh = 0;
+    RangeCursor nx;
     bool n_staged = false;
-    uint32_t q_la = 0, q_lb = 0;  // locus span of the range `ahead` holds the offsets of
-    uint32_t ahead = 0;           // lanes 0-3: offsets of the next range; lanes 4-5: span of the one after
-    auto fetch_ahead = [&](uint32_t r) {
-        const uint32_t *src = lane == 0u ? offI + q_la : lane == 1u ? offI + q_lb : lane == 2u ? offJ + q_la
-                            : lane == 3u ? offJ + q_lb : a.range_off + (r + lane - 3u);
-        ahead = 0u;
-        if (lane < 4u || (lane < 6u && r + 1u < r_end)) ahead = *src;
-    };
     auto prefetch = [&](uint32_t r) {
-        n_la = q_la;
-        n_lb = q_lb;
-        const uint32_t range_ib = __builtin_amdgcn_readlane(ahead, 0);
-        n_ib = max(range_ib, row_begin);  // this chunk's part of the range's row side
-        n_ie = max(n_ib, min((uint32_t)__builtin_amdgcn_readlane(ahead, 1), row_end));
-        n_dsh = n_ib - range_ib;
-        n_jb = __builtin_amdgcn_readlane(ahead, 2);
-        n_je = __builtin_amdgcn_readlane(ahead, 3);
-        q_la = __builtin_amdgcn_readlane(ahead, 4);
-        q_lb = __builtin_amdgcn_readlane(ahead, 5);
-        if (r + 1u < r_end) fetch_ahead(r + 1u);
-        n_staged = (n_je - n_jb) <= (uint32_t)CAPJ && (n_ie - n_ib) <= (uint32_t)CAPJ
-                && (n_lb - n_la) <= (uint32_t)CAPL;
+        nx.advance(a, tc, r);
+        n_staged = (nx.je - nx.jb) <= (uint32_t)CAPJ && (nx.ie - nx.ib) <= (uint32_t)CAPJ
+                && (nx.lb - nx.la) <= (uint32_t)CAPL;
         // Buffer loads: the descriptor (wave-uniform: base and byte count of the slice) does the bounds check, a
         // lane past the end gets 0 -- no compare, no exec mask, no address arithmetic per load (the per-lane
         // offset tid * 4 is loop-invariant, k * THREADS * 4 goes in the scalar offset).
         if (n_staged) {
             const __amdgpu_buffer_rsrc_t rj = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<uint32_t *>(a.entry32 + n_jb), 0, (int)((n_je - n_jb) * 4u), 0x00020000);
+                    const_cast<uint32_t *>(a.entry32 + nx.jb), 0, (int)((nx.je - nx.jb) * 4u), 0x00020000);
             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<uint32_t *>(offJ + n_la), 0, (int)((n_lb - n_la + 1u) * 4u), 0x00020000);
+                    const_cast<uint32_t *>(offJ + nx.la), 0, (int)((nx.lb - nx.la + 1u) * 4u), 0x00020000);
 #pragma unroll
             for (int k = 0; k < JPT; ++k)
                 pJ[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rj, (int)(tid * 4u), k * THREADS * 4, 0);
@@ -860,7 +852,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
     auto prefetch_rows = [&]() {
         if (n_staged) {
             const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<uint32_t *>(a.entry32 + n_ib), 0, (int)((n_ie - n_ib) * 4u), 0x00020000);
+                    const_cast<uint32_t *>(a.entry32 + nx.ib), 0, (int)((nx.ie - nx.ib) * 4u), 0x00020000);
 #pragma unroll
             for (int k = 0; k < JPT; ++k)
                 pI[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, (int)(tid * 4u), k * THREADS * 4, 0);
@@ -868,9 +860,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
     };
 
     if (r_begin < r_end) {
-        q_la = __builtin_amdgcn_readfirstlane(a.range_off[r_begin]);
-        q_lb = __builtin_amdgcn_readfirstlane(a.range_off[r_begin + 1u]);
-        fetch_ahead(r_begin);
+        nx.prime(a, tc);
         prefetch(r_begin);
         prefetch_rows();
     }
@@ -1037,7 +1027,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
         };
 
         for (uint32_t r = r_begin; r < r_end; ++r) {
-            const uint32_t la = n_la, ib = n_ib, ie = n_ie, jb = n_jb, dsh = n_dsh;
+            const uint32_t la = nx.la, ib = nx.ib, ie = nx.ie, jb = nx.jb, dsh = nx.dsh;
             const bool staged = n_staged;
             STAMP(s0);
             __syncthreads();  // every wave is done with the previous range (first time: with zeroing)
@@ -1228,8 +1218,9 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
         uint32_t *out = reinterpret_cast<uint32_t *>(a.slab) + (size_t)blockIdx.x * B * B;
         for (uint32_t i = tid; i < B * B; i += THREADS) out[i] = tile32[(i / B) * ROW_WORDS + (i % B)];  // dense rows
     }
-    // work counter: wave reduction, then one atomic pair per workgroup (see accumulate_tiles); every
-    // incidence counts as an update and as a read pair here, correct_tiles takes back what is neither
+    // work counters as add_work_counters() adds them, but ONE value for both: every incidence counts as an update and
+    // as a read pair here, correct_tiles takes back what is neither. (Through add_work_counters the value is reduced,
+    // stored and read twice: 57 instructions more and another block layout of the kernel, profiles/r18_pair_kernel_codegen.txt.)
     for (int off = 32; off > 0; off >>= 1) n_updates += __shfl_down(n_updates, off);
     unsigned long long *red = reinterpret_cast<unsigned long long *>(sJ);
     if (lane == 0u) red[tid >> 6] = n_updates;
@@ -1251,9 +1242,9 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
 // ------------------------------------------------------------------------------------------------
 // accumulate_masks: clustered loci (the 8-locus window masks staged), in the shape of accumulate_counts.
 //
-// accumulate_tiles<MASKS> flattens a batch's pairs over the lanes and then walks, per pair, a chain of
-// dependent LDS reads (owner strip -> row record -> row mask -> column entry -> column mask -> table): one
-// pair per lane and trip, nothing in flight beside it. Here the row side lives in registers as in
+// Its predecessor (accumulate_tiles with the masks staged too, retired) flattened a batch's pairs over the lanes and
+// then walked, per pair, a chain of dependent LDS reads (owner strip -> row record -> row mask -> column entry ->
+// column mask -> table): one pair per lane and trip, nothing in flight beside it. Here the row side lives in registers as in
 // accumulate_counts -- a thread keeps its JPT row entries of the range as items --, a wave pairs 64 items with
 // GROUP column entries each, the column entry arrives in ONE 8-byte LDS read, issued for the next item before
 // the current one is paired, and the value comes out of ONE unconditional table read. Longer items go through
@@ -1322,40 +1313,11 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
     uint32_t *ring_y = reinterpret_cast<uint32_t *>(reinterpret_cast<uint2 *>(sLut + MLUT_WORDS) + WAVES * RING)
             + (threadIdx.x >> 6) * RING;
 
-    const uint32_t t_local = a.wg_tile[blockIdx.x];
-    const uint32_t t = a.tile_ids ? a.tile_ids[t_local] : a.tile_begin + t_local;
-    const uint32_t chunk = blockIdx.x - a.tile_wg_begin[t_local];
-    const uint32_t n_chunks_t = a.tile_wg_begin[t_local + 1] - a.tile_wg_begin[t_local];
-    const uint32_t I = a.tile_row[t], J = a.tile_col[t];
-    const bool DIAG = (I == J);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t *offI = a.blk_off + (size_t)I * a.stride;
-    const uint32_t *offJ = a.blk_off + (size_t)J * a.stride;
-    // chunks: equal shares of the tile's row-side entries (see accumulate_tiles)
-    uint32_t r_begin = 0, r_end = a.num_ranges;
-    uint32_t row_begin = 0u, row_end = 0xFFFFFFFFu;
-    if (n_chunks_t > 1u) {
-        const uint32_t L = a.stride - 1u;
-        const uint32_t e0 = offI[0];
-        const unsigned long long n_row = offI[L] - e0;
-        row_begin = e0 + (uint32_t)(n_row * chunk / n_chunks_t);
-        row_end = e0 + (uint32_t)(n_row * (chunk + 1u) / n_chunks_t);
-        uint32_t before = 0, upto = 0;
-        for (uint32_t base = 0; base < a.num_ranges; base += THREADS) {
-            const uint32_t k = base + tid;
-            bool ends_before = false, begins_inside = false;
-            if (k < a.num_ranges) {
-                ends_before = offI[a.range_off[k + 1u]] <= row_begin;
-                begins_inside = offI[a.range_off[k]] < row_end;
-            }
-            before += (uint32_t)__syncthreads_count(ends_before);
-            upto += (uint32_t)__syncthreads_count(begins_inside);
-        }
-        r_begin = __builtin_amdgcn_readfirstlane(before);
-        r_end = __builtin_amdgcn_readfirstlane(upto);
-        row_begin = __builtin_amdgcn_readfirstlane(row_begin);
-        row_end = __builtin_amdgcn_readfirstlane(row_end);
-    }
+    const TileChunk tc = tile_chunk<THREADS>(a);
+    const uint32_t t = tc.t, r_begin = tc.r_begin, r_end = tc.r_end;
+    const bool DIAG = tc.diag;
+    const uint32_t tid = threadIdx.x, lane = tc.lane;
+    const uint32_t *offJ = tc.offJ;
     for (uint32_t i = tid; i < B * ROW_Q; i += THREADS) tile64[i] = 0ull;
     // the table by (x_s, shared next loci n): D(x_s, n + 1 - x_s); x_s > n + 1 cannot occur
     for (uint32_t i = tid; i < (uint32_t)MLUT_WORDS; i += THREADS) {
@@ -1370,38 +1332,20 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
 
     // the next range, in flight in registers while the current one is paired
     uint32_t pJ[JPT], pMj[JPT], pI[JPT], pXi[JPT], pMi[JPT], pO[OPT];
-    uint32_t n_la = 0, n_lb = 0, n_ib = 0, n_ie = 0, n_jb = 0, n_je = 0, n_dsh = 0;
+    RangeCursor nx;
     bool n_staged = false;
-    uint32_t q_la = 0, q_lb = 0;  // locus span of the range `ahead` holds the offsets of
-    uint32_t ahead = 0;           // lanes 0-3: offsets of the next range; lanes 4-5: span of the one after
-    auto fetch_ahead = [&](uint32_t r) {
-        const uint32_t *src = lane == 0u ? offI + q_la : lane == 1u ? offI + q_lb : lane == 2u ? offJ + q_la
-                            : lane == 3u ? offJ + q_lb : a.range_off + (r + lane - 3u);
-        ahead = 0u;
-        if (lane < 4u || (lane < 6u && r + 1u < r_end)) ahead = *src;
-    };
     auto prefetch = [&](uint32_t r) {
-        n_la = q_la;
-        n_lb = q_lb;
-        const uint32_t range_ib = __builtin_amdgcn_readlane(ahead, 0);
-        n_ib = max(range_ib, row_begin);  // this chunk's part of the range's row side
-        n_ie = max(n_ib, min((uint32_t)__builtin_amdgcn_readlane(ahead, 1), row_end));
-        n_dsh = n_ib - range_ib;
-        n_jb = __builtin_amdgcn_readlane(ahead, 2);
-        n_je = __builtin_amdgcn_readlane(ahead, 3);
-        q_la = __builtin_amdgcn_readlane(ahead, 4);
-        q_lb = __builtin_amdgcn_readlane(ahead, 5);
-        if (r + 1u < r_end) fetch_ahead(r + 1u);
-        n_staged = (n_je - n_jb) <= (uint32_t)CAPJ && (n_ie - n_ib) <= (uint32_t)CAPJ
-                && (n_lb - n_la) <= (uint32_t)CAPL;
+        nx.advance(a, tc, r);
+        n_staged = (nx.je - nx.jb) <= (uint32_t)CAPJ && (nx.ie - nx.ib) <= (uint32_t)CAPJ
+                && (nx.lb - nx.la) <= (uint32_t)CAPL;
         // buffer loads: the descriptor bounds the slice, a lane past the end gets 0 (see accumulate_counts)
         if (n_staged) {
             // (the column entries' words as masks_words() made them once per prepare: x with the cell's byte offset, y)
-            const int nj = (int)((n_je - n_jb) * 4u);
-            const __amdgpu_buffer_rsrc_t rj = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_xcol + n_jb), 0, nj, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_y + n_jb), 0, nj, 0x00020000);
+            const int nj = (int)((nx.je - nx.jb) * 4u);
+            const __amdgpu_buffer_rsrc_t rj = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_xcol + nx.jb), 0, nj, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_y + nx.jb), 0, nj, 0x00020000);
             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<uint32_t *>(offJ + n_la), 0, (int)((n_lb - n_la + 1u) * 4u), 0x00020000);
+                    const_cast<uint32_t *>(offJ + nx.la), 0, (int)((nx.lb - nx.la + 1u) * 4u), 0x00020000);
 #pragma unroll
             for (int k = 0; k < JPT; ++k) {
                 pJ[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rj, (int)(tid * 4u), k * THREADS * 4, 0);
@@ -1415,10 +1359,10 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
     auto prefetch_rows = [&]() {
         if (n_staged) {
             // (the row entries: entry32 for the locus, the cell and the wide flag, and their two words in the row form)
-            const int ni = (int)((n_ie - n_ib) * 4u);
-            const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.entry32 + n_ib), 0, ni, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_xrow + n_ib), 0, ni, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_y + n_ib), 0, ni, 0x00020000);
+            const int ni = (int)((nx.ie - nx.ib) * 4u);
+            const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.entry32 + nx.ib), 0, ni, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_xrow + nx.ib), 0, ni, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.mk_y + nx.ib), 0, ni, 0x00020000);
 #pragma unroll
             for (int k = 0; k < JPT; ++k) {
                 pI[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, (int)(tid * 4u), k * THREADS * 4, 0);
@@ -1428,9 +1372,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
         }
     };
     if (r_begin < r_end) {
-        q_la = __builtin_amdgcn_readfirstlane(a.range_off[r_begin]);
-        q_lb = __builtin_amdgcn_readfirstlane(a.range_off[r_begin + 1u]);
-        fetch_ahead(r_begin);
+        nx.prime(a, tc);
         prefetch(r_begin);
         prefetch_rows();
     }
@@ -1603,7 +1545,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
     };
 
     for (uint32_t r = r_begin; r < r_end; ++r) {
-        const uint32_t la = n_la, ib = n_ib, ie = n_ie, jb = n_jb, dsh = n_dsh;
+        const uint32_t la = nx.la, ib = nx.ib, ie = nx.ie, jb = nx.jb, dsh = nx.dsh;
         const bool staged = n_staged;
         __syncthreads();  // every wave is done with the previous range (first time: with zeroing)
         if (staged) {
@@ -1690,34 +1632,9 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
                 prefetch(r + 1);
                 prefetch_rows();
             }
-            // a locus range that does not fit the staging buffers (a single very deep locus): paired straight
-            // from HBM/L2 with the compact entries, straight into HBM (as accumulate_tiles does)
             const long long d10 = a.lut[1 * LUT_DIM + 0], d01 = a.lut[0 * LUT_DIM + 1];
             uint32_t upd = 0, skipped = 0;
-            for (uint32_t e1 = ib + tid; e1 < ie; e1 += THREADS) {
-                const uint32_t r1 = a.entry32[e1];
-                const uint32_t l = la + (r1 >> 16);
-                const uint32_t j0 = DIAG ? e1 + 1 : offJ[l];
-                const uint32_t j1 = offJ[l + 1];
-                const uint32_t row = (r1 & C_CELL) * B;
-                for (uint32_t e2 = j0; e2 < j1; ++e2) {
-                    const uint32_t r2 = a.entry32[e2];
-                    const uint32_t x = r1 ^ r2, both = r1 & r2;
-                    if (DIAG && (x & C_CELL) == 0u) continue;  // same cell (:215)
-                    if (both & C_TAIL) continue;               // both never flushed (:407-408)
-                    if ((r1 | r2) & C_WIDE) continue;          // wide_pairs
-                    ++upd;
-                    long long v = (x & (3u << C_BASE_SHIFT)) ? d01 : d10;
-                    if (both & C_MULTI) {
-                        v = pair_value_full(a.slow, e1, e2);
-                        if (v == NO_PAIR) {
-                            ++skipped;
-                            continue;
-                        }
-                    }
-                    atomicAdd(&dst[row + (r2 & C_CELL)], (unsigned long long)v);
-                }
-            }
+            pair_range_from_hbm<B, THREADS, true>(a, tc, la, ib, ie, dst, d10, d01, upd, skipped);
             n_updates += upd;
             n_pairs += (unsigned long long)upd - skipped;
         }
@@ -1731,28 +1648,7 @@ __global__ __launch_bounds__(THREADS) void accumulate_masks(const AccumulateArgs
         unsigned long long *out = reinterpret_cast<unsigned long long *>(a.slab) + (size_t)blockIdx.x * B * B;
         for (uint32_t i = tid; i < B * B; i += THREADS) out[i] = tile64[(i / B) * ROW_Q + (i % B)];  // dense rows
     }
-    // work counters: wave reduction, then one atomic pair per workgroup (see accumulate_tiles)
-    for (int off = 32; off > 0; off >>= 1) {
-        n_updates += __shfl_down(n_updates, off);
-        n_pairs += __shfl_down(n_pairs, off);
-    }
-    unsigned long long *red = reinterpret_cast<unsigned long long *>(sJ);
-    if (lane == 0u) {
-        red[(tid >> 6) * 2] = n_updates;
-        red[(tid >> 6) * 2 + 1] = n_pairs;
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        unsigned long long u = 0, q = 0;
-        for (int w = 0; w < WAVES; ++w) {
-            u += red[w * 2];
-            q += red[w * 2 + 1];
-        }
-        if (u | q) {
-            atomicAdd(&a.counters[0], u);
-            atomicAdd(&a.counters[1], q);
-        }
-    }
+    add_work_counters<WAVES>(a.counters, reinterpret_cast<unsigned long long *>(sJ), n_updates, n_pairs);
 }
 
 // The two words of every packed entry as accumulate_masks pairs from them, made ONCE per prepare (a pass over the
@@ -2420,25 +2316,30 @@ __global__ __launch_bounds__(256) void write_matrix(const long long *acc, const 
     }
 }
 
-template <int B, int THREADS, int CAPJ, int CAPL, int HCAP, bool MASKS>
-hipError_t launch_acc(const AccumulateArgs &args, uint32_t grid, hipStream_t stream) {
-    constexpr size_t lds = (size_t)B * B * 8 + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2
-            + (MASKS ? (size_t)CAPJ * 4 + SLUT_DIM * SLUT_DIM * 8 : 0) + 16
-            + (size_t)(THREADS / 64) * ((size_t)HCAP + 64 * 8 + (MASKS ? 64 * 4 : 0)
-                                        + (size_t)joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP, MASKS>() * 10);
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    static_assert((CAPL + 2) % 4 == 0 && CAPJ % 8 == 0 && HCAP % 16 == 0, "alignment of the LDS carve-up");
-    auto kern = &accumulate_tiles<B, THREADS, CAPJ, CAPL, HCAP, MASKS>;
-    static thread_local int configured_device = -1;  // the attribute is per device and sticky
+// A kernel may use more than 64 KiB of dynamic LDS once hipFuncAttributeMaxDynamicSharedMemorySize says so: the
+// attribute is per device and sticky, so it is set once per device -- and per kernel instance, KERN being a
+// template parameter.
+template <auto KERN>
+hipError_t allow_dynamic_lds(size_t lds) {
+    static thread_local int configured_device = -1;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess || configured_device == dev) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) configured_device = dev;
+    return e;
+}
+
+template <int B, int THREADS, int CAPJ, int CAPL, int HCAP>
+hipError_t launch_acc(const AccumulateArgs &args, uint32_t grid, hipStream_t stream) {
+    constexpr size_t lds = (size_t)B * B * 8 + (size_t)CAPJ * 2 + ((size_t)CAPL + 2) * 2 + 16
+            + (size_t)(THREADS / 64) * ((size_t)HCAP + 64 * 8
+                                        + (size_t)joint_list_cap<B, THREADS, CAPJ, CAPL, HCAP>() * 10);
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    static_assert((CAPL + 2) % 4 == 0 && CAPJ % 8 == 0 && HCAP % 16 == 0, "alignment of the LDS carve-up");
+    constexpr auto kern = &accumulate_tiles<B, THREADS, CAPJ, CAPL, HCAP>;
+    const hipError_t e = allow_dynamic_lds<kern>(lds);
     if (e != hipSuccess) return e;
-    if (configured_device != dev) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-        if (e != hipSuccess) return e;
-        configured_device = dev;
-    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, args);
     hipLaunchKernelGGL((reduce_slabs<B>), dim3(args.n_tiles * (B * B / 256)), dim3(256), 0, stream,
                        args.slab, args.tile_wg_begin, args.tile_begin, args.tile_ids, args.lut,
@@ -2455,17 +2356,9 @@ hipError_t launch_masks(const AccumulateArgs &args, uint32_t grid, hipStream_t s
             + MLUT_WORDS * 8 + (size_t)(THREADS / 64) * MASKS_RING * 12;
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
     static_assert((CAPL + 2) % 4 == 0 && CAPJ % 8 == 0, "alignment of the LDS carve-up");
-    auto kern = &accumulate_masks<B, THREADS, CAPJ, CAPL, GROUP>;
-    static thread_local int configured_device = -1;  // the attribute is per device and sticky
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    constexpr auto kern = &accumulate_masks<B, THREADS, CAPJ, CAPL, GROUP>;
+    const hipError_t e = allow_dynamic_lds<kern>(lds);
     if (e != hipSuccess) return e;
-    if (configured_device != dev) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-        if (e != hipSuccess) return e;
-        configured_device = dev;
-    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, args);
     hipLaunchKernelGGL((reduce_slabs<B>), dim3(args.n_tiles * (B * B / 256)), dim3(256), 0, stream, args.slab,
                        args.tile_wg_begin, args.tile_begin, args.tile_ids, args.lut,
@@ -2497,17 +2390,9 @@ hipError_t launch_counts(const AccumulateArgs &args, uint32_t grid, hipStream_t 
             + ((size_t)CAPL + 2) * (WORDS ? 4 : 2) + (size_t)(THREADS / 64) * (size_t)COUNTS_RING * 4;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static_assert((CAPL + 2) % 4 == 0 && CAPJ % 8 == 0, "alignment of the LDS carve-up");
-    auto kern = &accumulate_counts<B, THREADS, CAPJ, CAPL, GROUP, WORDS>;
-    static thread_local int configured_device = -1;  // the attribute is per device and sticky
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    constexpr auto kern = &accumulate_counts<B, THREADS, CAPJ, CAPL, GROUP, WORDS>;
+    hipError_t e = allow_dynamic_lds<kern>(lds);
     if (e != hipSuccess) return e;
-    if (configured_device != dev) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-        if (e != hipSuccess) return e;
-        configured_device = dev;
-    }
     // (the fused epilogue's corr, scorr and part in the same LDS)
     static_assert((size_t)B * B * 8 + ((size_t)SLUT_DIM * SLUT_DIM + 2 * (THREADS / 64)) * 8 <= lds, "LDS of the epilogue");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, args);
@@ -2519,21 +2404,13 @@ hipError_t launch_counts(const AccumulateArgs &args, uint32_t grid, hipStream_t 
 // The second kernel of the sparse-loci path, after the pair kernel.
 template <int B>
 hipError_t launch_correct(const AccumulateArgs &args, hipStream_t stream) {
-    hipError_t e = hipSuccess;
-    int dev = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
     // What the flags of the reads mean, and the count tiles' way into the accumulator: one workgroup per tile.
     CorrectArgs c = correct_args(args);
     constexpr int CT = B == 128 ? 1024 : 256;
     constexpr size_t corr_lds = (size_t)B * B * 8;
-    auto corr = &correct_tiles<B, CT>;
-    static thread_local int corr_device = -1;
-    if (corr_device != dev) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(corr), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)corr_lds);
-        if (e != hipSuccess) return e;
-        corr_device = dev;
-    }
+    constexpr auto corr = &correct_tiles<B, CT>;
+    hipError_t e = allow_dynamic_lds<corr>(corr_lds);
+    if (e != hipSuccess) return e;
     // (few tiles: several workgroups each; they add with atomics, into zeroes when the launch is to overwrite
     // -- a contiguous tile range then)
     c.split = counts_split(args.n_tiles);
@@ -2616,7 +2493,7 @@ hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, b
         }
     }
     if (block_cells == 128) {
-        // the 128 KiB int64 tile leaves no room for the window masks: joint terms go through HBM
+        // (no accumulate_masks for 128-cell tiles: stage_geometry never asks for the masks there)
         if (count_tile && args.short_ranges) {  // a staged word per locus: half the loci per range in the same LDS
             if (locus_words) *locus_words = true;
             if (args.group_hint == 2)
@@ -2630,14 +2507,13 @@ hipError_t launch_accumulate(const AccumulateArgs &args, uint32_t block_cells, b
             if (args.group_hint == 3) return launch_counts<128, 1024, kCapJ128C, kCapL128C, 3>(args, grid, stream, mid);
             return launch_counts<128, 1024, kCapJ128C, kCapL128C, 4>(args, grid, stream, mid);
         }
-        return launch_acc<128, 1024, kCapJ128, kCapL128, 512, false>(args, grid, stream);
+        return launch_acc<128, 1024, kCapJ128, kCapL128, 512>(args, grid, stream);
     }
     // accumulate_masks pairs an item with 3 column entries per pass: C2 clustered (9 entries per cell block and locus)
     // 1.160 / 1.143 / 1.111 ms of accumulate with 4 / 2 / 3 (measured, dropped and then deleted)
-    if (stage_masks && args.masks_kernel) return launch_masks<64, 512, kCapJ64M, kCapL64M, 3>(args, grid, stream);
-    if (stage_masks) return launch_acc<64, 512, kCapJ64M, kCapL64M, 1024, true>(args, grid, stream);
+    if (stage_masks) return launch_masks<64, 512, kCapJ64M, kCapL64M, 3>(args, grid, stream);
     if (count_tile) return launch_counts<64, 512, kCapJ64C, kCapL64C, 4>(args, grid, stream, mid);
-    return launch_acc<64, 256, kCapJ64, kCapL64, 1024, false>(args, grid, stream);
+    return launch_acc<64, 256, kCapJ64, kCapL64, 1024>(args, grid, stream);
 }
 
 __global__ void k_add_terms(long long *acc, const unsigned long long *index, const long long *value, uint32_t n) {

@@ -16,11 +16,12 @@ struct LlrModelDev {  // LlrModel of llr_table.hpp, by value into the kernel
     double ln_u1, ln_v1, ln_u2, ln_v2, ln_w1, ln_z1, ln_w2, ln_z2;
 };
 
-// LDS staging geometry of accumulate_tiles per tile size: column-side entries and loci per locus
-// range, without / with the 8-locus window masks staged too. pack_host.cpp cuts the locus ranges
-// to these limits. LDS per workgroup: B=64: 32 KiB tile + 12/28 KiB; B=128: 128 KiB tile + 24/28 KiB.
+// LDS staging geometry of the pair kernels per tile size: column-side entries and loci per locus range of
+// accumulate_tiles (kCapJ64 / kCapJ128), of accumulate_masks (M, 64-cell tiles only: the 8-locus window masks are
+// staged too) and of accumulate_counts (C). pack_host.cpp cuts the locus ranges to these limits. LDS per workgroup of
+// accumulate_tiles: B=64: 32 KiB tile + 12 KiB; B=128: 128 KiB tile + 24 KiB.
 constexpr uint32_t kCapJ64 = 4096, kCapL64 = 2046, kCapJ64M = 2048, kCapL64M = 2046, kCapJ64C = 4096, kCapL64C = 2046;
-constexpr uint32_t kCapJ128 = 4096, kCapL128 = 2046, kCapJ128M = 4096, kCapL128M = 2046;
+constexpr uint32_t kCapJ128 = 4096, kCapL128 = 2046;
 // the 64 KiB count tile leaves room for longer ranges. Entries per range, C3 pair kernel with one range per segment
 // (pack_device.hip): 6144 2.60 ms, 8192 2.34, 10240 2.33, 12288 2.24 (a range's two barriers, its staging and
 // its prefetch are paid per range; 14336 needs the rings halved and 116 VGPRs: 2.5)
@@ -83,8 +84,7 @@ struct AccumulateArgs {
     int group_hint = 4;                     // GROUP of accumulate_counts by the entries per (cell block, locus)
     bool short_ranges = false;              // no locus range spans more than kCapL128W loci (128-cell count tile)
     bool overwrite = false;                 // acc[tiles of the launch] = result (no need to zero them first)
-    bool masks_kernel = false;              // staged masks: accumulate_masks (+ wide_pairs) instead of accumulate_tiles
-    const uint32_t *mk_y = nullptr, *mk_xcol = nullptr, *mk_xrow = nullptr;  // ... the entries' words (masks_words)
+    const uint32_t *mk_y = nullptr, *mk_xcol = nullptr, *mk_xrow = nullptr;  // accumulate_masks: the entries' words (masks_words)
     const uint32_t *wide_off = nullptr;     // num_blocks + 1: the C_WIDE entries per cell block ...
     const uint32_t *wide_list = nullptr;    // ... their entry indices (null: none)
     // counts path, one workgroup per tile (counts_split(n_tiles) == 1), all tiles in one launch: max(0, max D) of
@@ -118,8 +118,9 @@ size_t accumulate_slab_bytes(uint32_t block_cells, bool count_tile, uint32_t n_w
 
 // stage_masks / count_tile: the kernel variants. count_tile (accumulate_counts + correct_tiles, or its fused
 // epilogue) requires fewer than 65536 pairs per cell pair (PackedPileup::pair_bound), !stage_masks and the flagged
-// entries' lists in AccumulateArgs; stage_masks (accumulate_masks, or accumulate_tiles with MASKS) exists for 64-cell
-// tiles only; neither: accumulate_tiles with the int64 tile. Unless args.overwrite the accumulator is added to.
+// entries' lists in AccumulateArgs; stage_masks (accumulate_masks + wide_pairs) exists for 64-cell tiles only and
+// requires the entries' words and the wide list in AccumulateArgs; neither: accumulate_tiles with the int64 tile.
+// Unless args.overwrite the accumulator is added to.
 // mid: when non-null, recorded on `stream` between the pair kernel and what follows it (the duration of the
 // dominant kernel by itself: secedo_simmat_last_pair_kernel_ms). locus_words: when non-null, whether the launch
 // took accumulate_counts' instance with a staged word per locus (set where the instance is picked)

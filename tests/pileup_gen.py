@@ -94,3 +94,71 @@ def from_rows(rows, n_chr_split=None):
     return FlatPileup(np.asarray(chr_off, dtype=np.uint32), np.asarray(pos, dtype=np.uint32),
                       np.asarray(off, dtype=np.uint64), np.asarray(rid, dtype=np.uint32),
                       np.asarray(idb, dtype=np.uint32))
+
+
+def deep_locus_pileup(seed=313, n_cells=100, block=64, deep_other=0):
+    """A pileup that takes accumulate_tiles by its own data: two cell blocks of 64, 40 loci 40 bp apart with 60
+    entries per block and locus, and early on (its reads are flushed before the pileup ends) one locus with 5000 entries in block 0 -- more than a locus range
+    stages (4096 column entries), so it is paired from HBM, and 300 of them in cell 0, so that a cell pair can
+    collect 65536 pairs and more (300^2: no 16-bit count tile). About 4 % of the entries belong to reads of two or more loci
+    (pairs of two multi-locus reads; too few for the window masks to be staged). deep_other: entries of the other blocks
+    at the deep locus (none, or some: the off-diagonal tile then pairs that range from HBM too)."""
+    rng = np.random.default_rng(seed)
+    n_blocks = (n_cells + block - 1) // block
+    rows, rid, last = [], 0, {}
+    for l in range(41):
+        deep = l == 5
+        ref, ents, now = int(rng.integers(0, 4)), [], {}
+        for b in range(n_blocks):
+            cells_b = min(block, n_cells - b * block)
+            if deep and b == 0:
+                cells = np.concatenate([np.zeros(300, dtype=np.int64), rng.integers(1, cells_b, size=4700)])
+            elif deep:
+                cells = rng.integers(0, cells_b, size=deep_other)
+            else:
+                cells = rng.integers(0, cells_b, size=60)
+            for cell in (cells + b * block).tolist():
+                base = ref if rng.random() < 0.7 else int(rng.integers(0, 4))
+                prev = last.get(cell)
+                if prev is not None and cell not in now and rng.random() < 0.1:
+                    r = prev  # a multi-locus read (at most one entry per locus)
+                else:
+                    r, rid = rid, rid + 1
+                now[cell] = r
+                ents.append((r, cell, base))
+        last = {} if deep else now  # (the deep locus' reads are single-locus: the multi-locus share stays small)
+        rows.append((1000 + 40 * l, ents))
+    return from_rows([rows])
+
+
+def pair_kernel_pileup(name):
+    """(pileup, cells, block_cells or None, the pair kernel it takes by its own data, a non-contiguous tile list or
+    None): clustered loci with reads that reach beyond their 8- and 16-locus windows (4 blocks of 64, 10 tiles, 17000
+    entries per full block against 2048 staged: many locus ranges and many workgroups per tile), sparse loci, and the
+    deep locus above (3 tiles)."""
+    if name == "clustered":
+        p = random_pileup(311, 200, 2, 900, 30, 12, frag_min=20, frag_max=260, dup_frac=0.03)
+        return p, 200, None, "accumulate_masks", [0, 3, 9]
+    if name == "sparse":
+        p = random_pileup(312, 300, 2, 1500, 40, 30000, frag_min=30, frag_max=500, dup_frac=0.03)
+        return p, 300, None, "accumulate_counts", None
+    if name == "deep":
+        return deep_locus_pileup(), 100, 64, "accumulate_tiles", [0, 2]
+    if name == "deep_offdiag":
+        # 300 entries of block 1 at the deep locus: the off-diagonal tile pairs that range from HBM as well
+        return deep_locus_pileup(deep_other=300), 100, 64, "accumulate_tiles", [0, 2]
+    if name in ("clustered_thin", "sparse_thin", "deep_thin"):
+        # one more cell block of two cells with one entry each, at an early locus (flushed): the last tile, that block
+        # against itself, has two row entries and as many workgroups as the pileup has locus ranges -- shares without
+        # a row entry. The tile list is that tile alone.
+        p, n, block, kernel, _ = pair_kernel_pileup(name[:-5])
+        first = (n + 63) // 64 * 64
+        at = int(p.locus_entry_off[4])  # behind the entries of locus 3
+        rid = int(p.read_ids.max()) + 1
+        off = p.locus_entry_off.copy()
+        off[4:] += 2
+        thin = FlatPileup(p.chr_locus_off, p.locus_pos, off,
+                          np.insert(p.read_ids, at, [rid, rid + 1]).astype(np.uint32),
+                          np.insert(p.id_base, at, [(first << 2) | 1, ((first + 1) << 2) | 2]).astype(np.uint32))
+        return thin, first + 2, 64, kernel, "last"
+    raise KeyError(name)

@@ -739,53 +739,81 @@ def test_plain_copy_readbacks_give_the_same_matrix(tmp_path):
     assert gu.normwise_err(outs[0], ref) <= TOL
 
 
-def test_masks_kernel_variants_agree_and_match_the_oracle(tmp_path):
-    """SECEDO_MASKS_KERNEL=0 selects another kernel for the same integer sums (read once per process: child
-    processes): clustered loci with reads that reach beyond their 8- and 16-locus windows -- accumulate_masks +
-    wide_pairs (default) against accumulate_tiles. The un-normalised matrices and both work counters must be
-    bit-identical (the accumulators themselves may differ inside diagonal tiles, which hold a pair in either
-    orientation). The default run of both pileups -- sparse loci run accumulate_counts -- is held to the oracle: the
-    raw matrix norm-wise, the work counters exactly."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = "\n".join([
-        "import numpy as np, sys, torch",
-        "sys.path.insert(0, %r)" % root,
-        "import secedo_amd",
-        "from tests.pileup_gen import random_pileup",
-        "clustered = random_pileup(311, 200, 2, 900, 30, 12, frag_min=20, frag_max=260, dup_frac=0.03)   # 4 blocks of 64, spans up to 40 loci",
-        "sparse = random_pileup(312, 300, 2, 1500, 40, 30000, frag_min=30, frag_max=500, dup_frac=0.03)",
-        "out = {}",
-        "for name, p, n in (('clustered', clustered, 200), ('sparse', sparse, 300)):",
-        "    with secedo_amd.SimilarityMatrixPlan(0) as plan:",
-        "        plan.prepare(p, n, 1000, None, 2)",
-        "        acc = plan.new_acc()",
-        "        plan.accumulate(acc, 0.01, 0.5, 0.01)",
-        "        torch.cuda.synchronize()",
-        "        out[name] = plan.finalize_raw(acc).cpu().numpy()",
-        "        out[name + '_counts'] = np.asarray(plan.last_counts(), dtype=np.uint64)",
-        "        out[name + '_kernel'] = np.frombuffer(plan.pair_kernel.encode(), dtype=np.uint8)",
-        "np.savez(sys.argv[1], **out)"])
-    runs = {}
-    for tag, env in (("default", {}), ("tiles", {"SECEDO_MASKS_KERNEL": "0"})):
-        out = str(tmp_path / (tag + ".npz"))
-        subprocess.run([sys.executable, "-c", script, out], check=True, env=dict(os.environ, **env), timeout=600)
-        runs[tag] = np.load(out)
-    kern = lambda z, name: bytes(z[name + "_kernel"]).decode()
-    assert kern(runs["default"], "clustered") == "accumulate_masks" and kern(runs["tiles"], "clustered") == "accumulate_tiles"
-    assert kern(runs["default"], "sparse") == "accumulate_counts"
+def _pair_kernel_matches_the_oracle(name):
+    """One pileup of tests/pileup_gen.py: pair_kernel_pileup, which takes its pair kernel by its own data. The
+    un-normalised matrix is held to the oracle norm-wise -- to its direct sums where a cell pair averages more than 1e4
+    read pairs (the oracle's own cancellation, as test_gpu_counts_items.py) --, both work counters exactly. Then the same
+    through a stored list of non-contiguous tiles and the list of the others: the accumulator bit for bit, the two
+    launches' counters adding up to the oracle's."""
+    import torch
+    from tests.pileup_gen import pair_kernel_pileup
+    p, n, block, kernel, tile_list = pair_kernel_pileup(name)
+    _, raw = ob.oracle_compute(p, n, 1000, None, 0.01, 0.5, 0.01, 2, "ADD_MIN", want_raw=True)
+    counts_ref = (ob.oracle_last_updates(), ob.oracle_last_read_pairs())
+    if counts_ref[1] / max(1.0, n * (n - 1) / 2) > 1e4:
+        ob.set_direct_llr_sum(True)
+        try:
+            _, raw = ob.oracle_compute(p, n, 1000, None, 0.01, 0.5, 0.01, 2, "ADD_MIN", want_raw=True)
+        finally:
+            ob.set_direct_llr_sum(False)
+    with secedo_amd.SimilarityMatrixPlan(0) as plan:
+        if block:
+            plan.prepare(p, n, 1000, None, 2, block_cells=block)
+        else:
+            plan.prepare(p, n, 1000, None, 2)
+        assert plan.pair_kernel == kernel
+        acc = plan.new_acc()
+        plan.accumulate(acc, 0.01, 0.5, 0.01)
+        torch.cuda.synchronize()
+        got = plan.finalize_raw(acc).cpu().numpy()
+        counts = plan.last_counts()
+        print("%s: %s, %d tiles, norm-wise %.2e, counters %s" % (name, kernel, plan.num_tiles,
+                                                                  gu.normwise_err(got, raw), counts))
+        assert gu.normwise_err(got, raw) <= TOL
+        assert counts == counts_ref
+        assert np.any(got != 0)
+        if name.startswith("deep"):
+            # three locus ranges at least (before, at and behind the deep locus), a workgroup per tile and range
+            from secedo_amd import _lib
+            assert _lib.lib().secedo_simmat_last_workgroups(plan._h) >= 3 * plan.num_tiles
+        if tile_list is not None:
+            listed = np.asarray([plan.num_tiles - 1] if tile_list == "last" else tile_list, dtype=np.uint32)
+            others = np.setdiff1d(np.arange(plan.num_tiles, dtype=np.uint32), listed)
+            assert listed.max() < plan.num_tiles and len(others)
+            acc2 = torch.full_like(acc, 0x0123456789ABCDEF)
+            plan.accumulate_list(acc2, 0.01, 0.5, 0.01, listed, overwrite=True)
+            c1 = plan.last_counts()
+            if tile_list == "last":
+                from secedo_amd import _lib
+                assert _lib.lib().secedo_simmat_last_workgroups(plan._h) > 2
+            plan.accumulate_list(acc2, 0.01, 0.5, 0.01, others, overwrite=True)
+            c2 = plan.last_counts()
+            torch.cuda.synchronize()
+            got2 = plan.finalize_raw(acc2).cpu().numpy()
+            print("%s by lists: counters %s + %s" % (name, c1, c2))
+            assert (c1[0] + c2[0], c1[1] + c2[1]) == counts_ref
+            assert 0 < c1[0] < counts_ref[0]
+            assert gu.normwise_err(got2, raw) <= TOL
+            b2 = plan.block_cells ** 2
+            assert torch.equal(acc2[:plan.num_tiles * b2], acc[:plan.num_tiles * b2])
+
+
+def test_each_pair_kernel_by_its_own_data_matches_the_oracle():
+    """Clustered loci with reads that reach beyond their 8- and 16-locus windows run accumulate_masks + wide_pairs,
+    sparse loci run accumulate_counts: the kernel names, the raw matrix against the oracle norm-wise, both work
+    counters exactly, a result that is not zero; the clustered pileup once more by tile lists [0, 3, 9] and the rest."""
     for name in ("clustered", "sparse"):
-        assert np.array_equal(runs["tiles"][name], runs["default"][name]), name
-        assert np.array_equal(runs["tiles"][name + "_counts"], runs["default"][name + "_counts"]), name
-    assert np.any(runs["default"]["clustered"] != 0) and np.any(runs["default"]["sparse"] != 0)
-    clustered = random_pileup(311, 200, 2, 900, 30, 12, frag_min=20, frag_max=260, dup_frac=0.03)
-    sparse = random_pileup(312, 300, 2, 1500, 40, 30000, frag_min=30, frag_max=500, dup_frac=0.03)
-    for name, p, n in (("clustered", clustered, 200), ("sparse", sparse, 300)):
-        _, raw = ob.oracle_compute(p, n, 1000, None, 0.01, 0.5, 0.01, 2, "ADD_MIN", want_raw=True)
-        counts_ref = (ob.oracle_last_updates(), ob.oracle_last_read_pairs())
-        assert gu.normwise_err(runs["default"][name], raw) <= TOL, name
-        assert tuple(int(c) for c in runs["default"][name + "_counts"]) == counts_ref, name
+        _pair_kernel_matches_the_oracle(name)
+
+
+@pytest.mark.parametrize("name", ["deep", "deep_offdiag", "clustered_thin", "sparse_thin", "deep_thin"])
+def test_pair_kernel_chunk_edges_match_the_oracle(name):
+    """The same checks where the shared tile and chunk walk can go wrong: accumulate_tiles on a deep locus (a range
+    paired from HBM in the diagonal tile and, for deep_offdiag, in the off-diagonal one too; three workgroups or more
+    per tile, with shares that begin inside a range; tile list [0, 2]), and the _thin pileups with a last cell block of
+    two entries: its tile, launched alone, gets more workgroups than it has row entries (shares of the row side that
+    are empty), under each of accumulate_masks, accumulate_counts and accumulate_tiles."""
+    _pair_kernel_matches_the_oracle(name)
 
 
 def test_staging_buffers_are_handed_to_one_caller_at_a_time():
