@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 namespace secedo {
 
@@ -722,7 +723,8 @@ constexpr uint32_t IT_REC_MASK = 0x1FFu;  // cell (7 bits) | base (2 bits)
 // (with seven vector instructions per slot, before col32, the empty slots of GROUP 4 cost more than the trips
 // through the ring: 4.87 / 4.49 / 4.38 / 5.62 on C3.) 4 by default, 2 below 2.5 entries per block and locus,
 // 3 below 3.2 (AccumulateArgs::group_hint); GROUP 1, 5, 6 and 8 were measured, dropped and then deleted.
-// Off the diagonal the pair slot is five hand-placed instructions between one s_and_saveexec and one s_mov exec.
+// Off the diagonal the slots of a group are one hand-placed block (group_pair; until round 19 GROUP 3 had three single
+// slots, five instructions between one s_and_saveexec and one s_mov exec each).
 // From the C++ form (pair_slot, which diagonal tiles keep) the compiler builds, per slot, saveexec + a branch around
 // the (out-of-line) body + s_or exec + the test of the wave-uniform `diag` flag with its branch: five scalar / branch
 // instructions for three vector ones and the ds_add -- 0.63e9 scalar instructions per C3 launch through the ONE
@@ -736,6 +738,11 @@ template <bool WORDS>
 __device__ __forceinline__ uint32_t counts_off_at(const uint16_t *sOff, uint32_t l) {
     if constexpr (WORDS) return (reinterpret_cast<const uint32_t *>(sOff)[l] >> IT_J_SHIFT) & IT_J_MASK;
     else return sOff[l];
+}
+// f(integral_constant<int, K>) for K = 0, 1, ...: a loop whose index is a constant in its body
+template <int... K, class F>
+__device__ __forceinline__ void for_each_index(std::integer_sequence<int, K...>, F &&f) {
+    (f(std::integral_constant<int, K>{}), ...);
 }
 template <int B, int THREADS, int CAPJ, int CAPL, int GROUP, bool WORDS>
 __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArgs a) {
@@ -878,7 +885,10 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
         // operand selects three vector instructions and the ds_add
         // the tile's place in LDS as ds_add takes it (the dynamic segment starts behind whatever static LDS the
         // kernel's helpers use): folded into the row offset of the hand-placed slot
-        const uint32_t lds_base = (uint32_t)reinterpret_cast<uintptr_t>(lds_raw);
+        // (taken from the LDS pointer itself: through the generic pointer the compiler tests the address for null --
+        // s_cmp + s_cselect -- wherever it rebuilds the constant, once per group step)
+        const uint32_t lds_base = (uint32_t)reinterpret_cast<uintptr_t>(
+                (__attribute__((address_space(3))) unsigned char *)lds_raw);
         auto pair_slot = [&](uint32_t rec9, uint32_t row_byte, uint32_t w, unsigned long long in) {
             if (DIAG) in &= __ballot((w & 0xFFFFu) != ((rec9 & C_CELL) << 2));  // same cell (:215)
             upd_w += (uint32_t)__popcll(in);
@@ -887,41 +897,60 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                 atomicAdd(reinterpret_cast<uint32_t *>(lds_raw + addr),
                           (w >> 16) != (rec9 >> C_BASE_SHIFT) ? 0x10000u : 1u);
         };
-        // the slot by hand, tiles off the diagonal (all but one in num_blocks): exec = in; same base? (third byte of w
-        // against the row entry's base); address = row + low half of w; 1 or 0x10000; ds_add; exec back. (The
-        // s_nop covers the SDWA compare's write of vcc before v_cndmask reads it, as in the compiler's own
-        // sequence. lgkmcnt: the compiler does not see this ds_add; LDS returns in order, so its counted waits
-        // for earlier reads can only become stricter.)
-        auto pair_slot_asm = [&](uint32_t rbase, uint32_t row_addr, uint32_t w, unsigned long long in) {
-            // (the updates counted elsewhere -- per lane in the group, v_min + v_add, or as the items' column entries
-            // when the items are built -- instead of this scalar population count per slot: C5 7-8 % slower both times)
-            upd_w += (uint32_t)__popcll(in);
-            uint32_t addr, val;
-            unsigned long long saved;
-            asm volatile("s_and_saveexec_b64 %[saved], %[in]\n\t"
-                         "v_cmp_eq_u32_sdwa vcc, %[w], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
-                         "v_add_u32_sdwa %[addr], %[row], %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD "
-                         "src1_sel:WORD_0\n\t"
-                         "s_nop 0\n\t"
-                         "v_cndmask_b32_e64 %[val], %[k], 1, vcc\n\t"
-                         "ds_add_u32 %[addr], %[val]\n\t"
-                         "s_mov_b64 exec, %[saved]"
-                         : [saved] "=&s"(saved), [addr] "=&v"(addr), [val] "=&v"(val)
-                         : [in] "s"(in), [w] "v"(w), [rb] "v"(rbase), [row] "v"(row_addr), [k] "v"(0x10000u)
-                         : "vcc", "memory");
+        // COUNTED WAITS (round 19). The column words of an item are read by hand (group_load: ds_read2_b32 / ds_read_b32
+        // in an asm statement), so the compiler neither tracks them nor waits for them, and the slot block of the item
+        // begins with ONE s_waitcnt lgkmcnt(N) of its own, N an immediate: the number of LDS instructions this wave is
+        // CERTAIN to have issued behind the reads it waits for. The primary loop loads TWO items ahead:
+        //     reads(0) reads(1) | reads(2) wait(0) adds(0) | reads(3) wait(1) adds(1) | ... | wait(JPT-1) adds(JPT-1)
+        // so behind reads(k) lie the GROUP ds_add of items k-2 and k-1 and the NREADS reads of items k+1 and k+2, as far
+        // as those items exist: N = 12 in the middle of GROUP 4's loop (10 / 6 for GROUP 3 / 2), 4 and 8 at its first two
+        // items, 10 and 8 at its last two; the counter has four bits. (One item ahead -- N = 6, a wave waits for reads
+        // issued one step earlier -- took 1.6 % off the pair kernel on C3, two ahead 2.6 %: profiles/README.md, round
+        // 19.) What is issued
+        // only sometimes -- the ring's ds_write_b32, a whole drain_one() between a load and its pair -- is left out of
+        // the count: when it occurs the wait is stricter, never weaker. Before round 19 the loads were the compiler's,
+        // which cannot see the ds_add of the hand-placed slots and met the conditional drain_one() loop between load
+        // and use: it put s_waitcnt lgkmcnt(0) in front of every step. That was accepted as harmless ("its counted
+        // waits can only become stricter") and is, for the result; but with it a wave sat out the round trip of its own
+        // four atomics and of the reads issued an instant before, once per step, behind the fifteen other waves of
+        // the CU in the LDS queue, and its ~25 vector and ~22 scalar instructions never ran beside its own LDS work.
+        // What the counts rest on (checked in the disassembly of every instance, profiles/r19_pair_kernel_codegen.txt):
+        //   * LDS operations of a wave return in order, so "at most N outstanding" means "all but the last N are done".
+        //   * No scalar memory load is in flight inside the range loop (scalar loads share the counter and return out of
+        //     order): every s_load of the kernel lies in its prologue. A change that makes the compiler reload a kernel
+        //     argument inside the loop has to hoist it.
+        //   * An LDS instruction issued under an empty exec mask still counts (the compiler's own counting assumes so for
+        //     every short block it runs with exec = 0).
+        //   * The operand registers of a ds_add may be overwritten right after issue (the compiler's own C++ slot does).
+        //   * The compiler takes an asm load's destination as written when the statement ends, so nothing may touch the
+        //     word registers between their load and their wait: three fixed sets in rotation through the unrolled
+        //     loop, no copy from "next" to "current", and the audit looks for v_mov / spills of them.
+        // The compiler's own waits (ring word, item words, staging) stay right: it counts only what it sees, the unseen
+        // operations behind a read make its counted wait stricter, and unseen ones in front of it have returned earlier.
+        constexpr int NREADS = GROUP == 2 ? 1 : 2;  // LDS read instructions per item
+        struct Words {             // the column words of one item: w01 = {w0, w1}; {w2, w3} in w23, or w2 alone (GROUP 3)
+            unsigned long long w01, w23;
+            uint32_t w2;
         };
 
         // 64 items, each against its first GROUP column entries; items with more go to the ring.
-        // group_load reads the column entries, group_pair does the rest: the primary batches issue the reads
-        // of the next item before they pair the current one.
-        auto group_load = [&](uint32_t item, uint32_t (&w)[GROUP]) {
-            const uint32_t *p = sJ + ((item >> IT_J_SHIFT) & IT_J_MASK);
+        // group_load issues the reads of the column entries, group_pair<WN> waits for them and does the rest: the primary
+        // batches issue the reads of the item after the next before they pair the current one.
+        auto group_load = [&](uint32_t item, Words &w) {
             // lanes with fewer than GROUP read on inside the staging area (or the offsets behind it): harmless,
             // masked by `in`
-#pragma unroll
-            for (int u = 0; u < GROUP; ++u) w[u] = p[u];
+            const uint32_t pa = lds_base + (uint32_t)TILE_BYTES + (((item >> IT_J_SHIFT) & IT_J_MASK) << 2);
+            if constexpr (GROUP == 4)
+                asm volatile("ds_read2_b32 %0, %2 offset1:1\n\tds_read2_b32 %1, %2 offset0:2 offset1:3"
+                             : "=&v"(w.w01), "=v"(w.w23) : "v"(pa) : "memory");
+            else if constexpr (GROUP == 3)
+                asm volatile("ds_read2_b32 %0, %2 offset1:1\n\tds_read_b32 %1, %2 offset:8"
+                             : "=&v"(w.w01), "=v"(w.w2) : "v"(pa) : "memory");
+            else
+                asm volatile("ds_read2_b32 %0, %1 offset1:1" : "=v"(w.w01) : "v"(pa) : "memory");
         };
-        auto group_pair = [&](uint32_t item, const uint32_t (&w)[GROUP]) {
+        auto group_pair = [&](uint32_t item, Words &wd, auto wn_c) {
+            constexpr int WN = decltype(wn_c)::value;  // LDS instructions certainly issued behind this item's reads
             const uint32_t c = item >> IT_C_SHIFT;
             const uint32_t rec9 = item & IT_REC_MASK;
             const uint32_t row_byte = (item & C_CELL) * (ROW_WORDS * 4u);
@@ -930,8 +959,9 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
             for (int u = 0; u < GROUP; ++u) in[u] = __ballot(c > (uint32_t)u);
             const unsigned long long more = __ballot(c > (uint32_t)GROUP);
             // (the wave-uniform `diag` flag is tested once per group, not once per slot)
-            if (!DIAG && (GROUP == 4 || GROUP == 2)) {
-                // The slots of a group as ONE block (round 4): the compares, addresses and values of all slots under
+            if (!DIAG) {
+                // The slots of a group as ONE block (round 4; GROUP 3 since round 19): the counted wait for the item's
+                // words, then the compares, addresses and values of all slots under
                 // the group's exec -- a lane that does not take part computes garbage nobody adds --, each compare
                 // into a scalar pair of its own, and only the ds_add under the slot's lanes. Per slot that is one
                 // s_mov instead of s_and_saveexec + s_nop + s_mov: the scalar unit, which a CU has once, was busy
@@ -940,10 +970,13 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                 const uint32_t rbase = rec9 >> C_BASE_SHIFT, row_addr = lds_base + row_byte;
 #pragma unroll
                 for (int u = 0; u < GROUP; ++u) upd_w += (uint32_t)__popcll(in[u]);
+                const uint32_t w0 = (uint32_t)wd.w01, w1 = (uint32_t)(wd.w01 >> 32);
                 uint32_t a0, a1, a2, a3, v0, v1, v2, v3;
                 unsigned long long saved, q0, q1, q2, q3;
-                if (GROUP == 4) {
-                    asm volatile("v_cmp_eq_u32_sdwa %[q0], %[w0], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+                if constexpr (GROUP == 4) {
+                    const uint32_t w2 = (uint32_t)wd.w23, w3 = (uint32_t)(wd.w23 >> 32);
+                    asm volatile("s_waitcnt lgkmcnt(%[wn])\n\t"
+                                 "v_cmp_eq_u32_sdwa %[q0], %[w0], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
                                  "v_cmp_eq_u32_sdwa %[q1], %[w1], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
                                  "v_cmp_eq_u32_sdwa %[q2], %[w2], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
                                  "v_cmp_eq_u32_sdwa %[q3], %[w3], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
@@ -968,12 +1001,40 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                                  : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [v0] "=&v"(v0), [v1] "=&v"(v1),
                                    [v2] "=&v"(v2), [v3] "=&v"(v3), [saved] "=&s"(saved), [q0] "=&s"(q0), [q1] "=&s"(q1),
                                    [q2] "=&s"(q2), [q3] "=&s"(q3)
-                                 : [w0] "v"(w[0]), [w1] "v"(w[1 % GROUP]), [w2] "v"(w[2 % GROUP]), [w3] "v"(w[3 % GROUP]),
+                                 : [w0] "v"(w0), [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3),
                                    [rb] "v"(rbase), [row] "v"(row_addr), [k] "v"(0x10000u), [in0] "s"(in[0]),
-                                   [in1] "s"(in[1 % GROUP]), [in2] "s"(in[2 % GROUP]), [in3] "s"(in[3 % GROUP])
+                                   [in1] "s"(in[1 % GROUP]), [in2] "s"(in[2 % GROUP]), [in3] "s"(in[3 % GROUP]), [wn] "n"(WN)
                                  : "memory");
+                } else if constexpr (GROUP == 3) {
+                    const uint32_t w2 = wd.w2;
+                    asm volatile("s_waitcnt lgkmcnt(%[wn])\n\t"
+                                 "v_cmp_eq_u32_sdwa %[q0], %[w0], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+                                 "v_cmp_eq_u32_sdwa %[q1], %[w1], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+                                 "v_cmp_eq_u32_sdwa %[q2], %[w2], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+                                 "v_add_u32_sdwa %[a0], %[row], %[w0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0\n\t"
+                                 "v_add_u32_sdwa %[a1], %[row], %[w1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0\n\t"
+                                 "v_add_u32_sdwa %[a2], %[row], %[w2] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0\n\t"
+                                 "s_mov_b64 %[saved], exec\n\t"
+                                 "v_cndmask_b32_e64 %[v0], %[k], 1, %[q0]\n\t"
+                                 "v_cndmask_b32_e64 %[v1], %[k], 1, %[q1]\n\t"
+                                 "v_cndmask_b32_e64 %[v2], %[k], 1, %[q2]\n\t"
+                                 "s_mov_b64 exec, %[in0]\n\t"
+                                 "ds_add_u32 %[a0], %[v0]\n\t"
+                                 "s_mov_b64 exec, %[in1]\n\t"
+                                 "ds_add_u32 %[a1], %[v1]\n\t"
+                                 "s_mov_b64 exec, %[in2]\n\t"
+                                 "ds_add_u32 %[a2], %[v2]\n\t"
+                                 "s_mov_b64 exec, %[saved]"
+                                 : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [v0] "=&v"(v0), [v1] "=&v"(v1), [v2] "=&v"(v2),
+                                   [saved] "=&s"(saved), [q0] "=&s"(q0), [q1] "=&s"(q1), [q2] "=&s"(q2)
+                                 : [w0] "v"(w0), [w1] "v"(w1), [w2] "v"(w2), [rb] "v"(rbase), [row] "v"(row_addr),
+                                   [k] "v"(0x10000u), [in0] "s"(in[0]), [in1] "s"(in[1 % GROUP]), [in2] "s"(in[2 % GROUP]),
+                                   [wn] "n"(WN)
+                                 : "memory");
+                    (void)a3; (void)v3; (void)q3;
                 } else {
-                    asm volatile("v_cmp_eq_u32_sdwa %[q0], %[w0], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
+                    asm volatile("s_waitcnt lgkmcnt(%[wn])\n\t"
+                                 "v_cmp_eq_u32_sdwa %[q0], %[w0], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
                                  "v_cmp_eq_u32_sdwa %[q1], %[w1], %[rb] src0_sel:WORD_1 src1_sel:DWORD\n\t"
                                  "v_add_u32_sdwa %[a0], %[row], %[w0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0\n\t"
                                  "v_add_u32_sdwa %[a1], %[row], %[w1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0\n\t"
@@ -987,18 +1048,24 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                                  "s_mov_b64 exec, %[saved]"
                                  : [a0] "=&v"(a0), [a1] "=&v"(a1), [v0] "=&v"(v0), [v1] "=&v"(v1), [saved] "=&s"(saved),
                                    [q0] "=&s"(q0), [q1] "=&s"(q1)
-                                 : [w0] "v"(w[0]), [w1] "v"(w[1 % GROUP]), [rb] "v"(rbase), [row] "v"(row_addr), [k] "v"(0x10000u),
-                                   [in0] "s"(in[0]), [in1] "s"(in[1 % GROUP])
+                                 : [w0] "v"(w0), [w1] "v"(w1), [rb] "v"(rbase), [row] "v"(row_addr), [k] "v"(0x10000u),
+                                   [in0] "s"(in[0]), [in1] "s"(in[1 % GROUP]), [wn] "n"(WN)
                                  : "memory");
                     (void)a2; (void)a3; (void)v2; (void)v3; (void)q2; (void)q3;
                 }
-            } else if (!DIAG) {
-                const uint32_t rbase = rec9 >> C_BASE_SHIFT, row_addr = lds_base + row_byte;
-#pragma unroll
-                for (int u = 0; u < GROUP; ++u) pair_slot_asm(rbase, row_addr, w[u], in[u]);
             } else {
-#pragma unroll
-                for (int u = 0; u < GROUP; ++u) pair_slot(rec9, row_byte, w[u], in[u]);
+                // diagonal tiles (63 of 2016 on C3) use the words in C++: a wait-only statement that names every word
+                // register, so that the compiler's first use of them lies behind it. Not worth counting.
+                if constexpr (GROUP == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wd.w01), "+v"(wd.w23)::"memory");
+                else if constexpr (GROUP == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wd.w01), "+v"(wd.w2)::"memory");
+                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wd.w01)::"memory");
+                pair_slot(rec9, row_byte, (uint32_t)wd.w01, in[0]);
+                pair_slot(rec9, row_byte, (uint32_t)(wd.w01 >> 32), in[1]);
+                if constexpr (GROUP == 3) pair_slot(rec9, row_byte, wd.w2, in[2 % GROUP]);
+                if constexpr (GROUP == 4) {
+                    pair_slot(rec9, row_byte, (uint32_t)wd.w23, in[2 % GROUP]);
+                    pair_slot(rec9, row_byte, (uint32_t)(wd.w23 >> 32), in[3 % GROUP]);
+                }
             }
             if (more) {
                 if (__builtin_amdgcn_inverse_ballot_w64(more)) {
@@ -1009,10 +1076,11 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                 ring_tail += (uint32_t)__popcll(more);
             }
         };
+        // a batch by itself (the ring's): reads, then the full wait
         auto group4 = [&](uint32_t item) {
-            uint32_t w[GROUP];
+            Words w;
             group_load(item, w);
-            group_pair(item, w);
+            group_pair(item, w, std::integral_constant<int, 0>{});
         };
         // one batch from the ring (up to 64 items)
         auto drain_one = [&]() {
@@ -1126,17 +1194,19 @@ __global__ __launch_bounds__(THREADS) void accumulate_counts(const AccumulateArg
                 if (r + 1 < r_end) prefetch(r + 1);  // pJ / pO are free again: the next range's column side
                 STAMP(s3);
                 {
-                    uint32_t wc[GROUP], wn[GROUP];
-                    group_load(item[0], wc);
-#pragma unroll
-                    for (int k = 0; k < JPT; ++k) {
-                        if (k + 1 < JPT) group_load(item[k + 1], wn);
+                    // three fixed word sets in rotation (no copy: see COUNTED WAITS), loads two items ahead
+                    Words ws[3];
+                    group_load(item[0], ws[0]);
+                    if (JPT > 1) group_load(item[1 % JPT], ws[1]);
+                    for_each_index(std::make_integer_sequence<int, JPT>{}, [&](auto kc) {
+                        constexpr int k = decltype(kc)::value;
+                        if constexpr (k + 2 < JPT) group_load(item[k + 2], ws[(k + 2) % 3]);
                         // room for 64 more continuations (a drained batch may push up to 64 itself)
                         while (ring_tail - ring_head > (uint32_t)(RING - 64)) drain_one();
-                        group_pair(item[k], wc);
-#pragma unroll
-                        for (int u = 0; u < GROUP; ++u) wc[u] = wn[u];
-                    }
+                        constexpr int WN = (k >= 2 ? GROUP : 0) + (k >= 1 ? GROUP : 0) + (k + 1 < JPT ? NREADS : 0)
+                                         + (k + 2 < JPT ? NREADS : 0);
+                        group_pair(item[k], ws[k % 3], std::integral_constant<int, WN>{});
+                    });
                 }
                 // (the row side right after the column side, its registers being free once the items are built, was
                 // measured slower: C3 2.84 against 2.77 ms, C5 28.5 against 26.5)
