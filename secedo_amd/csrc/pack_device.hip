@@ -16,6 +16,17 @@
 //   5  kept entries grouped by (cell block, locus, cell) -- per-locus LDS histograms, scan, placement,
 //      in-group ranking (or the radix sort) --, block offsets, pair bound, locus ranges, entry records
 //      (window masks) written at their final position
+//
+// The host half (struct PackAttempt, at the end of the file) is a function per stage and per route of a stage, over
+// the views of pack_workspace.hpp:
+//   1    group_by_read -> group_by_read_single_entry | group_by_read_counting | group_by_read_radix
+//   2-4  build_reads (reads, completed counts, the flush chain on the side stream), settle_flush_cuts (k_split_update
+//        to its fixed point)
+//   5    plan_tiles (cell blocks, staging limits, segments: host only), bin_counting | bin_radix,
+//        records_counting | records_radix, close_attempt (read-back 3, the repair of wrongly assumed limits, the
+//        fields of DevicePacked)
+// scalar_verdict turns a read-back of the scalars into what the attempt does next; an attempt ends as one Attempt
+// value (done, need the host, retry with the radix sorts, retry without assumptions, or an error with its text).
 #include "pack_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -190,7 +201,6 @@ struct HostTrace {
 // stable sort gives. A group longer than kRankScanLimit raises Scalars::regroup and the caller
 // falls back to the radix sorts.
 constexpr uint32_t kRankScanLimit = 8192;
-constexpr int kNoRetry = 0, kRetryRadix = 1, kRetrySameScheme = 2;  // what an attempt asks of its caller
 constexpr int kMaxSplitRounds = 32;  // rounds of k_split_update before the host emulation takes over
 // the counting scheme for read ids needs a table over the id space: used while max id < factor * entries
 constexpr uint32_t kIdSpaceFactor = 4;
@@ -514,7 +524,7 @@ __global__ void k_id_rank(Raw in, const uint32_t *dense, const uint32_t *id_off,
 // k_flag_scan, k_compact_m) where a scan that gathers hist[dense[e]] took 155 us; the reads of the M entries are
 // the groups of equal winner (k_m_fields counts them per winner, a scan over the M entries, k_group_scatter,
 // k_group_rank): no offsets over the id space (104 us), no histogram of the repeated ids.
-constexpr uint32_t kFlagBlock = 4096;      // entries per workgroup of the numbering passes
+// (kFlagBlock entries per workgroup of the numbering passes: pack_workspace.hpp)
 // (a thread takes four consecutive entries, 16 bytes per lane and stream; `vec`: the caller's read-id array is 16-byte
 // aligned -- the tables of this file are)
 // (The dense id is made twice, here and in k_id_check, from the entry's id and index: until round 17 this kernel read
@@ -777,26 +787,7 @@ __global__ __launch_bounds__(TPB) void k_pflag_groups(const uint32_t *blk_off, s
         grp[i] = chunk_pre[c] + (r ? (uint32_t)__popcll(chunk_mask[c] & ((1ull << r) - 1ull)) : 0u);
     }
 }
-// flag_list_scratch: block sums and offsets (nb each), chunk_pre (64 nb + 1), chunk_mask (64 nb, 8-byte aligned)
-uint32_t flag_blocks(uint32_t n_entries) { return std::max<uint32_t>(1u, (n_entries + kFlagBlock - 1) / kFlagBlock); }
-struct FlagScratch {
-    uint32_t nb;
-    uint32_t *block_sum, *block_off, *chunk_pre;
-    unsigned long long *chunk_mask;
-    FlagScratch(void *scratch, uint32_t n_entries) : nb(flag_blocks(n_entries)) {
-        block_sum = block_off = chunk_pre = nullptr;
-        chunk_mask = nullptr;
-        if (!scratch) return;
-        block_sum = static_cast<uint32_t *>(scratch);
-        block_off = block_sum + nb;
-        chunk_pre = block_off + nb;
-        chunk_mask = reinterpret_cast<unsigned long long *>(chunk_pre + 64 * (size_t)nb + 2);
-    }
-    static size_t bytes(uint32_t n_entries) {
-        const size_t nb = flag_blocks(n_entries);
-        return (2 * nb + 64 * nb + 2) * 4 + 64 * nb * 8;
-    }
-};
+// (the flag lists' scratch, struct FlagScratch: pack_workspace.hpp)
 void flag_groups(const FlagScratch &fs, const uint32_t *blk_off, size_t n_off, uint32_t *grp, hipStream_t stream) {
     if (!n_off) return;
     const uint32_t blocks = (uint32_t)std::min<size_t>((n_off + TPB - 1) / TPB, 256 * 32);
@@ -1975,446 +1966,117 @@ int bits_for(unsigned long long max_value) {
     return b;
 }
 
-#define HIP_OK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t e__ = (expr);                                                          \
-        if (e__ != hipSuccess) return std::string(#expr) + ": " + hipGetErrorString(e__); \
+// ---- the host half: one attempt at the pipeline, a function per stage and per route of a stage ------------------
+
+// What an attempt, or a step of one, comes to. Go: on with the next step (no attempt ends with it).
+struct Attempt {
+    enum Kind { Go, Done, NeedHost, RetryRadix, RetryPlain, Error } kind = Go;
+    std::string text;  // of an Error
+    bool go() const { return kind == Go; }
+    static Attempt stop(Kind k) {
+        Attempt a;
+        a.kind = k;
+        return a;
+    }
+    static Attempt error(std::string t) {
+        Attempt a;
+        a.kind = Error;
+        a.text = std::move(t);
+        return a;
+    }
+};
+
+#define HIP_OK(expr)                                                                                      \
+    do {                                                                                                  \
+        hipError_t e__ = (expr);                                                                          \
+        if (e__ != hipSuccess) return Attempt::error(std::string(#expr) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+#define STEP(expr)                  \
+    do {                            \
+        Attempt a__ = (expr);       \
+        if (!a__.go()) return a__;  \
     } while (0)
 
-// One attempt at the pipeline. With force_radix == false the two groupings (entries by read,
-// kept entries by (cell block, locus)) use the counting scheme when its preconditions hold; a group
-// too long for it sets *retry and the caller runs the attempt again with the radix sorts.
-std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_t mfl, uint32_t num_threads,
-                         uint32_t block_cells, StageGeometry (*geometry)(uint32_t), bool allow_count_tile,
-                         bool force_radix, bool no_assumptions, bool overlap, hipStream_t stream, DevicePacked *out,
-                         bool *need_host, int *retry) {
-    *retry = kNoRetry;
-    const uint32_t E = static_cast<uint32_t>(in.n_entries);
-    const uint32_t L = in.n_loci, C = in.n_chr;
-    DevicePacked &pk = *out;
-    // worst-case block count (64-cell blocks) for buffers sized before the tile size is chosen
-    const size_t n_off_max = (size_t)((num_cells + 63) / 64) * ((size_t)L + 1);
-    enum { KEY_A, KEY_B, VAL_A, VAL_B, ELOC, WORK_A, WORK_B, RUNS, CUB, TMP, MISC, BIN, ENTRY_KC,
-           M_CHUNKS, M_ENTRY, RID_M, IDB_M, ELOC_M, DENSE_M, MARK_M, ARANK_M, DUPF, SEGS };
-    auto &S = pk.scratch;
-    // the counting scheme for read ids needs a table over the id space
-    const size_t id_space_cap = std::min<size_t>((size_t)kIdSpaceFactor * E + 1024, (size_t)1 << 30);
+// What a read-back of the scalars says. Before the records are written: the input's order, a void attempt (the id
+// space was assumed too small), a group too long for the counting scheme, a size this path does not cover. Behind
+// them: the errors of the group mapping (k_keys2, k_bin_hist) and a (block, locus) group too long (k_entry_records).
+Attempt scalar_verdict(const Scalars &h, bool records_written) {
+    if (records_written) {
+        if (h.error == 1) return Attempt::error("group id outside group_id_to_pos");
+        if (h.error == 2) return Attempt::error("group_id_to_pos maps outside the matrix");
+        return h.regroup ? Attempt::stop(Attempt::RetryRadix) : Attempt();
+    }
+    if (h.error == 3) return Attempt::error("positions must be strictly increasing within a chromosome");
+    if (h.id_exceeded) return Attempt::stop(Attempt::RetryPlain);
+    if (h.regroup) return Attempt::stop(Attempt::RetryRadix);
+    return h.need_host ? Attempt::stop(Attempt::NeedHost) : Attempt();
+}
 
-    Raw raw{in.chr_locus_off, C, in.locus_pos, in.locus_entry_off, in.read_ids, in.id_base16,
-            in.id_base32, in.group_id_to_pos, in.n_groups, L, E};
-
-    // ---- buffers (sized up front: a re-allocation in mid-pipeline would synchronise) -----------
-    // MISC: Scalars | id_max[C] | id_negmin[C] | id_base[C+1] | rbeg[C+1] | flushed[C] | cnt[L] |
-    //       locus_chr[L] | locus_rel[L] | flush_loci[L] | flush_count[C] | tail_begin[C] | chr_entry[C+1]
-    HIP_OK(S[MISC].ensure(sizeof(Scalars) + sizeof(uint32_t) * ((size_t)8 * C + 8 + (size_t)4 * L) + 64));
-    Scalars *sc = S[MISC].as<Scalars>();
-    uint32_t *id_max = reinterpret_cast<uint32_t *>(sc + 1);
-    uint32_t *id_negmin = id_max + C;
-    uint32_t *id_base = id_negmin + C;
-    uint32_t *rbeg = id_base + C + 1;
-    uint32_t *flushed = rbeg + C + 1;
-    uint32_t *cnt = flushed + C;
-    uint32_t *locus_chr = cnt + L, *locus_rel = locus_chr + L;
-    uint32_t *flush_loci = locus_rel + L, *flush_count = flush_loci + L;
-    uint32_t *tail_begin = flush_count + C;
-    uint32_t *chr_entry = tail_begin + C;  // first entry of every chromosome, and the number of entries (k_id_bases)
-    // KEY_A: sort keys in, later mark[E+1] | arank[E+1], later the per-(block, locus) counts
-    // (marks and appearance ranks, 2 (E + 1) words, with the (block, locus) counts behind them: the ranks are
-    // still read when the counts are written, k_bin_hist)
-    HIP_OK(S[KEY_A].ensure(std::max<size_t>((size_t)E * 8, ((size_t)2 * E + 4 + n_off_max + 1) * 4)));
-    // KEY_B: sorted keys, later (counting path) the kept entries grouped by (block, locus)
-    HIP_OK(S[KEY_B].ensure((size_t)E * 8));
-    HIP_OK(S[VAL_A].ensure(std::max<size_t>(E, 64) * 4));
-    HIP_OK(S[VAL_B].ensure((size_t)E * 4));
-    // (ELOC, entry -> locus: sized where k_entry_locus is launched -- the single-entry path has no such table)
-    HIP_OK(S[WORK_A].ensure(((size_t)E + 1) * 4));
-    HIP_OK(S[WORK_B].ensure(((size_t)2 * E + 2) * 4));
-    // RUNS: run_start[R+1] | run_rank[R] | starts_by_rank[R], R <= E
-    HIP_OK(S[RUNS].ensure(((size_t)3 * E + 8) * 4));
-    // ENTRY_KC: locus per entry in sorted order (stages 2-4), later (k, cell) per entry (counting path)
-    HIP_OK(S[ENTRY_KC].ensure((size_t)E * 8));
-    uint32_t *sloc = S[ENTRY_KC].as<uint32_t>();
-    // TMP: read index per kept entry; BIN: key2 x2, val2 x2, per-cell squares
-    HIP_OK(S[TMP].ensure((size_t)E * 4 + 64));
-    HIP_OK(S[BIN].ensure((size_t)E * 24 + ((size_t)num_cells + 130) * 8 + 64));
-    unsigned long long *key_a = S[KEY_A].as<unsigned long long>(), *key_b = S[KEY_B].as<unsigned long long>();
-    uint32_t *val_a = S[VAL_A].as<uint32_t>(), *val_b = S[VAL_B].as<uint32_t>();
-    {
-        size_t need = 0, most = 0;
-        HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, key_a, key_b, val_a, val_b, (int)E, 0, 64, stream));
-        most = std::max(most, need);
-        {
-            hipcub::CountingInputIterator<uint32_t> positions(0u);
-            hipcub::TransformInputIterator<unsigned long long, HeadKeepOp, hipcub::CountingInputIterator<uint32_t>>
-                    flags(positions, HeadKeepOp{key_b, val_a, val_a});
-            HIP_OK(hipcub::DeviceScan::InclusiveSum(nullptr, need, flags, key_a, (int)E, stream));
-            most = std::max(most, need);
-        }
-        HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, val_a, val_b, (int)E + 1, stream));
-        most = std::max(most, need);
-        HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, val_a, val_b,
-                                                (int)std::max<size_t>(n_off_max, id_space_cap + 2), stream));
-        most = std::max(most, need);
-        HIP_OK(S[CUB].ensure(most + 1024));
-    }
-    void *cub_tmp = S[CUB].p;
-    size_t cub_cap = 0;
-    HIP_OK(hipMemsetAsync(sc, 0, sizeof(Scalars) + sizeof(uint32_t) * ((size_t)3 * C + 1), stream));
-
-    if (!pk.side) {
-        HIP_OK(hipStreamCreateWithFlags(&pk.side, hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&pk.ev_fork, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&pk.ev_join, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&pk.ev_offsets, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&pk.ev_flush, hipEventDisableTiming));
-    }
-    auto bin_tiles = [&](uint32_t nb_, uint32_t *TL_, uint32_t *grid_, size_t *lds_) {
-        // tiles of TL consecutive loci per workgroup: nb * (TL + 1) words of LDS, 32 KiB at most (nb <= 1024)
-        uint32_t TL = 64;
-        while (TL > 1 && (size_t)nb_ * (TL + 1) * 4 > 32768) TL >>= 1;
-        *TL_ = TL;
-        *grid_ = std::min<uint32_t>((L + TL - 1) / TL, 8192);
-        *lds_ = (size_t)nb_ * (TL + 1) * 4;
-    };
-
-    // ---- 1: entries grouped by (chromosome, read id), pileup order inside a read ---------------
-    const HostTrace trace;
-    trace.mark("begin");
-    const int ids_aligned = (reinterpret_cast<uintptr_t>(raw.read_ids) & 15u) == 0 ? 1 : 0;
-    hipLaunchKernelGGL(k_id_range, dim3(std::min<uint32_t>(256, (E + 4095) / 4096)), dim3(TPB), 0, stream, raw, id_max,
-                       id_negmin, ids_aligned, sc);
-    // The size of the id space decides between the counting scheme and the radix sort and sizes the
-    // histogram. A handle that has packed before assumes the size of the previous call and does not wait
-    // (k_id_bases raises Scalars::id_exceeded if that was too small: the attempt is then void and
-    // repeated with the read-back).
-    const bool assume = !force_radix && !no_assumptions && pk.id_space_hint && pk.id_space_hint <= id_space_cap;
-    hipLaunchKernelGGL(k_id_bases, dim3(1), dim3(64), 0, stream, raw, id_max, id_negmin, id_base, chr_entry,
-                       (unsigned long long)(assume ? pk.id_space_hint : 0), sc);
-    Scalars hsc;
-    std::memset(&hsc, 0, sizeof(hsc));
-    if (!assume) {
-        HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));  // read-back 1: the size of the id space
-        if (hsc.error == 3) return "positions must be strictly increasing within a chromosome";
-    }
-    const size_t id_space = assume ? (size_t)pk.id_space_hint
-                                   : (size_t)std::min<unsigned long long>(hsc.id_space, 1ull << 40);
-    const bool counting = !force_radix && id_space <= id_space_cap;
-    HIP_OK(S[WORK_A].ensure(std::max<size_t>((size_t)E + 1, counting ? id_space + 1 : 0) * 4));
-    HIP_OK(S[WORK_B].ensure(std::max<size_t>((size_t)2 * E + 2, counting ? id_space + 1 : 0) * 4));
-    uint32_t *work_a = S[WORK_A].as<uint32_t>(), *work_b = S[WORK_B].as<uint32_t>();
-    // The single-entry fast path (counting scheme only; SECEDO_PACK_SPLIT=0 turns it off): `sub` is the pileup
-    // the read assembly of stages 1-4 sees -- the whole one, or the compacted entries of the ids that occur more
-    // than once (n_m of them; m_entry maps them back, m_index numbers them: the M entries before an entry).
-    static const bool split_allowed = [] {
-        const char *e = std::getenv("SECEDO_PACK_SPLIT");
-        return !(e && std::atoi(e) == 0);
-    }();
-    if (!pk.split_pays && ++pk.calls_without_split >= 16) {  // (pileups change: look again now and then)
-        pk.split_pays = true;
-        pk.calls_without_split = 0;
-    }
-    bool split_singles = counting && split_allowed && pk.split_pays;
-    // The entry -> locus table serves the general counting path and the radix route. The single-entry path has none
-    // (the chromosome of an entry follows from its index, the locus is wanted of the M entries only: k_m_fields), so
-    // the table is made here where the route is not tried, and behind read-back 1b where it is given up.
-    uint32_t *eloc = nullptr;
-    auto make_entry_locus = [&]() -> std::string {
-        HIP_OK(S[ELOC].ensure((size_t)E * 4 + 16));
-        eloc = S[ELOC].as<uint32_t>();
-        hipLaunchKernelGGL(k_entry_locus, dim3(blocks_for((uint64_t)L * 64)), dim3(TPB), 0, stream, raw, eloc, sc);
-        return std::string();
-    };
-    if (!split_singles) {
-        const std::string err = make_entry_locus();
-        if (!err.empty()) return err;
-    }
-    Raw sub = raw;
-    const uint32_t *sub_eloc = nullptr;
-    uint32_t n_m = E;
+// Stage 1's product: the entries in (chromosome, read id) order, pileup order inside a read. `sub` is the pileup the
+// read assembly of stages 2-4 sees: the whole one, or (single-entry route) the compacted entries of the ids that
+// occur more than once -- n_m of them; m_entry maps them back, m_index numbers them (the M entries before an entry).
+struct Grouped : Attempt {
+    Grouped() = default;
+    Grouped(Attempt a) : Attempt(std::move(a)) {}
+    unsigned long long *skey = nullptr;
+    uint32_t *sval = nullptr, *sloc = nullptr;
+    Raw sub{};
+    uint32_t n_m = 0;
     MIndex m_index{nullptr, nullptr};
-    uint32_t *m_entry = nullptr;
-    if (counting) {
-        uint32_t *hist = work_a, *id_off = work_b, *grouped = val_a;
-        uint32_t *dense = S[KEY_A].as<uint32_t>();  // (general path; the radix path's unsorted keys live here)
-        if (!split_singles) HIP_OK(hipMemsetAsync(hist, 0, (id_space + 1) * 4, stream));
-        if (split_singles) {
-            // which ids repeat (k_id_store, k_id_check), the entries of those as a compacted pileup of their own
-            const size_t padded = ((size_t)E + kFlagBlock - 1) / kFlagBlock * kFlagBlock + 16;
-            const uint32_t n_flag_blocks = (uint32_t)((padded - 16) / kFlagBlock);
-            // the M entries' numbering: a mask and a prefix per 64-entry chunk, and the closing chunk
-            const size_t n_chunks = (size_t)n_flag_blocks * (kFlagBlock / 64) + 1;
-            HIP_OK(S[M_CHUNKS].ensure(n_chunks * 12 + 16));
-            unsigned long long *chunk_mask = S[M_CHUNKS].as<unsigned long long>();
-            uint32_t *chunk_pre = reinterpret_cast<uint32_t *>(chunk_mask + n_chunks);
-            m_index = MIndex{chunk_pre, chunk_mask};
-            HIP_OK(S[MARK_M].ensure(std::max(((size_t)E + 2) * 4, padded)));
-            uint8_t *multi = S[MARK_M].as<uint8_t>();  // (the marks of the M entries come later: k_dup_mark)
-            HIP_OK(hipMemsetAsync(multi, 0, padded, stream));
-            hipLaunchKernelGGL(k_id_store, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, raw, chr_entry, id_base,
-                               id_negmin, sc, hist, ids_aligned);
-            hipLaunchKernelGGL(k_id_check, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, raw, chr_entry, id_base,
-                               id_negmin, sc, hist, multi, ids_aligned);
-            for (int a : {M_ENTRY, RID_M, IDB_M, ELOC_M, ARANK_M}) HIP_OK(S[a].ensure((size_t)E * 4 + 16));
-            // (the reads of the M entries, at most half of all entries:
-            // count[n_m+1] | goff[n_m+1] | winner | begin | len | members)
-            HIP_OK(S[DENSE_M].ensure(((size_t)6 * (E / 2 + 1) + 8) * 4));
-            m_entry = S[M_ENTRY].as<uint32_t>();
-            uint32_t *block_sum = grouped, *block_off = grouped + n_flag_blocks + 1;  // (VAL_A: 2 words per 4096 entries)
-            hipLaunchKernelGGL(k_flag_count, dim3(n_flag_blocks), dim3(TPB), 0, stream, multi, block_sum);
-            hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, block_sum, n_flag_blocks, block_off,
-                               chunk_pre + (n_chunks - 1), sc);
-            hipLaunchKernelGGL(k_compact_m, dim3(n_flag_blocks), dim3(TPB), 0, stream, raw, multi, block_off, chunk_pre,
-                               chunk_mask, m_entry);
-            // read-back 1b: how many entries take the general path (sizes every launch over them)
-            HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));
-            if (hsc.error == 3) return "positions must be strictly increasing within a chromosome";
-            if (hsc.id_exceeded) {
-                pk.id_space_hint = 0;
-                *retry = kRetrySameScheme;
-                return std::string();
-            }
-            n_m = hsc.n_multi_id;
-            if ((uint64_t)n_m * 2 > E) {  // clustered loci: (nearly) every read has several entries, no short cut
-                split_singles = false;
-                pk.split_pays = false;
-                pk.calls_without_split = 0;
-                n_m = E;
-                m_index = MIndex{nullptr, nullptr};
-                m_entry = nullptr;
-                // (the id slots hold entry numbers, the general path wants counts -- and the entry -> locus table)
-                HIP_OK(hipMemsetAsync(hist, 0, (id_space + 1) * 4, stream));
-                const std::string err = make_entry_locus();
-                if (!err.empty()) return err;
-            }
-        }
-        if (split_singles) {
-            sub = raw;
-            sub.read_ids = S[RID_M].as<uint32_t>();
-            sub.id_base16 = nullptr;
-            sub.id_base32 = S[IDB_M].as<uint32_t>();
-            sub.n_entries = n_m;
-            sub_eloc = S[ELOC_M].as<uint32_t>();
-            if (n_m) {
-                // the reads of the M entries: the groups of equal winner
-                uint32_t *count_m = S[DENSE_M].as<uint32_t>(), *goff = count_m + n_m + 1, *winner_m = goff + n_m + 1;
-                uint32_t *g_begin = winner_m + n_m, *g_len = g_begin + n_m, *members = g_len + n_m;
-                HIP_OK(hipMemsetAsync(count_m, 0, ((size_t)n_m + 1) * 4, stream));
-                hipLaunchKernelGGL(k_m_fields, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, raw, chr_entry, id_base, id_negmin,
-                                   hist, m_index, m_entry, n_m, S[RID_M].as<uint32_t>(), S[IDB_M].as<uint32_t>(),
-                                   S[ELOC_M].as<uint32_t>(), winner_m, count_m);
-                cub_cap = S[CUB].bytes;
-                HIP_OK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, count_m, goff, (int)n_m + 1, stream));
-                hipLaunchKernelGGL(k_group_scatter, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, winner_m, n_m, goff, count_m,
-                                   members, g_begin, g_len);
-                hipLaunchKernelGGL(k_group_rank, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, sub, members, g_begin, g_len,
-                                   sub_eloc, n_m, key_b, val_b, sloc, sc);
-            }
-        } else {
-            hipLaunchKernelGGL(k_id_hist, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, eloc, id_base, id_negmin, sc,
-                               dense, hist);
-            cub_cap = S[CUB].bytes;
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, hist, id_off, (int)(id_space + 1), stream));
-            hipLaunchKernelGGL(k_id_scatter, dim3(blocks_for(E)), dim3(TPB), 0, stream, dense, E, id_off, sc, hist,
-                               grouped);
-            hipLaunchKernelGGL(k_id_rank, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, dense, id_off, grouped, eloc,
-                               key_b, val_b, sloc, sc);
-        }
-    } else {
-        const uint32_t id_bits = (uint32_t)bits_for(hsc.max_read_id);
-        hipLaunchKernelGGL(k_entry_keys, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, eloc, id_bits, key_a, val_a);
-        cub_cap = S[CUB].bytes;
-        HIP_OK(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_cap, key_a, key_b, val_a, val_b, (int)E, 0,
-                                                   (int)id_bits + bits_for(C), stream));
-        hipLaunchKernelGGL(k_sorted_locus, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, val_b, eloc, E, sloc);
-    }
-    const unsigned long long *skey = key_b;
-    const uint32_t *sval = val_b;
-    pk.used_single_entry = split_singles;
+    const uint32_t *m_entry = nullptr;
+    bool counting = false;      // not the radix sort
+    bool single_entry = false;  // the single-entry route, held to the end
+    bool abandoned = false;     // ... or given up (clustered loci): the caller takes the counting route
+};
 
-    // ---- 2-4: duplicate rule, reads = runs of equal key, per-read lists, appearance ranks ------
-    // (the number of reads R stays on the device until read-back 2; buffers indexed by read are laid
-    // out for the upper bound E)
-    uint32_t *keep = work_a;
-    unsigned long long *incl = reinterpret_cast<unsigned long long *>(work_b);  // alive until k_keys2
-    uint32_t *mark = S[KEY_A].as<uint32_t>();  // the unsorted keys / dense ids are dead
-    uint32_t *arank = mark + (E + 1);
-    uint32_t *run_start = S[RUNS].as<uint32_t>();
-    uint32_t *run_rank = run_start + E + 1;
-    // cuts of reads that outlive max_fragment_length: none on the first build (null), later the flags of
-    // k_split_update in TMP, which is free until k_keys2 writes the read index per kept entry there
-    uint32_t *split = nullptr;
-    HIP_OK(pk.read_off.ensure(((size_t)E + 1) * 4));
-    HIP_OK(pk.read_locus.ensure((size_t)E * 4));
-    HIP_OK(pk.read_base.ensure(E));
-    HIP_OK(pk.range_off.ensure(((size_t)L + 2) * 4));
-    HIP_OK(pk.entry.ensure((size_t)E * 16));
-    HIP_OK(pk.entry32.ensure((size_t)E * 4));
-    HIP_OK(pk.mask32.ensure((size_t)E * 4));
-    HIP_OK(pk.entry_read.ensure((size_t)E * 4));
-    HIP_OK(pk.blk_off.ensure((n_off_max + 1) * 4));
-    uint32_t *read_off = pk.read_off.as<uint32_t>(), *read_locus = pk.read_locus.as<uint32_t>();
-    uint8_t *read_base = pk.read_base.as<uint8_t>();
-    // reads from the current `split` flags, then completed counts and the flush chain. The chain is
-    // sequential (one lane per chromosome) and only the final gather needs its result: it runs on a
-    // side stream, next to the grouping of the kept entries.
-    // (`sub` / n_m: the entries that go through the read assembly -- all of them, or with the single-entry
-    // fast path those of the ids that occur more than once; marks and ranks are always those of the whole pileup)
-    const Ranks ranks{m_index, split_singles ? arank : nullptr, arank};
-    auto build_reads = [&]() -> std::string {
-        uint32_t *mark_sub = split_singles ? S[MARK_M].as<uint32_t>() : mark;
-        if (n_m) {
-            hipLaunchKernelGGL(k_dup_mark, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, sub, skey, sval, sloc, split, n_m,
-                               keep, mark_sub);
-            hipcub::CountingInputIterator<uint32_t> positions(0u);
-            hipcub::TransformInputIterator<unsigned long long, HeadKeepOp, hipcub::CountingInputIterator<uint32_t>>
-                    flags(positions, HeadKeepOp{skey, keep, split});
-            cub_cap = S[CUB].bytes;
-            HIP_OK(hipcub::DeviceScan::InclusiveSum(cub_tmp, cub_cap, flags, incl, (int)n_m, stream));
-        }
-        cub_cap = S[CUB].bytes;
-        const uint32_t *arank_sub = arank;
-        if (split_singles) {  // (the ranks' array holds the n_m + 1 prefix sums `unm` instead: struct Ranks)
-            hipcub::CountingInputIterator<uint32_t> entries(0u);
-            hipcub::TransformInputIterator<uint32_t, UnmarkedM, hipcub::CountingInputIterator<uint32_t>> unmarked(
-                    entries, UnmarkedM{mark_sub, n_m});
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, unmarked, arank, (int)n_m + 1, stream));
-            uint32_t *arank_m = S[ARANK_M].as<uint32_t>();
-            hipLaunchKernelGGL(k_arank_m, dim3(blocks_for(std::max(n_m, 1u))), dim3(TPB), 0, stream, arank, m_entry, n_m,
-                               E, arank_m, sc);
-            arank_sub = arank_m;
-            hipLaunchKernelGGL(k_rbeg, dim3(1), dim3(TPB), 0, stream, raw, ranks, rbeg);
-        } else {
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, mark, arank, (int)E + 1, stream));
-        }
-        if (n_m) {
-            hipLaunchKernelGGL(k_runs_csr, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, sub, incl, sval, sloc, n_m,
-                               run_start, read_locus, read_base);
-            hipLaunchKernelGGL(k_read_info, dim3(std::min<uint32_t>(blocks_for(n_m), 2048)), dim3(TPB), 0, stream, sub,
-                               incl, run_start, sval, sloc, arank_sub, mfl, run_rank, split_singles ? nullptr : rbeg,
-                               read_off, sc);
-        }
-        HIP_OK(hipEventRecord(pk.ev_fork, stream));
-        HIP_OK(hipStreamWaitEvent(pk.side, pk.ev_fork, 0));
-        hipLaunchKernelGGL(k_completed, dim3(blocks_for(L)), dim3(TPB), 0, pk.side, raw, ranks, rbeg, mfl, cnt, sc);
-        hipLaunchKernelGGL(k_flush_chain, dim3(C), dim3(TPB), 0, pk.side, raw, cnt, 4u * num_threads, sc, flushed,
-                           flush_loci, flush_count, ranks, rbeg, split_singles ? tail_begin : nullptr);
-        HIP_OK(hipEventRecord(pk.ev_flush, pk.side));
-        HIP_OK(hipEventRecord(pk.ev_join, pk.side));
-        return std::string();
-    };
-    {
-        const std::string err = build_reads();
-        if (!err.empty()) return err;
-    }
-    struct SideJoin {  // every way out of this function leaves the side stream idle
-        hipStream_t side;
-        bool joined = false;
-        ~SideJoin() { if (!joined) (void)hipStreamSynchronize(side); }
-    } side_join{pk.side};
+// What stages 2-4 write and stage 5 still reads. Marks and ranks are always those of the whole pileup; with the
+// single-entry route the M entries have marks and ranks of their own beside them.
+struct ReadViews {
+    uint32_t *keep;
+    unsigned long long *incl;
+    MarksRanksCounts marks;
+    Runs runs;
+    uint32_t *mark_sub, *arank_m;  // null without the single-entry route
+    Ranks ranks;
+    uint32_t *read_off, *read_locus;
+    uint8_t *read_base;
+};
 
-    // read-back 2: status flags, R, number of kept entries, multi-locus statistics
-    unsigned long long totals = 0;  // reads | kept entries << 32
-    trace.mark("reads built (launched)");
-    HIP_OK(read_scalars(pk, stream, sc, n_m ? incl + (n_m - 1) : nullptr, &hsc, &totals));
-    trace.mark("read-back 2 arrived");
-    if (hsc.error == 3) return "positions must be strictly increasing within a chromosome";
-    if (hsc.id_exceeded) {
-        pk.id_space_hint = 0;
-        *retry = kRetrySameScheme;
-        return std::string();
-    }
-    pk.id_space_hint = counting ? std::max<uint64_t>(hsc.id_space, 1) : 0;
-    if (hsc.regroup) {
-        *retry = kRetryRadix;
-        return std::string();
-    }
-    if (hsc.need_host) {
-        *need_host = true;
-        return std::string();
-    }
-    if (hsc.long_reads) {
-        // Some id's entries span >= max_fragment_length: a flush may erase it before its last entry and
-        // the id re-opens as a new read. Cut at the flush loci, rebuild, repeat until the cuts are stable
-        // (they move forward with the flushes they cause: a few rounds).
-        bool stable = false;
-        split = S[TMP].as<uint32_t>();
-        HIP_OK(hipMemsetAsync(split, 0, (size_t)std::max(n_m, 1u) * 4, stream));
-        for (int round = 0; round < kMaxSplitRounds && !stable; ++round) {
-            HIP_OK(hipStreamWaitEvent(stream, pk.ev_join, 0));  // the chain of the previous build
-            HIP_OK(hipMemsetAsync(&sc->split_changed, 0, 4, stream));
-            hipLaunchKernelGGL(k_split_update, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, sub, skey, sloc, mfl,
-                               flush_loci, flush_count, split, sc);
-            HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));
-            if (!hsc.split_changed) {
-                stable = true;
-                break;
-            }
-            HIP_OK(hipMemsetAsync(&sc->multi_entries, 0, 8, stream));  // k_read_info adds to it
-            const std::string err = build_reads();
-            if (!err.empty()) return err;
-            HIP_OK(read_scalars(pk, stream, sc, n_m ? incl + (n_m - 1) : nullptr, &hsc, &totals));
-        }
-        if (!stable) {
-            *need_host = true;  // did not settle: the exact sequential emulation decides
-            return std::string();
-        }
-    }
-    // (single-entry fast path: `totals` counts the reads and kept entries of the M entries; every S entry is a
-    // read and a kept entry of its own)
-    const uint32_t kept_m = (uint32_t)(totals >> 32);
-    const uint32_t R = split_singles ? hsc.reads_total : (uint32_t)totals;
-    const uint32_t n_kept = split_singles ? kept_m + (E - n_m) : kept_m;
-    const size_t nk = std::max<uint32_t>(n_kept, 1);
-    pk.multi_entries = hsc.multi_entries;
-    pk.max_read_entries = std::max(hsc.max_read_entries, n_kept ? 1u : 0u);
+// Stage 5's decisions, all made on the host from what read-back 2 brought: cell blocks, the binning tiles, the two
+// sets of staging limits the locus ranges are cut for, and the segments they are cut in.
+struct TilePlan {
+    uint32_t B, nb, B_log2, lbits;
+    bool stage_masks;
+    CapChoice caps;
+    uint32_t n_seg;
+    size_t variant_stride;
+    uint32_t TL, locus_grid;  // tiles of TL consecutive loci per workgroup: nb * (TL + 1) words of LDS, 32 KiB at most
+    size_t lds;
+};
+TilePlan plan_tiles(uint32_t num_cells, uint32_t L, uint32_t block_cells, StageGeometry (*geometry)(uint32_t),
+                    bool allow_count_tile, uint32_t n_kept, uint64_t multi_entries) {
+    TilePlan p;
     if (block_cells == 0) {
         const StageGeometry g64 = geometry(64);
-        const bool clustered = n_kept && (double)pk.multi_entries > g64.masks_threshold * (double)n_kept;
+        const bool clustered = n_kept && (double)multi_entries > g64.masks_threshold * (double)n_kept;
         block_cells = (clustered || num_cells <= 64) ? 64 : 128;
     }
     const StageGeometry geo = geometry(block_cells);
-    const uint32_t B = block_cells, nb = (num_cells + B - 1) / B;
-    if (B != 64 && B != 128) return "block_cells must be 64 or 128";
-    const uint32_t B_log2 = B == 64 ? 6u : 7u;
-    const uint32_t lbits = (uint32_t)bits_for(L - 1);
-    // k_bin_place packs the locus into 25 bits at most, and bit 31 of a k marks an S entry
-    if (!force_radix && (lbits + kCibBits > 32u || E >= kSingle)) {
-        *retry = kRetryRadix;
-        return std::string();
-    }
-    pk.num_cells = num_cells;
-    pk.block_cells = B;
-    pk.num_blocks = nb;
-    pk.num_loci = L;
-    pk.num_entries = n_kept;
-    pk.num_reads = R;
-    pk.stage_masks = n_kept && (double)pk.multi_entries > geo.masks_threshold * (double)n_kept;
-
-    // ---- 5: kept entries grouped by (cell block, locus, cell), offsets, bound, ranges, records ----
-    uint32_t *t_read = S[TMP].as<uint32_t>();
-    unsigned long long *key2_a = S[BIN].as<unsigned long long>();
-    unsigned long long *key2_b = key2_a + nk;
-    uint4 *m_rec = S[BIN].as<uint4>();  // counting path (no binning keys): 16 bytes per kept M entry, k_m_records
-    unsigned long long *per_cell_sq = key2_b + nk;  // nb * B entries
-    uint32_t *val2_a = reinterpret_cast<uint32_t *>(per_cell_sq + (size_t)nb * B + 1);
-    uint32_t *val2_b = val2_a + nk;
-    const size_t n_off = (size_t)nb * ((size_t)L + 1);
-    uint32_t *blk_off = pk.blk_off.as<uint32_t>();
-    uint32_t *blk_cnt = S[KEY_A].as<uint32_t>() + 2 * ((size_t)E + 1);  // behind the marks and ranks
-    // counting path: per pileup entry its k and cell (entry -> locus and the per-read scratch are dead)
-    unsigned long long *entry_kc = force_radix ? nullptr : S[ENTRY_KC].as<unsigned long long>();
-    HIP_OK(S[DUPF].ensure((size_t)L + 16));
-    uint8_t *dupflag = S[DUPF].as<uint8_t>();  // per locus: some cell has two kept entries there (k_bin_place)
+    p.B = block_cells;
+    p.nb = (num_cells + p.B - 1) / p.B;
+    p.B_log2 = p.B == 64 ? 6u : 7u;
+    p.lbits = (uint32_t)bits_for(L - 1);
+    p.stage_masks = n_kept && (double)multi_entries > geo.masks_threshold * (double)n_kept;
     // The pair bound decides the tile variant, and the tile variant the staging limits of the locus ranges;
-    // the bound comes out of the grouping below, the ranges need only the offsets: they are cut for both
-    // sets of limits on the side stream while the grouping runs (k_ranges_segment), and picked afterwards.
-    CapChoice caps;
-    caps.entries_plain = pk.stage_masks ? geo.cap_entries_masks : geo.cap_entries_plain;
-    caps.loci_plain = pk.stage_masks ? geo.cap_loci_masks : geo.cap_loci_plain;
+    // the bound comes out of the grouping, the ranges need only the offsets: they are cut for both sets of
+    // limits while the grouping runs (k_ranges_segment), and picked afterwards.
+    CapChoice &caps = p.caps;
+    caps.entries_plain = p.stage_masks ? geo.cap_entries_masks : geo.cap_entries_plain;
+    caps.loci_plain = p.stage_masks ? geo.cap_loci_masks : geo.cap_loci_plain;
     caps.entries_counts = geo.cap_entries_counts;
     caps.loci_counts = geo.cap_loci_counts;
     caps.count_limit = kCountTileLimit;
-    caps.allow_counts = (allow_count_tile && !pk.stage_masks) ? 1u : 0u;
+    caps.allow_counts = (allow_count_tile && !p.stage_masks) ? 1u : 0u;
     // Segment length of the count tile's ranges. A segment is cut greedily -- full ranges, then a remainder --, and
     // every range costs a workgroup the same set-up and the same item slots whatever it holds: a segment that
     // needs 1.3 ranges (C5: 8190 loci x 1.3 entries per cell block and locus against 8192 staged entries) becomes
@@ -2422,7 +2084,7 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     // entry limit, shorter segments that hold ONE range each at 93 % (the margin covers the densest block's
     // fluctuation; a segment that overflows all the same is cut in two) are taken if they give fewer ranges.
     if (caps.allow_counts && n_kept && L) {
-        const double density = (double)n_kept / ((double)num_cells / B) / (double)L;  // entries per (full cell block, locus)
+        const double density = (double)n_kept / ((double)num_cells / p.B) / (double)L;  // entries per (full cell block, locus)
         const double per_segment = density * caps.loci_counts / caps.entries_counts;  // ranges a full-length segment needs
         if (per_segment > 1.0) {
             const double greedy = std::ceil((double)L / caps.loci_counts) * std::ceil(per_segment);
@@ -2432,61 +2094,404 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
     }
     const uint32_t lo_loci = caps.allow_counts ? std::min(caps.loci_plain, caps.loci_counts) : caps.loci_plain;
     const uint32_t hi_loci = caps.allow_counts ? std::max(caps.loci_plain, caps.loci_counts) : caps.loci_plain;
-    const uint32_t n_seg = (L + lo_loci - 1) / lo_loci;
-    const size_t variant_stride = (size_t)n_seg * hi_loci + n_seg + 2;
-    HIP_OK(S[SEGS].ensure(2 * variant_stride * 4));
-    uint32_t *seg_count = S[SEGS].as<uint32_t>();  // (not over entry -> locus: the binning passes read it)
-    uint32_t *seg_ends = seg_count + n_seg;
-    auto cut_ranges_on_side = [&]() -> std::string {  // call when blk_off is complete on `stream`
+    p.n_seg = (L + lo_loci - 1) / lo_loci;
+    p.variant_stride = (size_t)p.n_seg * hi_loci + p.n_seg + 2;
+    p.TL = 64;
+    while (p.TL > 1 && (size_t)p.nb * (p.TL + 1) * 4 > 32768) p.TL >>= 1;
+    p.locus_grid = std::min<uint32_t>((L + p.TL - 1) / p.TL, 8192);
+    p.lds = (size_t)p.nb * (p.TL + 1) * 4;
+    return p;
+}
+
+// What stage 5 works on: the plan, the totals of read-back 2 and the views of its generations
+struct Stage5 {
+    TilePlan p;
+    uint32_t n_kept, kept_m;  // kept entries, and those of them that went through the read assembly
+    size_t n_off;
+    uint32_t *t_read, *krank, *blk_off, *blk_cnt;
+    uint8_t *kflags, *dupflag;
+    unsigned long long *entry_kc;  // null on the radix route
+    BinRadix bin;                  // (the radix route's; per_cell_sq is where both routes have it)
+    uint4 *m_rec;                  // the counting route's
+    unsigned long long *per_cell_sq;
+    Segs segs;
+};
+
+// One attempt. With force_radix == false the two groupings (entries by read, kept entries by (cell block, locus))
+// use the counting scheme when its preconditions hold; a group too long for it ends the attempt with RetryRadix.
+struct PackAttempt {
+    // fixed over the attempt
+    const DeviceFlatPileup &in;
+    const uint32_t num_cells, mfl, num_threads, block_cells;
+    StageGeometry (*const geometry)(uint32_t);
+    const bool allow_count_tile, force_radix, no_assumptions, overlap;
+    const hipStream_t stream;
+    DevicePacked &pk;
+    DeviceArena *const S;
+    const uint32_t E, L, C;
+    const PackShape shape;
+    const Raw raw;
+    const int ids_aligned;
+    HostTrace trace;
+    // set by prepare_workspace
+    MiscViews<Scalars> m{nullptr, PackShape{0, 0, 0, 0}};
+    Scalars *sc = nullptr;
+    void *cub_tmp = nullptr;
+
+    PackAttempt(const DeviceFlatPileup &in_, uint32_t num_cells_, uint32_t mfl_, uint32_t num_threads_,
+                uint32_t block_cells_, StageGeometry (*geometry_)(uint32_t), bool allow_count_tile_, bool force_radix_,
+                bool no_assumptions_, bool overlap_, hipStream_t stream_, DevicePacked &pk_)
+        : in(in_), num_cells(num_cells_), mfl(mfl_), num_threads(num_threads_), block_cells(block_cells_),
+          geometry(geometry_), allow_count_tile(allow_count_tile_), force_radix(force_radix_),
+          no_assumptions(no_assumptions_), overlap(overlap_), stream(stream_), pk(pk_), S(pk_.scratch),
+          E(static_cast<uint32_t>(in_.n_entries)), L(in_.n_loci), C(in_.n_chr), shape{E, L, C, num_cells_},
+          raw{in_.chr_locus_off, C, in_.locus_pos, in_.locus_entry_off, in_.read_ids, in_.id_base16, in_.id_base32,
+              in_.group_id_to_pos, in_.n_groups, L, E},
+          ids_aligned((reinterpret_cast<uintptr_t>(in_.read_ids) & 15u) == 0 ? 1 : 0) {}
+
+    hipError_t ensure(Arena::Id a, size_t id_slots = 0) { return S[a].ensure(arena_bytes<Scalars>(a, shape, id_slots)); }
+    template <class T>
+    hipError_t exclusive_sum(const T &in_it, uint32_t *out, size_t n) {
+        size_t cub_cap = S[Arena::CUB].bytes;
+        return hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, in_it, out, (int)n, stream);
+    }
+
+    // ---- buffers (sized up front: a re-allocation in mid-pipeline would synchronise) -----------
+    Attempt prepare_workspace() {
+        for (Arena::Id a : {Arena::MISC, Arena::KEY_A, Arena::KEY_B, Arena::VAL_A, Arena::VAL_B, Arena::WORK_A,
+                            Arena::WORK_B, Arena::RUNS, Arena::ENTRY_KC, Arena::TMP, Arena::BIN})
+            HIP_OK(ensure(a));
+        m = MiscViews<Scalars>(S[Arena::MISC].p, shape);
+        sc = m.sc;
+        {
+            // the counting scheme for read ids needs a table over the id space
+            unsigned long long *key_a = UnsortedKeys(S[Arena::KEY_A].p, E), *key_b = SortedKeys(S[Arena::KEY_B].p, E);
+            uint32_t *val_a = GroupedIds(S[Arena::VAL_A].p, E), *val_b = SortedValues(S[Arena::VAL_B].p, E);
+            size_t need = 0, most = 0;
+            HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, key_a, key_b, val_a, val_b, (int)E, 0, 64, stream));
+            most = std::max(most, need);
+            {
+                hipcub::CountingInputIterator<uint32_t> positions(0u);
+                hipcub::TransformInputIterator<unsigned long long, HeadKeepOp, hipcub::CountingInputIterator<uint32_t>>
+                        flags(positions, HeadKeepOp{key_b, val_a, val_a});
+                HIP_OK(hipcub::DeviceScan::InclusiveSum(nullptr, need, flags, key_a, (int)E, stream));
+                most = std::max(most, need);
+            }
+            HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, val_a, val_b, (int)E + 1, stream));
+            most = std::max(most, need);
+            HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, val_a, val_b,
+                                                    (int)std::max<size_t>(shape.n_off_max(), id_space_cap() + 2), stream));
+            most = std::max(most, need);
+            HIP_OK(S[Arena::CUB].ensure(most + 1024));
+        }
+        cub_tmp = S[Arena::CUB].p;
+        HIP_OK(hipMemsetAsync(sc, 0, m.zeroed, stream));
+        if (!pk.side) {
+            HIP_OK(hipStreamCreateWithFlags(&pk.side, hipStreamNonBlocking));
+            HIP_OK(hipEventCreateWithFlags(&pk.ev_fork, hipEventDisableTiming));
+            HIP_OK(hipEventCreateWithFlags(&pk.ev_join, hipEventDisableTiming));
+            HIP_OK(hipEventCreateWithFlags(&pk.ev_offsets, hipEventDisableTiming));
+            HIP_OK(hipEventCreateWithFlags(&pk.ev_flush, hipEventDisableTiming));
+        }
+        return Attempt();
+    }
+    size_t id_space_cap() const { return std::min<size_t>((size_t)kIdSpaceFactor * E + 1024, (size_t)1 << 30); }
+
+    // ---- 1: entries grouped by (chromosome, read id), pileup order inside a read ---------------
+    // The entry -> locus table serves the general counting route and the radix route. The single-entry route has none
+    // (the chromosome of an entry follows from its index, the locus is wanted of the M entries only: k_m_fields), so
+    // the table is made where that route is not tried, and behind read-back 1b where it is given up.
+    Attempt make_entry_locus() {
+        HIP_OK(ensure(Arena::ELOC));
+        hipLaunchKernelGGL(k_entry_locus, dim3(blocks_for((uint64_t)L * 64)), dim3(TPB), 0, stream, raw,
+                           EntryLocus(S[Arena::ELOC].p, E).p, sc);
+        return Attempt();
+    }
+    Grouped whole_pileup(bool counting) const {
+        Grouped g;
+        g.skey = SortedKeys(S[Arena::KEY_B].p, E), g.sval = SortedValues(S[Arena::VAL_B].p, E);
+        g.sloc = SortedLoci(S[Arena::ENTRY_KC].p, E);
+        g.sub = raw;
+        g.n_m = E;
+        g.counting = counting;
+        return g;
+    }
+
+    Grouped group_by_read() {
+        hipLaunchKernelGGL(k_id_range, dim3(std::min<uint32_t>(256, (E + 4095) / 4096)), dim3(TPB), 0, stream, raw,
+                           m.id_max, m.id_negmin, ids_aligned, sc);
+        // The size of the id space decides between the counting scheme and the radix sort and sizes the
+        // histogram. A handle that has packed before assumes the size of the previous call and does not wait
+        // (k_id_bases raises Scalars::id_exceeded if that was too small: the attempt is then void and
+        // repeated with the read-back).
+        const bool assume = !force_radix && !no_assumptions && pk.id_space_hint && pk.id_space_hint <= id_space_cap();
+        hipLaunchKernelGGL(k_id_bases, dim3(1), dim3(64), 0, stream, raw, m.id_max, m.id_negmin, m.id_base, m.chr_entry,
+                           (unsigned long long)(assume ? pk.id_space_hint : 0), sc);
+        Scalars hsc;
+        std::memset(&hsc, 0, sizeof(hsc));
+        if (!assume) {
+            HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));  // read-back 1: the size of the id space
+            STEP(scalar_verdict(hsc, false));
+        }
+        const size_t id_space = assume ? (size_t)pk.id_space_hint
+                                       : (size_t)std::min<unsigned long long>(hsc.id_space, 1ull << 40);
+        const bool counting = !force_radix && id_space <= id_space_cap();
+        HIP_OK(ensure(Arena::WORK_A, counting ? id_space + 1 : 0));
+        HIP_OK(ensure(Arena::WORK_B, counting ? id_space + 1 : 0));
+        // The single-entry route pays when most reads have one entry (counting scheme only): a call that finds more
+        // than half of the entries in multi-entry reads gives it up, and the handle's next calls do not try.
+        if (!pk.split_pays && ++pk.calls_without_split >= 16) {  // (pileups change: look again now and then)
+            pk.split_pays = true;
+            pk.calls_without_split = 0;
+        }
+        if (!(counting && pk.split_pays)) {
+            STEP(make_entry_locus());
+            return counting ? group_by_read_counting(id_space, false) : group_by_read_radix(hsc.max_read_id);
+        }
+        Grouped g = group_by_read_single_entry(id_space);
+        if (!g.abandoned) return g;
+        pk.split_pays = false;
+        pk.calls_without_split = 0;
+        return group_by_read_counting(id_space, true);
+    }
+
+    // which ids repeat (k_id_store, k_id_check), the entries of those as a compacted pileup of their own, and their
+    // reads: the groups of equal winner
+    Grouped group_by_read_single_entry(size_t id_space) {
+        const uint32_t n_flag_blocks = (uint32_t)shape.flag_blocks();
+        const size_t n_chunks = shape.chunks();
+        uint32_t *last = IdSlots(S[Arena::WORK_A].p, id_space + 1);  // per id the number of one of its entries
+        HIP_OK(ensure(Arena::M_CHUNKS));
+        const MChunks chunks(S[Arena::M_CHUNKS].p, shape);
+        HIP_OK(ensure(Arena::MARK_M));
+        uint8_t *multi = MultiFlags(S[Arena::MARK_M].p, shape.flag_bytes());
+        HIP_OK(hipMemsetAsync(multi, 0, shape.flag_bytes(), stream));
+        hipLaunchKernelGGL(k_id_store, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, raw, m.chr_entry, m.id_base,
+                           m.id_negmin, sc, last, ids_aligned);
+        hipLaunchKernelGGL(k_id_check, dim3(blocks_for((E + 3) / 4)), dim3(TPB), 0, stream, raw, m.chr_entry, m.id_base,
+                           m.id_negmin, sc, last, multi, ids_aligned);
+        for (Arena::Id a : {Arena::M_ENTRY, Arena::RID_M, Arena::IDB_M, Arena::ELOC_M, Arena::ARANK_M, Arena::DENSE_M})
+            HIP_OK(ensure(a));
+        uint32_t *m_entry = PerM(S[Arena::M_ENTRY].p, E), *rid_m = PerM(S[Arena::RID_M].p, E);
+        uint32_t *idb_m = PerM(S[Arena::IDB_M].p, E), *eloc_m = PerM(S[Arena::ELOC_M].p, E);
+        const FlagBlockSums sums(S[Arena::VAL_A].p, shape);
+        hipLaunchKernelGGL(k_flag_count, dim3(n_flag_blocks), dim3(TPB), 0, stream, multi, sums.block_sum);
+        hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, sums.block_sum, n_flag_blocks, sums.block_off,
+                           chunks.chunk_pre + (n_chunks - 1), sc);
+        hipLaunchKernelGGL(k_compact_m, dim3(n_flag_blocks), dim3(TPB), 0, stream, raw, multi, sums.block_off,
+                           chunks.chunk_pre, chunks.chunk_mask, m_entry);
+        // read-back 1b: how many entries take the general path (sizes every launch over them)
+        Scalars hsc;
+        HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));
+        STEP(scalar_verdict(hsc, false));
+        Grouped g = whole_pileup(true);
+        g.n_m = hsc.n_multi_id;
+        if ((uint64_t)g.n_m * 2 > E) {  // clustered loci: (nearly) every read has several entries, no short cut
+            g.abandoned = true;
+            return g;
+        }
+        g.single_entry = true;
+        g.m_index = MIndex{chunks.chunk_pre, chunks.chunk_mask};
+        g.m_entry = m_entry;
+        g.sub.read_ids = rid_m;
+        g.sub.id_base16 = nullptr;
+        g.sub.id_base32 = idb_m;
+        g.sub.n_entries = g.n_m;
+        if (g.n_m) {
+            const uint32_t n_m = g.n_m;
+            const MReads r(S[Arena::DENSE_M].p, n_m);
+            HIP_OK(hipMemsetAsync(r.count_m, 0, ((size_t)n_m + 1) * 4, stream));
+            hipLaunchKernelGGL(k_m_fields, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, raw, m.chr_entry, m.id_base,
+                               m.id_negmin, last, g.m_index, m_entry, n_m, rid_m, idb_m, eloc_m, r.winner_m, r.count_m);
+            HIP_OK(exclusive_sum(r.count_m, r.goff, (size_t)n_m + 1));
+            hipLaunchKernelGGL(k_group_scatter, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, r.winner_m, n_m, r.goff,
+                               r.count_m, r.members, r.g_begin, r.g_len);
+            hipLaunchKernelGGL(k_group_rank, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, g.sub, r.members, r.g_begin,
+                               r.g_len, eloc_m, n_m, g.skey,
+                               g.sval, g.sloc, sc);
+        }
+        return g;
+    }
+
+    // histogram over the dense id space, scan, scatter with an atomic cursor, rank inside the (short) group
+    Grouped group_by_read_counting(size_t id_space, bool single_entry_abandoned) {
+        Grouped g = whole_pileup(true);
+        uint32_t *hist = IdSlots(S[Arena::WORK_A].p, id_space + 1), *id_off = IdOffsets(S[Arena::WORK_B].p, id_space + 1);
+        uint32_t *grouped = GroupedIds(S[Arena::VAL_A].p, E), *dense = DenseIds(S[Arena::KEY_A].p, E);
+        // (given up: the id slots hold entry numbers, this route wants counts -- and the entry -> locus table)
+        HIP_OK(hipMemsetAsync(hist, 0, (id_space + 1) * 4, stream));
+        if (single_entry_abandoned) STEP(make_entry_locus());
+        const uint32_t *eloc = EntryLocus(S[Arena::ELOC].p, E);
+        hipLaunchKernelGGL(k_id_hist, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, eloc, m.id_base, m.id_negmin, sc,
+                           dense, hist);
+        HIP_OK(exclusive_sum(hist, id_off, id_space + 1));
+        hipLaunchKernelGGL(k_id_scatter, dim3(blocks_for(E)), dim3(TPB), 0, stream, dense, E, id_off, sc, hist, grouped);
+        hipLaunchKernelGGL(k_id_rank, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, dense, id_off, grouped, eloc,
+                           g.skey, g.sval, g.sloc, sc);
+        return g;
+    }
+
+    // the hipCUB radix sort: the ids are sparse, or a group was too long for the counting scheme
+    Grouped group_by_read_radix(uint32_t max_read_id) {
+        Grouped g = whole_pileup(false);
+        unsigned long long *key_a = UnsortedKeys(S[Arena::KEY_A].p, E);
+        uint32_t *val_a = GroupedIds(S[Arena::VAL_A].p, E);
+        const uint32_t *eloc = EntryLocus(S[Arena::ELOC].p, E);
+        const uint32_t id_bits = (uint32_t)bits_for(max_read_id);
+        hipLaunchKernelGGL(k_entry_keys, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, eloc, id_bits, key_a, val_a);
+        size_t cub_cap = S[Arena::CUB].bytes;
+        HIP_OK(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_cap, key_a, g.skey, val_a,
+                                                   g.sval, (int)E, 0, (int)id_bits + bits_for(C),
+                                                   stream));
+        hipLaunchKernelGGL(k_sorted_locus, dim3(blocks_for(E)), dim3(TPB), 0, stream, raw, g.sval, eloc, E, g.sloc);
+        return g;
+    }
+
+    // ---- 2-4: duplicate rule, reads = runs of equal key, per-read lists, appearance ranks ------
+    // (the number of reads R stays on the device until read-back 2; buffers indexed by read are laid
+    // out for the upper bound E)
+    Attempt ensure_outputs() {
+        const size_t n_off_max = shape.n_off_max();
+        HIP_OK(pk.read_off.ensure(((size_t)E + 1) * 4));
+        HIP_OK(pk.read_locus.ensure((size_t)E * 4));
+        HIP_OK(pk.read_base.ensure(E));
+        HIP_OK(pk.range_off.ensure(((size_t)L + 2) * 4));
+        HIP_OK(pk.entry.ensure((size_t)E * 16));
+        HIP_OK(pk.entry32.ensure((size_t)E * 4));
+        HIP_OK(pk.mask32.ensure((size_t)E * 4));
+        HIP_OK(pk.entry_read.ensure((size_t)E * 4));
+        HIP_OK(pk.blk_off.ensure((n_off_max + 1) * 4));
+        return Attempt();
+    }
+    ReadViews read_views(const Grouped &g) const {
+        const MarksRanksCounts marks(S[Arena::KEY_A].p, shape);
+        return ReadViews{KeepFlags(S[Arena::WORK_A].p, (size_t)E + 1),
+                         InclSums(S[Arena::WORK_B].p, (size_t)E + 1),
+                         marks,
+                         Runs(S[Arena::RUNS].p, shape),
+                         g.single_entry ? MarksOfM(S[Arena::MARK_M].p, (size_t)E + 2).p : nullptr,
+                         g.single_entry ? PerM(S[Arena::ARANK_M].p, E).p : nullptr,
+                         Ranks{g.m_index, g.single_entry ? marks.arank : nullptr, marks.arank},
+                         pk.read_off.as<uint32_t>(),
+                         pk.read_locus.as<uint32_t>(),
+                         pk.read_base.as<uint8_t>()};
+    }
+    // Reads from the current `split` flags (cuts of reads that outlive max_fragment_length: none on the first build,
+    // null), then completed counts and the flush chain. The chain is sequential (one lane per chromosome) and only
+    // the final gather needs its result: it runs on a side stream, next to the grouping of the kept entries.
+    Attempt build_reads(const Grouped &g, const ReadViews &v, const uint32_t *split) {
+        const uint32_t n_m = g.n_m;
+        uint32_t *mark_sub = g.single_entry ? v.mark_sub : v.marks.mark, *arank = v.marks.arank;
+        if (n_m) {
+            hipLaunchKernelGGL(k_dup_mark, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, g.sub, g.skey, g.sval, g.sloc, split,
+                               n_m, v.keep, mark_sub);
+            hipcub::CountingInputIterator<uint32_t> positions(0u);
+            hipcub::TransformInputIterator<unsigned long long, HeadKeepOp, hipcub::CountingInputIterator<uint32_t>>
+                    flags(positions, HeadKeepOp{g.skey, v.keep, split});
+            size_t cub_cap = S[Arena::CUB].bytes;
+            HIP_OK(hipcub::DeviceScan::InclusiveSum(cub_tmp, cub_cap, flags, v.incl, (int)n_m, stream));
+        }
+        const uint32_t *arank_sub = arank;
+        if (g.single_entry) {  // (the ranks' array holds the n_m + 1 prefix sums `unm` instead: struct Ranks)
+            hipcub::CountingInputIterator<uint32_t> entries(0u);
+            hipcub::TransformInputIterator<uint32_t, UnmarkedM, hipcub::CountingInputIterator<uint32_t>> unmarked(
+                    entries, UnmarkedM{mark_sub, n_m});
+            HIP_OK(exclusive_sum(unmarked, arank, (size_t)n_m + 1));
+            hipLaunchKernelGGL(k_arank_m, dim3(blocks_for(std::max(n_m, 1u))), dim3(TPB), 0, stream, arank, g.m_entry, n_m,
+                               E, v.arank_m, sc);
+            arank_sub = v.arank_m;
+            hipLaunchKernelGGL(k_rbeg, dim3(1), dim3(TPB), 0, stream, raw, v.ranks, m.rbeg);
+        } else {
+            HIP_OK(exclusive_sum(v.marks.mark, arank, (size_t)E + 1));
+        }
+        if (n_m) {
+            hipLaunchKernelGGL(k_runs_csr, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, g.sub, v.incl, g.sval, g.sloc, n_m,
+                               v.runs.run_start, v.read_locus, v.read_base);
+            hipLaunchKernelGGL(k_read_info, dim3(std::min<uint32_t>(blocks_for(n_m), 2048)), dim3(TPB), 0, stream, g.sub,
+                               v.incl, v.runs.run_start, g.sval, g.sloc, arank_sub, mfl, v.runs.run_rank,
+                               g.single_entry ? nullptr : m.rbeg, v.read_off, sc);
+        }
+        HIP_OK(hipEventRecord(pk.ev_fork, stream));
+        HIP_OK(hipStreamWaitEvent(pk.side, pk.ev_fork, 0));
+        hipLaunchKernelGGL(k_completed, dim3(blocks_for(L)), dim3(TPB), 0, pk.side, raw, v.ranks, m.rbeg, mfl, m.cnt, sc);
+        hipLaunchKernelGGL(k_flush_chain, dim3(C), dim3(TPB), 0, pk.side, raw, m.cnt, 4u * num_threads, sc, m.flushed,
+                           m.flush_loci, m.flush_count, v.ranks, m.rbeg, g.single_entry ? m.tail_begin : nullptr);
+        HIP_OK(hipEventRecord(pk.ev_flush, pk.side));
+        HIP_OK(hipEventRecord(pk.ev_join, pk.side));
+        return Attempt();
+    }
+    // Some id's entries span >= max_fragment_length: a flush may erase it before its last entry and the id re-opens
+    // as a new read. Cut at the flush loci, rebuild, repeat until the cuts are stable (they move forward with the
+    // flushes they cause: a few rounds). The cuts live in TMP, free until k_keys2.
+    Attempt settle_flush_cuts(const Grouped &g, const ReadViews &v, Scalars *hsc, unsigned long long *totals) {
+        const uint32_t n_m = g.n_m;
+        uint32_t *split = SplitFlags(S[Arena::TMP].p, E);
+        HIP_OK(hipMemsetAsync(split, 0, (size_t)std::max(n_m, 1u) * 4, stream));
+        for (int round = 0; round < kMaxSplitRounds; ++round) {
+            HIP_OK(hipStreamWaitEvent(stream, pk.ev_join, 0));  // the chain of the previous build
+            HIP_OK(hipMemsetAsync(&sc->split_changed, 0, 4, stream));
+            hipLaunchKernelGGL(k_split_update, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, g.sub, g.skey, g.sloc, mfl,
+                               m.flush_loci, m.flush_count, split, sc);
+            HIP_OK(read_scalars(pk, stream, sc, nullptr, hsc, nullptr));
+            if (!hsc->split_changed) return Attempt();
+            HIP_OK(hipMemsetAsync(&sc->multi_entries, 0, 8, stream));  // k_read_info adds to it
+            STEP(build_reads(g, v, split));
+            HIP_OK(read_scalars(pk, stream, sc, n_m ? v.incl + (n_m - 1) : nullptr, hsc, totals));
+        }
+        return Attempt::stop(Attempt::NeedHost);  // did not settle: the exact sequential emulation decides
+    }
+
+    // ---- 5: kept entries grouped by (cell block, locus, cell), offsets, bound, ranges, records ----
+    void launch_ranges_segment(const Stage5 &s, hipStream_t on) {
+        hipLaunchKernelGGL(k_ranges_segment, dim3(s.p.n_seg, s.p.caps.allow_counts ? 2u : 1u), dim3(TPB), 0, on, s.blk_off,
+                           s.p.nb, L, s.p.caps, s.segs.seg_ends, s.segs.seg_count, s.p.variant_stride);
+    }
+    Attempt cut_ranges_on_side(const Stage5 &s) {  // call when blk_off is complete on `stream`
         HIP_OK(hipEventRecord(pk.ev_offsets, stream));
         HIP_OK(hipStreamWaitEvent(pk.side, pk.ev_offsets, 0));
-        hipLaunchKernelGGL(k_ranges_segment, dim3(n_seg, caps.allow_counts ? 2u : 1u), dim3(TPB), 0, pk.side, blk_off, nb,
-                           L, caps, seg_ends, seg_count, variant_stride);
+        launch_ranges_segment(s, pk.side);
         HIP_OK(hipEventRecord(pk.ev_join, pk.side));
-        return std::string();
-    };
-    if (force_radix) HIP_OK(hipMemsetAsync(blk_cnt, 0, (n_off + 1) * 4, stream));
-    HIP_OK(hipMemsetAsync(per_cell_sq, 0, ((size_t)nb * B + 1) * 8, stream));
-    // per kept entry what k_records needs of its read: appearance rank (the duplicate-rule flags in WORK_A
-    // are dead) and base | multi flag (the grouped ids in VAL_A are dead)
-    uint32_t *krank = work_a;
-    uint8_t *kflags = S[VAL_A].as<uint8_t>();
-    uint32_t TL = 0, locus_grid = 0;
-    size_t lds = 0;
-    if (!force_radix) bin_tiles(nb, &TL, &locus_grid, &lds);
-    const bool hist_first = split_singles && !force_radix;  // the S entries are counted before the M entries join
-    if (hist_first) {
-        // (the group -> cell map rides in LDS if it fits beside the tile: 2 bytes per group)
-        static const bool g2p_allowed = [] { const char *e = std::getenv("SECEDO_PACK_G2P_LDS"); return !(e && std::atoi(e) == 0); }();
-        const size_t g2p_bytes = ((size_t)in.n_groups * 2 + 15) / 16 * 16;
-        const bool g2p_lds = g2p_allowed && num_cells <= 0xFFFFu && lds + g2p_bytes <= 49152;
-        hipLaunchKernelGGL(k_bin_hist, dim3(g2p_lds ? std::min<uint32_t>(locus_grid, 1024) : locus_grid), dim3(TPB),
-                           lds + (g2p_lds ? g2p_bytes : 0), stream, raw, nb, TL, entry_kc, m_index.chunk_mask, num_cells, B_log2, blk_cnt,
-                           sc, g2p_lds ? 1u : 0u);
+        return Attempt();
     }
-    if (n_m)
-        hipLaunchKernelGGL(k_keys2, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, sub, sval, incl, read_locus, run_rank,
-                           read_off, num_cells, B, lbits, force_radix ? key2_a : nullptr, force_radix ? val2_a : nullptr,
-                           t_read, krank, kflags, entry_kc, split_singles ? m_entry : nullptr,
-                           hist_first ? blk_cnt : nullptr, L, sc);
-    trace.mark("k_keys2 launched");
-    const uint32_t slice_grid = std::min<uint32_t>(2048, (n_kept + 4095) / 4096);
-    if (force_radix) {
-        if (n_kept) {
-            cub_cap = S[CUB].bytes;
-            HIP_OK(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_cap, key2_a, key2_b, val2_a, val2_b, (int)n_kept,
-                                                       0, (int)(kCibBits + lbits) + bits_for(nb - 1), stream));
-            hipLaunchKernelGGL(k_group_counts, dim3(slice_grid), dim3(TPB), 0, stream, key2_b, n_kept, B, L, lbits,
-                               blk_cnt, per_cell_sq);
+    // the M entries' records, on the side stream beside the placing pass
+    Attempt m_records_on_side(const Stage5 &s, const ReadViews &v) {
+        hipLaunchKernelGGL(k_m_records, dim3(blocks_for(s.kept_m)), dim3(TPB), 0, pk.side, raw, s.kept_m, s.t_read,
+                           v.read_off, v.read_locus, v.read_base, s.krank, s.kflags, m.rbeg, m.flushed,
+                           s.m_rec, sc);
+        HIP_OK(hipEventRecord(pk.ev_join, pk.side));
+        return Attempt();
+    }
+    // the locus ranges picked from the segments (assumed: 1 the count tile's limits, 0 the plain ones, -1 by the pair
+    // bound of sq_rows rows) and what a record needs of its locus
+    void pick_ranges(const Stage5 &s, uint32_t sq_rows, int assumed, const uint8_t *dupflag) {
+        hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, stream, s.segs.seg_ends, s.segs.seg_count,
+                           s.p.variant_stride, s.p.n_seg, s.p.caps, pk.range_off.as<uint32_t>(), s.per_cell_sq, sq_rows,
+                           assumed, sc);
+        if (s.n_kept)
+            hipLaunchKernelGGL(k_locus_info, dim3(blocks_for(L)), dim3(TPB), 0, stream, raw, pk.range_off.as<uint32_t>(),
+                               sc, dupflag, m.locus_chr, m.locus_rel);
+    }
+
+    // radix route: sort the kept entries by (block, locus, cell), count the groups
+    Attempt bin_radix(const Stage5 &s) {
+        const BinRadix &b = s.bin;
+        if (s.n_kept) {
+            size_t cub_cap = S[Arena::CUB].bytes;
+            HIP_OK(hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_cap, b.key2_a, b.key2_b, b.val2_a, b.val2_b,
+                                                       (int)s.n_kept, 0, (int)(kCibBits + s.p.lbits) + bits_for(s.p.nb - 1),
+                                                       stream));
+            hipLaunchKernelGGL(k_group_counts, dim3(std::min<uint32_t>(2048, (s.n_kept + 4095) / 4096)), dim3(TPB), 0,
+                               stream, b.key2_b, s.n_kept, s.p.B, L, s.p.lbits, s.blk_cnt, s.per_cell_sq);
         }
-        cub_cap = S[CUB].bytes;
-        HIP_OK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, blk_cnt, blk_off, (int)n_off, stream));
-        const std::string err = cut_ranges_on_side();
-        if (!err.empty()) return err;
-    } else {
+        HIP_OK(exclusive_sum(s.blk_cnt, s.blk_off, s.n_off));
+        return cut_ranges_on_side(s);
+    }
+    // counting route: per-locus LDS histograms (hist_first: launched already, in front of k_keys2), scan, placement
+    Attempt bin_counting(const Grouped &g, const ReadViews &v, const Stage5 &s, bool hist_first) {
+        const TilePlan &p = s.p;
         if (!hist_first)
-            hipLaunchKernelGGL(k_bin_hist, dim3(locus_grid), dim3(TPB), lds, stream, raw, nb, TL, entry_kc, nullptr, num_cells,
-                               B_log2, blk_cnt, sc, 0u);
+            hipLaunchKernelGGL(k_bin_hist, dim3(p.locus_grid), dim3(TPB), p.lds, stream, raw, p.nb, p.TL, s.entry_kc, nullptr,
+                               num_cells, p.B_log2, s.blk_cnt, sc, 0u);
         trace.mark("k_bin_hist launched");
         // Where most kept entries belong to multi-entry reads (clustered loci) the M entries' records are the longest
         // kernel of the packing (C3 clustered: 1.5 ms) and nothing but k_keys2 and the flush chain stands before
@@ -2494,128 +2499,202 @@ std::string pack_attempt(const DeviceFlatPileup &in, uint32_t num_cells, uint32_
         // AND the placing pass, not behind the range cutting (round 4: 0.5 ms of a 7.6 ms packing) --, and the short
         // range cutting stays on the main stream in front of the placing pass. On sparse loci (few M entries) the
         // order of round 3: range cutting, then the records, both on the side stream.
-        const bool records_first = kept_m && (uint64_t)kept_m * 4u > (uint64_t)n_kept;
+        const bool records_first = s.kept_m && (uint64_t)s.kept_m * 4u > (uint64_t)s.n_kept;
         if (records_first) {
             HIP_OK(hipEventRecord(pk.ev_offsets, stream));  // k_keys2 is through
             HIP_OK(hipStreamWaitEvent(pk.side, pk.ev_offsets, 0));
-            hipLaunchKernelGGL(k_m_records, dim3(blocks_for(kept_m)), dim3(TPB), 0, pk.side, raw, kept_m, t_read, read_off,
-                               read_locus, read_base, krank, kflags, rbeg, flushed, m_rec, sc);
-            HIP_OK(hipEventRecord(pk.ev_join, pk.side));
+            STEP(m_records_on_side(s, v));
         }
-        cub_cap = S[CUB].bytes;
-        HIP_OK(hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_cap, blk_cnt, blk_off, (int)n_off, stream));
+        HIP_OK(exclusive_sum(s.blk_cnt, s.blk_off, s.n_off));
         trace.mark("offset scan launched");
         if (records_first) {
-            hipLaunchKernelGGL(k_ranges_segment, dim3(n_seg, caps.allow_counts ? 2u : 1u), dim3(TPB), 0, stream, blk_off, nb,
-                               L, caps, seg_ends, seg_count, variant_stride);
+            launch_ranges_segment(s, stream);
         } else {
-            const std::string err = cut_ranges_on_side();
-            if (!err.empty()) return err;
-            if (kept_m) {  // behind the flush chain and the range cutting, beside the placing pass
-                hipLaunchKernelGGL(k_m_records, dim3(blocks_for(kept_m)), dim3(TPB), 0, pk.side, raw, kept_m, t_read,
-                                   read_off, read_locus, read_base, krank, kflags, rbeg, flushed, m_rec, sc);
-                HIP_OK(hipEventRecord(pk.ev_join, pk.side));
-            }
+            STEP(cut_ranges_on_side(s));
+            if (s.kept_m) STEP(m_records_on_side(s, v));  // behind the flush chain and the range cutting
         }
-        if (n_kept) {
-            unsigned long long *grouped = key_b;  // the sorted entry keys are dead after k_dup_rule
+        if (s.n_kept) {
             HIP_OK(hipStreamWaitEvent(stream, pk.ev_flush, 0));  // the S entries' tail flags
             // (a bitmap over the cells per wave beside the cursors, if 48 KiB of LDS hold both)
-            uint32_t bm_words = (nb * B + 31) / 32;
-            if (lds + (size_t)(TPB / 64) * bm_words * 4 > 49152) bm_words = 0;
-            hipLaunchKernelGGL(k_bin_place, dim3(locus_grid), dim3(TPB), lds + (size_t)(TPB / 64) * bm_words * 4, stream,
-                               raw, nb, TL, entry_kc, blk_off, B_log2, bm_words, split_singles ? tail_begin : nullptr,
-                               grouped, dupflag);
+            uint32_t bm_words = (p.nb * p.B + 31) / 32;
+            if (p.lds + (size_t)(TPB / 64) * bm_words * 4 > 49152) bm_words = 0;
+            hipLaunchKernelGGL(k_bin_place, dim3(p.locus_grid), dim3(TPB), p.lds + (size_t)(TPB / 64) * bm_words * 4, stream,
+                               raw, p.nb, p.TL, s.entry_kc, s.blk_off, p.B_log2, bm_words,
+                               g.single_entry ? m.tail_begin : nullptr, GroupedKept(S[Arena::KEY_B].p, E).p, s.dupflag);
         }
+        return Attempt();
     }
-    // the locus ranges were cut for both sets of limits on the side stream (after the flush chain): pick
-    HIP_OK(hipStreamWaitEvent(stream, pk.ev_join, 0));
-    side_join.joined = true;
-    bool lists_launched = false;
-    if (force_radix) {
-        hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, stream, seg_ends, seg_count, variant_stride, n_seg,
-                           caps, pk.range_off.as<uint32_t>(), per_cell_sq, n_kept ? nb * B : 0u, -1, sc);
-        if (n_kept) {
-            hipLaunchKernelGGL(k_locus_info, dim3(blocks_for(L)), dim3(TPB), 0, stream, raw, pk.range_off.as<uint32_t>(),
-                               sc, nullptr, locus_chr, locus_rel);
-            hipLaunchKernelGGL(k_records, dim3(blocks_for(n_kept)), dim3(TPB), 0, stream, raw, key2_b, val2_b, n_kept,
-                               t_read, read_off, read_locus, read_base, krank, kflags, rbeg, flushed, locus_chr,
-                               locus_rel, B, lbits, pk.entry.as<uint4>(), pk.entry32.as<uint32_t>(),
+    void records_radix(const ReadViews &v, const Stage5 &s) {
+        const BinRadix &b = s.bin;
+        pick_ranges(s, s.n_kept ? s.p.nb * s.p.B : 0u, -1, nullptr);
+        if (s.n_kept)
+            hipLaunchKernelGGL(k_records, dim3(blocks_for(s.n_kept)), dim3(TPB), 0, stream, raw, b.key2_b, b.val2_b, s.n_kept,
+                               s.t_read, v.read_off, v.read_locus, v.read_base, s.krank, s.kflags, m.rbeg, m.flushed,
+                               m.locus_chr, m.locus_rel, s.p.B, s.p.lbits, pk.entry.as<uint4>(), pk.entry32.as<uint32_t>(),
                                pk.stage_masks ? pk.mask32.as<uint32_t>() : nullptr, pk.entry_read.as<uint32_t>(), sc);
-        }
-    } else {
-        // Counting path: the entries stay in k_bin_place's order and one pass, a thread per (block, locus)
-        // group, writes the records and sums the per-cell squares. The locus ranges (their range-relative
-        // locus is part of a record) are cut for the count tile if it is allowed at all; the pair bound comes
-        // out of the same pass, and if it forbids the count tile the ranges are cut again and the records
-        // patched (deep pileups only).
-        const int assumed = caps.allow_counts ? 1 : 0;
-        hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, stream, seg_ends, seg_count, variant_stride, n_seg,
-                           caps, pk.range_off.as<uint32_t>(), per_cell_sq, 0u, assumed, sc);
-        if (n_kept) {
-            hipLaunchKernelGGL(k_locus_info, dim3(blocks_for(L)), dim3(TPB), 0, stream, raw, pk.range_off.as<uint32_t>(),
-                               sc, dupflag, locus_chr, locus_rel);
-            const RecordTables tables{m_rec, locus_rel, pk.entry.as<uint4>(), pk.entry32.as<uint32_t>(),
-                                      pk.stage_masks ? pk.mask32.as<uint32_t>() : nullptr,
-                                      pk.entry_read.as<uint32_t>()};
-            const unsigned long long *grouped = key_b;
+    }
+    // Counting route: the entries stay in k_bin_place's order and one pass, a thread per (block, locus) group, writes
+    // the records and sums the per-cell squares. The locus ranges (their range-relative locus is part of a record)
+    // are cut for the count tile if it is allowed at all; the pair bound comes out of the same pass, and if it forbids
+    // the count tile the ranges are cut again and the records patched (deep pileups only: close_attempt).
+    // Returns whether the records pass left the flags the flagged entries' lists are made of.
+    bool records_counting(const Stage5 &s) {
+        const TilePlan &p = s.p;
+        const int assumed = p.caps.allow_counts ? 1 : 0;
+        bool lists_here = false;
+        pick_ranges(s, 0u, assumed, s.dupflag);
+        if (s.n_kept) {
+            const RecordTables tables{s.m_rec, m.locus_rel, pk.entry.as<uint4>(), pk.entry32.as<uint32_t>(),
+                                      pk.stage_masks ? pk.mask32.as<uint32_t>() : nullptr, pk.entry_read.as<uint32_t>()};
             // The flagged entries' lists are wanted wherever the count tile is taken, and they do not depend on what
             // read-back 3 decides (the records carry the absolute locus, k_fix_locus_rel touches the upper half of
             // entry32 only): the records pass leaves the chunks' flags, and the list chain goes behind the publishing
-            // kernel of read-back 3 (below). If the pair bound forbids the count tile the lists are not used.
-            const bool lists_here = overlap && caps.allow_counts && !pk.stage_masks && pk.flag_lists.scratch;
-            const FlagScratch fs(pk.flag_lists.scratch, n_kept);
-            hipLaunchKernelGGL(k_entry_records, dim3((n_kept + kFlagBlock - 1) / kFlagBlock), dim3(TPB_REC), 0, stream,
-                               grouped, blk_off, n_kept, nb, L, B, lbits, tables, per_cell_sq, sc,
-                               lists_here ? fs.chunk_mask : nullptr, lists_here ? fs.block_sum : nullptr);
-            lists_launched = lists_here;
+            // kernel of read-back 3. If the pair bound forbids the count tile the lists are not used.
+            lists_here = overlap && p.caps.allow_counts && !pk.stage_masks && pk.flag_lists.scratch;
+            const FlagScratch fs(pk.flag_lists.scratch, s.n_kept);
+            hipLaunchKernelGGL(k_entry_records, dim3((s.n_kept + kFlagBlock - 1) / kFlagBlock), dim3(TPB_REC), 0, stream,
+                               GroupedKept(S[Arena::KEY_B].p, E).p, s.blk_off, s.n_kept, p.nb, L, p.B, p.lbits, tables,
+                               s.per_cell_sq, sc, lists_here ? fs.chunk_mask : nullptr, lists_here ? fs.block_sum : nullptr);
         }
-        hipLaunchKernelGGL(k_pair_bound, dim3(1), dim3(TPB), 0, stream, per_cell_sq, n_kept ? nb * B : 0u, caps,
+        hipLaunchKernelGGL(k_pair_bound, dim3(1), dim3(TPB), 0, stream, s.per_cell_sq, s.n_kept ? p.nb * p.B : 0u, p.caps,
                            (uint32_t)assumed, sc);
+        return lists_here;
     }
     // read-back 3: errors of the group mapping, pair bound (-> tile variant), number of ranges. The list chain goes
     // behind its publishing kernel: the GPU works through the lists while the host reads the scalars, returns to its
     // caller and launches the pair kernel. (In front of the publishing kernel the host learned the scalars 50 us
     // later and the GPU then stood idle for as long as the host needs from there to the pair kernel's launch: 74 us
     // under the profiler on C3, and C2, whose lists take 15 us, lost 20 us against the lists behind the read-back.)
-    trace.mark("records launched");
-    HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr, [&] {
-        if (lists_launched)
-            flag_lists_from_masks(FlagScratch(pk.flag_lists.scratch, n_kept), pk.entry.as<uint4>(), blk_off, n_off,
-                                  pk.flag_lists.grp, pk.flag_lists.rec, pk.flag_lists.idx, stream);
-    }));
-    trace.mark("read-back 3 arrived");
-    if (!force_radix && hsc.caps_wrong && !hsc.regroup && hsc.error == 0) {
-        hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, stream, seg_ends, seg_count, variant_stride, n_seg,
-                           caps, pk.range_off.as<uint32_t>(), per_cell_sq, 0u, 0, sc);
-        if (n_kept) {
-            hipLaunchKernelGGL(k_locus_info, dim3(blocks_for(L)), dim3(TPB), 0, stream, raw, pk.range_off.as<uint32_t>(),
-                               sc, nullptr, locus_chr, locus_rel);
-            hipLaunchKernelGGL(k_fix_locus_rel, dim3(blocks_for(n_off)), dim3(TPB), 0, stream, blk_off, nb, L, locus_rel,
-                               pk.entry32.as<uint32_t>());
+    Attempt close_attempt(const Stage5 &s, bool lists_launched) {
+        const TilePlan &p = s.p;
+        Scalars hsc;
+        trace.mark("records launched");
+        HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr, [&] {
+            if (lists_launched)
+                flag_lists_from_masks(FlagScratch(pk.flag_lists.scratch, s.n_kept), pk.entry.as<uint4>(), s.blk_off, s.n_off,
+                                      pk.flag_lists.grp, pk.flag_lists.rec, pk.flag_lists.idx, stream);
+        }));
+        trace.mark("read-back 3 arrived");
+        if (!force_radix && hsc.caps_wrong && !hsc.regroup && hsc.error == 0) {
+            pick_ranges(s, 0u, 0, nullptr);
+            if (s.n_kept)
+                hipLaunchKernelGGL(k_fix_locus_rel, dim3(blocks_for(s.n_off)), dim3(TPB), 0, stream, s.blk_off, p.nb, L,
+                                   m.locus_rel, pk.entry32.as<uint32_t>());
+            HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));  // the number of ranges
         }
-        HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));  // the number of ranges
+        STEP(scalar_verdict(hsc, true));
+        pk.pair_bound = hsc.pair_bound;
+        pk.cell_sq = s.per_cell_sq;
+        pk.cell_sq_n = s.n_kept ? p.nb * p.B : 0u;
+        pk.cell_sq_host.clear();
+        pk.count_tile = p.caps.allow_counts && pk.pair_bound < kCountTileLimit;
+        pk.cap_entries = pk.count_tile ? p.caps.entries_counts : p.caps.entries_plain;
+        pk.cap_loci = pk.count_tile ? p.caps.loci_counts : p.caps.loci_plain;
+        pk.num_ranges = hsc.num_ranges;
+        pk.max_range_span = hsc.max_range_span;
+        pk.n_wide = hsc.n_wide;
+        pk.flag_lists_built = lists_launched;
+        HIP_OK(hipGetLastError());
+        return Attempt::stop(Attempt::Done);
     }
-    if (hsc.error == 1) return "group id outside group_id_to_pos";
-    if (hsc.error == 2) return "group_id_to_pos maps outside the matrix";
-    if (hsc.regroup) {
-        *retry = kRetryRadix;
-        return std::string();
+
+    Attempt run() {
+        STEP(prepare_workspace());
+        trace.t0 = std::chrono::steady_clock::now();
+        trace.mark("begin");
+        const Grouped g = group_by_read();
+        if (!g.go()) return g;
+        pk.used_single_entry = g.single_entry;
+
+        STEP(ensure_outputs());
+        const ReadViews v = read_views(g);
+        STEP(build_reads(g, v, nullptr));
+        struct SideJoin {  // every way out of this function leaves the side stream idle
+            hipStream_t side;
+            bool joined = false;
+            ~SideJoin() { if (!joined) (void)hipStreamSynchronize(side); }
+        } side_join{pk.side};
+
+        // read-back 2: status flags, R, number of kept entries, multi-locus statistics
+        Scalars hsc;
+        unsigned long long totals = 0;  // reads | kept entries << 32
+        trace.mark("reads built (launched)");
+        HIP_OK(read_scalars(pk, stream, sc, g.n_m ? v.incl + (g.n_m - 1) : nullptr, &hsc, &totals));
+        trace.mark("read-back 2 arrived");
+        const Attempt verdict = scalar_verdict(hsc, false);
+        if (verdict.go() || verdict.kind == Attempt::RetryRadix || verdict.kind == Attempt::NeedHost)
+            pk.id_space_hint = g.counting ? std::max<uint64_t>(hsc.id_space, 1) : 0;  // (a void attempt: the caller drops it)
+        STEP(verdict);
+        if (hsc.long_reads) STEP(settle_flush_cuts(g, v, &hsc, &totals));
+
+        // (single-entry route: `totals` counts the reads and kept entries of the M entries; every S entry is a
+        // read and a kept entry of its own)
+        const uint32_t kept_m = (uint32_t)(totals >> 32);
+        const uint32_t R = g.single_entry ? hsc.reads_total : (uint32_t)totals;
+        const uint32_t n_kept = g.single_entry ? kept_m + (E - g.n_m) : kept_m;
+        pk.multi_entries = hsc.multi_entries;
+        pk.max_read_entries = std::max(hsc.max_read_entries, n_kept ? 1u : 0u);
+        const TilePlan p = plan_tiles(num_cells, L, block_cells, geometry, allow_count_tile, n_kept, pk.multi_entries);
+        if (p.B != 64 && p.B != 128) return Attempt::error("block_cells must be 64 or 128");
+        // k_bin_place packs the locus into 25 bits at most, and bit 31 of a k marks an S entry
+        if (!force_radix && (p.lbits + kCibBits > 32u || E >= kSingle)) return Attempt::stop(Attempt::RetryRadix);
+        pk.num_cells = num_cells;
+        pk.block_cells = p.B;
+        pk.num_blocks = p.nb;
+        pk.num_loci = L;
+        pk.num_entries = n_kept;
+        pk.num_reads = R;
+        pk.stage_masks = p.stage_masks;
+
+        HIP_OK(ensure(Arena::DUPF));
+        HIP_OK(S[Arena::SEGS].ensure(carved<Segs>((size_t)p.n_seg, p.variant_stride)));
+        const size_t nk = std::max<uint32_t>(n_kept, 1), rows = (size_t)p.nb * p.B;
+        const BinRadix bin(S[Arena::BIN].p, nk, rows);
+        const Stage5 s{p,
+                       n_kept,
+                       kept_m,
+                       (size_t)p.nb * ((size_t)L + 1),
+                       KeptRead(S[Arena::TMP].p, E),
+                       KeptRank(S[Arena::WORK_A].p, E),
+                       pk.blk_off.as<uint32_t>(),
+                       v.marks.blk_cnt,
+                       KeptFlags(S[Arena::VAL_A].p, E),
+                       DupFlags(S[Arena::DUPF].p, L),
+                       force_radix ? nullptr : EntryKC(S[Arena::ENTRY_KC].p, E).p,
+                       bin,
+                       reinterpret_cast<uint4 *>(BinCounting(S[Arena::BIN].p, nk, rows).m_rec),
+                       bin.per_cell_sq,
+                       Segs(S[Arena::SEGS].p, p.n_seg, p.variant_stride)};
+        if (force_radix) HIP_OK(hipMemsetAsync(s.blk_cnt, 0, (s.n_off + 1) * 4, stream));
+        HIP_OK(hipMemsetAsync(s.per_cell_sq, 0, (rows + 1) * 8, stream));
+        const bool hist_first = g.single_entry && !force_radix;  // the S entries are counted before the M entries join
+        if (hist_first) {
+            // (the group -> cell map rides in LDS if it fits beside the tile: 2 bytes per group)
+            const size_t g2p_bytes = ((size_t)in.n_groups * 2 + 15) / 16 * 16;
+            const bool g2p_lds = num_cells <= 0xFFFFu && p.lds + g2p_bytes <= 49152;
+            hipLaunchKernelGGL(k_bin_hist, dim3(g2p_lds ? std::min<uint32_t>(p.locus_grid, 1024) : p.locus_grid), dim3(TPB),
+                               p.lds + (g2p_lds ? g2p_bytes : 0), stream, raw, p.nb, p.TL, s.entry_kc, g.m_index.chunk_mask,
+                               num_cells, p.B_log2, s.blk_cnt, sc, g2p_lds ? 1u : 0u);
+        }
+        if (g.n_m) {
+            hipLaunchKernelGGL(k_keys2, dim3(blocks_for(g.n_m)), dim3(TPB), 0, stream, g.sub, g.sval, v.incl, v.read_locus,
+                               v.runs.run_rank, v.read_off, num_cells, p.B, p.lbits, force_radix ? bin.key2_a : nullptr,
+                               force_radix ? bin.val2_a : nullptr, s.t_read, s.krank, s.kflags, s.entry_kc,
+                               g.single_entry ? g.m_entry : nullptr, hist_first ? s.blk_cnt : nullptr, L, sc);
+        }
+        trace.mark("k_keys2 launched");
+        STEP(force_radix ? bin_radix(s) : bin_counting(g, v, s, hist_first));
+        // the locus ranges were cut for both sets of limits on the side stream (after the flush chain): pick
+        HIP_OK(hipStreamWaitEvent(stream, pk.ev_join, 0));
+        side_join.joined = true;
+        bool lists_launched = false;
+        if (force_radix)
+            records_radix(v, s);
+        else
+            lists_launched = records_counting(s);
+        return close_attempt(s, lists_launched);
     }
-    pk.pair_bound = hsc.pair_bound;
-    pk.cell_sq = per_cell_sq;
-    pk.cell_sq_n = n_kept ? nb * B : 0u;
-    pk.cell_sq_host.clear();
-    pk.count_tile = caps.allow_counts && pk.pair_bound < kCountTileLimit;
-    pk.cap_entries = pk.count_tile ? caps.entries_counts : caps.entries_plain;
-    pk.cap_loci = pk.count_tile ? caps.loci_counts : caps.loci_plain;
-    pk.num_ranges = hsc.num_ranges;
-    pk.max_range_span = hsc.max_range_span;
-    pk.n_wide = hsc.n_wide;
-    pk.flag_lists_built = lists_launched;
-    HIP_OK(hipGetLastError());
-    return std::string();
-}
+};
 
 }  // namespace
 
@@ -2647,9 +2726,7 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
     if (const char *env = std::getenv("SECEDO_PACK_OVERLAP")) overlap = std::atoi(env) != 0;
     // an attempt can ask to be repeated: with the radix sorts (a group too long for the counting scheme),
     // or as it was but without assuming the previous call's sizes
-    int retry = kNoRetry;
     bool no_assumptions = false;
-    std::string err;
     for (int attempt = 0; attempt < 3; ++attempt) {
         if (poison_level() >= 2) {  // debugging aid: nothing may depend on what the buffers held
             if (hipStreamSynchronize(stream) != hipSuccess || (out->side && hipStreamSynchronize(out->side) != hipSuccess))
@@ -2661,14 +2738,21 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
             for (DeviceArena &a : out->scratch)
                 if (a.p && hipMemset(a.p, 0xA5, a.bytes) != hipSuccess) return "poison: memset failed";
         }
-        err = pack_attempt(in, num_cells, mfl, num_threads, block_cells, geometry, allow_count_tile, force_radix,
-                           no_assumptions, overlap, stream, out, need_host, &retry);
-        if (!err.empty() || retry == kNoRetry) break;
-        if (retry == kRetryRadix) force_radix = true;
-        if (retry == kRetrySameScheme) no_assumptions = true;
+        Attempt result = PackAttempt(in, num_cells, mfl, num_threads, block_cells, geometry, allow_count_tile, force_radix,
+                                     no_assumptions, overlap, stream, *out).run();
+        switch (result.kind) {
+            case Attempt::Error: return std::move(result.text);
+            case Attempt::NeedHost: *need_host = true; return std::string();
+            case Attempt::RetryRadix: force_radix = true; break;
+            case Attempt::RetryPlain:  // the sizes of the previous call did not hold: ask the device
+                no_assumptions = true;
+                out->id_space_hint = 0;
+                break;
+            default: return std::string();
+        }
     }
-    if (err.empty() && retry != kNoRetry) *need_host = true;  // cannot happen: three attempts cover both requests
-    return err;
+    *need_host = true;  // cannot happen: three attempts cover both requests
+    return std::string();
 }
 
 
@@ -2687,3 +2771,4 @@ hipError_t pack_flag_lists(const uint32_t *entry32, const uint4 *entry, uint32_t
 }
 
 }  // namespace secedo
+

@@ -8,6 +8,7 @@
 #pragma once
 
 #include "pack_host.hpp"
+#include "pack_workspace.hpp"
 
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
@@ -54,7 +55,7 @@ struct DeviceArena {
 // The packed pileup in HBM: the arrays of PackedPileup, device resident
 struct DevicePacked {
     DeviceArena blk_off, entry32, mask32, entry, entry_read, range_off, read_off, read_locus, read_base;
-    DeviceArena scratch[24];  // temporaries, kept between calls to avoid re-allocation
+    DeviceArena scratch[Arena::kCount];  // temporaries (pack_workspace.hpp), kept between calls to avoid re-allocation
     uint32_t num_cells = 0, block_cells = 0, num_blocks = 0, num_loci = 0, num_ranges = 0;
     uint64_t num_entries = 0, num_reads = 0, pair_bound = 0, multi_entries = 0;
     uint32_t max_read_entries = 0;  // kept entries of the longest read (before flush splits: an upper bound)
@@ -69,7 +70,7 @@ struct DevicePacked {
     bool stage_masks = false;
     bool count_tile = false;
     uint32_t cap_entries = 0, cap_loci = 0;
-    // loci of the longest locus range (unknown: as long as cap_loci allows). A pack_attempt that returns early leaves
+    // loci of the longest locus range (unknown: as long as cap_loci allows). An attempt that ends early leaves
     // the previous call's value: it only picks accumulate_counts' instance, which tests every range's span against
     // its own capacity before it stages it (a range too long for it is paired from HBM), so a stale value costs
     // speed, never results
