@@ -4,8 +4,9 @@
  * get_next_chromosome and check_is_diploid (:81-224, :281-286). Library libsecedo_variant.so.
  *
  * The per-locus work (base counts per cluster, the genotype decisions, the per-cell counters behind the
- * `scores` file) runs on the GPU (secedo_amd/csrc/variant_kernels.hip). The FASTA / map reading, the gather of
- * the reference genotype per locus and the VCF text stay on the host. The pileup is the flat layout of
+ * `scores` file) runs on the GPU (secedo_amd/csrc/variant_kernels.hip). The map reading and the VCF text stay on
+ * the host; the FASTA parse and the gather of the reference genotype per locus run on the host by default and on the
+ * GPU on the device route (below). The pileup is the flat layout of
  * secedo_simmat.h, with id_base16 or id_base32. Error codes are those of secedo_simmat.h;
  * secedo_variant_last_error() holds the message. No CPU fallback for the compute entry points.
  *
@@ -51,6 +52,64 @@ typedef struct secedo_variant_times {
 
 const char *secedo_variant_last_error(void);
 
+/* ---- The reference genome file ------------------------------------------------------------------------------
+ *
+ * Every entry point that takes a FASTA path accepts three kinds of file, told apart by content, never by name, as
+ * secedo_bam.h tells its inputs apart:
+ *   TEXT  anything that does not start with the gzip magic 1f 8b
+ *   BGZF  gzip members with the BC extra subfield (bgzip, what samtools faidx reads)
+ *   GZIP  gzip without it, one member or several; inflated on the host with zlib, then treated as text
+ * Every member of a compressed file is inflated and its ISIZE and CRC32 are checked, whichever route reads it. A bad
+ * BGZF member is SECEDO_E_INVALID_ARG "<path>: BGZF block <k>: inflate failed or ISIZE mismatch" or "... CRC32
+ * mismatch" (the lowest k, ahead of any error of the parse); a truncated or corrupt gzip stream is
+ * SECEDO_E_INVALID_ARG naming the path.
+ *
+ * Two routes compute locus_ref and chr_locus_end. HOST: the parser that restates the reference's stream calls, one
+ * thread, then the gather on the host. DEVICE: the text (BGZF: the compressed members, inflated by the decoder of
+ * bgzf_kernels.hip) is uploaded in ranges of about SECEDO_FASTA_BATCH_BYTES bytes of text (default 256 MiB, at least
+ * 64 or one BGZF member; the results never depend on it), parsed and gathered in HBM (fasta_kernels.hip); neither the
+ * text nor the inflated bytes of a BGZF file live on the host. The route is read by secedo_variant_calling,
+ * secedo_variant_calling_device and secedo_variant_reference_genotypes_device:
+ *   - TEXT and GZIP follow the setting: secedo_variant_set_fasta_route, else the environment SECEDO_FASTA=host|device
+ *     (unset or empty: host; any other value is SECEDO_E_INVALID_ARG from every call that reads a FASTA, the
+ *     host-only ones included);
+ *   - BGZF takes the device route in those three calls whatever the setting;
+ *   - a non-empty map_file is not supported on the device route (out of scope, not an error): TEXT and GZIP then take
+ *     the host route, a BGZF file is inflated on the GPU, its text downloaded and the host route run on it.
+ * The functions documented "host only" below stay host-only for all three kinds: there both compressed kinds are
+ * inflated with zlib. The results of the two routes are equal byte for byte, the errors word for word. */
+#define SECEDO_FASTA_HOST 0
+#define SECEDO_FASTA_DEVICE 1
+
+#define SECEDO_FASTA_KIND_TEXT 0
+#define SECEDO_FASTA_KIND_BGZF 1
+#define SECEDO_FASTA_KIND_GZIP 2
+
+/* Process-wide. set: SECEDO_E_INVALID_ARG for another value; get: the route set, else the environment's, else HOST
+ * (a negative SECEDO_E_* for an unknown value of SECEDO_FASTA). */
+int secedo_variant_set_fasta_route(int route);
+int secedo_variant_get_fasta_route(void);
+
+/* What the last FASTA-reading call of this thread did. The times are the device route's split (ms); they overlap,
+ * since the upload and inflate of one range run beside the passes of the range before. */
+typedef struct secedo_variant_fasta_info {
+    uint32_t kind;                /* SECEDO_FASTA_KIND_* */
+    uint32_t route;               /* SECEDO_FASTA_* the call took */
+    uint32_t fell_back_for_map;   /* 1: the device route was due but a map file sent the call to the host route */
+    uint32_t reserved;
+    uint64_t host_inflated_bytes; /* text bytes zlib produced on the host */
+    uint64_t device_members;      /* BGZF members inflated on the GPU */
+    uint64_t uploaded_bytes;      /* FASTA bytes sent to the GPU: text, or compressed members */
+    uint64_t text_bytes;          /* FASTA text parsed: by the host parser as far as it read, by the device all of it */
+    uint64_t ranges;              /* ranges of the device route */
+    uint64_t contigs;             /* header lines seen (host route: contigs read) */
+    uint64_t contigs_used;        /* contigs that became (half of) a chromosome of the pileup */
+    double inflate_ms;            /* device: the inflate kernels (device events) */
+    double upload_ms;             /* device: host time inside the uploads */
+    double parse_gather_ms;       /* device: the parse passes, the gathers and the final pass (device events) */
+} secedo_variant_fasta_info;
+int secedo_variant_fasta_stats(secedo_variant_fasta_info *out);
+
 /* Host only (no GPU needed). The reference genome of the pileup's loci: chromosome c of the pileup takes the
  * c-th contig (diploid FASTA: contig pair) of `fasta`, as the reference's loop over pos_data does (a FASTA
  * with fewer contigs leaves the last one in place, :161-163); `map_file` ("" or NULL for none) is applied
@@ -63,6 +122,18 @@ const char *secedo_variant_last_error(void);
 int secedo_variant_reference_genotypes(const char *fasta, const char *map_file, const uint32_t *chr_locus_off,
                                        uint32_t n_chr, const uint32_t *locus_pos, uint32_t n_loci,
                                        uint8_t *locus_ref, uint32_t *chr_locus_end, double *fasta_ms);
+
+/* The same results on the device route (see above), for a pileup resident in HBM: d_chr_locus_off[n_chr + 1] and
+ * d_locus_pos[n_loci] in HBM, chr_locus_off the host copy of the offsets (they must run from 0 to n_loci and not
+ * decrease); d_locus_ref[n_loci] is written in HBM, chr_locus_end[n_chr] on the host. A TEXT or GZIP file under the
+ * HOST setting, or any file with a map, is read on the host route and its locus_ref uploaded (d_locus_pos is then
+ * read back). times (may be NULL): fasta_ms = the whole call, gather_ms = 0; the split is in
+ * secedo_variant_fasta_stats. Synchronises `stream`. */
+int secedo_variant_reference_genotypes_device(int device_id, const char *fasta, const char *map_file,
+                                              const uint32_t *d_chr_locus_off, const uint32_t *chr_locus_off,
+                                              uint32_t n_chr, const uint32_t *d_locus_pos, uint32_t n_loci,
+                                              uint8_t *d_locus_ref, uint32_t *chr_locus_end,
+                                              secedo_variant_times *times, void *stream);
 
 /* Host only. check_is_diploid (:281-286): 1 when the first word of the file contains "maternal", 0 when not,
  * a negative SECEDO_E_* when the file cannot be opened. */
@@ -119,7 +190,9 @@ int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_
                            const char *out_dir, secedo_variant_times *times);
 
 /* Same on a flat pileup resident in HBM (the layout secedo_divide_cluster_device takes); clusters is host.
- * The chromosome offsets and positions are read back for the host gather. Synchronises `stream`. */
+ * The chromosome offsets and positions are read back: the positions for the VCF text and, on the host route, for the
+ * host gather. On the device route locus_ref is computed in HBM and only downloaded for the VCF text; fasta_ms is
+ * then the whole of secedo_variant_reference_genotypes_device and gather_ms 0. Synchronises `stream`. */
 int secedo_variant_calling_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
                                   const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
                                   const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci,

@@ -2,21 +2,18 @@
 // per-locus gather of the reference genotype, the constant tables, the launches of variant_kernels.hip and the
 // VCF / scores text of the reference's variant_calling() (variant_calling.cpp:81-461).
 //
-// The FASTA is memory-mapped and read through a small restatement of the std::ifstream calls the reference
-// makes (getline, peek, get, putback), so that its quirks carry over: a contig header directly after another
-// is read as sequence, a FASTA with fewer contigs than the pileup has chromosomes leaves the last contig in
-// place (:161-163), and a missing paternal contig reads as empty.
+// The FASTA is memory-mapped (a compressed one inflated, fasta_source.cpp) and read through a small restatement of
+// the std::ifstream calls the reference makes (getline, peek, get, putback), so that its quirks carry over: a contig
+// header directly after another is read as sequence, a FASTA with fewer contigs than the pileup has chromosomes
+// leaves the last contig in place (:161-163), and a missing paternal contig reads as empty. That is the host route;
+// the device route of the same results is fasta_device.cpp.
 #include "secedo_variant.h"
 #include "secedo_simmat.h"
+#include "fasta_source.hpp"
 #include "host_util.hpp"
 #include "variant_kernels.hpp"
 
 #include <hip/hip_runtime.h>
-
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cmath>
@@ -34,6 +31,7 @@ namespace {
 
 using secedo::variant::Logs;
 using namespace secedo::host;
+using namespace secedo::fasta_host;
 
 constexpr char kIntToChar[6] = {'A', 'C', 'G', 'T', 'N', 'N'};
 
@@ -56,32 +54,16 @@ std::string id_to_chromosome(uint32_t chr_id) {
 // ---------------------------------------------------------------------------------------------------------------
 // The reference genome
 
-// A read-only mapping of a file with the std::istream calls get_next_chromosome makes. `fail` is the stream's
-// failbit: once set, every call fails, as the reference's stream does.
+// A text it does not own (the mapped file, or what was inflated from it) with the std::istream calls
+// get_next_chromosome makes. `fail` is the stream's failbit: once set, every call fails, as the reference's stream
+// does.
 struct Fasta {
     const char *p = nullptr;
     size_t n = 0, pos = 0;
     bool fail = false;
-    int fd = -1;
+    uint64_t headers = 0;  // header lines read
 
-    ~Fasta() {
-        if (p && n) munmap(const_cast<char *>(p), n);
-        if (fd >= 0) close(fd);
-    }
-    bool open(const char *path) {
-        fd = ::open(path, O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        if (fstat(fd, &st) != 0) return false;
-        n = static_cast<size_t>(st.st_size);
-        if (n) {
-            void *m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) return false;
-            madvise(m, n, MADV_SEQUENTIAL);
-            p = static_cast<const char *>(m);
-        }
-        return true;
-    }
+    Fasta(const uint8_t *text, size_t bytes) : p(reinterpret_cast<const char *>(text)), n(bytes) {}
     bool getline(std::string_view *line) {
         if (fail || pos >= n) {
             fail = true;
@@ -248,6 +230,7 @@ int get_next_chromosome(Fasta &f, const Map &map, bool is_diploid, std::vector<u
                         std::vector<uint8_t> *tmp1, std::vector<uint8_t> *tmp2) {
     std::string_view header;
     if (!f.getline(&header)) return SECEDO_OK;  // fewer contigs: the previous one stays
+    ++f.headers;
     if (header.empty()) return fail(SECEDO_E_INVALID_ARG, "reference genome: empty line where a contig header is expected");
     const char chromosome = header.size() > 1 ? header[1] : '\0';
     std::string chr_name(header.substr(1));
@@ -265,7 +248,9 @@ int get_next_chromosome(Fasta &f, const Map &map, bool is_diploid, std::vector<u
         return SECEDO_OK;
     }
     std::string_view second;
-    if (f.getline(&second) && !second.empty()) chr_name.assign(second.substr(1));  // else the line is unchanged
+    const bool has_second = f.getline(&second);
+    f.headers += has_second;
+    if (has_second && !second.empty()) chr_name.assign(second.substr(1));  // else the line is unchanged
     tmp1->clear();
     read_contig(f, tmp1);
     it = map.find(chr_name);
@@ -279,19 +264,18 @@ int get_next_chromosome(Fasta &f, const Map &map, bool is_diploid, std::vector<u
     return SECEDO_OK;
 }
 
-int open_fasta(const char *path, Fasta *f) {
-    if (!path || !std::filesystem::exists(path))
-        return fail(SECEDO_E_INVALID_ARG, std::string("Reference genome ") + (path ? path : "(null)") + " does not exist");
-    if (!f->open(path)) return fail(SECEDO_E_INVALID_ARG, std::string("cannot read ") + path);
+// The file opened for a host function: both compressed kinds inflated with zlib.
+int open_text(const char *path, Source *src) {
+    SECEDO_CALL(open_source(path, src));
+    if (!src->has_text) SECEDO_CALL(inflate_bgzf_host(src));
     return SECEDO_OK;
 }
 
 // The host half of variant_calling before the locus loop: locus_ref and chr_locus_end (see the header).
-int reference_genotypes(const char *fasta, const char *map_file, const uint32_t *chr_locus_off, uint32_t n_chr,
+int reference_genotypes(const Source &src, const char *map_file, const uint32_t *chr_locus_off, uint32_t n_chr,
                         const uint32_t *locus_pos, uint8_t *locus_ref, uint32_t *chr_locus_end, double *fasta_ms) {
     Clock::time_point t0 = Clock::now();
-    Fasta f;
-    SECEDO_CALL(open_fasta(fasta, &f));
+    Fasta f(src.text(), src.text_bytes());
     std::vector<MapEntry> entries;
     SECEDO_CALL(read_map(map_file, &entries));
     const Map map = group_map(entries);
@@ -313,6 +297,10 @@ int reference_genotypes(const char *fasta, const char *map_file, const uint32_t 
         for (; l < e; ++l) locus_ref[l] = 0;
     }
     if (fasta_ms) *fasta_ms = parse + (n_chr == 0 ? ms_lap(t0) : 0.0);
+    secedo_variant_fasta_info &st = info();
+    st.route = SECEDO_FASTA_HOST;
+    st.text_bytes = f.pos;
+    st.contigs = st.contigs_used = f.headers;
     return SECEDO_OK;
 }
 
@@ -324,6 +312,74 @@ int set_device(int device_id) {
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(SECEDO_E_NO_DEVICE, "no HIP device");
     if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_INVALID_ARG, "device id out of range");
     SECEDO_TRY(hipSetDevice(device_id));
+    return SECEDO_OK;
+}
+
+// The reference genotypes of a pileup resident in HBM, by the route the file and the setting ask for.
+struct RefArgs {
+    const uint32_t *d_chr_locus_off, *chr_locus_off;  // device and host copies
+    uint32_t n_chr;
+    const uint32_t *d_locus_pos, *locus_pos;  // either may be null: the missing copy is made when the route needs it
+    uint32_t n_loci;
+    uint8_t *d_locus_ref;  // out, HBM
+    uint8_t *locus_ref;    // out, host; may be null
+    uint32_t *chr_locus_end;
+};
+
+// fasta_ms / gather_ms as secedo_variant_times has them: on the device route the whole is fasta_ms. On the host route
+// with a.locus_ref given, its upload is left in flight on s.
+int reference_any(const char *fasta, const char *map_file, const RefArgs &a, double *fasta_ms, double *gather_ms,
+                  hipStream_t s) {
+    Clock::time_point t0 = Clock::now();
+    Source src;
+    SECEDO_CALL(open_source(fasta, &src));
+    bool device = false;
+    SECEDO_CALL(fasta_route(&device));
+    device = device || src.kind == SECEDO_FASTA_KIND_BGZF;
+    if (device && map_file && *map_file) {  // the Varsim map is the host route's alone
+        device = false;
+        if (!src.has_text) SECEDO_CALL(download_bgzf_text(&src, s));
+        info().fell_back_for_map = 1;
+    }
+    if (!device) {
+        std::vector<uint32_t> pos;
+        std::vector<uint8_t> ref;
+        const uint32_t *locus_pos = a.locus_pos;
+        if (!locus_pos) {
+            pos.resize(a.n_loci);
+            if (a.n_loci) SECEDO_TRY(hipMemcpyAsync(pos.data(), a.d_locus_pos, (size_t)a.n_loci * 4, hipMemcpyDeviceToHost, s));
+            SECEDO_TRY(hipStreamSynchronize(s));
+            locus_pos = pos.data();
+        }
+        uint8_t *locus_ref = a.locus_ref;
+        if (!locus_ref) {
+            ref.resize(a.n_loci);
+            locus_ref = ref.data();
+        }
+        SECEDO_CALL(reference_genotypes(src, map_file, a.chr_locus_off, a.n_chr, locus_pos, locus_ref, a.chr_locus_end,
+                                        fasta_ms));
+        *gather_ms = ms_since(t0) - *fasta_ms;
+        if (a.n_loci) SECEDO_TRY(hipMemcpyAsync(a.d_locus_ref, locus_ref, a.n_loci, hipMemcpyHostToDevice, s));
+        if (!a.locus_ref) SECEDO_TRY(hipStreamSynchronize(s));
+        return SECEDO_OK;
+    }
+    Buf b_pos;
+    const uint32_t *d_locus_pos = a.d_locus_pos;
+    if (!d_locus_pos) {
+        SECEDO_TRY(b_pos.alloc((size_t)a.n_loci * 4));
+        if (a.n_loci) SECEDO_TRY(hipMemcpyAsync(b_pos.p, a.locus_pos, (size_t)a.n_loci * 4, hipMemcpyHostToDevice, s));
+        d_locus_pos = b_pos.as<uint32_t>();
+    }
+    bool diploid = false;
+    if (src.has_text) diploid = first_word_has_maternal(src.text(), src.text_bytes());
+    else SECEDO_CALL(bgzf_is_diploid(src, &diploid));
+    SECEDO_CALL(device_genotypes(src, diploid, a.d_chr_locus_off, a.chr_locus_off, a.n_chr, d_locus_pos, a.n_loci,
+                                 a.d_locus_ref, a.chr_locus_end, s));
+    if (a.locus_ref && a.n_loci)
+        SECEDO_TRY(hipMemcpyAsync(a.locus_ref, a.d_locus_ref, a.n_loci, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    *fasta_ms = ms_since(t0);
+    *gather_ms = 0;
     return SECEDO_OK;
 }
 
@@ -541,9 +597,11 @@ int write_outputs(const std::filesystem::path &out_dir, const std::string &refer
     return write_file(out_dir / "scores", scores);
 }
 
-// variant_calling on a resident pileup with the host copies of its chromosome offsets and positions.
+// variant_calling on a resident pileup with the host copies of its chromosome offsets and positions (the positions
+// also in HBM where the caller has them there: d_locus_pos, else null).
 int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_locus_off, uint32_t n_chr,
-            const uint32_t *locus_pos, const uint64_t *d_locus_entry_off, const uint16_t *d_id_base16,
+            const uint32_t *locus_pos, const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+            const uint16_t *d_id_base16,
             const uint32_t *d_id_base32, uint32_t n_loci, const uint16_t *clusters, uint32_t n,
             const char *reference_genome, const char *map_file, double hetero_prior, double theta,
             const char *out_dir, secedo_variant_times *times, hipStream_t s, double pre_device_ms) {
@@ -551,17 +609,17 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
     Clock::time_point t0 = Clock::now();
     std::vector<uint8_t> locus_ref(n_loci);
     std::vector<uint32_t> chr_end(n_chr);
-    SECEDO_CALL(reference_genotypes(reference_genome, map_file, chr_locus_off, n_chr, locus_pos, locus_ref.data(),
-                                chr_end.data(), &t.fasta_ms));
-    t.gather_ms = ms_lap(t0) - t.fasta_ms;
-    const uint32_t num_clusters = static_cast<uint32_t>(*std::max_element(clusters, clusters + n)) + 1;
-
     Buf b_ref, b_cl, b_mm, b_loci;
     SECEDO_TRY(b_ref.alloc(n_loci));
+    const RefArgs ref{d_chr_locus_off, chr_locus_off, n_chr, d_locus_pos, locus_pos, n_loci, b_ref.as<uint8_t>(),
+                      locus_ref.data(), chr_end.data()};
+    SECEDO_CALL(reference_any(reference_genome, map_file, ref, &t.fasta_ms, &t.gather_ms, s));
+    (void)ms_lap(t0);
+    const uint32_t num_clusters = static_cast<uint32_t>(*std::max_element(clusters, clusters + n)) + 1;
+
     SECEDO_TRY(b_cl.alloc((size_t)n * 2));
     SECEDO_TRY(b_mm.alloc((size_t)n * 4));
     SECEDO_TRY(b_loci.alloc((size_t)n * 4));
-    if (n_loci) SECEDO_TRY(hipMemcpyAsync(b_ref.p, locus_ref.data(), n_loci, hipMemcpyHostToDevice, s));
     SECEDO_TRY(hipMemcpyAsync(b_cl.p, clusters, (size_t)n * 2, hipMemcpyHostToDevice, s));
     Calls calls;
     SECEDO_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, b_cl.as<uint16_t>(),
@@ -607,19 +665,54 @@ int secedo_variant_reference_genotypes(const char *fasta, const char *map_file, 
         return fail(SECEDO_E_INVALID_ARG, "null argument");
     if (chr_locus_off[0] != 0 || chr_locus_off[n_chr] != n_loci)
         return fail(SECEDO_E_INVALID_ARG, "chr_locus_off must run from 0 to n_loci");
-    return reference_genotypes(fasta, map_file, chr_locus_off, n_chr, locus_pos, locus_ref, chr_locus_end, fasta_ms);
+    Source src;
+    SECEDO_CALL(open_text(fasta, &src));
+    return reference_genotypes(src, map_file, chr_locus_off, n_chr, locus_pos, locus_ref, chr_locus_end, fasta_ms);
+}
+
+int secedo_variant_set_fasta_route(int route) {
+    if (route != SECEDO_FASTA_HOST && route != SECEDO_FASTA_DEVICE)
+        return fail(SECEDO_E_INVALID_ARG, "route must be SECEDO_FASTA_HOST or SECEDO_FASTA_DEVICE");
+    set_route(route);
+    return SECEDO_OK;
+}
+
+int secedo_variant_get_fasta_route(void) { return get_route(); }
+
+int secedo_variant_fasta_stats(secedo_variant_fasta_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = info();
+    return SECEDO_OK;
+}
+
+int secedo_variant_reference_genotypes_device(int device_id, const char *fasta, const char *map_file,
+                                              const uint32_t *d_chr_locus_off, const uint32_t *chr_locus_off,
+                                              uint32_t n_chr, const uint32_t *d_locus_pos, uint32_t n_loci,
+                                              uint8_t *d_locus_ref, uint32_t *chr_locus_end,
+                                              secedo_variant_times *times, void *stream) {
+    if (!chr_locus_off || !d_chr_locus_off || (n_chr && !chr_locus_end) || (n_loci && (!d_locus_pos || !d_locus_ref)))
+        return fail(SECEDO_E_INVALID_ARG, "null argument");
+    if (chr_locus_off[0] != 0 || chr_locus_off[n_chr] != n_loci)
+        return fail(SECEDO_E_INVALID_ARG, "chr_locus_off must run from 0 to n_loci");
+    SECEDO_CALL(set_device(device_id));
+    secedo_variant_times t{};
+    const RefArgs ref{d_chr_locus_off, chr_locus_off, n_chr, d_locus_pos, nullptr, n_loci, d_locus_ref, nullptr, chr_locus_end};
+    SECEDO_CALL(reference_any(fasta, map_file, ref, &t.fasta_ms, &t.gather_ms, static_cast<hipStream_t>(stream)));
+    if (times) *times = t;
+    return SECEDO_OK;
 }
 
 int secedo_variant_is_diploid(const char *fasta) {
-    Fasta f;
-    SECEDO_CALL(open_fasta(fasta, &f));
-    return check_is_diploid(f) ? 1 : 0;
+    Source src;
+    SECEDO_CALL(open_text(fasta, &src));
+    return first_word_has_maternal(src.text(), src.text_bytes()) ? 1 : 0;
 }
 
 int secedo_variant_read_chromosome(const char *fasta, const char *map_file, uint32_t index, uint8_t *out,
                                    uint64_t capacity, uint64_t *length) {
-    Fasta f;
-    SECEDO_CALL(open_fasta(fasta, &f));
+    Source src;
+    SECEDO_CALL(open_text(fasta, &src));
+    Fasta f(src.text(), src.text_bytes());
     std::vector<MapEntry> entries;
     SECEDO_CALL(read_map(map_file, &entries));
     const Map map = group_map(entries);
@@ -739,7 +832,7 @@ int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_
         SECEDO_TRY(hipMemcpyAsync(b_idb.p, id_base16 ? (const void *)id_base16 : (const void *)id_base32, idb_bytes,
                               hipMemcpyHostToDevice, s));
     const double upload_ms = ms_lap(t0);
-    return calling(device_id, b_chr.as<uint32_t>(), chr_locus_off, n_chr, locus_pos, b_off.as<uint64_t>(),
+    return calling(device_id, b_chr.as<uint32_t>(), chr_locus_off, n_chr, locus_pos, nullptr, b_off.as<uint64_t>(),
                    id_base16 ? b_idb.as<uint16_t>() : nullptr, id_base16 ? nullptr : b_idb.as<uint32_t>(), n_loci,
                    clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times, s, upload_ms);
 }
@@ -766,7 +859,7 @@ int secedo_variant_calling_device(int device_id, const uint32_t *d_chr_locus_off
     if (chr_off[0] != 0 || chr_off[n_chr] != n_loci)
         return fail(SECEDO_E_INVALID_ARG, "chr_locus_off must run from 0 to n_loci");
     const double download_ms = ms_lap(t0);
-    return calling(device_id, d_chr_locus_off, chr_off.data(), n_chr, pos.data(), d_locus_entry_off, d_id_base16,
+    return calling(device_id, d_chr_locus_off, chr_off.data(), n_chr, pos.data(), d_locus_pos, d_locus_entry_off, d_id_base16,
                    d_id_base32, n_loci, clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times,
                    s, download_ms);
 }

@@ -6,7 +6,9 @@ on the resident pileup, writing the reference's per-level files into -o, and cal
 --reference_genome is given. Flags, defaults and validators are the reference's, in the gflags spellings
 (--f=v, --f v, -f v, --flag, --noflag, --flag=false). Flag and file-name checks run before torch is imported.
 Departures: two input files for one chromosome and a --clustering file whose length is not the cell count are
-errors (exit 1); --num_threads only sizes host pools (at most 16).
+errors (exit 1); --num_threads only sizes host pools (at most 16). --reference_genome may be plain FASTA, bgzip
+(BGZF) or plain gzip (.fa.gz works; the kind is told by content); --fasta_route host|device (default: the
+environment SECEDO_FASTA, else host) says where its parse and per-locus gather run, see secedo_amd/variant.py.
 """
 from __future__ import annotations
 
@@ -43,6 +45,7 @@ FLAGS: Dict[str, Tuple[str, object]] = {
     "arma_kmeans": ("bool", False),
     "reference_genome": ("str", ""),
     "map_file": ("str", ""),
+    "fasta_route": ("str", ""),
     "clustering": ("str", ""),
     "compute_read_stats": ("bool", False),
     "num_threads": ("uint", 8),
@@ -63,6 +66,8 @@ def usage() -> str:
     lines = [USAGE, "", "Flags:"]
     for name, (kind, default) in FLAGS.items():
         lines.append("  -%s (%s) default: %r" % (name, kind, default))
+    lines += ["", "--reference_genome takes plain FASTA, bgzip (BGZF) or plain gzip: genome.fa.gz works as it is.",
+              "--fasta_route host|device: where the FASTA is parsed (default: SECEDO_FASTA, else host; BGZF: device)."]
     return "\n".join(lines)
 
 
@@ -131,6 +136,8 @@ def validate(f: Flags) -> None:
     if f.normalization not in ("ADD_MIN", "EXPONENTIATE", "SCALE_MAX_1"):
         raise UsageError("Invalid value for --normalization: %s.\nShould be one of ADD_MIN, EXPONENTIATE, "
                          "SCALE_MAX_1" % f.normalization)
+    if f.fasta_route not in ("", "host", "device"):
+        raise UsageError("Invalid value for --fasta_route: %s.\nShould be one of host, device" % f.fasta_route)
     if not 1 <= f.tumor_purity <= 5:
         raise UsageError("Invalid value for --tumor_purity: %d.\nShould be 1,2,3,4, or 5" % f.tumor_purity)
     if f.arma_kmeans and f.clustering_type != "FIEDLER":
@@ -317,7 +324,7 @@ def run(plan: Plan) -> int:
     from . import SimilarityMatrixPlan
     from .cluster import divide_cluster_resident
     from .pileup_reader import get_grouping
-    from .variant import variant_calling_resident
+    from .variant import fasta_stats, variant_calling_resident
 
     f = plan.flags
     t0 = time.perf_counter()
@@ -363,7 +370,12 @@ def run(plan: Plan) -> int:
         if f.reference_genome:
             _log(f, "Performing variant calling against %s" % f.reference_genome)
             vc_times = variant_calling_resident(sm, res, clusters, f.reference_genome, f.map_file, 1e-3,
-                                                f.seq_error_rate, f.o)
+                                                f.seq_error_rate, f.o, fasta_route=f.fasta_route or None)
+            fs = fasta_stats()
+            vc_times["fasta"] = "%s on %s" % (fs["kind"], fs["route"])
+            if fs["route"] == "device":  # the device route's split; the three overlap
+                vc_times.update(fasta_inflate_ms=fs["inflate_ms"], fasta_upload_ms=fs["upload_ms"],
+                                fasta_parse_gather_ms=fs["parse_gather_ms"])
         else:
             _log(f, "Skipping variant calling, because no reference genome was provided")
         t_end = time.perf_counter()
@@ -373,7 +385,8 @@ def run(plan: Plan) -> int:
     _log(f, "times: load %.1f ms (%s), clustering %.1f ms, variant calling %.1f ms%s, total %.1f ms" % (
         1e3 * (t_load - t0), ", ".join("%s %.1f" % kv for kv in times.items()) or "host reader",
         1e3 * (t_cluster - t_load), 1e3 * (t_end - t_cluster),
-        "" if vc_times is None else " (%s)" % ", ".join("%s %.1f" % kv for kv in vc_times.items()),
+        "" if vc_times is None else " (%s)" % ", ".join(
+            ("%s %.1f" if isinstance(kv[1], float) else "%s %s") % kv for kv in vc_times.items()),
         1e3 * (t_end - t0)))
     _log(f, "Done.")
     return 0

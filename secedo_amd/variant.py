@@ -5,9 +5,15 @@ hetero_prior, theta, out_dir)`` (variant_calling.cpp:323-461): the per-locus gen
 counters run on the GPU (secedo_amd/csrc/variant_kernels.hip); the FASTA / map reading and the VCF text are
 host code in the library. ``reference_genotypes`` and the FASTA / map helpers need no GPU. No CPU fallback for
 the calls.
+
+The reference genome may be plain text, BGZF or plain gzip (told by content). Its parse and the per-locus gather
+run on the host by default; ``set_fasta_route("device")``, the environment ``SECEDO_FASTA=device`` or the
+``fasta_route`` keyword of the calling functions move them to the GPU (a BGZF file always goes there), where the
+text never lives on the host. ``fasta_stats()`` says what the last call did.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -38,6 +44,17 @@ class Times(C.Structure):
                 ("write_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class FastaInfo(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("route", C.c_uint32), ("fell_back_for_map", C.c_uint32),
+                ("reserved", C.c_uint32), ("host_inflated_bytes", C.c_uint64), ("device_members", C.c_uint64),
+                ("uploaded_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("ranges", C.c_uint64),
+                ("contigs", C.c_uint64), ("contigs_used", C.c_uint64), ("inflate_ms", C.c_double),
+                ("upload_ms", C.c_double), ("parse_gather_ms", C.c_double)]
+
+
+FASTA_ROUTES = ("host", "device")
+FASTA_KINDS = ("text", "bgzf", "gzip")
+
 RECORD_DTYPE = np.dtype([("locus", np.uint32), ("cluster", np.uint16), ("genotype", np.uint8), ("kind", np.uint8),
                          ("counts", np.uint16, (4,))])
 
@@ -45,6 +62,11 @@ SIGNATURES = {
     "secedo_variant_last_error": (C.c_char_p, []),
     "secedo_variant_reference_genotypes": (C.c_int, [C.c_char_p, C.c_char_p, _vp, C.c_uint32, _vp, C.c_uint32, _vp,
                                                      _vp, _f64p]),
+    "secedo_variant_set_fasta_route": (C.c_int, [C.c_int]),
+    "secedo_variant_get_fasta_route": (C.c_int, []),
+    "secedo_variant_fasta_stats": (C.c_int, [C.POINTER(FastaInfo)]),
+    "secedo_variant_reference_genotypes_device": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, _vp, _vp, C.c_uint32, _vp,
+                                                            C.c_uint32, _vp, _vp, C.POINTER(Times), _vp]),
     "secedo_variant_is_diploid": (C.c_int, [C.c_char_p]),
     "secedo_variant_read_chromosome": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "secedo_variant_read_map": (C.c_int, [C.c_char_p, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _u32p]),
@@ -101,13 +123,63 @@ def _flat(pos_data):
     return p, None, np.ascontiguousarray(idb, dtype=np.uint32)
 
 
-def reference_genotypes(reference_genome, chr_locus_off, locus_pos, map_file=""):
+def set_fasta_route(route):
+    """The process-wide route of the FASTA parse and gather: "host" or "device" (see the module docstring)."""
+    if route not in FASTA_ROUTES:
+        raise ValueError("fasta route must be 'host' or 'device', not %r" % (route,))
+    check(lib().secedo_variant_set_fasta_route(FASTA_ROUTES.index(route)))
+
+
+def get_fasta_route() -> str:
+    rc = lib().secedo_variant_get_fasta_route()
+    if rc < 0:
+        check(rc)
+    return FASTA_ROUTES[rc]
+
+
+@contextlib.contextmanager
+def _route(route):
+    """A scoped override of the FASTA route; None leaves the setting alone. Afterwards the route that held before is
+    set explicitly, so the environment is no longer consulted in this process."""
+    if route is None:
+        yield
+        return
+    before = get_fasta_route()
+    set_fasta_route(route)
+    try:
+        yield
+    finally:
+        set_fasta_route(before)
+
+
+def fasta_stats() -> dict:
+    """What the last FASTA-reading call of this thread did (secedo_variant_fasta_info), kind and route as words."""
+    info = FastaInfo()
+    check(lib().secedo_variant_fasta_stats(C.byref(info)))
+    out = {name: getattr(info, name) for name, _ in FastaInfo._fields_ if name != "reserved"}
+    out["kind"], out["route"] = FASTA_KINDS[info.kind], FASTA_ROUTES[info.route]
+    return out
+
+
+def reference_genotypes(reference_genome, chr_locus_off, locus_pos, map_file="", device=None):
     """The reference genotype of every locus (maternal << 3 | paternal, N = 5) and each chromosome's end (the
-    first locus with position - 1 >= its contig's length). No GPU. -> (locus_ref u8[L], chr_locus_end u32[C])."""
+    first locus with position - 1 >= its contig's length) -> (locus_ref u8[L], chr_locus_end u32[C]), host arrays.
+    device=None: the host function, no GPU. device=<id>: secedo_variant_reference_genotypes_device on copies of the
+    offsets and positions in that GPU's memory, by the route the file and the setting ask for."""
     off = np.ascontiguousarray(chr_locus_off, dtype=np.uint32)
     pos = np.ascontiguousarray(locus_pos, dtype=np.uint32)
     ref = np.zeros(max(len(pos), 1), dtype=np.uint8)
     end = np.zeros(max(len(off) - 1, 1), dtype=np.uint32)
+    if device is not None:
+        import torch
+        dev = "cuda:%d" % device
+        d_off, d_pos = _dev(off, np.int32, dev), _dev(pos, np.int32, dev)
+        d_ref = torch.zeros(max(len(pos), 1), dtype=torch.uint8, device=dev)
+        check(lib().secedo_variant_reference_genotypes_device(
+            device, _b(reference_genome), _b(map_file), C.c_void_p(d_off.data_ptr()), _lib.ptr(off), len(off) - 1,
+            C.c_void_p(d_pos.data_ptr()), len(pos), C.c_void_p(d_ref.data_ptr()), _lib.ptr(end), None,
+            _stream(device)))
+        return d_ref.cpu().numpy()[:len(pos)].copy(), end[:len(off) - 1]
     check(lib().secedo_variant_reference_genotypes(_b(reference_genome), _b(map_file), _lib.ptr(off), len(off) - 1,
                                                    _lib.ptr(pos), len(pos), _lib.ptr(ref), _lib.ptr(end), None))
     return ref[:len(pos)], end[:len(off) - 1]
@@ -190,14 +262,17 @@ def _stream(device):
 
 
 def variant_calls(pos_data, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01, capacity=None,
-                  device=0, with_kernel_ms=False):
+                  device=0, with_kernel_ms=False, fasta_route=None):
     """The device calls alone -> (records as a RECORD_DTYPE array in write order, mismatch u32[n], loci u32[n]).
     `capacity` (default: enough) bounds the records; SecedoError(E_LIMIT) when more are needed, its
-    `required` attribute the count."""
+    `required` attribute the count. fasta_route: None reads the reference genome with the host function, "host" or
+    "device" through secedo_variant_reference_genotypes_device under that route."""
     import torch
     p, b16, b32 = _flat(pos_data)
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
-    ref, end = reference_genotypes(reference_genome, p.chr_locus_off, p.locus_pos, map_file)
+    with _route(fasta_route):
+        ref, end = reference_genotypes(reference_genome, p.chr_locus_off, p.locus_pos, map_file,
+                                       None if fasta_route is None else device)
     dev = "cuda:%d" % device
     d_chr = _dev(p.chr_locus_off, np.int32, dev)
     d_pos = _dev(p.locus_pos, np.int32, dev)
@@ -236,29 +311,32 @@ def _times(t):
 
 
 def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                    out_dir="variant_calling", device=0):
+                    out_dir="variant_calling", device=0, fasta_route=None):
     """variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir): writes
-    cluster_<i>.vcf, common.vcf, variant and scores under out_dir as the reference does. -> step times (ms)."""
+    cluster_<i>.vcf, common.vcf, variant and scores under out_dir as the reference does. fasta_route ("host",
+    "device"; None: the setting) overrides the FASTA route for this call. -> step times (ms)."""
     p, b16, b32 = _flat(pos_data)
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     t = Times()
-    check(lib().secedo_variant_calling(device, _lib.ptr(p.chr_locus_off), p.n_chr, _lib.ptr(p.locus_pos),
-                                       _lib.ptr(p.locus_entry_off), _lib.ptr(b16), _lib.ptr(b32), _lib.ptr(cl),
-                                       len(cl), _b(reference_genome), _b(map_file), hetero_prior, theta, _b(out_dir),
-                                       C.byref(t)))
+    with _route(fasta_route):
+        check(lib().secedo_variant_calling(device, _lib.ptr(p.chr_locus_off), p.n_chr, _lib.ptr(p.locus_pos),
+                                           _lib.ptr(p.locus_entry_off), _lib.ptr(b16), _lib.ptr(b32), _lib.ptr(cl),
+                                           len(cl), _b(reference_genome), _b(map_file), hetero_prior, theta,
+                                           _b(out_dir), C.byref(t)))
     return _times(t)
 
 
 def variant_calling_resident(plan, res, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                             out_dir="variant_calling"):
+                             out_dir="variant_calling", fasta_route=None):
     """variant_calling on the pileup `res` resident in HBM (SimilarityMatrixPlan.upload, as divide_cluster_resident
-    takes it), in the plan's current stream. -> step times (ms)."""
+    takes it), in the plan's current stream. fasta_route as in variant_calling. -> step times (ms)."""
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     idb = C.c_void_p(res["idb"].data_ptr())
     t = Times()
-    check(lib().secedo_variant_calling_device(
-        plan.device, C.c_void_p(res["chr"].data_ptr()), res["n_chr"], C.c_void_p(res["pos"].data_ptr()),
-        C.c_void_p(res["off"].data_ptr()), idb if res["idb_is16"] else None, None if res["idb_is16"] else idb,
-        res["n_loci"], res["n_entries"], _lib.ptr(cl), len(cl), _b(reference_genome), _b(map_file), hetero_prior,
-        theta, _b(out_dir), C.byref(t), plan._stream()))
+    with _route(fasta_route):
+        check(lib().secedo_variant_calling_device(
+            plan.device, C.c_void_p(res["chr"].data_ptr()), res["n_chr"], C.c_void_p(res["pos"].data_ptr()),
+            C.c_void_p(res["off"].data_ptr()), idb if res["idb_is16"] else None, None if res["idb_is16"] else idb,
+            res["n_loci"], res["n_entries"], _lib.ptr(cl), len(cl), _b(reference_genome), _b(map_file), hetero_prior,
+            theta, _b(out_dir), C.byref(t), plan._stream()))
     return _times(t)

@@ -8,18 +8,30 @@ workload:
     whole   a whole-pileup-sized synthetic: 24 chromosomes, 10 M loci, coverage 30 (300 M entries), one locus
             every 100 bp (a 1 Gbp diploid FASTA, 60 bases per line), the same clone-tree clusters, 2 % of the
             loci with a planted clone-specific variant
+    fasta   the genome and the loci of `whole` without its entries: the reference genotypes alone
+            (secedo_variant_reference_genotypes on the host route, ..._device on the device route), with the
+            device route's inflate / upload / parse+gather split and GB/s of FASTA text
+
+--fasta_route host|device picks the route of the FASTA parse and gather (default: the library's setting),
+--compress none|gzip|bgzf how the synthetic genome is written, --lib PATH another build of libsecedo_variant.so
+(an A/B against the parent commit; one without the device entry point runs `fasta` on the host function).
 
 Each line: the two kernels (device events), the end-to-end call split into FASTA parse / gather / device (uploads,
 kernels, downloads) / write, and the achieved bytes/s of the kernels against the HBM peak (8 TB/s spec, 6.3
 TB/s measured with a float4 copy). The bytes counted are the compulsory ones: id_base, the entry offsets, one cluster
 id and one counter update per entry, the reference genotype and flag per locus. Every workload runs once
 untimed first. Run every step under a time limit (timeout -k 10 ...)."""
+import argparse
+import gzip
 import json
 import os
 import shutil
+import struct
 import sys
 import tempfile
 import time
+import zlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -58,6 +70,33 @@ def write_fasta(path, lengths, seed):
                 f.write(body.tobytes())
 
 
+def _bgzf_member(piece):
+    c = zlib.compressobj(1, zlib.DEFLATED, -15)
+    payload = c.compress(piece) + c.flush()
+    return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(payload) + 25) + payload +
+            struct.pack("<II", zlib.crc32(piece), len(piece)))
+
+
+def compress_file(path, how):
+    """The file rewritten in place as plain gzip or as BGZF (64 KiB - 256 members, level 1, 16 threads)."""
+    if how == "none":
+        return
+    with open(path, "rb") as f:
+        data = f.read()
+    with open(path, "wb") as f:
+        if how == "gzip":
+            f.write(gzip.compress(data, 1, mtime=0))
+            return
+        view = memoryview(data)
+        with ThreadPoolExecutor(16) as pool:  # zlib releases the interpreter lock
+            for m in pool.map(_bgzf_member, (view[o:o + 0xFF00] for o in range(0, len(data), 0xFF00))):
+                f.write(m)
+        f.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+
+
+OPTIONS = dict(fasta_route=None, compress="none")
+
+
 def compulsory_bytes(p, n_groups, idb_bytes):
     e, l = p.n_entries, p.n_loci
     return e * (idb_bytes + 2 + 4) + (l + 1) * 8 + 2 * l + 2 * n_groups * 4
@@ -66,12 +105,17 @@ def compulsory_bytes(p, n_groups, idb_bytes):
 def run(name, p, clusters, fasta, reps=3):
     out = tempfile.mkdtemp(prefix="vc_bench_")
     try:
-        variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out)  # warm-up
+        route = OPTIONS["fasta_route"]
+        variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out, fasta_route=route)  # warm-up
         runs = []
         for _ in range(reps):
             t0 = time.perf_counter()
-            t = variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out)
+            t = variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out, fasta_route=route)
             t["total_ms"] = (time.perf_counter() - t0) * 1e3
+            fs = (variant.fasta_stats() if hasattr(variant.lib(), "secedo_variant_fasta_stats") else
+                  dict(route="host", kind="text", text_bytes=0, inflate_ms=0.0, upload_ms=0.0, parse_gather_ms=0.0))
+            t.update(fasta_inflate_ms=fs["inflate_ms"], fasta_upload_ms=fs["upload_ms"],
+                     fasta_parse_gather_ms=fs["parse_gather_ms"])
             runs.append(t)
         med = {k: round(float(np.median([r[k] for r in runs])), 3) for k in runs[0]}
         n_lines = sum(1 for f in os.listdir(out) if f.endswith(".vcf")
@@ -89,7 +133,9 @@ def run(name, p, clusters, fasta, reps=3):
     idb_bytes = 2 if p.n_entries == 0 or int(p.id_base.max()) <= 0xFFFF else 4
     by = compulsory_bytes(p, len(clusters), idb_bytes)
     print(json.dumps(dict(workload=name, cells=len(clusters), loci=p.n_loci, entries=p.n_entries,
-                          chromosomes=p.n_chr, fasta_bytes=os.path.getsize(fasta), records=len(recs),
+                          chromosomes=p.n_chr, fasta_bytes=os.path.getsize(fasta), compress=OPTIONS["compress"],
+                          fasta_route=fs["route"], fasta_kind=fs["kind"], fasta_text_bytes=fs["text_bytes"],
+                          records=len(recs),
                           vcf_lines=n_lines, **med, kernel_ms_calls=round(kms, 3),
                           kernel_ms_lds_counters=modes["lds"], kernel_ms_global_counters=modes["global"], compulsory_bytes=by,
                           achieved_bytes_per_s=by / (med["kernel_ms"] * 1e-3),
@@ -113,15 +159,53 @@ def c3(tmp):
     run("C3", p, clone_clusters(max(n_cells, 8000)), fasta)
 
 
+def whole_genome(tmp, n_loci, n_chr, spacing):
+    """The genome of `whole`, written as --compress says -> (path, text bytes, chr_locus_off, locus_pos)."""
+    per = n_loci // n_chr
+    chr_off = (np.arange(n_chr + 1) * per).astype(np.uint32)
+    pos = np.tile(1 + spacing * np.arange(per, dtype=np.uint32), n_chr)
+    fasta = os.path.join(tmp, "whole.fa")
+    write_fasta(fasta, [spacing * per + 10] * n_chr, 5)
+    text_bytes = os.path.getsize(fasta)
+    compress_file(fasta, OPTIONS["compress"])
+    return fasta, text_bytes, chr_off, pos
+
+
+def fasta_only(tmp, n_loci=10_000_000, n_chr=24, spacing=100, reps=5):
+    """The reference genotypes of `whole`'s loci alone: medians of `reps` calls after one untimed call."""
+    fasta, text_bytes, chr_off, pos = whole_genome(tmp, n_loci, n_chr, spacing)
+    route = OPTIONS["fasta_route"]
+    on_device = hasattr(variant.lib(), "secedo_variant_reference_genotypes_device") and route is not None
+
+    def call():
+        t0 = time.perf_counter()
+        if on_device:
+            with variant._route(route):
+                ref, end = variant.reference_genotypes(fasta, chr_off, pos, device=0)
+        else:
+            ref, end = variant.reference_genotypes(fasta, chr_off, pos)
+        ms = (time.perf_counter() - t0) * 1e3
+        fs = variant.fasta_stats() if hasattr(variant.lib(), "secedo_variant_fasta_stats") else {}
+        return ms, fs, int(ref.astype(np.uint64).sum()), int(end.astype(np.uint64).sum())
+    call()
+    runs = [call() for _ in range(reps)]
+    ms = float(np.median([r[0] for r in runs]))
+    fs = runs[-1][1]
+    split = {k: round(float(np.median([r[1][k] for r in runs])), 3)
+             for k in ("inflate_ms", "upload_ms", "parse_gather_ms") if k in fs}
+    print(json.dumps(dict(workload="fasta", loci=len(pos), chromosomes=n_chr, text_bytes=text_bytes,
+                          file_bytes=os.path.getsize(fasta), compress=OPTIONS["compress"],
+                          entry="device" if on_device else "host function", route=fs.get("route", "host"),
+                          kind=fs.get("kind", "text"), ranges=fs.get("ranges", 0), call_ms=round(ms, 3),
+                          all_call_ms=[round(r[0], 1) for r in runs], text_gb_per_s=round(text_bytes / ms / 1e6, 3),
+                          **split, checksum=[runs[0][2], runs[0][3]])), flush=True)
+
+
 def whole(tmp, n_loci=10_000_000, n_chr=24, cov=30, n_cells=8000, spacing=100):
     rng = np.random.default_rng(7)
     per = n_loci // n_chr
     n_loci = per * n_chr
-    chr_off = (np.arange(n_chr + 1) * per).astype(np.uint32)
-    pos = np.tile(1 + spacing * np.arange(per, dtype=np.uint32), n_chr)
-    lengths = [spacing * per + 10] * n_chr
-    fasta = os.path.join(tmp, "whole.fa")
-    write_fasta(fasta, lengths, 5)
+    fasta, _, chr_off, pos = whole_genome(tmp, n_loci, n_chr, spacing)
     cl = clone_clusters(n_cells)
     counts = rng.poisson(cov, n_loci).astype(np.uint64)
     off = np.zeros(n_loci + 1, dtype=np.uint64)
@@ -149,9 +233,23 @@ def main(which):
             c3(tmp)
         if "whole" in which:
             whole(tmp)
+        if "fasta" in which:
+            fasta_only(tmp)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or ["C3", "whole"])
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("workloads", nargs="*", default=["C3", "whole"], help="C3, whole, fasta")
+    ap.add_argument("--fasta_route", choices=["host", "device"], default=None)
+    ap.add_argument("--compress", choices=["none", "gzip", "bgzf"], default="none")
+    ap.add_argument("--lib", default=None, help="another libsecedo_variant.so to load (A/B against a parent build)")
+    args = ap.parse_args()
+    OPTIONS.update(fasta_route=args.fasta_route, compress=args.compress)
+    if args.lib:
+        variant.LIB_PATH = os.path.abspath(args.lib)
+        if not hasattr(__import__("ctypes").CDLL(variant.LIB_PATH), "secedo_variant_fasta_stats"):
+            for name in [n for n in variant.SIGNATURES if "fasta" in n or n.endswith("genotypes_device")]:
+                del variant.SIGNATURES[name]  # a build from before the device route
+    main(args.workloads)
