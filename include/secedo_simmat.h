@@ -151,6 +151,28 @@ int secedo_simmat_used_device_packing(const secedo_simmat_t *handle);
  * 0 where that path is not tried (sparse id space, radix grouping) or was given up because more than half of the
  * entries belong to repeated ids. The packed pileup is the same either way; tests use this to know what they ran. */
 int secedo_simmat_used_single_entry_path(const secedo_simmat_t *handle);
+/* What the device packing of the last prepare() decided, as a bit field (0 before any prepare() and in host mode,
+ * where the device packing is not asked):
+ *   bits 0-1  SECEDO_ROUTE_ATTEMPTS       attempts at the device pipeline that were started, 0 to 3. One is the rule.
+ *                                         A second follows an attempt that voided itself: a read id, or a (cell
+ *                                         block, locus) group, with more than 8192 entries (repeated with the radix
+ *                                         sorts), or a read-id space larger than the handle's previous pileup had
+ *                                         (repeated without assuming that size). 0 with SECEDO_ROUTE_ASKED_HOST: a
+ *                                         size limit was seen before any attempt (the empty pileup, >= 2^31 entries,
+ *                                         4 * num_threads >= 2^32).
+ *   bit 2     SECEDO_ROUTE_RADIX          the last attempt grouped with the radix sorts throughout: it followed an
+ *                                         attempt that asked for them, or SECEDO_PACK_GROUPING=radix is set. (A
+ *                                         sparse id space alone sorts the entries by read id with the radix sort and
+ *                                         still groups the kept entries by counting: not reported here.)
+ *   bit 3     SECEDO_ROUTE_RETRIED_PLAIN  an attempt was repeated without the previous call's sizes
+ *   bit 4     SECEDO_ROUTE_ASKED_HOST     the device packing asked for the host packing (prepare() then packed on the
+ *                                         host, or failed with SECEDO_E_LIMIT in device mode)
+ * It is a report for tests and diagnostics: the packed pileup does not depend on the route. */
+#define SECEDO_ROUTE_ATTEMPTS 3
+#define SECEDO_ROUTE_RADIX 4
+#define SECEDO_ROUTE_RETRIED_PLAIN 8
+#define SECEDO_ROUTE_ASKED_HOST 16
+int secedo_simmat_packing_route(const secedo_simmat_t *handle);
 
 /* Read assembly, flush schedule, tile packing (see above). Work is enqueued on `stream` with a few
  * stream synchronisations for scalar read-backs; host packing is synchronous.

@@ -74,6 +74,7 @@ SIGNATURES = {
     "secedo_simmat_set_packing": (C.c_int, [_vp, C.c_int]),
     "secedo_simmat_used_device_packing": (C.c_int, [_vp]),
     "secedo_simmat_used_single_entry_path": (C.c_int, [_vp]),
+    "secedo_simmat_packing_route": (C.c_int, [_vp]),
     "secedo_simmat_prepare": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "secedo_simmat_num_tiles": (C.c_uint32, [_vp]),
     "secedo_simmat_block_cells": (C.c_uint32, [_vp]),

@@ -1999,12 +1999,16 @@ struct Attempt {
 
 // What a read-back of the scalars says. Before the records are written: the input's order, a void attempt (the id
 // space was assumed too small), a group too long for the counting scheme, a size this path does not cover. Behind
-// them: the errors of the group mapping (k_keys2, k_bin_hist) and a (block, locus) group too long (k_entry_records).
+// them: the errors of the group mapping (k_keys2, k_bin_hist), a (block, locus) group too long (k_entry_records) --
+// and the size limit once more: k_completed raises need_host on the side stream, beside read-back 2, which may or
+// may not see it. The read-back behind the records does: `stream` has waited for the side stream's ev_join by then
+// (PackAttempt::run, in front of the records), and every ev_join is recorded behind the build's k_completed.
 Attempt scalar_verdict(const Scalars &h, bool records_written) {
     if (records_written) {
         if (h.error == 1) return Attempt::error("group id outside group_id_to_pos");
         if (h.error == 2) return Attempt::error("group_id_to_pos maps outside the matrix");
-        return h.regroup ? Attempt::stop(Attempt::RetryRadix) : Attempt();
+        if (h.regroup) return Attempt::stop(Attempt::RetryRadix);
+        return h.need_host ? Attempt::stop(Attempt::NeedHost) : Attempt();
     }
     if (h.error == 3) return Attempt::error("positions must be strictly increasing within a chromosome");
     if (h.id_exceeded) return Attempt::stop(Attempt::RetryPlain);
@@ -2582,7 +2586,11 @@ struct PackAttempt {
                                    m.locus_rel, pk.entry32.as<uint32_t>());
             HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));  // the number of ranges
         }
-        STEP(scalar_verdict(hsc, true));
+        const Attempt verdict = scalar_verdict(hsc, true);
+        // (the host packing's uploads do not go through `stream`, and the list chain behind the read-back still
+        // reads the records and offsets they replace: a hand-over this late waits for it)
+        if (verdict.kind == Attempt::NeedHost) HIP_OK(hipStreamSynchronize(stream));
+        STEP(verdict);
         pk.pair_bound = hsc.pair_bound;
         pk.cell_sq = s.per_cell_sq;
         pk.cell_sq_n = s.n_kept ? p.nb * p.B : 0u;
@@ -2705,6 +2713,7 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
     *need_host = false;
     out->flag_lists_built = false;
     out->used_single_entry = false;
+    out->route = DevicePacked::Route();
     if ((in.id_base16 != nullptr) == (in.id_base32 != nullptr))
         return "exactly one of id_base16 / id_base32 must be given";
     if (num_threads == 0) return "num_threads must be positive";
@@ -2715,7 +2724,7 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
     const size_t n_off_max = (size_t)((num_cells + 63) / 64) * ((size_t)L + 1);
     if (E64 >= (1ull << 31) || L == 0 || L >= (1u << 30) || E64 == 0 || (uint64_t)4 * num_threads > 0xFFFFFFFFull
         || n_off_max >= (1ull << 31)) {
-        *need_host = true;  // sizes this path does not cover (incl. the empty pileup)
+        *need_host = out->route.asked_host = true;  // sizes this path does not cover (incl. the empty pileup)
         return std::string();
     }
     bool force_radix = false;
@@ -2738,20 +2747,22 @@ std::string pack_pileup_device(const DeviceFlatPileup &in, uint32_t num_cells, u
             for (DeviceArena &a : out->scratch)
                 if (a.p && hipMemset(a.p, 0xA5, a.bytes) != hipSuccess) return "poison: memset failed";
         }
+        ++out->route.attempts;
+        out->route.radix = force_radix;
         Attempt result = PackAttempt(in, num_cells, mfl, num_threads, block_cells, geometry, allow_count_tile, force_radix,
                                      no_assumptions, overlap, stream, *out).run();
         switch (result.kind) {
             case Attempt::Error: return std::move(result.text);
-            case Attempt::NeedHost: *need_host = true; return std::string();
+            case Attempt::NeedHost: *need_host = out->route.asked_host = true; return std::string();
             case Attempt::RetryRadix: force_radix = true; break;
             case Attempt::RetryPlain:  // the sizes of the previous call did not hold: ask the device
-                no_assumptions = true;
+                no_assumptions = out->route.retried_plain = true;
                 out->id_space_hint = 0;
                 break;
             default: return std::string();
         }
     }
-    *need_host = true;  // cannot happen: three attempts cover both requests
+    *need_host = out->route.asked_host = true;  // cannot happen: three attempts cover both requests
     return std::string();
 }
 

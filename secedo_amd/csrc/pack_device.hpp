@@ -82,6 +82,14 @@ struct DevicePacked {
     uint32_t calls_without_split = 0;
     // ... and whether the packing that has just returned took it to the end (secedo_simmat_used_single_entry_path)
     bool used_single_entry = false;
+    // What the packing that has just returned decided (secedo_simmat_packing_route): the attempts it ran, whether
+    // the last of them was made with the radix sorts (SECEDO_PACK_GROUPING=radix, or behind a RetryRadix), whether
+    // one was repeated without the previous call's sizes (RetryPlain), and whether it asked for the host -- by a
+    // size limit before any attempt, or by an attempt's verdict. pack_pileup_device alone writes it.
+    struct Route {
+        uint32_t attempts = 0;
+        bool radix = false, retried_plain = false, asked_host = false;
+    } route;
     // side stream for the branch of the pipeline nothing else waits for until the final gather
     // (completed counts + flush chain); created on first use
     hipStream_t side = nullptr;

@@ -73,7 +73,8 @@ std::string pack_pileup(const FlatPileupView &in, uint32_t num_cells, uint32_t m
     segs.reserve(E / 2 + 16);
     IdMap map;
     uint32_t completed = 0;  // NOT reset per chromosome (similarity_matrix.cpp:344)
-    const uint64_t flush_at = 4ull * num_threads;  // :354-356
+    // :354-356, uint32 arithmetic as in the reference: from 2^30 threads on the product wraps (2^30: every locus flushes)
+    const uint32_t flush_at = 4u * num_threads;
     for (uint32_t c = 0; c < in.n_chr; ++c) {
         const uint32_t l0 = in.chr_locus_off[c], l1 = in.chr_locus_off[c + 1];
         if (l1 < l0 || l1 > L) return "chr_locus_off is not monotone";

@@ -396,6 +396,12 @@ int secedo_simmat_used_device_packing(const secedo_simmat_t *h) { return h ? h->
 int secedo_simmat_used_single_entry_path(const secedo_simmat_t *h) {
     return h && h->used_device_packing && h->pk.used_single_entry ? 1 : 0;
 }
+int secedo_simmat_packing_route(const secedo_simmat_t *h) {
+    if (!h) return 0;
+    const secedo::DevicePacked::Route &r = h->pk.route;
+    return (int)(r.attempts & SECEDO_ROUTE_ATTEMPTS) | (r.radix ? SECEDO_ROUTE_RADIX : 0) |
+           (r.retried_plain ? SECEDO_ROUTE_RETRIED_PLAIN : 0) | (r.asked_host ? SECEDO_ROUTE_ASKED_HOST : 0);
+}
 
 int secedo_simmat_prepare(secedo_simmat_t *h, uint32_t num_cells, uint32_t max_fragment_length,
                           uint32_t num_threads, uint32_t block_cells, void *stream) {
@@ -413,6 +419,7 @@ int secedo_simmat_prepare(secedo_simmat_t *h, uint32_t num_cells, uint32_t max_f
     hipStream_t s = static_cast<hipStream_t>(stream);
     h->prepared = false;
     h->used_device_packing = 0;
+    h->pk.route = secedo::DevicePacked::Route();  // (host mode: the device packing is not asked at all)
     h->num_threads = num_threads;
 
     bool need_host = (p.mode == 1);

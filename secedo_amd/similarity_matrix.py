@@ -9,7 +9,7 @@ libsecedo_simmat.so on the GPU; this module only moves arrays and pointers.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
@@ -109,6 +109,14 @@ def llr_closed_form(x_s: int, x_d: int, mutation_rate: float, homozygous_rate: f
                                                           seq_error_rate))
 
 
+class PackingRoute(NamedTuple):
+    """SimilarityMatrixPlan.packing_route: the fields of secedo_simmat_packing_route (secedo_simmat.h)."""
+    attempts: int          # attempts at the device pipeline, 0 to 3
+    radix: bool            # the last attempt grouped with the radix sorts throughout
+    retried_plain: bool    # an attempt was repeated without the previous call's sizes
+    asked_host: bool       # the device packing asked for the host packing
+
+
 class SimilarityMatrixPlan:
     """Staged interface: device-resident packed pileup, explicit stream, tile ranges.
 
@@ -156,6 +164,12 @@ class SimilarityMatrixPlan:
     def used_single_entry_path(self) -> bool:
         """The last prepare packed on the GPU and its single-entry path ran to the end (secedo_simmat.h)."""
         return bool(_lib.lib().secedo_simmat_used_single_entry_path(self._h))
+
+    @property
+    def packing_route(self) -> "PackingRoute":
+        """What the device packing of the last prepare decided (secedo_simmat_packing_route, secedo_simmat.h)."""
+        bits = int(_lib.lib().secedo_simmat_packing_route(self._h))
+        return PackingRoute(bits & 3, bool(bits & 4), bool(bits & 8), bool(bits & 16))
 
     def upload(self, pos_data, group_id_to_pos=None, num_cells=None):
         """Raw flat pileup -> HBM (torch tensors); returns the resident pileup for prepare_resident."""

@@ -47,6 +47,18 @@ def test_version_and_device_count():
     assert L.secedo_simmat_device_count() >= 0
 
 
+def test_packing_route_bits_and_python_fields():
+    """secedo_simmat_packing_route: the header's bit masks are those SimilarityMatrixPlan.packing_route takes apart, and
+    a null handle reports nothing (like the accessors beside it)."""
+    header = open(os.path.join(ROOT, "include", "secedo_simmat.h")).read()
+    masks = {name: int(value) for name, value in re.findall(r"#define SECEDO_ROUTE_([A-Z_]+) (\d+)", header)}
+    assert masks == {"ATTEMPTS": 3, "RADIX": 4, "RETRIED_PLAIN": 8, "ASKED_HOST": 16}
+    assert secedo_amd.PackingRoute._fields == ("attempts", "radix", "retried_plain", "asked_host")
+    L = _lib.lib()
+    assert L.secedo_simmat_packing_route(None) == 0
+    assert L.secedo_simmat_used_device_packing(None) == 0 and L.secedo_simmat_used_single_entry_path(None) == 0
+
+
 def test_normalization_strings():
     # reference: to_enum, similarity_matrix.cpp:256-266
     assert secedo_amd.to_enum("ADD_MIN") == 0

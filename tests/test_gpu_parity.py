@@ -293,6 +293,9 @@ def test_edge_inputs():
     assert got.shape == (1, 1) and got[0, 0] == 0
     with pytest.raises(secedo_amd.InvalidNormalization):
         secedo_amd.compute_similarity_matrix(empty, 5, 1000, None, 0.01, 0.5, 0.01, 1, "", "bogus")
+    with secedo_amd.SimilarityMatrixPlan(0) as plan:   # the device packing makes no attempt at it and asks for the host
+        plan.prepare(empty, 5, 1000, None, 1)
+        assert not plan.used_device_packing and plan.packing_route == (0, False, False, True)
     # a group id that maps outside the matrix is an argument error, not a crash
     p = from_rows([[(10, [(1, 0, 0), (2, 9, 1)])]])
     with pytest.raises(secedo_amd.SecedoError):
@@ -861,10 +864,11 @@ def test_more_chromosomes_than_the_lds_tables_hold():
 
 @pytest.mark.gpu
 def test_a_read_id_with_thousands_of_entries():
-    """The single-entry fast path finds the reads of the repeated ids by walking the links between their entries, one
-    thread per read: an id with more entries than that suits (kChainLimit = 1024, pack_device.hip) voids the attempt
-    and the packing falls back to the radix sorts. One id present at 1600 consecutive loci among single-locus reads
-    (the reference keeps such a read alive while max_fragment_length covers it, similarity_matrix.cpp:376-403)."""
+    """One id present at 1600 consecutive loci among single-locus reads (the reference keeps such a read alive while
+    max_fragment_length covers it, similarity_matrix.cpp:376-403). The single-entry path groups the entries of the
+    repeated ids by the entry that won their id's slot and ranks a read's members by scanning them, up to 8192 of them
+    (kRankScanLimit, pack_device.hip): 1600 stay on that path, in one counting attempt. (Written when the path walked
+    links between a read's entries and gave up beyond 1024 of them; test_gpu_pack_handover.py has the limit itself.)"""
     rng = np.random.default_rng(83)
     n = 40
     rows, rid, pos = [], 1, 5000
@@ -885,6 +889,7 @@ def test_a_read_id_with_thousands_of_entries():
         plan.set_packing("device")
         plan.prepare(p, n, 6000, None, 2)
         assert plan.used_device_packing
+        assert plan.used_single_entry_path and plan.packing_route == (1, False, False, False)
         acc = plan.new_acc()
         plan.accumulate(acc, 0.01, 0.5, 0.01)
         got = plan.finalize(acc, "ADD_MIN").cpu().numpy()
