@@ -4,9 +4,10 @@
  * get_next_chromosome and check_is_diploid (:81-224, :281-286). Library libsecedo_variant.so.
  *
  * The per-locus work (base counts per cluster, the genotype decisions, the per-cell counters behind the
- * `scores` file) runs on the GPU (secedo_amd/csrc/variant_kernels.hip). The map reading and the VCF text stay on
- * the host; the FASTA parse and the gather of the reference genotype per locus run on the host by default and on the
- * GPU on the device route (below). The pileup is the flat layout of
+ * `scores` file) runs on the GPU (secedo_amd/csrc/variant_kernels.hip). The map reading stays on the host, and so
+ * does the VCF text by default (under SECEDO_VCF_BGZF it is formatted and compressed on the GPU, below); the FASTA
+ * parse and the gather of the reference genotype per locus run on the host by default and on the GPU on the device
+ * route (below). The pileup is the flat layout of
  * secedo_simmat.h, with id_base16 or id_base32. Error codes are those of secedo_simmat.h;
  * secedo_variant_last_error() holds the message. No CPU fallback for the compute entry points.
  *
@@ -180,9 +181,73 @@ int secedo_variant_genotypes_device(int device_id, const uint16_t *counts, uint3
                                     int likely_homozygous_total, double hetero_prior, double theta,
                                     uint8_t *homozygous, uint8_t *genotype);
 
+/* ---- The VCF output ----------------------------------------------------------------------------------------------
+ *
+ * Two kinds of output, chosen process-wide like the FASTA route: secedo_variant_set_vcf_output, else the environment
+ * SECEDO_VCF=plain|bgzf (unset or empty: plain; any other value is SECEDO_E_INVALID_ARG from the file-writing calls).
+ *   PLAIN  cluster_<i>.vcf and common.vcf, text built on the host from the downloaded records (the default)
+ *   BGZF   cluster_<i>.vcf.gz and common.vcf.gz instead: the same text, formatted in HBM from the records where the
+ *          calls left them and deflated there; neither the records nor the text come to the host, only the
+ *          compressed bytes. Each file is a sequence of BGZF members of at most 0xFF00 text bytes (18-byte header with
+ *          the BC subfield and BSIZE, one raw DEFLATE block with the fixed codes or, where that would not be smaller,
+ *          a stored one, CRC32, ISIZE) and ends with the 28-byte EOF member, as bgzip writes them; it inflates to the
+ *          bytes PLAIN writes. The preamble is made by the host (##fileDate is the time of the call) and compressed as
+ *          the file's first bytes. `variant` and `scores` are the same on both; errors are PLAIN's word for word.
+ * Both secedo_variant_calling and secedo_variant_calling_device honour the setting. */
+#define SECEDO_VCF_PLAIN 0
+#define SECEDO_VCF_BGZF 1
+
+/* Process-wide. set: SECEDO_E_INVALID_ARG for another value; get: the kind set, else the environment's, else PLAIN
+ * (a negative SECEDO_E_* for an unknown value of SECEDO_VCF). */
+int secedo_variant_set_vcf_output(int output);
+int secedo_variant_get_vcf_output(void);
+
+/* What the last file-writing call of this thread (or secedo_variant_bgzf_deflate) did. Times in ms, host wall clock. */
+typedef struct secedo_variant_vcf_info {
+    uint32_t output;            /* SECEDO_VCF_* the call wrote */
+    uint32_t reserved;
+    uint64_t files;             /* VCF files: clusters + 1 */
+    uint64_t text_bytes;        /* their text */
+    uint64_t compressed_bytes;  /* BGZF: the bytes of the .vcf.gz files, EOF members included; PLAIN: 0 */
+    uint64_t blocks;            /* BGZF members with text (the EOF members not counted) */
+    uint64_t stored_blocks;     /* of those, the ones that fell back to a stored block */
+    double format_ms;           /* BGZF: preambles, the formatter's kernels, the download of the file offsets */
+    double deflate_ms;          /* BGZF: descriptors up, the encoder and pack kernels, member sizes down */
+    double download_ms;         /* BGZF: the compressed bytes down */
+    double write_ms;            /* the files (PLAIN: building the text as well) */
+    double deflate_kernel_ms;   /* BGZF: the encoder kernel alone (device events), included in deflate_ms */
+} secedo_variant_vcf_info;
+int secedo_variant_vcf_stats(secedo_variant_vcf_info *out);
+
+/* Test entry points: the VCF text of host records, by the host code of the PLAIN route and by the kernels of the
+ * BGZF route. records[n_records] in write order (loci ascending, checked), chr_locus_off[n_chr + 1], locus_pos and
+ * locus_ref[n_loci] as the calling functions have them; num_clusters cluster files and common. preamble /
+ * preamble_off[num_clusters + 1] (both may be NULL: no preambles): cluster file i starts with bytes
+ * [preamble_off[i], preamble_off[i + 1]) of preamble. Out: the files' texts back to back in text[capacity], cluster
+ * files in order, then common; file_off[num_clusters + 2] their bounds (SECEDO_E_LIMIT when the text exceeds
+ * capacity: file_off is set, text is not). */
+int secedo_variant_format_host(const secedo_variant_record *records, uint32_t n_records,
+                               const uint32_t *chr_locus_off, uint32_t n_chr, const uint32_t *locus_pos,
+                               const uint8_t *locus_ref, uint32_t n_loci, uint32_t num_clusters, const char *preamble,
+                               const uint64_t *preamble_off, char *text, uint64_t capacity, uint64_t *file_off);
+int secedo_variant_format_device(int device_id, const secedo_variant_record *records, uint32_t n_records,
+                                 const uint32_t *chr_locus_off, uint32_t n_chr, const uint32_t *locus_pos,
+                                 const uint8_t *locus_ref, uint32_t n_loci, uint32_t num_clusters,
+                                 const char *preamble, const uint64_t *preamble_off, char *text, uint64_t capacity,
+                                 uint64_t *file_off);
+
+/* The BGZF encoder alone, on the GPU: n_files inputs, input f the bytes [data_off[f], data_off[f + 1]) of data (host),
+ * all compressed in one launch. Out: the BGZF files back to back in out[capacity], out_off[n_files + 1] their bounds;
+ * an empty input gives the EOF member alone. An input of n bytes needs at most n + 31 * ceil(n / 65280) + 28 bytes
+ * (SECEDO_E_LIMIT when capacity is less: out_off is set, out is not). Sets secedo_variant_vcf_stats. Synchronises
+ * `stream`. */
+int secedo_variant_bgzf_deflate(int device_id, const uint8_t *data, const uint64_t *data_off, uint32_t n_files,
+                                uint8_t *out, uint64_t capacity, uint64_t *out_off, void *stream);
+
 /* The drop-in: variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir)
  * on a host flat pileup. Writes cluster_<i>.vcf for i = 0..max(clusters), common.vcf, an empty `variant` and
- * `scores` under out_dir (created), as the reference does; n == 0 writes nothing. times may be NULL. */
+ * `scores` under out_dir (created), as the reference does (the .vcf files as .vcf.gz under SECEDO_VCF_BGZF, above);
+ * n == 0 writes nothing. times may be NULL. */
 int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
                            const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint16_t *id_base16,
                            const uint32_t *id_base32, const uint16_t *clusters, uint32_t n,

@@ -1,6 +1,6 @@
 // variant_api.cpp -- host side of include/secedo_variant.h: the reference genome (FASTA + Varsim map), the
-// per-locus gather of the reference genotype, the constant tables, the launches of variant_kernels.hip and the
-// VCF / scores text of the reference's variant_calling() (variant_calling.cpp:81-461).
+// per-locus gather of the reference genotype, the constant tables and the launches of variant_kernels.hip for the
+// reference's variant_calling() (variant_calling.cpp:81-461). The files it leaves are vcf_output.cpp's.
 //
 // The FASTA is memory-mapped (a compressed one inflated, fasta_source.cpp) and read through a small restatement of
 // the std::ifstream calls the reference makes (getline, peek, get, putback), so that its quirks carry over: a contig
@@ -11,7 +11,9 @@
 #include "secedo_simmat.h"
 #include "fasta_source.hpp"
 #include "host_util.hpp"
+#include "bgzf_deflate_kernels.hpp"
 #include "variant_kernels.hpp"
+#include "vcf_output.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -20,7 +22,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <ctime>
 #include <filesystem>
 #include <string>
 #include <string_view>
@@ -33,8 +34,6 @@ using secedo::variant::Logs;
 using namespace secedo::host;
 using namespace secedo::fasta_host;
 
-constexpr char kIntToChar[6] = {'A', 'C', 'G', 'T', 'N', 'N'};
-
 // CharToInt (util/util.hpp:17-22): A/a 0, C/c 1, G/g 2, T/t/U/u 3, anything else 5
 uint8_t char_to_int(char c) {
     switch (c) {
@@ -44,11 +43,6 @@ uint8_t char_to_int(char c) {
         case 'T': case 't': case 'U': case 'u': return 3;
         default: return 5;
     }
-}
-
-std::string id_to_chromosome(uint32_t chr_id) {
-    if (chr_id < 22) return std::to_string(chr_id + 1);
-    return chr_id == 22 ? "X" : "Y";
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -400,20 +394,24 @@ constexpr bool kLdsDefault = false;
 
 struct Calls {
     std::vector<secedo_variant_record> records;
+    Buf d_records;  // the records in HBM, for a caller that asked to keep them there
     uint32_t total = 0;
     double kernel_ms = 0;
 };
 
-// Both passes on a resident pileup; records downloaded when they fit `capacity`.
+// Both passes on a resident pileup; records downloaded when they fit `capacity`, or left in out->d_records and not
+// downloaded when keep_on_device.
 int run_calls(const uint32_t *d_chr_locus_off, uint32_t n_chr, const uint64_t *d_locus_entry_off,
               const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci, const uint16_t *d_clusters,
               uint32_t n_groups, const uint8_t *d_locus_ref, const uint32_t *chr_locus_end, double hetero_prior,
-              double theta, uint32_t capacity, uint32_t *d_mismatch, uint32_t *d_loci, Calls *out, hipStream_t s) {
+              double theta, uint32_t capacity, uint32_t *d_mismatch, uint32_t *d_loci, Calls *out, hipStream_t s,
+              bool keep_on_device = false) {
     namespace V = secedo::variant;
     const uint32_t ranges = V::num_ranges(n_loci);
     const std::vector<double> thr = threshold_table(theta);
     const size_t scan_bytes = V::scan_workspace(n_loci);
-    Buf b_thr, b_end, b_cnt, b_off, b_flag, b_err, b_scan, b_rec;
+    Buf b_thr, b_end, b_cnt, b_off, b_flag, b_err, b_scan;
+    Buf &b_rec = out->d_records;
     SECEDO_TRY(b_thr.alloc(thr.size() * sizeof(double)));
     SECEDO_TRY(b_end.alloc((size_t)n_chr * 4));
     SECEDO_TRY(b_cnt.alloc(((size_t)ranges + 1) * 4));
@@ -461,140 +459,14 @@ int run_calls(const uint32_t *d_chr_locus_off, uint32_t n_chr, const uint64_t *d
     SECEDO_TRY(hipEventRecord(e2, s));
     SECEDO_TRY(V::write_calls(in, b_off.as<uint32_t>(), b_flag.as<uint8_t>(), b_rec.as<secedo_variant_record>(), s));
     SECEDO_TRY(hipEventRecord(e3, s));
-    out->records.resize(out->total);
-    if (out->total)
+    if (!keep_on_device) out->records.resize(out->total);
+    if (out->total && !keep_on_device)
         SECEDO_TRY(hipMemcpyAsync(out->records.data(), b_rec.p, (size_t)out->total * sizeof(secedo_variant_record),
                               hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     SECEDO_TRY(hipEventElapsedTime(&k2, e2, e3));
     out->kernel_ms += k2;
     return SECEDO_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The files
-
-const char *const kInfoFormat = "\t.\t.\tVARIANT_OVERALL_TYPE=SNP\tGT\t";
-
-bool is_homozygous(uint32_t g) { return (g & 7) == (g >> 3); }
-
-void append_counts(std::string &o, const uint16_t c[4]) {
-    for (int j = 0; j < 4; ++j) {
-        o += std::to_string(c[j]);
-        o += ' ';
-    }
-    o += '\n';
-}
-
-void append_head(std::string &o, const std::string &chr, uint32_t pos, char ref, const std::string &alt) {
-    o += chr;
-    o += '\t';
-    o += std::to_string(pos);
-    o += "\t.\t";
-    o += ref;
-    o += '\t';
-    o += alt;
-    o += kInfoFormat;
-}
-
-// write_vcf_line (:288-321) for a record the device already found to be written; get_differing_bases (:247-279)
-void append_vcf_line(std::string &o, const std::string &chr, uint32_t pos, uint32_t ref, uint32_t g,
-                     const uint16_t c[4]) {
-    if (is_homozygous(ref)) {
-        std::string alt(1, kIntToChar[g & 7]);
-        const char *gt = "1/1";
-        if (!is_homozygous(g)) {
-            alt += kIntToChar[g >> 3];
-            gt = "0/1";
-        }
-        append_head(o, chr, pos, kIntToChar[ref & 7], alt);
-        o += gt;
-        o += '\t';
-        append_counts(o, c);
-        return;
-    }
-    char r1 = kIntToChar[ref & 7], r2 = kIntToChar[ref >> 3];
-    if (r1 > r2) std::swap(r1, r2);
-    char g1 = kIntToChar[g & 7], g2 = kIntToChar[g >> 3];
-    if (g1 > g2) std::swap(g1, g2);
-    std::pair<char, char> pairs[2];
-    int n = 0;
-    if (g1 == r1 && g2 == r2) n = 0;
-    else if (g1 == r1) pairs[n++] = {r2, g2};
-    else if (g2 == r2) pairs[n++] = {r1, g1};
-    else {
-        pairs[n++] = {r1, g1};
-        pairs[n++] = {r2, g2};
-    }
-    for (int k = 0; k < n; ++k) {
-        append_head(o, chr, pos, pairs[k].first, std::string(1, pairs[k].second));
-        o += "1/1\t";
-        append_counts(o, c);
-    }
-}
-
-int write_file(const std::filesystem::path &path, const std::string &text) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) return fail(SECEDO_E_INVALID_ARG, "cannot write " + path.string());
-    const size_t w = text.empty() ? 0 : fwrite(text.data(), 1, text.size(), f);
-    const bool closed = fclose(f) == 0;
-    const bool ok = w == text.size() && closed;
-    return ok ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, "cannot write " + path.string());
-}
-
-// write_vcf_preamble (:226-241)
-std::string preamble(const std::string &reference, uint32_t cluster) {
-    std::time_t now = std::chrono::system_clock::to_time_t(std::chrono::system_clock::now());
-    std::string o = "##fileformat=VCFv4.2\n##fileDate=";
-    o += std::ctime(&now);
-    o += "##source=SVC (Somatic Variant Caller)\n##reference=" + reference + "\n##cluster=" +
-         std::to_string(cluster) + "\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tcluster-" +
-         std::to_string(cluster) + "\n";
-    return o;
-}
-
-int write_outputs(const std::filesystem::path &out_dir, const std::string &reference, uint32_t num_clusters,
-                  const std::vector<secedo_variant_record> &records, const uint32_t *chr_locus_off, uint32_t n_chr,
-                  const uint32_t *locus_pos, const uint8_t *locus_ref, const std::vector<uint32_t> &mismatch,
-                  const std::vector<uint32_t> &loci) {
-    std::vector<std::string> vcfs(num_clusters);
-    for (uint32_t i = 0; i < num_clusters; ++i) vcfs[i] = preamble(reference, i);
-    std::string common;
-    uint32_t chr = 0;
-    std::string chr_name = id_to_chromosome(0);
-    for (const secedo_variant_record &r : records) {
-        while (chr + 1 < n_chr && r.locus >= chr_locus_off[chr + 1]) chr_name = id_to_chromosome(++chr);
-        const uint32_t pos = locus_pos[r.locus], ref = locus_ref[r.locus];
-        if (r.kind == SECEDO_VARIANT_POOLED) {  // :395-406
-            const uint32_t new_base = r.genotype & 7;
-            const uint32_t ref_base = (ref & 7) == new_base ? (ref >> 3) & 7 : ref & 7;
-            append_head(common, chr_name, pos, kIntToChar[ref_base], std::string(1, kIntToChar[new_base]));
-            common += "1/1\t";
-            append_counts(common, r.counts);
-        } else if (r.kind == SECEDO_VARIANT_COMMON) {
-            append_vcf_line(common, chr_name, pos, ref, r.genotype, r.counts);
-        } else {
-            append_vcf_line(vcfs[r.cluster], chr_name, pos, ref, r.genotype, r.counts);
-        }
-    }
-    for (uint32_t i = 0; i < num_clusters; ++i)
-        SECEDO_CALL(write_file(out_dir / ("cluster_" + std::to_string(i) + ".vcf"), vcfs[i]));
-    SECEDO_CALL(write_file(out_dir / "common.vcf", common));
-    SECEDO_CALL(write_file(out_dir / "variant", ""));
-    // write_vec(scores): default ostream formatting (%g, 6 digits); 0.0 / 0 prints as -nan on x86-64
-    std::string scores;
-    char buf[64];
-    for (size_t i = 0; i < loci.size(); ++i) {
-        if (i) scores += ',';
-        if (loci[i] == 0) {
-            scores += "-nan";
-        } else {
-            snprintf(buf, sizeof buf, "%g", static_cast<double>(mismatch[i]) / loci[i]);
-            scores += buf;
-        }
-    }
-    scores += '\n';
-    return write_file(out_dir / "scores", scores);
 }
 
 // variant_calling on a resident pileup with the host copies of its chromosome offsets and positions (the positions
@@ -607,12 +479,15 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
             const char *out_dir, secedo_variant_times *times, hipStream_t s, double pre_device_ms) {
     secedo_variant_times t{};
     Clock::time_point t0 = Clock::now();
-    std::vector<uint8_t> locus_ref(n_loci);
+    int output = SECEDO_VCF_PLAIN;
+    SECEDO_CALL(secedo::vcf::output_kind(&output));
+    const bool bgzf = output == SECEDO_VCF_BGZF;  // the text is then made in HBM: locus_ref stays there too
+    std::vector<uint8_t> locus_ref(bgzf ? 0 : n_loci);
     std::vector<uint32_t> chr_end(n_chr);
-    Buf b_ref, b_cl, b_mm, b_loci;
+    Buf b_ref, b_cl, b_mm, b_loci, b_pos;
     SECEDO_TRY(b_ref.alloc(n_loci));
     const RefArgs ref{d_chr_locus_off, chr_locus_off, n_chr, d_locus_pos, locus_pos, n_loci, b_ref.as<uint8_t>(),
-                      locus_ref.data(), chr_end.data()};
+                      bgzf ? nullptr : locus_ref.data(), chr_end.data()};
     SECEDO_CALL(reference_any(reference_genome, map_file, ref, &t.fasta_ms, &t.gather_ms, s));
     (void)ms_lap(t0);
     const uint32_t num_clusters = static_cast<uint32_t>(*std::max_element(clusters, clusters + n)) + 1;
@@ -624,15 +499,27 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
     Calls calls;
     SECEDO_CALL(run_calls(d_chr_locus_off, n_chr, d_locus_entry_off, d_id_base16, d_id_base32, n_loci, b_cl.as<uint16_t>(),
                       n, b_ref.as<uint8_t>(), chr_end.data(), hetero_prior, theta, UINT32_MAX, b_mm.as<uint32_t>(),
-                      b_loci.as<uint32_t>(), &calls, s));
+                      b_loci.as<uint32_t>(), &calls, s, bgzf));
     std::vector<uint32_t> mismatch(n), loci(n);
     SECEDO_TRY(hipMemcpyAsync(mismatch.data(), b_mm.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipMemcpyAsync(loci.data(), b_loci.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     t.device_ms = ms_lap(t0) + pre_device_ms;
     t.kernel_ms = calls.kernel_ms;
-    SECEDO_CALL(write_outputs(out_dir, reference_genome, num_clusters, calls.records, chr_locus_off, n_chr, locus_pos,
-                          locus_ref.data(), mismatch, loci));
+    if (bgzf) {
+        if (!d_locus_pos) {  // a host pileup: the formatter reads the positions in HBM
+            SECEDO_TRY(b_pos.alloc((size_t)n_loci * 4));
+            if (n_loci) SECEDO_TRY(hipMemcpyAsync(b_pos.p, locus_pos, (size_t)n_loci * 4, hipMemcpyHostToDevice, s));
+            d_locus_pos = b_pos.as<uint32_t>();
+        }
+        SECEDO_CALL(secedo::vcf::write_outputs_bgzf(out_dir, reference_genome, num_clusters,
+                                                    calls.d_records.as<secedo_variant_record>(), calls.total,
+                                                    d_chr_locus_off, n_chr, d_locus_pos, b_ref.as<uint8_t>(), mismatch,
+                                                    loci, s));
+    } else {
+        SECEDO_CALL(secedo::vcf::write_outputs(out_dir, reference_genome, num_clusters, calls.records, chr_locus_off,
+                                               n_chr, locus_pos, locus_ref.data(), mismatch, loci));
+    }
     t.write_ms = ms_lap(t0);
     if (times) *times = t;
     return SECEDO_OK;
@@ -801,6 +688,130 @@ int secedo_variant_genotypes_device(int device_id, const uint16_t *counts, uint3
                                       host_logs(hetero_prior, theta), b_h.as<uint8_t>(), b_g.as<uint8_t>(), 0));
     SECEDO_TRY(hipMemcpy(homozygous, b_h.p, n, hipMemcpyDeviceToHost));
     SECEDO_TRY(hipMemcpy(genotype, b_g.p, n, hipMemcpyDeviceToHost));
+    return SECEDO_OK;
+}
+
+int secedo_variant_set_vcf_output(int output) {
+    if (output != SECEDO_VCF_PLAIN && output != SECEDO_VCF_BGZF)
+        return fail(SECEDO_E_INVALID_ARG, "output must be SECEDO_VCF_PLAIN or SECEDO_VCF_BGZF");
+    secedo::vcf::set_output(output);
+    return SECEDO_OK;
+}
+
+int secedo_variant_get_vcf_output(void) { return secedo::vcf::get_output(); }
+
+int secedo_variant_vcf_stats(secedo_variant_vcf_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = secedo::vcf::info();
+    return SECEDO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+std::vector<std::string> preamble_strings(const char *preamble, const uint64_t *preamble_off, uint32_t num_clusters) {
+    std::vector<std::string> pre(num_clusters);
+    if (preamble && preamble_off)
+        for (uint32_t i = 0; i < num_clusters; ++i) pre[i].assign(preamble + preamble_off[i], preamble_off[i + 1] - preamble_off[i]);
+    return pre;
+}
+
+int check_format_args(const secedo_variant_record *records, uint32_t n_records, const uint32_t *chr_locus_off,
+                      uint32_t n_chr, const uint32_t *locus_pos, const uint8_t *locus_ref, uint32_t n_loci,
+                      uint32_t num_clusters, const uint64_t *file_off) {
+    if (!chr_locus_off || !file_off || (n_records && !records) || (n_loci && (!locus_pos || !locus_ref)))
+        return fail(SECEDO_E_INVALID_ARG, "null argument");
+    (void)n_chr;
+    for (uint32_t k = 0; k < n_records; ++k) {
+        if (records[k].locus >= n_loci) return fail(SECEDO_E_INVALID_ARG, "a record's locus is >= n_loci");
+        if (records[k].kind == SECEDO_VARIANT_CLUSTER && records[k].cluster >= num_clusters)
+            return fail(SECEDO_E_INVALID_ARG, "a record's cluster is >= num_clusters");
+        if (k && records[k].locus < records[k - 1].locus)
+            return fail(SECEDO_E_INVALID_ARG, "records must ascend in locus");
+    }
+    return SECEDO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int secedo_variant_format_host(const secedo_variant_record *records, uint32_t n_records,
+                               const uint32_t *chr_locus_off, uint32_t n_chr, const uint32_t *locus_pos,
+                               const uint8_t *locus_ref, uint32_t n_loci, uint32_t num_clusters, const char *preamble,
+                               const uint64_t *preamble_off, char *text, uint64_t capacity, uint64_t *file_off) {
+    SECEDO_CALL(check_format_args(records, n_records, chr_locus_off, n_chr, locus_pos, locus_ref, n_loci, num_clusters,
+                                  file_off));
+    std::vector<std::string> vcfs;
+    std::string common;
+    secedo::vcf::build_texts(preamble_strings(preamble, preamble_off, num_clusters), records, n_records, chr_locus_off,
+                             n_chr, locus_pos, locus_ref, &vcfs, &common);
+    vcfs.push_back(std::move(common));
+    uint64_t at = 0;
+    for (uint32_t f = 0; f <= num_clusters; ++f) {
+        file_off[f] = at;
+        if (text && at + vcfs[f].size() <= capacity) memcpy(text + at, vcfs[f].data(), vcfs[f].size());
+        at += vcfs[f].size();
+    }
+    file_off[num_clusters + 1] = at;
+    if (at > capacity) return fail(SECEDO_E_LIMIT, std::to_string(at) + " bytes of text, capacity " + std::to_string(capacity));
+    return SECEDO_OK;
+}
+
+int secedo_variant_format_device(int device_id, const secedo_variant_record *records, uint32_t n_records,
+                                 const uint32_t *chr_locus_off, uint32_t n_chr, const uint32_t *locus_pos,
+                                 const uint8_t *locus_ref, uint32_t n_loci, uint32_t num_clusters,
+                                 const char *preamble, const uint64_t *preamble_off, char *text, uint64_t capacity,
+                                 uint64_t *file_off) {
+    SECEDO_CALL(check_format_args(records, n_records, chr_locus_off, n_chr, locus_pos, locus_ref, n_loci, num_clusters,
+                                  file_off));
+    SECEDO_CALL(set_device(device_id));
+    Buf b_rec, b_chr, b_pos, b_ref;
+    SECEDO_TRY(b_rec.alloc((size_t)n_records * sizeof(secedo_variant_record)));
+    SECEDO_TRY(b_chr.alloc(((size_t)n_chr + 1) * 4));
+    SECEDO_TRY(b_pos.alloc((size_t)n_loci * 4));
+    SECEDO_TRY(b_ref.alloc(n_loci));
+    if (n_records) SECEDO_TRY(hipMemcpy(b_rec.p, records, (size_t)n_records * sizeof(secedo_variant_record), hipMemcpyHostToDevice));
+    SECEDO_TRY(hipMemcpy(b_chr.p, chr_locus_off, ((size_t)n_chr + 1) * 4, hipMemcpyHostToDevice));
+    if (n_loci) SECEDO_TRY(hipMemcpy(b_pos.p, locus_pos, (size_t)n_loci * 4, hipMemcpyHostToDevice));
+    if (n_loci) SECEDO_TRY(hipMemcpy(b_ref.p, locus_ref, n_loci, hipMemcpyHostToDevice));
+    secedo::vcf::DeviceText dt;
+    SECEDO_CALL(secedo::vcf::format_device(preamble_strings(preamble, preamble_off, num_clusters),
+                                           b_rec.as<secedo_variant_record>(), n_records, b_chr.as<uint32_t>(), n_chr,
+                                           b_pos.as<uint32_t>(), b_ref.as<uint8_t>(), &dt, nullptr));
+    for (uint32_t f = 0; f <= num_clusters + 1; ++f) file_off[f] = dt.file_off[f];
+    const uint64_t total = dt.file_off.back();
+    if (total > capacity) return fail(SECEDO_E_LIMIT, std::to_string(total) + " bytes of text, capacity " + std::to_string(capacity));
+    if (total) SECEDO_TRY(hipMemcpy(text, dt.text(), total, hipMemcpyDeviceToHost));
+    return SECEDO_OK;
+}
+
+int secedo_variant_bgzf_deflate(int device_id, const uint8_t *data, const uint64_t *data_off, uint32_t n_files,
+                                uint8_t *out, uint64_t capacity, uint64_t *out_off, void *stream) {
+    if (!data_off || !out_off || (data_off[n_files] && !data)) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    for (uint32_t f = 0; f < n_files; ++f)
+        if (data_off[f] > data_off[f + 1]) return fail(SECEDO_E_INVALID_ARG, "data_off must not decrease");
+    SECEDO_CALL(set_device(device_id));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t b = data_off[0], total = data_off[n_files] - b;
+    Buf b_text;
+    SECEDO_TRY(b_text.alloc(total + 2 * secedo::bgzf::kDeflateInSlack));
+    uint8_t *d_text = b_text.as<uint8_t>() + secedo::bgzf::kDeflateInSlack;
+    if (total) SECEDO_TRY(hipMemcpyAsync(d_text, data + b, total, hipMemcpyHostToDevice, s));
+    std::vector<uint64_t> file_off(data_off, data_off + n_files + 1);
+    for (uint64_t &v : file_off) v -= b;
+    secedo::vcf::info() = secedo_variant_vcf_info{};
+    secedo::vcf::info().output = SECEDO_VCF_BGZF;
+    secedo::vcf::info().files = n_files;
+    secedo::vcf::info().text_bytes = total;
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> off;
+    SECEDO_CALL(secedo::vcf::deflate_device(d_text, file_off, &bytes, &off, s));
+    for (uint32_t f = 0; f <= n_files; ++f) out_off[f] = off[f];
+    if (bytes.size() > capacity)
+        return fail(SECEDO_E_LIMIT, std::to_string(bytes.size()) + " bytes of output, capacity " + std::to_string(capacity));
+    if (!bytes.empty()) memcpy(out, bytes.data(), bytes.size());
     return SECEDO_OK;
 }
 

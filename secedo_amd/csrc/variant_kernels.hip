@@ -323,6 +323,228 @@ __global__ void k_genotypes(const uint16_t *counts, uint32_t n, int lht, const d
 
 uint32_t grid_for(uint32_t n_ranges) { return (n_ranges + WAVES - 1) / WAVES; }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The VCF text (the bgzf output route): write_outputs, append_vcf_line, append_head and append_counts of
+// vcf_output.cpp restated. A record's lines go through a sink, once to count their bytes and once to store them, so
+// the length a line was given room for is the length it has.
+
+struct CountSink {
+    uint32_t n = 0;
+    __device__ void put(char) { ++n; }
+};
+struct ByteSink {
+    uint8_t *p;
+    __device__ void put(char c) { *p++ = uint8_t(c); }
+};
+
+template <class S>
+__device__ void put_str(S &s, const char *t) {
+    for (; *t; ++t) s.put(*t);
+}
+
+// std::to_string of an unsigned: decimal, no padding
+template <class S>
+__device__ void put_uint(S &s, uint32_t v) {
+    uint32_t pow = 1;
+    while (v / pow >= 10) pow *= 10;  // v / pow < 10 is reached before pow * 10 could overflow
+    for (; pow; pow /= 10) s.put(char('0' + (v / pow) % 10));
+}
+
+__device__ __forceinline__ char base_char(uint32_t b) { return b < 6 ? "ACGTNN"[b] : 'N'; }
+
+template <class S>
+__device__ void put_head(S &s, uint32_t chr, uint32_t pos, char ref, char alt1, char alt2) {
+    if (chr < 22) put_uint(s, chr + 1);  // id_to_chromosome
+    else s.put(chr == 22 ? 'X' : 'Y');
+    s.put('\t');
+    put_uint(s, pos);
+    put_str(s, "\t.\t");
+    s.put(ref);
+    s.put('\t');
+    s.put(alt1);
+    if (alt2) s.put(alt2);
+    put_str(s, "\t.\t.\tVARIANT_OVERALL_TYPE=SNP\tGT\t");
+}
+
+template <class S>
+__device__ void put_tail(S &s, const char *gt, const uint16_t c[4]) {
+    put_str(s, gt);
+    s.put('\t');
+    for (int j = 0; j < 4; ++j) {
+        put_uint(s, c[j]);
+        s.put(' ');
+    }
+    s.put('\n');
+}
+
+// the 0, 1 or 2 lines of one record
+template <class S>
+__device__ void put_record(S &s, const secedo_variant_record &r, uint32_t chr, uint32_t pos, uint32_t ref) {
+    const uint32_t g = r.genotype;
+    if (r.kind == SECEDO_VARIANT_POOLED) {
+        const uint32_t new_base = g & 7;
+        const uint32_t ref_base = (ref & 7) == new_base ? (ref >> 3) & 7 : ref & 7;
+        put_head(s, chr, pos, base_char(ref_base), base_char(new_base), 0);
+        put_tail(s, "1/1", r.counts);
+        return;
+    }
+    if ((ref & 7) == (ref >> 3)) {  // homozygous reference
+        const bool hom = (g & 7) == (g >> 3);
+        put_head(s, chr, pos, base_char(ref & 7), base_char(g & 7), hom ? 0 : base_char(g >> 3));
+        put_tail(s, hom ? "1/1" : "0/1", r.counts);
+        return;
+    }
+    // heterozygous reference: get_differing_bases on the sorted pairs
+    char r1 = base_char(ref & 7), r2 = base_char(ref >> 3), g1 = base_char(g & 7), g2 = base_char(g >> 3);
+    if (r1 > r2) {
+        const char t = r1;
+        r1 = r2, r2 = t;
+    }
+    if (g1 > g2) {
+        const char t = g1;
+        g1 = g2, g2 = t;
+    }
+    const bool first = g1 != r1, second = g2 != r2;
+    if (first && second) {
+        put_head(s, chr, pos, r1, g1, 0);
+        put_tail(s, "1/1", r.counts);
+        put_head(s, chr, pos, r2, g2, 0);
+        put_tail(s, "1/1", r.counts);
+    } else if (second) {  // g1 == r1
+        put_head(s, chr, pos, r2, g2, 0);
+        put_tail(s, "1/1", r.counts);
+    } else if (first) {  // g2 == r2
+        put_head(s, chr, pos, r1, g1, 0);
+        put_tail(s, "1/1", r.counts);
+    }
+}
+
+// the chromosome write_outputs has reached at a record of this locus (records ascend in locus)
+__device__ uint32_t chromosome_of(const uint32_t *__restrict__ chr_locus_off, uint32_t n_chr, uint32_t locus) {
+    uint32_t chr = 0;
+    while (chr + 1 < n_chr && locus >= chr_locus_off[chr + 1]) ++chr;
+    return chr;
+}
+
+// the workspace of the two steps, carved from one allocation
+struct FormatWork {
+    uint32_t *key, *key_sorted, *idx, *idx_sorted, *len;
+    uint64_t *len_sorted, *off;  // [n_records + 1]: the last length 0, the last offset the total
+    void *cub;
+    size_t cub_bytes, total;
+};
+
+size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
+
+FormatWork carve(void *base, uint32_t n) {
+    FormatWork w{};
+    size_t sort_bytes = 0, scan_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                             (uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, 32);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (int)n + 1);
+    uint8_t *p = static_cast<uint8_t *>(base);
+    size_t at = 0;
+    auto take = [&](size_t bytes) {  // base may be null: then only the total is wanted
+        uint8_t *q = p ? p + at : nullptr;
+        at += align_up(bytes);
+        return q;
+    };
+    w.key = reinterpret_cast<uint32_t *>(take((size_t)n * 4));
+    w.key_sorted = reinterpret_cast<uint32_t *>(take((size_t)n * 4));
+    w.idx = reinterpret_cast<uint32_t *>(take((size_t)n * 4));
+    w.idx_sorted = reinterpret_cast<uint32_t *>(take((size_t)n * 4));
+    w.len = reinterpret_cast<uint32_t *>(take((size_t)n * 4));
+    w.len_sorted = reinterpret_cast<uint64_t *>(take(((size_t)n + 1) * 8));
+    w.off = reinterpret_cast<uint64_t *>(take(((size_t)n + 1) * 8));
+    w.cub_bytes = std::max(sort_bytes, scan_bytes);
+    w.cub = take(w.cub_bytes);
+    w.total = at;
+    return w;
+}
+
+__global__ __launch_bounds__(TPB) void k_vcf_measure(FormatIn in, uint32_t *__restrict__ key,
+                                                     uint32_t *__restrict__ idx, uint32_t *__restrict__ len) {
+    const uint32_t r = blockIdx.x * TPB + threadIdx.x;
+    if (r >= in.n_records) return;
+    const secedo_variant_record rec = in.records[r];
+    CountSink s;
+    put_record(s, rec, chromosome_of(in.chr_locus_off, in.n_chr, rec.locus), in.locus_pos[rec.locus],
+               in.locus_ref[rec.locus]);
+    key[r] = rec.kind == SECEDO_VARIANT_CLUSTER ? min((uint32_t)rec.cluster, in.num_clusters) : in.num_clusters;
+    idx[r] = r;
+    len[r] = s.n;
+}
+
+__global__ __launch_bounds__(TPB) void k_vcf_gather(const uint32_t *__restrict__ len,
+                                                    const uint32_t *__restrict__ idx_sorted, uint32_t n,
+                                                    uint64_t *__restrict__ len_sorted) {
+    const uint32_t j = blockIdx.x * TPB + threadIdx.x;
+    if (j <= n) len_sorted[j] = j < n ? len[idx_sorted[j]] : 0;
+}
+
+// file f begins where its preamble does: after the preambles of the files before and the lines sorted before its own
+__global__ __launch_bounds__(TPB) void k_vcf_files(const uint32_t *__restrict__ key_sorted,
+                                                   const uint64_t *__restrict__ off, uint32_t n,
+                                                   const uint64_t *__restrict__ preamble_off, uint32_t n_files,
+                                                   uint64_t *__restrict__ file_off) {
+    const uint32_t f = blockIdx.x * TPB + threadIdx.x;
+    if (f > n_files) return;
+    uint32_t lo = 0, hi = n;  // the first sorted record with key >= f
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (key_sorted[mid] < f) lo = mid + 1;
+        else hi = mid;
+    }
+    file_off[f] = preamble_off[f] + off[lo];
+}
+
+constexpr uint32_t kStageBytes = 2 * kMaxLineBytes * TPB + 64;  // a workgroup's lines when no preamble lies between
+
+// A workgroup's 256 sorted records are consecutive in the buffer but for the preambles of the files that begin among
+// them. Their lines are put together in LDS and leave as whole dwords; the preamble gaps carry whatever LDS held and
+// are overwritten by k_vcf_preambles, which runs after. A group whose span exceeds the stage stores bytes directly.
+__global__ __launch_bounds__(TPB) void k_vcf_write(FormatIn in, const uint32_t *__restrict__ key_sorted,
+                                                   const uint32_t *__restrict__ idx_sorted,
+                                                   const uint64_t *__restrict__ off, uint8_t *__restrict__ text) {
+    __shared__ __align__(16) uint8_t stage[kStageBytes];
+    const uint32_t n = in.n_records, j0 = blockIdx.x * TPB, j = j0 + threadIdx.x;
+    const uint32_t j1 = min(n, j0 + TPB) - 1;  // the group's last record
+    const uint64_t start = off[j0] + in.preamble_off[key_sorted[j0] + 1];
+    const uint64_t end = off[j1 + 1] + in.preamble_off[key_sorted[j1] + 1];  // off[j1 + 1] - off[j1] is j1's length
+    const bool staged = end - start <= kStageBytes;
+    if (j < n) {
+        const secedo_variant_record rec = in.records[idx_sorted[j]];
+        const uint64_t at = off[j] + in.preamble_off[key_sorted[j] + 1];
+        ByteSink s{staged ? stage + (at - start) : text + at};
+        put_record(s, rec, chromosome_of(in.chr_locus_off, in.n_chr, rec.locus), in.locus_pos[rec.locus],
+                   in.locus_ref[rec.locus]);
+    }
+    if (!staged) return;
+    __syncthreads();
+    const uint32_t span = uint32_t(end - start);
+    uint8_t *dst = text + start;
+    const uint32_t head = min(span, uint32_t(-reinterpret_cast<uintptr_t>(dst)) & 3u);
+    const uint32_t words = (span - head) / 4, tail = head + 4 * words;
+    if (threadIdx.x < head) dst[threadIdx.x] = stage[threadIdx.x];
+    for (uint32_t k = threadIdx.x; k < words; k += TPB) {
+        const uint8_t *b = stage + head + 4 * k;
+        *reinterpret_cast<uint32_t *>(dst + head + 4 * k) =
+            uint32_t(b[0]) | uint32_t(b[1]) << 8 | uint32_t(b[2]) << 16 | uint32_t(b[3]) << 24;
+    }
+    if (tail + threadIdx.x < span) dst[tail + threadIdx.x] = stage[tail + threadIdx.x];
+}
+
+__global__ __launch_bounds__(64) void k_vcf_preambles(const uint8_t *__restrict__ preamble,
+                                                      const uint64_t *__restrict__ preamble_off,
+                                                      const uint64_t *__restrict__ file_off, uint32_t n_files,
+                                                      uint8_t *__restrict__ text) {
+    const uint32_t f = blockIdx.x;
+    if (f >= n_files) return;
+    const uint64_t b = preamble_off[f], n = preamble_off[f + 1] - b;
+    uint8_t *dst = text + file_off[f];
+    for (uint64_t i = threadIdx.x; i < n; i += 64) dst[i] = preamble[b + i];
+}
+
 }  // namespace
 
 static_assert(kLociPerWave <= 64, "k_write takes a wave's locus flags in one ballot");
@@ -371,6 +593,51 @@ hipError_t genotypes(const uint16_t *d_counts, uint32_t n, int likely_homozygous
     if (n > 0)
         hipLaunchKernelGGL(k_genotypes, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, stream, d_counts, n,
                            likely_homozygous_total, d_threshold, logs, d_homozygous, d_genotype);
+    return hipGetLastError();
+}
+
+size_t format_workspace(uint32_t n_records) {
+    return carve(nullptr, n_records).total;
+}
+
+hipError_t format_measure(const FormatIn &in, void *workspace, size_t workspace_bytes, uint64_t *d_file_off,
+                          hipStream_t stream) {
+    const uint32_t n = in.n_records, n_files = in.num_clusters + 1;
+    const FormatWork w = carve(workspace, n);
+    if (w.total > workspace_bytes) return hipErrorInvalidValue;
+    hipError_t e;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_vcf_measure, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, stream, in, w.key, w.idx, w.len);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        uint32_t bits = 1;  // keys are 0 .. num_clusters
+        while (bits < 32 && (in.num_clusters >> bits)) ++bits;
+        size_t cub_bytes = w.cub_bytes;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(w.cub, cub_bytes, w.key, w.key_sorted, w.idx, w.idx_sorted, (int)n,
+                                                    0, (int)bits, stream)) != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(k_vcf_gather, dim3(n / TPB + 1), dim3(TPB), 0, stream, w.len, w.idx_sorted, n, w.len_sorted);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    size_t cub_bytes = w.cub_bytes;
+    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cub_bytes, w.len_sorted, w.off, (int)n + 1, stream)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_vcf_files, dim3(n_files / TPB + 1), dim3(TPB), 0, stream, w.key_sorted, w.off, n,
+                       in.preamble_off, n_files, d_file_off);
+    return hipGetLastError();
+}
+
+hipError_t format_write(const FormatIn &in, const void *workspace, size_t workspace_bytes, const uint64_t *d_file_off,
+                        uint8_t *d_text, hipStream_t stream) {
+    const uint32_t n = in.n_records, n_files = in.num_clusters + 1;
+    const FormatWork w = carve(const_cast<void *>(workspace), n);
+    if (w.total > workspace_bytes) return hipErrorInvalidValue;
+    if (n > 0)
+        hipLaunchKernelGGL(k_vcf_write, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, stream, in, w.key_sorted,
+                           w.idx_sorted, w.off, d_text);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_vcf_preambles, dim3(n_files), dim3(64), 0, stream, in.preamble, in.preamble_off, d_file_off,
+                       n_files, d_text);
     return hipGetLastError();
 }
 

@@ -61,5 +61,36 @@ hipError_t write_calls(const CallsIn &in, const uint32_t *d_range_off, const uin
 hipError_t genotypes(const uint16_t *d_counts, uint32_t n, int likely_homozygous_total, const double *d_threshold,
                      Logs logs, uint8_t *d_homozygous, uint8_t *d_genotype, hipStream_t stream);
 
+// ---- The VCF text, formatted in HBM (the bgzf output route) -----------------------------------------------------
+//
+// The files are cluster_0 .. cluster_<num_clusters - 1>, then common: num_clusters + 1 of them. Their texts stand
+// back to back in that order in one buffer, each file's preamble (made by the host; common has none) first.
+struct FormatIn {
+    const secedo_variant_record *records;  // device, in write order
+    uint32_t n_records;
+    const uint32_t *chr_locus_off;  // device [n_chr + 1]
+    uint32_t n_chr;
+    const uint32_t *locus_pos;  // device
+    const uint8_t *locus_ref;   // device
+    uint32_t num_clusters;
+    const uint8_t *preamble;       // device: the preambles back to back
+    const uint64_t *preamble_off;  // device [num_clusters + 2]: file f's preamble is bytes [off[f], off[f + 1])
+};
+
+constexpr uint32_t kMaxLineBytes = 82;  // "22\t4294967295\t.\tA\tCG" + the fixed columns + "1/1\t" + 4 x "65535 " + "\n"
+
+// Bytes of workspace format_measure and format_write share for n_records records.
+size_t format_workspace(uint32_t n_records);
+
+// Step 1: each record's destination file and text length, the stable partition by file (records keep their write
+// order within a file), the u64 scan of the lengths. d_file_off[num_clusters + 2] receives each file's first byte in
+// the buffer, the last entry the total.
+hipError_t format_measure(const FormatIn &in, void *workspace, size_t workspace_bytes, uint64_t *d_file_off,
+                          hipStream_t stream);
+
+// Step 2: the lines and the preambles into d_text (d_file_off's total bytes), from the workspace step 1 left.
+hipError_t format_write(const FormatIn &in, const void *workspace, size_t workspace_bytes, const uint64_t *d_file_off,
+                        uint8_t *d_text, hipStream_t stream);
+
 }  // namespace variant
 }  // namespace secedo

@@ -9,6 +9,8 @@ Departures: two input files for one chromosome and a --clustering file whose len
 errors (exit 1); --num_threads only sizes host pools (at most 16). --reference_genome may be plain FASTA, bgzip
 (BGZF) or plain gzip (.fa.gz works; the kind is told by content); --fasta_route host|device (default: the
 environment SECEDO_FASTA, else host) says where its parse and per-locus gather run, see secedo_amd/variant.py.
+--vcf_output plain|bgzf (default: the environment SECEDO_VCF, else plain) says whether the VCF files are written as
+text by the host or as bgzip-compressed .vcf.gz, formatted and deflated on the GPU.
 """
 from __future__ import annotations
 
@@ -46,6 +48,7 @@ FLAGS: Dict[str, Tuple[str, object]] = {
     "reference_genome": ("str", ""),
     "map_file": ("str", ""),
     "fasta_route": ("str", ""),
+    "vcf_output": ("str", ""),
     "clustering": ("str", ""),
     "compute_read_stats": ("bool", False),
     "num_threads": ("uint", 8),
@@ -67,7 +70,9 @@ def usage() -> str:
     for name, (kind, default) in FLAGS.items():
         lines.append("  -%s (%s) default: %r" % (name, kind, default))
     lines += ["", "--reference_genome takes plain FASTA, bgzip (BGZF) or plain gzip: genome.fa.gz works as it is.",
-              "--fasta_route host|device: where the FASTA is parsed (default: SECEDO_FASTA, else host; BGZF: device)."]
+              "--fasta_route host|device: where the FASTA is parsed (default: SECEDO_FASTA, else host; BGZF: device).",
+              "--vcf_output plain|bgzf: cluster_<i>.vcf / common.vcf as text, or as .vcf.gz compressed on the GPU "
+              "(default: SECEDO_VCF, else plain)."]
     return "\n".join(lines)
 
 
@@ -138,6 +143,8 @@ def validate(f: Flags) -> None:
                          "SCALE_MAX_1" % f.normalization)
     if f.fasta_route not in ("", "host", "device"):
         raise UsageError("Invalid value for --fasta_route: %s.\nShould be one of host, device" % f.fasta_route)
+    if f.vcf_output not in ("", "plain", "bgzf"):
+        raise UsageError("Invalid value for --vcf_output: %s.\nShould be one of plain, bgzf" % f.vcf_output)
     if not 1 <= f.tumor_purity <= 5:
         raise UsageError("Invalid value for --tumor_purity: %d.\nShould be 1,2,3,4, or 5" % f.tumor_purity)
     if f.arma_kmeans and f.clustering_type != "FIEDLER":
@@ -324,7 +331,7 @@ def run(plan: Plan) -> int:
     from . import SimilarityMatrixPlan
     from .cluster import divide_cluster_resident
     from .pileup_reader import get_grouping
-    from .variant import fasta_stats, variant_calling_resident
+    from .variant import fasta_stats, variant_calling_resident, vcf_stats
 
     f = plan.flags
     t0 = time.perf_counter()
@@ -370,12 +377,20 @@ def run(plan: Plan) -> int:
         if f.reference_genome:
             _log(f, "Performing variant calling against %s" % f.reference_genome)
             vc_times = variant_calling_resident(sm, res, clusters, f.reference_genome, f.map_file, 1e-3,
-                                                f.seq_error_rate, f.o, fasta_route=f.fasta_route or None)
+                                                f.seq_error_rate, f.o, fasta_route=f.fasta_route or None,
+                                                vcf_output=f.vcf_output or None)
             fs = fasta_stats()
             vc_times["fasta"] = "%s on %s" % (fs["kind"], fs["route"])
             if fs["route"] == "device":  # the device route's split; the three overlap
                 vc_times.update(fasta_inflate_ms=fs["inflate_ms"], fasta_upload_ms=fs["upload_ms"],
                                 fasta_parse_gather_ms=fs["parse_gather_ms"])
+            vs = vcf_stats()
+            vc_times["vcf"] = "%s, %d files, %d bytes of text" % (vs["output"], vs["files"], vs["text_bytes"])
+            if vs["output"] == "bgzf":
+                vc_times["vcf"] += ", %d compressed in %d blocks (%d stored)" % (
+                    vs["compressed_bytes"], vs["blocks"], vs["stored_blocks"])
+                vc_times.update(vcf_format_ms=vs["format_ms"], vcf_deflate_ms=vs["deflate_ms"],
+                                vcf_download_ms=vs["download_ms"], vcf_write_ms=vs["write_ms"])
         else:
             _log(f, "Skipping variant calling, because no reference genome was provided")
         t_end = time.perf_counter()

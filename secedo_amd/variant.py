@@ -10,6 +10,13 @@ The reference genome may be plain text, BGZF or plain gzip (told by content). It
 run on the host by default; ``set_fasta_route("device")``, the environment ``SECEDO_FASTA=device`` or the
 ``fasta_route`` keyword of the calling functions move them to the GPU (a BGZF file always goes there), where the
 text never lives on the host. ``fasta_stats()`` says what the last call did.
+
+The VCF files are plain text written by the host by default. ``set_vcf_output("bgzf")``, the environment
+``SECEDO_VCF=bgzf`` or the ``vcf_output`` keyword of the calling functions write ``cluster_<i>.vcf.gz`` and
+``common.vcf.gz`` instead: the lines are formatted on the GPU from the records where the calls left them, cut into BGZF
+members and deflated there (secedo_amd/csrc/bgzf_deflate_kernels.hip), and only compressed bytes come back. Each file
+inflates to the bytes the plain route writes. ``vcf_stats()`` says what the last call wrote; ``bgzf_deflate`` is the
+encoder alone, the mirror of ``secedo_amd.bgzf_inflate``.
 """
 from __future__ import annotations
 
@@ -52,7 +59,16 @@ class FastaInfo(C.Structure):
                 ("upload_ms", C.c_double), ("parse_gather_ms", C.c_double)]
 
 
+class VcfInfo(C.Structure):
+    _fields_ = [("output", C.c_uint32), ("reserved", C.c_uint32), ("files", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("compressed_bytes", C.c_uint64), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64),
+                ("format_ms", C.c_double), ("deflate_ms", C.c_double), ("download_ms", C.c_double),
+                ("write_ms", C.c_double), ("deflate_kernel_ms", C.c_double)]
+
+
 FASTA_ROUTES = ("host", "device")
+VCF_OUTPUTS = ("plain", "bgzf")
+BGZF_CUT = 0xFF00  # text bytes per BGZF member at the most
 FASTA_KINDS = ("text", "bgzf", "gzip")
 
 RECORD_DTYPE = np.dtype([("locus", np.uint32), ("cluster", np.uint16), ("genotype", np.uint8), ("kind", np.uint8),
@@ -67,6 +83,14 @@ SIGNATURES = {
     "secedo_variant_fasta_stats": (C.c_int, [C.POINTER(FastaInfo)]),
     "secedo_variant_reference_genotypes_device": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, _vp, _vp, C.c_uint32, _vp,
                                                             C.c_uint32, _vp, _vp, C.POINTER(Times), _vp]),
+    "secedo_variant_set_vcf_output": (C.c_int, [C.c_int]),
+    "secedo_variant_get_vcf_output": (C.c_int, []),
+    "secedo_variant_vcf_stats": (C.c_int, [C.POINTER(VcfInfo)]),
+    "secedo_variant_format_host": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32,
+                                             C.c_char_p, _vp, _vp, C.c_uint64, _vp]),
+    "secedo_variant_format_device": (C.c_int, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32,
+                                               C.c_uint32, C.c_char_p, _vp, _vp, C.c_uint64, _vp]),
+    "secedo_variant_bgzf_deflate": (C.c_int, [C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
     "secedo_variant_is_diploid": (C.c_int, [C.c_char_p]),
     "secedo_variant_read_chromosome": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "secedo_variant_read_map": (C.c_int, [C.c_char_p, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _u32p]),
@@ -150,6 +174,98 @@ def _route(route):
         yield
     finally:
         set_fasta_route(before)
+
+
+def set_vcf_output(output):
+    """The process-wide kind of VCF output: "plain" (cluster_<i>.vcf, common.vcf) or "bgzf" (the same text as
+    .vcf.gz, formatted and deflated on the GPU; see the module docstring)."""
+    if output not in VCF_OUTPUTS:
+        raise ValueError("vcf output must be 'plain' or 'bgzf', not %r" % (output,))
+    check(lib().secedo_variant_set_vcf_output(VCF_OUTPUTS.index(output)))
+
+
+def get_vcf_output() -> str:
+    rc = lib().secedo_variant_get_vcf_output()
+    if rc < 0:
+        check(rc)
+    return VCF_OUTPUTS[rc]
+
+
+@contextlib.contextmanager
+def _output(output):
+    """A scoped override of the VCF output, as _route is of the FASTA route."""
+    if output is None:
+        yield
+        return
+    before = get_vcf_output()
+    set_vcf_output(output)
+    try:
+        yield
+    finally:
+        set_vcf_output(before)
+
+
+def vcf_stats() -> dict:
+    """What the last file-writing call of this thread (or bgzf_deflate) did (secedo_variant_vcf_info), the output as a
+    word."""
+    info = VcfInfo()
+    check(lib().secedo_variant_vcf_stats(C.byref(info)))
+    out = {name: getattr(info, name) for name, _ in VcfInfo._fields_ if name != "reserved"}
+    out["output"] = VCF_OUTPUTS[info.output]
+    return out
+
+
+def bgzf_deflate_many(inputs, device=0):
+    """Every input (bytes-like) compressed on the GPU in one launch -> a list of complete BGZF files (bytes): members
+    of at most 0xFF00 input bytes and the EOF member; an empty input gives the EOF member alone."""
+    datas = [bytes(d) for d in inputs]
+    off = np.zeros(len(datas) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(d) for d in datas], dtype=np.uint64)
+    data = np.frombuffer(b"".join(datas), dtype=np.uint8)
+    cap = int(sum(len(d) + 31 * (-(-len(d) // BGZF_CUT)) + 28 for d in datas))
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    out_off = np.zeros(len(datas) + 1, dtype=np.uint64)
+    check(lib().secedo_variant_bgzf_deflate(device, _lib.ptr(data) if len(data) else None, _lib.ptr(off), len(datas),
+                                            _lib.ptr(out), cap, _lib.ptr(out_off), _stream(device)))
+    return [out[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(len(datas))]
+
+
+def bgzf_deflate(data, device=0) -> bytes:
+    """The BGZF encoder alone, on the GPU: `data` (bytes-like) -> a complete BGZF file, as `bgzip` would cut it. The
+    mirror of secedo_amd.bgzf_inflate(path)."""
+    return bgzf_deflate_many([data], device)[0]
+
+
+def _format(fn, records, chr_locus_off, locus_pos, locus_ref, num_clusters, preambles):
+    rec = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    off = np.ascontiguousarray(chr_locus_off, dtype=np.uint32)
+    pos = np.ascontiguousarray(locus_pos, dtype=np.uint32)
+    ref = np.ascontiguousarray(locus_ref, dtype=np.uint8)
+    pre = [bytes(p) for p in (preambles or [b""] * num_clusters)]
+    if len(pre) != num_clusters:
+        raise ValueError("one preamble per cluster")
+    pre_off = np.zeros(num_clusters + 1, dtype=np.uint64)
+    pre_off[1:] = np.cumsum([len(p) for p in pre], dtype=np.uint64)
+    file_off = np.zeros(num_clusters + 2, dtype=np.uint64)
+    cap = int(pre_off[-1]) + 2 * 82 * len(rec)  # a record is at most two lines of 82 bytes
+    text = np.zeros(max(cap, 1), dtype=np.uint8)
+    check(fn(_lib.ptr(rec) if len(rec) else None, len(rec), _lib.ptr(off), len(off) - 1,
+             _lib.ptr(pos) if len(pos) else None, _lib.ptr(ref) if len(ref) else None, len(pos), num_clusters,
+             b"".join(pre), _lib.ptr(pre_off), _lib.ptr(text), cap, _lib.ptr(file_off)))
+    return [text[int(file_off[i]):int(file_off[i + 1])].tobytes() for i in range(num_clusters + 1)]
+
+
+def format_host(records, chr_locus_off, locus_pos, locus_ref, num_clusters, preambles=None):
+    """The VCF text of `records` (RECORD_DTYPE, write order) as the plain route builds it -> [cluster_0, ...,
+    cluster_<num_clusters - 1>, common] as bytes; preambles: the cluster files' first bytes. No GPU."""
+    return _format(lib().secedo_variant_format_host, records, chr_locus_off, locus_pos, locus_ref, num_clusters,
+                   preambles)
+
+
+def format_device(records, chr_locus_off, locus_pos, locus_ref, num_clusters, preambles=None, device=0):
+    """The same text by the formatter kernels of the bgzf route."""
+    fn = lib().secedo_variant_format_device
+    return _format(lambda *a: fn(device, *a), records, chr_locus_off, locus_pos, locus_ref, num_clusters, preambles)
 
 
 def fasta_stats() -> dict:
@@ -311,14 +427,15 @@ def _times(t):
 
 
 def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                    out_dir="variant_calling", device=0, fasta_route=None):
+                    out_dir="variant_calling", device=0, fasta_route=None, vcf_output=None):
     """variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir): writes
     cluster_<i>.vcf, common.vcf, variant and scores under out_dir as the reference does. fasta_route ("host",
-    "device"; None: the setting) overrides the FASTA route for this call. -> step times (ms)."""
+    "device"; None: the setting) overrides the FASTA route for this call, vcf_output ("plain", "bgzf"; None: the
+    setting) the kind of VCF files. -> step times (ms)."""
     p, b16, b32 = _flat(pos_data)
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     t = Times()
-    with _route(fasta_route):
+    with _route(fasta_route), _output(vcf_output):
         check(lib().secedo_variant_calling(device, _lib.ptr(p.chr_locus_off), p.n_chr, _lib.ptr(p.locus_pos),
                                            _lib.ptr(p.locus_entry_off), _lib.ptr(b16), _lib.ptr(b32), _lib.ptr(cl),
                                            len(cl), _b(reference_genome), _b(map_file), hetero_prior, theta,
@@ -327,13 +444,13 @@ def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_pr
 
 
 def variant_calling_resident(plan, res, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                             out_dir="variant_calling", fasta_route=None):
+                             out_dir="variant_calling", fasta_route=None, vcf_output=None):
     """variant_calling on the pileup `res` resident in HBM (SimilarityMatrixPlan.upload, as divide_cluster_resident
-    takes it), in the plan's current stream. fasta_route as in variant_calling. -> step times (ms)."""
+    takes it), in the plan's current stream. fasta_route and vcf_output as in variant_calling. -> step times (ms)."""
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     idb = C.c_void_p(res["idb"].data_ptr())
     t = Times()
-    with _route(fasta_route):
+    with _route(fasta_route), _output(vcf_output):
         check(lib().secedo_variant_calling_device(
             plan.device, C.c_void_p(res["chr"].data_ptr()), res["n_chr"], C.c_void_p(res["pos"].data_ptr()),
             C.c_void_p(res["off"].data_ptr()), idb if res["idb_is16"] else None, None if res["idb_is16"] else idb,

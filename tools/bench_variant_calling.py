@@ -15,6 +15,9 @@ workload:
 --fasta_route host|device picks the route of the FASTA parse and gather (default: the library's setting),
 --compress none|gzip|bgzf how the synthetic genome is written, --lib PATH another build of libsecedo_variant.so
 (an A/B against the parent commit; one without the device entry point runs `fasta` on the host function).
+--vcf_output plain|bgzf|both picks the kind of VCF files (default: the library's setting); `both` measures the two on
+the same data, one JSON line each, with the bgzf route's format / deflate / download / write split, its compressed
+size and the encoder kernel's time.
 
 Each line: the two kernels (device events), the end-to-end call split into FASTA parse / gather / device (uploads,
 kernels, downloads) / write, and the achieved bytes/s of the kernels against the HBM peak (8 TB/s spec, 6.3
@@ -94,7 +97,7 @@ def compress_file(path, how):
         f.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
 
 
-OPTIONS = dict(fasta_route=None, compress="none")
+OPTIONS = dict(fasta_route=None, compress="none", vcf_output=None)
 
 
 def compulsory_bytes(p, n_groups, idb_bytes):
@@ -103,23 +106,37 @@ def compulsory_bytes(p, n_groups, idb_bytes):
 
 
 def run(name, p, clusters, fasta, reps=3):
+    outputs = ["plain", "bgzf"] if OPTIONS["vcf_output"] == "both" else [OPTIONS["vcf_output"]]
+    for output in outputs:
+        run_one(name, p, clusters, fasta, reps, output)
+
+
+def run_one(name, p, clusters, fasta, reps, output):
     out = tempfile.mkdtemp(prefix="vc_bench_")
+    kw = {} if output is None else dict(vcf_output=output)  # a parent build's variant.py has no such keyword
+    has_vcf = hasattr(variant, "vcf_stats") and hasattr(variant.lib(), "secedo_variant_vcf_stats")
     try:
         route = OPTIONS["fasta_route"]
-        variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out, fasta_route=route)  # warm-up
+        variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out, fasta_route=route, **kw)  # warm-up
         runs = []
         for _ in range(reps):
             t0 = time.perf_counter()
-            t = variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out, fasta_route=route)
+            t = variant.variant_calling(p, clusters, fasta, "", 1e-3, 0.01, out, fasta_route=route, **kw)
             t["total_ms"] = (time.perf_counter() - t0) * 1e3
+            vs = variant.vcf_stats() if has_vcf else dict(output="plain")
+            t.update({"vcf_" + k: float(vs[k]) for k in ("format_ms", "deflate_ms", "download_ms", "write_ms",
+                                                         "deflate_kernel_ms") if k in vs})
             fs = (variant.fasta_stats() if hasattr(variant.lib(), "secedo_variant_fasta_stats") else
                   dict(route="host", kind="text", text_bytes=0, inflate_ms=0.0, upload_ms=0.0, parse_gather_ms=0.0))
             t.update(fasta_inflate_ms=fs["inflate_ms"], fasta_upload_ms=fs["upload_ms"],
                      fasta_parse_gather_ms=fs["parse_gather_ms"])
             runs.append(t)
         med = {k: round(float(np.median([r[k] for r in runs])), 3) for k in runs[0]}
-        n_lines = sum(1 for f in os.listdir(out) if f.endswith(".vcf")
-                      for line in open(os.path.join(out, f)) if line[0] != "#")
+        n_lines = sum(1 for f in os.listdir(out) if f.endswith((".vcf", ".vcf.gz"))
+                      for line in (gzip.open if f.endswith(".gz") else open)(os.path.join(out, f), "rb")
+                      if line[:1] != b"#")
+        vcf = {k: vs[k] for k in ("output", "files", "text_bytes", "compressed_bytes", "blocks", "stored_blocks")
+               if k in vs}
         recs, _, _, kms = variant.variant_calls(p, clusters, fasta, with_kernel_ms=True)
         modes = {}
         for mode in ("lds", "global"):  # the counted-entry counters: LDS-privatised vs global atomics
@@ -135,7 +152,7 @@ def run(name, p, clusters, fasta, reps=3):
     print(json.dumps(dict(workload=name, cells=len(clusters), loci=p.n_loci, entries=p.n_entries,
                           chromosomes=p.n_chr, fasta_bytes=os.path.getsize(fasta), compress=OPTIONS["compress"],
                           fasta_route=fs["route"], fasta_kind=fs["kind"], fasta_text_bytes=fs["text_bytes"],
-                          records=len(recs),
+                          records=len(recs), vcf=vcf,
                           vcf_lines=n_lines, **med, kernel_ms_calls=round(kms, 3),
                           kernel_ms_lds_counters=modes["lds"], kernel_ms_global_counters=modes["global"], compulsory_bytes=by,
                           achieved_bytes_per_s=by / (med["kernel_ms"] * 1e-3),
@@ -244,12 +261,14 @@ if __name__ == "__main__":
     ap.add_argument("workloads", nargs="*", default=["C3", "whole"], help="C3, whole, fasta")
     ap.add_argument("--fasta_route", choices=["host", "device"], default=None)
     ap.add_argument("--compress", choices=["none", "gzip", "bgzf"], default="none")
+    ap.add_argument("--vcf_output", choices=["plain", "bgzf", "both"], default=None)
     ap.add_argument("--lib", default=None, help="another libsecedo_variant.so to load (A/B against a parent build)")
     args = ap.parse_args()
-    OPTIONS.update(fasta_route=args.fasta_route, compress=args.compress)
+    OPTIONS.update(fasta_route=args.fasta_route, compress=args.compress, vcf_output=args.vcf_output)
     if args.lib:
         variant.LIB_PATH = os.path.abspath(args.lib)
-        if not hasattr(__import__("ctypes").CDLL(variant.LIB_PATH), "secedo_variant_fasta_stats"):
-            for name in [n for n in variant.SIGNATURES if "fasta" in n or n.endswith("genotypes_device")]:
-                del variant.SIGNATURES[name]  # a build from before the device route
+        import torch  # noqa: F401  -- one HIP runtime per process: torch's, loaded first, as variant.lib() does
+        other = __import__("ctypes").CDLL(variant.LIB_PATH)
+        for name in [n for n in variant.SIGNATURES if not hasattr(other, n)]:
+            del variant.SIGNATURES[name]  # a build from before the FASTA device route or the bgzf output
     main(args.workloads)
