@@ -244,6 +244,61 @@ int secedo_variant_format_device(int device_id, const secedo_variant_record *rec
 int secedo_variant_bgzf_deflate(int device_id, const uint8_t *data, const uint64_t *data_off, uint32_t n_files,
                                 uint8_t *out, uint64_t capacity, uint64_t *out_off, void *stream);
 
+/* ---- The tabix index (.tbi) of a bgzip-compressed VCF -------------------------------------------------------------
+ *
+ * A region query (tabix file.vcf.gz 7:1000-2000, bcftools view -r) needs <file>.tbi beside the file. Two routes build
+ * it on the GPU with one line pass (tabix_kernels.hip) and one host builder (tabix_build.hpp):
+ *   the writer      under SECEDO_VCF_INDEX_TBI the BGZF output also leaves cluster_<i>.vcf.gz.tbi and
+ *                   common.vcf.gz.tbi: the line pass runs on the text where the formatter left it, the member table is
+ *                   the encoder's, and the index bodies are compressed by one more call of the encoder;
+ *   stand-alone     secedo_variant_tabix_build for files that exist: their compressed bytes are uploaded, inflated in
+ *                   HBM (ISIZE and CRC32 checked) and indexed; many small files go into one batch.
+ * Both give the same bytes for the same file. The setting is process-wide like the output: secedo_variant_set_vcf_index,
+ * else the environment SECEDO_VCF_INDEX=none|tbi (unset or empty: none; any other value is SECEDO_E_INVALID_ARG from the
+ * file-writing calls). TBI with SECEDO_VCF_PLAIN is SECEDO_E_INVALID_ARG: there is no index of plain text.
+ *
+ * The index: a data line is one whose first byte is not '#' and that is not empty. Its name is column 1, beg = POS - 1
+ * (0 for POS 0), end = beg + the length of REF, or the value of INFO's first END= key where that is a decimal number
+ * above beg; end > beg always. Bins and 16 kb windows as in a BAI (bins ascending, a chunk per run of consecutive data
+ * lines in one bin, the pseudo-bin 37450 last, the linear index filled backward); names in the order of their first line;
+ * small bins are not merged into their parents as newer htslib does, which readers accept alike. A chunk begins at its
+ * first line and ends where the next run's first line begins, the last one at the end of the data (the EOF member).
+ * A file without data lines has n_ref = 0. Refused with SECEDO_E_INVALID_ARG "<file>: line <n>: ...": a data line with
+ * fewer than two columns, a POS that is not a decimal number, an end past 2^29, a POS lower than that of the data line
+ * before it under the same name, a name that comes back after another one ("chromosome blocks not continuous"). */
+#define SECEDO_VCF_INDEX_NONE 0
+#define SECEDO_VCF_INDEX_TBI 1
+
+/* Process-wide. set: SECEDO_E_INVALID_ARG for another value; get: the kind set, else the environment's, else NONE
+ * (a negative SECEDO_E_* for an unknown value of SECEDO_VCF_INDEX). */
+int secedo_variant_set_vcf_index(int index);
+int secedo_variant_get_vcf_index(void);
+
+/* Indexes n bgzip-compressed VCF files: paths[f] gets paths[f] + ".tbi". A file that is plain gzip or not compressed
+ * is SECEDO_E_INVALID_ARG, as is an index that exists unless overwrite is non-zero. When a file fails, the files in
+ * front of it in `paths` keep their indexes. Sets secedo_variant_tabix_stats. Synchronises `stream`. */
+int secedo_variant_tabix_build(int device_id, const char *const *paths, uint32_t n, int overwrite, void *stream);
+
+/* What the last index-writing call of this thread did (the writer under TBI, or secedo_variant_tabix_build); all zero
+ * after a call that wrote no index. Times in ms, host wall clock. */
+typedef struct secedo_variant_tabix_info {
+    uint64_t files;             /* indexes written */
+    uint64_t lines;             /* lines of their texts, '#' lines and empty ones included */
+    uint64_t data_lines;
+    uint64_t names;             /* chromosome names, summed over the files */
+    uint64_t bins;              /* written, the pseudo-bins not counted */
+    uint64_t chunks;
+    uint64_t windows;           /* n_intv summed */
+    uint64_t ranges;            /* ranges the line pass walked the texts in */
+    uint64_t index_bytes;       /* the indexes before compression */
+    uint64_t compressed_bytes;  /* the .tbi files */
+    double pass_ms;             /* the line pass: kernels, scans, the downloads of heads, windows and names */
+    double build_ms;            /* the host builder */
+    double deflate_ms;          /* the index bodies through the encoder */
+    double write_ms;            /* the .tbi files */
+} secedo_variant_tabix_info;
+int secedo_variant_tabix_stats(secedo_variant_tabix_info *out);
+
 /* The drop-in: variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir)
  * on a host flat pileup. Writes cluster_<i>.vcf for i = 0..max(clusters), common.vcf, an empty `variant` and
  * `scores` under out_dir (created), as the reference does (the .vcf files as .vcf.gz under SECEDO_VCF_BGZF, above);

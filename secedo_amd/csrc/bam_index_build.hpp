@@ -100,57 +100,93 @@ public:
     std::string add_window(const Window &w) {
         if (w.ref < 0 || uint32_t(w.ref) >= refs_.size()) return "a window of a RefID outside the reference list";
         if (w.w >= kMaxWindows) return "a window past 2^29";
-        if (w.start == 0) return "a window at virtual offset 0";
+        if (w.start == 0 && !zero_ok_) return "a window at virtual offset 0";
+        if (w.start == UINT64_MAX) return "a window at the last virtual offset";
+        // held as offset + 1: 0 is an untouched window
         std::vector<uint64_t> &lin = refs_[w.ref].linear;
         if (lin.size() <= w.w) lin.resize(size_t(w.w) + 1, 0);
-        if (lin[w.w] == 0 || w.start < lin[w.w]) lin[w.w] = w.start;
+        if (lin[w.w] == 0 || w.start + 1 < lin[w.w]) lin[w.w] = w.start + 1;
         return std::string();
     }
 
+    // One more reference behind the last (a reader that meets its names as it goes: tabix_build.hpp) -> its number.
+    uint32_t add_ref() {
+        refs_.emplace_back();
+        return uint32_t(refs_.size() - 1);
+    }
+    uint32_t n_ref() const { return uint32_t(refs_.size()); }
+    // A text file's first line may lie at virtual offset 0; a BAM's first record never does, and there a window at 0
+    // stays refused.
+    void allow_offset_zero() { zero_ok_ = true; }
+
+    // Ends the run under way. end: the virtual offset behind the last record; n_records: the file's.
+    std::string close_runs(uint64_t end, uint64_t n_records) {
+        if (!open_) return std::string();
+        if (n_records <= ord_) return "fewer records than the last head's ordinal";
+        if (end < start_) return "the end lies before the last head";
+        count(n_records - ord_);
+        close(end);
+        open_ = false;
+        return std::string();
+    }
+
+    // After close_runs: the body of reference `ref` (n_bin, the bins, n_intv, the windows) appended to *out. A BAI and
+    // a TBI hold the same body behind different headers.
+    std::string append_ref(uint32_t ref, std::vector<uint8_t> *out) {
+        if (ref >= refs_.size()) return "a RefID outside the reference list";
+        Ref &r = refs_[ref];
+        if (r.chunks.empty() && !r.linear.empty()) return "windows of a reference without records";
+        // file order within a bin: the sort is stable
+        std::stable_sort(r.chunks.begin(), r.chunks.end(), [](const Chunk &a, const Chunk &b) { return a.bin < b.bin; });
+        uint32_t n_bin = 0;
+        for (size_t c = 0; c < r.chunks.size(); ++c) n_bin += c == 0 || r.chunks[c].bin != r.chunks[c - 1].bin;
+        stats_.bins += n_bin;
+        stats_.chunks += r.chunks.size();
+        put32(out, n_bin + (r.chunks.empty() ? 0 : 1));
+        for (size_t c = 0; c < r.chunks.size();) {
+            size_t e = c;
+            while (e < r.chunks.size() && r.chunks[e].bin == r.chunks[c].bin) ++e;
+            put32(out, r.chunks[c].bin);
+            put32(out, uint32_t(e - c));
+            for (; c < e; ++c) put64(out, r.chunks[c].beg), put64(out, r.chunks[c].end);
+        }
+        if (!r.chunks.empty()) {
+            put32(out, kPseudoBin);
+            put32(out, 2);
+            put64(out, r.first), put64(out, r.last);
+            put64(out, r.mapped), put64(out, r.unmapped);
+        }
+        for (size_t w = r.linear.size(); w-- > 1;)
+            if (r.linear[w - 1] == 0) r.linear[w - 1] = r.linear[w];
+        stats_.windows += r.linear.size();
+        put32(out, uint32_t(r.linear.size()));
+        for (const uint64_t v : r.linear) put64(out, v - 1);
+        return std::string();
+    }
+    const Stats &stats() const { return stats_; }
+
     // end: the virtual offset behind the last record; n_records: the file's. The index bytes to *out.
     std::string finish(uint64_t end, uint64_t n_records, std::vector<uint8_t> *out, Stats *stats) {
-        if (open_) {
-            if (n_records <= ord_) return "fewer records than the last head's ordinal";
-            if (end < start_) return "the end lies before the last head";
-            count(n_records - ord_);
-            close(end);
-            open_ = false;
-        }
+        const std::string why = close_runs(end, n_records);
+        if (!why.empty()) return why;
         out->clear();
         put(out, "BAI\1", 4);
         put32(out, uint32_t(refs_.size()));
-        for (Ref &r : refs_) {
-            if (r.chunks.empty() && !r.linear.empty()) return "windows of a reference without records";
-            // file order within a bin: the sort is stable
-            std::stable_sort(r.chunks.begin(), r.chunks.end(), [](const Chunk &a, const Chunk &b) { return a.bin < b.bin; });
-            uint32_t n_bin = 0;
-            for (size_t c = 0; c < r.chunks.size(); ++c) n_bin += c == 0 || r.chunks[c].bin != r.chunks[c - 1].bin;
-            stats_.bins += n_bin;
-            stats_.chunks += r.chunks.size();
-            put32(out, n_bin + (r.chunks.empty() ? 0 : 1));
-            for (size_t c = 0; c < r.chunks.size();) {
-                size_t e = c;
-                while (e < r.chunks.size() && r.chunks[e].bin == r.chunks[c].bin) ++e;
-                put32(out, r.chunks[c].bin);
-                put32(out, uint32_t(e - c));
-                for (; c < e; ++c) put64(out, r.chunks[c].beg), put64(out, r.chunks[c].end);
-            }
-            if (!r.chunks.empty()) {
-                put32(out, kPseudoBin);
-                put32(out, 2);
-                put64(out, r.first), put64(out, r.last);
-                put64(out, r.mapped), put64(out, r.unmapped);
-            }
-            for (size_t w = r.linear.size(); w-- > 1;)
-                if (r.linear[w - 1] == 0) r.linear[w - 1] = r.linear[w];
-            stats_.windows += r.linear.size();
-            put32(out, uint32_t(r.linear.size()));
-            for (const uint64_t v : r.linear) put64(out, v);
+        for (uint32_t r = 0; r < refs_.size(); ++r) {
+            const std::string bad = append_ref(r, out);
+            if (!bad.empty()) return bad;
         }
         put64(out, no_coor_);
         *stats = stats_;
         return std::string();
     }
+
+    static void put(std::vector<uint8_t> *out, const void *p, size_t n) {
+        const uint8_t *b = static_cast<const uint8_t *>(p);
+        out->insert(out->end(), b, b + n);
+    }
+    static void put32(std::vector<uint8_t> *out, uint32_t v) { put(out, &v, 4); }
+    static void put64(std::vector<uint8_t> *out, uint64_t v) { put(out, &v, 8); }
 
 private:
     struct Chunk {
@@ -162,13 +198,6 @@ private:
         std::vector<uint64_t> linear;
         uint64_t first = 0, last = 0, mapped = 0, unmapped = 0;
     };
-
-    static void put(std::vector<uint8_t> *out, const void *p, size_t n) {
-        const uint8_t *b = static_cast<const uint8_t *>(p);
-        out->insert(out->end(), b, b + n);
-    }
-    static void put32(std::vector<uint8_t> *out, uint32_t v) { put(out, &v, 4); }
-    static void put64(std::vector<uint8_t> *out, uint64_t v) { put(out, &v, 8); }
 
     // n more records of the run under way
     void count(uint64_t n) {
@@ -185,7 +214,7 @@ private:
     }
 
     std::vector<Ref> refs_;
-    bool open_ = false, unmapped_ = false;
+    bool open_ = false, unmapped_ = false, zero_ok_ = false;
     int32_t ref_ = -1;
     uint32_t bin_ = 0;
     uint64_t start_ = 0, ord_ = 0, no_coor_ = 0;

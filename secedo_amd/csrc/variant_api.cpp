@@ -13,6 +13,7 @@
 #include "host_util.hpp"
 #include "bgzf_deflate_kernels.hpp"
 #include "variant_kernels.hpp"
+#include "tabix_host.hpp"
 #include "vcf_output.hpp"
 
 #include <hip/hip_runtime.h>
@@ -482,6 +483,12 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
     int output = SECEDO_VCF_PLAIN;
     SECEDO_CALL(secedo::vcf::output_kind(&output));
     const bool bgzf = output == SECEDO_VCF_BGZF;  // the text is then made in HBM: locus_ref stays there too
+    int index = SECEDO_VCF_INDEX_NONE;
+    SECEDO_CALL(secedo::tabix_host::index_kind(&index));
+    secedo::tabix_host::info() = secedo_variant_tabix_info{};
+    if (index == SECEDO_VCF_INDEX_TBI && !bgzf)
+        return fail(SECEDO_E_INVALID_ARG, "vcf_index tbi indexes the compressed output only: add --vcf_output bgzf "
+                                          "(SECEDO_VCF=bgzf, secedo_variant_set_vcf_output)");
     std::vector<uint8_t> locus_ref(bgzf ? 0 : n_loci);
     std::vector<uint32_t> chr_end(n_chr);
     Buf b_ref, b_cl, b_mm, b_loci, b_pos;

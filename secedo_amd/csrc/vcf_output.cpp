@@ -6,6 +6,8 @@
 #include "bgzf_deflate.hpp"
 #include "bgzf_deflate_kernels.hpp"
 #include "host_util.hpp"
+#include "tabix_host.hpp"
+#include "tabix_kernels.hpp"
 #include "variant_kernels.hpp"
 
 #include <hip/hip_runtime.h>
@@ -264,7 +266,9 @@ int format_device(const std::vector<std::string> &pre, const secedo_variant_reco
 }
 
 int deflate_device(const uint8_t *d_text, const std::vector<uint64_t> &file_off, std::vector<uint8_t> *out,
-                   std::vector<uint64_t> *out_off, hipStream_t s) {
+                   std::vector<uint64_t> *out_off, hipStream_t s, MemberTable *table,
+                   secedo_variant_vcf_info *counts) {
+    secedo_variant_vcf_info &st = counts ? *counts : g_info;
     using namespace secedo::bgzf;
     const size_t n_files = file_off.size() - 1;
     // every member of every file, in file order; a file's last member is followed by the EOF member
@@ -294,8 +298,16 @@ int deflate_device(const uint8_t *d_text, const std::vector<uint64_t> &file_off,
     uint64_t end = 0;  // bytes of output laid out so far
     size_t file = 0;   // the file the next member belongs to
     uint32_t left = n_files ? members_of[0] : 0;
+    if (table) {
+        table->m.clear();
+        table->first.assign(n_files + 1, 0);
+    }
     const auto close_files = [&]() {  // files with no member left: their EOF member, the next file's start
         while (file < n_files && left == 0) {
+            if (table) {
+                table->m.push_back(bamindexbuild::Member{end - (*out_off)[file], file_off[file + 1] - file_off[file], 0});
+                table->first[file + 1] = table->m.size();
+            }
             out->resize(end + kEofBytes);
             for (uint32_t k = 0; k < kEofBytes; ++k) (*out)[end + k] = uint8_t(eof_member_byte(k));
             end += kEofBytes;
@@ -315,26 +327,29 @@ int deflate_device(const uint8_t *d_text, const std::vector<uint64_t> &file_off,
         SECEDO_TRY(hipStreamSynchronize(s));
         float k_ms = 0;
         SECEDO_TRY(hipEventElapsedTime(&k_ms, ev.a, ev.b));
-        g_info.deflate_kernel_ms += k_ms;
+        st.deflate_kernel_ms += k_ms;
         // where each member goes: behind the one before, EOF members in between
         const uint64_t first = end;
         for (uint32_t k = 0; k < nb; ++k) {
             const uint32_t bytes = size[k] & ~kDeflateStoredFlag;
             if (bytes < kHeaderBytes + kTrailerBytes || bytes > kMaxMember)
                 return fail(SECEDO_E_STATE, "BGZF encoder: a member of " + std::to_string(bytes) + " bytes");
-            g_info.stored_blocks += (size[k] & kDeflateStoredFlag) != 0;
+            st.stored_blocks += (size[k] & kDeflateStoredFlag) != 0;
+            if (table)
+                table->m.push_back(bamindexbuild::Member{end - (*out_off)[file], desc[b0 + k].in_off - file_off[file],
+                                                         desc[b0 + k].n});
             at[k] = end - first;
             end += bytes;
             --left;
             out->resize(end);
             close_files();
         }
-        g_info.blocks += nb;
+        st.blocks += nb;
         SECEDO_TRY(b_packed.alloc(end - first));
         SECEDO_TRY(hipMemcpyAsync(b_at.p, at.data(), nb * 8, hipMemcpyHostToDevice, s));
         SECEDO_TRY(bgzf_pack(b_slots.as<uint8_t>(), b_size.as<uint32_t>(), b_at.as<uint64_t>(), nb, b_packed.as<uint8_t>(), s));
         SECEDO_TRY(hipStreamSynchronize(s));
-        g_info.deflate_ms += ms_lap(t0);
+        st.deflate_ms += ms_lap(t0);
         // one download; the EOF members laid out among these bytes are put back over what came down in their place
         SECEDO_TRY(hipMemcpyAsync(out->data() + first, b_packed.p, end - first, hipMemcpyDeviceToHost, s));
         SECEDO_TRY(hipStreamSynchronize(s));
@@ -343,9 +358,9 @@ int deflate_device(const uint8_t *d_text, const std::vector<uint64_t> &file_off,
             if (e < first + kEofBytes || e > end) continue;
             for (uint32_t k = 0; k < kEofBytes; ++k) (*out)[e - kEofBytes + k] = uint8_t(eof_member_byte(k));
         }
-        g_info.download_ms += ms_lap(t0);
+        st.download_ms += ms_lap(t0);
     }
-    g_info.compressed_bytes += end;
+    st.compressed_bytes += end;
     return SECEDO_OK;
 }
 
@@ -362,17 +377,36 @@ int write_outputs_bgzf(const std::filesystem::path &out_dir, const std::string &
     g_info.files = uint64_t(num_clusters) + 1;
     g_info.text_bytes = text.file_off.back();
     g_info.format_ms = ms_lap(t0);
+    int index = SECEDO_VCF_INDEX_NONE;
+    SECEDO_CALL(tabix_host::index_kind(&index));
+    const bool tbi = index == SECEDO_VCF_INDEX_TBI;
     std::vector<uint8_t> bytes;
     std::vector<uint64_t> off;
-    SECEDO_CALL(deflate_device(text.text(), text.file_off, &bytes, &off, s));
+    MemberTable table;
+    SECEDO_CALL(deflate_device(text.text(), text.file_off, &bytes, &off, s, tbi ? &table : nullptr));
     (void)ms_lap(t0);
+    std::vector<std::string> names(size_t(num_clusters) + 1);
     for (uint32_t i = 0; i <= num_clusters; ++i) {
-        const std::string name = i < num_clusters ? "cluster_" + std::to_string(i) + ".vcf.gz" : "common.vcf.gz";
-        SECEDO_CALL(write_bytes(out_dir / name, bytes.data() + off[i], off[i + 1] - off[i]));
+        names[i] = i < num_clusters ? "cluster_" + std::to_string(i) + ".vcf.gz" : "common.vcf.gz";
+        SECEDO_CALL(write_bytes(out_dir / names[i], bytes.data() + off[i], off[i + 1] - off[i]));
     }
     SECEDO_CALL(write_variant_and_scores(out_dir, mismatch, loci));
     g_info.write_ms = ms_lap(t0);
-    return SECEDO_OK;
+    if (!tbi) return SECEDO_OK;
+    // the indexes: the line pass over the text where the formatter left it, the members as the encoder laid them out
+    static_assert(tabix::kTextSlack <= bgzf::kDeflateInSlack, "the line pass reads within the encoder's slack");
+    std::vector<tabix_host::IndexedFile> files(names.size());
+    std::vector<std::string> paths(names.size());
+    for (size_t i = 0; i < names.size(); ++i) {
+        files[i].label = (out_dir / names[i]).string();
+        files[i].members.assign(table.m.begin() + table.first[i], table.m.begin() + table.first[i + 1]);
+        files[i].file_bytes = off[i + 1] - off[i];
+        paths[i] = files[i].label + ".tbi";
+    }
+    std::vector<std::vector<uint8_t>> raw;
+    size_t n_good = 0;
+    SECEDO_CALL(tabix_host::build_raw(text.text(), text.file_off, files, &raw, &n_good, s));
+    return tabix_host::compress_and_write(raw, n_good, paths, s);
 }
 
 }  // namespace vcf

@@ -2,9 +2,11 @@
 // (variant_calling.cpp:226-321, :395-442), `variant` and `scores`, by two routes. PLAIN builds the text on the host
 // from downloaded records and writes cluster_<i>.vcf / common.vcf. BGZF formats the same text in HBM from the records
 // where write_calls left them (variant_kernels.hip), deflates it there (bgzf_deflate_kernels.hip) and writes
-// cluster_<i>.vcf.gz / common.vcf.gz; only compressed bytes come to the host. Internal to libsecedo_variant.so.
+// cluster_<i>.vcf.gz / common.vcf.gz; only compressed bytes come to the host. Under SECEDO_VCF_INDEX_TBI the BGZF route
+// also writes <file>.tbi beside each (tabix_host.hpp). Internal to libsecedo_variant.so.
 #pragma once
 
+#include "bam_index_build.hpp"  // Member: a BGZF member for virtual offsets
 #include "secedo_variant.h"
 
 #include <hip/hip_runtime_api.h>
@@ -55,9 +57,17 @@ int format_device(const std::vector<std::string> &preambles, const secedo_varian
 
 // The encoder alone: every file [file_off[f], file_off[f + 1]) of d_text (kDeflateInSlack readable bytes before and
 // after the whole) cut into members of at most 0xFF00 bytes, deflated, and closed with the EOF member. *out receives
-// the BGZF files back to back, out_off[files + 1] their bounds. Adds to info(). Synchronises s.
+// the BGZF files back to back, out_off[files + 1] their bounds. Adds to info(), or to *counts where that is given (the
+// index bodies are not VCF files). Synchronises s. *table (may be null)
+// receives what was laid out: the members of file f are m[first[f], first[f + 1]), the EOF member last, each with its
+// byte in the file and the text bytes of the file it holds.
+struct MemberTable {
+    std::vector<bamindexbuild::Member> m;
+    std::vector<size_t> first;  // [files + 1]
+};
 int deflate_device(const uint8_t *d_text, const std::vector<uint64_t> &file_off, std::vector<uint8_t> *out,
-                   std::vector<uint64_t> *out_off, hipStream_t s);
+                   std::vector<uint64_t> *out_off, hipStream_t s, MemberTable *table = nullptr,
+                   secedo_variant_vcf_info *counts = nullptr);
 
 // BGZF: everything under out_dir, the records and tables in HBM. Resets info(). Synchronises s.
 int write_outputs_bgzf(const std::filesystem::path &out_dir, const std::string &reference, uint32_t num_clusters,

@@ -10,7 +10,9 @@ errors (exit 1); --num_threads only sizes host pools (at most 16). --reference_g
 (BGZF) or plain gzip (.fa.gz works; the kind is told by content); --fasta_route host|device (default: the
 environment SECEDO_FASTA, else host) says where its parse and per-locus gather run, see secedo_amd/variant.py.
 --vcf_output plain|bgzf (default: the environment SECEDO_VCF, else plain) says whether the VCF files are written as
-text by the host or as bgzip-compressed .vcf.gz, formatted and deflated on the GPU.
+text by the host or as bgzip-compressed .vcf.gz, formatted and deflated on the GPU. --vcf_index none|tbi (default: the
+environment SECEDO_VCF_INDEX, else none) adds <file>.vcf.gz.tbi, the tabix index, beside each .vcf.gz; it needs
+--vcf_output bgzf.
 """
 from __future__ import annotations
 
@@ -49,6 +51,7 @@ FLAGS: Dict[str, Tuple[str, object]] = {
     "map_file": ("str", ""),
     "fasta_route": ("str", ""),
     "vcf_output": ("str", ""),
+    "vcf_index": ("str", ""),
     "clustering": ("str", ""),
     "compute_read_stats": ("bool", False),
     "num_threads": ("uint", 8),
@@ -72,7 +75,9 @@ def usage() -> str:
     lines += ["", "--reference_genome takes plain FASTA, bgzip (BGZF) or plain gzip: genome.fa.gz works as it is.",
               "--fasta_route host|device: where the FASTA is parsed (default: SECEDO_FASTA, else host; BGZF: device).",
               "--vcf_output plain|bgzf: cluster_<i>.vcf / common.vcf as text, or as .vcf.gz compressed on the GPU "
-              "(default: SECEDO_VCF, else plain)."]
+              "(default: SECEDO_VCF, else plain).",
+              "--vcf_index none|tbi: with --vcf_output bgzf, a tabix index <file>.vcf.gz.tbi beside each file "
+              "(default: SECEDO_VCF_INDEX, else none)."]
     return "\n".join(lines)
 
 
@@ -145,6 +150,10 @@ def validate(f: Flags) -> None:
         raise UsageError("Invalid value for --fasta_route: %s.\nShould be one of host, device" % f.fasta_route)
     if f.vcf_output not in ("", "plain", "bgzf"):
         raise UsageError("Invalid value for --vcf_output: %s.\nShould be one of plain, bgzf" % f.vcf_output)
+    if f.vcf_index not in ("", "none", "tbi"):
+        raise UsageError("Invalid value for --vcf_index: %s.\nShould be one of none, tbi" % f.vcf_index)
+    if f.vcf_index == "tbi" and (f.vcf_output or os.environ.get("SECEDO_VCF") or "plain") != "bgzf":
+        raise UsageError("--vcf_index tbi indexes the compressed output only: add --vcf_output bgzf")
     if not 1 <= f.tumor_purity <= 5:
         raise UsageError("Invalid value for --tumor_purity: %d.\nShould be 1,2,3,4, or 5" % f.tumor_purity)
     if f.arma_kmeans and f.clustering_type != "FIEDLER":
@@ -331,7 +340,7 @@ def run(plan: Plan) -> int:
     from . import SimilarityMatrixPlan
     from .cluster import divide_cluster_resident
     from .pileup_reader import get_grouping
-    from .variant import fasta_stats, variant_calling_resident, vcf_stats
+    from .variant import fasta_stats, tabix_stats, variant_calling_resident, vcf_stats
 
     f = plan.flags
     t0 = time.perf_counter()
@@ -378,7 +387,7 @@ def run(plan: Plan) -> int:
             _log(f, "Performing variant calling against %s" % f.reference_genome)
             vc_times = variant_calling_resident(sm, res, clusters, f.reference_genome, f.map_file, 1e-3,
                                                 f.seq_error_rate, f.o, fasta_route=f.fasta_route or None,
-                                                vcf_output=f.vcf_output or None)
+                                                vcf_output=f.vcf_output or None, vcf_index=f.vcf_index or None)
             fs = fasta_stats()
             vc_times["fasta"] = "%s on %s" % (fs["kind"], fs["route"])
             if fs["route"] == "device":  # the device route's split; the three overlap
@@ -391,6 +400,12 @@ def run(plan: Plan) -> int:
                     vs["compressed_bytes"], vs["blocks"], vs["stored_blocks"])
                 vc_times.update(vcf_format_ms=vs["format_ms"], vcf_deflate_ms=vs["deflate_ms"],
                                 vcf_download_ms=vs["download_ms"], vcf_write_ms=vs["write_ms"])
+            ts = tabix_stats()
+            if ts["files"]:
+                vc_times["tbi"] = "%d files, %d data lines, %d chunks, %d bytes in %d" % (
+                    ts["files"], ts["data_lines"], ts["chunks"], ts["index_bytes"], ts["compressed_bytes"])
+                vc_times.update(tbi_pass_ms=ts["pass_ms"], tbi_build_ms=ts["build_ms"],
+                                tbi_deflate_ms=ts["deflate_ms"], tbi_write_ms=ts["write_ms"])
         else:
             _log(f, "Skipping variant calling, because no reference genome was provided")
         t_end = time.perf_counter()

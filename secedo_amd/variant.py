@@ -17,6 +17,12 @@ The VCF files are plain text written by the host by default. ``set_vcf_output("b
 members and deflated there (secedo_amd/csrc/bgzf_deflate_kernels.hip), and only compressed bytes come back. Each file
 inflates to the bytes the plain route writes. ``vcf_stats()`` says what the last call wrote; ``bgzf_deflate`` is the
 encoder alone, the mirror of ``secedo_amd.bgzf_inflate``.
+
+``set_vcf_index("tbi")``, the environment ``SECEDO_VCF_INDEX=tbi`` or the ``vcf_index`` keyword of the calling
+functions make the bgzf output also write ``<file>.vcf.gz.tbi``, the tabix index region queries need, from a line pass
+over the text where the formatter left it (secedo_amd/csrc/tabix_kernels.hip). ``tabix_build(files)`` indexes
+bgzip-compressed VCFs that exist: their compressed bytes are inflated and indexed on the GPU, many small files to a
+batch. Both give the same bytes for the same file; ``tabix_stats()`` says what the last of either did.
 """
 from __future__ import annotations
 
@@ -66,8 +72,16 @@ class VcfInfo(C.Structure):
                 ("write_ms", C.c_double), ("deflate_kernel_ms", C.c_double)]
 
 
+class TabixInfo(C.Structure):
+    _fields_ = [("files", C.c_uint64), ("lines", C.c_uint64), ("data_lines", C.c_uint64), ("names", C.c_uint64),
+                ("bins", C.c_uint64), ("chunks", C.c_uint64), ("windows", C.c_uint64), ("ranges", C.c_uint64),
+                ("index_bytes", C.c_uint64), ("compressed_bytes", C.c_uint64), ("pass_ms", C.c_double),
+                ("build_ms", C.c_double), ("deflate_ms", C.c_double), ("write_ms", C.c_double)]
+
+
 FASTA_ROUTES = ("host", "device")
 VCF_OUTPUTS = ("plain", "bgzf")
+VCF_INDEXES = ("none", "tbi")
 BGZF_CUT = 0xFF00  # text bytes per BGZF member at the most
 FASTA_KINDS = ("text", "bgzf", "gzip")
 
@@ -86,6 +100,10 @@ SIGNATURES = {
     "secedo_variant_set_vcf_output": (C.c_int, [C.c_int]),
     "secedo_variant_get_vcf_output": (C.c_int, []),
     "secedo_variant_vcf_stats": (C.c_int, [C.POINTER(VcfInfo)]),
+    "secedo_variant_set_vcf_index": (C.c_int, [C.c_int]),
+    "secedo_variant_get_vcf_index": (C.c_int, []),
+    "secedo_variant_tabix_build": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_int, _vp]),
+    "secedo_variant_tabix_stats": (C.c_int, [C.POINTER(TabixInfo)]),
     "secedo_variant_format_host": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32,
                                              C.c_char_p, _vp, _vp, C.c_uint64, _vp]),
     "secedo_variant_format_device": (C.c_int, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32,
@@ -203,6 +221,56 @@ def _output(output):
         yield
     finally:
         set_vcf_output(before)
+
+
+def set_vcf_index(index):
+    """The process-wide index of the bgzf VCF output: "none", or "tbi" (<file>.vcf.gz.tbi beside each file, built on
+    the GPU; see the module docstring). "tbi" with plain output makes the file-writing calls fail."""
+    if index not in VCF_INDEXES:
+        raise ValueError("vcf index must be 'none' or 'tbi', not %r" % (index,))
+    check(lib().secedo_variant_set_vcf_index(VCF_INDEXES.index(index)))
+
+
+def get_vcf_index() -> str:
+    rc = lib().secedo_variant_get_vcf_index()
+    if rc < 0:
+        check(rc)
+    return VCF_INDEXES[rc]
+
+
+@contextlib.contextmanager
+def _index(index):
+    """A scoped override of the VCF index, as _route is of the FASTA route."""
+    if index is None:
+        yield
+        return
+    before = get_vcf_index()
+    set_vcf_index(index)
+    try:
+        yield
+    finally:
+        set_vcf_index(before)
+
+
+def tabix_stats() -> dict:
+    """What the last index-writing call of this thread did (secedo_variant_tabix_info): a file-writing call under
+    "tbi", or tabix_build. All zero after a call that wrote no index."""
+    info = TabixInfo()
+    check(lib().secedo_variant_tabix_stats(C.byref(info)))
+    return {name: getattr(info, name) for name, _ in TabixInfo._fields_}
+
+
+def tabix_build(files, overwrite=False, device=0) -> dict:
+    """<file>.tbi for every bgzip-compressed VCF of `files` (a path or a list of paths), built on the GPU: the
+    compressed bytes are uploaded, inflated there (ISIZE and CRC32 checked) and indexed, many small files to a batch.
+    An index that exists is an error unless overwrite; when a file fails, the files in front of it keep their indexes.
+    -> tabix_stats()."""
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    paths = [_b(f) for f in files]
+    arr = (C.c_char_p * max(len(paths), 1))(*paths)
+    check(lib().secedo_variant_tabix_build(device, arr, len(paths), int(bool(overwrite)), _stream(device)))
+    return tabix_stats()
 
 
 def vcf_stats() -> dict:
@@ -427,15 +495,16 @@ def _times(t):
 
 
 def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                    out_dir="variant_calling", device=0, fasta_route=None, vcf_output=None):
+                    out_dir="variant_calling", device=0, fasta_route=None, vcf_output=None, vcf_index=None):
     """variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir): writes
     cluster_<i>.vcf, common.vcf, variant and scores under out_dir as the reference does. fasta_route ("host",
     "device"; None: the setting) overrides the FASTA route for this call, vcf_output ("plain", "bgzf"; None: the
-    setting) the kind of VCF files. -> step times (ms)."""
+    setting) the kind of VCF files, vcf_index ("none", "tbi"; None: the setting) whether the bgzf files get a tabix
+    index. -> step times (ms)."""
     p, b16, b32 = _flat(pos_data)
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     t = Times()
-    with _route(fasta_route), _output(vcf_output):
+    with _route(fasta_route), _output(vcf_output), _index(vcf_index):
         check(lib().secedo_variant_calling(device, _lib.ptr(p.chr_locus_off), p.n_chr, _lib.ptr(p.locus_pos),
                                            _lib.ptr(p.locus_entry_off), _lib.ptr(b16), _lib.ptr(b32), _lib.ptr(cl),
                                            len(cl), _b(reference_genome), _b(map_file), hetero_prior, theta,
@@ -444,13 +513,14 @@ def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_pr
 
 
 def variant_calling_resident(plan, res, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                             out_dir="variant_calling", fasta_route=None, vcf_output=None):
+                             out_dir="variant_calling", fasta_route=None, vcf_output=None, vcf_index=None):
     """variant_calling on the pileup `res` resident in HBM (SimilarityMatrixPlan.upload, as divide_cluster_resident
-    takes it), in the plan's current stream. fasta_route and vcf_output as in variant_calling. -> step times (ms)."""
+    takes it), in the plan's current stream. fasta_route, vcf_output and vcf_index as in variant_calling. -> step times
+    (ms)."""
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     idb = C.c_void_p(res["idb"].data_ptr())
     t = Times()
-    with _route(fasta_route), _output(vcf_output):
+    with _route(fasta_route), _output(vcf_output), _index(vcf_index):
         check(lib().secedo_variant_calling_device(
             plan.device, C.c_void_p(res["chr"].data_ptr()), res["n_chr"], C.c_void_p(res["pos"].data_ptr()),
             C.c_void_p(res["off"].data_ptr()), idb if res["idb_is16"] else None, None if res["idb_is16"] else idb,

@@ -17,7 +17,9 @@ workload:
 (an A/B against the parent commit; one without the device entry point runs `fasta` on the host function).
 --vcf_output plain|bgzf|both picks the kind of VCF files (default: the library's setting); `both` measures the two on
 the same data, one JSON line each, with the bgzf route's format / deflate / download / write split, its compressed
-size and the encoder kernel's time.
+size and the encoder kernel's time. --vcf_index tbi (with the bgzf output) also writes the tabix indexes: the line adds
+the index's pass / build / deflate / write split and the time of `tabix_build` on the same .vcf.gz files; `both`
+measures the bgzf output without and with the index on the same data.
 
 Each line: the two kernels (device events), the end-to-end call split into FASTA parse / gather / device (uploads,
 kernels, downloads) / write, and the achieved bytes/s of the kernels against the HBM peak (8 TB/s spec, 6.3
@@ -97,7 +99,7 @@ def compress_file(path, how):
         f.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
 
 
-OPTIONS = dict(fasta_route=None, compress="none", vcf_output=None)
+OPTIONS = dict(fasta_route=None, compress="none", vcf_output=None, vcf_index=None, reps=None)
 
 
 def compulsory_bytes(p, n_groups, idb_bytes):
@@ -106,14 +108,19 @@ def compulsory_bytes(p, n_groups, idb_bytes):
 
 
 def run(name, p, clusters, fasta, reps=3):
+    reps = OPTIONS["reps"] or reps
     outputs = ["plain", "bgzf"] if OPTIONS["vcf_output"] == "both" else [OPTIONS["vcf_output"]]
     for output in outputs:
-        run_one(name, p, clusters, fasta, reps, output)
+        for index in (["none", "tbi"] if OPTIONS["vcf_index"] == "both" and output == "bgzf" else [OPTIONS["vcf_index"]]):
+            run_one(name, p, clusters, fasta, reps, output, index)
 
 
-def run_one(name, p, clusters, fasta, reps, output):
+def run_one(name, p, clusters, fasta, reps, output, index):
     out = tempfile.mkdtemp(prefix="vc_bench_")
     kw = {} if output is None else dict(vcf_output=output)  # a parent build's variant.py has no such keyword
+    tbi = index == "tbi" and output == "bgzf"
+    if tbi:
+        kw["vcf_index"] = "tbi"
     has_vcf = hasattr(variant, "vcf_stats") and hasattr(variant.lib(), "secedo_variant_vcf_stats")
     try:
         route = OPTIONS["fasta_route"]
@@ -130,6 +137,9 @@ def run_one(name, p, clusters, fasta, reps, output):
                   dict(route="host", kind="text", text_bytes=0, inflate_ms=0.0, upload_ms=0.0, parse_gather_ms=0.0))
             t.update(fasta_inflate_ms=fs["inflate_ms"], fasta_upload_ms=fs["upload_ms"],
                      fasta_parse_gather_ms=fs["parse_gather_ms"])
+            if tbi:
+                ts = variant.tabix_stats()
+                t.update({"tbi_" + k: float(ts[k]) for k in ("pass_ms", "build_ms", "deflate_ms", "write_ms")})
             runs.append(t)
         med = {k: round(float(np.median([r[k] for r in runs])), 3) for k in runs[0]}
         n_lines = sum(1 for f in os.listdir(out) if f.endswith((".vcf", ".vcf.gz"))
@@ -137,6 +147,17 @@ def run_one(name, p, clusters, fasta, reps, output):
                       if line[:1] != b"#")
         vcf = {k: vs[k] for k in ("output", "files", "text_bytes", "compressed_bytes", "blocks", "stored_blocks")
                if k in vs}
+        if tbi:  # the index of the same files by the stand-alone route
+            vcf["tbi"] = {k: ts[k] for k in ("files", "lines", "data_lines", "names", "bins", "chunks", "windows",
+                                             "ranges", "index_bytes", "compressed_bytes")}
+            gz = sorted(os.path.join(out, f) for f in os.listdir(out) if f.endswith(".vcf.gz"))
+            alone = []
+            for _ in range(reps + 1):
+                t0 = time.perf_counter()
+                variant.tabix_build(gz, overwrite=True)
+                alone.append((time.perf_counter() - t0) * 1e3)
+            med["tabix_build_ms"] = round(float(np.median(alone[1:])), 3)
+        med["all_total_ms"] = [round(r["total_ms"], 2) for r in runs]
         recs, _, _, kms = variant.variant_calls(p, clusters, fasta, with_kernel_ms=True)
         modes = {}
         for mode in ("lds", "global"):  # the counted-entry counters: LDS-privatised vs global atomics
@@ -152,7 +173,7 @@ def run_one(name, p, clusters, fasta, reps, output):
     print(json.dumps(dict(workload=name, cells=len(clusters), loci=p.n_loci, entries=p.n_entries,
                           chromosomes=p.n_chr, fasta_bytes=os.path.getsize(fasta), compress=OPTIONS["compress"],
                           fasta_route=fs["route"], fasta_kind=fs["kind"], fasta_text_bytes=fs["text_bytes"],
-                          records=len(recs), vcf=vcf,
+                          records=len(recs), vcf=vcf, vcf_index="tbi" if tbi else "none",
                           vcf_lines=n_lines, **med, kernel_ms_calls=round(kms, 3),
                           kernel_ms_lds_counters=modes["lds"], kernel_ms_global_counters=modes["global"], compulsory_bytes=by,
                           achieved_bytes_per_s=by / (med["kernel_ms"] * 1e-3),
@@ -262,9 +283,12 @@ if __name__ == "__main__":
     ap.add_argument("--fasta_route", choices=["host", "device"], default=None)
     ap.add_argument("--compress", choices=["none", "gzip", "bgzf"], default="none")
     ap.add_argument("--vcf_output", choices=["plain", "bgzf", "both"], default=None)
+    ap.add_argument("--vcf_index", choices=["none", "tbi", "both"], default=None)
+    ap.add_argument("--reps", type=int, default=None, help="timed calls per workload (default: C3 3, whole 2)")
     ap.add_argument("--lib", default=None, help="another libsecedo_variant.so to load (A/B against a parent build)")
     args = ap.parse_args()
-    OPTIONS.update(fasta_route=args.fasta_route, compress=args.compress, vcf_output=args.vcf_output)
+    OPTIONS.update(fasta_route=args.fasta_route, compress=args.compress, vcf_output=args.vcf_output,
+                   vcf_index=args.vcf_index, reps=args.reps)
     if args.lib:
         variant.LIB_PATH = os.path.abspath(args.lib)
         import torch  # noqa: F401  -- one HIP runtime per process: torch's, loaded first, as variant.lib() does
