@@ -25,7 +25,6 @@
 #include "bam_index_kernels.hpp"
 #include "bam_kernels.hpp"  // the scan wrappers
 #include "bam_walk_kernels.hpp"
-#include "bgzf_inflate.hpp"  // the status codes
 
 #include <unistd.h>
 
@@ -64,7 +63,6 @@ struct DevFile {
     // secedo_bam_index_build: the reference lengths are kept, and what the index takes from batch to batch
     bool want_refs = false;
     std::vector<uint32_t> l_ref;
-    std::vector<bamindexbuild::Member> members;
     std::unique_ptr<bamindexbuild::Builder> builder;
     std::string out_path;
     uint64_t device_bytes() const { return carry.size() + (hb < blocks.size() ? total - blocks[hb].out : 0); }
@@ -160,9 +158,8 @@ int open_file(size_t f, const std::string &path, size_t n_chr, DevFile *df) {
         const Block &b = df->blocks[df->hb];
         const size_t at = head.size();
         head.resize(at + b.isize);
-        const std::string err = inflate_block(b, head.data() + at);
-        if (!err.empty())
-            return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(df->hb) + ": " + err);
+        const std::string err = bm::inflate_member_zlib(df->m.p + b.payload(), b, head.data() + at);
+        if (!err.empty()) return bad_block(path, bm::block_where(df->hb), err);
         ++df->hb;
     }
     df->carry.assign(head.begin() + df->h.first_record, head.end());
@@ -205,11 +202,8 @@ int file_error(const BamDevWork &w, const Piece &p, const WalkFile &F) {
     }
     if (F.bad != ~0ull) {
         const uint64_t k = p.b0 + ((F.bad >> 8) - p.first_member);
-        return fail(SECEDO_E_INVALID_ARG,
-                    path + ": BGZF block " +
-                        (p.span ? "at byte " + std::to_string(p.span->blocks[k].coff) : std::to_string(k)) + ": " +
-                        (uint32_t(F.bad & 0xFF) == secedo::bgzf::kCrcMismatch ? "CRC32 mismatch"
-                                                                               : "inflate failed or ISIZE mismatch"));
+        return bad_block(path, p.span ? bm::block_where_byte(p.span->blocks[k].coff) : bm::block_where(k),
+                         bm::status_text(uint32_t(F.bad & 0xFF)));
     }
     return SECEDO_OK;
 }
@@ -277,7 +271,7 @@ int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch
         DevFile &df = *pieces[h.file].df;
         if (h.lin > df.total) return bad(df, "an offset past the file's bytes");
         const std::string why = df.builder->add_head(bamindexbuild::Head{
-            h.ref, h.bin, h.unmapped, bamindexbuild::voffset(df.members, df.total, df.m.n, h.lin), h.ord});
+            h.ref, h.bin, h.unmapped, bamindexbuild::voffset(df.blocks, df.total, df.m.n, h.lin), h.ord});
         if (!why.empty()) return bad(df, why);
     }
     for (const IndexWin &v : w->h_wins) {
@@ -285,7 +279,7 @@ int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch
         DevFile &df = *pieces[v.file].df;
         if (v.lin > df.total) return bad(df, "an offset past the file's bytes");
         const std::string why = df.builder->add_window(
-            bamindexbuild::Window{v.ref, v.w, bamindexbuild::voffset(df.members, df.total, df.m.n, v.lin)});
+            bamindexbuild::Window{v.ref, v.w, bamindexbuild::voffset(df.blocks, df.total, df.m.n, v.lin)});
         if (!why.empty()) return bad(df, why);
     }
     return SECEDO_OK;
@@ -337,21 +331,20 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
         uint64_t o = data_start + carry;
         if (p.b0 < p.b1) {
             const std::vector<Block> &bl = p.blocks();
-            const uint8_t *lo = bl[p.b0].cdata - kBgzfInSlack;  // a member's header is 18 bytes: inside the file
-            const uint8_t *pay_end = bl[p.b1 - 1].cdata + bl[p.b1 - 1].clen;
-            const uint8_t *hi = std::min(p.mapped().p + p.mapped().n, pay_end + kBgzfInSlack);
-            for (uint64_t c = 0; c < uint64_t(hi - lo); c += 4u << 20)
-                copies.push_back({in_pos + c, lo + c, std::min<uint64_t>(4u << 20, uint64_t(hi - lo) - c)});
+            const bm::PayloadSpan sp = bm::payload_span(bl, p.b0, p.b1, p.mapped().n);
+            const uint8_t *lo = p.mapped().p + sp.lo;
+            for (uint64_t c = 0; c < sp.hi - sp.lo; c += 4u << 20)
+                copies.push_back({in_pos + c, lo + c, std::min<uint64_t>(4u << 20, sp.hi - sp.lo - c)});
+            w->h_desc.resize(p.first_member + (p.b1 - p.b0));
+            bm::fill_desc(bl, p.b0, p.b1, sp.lo, in_pos, o, w->h_desc.data() + p.first_member);
             for (size_t b = p.b0; b < p.b1; ++b) {
-                w->h_desc.push_back(BgzfDesc{in_pos + uint64_t(bl[b].cdata - lo), o, bl[b].clen, bl[b].isize,
-                                             bl[b].crc, 0});
                 // a span is entered at its first record, a known record start
                 const uint64_t start = b != p.b0 ? o : data_start + (p.span && first_range ? p.span->entry : 0);
                 o += bl[b].isize;
                 w->h_segs.push_back(bw::Seg{uint32_t(start), uint32_t(o), k, uint32_t(n_list)});
                 n_list += bw::list_cap(uint32_t(o - start));
             }
-            in_pos += uint64_t(pay_end - lo) + kBgzfInSlack;
+            in_pos += sp.needed;
             F.n_seg = uint32_t(p.b1 - p.b0);
         }
         F.first_seg = p.first_member;
@@ -751,7 +744,7 @@ int write_renamed(const std::string &path, const std::vector<uint8_t> &bytes) {
 int finish_index(DevFile *df, secedo_bam_build_info *info) {
     std::vector<uint8_t> bytes;
     bamindexbuild::Stats st;
-    const std::string why = df->builder->finish(bamindexbuild::voffset(df->members, df->total, df->m.n, df->total),
+    const std::string why = df->builder->finish(bamindexbuild::voffset(df->blocks, df->total, df->m.n, df->total),
                                                 df->rec_base, &bytes, &st);
     if (!why.empty())
         return fail(SECEDO_E_STATE, df->path + ": the device index pass returned inconsistent results (" + why + ")");
@@ -779,8 +772,6 @@ int open_for_index(size_t f, const std::string &path, const std::string &out, in
             return fail(SECEDO_E_INVALID_ARG, path + ": reference " + std::to_string(r) + " is " +
                                                   std::to_string(df->l_ref[r]) +
                                                   " long, past 2^29: a BAI index cannot hold it");
-    df->members.reserve(df->blocks.size());
-    for (const Block &b : df->blocks) df->members.push_back(bamindexbuild::Member{b.coff, b.out, b.isize});
     df->builder.reset(new bamindexbuild::Builder(df->h.n_ref));
     return SECEDO_OK;
 }

@@ -2,6 +2,7 @@
 // into one ChrInput per requested chromosome, bam_pileup.cpp turns those into the pileup. Internal, nothing exported.
 #pragma once
 
+#include "bgzf_members.hpp"
 #include "host_util.hpp"
 #include "secedo_bam.h"
 
@@ -102,20 +103,21 @@ struct Mapped {
     }
 };
 
-struct Block {
-    const uint8_t *cdata;
-    uint32_t clen, crc, isize;
-    uint64_t out;  // offset in the file's inflated buffer (of an indexed file: in its span's)
-    uint64_t coff = 0;  // its byte in the file
-};
+// A BGZF block is a member of bgzf_members.hpp, which lists, describes and inflates them; these two put the file's
+// name in front of its reasons.
+namespace bm = secedo::bgzf_members;
+using Block = bm::Member;
+
+// "<path>: <bm::block_where*()>: <why>": the error of every route for a block that does not inflate
+inline int bad_block(const std::string &path, const std::string &where, const std::string &why) {
+    return fail(SECEDO_E_INVALID_ARG, path + ": " + where + ": " + why);
+}
 
 // the BGZF block at byte off < m.n of a mapped file (its `out` left 0); *len = its bytes in the file
 int read_block(const std::string &path, const Mapped &m, uint64_t off, Block *blk, uint32_t *len);
 
 // a file mapped and its BGZF blocks listed; *total = its inflated size
 int open_bgzf(const std::string &path, Mapped *m, std::vector<Block> *blocks, uint64_t *total);
-// zlib raw inflate of one block into dst[isize], ISIZE and CRC32 checked: empty on success, else the message's tail
-std::string inflate_block(const Block &b, uint8_t *dst);
 
 struct Header {
     uint32_t l_text = 0, n_ref = 0;

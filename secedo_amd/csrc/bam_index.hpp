@@ -8,6 +8,8 @@
 // A virtual offset is coffset << 16 | uoffset: the byte of a BGZF member in the file and a byte of its inflated data.
 #pragma once
 
+#include "bgzf_members.hpp"
+
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -34,7 +36,6 @@ inline std::string voffset_str(uint64_t v) { return std::to_string(coffset(v)) +
 namespace detail {
 inline uint32_t rd32(const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
 inline uint64_t rd64(const uint8_t *p) { uint64_t v; std::memcpy(&v, p, 8); return v; }
-inline uint32_t rd16(const uint8_t *p) { uint16_t v; std::memcpy(&v, p, 2); return v; }
 }  // namespace detail
 
 // The index in d[0, n): one RefRange per reference. Empty on success, else why the bytes are no index.
@@ -86,32 +87,10 @@ inline std::string parse(const uint8_t *d, uint64_t n, std::vector<RefRange> *ou
     return std::string();  // n_no_coor may follow
 }
 
-// What stands at byte off of the file bytes p[0, n): a BGZF member (its length in the file, its ISIZE and the length
-// of its extra field), or why not. The one parse of a member header: bam_input.cpp's read_block reports from it.
-enum Member { kMember = 0, kNoMember = 1, kBadBsize = 2, kBigIsize = 3 };
-inline Member member_header(const uint8_t *p, uint64_t n, uint64_t off, uint32_t *len, uint32_t *isize,
-                            uint32_t *xlen_out) {
-    using namespace detail;
-    if (off >= n || n - off < 18) return kNoMember;
-    const uint8_t *b = p + off;
-    if (b[0] != 31 || b[1] != 139 || b[2] != 8 || !(b[3] & 4)) return kNoMember;
-    const uint32_t xlen = rd16(b + 10);
-    uint32_t bsize = UINT32_MAX;
-    for (uint32_t x = 12; x + 4 <= 12 + xlen && 12 + uint64_t(xlen) <= n - off;) {
-        const uint32_t slen = rd16(b + x + 2);
-        if (b[x] == 'B' && b[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen) bsize = rd16(b + x + 4);
-        x += 4 + slen;
-    }
-    if (bsize == UINT32_MAX || uint64_t(bsize) + 1 > n - off || bsize + 1 < 12 + xlen + 8) return kBadBsize;
-    *len = bsize + 1;
-    *isize = rd32(b + *len - 4);
-    *xlen_out = xlen;
-    return *isize > 65536 ? kBigIsize : kMember;
-}
-
+// a BGZF member stands at byte off of p[0, n) (bgzf_members.hpp holds the one parse of a member's header)
 inline bool member_at(const uint8_t *p, uint64_t n, uint64_t off, uint32_t *len, uint32_t *isize) {
     uint32_t xlen = 0;
-    return member_header(p, n, off, len, isize, &xlen) == kMember;
+    return bgzf_members::member_header(p, n, off, len, isize, &xlen) == bgzf_members::kMember;
 }
 
 // The file-level checks of parsed ranges against the BAM they are said to index: n_ref, and for the start and the end

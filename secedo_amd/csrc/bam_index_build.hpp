@@ -16,6 +16,8 @@
 // Whatever it is fed, the builder answers with bytes or with a reason, never with a read or write out of bounds.
 #pragma once
 
+#include "bgzf_members.hpp"
+
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -221,11 +223,9 @@ private:
     Stats stats_;
 };
 
-// One BGZF member of the file for virtual offsets: its byte in the file and the inflated bytes [out, out + isize).
-struct Member {
-    uint64_t coff, out;
-    uint32_t isize;
-};
+// One BGZF member of the file: virtual offsets take its byte in the file and the inflated bytes [out, out + isize),
+// which are its first three fields. A reader's list goes in as it is; a writer gives Member{coff, out, isize}.
+using Member = bgzf_members::Member;
 
 // The virtual offset of inflated byte `lin` of a file of `file_bytes` bytes and `total` inflated bytes, lin <= total:
 // the first member that holds a byte at or past it; the end of the data names the first empty member behind it (the

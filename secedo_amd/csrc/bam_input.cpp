@@ -12,15 +12,13 @@
 // reads it, plan_index below turns it into spans of members, and only those are inflated and walked, on either route;
 // with or without an index the result is the same.
 // The opt-in device route for BAM (secedo_bam_set_inflate) branches off in load_inputs to bam_device_input.cpp; the
-// BGZF listing, the zlib inflate of one block and the header parse below are what the two routes share.
+// BGZF listing and the zlib inflate of one block (bgzf_members.hpp) and the header parse below are what the two routes
+// share.
 #include "bam_host.hpp"
 #include "bam_index.hpp"
 #include "bam_kernels.hpp"  // the scan wrappers
-#include "bgzf_inflate.hpp"  // the status codes
 #include "bgzf_kernels.hpp"
 #include "sam_kernels.hpp"
-
-#include <zlib.h>
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -43,14 +41,7 @@ namespace {
 constexpr uint64_t kBatchBytes = 512ull << 20;
 }
 
-uint64_t batch_bytes() {
-    const char *e = std::getenv("SECEDO_BAM_BATCH_BYTES");
-    if (e && *e) {
-        const unsigned long long v = std::strtoull(e, nullptr, 10);
-        if (v > 0) return v;
-    }
-    return kBatchBytes;
-}
+uint64_t batch_bytes() { return env_u64("SECEDO_BAM_BATCH_BYTES", kBatchBytes); }
 
 int map_file(const std::string &path, Mapped *m) {
     const int fd = open(path.c_str(), O_RDONLY);
@@ -73,56 +64,16 @@ int map_file(const std::string &path, Mapped *m) {
     return SECEDO_OK;
 }
 
-// the BGZF block at byte off < m.n of a mapped file (its `out` left 0); *len = its bytes in the file
 int read_block(const std::string &path, const Mapped &m, uint64_t off, Block *blk, uint32_t *len) {
-    uint32_t isize = 0, xlen = 0;
-    const bamindex::Member what = bamindex::member_header(m.p, m.n, off, len, &isize, &xlen);
-    if (what == bamindex::kNoMember)
-        return fail(SECEDO_E_INVALID_ARG, path + ": not a BGZF block at byte " + std::to_string(off));
-    if (what == bamindex::kBadBsize)
-        return fail(SECEDO_E_INVALID_ARG, path + ": bad BGZF block size at byte " + std::to_string(off));
-    if (what == bamindex::kBigIsize) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF ISIZE above 64 KiB");
-    const uint8_t *b = m.p + off;
-    *blk = Block{b + 12 + xlen, *len - xlen - 20, rd32(b + *len - 8), isize, 0, off};
-    return SECEDO_OK;
-}
-
-// BGZF block list of one mapped file
-int list_blocks(const std::string &path, const Mapped &m, std::vector<Block> *blocks, uint64_t *total) {
-    uint64_t off = 0, out = 0;
-    while (off < m.n) {
-        Block blk;
-        uint32_t len = 0;
-        SECEDO_CALL(read_block(path, m, off, &blk, &len));
-        blk.out = out;
-        blocks->push_back(blk);
-        out += blk.isize;
-        off += len;
-    }
-    *total = out;
-    return SECEDO_OK;
-}
-
-// 0 on success, else a message
-std::string inflate_block(const Block &b, uint8_t *dst) {
-    z_stream z{};
-    if (inflateInit2(&z, -15) != Z_OK) return "inflateInit2 failed";
-    z.next_in = const_cast<Bytef *>(b.cdata);
-    z.avail_in = b.clen;
-    z.next_out = dst;
-    z.avail_out = b.isize;
-    const int rc = inflate(&z, Z_FINISH);
-    const uint64_t got = z.total_out;
-    inflateEnd(&z);
-    if (rc != Z_STREAM_END || got != b.isize) return "inflate failed or ISIZE mismatch";
-    if (uint32_t(crc32(crc32(0, nullptr, 0), dst, b.isize)) != b.crc) return "CRC32 mismatch";
-    return std::string();
+    const std::string why = bm::read_member(m.p, m.n, off, blk, len);
+    return why.empty() ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, path + ": " + why);
 }
 
 // a file mapped and its BGZF blocks listed; *total = its inflated size
 int open_bgzf(const std::string &path, Mapped *m, std::vector<Block> *blocks, uint64_t *total) {
     SECEDO_CALL(map_file(path, m));
-    return list_blocks(path, *m, blocks, total);
+    const std::string why = bm::list_members(m->p, m->n, blocks, total);
+    return why.empty() ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, path + ": " + why);
 }
 
 // final: d ends the file, so a cut header is an error; else kNeedMore
@@ -155,25 +106,27 @@ using namespace secedo::bam_host;
 
 struct InflateJob {
     const std::string *path;
+    const uint8_t *file;  // the mapped file
     const Block *block;
     uint64_t index;  // of the block in its file (messages)
     uint8_t *dst;
     bool by_byte = false;  // an indexed file: the ordinal is unknown, the message names the block's byte
 };
 
-std::string block_where(const std::string &path, const InflateJob &j) {
-    if (j.by_byte) return path + ": BGZF block at byte " + std::to_string(j.block->coff);
-    return path + ": BGZF block " + std::to_string(j.index);
-}
-
 // the jobs in one pool; the first failed job in list order is the error
 int inflate_blocks(const std::vector<InflateJob> &jobs, uint32_t threads) {
     std::vector<std::string> errs(jobs.size());
-    parallel_for(threads, jobs.size(), [&](uint64_t k) { errs[k] = inflate_block(*jobs[k].block, jobs[k].dst); });
+    parallel_for(threads, jobs.size(), [&](uint64_t k) {
+        const InflateJob &j = jobs[k];
+        errs[k] = bm::inflate_member_zlib(j.file + j.block->payload(), *j.block, j.dst);
+    });
     route().host_blocks += jobs.size();
-    for (size_t k = 0; k < jobs.size(); ++k)
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        const InflateJob &j = jobs[k];
         if (!errs[k].empty())
-            return fail(SECEDO_E_INVALID_ARG, block_where(*jobs[k].path, jobs[k]) + ": " + errs[k]);
+            return bad_block(*j.path, j.by_byte ? bm::block_where_byte(j.block->coff)
+                                                : bm::block_where(j.index), errs[k]);
+    }
     return SECEDO_OK;
 }
 
@@ -196,7 +149,7 @@ int inflate_files(const std::vector<std::string> &paths, uint32_t threads, std::
         (*out)[f].data.resize(total);
         (*out)[f].n_blocks = blocks[f].size();
         for (size_t b = 0; b < blocks[f].size(); ++b)
-            jobs.push_back({&paths[f], &blocks[f][b], b, (*out)[f].data.data() + blocks[f][b].out});
+            jobs.push_back({&paths[f], maps[f].p, &blocks[f][b], b, (*out)[f].data.data() + blocks[f][b].out});
     }
     return inflate_blocks(jobs, threads);
 }
@@ -336,7 +289,7 @@ int load_file_ranges(size_t f, uint32_t threads, uint64_t batch, Inputs *in, Run
         buf.resize(carry + bytes);
         jobs.clear();
         for (size_t b = b0; b < b1; ++b)
-            jobs.push_back({&path, &blocks[b], b, buf.data() + carry + (blocks[b].out - blocks[b0].out)});
+            jobs.push_back({&path, m.p, &blocks[b], b, buf.data() + carry + (blocks[b].out - blocks[b0].out)});
         SECEDO_CALL(inflate_blocks(jobs, threads));
         if (t) {
             t->inflate_ms += ms_since(t0);
@@ -384,7 +337,8 @@ int load_file_spans(size_t f, const IndexPlan &plan, uint32_t threads, uint64_t 
             buf.resize(carry + bytes);
             jobs.clear();
             for (size_t b = b0; b < b1; ++b)
-                jobs.push_back({&path, &blocks[b], b, buf.data() + carry + (blocks[b].out - blocks[b0].out), true});
+                jobs.push_back({&path, plan.m.p, &blocks[b], b, buf.data() + carry + (blocks[b].out - blocks[b0].out),
+                                true});
             SECEDO_CALL(inflate_blocks(jobs, threads));
             if (t) {
                 t->inflate_ms += ms_since(t0);
@@ -444,7 +398,8 @@ int sniff_bgzf(const std::string &path, Kind *kind) {
         if (read_block(path, m, off, &blk, &len) != SECEDO_OK) return SECEDO_OK;
         if (blk.isize) {
             std::vector<uint8_t> d(blk.isize);
-            if (inflate_block(blk, d.data()).empty() && !(d.size() >= 4 && std::memcmp(d.data(), "BAM\1", 4) == 0))
+            if (bm::inflate_member_zlib(m.p + blk.payload(), blk, d.data()).empty() &&
+                !(d.size() >= 4 && std::memcmp(d.data(), "BAM\1", 4) == 0))
                 *kind = kSamGz;
             return SECEDO_OK;
         }
@@ -535,20 +490,15 @@ int inflate_range_device(const std::string &path, const Mapped &m, const std::ve
                          secedo_bam_times *t) {
     if (b0 >= b1) return SECEDO_OK;
     Clock::time_point t0 = Clock::now();
-    // the payloads of the range and kBgzfInSlack bytes on either side (the first payload lies 18 bytes into the file)
-    const uint8_t *lo = blocks[b0].cdata - kBgzfInSlack;
-    const uint8_t *pay_end = blocks[b1 - 1].cdata + blocks[b1 - 1].clen;
-    const uint8_t *hi = std::min(m.p + m.n, pay_end + kBgzfInSlack);
+    const bm::PayloadSpan sp = bm::payload_span(blocks, b0, b1, m.n);
     const uint64_t n_blocks = b1 - b0;
     if (n_blocks > UINT32_MAX) return fail(SECEDO_E_LIMIT, path + ": too many BGZF blocks in one range");
     g->h_desc.resize(n_blocks);
-    for (size_t b = b0; b < b1; ++b)
-        g->h_desc[b - b0] = BgzfDesc{uint64_t(blocks[b].cdata - lo), out_base + (blocks[b].out - blocks[b0].out),
-                                     blocks[b].clen, blocks[b].isize, blocks[b].crc, 0};
-    SECEDO_TRY(g->in.grow(uint64_t(pay_end - lo) + kBgzfInSlack, 0, s));
+    bm::fill_desc(blocks, b0, b1, sp.lo, 0, out_base, g->h_desc.data());
+    SECEDO_TRY(g->in.grow(sp.needed, 0, s));
     SECEDO_TRY(g->desc.grow(n_blocks, 0, s));
     SECEDO_TRY(g->status.grow(n_blocks, 0, s));
-    SECEDO_TRY(hipMemcpyAsync(g->in.p, lo, size_t(hi - lo), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(g->in.p, m.p + sp.lo, size_t(sp.hi - sp.lo), hipMemcpyHostToDevice, s));
     SECEDO_TRY(hipMemcpyAsync(g->desc.p, g->h_desc.data(), n_blocks * sizeof(BgzfDesc), hipMemcpyHostToDevice, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     if (t) t->upload_ms += ms_lap(t0);
@@ -558,14 +508,11 @@ int inflate_range_device(const std::string &path, const Mapped &m, const std::ve
     SECEDO_TRY(hipStreamSynchronize(s));
     if (t) t->inflate_ms += ms_lap(t0);
     route().device_blocks += n_blocks;
-    route().uploaded_bytes += uint64_t(hi - lo);
+    route().uploaded_bytes += sp.hi - sp.lo;
     route().batches += 1;
-    for (size_t k = 0; k < n_blocks; ++k)
-        if (g->h_status[k] != secedo::bgzf::kOk)
-            return fail(SECEDO_E_INVALID_ARG,
-                        path + ": BGZF block " + std::to_string(b0 + k) + ": " +
-                            (g->h_status[k] == secedo::bgzf::kCrcMismatch ? "CRC32 mismatch"
-                                                                          : "inflate failed or ISIZE mismatch"));
+    const size_t bad = bm::first_bad(g->h_status.data(), n_blocks);
+    if (bad < n_blocks)
+        return bad_block(path, bm::block_where(b0 + bad), bm::status_text(g->h_status[bad]));
     return SECEDO_OK;
 }
 
@@ -827,8 +774,8 @@ int load_samgz_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs
         if (hb == blocks.size()) break;
         const size_t at = head.size();
         head.resize(at + blocks[hb].isize);
-        const std::string err = inflate_block(blocks[hb], head.data() + at);
-        if (!err.empty()) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(hb) + ": " + err);
+        const std::string err = bm::inflate_member_zlib(m.p + blocks[hb].payload(), blocks[hb], head.data() + at);
+        if (!err.empty()) return bad_block(path, bm::block_where(hb), err);
         ++hb;
     }
     route().host_blocks += hb;
@@ -1003,9 +950,8 @@ int read_header(const std::string &path, IndexPlan *plan) {
         SECEDO_CALL(read_block(path, plan->m, off, &blk, &len));
         blk.out = head.size();
         head.resize(head.size() + blk.isize);
-        const std::string err = inflate_block(blk, head.data() + blk.out);
-        if (!err.empty())
-            return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(plan->head.size()) + ": " + err);
+        const std::string err = bm::inflate_member_zlib(plan->m.p + blk.payload(), blk, head.data() + blk.out);
+        if (!err.empty()) return bad_block(path, bm::block_where(plan->head.size()), err);
         plan->head.push_back(blk);
         off += len;
     }

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // __forceinline__
 #define BGZF_HD __host__ __device__ __forceinline__
 #else
 #define BGZF_HD inline

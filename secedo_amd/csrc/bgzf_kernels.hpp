@@ -1,6 +1,9 @@
 // bgzf_kernels.hpp -- launch wrappers of bgzf_kernels.hip (gfx950): BGZF members inflated in HBM, CRC32 and ISIZE
-// checked there, and the last '\n' of a text range. See bgzf_kernels.hip for the kernel's layout.
+// checked there, and the last '\n' of a text range. See bgzf_kernels.hip for the kernel's layout; BgzfDesc and the
+// input slack are in bgzf_members.hpp, beside the host code that fills them.
 #pragma once
+
+#include "bgzf_members.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -9,17 +12,6 @@
 
 namespace secedo {
 namespace bam {
-
-// one BGZF member: its raw-DEFLATE payload at d_in + in_off (clen bytes) inflates to d_out + out_off (isize bytes)
-struct BgzfDesc {
-    uint64_t in_off, out_off;
-    uint32_t clen, isize, crc, reserved;
-};
-
-// bytes the kernel may read beyond a payload's ends (whole 16-byte vectors): d_in needs that much room before the
-// first payload and after the last one
-constexpr uint32_t kBgzfInSlack = 16;
-constexpr uint32_t kBgzfMaxIsize = 65536;
 
 // d_status[k] = secedo::bgzf::Status of member k (0 = inflated, ISIZE and CRC32 right). Members must not overlap in
 // d_out; isize <= kBgzfMaxIsize.

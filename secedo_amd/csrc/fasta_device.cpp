@@ -14,7 +14,6 @@
 // reach lie at or past that chromosome's end and the final pass zeroes them.
 #include "fasta_source.hpp"
 
-#include "bgzf_inflate.hpp"  // the status codes
 #include "bgzf_kernels.hpp"
 #include "fasta_kernels.hpp"
 
@@ -28,7 +27,6 @@ namespace {
 
 namespace F = secedo::fasta;
 using secedo::bam::BgzfDesc;
-using secedo::bam::kBgzfInSlack;
 
 struct Range {
     uint64_t a, b;  // text: bytes [a, b) of it; BGZF: members [a, b)
@@ -86,13 +84,13 @@ struct Stager {
             max_len = std::max(max_len, r.len);
             if (members) {
                 max_members = std::max<uint32_t>(max_members, uint32_t(r.b - r.a));
-                max_in = std::max<uint64_t>(max_in, compressed_span(r, nullptr));
+                max_in = std::max(max_in, bm::payload_span(src.members, r.a, r.b, src.file_bytes).needed);
             }
         }
         for (int k = 0; k < 2; ++k) {
             SECEDO_TRY(text[k].alloc(size_t(max_len) + 16));
             if (!members) continue;
-            SECEDO_TRY(in[k].alloc(max_in + 2 * kBgzfInSlack));
+            SECEDO_TRY(in[k].alloc(max_in));
             SECEDO_TRY(desc[k].alloc(size_t(max_members) * sizeof(BgzfDesc)));
             SECEDO_TRY(status[k].alloc(size_t(max_members) * 4));
         }
@@ -102,16 +100,6 @@ struct Stager {
         uint32_t m = 0;
         for (const Range &r : ranges) m = std::max(m, r.len);
         return m;
-    }
-
-    // the file bytes that hold the payloads of a range's members, with up to kBgzfInSlack bytes of the file around them
-    // (a member's header is 18 bytes, so the bytes in front are always there)
-    uint64_t compressed_span(const Range &r, const uint8_t **lo_out) const {
-        const Member &first = src.members[r.a], &last = src.members[r.b - 1];
-        const uint8_t *lo = first.cdata - kBgzfInSlack;
-        const uint8_t *hi = std::min(src.file + src.file_bytes, last.cdata + last.clen + kBgzfInSlack);
-        if (lo_out) *lo_out = lo;
-        return uint64_t(hi - lo);
     }
 
     // Issues the upload (and inflate) of range r; `consumed`: the passes of range r - 2 read this slot, wait for them.
@@ -125,16 +113,11 @@ struct Stager {
             SECEDO_TRY(hipMemcpyAsync(text[k].p, src.text() + x.a, x.len, hipMemcpyHostToDevice, up.s));
             st.uploaded_bytes += x.len;
         } else {
-            const uint8_t *lo = nullptr;
-            const uint64_t span = compressed_span(x, &lo);
-            h_desc[k].clear();
-            uint64_t out = 0;
-            for (uint64_t m = x.a; m < x.b; ++m) {
-                const Member &mb = src.members[m];
-                h_desc[k].push_back(BgzfDesc{uint64_t(mb.cdata - lo), out, mb.clen, mb.isize, mb.crc, 0});
-                out += mb.isize;
-            }
-            SECEDO_TRY(hipMemcpyAsync(in[k].p, lo, span, hipMemcpyHostToDevice, up.s));
+            const bm::PayloadSpan sp = bm::payload_span(src.members, x.a, x.b, src.file_bytes);
+            const uint64_t span = sp.hi - sp.lo;
+            h_desc[k].resize(x.b - x.a);
+            bm::fill_desc(src.members, x.a, x.b, sp.lo, 0, 0, h_desc[k].data());
+            SECEDO_TRY(hipMemcpyAsync(in[k].p, src.file + sp.lo, span, hipMemcpyHostToDevice, up.s));
             SECEDO_TRY(hipMemcpyAsync(desc[k].p, h_desc[k].data(), h_desc[k].size() * sizeof(BgzfDesc),
                                       hipMemcpyHostToDevice, up.s));
             st.uploaded_bytes += span;
@@ -152,19 +135,10 @@ struct Stager {
 
 // the lowest bad member of a range whose status words were read back
 void note_bad(const std::vector<uint32_t> &status, const Range &x, uint64_t *bad_k, uint32_t *bad_status) {
-    if (*bad_k != UINT64_MAX) return;
-    for (uint64_t m = 0; m < x.b - x.a; ++m)
-        if (status[m] != secedo::bgzf::kOk) {
-            *bad_k = x.a + m;
-            *bad_status = status[m];
-            return;
-        }
-}
-
-int bad_member(const Source &src, uint64_t k, uint32_t status) {
-    return fail(SECEDO_E_INVALID_ARG, src.path + ": BGZF block " + std::to_string(k) + ": " +
-                                          (status == secedo::bgzf::kCrcMismatch ? "CRC32 mismatch"
-                                                                                : "inflate failed or ISIZE mismatch"));
+    const size_t m = bm::first_bad(status.data(), x.b - x.a);
+    if (*bad_k != UINT64_MAX || m == x.b - x.a) return;
+    *bad_k = x.a + m;
+    *bad_status = status[m];
 }
 
 }  // namespace
@@ -276,7 +250,7 @@ int device_genotypes(const Source &src, bool diploid, const uint32_t *d_chr_locu
     SECEDO_TRY(hipStreamSynchronize(stager.up.s));
     SECEDO_TRY(hipStreamSynchronize(s));
     SECEDO_CALL(read_timed());
-    if (bad_k != UINT64_MAX) return bad_member(src, bad_k, bad_status);
+    if (bad_k != UINT64_MAX) return bad_member(src.path, bad_k, bm::status_text(bad_status));
 
     table.finish();
     st.contigs = table.headers();
@@ -329,7 +303,7 @@ int download_bgzf_text(Source *src, hipStream_t s) {
         at += x.len;
     }
     SECEDO_TRY(hipStreamSynchronize(stager.up.s));
-    if (bad_k != UINT64_MAX) return bad_member(*src, bad_k, bad_status);
+    if (bad_k != UINT64_MAX) return bad_member(src->path, bad_k, bm::status_text(bad_status));
     src->has_text = true;
     return SECEDO_OK;
 }

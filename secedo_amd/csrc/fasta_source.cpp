@@ -2,8 +2,6 @@
 // text, inflated with zlib (see fasta_source.hpp).
 #include "fasta_source.hpp"
 
-#include "bam_index.hpp"  // member_header: the one reader of a BGZF member's header
-
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -25,31 +23,9 @@ namespace {
 std::atomic<int> g_route{-1};
 thread_local secedo_variant_fasta_info g_info;
 
-uint32_t rd32(const uint8_t *p) {
-    uint32_t v;
-    std::memcpy(&v, p, 4);
-    return v;
-}
-
-// raw inflate of one member into dst[isize]; empty on success, else the message's tail (the BAM route's words)
-std::string inflate_member(const Member &m, uint8_t *dst) {
-    z_stream z{};
-    if (inflateInit2(&z, -15) != Z_OK) return "inflateInit2 failed";
-    z.next_in = const_cast<Bytef *>(m.cdata);
-    z.avail_in = m.clen;
-    uint8_t none;  // an empty member (the end-of-file marker) still needs room to be told from a full buffer
-    z.next_out = m.isize ? dst : &none;
-    z.avail_out = m.isize ? m.isize : 1;
-    const int rc = inflate(&z, Z_FINISH);
-    const uint64_t got = z.total_out;
-    inflateEnd(&z);
-    if (rc != Z_STREAM_END || got != m.isize) return "inflate failed or ISIZE mismatch";
-    if (uint32_t(crc32(crc32(0, nullptr, 0), dst, m.isize)) != m.crc) return "CRC32 mismatch";
-    return std::string();
-}
-
-int bad_member(const std::string &path, size_t k, const std::string &what) {
-    return fail(SECEDO_E_INVALID_ARG, path + ": BGZF block " + std::to_string(k) + ": " + what);
+// zlib raw inflate of member k into dst[isize]; empty on success, else the message's tail
+std::string inflate_member(const Source &src, size_t k, uint8_t *dst) {
+    return bm::inflate_member_zlib(src.file + src.members[k].payload(), src.members[k], dst);
 }
 
 // gzip members one after another through zlib's gzip wrapper, which checks each member's CRC32 and ISIZE
@@ -86,24 +62,6 @@ int inflate_gzip(const std::string &path, const uint8_t *p, size_t n, std::vecto
     return SECEDO_OK;
 }
 
-int list_members(Source *src) {
-    uint64_t off = 0;
-    while (off < src->file_bytes) {
-        uint32_t len = 0, isize = 0, xlen = 0;
-        const bamindex::Member what = bamindex::member_header(src->file, src->file_bytes, off, &len, &isize, &xlen);
-        if (what == bamindex::kNoMember)
-            return fail(SECEDO_E_INVALID_ARG, src->path + ": not a BGZF block at byte " + std::to_string(off));
-        if (what == bamindex::kBadBsize)
-            return fail(SECEDO_E_INVALID_ARG, src->path + ": bad BGZF block size at byte " + std::to_string(off));
-        if (what == bamindex::kBigIsize) return fail(SECEDO_E_INVALID_ARG, src->path + ": BGZF ISIZE above 64 KiB");
-        const uint8_t *b = src->file + off;
-        src->members.push_back(Member{b + 12 + xlen, len - xlen - 20, rd32(b + len - 8), isize});
-        src->members_text += isize;
-        off += len;
-    }
-    return SECEDO_OK;
-}
-
 }  // namespace
 
 Source::~Source() {
@@ -130,15 +88,7 @@ int fasta_route(bool *device) {
     return SECEDO_OK;
 }
 
-uint64_t batch_bytes() {
-    const char *e = std::getenv("SECEDO_FASTA_BATCH_BYTES");
-    uint64_t v = 256ull << 20;
-    if (e && *e) {
-        const unsigned long long x = std::strtoull(e, nullptr, 10);
-        if (x > 0) v = x;
-    }
-    return std::max<uint64_t>(v, 64);
-}
+uint64_t batch_bytes() { return std::max<uint64_t>(env_u64("SECEDO_FASTA_BATCH_BYTES", 256ull << 20), 64); }
 
 int open_source(const char *path, Source *src) {
     g_info = secedo_variant_fasta_info{};
@@ -171,7 +121,7 @@ int open_source(const char *path, Source *src) {
         return SECEDO_OK;
     }
     uint32_t len = 0, isize = 0, xlen = 0;
-    if (bamindex::member_header(src->file, src->file_bytes, 0, &len, &isize, &xlen) == bamindex::kNoMember) {
+    if (bm::member_header(src->file, src->file_bytes, 0, &len, &isize, &xlen) == bm::kNoMember) {
         src->kind = g_info.kind = SECEDO_FASTA_KIND_GZIP;
         SECEDO_CALL(inflate_gzip(src->path, src->file, src->file_bytes, &src->inflated));
         g_info.host_inflated_bytes = src->inflated.size();
@@ -179,14 +129,15 @@ int open_source(const char *path, Source *src) {
         return SECEDO_OK;
     }
     src->kind = g_info.kind = SECEDO_FASTA_KIND_BGZF;
-    return list_members(src);
+    const std::string why = bm::list_members(src->file, src->file_bytes, &src->members, &src->members_text);
+    return why.empty() ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, src->path + ": " + why);
 }
 
 int inflate_bgzf_host(Source *src) {
     src->inflated.resize(src->members_text);
     uint64_t at = 0;
     for (size_t k = 0; k < src->members.size(); ++k) {
-        const std::string err = inflate_member(src->members[k], src->inflated.data() + at);
+        const std::string err = inflate_member(*src, k, src->inflated.data() + at);
         if (!err.empty()) return bad_member(src->path, k, err);
         at += src->members[k].isize;
     }
@@ -208,7 +159,7 @@ int bgzf_is_diploid(const Source &src, bool *diploid) {
     for (size_t k = 0; k < src.members.size(); ++k) {
         const size_t at = head.size();
         head.resize(at + src.members[k].isize);
-        const std::string err = inflate_member(src.members[k], head.data() + at);
+        const std::string err = inflate_member(src, k, head.data() + at);
         if (!err.empty()) return bad_member(src.path, k, err);
         g_info.host_inflated_bytes += src.members[k].isize;
         size_t b = 0;

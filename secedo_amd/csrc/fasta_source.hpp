@@ -4,6 +4,7 @@
 // (BGZF: the compressed members) uploaded in ranges, parsed and gathered in HBM. Internal, nothing exported.
 #pragma once
 
+#include "bgzf_members.hpp"
 #include "host_util.hpp"
 #include "secedo_variant.h"
 
@@ -16,11 +17,13 @@ namespace fasta_host __attribute__((visibility("hidden"))) {
 
 using namespace secedo::host;
 
-// one BGZF member of the mapped file: its raw-DEFLATE payload
-struct Member {
-    const uint8_t *cdata;
-    uint32_t clen, crc, isize;
-};
+namespace bm = secedo::bgzf_members;  // the member list of a BGZF file, its descriptors and its error words
+using bm::Member;
+
+// "<path>: BGZF block <k>: <why>", from either route
+inline int bad_member(const std::string &path, uint64_t k, const std::string &why) {
+    return fail(SECEDO_E_INVALID_ARG, path + ": " + bm::block_where(k) + ": " + why);
+}
 
 struct Source {
     std::string path;

@@ -10,6 +10,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstdint>
+#include <cstdlib>
 #include <string>
 
 namespace secedo {
@@ -35,6 +37,23 @@ inline int fail(int code, const std::string &msg) {
         int rc_ = (expr);                 \
         if (rc_ != SECEDO_OK) return rc_; \
     } while (0)
+
+// The decimal value of environment variable `name` where it is set to a number above 0, else `fallback`. Read at every
+// call; the caller clamps.
+inline uint64_t env_u64(const char *name, uint64_t fallback) {
+    const char *e = std::getenv(name);
+    const unsigned long long v = e && *e ? std::strtoull(e, nullptr, 10) : 0;
+    return v > 0 ? v : fallback;
+}
+
+// the calling thread's device, checked against the devices there are
+inline int set_device(int device_id) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(SECEDO_E_NO_DEVICE, "no HIP device");
+    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_INVALID_ARG, "device id out of range");
+    SECEDO_TRY(hipSetDevice(device_id));
+    return SECEDO_OK;
+}
 
 using Clock = std::chrono::steady_clock;
 

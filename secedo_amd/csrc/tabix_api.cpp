@@ -3,10 +3,9 @@
 // stand-alone route, which uploads the compressed bytes of files that exist and inflates them in HBM first.
 #include "tabix_host.hpp"
 
-#include "bam_index.hpp"     // member_header: the one reader of a BGZF member's header
 #include "bgzf_deflate_kernels.hpp"  // kDeflateInSlack
-#include "bgzf_inflate.hpp"  // the status codes
 #include "bgzf_kernels.hpp"
+#include "bgzf_members.hpp"  // the member list of a file that is read, its descriptors and its error words
 #include "host_util.hpp"
 #include "tabix_build.hpp"
 #include "tabix_kernels.hpp"
@@ -26,6 +25,7 @@ namespace tabix_host {
 
 using namespace secedo::host;
 namespace T = secedo::tabix;
+namespace bm = secedo::bgzf_members;
 
 namespace {
 
@@ -34,24 +34,12 @@ thread_local secedo_variant_tabix_info g_info;
 
 // text bytes per range of the line pass (tabix_kernels.hpp)
 uint64_t budget_bytes() {
-    const char *e = std::getenv("SECEDO_TABIX_BATCH_BYTES");
-    uint64_t v = T::kDefaultBudget;
-    if (e && *e) {
-        const unsigned long long x = std::strtoull(e, nullptr, 10);
-        if (x > 0) v = x;
-    }
-    return std::min(std::max(v, T::kMinBudget), T::kMaxRange);
+    return std::min(std::max(env_u64("SECEDO_TABIX_BATCH_BYTES", T::kDefaultBudget), T::kMinBudget), T::kMaxRange);
 }
 
 // windows a range may emit (tabix_kernels.hpp)
 uint64_t max_range_windows() {
-    const char *e = std::getenv("SECEDO_TABIX_MAX_WINDOWS");
-    uint64_t v = T::kMaxRangeWindows;
-    if (e && *e) {
-        const unsigned long long x = std::strtoull(e, nullptr, 10);
-        if (x > 0) v = x;
-    }
-    return std::min(v, T::kMaxRangeWindows);
+    return std::min(env_u64("SECEDO_TABIX_MAX_WINDOWS", T::kMaxRangeWindows), T::kMaxRangeWindows);
 }
 
 // the file that holds text byte x: the last one that begins at or before it
@@ -382,16 +370,10 @@ namespace {
 
 // ---- the stand-alone route
 
-struct Payload {  // one member's raw-DEFLATE bytes in its file
-    uint64_t at;
-    uint32_t clen, crc;
-};
-
 struct Opened {
     std::string path;
     std::vector<uint8_t> bytes;
-    IndexedFile file;
-    std::vector<Payload> payloads;
+    IndexedFile file;  // its members as bgzf_members.hpp lists them: the payloads for the inflate are among them
     uint64_t text_bytes = 0;
 };
 
@@ -410,24 +392,13 @@ int open_vcf_gz(const std::string &path, int overwrite, Opened *o) {
     if (b.size() < 2 || b[0] != 31 || b[1] != 139)
         return fail(SECEDO_E_INVALID_ARG, path + ": not a bgzip-compressed file; compress it with bgzip");
     uint32_t len = 0, isize = 0, xlen = 0;
-    if (bamindex::member_header(b.data(), b.size(), 0, &len, &isize, &xlen) == bamindex::kNoMember)
+    if (bm::member_header(b.data(), b.size(), 0, &len, &isize, &xlen) == bm::kNoMember)
         return fail(SECEDO_E_INVALID_ARG, path + ": a gzip file that is not BGZF; decompress it and compress it with "
                                                  "bgzip");
     if (!overwrite && access((path + ".tbi").c_str(), F_OK) == 0)
         return fail(SECEDO_E_INVALID_ARG, path + ": the index " + path + ".tbi exists; pass overwrite to replace it");
-    for (uint64_t off = 0; off < b.size(); off += len) {
-        const bamindex::Member what = bamindex::member_header(b.data(), b.size(), off, &len, &isize, &xlen);
-        if (what == bamindex::kNoMember)
-            return fail(SECEDO_E_INVALID_ARG, path + ": not a BGZF block at byte " + std::to_string(off));
-        if (what == bamindex::kBadBsize)
-            return fail(SECEDO_E_INVALID_ARG, path + ": bad BGZF block size at byte " + std::to_string(off));
-        if (what == bamindex::kBigIsize) return fail(SECEDO_E_INVALID_ARG, path + ": BGZF ISIZE above 64 KiB");
-        uint32_t crc;
-        std::memcpy(&crc, b.data() + off + len - 8, 4);
-        o->file.members.push_back(bamindexbuild::Member{off, o->text_bytes, isize});
-        o->payloads.push_back(Payload{off + 12 + xlen, len - xlen - 20, crc});
-        o->text_bytes += isize;
-    }
+    const std::string why = bm::list_members(b.data(), b.size(), &o->file.members, &o->text_bytes);
+    if (!why.empty()) return fail(SECEDO_E_INVALID_ARG, path + ": " + why);
     o->file.file_bytes = b.size();
     return SECEDO_OK;
 }
@@ -438,7 +409,7 @@ constexpr uint64_t kBatchText = 1ull << 30;
 int run_batch(std::vector<Opened> &batch, hipStream_t s) {
     if (batch.empty()) return SECEDO_OK;
     using secedo::bam::BgzfDesc;
-    using secedo::bam::kBgzfInSlack;
+    using secedo::bam::kBgzfInSlack;  // around the whole batch: every file goes up from its first byte to its last
     Clock::time_point t0 = Clock::now();
     std::vector<uint64_t> file_off(batch.size() + 1, 0), in_off(batch.size() + 1, 0);
     std::vector<BgzfDesc> desc;
@@ -447,9 +418,9 @@ int run_batch(std::vector<Opened> &batch, hipStream_t s) {
         const Opened &o = batch[f];
         file_off[f + 1] = file_off[f] + o.text_bytes;
         in_off[f + 1] = in_off[f] + o.bytes.size();
-        for (size_t k = 0; k < o.payloads.size(); ++k)
-            desc.push_back(BgzfDesc{in_off[f] + o.payloads[k].at, file_off[f] + o.file.members[k].out, o.payloads[k].clen,
-                                    o.file.members[k].isize, o.payloads[k].crc, 0});
+        desc.resize(desc.size() + o.file.members.size());
+        bm::fill_desc(o.file.members, 0, o.file.members.size(), 0, in_off[f], file_off[f],
+                      desc.data() + desc.size() - o.file.members.size());
         files.push_back(o.file);
     }
     if (desc.size() >= (1u << 31)) return fail(SECEDO_E_LIMIT, "more than 2^31 BGZF blocks in a batch");
@@ -472,14 +443,14 @@ int run_batch(std::vector<Opened> &batch, hipStream_t s) {
     // a bad member: the files in front of it are indexed, its own error is the call's
     size_t n_ok = batch.size();
     std::string bad;
-    for (size_t f = 0, k = 0; f < batch.size() && bad.empty(); ++f)
-        for (size_t m = 0; m < batch[f].payloads.size(); ++m, ++k)
-            if (status[k] != secedo::bgzf::kOk) {
-                n_ok = f;
-                bad = batch[f].path + ": BGZF block " + std::to_string(m) + ": " +
-                      (status[k] == secedo::bgzf::kCrcMismatch ? "CRC32 mismatch" : "inflate failed or ISIZE mismatch");
-                break;
-            }
+    size_t k = bm::first_bad(status.data(), status.size());  // of the batch, then of its file
+    if (k < status.size()) {
+        const uint32_t what = status[k];
+        size_t f = 0;
+        while (k >= batch[f].file.members.size()) k -= batch[f++].file.members.size();
+        n_ok = f;
+        bad = batch[f].path + ": " + bm::block_where(k) + ": " + bm::status_text(what);
+    }
     files.resize(n_ok);
     file_off.resize(n_ok + 1);
     std::vector<std::vector<uint8_t>> raw;
@@ -517,14 +488,6 @@ int tabix_build(const char *const *paths, uint32_t n, int overwrite, hipStream_t
     return run_batch(batch, s);
 }
 
-int set_device(int device_id) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(SECEDO_E_NO_DEVICE, "no HIP device");
-    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_INVALID_ARG, "device id out of range");
-    SECEDO_TRY(hipSetDevice(device_id));
-    return SECEDO_OK;
-}
-
 }  // namespace
 }  // namespace tabix_host
 }  // namespace secedo
@@ -549,7 +512,7 @@ int secedo_variant_tabix_stats(secedo_variant_tabix_info *out) {
 int secedo_variant_tabix_build(int device_id, const char *const *paths, uint32_t n, int overwrite, void *stream) {
     secedo::tabix_host::info() = secedo_variant_tabix_info{};
     if (!paths && n) return secedo::host::fail(SECEDO_E_INVALID_ARG, "null argument");
-    SECEDO_CALL(secedo::tabix_host::set_device(device_id));
+    SECEDO_CALL(secedo::host::set_device(device_id));
     return secedo::tabix_host::tabix_build(paths, n, overwrite, static_cast<hipStream_t>(stream));
 }
 

@@ -302,14 +302,6 @@ int reference_genotypes(const Source &src, const char *map_file, const uint32_t 
 // ---------------------------------------------------------------------------------------------------------------
 // Device side
 
-int set_device(int device_id) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(SECEDO_E_NO_DEVICE, "no HIP device");
-    if (device_id < 0 || device_id >= n_dev) return fail(SECEDO_E_INVALID_ARG, "device id out of range");
-    SECEDO_TRY(hipSetDevice(device_id));
-    return SECEDO_OK;
-}
-
 // The reference genotypes of a pileup resident in HBM, by the route the file and the setting ask for.
 struct RefArgs {
     const uint32_t *d_chr_locus_off, *chr_locus_off;  // device and host copies

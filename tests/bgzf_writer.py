@@ -215,6 +215,25 @@ def corrupt_member(raw: bytes, k: int) -> bytes:
     return raw[:at] + bytes([raw[at] ^ 0x10]) + raw[at + 1:]
 
 
+def listing_damage(raw: bytes):
+    """The three files whose member list no reader gets past member 0, made of a valid BGZF file of two members or
+    more (18-byte headers): -> [(name, bytes, the message behind the file's name)]. A valid first member, then 40
+    bytes that are no gzip header; a second member whose BSIZE is less than its header and trailer; a second member
+    whose ISIZE field says 65537."""
+    n0 = int.from_bytes(raw[16:18], "little") + 1
+    n1 = int.from_bytes(raw[n0 + 16:n0 + 18], "little") + 1
+    assert n0 + n1 <= len(raw) and raw[n0:n0 + 4] == raw[:4]
+    small, big = bytearray(raw), bytearray(raw)
+    small[n0 + 16:n0 + 18] = struct.pack("<H", 24)  # 25 bytes: 18 of header and 8 of trailer do not fit
+    big[n0 + n1 - 4:n0 + n1] = struct.pack("<I", 65537)
+    return [("not-bgzf", raw[:n0] + bytes(range(1, 41)), ": not a BGZF block at byte %d" % n0),
+            ("bad-bsize", bytes(small), ": bad BGZF block size at byte %d" % n0),
+            ("big-isize", bytes(big), ": BGZF ISIZE above 64 KiB")]
+
+
+LISTING_DAMAGE = ("not-bgzf", "bad-bsize", "big-isize")
+ERROR_PREFIX = "secedo_simmat error -1: "  # SecedoError's words in front of an E_INVALID_ARG message
+
 ERROR_WRITERS = {"stored": dict(level=0), "l6": dict(level=6), "fixed": dict(level=6, strategy="fixed")}
 ERROR_MEMBERS = (0, 3, 9)
 

@@ -222,6 +222,19 @@ def test_corrupt_members_are_named_lowest_first(tmp_path, monkeypatch, batch):
     assert got[0] == "error" and "BGZF block 2: " in got[2]
 
 
+@pytest.mark.parametrize("device", (False, True))
+@pytest.mark.parametrize("damage", range(len(bgzf_writer.LISTING_DAMAGE)))
+def test_a_file_whose_members_cannot_be_listed(tmp_path, damage, device):
+    """Member 0 is whole, which makes the file BGZF and not plain gzip; the list breaks at member 1, on either route."""
+    text = fc.kind_text("diploid", np.random.default_rng(12))
+    off, pos = fc.kind_loci(np.random.default_rng(13), "diploid")
+    _name, data, tail = bgzf_writer.listing_damage(bgzf_writer.bgzf(text, chunk=37))[damage]
+    path = tmp_path / "g.fa"
+    path.write_bytes(data)
+    assert _outcome(str(path), off, pos, device) == ("error", _lib.E_INVALID_ARG,
+                                                     bgzf_writer.ERROR_PREFIX + "<dir>/g.fa" + tail)
+
+
 # --- end to end ---------------------------------------------------------------------------------------------------
 
 def _files(d):

@@ -476,6 +476,17 @@ def test_block_errors(tmp_path):
     assert "BGZF block 3: " in str(e.value)
 
 
+@pytest.mark.parametrize("damage", range(len(gw.LISTING_DAMAGE)))
+def test_a_file_whose_members_cannot_be_listed(tmp_path, damage):
+    """Member 0 (the header's, which makes the file a BAM) is whole; the list breaks at member 1, on either route."""
+    raw = gw.bgzf(raw_of(bw.bam_bytes([("1", 3_000_000)], _many())), chunk=4000)
+    name, data, tail = gw.listing_damage(raw)[damage]
+    path = str(tmp_path / (name + ".bam"))
+    with open(path, "wb") as f:
+        f.write(data)
+    assert both_errors([path]) == gw.ERROR_PREFIX + path + tail
+
+
 # ---------------------------------------------------------------------------------------------- surface
 
 def test_cli_and_environment(synth, tmp_path):

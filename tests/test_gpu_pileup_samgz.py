@@ -186,6 +186,16 @@ def test_a_corrupt_block_is_reported_by_index(tmp_path):
         assert str(e2.value) == msg
 
 
+@pytest.mark.parametrize("damage", range(len(gw.LISTING_DAMAGE)))
+def test_a_file_whose_members_cannot_be_listed(tmp_path, damage):
+    """Member 0 (SAM text, which makes the file a .sam.gz) is whole; the list breaks at member 1."""
+    name, data, tail = gw.listing_damage(gw.bgzf(error_text()[:20000], chunk=4096))[damage]
+    path = tmp_path / (name + ".sam.gz")
+    path.write_bytes(data)
+    e = _err([str(path)])
+    assert e.code == -1 and str(e) == gw.ERROR_PREFIX + str(path) + tail
+
+
 def test_plain_gzip_is_still_refused_and_names_play_no_part(synth, tmp_path):
     import gzip
     _, _, bams, sams, gzs = synth

@@ -188,6 +188,16 @@ def test_refused_files(tmp_path):
     assert not [n for n in os.listdir(tmp_path) if n.endswith(".tbi")]
 
 
+@pytest.mark.parametrize("damage", range(len(gw.LISTING_DAMAGE)))
+def test_a_file_whose_members_cannot_be_listed(tmp_path, damage):
+    name, data, tail = gw.listing_damage(gw.bgzf(tc.spans(), chunk=8192))[damage]
+    path = str(tmp_path / (name + ".vcf.gz"))
+    with open(path, "wb") as f:
+        f.write(data)
+    assert _message(path) == gw.ERROR_PREFIX + path + tail
+    assert not os.path.exists(path + ".tbi")
+
+
 def _spanning(n_names):
     """n_names lines, each under its own name and over all 32768 windows"""
     return b"".join(b"n%d\t1\t.\tA\t<DEL>\t.\t.\tEND=%d\n" % (k, 1 << 29) for k in range(n_names))
