@@ -76,6 +76,12 @@
  * unknown: messages say "indexed record k" (k counts from the first record of the file's first span) and "BGZF
  * block at byte <coffset>". A defect outside every span is not seen. SAM, BGZF SAM and secedo_bam_scan[_device]
  * never use an index.
+ *
+ * Writing BAM (secedo_bam_split_clusters, below): one coordinate-sorted cluster_<k>.bam per cluster of a clustering,
+ * the pseudo-bulk files of the subclones. The inputs are read as for a pileup call, every kind, route and index mode;
+ * cell to cluster, the merged order (a stable radix sort), the gather of whole records into per-cluster streams and the
+ * BGZF DEFLATE run on the GPU (secedo_amd/csrc/bam_split_kernels.hip, bgzf_deflate_kernels.hip), and only compressed
+ * bytes come back. Records are copied byte for byte; the bytes of every output are fixed by the rules at the call.
  */
 #ifndef SECEDO_BAM_H
 #define SECEDO_BAM_H
@@ -245,6 +251,66 @@ typedef struct secedo_bam_build_info {
  * those. Sets secedo_bam_route_stats. Synchronous. num_threads: the staging pool, capped at 16 (0 = 1). */
 int secedo_bam_index_build(const char *const *bam_files, uint32_t n_files, const char *const *out_paths, int overwrite,
                            uint32_t num_threads, secedo_bam_build_info *info);
+
+/* What the last secedo_bam_split_clusters call on this thread wrote (all of it, also after a failure: then what it
+ * had done by then). */
+typedef struct secedo_bam_split_info {
+    uint64_t files;            /* input files */
+    uint64_t clusters;         /* cluster_<k>.bam files written: max(cell_cluster) + 1 */
+    uint64_t cells;
+    uint64_t records;          /* records written, over all clusters and chromosomes */
+    uint64_t dropped_records;  /* tag mode: records of the requested chromosomes without a listed barcode */
+    uint64_t text_bytes;       /* uncompressed bytes of the outputs: headers and records */
+    uint64_t compressed_bytes; /* bytes of the outputs, the EOF members included */
+    uint64_t members;          /* BGZF members made, the EOF members not counted */
+    uint64_t stored_members;   /* of those, the ones that fell back to a stored block */
+    double order_ms;           /* keys, compaction, sort, destinations, extents */
+    double gather_ms;          /* the gather kernel (stream events) */
+    double deflate_ms;         /* descriptors up, encoder and packer */
+    double download_ms;        /* compressed bytes to the host */
+    double write_ms;           /* appending to the temporary files, closing, renaming */
+} secedo_bam_split_info;
+
+/* Writes one coordinate-sorted BAM per cluster of a clustering: <out_dir>/cluster_<k>.bam for every k in
+ * 0..max(cell_cluster), holding the records of the cells c with cell_cluster[c] == k (a k no cell has gives a
+ * header-only file). The pseudo-bulk files of the subclones `secedo_main` found (its `clustering` file is cell_cluster).
+ *
+ * Cells: per-file mode (tag NULL): the cell of a record is its file's index, n_cells must equal n_files. Tag mode: the
+ * cell is the index of the record's Z-typed tag value in barcodes, as in secedo_pileup_bams_cells; n_cells must equal
+ * n_barcodes; records without the tag, with another type or an unlisted value are dropped and counted in
+ * info->dropped_records.
+ *
+ * Which records: of every file what the pileup calls read (the first contiguous run of each requested chromosome;
+ * BAM, SAM and BGZF SAM; either route, any index mode, any SECEDO_BAM_BATCH_BYTES, with the pileup calls' codes and
+ * messages for defective input), byte for byte as in the input, block_size included. Records with RefID -1 are not
+ * written. The read filter, the duplicate removal and the quality, MAPQ and pair rules of the pileup do not apply.
+ * chromosome_ids are RefIDs; they are sorted before use; a duplicate or an id at or past n_ref is SECEDO_E_INVALID_ARG.
+ * Order within an output: RefID, Position, input file index, the record's ordinal in its file.
+ *
+ * All inputs must share one reference list (count, names, lengths, order); else SECEDO_E_INVALID_ARG naming the file,
+ * the first file and the reference. Header of every output: "BAM\1", l_text, the text, n_ref and the first file's
+ * binary reference list (built from its @SQ lines when it is SAM). The text: "@HD\tVN:1.6\tSO:coordinate"; one
+ * "@SQ\tSN:<name>\tLN:<len>" per reference of that list; the distinct @RG lines of all inputs in order of first
+ * appearance (files in list order, lines in header order, compared as whole lines; two different lines with one ID
+ * are SECEDO_E_INVALID_ARG naming both files); "@PG\tID:secedo_amd.split\tPN:secedo_amd";
+ * "@CO\tsecedo_amd cluster <k>: <m> of <n> cells". Every line ends in '\n'; input @PG and @CO lines are not carried.
+ *
+ * Layout, fixed: with M(x) the members the BGZF encoder of secedo_amd/csrc/bgzf_deflate.hpp gives for bytes x (cut
+ * every 0xFF00 bytes from x's start, fixed Huffman or stored by its rule, nothing for empty x), a file is M(header),
+ * M(records of the first requested chromosome), ..., M(records of the last), the 28-byte EOF member. A member may cut
+ * a record anywhere. Cell to cluster, the merged order, the gather of whole records into per-cluster streams and the
+ * DEFLATE run on the GPU (secedo_amd/csrc/bam_split_kernels.hip); only compressed bytes come back.
+ *
+ * Files are written to a temporary name beside the target (<target>.tmp.<pid>) and renamed when all are complete. An
+ * existing target is SECEDO_E_INVALID_ARG unless overwrite. A failed call leaves no temporaries and no new
+ * cluster_*.bam. times is filled as the pileup calls fill it (write_ms: the outputs); secedo_bam_route_stats and
+ * secedo_bam_index_stats are set as for a pileup call. num_threads: the host inflate pool. Not done: unplaced records,
+ * RG/CB tags appended to records, merged cell groups, .csi, several GPUs. Synchronous. */
+int secedo_bam_split_clusters(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                              uint32_t n_chr, const uint16_t *cell_cluster, uint32_t n_cells, const char tag[2],
+                              const char *const *barcodes, uint32_t n_barcodes, const char *out_dir, int overwrite,
+                              uint32_t num_threads, secedo_bam_split_info *info, secedo_bam_times *times);
+int secedo_bam_split_stats(secedo_bam_split_info *out);
 
 /* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
  * num_threads: inflate pool size, capped at 16 (0 = 1). */

@@ -72,6 +72,12 @@ class SelectInfo(C.Structure):
                                           "large_templates", "duplicate_templates", "duplicate_records", "reserved")]
 
 
+class SplitInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("files", "clusters", "cells", "records", "dropped_records", "text_bytes",
+                                           "compressed_bytes", "members", "stored_members")] +
+                [(k, C.c_double) for k in ("order_ms", "gather_ms", "deflate_ms", "download_ms", "write_ms")])
+
+
 INFLATE_MODES = {"host": 0, "device": 1}
 INDEX_MODES = {"off": 0, "auto": 1, "require": 2}
 
@@ -111,6 +117,9 @@ SIGNATURES = {
     "secedo_bam_index_ranges": (C.c_int, [C.c_char_p, C.POINTER(_u32), _vp, _vp, _vp, _u32]),
     "secedo_bam_scan_device": (C.c_int, [C.c_char_p, _u32, C.POINTER(ScanInfo), _vp, _u32]),
     "secedo_bam_index_build": (C.c_int, [_files_t, _u32, _files_t, C.c_int, _u32, C.POINTER(BuildInfo)]),
+    "secedo_bam_split_clusters": (C.c_int, [_files_t, _u32, _vp, _u32, _vp, _u32, C.c_char_p, _files_t, _u32,
+                                            C.c_char_p, C.c_int, _u32, C.POINTER(SplitInfo), C.POINTER(Times)]),
+    "secedo_bam_split_stats": (C.c_int, [C.POINTER(SplitInfo)]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
@@ -325,6 +334,80 @@ def bam_index_build(files: Sequence[str], out_paths: Optional[Sequence[Optional[
     info = BuildInfo()
     check(lib().secedo_bam_index_build(arr, n, outs, int(bool(overwrite)), num_threads, C.byref(info)))
     return {k: int(getattr(info, k)) for k, _ in BuildInfo._fields_ if k != "reserved"}
+
+
+def read_clustering(path) -> list:
+    """The cluster of each cell from the comma-separated ``clustering`` file ``secedo_main`` writes; anything but
+    cluster numbers in [0, 65535] raises ValueError."""
+    with open(path) as f:
+        fields = [x.strip() for x in f.read().replace("\n", ",").split(",")]
+    out = []
+    for x in fields:
+        if not x:
+            continue
+        if not x.isdigit() or int(x) > 65535:
+            raise ValueError("%s: %r is not a cluster number in [0, 65535]" % (path, x))
+        out.append(int(x))
+    if not out:
+        raise ValueError("%s lists no cell" % path)
+    return out
+
+
+def _split_dict(info: SplitInfo) -> dict:
+    return {k: (int if t is C.c_uint64 else float)(getattr(info, k)) for k, t in SplitInfo._fields_}
+
+
+def split_stats() -> dict:
+    """What the last ``split_clusters`` call on this thread did, a failed one up to its failure: files, clusters,
+    cells, records written, dropped_records, text_bytes, compressed_bytes, members, stored_members and the stage
+    times order_ms, gather_ms, deflate_ms, download_ms, write_ms."""
+    info = SplitInfo()
+    check(lib().secedo_bam_split_stats(C.byref(info)))
+    return _split_dict(info)
+
+
+def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids: Sequence[int], *, cell_tag=None,
+                   cells=None, inflate=None, index=None, bai: bool = False, overwrite: bool = False,
+                   num_threads: int = 8, times: Optional[dict] = None) -> dict:
+    """Writes ``<out_dir>/cluster_<k>.bam`` for every k in 0..max(clustering): the records of the cells of cluster k
+    on the chromosomes ``chromosome_ids`` (RefIDs), merged in coordinate order (RefID, Position, input file, record),
+    byte for byte as they are in the input; a k no cell has gives a header-only file. The pseudo-bulk BAMs of the
+    subclones. ``clustering``: the cluster of each cell, a sequence or the path of the comma-separated file
+    ``secedo_main`` writes. The cell of a record is its file's index, or with ``cell_tag`` / ``cells`` the index of its
+    Z-typed tag value in ``cells`` as in ``pileup_bams`` (other records are dropped and counted). The inputs go through
+    the pileup's input layer: BAM, SAM and bgzipped SAM, ``inflate`` and ``index`` as in ``pileup_bams``; the flag
+    filter, the duplicate removal and the quality rules do not apply. Cell to cluster, the order, the gather of the
+    records into per-cluster streams and the DEFLATE run on the GPU; the bytes of every file are fixed (see
+    include/secedo_bam.h). All inputs must share one reference list. An existing output raises unless ``overwrite``; a
+    failed call leaves no file behind. ``bai``: also write ``cluster_<k>.bam.bai`` with ``bam_index_build``.
+    -> the dict of ``split_stats()``; ``times`` (a dict) receives the step times in ms."""
+    arr, n = _files(bam_files)
+    if isinstance(clustering, (str, bytes, os.PathLike)):
+        try:
+            clustering = read_clustering(clustering)
+        except ValueError as e:
+            raise _lib.SecedoError(_lib.E_INVALID_ARG, str(e))
+    cl = np.asarray(clustering)
+    if cl.ndim != 1 or cl.size == 0 or not np.issubdtype(cl.dtype, np.integer) or cl.min() < 0 or cl.max() > 65535:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "clustering is a non-empty sequence of cluster numbers in [0, 65535]")
+    cl = np.ascontiguousarray(cl, dtype=np.uint16)
+    tag, bcs, n_bcs = _cells(cell_tag, cells)
+    ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
+    try:
+        import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
+    except ImportError:
+        pass
+    info, t = SplitInfo(), Times()
+    with _route(inflate, index):
+        check(lib().secedo_bam_split_clusters(arr, n, _lib.ptr(ids) if len(ids) else None, len(ids), _lib.ptr(cl),
+                                              len(cl), tag, bcs, n_bcs, os.fsencode(str(out_dir)),
+                                              int(bool(overwrite)), num_threads, C.byref(info), C.byref(t)))
+    if times is not None:
+        times.update(_times(t))
+    if bai:
+        outs = [os.path.join(str(out_dir), "cluster_%d.bam" % k) for k in range(int(info.clusters))]
+        bam_index_build(outs, overwrite=True, num_threads=max(1, min(int(num_threads), 16)))
+    return _split_dict(info)
 
 
 def bam_route_stats() -> dict:

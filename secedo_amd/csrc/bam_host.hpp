@@ -2,6 +2,7 @@
 // into one ChrInput per requested chromosome, bam_pileup.cpp turns those into the pileup. Internal, nothing exported.
 #pragma once
 
+#include "bam_kernels.hpp"
 #include "bgzf_members.hpp"
 #include "host_util.hpp"
 #include "secedo_bam.h"
@@ -63,6 +64,34 @@ std::string record_where(const std::string &path, size_t f, uint64_t line0, uint
 // t: stage times are added to it; may be null.
 int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosome_ids, uint32_t n_chr,
                 uint32_t threads, Inputs *in, secedo_bam_times *t);
+
+// The header of one input file as a BAM holds it (bam_split.cpp writes headers from it): the text, and the binary
+// reference list (n_ref entries of l_name, name, l_ref). Of a SAM or BGZF SAM file the text is its leading '@' lines
+// and ref_list stays empty: its @SQ lines are the list. Host only; meant for files load_inputs has read already.
+struct FileHeader {
+    std::string text;
+    uint32_t n_ref = 0;
+    std::vector<uint8_t> ref_list;
+    bool sam = false;
+};
+int read_file_header(const std::string &path, FileHeader *h);
+
+// ---- what the calls of bam_pileup.cpp and bam_split.cpp share of tag mode and of their argument checks
+
+// tag: two characters [A-Za-z][A-Za-z0-9] (SAM spec 1.5)
+int check_tag(const char *tag);
+// the barcode list of tag mode: non-empty, at most SECEDO_BAM_MAX_FILES, no value twice
+int check_cells(const char *tag, const char *const *barcodes, uint32_t n, std::vector<std::string> *values);
+int check_files(const char *const *bam_files, uint32_t n_files, std::vector<std::string> *files);
+
+// The listed barcodes of tag mode on the device: packed values, their hashes sorted, the cell of each.
+struct DevCells {
+    Dev<uint8_t> bytes;
+    Dev<uint32_t> off, cell;
+    Dev<uint64_t> hash;
+    bam::CellList list{};
+};
+int upload_cells(const char tag[2], const std::vector<std::string> &values, hipStream_t s, DevCells *dc);
 
 // ---- what bam_input.cpp (host inflate, host walk) and bam_device_input.cpp (device inflate, device walk) share
 

@@ -747,20 +747,13 @@ int load_sam_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs, 
     return SECEDO_OK;
 }
 
-// One BGZF-compressed SAM file: what load_sam_file gives on its inflated text. The host lists the blocks and inflates
-// the leading ones with zlib until the '@' lines end; every block after those is inflated on the device, in ranges of
-// about `batch` inflated bytes, into the text buffer behind the carry (the bytes after the last '\n' of the range
-// before). [0, last '\n'] of each range goes to the parse; the inflated text never reaches the host.
-int load_samgz_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs, secedo_bam_times *t) {
-    const std::string &path = in->paths[f];
-    Clock::time_point t0 = Clock::now();
-    Mapped m;
-    std::vector<Block> blocks;
-    uint64_t total = 0;
-    SECEDO_CALL(open_bgzf(path, &m, &blocks, &total));
-    // the header: blocks inflated here until a line starts with something else than '@', or the file ends
-    std::vector<uint8_t> head;
-    size_t hb = 0;
+// The header of a BGZF SAM file: its leading blocks inflated on the host until a line starts with something else than
+// '@', or the file ends -> head (what those blocks hold, body bytes behind the header included), *hb = blocks inflated.
+int inflate_sam_head(const std::string &path, const Mapped &m, const std::vector<Block> &blocks,
+                     std::vector<uint8_t> *head_out, size_t *hb_out) {
+    std::vector<uint8_t> &head = *head_out;
+    size_t &hb = *hb_out;
+    hb = 0;
     for (uint64_t o = 0;;) {  // o: a line start, every line before it an '@' line
         const uint8_t *nl = nullptr;
         if (o < head.size()) {
@@ -778,6 +771,23 @@ int load_samgz_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs
         if (!err.empty()) return bad_block(path, bm::block_where(hb), err);
         ++hb;
     }
+    return SECEDO_OK;
+}
+
+// One BGZF-compressed SAM file: what load_sam_file gives on its inflated text. The host lists the blocks and inflates
+// the leading ones with zlib until the '@' lines end; every block after those is inflated on the device, in ranges of
+// about `batch` inflated bytes, into the text buffer behind the carry (the bytes after the last '\n' of the range
+// before). [0, last '\n'] of each range goes to the parse; the inflated text never reaches the host.
+int load_samgz_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs, secedo_bam_times *t) {
+    const std::string &path = in->paths[f];
+    Clock::time_point t0 = Clock::now();
+    Mapped m;
+    std::vector<Block> blocks;
+    uint64_t total = 0;
+    SECEDO_CALL(open_bgzf(path, &m, &blocks, &total));
+    std::vector<uint8_t> head;
+    size_t hb = 0;
+    SECEDO_CALL(inflate_sam_head(path, m, blocks, &head, &hb));
     route().host_blocks += hb;
     SamHeader h;
     SECEDO_CALL(parse_sam_header(path, f, head.data(), head.size(), &h));
@@ -937,8 +947,8 @@ std::string read_index(const std::string &path, const Mapped &m, uint32_t n_ref,
     return why.empty() ? why : name + ": " + why;
 }
 
-// the header's members of a mapped BAM inflated and the header parsed
-int read_header(const std::string &path, IndexPlan *plan) {
+// the header's members of a mapped BAM inflated and the header parsed; bytes (may be null): what was inflated
+int read_header(const std::string &path, IndexPlan *plan, std::vector<uint8_t> *bytes = nullptr) {
     std::vector<uint8_t> head;
     uint64_t off = 0;
     for (;;) {
@@ -955,6 +965,7 @@ int read_header(const std::string &path, IndexPlan *plan) {
         plan->head.push_back(blk);
         off += len;
     }
+    if (bytes) bytes->swap(head);
     return SECEDO_OK;
 }
 
@@ -1185,6 +1196,45 @@ int load_inputs(const std::vector<std::string> &files, const uint32_t *chromosom
         }
     }
     if (t) t->walk_ms += ms_since(t0);
+    return SECEDO_OK;
+}
+
+int read_file_header(const std::string &path, FileHeader *h) {
+    Kind kind = kBam;
+    SECEDO_CALL(sniff(path, &kind));
+    h->sam = kind != kBam;
+    if (kind == kBam) {
+        IndexPlan plan;
+        std::vector<uint8_t> head;
+        SECEDO_CALL(map_file(path, &plan.m));
+        SECEDO_CALL(read_header(path, &plan, &head));
+        h->text.assign(reinterpret_cast<const char *>(head.data()) + 8, plan.h.l_text);
+        h->n_ref = plan.h.n_ref;
+        h->ref_list.assign(head.begin() + 8 + plan.h.l_text + 4, head.begin() + plan.h.first_record);
+        return SECEDO_OK;
+    }
+    // SAM text: the leading '@' lines; of a BGZF SAM file its members are inflated until they end
+    Mapped m;
+    std::vector<uint8_t> head;
+    const uint8_t *p = nullptr;
+    uint64_t n = 0;
+    if (kind == kSam) {
+        SECEDO_CALL(map_file(path, &m));
+        p = m.p, n = m.n;
+    } else {
+        std::vector<Block> blocks;
+        uint64_t total = 0;
+        SECEDO_CALL(open_bgzf(path, &m, &blocks, &total));
+        size_t hb = 0;
+        SECEDO_CALL(inflate_sam_head(path, m, blocks, &head, &hb));
+        p = head.data(), n = head.size();
+    }
+    uint64_t o = 0;
+    while (o < n && p[o] == '@') {
+        const uint8_t *nl = static_cast<const uint8_t *>(std::memchr(p + o, '\n', n - o));
+        o = nl ? uint64_t(nl - p) + 1 : n;
+    }
+    h->text.assign(reinterpret_cast<const char *>(p), o);
     return SECEDO_OK;
 }
 

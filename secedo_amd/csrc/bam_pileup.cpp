@@ -160,14 +160,12 @@ struct ChrOut {
     std::vector<uint64_t> ord_off;  // per ordinal: byte offset in ChrInput::bytes
 };
 
-// The listed barcodes of tag mode on the device: packed values, their hashes sorted, the cell of each.
-struct DevCells {
-    Dev<uint8_t> bytes;
-    Dev<uint32_t> off, cell;
-    Dev<uint64_t> hash;
-    CellList list{};
-};
+}  // namespace
 
+namespace secedo {
+namespace bam_host {
+
+// tag mode's barcode list to the device (bam_host.hpp: DevCells); bam_split.cpp uses it too
 int upload_cells(const char tag[2], const std::vector<std::string> &values, hipStream_t s, DevCells *dc) {
     const uint32_t n = uint32_t(values.size());
     std::vector<uint8_t> bytes;
@@ -186,15 +184,20 @@ int upload_cells(const char tag[2], const std::vector<std::string> &values, hipS
     SECEDO_TRY(idx.alloc(n));
     if (!bytes.empty()) SECEDO_TRY(hipMemcpyAsync(dc->bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
     SECEDO_TRY(hipMemcpyAsync(dc->off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
-    SECEDO_TRY(list_hash(dc->bytes.p, dc->off.p, n, h.p, idx.p, s));
-    const size_t tb = sort_pairs_bytes(n);
+    SECEDO_TRY(bam::list_hash(dc->bytes.p, dc->off.p, n, h.p, idx.p, s));
+    const size_t tb = bam::sort_pairs_bytes(n);
     Dev<uint8_t> tmp;
     SECEDO_TRY(tmp.alloc(tb));
-    SECEDO_TRY(sort_pairs(tmp.p, tb, h.p, dc->hash.p, idx.p, dc->cell.p, n, s));
+    SECEDO_TRY(bam::sort_pairs(tmp.p, tb, h.p, dc->hash.p, idx.p, dc->cell.p, n, s));
     SECEDO_TRY(hipStreamSynchronize(s));
-    dc->list = CellList{dc->bytes.p, dc->off.p, dc->hash.p, dc->cell.p, n, uint8_t(tag[0]), uint8_t(tag[1])};
+    dc->list = bam::CellList{dc->bytes.p, dc->off.p, dc->hash.p, dc->cell.p, n, uint8_t(tag[0]), uint8_t(tag[1])};
     return SECEDO_OK;
 }
+
+}  // namespace bam_host
+}  // namespace secedo
+
+namespace {
 
 // Where the records of the global order come from, for error messages and the .map.
 struct Order {
@@ -759,6 +762,11 @@ int write_files(const std::string &prefix, bool text, uint32_t chromosome_id, co
     return (fclose(ft) == 0 && ok) ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, "Could not write " + prefix);
 }
 
+}  // namespace
+
+namespace secedo {
+namespace bam_host {
+
 // tag: two characters [A-Za-z][A-Za-z0-9] (SAM spec 1.5)
 int check_tag(const char *tag) {
     if (!tag) return fail(SECEDO_E_INVALID_ARG, "null tag");
@@ -791,6 +799,11 @@ int check_files(const char *const *bam_files, uint32_t n_files, std::vector<std:
     }
     return SECEDO_OK;
 }
+
+}  // namespace bam_host
+}  // namespace secedo
+
+namespace {
 
 // What one pileup call asks for; the four entry points differ in the chromosome list, the output files and the tag.
 struct Request {

@@ -1,0 +1,473 @@
+// bam_split.cpp -- secedo_bam_split_clusters of include/secedo_bam.h: one coordinate-sorted BAM per
+// cluster of a clustering. The inputs come through the pileup's input layer (bam_host.hpp: load_inputs, one ChrInput
+// per requested chromosome); per chromosome the records go up in input order and bam_split_kernels.hip turns them into
+// one stream, cluster after cluster, which the BGZF encoder (bgzf_deflate_kernels.hip) deflates member by member. Only
+// compressed bytes come back; they are appended to the clusters' temporary files. What decides bytes is in
+// bam_split.hpp.
+#include "bam_host.hpp"
+#include "bam_kernels.hpp"
+#include "bam_split.hpp"
+#include "bam_split_kernels.hpp"
+#include "bgzf_deflate.hpp"
+#include "bgzf_deflate_kernels.hpp"
+
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstdio>
+
+namespace {
+
+using namespace secedo::bam_host;
+namespace bam = secedo::bam;
+namespace bs = secedo::bamsplit;
+namespace bz = secedo::bgzf;
+
+static_assert(bs::kCut == bz::kCut, "bam_split.hpp cuts members where the encoder does");
+
+thread_local secedo_bam_split_info g_split{};
+
+// Members deflated per launch at the most: 256 MiB of slots, whatever the chromosome's size.
+constexpr size_t kSlice = 4096;
+// the gather's stream lies behind this much room (the encoder's 16-byte loads); keeps the stream 16-byte aligned
+constexpr uint64_t kFront = bz::kDeflateInSlack;
+static_assert(kFront % bs::kGatherVec == 0, "the gather stores whole aligned vectors");
+
+bool exists(const std::string &path) {
+    struct stat st;
+    return stat(path.c_str(), &st) == 0;
+}
+
+// The clusters' files: written under a temporary name beside the target, renamed by commit(). Whatever is left
+// uncommitted is removed. No file stays open between appends: there may be more clusters than descriptors.
+struct OutFiles {
+    std::vector<std::string> target, tmp;
+    bool committed = false;
+    OutFiles() = default;
+    OutFiles(const OutFiles &) = delete;
+    OutFiles &operator=(const OutFiles &) = delete;
+    ~OutFiles() {
+        if (!committed)
+            for (const std::string &t : tmp) (void)unlink(t.c_str());
+    }
+    int write(size_t k, const char *mode, const uint8_t *p, size_t n) {
+        FILE *f = fopen(tmp[k].c_str(), mode);
+        const bool ok = f && fwrite(p, 1, n, f) == n;
+        if ((f && fclose(f) != 0) || !ok) return fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp[k]);
+        return SECEDO_OK;
+    }
+    int open() {
+        const std::string suffix = ".tmp." + std::to_string(long(getpid()));
+        for (const std::string &t : target) {
+            tmp.push_back(t + suffix);
+            SECEDO_CALL(write(tmp.size() - 1, "wb", nullptr, 0));
+        }
+        return SECEDO_OK;
+    }
+    int append(size_t k, const uint8_t *p, size_t n) {
+        SECEDO_CALL(write(k, "ab", p, n));
+        g_split.compressed_bytes += n;
+        return SECEDO_OK;
+    }
+    int commit() {
+        // nothing is renamed before every file is complete; a rename that fails leaves the targets before it, which
+        // are complete files, and removes the rest
+        for (size_t k = 0; k < tmp.size(); ++k)
+            if (rename(tmp[k].c_str(), target[k].c_str()) != 0)
+                return fail(SECEDO_E_INVALID_ARG, "Could not rename " + tmp[k] + " to " + target[k]);
+        committed = true;
+        return SECEDO_OK;
+    }
+};
+
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+// The encoder's buffers, kept over the header and the chromosomes of one call.
+struct Encoder {
+    Buf desc, slots, size, at, packed;
+    std::vector<bz::DeflateDesc> h_desc;
+    std::vector<uint32_t> h_size;
+    std::vector<uint64_t> h_at;
+    std::vector<uint8_t> h_out;
+
+    size_t cap = 0;  // members the device buffers hold: grown to the largest slice met, at most kSlice
+
+    int reserve(size_t members) {
+        if (members <= cap) return SECEDO_OK;
+        SECEDO_TRY(desc.alloc(members * sizeof(bz::DeflateDesc)));
+        SECEDO_TRY(slots.alloc(members * size_t(bz::kDeflateSlot)));
+        SECEDO_TRY(size.alloc(members * 4));
+        SECEDO_TRY(at.alloc(members * 8));
+        h_desc.resize(members);
+        h_size.resize(members);
+        h_at.resize(members);
+        cap = members;
+        return SECEDO_OK;
+    }
+
+    // The members cuts[k] (offsets in the stream that starts kFront bytes into d_text) are deflated in slices and
+    // member k is appended to file owner[k]; owners ascend, so every file gets its members in stream order.
+    int run(const uint8_t *d_text, const std::vector<bs::Cut> &cuts, const std::vector<uint32_t> &owner, OutFiles *of,
+            hipStream_t s) {
+        SECEDO_CALL(reserve(std::min(kSlice, cuts.size())));
+        for (size_t b0 = 0; b0 < cuts.size(); b0 += kSlice) {
+            const uint32_t nb = uint32_t(std::min(kSlice, cuts.size() - b0));
+            Clock::time_point t0 = Clock::now();
+            for (uint32_t k = 0; k < nb; ++k) h_desc[k] = bz::DeflateDesc{kFront + cuts[b0 + k].off, cuts[b0 + k].n, 0};
+            SECEDO_TRY(hipMemcpyAsync(desc.p, h_desc.data(), nb * sizeof(bz::DeflateDesc), hipMemcpyHostToDevice, s));
+            SECEDO_TRY(bz::bgzf_deflate(d_text, desc.as<bz::DeflateDesc>(), nb, slots.as<uint8_t>(),
+                                        size.as<uint32_t>(), s));
+            SECEDO_TRY(hipMemcpyAsync(h_size.data(), size.p, nb * 4, hipMemcpyDeviceToHost, s));
+            SECEDO_TRY(hipStreamSynchronize(s));
+            uint64_t end = 0;
+            for (uint32_t k = 0; k < nb; ++k) {
+                const uint32_t bytes = h_size[k] & ~bz::kDeflateStoredFlag;
+                if (bytes < bz::kHeaderBytes + bz::kTrailerBytes || bytes > bz::kMaxMember)
+                    return fail(SECEDO_E_STATE, "BGZF encoder: a member of " + std::to_string(bytes) + " bytes");
+                g_split.stored_members += (h_size[k] & bz::kDeflateStoredFlag) != 0;
+                h_at[k] = end;
+                end += bytes;
+            }
+            g_split.members += nb;
+            if (packed.n < end) SECEDO_TRY(packed.alloc(end));
+            SECEDO_TRY(hipMemcpyAsync(at.p, h_at.data(), nb * 8, hipMemcpyHostToDevice, s));
+            SECEDO_TRY(bz::bgzf_pack(slots.as<uint8_t>(), size.as<uint32_t>(), at.as<uint64_t>(), nb,
+                                     packed.as<uint8_t>(), s));
+            SECEDO_TRY(hipStreamSynchronize(s));
+            g_split.deflate_ms += ms_lap(t0);
+            h_out.resize(end);
+            SECEDO_TRY(hipMemcpyAsync(h_out.data(), packed.p, end, hipMemcpyDeviceToHost, s));
+            SECEDO_TRY(hipStreamSynchronize(s));
+            g_split.download_ms += ms_lap(t0);
+            for (uint32_t k = 0; k < nb;) {  // the members of one file in one write
+                uint32_t e = k + 1;
+                while (e < nb && owner[b0 + e] == owner[b0 + k]) ++e;
+                const uint64_t stop = e < nb ? h_at[e] : end;
+                SECEDO_CALL(of->append(owner[b0 + k], h_out.data() + h_at[k], stop - h_at[k]));
+                k = e;
+            }
+            g_split.write_ms += ms_lap(t0);
+        }
+        return SECEDO_OK;
+    }
+};
+
+// What one call asks for, checked.
+struct Request {
+    std::vector<std::string> files, values;
+    std::vector<uint32_t> chr;  // sorted
+    std::vector<uint16_t> cell_cluster;
+    const char *tag = nullptr;
+    uint32_t n_clusters = 0;
+    uint32_t threads = 1;
+};
+
+// One chromosome: its records in HBM in input order -> the stream -> members appended to the clusters' files.
+int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList *cells, const uint16_t *d_cell_cluster,
+                     Encoder *enc, OutFiles *of, hipStream_t s, secedo_bam_times *t) {
+    Clock::time_point t0 = Clock::now();
+    std::vector<uint64_t> in_off;
+    std::vector<uint16_t> in_file;
+    for (size_t f = 0; f < ci.roff.size(); ++f)
+        for (size_t k = 0; k < ci.roff[f].size(); ++k) {
+            in_off.push_back(ci.file_base[f] + ci.roff[f][k]);
+            in_file.push_back(uint16_t(f));
+        }
+    if (in_off.size() >= (1ull << 32)) return fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome");
+    const uint32_t n_in = uint32_t(in_off.size());
+    t->walk_ms += ms_lap(t0);
+    if (n_in == 0) return SECEDO_OK;
+
+    // the gather reads whole aligned dwords: room behind the last record
+    Dev<uint8_t> d_bytes, tmp;
+    Dev<uint64_t> d_in_off;
+    Dev<uint16_t> d_file;
+    SECEDO_TRY(d_bytes.alloc(ci.bytes.size() + 16));
+    SECEDO_TRY(d_in_off.alloc(n_in));
+    SECEDO_TRY(hipMemcpyAsync(d_bytes.p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemsetAsync(d_bytes.p + ci.bytes.size(), 0, 16, s));
+    SECEDO_TRY(hipMemcpyAsync(d_in_off.p, in_off.data(), n_in * 8ull, hipMemcpyHostToDevice, s));
+    if (!cells) {
+        SECEDO_TRY(d_file.alloc(n_in));
+        SECEDO_TRY(hipMemcpyAsync(d_file.p, in_file.data(), n_in * 2ull, hipMemcpyHostToDevice, s));
+    }
+    SECEDO_TRY(hipStreamSynchronize(s));
+    t->upload_ms += ms_lap(t0);
+
+    // keys, compaction, order
+    const uint32_t n_cells = uint32_t(rq.cell_cluster.size());
+    Dev<uint64_t> tag_key, key, kc, ks;
+    Dev<uint32_t> tag_sel, sel, scan, vc, vs;
+    SECEDO_TRY(key.alloc(n_in));
+    SECEDO_TRY(sel.alloc(size_t(n_in) + 1));
+    if (cells) {  // rule 3b of bam_kernels.hip, its flag filter off: the cell of each record from its tag
+        SECEDO_TRY(tag_key.alloc(n_in));
+        SECEDO_TRY(tag_sel.alloc(n_in));
+        SECEDO_TRY(bam::cells(d_bytes.p, d_in_off.p, n_in, *cells, 0, 0, tag_key.p, tag_sel.p, nullptr, s));
+    }
+    SECEDO_TRY(bs::split_keys(d_bytes.p, d_in_off.p, n_in, d_file.p, tag_key.p, tag_sel.p, d_cell_cluster, n_cells,
+                              key.p, sel.p, s));
+    size_t tb = bam::scan_bytes(uint64_t(n_in) + 1);
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(scan.alloc(size_t(n_in) + 1));
+    SECEDO_TRY(hipMemsetAsync(sel.p + n_in, 0, 4, s));
+    SECEDO_TRY(bam::exclusive_sum(tmp.p, tb, sel.p, scan.p, uint64_t(n_in) + 1, s));
+    uint32_t m = 0;
+    SECEDO_TRY(hipMemcpyAsync(&m, scan.p + n_in, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    g_split.dropped_records += n_in - m;
+    if (m == 0) {
+        g_split.order_ms += ms_lap(t0);
+        return SECEDO_OK;
+    }
+    SECEDO_TRY(kc.alloc(m));
+    SECEDO_TRY(vc.alloc(m));
+    SECEDO_TRY(ks.alloc(m));
+    SECEDO_TRY(vs.alloc(m));
+    SECEDO_TRY(bam::compact_keys(key.p, sel.p, scan.p, n_in, kc.p, vc.p, s));
+    tb = bs::split_sort_bytes(m);
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(bs::split_sort(tmp.p, tb, kc.p, ks.p, vc.p, vs.p, m, bs::key_bits(rq.n_clusters - 1), s));
+    // destinations and extents
+    Dev<uint64_t> src, len, dst, beg;
+    SECEDO_TRY(src.alloc(m));
+    SECEDO_TRY(len.alloc(size_t(m) + 1));
+    SECEDO_TRY(dst.alloc(size_t(m) + 1));
+    SECEDO_TRY(beg.alloc(rq.n_clusters));
+    SECEDO_TRY(bs::split_lengths(d_bytes.p, d_in_off.p, vs.p, m, src.p, len.p, s));
+    tb = bam::scan_bytes(uint64_t(m) + 1);
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(bam::exclusive_sum64(tmp.p, tb, len.p, dst.p, uint64_t(m) + 1, s));
+    SECEDO_TRY(hipMemsetAsync(beg.p, 0xFF, rq.n_clusters * 8ull, s));
+    SECEDO_TRY(bs::split_extents(ks.p, dst.p, m, beg.p, s));
+    std::vector<uint64_t> h_beg(size_t(rq.n_clusters) + 1);
+    uint64_t total = 0;
+    SECEDO_TRY(hipMemcpyAsync(h_beg.data(), beg.p, rq.n_clusters * 8ull, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(&total, dst.p + m, 8, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    if (total > ci.bytes.size()) return fail(SECEDO_E_STATE, "split: the stream is longer than the chromosome's records");
+    g_split.order_ms += ms_lap(t0);
+    key.reset(), sel.reset(), scan.reset(), kc.reset(), vc.reset(), ks.reset(), vs.reset(), len.reset();
+    tag_key.reset(), tag_sel.reset(), tmp.reset();
+
+    // the gather: every byte of the stream read once and written once
+    const uint64_t padded = (total + bs::kGatherVec - 1) / bs::kGatherVec * bs::kGatherVec;
+    Dev<uint8_t> out;
+    SECEDO_TRY(out.alloc(kFront + padded + bz::kDeflateInSlack));
+    SECEDO_TRY(hipMemsetAsync(out.p, 0, kFront, s));
+    SECEDO_TRY(hipMemsetAsync(out.p + kFront + padded, 0, bz::kDeflateInSlack, s));
+    Events ev;
+    SECEDO_TRY(hipEventCreate(&ev.a));
+    SECEDO_TRY(hipEventCreate(&ev.b));
+    SECEDO_TRY(hipEventRecord(ev.a, s));
+    SECEDO_TRY(bs::split_gather(d_bytes.p, src.p, dst.p, m, total, out.p + kFront, s));
+    SECEDO_TRY(hipEventRecord(ev.b, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    float g_ms = 0;
+    SECEDO_TRY(hipEventElapsedTime(&g_ms, ev.a, ev.b));
+    g_split.gather_ms += g_ms;
+    d_bytes.reset(), d_in_off.reset(), d_file.reset(), src.reset(), dst.reset();
+    (void)ms_lap(t0);
+
+    // a cluster without records of this chromosome starts where the next one does
+    h_beg[rq.n_clusters] = total;
+    for (uint32_t c = rq.n_clusters; c-- > 0;)
+        if (h_beg[c] == ~0ull) h_beg[c] = h_beg[c + 1];
+    std::vector<bs::Cut> cuts;
+    std::vector<uint32_t> owner;
+    for (uint32_t c = 0; c < rq.n_clusters; ++c) {
+        bs::member_cuts(h_beg[c], h_beg[c + 1], &cuts);
+        owner.resize(cuts.size(), c);
+    }
+    const double before = g_split.deflate_ms + g_split.download_ms;
+    const double w_before = g_split.write_ms;
+    SECEDO_CALL(enc->run(out.p, cuts, owner, of, s));
+    t->device_ms += g_ms + (g_split.deflate_ms + g_split.download_ms - before);
+    t->write_ms += g_split.write_ms - w_before;
+    g_split.records += m;
+    g_split.text_bytes += total;
+    return SECEDO_OK;
+}
+
+// The headers of the inputs, checked against each other -> the header bytes of every cluster's file.
+int make_headers(const Request &rq, std::vector<std::vector<uint8_t>> *headers) {
+    std::vector<bs::Ref> first;
+    std::vector<uint8_t> first_list;
+    std::vector<std::string> texts;
+    for (size_t f = 0; f < rq.files.size(); ++f) {
+        FileHeader h;
+        SECEDO_CALL(read_file_header(rq.files[f], &h));
+        std::vector<bs::Ref> refs;
+        if (h.sam) refs = bs::refs_from_text(h.text);
+        else if (!bs::parse_ref_list(h.ref_list.data(), h.ref_list.size(), h.n_ref, &refs))
+            return fail(SECEDO_E_INVALID_ARG, rq.files[f] + ": truncated reference list");
+        if (f == 0) {
+            first = refs;
+            first_list = h.sam ? bs::ref_list_bytes(refs) : h.ref_list;
+        } else {
+            const std::string why = bs::refs_differ(first, refs);
+            if (!why.empty())
+                return fail(SECEDO_E_INVALID_ARG, rq.files[f] + ": its reference list is not that of the first file " +
+                                                      rq.files[0] + ": " + why);
+        }
+        texts.push_back(h.text);
+    }
+    for (uint32_t c : rq.chr)
+        if (c >= first.size())
+            return fail(SECEDO_E_INVALID_ARG, "chromosome id " + std::to_string(c) + " is at or past the " +
+                                                  std::to_string(first.size()) + " references of " +
+                                                  (rq.files.empty() ? std::string("the input") : rq.files[0]));
+    bs::RgMerge rg;
+    size_t a = 0, b = 0;
+    std::string id;
+    if (!bs::merge_rg(texts, &rg, &a, &b, &id))
+        return fail(SECEDO_E_INVALID_ARG, "@RG ID:" + id + " names different lines in " + rq.files[a] + " and " +
+                                              rq.files[b]);
+    std::vector<uint32_t> members(rq.n_clusters, 0);
+    for (uint16_t c : rq.cell_cluster) ++members[c];
+    for (uint32_t k = 0; k < rq.n_clusters; ++k)
+        headers->push_back(bs::header_bytes(
+            bs::header_text(first, rg.lines, k, members[k], uint32_t(rq.cell_cluster.size())), uint32_t(first.size()),
+            first_list));
+    return SECEDO_OK;
+}
+
+// the headers' members: the same encoder, once per file
+int write_headers(const std::vector<std::vector<uint8_t>> &headers, Encoder *enc, OutFiles *of, hipStream_t s) {
+    std::vector<uint8_t> all(kFront, 0);
+    std::vector<bs::Cut> cuts;
+    std::vector<uint32_t> owner;
+    for (size_t k = 0; k < headers.size(); ++k) {
+        const uint64_t beg = all.size() - kFront;
+        all.insert(all.end(), headers[k].begin(), headers[k].end());
+        bs::member_cuts(beg, all.size() - kFront, &cuts);
+        owner.resize(cuts.size(), uint32_t(k));
+        g_split.text_bytes += headers[k].size();
+    }
+    all.resize(all.size() + bz::kDeflateInSlack, 0);
+    Dev<uint8_t> d;
+    SECEDO_TRY(d.alloc(all.size()));
+    SECEDO_TRY(hipMemcpyAsync(d.p, all.data(), all.size(), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    return enc->run(d.p, cuts, owner, of, s);
+}
+
+int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids, uint32_t n_chr,
+          const uint16_t *cell_cluster, uint32_t n_cells, const char *tag, const char *const *barcodes,
+          uint32_t n_barcodes, const char *out_dir, int overwrite, uint32_t num_threads, secedo_bam_times *times) {
+    const Clock::time_point t_all = Clock::now();
+    secedo_bam_times tl{};
+    if ((n_files && !bam_files) || (n_chr && !chromosome_ids) || !cell_cluster || !out_dir)
+        return fail(SECEDO_E_INVALID_ARG, "null argument");
+    Request rq;
+    rq.tag = tag;
+    rq.threads = num_threads ? num_threads : 1;
+    if (n_files == 0) return fail(SECEDO_E_INVALID_ARG, "no input files");
+    if (n_cells == 0) return fail(SECEDO_E_INVALID_ARG, "an empty clustering");
+    if (tag) {
+        SECEDO_CALL(check_cells(tag, barcodes, n_barcodes, &rq.values));
+        if (n_cells != n_barcodes)
+            return fail(SECEDO_E_INVALID_ARG, "the clustering has " + std::to_string(n_cells) + " cells, the barcode "
+                                                  "list " + std::to_string(n_barcodes));
+    } else {
+        if (n_files > SECEDO_BAM_MAX_FILES)
+            return fail(SECEDO_E_LIMIT, "more than 16384 BAM files: cell ids do not fit 14 bits");
+        if (n_cells != n_files)
+            return fail(SECEDO_E_INVALID_ARG, "the clustering has " + std::to_string(n_cells) + " cells, there are " +
+                                                  std::to_string(n_files) + " files (one cell per file)");
+    }
+    SECEDO_CALL(check_files(bam_files, n_files, &rq.files));
+    rq.chr.assign(chromosome_ids, chromosome_ids + n_chr);
+    std::sort(rq.chr.begin(), rq.chr.end());
+    for (size_t c = 1; c < rq.chr.size(); ++c)
+        if (rq.chr[c] == rq.chr[c - 1])
+            return fail(SECEDO_E_INVALID_ARG, "chromosome id " + std::to_string(rq.chr[c]) + " is listed twice");
+    rq.cell_cluster.assign(cell_cluster, cell_cluster + n_cells);
+    rq.n_clusters = uint32_t(*std::max_element(rq.cell_cluster.begin(), rq.cell_cluster.end())) + 1;
+    g_split.files = n_files;
+    g_split.cells = n_cells;
+    g_split.clusters = rq.n_clusters;
+
+    const std::string dir(out_dir);
+    struct stat st;
+    if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode))
+        return fail(SECEDO_E_INVALID_ARG, dir + " is not a directory");
+    OutFiles of;
+    for (uint32_t k = 0; k < rq.n_clusters; ++k) {
+        of.target.push_back(dir + "/cluster_" + std::to_string(k) + ".bam");
+        if (!overwrite && exists(of.target.back()))
+            return fail(SECEDO_E_INVALID_ARG, of.target.back() + " exists; pass overwrite to replace it");
+    }
+
+    Inputs in;
+    SECEDO_CALL(load_inputs(rq.files, rq.chr.data(), n_chr, rq.threads, &in, &tl));
+    std::vector<std::vector<uint8_t>> headers;
+    SECEDO_CALL(make_headers(rq, &headers));
+
+    StreamGuard guard;
+    SECEDO_TRY(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    const hipStream_t s = guard.s;
+    Encoder enc;
+    Dev<uint16_t> d_cc;
+    SECEDO_TRY(d_cc.alloc(n_cells));
+    SECEDO_TRY(hipMemcpyAsync(d_cc.p, rq.cell_cluster.data(), n_cells * 2ull, hipMemcpyHostToDevice, s));
+    DevCells dc;
+    if (tag) SECEDO_CALL(upload_cells(tag, rq.values, s, &dc));
+    SECEDO_TRY(hipStreamSynchronize(s));
+
+    SECEDO_CALL(of.open());
+    {
+        const double w0 = g_split.write_ms, d0 = g_split.deflate_ms + g_split.download_ms;
+        SECEDO_CALL(write_headers(headers, &enc, &of, s));
+        tl.write_ms += g_split.write_ms - w0;
+        tl.device_ms += g_split.deflate_ms + g_split.download_ms - d0;
+    }
+    for (uint32_t c = 0; c < n_chr; ++c) {
+        const double o0 = g_split.order_ms;
+        SECEDO_CALL(split_chromosome(rq, in.chrs[c], tag ? &dc.list : nullptr, d_cc.p, &enc, &of, s, &tl));
+        tl.device_ms += g_split.order_ms - o0;
+        std::vector<uint8_t>().swap(in.chrs[c].bytes);
+    }
+    Clock::time_point t0 = Clock::now();
+    uint8_t eof[bz::kEofBytes];
+    for (uint32_t k = 0; k < bz::kEofBytes; ++k) eof[k] = uint8_t(bz::eof_member_byte(k));
+    for (uint32_t k = 0; k < rq.n_clusters; ++k) SECEDO_CALL(of.append(k, eof, sizeof eof));
+    SECEDO_CALL(of.commit());
+    const double w = ms_lap(t0);
+    g_split.write_ms += w;
+    tl.write_ms += w;
+    tl.total_ms = ms_since(t_all);
+    if (times) *times = tl;
+    return SECEDO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int secedo_bam_split_clusters(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                              uint32_t n_chr, const uint16_t *cell_cluster, uint32_t n_cells, const char tag[2],
+                              const char *const *barcodes, uint32_t n_barcodes, const char *out_dir, int overwrite,
+                              uint32_t num_threads, secedo_bam_split_info *info, secedo_bam_times *times) {
+    if (!info) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    g_split = secedo_bam_split_info{};
+    const int rc = split(bam_files, n_files, chromosome_ids, n_chr, cell_cluster, n_cells, tag, barcodes, n_barcodes,
+                         out_dir, overwrite, num_threads, times);
+    *info = g_split;
+    return rc;
+}
+
+int secedo_bam_split_stats(secedo_bam_split_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = g_split;
+    return SECEDO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,228 @@
+// bam_split.hpp -- everything that decides the bytes of secedo_bam_split_clusters (include/secedo_bam.h),
+// header-only, in plain C++ that g++ compiles alone (tests/cpp/bam_split_test.cpp runs it under the sanitizers): the
+// header every cluster_<k>.bam starts with (reference list, @RG merge, the fixed lines), the sort key of a record, the
+// member cuts of a cluster's extent, and the lookup from an output byte to the record that holds it, which the gather
+// kernel (bam_split_kernels.hip) compiles as device code. Failures come back as the reason's text.
+#pragma once
+
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define SPLIT_HD __host__ __device__ inline
+#else
+#define SPLIT_HD inline
+#endif
+
+namespace secedo {
+namespace bamsplit {
+
+// ---- the sort key of a record: cluster << 32 | Position. A stable sort of it over records in (file, record) order
+// gives (cluster, Position, file, record).
+
+SPLIT_HD uint64_t pack_key(uint32_t cluster, uint32_t pos) { return uint64_t(cluster) << 32 | pos; }
+SPLIT_HD uint32_t key_cluster(uint64_t key) { return uint32_t(key >> 32); }
+SPLIT_HD uint32_t key_pos(uint64_t key) { return uint32_t(key); }
+
+// the key bits in use with clusters 0..max_cluster: the radix sort's end bit
+inline int key_bits(uint32_t max_cluster) {
+    int b = 32;
+    while (b < 64 && (uint64_t(max_cluster) >> (b - 32)) != 0) ++b;
+    return b;
+}
+
+// ---- the gather's lookup. dst[0..n] are the ascending output offsets of the n records of the sorted order, dst[n] the
+// total. The record of output byte `b` is the last j in [lo, hi) with dst[j] <= b; the caller gives a range that holds
+// it (dst[lo] <= b, and hi == n or dst[hi] > b). Equal entries (records of no bytes, which BAM does not have, or the
+// entries of an empty tail) are skipped over: the last of them is taken.
+SPLIT_HD uint32_t record_of(const uint64_t *dst, uint32_t lo, uint32_t hi, uint64_t b) {
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (dst[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One workgroup of the gather writes kTileBytes of output. A record is at least kMinRecord bytes (block_size, the 32
+// fixed bytes and a name of one NUL), so the records that start inside a tile, and the one that reaches into it, are
+// at most kTileRecords; the lookup of every lane runs over that range only.
+constexpr uint32_t kGatherLanes = 256, kGatherVec = 16;
+constexpr uint32_t kTileBytes = kGatherLanes * kGatherVec;
+constexpr uint32_t kMinRecord = 4 + 32 + 1;
+constexpr uint32_t kTileRecords = kTileBytes / kMinRecord + 2;
+
+// ---- the member cuts of one extent [beg, end) of the output stream: every kCut bytes from its start
+
+constexpr uint32_t kCut = 0xFF00;  // bgzf::kCut; bam_split.cpp asserts they agree
+
+struct Cut {
+    uint64_t off;
+    uint32_t n;
+};
+
+inline void member_cuts(uint64_t beg, uint64_t end, std::vector<Cut> *out) {
+    for (uint64_t p = beg; p < end; p += kCut) out->push_back(Cut{p, uint32_t(end - p < kCut ? end - p : kCut)});
+}
+
+// ---- the header
+
+struct Ref {
+    std::string name;
+    uint32_t len = 0;
+    bool operator==(const Ref &o) const { return name == o.name && len == o.len; }
+};
+
+inline uint32_t rd32(const uint8_t *p) {
+    uint32_t v;
+    std::memcpy(&v, p, 4);
+    return v;
+}
+
+// the binary reference list of a BAM header (n_ref entries of l_name, name with its NUL, l_ref); false when cut short
+inline bool parse_ref_list(const uint8_t *p, uint64_t n, uint32_t n_ref, std::vector<Ref> *out) {
+    uint64_t o = 0;
+    for (uint32_t r = 0; r < n_ref; ++r) {
+        if (o + 4 > n) return false;
+        const uint64_t l = rd32(p + o);
+        if (o + 4 + l + 4 > n) return false;
+        Ref ref;
+        ref.name.assign(reinterpret_cast<const char *>(p + o + 4), l);
+        const size_t nul = ref.name.find('\0');
+        if (nul != std::string::npos) ref.name.resize(nul);
+        ref.len = rd32(p + o + 4 + l);
+        out->push_back(ref);
+        o += 4 + l + 4;
+    }
+    return true;
+}
+
+// the lines of a header text, without their '\n' (and without a '\r' in front of it, or NULs that pad the text)
+inline std::vector<std::string> text_lines(const std::string &text) {
+    std::vector<std::string> out;
+    size_t a = 0;
+    while (a < text.size()) {
+        size_t b = text.find('\n', a);
+        if (b == std::string::npos) b = text.size();
+        std::string line = text.substr(a, b - a);
+        while (!line.empty() && (line.back() == '\r' || line.back() == '\0')) line.pop_back();
+        if (!line.empty()) out.push_back(line);
+        a = b + 1;
+    }
+    return out;
+}
+
+inline bool is_line(const std::string &line, const char *type) {
+    return line.compare(0, 3, type) == 0 && (line.size() == 3 || line[3] == '\t');
+}
+
+// the value of field "XX:" of a header line, or "" (the first one counts)
+inline std::string line_field(const std::string &line, const char *key) {
+    for (size_t a = line.find('\t'); a != std::string::npos; a = line.find('\t', a + 1)) {
+        if (line.compare(a + 1, 3, key) != 0) continue;
+        const size_t e = line.find('\t', a + 1);
+        return line.substr(a + 4, e == std::string::npos ? std::string::npos : e - a - 4);
+    }
+    return std::string();
+}
+
+// the reference list a SAM header's @SQ lines give (SN, LN), in line order: what the BAM made from it holds
+inline std::vector<Ref> refs_from_text(const std::string &text) {
+    std::vector<Ref> out;
+    for (const std::string &line : text_lines(text)) {
+        if (!is_line(line, "@SQ")) continue;
+        Ref r;
+        r.name = line_field(line, "SN:");
+        r.len = uint32_t(std::strtoull(line_field(line, "LN:").c_str(), nullptr, 10));
+        out.push_back(r);
+    }
+    return out;
+}
+
+// Why file f's reference list is not the first file's ("" when it is): the count, or the first entry that differs.
+inline std::string refs_differ(const std::vector<Ref> &first, const std::vector<Ref> &other) {
+    if (first.size() != other.size())
+        return std::to_string(other.size()) + " references, the first file has " + std::to_string(first.size());
+    for (size_t r = 0; r < first.size(); ++r)
+        if (!(first[r] == other[r]))
+            return "reference " + std::to_string(r) + " is " + other[r].name + " of length " +
+                   std::to_string(other[r].len) + ", in the first file " + first[r].name + " of length " +
+                   std::to_string(first[r].len);
+    return std::string();
+}
+
+// The @RG lines of all inputs, distinct whole lines in order of first appearance (files in list order, lines in header
+// order). Two different lines with one ID: false, *clash_a < *clash_b the two files and *clash_id the ID.
+struct RgMerge {
+    std::vector<std::string> lines;
+    std::vector<size_t> file;  // where each was seen first
+};
+
+inline bool merge_rg(const std::vector<std::string> &texts, RgMerge *out, size_t *clash_a, size_t *clash_b,
+                     std::string *clash_id) {
+    for (size_t f = 0; f < texts.size(); ++f)
+        for (const std::string &line : text_lines(texts[f])) {
+            if (!is_line(line, "@RG")) continue;
+            const std::string id = line_field(line, "ID:");
+            bool known = false;
+            for (size_t k = 0; k < out->lines.size() && !known; ++k) {
+                if (out->lines[k] == line) known = true;
+                else if (line_field(out->lines[k], "ID:") == id) {
+                    *clash_a = out->file[k];
+                    *clash_b = f;
+                    *clash_id = id;
+                    return false;
+                }
+            }
+            if (known) continue;
+            out->lines.push_back(line);
+            out->file.push_back(f);
+        }
+    return true;
+}
+
+// the text of cluster k's header: m of the n cells are in the cluster
+inline std::string header_text(const std::vector<Ref> &refs, const std::vector<std::string> &rg, uint32_t k, uint32_t m,
+                               uint32_t n) {
+    std::string t = "@HD\tVN:1.6\tSO:coordinate\n";
+    for (const Ref &r : refs) t += "@SQ\tSN:" + r.name + "\tLN:" + std::to_string(r.len) + "\n";
+    for (const std::string &line : rg) t += line + "\n";
+    t += "@PG\tID:secedo_amd.split\tPN:secedo_amd\n";
+    t += "@CO\tsecedo_amd cluster " + std::to_string(k) + ": " + std::to_string(m) + " of " + std::to_string(n) +
+         " cells\n";
+    return t;
+}
+
+// "BAM\1", l_text, the text, n_ref and the first file's binary reference list as it stands
+inline std::vector<uint8_t> header_bytes(const std::string &text, uint32_t n_ref, const std::vector<uint8_t> &ref_list) {
+    std::vector<uint8_t> out{'B', 'A', 'M', 1};
+    const auto put32 = [&](uint32_t v) {
+        for (int k = 0; k < 4; ++k) out.push_back(uint8_t(v >> (8 * k)));
+    };
+    put32(uint32_t(text.size()));
+    out.insert(out.end(), text.begin(), text.end());
+    put32(n_ref);
+    out.insert(out.end(), ref_list.begin(), ref_list.end());
+    return out;
+}
+
+// the binary reference list of `refs` (SAM inputs have none of their own)
+inline std::vector<uint8_t> ref_list_bytes(const std::vector<Ref> &refs) {
+    std::vector<uint8_t> out;
+    const auto put32 = [&](uint32_t v) {
+        for (int k = 0; k < 4; ++k) out.push_back(uint8_t(v >> (8 * k)));
+    };
+    for (const Ref &r : refs) {
+        put32(uint32_t(r.name.size() + 1));
+        out.insert(out.end(), r.name.begin(), r.name.end());
+        out.push_back(0);
+        put32(r.len);
+    }
+    return out;
+}
+
+}  // namespace bamsplit
+}  // namespace secedo

@@ -1,0 +1,188 @@
+// bam_split_kernels.hip -- the device passes of secedo_bam_split_clusters (include/secedo_bam.h), gfx950.
+//
+// Per requested chromosome the records lie in HBM in input order (file, record), with the byte offset of each. The
+// passes turn them into one output stream, cluster after cluster, each cluster's records in (Position, file, record)
+// order, byte for byte as they came:
+//   k_split_keys     one thread per record: cell -> cluster, key = cluster << 32 | Position, sel = the record has a cell
+//   (scan, compaction: bam_kernels.hip's; stable radix sort of (key, ordinal) over the key bits in use: hipcub)
+//   k_split_lengths  one thread per sorted record: where it lies and how long it is (4 + block_size)
+//   (exclusive sum of the lengths: each record's destination, the total last)
+//   k_split_extents  one thread per sorted record: a cluster's first record gives where the cluster starts
+//   k_split_gather   one thread per 16 output bytes: the bandwidth pass
+//
+// The gather is balanced over output bytes, not over records: lane i of a workgroup writes bytes [16 i, 16 i + 16) of
+// the workgroup's 4 KiB tile with one aligned 16-byte store, so a wave's store instruction covers 1 KiB contiguous
+// bytes, and a 70 KB record is spread over 18 workgroups like any other bytes. Which record holds an output byte is a
+// binary search in the destination offsets: lane 0 searches all of them once for the tile's first byte, every lane then
+// searches only the records that can start inside the tile (bam_split.hpp: kTileRecords, at most 7 steps, L1/L2 hits).
+// The source side is at arbitrary byte alignment: a lane whose 16 bytes lie in one record reads the five aligned dwords
+// that cover them and shifts (consecutive lanes read consecutive dwords, so the loads coalesce as the stores do); a
+// lane on a record boundary, and the stream's last lane, assemble their dwords byte by byte.
+#include "bam_split.hpp"
+#include "bam_split_kernels.hpp"
+
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+namespace secedo {
+namespace bamsplit {
+namespace {
+
+constexpr int kBlock = 256;
+
+__device__ __forceinline__ uint32_t ld32(const uint8_t *p) {
+    return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
+}
+
+__global__ void __launch_bounds__(kBlock) k_split_keys(const uint8_t *__restrict__ bytes,
+                                                       const uint64_t *__restrict__ in_off, uint32_t n,
+                                                       const uint16_t *__restrict__ file,
+                                                       const uint64_t *__restrict__ tag_key,
+                                                       const uint32_t *__restrict__ tag_sel,
+                                                       const uint16_t *__restrict__ cell_cluster, uint32_t n_cells,
+                                                       uint64_t *__restrict__ key, uint32_t *__restrict__ sel) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o >= n) return;
+    uint32_t cell = ~0u;
+    if (tag_key) {
+        if (tag_sel[o]) cell = uint32_t(tag_key[o] >> 32) & 0x3FFF;  // chunk << 46 | cell << 32 | Position
+    } else {
+        cell = file[o];
+    }
+    const bool ok = cell < n_cells;
+    const uint32_t pos = ld32(bytes + in_off[o] + 4 + 4);  // >= 0: the input layer refuses negative positions
+    key[o] = ok ? pack_key(cell_cluster[cell], pos) : 0;
+    sel[o] = ok ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(kBlock) k_split_lengths(const uint8_t *__restrict__ bytes,
+                                                          const uint64_t *__restrict__ in_off,
+                                                          const uint32_t *__restrict__ val, uint32_t m,
+                                                          uint64_t *__restrict__ src, uint64_t *__restrict__ len) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j > m) return;
+    if (j == m) {
+        len[m] = 0;
+        return;
+    }
+    const uint64_t off = in_off[val[j]];
+    src[j] = off;
+    len[j] = 4ull + ld32(bytes + off);
+}
+
+__global__ void __launch_bounds__(kBlock) k_split_extents(const uint64_t *__restrict__ key,
+                                                          const uint64_t *__restrict__ dst, uint32_t m,
+                                                          uint64_t *__restrict__ beg) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t c = key_cluster(key[j]);
+    if (j == 0 || key_cluster(key[j - 1]) != c) beg[c] = dst[j];
+}
+
+// the dword at byte address p + s of an array whose base p is dword-aligned: two aligned loads and a shift
+__device__ __forceinline__ uint32_t dword_at(const uint32_t *__restrict__ w, uint64_t s) {
+    const uint64_t k = s >> 2;
+    const uint64_t pair = uint64_t(w[k + 1]) << 32 | w[k];
+    return uint32_t(pair >> (8 * uint32_t(s & 3)));
+}
+
+__global__ void __launch_bounds__(kGatherLanes) k_split_gather(const uint8_t *__restrict__ bytes,
+                                                               const uint64_t *__restrict__ src,
+                                                               const uint64_t *__restrict__ dst, uint32_t m,
+                                                               uint64_t total, uint8_t *__restrict__ out) {
+    __shared__ uint32_t s_first;
+    const uint64_t tile = uint64_t(blockIdx.x) * kTileBytes;
+    if (threadIdx.x == 0) s_first = record_of(dst, 0, m, tile);
+    __syncthreads();
+    const uint64_t b = tile + uint64_t(threadIdx.x) * kGatherVec;
+    if (b >= total) return;
+    const uint32_t lo = s_first;
+    const uint32_t hi = uint64_t(lo) + kTileRecords < m ? lo + kTileRecords : m;
+    uint32_t j = record_of(dst, lo, hi, b);
+    uint64_t d0 = dst[j], d1 = dst[j + 1], s0 = src[j];
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(bytes);
+    uint32_t v[4];
+    if (b + kGatherVec <= d1) {  // all 16 bytes in record j: five aligned dwords cover them
+        const uint64_t s = s0 + (b - d0);
+        const uint64_t k = s >> 2;
+        const uint32_t sh = 8 * uint32_t(s & 3);
+        uint32_t x[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) x[i] = w[k + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = uint32_t((uint64_t(x[i + 1]) << 32 | x[i]) >> sh);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t p = b + 4 * i;
+            while (p < total && p >= d1) {  // p < total = dst[m]: j + 1 <= m stays inside dst
+                ++j;
+                d0 = d1, d1 = dst[j + 1], s0 = src[j];
+            }
+            if (p + 4 <= d1) {
+                v[i] = dword_at(w, s0 + (p - d0));
+                continue;
+            }
+            uint32_t x = 0;
+            for (uint32_t q = 0; q < 4 && p + q < total; ++q) {
+                while (p + q >= d1) {
+                    ++j;
+                    d0 = d1, d1 = dst[j + 1], s0 = src[j];
+                }
+                x |= uint32_t(bytes[s0 + (p + q - d0)]) << (8 * q);
+            }
+            v[i] = x;
+        }
+    }
+    *reinterpret_cast<uint4 *>(out + b) = make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+inline uint32_t grid(uint64_t n) { return uint32_t((n + kBlock - 1) / kBlock); }
+
+}  // namespace
+
+hipError_t split_keys(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const uint16_t *d_file,
+                      const uint64_t *d_tag_key, const uint32_t *d_tag_sel, const uint16_t *d_cell_cluster,
+                      uint32_t n_cells, uint64_t *d_key, uint32_t *d_sel, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_split_keys<<<grid(n), kBlock, 0, s>>>(d_bytes, d_in_off, n, d_file, d_tag_key, d_tag_sel, d_cell_cluster,
+                                            n_cells, d_key, d_sel);
+    return hipGetLastError();
+}
+
+size_t split_sort_bytes(uint32_t n) {
+    size_t b = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                                             (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n));
+    return b;
+}
+
+hipError_t split_sort(void *tmp, size_t bytes, const uint64_t *k_in, uint64_t *k_out, const uint32_t *v_in,
+                      uint32_t *v_out, uint32_t n, int end_bit, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k_in, k_out, v_in, v_out, int(n), 0, end_bit, s);
+}
+
+hipError_t split_lengths(const uint8_t *d_bytes, const uint64_t *d_in_off, const uint32_t *d_val, uint32_t m,
+                         uint64_t *d_src, uint64_t *d_len, hipStream_t s) {
+    k_split_lengths<<<grid(uint64_t(m) + 1), kBlock, 0, s>>>(d_bytes, d_in_off, d_val, m, d_src, d_len);
+    return hipGetLastError();
+}
+
+hipError_t split_extents(const uint64_t *d_key, const uint64_t *d_dst, uint32_t m, uint64_t *d_beg, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    k_split_extents<<<grid(m), kBlock, 0, s>>>(d_key, d_dst, m, d_beg);
+    return hipGetLastError();
+}
+
+hipError_t split_gather(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst, uint32_t m,
+                        uint64_t total, uint8_t *d_out, hipStream_t s) {
+    if (m == 0 || total == 0) return hipSuccess;
+    const uint64_t tiles = (total + kTileBytes - 1) / kTileBytes;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    k_split_gather<<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, m, total, d_out);
+    return hipGetLastError();
+}
+
+}  // namespace bamsplit
+}  // namespace secedo

@@ -1,0 +1,106 @@
+"""``python -m secedo_amd.split_main``: one coordinate-sorted BAM per cluster of a clustering, on the GPU.
+
+After ``secedo_main`` has clustered the cells, this puts each subclone's reads back together as a pseudo-bulk BAM:
+``<o>/cluster_<k>.bam`` for every k in 0..max(clustering) holds the records of the cells of cluster k on the requested
+chromosomes, merged in coordinate order, byte for byte as they are in the input (``secedo_amd.split_clusters``; the
+layout of the files is fixed, see include/secedo_bam.h). A cluster number no cell has gives a header-only file.
+
+-i is the input of ``pileup_main`` (a BAM, SAM or bgzipped SAM file, or a directory searched for them, in the same
+sorted order), so cell i here is cell i there. --clustering FILE is the comma-separated file ``secedo_main`` writes:
+the cluster of each cell. With --cell_tag TG the inputs are multiplexed BAMs and --cells FILE lists the barcodes, one
+per line, cell c being line c; records without a listed barcode are dropped. --chromosomes, --inflate, --index and
+--build_index are ``pileup_main``'s. --bai also writes ``cluster_<k>.bam.bai``. Existing outputs are refused unless
+--overwrite.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from typing import List, Optional
+
+from .pileup_main import (DEFAULT_CHROMOSOMES, MAX_CELLS, build_missing_indexes, check_index_flags, chromosome_to_id,
+                          input_files, pool_size, read_cells, valid_tag)
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    ap = argparse.ArgumentParser(prog="python -m secedo_amd.split_main", description=__doc__.splitlines()[0])
+    ap.add_argument("-i", required=True, help="Input BAM, SAM or bgzipped SAM file, or a directory of them, as for "
+                                              "pileup_main")
+    ap.add_argument("--clustering", required=True, help="Comma-separated cluster of each cell, as secedo_main writes")
+    ap.add_argument("-o", default="./", help="Output directory: <o>/cluster_<k>.bam")
+    ap.add_argument("--chromosomes", default=DEFAULT_CHROMOSOMES, help="Comma-separated chromosomes (1..22, X, Y)")
+    ap.add_argument("--cell_tag", default=None, help="Multiplexed input: the aux tag naming a record's cell (e.g. CB)")
+    ap.add_argument("--cells", default=None, help="With --cell_tag: file of barcodes, one per line; cell c is line c")
+    ap.add_argument("--inflate", choices=("host", "device"), default=None,
+                    help="Where BAM files are inflated and their records walked; the outputs are the same")
+    ap.add_argument("--index", choices=("off", "auto", "require"), default=None,
+                    help="Read BAM files through their .bai index; the outputs are the same")
+    ap.add_argument("--build_index", action="store_true",
+                    help="Before the run, write <bam>.bai on the GPU for every input BAM without an index file")
+    ap.add_argument("--bai", action="store_true", help="Also write cluster_<k>.bam.bai for every output")
+    ap.add_argument("--overwrite", action="store_true", help="Replace existing cluster_<k>.bam files")
+    ap.add_argument("--num_threads", type=int, default=8, help="Host inflate threads (at most 16 are used)")
+    return ap.parse_args(argv)
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    a = parse_args(argv)
+    # everything below is checked before any BAM is read and before torch is imported
+    if not os.path.isfile(a.clustering):
+        raise SystemExit("--clustering file %s does not exist" % a.clustering)
+    cells = None
+    if a.cell_tag is None:
+        if a.cells is not None:
+            raise SystemExit("--cells needs --cell_tag")
+    else:
+        if not valid_tag(a.cell_tag):
+            raise SystemExit("Invalid --cell_tag %r: two characters [A-Za-z][A-Za-z0-9]" % a.cell_tag)
+        if a.cells is None:
+            raise SystemExit("--cell_tag needs --cells: the clustering numbers the cells by their line in that file")
+        if not os.path.isfile(a.cells):
+            raise SystemExit("--cells file %s does not exist" % a.cells)
+        cells = read_cells(a.cells)
+        if not cells:
+            raise SystemExit("--cells file %s lists no barcode" % a.cells)
+        if len(cells) > MAX_CELLS:
+            raise SystemExit("%d cells: at most %d are supported" % (len(cells), MAX_CELLS))
+    check_index_flags(a)
+    if not os.path.exists(a.i):
+        raise SystemExit("Input %s does not exist" % a.i)
+    files = input_files(a.i)
+    if not files:
+        raise SystemExit("No BAM or SAM files found in %s" % a.i)
+    from .bam_pileup import read_clustering  # imports no torch
+
+    try:
+        clustering = read_clustering(a.clustering)
+    except ValueError as e:
+        raise SystemExit("--clustering file %s" % e)
+    n_cells = len(files) if cells is None else len(cells)
+    if len(clustering) != n_cells:
+        raise SystemExit("--clustering file %s lists %d cells, the input has %d%s"
+                         % (a.clustering, len(clustering), n_cells, "" if cells is not None else " (one per file)"))
+    if not os.path.isdir(a.o):
+        raise SystemExit("-o %s is not a directory" % a.o)
+    outs = [os.path.join(a.o, "cluster_%d.bam" % k) for k in range(max(clustering) + 1)]
+    there = [o for o in outs if os.path.exists(o)]
+    if there and not a.overwrite:
+        raise SystemExit("%s exists; pass --overwrite to replace it" % there[0])
+    ids = [chromosome_to_id(c) for c in a.chromosomes.split(",")]
+    if a.build_index:
+        build_missing_indexes(files, pool_size(a.num_threads))
+    from .bam_pileup import split_clusters
+
+    tag_kw = {} if a.cell_tag is None else dict(cell_tag=a.cell_tag, cells=cells)
+    st = split_clusters(files, clustering, a.o, ids, inflate=a.inflate, index=a.index, bai=a.bai,
+                        overwrite=a.overwrite, num_threads=pool_size(a.num_threads), **tag_kw)
+    print("Written %d records of %d cells to %d files %s (%d bytes, %d BGZF members, %d of them stored)%s"
+          % (st["records"], st["cells"], st["clusters"], os.path.join(a.o, "cluster_<k>.bam"), st["compressed_bytes"],
+             st["members"], st["stored_members"],
+             "; %d records without a listed barcode dropped" % st["dropped_records"] if cells is not None else ""))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
