@@ -81,7 +81,8 @@
  * the pseudo-bulk files of the subclones. The inputs are read as for a pileup call, every kind, route and index mode;
  * cell to cluster, the merged order (a stable radix sort), the gather of whole records into per-cluster streams and the
  * BGZF DEFLATE run on the GPU (secedo_amd/csrc/bam_split_kernels.hip, bgzf_deflate_kernels.hip), and only compressed
- * bytes come back. Records are copied byte for byte; the bytes of every output are fixed by the rules at the call.
+ * bytes come back. Records are copied byte for byte, or with secedo_bam_split_clusters_rg with an RG tag that names
+ * their cell written inside the gather; the bytes of every output are fixed by the rules at the call.
  */
 #ifndef SECEDO_BAM_H
 #define SECEDO_BAM_H
@@ -305,12 +306,59 @@ typedef struct secedo_bam_split_info {
  * existing target is SECEDO_E_INVALID_ARG unless overwrite. A failed call leaves no temporaries and no new
  * cluster_*.bam. times is filled as the pileup calls fill it (write_ms: the outputs); secedo_bam_route_stats and
  * secedo_bam_index_stats are set as for a pileup call. num_threads: the host inflate pool. Not done: unplaced records,
- * RG/CB tags appended to records, merged cell groups, .csi, several GPUs. Synchronous. */
+ * CB tags appended to records (RG tags: secedo_bam_split_clusters_rg below), merged cell groups, .csi, several GPUs.
+ * Synchronous. */
 int secedo_bam_split_clusters(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
                               uint32_t n_chr, const uint16_t *cell_cluster, uint32_t n_cells, const char tag[2],
                               const char *const *barcodes, uint32_t n_barcodes, const char *out_dir, int overwrite,
                               uint32_t num_threads, secedo_bam_split_info *info, secedo_bam_times *times);
 int secedo_bam_split_stats(secedo_bam_split_info *out);
+
+/* What the last secedo_bam_split_clusters_rg call on this thread edited (also after a failure: up to it). All zero
+ * after a secedo_bam_split_clusters call. */
+typedef struct secedo_bam_split_rg_info {
+    uint64_t tagged_records;   /* records written with an appended RG */
+    uint64_t replaced_records; /* of those, the ones whose own RG field was removed */
+    uint64_t unparsed_records; /* of those, the ones whose aux area did not parse: nothing removed */
+    uint64_t added_bytes;      /* appended bytes, over all records */
+    uint64_t removed_bytes;    /* removed bytes, over all records */
+    uint64_t reserved[3];
+} secedo_bam_split_rg_info;
+
+/* secedo_bam_split_clusters with the cell of every read named in the files: one read group per cell. Everything of
+ * that call's contract holds (which records, their order, the layout M(header) M(chr) ... EOF, temporaries and
+ * renames, errors leave no file, the stats) except the three rules below; text_bytes and compressed_bytes count the
+ * edited bytes. The outputs are multiplexed BAMs: secedo_pileup_bams_cells with tag "RG" and a cluster's names reads
+ * one back cell by cell.
+ *
+ * 1. Cell names. cell_names NULL: the file's base name without the first of .sam.gz, .bam, .sam that it ends in
+ * (per-file mode), the barcode (tag mode). Else n_names must equal n_cells. A name, given or default, is 1 to 254
+ * bytes, every byte in 0x21..0x7E, and no two cells share one; else SECEDO_E_INVALID_ARG naming the cell index, or both
+ * for a clash. The names are checked before any input is read.
+ *
+ * 2. Header. The inputs' @RG lines are not carried (the tags that referred to them are removed, and their IDs cannot
+ * clash). In their place, between the @SQ lines and @PG, cluster k's file has one "@RG\tID:<name>\tSM:cluster_<k>" per
+ * cell of cluster k, in cell order.
+ *
+ * 3. Records. The aux area of a written record is walked strictly: a field is a two-byte tag, a type byte and a value
+ * (A c C: 1 byte; s S: 2; i I f: 4; Z H: up to and including the NUL; B: a subtype byte, a u32 count, count elements of
+ * the subtype's size); every field ends within the record and the walk ends exactly at its end. If it does, the first
+ * field named RG is removed whole (tag, type and value, whatever the type). If it does not (an unknown type, a field
+ * past the end, one or two bytes left), nothing is removed and the record counts in unparsed_records. In both cases
+ * 'R' 'G' 'Z' <name of the record's cell> '\0' is appended at the record's end and block_size becomes the new length
+ * minus 4; no other byte changes. RGZ inside another field's value means nothing. With tag "RG" the cell is found from
+ * the old value as ever, and the field is replaced like any other.
+ *
+ * The walk, the edited lengths and the gather that assembles the edited records run on the GPU
+ * (secedo_amd/csrc/bam_split_kernels.hip: k_split_plan, k_split_gather_rg; the rules in bam_split.hpp). Not done:
+ * unplaced records, CB tags, PL / LB fields of the @RG lines, merged cell groups. */
+int secedo_bam_split_clusters_rg(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                                 uint32_t n_chr, const uint16_t *cell_cluster, uint32_t n_cells, const char tag[2],
+                                 const char *const *barcodes, uint32_t n_barcodes, const char *out_dir, int overwrite,
+                                 uint32_t num_threads, secedo_bam_split_info *info, secedo_bam_times *times,
+                                 const char *const *cell_names, uint32_t n_names,
+                                 secedo_bam_split_rg_info *rg_info);
+int secedo_bam_split_rg_stats(secedo_bam_split_rg_info *out);
 
 /* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
  * num_threads: inflate pool size, capped at 16 (0 = 1). */

@@ -78,6 +78,11 @@ class SplitInfo(C.Structure):
                 [(k, C.c_double) for k in ("order_ms", "gather_ms", "deflate_ms", "download_ms", "write_ms")])
 
 
+class SplitRgInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("tagged_records", "replaced_records", "unparsed_records", "added_bytes",
+                                           "removed_bytes")] + [("reserved", C.c_uint64 * 3)])
+
+
 INFLATE_MODES = {"host": 0, "device": 1}
 INDEX_MODES = {"off": 0, "auto": 1, "require": 2}
 
@@ -120,6 +125,10 @@ SIGNATURES = {
     "secedo_bam_split_clusters": (C.c_int, [_files_t, _u32, _vp, _u32, _vp, _u32, C.c_char_p, _files_t, _u32,
                                             C.c_char_p, C.c_int, _u32, C.POINTER(SplitInfo), C.POINTER(Times)]),
     "secedo_bam_split_stats": (C.c_int, [C.POINTER(SplitInfo)]),
+    "secedo_bam_split_clusters_rg": (C.c_int, [_files_t, _u32, _vp, _u32, _vp, _u32, C.c_char_p, _files_t, _u32,
+                                               C.c_char_p, C.c_int, _u32, C.POINTER(SplitInfo), C.POINTER(Times),
+                                               _files_t, _u32, C.POINTER(SplitRgInfo)]),
+    "secedo_bam_split_rg_stats": (C.c_int, [C.POINTER(SplitRgInfo)]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
@@ -366,9 +375,23 @@ def split_stats() -> dict:
     return _split_dict(info)
 
 
+def _split_rg_dict(info: SplitRgInfo) -> dict:
+    return {k: int(getattr(info, k)) for k, _ in SplitRgInfo._fields_ if k != "reserved"}
+
+
+def split_rg_stats() -> dict:
+    """What the last ``split_clusters(..., read_groups=True)`` call on this thread edited, a failed one up to its
+    failure: tagged_records, replaced_records (their own RG field was removed), unparsed_records (the aux area did not
+    parse: nothing removed), added_bytes, removed_bytes. All zero after a call without ``read_groups``."""
+    info = SplitRgInfo()
+    check(lib().secedo_bam_split_rg_stats(C.byref(info)))
+    return _split_rg_dict(info)
+
+
 def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids: Sequence[int], *, cell_tag=None,
                    cells=None, inflate=None, index=None, bai: bool = False, overwrite: bool = False,
-                   num_threads: int = 8, times: Optional[dict] = None) -> dict:
+                   num_threads: int = 8, times: Optional[dict] = None, read_groups: bool = False,
+                   cell_names: Optional[Sequence[str]] = None) -> dict:
     """Writes ``<out_dir>/cluster_<k>.bam`` for every k in 0..max(clustering): the records of the cells of cluster k
     on the chromosomes ``chromosome_ids`` (RefIDs), merged in coordinate order (RefID, Position, input file, record),
     byte for byte as they are in the input; a k no cell has gives a header-only file. The pseudo-bulk BAMs of the
@@ -380,7 +403,16 @@ def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids
     records into per-cluster streams and the DEFLATE run on the GPU; the bytes of every file are fixed (see
     include/secedo_bam.h). All inputs must share one reference list. An existing output raises unless ``overwrite``; a
     failed call leaves no file behind. ``bai``: also write ``cluster_<k>.bam.bai`` with ``bam_index_build``.
-    -> the dict of ``split_stats()``; ``times`` (a dict) receives the step times in ms."""
+    ``read_groups``: name each read's cell in the files (secedo_bam_split_clusters_rg): every record gets
+    ``RG:Z:<name of its cell>`` as its last field in place of the RG field it had, and cluster k's header gets
+    ``@RG ID:<name> SM:cluster_<k>`` per cell of the cluster in place of the inputs' @RG lines; the edit runs on the
+    GPU inside the gather. ``cell_names``: one name per cell (1 to 254 bytes in 0x21..0x7E, no two equal); None names a
+    cell by its file's base name without .bam / .sam / .sam.gz, or by its barcode. The files are multiplexed BAMs that
+    ``pileup_bams(..., cell_tag="RG", cells=names)`` reads back cell by cell.
+    -> the dict of ``split_stats()``, with ``read_groups`` also the keys of ``split_rg_stats()``; ``times`` (a dict)
+    receives the step times in ms."""
+    if cell_names is not None and not read_groups:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "cell_names needs read_groups")
     arr, n = _files(bam_files)
     if isinstance(clustering, (str, bytes, os.PathLike)):
         try:
@@ -397,16 +429,24 @@ def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids
         import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
     except ImportError:
         pass
-    info, t = SplitInfo(), Times()
+    info, t, rg = SplitInfo(), Times(), SplitRgInfo()
+    args = (arr, n, _lib.ptr(ids) if len(ids) else None, len(ids), _lib.ptr(cl), len(cl), tag, bcs, n_bcs,
+            os.fsencode(str(out_dir)), int(bool(overwrite)), num_threads, C.byref(info), C.byref(t))
     with _route(inflate, index):
-        check(lib().secedo_bam_split_clusters(arr, n, _lib.ptr(ids) if len(ids) else None, len(ids), _lib.ptr(cl),
-                                              len(cl), tag, bcs, n_bcs, os.fsencode(str(out_dir)),
-                                              int(bool(overwrite)), num_threads, C.byref(info), C.byref(t)))
+        if read_groups:
+            names = None if cell_names is None else [_encode(x) for x in cell_names]
+            names_arr = None if names is None else (C.c_char_p * max(len(names), 1))(*names)
+            check(lib().secedo_bam_split_clusters_rg(*args, names_arr, 0 if names is None else len(names),
+                                                     C.byref(rg)))
+        else:
+            check(lib().secedo_bam_split_clusters(*args))
     if times is not None:
         times.update(_times(t))
     if bai:
         outs = [os.path.join(str(out_dir), "cluster_%d.bam" % k) for k in range(int(info.clusters))]
         bam_index_build(outs, overwrite=True, num_threads=max(1, min(int(num_threads), 16)))
+    if read_groups:
+        return dict(_split_dict(info), **_split_rg_dict(rg))
     return _split_dict(info)
 
 

@@ -3,7 +3,8 @@
 // per requested chromosome); per chromosome the records go up in input order and bam_split_kernels.hip turns them into
 // one stream, cluster after cluster, which the BGZF encoder (bgzf_deflate_kernels.hip) deflates member by member. Only
 // compressed bytes come back; they are appended to the clusters' temporary files. What decides bytes is in
-// bam_split.hpp.
+// bam_split.hpp. secedo_bam_split_clusters_rg is the same call with a gather that edits the records on
+// the way: every record gets RG:Z:<its cell's name>, the header one @RG line per cell of the cluster.
 #include "bam_host.hpp"
 #include "bam_kernels.hpp"
 #include "bam_split.hpp"
@@ -27,6 +28,7 @@ namespace bz = secedo::bgzf;
 static_assert(bs::kCut == bz::kCut, "bam_split.hpp cuts members where the encoder does");
 
 thread_local secedo_bam_split_info g_split{};
+thread_local secedo_bam_split_rg_info g_rg{};
 
 // Members deflated per launch at the most: 256 MiB of slots, whatever the chromosome's size.
 constexpr size_t kSlice = 4096;
@@ -167,11 +169,36 @@ struct Request {
     const char *tag = nullptr;
     uint32_t n_clusters = 0;
     uint32_t threads = 1;
+    bool rg = false;                 // the _rg call: records are edited, the header names the cells
+    std::vector<std::string> names;  // with rg: the read group of each cell
 };
+
+// The suffixes RGZ<name>\0 of all cells on the device, one after the other; off[c] .. off[c + 1] is cell c's.
+struct DevSuffixes {
+    Dev<uint8_t> bytes;
+    Dev<uint32_t> off;
+};
+
+int upload_suffixes(const std::vector<std::string> &names, hipStream_t s, DevSuffixes *ds) {
+    std::vector<uint8_t> bytes;
+    std::vector<uint32_t> off{0};
+    for (const std::string &n : names) {
+        const std::string suffix = bs::rg_suffix(n);
+        bytes.insert(bytes.end(), suffix.begin(), suffix.end());
+        off.push_back(uint32_t(bytes.size()));
+    }
+    bytes.resize(bytes.size() + 16, 0);  // room behind the last suffix, as behind the last record
+    SECEDO_TRY(ds->bytes.alloc(bytes.size()));
+    SECEDO_TRY(ds->off.alloc(off.size()));
+    SECEDO_TRY(hipMemcpyAsync(ds->bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(ds->off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    return SECEDO_OK;
+}
 
 // One chromosome: its records in HBM in input order -> the stream -> members appended to the clusters' files.
 int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList *cells, const uint16_t *d_cell_cluster,
-                     Encoder *enc, OutFiles *of, hipStream_t s, secedo_bam_times *t) {
+                     const DevSuffixes *suffixes, Encoder *enc, OutFiles *of, hipStream_t s, secedo_bam_times *t) {
     Clock::time_point t0 = Clock::now();
     std::vector<uint64_t> in_off;
     std::vector<uint16_t> in_file;
@@ -241,7 +268,17 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     SECEDO_TRY(len.alloc(size_t(m) + 1));
     SECEDO_TRY(dst.alloc(size_t(m) + 1));
     SECEDO_TRY(beg.alloc(rq.n_clusters));
-    SECEDO_TRY(bs::split_lengths(d_bytes.p, d_in_off.p, vs.p, m, src.p, len.p, s));
+    Dev<bs::RecordPlan> plan;
+    Dev<uint64_t> cnt;
+    if (suffixes) {  // the edited lengths, and what the gather needs to edit
+        SECEDO_TRY(plan.alloc(m));
+        SECEDO_TRY(cnt.alloc(4));
+        SECEDO_TRY(hipMemsetAsync(cnt.p, 0, 4 * 8, s));
+        SECEDO_TRY(bs::split_plan(d_bytes.p, d_in_off.p, vs.p, m, d_file.p, tag_key.p, suffixes->off.p, src.p, len.p,
+                                  plan.p, cnt.p, s));
+    } else {
+        SECEDO_TRY(bs::split_lengths(d_bytes.p, d_in_off.p, vs.p, m, src.p, len.p, s));
+    }
     tb = bam::scan_bytes(uint64_t(m) + 1);
     SECEDO_TRY(tmp.alloc(tb));
     SECEDO_TRY(bam::exclusive_sum64(tmp.p, tb, len.p, dst.p, uint64_t(m) + 1, s));
@@ -251,8 +288,18 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     uint64_t total = 0;
     SECEDO_TRY(hipMemcpyAsync(h_beg.data(), beg.p, rq.n_clusters * 8ull, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipMemcpyAsync(&total, dst.p + m, 8, hipMemcpyDeviceToHost, s));
+    uint64_t h_cnt[4] = {0, 0, 0, 0};  // replaced, unparsed, added, removed
+    if (suffixes) SECEDO_TRY(hipMemcpyAsync(h_cnt, cnt.p, sizeof h_cnt, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
-    if (total > ci.bytes.size()) return fail(SECEDO_E_STATE, "split: the stream is longer than the chromosome's records");
+    if (total > ci.bytes.size() + h_cnt[2])
+        return fail(SECEDO_E_STATE, "split: the stream is longer than the chromosome's records");
+    if (suffixes) {
+        g_rg.tagged_records += m;
+        g_rg.replaced_records += h_cnt[0];
+        g_rg.unparsed_records += h_cnt[1];
+        g_rg.added_bytes += h_cnt[2];
+        g_rg.removed_bytes += h_cnt[3];
+    }
     g_split.order_ms += ms_lap(t0);
     key.reset(), sel.reset(), scan.reset(), kc.reset(), vc.reset(), ks.reset(), vs.reset(), len.reset();
     tag_key.reset(), tag_sel.reset(), tmp.reset();
@@ -267,13 +314,17 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     SECEDO_TRY(hipEventCreate(&ev.a));
     SECEDO_TRY(hipEventCreate(&ev.b));
     SECEDO_TRY(hipEventRecord(ev.a, s));
-    SECEDO_TRY(bs::split_gather(d_bytes.p, src.p, dst.p, m, total, out.p + kFront, s));
+    if (suffixes)
+        SECEDO_TRY(bs::split_gather_rg(d_bytes.p, src.p, dst.p, plan.p, suffixes->off.p, suffixes->bytes.p, m, total,
+                                       out.p + kFront, s));
+    else
+        SECEDO_TRY(bs::split_gather(d_bytes.p, src.p, dst.p, m, total, out.p + kFront, s));
     SECEDO_TRY(hipEventRecord(ev.b, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     float g_ms = 0;
     SECEDO_TRY(hipEventElapsedTime(&g_ms, ev.a, ev.b));
     g_split.gather_ms += g_ms;
-    d_bytes.reset(), d_in_off.reset(), d_file.reset(), src.reset(), dst.reset();
+    d_bytes.reset(), d_in_off.reset(), d_file.reset(), src.reset(), dst.reset(), plan.reset(), cnt.reset();
     (void)ms_lap(t0);
 
     // a cluster without records of this chromosome starts where the next one does
@@ -327,15 +378,16 @@ int make_headers(const Request &rq, std::vector<std::vector<uint8_t>> *headers) 
     bs::RgMerge rg;
     size_t a = 0, b = 0;
     std::string id;
-    if (!bs::merge_rg(texts, &rg, &a, &b, &id))
+    if (!rq.rg && !bs::merge_rg(texts, &rg, &a, &b, &id))
         return fail(SECEDO_E_INVALID_ARG, "@RG ID:" + id + " names different lines in " + rq.files[a] + " and " +
                                               rq.files[b]);
     std::vector<uint32_t> members(rq.n_clusters, 0);
     for (uint16_t c : rq.cell_cluster) ++members[c];
     for (uint32_t k = 0; k < rq.n_clusters; ++k)
         headers->push_back(bs::header_bytes(
-            bs::header_text(first, rg.lines, k, members[k], uint32_t(rq.cell_cluster.size())), uint32_t(first.size()),
-            first_list));
+            bs::header_text(first, rq.rg ? bs::rg_header_lines(rq.names, rq.cell_cluster, k) : rg.lines, k, members[k],
+                            uint32_t(rq.cell_cluster.size())),
+            uint32_t(first.size()), first_list));
     return SECEDO_OK;
 }
 
@@ -361,7 +413,8 @@ int write_headers(const std::vector<std::vector<uint8_t>> &headers, Encoder *enc
 
 int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids, uint32_t n_chr,
           const uint16_t *cell_cluster, uint32_t n_cells, const char *tag, const char *const *barcodes,
-          uint32_t n_barcodes, const char *out_dir, int overwrite, uint32_t num_threads, secedo_bam_times *times) {
+          uint32_t n_barcodes, const char *out_dir, int overwrite, uint32_t num_threads, secedo_bam_times *times,
+          bool read_groups = false, const char *const *cell_names = nullptr, uint32_t n_names = 0) {
     const Clock::time_point t_all = Clock::now();
     secedo_bam_times tl{};
     if ((n_files && !bam_files) || (n_chr && !chromosome_ids) || !cell_cluster || !out_dir)
@@ -384,6 +437,24 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
                                                   std::to_string(n_files) + " files (one cell per file)");
     }
     SECEDO_CALL(check_files(bam_files, n_files, &rq.files));
+    if (read_groups) {  // the names, before any input is read
+        rq.rg = true;
+        if (cell_names) {
+            if (n_names != n_cells)
+                return fail(SECEDO_E_INVALID_ARG, "the clustering has " + std::to_string(n_cells) + " cells, the name "
+                                                      "list " + std::to_string(n_names));
+            for (uint32_t c = 0; c < n_names; ++c) {
+                if (!cell_names[c]) return fail(SECEDO_E_INVALID_ARG, "the name of cell " + std::to_string(c) + " is null");
+                rq.names.push_back(cell_names[c]);
+            }
+        } else if (tag) {
+            rq.names = rq.values;
+        } else {
+            for (const std::string &f : rq.files) rq.names.push_back(bs::default_name(f));
+        }
+        const std::string why = bs::names_fault(rq.names);
+        if (!why.empty()) return fail(SECEDO_E_INVALID_ARG, "read groups: " + why);
+    }
     rq.chr.assign(chromosome_ids, chromosome_ids + n_chr);
     std::sort(rq.chr.begin(), rq.chr.end());
     for (size_t c = 1; c < rq.chr.size(); ++c)
@@ -420,6 +491,8 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     SECEDO_TRY(hipMemcpyAsync(d_cc.p, rq.cell_cluster.data(), n_cells * 2ull, hipMemcpyHostToDevice, s));
     DevCells dc;
     if (tag) SECEDO_CALL(upload_cells(tag, rq.values, s, &dc));
+    DevSuffixes ds;
+    if (rq.rg) SECEDO_CALL(upload_suffixes(rq.names, s, &ds));
     SECEDO_TRY(hipStreamSynchronize(s));
 
     SECEDO_CALL(of.open());
@@ -431,7 +504,8 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     }
     for (uint32_t c = 0; c < n_chr; ++c) {
         const double o0 = g_split.order_ms;
-        SECEDO_CALL(split_chromosome(rq, in.chrs[c], tag ? &dc.list : nullptr, d_cc.p, &enc, &of, s, &tl));
+        SECEDO_CALL(split_chromosome(rq, in.chrs[c], tag ? &dc.list : nullptr, d_cc.p, rq.rg ? &ds : nullptr, &enc, &of,
+                                     s, &tl));
         tl.device_ms += g_split.order_ms - o0;
         std::vector<uint8_t>().swap(in.chrs[c].bytes);
     }
@@ -458,10 +532,32 @@ int secedo_bam_split_clusters(const char *const *bam_files, uint32_t n_files, co
                               uint32_t num_threads, secedo_bam_split_info *info, secedo_bam_times *times) {
     if (!info) return fail(SECEDO_E_INVALID_ARG, "null argument");
     g_split = secedo_bam_split_info{};
+    g_rg = secedo_bam_split_rg_info{};
     const int rc = split(bam_files, n_files, chromosome_ids, n_chr, cell_cluster, n_cells, tag, barcodes, n_barcodes,
                          out_dir, overwrite, num_threads, times);
     *info = g_split;
     return rc;
+}
+
+int secedo_bam_split_clusters_rg(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                                 uint32_t n_chr, const uint16_t *cell_cluster, uint32_t n_cells, const char tag[2],
+                                 const char *const *barcodes, uint32_t n_barcodes, const char *out_dir, int overwrite,
+                                 uint32_t num_threads, secedo_bam_split_info *info, secedo_bam_times *times,
+                                 const char *const *cell_names, uint32_t n_names, secedo_bam_split_rg_info *rg_info) {
+    if (!info || !rg_info) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    g_split = secedo_bam_split_info{};
+    g_rg = secedo_bam_split_rg_info{};
+    const int rc = split(bam_files, n_files, chromosome_ids, n_chr, cell_cluster, n_cells, tag, barcodes, n_barcodes,
+                         out_dir, overwrite, num_threads, times, true, cell_names, n_names);
+    *info = g_split;
+    *rg_info = g_rg;
+    return rc;
+}
+
+int secedo_bam_split_rg_stats(secedo_bam_split_rg_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = g_rg;
+    return SECEDO_OK;
 }
 
 int secedo_bam_split_stats(secedo_bam_split_info *out) {

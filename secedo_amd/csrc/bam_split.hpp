@@ -2,12 +2,15 @@
 // header-only, in plain C++ that g++ compiles alone (tests/cpp/bam_split_test.cpp runs it under the sanitizers): the
 // header every cluster_<k>.bam starts with (reference list, @RG merge, the fixed lines), the sort key of a record, the
 // member cuts of a cluster's extent, and the lookup from an output byte to the record that holds it, which the gather
-// kernel (bam_split_kernels.hip) compiles as device code. Failures come back as the reason's text.
+// kernel (bam_split_kernels.hip) compiles as device code. Failures come back as the reason's text. At the end, the
+// rules of secedo_bam_split_clusters_rg: the strict aux walk, the edited bytes of a record, the cells'
+// names and the @RG header lines.
 #pragma once
 
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -221,6 +224,153 @@ inline std::vector<uint8_t> ref_list_bytes(const std::vector<Ref> &refs) {
         out.push_back(0);
         put32(r.len);
     }
+    return out;
+}
+
+// ---- read groups (secedo_bam_split_clusters_rg): every written record gets RG:Z:<its cell's name> as its
+// last field, and the RG field it had is removed. What follows decides the edited bytes; the plan and gather kernels
+// compile it as device code.
+
+// The strict walk of a record's aux area. `rec` is the whole record, block_size word included, `len` = 4 + block_size.
+// A field is a two-byte tag, a type byte and a value: A c C 1 byte, s S 2, i I f 4, Z H up to and including the NUL,
+// B a subtype byte, a u32 count and count elements of the subtype's size. The walk succeeds when every field ends
+// within the record and the last one ends exactly at len; an unknown type or subtype, a field that runs past the end
+// and one or two bytes left over fail it. parsed: the walk succeeded. [hole_off, hole_off + hole_len) is then the
+// first field named RG, whole, whatever its type; without one, and after a failed walk, hole_off = len, hole_len = 0.
+// A B array is skipped by its count, so a long array costs a few loads.
+struct AuxHole {
+    uint32_t hole_off, hole_len;
+    bool parsed;
+};
+
+SPLIT_HD uint32_t aux_elem_size(uint8_t type) {
+    switch (type) {
+        case 'A': case 'c': case 'C': return 1;
+        case 's': case 'S': return 2;
+        case 'i': case 'I': case 'f': return 4;
+        default: return 0;
+    }
+}
+
+SPLIT_HD AuxHole aux_walk(const uint8_t *rec, uint32_t len) {
+    const AuxHole failed{len, 0, false};
+    if (len < 36) return failed;
+    const uint64_t l_name = rec[12];
+    const uint64_t n_cigar = uint32_t(rec[16]) | uint32_t(rec[17]) << 8;
+    const uint64_t l_seq = uint32_t(rec[20]) | uint32_t(rec[21]) << 8 | uint32_t(rec[22]) << 16 | uint32_t(rec[23]) << 24;
+    uint64_t p = 36 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
+    AuxHole out{len, 0, true};
+    while (p < len) {
+        if (len - p < 3) return failed;
+        const uint8_t type = rec[p + 2];
+        uint64_t q = p + 3;
+        if (type == 'Z' || type == 'H') {
+            while (q < len && rec[q] != 0) ++q;
+            if (q >= len) return failed;
+            ++q;
+        } else if (type == 'B') {
+            if (len - q < 5) return failed;
+            const uint64_t size = aux_elem_size(rec[q]);
+            if (size == 0 || rec[q] == 'A') return failed;
+            const uint64_t count = uint32_t(rec[q + 1]) | uint32_t(rec[q + 2]) << 8 | uint32_t(rec[q + 3]) << 16 |
+                                   uint32_t(rec[q + 4]) << 24;
+            q += 5 + count * size;
+        } else {
+            const uint64_t size = aux_elem_size(type);
+            if (size == 0) return failed;
+            q += size;
+        }
+        if (q > len) return failed;
+        if (out.hole_len == 0 && rec[p] == 'R' && rec[p + 1] == 'G') {
+            out.hole_off = uint32_t(p);
+            out.hole_len = uint32_t(q - p);
+        }
+        p = q;
+    }
+    if (p != len) return failed;  // the fixed part alone runs past the record
+    return out;
+}
+
+// The bytes a record of the cell named N gets at its end: 'R' 'G' 'Z' N '\0'.
+inline std::string rg_suffix(const std::string &name) { return "RGZ" + name + std::string(1, '\0'); }
+
+// One record's edit: its length, the hole and the length of its cell's suffix. The edited record is the record's
+// bytes without the hole, then the suffix; its first four bytes are the new block_size.
+struct Edit {
+    uint32_t len, hole_off, hole_len, suf_len;
+};
+
+SPLIT_HD uint32_t edited_len(const Edit &e) { return e.len - e.hole_len + e.suf_len; }
+
+// the byte at offset o < edited_len(e) of the edited record
+SPLIT_HD uint8_t edited_byte(const uint8_t *rec, const Edit &e, const uint8_t *suffix, uint32_t o) {
+    if (o < 4) return uint8_t((edited_len(e) - 4) >> (8 * o));
+    if (o < e.hole_off) return rec[o];
+    const uint32_t kept = e.len - e.hole_len;
+    if (o < kept) return rec[o + e.hole_len];
+    return suffix[o - kept];
+}
+
+// what the plan pass leaves the gather of a sorted record: the hole, the record's length and its cell
+struct RecordPlan {
+    uint32_t hole_off, hole_len, len, cell;
+};
+static_assert(sizeof(RecordPlan) == 16, "one 16-byte load per record");
+
+// The gather's tile bound holds for edited records too: the hole lies in the aux area, behind the 36 fixed bytes and
+// the name, so what is kept of a record of at least kMinRecord bytes is at least kMinRecord bytes, and a suffix
+// (at least 5 bytes) is added to it.
+constexpr uint32_t kMaxName = 254;
+
+// Why `name` cannot name a read group ("" when it can): 1 to 254 bytes, each in 0x21..0x7E.
+inline std::string name_fault(const std::string &name) {
+    if (name.empty()) return "is empty";
+    if (name.size() > kMaxName) return "is " + std::to_string(name.size()) + " bytes long, at most 254 are allowed";
+    for (size_t k = 0; k < name.size(); ++k) {
+        const unsigned char ch = static_cast<unsigned char>(name[k]);
+        if (ch < 0x21 || ch > 0x7E) return "has byte " + std::to_string(unsigned(ch)) + " at offset " + std::to_string(k) +
+                                           ", only 0x21 to 0x7E are allowed";
+    }
+    return std::string();
+}
+
+// Why the cells cannot be named `names` ("" when they can): the first cell whose name breaks the rule, else the first
+// two cells that share a name.
+inline std::string names_fault(const std::vector<std::string> &names) {
+    for (size_t c = 0; c < names.size(); ++c) {
+        const std::string why = name_fault(names[c]);
+        if (!why.empty()) return "the name of cell " + std::to_string(c) + " " + why;
+    }
+    std::map<std::string, size_t> first;
+    for (size_t c = 0; c < names.size(); ++c) {
+        const auto seen = first.emplace(names[c], c);
+        if (!seen.second)
+            return "cells " + std::to_string(seen.first->second) + " and " + std::to_string(c) + " share the name " +
+                   names[c];
+    }
+    return std::string();
+}
+
+// the default name of a per-file cell: the file's base name without the first of .sam.gz, .bam, .sam that it ends in
+inline std::string default_name(const std::string &path) {
+    const size_t slash = path.rfind('/');
+    std::string base = slash == std::string::npos ? path : path.substr(slash + 1);
+    for (const char *ext : {".sam.gz", ".bam", ".sam"}) {
+        const size_t n = std::strlen(ext);
+        if (base.size() >= n && base.compare(base.size() - n, n, ext) == 0) {
+            base.resize(base.size() - n);
+            break;
+        }
+    }
+    return base;
+}
+
+// the @RG lines of cluster k's file: one per cell of the cluster, in cell order
+inline std::vector<std::string> rg_header_lines(const std::vector<std::string> &names,
+                                                const std::vector<uint16_t> &cell_cluster, uint32_t k) {
+    std::vector<std::string> out;
+    for (size_t c = 0; c < names.size() && c < cell_cluster.size(); ++c)
+        if (cell_cluster[c] == k) out.push_back("@RG\tID:" + names[c] + "\tSM:cluster_" + std::to_string(k));
     return out;
 }
 

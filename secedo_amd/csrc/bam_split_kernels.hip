@@ -9,6 +9,9 @@
 //   (exclusive sum of the lengths: each record's destination, the total last)
 //   k_split_extents  one thread per sorted record: a cluster's first record gives where the cluster starts
 //   k_split_gather   one thread per 16 output bytes: the bandwidth pass
+// secedo_bam_split_clusters_rg runs k_split_plan in place of k_split_lengths (the aux walk, the hole of
+// the record's own RG field, the edited length) and k_split_gather_rg in place of k_split_gather (the same tiles over
+// edited records); both stand behind the plain call's kernels below.
 //
 // The gather is balanced over output bytes, not over records: lane i of a workgroup writes bytes [16 i, 16 i + 16) of
 // the workgroup's 4 KiB tile with one aligned 16-byte store, so a wave's store instruction covers 1 KiB contiguous
@@ -137,6 +140,129 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather(const uint8_t *__
     *reinterpret_cast<uint4 *>(out + b) = make_uint4(v[0], v[1], v[2], v[3]);
 }
 
+// ---- read groups
+
+// One thread per sorted record: where it lies, its cell (as k_split_keys found it), the strict aux walk of
+// bam_split.hpp and the edited length. cnt[0..3] += records with a hole, records whose walk failed, appended bytes,
+// removed bytes: summed per workgroup in LDS, one global atomic per counter and workgroup.
+__global__ void __launch_bounds__(kBlock) k_split_plan(const uint8_t *__restrict__ bytes,
+                                                       const uint64_t *__restrict__ in_off,
+                                                       const uint32_t *__restrict__ val, uint32_t m,
+                                                       const uint16_t *__restrict__ file,
+                                                       const uint64_t *__restrict__ tag_key,
+                                                       const uint32_t *__restrict__ suf_off,
+                                                       uint64_t *__restrict__ src, uint64_t *__restrict__ len,
+                                                       RecordPlan *__restrict__ plan,
+                                                       unsigned long long *__restrict__ cnt) {
+    __shared__ unsigned long long s_cnt[4];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j == m) len[m] = 0;
+    if (j < m) {
+        const uint32_t o = val[j];
+        const uint64_t off = in_off[o];
+        const uint32_t cell = tag_key ? uint32_t(tag_key[o] >> 32) & 0x3FFF : file[o];
+        const uint32_t n = 4u + ld32(bytes + off);
+        const AuxHole h = aux_walk(bytes + off, n);
+        const uint32_t suf = suf_off[cell + 1] - suf_off[cell];
+        src[j] = off;
+        plan[j] = RecordPlan{h.hole_off, h.hole_len, n, cell};
+        len[j] = uint64_t(n) - h.hole_len + suf;
+        if (h.hole_len) {
+            atomicAdd(&s_cnt[0], 1ull);
+            atomicAdd(&s_cnt[3], (unsigned long long)h.hole_len);
+        }
+        if (!h.parsed) atomicAdd(&s_cnt[1], 1ull);
+        atomicAdd(&s_cnt[2], (unsigned long long)suf);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+// The sorted record a lane of the editing gather stands in: its extent in the stream, its source, its edit and its
+// cell's suffix.
+struct Cursor {
+    uint64_t d0, d1, s0;
+    Edit e;
+    const uint8_t *suffix;
+    __device__ __forceinline__ void load(const uint64_t *__restrict__ src, const uint64_t *__restrict__ dst,
+                                         const RecordPlan *__restrict__ plan, const uint32_t *__restrict__ suf_off,
+                                         const uint8_t *__restrict__ suf, uint32_t j) {
+        d0 = dst[j], d1 = dst[j + 1], s0 = src[j];
+        const RecordPlan p = plan[j];
+        const uint32_t so = suf_off[p.cell];
+        e = Edit{p.len, p.hole_off, p.hole_len, suf_off[p.cell + 1] - so};
+        suffix = suf + so;
+    }
+};
+
+// k_split_gather over edited records: the same tiles, lanes and stores. An edited record is the patched block_size
+// word, the bytes before the hole, the bytes after it and the cell's suffix. A lane whose 16 bytes lie in one of the
+// two copied segments keeps the five-dword path; any other lane (a record's first bytes, a hole, a suffix, a record
+// boundary, the stream's end) takes whole dwords where a dword lies in a copied segment and edited_byte's rule for the
+// rest. The tile bound is the plain gather's (bam_split.hpp says why it holds for edited records).
+__global__ void __launch_bounds__(kGatherLanes) k_split_gather_rg(const uint8_t *__restrict__ bytes,
+                                                                  const uint64_t *__restrict__ src,
+                                                                  const uint64_t *__restrict__ dst,
+                                                                  const RecordPlan *__restrict__ plan,
+                                                                  const uint32_t *__restrict__ suf_off,
+                                                                  const uint8_t *__restrict__ suf, uint32_t m,
+                                                                  uint64_t total, uint8_t *__restrict__ out) {
+    __shared__ uint32_t s_first;
+    const uint64_t tile = uint64_t(blockIdx.x) * kTileBytes;
+    if (threadIdx.x == 0) s_first = record_of(dst, 0, m, tile);
+    __syncthreads();
+    const uint64_t b = tile + uint64_t(threadIdx.x) * kGatherVec;
+    if (b >= total) return;
+    const uint32_t lo = s_first;
+    const uint32_t hi = uint64_t(lo) + kTileRecords < m ? lo + kTileRecords : m;
+    uint32_t j = record_of(dst, lo, hi, b);
+    Cursor c;
+    c.load(src, dst, plan, suf_off, suf, j);
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(bytes);
+    uint32_t v[4];
+    const uint64_t r = b - c.d0;  // < 2^32: inside record j
+    const uint32_t kept = c.e.len - c.e.hole_len;
+    const bool before = r >= 4 && r + kGatherVec <= c.e.hole_off;
+    const bool after = r >= c.e.hole_off && r + kGatherVec <= kept;  // hole_off >= 36 > 4
+    if (b + kGatherVec <= c.d1 && (before || after)) {
+        const uint64_t s = c.s0 + r + (after ? c.e.hole_len : 0u);
+        const uint64_t k = s >> 2;
+        const uint32_t sh = 8 * uint32_t(s & 3);
+        uint32_t x[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) x[i] = w[k + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = uint32_t((uint64_t(x[i + 1]) << 32 | x[i]) >> sh);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t p = b + 4 * i;
+            while (p < total && p >= c.d1) c.load(src, dst, plan, suf_off, suf, ++j);  // j <= m - 1: p < dst[m]
+            const uint64_t q = p - c.d0;
+            const uint32_t keep = c.e.len - c.e.hole_len;
+            if (p + 4 <= c.d1 && q >= 4 && q + 4 <= c.e.hole_off) {
+                v[i] = dword_at(w, c.s0 + q);
+                continue;
+            }
+            if (p + 4 <= c.d1 && q >= c.e.hole_off && q + 4 <= keep) {
+                v[i] = dword_at(w, c.s0 + q + c.e.hole_len);
+                continue;
+            }
+            uint32_t x = 0;
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t) {
+                if (p + t >= total) break;
+                while (p + t >= c.d1) c.load(src, dst, plan, suf_off, suf, ++j);
+                x |= uint32_t(edited_byte(bytes + c.s0, c.e, c.suffix, uint32_t(p + t - c.d0))) << (8 * t);
+            }
+            v[i] = x;
+        }
+    }
+    *reinterpret_cast<uint4 *>(out + b) = make_uint4(v[0], v[1], v[2], v[3]);
+}
+
 inline uint32_t grid(uint64_t n) { return uint32_t((n + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -181,6 +307,26 @@ hipError_t split_gather(const uint8_t *d_bytes, const uint64_t *d_src, const uin
     const uint64_t tiles = (total + kTileBytes - 1) / kTileBytes;
     if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
     k_split_gather<<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, m, total, d_out);
+    return hipGetLastError();
+}
+
+hipError_t split_plan(const uint8_t *d_bytes, const uint64_t *d_in_off, const uint32_t *d_val, uint32_t m,
+                      const uint16_t *d_file, const uint64_t *d_tag_key, const uint32_t *d_suf_off, uint64_t *d_src,
+                      uint64_t *d_len, RecordPlan *d_plan, uint64_t *d_cnt, hipStream_t s) {
+    k_split_plan<<<grid(uint64_t(m) + 1), kBlock, 0, s>>>(d_bytes, d_in_off, d_val, m, d_file, d_tag_key, d_suf_off,
+                                                          d_src, d_len, d_plan,
+                                                          reinterpret_cast<unsigned long long *>(d_cnt));
+    return hipGetLastError();
+}
+
+hipError_t split_gather_rg(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst,
+                           const RecordPlan *d_plan, const uint32_t *d_suf_off, const uint8_t *d_suf, uint32_t m,
+                           uint64_t total, uint8_t *d_out, hipStream_t s) {
+    if (m == 0 || total == 0) return hipSuccess;
+    const uint64_t tiles = (total + kTileBytes - 1) / kTileBytes;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    k_split_gather_rg<<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, d_plan, d_suf_off, d_suf, m,
+                                                               total, d_out);
     return hipGetLastError();
 }
 

@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "bam_split.hpp"
+
 namespace secedo {
 namespace bamsplit {
 
@@ -38,6 +40,22 @@ hipError_t split_extents(const uint64_t *d_key, const uint64_t *d_dst, uint32_t 
 // zero). d_bytes is read as aligned dwords: it needs 8 bytes of room behind its last record.
 hipError_t split_gather(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst, uint32_t m,
                         uint64_t total, uint8_t *d_out, hipStream_t s);
+
+// ---- read groups (secedo_bam_split_clusters_rg); RecordPlan and the rules are bam_split.hpp's
+
+// The plan, one thread per sorted record j < m (input ordinal d_val[j]): d_src[j] as split_lengths gives it, d_plan[j]
+// = the hole of the strict aux walk, the record's length and its cell (d_file / d_tag_key as for split_keys), d_len[j]
+// = the edited length, d_len[m] = 0. d_suf_off[n_cells + 1]: where each cell's suffix starts in the suffix table.
+// d_cnt[0..3] += records with a hole, records whose walk failed, appended bytes, removed bytes (zero them first).
+hipError_t split_plan(const uint8_t *d_bytes, const uint64_t *d_in_off, const uint32_t *d_val, uint32_t m,
+                      const uint16_t *d_file, const uint64_t *d_tag_key, const uint32_t *d_suf_off, uint64_t *d_src,
+                      uint64_t *d_len, RecordPlan *d_plan, uint64_t *d_cnt, hipStream_t s);
+
+// split_gather over edited records: record j's edited bytes at d_dst[j]. d_bytes and d_out as for split_gather; d_suf
+// is read byte by byte.
+hipError_t split_gather_rg(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst,
+                           const RecordPlan *d_plan, const uint32_t *d_suf_off, const uint8_t *d_suf, uint32_t m,
+                           uint64_t total, uint8_t *d_out, hipStream_t s);
 
 }  // namespace bamsplit
 }  // namespace secedo

@@ -11,6 +11,11 @@ the cluster of each cell. With --cell_tag TG the inputs are multiplexed BAMs and
 per line, cell c being line c; records without a listed barcode are dropped. --chromosomes, --inflate, --index and
 --build_index are ``pileup_main``'s. --bai also writes ``cluster_<k>.bam.bai``. Existing outputs are refused unless
 --overwrite.
+
+--read_groups names each read's cell in the files: every record gets RG:Z:<name of its cell> in place of the RG field it
+had, and the header of cluster k one ``@RG ID:<name> SM:cluster_<k>`` line per cell of the cluster, so a somatic caller
+takes the files and ``pileup_main --cell_tag RG`` reads them back cell by cell. --cell_names FILE gives the names, one
+per line, cell c being line c; without it a cell is named by its file's base name, or by its barcode.
 """
 from __future__ import annotations
 
@@ -39,6 +44,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--build_index", action="store_true",
                     help="Before the run, write <bam>.bai on the GPU for every input BAM without an index file")
     ap.add_argument("--bai", action="store_true", help="Also write cluster_<k>.bam.bai for every output")
+    ap.add_argument("--read_groups", action="store_true",
+                    help="Tag every record with RG:Z:<name of its cell> and write one @RG line per cell")
+    ap.add_argument("--cell_names", default=None,
+                    help="With --read_groups: file of read-group names, one per line; cell c is line c")
     ap.add_argument("--overwrite", action="store_true", help="Replace existing cluster_<k>.bam files")
     ap.add_argument("--num_threads", type=int, default=8, help="Host inflate threads (at most 16 are used)")
     return ap.parse_args(argv)
@@ -81,6 +90,19 @@ def main(argv: Optional[List[str]] = None) -> int:
     if len(clustering) != n_cells:
         raise SystemExit("--clustering file %s lists %d cells, the input has %d%s"
                          % (a.clustering, len(clustering), n_cells, "" if cells is not None else " (one per file)"))
+    names = None
+    if a.cell_names is not None:
+        if not a.read_groups:
+            raise SystemExit("--cell_names needs --read_groups")
+        if not os.path.isfile(a.cell_names):
+            raise SystemExit("--cell_names file %s does not exist" % a.cell_names)
+        with open(a.cell_names) as f:
+            names = [line.rstrip("\r\n") for line in f]
+        while names and not names[-1]:
+            names.pop()
+        if len(names) != n_cells:
+            raise SystemExit("--cell_names file %s lists %d names, the input has %d cells"
+                             % (a.cell_names, len(names), n_cells))
     if not os.path.isdir(a.o):
         raise SystemExit("-o %s is not a directory" % a.o)
     outs = [os.path.join(a.o, "cluster_%d.bam" % k) for k in range(max(clustering) + 1)]
@@ -93,12 +115,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .bam_pileup import split_clusters
 
     tag_kw = {} if a.cell_tag is None else dict(cell_tag=a.cell_tag, cells=cells)
+    if a.read_groups:
+        tag_kw.update(read_groups=True, cell_names=names)
     st = split_clusters(files, clustering, a.o, ids, inflate=a.inflate, index=a.index, bai=a.bai,
                         overwrite=a.overwrite, num_threads=pool_size(a.num_threads), **tag_kw)
     print("Written %d records of %d cells to %d files %s (%d bytes, %d BGZF members, %d of them stored)%s"
           % (st["records"], st["cells"], st["clusters"], os.path.join(a.o, "cluster_<k>.bam"), st["compressed_bytes"],
              st["members"], st["stored_members"],
              "; %d records without a listed barcode dropped" % st["dropped_records"] if cells is not None else ""))
+    if a.read_groups:
+        print("Tagged %d records with their cell's read group (%d had an RG field, replaced; %d did not parse, kept whole)"
+              % (st["tagged_records"], st["replaced_records"], st["unparsed_records"]))
     return 0
 
 

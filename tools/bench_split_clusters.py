@@ -14,7 +14,10 @@ tag-mode call, split_stats() of the last of --repeat runs after one untimed run 
   zlib1_ratio, zlib6_ratio   zlib at level 1 and 6 over the same 0xFF00-byte pieces of one cluster file's bytes (at
                       most --zlib-mib MiB of them), payload bytes over input bytes, and ours on those pieces
 
-and whether the two calls wrote the same number of records. Run it under a time limit (timeout -k 10 ...)."""
+and whether the two calls wrote the same number of records. --read_groups runs the same two calls with
+read_groups=True (every record tagged RG:Z:<its cell>): the line then also holds split_rg_stats(), and the
+gather's bytes are what the editing gather reads and writes. total_ms_runs lists the call totals of the timed runs, so
+that two lines can be compared against their own run-to-run spread. Run it under a time limit (timeout -k 10 ...)."""
 import argparse
 import gzip
 import json
@@ -47,8 +50,11 @@ def run(files, clustering, out, repeat, threads, **kw):
     for key in STAGES:
         r[key] = round(float(np.median([x[key] for x in runs])), 3)
     r["times"] = {key: round(float(np.median([x[key] for x in times])), 2) for key in STEPS}
+    r["total_ms_runs"] = [round(float(x["total_ms"]), 2) for x in times]
     record_bytes = r["text_bytes"]  # the headers' few hundred bytes per file included
-    r["gather_GBps"] = 2 * record_bytes / (r["gather_ms"] * 1e-3) / 1e9 if r["gather_ms"] else None
+    # the editing gather reads what it writes less the appended bytes plus the removed ones
+    moved = 2 * record_bytes - r.get("added_bytes", 0) + r.get("removed_bytes", 0)
+    r["gather_GBps"] = moved / (r["gather_ms"] * 1e-3) / 1e9 if r["gather_ms"] else None
     r["gather_fraction_of_hbm_measured"] = r["gather_GBps"] * 1e9 / HBM_MEASURED if r["gather_ms"] else None
     r["deflate_GBps"] = r["text_bytes"] / (r["deflate_ms"] * 1e-3) / 1e9
     r["stored_share"] = r["stored_members"] / max(r["members"], 1)
@@ -84,6 +90,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--zlib-mib", type=int, default=16)
+    ap.add_argument("--read_groups", action="store_true", help="tag every record with its cell's read group")
     a = ap.parse_args()
     import bench_pileup_bams as bp
 
@@ -99,9 +106,11 @@ def main():
         outs.append(d)
     line = dict(workload="split_clusters_uniform", cells=a.cells, pairs=a.pairs, mbp=a.mbp, clusters=a.clusters,
                 threads=a.threads, records=a.cells * a.pairs * 2, record_bytes=a.cells * a.pairs * 2 * 211,
-                bam_bytes=sum(os.path.getsize(p) for p in paths), hbm_measured_GBps=HBM_MEASURED / 1e9)
-    line["per_cell"] = run(paths, clustering, outs[0], a.repeat, a.threads)
-    line["multiplexed"] = run([mpath], clustering, outs[1], a.repeat, a.threads, cell_tag="CB", cells=barcodes)
+                bam_bytes=sum(os.path.getsize(p) for p in paths), hbm_measured_GBps=HBM_MEASURED / 1e9,
+                read_groups=a.read_groups)
+    kw = dict(read_groups=True) if a.read_groups else {}
+    line["per_cell"] = run(paths, clustering, outs[0], a.repeat, a.threads, **kw)
+    line["multiplexed"] = run([mpath], clustering, outs[1], a.repeat, a.threads, cell_tag="CB", cells=barcodes, **kw)
     # the multiplexed records carry the CB:Z tag, so the two calls' files differ; their record counts must not
     line["records_equal"] = line["per_cell"]["records"] == line["multiplexed"]["records"] == line["records"]
     line["zlib"] = zlib_beside(os.path.join(outs[0], "cluster_0.bam"), a.zlib_mib)
