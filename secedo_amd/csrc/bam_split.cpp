@@ -9,8 +9,7 @@
 #include "bam_kernels.hpp"
 #include "bam_split.hpp"
 #include "bam_split_kernels.hpp"
-#include "bgzf_deflate.hpp"
-#include "bgzf_deflate_kernels.hpp"
+#include "bgzf_encoder.hpp"
 
 #include <sys/stat.h>
 #include <unistd.h>
@@ -24,8 +23,6 @@ using namespace secedo::bam_host;
 namespace bam = secedo::bam;
 namespace bs = secedo::bamsplit;
 namespace bz = secedo::bgzf;
-
-static_assert(bs::kCut == bz::kCut, "bam_split.hpp cuts members where the encoder does");
 
 thread_local secedo_bam_split_info g_split{};
 thread_local secedo_bam_split_rg_info g_rg{};
@@ -83,83 +80,35 @@ struct OutFiles {
     }
 };
 
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
-// The encoder's buffers, kept over the header and the chromosomes of one call.
-struct Encoder {
-    Buf desc, slots, size, at, packed;
-    std::vector<bz::DeflateDesc> h_desc;
-    std::vector<uint32_t> h_size;
-    std::vector<uint64_t> h_at;
-    std::vector<uint8_t> h_out;
-
-    size_t cap = 0;  // members the device buffers hold: grown to the largest slice met, at most kSlice
-
-    int reserve(size_t members) {
-        if (members <= cap) return SECEDO_OK;
-        SECEDO_TRY(desc.alloc(members * sizeof(bz::DeflateDesc)));
-        SECEDO_TRY(slots.alloc(members * size_t(bz::kDeflateSlot)));
-        SECEDO_TRY(size.alloc(members * 4));
-        SECEDO_TRY(at.alloc(members * 8));
-        h_desc.resize(members);
-        h_size.resize(members);
-        h_at.resize(members);
-        cap = members;
-        return SECEDO_OK;
-    }
-
-    // The members cuts[k] (offsets in the stream that starts kFront bytes into d_text) are deflated in slices and
-    // member k is appended to file owner[k]; owners ascend, so every file gets its members in stream order.
-    int run(const uint8_t *d_text, const std::vector<bs::Cut> &cuts, const std::vector<uint32_t> &owner, OutFiles *of,
-            hipStream_t s) {
-        SECEDO_CALL(reserve(std::min(kSlice, cuts.size())));
-        for (size_t b0 = 0; b0 < cuts.size(); b0 += kSlice) {
-            const uint32_t nb = uint32_t(std::min(kSlice, cuts.size() - b0));
-            Clock::time_point t0 = Clock::now();
-            for (uint32_t k = 0; k < nb; ++k) h_desc[k] = bz::DeflateDesc{kFront + cuts[b0 + k].off, cuts[b0 + k].n, 0};
-            SECEDO_TRY(hipMemcpyAsync(desc.p, h_desc.data(), nb * sizeof(bz::DeflateDesc), hipMemcpyHostToDevice, s));
-            SECEDO_TRY(bz::bgzf_deflate(d_text, desc.as<bz::DeflateDesc>(), nb, slots.as<uint8_t>(),
-                                        size.as<uint32_t>(), s));
-            SECEDO_TRY(hipMemcpyAsync(h_size.data(), size.p, nb * 4, hipMemcpyDeviceToHost, s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            uint64_t end = 0;
-            for (uint32_t k = 0; k < nb; ++k) {
-                const uint32_t bytes = h_size[k] & ~bz::kDeflateStoredFlag;
-                if (bytes < bz::kHeaderBytes + bz::kTrailerBytes || bytes > bz::kMaxMember)
-                    return fail(SECEDO_E_STATE, "BGZF encoder: a member of " + std::to_string(bytes) + " bytes");
-                g_split.stored_members += (h_size[k] & bz::kDeflateStoredFlag) != 0;
-                h_at[k] = end;
-                end += bytes;
-            }
-            g_split.members += nb;
-            if (packed.n < end) SECEDO_TRY(packed.alloc(end));
-            SECEDO_TRY(hipMemcpyAsync(at.p, h_at.data(), nb * 8, hipMemcpyHostToDevice, s));
-            SECEDO_TRY(bz::bgzf_pack(slots.as<uint8_t>(), size.as<uint32_t>(), at.as<uint64_t>(), nb,
-                                     packed.as<uint8_t>(), s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            g_split.deflate_ms += ms_lap(t0);
-            h_out.resize(end);
-            SECEDO_TRY(hipMemcpyAsync(h_out.data(), packed.p, end, hipMemcpyDeviceToHost, s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            g_split.download_ms += ms_lap(t0);
-            for (uint32_t k = 0; k < nb;) {  // the members of one file in one write
-                uint32_t e = k + 1;
-                while (e < nb && owner[b0 + e] == owner[b0 + k]) ++e;
-                const uint64_t stop = e < nb ? h_at[e] : end;
-                SECEDO_CALL(of->append(owner[b0 + k], h_out.data() + h_at[k], stop - h_at[k]));
-                k = e;
-            }
-            g_split.write_ms += ms_lap(t0);
+// The members desc of the text at d_text go through the encoder (kept over the header and the chromosomes of one
+// call) and member k is appended to file owner[k]; owners ascend, so every file gets its members in stream order.
+int encode_to_files(bz::Encoder *enc, const uint8_t *d_text, const std::vector<bz::DeflateDesc> &desc,
+                    const std::vector<uint32_t> &owner, OutFiles *of, hipStream_t s) {
+    const int rc = enc->run(d_text, desc, s, [&](size_t b0, uint32_t n, const uint32_t *bytes, uint64_t *at) -> int {
+        uint64_t end = 0;
+        for (uint32_t k = 0; k < n; ++k) {
+            at[k] = end;
+            end += bytes[k];
         }
+        SECEDO_CALL(enc->fetch(end, &enc->bytes, 0));
+        Clock::time_point t0 = Clock::now();
+        for (uint32_t k = 0; k < n;) {  // the members of one file in one write
+            uint32_t e = k + 1;
+            while (e < n && owner[b0 + e] == owner[b0 + k]) ++e;
+            const uint64_t stop = e < n ? at[e] : end;
+            SECEDO_CALL(of->append(owner[b0 + k], enc->bytes.data() + at[k], stop - at[k]));
+            k = e;
+        }
+        g_split.write_ms += ms_since(t0);
         return SECEDO_OK;
-    }
-};
+    });
+    g_split.members += enc->counts.members;
+    g_split.stored_members += enc->counts.stored_members;
+    g_split.deflate_ms += enc->counts.deflate_ms;
+    g_split.download_ms += enc->counts.download_ms;
+    enc->counts = bz::EncoderCounts{};  // taken
+    return rc;
+}
 
 // What one call asks for, checked.
 struct Request {
@@ -198,7 +147,7 @@ int upload_suffixes(const std::vector<std::string> &names, hipStream_t s, DevSuf
 
 // One chromosome: its records in HBM in input order -> the stream -> members appended to the clusters' files.
 int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList *cells, const uint16_t *d_cell_cluster,
-                     const DevSuffixes *suffixes, Encoder *enc, OutFiles *of, hipStream_t s, secedo_bam_times *t) {
+                     const DevSuffixes *suffixes, bz::Encoder *enc, OutFiles *of, hipStream_t s, secedo_bam_times *t) {
     Clock::time_point t0 = Clock::now();
     std::vector<uint64_t> in_off;
     std::vector<uint16_t> in_file;
@@ -310,19 +259,18 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     SECEDO_TRY(out.alloc(kFront + padded + bz::kDeflateInSlack));
     SECEDO_TRY(hipMemsetAsync(out.p, 0, kFront, s));
     SECEDO_TRY(hipMemsetAsync(out.p + kFront + padded, 0, bz::kDeflateInSlack, s));
-    Events ev;
-    SECEDO_TRY(hipEventCreate(&ev.a));
-    SECEDO_TRY(hipEventCreate(&ev.b));
-    SECEDO_TRY(hipEventRecord(ev.a, s));
+    Events<2> ev;
+    SECEDO_CALL(ev.create());
+    SECEDO_TRY(hipEventRecord(ev.e[0], s));
     if (suffixes)
         SECEDO_TRY(bs::split_gather_rg(d_bytes.p, src.p, dst.p, plan.p, suffixes->off.p, suffixes->bytes.p, m, total,
                                        out.p + kFront, s));
     else
         SECEDO_TRY(bs::split_gather(d_bytes.p, src.p, dst.p, m, total, out.p + kFront, s));
-    SECEDO_TRY(hipEventRecord(ev.b, s));
+    SECEDO_TRY(hipEventRecord(ev.e[1], s));
     SECEDO_TRY(hipStreamSynchronize(s));
     float g_ms = 0;
-    SECEDO_TRY(hipEventElapsedTime(&g_ms, ev.a, ev.b));
+    SECEDO_TRY(hipEventElapsedTime(&g_ms, ev.e[0], ev.e[1]));
     g_split.gather_ms += g_ms;
     d_bytes.reset(), d_in_off.reset(), d_file.reset(), src.reset(), dst.reset(), plan.reset(), cnt.reset();
     (void)ms_lap(t0);
@@ -331,17 +279,13 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     h_beg[rq.n_clusters] = total;
     for (uint32_t c = rq.n_clusters; c-- > 0;)
         if (h_beg[c] == ~0ull) h_beg[c] = h_beg[c + 1];
-    std::vector<bs::Cut> cuts;
+    std::vector<bz::DeflateDesc> desc;
     std::vector<uint32_t> owner;
     for (uint32_t c = 0; c < rq.n_clusters; ++c) {
-        bs::member_cuts(h_beg[c], h_beg[c + 1], &cuts);
-        owner.resize(cuts.size(), c);
+        bz::member_cuts(h_beg[c], h_beg[c + 1], &desc);
+        owner.resize(desc.size(), c);
     }
-    const double before = g_split.deflate_ms + g_split.download_ms;
-    const double w_before = g_split.write_ms;
-    SECEDO_CALL(enc->run(out.p, cuts, owner, of, s));
-    t->device_ms += g_ms + (g_split.deflate_ms + g_split.download_ms - before);
-    t->write_ms += g_split.write_ms - w_before;
+    SECEDO_CALL(encode_to_files(enc, out.p + kFront, desc, owner, of, s));
     g_split.records += m;
     g_split.text_bytes += total;
     return SECEDO_OK;
@@ -392,15 +336,15 @@ int make_headers(const Request &rq, std::vector<std::vector<uint8_t>> *headers) 
 }
 
 // the headers' members: the same encoder, once per file
-int write_headers(const std::vector<std::vector<uint8_t>> &headers, Encoder *enc, OutFiles *of, hipStream_t s) {
+int write_headers(const std::vector<std::vector<uint8_t>> &headers, bz::Encoder *enc, OutFiles *of, hipStream_t s) {
     std::vector<uint8_t> all(kFront, 0);
-    std::vector<bs::Cut> cuts;
+    std::vector<bz::DeflateDesc> desc;
     std::vector<uint32_t> owner;
     for (size_t k = 0; k < headers.size(); ++k) {
         const uint64_t beg = all.size() - kFront;
         all.insert(all.end(), headers[k].begin(), headers[k].end());
-        bs::member_cuts(beg, all.size() - kFront, &cuts);
-        owner.resize(cuts.size(), uint32_t(k));
+        bz::member_cuts(beg, all.size() - kFront, &desc);
+        owner.resize(desc.size(), uint32_t(k));
         g_split.text_bytes += headers[k].size();
     }
     all.resize(all.size() + bz::kDeflateInSlack, 0);
@@ -408,7 +352,7 @@ int write_headers(const std::vector<std::vector<uint8_t>> &headers, Encoder *enc
     SECEDO_TRY(d.alloc(all.size()));
     SECEDO_TRY(hipMemcpyAsync(d.p, all.data(), all.size(), hipMemcpyHostToDevice, s));
     SECEDO_TRY(hipStreamSynchronize(s));
-    return enc->run(d.p, cuts, owner, of, s);
+    return encode_to_files(enc, d.p + kFront, desc, owner, of, s);
 }
 
 int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids, uint32_t n_chr,
@@ -485,7 +429,7 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     StreamGuard guard;
     SECEDO_TRY(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
     const hipStream_t s = guard.s;
-    Encoder enc;
+    bz::Encoder enc(kSlice);
     Dev<uint16_t> d_cc;
     SECEDO_TRY(d_cc.alloc(n_cells));
     SECEDO_TRY(hipMemcpyAsync(d_cc.p, rq.cell_cluster.data(), n_cells * 2ull, hipMemcpyHostToDevice, s));
@@ -496,27 +440,19 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     SECEDO_TRY(hipStreamSynchronize(s));
 
     SECEDO_CALL(of.open());
-    {
-        const double w0 = g_split.write_ms, d0 = g_split.deflate_ms + g_split.download_ms;
-        SECEDO_CALL(write_headers(headers, &enc, &of, s));
-        tl.write_ms += g_split.write_ms - w0;
-        tl.device_ms += g_split.deflate_ms + g_split.download_ms - d0;
-    }
+    SECEDO_CALL(write_headers(headers, &enc, &of, s));
     for (uint32_t c = 0; c < n_chr; ++c) {
-        const double o0 = g_split.order_ms;
         SECEDO_CALL(split_chromosome(rq, in.chrs[c], tag ? &dc.list : nullptr, d_cc.p, rq.rg ? &ds : nullptr, &enc, &of,
                                      s, &tl));
-        tl.device_ms += g_split.order_ms - o0;
         std::vector<uint8_t>().swap(in.chrs[c].bytes);
     }
     Clock::time_point t0 = Clock::now();
-    uint8_t eof[bz::kEofBytes];
-    for (uint32_t k = 0; k < bz::kEofBytes; ++k) eof[k] = uint8_t(bz::eof_member_byte(k));
-    for (uint32_t k = 0; k < rq.n_clusters; ++k) SECEDO_CALL(of.append(k, eof, sizeof eof));
+    const auto eof = bz::eof_member();
+    for (uint32_t k = 0; k < rq.n_clusters; ++k) SECEDO_CALL(of.append(k, eof.data(), eof.size()));
     SECEDO_CALL(of.commit());
-    const double w = ms_lap(t0);
-    g_split.write_ms += w;
-    tl.write_ms += w;
+    g_split.write_ms += ms_since(t0);
+    tl.device_ms += g_split.order_ms + g_split.gather_ms + g_split.deflate_ms + g_split.download_ms;
+    tl.write_ms += g_split.write_ms;
     tl.total_ms = ms_since(t_all);
     if (times) *times = tl;
     return SECEDO_OK;

@@ -1,10 +1,10 @@
 // bam_split.hpp -- everything that decides the bytes of secedo_bam_split_clusters (include/secedo_bam.h),
 // header-only, in plain C++ that g++ compiles alone (tests/cpp/bam_split_test.cpp runs it under the sanitizers): the
-// header every cluster_<k>.bam starts with (reference list, @RG merge, the fixed lines), the sort key of a record, the
-// member cuts of a cluster's extent, and the lookup from an output byte to the record that holds it, which the gather
-// kernel (bam_split_kernels.hip) compiles as device code. Failures come back as the reason's text. At the end, the
-// rules of secedo_bam_split_clusters_rg: the strict aux walk, the edited bytes of a record, the cells'
-// names and the @RG header lines.
+// header every cluster_<k>.bam starts with (reference list, @RG merge, the fixed lines), the sort key of a record, and
+// the lookup from an output byte to the record that holds it, which the gather kernel (bam_split_kernels.hip) compiles
+// as device code (the member cuts of a cluster's extent are every writer's: bgzf_members.hpp). Failures come back as
+// the reason's text. At the end, the rules of secedo_bam_split_clusters_rg: the strict aux walk, the
+// edited bytes of a record, the cells' names and the @RG header lines.
 #pragma once
 
 #include <cstdint>
@@ -57,19 +57,6 @@ constexpr uint32_t kGatherLanes = 256, kGatherVec = 16;
 constexpr uint32_t kTileBytes = kGatherLanes * kGatherVec;
 constexpr uint32_t kMinRecord = 4 + 32 + 1;
 constexpr uint32_t kTileRecords = kTileBytes / kMinRecord + 2;
-
-// ---- the member cuts of one extent [beg, end) of the output stream: every kCut bytes from its start
-
-constexpr uint32_t kCut = 0xFF00;  // bgzf::kCut; bam_split.cpp asserts they agree
-
-struct Cut {
-    uint64_t off;
-    uint32_t n;
-};
-
-inline void member_cuts(uint64_t beg, uint64_t end, std::vector<Cut> *out) {
-    for (uint64_t p = beg; p < end; p += kCut) out->push_back(Cut{p, uint32_t(end - p < kCut ? end - p : kCut)});
-}
 
 // ---- the header
 

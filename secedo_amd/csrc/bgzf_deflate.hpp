@@ -30,6 +30,8 @@
 
 #include "bgzf_inflate.hpp"
 
+#include <array>
+
 #if defined(__HIPCC__)
 #define BGZF_UNROLL _Pragma("unroll")
 #else
@@ -39,7 +41,6 @@
 namespace secedo {
 namespace bgzf {
 
-constexpr uint32_t kCut = 0xFF00;  // text bytes per member at the most: bgzip's cut
 constexpr uint32_t kHeaderBytes = 18, kTrailerBytes = 8, kStoredHead = 5;
 constexpr uint32_t kMaxMember = kHeaderBytes + kStoredHead + kCut + kTrailerBytes;
 static_assert(kMaxMember <= 65536, "BSIZE is 16 bits");
@@ -57,6 +58,11 @@ constexpr uint32_t kOverrunBytes = 4 * kStageWords;
 constexpr uint32_t kEofBytes = 28;
 BGZF_HD uint32_t eof_member_byte(uint32_t k) {
     return uint8_t("\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00\x42\x43\x02\x00\x1b\x00\x03\x00\x00\x00\x00\x00\x00\x00\x00\x00"[k]);
+}
+inline std::array<uint8_t, kEofBytes> eof_member() {  // for the host: what every writer ends a file with
+    std::array<uint8_t, kEofBytes> m;
+    for (uint32_t k = 0; k < kEofBytes; ++k) m[k] = uint8_t(eof_member_byte(k));
+    return m;
 }
 
 // the encoder's working set: LDS on the device, the stack on the host

@@ -1,7 +1,9 @@
 // bgzf_deflate_kernels.hpp -- launch wrappers of bgzf_deflate_kernels.hip (gfx950): text in HBM cut into BGZF members,
 // each deflated, checksummed and framed there, then packed back to back. See bgzf_deflate_kernels.hip for the layout
-// and bgzf_deflate.hpp for the rules that decide the bytes.
+// and bgzf_deflate.hpp for the rules that decide the bytes; DeflateDesc is in bgzf_members.hpp, beside its cut rule.
 #pragma once
+
+#include "bgzf_members.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -10,12 +12,6 @@
 
 namespace secedo {
 namespace bgzf {
-
-// one member to make: text bytes [in_off, in_off + n) of d_text, 1 <= n <= kCut (0xFF00)
-struct DeflateDesc {
-    uint64_t in_off;
-    uint32_t n, reserved;
-};
 
 // bytes the kernel may read beyond a text's ends (whole 16-byte vectors): d_text needs that much room before the first
 // text and after the last one, as the payloads of BgzfDesc do

@@ -52,6 +52,7 @@ enum Status : uint32_t {
 
 constexpr uint32_t kLitBits = 10, kDistBits = 8;  // primary table widths; longer codes take the canonical walk
 constexpr uint32_t kMaxLit = 288, kMaxDist = 32, kMaxBits = 15;
+constexpr uint32_t kCut = 0xFF00;  // text bytes per member at the most: bgzip's cut, every writer's (bgzf_members.hpp)
 
 // one canonical Huffman code: symbols sorted by (length, value), counts per length, and the primary table
 // entry = symbol << 4 | length (0 = no code of at most `bits` bits starts so)

@@ -3,10 +3,10 @@
 // one parse of its header, the walk that lists a file's members, the file bytes and descriptors the device inflate
 // (bgzf_kernels.hpp) takes for a range of members, the zlib inflate of one member, and the words for a member that
 // cannot be listed or does not inflate. Failures come back as the reason's text, without the file's name; nothing here
-// knows the libraries' error string. A new BGZF consumer starts from here.
+// knows the libraries' error string. A new BGZF consumer starts from here; so does a writer (DeflateDesc, member_cuts).
 #pragma once
 
-#include "bgzf_inflate.hpp"  // the status codes
+#include "bgzf_inflate.hpp"  // the status codes, kCut
 
 #include <zlib.h>
 
@@ -32,6 +32,18 @@ constexpr uint32_t kBgzfInSlack = 16;
 constexpr uint32_t kBgzfMaxIsize = 65536;
 
 }  // namespace bam
+
+namespace bgzf {
+// one member to make (bgzf_deflate_kernels.hpp): text bytes [in_off, in_off + n) of d_text, 1 <= n <= kCut (0xFF00)
+struct DeflateDesc {
+    uint64_t in_off;
+    uint32_t n, reserved;
+};
+// The one cut rule of every writer: the members of text [beg, end), one every kCut bytes from beg, appended to *out.
+inline void member_cuts(uint64_t beg, uint64_t end, std::vector<DeflateDesc> *out) {
+    for (uint64_t p = beg; p < end; p += kCut) out->push_back({p, uint32_t(std::min<uint64_t>(kCut, end - p)), 0});
+}
+}  // namespace bgzf
 
 namespace bgzf_members __attribute__((visibility("hidden"))) {
 

@@ -51,18 +51,6 @@ std::vector<Range> cut_ranges(const Source &src, bool from_members) {
     return r;
 }
 
-struct Events {
-    hipEvent_t e[10] = {};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    int create() {
-        for (hipEvent_t &x : e) SECEDO_TRY(hipEventCreate(&x));
-        return SECEDO_OK;
-    }
-};
-
 // The upload side: range r into text buffer r & 1, on its own stream.
 struct Stager {
     const Source &src;
@@ -71,7 +59,7 @@ struct Stager {
     StreamGuard up;
     Buf text[2], in[2], desc[2], status[2];
     std::vector<BgzfDesc> h_desc[2];
-    Events ev;  // per slot k: [k] staged, [2 + k] consumed, [4 + 2k, 5 + 2k] its inflate's begin and end
+    Events<10> ev;  // per slot k: [k] staged, [2 + k] consumed, [4 + 2k, 5 + 2k] its inflate's begin and end
 
     Stager(const Source &s, bool m) : src(s), members(m), ranges(cut_ranges(s, m)) {}
 
@@ -182,7 +170,7 @@ int device_genotypes(const Source &src, bool diploid, const uint32_t *d_chr_locu
         SECEDO_TRY(hipMemsetAsync(b_mat.p, 0, n_loci, s));
         SECEDO_TRY(hipMemsetAsync(b_pat.p, 0, n_loci, s));
     }
-    Events ev;  // per parity k of a range: [4k, 4k + 1] its passes, [4k + 2, 4k + 3] its gathers; [8, 9] the final pass
+    Events<10> ev;  // per parity k of a range: [4k, 4k + 1] its passes, [4k + 2, 4k + 3] its gathers; [8, 9] the final pass
     SECEDO_CALL(ev.create());
 
     F::Table table(diploid, needed);

@@ -1,5 +1,5 @@
 // host_util.hpp -- the host plumbing every stand-alone library's host file needs: the last-error string, the
-// early-return macros, a clock, RAII device buffers and a stream guard. Internal: nothing here is exported (the
+// early-return macros, a clock, RAII device buffers, a stream guard and events. Internal: nothing here is exported (the
 // namespace is hidden), and each library that includes it gets its own error string, since the libraries do not
 // link one another's copy.
 #pragma once
@@ -124,6 +124,20 @@ struct StreamGuard {
     hipStream_t s = nullptr;
     ~StreamGuard() {
         if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+template <size_t N = 2>
+struct Events {  // made by create(): a pair around a kernel whose time is reported, or more for hand-overs
+    hipEvent_t e[N] = {};
+    ~Events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    int create() {
+        for (hipEvent_t &x : e)
+            if (!x) SECEDO_TRY(hipEventCreate(&x));
+        return SECEDO_OK;
     }
 };
 

@@ -3,7 +3,7 @@
 // stand-alone route, which uploads the compressed bytes of files that exist and inflates them in HBM first.
 #include "tabix_host.hpp"
 
-#include "bgzf_deflate_kernels.hpp"  // kDeflateInSlack
+#include "bgzf_encoder.hpp"  // kDeflateInSlack, EncoderCounts
 #include "bgzf_kernels.hpp"
 #include "bgzf_members.hpp"  // the member list of a file that is read, its descriptors and its error words
 #include "host_util.hpp"
@@ -355,7 +355,7 @@ int compress_and_write(const std::vector<std::vector<uint8_t>> &raw, size_t n, c
     SECEDO_TRY(hipMemcpyAsync(b_text.p + kSlack, all.data(), all.size(), hipMemcpyHostToDevice, s));
     std::vector<uint8_t> bytes;
     std::vector<uint64_t> out_off;
-    secedo_variant_vcf_info counts{};  // the encoder's counts of the index bodies: not the VCF files' statistics
+    secedo::bgzf::EncoderCounts counts;  // the encoder's counts of the index bodies: not the VCF files' statistics
     SECEDO_CALL(secedo::vcf::deflate_device(b_text.p + kSlack, off, &bytes, &out_off, s, nullptr, &counts));
     g_info.deflate_ms += ms_lap(t0);
     for (size_t k = 0; k < n; ++k) {

@@ -3,8 +3,7 @@
 // for the device, and tests/test_gpu_vcf_output.py holds the two against each other.
 #include "vcf_output.hpp"
 
-#include "bgzf_deflate.hpp"
-#include "bgzf_deflate_kernels.hpp"
+#include "bgzf_encoder.hpp"
 #include "host_util.hpp"
 #include "tabix_host.hpp"
 #include "tabix_kernels.hpp"
@@ -139,14 +138,6 @@ int write_variant_and_scores(const std::filesystem::path &out_dir, const std::ve
     return write_file(out_dir / "scores", scores);
 }
 
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
 }  // namespace
 
 void set_output(int kind) { g_output.store(kind); }
@@ -266,101 +257,57 @@ int format_device(const std::vector<std::string> &pre, const secedo_variant_reco
 }
 
 int deflate_device(const uint8_t *d_text, const std::vector<uint64_t> &file_off, std::vector<uint8_t> *out,
-                   std::vector<uint64_t> *out_off, hipStream_t s, MemberTable *table,
-                   secedo_variant_vcf_info *counts) {
-    secedo_variant_vcf_info &st = counts ? *counts : g_info;
+                   std::vector<uint64_t> *out_off, hipStream_t s, MemberTable *table, bgzf::EncoderCounts *counts) {
     using namespace secedo::bgzf;
     const size_t n_files = file_off.size() - 1;
-    // every member of every file, in file order; a file's last member is followed by the EOF member
-    std::vector<DeflateDesc> desc;
-    std::vector<uint32_t> members_of(n_files);
-    for (size_t f = 0; f < n_files; ++f) {
-        for (uint64_t p = file_off[f]; p < file_off[f + 1]; p += kCut) {
-            desc.push_back(DeflateDesc{p, uint32_t(std::min<uint64_t>(kCut, file_off[f + 1] - p)), 0});
-            ++members_of[f];
-        }
-    }
-    // in rounds of at most kRound members: 1 GiB of slots
-    constexpr size_t kRound = 16384;
-    const size_t round_cap = std::min(desc.size(), kRound);
-    Buf b_desc, b_slots, b_size, b_at, b_packed;
-    SECEDO_TRY(b_desc.alloc(round_cap * sizeof(DeflateDesc)));
-    SECEDO_TRY(b_slots.alloc(round_cap * kDeflateSlot));
-    SECEDO_TRY(b_size.alloc(round_cap * 4));
-    SECEDO_TRY(b_at.alloc(round_cap * 8));
-    Events ev;
-    SECEDO_TRY(hipEventCreate(&ev.a));
-    SECEDO_TRY(hipEventCreate(&ev.b));
+    std::vector<DeflateDesc> desc;  // every member of every file, in file order
+    for (size_t f = 0; f < n_files; ++f) member_cuts(file_off[f], file_off[f + 1], &desc);
     out->clear();
     out_off->assign(n_files + 1, 0);
-    std::vector<uint32_t> size(round_cap);
-    std::vector<uint64_t> at(round_cap);
+    if (table) *table = MemberTable{{}, std::vector<size_t>(n_files + 1, 0)};
     uint64_t end = 0;  // bytes of output laid out so far
     size_t file = 0;   // the file the next member belongs to
-    uint32_t left = n_files ? members_of[0] : 0;
-    if (table) {
-        table->m.clear();
-        table->first.assign(n_files + 1, 0);
-    }
-    const auto close_files = [&]() {  // files with no member left: their EOF member, the next file's start
-        while (file < n_files && left == 0) {
+    std::vector<uint64_t> eof_at;
+    // with the text before `pos` laid out, the files that end there: room for their EOF member, the next file's start
+    const auto close_files = [&](uint64_t pos) {
+        while (file < n_files && pos == file_off[file + 1]) {
             if (table) {
                 table->m.push_back(bamindexbuild::Member{end - (*out_off)[file], file_off[file + 1] - file_off[file], 0});
                 table->first[file + 1] = table->m.size();
             }
-            out->resize(end + kEofBytes);
-            for (uint32_t k = 0; k < kEofBytes; ++k) (*out)[end + k] = uint8_t(eof_member_byte(k));
+            eof_at.push_back(end);
             end += kEofBytes;
             (*out_off)[++file] = end;
-            left = file < n_files ? members_of[file] : 0;
         }
     };
-    close_files();
-    for (size_t b0 = 0; b0 < desc.size(); b0 += kRound) {
-        const uint32_t nb = uint32_t(std::min(kRound, desc.size() - b0));
-        Clock::time_point t0 = Clock::now();
-        SECEDO_TRY(hipMemcpyAsync(b_desc.p, desc.data() + b0, nb * sizeof(DeflateDesc), hipMemcpyHostToDevice, s));
-        SECEDO_TRY(hipEventRecord(ev.a, s));
-        SECEDO_TRY(bgzf_deflate(d_text, b_desc.as<DeflateDesc>(), nb, b_slots.as<uint8_t>(), b_size.as<uint32_t>(), s));
-        SECEDO_TRY(hipEventRecord(ev.b, s));
-        SECEDO_TRY(hipMemcpyAsync(size.data(), b_size.p, nb * 4, hipMemcpyDeviceToHost, s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        float k_ms = 0;
-        SECEDO_TRY(hipEventElapsedTime(&k_ms, ev.a, ev.b));
-        st.deflate_kernel_ms += k_ms;
+    close_files(file_off[0]);
+    Encoder enc(16384, true);  // 1 GiB of slots; the kernel's time is a field of the statistics
+    SECEDO_CALL(enc.run(d_text, desc, s, [&](size_t b0, uint32_t n, const uint32_t *bytes, uint64_t *at) {
         // where each member goes: behind the one before, EOF members in between
         const uint64_t first = end;
-        for (uint32_t k = 0; k < nb; ++k) {
-            const uint32_t bytes = size[k] & ~kDeflateStoredFlag;
-            if (bytes < kHeaderBytes + kTrailerBytes || bytes > kMaxMember)
-                return fail(SECEDO_E_STATE, "BGZF encoder: a member of " + std::to_string(bytes) + " bytes");
-            st.stored_blocks += (size[k] & kDeflateStoredFlag) != 0;
-            if (table)
-                table->m.push_back(bamindexbuild::Member{end - (*out_off)[file], desc[b0 + k].in_off - file_off[file],
-                                                         desc[b0 + k].n});
+        for (uint32_t k = 0; k < n; ++k) {
+            const DeflateDesc &d = desc[b0 + k];
+            if (table) table->m.push_back(bamindexbuild::Member{end - (*out_off)[file], d.in_off - file_off[file], d.n});
             at[k] = end - first;
-            end += bytes;
-            --left;
-            out->resize(end);
-            close_files();
+            end += bytes[k];
+            close_files(d.in_off + d.n);
         }
-        st.blocks += nb;
-        SECEDO_TRY(b_packed.alloc(end - first));
-        SECEDO_TRY(hipMemcpyAsync(b_at.p, at.data(), nb * 8, hipMemcpyHostToDevice, s));
-        SECEDO_TRY(bgzf_pack(b_slots.as<uint8_t>(), b_size.as<uint32_t>(), b_at.as<uint64_t>(), nb, b_packed.as<uint8_t>(), s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        st.deflate_ms += ms_lap(t0);
-        // one download; the EOF members laid out among these bytes are put back over what came down in their place
-        SECEDO_TRY(hipMemcpyAsync(out->data() + first, b_packed.p, end - first, hipMemcpyDeviceToHost, s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        for (size_t f = 1; f <= n_files; ++f) {
-            const uint64_t e = (*out_off)[f];
-            if (e < first + kEofBytes || e > end) continue;
-            for (uint32_t k = 0; k < kEofBytes; ++k) (*out)[e - kEofBytes + k] = uint8_t(eof_member_byte(k));
-        }
-        st.download_ms += ms_lap(t0);
-    }
-    st.compressed_bytes += end;
+        out->resize(end);
+        return enc.fetch(end - first, out, first);
+    }));
+    // the EOF members, over what came down in their place; files without text had no slice to make their room
+    Clock::time_point t0 = Clock::now();
+    out->resize(end);
+    const auto eof = eof_member();
+    for (const uint64_t e : eof_at) std::copy(eof.begin(), eof.end(), out->begin() + e);
+    enc.counts.download_ms += ms_since(t0);
+    if (counts) { *counts = enc.counts; return SECEDO_OK; }
+    g_info.blocks += enc.counts.members;
+    g_info.stored_blocks += enc.counts.stored_members;
+    g_info.deflate_kernel_ms += enc.counts.kernel_ms;
+    g_info.deflate_ms += enc.counts.deflate_ms;
+    g_info.download_ms += enc.counts.download_ms;
+    g_info.compressed_bytes += end;
     return SECEDO_OK;
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 namespace secedo {
+namespace bgzf { struct EncoderCounts; }  // bgzf_encoder.hpp
 namespace vcf {
 
 // The output kind of this call: secedo_variant_set_vcf_output, else SECEDO_VCF (unset or empty: plain). An unknown
@@ -57,17 +58,17 @@ int format_device(const std::vector<std::string> &preambles, const secedo_varian
 
 // The encoder alone: every file [file_off[f], file_off[f + 1]) of d_text (kDeflateInSlack readable bytes before and
 // after the whole) cut into members of at most 0xFF00 bytes, deflated, and closed with the EOF member. *out receives
-// the BGZF files back to back, out_off[files + 1] their bounds. Adds to info(), or to *counts where that is given (the
-// index bodies are not VCF files). Synchronises s. *table (may be null)
-// receives what was laid out: the members of file f are m[first[f], first[f + 1]), the EOF member last, each with its
-// byte in the file and the text bytes of the file it holds.
+// the BGZF files back to back, out_off[files + 1] their bounds (the loop around the kernels is bgzf_encoder.hpp's).
+// Adds the encoder's counts to info(), or gives them in *counts (the index bodies are not VCF files). Synchronises s.
+// *table (may be null) receives what was laid out: the members of file f are m[first[f], first[f + 1]), the EOF
+// member last, each with its byte in the file and the text bytes of the file it holds.
 struct MemberTable {
     std::vector<bamindexbuild::Member> m;
     std::vector<size_t> first;  // [files + 1]
 };
 int deflate_device(const uint8_t *d_text, const std::vector<uint64_t> &file_off, std::vector<uint8_t> *out,
                    std::vector<uint64_t> *out_off, hipStream_t s, MemberTable *table = nullptr,
-                   secedo_variant_vcf_info *counts = nullptr);
+                   bgzf::EncoderCounts *counts = nullptr);
 
 // BGZF: everything under out_dir, the records and tables in HBM. Resets info(). Synchronises s.
 int write_outputs_bgzf(const std::filesystem::path &out_dir, const std::string &reference, uint32_t num_clusters,

@@ -1,6 +1,6 @@
 // bam_split_test -- secedo_amd/csrc/bam_split.hpp on the host, under AddressSanitizer and UBSan: the header text
-// (@RG merge, the ID clash, a reference-list mismatch), the key, the member cuts of an extent and the lookup from an
-// output byte to its record. Arrays the lookup and the parsers read live in heap blocks of their exact size, so a read
+// (@RG merge, the ID clash, a reference-list mismatch), the key and the lookup from an output byte to its record (the
+// member cuts of an extent are checked with their home, in bgzf_members_test.cpp). Arrays the lookup and the parsers read live in heap blocks of their exact size, so a read
 // past them is a sanitizer report. Prints "ok <n> checks" and exits 0, or names the first check that failed.
 #include "bam_split.hpp"
 
@@ -107,30 +107,6 @@ int test_key() {
     return 0;
 }
 
-int test_cuts() {
-    const uint64_t base = 12345;  // an extent need not start at 0: cuts count from its start
-    const uint64_t sizes[] = {0, 1, kCut, kCut + 1, 3ull * kCut};
-    const size_t want[] = {0, 1, 1, 2, 3};
-    for (size_t i = 0; i < 5; ++i) {
-        std::vector<Cut> cuts;
-        member_cuts(base, base + sizes[i], &cuts);
-        CHECK(cuts.size() == want[i]);
-        uint64_t at = base;
-        for (size_t k = 0; k < cuts.size(); ++k) {
-            CHECK(cuts[k].off == at && cuts[k].n >= 1 && cuts[k].n <= kCut);
-            CHECK(k + 1 == cuts.size() || cuts[k].n == kCut);  // every member but the last is full
-            at += cuts[k].n;
-        }
-        CHECK(at == base + sizes[i]);
-    }
-    std::vector<Cut> cuts;
-    member_cuts(0, kCut + 1, &cuts);
-    CHECK(cuts[1].off == kCut && cuts[1].n == 1);
-    member_cuts(7, 7, &cuts);  // appends nothing
-    CHECK(cuts.size() == 2);
-    return 0;
-}
-
 int test_lookup() {
     // records of 40, 37, 70000 and 41 bytes; dst has n + 1 entries, in a heap block of its exact size
     const uint64_t len[] = {40, 37, 70000, 41};
@@ -183,7 +159,7 @@ int test_lookup() {
 }  // namespace
 
 int main() {
-    if (test_header() || test_key() || test_cuts() || test_lookup()) return 1;
+    if (test_header() || test_key() || test_lookup()) return 1;
     std::printf("ok %d checks\n", g_checks);
     return 0;
 }

@@ -126,8 +126,6 @@ int main(int argc, char **argv) {
         }
         std::fwrite(m.buf.data(), 1, size, out);
     }
-    uint8_t eof[kEofBytes];
-    for (uint32_t k = 0; k < kEofBytes; ++k) eof[k] = uint8_t(eof_member_byte(k));
-    std::fwrite(eof, 1, kEofBytes, out);
+    std::fwrite(eof_member().data(), 1, kEofBytes, out);
     return std::fclose(out) == 0 ? 0 : 3;
 }

@@ -1,7 +1,7 @@
 // bgzf_members_test -- secedo_amd/csrc/bgzf_members.hpp on the host, under AddressSanitizer and UBSan.
 //   bgzf_members_test list <file>
 //       prints "total <inflated bytes>" and "member coff poff clen crc isize out" per member, or "rejected: <why>".
-//   bgzf_members_test small | hostile | span | words | inflate
+//   bgzf_members_test small | hostile | span | cuts | words | inflate
 //       the checks of that group on files the program writes itself (zlib deflates their members); prints "ok ..." and
 //       exits 0, or names the line of the first check that failed and exits 1.
 // Every listing reads a heap block of the file's exact size, so a read past the bytes is a sanitizer report.
@@ -221,6 +221,35 @@ int span() {
     return 0;
 }
 
+// the writers' cut rule: the members of an extent, one every kCut bytes from its start
+int cuts() {
+    using bz::kCut;
+    const uint64_t base = 12345;  // an extent need not start at 0: cuts count from its start
+    const uint64_t sizes[] = {0, 1, kCut - 1, kCut, kCut + 1, 3ull * kCut};
+    const size_t want[] = {0, 1, 1, 1, 2, 3};
+    for (size_t i = 0; i < 6; ++i) {
+        std::vector<bz::DeflateDesc> desc;
+        bz::member_cuts(base, base + sizes[i], &desc);
+        CHECK(desc.size() == want[i]);
+        uint64_t at = base;
+        for (size_t k = 0; k < desc.size(); ++k) {
+            CHECK(desc[k].in_off == at && desc[k].n >= 1 && desc[k].n <= kCut && desc[k].reserved == 0);
+            CHECK(k + 1 == desc.size() || desc[k].n == kCut);  // every member but the last is full
+            at += desc[k].n;
+        }
+        CHECK(at == base + sizes[i]);
+    }
+    std::vector<bz::DeflateDesc> desc;
+    bz::member_cuts(0, kCut + 1, &desc);
+    CHECK(desc[1].in_off == kCut && desc[1].n == 1);
+    bz::member_cuts(7, 7, &desc);  // appends nothing
+    CHECK(desc.size() == 2);
+    bz::member_cuts(7, 8, &desc);  // appends behind what is there
+    CHECK(desc.size() == 3 && desc[2].in_off == 7 && desc[2].n == 1);
+    std::printf("ok cuts\n");
+    return 0;
+}
+
 int words() {
     for (uint32_t s = 0; s < bz::kStatusCodes; ++s)
         CHECK(std::string(status_text(s)) ==
@@ -299,8 +328,9 @@ int main(int argc, char **argv) {
     if (argc == 2 && mode == "small") return small();
     if (argc == 2 && mode == "hostile") return hostile();
     if (argc == 2 && mode == "span") return span();
+    if (argc == 2 && mode == "cuts") return cuts();
     if (argc == 2 && mode == "words") return words();
     if (argc == 2 && mode == "inflate") return inflate_cases();
-    std::fprintf(stderr, "usage: bgzf_members_test list <file> | small | hostile | span | words | inflate\n");
+    std::fprintf(stderr, "usage: bgzf_members_test list <file> | small | hostile | span | cuts | words | inflate\n");
     return 2;
 }

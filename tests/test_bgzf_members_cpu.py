@@ -1,7 +1,8 @@
 """The host code every BGZF reader shares (secedo_amd/csrc/bgzf_members.hpp), without a GPU, under AddressSanitizer and
 UBSan (secedo_amd/csrc/build/bgzf_members_test): the member list of every golden BAM against the table Python makes of
 the file's bytes, and the program's own groups of checks: the small files, the cut and mutated files, the payload span
-and the descriptors of a range, the words of a member that does not inflate, and the zlib inflate of one member."""
+and the descriptors of a range, the writers' member cuts of an extent, the words of a member that does not inflate, and
+the zlib inflate of one member."""
 import os
 import struct
 import subprocess
@@ -59,6 +60,6 @@ def test_the_test_writers_files_and_the_three_refusals(tmp_path):
         assert ": " + listed(path) == tail
 
 
-@pytest.mark.parametrize("group", ["small", "hostile", "span", "words", "inflate"])
+@pytest.mark.parametrize("group", ["small", "hostile", "span", "cuts", "words", "inflate"])
 def test_the_programs_own_checks(group):
     assert program(group).startswith("ok " + group)

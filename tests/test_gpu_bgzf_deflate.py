@@ -62,6 +62,59 @@ def test_one_launch_with_300_tiny_inputs(host, tmp_path):
     assert files[1] == dc.host_encode(inputs[1], tmp_path, "tiny")
 
 
+# ---- the slice borders of the encoder's driver (bgzf_encoder.cpp), reached through SECEDO_BGZF_SLICE_MEMBERS
+
+def _border_inputs():
+    """Eight files of 0, 1, 0xFF00, 2 * 0xFF00 + 1, 5, 0, 0 and 0xFF00 + 1 bytes: 8 members. The one of 0xFF00 bytes
+    is random (a stored member), the rest SAM-like text. In this order 6 members lie in front of the two empty files,
+    so their EOF members follow a slice's last member at 1, 2 and 3 members per slice."""
+    sam = CASES["sam_%d" % (2 * dc.CUT + 1)]
+    sizes = [0, 1, dc.CUT, 2 * dc.CUT + 1, 5, 0, 0, dc.CUT + 1]
+    return [CASES["random_65280"] if n == dc.CUT else sam[:n] for n in sizes]
+
+
+def _borders_met(counts, per_slice):
+    """From the files' member counts: (a file's last member ends a slice, a file's last member starts a slice, a file
+    lies over a slice border, an empty file follows a slice's last member), with more slices behind in every case"""
+    total, first = sum(counts), np.concatenate([[0], np.cumsum(counts)])
+    spans = [(int(first[f]), int(first[f + 1])) for f in range(len(counts))]
+    return (any(a < b < total and b % per_slice == 0 for a, b in spans),
+            any(a < b and (b - 1) % per_slice == 0 for a, b in spans),
+            any(k % per_slice == 0 for a, b in spans for k in range(a + 1, b)),
+            any(0 < a == b < total and a % per_slice == 0 for a, b in spans))
+
+
+@pytest.fixture(scope="module")
+def border_host(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("border_host")
+    return [dc.host_encode(d, tmp, "f%d" % k) for k, d in enumerate(_border_inputs())]
+
+
+@pytest.fixture(scope="module")
+def border_unset():
+    files = variant.bgzf_deflate_many(_border_inputs())
+    return files, variant.vcf_stats()
+
+
+@pytest.mark.parametrize("per_slice", ["1", "2", "3", "0", "99999"])
+def test_slice_borders_of_the_vcf_driver(border_host, border_unset, monkeypatch, per_slice):
+    inputs = _border_inputs()
+    counts = [-(-len(d) // dc.CUT) for d in inputs]
+    assert sum(counts) == 8
+    if per_slice in ("1", "2", "3"):
+        assert _borders_met(counts, int(per_slice)) == (True, True, True, True)
+    monkeypatch.setenv("SECEDO_BGZF_SLICE_MEMBERS", per_slice)  # 0 and a value above the writer's 16384: one slice
+    files = variant.bgzf_deflate_many(inputs)
+    st = variant.vcf_stats()
+    assert files == border_host  # every file is the host encoder's
+    assert files == border_unset[0]
+    for raw, data in zip(files, inputs):
+        dc.check_file(raw, data, with_tokens=False)
+    assert (st["blocks"], st["stored_blocks"], st["compressed_bytes"]) == (8, 1, sum(map(len, files)))
+    for key in ("files", "text_bytes", "blocks", "stored_blocks", "compressed_bytes"):
+        assert st[key] == border_unset[1][key], key
+
+
 @pytest.mark.parametrize("which", ["vcf", "sam"])
 def test_ratio_against_zlib_level_1(which):
     """Compressed size over zlib's at level 1 on the same blocks (the bound and the measured quotient are in

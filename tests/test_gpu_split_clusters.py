@@ -136,6 +136,31 @@ def test_long_record(tmp_path):
     assert info["stored_members"] >= 1 and info["members"] > info["stored_members"]
 
 
+@pytest.mark.parametrize("which", ["edges", "long"])
+def test_slice_borders_of_the_encoder(tmp_path, monkeypatch, which):
+    """The two sets above with SECEDO_BGZF_SLICE_MEMBERS at 1 and 2 (members of one file on both sides of a slice
+    border, in the headers' run and in the chromosome's), at 0 and above the writer's 4096: the expected files, and the
+    counts of the run without the variable."""
+    cells, clustering = (se.edge_cells(), [0, 1, 2]) if which == "edges" else (se.long_read_cells(), [0, 1])
+    paths = []
+    for c, recs in enumerate(cells):
+        paths.append(str(tmp_path / ("%s_%d.bam" % (which, c))))
+        bw.write_bam(paths[-1], se.REFS, recs)
+    expected, _ = se.expected_files([se.source_of_recs(se.REFS, recs) for recs in cells], clustering, [0], tmp_path)
+    assert max(len(se.member_sizes(raw)) for raw in expected) >= 4  # header, two of the stream, EOF: a border to cross
+    infos = {}
+    for value in (None, "1", "2", "0", "99999"):
+        if value is not None:
+            monkeypatch.setenv("SECEDO_BGZF_SLICE_MEMBERS", value)
+        out = tmp_path / ("out_%s" % value)
+        out.mkdir()
+        infos[value] = secedo_amd.split_clusters(paths, clustering, out, [0])
+        check_outputs(out, expected)
+        for key in ("members", "stored_members", "compressed_bytes", "records", "text_bytes"):
+            assert infos[value][key] == infos[None][key], (value, key)
+    assert (infos[None]["members"], infos[None]["stored_members"]) == members_and_stored(expected)
+
+
 def test_tag_mode(case1, tmp_path):
     recs, n_extra = se.multiplexed_records(case1["cells"])
     path = str(tmp_path / "multiplexed.bam")

@@ -131,6 +131,27 @@ def test_extent_edges(tmp_path):
     check_stats(info, stats, expected)
 
 
+def test_extent_edges_with_one_member_per_slice(tmp_path, monkeypatch):
+    """The set above with SECEDO_BGZF_SLICE_MEMBERS=1: the members of cluster 1's file lie in different slices of the
+    encoder's driver. The expected files, and the counts of the run without the variable."""
+    names = ["full-cell", "o", "single"]
+    cells = sr.edge_items(names)
+    paths = write_cells(tmp_path, cells, "edge_%d")
+    sources = [se.source_of_recs(se.REFS, c) for c in cells]
+    expected, _, stats = sr.expected_files(sources, [0, 1, 2], [0], names, tmp_path)
+    infos = []
+    for value in (None, "1"):
+        if value is not None:
+            monkeypatch.setenv("SECEDO_BGZF_SLICE_MEMBERS", value)
+        out = tmp_path / ("out_%s" % value)
+        out.mkdir()
+        infos.append(secedo_amd.split_clusters(paths, [0, 1, 2], out, [0], read_groups=True, cell_names=names))
+        check_outputs(out, expected)
+        check_stats(infos[-1], stats, expected)
+    for key in ("members", "stored_members", "compressed_bytes"):
+        assert infos[1][key] == infos[0][key], key
+
+
 def test_long_record(tmp_path):
     """The hole of the 70 000-base read lies behind its ML:B:C array, dozens of tiles from the record's start."""
     cells = sr.long_items()

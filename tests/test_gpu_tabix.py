@@ -336,6 +336,28 @@ def test_tbi_with_plain_output_raises_and_the_setting_routes_a_call(tmp_path):
         assert _raw_index(str(tmp_path / "a" / (n + ".vcf.gz.tbi"))) == te.expected_bytes(gz)
 
 
+def test_writer_with_one_member_per_slice(tmp_path, monkeypatch):
+    """The two-cluster call above with SECEDO_BGZF_SLICE_MEMBERS=1: every file border of the .vcf.gz files and of the
+    index bodies is a slice border of the encoder's driver. The preamble holds the time to the second, so the pair of
+    calls is made again should the second have changed between them."""
+    p = _flat([[(1, [i << 2 for i in range(10)])]])
+    for attempt in range(3):
+        dirs = [tmp_path / ("%s%d" % (k, attempt)) for k in ("unset", "one")]
+        variant.variant_calling(p, [1] * 10, FEMALE, "", 1e-3, 1e-3, str(dirs[0]), vcf_output="bgzf", vcf_index="tbi")
+        with monkeypatch.context() as env:
+            env.setenv("SECEDO_BGZF_SLICE_MEMBERS", "1")
+            variant.variant_calling(p, [1] * 10, FEMALE, "", 1e-3, 1e-3, str(dirs[1]), vcf_output="bgzf",
+                                    vcf_index="tbi")
+        unset, one = _files(dirs[0]), _files(dirs[1])
+        if all(unset[n] == one[n] for n in ("cluster_0.vcf.gz", "cluster_1.vcf.gz")):
+            break
+    assert sorted(one) == sorted(unset) and len([n for n in one if n.endswith(".tbi")]) == 3
+    for n in ("cluster_0", "cluster_1", "common"):
+        gz = one[n + ".vcf.gz"]
+        assert gz == unset[n + ".vcf.gz"] and one[n + ".vcf.gz.tbi"] == unset[n + ".vcf.gz.tbi"], n
+        assert _raw_index(str(dirs[1] / (n + ".vcf.gz.tbi"))) == te.expected_bytes(gz), n
+
+
 # --- 4. the command lines ----------------------------------------------------------------------------------------
 
 def test_cli_writes_the_index_files(tmp_path, capsys):
