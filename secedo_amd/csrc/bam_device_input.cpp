@@ -13,8 +13,15 @@
 // A file read through its index (bam_host.hpp's IndexPlan) has one chain per span instead of one per file: the chain
 // enters at the span's first record inside its first member and its bytes end at the span's limit. The spans of a
 // file go one after another, span k of every file of the call in the same batches (the first spans together with the
-// files read in full), so many small files still share one upload, one inflate launch and one walk; the file's walk state (record count, last record, runs) passes from span
-// to span as it passes from range to range. A span larger than a batch goes alone, in ranges of members.
+// files read in full), so many small files still share one upload, one inflate launch and one walk; the file's walk
+// state (record count, last record, runs) passes from span to span as it passes from range to range. A span larger
+// than a batch goes alone, in ranges of members.
+//
+// run_batch is a sequence of stages over BamDevWork, each a function of its own: lay_out (where everything of the
+// batch lies: bam_batch.hpp's lay_out_batch, plain arithmetic that tests/cpp/bam_batch_test.cpp checks on the host),
+// upload, inflate_batch, walk_and_scan, verdicts (the errors, in the host route's order and words), check_results,
+// index_batch (index build only), fetch_taken, append_runs (the runs into ChrInput, the state and the device carry
+// for the next range). Ranges are cut by bgzf_members.hpp's next_range.
 //
 // secedo_bam_index_build (at the end of the file) sends files through the same batches and ranges with no chromosome
 // requested, and after each batch's walk the index pass of bam_index_kernels.hip over its records: the heads of the
@@ -40,8 +47,8 @@ namespace bw = secedo::bamwalk;
 
 namespace {
 
-// one BAM file on its way through the device route
-struct DevFile {
+// one BAM file on its way through the device route; its walk state (FileWalk) passes between its ranges and spans
+struct DevFile : FileWalk {
     size_t f = 0;  // its index in the call's file list
     std::string path;
     Mapped m;
@@ -50,11 +57,7 @@ struct DevFile {
     size_t hb = 0;               // leading members inflated here: the header's
     Header h;
     std::vector<uint8_t> carry;  // what they hold past the first record
-    // the walk's state between the ranges of a file that goes alone
-    uint64_t rec_base = 0, dev_carry = 0;
-    bool has_prev = false;
-    int32_t prev_ref = 0, prev_pos = 0;
-    std::vector<uint32_t> run_first, run_last;  // per requested chromosome (bam_walk.hpp's started / done rule)
+    uint64_t dev_carry = 0;  // the cut record's bytes at the front of the buffer, between the ranges of a file
     bool sorted = true;
     // read through its index: the plan, and of the span under way what the ranges so far found per requested chromosome
     const IndexPlan *plan = nullptr;
@@ -66,60 +69,102 @@ struct DevFile {
     std::unique_ptr<bamindexbuild::Builder> builder;
     std::string out_path;
     uint64_t device_bytes() const { return carry.size() + (hb < blocks.size() ? total - blocks[hb].out : 0); }
+    // a fresh file: no run of a requested chromosome has started
+    void start(size_t file, const std::string &name, size_t n_chr) {
+        f = file;
+        path = name;
+        run_first.assign(n_chr, bw::kNoRun);
+        run_last.assign(n_chr, bw::kNoRun);
+    }
 };
 
-// members [b0, b1) of a file in one batch
-struct Piece {
-    DevFile *df;
-    size_t b0, b1;
-    bool final;
-    uint32_t first_member = 0;   // of the batch
-    const Span *span = nullptr;  // an indexed file: b0, b1 count the span's members
-    bool first_range() const { return span ? b0 == 0 : b0 == df->hb; }
-    const std::vector<Block> &blocks() const { return span ? span->blocks : df->blocks; }
-    const Mapped &mapped() const { return span ? df->plan->m : df->m; }
+// members [b0, b1) of a file in one batch: what the layout takes (bam_batch.hpp), and the file
+struct Piece : BatchPiece {
+    DevFile *df = nullptr;
 };
+
+// span: an indexed file, b0 and b1 count the span's members. Made when the piece joins its batch: a file's carries
+// and its place in the file do not change until the batch has run.
+Piece piece_of(DevFile *df, size_t b0, size_t b1, bool final, const Span *span = nullptr) {
+    const Mapped &m = span ? df->plan->m : df->m;
+    Piece p;
+    p.df = df;
+    p.blocks = span ? &span->blocks : &df->blocks;
+    p.b0 = b0, p.b1 = b1;
+    p.file = m.p, p.file_bytes = m.n;
+    p.first_range = span ? b0 == 0 : b0 == df->hb;
+    p.final = final;
+    p.carry_bytes = df->carry.data();
+    p.carry = !p.first_range ? df->dev_carry : span ? 0 : df->carry.size();
+    p.walk = df;
+    p.span = span;
+    p.n_ref = df->h.n_ref;
+    p.lin0 = b0 < df->blocks.size() ? df->blocks[b0].out : df->total;
+    return p;
+}
 
 }  // namespace
 
+// What a call keeps on the device route, grouped by who fills and who reads it.
 struct BamDevWork {
     hipStream_t s = nullptr;
-    uint8_t *h_in = nullptr;  // pinned staging of the compressed bytes
-    size_t h_in_cap = 0;
-    Dev<uint8_t> in, buf, out, tmp, carry;
-    Dev<BgzfDesc> desc;
-    Dev<uint32_t> status, lists, rewalk, seg_cnt, seg_base, chr, r_off, r_file, sel, sel_scan;
-    Dev<bw::Seg> segs;
-    Dev<bw::SegWalk> walk;
-    Dev<bw::SegJoin> join;
-    Dev<WalkFile> files;
-    Dev<WalkRun> runs;
-    Dev<SpanCheck> checks;
-    std::vector<SpanCheck> h_checks;
-    Dev<int32_t> r_ref, r_pos, sel_pos;
-    Dev<uint64_t> size, size_scan, sel_off, sel_idx, totals;
-    Dev<unsigned long long> per_ref;
+    // the call: set once, by start_work and the entry points
     std::vector<uint32_t> chr_ids;  // the requested chromosomes, each once
+    Dev<uint32_t> chr;
     uint32_t n_ref = 0;             // scan: per_ref counts n_ref RefIDs and the unmapped records
     bool scan = false;              // scan: unsorted input is no error, nothing is taken
+    Dev<unsigned long long> per_ref;
     // index build: the index pass follows the walk of every batch; `failed` = the piece whose error a batch returned
     bool index = false;
     uint32_t failed = UINT32_MAX;
+    // the batch's layout (bam_batch.hpp): lay_out fills it, every stage reads it; its files, runs, checks and ix_files
+    // are also where the walk's and the index pass's results come back to
+    BatchLayout lay;
+    // staging and inflate: upload fills them, inflate and the walk read them; carry: the cut record between ranges
+    uint8_t *h_in = nullptr;  // pinned staging of the compressed bytes
+    size_t h_in_cap = 0;
+    Dev<uint8_t> in, buf, carry;
+    Dev<BgzfDesc> desc;
+    Dev<uint32_t> status;
+    // the walk: per segment, per file, per record; tmp is the scans' (the index pass's too)
+    Dev<bw::Seg> segs;
+    Dev<bw::SegWalk> walk;
+    Dev<bw::SegJoin> join;
+    Dev<uint32_t> lists, rewalk, seg_cnt, seg_base;
+    Dev<WalkFile> files;
+    Dev<WalkRun> runs;
+    Dev<SpanCheck> checks;
+    Dev<uint8_t> tmp;
+    Dev<uint32_t> r_off, r_file, sel, sel_scan;
+    Dev<int32_t> r_ref, r_pos;
+    Dev<uint64_t> size, size_scan, totals;
+    uint32_t n_rec = 0;                 // records of the batch
+    uint64_t n_sel = 0, sel_bytes = 0;  // the taken ones, and their bytes
+    WalkBatch walk_batch() const {
+        return WalkBatch{buf.p,   lay.buf_bytes / 16 * 16,    segs.p,  files.p,  uint32_t(lay.segs.size()),
+                         uint32_t(lay.files.size()), lists.p, rewalk.p, walk.p, join.p, seg_cnt.p, seg_base.p};
+    }
+    WalkRecords walk_records() const {
+        return WalkRecords{n_rec, r_off.p, r_file.p, r_ref.p, r_pos.p, sel.p, size.p, sel_scan.p, size_scan.p};
+    }
+    // the taken records: fetch_taken fills them, append_runs reads them
+    Dev<uint8_t> out;
+    Dev<uint64_t> sel_off, sel_idx;
+    Dev<int32_t> sel_pos;
+    std::vector<uint8_t> h_out;
+    std::vector<uint64_t> h_sel_off, h_sel_idx;
+    std::vector<int32_t> h_sel_pos;
+    // the index pass: index_batch fills and reads them
     Dev<IndexFile> ix_files;
     Dev<uint32_t> ix_meta, ix_head, ix_head_scan;
     Dev<uint64_t> ix_key, ix_key_max, ix_n_win, ix_n_win_scan;
     Dev<IndexHead> ix_heads;
     Dev<IndexWin> ix_wins;
-    std::vector<IndexFile> h_ix_files;
     std::vector<IndexHead> h_heads;
     std::vector<IndexWin> h_wins;
-    std::vector<BgzfDesc> h_desc;
-    std::vector<bw::Seg> h_segs;
-    std::vector<WalkFile> h_files;
-    std::vector<WalkRun> h_runs;
-    std::vector<uint8_t> h_out;
-    std::vector<uint64_t> h_sel_off, h_sel_idx;
-    std::vector<int32_t> h_sel_pos;
+    IndexRecords index_records() const {
+        return IndexRecords{ix_meta.p, ix_key.p, ix_key_max.p, ix_head.p, ix_head_scan.p, ix_n_win.p, ix_n_win_scan.p};
+    }
     ~BamDevWork() {
         if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
         if (h_in) (void)hipHostFree(h_in);
@@ -135,8 +180,7 @@ int start_work(BamDevWork *w, const std::vector<ChrInput> &chrs) {
     if (!w->s) SECEDO_TRY(hipStreamCreateWithFlags(&w->s, hipStreamNonBlocking));
     if (w->chr_ids.empty() && !chrs.empty()) {
         for (const auto &ci : chrs)
-            if (std::find(w->chr_ids.begin(), w->chr_ids.end(), ci.chromosome) == w->chr_ids.end())
-                w->chr_ids.push_back(ci.chromosome);
+            if (slot_of(w->chr_ids, ci.chromosome) == w->chr_ids.size()) w->chr_ids.push_back(ci.chromosome);
         SECEDO_TRY(w->chr.grow(w->chr_ids.size(), 0, w->s));
         SECEDO_TRY(hipMemcpyAsync(w->chr.p, w->chr_ids.data(), w->chr_ids.size() * 4, hipMemcpyHostToDevice, w->s));
         SECEDO_TRY(hipStreamSynchronize(w->s));
@@ -146,8 +190,7 @@ int start_work(BamDevWork *w, const std::vector<ChrInput> &chrs) {
 
 // The file mapped, its members listed, the header's members inflated here and the header parsed.
 int open_file(size_t f, const std::string &path, size_t n_chr, DevFile *df) {
-    df->f = f;
-    df->path = path;
+    df->start(f, path, n_chr);
     SECEDO_CALL(open_bgzf(path, &df->m, &df->blocks, &df->total));
     std::vector<uint8_t> head;
     for (;;) {
@@ -171,37 +214,24 @@ int open_file(size_t f, const std::string &path, size_t n_chr, DevFile *df) {
             o += 4;
         }
     }
-    df->run_first.assign(n_chr, bw::kNoRun);
-    df->run_last.assign(n_chr, bw::kNoRun);
     route().host_blocks += df->hb;
     return SECEDO_OK;
 }
 
-const uint64_t kMaxBatchBytes = (1ull << 32) - (1u << 20);  // offsets in a batch are u32
-
 // the error of one file of a finished batch, if it has one: its lowest record error, else its first bad member
-int file_error(const BamDevWork &w, const Piece &p, const WalkFile &F) {
+int file_error(const BamDevWork &w, const Piece &p, uint32_t first_member, const WalkFile &F) {
     unsigned long long e = F.err;
     if (!w.scan && F.unsorted != ~0ull) e = std::min(e, F.unsorted << 8 | bw::kErrUnsorted);
     const std::string &path = p.df->path;
     if (e != ~0ull) {
         const uint32_t code = uint32_t(e & 0xFF);
-        const std::string where = record_where(path, 0, 0, e >> 8, Stage::kLoad, p.span != nullptr);
         if (p.span && (code == bw::kErrTruncated || code == bw::kErrBlockSize))  // as the host walk of a span
-            return index_mismatch(path, "the record chain breaks: indexed record " + std::to_string(e >> 8) +
-                                            (code == bw::kErrTruncated ? " is truncated" : " has a bad block_size"));
-        std::string what;
-        if (code == bw::kErrTruncated) what = " is truncated";
-        else if (code == bw::kErrBlockSize) what = " has a bad block_size";
-        else if (code == bw::kErrLonger) what = " is longer than its block_size";
-        else if (code == bw::kErrUnsorted) what = ": input is not coordinate-sorted";
-        else if (code == bw::kErrNegative) what = " has a negative position";
-        else if (code == bw::kErrCigarSeq) what = ": CIGAR and SEQ lengths differ";
-        else what = ": invalid CIGAR op code " + std::to_string(code & 15);
-        return fail(SECEDO_E_INVALID_ARG, where + what);
+            return chain_break(path, e >> 8, code);
+        return fail(SECEDO_E_INVALID_ARG,
+                    record_where(path, 0, 0, e >> 8, Stage::kLoad, p.span != nullptr) + defect_tail(code));
     }
     if (F.bad != ~0ull) {
-        const uint64_t k = p.b0 + ((F.bad >> 8) - p.first_member);
+        const uint64_t k = p.b0 + ((F.bad >> 8) - first_member);
         return bad_block(path, p.span ? bm::block_where_byte(p.span->blocks[k].coff) : bm::block_where(k),
                          bm::status_text(uint32_t(F.bad & 0xFF)));
     }
@@ -210,8 +240,11 @@ int file_error(const BamDevWork &w, const Piece &p, const WalkFile &F) {
 
 // The index pass over the records of a walked batch whose files passed the walk's checks: its own errors first, in
 // file order, then the heads and windows to each file's builder. A builder is touched only by a batch without errors.
-int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch &wb, const WalkRecords &wr) {
+int index_batch(BamDevWork *w, const std::vector<Piece> &pieces) {
     hipStream_t s = w->s;
+    const WalkBatch wb = w->walk_batch();
+    const WalkRecords wr = w->walk_records();
+    std::vector<IndexFile> &h_ix_files = w->lay.ix_files;
     const uint32_t n_files = uint32_t(pieces.size()), n = wr.n;
     SECEDO_TRY(w->ix_files.grow(n_files, 0, s));
     SECEDO_TRY(w->ix_meta.grow(n, 0, s));
@@ -223,10 +256,8 @@ int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch
     SECEDO_TRY(w->ix_n_win_scan.grow(uint64_t(n) + 1, 0, s));
     const size_t tb = std::max(scan_bytes(uint64_t(n) + 1), index_scan_bytes(n));
     SECEDO_TRY(w->tmp.grow(tb, 0, s));
-    SECEDO_TRY(hipMemcpyAsync(w->ix_files.p, w->h_ix_files.data(), n_files * sizeof(IndexFile), hipMemcpyHostToDevice,
-                              s));
-    const IndexRecords x{w->ix_meta.p,      w->ix_key.p,   w->ix_key_max.p,  w->ix_head.p,
-                         w->ix_head_scan.p, w->ix_n_win.p, w->ix_n_win_scan.p};
+    SECEDO_TRY(hipMemcpyAsync(w->ix_files.p, h_ix_files.data(), n_files * sizeof(IndexFile), hipMemcpyHostToDevice, s));
+    const IndexRecords x = w->index_records();
     SECEDO_TRY(index_records(wb, wr, x, w->ix_files.p, w->tmp.p, tb, s));
     SECEDO_TRY(index_flags(wb, wr, x, s));
     SECEDO_TRY(exclusive_sum(w->tmp.p, tb, x.head, x.head_scan, uint64_t(n) + 1, s));
@@ -235,11 +266,10 @@ int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch
     uint64_t n_wins = 0;
     SECEDO_TRY(hipMemcpyAsync(&n_heads, x.head_scan + n, 4, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipMemcpyAsync(&n_wins, x.n_win_scan + n, 8, hipMemcpyDeviceToHost, s));
-    SECEDO_TRY(hipMemcpyAsync(w->h_ix_files.data(), w->ix_files.p, n_files * sizeof(IndexFile), hipMemcpyDeviceToHost,
-                              s));
+    SECEDO_TRY(hipMemcpyAsync(h_ix_files.data(), w->ix_files.p, n_files * sizeof(IndexFile), hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     for (uint32_t k = 0; k < n_files; ++k) {
-        const unsigned long long e = w->h_ix_files[k].err;
+        const unsigned long long e = h_ix_files[k].err;
         if (e == ~0ull) continue;
         w->failed = k;
         const std::string where = record_where(pieces[k].df->path, 0, 0, e >> 8, Stage::kLoad);
@@ -247,7 +277,7 @@ int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch
         return fail(SECEDO_E_INVALID_ARG,
                     where + (code == kIndexErrRef   ? " has a RefID outside the reference list"
                              : code == kIndexErrEnd ? " ends past position 2^29: a BAI index cannot hold it"
-                                                    : " is longer than its block_size"));
+                                                    : defect_tail(bw::kErrLonger)));
     }
     // a record starts at most one run, and is the first over at most the 2^15 windows of its reference
     if (n_heads > n || n_wins > (uint64_t(n) << 15))
@@ -285,281 +315,206 @@ int index_batch(BamDevWork *w, const std::vector<Piece> &pieces, const WalkBatch
     return SECEDO_OK;
 }
 
-// One batch through the device: inflate, walk, the taken records back into runs / in (both may be null: scan).
-int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Inputs *in, Runs *runs,
-              secedo_bam_times *t) {
+// ---- the stages of one batch, in run_batch's order
+
+// Stage 1: where everything of the batch lies (bam_batch.hpp).
+int lay_out(BamDevWork *w, const std::vector<Piece> &pieces) {
+    if (lay_out_batch(pieces, w->chr_ids, w->index, &w->lay)) return SECEDO_OK;
+    return fail(SECEDO_E_LIMIT, pieces[w->lay.overflow].df->path +
+                                    ": a batch of 4 GiB or more of inflated BAM (a record that long, or "
+                                    "SECEDO_BAM_BATCH_BYTES too large)");
+}
+
+// Stage 2: the compressed bytes into staging, the device buffers grown, staging and the layout's tables up.
+int upload(BamDevWork *w, const std::vector<Piece> &pieces, uint32_t threads) {
     hipStream_t s = w->s;
-    Clock::time_point t0 = Clock::now();
-    const uint32_t n_files = uint32_t(pieces.size()), n_chr = uint32_t(w->chr_ids.size());
-    // ---- layout: the staging buffer, the descriptors, the inflated buffer, the segments
-    struct Copy {
-        uint64_t dst;
-        const uint8_t *src;
-        uint64_t n;
-    };
-    std::vector<Copy> copies;
-    w->h_desc.clear();
-    w->h_segs.clear();
-    w->h_files.assign(n_files, WalkFile{});
-    w->h_runs.assign(size_t(n_files) * n_chr, WalkRun{});
-    w->h_checks.assign(size_t(n_files) * n_chr, SpanCheck{});
-    bool any_span = false;
-    if (w->index) {
-        w->failed = UINT32_MAX;
-        w->h_ix_files.assign(n_files, IndexFile{});
-        uint64_t seg = 0;
-        for (uint32_t k = 0; k < n_files; ++k) {
-            w->h_ix_files[k] = IndexFile{0, seg, pieces[k].df->h.n_ref, 0, ~0ull};
-            seg += uint64_t(pieces[k].df->h.n_ref) + 1;
-        }
-    }
-    uint64_t in_pos = kBgzfInSlack, out_pos = 0, n_list = 0;
-    for (uint32_t k = 0; k < n_files; ++k) {
-        Piece &p = pieces[k];
-        DevFile &df = *p.df;
-        WalkFile &F = w->h_files[k];
-        p.first_member = uint32_t(w->h_desc.size());
-        const bool first_range = p.first_range();
-        const uint64_t carry = !first_range ? df.dev_carry : p.span ? 0 : df.carry.size();
-        if (first_range && carry) {
-            F.carry_src = in_pos;
-            F.carry_len = uint32_t(carry);
-            copies.push_back({in_pos, df.carry.data(), carry});
-            in_pos += carry + kBgzfInSlack;
-        }
-        const uint64_t data_start = out_pos;
-        uint64_t o = data_start + carry;
-        if (p.b0 < p.b1) {
-            const std::vector<Block> &bl = p.blocks();
-            const bm::PayloadSpan sp = bm::payload_span(bl, p.b0, p.b1, p.mapped().n);
-            const uint8_t *lo = p.mapped().p + sp.lo;
-            for (uint64_t c = 0; c < sp.hi - sp.lo; c += 4u << 20)
-                copies.push_back({in_pos + c, lo + c, std::min<uint64_t>(4u << 20, sp.hi - sp.lo - c)});
-            w->h_desc.resize(p.first_member + (p.b1 - p.b0));
-            bm::fill_desc(bl, p.b0, p.b1, sp.lo, in_pos, o, w->h_desc.data() + p.first_member);
-            for (size_t b = p.b0; b < p.b1; ++b) {
-                // a span is entered at its first record, a known record start
-                const uint64_t start = b != p.b0 ? o : data_start + (p.span && first_range ? p.span->entry : 0);
-                o += bl[b].isize;
-                w->h_segs.push_back(bw::Seg{uint32_t(start), uint32_t(o), k, uint32_t(n_list)});
-                n_list += bw::list_cap(uint32_t(o - start));
-            }
-            in_pos += sp.needed;
-            F.n_seg = uint32_t(p.b1 - p.b0);
-        }
-        F.first_seg = p.first_member;
-        F.data_end = F.limit = uint32_t(o);
-        if (w->index)  // the byte behind the carry is the first of member b0 (of the file's end, if none is left)
-            w->h_ix_files[k].delta = (long long)(p.b0 < df.blocks.size() ? df.blocks[p.b0].out : df.total) -
-                                     (long long)(data_start + carry);
-        if (p.span) {  // the span's offsets as offsets of the buffer; its last range ends at its limit
-            const Span &sp = *p.span;
-            const long long base = (long long)(data_start + carry) - (long long)sp.blocks[p.b0].out;
-            if (p.final) F.data_end = F.limit = uint32_t(base + (long long)sp.limit);
-            for (size_t c = 0; c < sp.chrs.size(); ++c) {
-                const size_t u = std::find(w->chr_ids.begin(), w->chr_ids.end(), sp.chrs[c].chromosome) -
-                                 w->chr_ids.begin();
-                SpanCheck &ck = w->h_checks[size_t(k) * n_chr + u];
-                ck.beg = base + (long long)sp.chrs[c].beg;
-                ck.end = base + (long long)sp.chrs[c].end;
-                ck.ref = int32_t(sp.chrs[c].chromosome);
-                ck.flags = kSpanOn | (c == 0 && first_range ? kSpanEntry : 0) |
-                           (c + 1 == sp.chrs.size() && p.final && sp.limit + 8 <= sp.bytes ? kSpanTail : 0);
-            }
-            any_span = true;
-        }
-        F.final = p.final;
-        F.has_prev = df.has_prev;
-        F.rec_base = df.rec_base;
-        F.prev_ref = df.prev_ref;
-        F.prev_pos = df.prev_pos;
-        F.stop_off = F.data_end;
-        F.bad = F.err = F.unsorted = ~0ull;
-        for (uint32_t u = 0; u < n_chr; ++u) {
-            w->h_runs[size_t(k) * n_chr + u].first = df.run_first[u];
-            w->h_runs[size_t(k) * n_chr + u].last = df.run_last[u];
-        }
-        out_pos = (o + 15) / 16 * 16;
-        if (out_pos > kMaxBatchBytes || n_list > UINT32_MAX)
-            return fail(SECEDO_E_LIMIT, df.path + ": a batch of 4 GiB or more of inflated BAM (a record that long, or "
-                                                  "SECEDO_BAM_BATCH_BYTES too large)");
-    }
-    const uint32_t n_members = uint32_t(w->h_desc.size());
-    // a file without a member in the batch (its header's members held all of it) walks its carry as one segment
-    for (uint32_t k = 0; k < n_files; ++k) {
-        WalkFile &F = w->h_files[k];
-        if (F.n_seg) continue;
-        const uint32_t len = uint32_t(pieces[k].df->carry.size());
-        F.first_seg = uint32_t(w->h_segs.size());
-        F.n_seg = 1;
-        w->h_segs.push_back(bw::Seg{F.data_end - len, F.data_end, k, uint32_t(n_list)});
-        n_list += bw::list_cap(len);
-    }
-    const uint32_t n_seg = uint32_t(w->h_segs.size());
-    const uint64_t buf_bytes = out_pos + kWalkWindow;
-    // ---- staging and upload
-    if (in_pos > w->h_in_cap) {
+    const BatchLayout &L = w->lay;
+    const uint64_t n_members = L.desc.size(), n_seg = L.segs.size();
+    if (L.in_bytes > w->h_in_cap) {
         if (w->h_in) SECEDO_TRY(hipHostFree(w->h_in));
         w->h_in = nullptr;
         w->h_in_cap = 0;
-        const size_t cap = std::max<size_t>(in_pos + in_pos / 2, 1u << 20);
+        const size_t cap = std::max<size_t>(L.in_bytes + L.in_bytes / 2, 1u << 20);
         SECEDO_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->h_in), cap, hipHostMallocDefault));
         w->h_in_cap = cap;
     }
-    parallel_for(threads, copies.size(),
-                 [&](uint64_t c) { std::memcpy(w->h_in + copies[c].dst, copies[c].src, copies[c].n); });
-    SECEDO_TRY(w->in.grow(in_pos, 0, s));
-    SECEDO_TRY(w->buf.grow(buf_bytes, pieces[0].first_range() ? 0 : pieces[0].df->dev_carry, s));
+    parallel_for(threads, L.copies.size(),
+                 [&](uint64_t c) { std::memcpy(w->h_in + L.copies[c].dst, L.copies[c].src, L.copies[c].n); });
+    SECEDO_TRY(w->in.grow(L.in_bytes, 0, s));
+    SECEDO_TRY(w->buf.grow(L.buf_bytes, pieces[0].first_range ? 0 : pieces[0].df->dev_carry, s));
     SECEDO_TRY(w->desc.grow(n_members, 0, s));
     SECEDO_TRY(w->status.grow(n_members, 0, s));
     SECEDO_TRY(w->segs.grow(n_seg, 0, s));
     SECEDO_TRY(w->walk.grow(n_seg, 0, s));
     SECEDO_TRY(w->join.grow(n_seg, 0, s));
-    SECEDO_TRY(w->seg_cnt.grow(uint64_t(n_seg) + 1, 0, s));
-    SECEDO_TRY(w->seg_base.grow(uint64_t(n_seg) + 1, 0, s));
-    SECEDO_TRY(w->lists.grow(n_list, 0, s));
-    SECEDO_TRY(w->rewalk.grow(n_list, 0, s));
-    SECEDO_TRY(w->files.grow(n_files, 0, s));
-    SECEDO_TRY(w->runs.grow(w->h_runs.size(), 0, s));
+    SECEDO_TRY(w->seg_cnt.grow(n_seg + 1, 0, s));
+    SECEDO_TRY(w->seg_base.grow(n_seg + 1, 0, s));
+    SECEDO_TRY(w->lists.grow(L.n_list, 0, s));
+    SECEDO_TRY(w->rewalk.grow(L.n_list, 0, s));
+    SECEDO_TRY(w->files.grow(L.files.size(), 0, s));
+    SECEDO_TRY(w->runs.grow(L.runs.size(), 0, s));
     SECEDO_TRY(w->totals.grow(2, 0, s));
-    if (any_span) {
-        SECEDO_TRY(w->checks.grow(w->h_checks.size(), 0, s));
-        SECEDO_TRY(hipMemcpyAsync(w->checks.p, w->h_checks.data(), w->h_checks.size() * sizeof(SpanCheck),
+    if (L.any_span) {
+        SECEDO_TRY(w->checks.grow(L.checks.size(), 0, s));
+        SECEDO_TRY(hipMemcpyAsync(w->checks.p, L.checks.data(), L.checks.size() * sizeof(SpanCheck),
                                   hipMemcpyHostToDevice, s));
     }
-    SECEDO_TRY(hipMemcpyAsync(w->in.p, w->h_in, in_pos, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(w->in.p, w->h_in, L.in_bytes, hipMemcpyHostToDevice, s));
     if (n_members)
-        SECEDO_TRY(hipMemcpyAsync(w->desc.p, w->h_desc.data(), n_members * sizeof(BgzfDesc), hipMemcpyHostToDevice, s));
-    SECEDO_TRY(hipMemcpyAsync(w->segs.p, w->h_segs.data(), n_seg * sizeof(bw::Seg), hipMemcpyHostToDevice, s));
-    SECEDO_TRY(hipMemcpyAsync(w->files.p, w->h_files.data(), n_files * sizeof(WalkFile), hipMemcpyHostToDevice, s));
-    if (!w->h_runs.empty())
-        SECEDO_TRY(hipMemcpyAsync(w->runs.p, w->h_runs.data(), w->h_runs.size() * sizeof(WalkRun),
-                                  hipMemcpyHostToDevice, s));
+        SECEDO_TRY(hipMemcpyAsync(w->desc.p, L.desc.data(), n_members * sizeof(BgzfDesc), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(w->segs.p, L.segs.data(), n_seg * sizeof(bw::Seg), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemcpyAsync(w->files.p, L.files.data(), L.files.size() * sizeof(WalkFile), hipMemcpyHostToDevice, s));
+    if (!L.runs.empty())
+        SECEDO_TRY(hipMemcpyAsync(w->runs.p, L.runs.data(), L.runs.size() * sizeof(WalkRun), hipMemcpyHostToDevice, s));
     SECEDO_TRY(hipStreamSynchronize(s));
-    if (t) t->upload_ms += ms_lap(t0);
-    // ---- inflate
-    SECEDO_TRY(bgzf_inflate(w->in.p, w->desc.p, n_members, w->buf.p, w->status.p, s));
-    SECEDO_TRY(hipStreamSynchronize(s));
-    if (t) {
-        t->inflate_ms += ms_lap(t0);
-        for (const BgzfDesc &d : w->h_desc) t->inflated_bytes += double(d.isize);
-    }
-    // ---- walk
-    const WalkBatch wb{w->buf.p,  buf_bytes / 16 * 16, w->segs.p, w->files.p,   n_seg,        n_files,
-                       w->lists.p, w->rewalk.p,        w->walk.p, w->join.p,    w->seg_cnt.p, w->seg_base.p};
+    return SECEDO_OK;
+}
+
+// Stage 3: every member of the batch inflated into the buffer.
+int inflate_batch(BamDevWork *w) {
+    SECEDO_TRY(bgzf_inflate(w->in.p, w->desc.p, uint32_t(w->lay.desc.size()), w->buf.p, w->status.p, w->s));
+    SECEDO_TRY(hipStreamSynchronize(w->s));
+    return SECEDO_OK;
+}
+
+// Stage 4: the walk up to the record count, then the record passes and their scans; the files, the runs, the span
+// checks and the totals come back, and the route's counters take what the batch did.
+int walk_and_scan(BamDevWork *w) {
+    hipStream_t s = w->s;
+    BatchLayout &L = w->lay;
+    const uint32_t n_members = uint32_t(L.desc.size()), n_seg = uint32_t(L.segs.size());
+    const uint32_t n_chr = uint32_t(w->chr_ids.size());
+    const WalkBatch wb = w->walk_batch();
     SECEDO_TRY(walk_prepare(wb, w->in.p, w->desc.p, w->status.p, n_members, s));
     SECEDO_TRY(walk_segments(wb, s));
     SECEDO_TRY(hipMemsetAsync(w->seg_cnt.p + n_seg, 0, 4, s));
     size_t tb = scan_bytes(uint64_t(n_seg) + 1);
     SECEDO_TRY(w->tmp.grow(tb, 0, s));
     SECEDO_TRY(exclusive_sum(w->tmp.p, tb, w->seg_cnt.p, w->seg_base.p, uint64_t(n_seg) + 1, s));
-    uint32_t n_rec = 0;
-    SECEDO_TRY(hipMemcpyAsync(&n_rec, w->seg_base.p + n_seg, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(&w->n_rec, w->seg_base.p + n_seg, 4, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
+    const uint64_t n_rec = w->n_rec;
     SECEDO_TRY(w->r_off.grow(n_rec, 0, s));
     SECEDO_TRY(w->r_file.grow(n_rec, 0, s));
     SECEDO_TRY(w->r_ref.grow(n_rec, 0, s));
     SECEDO_TRY(w->r_pos.grow(n_rec, 0, s));
-    SECEDO_TRY(w->sel.grow(uint64_t(n_rec) + 1, 0, s));
-    SECEDO_TRY(w->sel_scan.grow(uint64_t(n_rec) + 1, 0, s));
-    SECEDO_TRY(w->size.grow(uint64_t(n_rec) + 1, 0, s));
-    SECEDO_TRY(w->size_scan.grow(uint64_t(n_rec) + 1, 0, s));
-    const WalkRecords wr{n_rec,    w->r_off.p, w->r_file.p,   w->r_ref.p,
-                         w->r_pos.p, w->sel.p,   w->size.p,     w->sel_scan.p, w->size_scan.p};
+    SECEDO_TRY(w->sel.grow(n_rec + 1, 0, s));
+    SECEDO_TRY(w->sel_scan.grow(n_rec + 1, 0, s));
+    SECEDO_TRY(w->size.grow(n_rec + 1, 0, s));
+    SECEDO_TRY(w->size_scan.grow(n_rec + 1, 0, s));
+    const WalkRecords wr = w->walk_records();
     SECEDO_TRY(walk_records(wb, wr, w->chr.p, n_chr, w->runs.p, w->scan ? w->per_ref.p : nullptr, w->n_ref, s));
-    if (any_span) {
+    if (L.any_span) {
         SECEDO_TRY(walk_span_check(wb, wr, n_chr, w->checks.p, s));
-        SECEDO_TRY(hipMemcpyAsync(w->h_checks.data(), w->checks.p, w->h_checks.size() * sizeof(SpanCheck),
+        SECEDO_TRY(hipMemcpyAsync(L.checks.data(), w->checks.p, L.checks.size() * sizeof(SpanCheck),
                                   hipMemcpyDeviceToHost, s));
     }
-    tb = scan_bytes(uint64_t(n_rec) + 1);
+    tb = scan_bytes(n_rec + 1);
     SECEDO_TRY(w->tmp.grow(tb, 0, s));
-    SECEDO_TRY(exclusive_sum(w->tmp.p, tb, w->sel.p, w->sel_scan.p, uint64_t(n_rec) + 1, s));
-    SECEDO_TRY(exclusive_sum64(w->tmp.p, tb, w->size.p, w->size_scan.p, uint64_t(n_rec) + 1, s));
+    SECEDO_TRY(exclusive_sum(w->tmp.p, tb, w->sel.p, w->sel_scan.p, n_rec + 1, s));
+    SECEDO_TRY(exclusive_sum64(w->tmp.p, tb, w->size.p, w->size_scan.p, n_rec + 1, s));
     SECEDO_TRY(walk_runs(wb, wr, n_chr, w->runs.p, w->totals.p, s));
     uint64_t totals[2] = {0, 0};
-    SECEDO_TRY(hipMemcpyAsync(w->h_files.data(), w->files.p, n_files * sizeof(WalkFile), hipMemcpyDeviceToHost, s));
-    if (!w->h_runs.empty())
-        SECEDO_TRY(hipMemcpyAsync(w->h_runs.data(), w->runs.p, w->h_runs.size() * sizeof(WalkRun),
-                                  hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(L.files.data(), w->files.p, L.files.size() * sizeof(WalkFile), hipMemcpyDeviceToHost, s));
+    if (!L.runs.empty())
+        SECEDO_TRY(hipMemcpyAsync(L.runs.data(), w->runs.p, L.runs.size() * sizeof(WalkRun), hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipMemcpyAsync(totals, w->totals.p, 16, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
+    w->n_sel = totals[0];
+    w->sel_bytes = totals[1];
     route().device_blocks += n_members;
     route().segments += n_seg;
-    route().uploaded_bytes += in_pos;
+    route().uploaded_bytes += L.in_bytes;
     route().batches += 1;
-    for (uint32_t k = 0; k < n_files; ++k) {
-        route().device_records += w->h_files[k].n_rec;
-        route().rewalked_segments += w->h_files[k].rewalked;
+    for (const WalkFile &F : L.files) {
+        route().device_records += F.n_rec;
+        route().rewalked_segments += F.rewalked;
     }
-    // per file in order: the RefID at a span's entry, then the walk's own errors, then what the index says of the span
-    for (uint32_t k = 0; k < n_files; ++k) {
+    return SECEDO_OK;
+}
+
+// Stage 5: the verdicts, per file in order: the RefID at a span's entry, then the walk's own errors, then what the
+// index says of the span (its counts summed over its ranges, its tail on the last).
+int verdicts(BamDevWork *w, const std::vector<Piece> &pieces) {
+    const size_t n_chr = w->chr_ids.size();
+    for (size_t k = 0; k < pieces.size(); ++k) {
         const Piece &p = pieces[k];
+        const SpanCheck *checks = w->lay.checks.data() + k * n_chr;
         if (p.span) {
             index_info().members += p.b1 - p.b0;
-            index_info().spans += p.first_range() ? 1 : 0;
-            const Span &sp = *p.span;
-            const size_t u0 = std::find(w->chr_ids.begin(), w->chr_ids.end(), sp.chrs[0].chromosome) -
-                              w->chr_ids.begin();
-            if (w->h_checks[size_t(k) * n_chr + u0].entry_bad) return check_span_chr(p.df->path, sp.chrs[0], false, 0);
+            index_info().spans += p.first_range ? 1 : 0;
+            const SpanChr &c0 = p.span->chrs[0];
+            if (checks[slot_of(w->chr_ids, c0.chromosome)].entry_bad) return check_span_chr(p.df->path, c0, false, 0);
         }
-        if (const int rc = file_error(*w, p, w->h_files[k])) {
-            w->failed = k;
+        if (const int rc = file_error(*w, p, w->lay.first_member[k], w->lay.files[k])) {
+            w->failed = uint32_t(k);
             return rc;
         }
         if (!p.span) continue;
         DevFile &df = *p.df;
-        for (uint32_t u = 0; u < n_chr; ++u) {
-            const SpanCheck &ck = w->h_checks[size_t(k) * n_chr + u];
-            if (!(ck.flags & kSpanOn)) continue;
-            df.sp_count[u] += ck.count;
-            if (ck.start) df.sp_start[u] = ck.start == 1;
+        for (size_t u = 0; u < n_chr; ++u) {
+            if (!(checks[u].flags & kSpanOn)) continue;
+            df.sp_count[u] += checks[u].count;
+            if (checks[u].start) df.sp_start[u] = checks[u].start == 1;
         }
         if (!p.final) continue;
         for (const SpanChr &sc : p.span->chrs) {
-            const size_t u = std::find(w->chr_ids.begin(), w->chr_ids.end(), sc.chromosome) - w->chr_ids.begin();
+            const size_t u = slot_of(w->chr_ids, sc.chromosome);
             SECEDO_CALL(check_span_chr(df.path, sc, df.sp_start[u] != 0, df.sp_count[u]));
-            if (w->h_checks[size_t(k) * n_chr + u].tail_bad) return span_tail_mismatch(df.path, sc);
+            if (checks[u].tail_bad) return span_tail_mismatch(df.path, sc);
         }
     }
-    // ---- the taken records
-    const uint64_t n_sel = totals[0], sel_bytes = totals[1];
-    // what came back must be consistent before it is used as an index
+    return SECEDO_OK;
+}
+
+// Stage 6: what came back must be consistent before it is used as an index.
+int check_results(const BamDevWork &w, const std::vector<Piece> &pieces) {
     uint64_t sum_rec = 0;
-    bool sane = n_sel <= n_rec && sel_bytes <= out_pos;
-    for (uint32_t k = 0; k < n_files; ++k) {
-        const WalkFile &F = w->h_files[k];
+    bool sane = w.n_sel <= w.n_rec && w.sel_bytes <= w.lay.out_bytes;
+    for (const WalkFile &F : w.lay.files) {
         sum_rec += F.n_rec;
         sane = sane && F.stop_off <= F.data_end;
     }
-    for (const WalkRun &run : w->h_runs)
-        sane = sane && run.j0 <= run.j1 && run.j1 <= n_sel && run.b0 <= run.b1 && run.b1 <= sel_bytes;
-    if (!sane || sum_rec != n_rec)
+    for (const WalkRun &run : w.lay.runs)
+        sane = sane && run.j0 <= run.j1 && run.j1 <= w.n_sel && run.b0 <= run.b1 && run.b1 <= w.sel_bytes;
+    if (!sane || sum_rec != w.n_rec)
         return fail(SECEDO_E_STATE, pieces[0].df->path + ": the device walk returned inconsistent results");
-    if (w->index) SECEDO_CALL(index_batch(w, pieces, wb, wr));
-    if (n_sel) {
-        SECEDO_TRY(w->out.grow(sel_bytes, 0, s));
-        SECEDO_TRY(w->sel_off.grow(n_sel, 0, s));
-        SECEDO_TRY(w->sel_pos.grow(n_sel, 0, s));
-        SECEDO_TRY(w->sel_idx.grow(n_sel, 0, s));
-        SECEDO_TRY(walk_gather(wb, wr, w->out.p, w->sel_off.p, w->sel_pos.p, w->sel_idx.p, s));
-        w->h_out.resize(sel_bytes);
-        w->h_sel_off.resize(n_sel);
-        w->h_sel_pos.resize(n_sel);
-        w->h_sel_idx.resize(n_sel);
-        SECEDO_TRY(hipMemcpyAsync(w->h_out.data(), w->out.p, sel_bytes, hipMemcpyDeviceToHost, s));
-        SECEDO_TRY(hipMemcpyAsync(w->h_sel_off.data(), w->sel_off.p, n_sel * 8, hipMemcpyDeviceToHost, s));
-        SECEDO_TRY(hipMemcpyAsync(w->h_sel_pos.data(), w->sel_pos.p, n_sel * 4, hipMemcpyDeviceToHost, s));
-        SECEDO_TRY(hipMemcpyAsync(w->h_sel_idx.data(), w->sel_idx.p, n_sel * 8, hipMemcpyDeviceToHost, s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        route().downloaded_record_bytes += sel_bytes;
-    }
-    // ---- per file: its runs appended as FileSink appends them, and the state the next range starts from
-    for (uint32_t k = 0; k < n_files; ++k) {
+    return SECEDO_OK;
+}
+
+// Stage 7: the taken records gathered and brought back, with their offsets, Positions and file indexes.
+int fetch_taken(BamDevWork *w) {
+    hipStream_t s = w->s;
+    const uint64_t n_sel = w->n_sel, sel_bytes = w->sel_bytes;
+    if (!n_sel) return SECEDO_OK;
+    SECEDO_TRY(w->out.grow(sel_bytes, 0, s));
+    SECEDO_TRY(w->sel_off.grow(n_sel, 0, s));
+    SECEDO_TRY(w->sel_pos.grow(n_sel, 0, s));
+    SECEDO_TRY(w->sel_idx.grow(n_sel, 0, s));
+    SECEDO_TRY(walk_gather(w->walk_batch(), w->walk_records(), w->out.p, w->sel_off.p, w->sel_pos.p, w->sel_idx.p, s));
+    w->h_out.resize(sel_bytes);
+    w->h_sel_off.resize(n_sel);
+    w->h_sel_pos.resize(n_sel);
+    w->h_sel_idx.resize(n_sel);
+    SECEDO_TRY(hipMemcpyAsync(w->h_out.data(), w->out.p, sel_bytes, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(w->h_sel_off.data(), w->sel_off.p, n_sel * 8, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(w->h_sel_pos.data(), w->sel_pos.p, n_sel * 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipMemcpyAsync(w->h_sel_idx.data(), w->sel_idx.p, n_sel * 8, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    route().downloaded_record_bytes += sel_bytes;
+    return SECEDO_OK;
+}
+
+// Stage 8, per file: its runs appended as FileSink appends them, the state the next range starts from, and the cut
+// record to the front of the buffer (only a file that goes alone has a next range).
+int append_runs(BamDevWork *w, const std::vector<Piece> &pieces, Inputs *in, Runs *runs) {
+    hipStream_t s = w->s;
+    const size_t n_chr = w->chr_ids.size();
+    for (size_t k = 0; k < pieces.size(); ++k) {
         DevFile &df = *pieces[k].df;
-        const WalkFile &F = w->h_files[k];
-        for (uint32_t u = 0; u < n_chr; ++u) {
-            const WalkRun &run = w->h_runs[size_t(k) * n_chr + u];
+        const WalkFile &F = w->lay.files[k];
+        for (size_t u = 0; u < n_chr; ++u) {
+            const WalkRun &run = w->lay.runs[k * n_chr + u];
             if (run.last != bw::kNoRun) df.run_first[u] = df.run_last[u] = 0;  // done
             else if (run.first != bw::kNoRun) df.run_first[u] = 0;             // open
             if (run.j1 == run.j0) continue;
@@ -582,12 +537,34 @@ int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Input
         df.rec_base += F.n_rec;
         if (F.unsorted != ~0ull) df.sorted = false;
         df.dev_carry = F.data_end - F.stop_off;
-        if (!pieces[k].final && df.dev_carry) {  // the cut record to the front of the buffer (one file goes alone)
+        if (!pieces[k].final && df.dev_carry) {
             SECEDO_TRY(w->carry.grow(df.dev_carry, 0, s));
             SECEDO_TRY(hipMemcpyAsync(w->carry.p, w->buf.p + F.stop_off, df.dev_carry, hipMemcpyDeviceToDevice, s));
             SECEDO_TRY(hipMemcpyAsync(w->buf.p, w->carry.p, df.dev_carry, hipMemcpyDeviceToDevice, s));
         }
     }
+    return SECEDO_OK;
+}
+
+// One batch through the device: inflate, walk, the taken records back into runs / in (both may be null: scan).
+int run_batch(BamDevWork *w, std::vector<Piece> &pieces, uint32_t threads, Inputs *in, Runs *runs,
+              secedo_bam_times *t) {
+    Clock::time_point t0 = Clock::now();
+    w->failed = UINT32_MAX;
+    SECEDO_CALL(lay_out(w, pieces));
+    SECEDO_CALL(upload(w, pieces, threads));
+    if (t) t->upload_ms += ms_lap(t0);
+    SECEDO_CALL(inflate_batch(w));
+    if (t) {
+        t->inflate_ms += ms_lap(t0);
+        for (const BgzfDesc &d : w->lay.desc) t->inflated_bytes += double(d.isize);
+    }
+    SECEDO_CALL(walk_and_scan(w));
+    SECEDO_CALL(verdicts(w, pieces));
+    SECEDO_CALL(check_results(*w, pieces));
+    if (w->index) SECEDO_CALL(index_batch(w, pieces));
+    SECEDO_CALL(fetch_taken(w));
+    SECEDO_CALL(append_runs(w, pieces, in, runs));
     if (t) t->walk_ms += ms_lap(t0);
     return SECEDO_OK;
 }
@@ -597,11 +574,9 @@ int run_ranges(BamDevWork *w, DevFile *df, const Span *span, uint32_t threads, u
                secedo_bam_times *t) {
     const std::vector<Block> &bl = span ? span->blocks : df->blocks;
     for (size_t b0 = span ? 0 : df->hb;;) {
-        size_t b1 = b0;
-        uint64_t bytes = 0;
-        while (b1 < bl.size() && (b1 == b0 || bytes + bl[b1].isize <= batch)) bytes += bl[b1++].isize;
-        if (!span && b1 < bl.size() && bl[b1].out == df->total) b1 = bl.size();  // only empty members follow
-        std::vector<Piece> one{Piece{df, b0, b1, b1 == bl.size(), 0, span}};
+        // a file's tail of only empty members goes with its last range; a span has none
+        const size_t b1 = bm::next_range(bl, b0, batch, span ? bm::kNoFold : df->total);
+        std::vector<Piece> one{piece_of(df, b0, b1, b1 == bl.size(), span)};
         SECEDO_CALL(run_batch(w, one, threads, in, runs, t));
         if (b1 == bl.size()) return SECEDO_OK;
         b0 = b1;
@@ -630,12 +605,9 @@ int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, Bam
         const Clock::time_point t0 = Clock::now();
         if (plans && (*plans)[f].indexed) {  // its header is read; its spans follow below
             std::unique_ptr<DevFile> df(new DevFile());
-            df->f = f;
-            df->path = in->paths[f];
+            df->start(f, in->paths[f], n_chr);
             df->plan = &(*plans)[f];
             df->h = df->plan->h;
-            df->run_first.assign(n_chr, bw::kNoRun);
-            df->run_last.assign(n_chr, bw::kNoRun);
             indexed.push_back(std::move(df));
             continue;
         }
@@ -655,7 +627,7 @@ int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, Bam
             continue;
         }
         if (!pieces.empty() && bytes + n > batch) SECEDO_CALL(flush());
-        pieces.push_back(Piece{df.get(), df->hb, df->blocks.size(), true});
+        pieces.push_back(piece_of(df.get(), df->hb, df->blocks.size(), true));
         open.push_back(std::move(df));
         bytes += n;
     }
@@ -675,7 +647,7 @@ int load_bams_device(size_t f0, size_t f1, uint32_t threads, uint64_t batch, Bam
                 continue;
             }
             if (!pieces.empty() && bytes + sp->bytes > batch) SECEDO_CALL(flush());
-            pieces.push_back(Piece{df.get(), 0, sp->blocks.size(), true, 0, sp});
+            pieces.push_back(piece_of(df.get(), 0, sp->blocks.size(), true, sp));
             bytes += sp->bytes;
         }
         SECEDO_CALL(flush());
@@ -824,7 +796,7 @@ int index_build(const char *const *bam_files, uint32_t n_files, const char *cons
             continue;
         }
         if (!pieces.empty() && bytes + n > batch) SECEDO_CALL(flush());
-        pieces.push_back(Piece{df.get(), df->hb, df->blocks.size(), true});
+        pieces.push_back(piece_of(df.get(), df->hb, df->blocks.size(), true));
         open.push_back(std::move(df));
         bytes += n;
     }

@@ -2,6 +2,7 @@
 // into one ChrInput per requested chromosome, bam_pileup.cpp turns those into the pileup. Internal, nothing exported.
 #pragma once
 
+#include "bam_batch.hpp"
 #include "bam_kernels.hpp"
 #include "bgzf_members.hpp"
 #include "host_util.hpp"
@@ -132,10 +133,8 @@ struct Mapped {
     }
 };
 
-// A BGZF block is a member of bgzf_members.hpp, which lists, describes and inflates them; these two put the file's
-// name in front of its reasons.
-namespace bm = secedo::bgzf_members;
-using Block = bm::Member;
+// A BGZF block is a member of bgzf_members.hpp (bm::Member; Block and bm come with bam_batch.hpp), which lists,
+// describes and inflates them; these two put the file's name in front of its reasons.
 
 // "<path>: <bm::block_where*()>: <why>": the error of every route for a block that does not inflate
 inline int bad_block(const std::string &path, const std::string &where, const std::string &why) {
@@ -160,22 +159,7 @@ int parse_header(const std::string &path, const uint8_t *d, uint64_t n, bool fin
 
 // ---- reading through the .bai index (secedo_bam_set_index, SECEDO_BAM_INDEX; bam_index.hpp parses the file)
 
-// one requested chromosome inside a span; offsets count the span's inflated bytes from its first member's first byte
-struct SpanChr {
-    uint32_t chromosome;
-    uint64_t beg, end;  // its records start at beg and end in front of end
-    uint64_t count;     // the pseudo-bin's record count, or bamindex::kNoCount
-};
-
-// A run of members that holds the records of one or more requested chromosomes, entered at a known record start.
-struct Span {
-    std::vector<Block> blocks;  // its members in file order, `out` from 0
-    uint64_t entry = 0;         // the first record starts here (the start's uoffset)
-    uint64_t limit = 0;         // no record of the span starts at or past this
-    uint64_t bytes = 0;         // inflated bytes of its members
-    uint64_t beg_v = 0;         // the virtual offset of the entry (messages)
-    std::vector<SpanChr> chrs;  // in file order; chrs[0].beg == entry, chrs.back().end == limit
-};
+// SpanChr and Span, a run of members entered at a known record start: bam_batch.hpp
 
 // What the index says of one BAM for the requested chromosomes.
 struct IndexPlan {
@@ -194,6 +178,15 @@ int index_mode(int *mode);
 int plan_index(const std::string &path, const std::vector<uint32_t> &chromosomes, int mode, IndexPlan *plan);
 // "<path>: index does not match the file (<why>); re-index it or use --index off"
 int index_mismatch(const std::string &path, const std::string &why);
+// "<where the record is>" + defect_tail(code): bam_walk.hpp's words of a record defect, the op's number behind them
+inline std::string defect_tail(uint32_t code) {
+    return bamwalk::defect_words(code) + (bamwalk::is_cigar_op(code) ? std::to_string(code & 15) : std::string());
+}
+// Under a span a record chain that breaks (bamwalk::kErrTruncated, kErrBlockSize at indexed record idx) means that
+// the index does not fit the file: the same sentence from both routes.
+inline int chain_break(const std::string &path, uint64_t idx, uint32_t code) {
+    return index_mismatch(path, "the record chain breaks: indexed record " + std::to_string(idx) + defect_tail(code));
+}
 // The checks made after a span was read, the same words from both routes. got_count: records that start in
 // [c.beg, c.end); start_ok: one starts at c.beg with the chromosome's RefID.
 int check_span_chr(const std::string &path, const SpanChr &c, bool start_ok, uint64_t got_count);

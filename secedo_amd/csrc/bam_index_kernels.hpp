@@ -18,13 +18,7 @@ constexpr uint32_t kIndexErrRef = 1;   // a RefID at or past the header's n_ref
 constexpr uint32_t kIndexErrEnd = 2;   // the record ends past 2^29
 constexpr uint32_t kIndexErrSize = 3;  // the CIGAR does not lie inside the record (the walk reports it first)
 
-// One file of the batch, entry k of WalkBatch::files too.
-struct IndexFile {
-    long long delta;         // a buffer offset + delta = the file-linear inflated offset
-    uint64_t seg_base;       // the batch-wide number of its RefID 0; a file takes n_ref + 1 numbers
-    uint32_t n_ref, pad;
-    unsigned long long err;  // in: ~0
-};
+// IndexFile, one file of the batch: bam_batch.hpp, which fills it
 
 // the first record of a run of consecutive records of one file with the same (RefID, bin, flag 0x4)
 struct IndexHead {

@@ -103,6 +103,7 @@ namespace {
 
 using namespace secedo::bam;
 using namespace secedo::bam_host;
+namespace bamwalk = secedo::bamwalk;
 
 struct InflateJob {
     const std::string *path;
@@ -199,20 +200,17 @@ int walk_range(const std::string &path, const uint8_t *d, uint64_t n, bool final
         *used = o;
         if (o >= n) return SECEDO_OK;
         const std::string where = record_where(path, 0, 0, st->idx, Stage::kLoad, st->span);
-        const auto broken = [&](const char *what) {
-            if (st->span) return index_mismatch(path, "the record chain breaks: indexed record " +
-                                                          std::to_string(st->idx) + what);
-            return fail(SECEDO_E_INVALID_ARG, where + what);
-        };
-        if (n - o < 4 + 32) return final ? broken(" is truncated") : SECEDO_OK;
+        const auto defect = [&](uint32_t code) { return fail(SECEDO_E_INVALID_ARG, where + defect_tail(code)); };
+        const auto broken = [&](uint32_t code) { return st->span ? chain_break(path, st->idx, code) : defect(code); };
+        if (n - o < 4 + 32) return final ? broken(bamwalk::kErrTruncated) : SECEDO_OK;
         const uint32_t bs = rd32(d + o);
         const uint8_t *c = d + o + 4;
-        if (bs < 32) return broken(" has a bad block_size");
-        if (bs > n - o - 4) return final ? broken(" has a bad block_size") : SECEDO_OK;
-        if (rec_aux_off(c) > bs) return fail(SECEDO_E_INVALID_ARG, where + " is longer than its block_size");
+        if (bs < 32) return broken(bamwalk::kErrBlockSize);
+        if (bs > n - o - 4) return final ? broken(bamwalk::kErrBlockSize) : SECEDO_OK;
+        if (rec_aux_off(c) > bs) return defect(bamwalk::kErrLonger);
         const int32_t ref = int32_t(rd32(c)), pos = int32_t(rd32(c + 4));
         if (!st->order.check(ref, pos)) {
-            if (st->require_sorted) return fail(SECEDO_E_INVALID_ARG, where + ": input is not coordinate-sorted");
+            if (st->require_sorted) return defect(bamwalk::kErrUnsorted);
             st->sorted = false;
         }
         SECEDO_CALL(on_record(st->idx, d + o, ref, pos));
@@ -227,11 +225,11 @@ int check_cigar(const uint8_t *rec, const std::string &where) {
     uint64_t query = 0;
     for (uint32_t k = 0; k < n_cigar; ++k) {
         const uint32_t v = rd32(c + 32 + l_name + 4 * k), t = v & 15;
-        if (t > 8) return fail(SECEDO_E_INVALID_ARG, where + ": invalid CIGAR op code " + std::to_string(t));
+        if (t > 8) return fail(SECEDO_E_INVALID_ARG, where + defect_tail(bamwalk::kErrCigarOp | t));
         if (t == 0 || t == 1 || t == 4 || t == 7 || t == 8) query += v >> 4;
     }
     if (l_seq > 0 && n_cigar > 0 && query != l_seq)
-        return fail(SECEDO_E_INVALID_ARG, where + ": CIGAR and SEQ lengths differ");
+        return fail(SECEDO_E_INVALID_ARG, where + defect_tail(bamwalk::kErrCigarSeq));
     return SECEDO_OK;
 }
 
@@ -254,7 +252,7 @@ struct FileSink {
                 continue;
             }
             const std::string where = record_where(in.paths[f], f, in.line0[f], idx, Stage::kLoad, in.indexed[f] != 0);
-            if (pos < 0) return fail(SECEDO_E_INVALID_ARG, where + " has a negative position");
+            if (pos < 0) return fail(SECEDO_E_INVALID_ARG, where + defect_tail(bamwalk::kErrNegative));
             SECEDO_CALL(check_cigar(rec, where));
             started[c] = 1;
             std::vector<uint8_t> &run = *runs[c];
@@ -282,9 +280,8 @@ int load_file_ranges(size_t f, uint32_t threads, uint64_t batch, Inputs *in, Run
     uint64_t carry = 0;
     size_t b0 = 0;
     do {
-        size_t b1 = b0;
-        uint64_t bytes = 0;
-        while (b1 < blocks.size() && (b1 == b0 || bytes + blocks[b1].isize <= batch)) bytes += blocks[b1++].isize;
+        const size_t b1 = bm::next_range(blocks, b0, batch);
+        const uint64_t bytes = bm::range_bytes(blocks, b0, b1);
         Clock::time_point t0 = Clock::now();
         buf.resize(carry + bytes);
         jobs.clear();
@@ -329,9 +326,8 @@ int load_file_spans(size_t f, const IndexPlan &plan, uint32_t threads, uint64_t 
         uint64_t carry = 0;
         buf.clear();
         for (size_t b0 = 0; b0 < blocks.size();) {
-            size_t b1 = b0;
-            uint64_t bytes = 0;
-            while (b1 < blocks.size() && (b1 == b0 || bytes + blocks[b1].isize <= batch)) bytes += blocks[b1++].isize;
+            const size_t b1 = bm::next_range(blocks, b0, batch);
+            const uint64_t bytes = bm::range_bytes(blocks, b0, b1);
             const bool final = b1 == blocks.size();
             Clock::time_point t0 = Clock::now();
             buf.resize(carry + bytes);
@@ -671,7 +667,7 @@ int collect_sam_range(const SamWork &w, const SamRange &r, const std::vector<uin
         const uint64_t idx = r.line_base + k;
         if (!order->check(ref, pos))
             return fail(SECEDO_E_INVALID_ARG,
-                        record_where(path, sink->f, line0, idx) + ": input is not coordinate-sorted");
+                        record_where(path, sink->f, line0, idx) + defect_tail(bamwalk::kErrUnsorted));
         if (ref >= 0 && size_t(ref) < sel.size() && sel[ref]) {
             const uint8_t *rec = w.h_out.data() + o;
             SECEDO_CALL((*sink)(idx, rec, ref, pos));
@@ -813,10 +809,8 @@ int load_samgz_file(size_t f, uint64_t batch, SamWork *w, Inputs *in, Runs *runs
     SortCheck order;
     SamRange r;
     for (size_t b0 = hb;;) {
-        size_t b1 = b0;
-        uint64_t bytes = 0;
-        while (b1 < blocks.size() && (b1 == b0 || bytes + blocks[b1].isize <= batch)) bytes += blocks[b1++].isize;
-        if (b1 < blocks.size() && blocks[b1].out == total) b1 = blocks.size();  // only empty blocks follow
+        const size_t b1 = bm::next_range(blocks, b0, batch, total);  // a tail of only empty blocks goes with it
+        const uint64_t bytes = bm::range_bytes(blocks, b0, b1);
         const bool ends = b1 == blocks.size();
         const uint64_t len = carry + bytes;
         if (len >= (1ull << 32) - 64)
@@ -1350,9 +1344,7 @@ extern "C" int secedo_bgzf_inflate(const char *path, uint64_t *bytes) {
     GzWork g;
     const uint64_t batch = batch_bytes();
     for (size_t b0 = 0; b0 < blocks.size();) {
-        size_t b1 = b0;
-        uint64_t n = 0;
-        while (b1 < blocks.size() && (b1 == b0 || n + blocks[b1].isize <= batch)) n += blocks[b1++].isize;
+        const size_t b1 = bm::next_range(blocks, b0, batch);
         SECEDO_CALL(inflate_range_device(path, m, blocks, b0, b1, &g, res->data.p, blocks[b0].out, sg.s, nullptr));
         b0 = b1;
     }

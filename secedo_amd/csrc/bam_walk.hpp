@@ -45,6 +45,21 @@ enum Code : uint32_t {
     kErrCigarSeq = 0x20,
 };
 
+// The words of a record defect, the same from the host walk and from the device walk: "<where the record is>" +
+// defect_words(code), and for kErrCigarOp | op (is_cigar_op) the op's number, code & 15, behind them.
+constexpr bool is_cigar_op(uint32_t code) { return (code & 0xF0) == kErrCigarOp; }
+inline const char *defect_words(uint32_t code) {
+    switch (code) {
+        case kErrTruncated: return " is truncated";
+        case kErrBlockSize: return " has a bad block_size";
+        case kErrLonger: return " is longer than its block_size";
+        case kErrUnsorted: return ": input is not coordinate-sorted";
+        case kErrNegative: return " has a negative position";
+        case kErrCigarSeq: return ": CIGAR and SEQ lengths differ";
+        default: return ": invalid CIGAR op code ";
+    }
+}
+
 // records a segment of `bytes` bytes can start
 SECEDO_HD inline uint32_t list_cap(uint32_t bytes) { return (bytes + kMinRecord - 1) / kMinRecord; }
 

@@ -2,6 +2,7 @@
 // bgzf_kernels.hip inflated in HBM. See bam_walk_kernels.hip for the passes and bam_walk.hpp for the decisions.
 #pragma once
 
+#include "bam_batch.hpp"
 #include "bam_walk.hpp"
 #include "bgzf_kernels.hpp"
 
@@ -13,57 +14,7 @@
 namespace secedo {
 namespace bam {
 
-// bytes the walk may read past the last inflated byte of the buffer (its LDS window is staged in whole vectors)
-constexpr uint32_t kWalkWindow = 4096;
-
-// One file of a batch (or one range of a file): set by the host, updated by the passes, read back whole.
-struct WalkFile {
-    // in
-    uint32_t first_seg, n_seg;  // its segments, one per BGZF member of the batch, in file order
-    uint32_t data_end;          // the end of its bytes in the buffer (they start at its first segment's start)
-    uint32_t final;             // the bytes end the file
-    uint64_t carry_src;         // carry_len bytes at d_in + carry_src go in front of its first member's bytes
-    uint32_t carry_len, has_prev;
-    uint64_t rec_base;          // records of the file before this range
-    int32_t prev_ref, prev_pos; // of the last of them (has_prev)
-    // out
-    uint32_t limit;             // in: data_end; the start of the first member that did not inflate, if lower
-    uint32_t stop_off;          // where the chain stopped: the bytes from here on are carried into the next range
-    unsigned long long bad;     // in: ~0; min of (member of the batch << 8 | its bgzf status) over bad members
-    unsigned long long err;     // in: ~0; min of (record of the file << 8 | bamwalk::Code)
-    unsigned long long unsorted;  // in: ~0; the lowest record that sorts before its predecessor
-    uint64_t n_rec;             // records in these bytes
-    uint32_t first_rec;         // the batch's index of the first of them
-    uint32_t rewalked;          // segments joined by a walk of their own
-    int32_t last_ref, last_pos; // of the last record (n_rec > 0)
-};
-
-// the first run of requested chromosome u in file f, entry f * n_chr + u
-struct WalkRun {
-    uint32_t first, last;  // in and out: bam_walk.hpp's started / done rule (kNoRun, kNoRun for a fresh file)
-    uint32_t j0, j1;       // out: its records among the batch's selected ones
-    uint64_t b0, b1;       // out: its bytes among the gathered ones
-};
-
-// One requested chromosome u of file f of a batch whose bytes are a span of an indexed file (or a range of one),
-// entry f * n_chr + u: what the index says of it, as offsets of the batch's buffer, against the records the walk found.
-// The offsets are signed: a chromosome may start or end in another range of the span.
-constexpr uint32_t kSpanOn = 1;     // the chromosome lies in this span
-constexpr uint32_t kSpanEntry = 2;  // beg is where the walk enters the span: the RefID there is read before the walk's
-                                    // results are believed (when those 8 bytes lie below the file's limit)
-constexpr uint32_t kSpanTail = 4;   // end is the span's limit and the 8 bytes at it are inflated: the RefID there
-struct SpanCheck {
-    // in
-    long long beg, end;
-    uint32_t flags;
-    int32_t ref;
-    // out
-    uint32_t start;      // 0: beg is no record start of this range's; 1: the record there has RefID ref; 2: none has
-    uint32_t entry_bad;  // kSpanEntry: the RefID at beg is not ref
-    uint32_t tail_bad;   // kSpanTail: the RefID at end is ref
-    uint32_t reserved;
-    uint64_t count;      // records of this range that start in [beg, end)
-};
+// kWalkWindow, WalkFile, WalkRun, SpanCheck and the kSpan* flags: bam_batch.hpp, which fills them
 
 // the arrays of one batch
 struct WalkBatch {

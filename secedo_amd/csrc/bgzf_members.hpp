@@ -138,6 +138,24 @@ inline void fill_desc(const std::vector<Member> &m, size_t b0, size_t b1, uint64
                                 m[b].isize, m[b].crc, 0};
 }
 
+// The one range cut of every reader that takes a file in ranges: members [b0, b1) of about `batch` inflated bytes, at
+// least one; b1 is returned. fold_empty_tail_total: the list's inflated size, for a reader whose last range also takes
+// a tail of only empty members (the EOF member) in place of a range of nothing; kNoFold for one that gives them a
+// range of their own. The two kinds are kept apart: which one a reader is shows in its batch and range counts.
+constexpr uint64_t kNoFold = UINT64_MAX;
+inline size_t next_range(const std::vector<Member> &m, size_t b0, uint64_t batch,
+                         uint64_t fold_empty_tail_total = kNoFold) {
+    size_t b1 = b0;
+    uint64_t bytes = 0;
+    while (b1 < m.size() && (b1 == b0 || bytes + m[b1].isize <= batch)) bytes += m[b1++].isize;
+    if (b1 < m.size() && m[b1].out == fold_empty_tail_total) b1 = m.size();
+    return b1;
+}
+// the inflated bytes of members [b0, b1) of a list whose `out` is the running sum of `isize`
+inline uint64_t range_bytes(const std::vector<Member> &m, size_t b0, size_t b1) {
+    return b0 < b1 ? m[b1 - 1].out + m[b1 - 1].isize - m[b0].out : 0;
+}
+
 // ---- the words for a member that does not inflate: "<path>: " + block_where*() + ": " + status_text()
 
 inline const char *status_text(uint32_t status) {

@@ -364,6 +364,30 @@ def test_102_files_go_through_in_batches(tmp_path, monkeypatch):
         assert stats["device_records"] == 204 and stats["host_blocks"] == 102
 
 
+def test_a_file_without_a_member_left_shares_a_batch(tmp_path):
+    """The middle file is one member that holds the header and every record, with no EOF member behind it: nothing of
+    it is left to inflate on the device, and its carry is walked as one segment between two files that have members."""
+    refs, paths, n_rec = [("1", 100000), ("2", 100000)], [], 0
+    for f, chunk in enumerate((1000, None, 700)):
+        recs = [bw.Rec("r%d_%d" % (f, k), k // 60, 100 + 7 * (k % 60) + f, [("M", 8)], "ACGTACGT"[f:] + "ACGTACGT"[:f],
+                       qual=[40] * 8) for k in range(100 + f)]
+        raw = raw_of(bw.bam_bytes(refs, recs))
+        path = str(tmp_path / ("f%d.bam" % f))
+        with open(path, "wb") as out:
+            out.write(gw.bgzf(raw, chunk=chunk) if chunk else gw.bgzf(raw, eof=False))
+        paths.append(path)
+        n_rec += len(recs)
+    assert [n_members(p) == header_blocks(p) for p in paths] == [False, True, False] and n_members(paths[1]) == 1
+    for chromosome in (0, 1):
+        _, stats = same(paths, tmp_path, tag=str(chromosome), chromosome=chromosome)
+        assert stats["batches"] == 1 and stats["device_records"] == n_rec
+        assert stats["host_blocks"] == sum(header_blocks(p) for p in paths)
+        assert stats["device_blocks"] == sum(n_members(p) for p in paths) - stats["host_blocks"]
+        assert stats["segments"] == stats["device_blocks"] + 1  # the middle file's carry
+    for p in paths:
+        _scan_equal(p)
+
+
 # ---------------------------------------------------------------------------------------------- errors
 
 def both_errors(files, **kw):
