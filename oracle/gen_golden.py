@@ -585,8 +585,54 @@ def em_cases():
     np.savez_compressed(os.path.join(GOLDEN, "em_cases.npz"), theta=np.float64(1e-3), **out)
 
 
+def save_npz_fixed(path, arrays):
+    """np.savez_compressed with the members' time stamps fixed, so that the same arrays give the same bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asarray(arrays[k]), allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(),
+                       compress_type=zipfile.ZIP_DEFLATED)
+
+
+def pileup_edges():
+    """tests/golden/pileup_edges.npz: the compiled reference's pileup_bams() (oracle/_ref/ref_pileup) on every case of
+    tests/pileup_edge_cases.py. Per case the exit status and, for a clean exit, the SHA-256 of .bin and of .map, the
+    numbers of loci and entries and, for the small families, the .txt lines of the loci with at most 16 entries. The
+    cases where the reference reads past the quality string (undefined behaviour) are not recorded."""
+    from tests import pileup_edge_cases as pe
+    if not pe.have_reference():
+        sys.exit("oracle/_ref/ref_pileup missing: run `make -C oracle ref` in the container")
+    rows = []
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "out")
+        for c in pe.build_all(tmp):
+            if c.kind == pe.UNDEFINED:
+                continue
+            status = pe.run_reference(c, out)
+            assert (status == 0) == (c.kind == pe.CLEAN) and status in (0, pe.ABORT_STATUS), (c.name, status)
+            s = pe.summary_of_files(out) if status == 0 else dict(bin_sha="", map_sha="", n_loci=0, n_entries=0, txt="")
+            if pe.family_of(c.name) not in pe.SMALL_FAMILIES:
+                s["txt"] = ""
+            rows.append((c.name, status, s))
+    arrays = dict(name=np.array([r[0] for r in rows]), status=np.array([r[1] for r in rows], dtype=np.int32))
+    for k in ("bin_sha", "map_sha", "txt"):
+        arrays[k] = np.array([r[2][k] for r in rows])
+    for k in ("n_loci", "n_entries"):
+        arrays[k] = np.array([r[2][k] for r in rows], dtype=np.int64)
+    path = os.path.join(GOLDEN, "pileup_edges.npz")
+    save_npz_fixed(path, arrays)
+    print("pileup_edges: %d cases, %d aborts  %.1f KB" % (len(rows), sum(r[1] != 0 for r in rows),
+                                                        os.path.getsize(path) / 1024))
+
+
 def main():
     only = set(sys.argv[1:])
+    if only == {"pileup_edges"}:  # needs oracle/_ref/ref_pileup alone
+        os.makedirs(GOLDEN, exist_ok=True)
+        return pileup_edges()
     if not ob.have_ref():
         sys.exit("oracle/_ref/libsecedo_ref.so missing: run `make -C oracle ref` in the container")
     os.makedirs(GOLDEN, exist_ok=True)
@@ -594,6 +640,8 @@ def main():
                random_cases, wrap_cases, c2_reference_run, files_pipeline, spectral_cases, filter_cases, reader_cases, laplacian_kat, em_cases):
         if not only or fn.__name__ in only:
             fn()
+    if "pileup_edges" in only:   # by name: a minute of the reference's pileup_bams()
+        pileup_edges()
     if "c3_reference_run" in only:   # five minutes of the reference: only when asked for by name
         c3_reference_run()
     if "c2_clustered_reference_run" in only:

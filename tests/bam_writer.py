@@ -34,6 +34,7 @@ class Rec:
     next_ref: int = -1
     next_pos: int = -1
     tlen: int = 0
+    aux: Optional[bytes] = None  # the aux block verbatim, in place of ``tags`` (layouts ``_tag`` cannot write)
 
 
 def reg2bin(beg: int, end: int) -> int:
@@ -74,7 +75,7 @@ def encode_record(r: Rec) -> bytes:
     seq = bytes((codes[i] << 4) | codes[i + 1] for i in range(0, len(codes), 2))
     qual = bytes([0xFF] * l_seq) if r.qual is None else bytes(r.qual)
     assert len(qual) == l_seq
-    body = core + name + cig + seq + qual + b"".join(_tag(*t) for t in r.tags)
+    body = core + name + cig + seq + qual + (b"".join(_tag(*t) for t in r.tags) if r.aux is None else r.aux)
     return struct.pack("<i", len(body)) + body
 
 

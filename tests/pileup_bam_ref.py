@@ -1,8 +1,9 @@
 """Plain Python restatement of the reference's pileup_bams() (pileup.cpp:49-348) at num_threads = 1, the
 deterministic run, on records decoded by tests/bam_writer.read_bam. Like tests/variant_ref.py it follows the
 reference statement by statement, including BamTools' AlignedBases / Qualities / GetTag("AS", uint32_t&), and
-is pinned by the expectations of the reference's tests/test_pileup.cpp. The reference's asserts raise
-RefAbort.
+is pinned by the expectations of the reference's tests/test_pileup.cpp and, on the edge inputs of
+tests/pileup_edge_cases.py, by the compiled reference itself (tests/test_pileup_edges_cpu.py). The reference's asserts
+raise RefAbort; so does a quality index past the quality string, which the reference reads (undefined behaviour).
 """
 from __future__ import annotations
 
