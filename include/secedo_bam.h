@@ -27,7 +27,13 @@
  * and encodes the BAM records, following htslib's sam_parse1. Departures and limits:
  *  - an RNAME or RNEXT that no @SQ line names is an error (htslib warns and treats the record as unmapped);
  *  - an '@' line after the first alignment line, and an empty line other than the file's last, are errors;
- *  - f aux values are converted to float32 without correct rounding of the last bit (no pass reads them);
+ *  - a SEQ character that is neither a letter nor '=' gives code 15 (N); htslib reads the digits 0 to 3 as A, C, G, T,
+ *    and the SAM specification allows neither;
+ *  - f aux values are converted to float32 through double (the leading 18 digits times a power of ten, rounded
+ *    twice), which is not the correctly rounded float32 for every text. The pileup reads no f value, but
+ *    secedo_bam_split_clusters[_rg] copies them into its output files. What the tests pin (tests/sam_cases.py): texts
+ *    of up to 9 significant digits, what "%.9g" and "%g" print, give the correctly rounded float32, exact ties
+ *    between two floats included;
  *  - no line-length limit below 4 GiB (a range grows to hold its longest line); more than 65535 CIGAR ops or a
  *    record of 2^31 bytes or more is SECEDO_E_LIMIT;
  *  - a .sam.gz that is plain gzip, standard input and CRAM are not read.
