@@ -290,7 +290,8 @@ typedef struct secedo_bam_split_info {
  * Which records: of every file what the pileup calls read (the first contiguous run of each requested chromosome;
  * BAM, SAM and BGZF SAM; either route, any index mode, any SECEDO_BAM_BATCH_BYTES, with the pileup calls' codes and
  * messages for defective input), byte for byte as in the input, block_size included. Records with RefID -1 are not
- * written. The read filter, the duplicate removal and the quality, MAPQ and pair rules of the pileup do not apply.
+ * written. The read filter, the duplicate removal and the quality, MAPQ and pair rules of the pileup do not apply (a
+ * selection of the call's own: secedo_bam_split_clusters_select below).
  * chromosome_ids are RefIDs; they are sorted before use; a duplicate or an id at or past n_ref is SECEDO_E_INVALID_ARG.
  * Order within an output: RefID, Position, input file index, the record's ordinal in its file.
  *
@@ -365,6 +366,54 @@ int secedo_bam_split_clusters_rg(const char *const *bam_files, uint32_t n_files,
                                  const char *const *cell_names, uint32_t n_names,
                                  secedo_bam_split_rg_info *rg_info);
 int secedo_bam_split_rg_stats(secedo_bam_split_rg_info *out);
+
+/* secedo_bam_split_clusters (read_groups 0) or secedo_bam_split_clusters_rg (read_groups != 0; rg_info, cell_names and
+ * n_names are ignored when it is 0) with records selected while each record's cell is still known: after the merge two
+ * reads of one cluster file with the same ends may come from two cells, and are then no duplicates, so no tool can mark
+ * a cluster file. require, exclude and duplicates (SECEDO_BAM_DUPLICATES_KEEP, _REMOVE or _MARK) are this call's own;
+ * with 0, 0, _KEEP the call is the plain one: the same bytes, launches and allocations. The process-wide
+ * secedo_bam_set_read_filter and secedo_bam_set_duplicates and the environment variables SECEDO_BAM_REQUIRE_FLAGS,
+ * SECEDO_BAM_EXCLUDE_FLAGS and SECEDO_BAM_DUPLICATES have no effect on any split call, this one included.
+ *
+ * Let S be the records the plain call would write: those of the requested chromosomes that have a cell.
+ * 1. Filter. A record of S is kept iff (flag & require) == require && (flag & exclude) == 0. Masks above 0xFFFF, or
+ *    masks that share a bit, are SECEDO_E_INVALID_ARG, as is an unknown duplicates mode; both are checked before any
+ *    input is read. Filtered records are not written and take no part in rule 2.
+ * 2. Duplicates. Among what rule 1 kept, per cell and per chromosome, exactly as rule 3d of
+ *    secedo_amd/csrc/bam_kernels.hip (secedo_bam_set_duplicates above): a template is the records of one cell with one
+ *    read name; singles with the same unclipped 5' end and strand are duplicates of each other, pairs with the same two
+ *    ends likewise, a single never of a pair; the template with the highest sum of base qualities >= 15 stays, on a tie
+ *    the one holding the record that comes first in the pileup's global order; templates of three or more records are
+ *    left alone; mates on another chromosome are not seen. The records chosen are the ones
+ *    secedo_pileup_bams(_cells) with duplicate removal on drops for the same input, cells and filter.
+ * 3. _REMOVE: the chosen records are not written. Every output equals what the plain call writes on inputs that never
+ *    held the records dropped by rules 1 and 2.
+ * 4. _MARK: the chosen records are written with bit 0x400 set in their FLAG: byte 19 of the record counting from
+ *    block_size, OR 0x04. No other byte of any record changes and no bit is ever cleared: a record that arrives marked
+ *    and is not chosen keeps its mark (put 0x400 into exclude to drop incoming marks). Record lengths, order, extents,
+ *    member cuts and headers are those of the same call with _KEEP.
+ * 5. Unchanged from the plain call: the header text (no new @PG line), the layout M(header) M(chr) ... EOF,
+ *    temporaries and renames, and a failed call leaves no file. A cluster whose records were all dropped gives a
+ *    header-only file; a chromosome whose records were all dropped contributes no member.
+ * 6. With read_groups the RG edit is applied to what rules 1 to 3 kept; a marked record gets both edits (the FLAG lies
+ *    in the fixed 36 bytes, in front of any hole).
+ *
+ * *select_info (secedo_bam_split_select_stats: the last split call of this thread, all zero after a call without
+ * selection) has the meanings of secedo_bam_select_info: records reached the filter (0 with it off),
+ * duplicate_templates and duplicate_records count what rule 2 chose, marked or removed. secedo_bam_select_stats, the
+ * pileup's getter, is not touched. info->dropped_records stays the records without a listed barcode; info->records is
+ * what was written. The filter, rule 3d's passes over the sorted records, the compaction and the mark (carried to the
+ * gather in the top bit of each record's source offset) run on the GPU: secedo_amd/csrc/bam_split_kernels.hip,
+ * bam_kernels.hip. Not done: clearing marks, optical or UMI-aware duplicates, a @PG line for the marking. */
+#define SECEDO_BAM_DUPLICATES_MARK 2 /* split calls only; secedo_bam_set_duplicates(2) stays an error */
+int secedo_bam_split_clusters_select(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                                     uint32_t n_chr, const uint16_t *cell_cluster, uint32_t n_cells, const char tag[2],
+                                     const char *const *barcodes, uint32_t n_barcodes, const char *out_dir,
+                                     int overwrite, uint32_t num_threads, secedo_bam_split_info *info,
+                                     secedo_bam_times *times, const char *const *cell_names, uint32_t n_names,
+                                     secedo_bam_split_rg_info *rg_info, int read_groups, uint32_t require,
+                                     uint32_t exclude, int duplicates, secedo_bam_select_info *select_info);
+int secedo_bam_split_select_stats(secedo_bam_select_info *out);
 
 /* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
  * num_threads: inflate pool size, capped at 16 (0 = 1). */

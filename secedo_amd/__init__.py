@@ -17,6 +17,6 @@ from .variant import (bgzf_deflate, fasta_stats, get_fasta_route, get_vcf_index,
                       variant_calling, variant_calling_resident, variant_calls, vcf_stats)
 from .bam_pileup import (bam_barcodes, bam_index_build, bam_index_ranges, bam_index_stats, bam_route_stats,  # noqa: F401,E402
                          bam_scan, bam_select_stats, bgzf_inflate, pileup_bams, pileup_bams_resident, set_index,
-                         split_clusters, split_rg_stats, split_stats)
+                         split_clusters, split_rg_stats, split_select_stats, split_stats)
 from .sam_flags import FLAG_NAMES, parse_flags  # noqa: F401,E402
 from .pileup_load import read_pileups_resident  # noqa: F401,E402

@@ -85,6 +85,7 @@ class SplitRgInfo(C.Structure):
 
 INFLATE_MODES = {"host": 0, "device": 1}
 INDEX_MODES = {"off": 0, "auto": 1, "require": 2}
+SPLIT_DUPLICATES = {"off": 0, "remove": 1, "mark": 2}  # SECEDO_BAM_DUPLICATES_KEEP, _REMOVE, _MARK
 
 _vp = C.c_void_p
 _u32 = C.c_uint32
@@ -129,6 +130,11 @@ SIGNATURES = {
                                                C.c_char_p, C.c_int, _u32, C.POINTER(SplitInfo), C.POINTER(Times),
                                                _files_t, _u32, C.POINTER(SplitRgInfo)]),
     "secedo_bam_split_rg_stats": (C.c_int, [C.POINTER(SplitRgInfo)]),
+    "secedo_bam_split_clusters_select": (C.c_int, [_files_t, _u32, _vp, _u32, _vp, _u32, C.c_char_p, _files_t, _u32,
+                                                   C.c_char_p, C.c_int, _u32, C.POINTER(SplitInfo), C.POINTER(Times),
+                                                   _files_t, _u32, C.POINTER(SplitRgInfo), C.c_int, _u32, _u32,
+                                                   C.c_int, C.POINTER(SelectInfo)]),
+    "secedo_bam_split_select_stats": (C.c_int, [C.POINTER(SelectInfo)]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
@@ -388,10 +394,26 @@ def split_rg_stats() -> dict:
     return _split_rg_dict(info)
 
 
+def _select_dict(info: SelectInfo) -> dict:
+    return {k: int(getattr(info, k)) for k, _ in SelectInfo._fields_ if k != "reserved"}
+
+
+def split_select_stats() -> dict:
+    """What the last ``split_clusters`` call on this thread selected (``require_flags``, ``exclude_flags``,
+    ``duplicates``), a failed one up to its failure, with the keys of ``bam_select_stats()``: records that reached the
+    flag filter, dropped_require, dropped_exclude, templates, large_templates, and duplicate_templates /
+    duplicate_records chosen, whether marked or removed. All zero after a call with the three options off.
+    ``bam_select_stats()`` itself is the pileup's and is not touched by a split call."""
+    info = SelectInfo()
+    check(lib().secedo_bam_split_select_stats(C.byref(info)))
+    return _select_dict(info)
+
+
 def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids: Sequence[int], *, cell_tag=None,
                    cells=None, inflate=None, index=None, bai: bool = False, overwrite: bool = False,
                    num_threads: int = 8, times: Optional[dict] = None, read_groups: bool = False,
-                   cell_names: Optional[Sequence[str]] = None) -> dict:
+                   cell_names: Optional[Sequence[str]] = None, require_flags=None, exclude_flags=None,
+                   duplicates: str = "off") -> dict:
     """Writes ``<out_dir>/cluster_<k>.bam`` for every k in 0..max(clustering): the records of the cells of cluster k
     on the chromosomes ``chromosome_ids`` (RefIDs), merged in coordinate order (RefID, Position, input file, record),
     byte for byte as they are in the input; a k no cell has gives a header-only file. The pseudo-bulk BAMs of the
@@ -409,10 +431,26 @@ def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids
     GPU inside the gather. ``cell_names``: one name per cell (1 to 254 bytes in 0x21..0x7E, no two equal); None names a
     cell by its file's base name without .bam / .sam / .sam.gz, or by its barcode. The files are multiplexed BAMs that
     ``pileup_bams(..., cell_tag="RG", cells=names)`` reads back cell by cell.
-    -> the dict of ``split_stats()``, with ``read_groups`` also the keys of ``split_rg_stats()``; ``times`` (a dict)
-    receives the step times in ms."""
+    ``require_flags`` / ``exclude_flags`` (an int, or a string as for ``pileup_bams``, see sam_flags.py) and
+    ``duplicates`` ("off", "mark" or "remove") select records while each record's cell is still known
+    (secedo_bam_split_clusters_select): a record is written iff ``(flag & require) == require and (flag & exclude) ==
+    0``, and among those duplicates are decided per cell and chromosome exactly as ``pileup_bams(...,
+    remove_duplicates=True)`` decides them; "remove" leaves them out, "mark" writes them with 0x400 set in their FLAG
+    and changes nothing else. Two reads of one cluster with the same ends from two cells are no duplicates, which no
+    tool can tell once the files are merged. These are this call's own options: the process-wide filter and duplicate
+    settings of the pileup calls, and their environment variables, never apply to ``split_clusters``.
+    -> the dict of ``split_stats()``, with ``read_groups`` also the keys of ``split_rg_stats()``, with any of the three
+    selection options on also those of ``split_select_stats()`` (its ``records``, the records that reached the filter,
+    as ``filter_records``: ``records`` stays the records written); ``times`` (a dict) receives the step times in ms."""
     if cell_names is not None and not read_groups:
         raise _lib.SecedoError(_lib.E_INVALID_ARG, "cell_names needs read_groups")
+    if duplicates not in SPLIT_DUPLICATES:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "duplicates is 'off', 'mark' or 'remove', got %r" % (duplicates,))
+    try:
+        require, exclude = parse_filter(require_flags, exclude_flags)
+    except ValueError as e:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, str(e))
+    select = bool(require or exclude or SPLIT_DUPLICATES[duplicates])
     arr, n = _files(bam_files)
     if isinstance(clustering, (str, bytes, os.PathLike)):
         try:
@@ -429,13 +467,17 @@ def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids
         import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
     except ImportError:
         pass
-    info, t, rg = SplitInfo(), Times(), SplitRgInfo()
+    info, t, rg, sel = SplitInfo(), Times(), SplitRgInfo(), SelectInfo()
     args = (arr, n, _lib.ptr(ids) if len(ids) else None, len(ids), _lib.ptr(cl), len(cl), tag, bcs, n_bcs,
             os.fsencode(str(out_dir)), int(bool(overwrite)), num_threads, C.byref(info), C.byref(t))
     with _route(inflate, index):
-        if read_groups:
-            names = None if cell_names is None else [_encode(x) for x in cell_names]
-            names_arr = None if names is None else (C.c_char_p * max(len(names), 1))(*names)
+        names = None if cell_names is None else [_encode(x) for x in cell_names]
+        names_arr = None if names is None else (C.c_char_p * max(len(names), 1))(*names)
+        if select:
+            check(lib().secedo_bam_split_clusters_select(*args, names_arr, 0 if names is None else len(names),
+                                                         C.byref(rg), int(bool(read_groups)), require, exclude,
+                                                         SPLIT_DUPLICATES[duplicates], C.byref(sel)))
+        elif read_groups:
             check(lib().secedo_bam_split_clusters_rg(*args, names_arr, 0 if names is None else len(names),
                                                      C.byref(rg)))
         else:
@@ -445,9 +487,12 @@ def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids
     if bai:
         outs = [os.path.join(str(out_dir), "cluster_%d.bam" % k) for k in range(int(info.clusters))]
         bam_index_build(outs, overwrite=True, num_threads=max(1, min(int(num_threads), 16)))
+    out = _split_dict(info)
     if read_groups:
-        return dict(_split_dict(info), **_split_rg_dict(rg))
-    return _split_dict(info)
+        out.update(_split_rg_dict(rg))
+    if select:  # "records" is the split's own key (records written): the filter's count goes by filter_records
+        out.update(("filter_records" if k == "records" else k, v) for k, v in _select_dict(sel).items())
+    return out
 
 
 def bam_route_stats() -> dict:

@@ -94,6 +94,42 @@ struct DevCells {
 };
 int upload_cells(const char tag[2], const std::vector<std::string> &values, hipStream_t s, DevCells *dc);
 
+// ---- rules 3c and 3d of bam_kernels.hip, shared by the pileup calls and secedo_bam_split_clusters_select
+
+// The device counters of the front passes (bam::Sel slots), added to a call's secedo_bam_select_info when a
+// chromosome's passes are done. Stays unallocated, and adds nothing, with both rules off.
+struct SelStat {
+    Dev<unsigned long long> d;
+    int init(hipStream_t s) {
+        SECEDO_TRY(d.alloc(bam::kSelSlots));
+        SECEDO_TRY(hipMemsetAsync(d.p, 0, bam::kSelSlots * 8, s));
+        return SECEDO_OK;
+    }
+    int add_to(hipStream_t s, secedo_bam_select_info *info) {
+        if (!d.p) return SECEDO_OK;
+        unsigned long long h[bam::kSelSlots];
+        SECEDO_TRY(hipMemcpyAsync(h, d.p, sizeof h, hipMemcpyDeviceToHost, s));
+        SECEDO_TRY(hipStreamSynchronize(s));
+        info->records += h[bam::kSelRecords];
+        info->dropped_require += h[bam::kSelRequire];
+        info->dropped_exclude += h[bam::kSelExclude];
+        info->templates += h[bam::kSelTemplates];
+        info->large_templates += h[bam::kSelLarge];
+        info->duplicate_templates += h[bam::kSelDupTemplates];
+        info->duplicate_records += h[bam::kSelDupRecords];
+        return SECEDO_OK;
+    }
+};
+
+// Selected (key, input ordinal) pairs of d_key / d_sel (n records; d_sel has n + 1 entries), sorted by key (stable):
+// -> *n_sel, d_ks, d_vs.
+int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
+                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs);
+// Rule 3d over the rs.n >= 1 records of rs, whose order within a cell is the global order: (*keep)[o] (rs.n + 1
+// entries allocated) = 0 for every record of a template that is not the best of its key, 1 elsewhere. d_stat: Sel
+// counters (kSelTemplates, kSelLarge, kSelDupTemplates, kSelDupRecords). The passes' arrays are freed on return.
+int duplicate_keep(const bam::Records &rs, unsigned long long *d_stat, hipStream_t s, Dev<uint32_t> *keep);
+
 // ---- what bam_input.cpp (host inflate, host walk) and bam_device_input.cpp (device inflate, device walk) share
 
 constexpr uint32_t kMaxThreads = 16;

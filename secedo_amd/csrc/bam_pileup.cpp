@@ -130,30 +130,6 @@ int current_select(Select *sel) {
     return SECEDO_OK;
 }
 
-// The device counters of the front passes (bam::Sel slots), added to g_select when a chromosome's passes are done.
-struct SelStat {
-    Dev<unsigned long long> d;
-    int init(hipStream_t s) {
-        SECEDO_TRY(d.alloc(kSelSlots));
-        SECEDO_TRY(hipMemsetAsync(d.p, 0, kSelSlots * 8, s));
-        return SECEDO_OK;
-    }
-    int add_to_stats(hipStream_t s) {
-        if (!d.p) return SECEDO_OK;
-        unsigned long long h[kSelSlots];
-        SECEDO_TRY(hipMemcpyAsync(h, d.p, sizeof h, hipMemcpyDeviceToHost, s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        g_select.records += h[kSelRecords];
-        g_select.dropped_require += h[kSelRequire];
-        g_select.dropped_exclude += h[kSelExclude];
-        g_select.templates += h[kSelTemplates];
-        g_select.large_templates += h[kSelLarge];
-        g_select.duplicate_templates += h[kSelDupTemplates];
-        g_select.duplicate_records += h[kSelDupRecords];
-        return SECEDO_OK;
-    }
-};
-
 struct ChrOut {
     std::vector<uint8_t> first;  // per ordinal: first occurrence of its name (host files only)
     std::vector<uint32_t> id;
@@ -191,6 +167,87 @@ int upload_cells(const char tag[2], const std::vector<std::string> &values, hipS
     SECEDO_TRY(bam::sort_pairs(tmp.p, tb, h.p, dc->hash.p, idx.p, dc->cell.p, n, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     dc->list = bam::CellList{dc->bytes.p, dc->off.p, dc->hash.p, dc->cell.p, n, uint8_t(tag[0]), uint8_t(tag[1])};
+    return SECEDO_OK;
+}
+
+// Selected (key, input ordinal) pairs of d_key / d_sel (n records), sorted by key: -> *n_sel, d_ks, d_vs.
+int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
+                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs) {
+    using namespace secedo::bam;
+    Dev<uint32_t> scan, vc;
+    Dev<uint64_t> kc;
+    Dev<uint8_t> tmp;
+    size_t tb = scan_bytes(uint64_t(n) + 1);
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(scan.alloc(n + 1));
+    SECEDO_TRY(hipMemsetAsync(d_sel.p + n, 0, 4, s));
+    SECEDO_TRY(exclusive_sum(tmp.p, tb, d_sel.p, scan.p, uint64_t(n) + 1, s));
+    *n_sel = 0;
+    SECEDO_TRY(hipMemcpyAsync(n_sel, scan.p + n, 4, hipMemcpyDeviceToHost, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    const uint32_t m = *n_sel;
+    SECEDO_TRY(kc.alloc(m));
+    SECEDO_TRY(vc.alloc(m));
+    SECEDO_TRY(d_ks->alloc(m));
+    SECEDO_TRY(d_vs->alloc(m));
+    SECEDO_TRY(compact_keys(d_key.p, d_sel.p, scan.p, n, kc.p, vc.p, s));
+    tb = sort_pairs_bytes(m);
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(sort_pairs(tmp.p, tb, kc.p, d_ks->p, vc.p, d_vs->p, m, s));  // radix sort: stable
+    SECEDO_TRY(hipStreamSynchronize(s));
+    return SECEDO_OK;
+}
+
+// Rule 3d over the n >= 1 records rs: ends and scores -> templates by (cell, name) -> groups by key -> the drop flags
+// (bam_host.hpp: duplicate_keep; bam_split.cpp runs it over its own view of the records).
+int duplicate_keep(const bam::Records &rs, unsigned long long *d_stat, hipStream_t s, Dev<uint32_t> *keep_out) {
+    using namespace secedo::bam;
+    const uint32_t n = rs.n;
+    Dev<uint32_t> &keep = *keep_out;
+    Dev<uint64_t> key, key2, end, gkey, gks;
+    Dev<uint32_t> val, val2, score, run, rep, extra, tscore, mate, sel, vs, grp;
+    Dev<unsigned long long> best;
+    Dev<uint8_t> tmp;
+    const size_t tb = std::max(sort_pairs_bytes(n), scan_bytes(uint64_t(n) + 1));
+    SECEDO_TRY(tmp.alloc(tb));
+    SECEDO_TRY(key.alloc(n));
+    SECEDO_TRY(key2.alloc(n));
+    SECEDO_TRY(val.alloc(n));
+    SECEDO_TRY(val2.alloc(n));
+    SECEDO_TRY(end.alloc(n));
+    SECEDO_TRY(score.alloc(n));
+    SECEDO_TRY(ends_and_scores(rs, key.p, val.p, end.p, score.p, s));
+    SECEDO_TRY(sort_pairs(tmp.p, tb, key.p, key2.p, val.p, val2.p, n, s));  // radix sort: stable
+    SECEDO_TRY(run.alloc(n));
+    SECEDO_TRY(rep.alloc(n));
+    SECEDO_TRY(extra.alloc(n));
+    SECEDO_TRY(tscore.alloc(n));
+    SECEDO_TRY(mate.alloc(n));
+    SECEDO_TRY(gkey.alloc(n));
+    SECEDO_TRY(sel.alloc(n + 1));
+    SECEDO_TRY(hipMemsetAsync(extra.p, 0, n * 4ull, s));
+    SECEDO_TRY(hipMemsetAsync(tscore.p, 0, n * 4ull, s));
+    SECEDO_TRY(hipMemsetAsync(mate.p, 0, n * 4ull, s));
+    SECEDO_TRY(templates(rs, key2.p, val2.p, score.p, end.p, run.p, rep.p, extra.p, tscore.p, mate.p, gkey.p, sel.p,
+                         d_stat, tmp.p, tb, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    key.reset();
+    key2.reset();
+    val.reset();
+    val2.reset();
+    score.reset();
+    rep.reset();
+    uint32_t m = 0;
+    SECEDO_CALL(compact_and_sort(gkey, sel, n, s, &m, &gks, &vs));
+    gkey.reset();
+    sel.reset();
+    SECEDO_TRY(grp.alloc(n));
+    SECEDO_TRY(best.alloc(n));
+    SECEDO_TRY(keep.alloc(n + 1));
+    SECEDO_TRY(hipMemsetAsync(best.p, 0, n * 8ull, s));
+    SECEDO_TRY(mark_duplicates(rs, gks.p, vs.p, m, extra.p, mate.p, end.p, tscore.p, run.p, grp.p, best.p, keep.p,
+                               d_stat, tmp.p, tb, s));
+    SECEDO_TRY(hipStreamSynchronize(s));  // the workspace above goes with this scope
     return SECEDO_OK;
 }
 
@@ -237,33 +294,6 @@ int upload_input_order(const ChrInput &ci, hipStream_t s, std::vector<uint64_t> 
     if (n_in) SECEDO_TRY(hipMemcpyAsync(d_in_off->p, in_off->data(), n_in * 8ull, hipMemcpyHostToDevice, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     if (t) t->upload_ms += ms_since(t0);
-    return SECEDO_OK;
-}
-
-// Selected (key, input ordinal) pairs of d_key / d_sel (n records), sorted by key: -> *n_sel, d_ks, d_vs.
-int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
-                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs) {
-    Dev<uint32_t> scan, vc;
-    Dev<uint64_t> kc;
-    Dev<uint8_t> tmp;
-    size_t tb = scan_bytes(uint64_t(n) + 1);
-    SECEDO_TRY(tmp.alloc(tb));
-    SECEDO_TRY(scan.alloc(n + 1));
-    SECEDO_TRY(hipMemsetAsync(d_sel.p + n, 0, 4, s));
-    SECEDO_TRY(exclusive_sum(tmp.p, tb, d_sel.p, scan.p, uint64_t(n) + 1, s));
-    *n_sel = 0;
-    SECEDO_TRY(hipMemcpyAsync(n_sel, scan.p + n, 4, hipMemcpyDeviceToHost, s));
-    SECEDO_TRY(hipStreamSynchronize(s));
-    const uint32_t m = *n_sel;
-    SECEDO_TRY(kc.alloc(m));
-    SECEDO_TRY(vc.alloc(m));
-    SECEDO_TRY(d_ks->alloc(m));
-    SECEDO_TRY(d_vs->alloc(m));
-    SECEDO_TRY(compact_keys(d_key.p, d_sel.p, scan.p, n, kc.p, vc.p, s));
-    tb = sort_pairs_bytes(m);
-    SECEDO_TRY(tmp.alloc(tb));
-    SECEDO_TRY(sort_pairs(tmp.p, tb, kc.p, d_ks->p, vc.p, d_vs->p, m, s));  // radix sort: stable
-    SECEDO_TRY(hipStreamSynchronize(s));
     return SECEDO_OK;
 }
 
@@ -628,54 +658,11 @@ int filter_flags(const ChrInput &ci, const Select &sl, unsigned long long *d_sta
     return compact_chr(ci, keep, s, cd);
 }
 
-// Rule 3d: ends and scores -> templates by (cell, name) -> groups by key -> the drop flags -> compaction.
+// Rule 3d: the drop flags of duplicate_keep -> compaction.
 int remove_duplicates(const ChrInput &ci, unsigned long long *d_stat, hipStream_t s, ChrDev *cd) {
-    const uint32_t n = cd->ord.n;
-    if (n == 0) return SECEDO_OK;
-    const Records rs = cd->records();
-    Dev<uint64_t> key, key2, end, gkey, gks;
-    Dev<uint32_t> val, val2, score, run, rep, extra, tscore, mate, sel, vs, grp, keep;
-    Dev<unsigned long long> best;
-    Dev<uint8_t> tmp;
-    const size_t tb = std::max(sort_pairs_bytes(n), scan_bytes(uint64_t(n) + 1));
-    SECEDO_TRY(tmp.alloc(tb));
-    SECEDO_TRY(key.alloc(n));
-    SECEDO_TRY(key2.alloc(n));
-    SECEDO_TRY(val.alloc(n));
-    SECEDO_TRY(val2.alloc(n));
-    SECEDO_TRY(end.alloc(n));
-    SECEDO_TRY(score.alloc(n));
-    SECEDO_TRY(ends_and_scores(rs, key.p, val.p, end.p, score.p, s));
-    SECEDO_TRY(sort_pairs(tmp.p, tb, key.p, key2.p, val.p, val2.p, n, s));  // radix sort: stable
-    SECEDO_TRY(run.alloc(n));
-    SECEDO_TRY(rep.alloc(n));
-    SECEDO_TRY(extra.alloc(n));
-    SECEDO_TRY(tscore.alloc(n));
-    SECEDO_TRY(mate.alloc(n));
-    SECEDO_TRY(gkey.alloc(n));
-    SECEDO_TRY(sel.alloc(n + 1));
-    SECEDO_TRY(hipMemsetAsync(extra.p, 0, n * 4ull, s));
-    SECEDO_TRY(hipMemsetAsync(tscore.p, 0, n * 4ull, s));
-    SECEDO_TRY(hipMemsetAsync(mate.p, 0, n * 4ull, s));
-    SECEDO_TRY(templates(rs, key2.p, val2.p, score.p, end.p, run.p, rep.p, extra.p, tscore.p, mate.p, gkey.p, sel.p,
-                         d_stat, tmp.p, tb, s));
-    SECEDO_TRY(hipStreamSynchronize(s));
-    key.reset();
-    key2.reset();
-    val.reset();
-    val2.reset();
-    score.reset();
-    rep.reset();
-    uint32_t m = 0;
-    SECEDO_CALL(compact_and_sort(gkey, sel, n, s, &m, &gks, &vs));
-    gkey.reset();
-    sel.reset();
-    SECEDO_TRY(grp.alloc(n));
-    SECEDO_TRY(best.alloc(n));
-    SECEDO_TRY(keep.alloc(n + 1));
-    SECEDO_TRY(hipMemsetAsync(best.p, 0, n * 8ull, s));
-    SECEDO_TRY(mark_duplicates(rs, gks.p, vs.p, m, extra.p, mate.p, end.p, tscore.p, run.p, grp.p, best.p, keep.p,
-                               d_stat, tmp.p, tb, s));
+    if (cd->ord.n == 0) return SECEDO_OK;
+    Dev<uint32_t> keep;
+    SECEDO_CALL(duplicate_keep(cd->records(), d_stat, s, &keep));
     return compact_chr(ci, keep, s, cd);
 }
 
@@ -693,7 +680,7 @@ int run_chromosome(const Inputs &in, const ChrInput &ci, const Params &prm, cons
     const Clock::time_point t0 = Clock::now();
     if (sl.filter() && !cells) SECEDO_CALL(filter_flags(ci, sl, stat.d.p, s, &cd));
     if (sl.dedup) SECEDO_CALL(remove_duplicates(ci, stat.d.p, s, &cd));
-    SECEDO_CALL(stat.add_to_stats(s));
+    SECEDO_CALL(stat.add_to(s, &g_select));
     const uint64_t locus_base = res->n_loci;
     SECEDO_CALL(decode_and_number(in, prm, cells != nullptr, want_map, s, &cd, co));
     if (cd.ord.n) SECEDO_CALL(pile_windows(cd, prm, d_i2g, n_groups, s, res));
@@ -934,7 +921,7 @@ int count_values(const ChrInput &ci, const char *tag, const Select &sl, hipStrea
     SECEDO_TRY(tag_keys(d_bytes.p, d_in_off.p, n_in, t0, t1, sl.require, sl.exclude, key.p, sel.p, stat.d.p, s));
     uint32_t n = 0;
     SECEDO_CALL(compact_and_sort(key, sel, n_in, s, &n, &ks, &vs));
-    SECEDO_CALL(stat.add_to_stats(s));
+    SECEDO_CALL(stat.add_to(s, &g_select));
     if (n == 0) return SECEDO_OK;
     const size_t tb = scan_bytes(n);
     SECEDO_TRY(tmp.alloc(tb));

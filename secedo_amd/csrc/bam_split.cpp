@@ -5,6 +5,9 @@
 // compressed bytes come back; they are appended to the clusters' temporary files. What decides bytes is in
 // bam_split.hpp. secedo_bam_split_clusters_rg is the same call with a gather that edits the records on
 // the way: every record gets RG:Z:<its cell's name>, the header one @RG line per cell of the cluster.
+// secedo_bam_split_clusters_select selects records on the way: the flag filter in front of the compaction,
+// rule 3d's passes (bam_host.hpp: duplicate_keep) over the sorted records, whose choice is removed before the lengths
+// or carried to the gather as a mark.
 #include "bam_host.hpp"
 #include "bam_kernels.hpp"
 #include "bam_split.hpp"
@@ -26,6 +29,7 @@ namespace bz = secedo::bgzf;
 
 thread_local secedo_bam_split_info g_split{};
 thread_local secedo_bam_split_rg_info g_rg{};
+thread_local secedo_bam_select_info g_sel{};
 
 // Members deflated per launch at the most: 256 MiB of slots, whatever the chromosome's size.
 constexpr size_t kSlice = 4096;
@@ -120,6 +124,10 @@ struct Request {
     uint32_t threads = 1;
     bool rg = false;                 // the _rg call: records are edited, the header names the cells
     std::vector<std::string> names;  // with rg: the read group of each cell
+    uint32_t require = 0, exclude = 0;  // the _select call: rule 1, 0 and 0 = off
+    int dup = SECEDO_BAM_DUPLICATES_KEEP;  // the _select call: rule 2, _KEEP = off
+    bool filter() const { return (require | exclude) != 0; }
+    bool select() const { return filter() || dup != SECEDO_BAM_DUPLICATES_KEEP; }
 };
 
 // The suffixes RGZ<name>\0 of all cells on the device, one after the other; off[c] .. off[c + 1] is cell c's.
@@ -181,15 +189,33 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     const uint32_t n_cells = uint32_t(rq.cell_cluster.size());
     Dev<uint64_t> tag_key, key, kc, ks;
     Dev<uint32_t> tag_sel, sel, scan, vc, vs;
+    SelStat stat;  // stays unallocated in the plain and _rg calls
+    if (rq.select()) SECEDO_CALL(stat.init(s));
+    // what the selection counted goes to the call's stats; dropped_records stays the records without a cell
+    const auto take_stats = [&]() -> int {
+        const uint64_t before = g_sel.dropped_require + g_sel.dropped_exclude;
+        SECEDO_CALL(stat.add_to(s, &g_sel));
+        g_split.dropped_records -= g_sel.dropped_require + g_sel.dropped_exclude - before;
+        return SECEDO_OK;
+    };
     SECEDO_TRY(key.alloc(n_in));
     SECEDO_TRY(sel.alloc(size_t(n_in) + 1));
-    if (cells) {  // rule 3b of bam_kernels.hip, its flag filter off: the cell of each record from its tag
+    if (cells) {  // rule 3b of bam_kernels.hip, with its flag filter (3c) in the _select call: the cell from the tag
         SECEDO_TRY(tag_key.alloc(n_in));
         SECEDO_TRY(tag_sel.alloc(n_in));
-        SECEDO_TRY(bam::cells(d_bytes.p, d_in_off.p, n_in, *cells, 0, 0, tag_key.p, tag_sel.p, nullptr, s));
+        SECEDO_TRY(bam::cells(d_bytes.p, d_in_off.p, n_in, *cells, rq.require, rq.exclude, tag_key.p, tag_sel.p,
+                              rq.filter() ? stat.d.p : nullptr, s));
     }
     SECEDO_TRY(bs::split_keys(d_bytes.p, d_in_off.p, n_in, d_file.p, tag_key.p, tag_sel.p, d_cell_cluster, n_cells,
                               key.p, sel.p, s));
+    if (rq.filter() && !cells) {  // rule 3c in per-file mode: the flag test joins the selection (all have a cell)
+        Dev<uint32_t> pass;
+        SECEDO_TRY(pass.alloc(n_in));
+        SECEDO_TRY(bam::flag_test(bam::Records{d_bytes.p, d_in_off.p, d_file.p, n_in}, rq.require, rq.exclude, pass.p,
+                                  stat.d.p, s));
+        SECEDO_TRY(bs::split_and(sel.p, pass.p, n_in, s));
+        SECEDO_TRY(hipStreamSynchronize(s));  // pass goes with this scope
+    }
     size_t tb = bam::scan_bytes(uint64_t(n_in) + 1);
     SECEDO_TRY(tmp.alloc(tb));
     SECEDO_TRY(scan.alloc(size_t(n_in) + 1));
@@ -200,6 +226,7 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     SECEDO_TRY(hipStreamSynchronize(s));
     g_split.dropped_records += n_in - m;
     if (m == 0) {
+        SECEDO_CALL(take_stats());
         g_split.order_ms += ms_lap(t0);
         return SECEDO_OK;
     }
@@ -211,6 +238,42 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     tb = bs::split_sort_bytes(m);
     SECEDO_TRY(tmp.alloc(tb));
     SECEDO_TRY(bs::split_sort(tmp.p, tb, kc.p, ks.p, vc.p, vs.p, m, bs::key_bits(rq.n_clusters - 1), s));
+    // Rule 2. Within a cell the sorted records stand in the pileup's global order, so rule 3d's passes over them choose
+    // the pileup's set. remove: the choice leaves the order here; mark: dup_keep goes on to the sources.
+    Dev<uint32_t> dup_keep;
+    if (rq.dup != SECEDO_BAM_DUPLICATES_KEEP) {
+        SECEDO_TRY(hipStreamSynchronize(s));
+        key.reset(), sel.reset(), scan.reset(), kc.reset(), vc.reset(), tag_sel.reset(), tmp.reset();
+        {
+            Dev<uint64_t> v_off;
+            Dev<uint16_t> v_cell;
+            SECEDO_TRY(v_off.alloc(m));
+            SECEDO_TRY(v_cell.alloc(m));
+            SECEDO_TRY(bs::split_view(d_in_off.p, vs.p, m, d_file.p, tag_key.p, v_off.p, v_cell.p, s));
+            SECEDO_CALL(duplicate_keep(bam::Records{d_bytes.p, v_off.p, v_cell.p, m}, stat.d.p, s, &dup_keep));
+        }
+        if (rq.dup == SECEDO_BAM_DUPLICATES_REMOVE) {
+            tb = bam::scan_bytes(uint64_t(m) + 1);
+            SECEDO_TRY(tmp.alloc(tb));
+            SECEDO_TRY(scan.alloc(size_t(m) + 1));
+            SECEDO_TRY(hipMemsetAsync(dup_keep.p + m, 0, 4, s));
+            SECEDO_TRY(bam::exclusive_sum(tmp.p, tb, dup_keep.p, scan.p, uint64_t(m) + 1, s));
+            uint32_t m2 = 0;
+            SECEDO_TRY(hipMemcpyAsync(&m2, scan.p + m, 4, hipMemcpyDeviceToHost, s));
+            SECEDO_TRY(hipStreamSynchronize(s));
+            if (m2 != m) {  // m2 >= 1: the best template of every key stays
+                SECEDO_TRY(kc.alloc(m2));
+                SECEDO_TRY(vc.alloc(m2));
+                SECEDO_TRY(bs::split_compact(ks.p, vs.p, dup_keep.p, scan.p, m, kc.p, vc.p, s));
+                SECEDO_TRY(hipStreamSynchronize(s));
+                std::swap(ks.p, kc.p), std::swap(ks.n, kc.n);
+                std::swap(vs.p, vc.p), std::swap(vs.n, vc.n);
+                m = m2;
+            }
+            dup_keep.reset();
+        }
+    }
+    SECEDO_CALL(take_stats());
     // destinations and extents
     Dev<uint64_t> src, len, dst, beg;
     SECEDO_TRY(src.alloc(m));
@@ -228,6 +291,8 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     } else {
         SECEDO_TRY(bs::split_lengths(d_bytes.p, d_in_off.p, vs.p, m, src.p, len.p, s));
     }
+    const bool marks = dup_keep.p != nullptr;
+    if (marks) SECEDO_TRY(bs::split_mark(src.p, dup_keep.p, m, s));
     tb = bam::scan_bytes(uint64_t(m) + 1);
     SECEDO_TRY(tmp.alloc(tb));
     SECEDO_TRY(bam::exclusive_sum64(tmp.p, tb, len.p, dst.p, uint64_t(m) + 1, s));
@@ -251,7 +316,7 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     }
     g_split.order_ms += ms_lap(t0);
     key.reset(), sel.reset(), scan.reset(), kc.reset(), vc.reset(), ks.reset(), vs.reset(), len.reset();
-    tag_key.reset(), tag_sel.reset(), tmp.reset();
+    tag_key.reset(), tag_sel.reset(), tmp.reset(), dup_keep.reset();
 
     // the gather: every byte of the stream read once and written once
     const uint64_t padded = (total + bs::kGatherVec - 1) / bs::kGatherVec * bs::kGatherVec;
@@ -264,9 +329,9 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
     SECEDO_TRY(hipEventRecord(ev.e[0], s));
     if (suffixes)
         SECEDO_TRY(bs::split_gather_rg(d_bytes.p, src.p, dst.p, plan.p, suffixes->off.p, suffixes->bytes.p, m, total,
-                                       out.p + kFront, s));
+                                       out.p + kFront, s, marks));
     else
-        SECEDO_TRY(bs::split_gather(d_bytes.p, src.p, dst.p, m, total, out.p + kFront, s));
+        SECEDO_TRY(bs::split_gather(d_bytes.p, src.p, dst.p, m, total, out.p + kFront, s, marks));
     SECEDO_TRY(hipEventRecord(ev.e[1], s));
     SECEDO_TRY(hipStreamSynchronize(s));
     float g_ms = 0;
@@ -358,12 +423,23 @@ int write_headers(const std::vector<std::vector<uint8_t>> &headers, bz::Encoder 
 int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids, uint32_t n_chr,
           const uint16_t *cell_cluster, uint32_t n_cells, const char *tag, const char *const *barcodes,
           uint32_t n_barcodes, const char *out_dir, int overwrite, uint32_t num_threads, secedo_bam_times *times,
-          bool read_groups = false, const char *const *cell_names = nullptr, uint32_t n_names = 0) {
+          bool read_groups = false, const char *const *cell_names = nullptr, uint32_t n_names = 0,
+          uint32_t require = 0, uint32_t exclude = 0, int duplicates = SECEDO_BAM_DUPLICATES_KEEP) {
     const Clock::time_point t_all = Clock::now();
     secedo_bam_times tl{};
     if ((n_files && !bam_files) || (n_chr && !chromosome_ids) || !cell_cluster || !out_dir)
         return fail(SECEDO_E_INVALID_ARG, "null argument");
     Request rq;
+    {  // the selection, before any input is read
+        const std::string why = bs::masks_fault(require, exclude);
+        if (!why.empty()) return fail(SECEDO_E_INVALID_ARG, "secedo_bam_split_clusters_select: " + why);
+        if (duplicates != SECEDO_BAM_DUPLICATES_KEEP && duplicates != SECEDO_BAM_DUPLICATES_REMOVE &&
+            duplicates != SECEDO_BAM_DUPLICATES_MARK)
+            return fail(SECEDO_E_INVALID_ARG, "secedo_bam_split_clusters_select: duplicates " +
+                                                  std::to_string(duplicates) +
+                                                  " is none of SECEDO_BAM_DUPLICATES_KEEP, _REMOVE and _MARK");
+        rq.require = require, rq.exclude = exclude, rq.dup = duplicates;
+    }
     rq.tag = tag;
     rq.threads = num_threads ? num_threads : 1;
     if (n_files == 0) return fail(SECEDO_E_INVALID_ARG, "no input files");
@@ -469,6 +545,7 @@ int secedo_bam_split_clusters(const char *const *bam_files, uint32_t n_files, co
     if (!info) return fail(SECEDO_E_INVALID_ARG, "null argument");
     g_split = secedo_bam_split_info{};
     g_rg = secedo_bam_split_rg_info{};
+    g_sel = secedo_bam_select_info{};
     const int rc = split(bam_files, n_files, chromosome_ids, n_chr, cell_cluster, n_cells, tag, barcodes, n_barcodes,
                          out_dir, overwrite, num_threads, times);
     *info = g_split;
@@ -483,11 +560,38 @@ int secedo_bam_split_clusters_rg(const char *const *bam_files, uint32_t n_files,
     if (!info || !rg_info) return fail(SECEDO_E_INVALID_ARG, "null argument");
     g_split = secedo_bam_split_info{};
     g_rg = secedo_bam_split_rg_info{};
+    g_sel = secedo_bam_select_info{};
     const int rc = split(bam_files, n_files, chromosome_ids, n_chr, cell_cluster, n_cells, tag, barcodes, n_barcodes,
                          out_dir, overwrite, num_threads, times, true, cell_names, n_names);
     *info = g_split;
     *rg_info = g_rg;
     return rc;
+}
+
+int secedo_bam_split_clusters_select(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids,
+                                     uint32_t n_chr, const uint16_t *cell_cluster, uint32_t n_cells, const char tag[2],
+                                     const char *const *barcodes, uint32_t n_barcodes, const char *out_dir,
+                                     int overwrite, uint32_t num_threads, secedo_bam_split_info *info,
+                                     secedo_bam_times *times, const char *const *cell_names, uint32_t n_names,
+                                     secedo_bam_split_rg_info *rg_info, int read_groups, uint32_t require,
+                                     uint32_t exclude, int duplicates, secedo_bam_select_info *select_info) {
+    if (!info || !select_info || (read_groups && !rg_info)) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    g_split = secedo_bam_split_info{};
+    g_rg = secedo_bam_split_rg_info{};
+    g_sel = secedo_bam_select_info{};
+    const int rc = split(bam_files, n_files, chromosome_ids, n_chr, cell_cluster, n_cells, tag, barcodes, n_barcodes,
+                         out_dir, overwrite, num_threads, times, read_groups != 0, read_groups ? cell_names : nullptr,
+                         read_groups ? n_names : 0, require, exclude, duplicates);
+    *info = g_split;
+    if (rg_info) *rg_info = g_rg;
+    *select_info = g_sel;
+    return rc;
+}
+
+int secedo_bam_split_select_stats(secedo_bam_select_info *out) {
+    if (!out) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    *out = g_sel;
+    return SECEDO_OK;
 }
 
 int secedo_bam_split_rg_stats(secedo_bam_split_rg_info *out) {

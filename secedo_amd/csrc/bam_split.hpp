@@ -4,7 +4,9 @@
 // the lookup from an output byte to the record that holds it, which the gather kernel (bam_split_kernels.hip) compiles
 // as device code (the member cuts of a cluster's extent are every writer's: bgzf_members.hpp). Failures come back as
 // the reason's text. At the end, the rules of secedo_bam_split_clusters_rg: the strict aux walk, the
-// edited bytes of a record, the cells' names and the @RG header lines.
+// edited bytes of a record, the cells' names and the @RG header lines; and those of secedo_bam_split_clusters_select
+// (DESIGN 12t): the mask rule, the marked byte and how the mark rides to the gather
+// (tests/cpp/bam_split_select_test.cpp).
 #pragma once
 
 #include <cstdint>
@@ -297,6 +299,60 @@ SPLIT_HD uint8_t edited_byte(const uint8_t *rec, const Edit &e, const uint8_t *s
     if (o < kept) return rec[o + e.hole_len];
     return suffix[o - kept];
 }
+
+// ---- record selection (secedo_bam_split_clusters_select): the flag filter, and duplicates marked or
+// removed per cell. Which records are chosen is rule 3d of bam_kernels.hip; what follows decides the bytes of a marked
+// record and how the mark reaches the gather.
+
+// Why the masks are refused ("" when they are not): a SAM flag has 16 bits, and a bit in both masks passes no record.
+inline std::string masks_fault(uint64_t require, uint64_t exclude) {
+    if (require > 0xFFFF || exclude > 0xFFFF) return "a SAM flag mask is at most 0xFFFF";
+    if (require & exclude)
+        return "require " + std::to_string(require) + " and exclude " + std::to_string(exclude) +
+               " share a bit, no record could pass";
+    return std::string();
+}
+
+// A marked record is the record with 0x400 set in its FLAG: the u16 at bytes 18..19 counting from block_size, so byte
+// kDupByte |= kDupBits. No other byte changes and no bit is cleared.
+constexpr uint32_t kDupByte = 19;
+constexpr uint8_t kDupBits = 0x04;
+
+// byte `value` at offset o of a record, marked or not
+SPLIT_HD uint8_t marked_byte(uint8_t value, uint32_t o, bool marked) {
+    return (marked && o == kDupByte) ? uint8_t(value | kDupBits) : value;
+}
+
+// The mark travels to the gather in the top bit of the record's source offset (offsets are far below 2^63), so a lane
+// that loads src[j] has it without another load.
+constexpr uint64_t kMarkBit = 1ull << 63;
+SPLIT_HD uint64_t pack_src(uint64_t off, bool marked) { return marked ? off | kMarkBit : off; }
+SPLIT_HD uint64_t src_off(uint64_t src) { return src & ~kMarkBit; }
+SPLIT_HD bool src_marked(uint64_t src) { return (src & kMarkBit) != 0; }
+
+// The 16 bytes v[0..3] (little-endian dwords) of a gather lane that start at offset r of a marked record and lie
+// wholly inside it: the lane that holds byte kDupByte sets the bits.
+SPLIT_HD void mark_vector(uint32_t v[4], uint64_t r) {
+    if (r <= kDupByte && kDupByte - r < kGatherVec) {
+        const uint32_t at = kDupByte - uint32_t(r);
+        const uint32_t bits = uint32_t(kDupBits) << (8 * (at & 3));
+        const uint32_t word = at >> 2;  // constant indices only: v stays in registers
+        v[0] |= word == 0 ? bits : 0u;
+        v[1] |= word == 1 ? bits : 0u;
+        v[2] |= word == 2 ? bits : 0u;
+        v[3] |= word == 3 ? bits : 0u;
+    }
+}
+// Only such lanes are patched, and no other lane holds the byte. A lane of the plain gather that is not wholly inside
+// one record starts in a record j at offset r and reaches past its end: r + 16 > len >= kMinRecord, so r > kDupByte,
+// and byte kDupByte of record j + 1 lies more than kDupByte >= 16 bytes past the lane's first byte. In the editing
+// gather a lane that holds byte kDupByte starts at offset r in 4..19 (r + 15 >= 19) and ends at r + 16 <= 35, in front
+// of any hole (hole_off >= 36 + l_name >= kMinRecord) and inside the edited record, which is no shorter than
+// kMinRecord: it lies in the copied segment in front of the hole and takes the five-dword path.
+static_assert(kMinRecord >= kDupByte + 1 + kGatherVec, "a lane on a record boundary never holds the FLAG's high byte");
+static_assert(kDupByte >= kGatherVec, "a lane never reaches the next record's FLAG");
+static_assert(kDupByte + kGatherVec <= kMinRecord, "a lane that holds the FLAG's high byte ends before any hole");
+static_assert(kDupByte + 1 >= 4 + kGatherVec, "a lane that holds the FLAG's high byte starts behind block_size");
 
 // what the plan pass leaves the gather of a sorted record: the hole, the record's length and its cell
 struct RecordPlan {

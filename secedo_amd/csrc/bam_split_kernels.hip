@@ -11,7 +11,11 @@
 //   k_split_gather   one thread per 16 output bytes: the bandwidth pass
 // secedo_bam_split_clusters_rg runs k_split_plan in place of k_split_lengths (the aux walk, the hole of
 // the record's own RG field, the edited length) and k_split_gather_rg in place of k_split_gather (the same tiles over
-// edited records); both stand behind the plain call's kernels below.
+// edited records); both stand behind the plain call's kernels below. secedo_bam_split_clusters_select
+// adds, only when asked: k_split_and (per-file mode's flag test joins the selection), k_split_view (the sorted records
+// as the bam::Records that rule 3d's passes of bam_kernels.hip take), k_split_compact (remove: the chosen records
+// leave the order) and k_split_mark (mark: the choice goes into the top bit of src[j]); the two gathers are templates
+// whose <true> instantiation sets 0x04 in byte 19 of a marked record, and whose <false> one is the code they were.
 //
 // The gather is balanced over output bytes, not over records: lane i of a workgroup writes bytes [16 i, 16 i + 16) of
 // the workgroup's 4 KiB tile with one aligned 16-byte store, so a wave's store instruction covers 1 KiB contiguous
@@ -89,6 +93,9 @@ __device__ __forceinline__ uint32_t dword_at(const uint32_t *__restrict__ w, uin
     return uint32_t(pair >> (8 * uint32_t(s & 3)));
 }
 
+// kMark: src[j] carries the record's duplicate mark in its top bit (bam_split.hpp: pack_src); the lane
+// that holds byte 19 of a marked record sets 0x04 in it. Without kMark src[j] is the offset and nothing is tested.
+template <bool kMark>
 __global__ void __launch_bounds__(kGatherLanes) k_split_gather(const uint8_t *__restrict__ bytes,
                                                                const uint64_t *__restrict__ src,
                                                                const uint64_t *__restrict__ dst, uint32_t m,
@@ -103,6 +110,8 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather(const uint8_t *__
     const uint32_t hi = uint64_t(lo) + kTileRecords < m ? lo + kTileRecords : m;
     uint32_t j = record_of(dst, lo, hi, b);
     uint64_t d0 = dst[j], d1 = dst[j + 1], s0 = src[j];
+    const bool marked = kMark && src_marked(s0);
+    if (kMark) s0 = src_off(s0);
     const uint32_t *w = reinterpret_cast<const uint32_t *>(bytes);
     uint32_t v[4];
     if (b + kGatherVec <= d1) {  // all 16 bytes in record j: five aligned dwords cover them
@@ -114,13 +123,14 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather(const uint8_t *__
         for (int i = 0; i < 5; ++i) x[i] = w[k + i];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = uint32_t((uint64_t(x[i + 1]) << 32 | x[i]) >> sh);
-    } else {
+        if (marked) mark_vector(v, b - d0);
+    } else {  // a record boundary or the stream's end: never byte 19 of a record (bam_split.hpp)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint64_t p = b + 4 * i;
             while (p < total && p >= d1) {  // p < total = dst[m]: j + 1 <= m stays inside dst
                 ++j;
-                d0 = d1, d1 = dst[j + 1], s0 = src[j];
+                d0 = d1, d1 = dst[j + 1], s0 = kMark ? src_off(src[j]) : src[j];
             }
             if (p + 4 <= d1) {
                 v[i] = dword_at(w, s0 + (p - d0));
@@ -130,7 +140,7 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather(const uint8_t *__
             for (uint32_t q = 0; q < 4 && p + q < total; ++q) {
                 while (p + q >= d1) {
                     ++j;
-                    d0 = d1, d1 = dst[j + 1], s0 = src[j];
+                    d0 = d1, d1 = dst[j + 1], s0 = kMark ? src_off(src[j]) : src[j];
                 }
                 x |= uint32_t(bytes[s0 + (p + q - d0)]) << (8 * q);
             }
@@ -186,10 +196,14 @@ struct Cursor {
     uint64_t d0, d1, s0;
     Edit e;
     const uint8_t *suffix;
+    bool marked;
+    template <bool kMark>
     __device__ __forceinline__ void load(const uint64_t *__restrict__ src, const uint64_t *__restrict__ dst,
                                          const RecordPlan *__restrict__ plan, const uint32_t *__restrict__ suf_off,
                                          const uint8_t *__restrict__ suf, uint32_t j) {
         d0 = dst[j], d1 = dst[j + 1], s0 = src[j];
+        marked = kMark && src_marked(s0);
+        if (kMark) s0 = src_off(s0);
         const RecordPlan p = plan[j];
         const uint32_t so = suf_off[p.cell];
         e = Edit{p.len, p.hole_off, p.hole_len, suf_off[p.cell + 1] - so};
@@ -201,7 +215,9 @@ struct Cursor {
 // word, the bytes before the hole, the bytes after it and the cell's suffix. A lane whose 16 bytes lie in one of the
 // two copied segments keeps the five-dword path; any other lane (a record's first bytes, a hole, a suffix, a record
 // boundary, the stream's end) takes whole dwords where a dword lies in a copied segment and edited_byte's rule for the
-// rest. The tile bound is the plain gather's (bam_split.hpp says why it holds for edited records).
+// rest. The tile bound is the plain gather's (bam_split.hpp says why it holds for edited records). kMark as in
+// k_split_gather: byte 19 lies in front of any hole, in a lane of the five-dword path (bam_split.hpp).
+template <bool kMark>
 __global__ void __launch_bounds__(kGatherLanes) k_split_gather_rg(const uint8_t *__restrict__ bytes,
                                                                   const uint64_t *__restrict__ src,
                                                                   const uint64_t *__restrict__ dst,
@@ -219,7 +235,7 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather_rg(const uint8_t 
     const uint32_t hi = uint64_t(lo) + kTileRecords < m ? lo + kTileRecords : m;
     uint32_t j = record_of(dst, lo, hi, b);
     Cursor c;
-    c.load(src, dst, plan, suf_off, suf, j);
+    c.template load<kMark>(src, dst, plan, suf_off, suf, j);
     const uint32_t *w = reinterpret_cast<const uint32_t *>(bytes);
     uint32_t v[4];
     const uint64_t r = b - c.d0;  // < 2^32: inside record j
@@ -235,11 +251,13 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather_rg(const uint8_t 
         for (int i = 0; i < 5; ++i) x[i] = w[k + i];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = uint32_t((uint64_t(x[i + 1]) << 32 | x[i]) >> sh);
+        if (c.marked) mark_vector(v, r);
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint64_t p = b + 4 * i;
-            while (p < total && p >= c.d1) c.load(src, dst, plan, suf_off, suf, ++j);  // j <= m - 1: p < dst[m]
+            // j <= m - 1: p < dst[m]
+            while (p < total && p >= c.d1) c.template load<kMark>(src, dst, plan, suf_off, suf, ++j);
             const uint64_t q = p - c.d0;
             const uint32_t keep = c.e.len - c.e.hole_len;
             if (p + 4 <= c.d1 && q >= 4 && q + 4 <= c.e.hole_off) {
@@ -254,7 +272,7 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather_rg(const uint8_t 
 #pragma unroll
             for (uint32_t t = 0; t < 4; ++t) {
                 if (p + t >= total) break;
-                while (p + t >= c.d1) c.load(src, dst, plan, suf_off, suf, ++j);
+                while (p + t >= c.d1) c.template load<kMark>(src, dst, plan, suf_off, suf, ++j);
                 x |= uint32_t(edited_byte(bytes + c.s0, c.e, c.suffix, uint32_t(p + t - c.d0))) << (8 * t);
             }
             v[i] = x;
@@ -263,9 +281,79 @@ __global__ void __launch_bounds__(kGatherLanes) k_split_gather_rg(const uint8_t 
     *reinterpret_cast<uint4 *>(out + b) = make_uint4(v[0], v[1], v[2], v[3]);
 }
 
+// ---- record selection
+
+// per-file mode's flag filter: the selection of k_split_keys ANDed with bam::flag_test's keep, in front of the scan
+__global__ void __launch_bounds__(kBlock) k_split_and(uint32_t *__restrict__ sel, const uint32_t *__restrict__ keep,
+                                                      uint32_t n) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o < n && !keep[o]) sel[o] = 0;
+}
+
+// The bam::Records view of the sorted records, one thread per sorted record j: where it lies and its cell (as
+// k_split_keys found it). Within a cell the sorted order is the pileup's global order, so rule 3d's passes over this
+// view choose the pileup's set.
+__global__ void __launch_bounds__(kBlock) k_split_view(const uint64_t *__restrict__ in_off,
+                                                       const uint32_t *__restrict__ val, uint32_t m,
+                                                       const uint16_t *__restrict__ file,
+                                                       const uint64_t *__restrict__ tag_key,
+                                                       uint64_t *__restrict__ off, uint16_t *__restrict__ cell) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t o = val[j];
+    off[j] = in_off[o];
+    cell[j] = tag_key ? uint16_t((tag_key[o] >> 32) & 0x3FFF) : file[o];
+}
+
+// remove: the sorted (key, ordinal) pairs with keep[j] at scan[j] (keep's exclusive sum), order kept
+__global__ void __launch_bounds__(kBlock) k_split_compact(const uint64_t *__restrict__ key,
+                                                          const uint32_t *__restrict__ val,
+                                                          const uint32_t *__restrict__ keep,
+                                                          const uint32_t *__restrict__ scan, uint32_t m,
+                                                          uint64_t *__restrict__ key_out,
+                                                          uint32_t *__restrict__ val_out) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m || !keep[j]) return;
+    key_out[scan[j]] = key[j];
+    val_out[scan[j]] = val[j];
+}
+
+// mark: the chosen records (keep[j] == 0) get the top bit of their source offset set
+__global__ void __launch_bounds__(kBlock) k_split_mark(uint64_t *__restrict__ src, const uint32_t *__restrict__ keep,
+                                                       uint32_t m) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j < m) src[j] = pack_src(src[j], keep[j] == 0);
+}
+
 inline uint32_t grid(uint64_t n) { return uint32_t((n + kBlock - 1) / kBlock); }
 
 }  // namespace
+
+hipError_t split_and(uint32_t *d_sel, const uint32_t *d_keep, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_split_and<<<grid(n), kBlock, 0, s>>>(d_sel, d_keep, n);
+    return hipGetLastError();
+}
+
+hipError_t split_view(const uint64_t *d_in_off, const uint32_t *d_val, uint32_t m, const uint16_t *d_file,
+                      const uint64_t *d_tag_key, uint64_t *d_off, uint16_t *d_cell, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    k_split_view<<<grid(m), kBlock, 0, s>>>(d_in_off, d_val, m, d_file, d_tag_key, d_off, d_cell);
+    return hipGetLastError();
+}
+
+hipError_t split_compact(const uint64_t *d_key, const uint32_t *d_val, const uint32_t *d_keep, const uint32_t *d_scan,
+                         uint32_t m, uint64_t *d_key_out, uint32_t *d_val_out, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    k_split_compact<<<grid(m), kBlock, 0, s>>>(d_key, d_val, d_keep, d_scan, m, d_key_out, d_val_out);
+    return hipGetLastError();
+}
+
+hipError_t split_mark(uint64_t *d_src, const uint32_t *d_keep, uint32_t m, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    k_split_mark<<<grid(m), kBlock, 0, s>>>(d_src, d_keep, m);
+    return hipGetLastError();
+}
 
 hipError_t split_keys(const uint8_t *d_bytes, const uint64_t *d_in_off, uint32_t n, const uint16_t *d_file,
                       const uint64_t *d_tag_key, const uint32_t *d_tag_sel, const uint16_t *d_cell_cluster,
@@ -302,11 +390,12 @@ hipError_t split_extents(const uint64_t *d_key, const uint64_t *d_dst, uint32_t 
 }
 
 hipError_t split_gather(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst, uint32_t m,
-                        uint64_t total, uint8_t *d_out, hipStream_t s) {
+                        uint64_t total, uint8_t *d_out, hipStream_t s, bool marks) {
     if (m == 0 || total == 0) return hipSuccess;
     const uint64_t tiles = (total + kTileBytes - 1) / kTileBytes;
     if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_split_gather<<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, m, total, d_out);
+    if (marks) k_split_gather<true><<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, m, total, d_out);
+    else k_split_gather<false><<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, m, total, d_out);
     return hipGetLastError();
 }
 
@@ -321,12 +410,16 @@ hipError_t split_plan(const uint8_t *d_bytes, const uint64_t *d_in_off, const ui
 
 hipError_t split_gather_rg(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst,
                            const RecordPlan *d_plan, const uint32_t *d_suf_off, const uint8_t *d_suf, uint32_t m,
-                           uint64_t total, uint8_t *d_out, hipStream_t s) {
+                           uint64_t total, uint8_t *d_out, hipStream_t s, bool marks) {
     if (m == 0 || total == 0) return hipSuccess;
     const uint64_t tiles = (total + kTileBytes - 1) / kTileBytes;
     if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_split_gather_rg<<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, d_plan, d_suf_off, d_suf, m,
-                                                               total, d_out);
+    if (marks)
+        k_split_gather_rg<true><<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, d_plan, d_suf_off,
+                                                                         d_suf, m, total, d_out);
+    else
+        k_split_gather_rg<false><<<uint32_t(tiles), kGatherLanes, 0, s>>>(d_bytes, d_src, d_dst, d_plan, d_suf_off,
+                                                                          d_suf, m, total, d_out);
     return hipGetLastError();
 }
 

@@ -37,9 +37,10 @@ hipError_t split_extents(const uint64_t *d_key, const uint64_t *d_dst, uint32_t 
 
 // The gather: output bytes [0, total) of the one stream, record j's bytes at d_dst[j] (d_dst[m] = total), written to
 // d_out as whole 16-byte vectors (d_out 16-byte aligned, room for total rounded up to 16; the bytes past total are
-// zero). d_bytes is read as aligned dwords: it needs 8 bytes of room behind its last record.
+// zero). d_bytes is read as aligned dwords: it needs 8 bytes of room behind its last record. marks: d_src went through
+// split_mark, and a marked record is written with 0x400 set in its FLAG (the kMark instantiation).
 hipError_t split_gather(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst, uint32_t m,
-                        uint64_t total, uint8_t *d_out, hipStream_t s);
+                        uint64_t total, uint8_t *d_out, hipStream_t s, bool marks = false);
 
 // ---- read groups (secedo_bam_split_clusters_rg); RecordPlan and the rules are bam_split.hpp's
 
@@ -52,10 +53,24 @@ hipError_t split_plan(const uint8_t *d_bytes, const uint64_t *d_in_off, const ui
                       uint64_t *d_len, RecordPlan *d_plan, uint64_t *d_cnt, hipStream_t s);
 
 // split_gather over edited records: record j's edited bytes at d_dst[j]. d_bytes and d_out as for split_gather; d_suf
-// is read byte by byte.
+// is read byte by byte. marks as for split_gather.
 hipError_t split_gather_rg(const uint8_t *d_bytes, const uint64_t *d_src, const uint64_t *d_dst,
                            const RecordPlan *d_plan, const uint32_t *d_suf_off, const uint8_t *d_suf, uint32_t m,
-                           uint64_t total, uint8_t *d_out, hipStream_t s);
+                           uint64_t total, uint8_t *d_out, hipStream_t s, bool marks = false);
+
+// ---- record selection (secedo_bam_split_clusters_select)
+
+// per-file mode's flag filter: d_sel[o] = 0 where d_keep[o] == 0 (bam::flag_test over the input order)
+hipError_t split_and(uint32_t *d_sel, const uint32_t *d_keep, uint32_t n, hipStream_t s);
+// The bam::Records view of the sorted records for rule 3d's passes: d_off[j] = d_in_off[d_val[j]], d_cell[j] = the
+// cell of sorted record j (d_file / d_tag_key as for split_keys).
+hipError_t split_view(const uint64_t *d_in_off, const uint32_t *d_val, uint32_t m, const uint16_t *d_file,
+                      const uint64_t *d_tag_key, uint64_t *d_off, uint16_t *d_cell, hipStream_t s);
+// remove: the sorted pairs with d_keep[j] != 0 at d_scan[j] (the exclusive sum of d_keep), order kept
+hipError_t split_compact(const uint64_t *d_key, const uint32_t *d_val, const uint32_t *d_keep, const uint32_t *d_scan,
+                         uint32_t m, uint64_t *d_key_out, uint32_t *d_val_out, hipStream_t s);
+// mark: d_src[j] = pack_src(d_src[j], d_keep[j] == 0)
+hipError_t split_mark(uint64_t *d_src, const uint32_t *d_keep, uint32_t m, hipStream_t s);
 
 }  // namespace bamsplit
 }  // namespace secedo

@@ -16,6 +16,12 @@ per line, cell c being line c; records without a listed barcode are dropped. --c
 had, and the header of cluster k one ``@RG ID:<name> SM:cluster_<k>`` line per cell of the cluster, so a somatic caller
 takes the files and ``pileup_main --cell_tag RG`` reads them back cell by cell. --cell_names FILE gives the names, one
 per line, cell c being line c; without it a cell is named by its file's base name, or by its barcode.
+
+--require_flags / --exclude_flags (decimal, 0x hex or samtools' names, as for ``pileup_main``) write only the records
+whose FLAG has all of the first and none of the second. --duplicates mark|remove decides PCR duplicates per cell, as
+``pileup_main --remove_duplicates`` does, while each read's cell is still known: in the merged files two reads with the
+same ends may come from two cells, and no tool could tell. ``mark`` sets 0x400 in the FLAG of the duplicates and changes
+nothing else, ``remove`` leaves them out.
 """
 from __future__ import annotations
 
@@ -24,8 +30,8 @@ import os
 import sys
 from typing import List, Optional
 
-from .pileup_main import (DEFAULT_CHROMOSOMES, MAX_CELLS, build_missing_indexes, check_index_flags, chromosome_to_id,
-                          input_files, pool_size, read_cells, valid_tag)
+from .pileup_main import (DEFAULT_CHROMOSOMES, MAX_CELLS, build_missing_indexes, check_index_flags, check_select_flags,
+                          chromosome_to_id, input_files, pool_size, read_cells, valid_tag)
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -48,6 +54,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                     help="Tag every record with RG:Z:<name of its cell> and write one @RG line per cell")
     ap.add_argument("--cell_names", default=None,
                     help="With --read_groups: file of read-group names, one per line; cell c is line c")
+    ap.add_argument("--require_flags", default=None,
+                    help="Write only records with all of these SAM flags (decimal, 0x hex or names, e.g. PROPER_PAIR)")
+    ap.add_argument("--exclude_flags", default=None,
+                    help="Write no record with any of these SAM flags (e.g. SECONDARY,SUPPLEMENTARY,QCFAIL or 0xF00)")
+    ap.add_argument("--duplicates", default="off",
+                    help="off, mark or remove: duplicates per cell and chromosome, marked with FLAG 0x400 or left out")
     ap.add_argument("--overwrite", action="store_true", help="Replace existing cluster_<k>.bam files")
     ap.add_argument("--num_threads", type=int, default=8, help="Host inflate threads (at most 16 are used)")
     return ap.parse_args(argv)
@@ -56,6 +68,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
 def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
     # everything below is checked before any BAM is read and before torch is imported
+    if a.duplicates not in ("off", "mark", "remove"):
+        raise SystemExit("Invalid --duplicates %r: off, mark or remove" % a.duplicates)
+    check_select_flags(a)
     if not os.path.isfile(a.clustering):
         raise SystemExit("--clustering file %s does not exist" % a.clustering)
     cells = None
@@ -117,6 +132,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     tag_kw = {} if a.cell_tag is None else dict(cell_tag=a.cell_tag, cells=cells)
     if a.read_groups:
         tag_kw.update(read_groups=True, cell_names=names)
+    filtered = a.require_flags is not None
+    if filtered:
+        tag_kw.update(require_flags=a.require_flags, exclude_flags=a.exclude_flags)
+    if a.duplicates != "off":
+        tag_kw.update(duplicates=a.duplicates)
     st = split_clusters(files, clustering, a.o, ids, inflate=a.inflate, index=a.index, bai=a.bai,
                         overwrite=a.overwrite, num_threads=pool_size(a.num_threads), **tag_kw)
     print("Written %d records of %d cells to %d files %s (%d bytes, %d BGZF members, %d of them stored)%s"
@@ -126,6 +146,15 @@ def main(argv: Optional[List[str]] = None) -> int:
     if a.read_groups:
         print("Tagged %d records with their cell's read group (%d had an RG field, replaced; %d did not parse, kept whole)"
               % (st["tagged_records"], st["replaced_records"], st["unparsed_records"]))
+    if filtered and "filter_records" in st:
+        print("Flag filter: %d of %d records dropped (%d lack a required flag, %d have an excluded one)"
+              % (st["dropped_require"] + st["dropped_exclude"], st["filter_records"], st["dropped_require"],
+                 st["dropped_exclude"]))
+    if a.duplicates != "off":
+        print("Duplicates: %d records of %d templates %s (%d templates seen, %d of three or more records left alone)"
+              % (st["duplicate_records"], st["duplicate_templates"],
+                 "marked with FLAG 0x400" if a.duplicates == "mark" else "removed", st["templates"],
+                 st["large_templates"]))
     return 0
 
 

@@ -17,12 +17,17 @@ tag-mode call, split_stats() of the last of --repeat runs after one untimed run 
 and whether the two calls wrote the same number of records. --read_groups runs the same two calls with
 read_groups=True (every record tagged RG:Z:<its cell>): the line then also holds split_rg_stats(), and the
 gather's bytes are what the editing gather reads and writes. total_ms_runs lists the call totals of the timed runs, so
-that two lines can be compared against their own run-to-run spread. Run it under a time limit (timeout -k 10 ...)."""
+that two lines can be compared against their own run-to-run spread. --require_flags, --exclude_flags and --duplicates
+off|mark|remove run the calls with records selected on the way: the line then also holds the select
+counts, and with "mark" the gather is the marking instantiation. The uniform set has almost no duplicates, so
+--dup_rate R plants them: in every cell R x pairs of its pairs are written a second time under another name, and the
+multiplexed file is made from those cells. Run it under a time limit (timeout -k 10 ...)."""
 import argparse
 import gzip
 import json
 import os
 import shutil
+import struct
 import sys
 
 import numpy as np
@@ -62,6 +67,43 @@ def run(files, clustering, out, repeat, threads, **kw):
     return r
 
 
+def plant_duplicates(paths, d, rate, seed=9):
+    """The cells of write_set with int(rate * pairs) of each cell's pairs written twice, the copy under a name whose
+    first character differs, records in coordinate order -> (paths under d, records added in all)."""
+    from tests import bam_writer as bw
+
+    os.makedirs(d, exist_ok=True)
+    stamp = os.path.join(d, "dup.json")
+    want = dict(rate=rate, seed=seed, cells=len(paths))
+    out = [os.path.join(d, os.path.basename(p)) for p in paths]
+    if os.path.exists(stamp):
+        have = json.load(open(stamp))
+        if {k: have.get(k) for k in want} == want:
+            return out, have["added"]
+    rng = np.random.default_rng(seed)
+    added = 0
+    for p, q in zip(paths, out):
+        raw = gzip.decompress(open(p, "rb").read())
+        o = 8 + struct.unpack_from("<i", raw, 4)[0] + 4 + 4 + 2 + 4  # one reference named "1"
+        rec = np.frombuffer(raw, dtype=np.uint8, offset=o).reshape(-1, 211)  # uniform_cell_bam's fixed size
+        names = [r.tobytes() for r in rec[:, 36:53]]
+        by_name = {}
+        for k, name in enumerate(names):
+            by_name.setdefault(name, []).append(k)
+        pairs = [v for v in by_name.values() if len(v) == 2]
+        take = rng.choice(len(pairs), int(rate * len(pairs)), replace=False)
+        copy = rec[[k for t in take for k in pairs[t]]].copy()
+        copy[:, 36] = ord("~")  # no name of the set starts with it
+        both = np.concatenate([rec, copy])
+        pos = both[:, 8:12].copy().view("<i4").ravel()
+        both = both[np.argsort(pos, kind="stable")]
+        added += len(copy)
+        with open(q, "wb") as f:
+            f.write(bw.bgzf(raw[:o] + both.tobytes()))
+    json.dump(dict(want, added=added), open(stamp, "w"))
+    return out, added
+
+
 def zlib_beside(path, mib):
     """zlib level 1 and 6 and our members over the first pieces of one written file."""
     from tests import bgzf_deflate_cases as dc
@@ -91,11 +133,20 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--zlib-mib", type=int, default=16)
     ap.add_argument("--read_groups", action="store_true", help="tag every record with its cell's read group")
+    ap.add_argument("--require_flags", default=None, help="write only records with all of these SAM flags")
+    ap.add_argument("--exclude_flags", default=None, help="write no record with any of these SAM flags")
+    ap.add_argument("--duplicates", choices=("off", "mark", "remove"), default="off")
+    ap.add_argument("--dup_rate", type=float, default=0.0, help="plant this share of every cell's pairs a second time")
     a = ap.parse_args()
     import bench_pileup_bams as bp
 
     paths, gen_s = bp.write_set(a.dir, a.cells, a.pairs, a.mbp)
-    mpath, barcodes, mux_s = bp.write_multiplexed(a.dir, paths, dict(cells=a.cells, pairs=a.pairs, mbp=a.mbp))
+    mux_dir, planted = a.dir, 0
+    if a.dup_rate > 0:
+        mux_dir = os.path.join(a.dir, "dup_%g" % a.dup_rate)
+        paths, planted = plant_duplicates(paths, mux_dir, a.dup_rate)
+    mpath, barcodes, mux_s = bp.write_multiplexed(mux_dir, paths, dict(cells=a.cells, pairs=a.pairs, mbp=a.mbp,
+                                                                       dup_rate=a.dup_rate))
     print("set ready (%.1f s, multiplexed %.1f s)" % (gen_s, mux_s), file=sys.stderr, flush=True)
     clustering = [c % a.clusters for c in range(a.cells)]
     outs = []
@@ -105,14 +156,22 @@ def main():
         os.makedirs(d)
         outs.append(d)
     line = dict(workload="split_clusters_uniform", cells=a.cells, pairs=a.pairs, mbp=a.mbp, clusters=a.clusters,
-                threads=a.threads, records=a.cells * a.pairs * 2, record_bytes=a.cells * a.pairs * 2 * 211,
+                threads=a.threads, records=a.cells * a.pairs * 2 + planted,
+                record_bytes=(a.cells * a.pairs * 2 + planted) * 211,
                 bam_bytes=sum(os.path.getsize(p) for p in paths), hbm_measured_GBps=HBM_MEASURED / 1e9,
-                read_groups=a.read_groups)
+                read_groups=a.read_groups, require_flags=a.require_flags, exclude_flags=a.exclude_flags,
+                duplicates=a.duplicates, dup_rate=a.dup_rate, planted_records=planted)
     kw = dict(read_groups=True) if a.read_groups else {}
+    if a.require_flags is not None or a.exclude_flags is not None:
+        kw.update(require_flags=a.require_flags, exclude_flags=a.exclude_flags)
+    if a.duplicates != "off":
+        kw.update(duplicates=a.duplicates)
     line["per_cell"] = run(paths, clustering, outs[0], a.repeat, a.threads, **kw)
     line["multiplexed"] = run([mpath], clustering, outs[1], a.repeat, a.threads, cell_tag="CB", cells=barcodes, **kw)
     # the multiplexed records carry the CB:Z tag, so the two calls' files differ; their record counts must not
-    line["records_equal"] = line["per_cell"]["records"] == line["multiplexed"]["records"] == line["records"]
+    line["records_equal"] = line["per_cell"]["records"] == line["multiplexed"]["records"]
+    if "duplicate_records" not in line["per_cell"]:  # nothing selected: every input record is written
+        line["records_equal"] = line["records_equal"] and line["per_cell"]["records"] == line["records"]
     line["zlib"] = zlib_beside(os.path.join(outs[0], "cluster_0.bam"), a.zlib_mib)
     print(json.dumps(line), flush=True)
 
