@@ -299,10 +299,106 @@ typedef struct secedo_variant_tabix_info {
 } secedo_variant_tabix_info;
 int secedo_variant_tabix_stats(secedo_variant_tabix_info *out);
 
+/* ---- Per-cell allele counts at the called variants (cell x site matrices) ------------------------------------------
+ *
+ * Opt-in, process-wide like the VCF output: secedo_variant_set_allele_counts, else the environment
+ * SECEDO_ALLELE_COUNTS=none|all|cluster (unset or empty: none; any other value is SECEDO_E_INVALID_ARG from the
+ * file-writing calls). With NONE nothing below runs and no file is added.
+ *
+ * A SITE is a locus with at least one call record (ALL), or with at least one SECEDO_VARIANT_CLUSTER record (CLUSTER);
+ * sites are numbered in ascending locus order. Each has two 4-bit base masks (bit b = base b, A,C,G,T = 0..3):
+ *   Rf = the bits of {ref & 7, ref >> 3} that are 0..3 (an N adds nothing)
+ *   G  = the OR, over all records of the locus whatever their kind, of the bits of {genotype & 7, genotype >> 3}
+ *   alt_mask = G & ~Rf, ref_mask = Rf; where that alt_mask is 0 (the calls only lose an allele of a heterozygous
+ *   reference: diploid FASTA only) alt_mask = G and ref_mask = Rf & ~G. ref_mask may be 0, alt_mask never is.
+ * For site s and group (cell) g, over the entries of the locus with that group id: ad = entries whose base is in
+ * alt_mask, rd = those in ref_mask, oth = the rest, dp = ad + rd. A pair (s, g) exists when ad + rd + oth > 0; pairs
+ * are ordered by s, then g. The entries of a locus need not be sorted by group, and a group may occur many times.
+ *
+ * The files, under <out_dir>/allele_counts/ (the layout cellsnp-lite writes and vireo / cardelino read; none of these
+ * tools was run against them: the contract is the bytes stated here):
+ *   cellSNP.tag.AD.mtx, cellSNP.tag.DP.mtx, cellSNP.tag.OTH.mtx   each exactly
+ *       "%%MatrixMarket matrix coordinate integer general\n%\n<n_sites>\t<n_cells>\t<nnz>\n" and then
+ *       "<site>\t<cell>\t<value>\n" per pair with value > 0, 1-based, site then cell ascending; n_cells = n
+ *   cellSNP.base.vcf   "##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n", then per site
+ *       "CHROM\tPOS\t.\tREF\tALT\t.\tPASS\tAD=<sum ad>;DP=<sum dp>;OTH=<sum oth>\n": CHROM as the VCF writer names it,
+ *       REF and ALT the masks' letters in ACGT order joined by ',', REF 'N' for an empty ref_mask. A REF of two
+ *       letters (heterozygous reference, diploid FASTA only) is not strict VCF.
+ *   cellSNP.samples.tsv   one name per line: cell_<i> (0-based group id), or the names of secedo_variant_set_cell_names
+ * Under SECEDO_VCF_BGZF the matrices and the VCF are .mtx.gz / .vcf.gz (BGZF, the same bytes once inflated; only
+ * compressed bytes are downloaded); samples.tsv is always plain. The text is formatted on the GPU on both outputs, in
+ * ranges of sites of at most SECEDO_ALLELE_BATCH_BYTES bytes of text (default 256 MiB, at least one site; the text
+ * never depends on it; under BGZF the member cuts follow the ranges). */
+#define SECEDO_ALLELE_NONE 0
+#define SECEDO_ALLELE_ALL 1
+#define SECEDO_ALLELE_CLUSTER 2
+
+/* Process-wide. set: SECEDO_E_INVALID_ARG for another value; get: the selection set, else the environment's, else NONE
+ * (a negative SECEDO_E_* for an unknown value of SECEDO_ALLELE_COUNTS). */
+int secedo_variant_set_allele_counts(int selection);
+int secedo_variant_get_allele_counts(void);
+
+/* Process-wide: the n lines of cellSNP.samples.tsv (copied); n = 0 returns to cell_<i>. A name that is empty or holds
+ * a tab or a line break is SECEDO_E_INVALID_ARG. A count other than the length of `clusters` makes the file-writing
+ * calls fail with SECEDO_E_INVALID_ARG while a selection is on. The _file variant reads one name per line. */
+int secedo_variant_set_cell_names(const char *const *names, uint32_t n);
+int secedo_variant_set_cell_names_file(const char *path);
+
+/* One (site, group) pair. */
+typedef struct secedo_allele_pair {
+    uint32_t site;   /* 0-based */
+    uint32_t group;  /* 0-based */
+    uint32_t ad, rd, oth;
+} secedo_allele_pair;
+
+/* Host only (no GPU needed). The sites of records[n_records] (locus ascending, each < n_loci: checked) under
+ * `selection` (ALL or CLUSTER): site_locus / ref_mask / alt_mask[capacity] and *n_sites (SECEDO_E_LIMIT when more than
+ * capacity: the required count in *n_sites, nothing written). */
+int secedo_variant_allele_masks(const secedo_variant_record *records, uint32_t n_records, const uint8_t *locus_ref,
+                                uint32_t n_loci, int selection, uint32_t *site_locus, uint8_t *ref_mask,
+                                uint8_t *alt_mask, uint32_t capacity, uint32_t *n_sites);
+
+/* The counts alone, on a flat pileup resident in HBM: host records as secedo_variant_calls_device returns them,
+ * d_locus_ref[n_loci] in HBM. Out (host): the sites as secedo_variant_allele_masks gives them, site_totals
+ * [3 * site_capacity] = the sums of ad, rd, oth per site, pairs[pair_capacity] in (site, group) order. SECEDO_E_LIMIT
+ * when either capacity is too small: the required counts in *n_sites and *n_pairs, nothing written. A group id >=
+ * n_cells is SECEDO_E_INVALID_ARG. Sets secedo_variant_allele_stats. Synchronises `stream`. */
+int secedo_variant_allele_counts_device(int device_id, const uint64_t *d_locus_entry_off, const uint16_t *d_id_base16,
+                                        const uint32_t *d_id_base32, uint32_t n_loci,
+                                        const secedo_variant_record *records, uint32_t n_records,
+                                        const uint8_t *d_locus_ref, uint32_t n_cells, int selection,
+                                        uint32_t *site_locus, uint8_t *ref_mask, uint8_t *alt_mask,
+                                        uint32_t *site_totals, uint32_t site_capacity, uint32_t *n_sites,
+                                        secedo_allele_pair *pairs, uint64_t pair_capacity, uint64_t *n_pairs,
+                                        void *stream);
+
+/* What the allele counting of the last file-writing call of this thread (or secedo_variant_allele_counts_device) did;
+ * all zero after a file-writing call under NONE. Times in ms, host wall clock unless said otherwise. */
+typedef struct secedo_variant_allele_info {
+    uint32_t selection;         /* SECEDO_ALLELE_* */
+    uint32_t output;            /* SECEDO_VCF_* of the files; 0 for the counts alone */
+    uint64_t sites;
+    uint64_t deep_sites;        /* of those, the sites with more than 128 entries (the sorted route) */
+    uint64_t entries_read;      /* pileup entries of the sites */
+    uint64_t pairs;
+    uint64_t nnz_ad, nnz_dp, nnz_oth;
+    uint64_t text_bytes;        /* the four texts */
+    uint64_t compressed_bytes;  /* BGZF: the four .gz files; PLAIN: 0 */
+    uint64_t ranges;            /* ranges of sites the formatter ran in */
+    double count_ms;            /* sites, counts, scans and pairs, with their read-backs */
+    double format_ms;           /* the formatter's kernels and the download of the file offsets */
+    double deflate_ms;          /* BGZF: the encoder */
+    double download_ms;         /* the text (PLAIN) or the compressed bytes (BGZF) down */
+    double write_ms;            /* the files */
+    double count_kernel_ms;     /* the site, count and write kernels alone (device events), included in count_ms */
+} secedo_variant_allele_info;
+int secedo_variant_allele_stats(secedo_variant_allele_info *out);
+
 /* The drop-in: variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir)
  * on a host flat pileup. Writes cluster_<i>.vcf for i = 0..max(clusters), common.vcf, an empty `variant` and
  * `scores` under out_dir (created), as the reference does (the .vcf files as .vcf.gz under SECEDO_VCF_BGZF, above);
- * n == 0 writes nothing. times may be NULL. */
+ * n == 0 writes nothing. times may be NULL. Under SECEDO_ALLELE_ALL / _CLUSTER also out_dir/allele_counts/ (above),
+ * after the other files; its time is in secedo_variant_allele_stats, not in `times`. */
 int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
                            const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint16_t *id_base16,
                            const uint32_t *id_base32, const uint16_t *clusters, uint32_t n,

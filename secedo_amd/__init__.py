@@ -12,9 +12,10 @@ from .pileup_reader import get_grouping, read_pileup  # noqa: F401,E402
 from .spectral import laplacian, smallest_eigenpairs  # noqa: F401,E402
 from .em import expectation_maximization  # noqa: F401,E402
 from .cluster import divide_cluster, divide_cluster_resident, spectral_clustering  # noqa: F401,E402
-from .variant import (bgzf_deflate, fasta_stats, get_fasta_route, get_vcf_index, get_vcf_output,  # noqa: F401,E402
-                      reference_genotypes, set_fasta_route, set_vcf_index, set_vcf_output, tabix_build, tabix_stats,
-                      variant_calling, variant_calling_resident, variant_calls, vcf_stats)
+from .variant import (allele_counts, allele_masks, allele_stats, bgzf_deflate, fasta_stats,  # noqa: F401,E402
+                      get_allele_counts, get_fasta_route, get_vcf_index, get_vcf_output, reference_genotypes,
+                      set_allele_counts, set_cell_names, set_fasta_route, set_vcf_index, set_vcf_output, tabix_build,
+                      tabix_stats, variant_calling, variant_calling_resident, variant_calls, vcf_stats)
 from .bam_pileup import (bam_barcodes, bam_index_build, bam_index_ranges, bam_index_stats, bam_route_stats,  # noqa: F401,E402
                          bam_scan, bam_select_stats, bgzf_inflate, pileup_bams, pileup_bams_resident, set_index,
                          split_clusters, split_rg_stats, split_select_stats, split_stats)

@@ -9,6 +9,7 @@
 // the device route of the same results is fasta_device.cpp.
 #include "secedo_variant.h"
 #include "secedo_simmat.h"
+#include "allele_output.hpp"
 #include "fasta_source.hpp"
 #include "host_util.hpp"
 #include "bgzf_deflate_kernels.hpp"
@@ -481,6 +482,10 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
     if (index == SECEDO_VCF_INDEX_TBI && !bgzf)
         return fail(SECEDO_E_INVALID_ARG, "vcf_index tbi indexes the compressed output only: add --vcf_output bgzf "
                                           "(SECEDO_VCF=bgzf, secedo_variant_set_vcf_output)");
+    int allele = SECEDO_ALLELE_NONE;
+    SECEDO_CALL(secedo::allele::selection_kind(&allele));
+    secedo::allele::info() = secedo_variant_allele_info{};
+    if (allele != SECEDO_ALLELE_NONE) SECEDO_CALL(secedo::allele::check_cell_names(n));
     std::vector<uint8_t> locus_ref(bgzf ? 0 : n_loci);
     std::vector<uint32_t> chr_end(n_chr);
     Buf b_ref, b_cl, b_mm, b_loci, b_pos;
@@ -521,6 +526,17 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
     }
     t.write_ms = ms_lap(t0);
     if (times) *times = t;
+    if (allele != SECEDO_ALLELE_NONE) {  // its own stage, timed by secedo_variant_allele_stats
+        if (!d_locus_pos) {  // a host pileup under the plain output: the formatter reads the positions in HBM
+            SECEDO_TRY(b_pos.alloc((size_t)n_loci * 4));
+            if (n_loci) SECEDO_TRY(hipMemcpyAsync(b_pos.p, locus_pos, (size_t)n_loci * 4, hipMemcpyHostToDevice, s));
+            d_locus_pos = b_pos.as<uint32_t>();
+        }
+        const secedo::allele::Pileup pileup{d_locus_entry_off, d_id_base16, d_id_base32, n};
+        SECEDO_CALL(secedo::allele::write_outputs(out_dir, allele, bgzf, pileup,
+                                                  calls.d_records.as<secedo_variant_record>(), calls.total,
+                                                  b_ref.as<uint8_t>(), d_chr_locus_off, n_chr, d_locus_pos, s));
+    }
     return SECEDO_OK;
 }
 
@@ -529,6 +545,8 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
 int begin_calling(uint32_t n, const char *reference_genome, const char *out_dir, bool *done) {
     *done = n == 0;
     if (*done) return SECEDO_OK;
+    int allele = SECEDO_ALLELE_NONE;  // an unknown SECEDO_ALLELE_COUNTS is refused before anything is made
+    SECEDO_CALL(secedo::allele::selection_kind(&allele));
     if (!out_dir || !reference_genome) return fail(SECEDO_E_INVALID_ARG, "null path");
     std::error_code ec;
     std::filesystem::create_directories(out_dir, ec);

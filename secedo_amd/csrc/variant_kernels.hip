@@ -37,6 +37,7 @@
 //     when all_same holds, common.vcf gets cluster 0's genotype with the pooled counts.
 //   * mismatches need the cluster's coverage > 9 and are counted only at loci that are not all_same.
 #include "variant_kernels.hpp"
+#include "text_sink.hpp"
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -328,27 +329,10 @@ uint32_t grid_for(uint32_t n_ranges) { return (n_ranges + WAVES - 1) / WAVES; }
 // vcf_output.cpp restated. A record's lines go through a sink, once to count their bytes and once to store them, so
 // the length a line was given room for is the length it has.
 
-struct CountSink {
-    uint32_t n = 0;
-    __device__ void put(char) { ++n; }
-};
-struct ByteSink {
-    uint8_t *p;
-    __device__ void put(char c) { *p++ = uint8_t(c); }
-};
-
-template <class S>
-__device__ void put_str(S &s, const char *t) {
-    for (; *t; ++t) s.put(*t);
-}
-
-// std::to_string of an unsigned: decimal, no padding
-template <class S>
-__device__ void put_uint(S &s, uint32_t v) {
-    uint32_t pow = 1;
-    while (v / pow >= 10) pow *= 10;  // v / pow < 10 is reached before pow * 10 could overflow
-    for (; pow; pow /= 10) s.put(char('0' + (v / pow) % 10));
-}
+using text::ByteSink;  // text_sink.hpp
+using text::CountSink;
+using text::put_str;
+using text::put_uint;
 
 __device__ __forceinline__ char base_char(uint32_t b) { return b < 6 ? "ACGTNN"[b] : 'N'; }
 

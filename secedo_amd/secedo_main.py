@@ -12,7 +12,10 @@ environment SECEDO_FASTA, else host) says where its parse and per-locus gather r
 --vcf_output plain|bgzf (default: the environment SECEDO_VCF, else plain) says whether the VCF files are written as
 text by the host or as bgzip-compressed .vcf.gz, formatted and deflated on the GPU. --vcf_index none|tbi (default: the
 environment SECEDO_VCF_INDEX, else none) adds <file>.vcf.gz.tbi, the tabix index, beside each .vcf.gz; it needs
---vcf_output bgzf.
+--vcf_output bgzf. --allele_counts none|all|cluster (default: the environment SECEDO_ALLELE_COUNTS, else none) adds
+<-o>/allele_counts/: the per-cell alternate / total / other read counts at the called variants as sparse matrices
+(cellSNP.tag.AD.mtx, .DP.mtx, .OTH.mtx), their sites (cellSNP.base.vcf) and cells (cellSNP.samples.tsv, the names from
+--cell_names <file> or cell_<i>); it needs --reference_genome.
 """
 from __future__ import annotations
 
@@ -52,6 +55,8 @@ FLAGS: Dict[str, Tuple[str, object]] = {
     "fasta_route": ("str", ""),
     "vcf_output": ("str", ""),
     "vcf_index": ("str", ""),
+    "allele_counts": ("str", ""),
+    "cell_names": ("str", ""),
     "clustering": ("str", ""),
     "compute_read_stats": ("bool", False),
     "num_threads": ("uint", 8),
@@ -77,7 +82,12 @@ def usage() -> str:
               "--vcf_output plain|bgzf: cluster_<i>.vcf / common.vcf as text, or as .vcf.gz compressed on the GPU "
               "(default: SECEDO_VCF, else plain).",
               "--vcf_index none|tbi: with --vcf_output bgzf, a tabix index <file>.vcf.gz.tbi beside each file "
-              "(default: SECEDO_VCF_INDEX, else none)."]
+              "(default: SECEDO_VCF_INDEX, else none).",
+              "--allele_counts none|all|cluster: with --reference_genome, per-cell allele counts at the called variants "
+              "under <-o>/allele_counts/ (sites x cells matrices AD, DP, OTH as Matrix Market, the sites as a VCF, the "
+              "cells as a list); all: every locus with a call, cluster: the loci where clusters differ (default: "
+              "SECEDO_ALLELE_COUNTS, else none).",
+              "--cell_names <file>: one name per line for cellSNP.samples.tsv (default: cell_<i>)."]
     return "\n".join(lines)
 
 
@@ -154,6 +164,12 @@ def validate(f: Flags) -> None:
         raise UsageError("Invalid value for --vcf_index: %s.\nShould be one of none, tbi" % f.vcf_index)
     if f.vcf_index == "tbi" and (f.vcf_output or os.environ.get("SECEDO_VCF") or "plain") != "bgzf":
         raise UsageError("--vcf_index tbi indexes the compressed output only: add --vcf_output bgzf")
+    if f.allele_counts not in ("", "none", "all", "cluster"):
+        raise UsageError("Invalid value for --allele_counts: %s.\nShould be one of none, all, cluster" % f.allele_counts)
+    if f.allele_counts in ("all", "cluster") and not f.reference_genome:
+        raise UsageError("--allele_counts counts at the called variants: add --reference_genome")
+    if f.cell_names and not os.path.exists(f.cell_names):
+        raise UsageError("Cannot find cell names file: " + f.cell_names)
     if not 1 <= f.tumor_purity <= 5:
         raise UsageError("Invalid value for --tumor_purity: %d.\nShould be 1,2,3,4, or 5" % f.tumor_purity)
     if f.arma_kmeans and f.clustering_type != "FIEDLER":
@@ -340,7 +356,7 @@ def run(plan: Plan) -> int:
     from . import SimilarityMatrixPlan
     from .cluster import divide_cluster_resident
     from .pileup_reader import get_grouping
-    from .variant import fasta_stats, tabix_stats, variant_calling_resident, vcf_stats
+    from .variant import allele_stats, fasta_stats, tabix_stats, variant_calling_resident, vcf_stats
 
     f = plan.flags
     t0 = time.perf_counter()
@@ -387,7 +403,9 @@ def run(plan: Plan) -> int:
             _log(f, "Performing variant calling against %s" % f.reference_genome)
             vc_times = variant_calling_resident(sm, res, clusters, f.reference_genome, f.map_file, 1e-3,
                                                 f.seq_error_rate, f.o, fasta_route=f.fasta_route or None,
-                                                vcf_output=f.vcf_output or None, vcf_index=f.vcf_index or None)
+                                                vcf_output=f.vcf_output or None, vcf_index=f.vcf_index or None,
+                                                allele_counts=f.allele_counts or None,
+                                                cell_names=f.cell_names or None)
             fs = fasta_stats()
             vc_times["fasta"] = "%s on %s" % (fs["kind"], fs["route"])
             if fs["route"] == "device":  # the device route's split; the three overlap
@@ -406,6 +424,13 @@ def run(plan: Plan) -> int:
                     ts["files"], ts["data_lines"], ts["chunks"], ts["index_bytes"], ts["compressed_bytes"])
                 vc_times.update(tbi_pass_ms=ts["pass_ms"], tbi_build_ms=ts["build_ms"],
                                 tbi_deflate_ms=ts["deflate_ms"], tbi_write_ms=ts["write_ms"])
+            als = allele_stats()
+            if als["selection"] != "none":
+                vc_times["alleles"] = "%s, %d sites, %d pairs, %d bytes of text in %d ranges" % (
+                    als["selection"], als["sites"], als["pairs"], als["text_bytes"], als["ranges"])
+                vc_times.update(allele_count_ms=als["count_ms"], allele_format_ms=als["format_ms"],
+                                allele_deflate_ms=als["deflate_ms"], allele_download_ms=als["download_ms"],
+                                allele_write_ms=als["write_ms"])
         else:
             _log(f, "Skipping variant calling, because no reference genome was provided")
         t_end = time.perf_counter()

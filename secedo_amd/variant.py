@@ -23,6 +23,14 @@ functions make the bgzf output also write ``<file>.vcf.gz.tbi``, the tabix index
 over the text where the formatter left it (secedo_amd/csrc/tabix_kernels.hip). ``tabix_build(files)`` indexes
 bgzip-compressed VCFs that exist: their compressed bytes are inflated and indexed on the GPU, many small files to a
 batch. Both give the same bytes for the same file; ``tabix_stats()`` says what the last of either did.
+
+``set_allele_counts("all" | "cluster")``, the environment ``SECEDO_ALLELE_COUNTS`` or the ``allele_counts`` keyword of
+the calling functions add ``<out_dir>/allele_counts/``: the sparse sites x cells matrices of alternate-allele, total and
+other read counts at the called variants (``cellSNP.tag.AD.mtx``, ``.DP.mtx``, ``.OTH.mtx``), the sites as
+``cellSNP.base.vcf`` and the cells as ``cellSNP.samples.tsv`` (``cell_names``: a list or a file of names), counted and
+formatted on the GPU (secedo_amd/csrc/allele_kernels.hip) and compressed to ``.gz`` under the bgzf output. "all" takes
+every locus with a call, "cluster" the loci where clusters differ. ``allele_masks`` (no GPU) and ``allele_counts`` give
+the sites and the (site, cell) pairs as arrays; ``allele_stats()`` says what the last call did. Off by default.
 """
 from __future__ import annotations
 
@@ -79,7 +87,19 @@ class TabixInfo(C.Structure):
                 ("build_ms", C.c_double), ("deflate_ms", C.c_double), ("write_ms", C.c_double)]
 
 
+class AlleleInfo(C.Structure):
+    _fields_ = [("selection", C.c_uint32), ("output", C.c_uint32), ("sites", C.c_uint64), ("deep_sites", C.c_uint64),
+                ("entries_read", C.c_uint64), ("pairs", C.c_uint64), ("nnz_ad", C.c_uint64), ("nnz_dp", C.c_uint64),
+                ("nnz_oth", C.c_uint64), ("text_bytes", C.c_uint64), ("compressed_bytes", C.c_uint64),
+                ("ranges", C.c_uint64), ("count_ms", C.c_double), ("format_ms", C.c_double),
+                ("deflate_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double),
+                ("count_kernel_ms", C.c_double)]
+
+
 FASTA_ROUTES = ("host", "device")
+ALLELE_COUNTS = ("none", "all", "cluster")
+PAIR_DTYPE = np.dtype([("site", np.uint32), ("group", np.uint32), ("ad", np.uint32), ("rd", np.uint32),
+                       ("oth", np.uint32)])
 VCF_OUTPUTS = ("plain", "bgzf")
 VCF_INDEXES = ("none", "tbi")
 BGZF_CUT = 0xFF00  # text bytes per BGZF member at the most
@@ -109,6 +129,16 @@ SIGNATURES = {
     "secedo_variant_format_device": (C.c_int, [C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32,
                                                C.c_uint32, C.c_char_p, _vp, _vp, C.c_uint64, _vp]),
     "secedo_variant_bgzf_deflate": (C.c_int, [C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
+    "secedo_variant_set_allele_counts": (C.c_int, [C.c_int]),
+    "secedo_variant_get_allele_counts": (C.c_int, []),
+    "secedo_variant_set_cell_names": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint32]),
+    "secedo_variant_set_cell_names_file": (C.c_int, [C.c_char_p]),
+    "secedo_variant_allele_masks": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_uint32,
+                                              _u32p]),
+    "secedo_variant_allele_counts_device": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp,
+                                                      C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, C.c_uint32, _u32p, _vp,
+                                                      C.c_uint64, _u64p, _vp]),
+    "secedo_variant_allele_stats": (C.c_int, [C.POINTER(AlleleInfo)]),
     "secedo_variant_is_diploid": (C.c_int, [C.c_char_p]),
     "secedo_variant_read_chromosome": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "secedo_variant_read_map": (C.c_int, [C.c_char_p, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _u32p]),
@@ -250,6 +280,117 @@ def _index(index):
         yield
     finally:
         set_vcf_index(before)
+
+
+def set_allele_counts(selection):
+    """The process-wide selection of the per-cell allele counts: "none" (the default: nothing is added), "all" (every
+    locus with a call) or "cluster" (the loci where clusters differ); see the module docstring."""
+    if selection not in ALLELE_COUNTS:
+        raise ValueError("allele counts must be 'none', 'all' or 'cluster', not %r" % (selection,))
+    check(lib().secedo_variant_set_allele_counts(ALLELE_COUNTS.index(selection)))
+
+
+def get_allele_counts() -> str:
+    rc = lib().secedo_variant_get_allele_counts()
+    if rc < 0:
+        check(rc)
+    return ALLELE_COUNTS[rc]
+
+
+def set_cell_names(names):
+    """The lines of cellSNP.samples.tsv: a list of names, the path of a file with one name per line, or None for
+    cell_<i>. Their count must be the length of `clusters` of the file-writing call."""
+    if names is None:
+        check(lib().secedo_variant_set_cell_names(None, 0))
+    elif isinstance(names, (str, bytes, os.PathLike)):
+        check(lib().secedo_variant_set_cell_names_file(_b(names)))
+    else:
+        enc = [str(x).encode() for x in names]
+        check(lib().secedo_variant_set_cell_names((C.c_char_p * max(len(enc), 1))(*enc), len(enc)))
+
+
+@contextlib.contextmanager
+def _alleles(selection, cell_names):
+    """A scoped override of the allele-count selection, as _route is of the FASTA route; cell names given for the call
+    are dropped after it."""
+    before = None if selection is None else get_allele_counts()
+    if selection is not None:
+        set_allele_counts(selection)
+    try:
+        if cell_names is not None:
+            set_cell_names(cell_names)
+        yield
+    finally:
+        if cell_names is not None:
+            set_cell_names(None)
+        if before is not None:
+            set_allele_counts(before)
+
+
+def allele_stats() -> dict:
+    """What the allele counting of the last file-writing call of this thread (or allele_counts) did
+    (secedo_variant_allele_info), selection and output as words. All zero ("none") when it was off."""
+    info = AlleleInfo()
+    check(lib().secedo_variant_allele_stats(C.byref(info)))
+    out = {name: getattr(info, name) for name, _ in AlleleInfo._fields_}
+    out["selection"], out["output"] = ALLELE_COUNTS[info.selection], VCF_OUTPUTS[info.output]
+    return out
+
+
+def _selection(sites):
+    if sites not in ALLELE_COUNTS[1:]:
+        raise ValueError("sites must be 'all' or 'cluster', not %r" % (sites,))
+    return ALLELE_COUNTS.index(sites)
+
+
+def allele_masks(records, locus_ref, n_loci, sites="all") -> dict:
+    """The sites of `records` (RECORD_DTYPE, write order) and their base masks, on the host (no GPU): {"site_locus"
+    u32[S], "ref_mask" u8[S], "alt_mask" u8[S]}; bit b of a mask = base b, A,C,G,T = 0..3."""
+    rec = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    ref = np.ascontiguousarray(locus_ref, dtype=np.uint8)
+    if len(ref) < n_loci:
+        raise ValueError("locus_ref is shorter than n_loci")
+    cap = max(len(rec), 1)
+    loc, rm, am = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+    n = C.c_uint32(0)
+    check(lib().secedo_variant_allele_masks(_lib.ptr(rec) if len(rec) else None, len(rec),
+                                            _lib.ptr(ref) if len(ref) else None, n_loci, _selection(sites),
+                                            _lib.ptr(loc), _lib.ptr(rm), _lib.ptr(am), cap, C.byref(n)))
+    return {"site_locus": loc[:n.value], "ref_mask": rm[:n.value], "alt_mask": am[:n.value]}
+
+
+def allele_counts(pos_data, records, locus_ref, n_cells, sites="all", device=0) -> dict:
+    """The per-cell allele counts alone, on the GPU: allele_masks' arrays, "totals" u32[S, 3] (the sums of ad, rd, oth
+    per site) and "pairs" (PAIR_DTYPE, site then group ascending: the (site, cell) pairs with at least one read)."""
+    import torch
+    p, b16, b32 = _flat(pos_data)
+    rec = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    dev = "cuda:%d" % device
+    d_off = _dev(p.locus_entry_off, np.int64, dev)
+    d_idb = _dev(b16, np.int16, dev) if b16 is not None else _dev(b32, np.int32, dev)
+    d_ref = _dev(np.ascontiguousarray(locus_ref, dtype=np.uint8), np.uint8, dev)
+    idb = C.c_void_p(d_idb.data_ptr())
+    cap = max(len(rec), 1)
+    loc, rm, am = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+    tot = np.zeros((cap, 3), np.uint32)
+    pairs = np.zeros(1, dtype=PAIR_DTYPE)
+    n_sites, n_pairs = C.c_uint32(0), C.c_uint64(0)
+    for capacity in (0, None):  # the first call asks for the number of pairs
+        if capacity is None:
+            capacity = n_pairs.value
+            pairs = np.zeros(max(capacity, 1), dtype=PAIR_DTYPE)
+        rc = lib().secedo_variant_allele_counts_device(
+            device, C.c_void_p(d_off.data_ptr()), idb if b16 is not None else None, None if b16 is not None else idb,
+            p.n_loci, _lib.ptr(rec) if len(rec) else None, len(rec), C.c_void_p(d_ref.data_ptr()), n_cells,
+            _selection(sites), _lib.ptr(loc), _lib.ptr(rm), _lib.ptr(am), _lib.ptr(tot), cap, C.byref(n_sites),
+            _lib.ptr(pairs), capacity, C.byref(n_pairs), _stream(device))
+        if rc != _lib.E_LIMIT:
+            break
+    check(rc)
+    torch.cuda.synchronize(device)
+    s = n_sites.value
+    return {"site_locus": loc[:s], "ref_mask": rm[:s], "alt_mask": am[:s], "totals": tot[:s],
+            "pairs": pairs[:n_pairs.value]}
 
 
 def tabix_stats() -> dict:
@@ -495,16 +636,18 @@ def _times(t):
 
 
 def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                    out_dir="variant_calling", device=0, fasta_route=None, vcf_output=None, vcf_index=None):
+                    out_dir="variant_calling", device=0, fasta_route=None, vcf_output=None, vcf_index=None,
+                    allele_counts=None, cell_names=None):
     """variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir): writes
     cluster_<i>.vcf, common.vcf, variant and scores under out_dir as the reference does. fasta_route ("host",
     "device"; None: the setting) overrides the FASTA route for this call, vcf_output ("plain", "bgzf"; None: the
     setting) the kind of VCF files, vcf_index ("none", "tbi"; None: the setting) whether the bgzf files get a tabix
-    index. -> step times (ms)."""
+    index, allele_counts ("none", "all", "cluster"; None: the setting) whether out_dir/allele_counts/ is written, with
+    cell_names (a list or a file; None: the names set, else cell_<i>) in its samples file. -> step times (ms)."""
     p, b16, b32 = _flat(pos_data)
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     t = Times()
-    with _route(fasta_route), _output(vcf_output), _index(vcf_index):
+    with _route(fasta_route), _output(vcf_output), _index(vcf_index), _alleles(allele_counts, cell_names):
         check(lib().secedo_variant_calling(device, _lib.ptr(p.chr_locus_off), p.n_chr, _lib.ptr(p.locus_pos),
                                            _lib.ptr(p.locus_entry_off), _lib.ptr(b16), _lib.ptr(b32), _lib.ptr(cl),
                                            len(cl), _b(reference_genome), _b(map_file), hetero_prior, theta,
@@ -513,14 +656,15 @@ def variant_calling(pos_data, clusters, reference_genome, map_file="", hetero_pr
 
 
 def variant_calling_resident(plan, res, clusters, reference_genome, map_file="", hetero_prior=1e-3, theta=0.01,
-                             out_dir="variant_calling", fasta_route=None, vcf_output=None, vcf_index=None):
+                             out_dir="variant_calling", fasta_route=None, vcf_output=None, vcf_index=None,
+                             allele_counts=None, cell_names=None):
     """variant_calling on the pileup `res` resident in HBM (SimilarityMatrixPlan.upload, as divide_cluster_resident
-    takes it), in the plan's current stream. fasta_route, vcf_output and vcf_index as in variant_calling. -> step times
-    (ms)."""
+    takes it), in the plan's current stream. fasta_route, vcf_output, vcf_index, allele_counts and cell_names as in
+    variant_calling. -> step times (ms)."""
     cl = np.ascontiguousarray(clusters, dtype=np.uint16)
     idb = C.c_void_p(res["idb"].data_ptr())
     t = Times()
-    with _route(fasta_route), _output(vcf_output), _index(vcf_index):
+    with _route(fasta_route), _output(vcf_output), _index(vcf_index), _alleles(allele_counts, cell_names):
         check(lib().secedo_variant_calling_device(
             plan.device, C.c_void_p(res["chr"].data_ptr()), res["n_chr"], C.c_void_p(res["pos"].data_ptr()),
             C.c_void_p(res["off"].data_ptr()), idb if res["idb_is16"] else None, None if res["idb_is16"] else idb,
