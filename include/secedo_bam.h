@@ -415,6 +415,92 @@ int secedo_bam_split_clusters_select(const char *const *bam_files, uint32_t n_fi
                                      uint32_t exclude, int duplicates, secedo_bam_select_info *select_info);
 int secedo_bam_split_select_stats(secedo_bam_select_info *out);
 
+/* ---- Per-cell read depth in fixed genomic bins: the bins x cells count matrix that copy-number tools
+ * start from (HMMcopy's readCounter, Ginkgo, SCOPE), counted on the GPU from the inputs of the pileup calls (BAM, SAM,
+ * bgzipped SAM, per cell or multiplexed by tag, either inflate route, through .bai or not). No outside tool was run
+ * against the files; the contract is what follows, byte for byte.
+ *
+ * Bins. Chromosome id c is @SQ index c. LN_c and the name come from the first input's reference list; all inputs must
+ * carry the same list (SECEDO_E_INVALID_ARG in the words of the split calls). With bin_size S >= 1 chromosome c has
+ * ceil(LN_c / S) bins and bin b covers [b S, min((b + 1) S, LN_c)). Global bin numbers run over the requested
+ * chromosomes in ascending id, whatever order they were given in. S == 0 is SECEDO_E_INVALID_ARG, more than 2^32 - 1
+ * bins in total SECEDO_E_LIMIT, each with a reason.
+ *
+ * Cells. As in secedo_bam_split_clusters: the file index, or with tag / barcodes the index of the record's barcode in
+ * the list. Names (depth.samples.tsv, depth.cells.tsv): cell_names (n_names = the cell count), else the barcode, else
+ * the file's base name without .bam / .sam / .sam.gz; a name that is empty or holds a tab or a line break is
+ * SECEDO_E_INVALID_ARG.
+ *
+ * Selection, in this order, from this call's arguments only (the process-wide secedo_bam_set_read_filter and
+ * secedo_bam_set_duplicates and their environment variables have no effect): 1. the barcode; 2. the flag masks:
+ * (flag & require) == require && (flag & exclude) == 0, `require` counted first; 3. duplicates (SECEDO_BAM_DUPLICATES_KEEP
+ * or _REMOVE): per cell and chromosome exactly as secedo_bam_split_clusters_select's rule 2; 4. MapQuality >=
+ * min_map_quality; 5. range: a record whose Position is < 0 or >= LN_c is dropped and counted as out_of_range.
+ *
+ * What is counted. SECEDO_BAM_DEPTH_READS: each surviving record adds 1 to the bin of its 0-based Position.
+ * SECEDO_BAM_DEPTH_BASES: each surviving record adds, to every bin it touches, the number of reference positions in
+ * that bin that an M, = or X op of its CIGAR covers; D, N, P, I, S and H add nothing, D and N advance the position,
+ * positions >= LN_c add nothing, and a record without a CIGAR adds nothing but is still a counted record (the mean
+ * depth times the width that `mosdepth --by` reports, kept as an integer). Values are uint64 everywhere; only integer
+ * sums exist, so no result depends on an execution order and two runs are byte-identical.
+ *
+ * Files, under <out_dir>/depth/ (created when missing), only with out_dir != NULL; out_dir must be a directory. An
+ * existing output is refused unless overwrite; every file is written under <name>.tmp.<pid> and renamed when all are
+ * complete, and a failed call leaves nothing behind.
+ *   depth.bins.bed      "<name>\t<start>\t<end>\n" per global bin, 0-based half-open
+ *   depth.counts.mtx    "%%MatrixMarket matrix coordinate integer general\n%\n<n_bins>\t<n_cells>\t<nnz>\n", then
+ *                       "<bin>\t<cell>\t<value>\n" per pair with value > 0, numbers 1-based, ordered by bin and then
+ *                       cell ascending (the convention of cellSNP.tag.*.mtx)
+ *   depth.samples.tsv   one cell name per line
+ *   depth.cells.tsv     "cell\tname\trecords\tcounted\tsum\tnonzero_bins\tmax_value\n", then one line per cell (cell
+ *                       0-based): records = the cell's records on the requested chromosomes after step 1, counted =
+ *                       those that survived all five steps, sum = the sum of the cell's values, nonzero_bins and
+ *                       max_value over the cell's pairs
+ *   depth.clusters.tsv  with a clustering only (n_clustering = the cell count, else SECEDO_E_INVALID_ARG):
+ *                       "chrom\tstart\tend\tcluster_0\t...\tcluster_<K-1>\n", K = max(clustering) + 1, then one line
+ *                       per global bin, empty ones included, with the sum over each cluster's cells; a cluster
+ *                       without cells gives a column of zeros
+ * With SECEDO_BAM_DEPTH_BGZF the .mtx and the two .tsv with per-bin or per-cell lines are BGZF files .mtx.gz /
+ * .tsv.gz that inflate to the same bytes; bins.bed and samples.tsv stay plain. The text is formatted on the GPU in
+ * ranges of at most SECEDO_DEPTH_BATCH_BYTES bytes (default 256 MiB, at least one line), which never changes a byte
+ * of text; under BGZF the member cuts follow the ranges and only compressed bytes are downloaded.
+ *
+ * The result (bins, pairs, per-cell table, cluster sums) stays on the host until the next call on this thread or
+ * secedo_bam_release; secedo_bam_depth_fetch copies it out. Chromosomes are processed one after the other with a
+ * chromosome's records resident: fewer than 2^32 records and at most 2^32 - 1 pieces (a piece is a record in `reads`
+ * mode, a (record, touched bin) in `bases` mode) per chromosome, else SECEDO_E_LIMIT. Not done: GC content and
+ * mappability per bin, normalisation, segmentation, counting templates instead of records, CG-tag CIGARs. */
+#define SECEDO_BAM_DEPTH_READS 0
+#define SECEDO_BAM_DEPTH_BASES 1
+#define SECEDO_BAM_DEPTH_PLAIN 0
+#define SECEDO_BAM_DEPTH_BGZF 1
+
+typedef struct secedo_bam_depth_info {
+    uint64_t files, cells, chromosomes, bins, clusters; /* clusters: K, 0 without a clustering */
+    uint64_t records, counted;                           /* after step 1; after all five steps */
+    uint64_t dropped_barcode, dropped_require, dropped_exclude, dropped_duplicate, dropped_mapq, out_of_range;
+    uint64_t pieces, pairs;                              /* sorted (record, bin) pieces; pairs with value > 0 */
+    uint64_t text_bytes, compressed_bytes, members, ranges; /* of the GPU-formatted files; compressed: BGZF only */
+    double order_ms, count_ms, format_ms, deflate_ms, download_ms, write_ms;
+} secedo_bam_depth_info;
+
+/* tag / barcodes: NULL for one cell per file. clustering, cell_names, out_dir: NULL for none. info may not be NULL,
+ * times may. Synchronous. */
+int secedo_bam_depth(const char *const *bam_files, uint32_t n_files, const uint32_t *chromosome_ids, uint32_t n_chr,
+                     const char tag[2], const char *const *barcodes, uint32_t n_barcodes, uint32_t bin_size, int mode,
+                     uint32_t min_map_quality, uint32_t require, uint32_t exclude, int duplicates,
+                     const uint16_t *clustering, uint32_t n_clustering, const char *const *cell_names,
+                     uint32_t n_names, const char *out_dir, int output, int overwrite, uint32_t num_threads,
+                     secedo_bam_depth_info *info, secedo_bam_times *times);
+/* Copies the last result of this thread into host buffers, any may be NULL: bin_chr / bin_start / bin_end [bins] (the
+ * chromosome id and the 0-based half-open extent of each global bin), pair_bin / pair_cell / pair_value [pairs]
+ * (0-based, in the .mtx order), cell_table [cells][5] (records, counted, sum, nonzero_bins, max_value), cluster_sums
+ * [bins][clusters]. SECEDO_E_STATE without a result. */
+int secedo_bam_depth_fetch(uint32_t *bin_chr, uint32_t *bin_start, uint32_t *bin_end, uint32_t *pair_bin,
+                           uint32_t *pair_cell, uint64_t *pair_value, uint64_t *cell_table, uint64_t *cluster_sums);
+/* the last secedo_bam_depth call of this thread, a failed one up to its failure */
+int secedo_bam_depth_stats(secedo_bam_depth_info *out);
+
 /* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
  * num_threads: inflate pool size, capped at 16 (0 = 1). */
 int secedo_bam_scan(const char *path, uint32_t num_threads, secedo_bam_scan_info *info, uint64_t *records_per_ref,
@@ -475,7 +561,7 @@ int secedo_bam_barcodes_fetch(char *values, uint64_t *value_off, uint64_t *count
 int secedo_bam_fetch(uint32_t *chr_locus_off, uint32_t *locus_pos, uint64_t *locus_entry_off, uint32_t *read_ids,
                      uint16_t *id_base16);
 
-/* Frees the device memory of the last result (that of secedo_bgzf_inflate too). */
+/* Frees the device memory of the last result (that of secedo_bgzf_inflate too) and the last secedo_bam_depth result. */
 void secedo_bam_release(void);
 
 /* Inflates any BGZF file (BAM, bgzipped SAM, ...) on the GPU, in ranges of about SECEDO_BAM_BATCH_BYTES, ISIZE and

@@ -17,7 +17,8 @@ from .variant import (allele_counts, allele_masks, allele_stats, bgzf_deflate, f
                       set_allele_counts, set_cell_names, set_fasta_route, set_vcf_index, set_vcf_output, tabix_build,
                       tabix_stats, variant_calling, variant_calling_resident, variant_calls, vcf_stats)
 from .bam_pileup import (bam_barcodes, bam_index_build, bam_index_ranges, bam_index_stats, bam_route_stats,  # noqa: F401,E402
-                         bam_scan, bam_select_stats, bgzf_inflate, pileup_bams, pileup_bams_resident, set_index,
-                         split_clusters, split_rg_stats, split_select_stats, split_stats)
+                         bam_scan, bam_select_stats, bgzf_inflate, bin_depth, depth_stats, pileup_bams,
+                         pileup_bams_resident, set_index, split_clusters, split_rg_stats, split_select_stats,
+                         split_stats)
 from .sam_flags import FLAG_NAMES, parse_flags  # noqa: F401,E402
 from .pileup_load import read_pileups_resident  # noqa: F401,E402

@@ -83,7 +83,19 @@ class SplitRgInfo(C.Structure):
                                            "removed_bytes")] + [("reserved", C.c_uint64 * 3)])
 
 
+class DepthInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("files", "cells", "chromosomes", "bins", "clusters", "records", "counted",
+                                           "dropped_barcode", "dropped_require", "dropped_exclude",
+                                           "dropped_duplicate", "dropped_mapq", "out_of_range", "pieces", "pairs",
+                                           "text_bytes", "compressed_bytes", "members", "ranges")] +
+                [(k, C.c_double) for k in ("order_ms", "count_ms", "format_ms", "deflate_ms", "download_ms",
+                                           "write_ms")])
+
+
 INFLATE_MODES = {"host": 0, "device": 1}
+DEPTH_MODES = {"reads": 0, "bases": 1}      # SECEDO_BAM_DEPTH_READS, _BASES
+DEPTH_OUTPUTS = {"plain": 0, "bgzf": 1}     # SECEDO_BAM_DEPTH_PLAIN, _BGZF
+DEPTH_DUPLICATES = {"off": 0, "remove": 1}  # SECEDO_BAM_DUPLICATES_KEEP, _REMOVE
 INDEX_MODES = {"off": 0, "auto": 1, "require": 2}
 SPLIT_DUPLICATES = {"off": 0, "remove": 1, "mark": 2}  # SECEDO_BAM_DUPLICATES_KEEP, _REMOVE, _MARK
 
@@ -135,6 +147,11 @@ SIGNATURES = {
                                                    _files_t, _u32, C.POINTER(SplitRgInfo), C.c_int, _u32, _u32,
                                                    C.c_int, C.POINTER(SelectInfo)]),
     "secedo_bam_split_select_stats": (C.c_int, [C.POINTER(SelectInfo)]),
+    "secedo_bam_depth": (C.c_int, [_files_t, _u32, _vp, _u32, C.c_char_p, _files_t, _u32, _u32, C.c_int, _u32, _u32,
+                                   _u32, C.c_int, _vp, _u32, _files_t, _u32, C.c_char_p, C.c_int, C.c_int, _u32,
+                                   C.POINTER(DepthInfo), C.POINTER(Times)]),
+    "secedo_bam_depth_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "secedo_bam_depth_stats": (C.c_int, [C.POINTER(DepthInfo)]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
@@ -493,6 +510,123 @@ def split_clusters(bam_files: Sequence[str], clustering, out_dir, chromosome_ids
     if select:  # "records" is the split's own key (records written): the filter's count goes by filter_records
         out.update(("filter_records" if k == "records" else k, v) for k, v in _select_dict(sel).items())
     return out
+
+
+def _depth_dict(info: DepthInfo) -> dict:
+    return {k: (int if ty is C.c_uint64 else float)(getattr(info, k)) for k, ty in DepthInfo._fields_}
+
+
+def depth_stats() -> dict:
+    """What the last ``bin_depth`` call on this thread did, a failed one up to its failure: files, cells, chromosomes,
+    bins, clusters, records (after the barcode step), counted (after all five steps), dropped_barcode,
+    dropped_require, dropped_exclude, dropped_duplicate, dropped_mapq, out_of_range, pieces, pairs, text_bytes,
+    compressed_bytes, members, ranges and the stage times order_ms, count_ms, format_ms, deflate_ms, download_ms,
+    write_ms."""
+    info = DepthInfo()
+    check(lib().secedo_bam_depth_stats(C.byref(info)))
+    return _depth_dict(info)
+
+
+def bin_depth(files: Sequence[str], bin_size: int, chromosome_ids: Sequence[int], out_dir=None, mode: str = "reads",
+              min_map_quality: int = 30, require_flags=None, exclude_flags=None, duplicates: str = "off",
+              cell_tag=None, cells=None, clustering=None, cell_names: Optional[Sequence[str]] = None,
+              output: str = "plain", overwrite: bool = False, times: Optional[dict] = None, *, inflate=None,
+              index=None, num_threads: int = 8) -> dict:
+    """Per-cell read depth in fixed genomic bins: the bins x cells count matrix copy-number tools start from, counted
+    on the GPU (secedo_bam_depth; the rules and the bytes of the files are in include/secedo_bam.h). ``files`` are the
+    inputs of ``pileup_bams`` (BAM, SAM, bgzipped SAM; ``inflate`` and ``index`` as there), one cell per file, or with
+    ``cell_tag`` / ``cells`` multiplexed files whose records name their cell by a barcode. Chromosome ``c`` of
+    ``chromosome_ids`` (RefIDs, any order) has ``ceil(LN_c / bin_size)`` bins; global bin numbers run over the
+    requested chromosomes in ascending id. A record is selected by, in this order, its barcode, ``require_flags`` /
+    ``exclude_flags`` (as for ``split_clusters``), ``duplicates`` ("off" or "remove": per cell and chromosome, the
+    pileup's rule), ``MapQuality >= min_map_quality`` and ``0 <= Position < LN_c``; these are this call's own, the
+    process-wide filter and duplicate settings never apply. ``mode`` "reads": each surviving record adds 1 to the bin
+    of its Position; "bases": it adds to every bin it touches the reference positions there that an M, = or X op of
+    its CIGAR covers. ``clustering`` (a sequence, or the file ``secedo_main`` writes) adds the per-cluster sums.
+    ``out_dir``: also write ``<out_dir>/depth/`` (depth.bins.bed, depth.counts.mtx, depth.samples.tsv,
+    depth.cells.tsv and with a clustering depth.clusters.tsv; ``output="bgzf"`` writes the .mtx and the two longer
+    .tsv as .gz); existing files raise unless ``overwrite``; a failed call leaves nothing behind. ``cell_names``: one
+    name per cell; None names a cell by its barcode or its file's base name.
+    -> dict of numpy arrays: bin_chrom, bin_start, bin_end [bins]; pair_bin, pair_cell (0-based, uint32), pair_value
+    (uint64) [pairs], ordered by bin and then cell; cells [n_cells, 5] uint64 (records, counted, sum, nonzero_bins,
+    max_value); cluster_sums [bins, K] uint64 (with a clustering); names (list of str); stats (``depth_stats()``).
+    ``times`` (a dict) receives the input layer's step times in ms."""
+    if mode not in DEPTH_MODES:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "mode is 'reads' or 'bases', got %r" % (mode,))
+    if output not in DEPTH_OUTPUTS:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "output is 'plain' or 'bgzf', got %r" % (output,))
+    if duplicates not in DEPTH_DUPLICATES:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "duplicates is 'off' or 'remove', got %r" % (duplicates,))
+    if not isinstance(bin_size, (int, np.integer)) or bin_size < 0 or bin_size > 0xFFFFFFFF:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "bin_size is an integer in [1, 2^32 - 1], got %r" % (bin_size,))
+    if not isinstance(min_map_quality, (int, np.integer)) or not 0 <= min_map_quality <= 255:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "min_map_quality is an integer in [0, 255], got %r"
+                               % (min_map_quality,))
+    try:
+        require, exclude = parse_filter(require_flags, exclude_flags)
+    except ValueError as e:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, str(e))
+    if isinstance(files, (str, bytes, os.PathLike)):
+        files = [files]
+    arr, n = _files(files)
+    cl = None
+    if clustering is not None:
+        if isinstance(clustering, (str, bytes, os.PathLike)):
+            try:
+                clustering = read_clustering(clustering)
+            except ValueError as e:
+                raise _lib.SecedoError(_lib.E_INVALID_ARG, str(e))
+        cl = np.asarray(clustering)
+        if cl.ndim != 1 or cl.size == 0 or not np.issubdtype(cl.dtype, np.integer) or cl.min() < 0 or cl.max() > 65535:
+            raise _lib.SecedoError(_lib.E_INVALID_ARG,
+                                   "clustering is a non-empty sequence of cluster numbers in [0, 65535]")
+        cl = np.ascontiguousarray(cl, dtype=np.uint16)
+    tag, bcs, n_bcs = _cells(cell_tag, cells)
+    ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
+    names = None if cell_names is None else [_encode(x) for x in cell_names]
+    names_arr = None if names is None else (C.c_char_p * max(len(names), 1))(*names)
+    try:
+        import torch  # noqa: F401  -- the HIP runtime torch initialises, as for the pileup calls
+    except ImportError:
+        pass
+    info, t = DepthInfo(), Times()
+    with _route(inflate, index):
+        check(lib().secedo_bam_depth(arr, n, _lib.ptr(ids) if len(ids) else None, len(ids), tag, bcs, n_bcs,
+                                     int(bin_size), DEPTH_MODES[mode], int(min_map_quality), require, exclude,
+                                     DEPTH_DUPLICATES[duplicates], _lib.ptr(cl), 0 if cl is None else len(cl),
+                                     names_arr, 0 if names is None else len(names),
+                                     None if out_dir is None else os.fsencode(str(out_dir)), DEPTH_OUTPUTS[output],
+                                     int(bool(overwrite)), num_threads, C.byref(info), C.byref(t)))
+    if times is not None:
+        times.update(_times(t))
+    n_bins, n_pairs, n_cells, k = int(info.bins), int(info.pairs), int(info.cells), int(info.clusters)
+    out = dict(bin_chrom=np.zeros(n_bins, np.uint32), bin_start=np.zeros(n_bins, np.uint32),
+               bin_end=np.zeros(n_bins, np.uint32), pair_bin=np.zeros(n_pairs, np.uint32),
+               pair_cell=np.zeros(n_pairs, np.uint32), pair_value=np.zeros(n_pairs, np.uint64),
+               cells=np.zeros((n_cells, 5), np.uint64), cluster_sums=np.zeros((n_bins, k), np.uint64))
+    check(lib().secedo_bam_depth_fetch(*[_lib.ptr(out[key]) for key in ("bin_chrom", "bin_start", "bin_end",
+                                                                        "pair_bin", "pair_cell", "pair_value",
+                                                                        "cells", "cluster_sums")]))
+    if cl is None:
+        del out["cluster_sums"]
+    if cell_names is not None:
+        out["names"] = [str(x) for x in cell_names]
+    elif cell_tag is not None:
+        out["names"] = [x.decode("utf-8", "surrogateescape") if isinstance(x, bytes) else str(x) for x in cells]
+    else:
+        out["names"] = [default_cell_name(f) for f in files]
+    out["stats"] = _depth_dict(info)
+    return out
+
+
+def default_cell_name(path) -> str:
+    """The name a per-file cell gets without ``cell_names``: the file's base name without the first of .sam.gz, .bam,
+    .sam that it ends in."""
+    base = os.path.basename(os.fspath(path))
+    for ext in (".sam.gz", ".bam", ".sam"):
+        if base.endswith(ext):
+            return base[:-len(ext)]
+    return base
 
 
 def bam_route_stats() -> dict:

@@ -4,6 +4,7 @@
 
 #include "bam_batch.hpp"
 #include "bam_kernels.hpp"
+#include "bam_split.hpp"
 #include "bgzf_members.hpp"
 #include "host_util.hpp"
 #include "secedo_bam.h"
@@ -76,6 +77,13 @@ struct FileHeader {
     bool sam = false;
 };
 int read_file_header(const std::string &path, FileHeader *h);
+
+// The reference lists of `files` (read_file_header; a SAM file's @SQ lines are its list), checked against the first
+// one's (bamsplit::refs_differ: "<path>: its reference list is not that of the first file <path>: <why>") -> *first,
+// its binary form *first_list and every file's header text (bam_split.cpp defines it; bam_depth.cpp takes the bins
+// from *first).
+int read_reference_lists(const std::vector<std::string> &files, std::vector<bamsplit::Ref> *first,
+                         std::vector<uint8_t> *first_list, std::vector<std::string> *texts);
 
 // ---- what the calls of bam_pileup.cpp and bam_split.cpp share of tag mode and of their argument checks
 
@@ -253,6 +261,8 @@ int require_bam(const std::string &path, const std::string &what);
 
 // Frees the device memory of the last secedo_bgzf_inflate result of this thread (secedo_bam_release calls it).
 void release_inflated();
+// Frees the last secedo_bam_depth result of this thread (bam_depth.cpp; secedo_bam_release calls it).
+void release_depth();
 
 }  // namespace bam_host
 }  // namespace secedo

@@ -1108,6 +1108,7 @@ void secedo_bam_release(void) {
     delete g_result;
     g_result = nullptr;
     release_inflated();
+    release_depth();
 }
 
 }  // extern "C"

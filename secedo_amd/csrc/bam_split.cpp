@@ -361,24 +361,7 @@ int make_headers(const Request &rq, std::vector<std::vector<uint8_t>> *headers) 
     std::vector<bs::Ref> first;
     std::vector<uint8_t> first_list;
     std::vector<std::string> texts;
-    for (size_t f = 0; f < rq.files.size(); ++f) {
-        FileHeader h;
-        SECEDO_CALL(read_file_header(rq.files[f], &h));
-        std::vector<bs::Ref> refs;
-        if (h.sam) refs = bs::refs_from_text(h.text);
-        else if (!bs::parse_ref_list(h.ref_list.data(), h.ref_list.size(), h.n_ref, &refs))
-            return fail(SECEDO_E_INVALID_ARG, rq.files[f] + ": truncated reference list");
-        if (f == 0) {
-            first = refs;
-            first_list = h.sam ? bs::ref_list_bytes(refs) : h.ref_list;
-        } else {
-            const std::string why = bs::refs_differ(first, refs);
-            if (!why.empty())
-                return fail(SECEDO_E_INVALID_ARG, rq.files[f] + ": its reference list is not that of the first file " +
-                                                      rq.files[0] + ": " + why);
-        }
-        texts.push_back(h.text);
-    }
+    SECEDO_CALL(read_reference_lists(rq.files, &first, &first_list, &texts));
     for (uint32_t c : rq.chr)
         if (c >= first.size())
             return fail(SECEDO_E_INVALID_ARG, "chromosome id " + std::to_string(c) + " is at or past the " +
@@ -535,6 +518,35 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
 }
 
 }  // namespace
+
+namespace secedo {
+namespace bam_host {
+
+int read_reference_lists(const std::vector<std::string> &files, std::vector<bamsplit::Ref> *first,
+                         std::vector<uint8_t> *first_list, std::vector<std::string> *texts) {
+    for (size_t f = 0; f < files.size(); ++f) {
+        FileHeader h;
+        SECEDO_CALL(read_file_header(files[f], &h));
+        std::vector<bs::Ref> refs;
+        if (h.sam) refs = bs::refs_from_text(h.text);
+        else if (!bs::parse_ref_list(h.ref_list.data(), h.ref_list.size(), h.n_ref, &refs))
+            return fail(SECEDO_E_INVALID_ARG, files[f] + ": truncated reference list");
+        if (f == 0) {
+            *first = refs;
+            *first_list = h.sam ? bs::ref_list_bytes(refs) : h.ref_list;
+        } else {
+            const std::string why = bs::refs_differ(*first, refs);
+            if (!why.empty())
+                return fail(SECEDO_E_INVALID_ARG, files[f] + ": its reference list is not that of the first file " +
+                                                      files[0] + ": " + why);
+        }
+        texts->push_back(h.text);
+    }
+    return SECEDO_OK;
+}
+
+}  // namespace bam_host
+}  // namespace secedo
 
 extern "C" {
 
