@@ -468,8 +468,10 @@ int secedo_bam_split_select_stats(secedo_bam_select_info *out);
  * The result (bins, pairs, per-cell table, cluster sums) stays on the host until the next call on this thread or
  * secedo_bam_release; secedo_bam_depth_fetch copies it out. Chromosomes are processed one after the other with a
  * chromosome's records resident: fewer than 2^32 records and at most 2^32 - 1 pieces (a piece is a record in `reads`
- * mode, a (record, touched bin) in `bases` mode) per chromosome, else SECEDO_E_LIMIT. Not done: GC content and
- * mappability per bin, normalisation, segmentation, counting templates instead of records, CG-tag CIGARs. */
+ * mode, a (record, touched bin) in `bases` mode) per chromosome, else SECEDO_E_LIMIT. GC, N and soft-mask content of
+ * the same bins: secedo_variant_genome_bins (secedo_variant.h), given the names and lengths that
+ * secedo_bam_depth_chromosomes returns. Not done: mappability tracks (bigWig), normalisation, segmentation, counting
+ * templates instead of records, CG-tag CIGARs. */
 #define SECEDO_BAM_DEPTH_READS 0
 #define SECEDO_BAM_DEPTH_BASES 1
 #define SECEDO_BAM_DEPTH_PLAIN 0
@@ -500,6 +502,12 @@ int secedo_bam_depth_fetch(uint32_t *bin_chr, uint32_t *bin_start, uint32_t *bin
                            uint32_t *pair_cell, uint64_t *pair_value, uint64_t *cell_table, uint64_t *cluster_sums);
 /* the last secedo_bam_depth call of this thread, a failed one up to its failure */
 int secedo_bam_depth_stats(secedo_bam_depth_info *out);
+/* The requested chromosomes of the last depth result of this thread, in ascending id (the order of the bins): their
+ * @SQ names one after the other in names[capacity] with name_off[chromosomes + 1] their bounds, and lengths
+ * [chromosomes] their LN. Any may be NULL. *name_bytes (may be NULL) = the bytes the names take; names with a capacity
+ * below that is SECEDO_E_LIMIT (name_bytes is set, nothing else written). SECEDO_E_STATE without a result. */
+int secedo_bam_depth_chromosomes(char *names, uint64_t capacity, uint64_t *name_off, uint32_t *lengths,
+                                 uint64_t *name_bytes);
 
 /* Host only. records_per_ref[r] (r < min(capacity, n_ref)) = records with RefID r; may be NULL.
  * num_threads: inflate pool size, capped at 16 (0 = 1). */

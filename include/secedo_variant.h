@@ -394,6 +394,83 @@ typedef struct secedo_variant_allele_info {
 } secedo_variant_allele_info;
 int secedo_variant_allele_stats(secedo_variant_allele_info *out);
 
+/* ---- Genome composition per bin (GC, N, soft-mask) -----------------------------------------------------------------
+ *
+ * The companion of secedo_bam_depth (secedo_bam.h): per bin of the reference genome the counts that a copy-number tool
+ * regresses depth on (GC) and filters bins by (N, repeats). The FASTA may be plain, gzip or BGZF; it is read through
+ * the device route's input layer whatever SECEDO_FASTA says, counted in HBM (genome_bins_kernels.hip), and the rules
+ * that decide numbers and bytes are in secedo_amd/csrc/genome_bins.hpp. This is the one statement of the contract.
+ *
+ * Contigs. Lines and their roles are those of fasta_lines.hpp (step): line 0 is a header, a '>' line directly after a
+ * header is sequence. Every header starts a contig; its sequence is the sequence bytes up to the next header. There is
+ * no maternal / paternal pairing: a diploid FASTA is more contigs. The name is the header's bytes after its first
+ * byte, up to but excluding the first space, tab, '\r' or the line's end. A name may be empty; a name longer than 4096
+ * bytes is SECEDO_E_INVALID_ARG. Of two contigs with one name the first is taken, the rest are counted in
+ * duplicate_names.
+ *
+ * Selection. names == NULL: all contigs in file order. Else the n_names listed names in the listed order, matched
+ * exactly: there is no chr aliasing, and the error says so. A listed name no contig has, or one listed twice, is
+ * SECEDO_E_INVALID_ARG and is named in the message. lengths != NULL (with names): a contig whose sequence length
+ * differs from lengths[i] is SECEDO_E_INVALID_ARG "<name>: the genome has <n> bases, expected <m>". An empty file and
+ * an empty list are SECEDO_E_INVALID_ARG. A selected contig of more than 2^32 - 1 bases is SECEDO_E_LIMIT.
+ *
+ * Bins. Selected contig k of length L_k has ceil(L_k / S) bins [bS, min((b + 1)S, L_k)); global bin numbers run in
+ * selection order: the layout of secedo_bam_depth. S == 0 is SECEDO_E_INVALID_ARG, more than 2^32 - 1 bins
+ * SECEDO_E_LIMIT. A contig of length 0 has no bins.
+ *
+ * Counted. Six uint32 per bin, from the raw byte of every sequence byte in the bin: a (A a), c (C c), g (G g),
+ * t (T t U u), other (every other byte: N, IUPAC codes, a '\r' inside a sequence line, a '>' that the line rule reads
+ * as sequence) and masked (bytes 'a'..'z', counted in addition to the byte's class). a + c + g + t + other == end -
+ * start always, and only integer sums exist: two runs give identical bytes.
+ *
+ * File. Only with out_path != NULL: "chrom\tstart\tend\ta\tc\tg\tt\tother\tmasked\n", then per global bin
+ * "<name>\t<start>\t<end>\t<a>\t<c>\t<g>\t<t>\t<other>\t<masked>\n", 0-based half-open. SECEDO_GENOME_BINS_BGZF
+ * writes <out_path>.gz instead, BGZF that inflates to the same bytes. An existing file is refused unless overwrite;
+ * the file is written as <name>.tmp.<pid> and renamed, a failed call leaves nothing behind. The lines are formatted
+ * on the GPU in ranges of at most SECEDO_GENOME_BINS_BATCH_BYTES of text (default 256 MiB, at least one line), which
+ * never changes a byte of text; under BGZF the member cuts follow the ranges and only compressed bytes come down.
+ * The text ranges of the input are SECEDO_FASTA_BATCH_BYTES as on the device route.
+ *
+ * Not done: mappability tracks (bigWig), normalisation of depth by these counts, .fai random access. */
+#define SECEDO_GENOME_BINS_PLAIN 0
+#define SECEDO_GENOME_BINS_BGZF 1
+#define SECEDO_GENOME_BINS_COLUMNS 6 /* a, c, g, t, other, masked */
+
+typedef struct secedo_variant_genome_bins_info {
+    uint32_t kind;              /* SECEDO_FASTA_KIND_* */
+    uint32_t output;            /* SECEDO_GENOME_BINS_* */
+    uint64_t contigs;           /* header lines of the file */
+    uint64_t selected;
+    uint64_t duplicate_names;
+    uint64_t bins;
+    uint64_t bases;             /* sequence bytes of the selected contigs */
+    uint64_t name_bytes;        /* the selected names one after the other: what _fetch's `names` must hold */
+    uint64_t ranges;            /* ranges of FASTA text */
+    uint64_t uploaded_bytes;    /* FASTA bytes sent to the GPU: text, or compressed members */
+    uint64_t device_members;    /* BGZF members inflated on the GPU */
+    uint64_t fasta_bytes;       /* FASTA text parsed and counted */
+    uint64_t text_bytes;        /* the output file's text */
+    uint64_t compressed_bytes;  /* BGZF: the bytes of the .gz file, the EOF member included; PLAIN: 0 */
+    uint64_t members;           /* BGZF members with text */
+    double upload_ms;           /* host time inside the uploads (they run beside the passes of the range before) */
+    double parse_ms;            /* the reused scans and the header table (device events) */
+    double count_ms;            /* k_compose (device events) */
+    double format_ms, deflate_ms, download_ms, write_ms; /* the output file, host clocks as for secedo_bam_depth */
+} secedo_variant_genome_bins_info;
+
+/* names, lengths, out_path: NULL for none; info may not be NULL. Runs on the calling thread's device. Synchronous. */
+int secedo_variant_genome_bins(const char *fasta, uint32_t bin_size, const char *const *names, const uint64_t *lengths,
+                               uint32_t n_names, const char *out_path, int output, int overwrite,
+                               secedo_variant_genome_bins_info *info);
+/* Copies the last result of this thread into host buffers, any may be NULL: the selected names one after the other in
+ * names[name_bytes] with name_off[selected + 1] their bounds, contig_lengths[selected], bin_contig (the position in
+ * the selection) / bin_start / bin_end [bins], counts[bins][6]. The result stays until the next call on the thread.
+ * SECEDO_E_STATE without a result. */
+int secedo_variant_genome_bins_fetch(char *names, uint64_t *name_off, uint64_t *contig_lengths, uint32_t *bin_contig,
+                                     uint32_t *bin_start, uint32_t *bin_end, uint32_t *counts);
+/* the last secedo_variant_genome_bins call of this thread, a failed one up to its failure */
+int secedo_variant_genome_bins_stats(secedo_variant_genome_bins_info *out);
+
 /* The drop-in: variant_calling(pos_data, clusters, reference_genome, map_file, hetero_prior, theta, out_dir)
  * on a host flat pileup. Writes cluster_<i>.vcf for i = 0..max(clusters), common.vcf, an empty `variant` and
  * `scores` under out_dir (created), as the reference does (the .vcf files as .vcf.gz under SECEDO_VCF_BGZF, above);

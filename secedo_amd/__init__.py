@@ -13,7 +13,8 @@ from .spectral import laplacian, smallest_eigenpairs  # noqa: F401,E402
 from .em import expectation_maximization  # noqa: F401,E402
 from .cluster import divide_cluster, divide_cluster_resident, spectral_clustering  # noqa: F401,E402
 from .variant import (allele_counts, allele_masks, allele_stats, bgzf_deflate, fasta_stats,  # noqa: F401,E402
-                      get_allele_counts, get_fasta_route, get_vcf_index, get_vcf_output, reference_genotypes,
+                      genome_bins, genome_bins_stats, get_allele_counts, get_fasta_route, get_vcf_index,
+                      get_vcf_output, reference_genotypes,
                       set_allele_counts, set_cell_names, set_fasta_route, set_vcf_index, set_vcf_output, tabix_build,
                       tabix_stats, variant_calling, variant_calling_resident, variant_calls, vcf_stats)
 from .bam_pileup import (bam_barcodes, bam_index_build, bam_index_ranges, bam_index_stats, bam_route_stats,  # noqa: F401,E402

@@ -152,6 +152,7 @@ SIGNATURES = {
                                    C.POINTER(DepthInfo), C.POINTER(Times)]),
     "secedo_bam_depth_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "secedo_bam_depth_stats": (C.c_int, [C.POINTER(DepthInfo)]),
+    "secedo_bam_depth_chromosomes": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "secedo_bgzf_inflate_fetch": (C.c_int, [_vp]),
 }
@@ -531,7 +532,7 @@ def bin_depth(files: Sequence[str], bin_size: int, chromosome_ids: Sequence[int]
               min_map_quality: int = 30, require_flags=None, exclude_flags=None, duplicates: str = "off",
               cell_tag=None, cells=None, clustering=None, cell_names: Optional[Sequence[str]] = None,
               output: str = "plain", overwrite: bool = False, times: Optional[dict] = None, *, inflate=None,
-              index=None, num_threads: int = 8) -> dict:
+              index=None, num_threads: int = 8, reference_genome=None) -> dict:
     """Per-cell read depth in fixed genomic bins: the bins x cells count matrix copy-number tools start from, counted
     on the GPU (secedo_bam_depth; the rules and the bytes of the files are in include/secedo_bam.h). ``files`` are the
     inputs of ``pileup_bams`` (BAM, SAM, bgzipped SAM; ``inflate`` and ``index`` as there), one cell per file, or with
@@ -546,7 +547,12 @@ def bin_depth(files: Sequence[str], bin_size: int, chromosome_ids: Sequence[int]
     ``out_dir``: also write ``<out_dir>/depth/`` (depth.bins.bed, depth.counts.mtx, depth.samples.tsv,
     depth.cells.tsv and with a clustering depth.clusters.tsv; ``output="bgzf"`` writes the .mtx and the two longer
     .tsv as .gz); existing files raise unless ``overwrite``; a failed call leaves nothing behind. ``cell_names``: one
-    name per cell; None names a cell by its barcode or its file's base name.
+    name per cell; None names a cell by its barcode or its file's base name. ``reference_genome`` (a FASTA, plain,
+    gzip or bgzip): after the depth, ``genome_bins`` runs on it with the requested chromosomes' @SQ names and LN as
+    ``contigs`` and ``lengths``, so a genome with other names or lengths raises and says why; the result gains ``gc``
+    (uint32 [bins, 6]: a, c, g, t, other, masked, row for row with the bins) and ``out_dir`` gains
+    ``depth/depth.gc.tsv`` (``.gz`` under ``output="bgzf"``), whose first three columns are depth.bins.bed's. When the
+    genome step fails, what the depth step of this call wrote is removed again.
     -> dict of numpy arrays: bin_chrom, bin_start, bin_end [bins]; pair_bin, pair_cell (0-based, uint32), pair_value
     (uint64) [pairs], ordered by bin and then cell; cells [n_cells, 5] uint64 (records, counted, sum, nonzero_bins,
     max_value); cluster_sums [bins, K] uint64 (with a clustering); names (list of str); stats (``depth_stats()``).
@@ -583,6 +589,13 @@ def bin_depth(files: Sequence[str], bin_size: int, chromosome_ids: Sequence[int]
         cl = np.ascontiguousarray(cl, dtype=np.uint16)
     tag, bcs, n_bcs = _cells(cell_tag, cells)
     ids = np.ascontiguousarray(chromosome_ids, dtype=np.uint32)
+    gc_path, had_dir = None, False
+    if reference_genome is not None and out_dir is not None:
+        had_dir = os.path.isdir(os.path.join(str(out_dir), "depth"))
+        gc_path = os.path.join(str(out_dir), "depth", "depth.gc.tsv")
+        gc_target = gc_path + (".gz" if output == "bgzf" else "")
+        if not overwrite and os.path.exists(gc_target):  # before anything runs
+            raise _lib.SecedoError(_lib.E_INVALID_ARG, "%s exists; pass overwrite to replace it" % gc_target)
     names = None if cell_names is None else [_encode(x) for x in cell_names]
     names_arr = None if names is None else (C.c_char_p * max(len(names), 1))(*names)
     try:
@@ -616,7 +629,58 @@ def bin_depth(files: Sequence[str], bin_size: int, chromosome_ids: Sequence[int]
     else:
         out["names"] = [default_cell_name(f) for f in files]
     out["stats"] = _depth_dict(info)
+    if reference_genome is not None:
+        try:
+            out["gc"] = _depth_gc(reference_genome, int(bin_size), gc_path, output, overwrite)
+        except Exception:
+            if out_dir is not None:  # a failed call leaves nothing behind: what the depth step of this call wrote
+                _remove_depth_files(os.path.join(str(out_dir), "depth"), output, cl is not None, not had_dir)
+            raise
     return out
+
+
+def depth_chromosomes():
+    """The requested chromosomes of the last ``bin_depth`` call on this thread, in ascending id (the order of the
+    bins) -> (names, lengths): their @SQ names (list of str) and LN (uint32 array)."""
+    n_bytes = C.c_uint64(0)
+    check(lib().secedo_bam_depth_chromosomes(None, 0, None, None, C.byref(n_bytes)))
+    info = DepthInfo()
+    check(lib().secedo_bam_depth_stats(C.byref(info)))
+    n = int(info.chromosomes)
+    raw = np.zeros(max(int(n_bytes.value), 1), np.uint8)
+    off, ln = np.zeros(n + 1, np.uint64), np.zeros(n, np.uint32)
+    check(lib().secedo_bam_depth_chromosomes(_lib.ptr(raw), int(n_bytes.value), _lib.ptr(off), _lib.ptr(ln), None))
+    data = raw.tobytes()
+    return [data[int(off[i]):int(off[i + 1])].decode("utf-8", "surrogateescape") for i in range(n)], ln
+
+
+def _depth_gc(reference_genome, bin_size, gc_path, output, overwrite):
+    """The genome step of ``bin_depth``: the composition of the depth call's bins, refused unless the genome has the
+    BAM header's chromosome names and lengths."""
+    from .variant import genome_bins
+
+    names, ln = depth_chromosomes()
+    try:
+        g = genome_bins(reference_genome, bin_size, contigs=names, lengths=ln, out_path=gc_path, output=output,
+                        overwrite=overwrite)
+    except _lib.SecedoError as e:
+        raise _lib.SecedoError(e.code, "reference_genome %s does not fit the BAM header (its @SQ names and LN are the "
+                               "contigs and lengths asked for): %s" % (reference_genome, str(e).split(": ", 1)[-1]))
+    return g["counts"]
+
+
+def _remove_depth_files(depth_dir, output, clustered, made_dir):
+    """Removes what secedo_bam_depth wrote under ``depth_dir`` for this output kind, and the directory if asked."""
+    gz = ".gz" if output == "bgzf" else ""
+    names = ["depth.bins.bed", "depth.samples.tsv", "depth.counts.mtx" + gz, "depth.cells.tsv" + gz]
+    if clustered:
+        names.append("depth.clusters.tsv" + gz)
+    for name in names:
+        path = os.path.join(depth_dir, name)
+        if os.path.exists(path):
+            os.unlink(path)
+    if made_dir and os.path.isdir(depth_dir) and not os.listdir(depth_dir):
+        os.rmdir(depth_dir)
 
 
 def default_cell_name(path) -> str:

@@ -36,6 +36,8 @@ struct Result {
     std::vector<bd::Pair> pairs;
     std::vector<bd::CellRow> rows;
     std::vector<uint64_t> table;  // [bins][clusters]
+    std::vector<std::string> chr_names;  // of the requested chromosomes, ascending id
+    std::vector<uint32_t> chr_len;
 };
 thread_local Result *g_result = nullptr;
 
@@ -601,6 +603,11 @@ int depth(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
             res->bin_end.push_back(bd::bin_end(uint32_t(b), rq.S, lay.len[k]));
         }
 
+    for (size_t k = 0; k < lay.chr.size(); ++k) {
+        res->chr_names.push_back(refs[lay.chr[k]].name);
+        res->chr_len.push_back(lay.len[k]);
+    }
+
     Inputs in;
     SECEDO_CALL(load_inputs(rq.files, rq.chr.data(), n_chr, rq.threads, &in, &tl));
 
@@ -730,6 +737,26 @@ int secedo_bam_depth_fetch(uint32_t *bin_chr, uint32_t *bin_start, uint32_t *bin
             std::copy(v, v + bd::kCellColumns, cell_table + c * bd::kCellColumns);
         }
     if (cluster_sums) std::copy(r.table.begin(), r.table.end(), cluster_sums);
+    return SECEDO_OK;
+}
+
+int secedo_bam_depth_chromosomes(char *names, uint64_t capacity, uint64_t *name_off, uint32_t *lengths,
+                                 uint64_t *name_bytes) {
+    if (!g_result) return fail(SECEDO_E_STATE, "no depth result: call secedo_bam_depth first");
+    const Result &r = *g_result;
+    uint64_t total = 0;
+    for (const std::string &n : r.chr_names) total += n.size();
+    if (name_bytes) *name_bytes = total;
+    if (names && capacity < total)
+        return fail(SECEDO_E_LIMIT, "the chromosome names take " + std::to_string(total) + " bytes");
+    uint64_t at = 0;
+    for (size_t k = 0; k < r.chr_names.size(); ++k) {
+        if (name_off) name_off[k] = at;
+        if (names) std::copy(r.chr_names[k].begin(), r.chr_names[k].end(), names + at);
+        at += r.chr_names[k].size();
+    }
+    if (name_off) name_off[r.chr_names.size()] = at;
+    if (lengths) std::copy(r.chr_len.begin(), r.chr_len.end(), lengths);
     return SECEDO_OK;
 }
 

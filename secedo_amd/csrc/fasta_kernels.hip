@@ -171,6 +171,16 @@ hipError_t parse_range(const uint8_t *d_text, uint32_t len, uint32_t state, cons
     return hipGetLastError();
 }
 
+hipError_t emit_range(const uint8_t *d_text, uint32_t len, uint32_t state, const RangeWork &w, hipStream_t s) {
+    if (len == 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(w.totals, 0xFF, table_bytes(w.cap), s);
+    if (e != hipSuccess) return e;
+    const uint32_t chunks = num_chunks(len);
+    hipLaunchKernelGGL(k_emit, dim3(blocks(chunks)), dim3(kBlock), 0, s, d_text, len, chunks, state, w.tf_in,
+                       w.cnt_before, w.codes, w.totals, w.cap);
+    return hipGetLastError();
+}
+
 hipError_t gather(const uint8_t *d_codes, uint32_t code_off, uint32_t count, uint64_t q0, const uint32_t *d_pos,
                   uint32_t l0, uint32_t l1, uint8_t *d_dst, hipStream_t s) {
     if (l1 <= l0 || !count || q0 > UINT32_MAX) return hipSuccess;

@@ -38,6 +38,11 @@ size_t scan_workspace(uint32_t max_len);
 // len may be 0 (the totals then say so). Asynchronous on s.
 hipError_t parse_range(const uint8_t *d_text, uint32_t len, uint32_t state, const RangeWork &w, hipStream_t s);
 
+// The last pass alone, over the tf_in and cnt_before that parse_range left for this same range: the totals and the
+// slots again, for a caller that found w.cap too small (RangeTotals.headers >= cap) and comes back with a table that
+// fits. w.codes may be null here and in parse_range: the codes are then not written.
+hipError_t emit_range(const uint8_t *d_text, uint32_t len, uint32_t state, const RangeWork &w, hipStream_t s);
+
 // d_dst[l] = d_codes[code_off + (p - q0)] for the loci l of [l0, l1) with p = d_pos[l] - 1 in [q0, q0 + count)
 hipError_t gather(const uint8_t *d_codes, uint32_t code_off, uint32_t count, uint64_t q0, const uint32_t *d_pos,
                   uint32_t l0, uint32_t l1, uint8_t *d_dst, hipStream_t s);

@@ -15,7 +15,9 @@ positions its M, = and X ops cover there. A record is selected by its barcode, -
 Position lying inside the chromosome, in this order. --clustering FILE is the comma-separated file ``secedo_main``
 writes. --cell_names FILE names the cells, one per line; without it a cell is named by its barcode or its file's base
 name. --output bgzf writes the .mtx and the two longer .tsv bgzip-compressed (.gz). Existing outputs are refused unless
---overwrite.
+--overwrite. --reference_genome genome.fa[.gz] adds depth.gc.tsv: per bin the genome's a, c, g, t, other (N and the
+rest) and soft-masked counts, for GC correction and bin filtering; the genome must have the BAM header's chromosome
+names and lengths (``secedo_amd.genome_bins``, ``python -m secedo_amd.gc_main``).
 """
 from __future__ import annotations
 
@@ -28,7 +30,8 @@ from .pileup_main import (DEFAULT_CHROMOSOMES, MAX_CELLS, build_missing_indexes,
                           chromosome_to_id, input_files, pool_size, read_cells, valid_tag)
 
 FILES = ("depth.bins.bed", "depth.samples.tsv", "depth.counts.mtx", "depth.cells.tsv", "depth.clusters.tsv")
-COMPRESSED = FILES[2:]  # .gz under --output bgzf
+GC_FILE = "depth.gc.tsv"  # with --reference_genome
+COMPRESSED = FILES[2:] + (GC_FILE,)  # .gz under --output bgzf
 
 
 def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -57,14 +60,17 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
                     help="Read BAM files through their .bai index; the outputs are the same")
     ap.add_argument("--build_index", action="store_true",
                     help="Before the run, write <bam>.bai on the GPU for every input BAM without an index file")
+    ap.add_argument("--reference_genome", default=None,
+                    help="FASTA (plain, gzip or bgzip) of the BAMs' reference: also write depth.gc.tsv[.gz], the "
+                         "composition of every bin")
     ap.add_argument("--overwrite", action="store_true", help="Replace existing depth.* files")
     ap.add_argument("--num_threads", type=int, default=8, help="Host inflate threads (at most 16 are used)")
     return ap.parse_args(argv)
 
 
-def output_paths(out_dir: str, output: str, clustered: bool) -> List[str]:
+def output_paths(out_dir: str, output: str, clustered: bool, genome: bool = False) -> List[str]:
     """The files a run writes under <out_dir>/depth/."""
-    names = FILES if clustered else FILES[:-1]
+    names = (FILES if clustered else FILES[:-1]) + ((GC_FILE,) if genome else ())
     return [os.path.join(out_dir, "depth", n + (".gz" if output == "bgzf" and n in COMPRESSED else "")) for n in names]
 
 
@@ -137,9 +143,12 @@ def main(argv: Optional[List[str]] = None) -> int:
         bad = [c for c, n in enumerate(names) if not n or "\t" in n]
         if bad:
             raise SystemExit("--cell_names file %s: the name of cell %d is empty or holds a tab" % (a.cell_names, bad[0]))
+    if a.reference_genome is not None and not os.path.isfile(a.reference_genome):
+        raise SystemExit("--reference_genome file %s does not exist" % a.reference_genome)
     if not os.path.isdir(a.o):
         raise SystemExit("-o %s is not a directory" % a.o)
-    there = [o for o in output_paths(a.o, a.output, clustering is not None) if os.path.exists(o)]
+    there = [o for o in output_paths(a.o, a.output, clustering is not None, a.reference_genome is not None)
+             if os.path.exists(o)]
     if there and not a.overwrite:
         raise SystemExit("%s exists; pass --overwrite to replace it" % there[0])
     ids = [chromosome_to_id(c) for c in a.chromosomes.split(",")]
@@ -153,7 +162,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     out = bin_depth(files, a.bin_size, ids, out_dir=a.o, mode=a.mode, min_map_quality=a.min_map_quality,
                     duplicates=a.duplicates, clustering=clustering, cell_names=names, output=a.output,
                     overwrite=a.overwrite, inflate=a.inflate, index=a.index, num_threads=pool_size(a.num_threads),
-                    **tag_kw)
+                    reference_genome=a.reference_genome, **tag_kw)
     st = out["stats"]
     print("Counted %d of %d records of %d cells into %d bins of %d bp on %d chromosomes: %d nonzero pairs, written to %s"
           % (st["counted"], st["records"], st["cells"], st["bins"], a.bin_size, st["chromosomes"], st["pairs"],
@@ -162,6 +171,10 @@ def main(argv: Optional[List[str]] = None) -> int:
           "%d below MapQuality %d, %d out of range"
           % (st["dropped_barcode"], st["dropped_require"], st["dropped_exclude"], st["dropped_duplicate"],
              st["dropped_mapq"], a.min_map_quality, st["out_of_range"]))
+    if "gc" in out:
+        gc = out["gc"].sum(axis=0, dtype="uint64")
+        print("Genome composition of the bins: %d A, %d C, %d G, %d T, %d other, %d soft-masked, written to %s"
+              % (gc[0], gc[1], gc[2], gc[3], gc[4], gc[5], output_paths(a.o, a.output, False, True)[-1]))
     return 0
 
 

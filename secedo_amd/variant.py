@@ -96,7 +96,19 @@ class AlleleInfo(C.Structure):
                 ("count_kernel_ms", C.c_double)]
 
 
+class GenomeBinsInfo(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("output", C.c_uint32), ("contigs", C.c_uint64), ("selected", C.c_uint64),
+                ("duplicate_names", C.c_uint64), ("bins", C.c_uint64), ("bases", C.c_uint64),
+                ("name_bytes", C.c_uint64), ("ranges", C.c_uint64), ("uploaded_bytes", C.c_uint64),
+                ("device_members", C.c_uint64), ("fasta_bytes", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("compressed_bytes", C.c_uint64), ("members", C.c_uint64), ("upload_ms", C.c_double),
+                ("parse_ms", C.c_double), ("count_ms", C.c_double), ("format_ms", C.c_double),
+                ("deflate_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
 FASTA_ROUTES = ("host", "device")
+GENOME_BINS_OUTPUTS = ("plain", "bgzf")
+GENOME_BINS_COLUMNS = ("a", "c", "g", "t", "other", "masked")
 ALLELE_COUNTS = ("none", "all", "cluster")
 PAIR_DTYPE = np.dtype([("site", np.uint32), ("group", np.uint32), ("ad", np.uint32), ("rd", np.uint32),
                        ("oth", np.uint32)])
@@ -139,6 +151,10 @@ SIGNATURES = {
                                                       C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, C.c_uint32, _u32p, _vp,
                                                       C.c_uint64, _u64p, _vp]),
     "secedo_variant_allele_stats": (C.c_int, [C.POINTER(AlleleInfo)]),
+    "secedo_variant_genome_bins": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), _vp, C.c_uint32,
+                                             C.c_char_p, C.c_int, C.c_int, C.POINTER(GenomeBinsInfo)]),
+    "secedo_variant_genome_bins_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "secedo_variant_genome_bins_stats": (C.c_int, [C.POINTER(GenomeBinsInfo)]),
     "secedo_variant_is_diploid": (C.c_int, [C.c_char_p]),
     "secedo_variant_read_chromosome": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "secedo_variant_read_map": (C.c_int, [C.c_char_p, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _u32p]),
@@ -671,3 +687,73 @@ def variant_calling_resident(plan, res, clusters, reference_genome, map_file="",
             res["n_loci"], res["n_entries"], _lib.ptr(cl), len(cl), _b(reference_genome), _b(map_file), hetero_prior,
             theta, _b(out_dir), C.byref(t), plan._stream()))
     return _times(t)
+
+
+def _genome_bins_dict(info: GenomeBinsInfo) -> dict:
+    out = {k: (float if ty is C.c_double else int)(getattr(info, k)) for k, ty in GenomeBinsInfo._fields_}
+    out["kind"] = FASTA_KINDS[out["kind"]]
+    out["output"] = GENOME_BINS_OUTPUTS[out["output"]]
+    return out
+
+
+def genome_bins_stats() -> dict:
+    """What the last ``genome_bins`` call on this thread did, a failed one up to its failure: kind, output, contigs,
+    selected, duplicate_names, bins, bases, name_bytes, ranges, uploaded_bytes, device_members, fasta_bytes,
+    text_bytes, compressed_bytes, members and the stage times upload_ms, parse_ms, count_ms, format_ms, deflate_ms,
+    download_ms, write_ms."""
+    info = GenomeBinsInfo()
+    check(lib().secedo_variant_genome_bins_stats(C.byref(info)))
+    return _genome_bins_dict(info)
+
+
+def _name_bytes(x) -> bytes:
+    return x if isinstance(x, bytes) else str(x).encode("utf-8", "surrogateescape")
+
+
+def genome_bins(fasta, bin_size: int, contigs=None, lengths=None, out_path=None, output: str = "plain",
+                overwrite: bool = False) -> dict:
+    """The composition of a reference genome per bin, counted on the GPU: what a copy-number tool regresses depth on
+    (GC) and filters bins by (N, soft-masked repeats); the companion of ``bin_depth``
+    (secedo_variant_genome_bins; the rules and the bytes of the file are in include/secedo_variant.h). ``fasta`` is
+    plain, gzip or bgzip-compressed. Every header line starts a contig, named by the header's bytes after its first up
+    to the first space, tab or '\\r'; of two contigs with one name the first counts. ``contigs`` None: all contigs in
+    file order; else the listed names in the listed order, matched exactly (no ``chr`` aliasing), a missing one raises.
+    ``lengths`` (with ``contigs``): the length each listed contig must have, else the call raises. Contig ``k`` has
+    ``ceil(L_k / bin_size)`` bins, numbered in selection order: the bins of ``bin_depth`` for the same names and
+    lengths. ``out_path``: also write that file (``output="bgzf"``: ``<out_path>.gz``), a header line and one line
+    per bin ``name start end a c g t other masked``, tab-separated; an existing file raises unless ``overwrite``.
+    -> dict: names (list of str), contig_lengths uint64 [selected], bin_contig (the position in ``names``), bin_start,
+    bin_end uint32 [bins], counts uint32 [bins, 6] (a, c, g, t, other, masked: masked counts bytes 'a'..'z' in
+    addition to their class, so a + c + g + t + other == bin_end - bin_start), stats (``genome_bins_stats()``)."""
+    if output not in GENOME_BINS_OUTPUTS:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "output is 'plain' or 'bgzf', got %r" % (output,))
+    if not isinstance(bin_size, (int, np.integer)) or bin_size < 0 or bin_size > 0xFFFFFFFF:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "bin_size is an integer in [1, 2^32 - 1], got %r" % (bin_size,))
+    if lengths is not None and contigs is None:
+        raise _lib.SecedoError(_lib.E_INVALID_ARG, "lengths needs contigs")
+    names_arr, len_arr, n = None, None, 0
+    if contigs is not None:
+        if isinstance(contigs, (str, bytes)):
+            contigs = [contigs]
+        names = [_name_bytes(x) for x in contigs]
+        n = len(names)
+        names_arr = (C.c_char_p * max(n, 1))(*names)
+        if lengths is not None:
+            len_arr = np.ascontiguousarray(lengths, dtype=np.uint64)
+            if len_arr.shape != (n,):
+                raise _lib.SecedoError(_lib.E_INVALID_ARG, "%d lengths for %d contigs" % (len_arr.size, n))
+    info = GenomeBinsInfo()
+    check(lib().secedo_variant_genome_bins(_b(fasta), int(bin_size), names_arr, _lib.ptr(len_arr), n, _b(out_path),
+                                           GENOME_BINS_OUTPUTS.index(output), int(bool(overwrite)), C.byref(info)))
+    n_sel, n_bins = int(info.selected), int(info.bins)
+    raw = np.zeros(max(int(info.name_bytes), 1), np.uint8)
+    off = np.zeros(n_sel + 1, np.uint64)
+    out = dict(contig_lengths=np.zeros(n_sel, np.uint64), bin_contig=np.zeros(n_bins, np.uint32),
+               bin_start=np.zeros(n_bins, np.uint32), bin_end=np.zeros(n_bins, np.uint32),
+               counts=np.zeros((n_bins, len(GENOME_BINS_COLUMNS)), np.uint32))
+    check(lib().secedo_variant_genome_bins_fetch(_lib.ptr(raw), _lib.ptr(off), *[_lib.ptr(out[k]) for k in (
+        "contig_lengths", "bin_contig", "bin_start", "bin_end", "counts")]))
+    data = raw.tobytes()
+    out["names"] = [data[int(off[i]):int(off[i + 1])].decode("utf-8", "surrogateescape") for i in range(n_sel)]
+    out["stats"] = _genome_bins_dict(info)
+    return out
