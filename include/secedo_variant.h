@@ -475,7 +475,11 @@ int secedo_variant_genome_bins_stats(secedo_variant_genome_bins_info *out);
  * on a host flat pileup. Writes cluster_<i>.vcf for i = 0..max(clusters), common.vcf, an empty `variant` and
  * `scores` under out_dir (created), as the reference does (the .vcf files as .vcf.gz under SECEDO_VCF_BGZF, above);
  * n == 0 writes nothing. times may be NULL. Under SECEDO_ALLELE_ALL / _CLUSTER also out_dir/allele_counts/ (above),
- * after the other files; its time is in secedo_variant_allele_stats, not in `times`. */
+ * after the other files; its time is in secedo_variant_allele_stats, not in `times`.
+ * n_chr > 24 is SECEDO_E_INVALID_ARG before anything is made: the lines name the chromosomes 1..22, X, Y, and the
+ * reference asserts on a later one. A reference genome or map that is refused (unequal maternal and paternal
+ * contigs, where the reference ends its process after writing the preambles) leaves nothing behind: out_dir is
+ * removed again if the call created it. */
 int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
                            const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint16_t *id_base16,
                            const uint32_t *id_base32, const uint16_t *clusters, uint32_t n,

@@ -216,6 +216,48 @@ def ref_read_pileup(fname, merge_count=1, merge_file="", max_coverage=100):
     return pos, off, rid, idb, nc.value, ml.value
 
 
+REF_VARIANT = os.path.join(HERE, "_ref", "ref_variant")
+REF_VARIANT_BAD_FILE, REF_VARIANT_BAD_GROUP = 65, 66  # the driver's own statuses (oracle/ref_variant_driver.cpp)
+
+
+def have_ref_variant() -> bool:
+    return os.path.exists(REF_VARIANT)
+
+
+def ref_variant_genotypes(counts, likely_homozygous_total, hetero_prior, theta, scratch_dir, timeout=120):
+    """The compiled reference's likely_homozygous and most_likely_genotype on (n, 4) u16 counts
+    -> (homozygous u8[n], genotype u8[n], coverage u16[n]). Files go through ``scratch_dir``."""
+    c = np.ascontiguousarray(counts, dtype=np.uint16).reshape(-1, 4)
+    src, dst = os.path.join(scratch_dir, "counts.bin"), os.path.join(scratch_dir, "genotypes.bin")
+    c.tofile(src)
+    r = subprocess.run([REF_VARIANT, "genotypes", src, str(int(bool(likely_homozygous_total))), repr(float(hetero_prior)),
+                        repr(float(theta)), dst], capture_output=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError("ref_variant genotypes failed: %d %s" % (r.returncode, r.stderr.decode(errors="replace")))
+    out = np.fromfile(dst, dtype=np.uint8).reshape(-1, 4)
+    if out.shape[0] != c.shape[0]:
+        raise RuntimeError("ref_variant genotypes: %d results for %d tuples" % (out.shape[0], c.shape[0]))
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2:].copy().view(np.uint16).reshape(-1)
+
+
+def ref_variant_calling(pileup_bin, clusters_bin, reference_genome, map_file, hetero_prior, theta, out_dir,
+                        timeout=300):
+    """The compiled reference's variant_calling() as a child program, on the flat files of
+    tests/cpp/variant_calling_test.cpp -> (returncode, stderr, {file name: text}). The reference logs
+    through spdlog's coloured stdout sink, so `stderr` is the text of both streams, stdout first. The
+    status is the reference's own (1 where it calls exit(1)), or one of the driver's; the files are
+    what the run left under ``out_dir``, none when it made no directory."""
+    r = subprocess.run([REF_VARIANT, "call", str(pileup_bin), str(clusters_bin), str(reference_genome),
+                        str(map_file or ""), repr(float(hetero_prior)), repr(float(theta)), str(out_dir)],
+                       capture_output=True, timeout=timeout)
+    files = {}
+    if os.path.isdir(out_dir):
+        for name in sorted(os.listdir(out_dir)):
+            with open(os.path.join(out_dir, name), "rb") as f:
+                files[name] = f.read().decode("utf-8", "surrogateescape")
+    return r.returncode, (r.stdout + r.stderr).decode("utf-8", "replace"), files
+
+
 NO_POS = 16383  # util/is_significant.hpp:11
 
 

@@ -628,8 +628,35 @@ def pileup_edges():
                                                         os.path.getsize(path) / 1024))
 
 
+def variant_cases():
+    """tests/golden/variant_reference.npz: the compiled reference's variant calling (oracle/_ref/ref_variant) on every
+    case of tests/variant_cases.py: every output file's bytes (without ##fileDate, the genome's path marked), the exit
+    status and words of the inputs it refuses, and its two decision functions on the tuple set under twelve
+    settings."""
+    from tests import variant_cases as vc
+    if not ob.have_ref_variant():
+        sys.exit("oracle/_ref/ref_variant missing: run `make -C oracle ref` in the container")
+    results, refusals = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for c in vc.accepted():
+            rc, log, files = vc.run_reference(c, tmp)
+            assert rc == 0 and files, (c[0], rc, log)
+            results[c[0]] = files
+        for c in vc.refused():
+            rc, log, _ = vc.run_reference(c, tmp)
+            refusals[c[0]] = (rc, vc.mismatch_message(log))
+        tuples = vc.reference_tuples(tmp)
+    path = vc.GOLDEN
+    save_npz_fixed(path, vc.golden_arrays(results, refusals, tuples))
+    print("variant_cases: %d cases, %d refused, %d tuples x %d settings  %.1f KB"
+          % (len(results), len(refusals), len(tuples[3]), len(vc.SETTINGS), os.path.getsize(path) / 1024))
+
+
 def main():
     only = set(sys.argv[1:])
+    if only == {"variant_cases"}:  # needs oracle/_ref/ref_variant alone
+        os.makedirs(GOLDEN, exist_ok=True)
+        return variant_cases()
     if only == {"pileup_edges"}:  # needs oracle/_ref/ref_pileup alone
         os.makedirs(GOLDEN, exist_ok=True)
         return pileup_edges()
@@ -642,6 +669,8 @@ def main():
             fn()
     if "pileup_edges" in only:   # by name: a minute of the reference's pileup_bams()
         pileup_edges()
+    if not only or "variant_cases" in only:
+        variant_cases()
     if "c3_reference_run" in only:   # five minutes of the reference: only when asked for by name
         c3_reference_run()
     if "c2_clustered_reference_run" in only:

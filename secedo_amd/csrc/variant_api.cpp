@@ -463,6 +463,21 @@ int run_calls(const uint32_t *d_chr_locus_off, uint32_t n_chr, const uint64_t *d
     return SECEDO_OK;
 }
 
+// A reference genome that the reference refuses (unequal maternal and paternal contigs: its process ends there, after
+// the preambles are written) leaves nothing behind here: out_dir is removed again if this call created it. remove()
+// takes an empty directory only. Every other failure leaves out_dir as it is.
+struct OutDirGuard {
+    const char *dir = nullptr;
+    bool created = false, refused = false;
+    int done(int rc) {
+        if (rc != SECEDO_OK && created && refused && dir) {
+            std::error_code ec;
+            std::filesystem::remove(dir, ec);
+        }
+        return rc;
+    }
+};
+
 // variant_calling on a resident pileup with the host copies of its chromosome offsets and positions (the positions
 // also in HBM where the caller has them there: d_locus_pos, else null).
 int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_locus_off, uint32_t n_chr,
@@ -470,7 +485,8 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
             const uint16_t *d_id_base16,
             const uint32_t *d_id_base32, uint32_t n_loci, const uint16_t *clusters, uint32_t n,
             const char *reference_genome, const char *map_file, double hetero_prior, double theta,
-            const char *out_dir, secedo_variant_times *times, hipStream_t s, double pre_device_ms) {
+            const char *out_dir, secedo_variant_times *times, hipStream_t s, double pre_device_ms,
+            OutDirGuard *out_guard) {
     secedo_variant_times t{};
     Clock::time_point t0 = Clock::now();
     int output = SECEDO_VCF_PLAIN;
@@ -492,7 +508,10 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
     SECEDO_TRY(b_ref.alloc(n_loci));
     const RefArgs ref{d_chr_locus_off, chr_locus_off, n_chr, d_locus_pos, locus_pos, n_loci, b_ref.as<uint8_t>(),
                       bgzf ? nullptr : locus_ref.data(), chr_end.data()};
-    SECEDO_CALL(reference_any(reference_genome, map_file, ref, &t.fasta_ms, &t.gather_ms, s));
+    if (int rc = reference_any(reference_genome, map_file, ref, &t.fasta_ms, &t.gather_ms, s)) {
+        out_guard->refused = true;
+        return rc;
+    }
     (void)ms_lap(t0);
     const uint32_t num_clusters = static_cast<uint32_t>(*std::max_element(clusters, clusters + n)) + 1;
 
@@ -541,15 +560,21 @@ int calling(int device_id, const uint32_t *d_chr_locus_off, const uint32_t *chr_
 }
 
 // The steps before the reference's locus loop (:330-337): nothing for no cells; out_dir is created before the
-// reference genome is checked.
-int begin_calling(uint32_t n, const char *reference_genome, const char *out_dir, bool *done) {
+// reference genome is checked. More than 24 chromosomes are refused before anything is made: the reference names the
+// 23rd X and the 24th Y and asserts on a line for any later one (id_to_chromosome, util.cpp:162-170).
+int begin_calling(uint32_t n, uint32_t n_chr, const char *reference_genome, const char *out_dir, bool *done,
+                  OutDirGuard *out_guard) {
     *done = n == 0;
     if (*done) return SECEDO_OK;
+    if (n_chr > 24)
+        return fail(SECEDO_E_INVALID_ARG, "more than 24 chromosomes (" + std::to_string(n_chr) +
+                                          "): the VCF lines name them 1..22, X, Y");
     int allele = SECEDO_ALLELE_NONE;  // an unknown SECEDO_ALLELE_COUNTS is refused before anything is made
     SECEDO_CALL(secedo::allele::selection_kind(&allele));
     if (!out_dir || !reference_genome) return fail(SECEDO_E_INVALID_ARG, "null path");
     std::error_code ec;
-    std::filesystem::create_directories(out_dir, ec);
+    out_guard->dir = out_dir;
+    out_guard->created = std::filesystem::create_directories(out_dir, ec);
     if (ec) return fail(SECEDO_E_INVALID_ARG, std::string("cannot create ") + out_dir + ": " + ec.message());
     if (!std::filesystem::exists(reference_genome))
         return fail(SECEDO_E_INVALID_ARG, std::string("Reference genome ") + reference_genome + " does not exist");
@@ -832,13 +857,13 @@ int secedo_variant_bgzf_deflate(int device_id, const uint8_t *data, const uint64
     return SECEDO_OK;
 }
 
-int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
-                           const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint16_t *id_base16,
-                           const uint32_t *id_base32, const uint16_t *clusters, uint32_t n,
-                           const char *reference_genome, const char *map_file, double hetero_prior, double theta,
-                           const char *out_dir, secedo_variant_times *times) {
+static int calling_host(OutDirGuard *out_guard, int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
+                        const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint16_t *id_base16,
+                        const uint32_t *id_base32, const uint16_t *clusters, uint32_t n,
+                        const char *reference_genome, const char *map_file, double hetero_prior, double theta,
+                        const char *out_dir, secedo_variant_times *times) {
     bool done;
-    SECEDO_CALL(begin_calling(n, reference_genome, out_dir, &done));
+    SECEDO_CALL(begin_calling(n, n_chr, reference_genome, out_dir, &done, out_guard));
     if (done) return SECEDO_OK;
     if (!chr_locus_off || !clusters || (!!id_base16 == !!id_base32 && chr_locus_off[n_chr] > 0))
         return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
@@ -862,18 +887,28 @@ int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_
     const double upload_ms = ms_lap(t0);
     return calling(device_id, b_chr.as<uint32_t>(), chr_locus_off, n_chr, locus_pos, nullptr, b_off.as<uint64_t>(),
                    id_base16 ? b_idb.as<uint16_t>() : nullptr, id_base16 ? nullptr : b_idb.as<uint32_t>(), n_loci,
-                   clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times, s, upload_ms);
+                   clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times, s, upload_ms, out_guard);
 }
 
-int secedo_variant_calling_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
-                                  const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
-                                  const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci,
-                                  uint64_t n_entries, const uint16_t *clusters, uint32_t n,
-                                  const char *reference_genome, const char *map_file, double hetero_prior,
-                                  double theta, const char *out_dir, secedo_variant_times *times, void *stream) {
-    (void)n_entries;
+int secedo_variant_calling(int device_id, const uint32_t *chr_locus_off, uint32_t n_chr,
+                           const uint32_t *locus_pos, const uint64_t *locus_entry_off, const uint16_t *id_base16,
+                           const uint32_t *id_base32, const uint16_t *clusters, uint32_t n,
+                           const char *reference_genome, const char *map_file, double hetero_prior, double theta,
+                           const char *out_dir, secedo_variant_times *times) {
+    OutDirGuard out_guard;
+    return out_guard.done(calling_host(&out_guard, device_id, chr_locus_off, n_chr, locus_pos, locus_entry_off,
+                                       id_base16, id_base32, clusters, n, reference_genome, map_file, hetero_prior,
+                                       theta, out_dir, times));
+}
+
+static int calling_resident(OutDirGuard *out_guard, int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                            const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+                            const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci,
+                            const uint16_t *clusters, uint32_t n, const char *reference_genome, const char *map_file,
+                            double hetero_prior, double theta, const char *out_dir, secedo_variant_times *times,
+                            void *stream) {
     bool done;
-    SECEDO_CALL(begin_calling(n, reference_genome, out_dir, &done));
+    SECEDO_CALL(begin_calling(n, n_chr, reference_genome, out_dir, &done, out_guard));
     if (done) return SECEDO_OK;
     if (!clusters || (!!d_id_base16 == !!d_id_base32 && n_loci > 0))
         return fail(SECEDO_E_INVALID_ARG, "invalid argument (exactly one of id_base16 / id_base32)");
@@ -889,7 +924,20 @@ int secedo_variant_calling_device(int device_id, const uint32_t *d_chr_locus_off
     const double download_ms = ms_lap(t0);
     return calling(device_id, d_chr_locus_off, chr_off.data(), n_chr, pos.data(), d_locus_pos, d_locus_entry_off, d_id_base16,
                    d_id_base32, n_loci, clusters, n, reference_genome, map_file, hetero_prior, theta, out_dir, times,
-                   s, download_ms);
+                   s, download_ms, out_guard);
+}
+
+int secedo_variant_calling_device(int device_id, const uint32_t *d_chr_locus_off, uint32_t n_chr,
+                                  const uint32_t *d_locus_pos, const uint64_t *d_locus_entry_off,
+                                  const uint16_t *d_id_base16, const uint32_t *d_id_base32, uint32_t n_loci,
+                                  uint64_t n_entries, const uint16_t *clusters, uint32_t n,
+                                  const char *reference_genome, const char *map_file, double hetero_prior,
+                                  double theta, const char *out_dir, secedo_variant_times *times, void *stream) {
+    (void)n_entries;
+    OutDirGuard out_guard;
+    return out_guard.done(calling_resident(&out_guard, device_id, d_chr_locus_off, n_chr, d_locus_pos,
+                                           d_locus_entry_off, d_id_base16, d_id_base32, n_loci, clusters, n,
+                                           reference_genome, map_file, hetero_prior, theta, out_dir, times, stream));
 }
 
 }  // extern "C"

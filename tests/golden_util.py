@@ -12,7 +12,7 @@ NORMS = ("ADD_MIN", "EXPONENTIATE", "SCALE_MAX_1")
 
 def fixture_names():
     return sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, "*.npz"))
-                  if not os.path.basename(f).startswith(("kat_", "filter_", "reader_", "laplacian_", "em_", "c2_reference", "c3_reference", "wrap_beyond128", "ref_files_pipeline", "spectral_", "pileup_edges"))
+                  if not os.path.basename(f).startswith(("kat_", "filter_", "reader_", "laplacian_", "em_", "c2_reference", "c3_reference", "wrap_beyond128", "ref_files_pipeline", "spectral_", "pileup_edges", "variant_reference"))
                   and not os.path.basename(f).endswith("_reference_digest.npz"))
 
 

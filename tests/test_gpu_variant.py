@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from secedo_amd.pileup import FlatPileup
+from tests import variant_cases as vc
 from tests import variant_ref as vr
 from tests.clone_tree_gen import clone_tree
 
@@ -24,17 +25,7 @@ def _v():
     return variant
 
 
-def _flat(chromosomes):
-    chr_off, pos, off, idb = [0], [], [0], []
-    for chrom in chromosomes:
-        for p, entries in chrom:
-            pos.append(p)
-            idb.extend(entries)
-            off.append(len(idb))
-        chr_off.append(len(pos))
-    idb = np.asarray(idb, dtype=np.uint32)
-    return FlatPileup(np.asarray(chr_off), np.asarray(pos), np.asarray(off, dtype=np.uint64),
-                      np.arange(len(idb), dtype=np.uint32), idb)
+_flat = vc.flat
 
 
 def _both(tmp_path, name, chromosomes, clusters, fasta, map_file="", prior=1e-3, theta=1e-3):
@@ -353,16 +344,8 @@ def test_cpp_entry_point_equals_python(tmp_path):
     rng = np.random.default_rng(9)
     chroms, clusters = _synthetic(rng, 200, 5, [11, 7, 6], 3)
     p = _flat(chroms)
-    with open(tmp_path / "p.bin", "wb") as f:
-        np.asarray([p.n_chr, p.n_loci, p.n_entries, len(clusters)], dtype=np.uint64).tofile(f)
-        p.chr_locus_off.tofile(f)
-        p.locus_pos.tofile(f)
-        p.locus_entry_off.tofile(f)
-        p.read_ids.tofile(f)
-        p.id_base.astype(np.uint16).tofile(f)
-    with open(tmp_path / "c.bin", "wb") as f:
-        np.asarray([len(clusters)], dtype=np.uint64).tofile(f)
-        clusters.astype(np.uint16).tofile(f)
+    vc.write_flat(str(tmp_path / "p.bin"), p, len(clusters))
+    vc.write_clusters(str(tmp_path / "c.bin"), clusters)
     d_cpp, d_py = str(tmp_path / "cpp"), str(tmp_path / "py")
     subprocess.run([exe, str(tmp_path / "p.bin"), str(tmp_path / "c.bin"), MALE, MALE_MAP, "0.001", "0.01", d_cpp],
                    check=True)

@@ -269,3 +269,21 @@ def test_scores_format():
     assert vr.format_score(0, 0) == "-nan"
     assert vr.format_score(1, 3) == "0.333333"
     assert vr.format_score(0, 5) == "0" and vr.format_score(1, 1) == "1"
+
+
+# --- more than 24 chromosomes -----------------------------------------------------------------------------------------
+
+def test_more_than_24_chromosomes_are_refused_before_anything_is_made(tmp_path):
+    """The VCF lines name chromosomes 1..22, X, Y; the reference asserts on a line for a 25th (id_to_chromosome). The
+    call is refused on its arguments alone: no GPU is touched and no directory is made."""
+    from secedo_amd import _lib
+    from tests import variant_cases as vc
+    locus = [(1, [g << 2 for g in range(12)])]
+    out = tmp_path / "out"
+    with pytest.raises(_lib.SecedoError) as e:
+        _v().variant_calling(vc.flat([locus] * 25), np.ones(12, np.uint16), HAPLOID, "", 1e-3, 0.01, str(out))
+    assert e.value.code == _lib.E_INVALID_ARG and "more than 24 chromosomes (25)" in str(e.value)
+    assert not out.exists()
+    # no cells: nothing is done and nothing is an error, as in the reference
+    _v().variant_calling(vc.flat([locus] * 25), np.zeros(0, np.uint16), HAPLOID, "", 1e-3, 0.01, str(out))
+    assert not out.exists()
