@@ -4,20 +4,20 @@
 // pieces, sorts the pieces by global_bin * n_cells + cell and reduces the runs to the pairs in output order. The pairs
 // of all chromosomes are held until the last one (the .mtx header needs their number), then the summaries run over
 // them and the text of the per-pair, per-cell and per-bin files is formatted on the GPU in ranges, downloaded as it is
-// or deflated by the shared BGZF encoder. What decides numbers and bytes is in bam_depth.hpp.
+// or deflated by the shared BGZF encoder. The record upload and the compaction are bam_host.hpp's, the ranged
+// formatter, the way down and the name upload text_out.hpp's, the temporary files out_files.hpp's. What decides
+// numbers and bytes is in bam_depth.hpp.
 #include "bam_depth.hpp"
 #include "bam_depth_kernels.hpp"
 #include "bam_host.hpp"
 #include "bam_kernels.hpp"
 #include "bam_split.hpp"
 #include "bam_split_kernels.hpp"
-#include "bgzf_encoder.hpp"
+#include "text_out.hpp"
 
 #include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <memory>
 
 namespace {
@@ -41,10 +41,6 @@ struct Result {
 };
 thread_local Result *g_result = nullptr;
 
-constexpr size_t kSlice = 4096;  // members deflated per launch at the most
-constexpr uint64_t kDefaultBatchBytes = 256ull << 20;
-constexpr uint64_t kMaxBatchBytes = 1ull << 30;  // keeps a range's lines and threads well inside 2^31
-
 // What one call asks for, checked.
 struct Request {
     std::vector<std::string> files, values, names;
@@ -55,182 +51,6 @@ struct Request {
     int mode = SECEDO_BAM_DEPTH_READS, dup = SECEDO_BAM_DUPLICATES_KEEP;
     bool bgzf = false, overwrite = false, write = false;
     std::string out_dir;
-};
-
-// The output files: written under a temporary name beside the target, renamed by commit(). Whatever is left
-// uncommitted is removed, the depth/ directory too where this call made it.
-struct OutFiles {
-    std::string dir;
-    bool made_dir = false, committed = false;
-    std::vector<std::string> target, tmp;
-    std::vector<FILE *> f;
-    OutFiles() = default;
-    OutFiles(const OutFiles &) = delete;
-    OutFiles &operator=(const OutFiles &) = delete;
-    ~OutFiles() {
-        for (FILE *x : f)
-            if (x) fclose(x);
-        if (committed) return;
-        for (const std::string &t : tmp) (void)unlink(t.c_str());
-        if (made_dir) (void)rmdir(dir.c_str());
-    }
-    int open() {
-        struct stat st;
-        if (stat(dir.c_str(), &st) != 0) {
-            if (mkdir(dir.c_str(), 0777) != 0) return fail(SECEDO_E_INVALID_ARG, "Could not create " + dir);
-            made_dir = true;
-        } else if (!S_ISDIR(st.st_mode)) {
-            return fail(SECEDO_E_INVALID_ARG, dir + " is not a directory");
-        }
-        const std::string suffix = ".tmp." + std::to_string(long(getpid()));
-        for (const std::string &t : target) {
-            tmp.push_back(t + suffix);
-            f.push_back(fopen(tmp.back().c_str(), "wb"));
-            if (!f.back()) return fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp.back());
-        }
-        return SECEDO_OK;
-    }
-    int append(size_t k, const void *p, size_t n) {
-        if (n && fwrite(p, 1, n, f[k]) != n) return fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp[k]);
-        return SECEDO_OK;
-    }
-    int commit() {
-        for (size_t k = 0; k < f.size(); ++k) {
-            const bool ok = fclose(f[k]) == 0;
-            f[k] = nullptr;
-            if (!ok) return fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp[k]);
-        }
-        // nothing is renamed before every file is complete
-        for (size_t k = 0; k < tmp.size(); ++k)
-            if (rename(tmp[k].c_str(), target[k].c_str()) != 0)
-                return fail(SECEDO_E_INVALID_ARG, "Could not rename " + tmp[k] + " to " + target[k]);
-        committed = true;
-        return SECEDO_OK;
-    }
-};
-
-// One GPU-formatted file: text on the device goes down as it is, or through the encoder, member cuts per call.
-struct TextOut {
-    OutFiles *of;
-    size_t k;
-    bool bgzf;
-    bz::Encoder *enc;
-    hipStream_t s;
-    std::vector<uint8_t> down;
-    Dev<uint8_t> stage;
-
-    // d_text: `total` bytes with bz::kDeflateInSlack readable bytes around them
-    int device(const uint8_t *d_text, uint64_t total) {
-        if (total == 0) return SECEDO_OK;
-        Clock::time_point t0 = Clock::now();
-        g_info.text_bytes += total;
-        if (!bgzf) {
-            down.resize(total);
-            SECEDO_TRY(hipMemcpyAsync(down.data(), d_text, total, hipMemcpyDeviceToHost, s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            g_info.download_ms += ms_lap(t0);
-            SECEDO_CALL(of->append(k, down.data(), total));
-            g_info.write_ms += ms_lap(t0);
-            return SECEDO_OK;
-        }
-        std::vector<bz::DeflateDesc> desc;
-        bz::member_cuts(0, total, &desc);
-        const int rc = enc->run(d_text, desc, s, [&](size_t, uint32_t n, const uint32_t *bytes, uint64_t *at) -> int {
-            uint64_t end = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                at[i] = end;
-                end += bytes[i];
-            }
-            SECEDO_CALL(enc->fetch(end, &enc->bytes, 0));
-            Clock::time_point t1 = Clock::now();
-            SECEDO_CALL(of->append(k, enc->bytes.data(), end));
-            g_info.compressed_bytes += end;
-            g_info.write_ms += ms_since(t1);
-            return SECEDO_OK;
-        });
-        g_info.members += enc->counts.members;
-        g_info.deflate_ms += enc->counts.deflate_ms;
-        g_info.download_ms += enc->counts.download_ms;
-        enc->counts = bz::EncoderCounts{};  // taken
-        return rc;
-    }
-    // text made on the host (a header line): the same way out
-    int host(const std::string &text) {
-        if (!bgzf) {
-            g_info.text_bytes += text.size();
-            return of->append(k, text.data(), text.size());
-        }
-        std::vector<uint8_t> all(bz::kDeflateInSlack, 0);
-        all.insert(all.end(), text.begin(), text.end());
-        all.resize(all.size() + bz::kDeflateInSlack, 0);
-        SECEDO_TRY(stage.alloc(all.size()));
-        SECEDO_TRY(hipMemcpyAsync(stage.p, all.data(), all.size(), hipMemcpyHostToDevice, s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        return device(stage.p + bz::kDeflateInSlack, text.size());
-    }
-    int finish() {
-        if (!bgzf) return SECEDO_OK;
-        const auto eof = bz::eof_member();
-        g_info.compressed_bytes += eof.size();
-        return of->append(k, eof.data(), eof.size());
-    }
-};
-
-// names one after the other on the device
-struct DevNames {
-    Dev<uint8_t> bytes;
-    Dev<uint32_t> off;
-    uint64_t longest = 0;
-    bd::Names view() const { return bd::Names{bytes.p, off.p}; }
-};
-
-int upload_names(const std::vector<std::string> &names, hipStream_t s, DevNames *dn) {
-    std::vector<uint8_t> bytes;
-    std::vector<uint32_t> off{0};
-    for (const std::string &n : names) {
-        bytes.insert(bytes.end(), n.begin(), n.end());
-        off.push_back(uint32_t(bytes.size()));
-        dn->longest = std::max<uint64_t>(dn->longest, n.size());
-    }
-    SECEDO_TRY(dn->bytes.alloc(bytes.size()));
-    SECEDO_TRY(dn->off.alloc(off.size()));
-    if (!bytes.empty()) SECEDO_TRY(hipMemcpyAsync(dn->bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
-    SECEDO_TRY(hipMemcpyAsync(dn->off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
-    SECEDO_TRY(hipStreamSynchronize(s));
-    return SECEDO_OK;
-}
-
-// The lines of items [0, n_items) of one file, in ranges of `per_range` lines: measure, scan, store, out.
-struct Formatter {
-    Dev<uint64_t> len, off;
-    Dev<uint8_t> tmp, text;
-    template <class Measure, class Write>
-    int run(uint64_t n_items, uint64_t per_range, const Measure &measure, const Write &write, TextOut *out,
-            hipStream_t s) {
-        for (uint64_t i0 = 0; i0 < n_items; i0 += per_range) {
-            Clock::time_point t0 = Clock::now();
-            const uint32_t n = uint32_t(std::min<uint64_t>(per_range, n_items - i0));
-            const size_t tb = bam::scan_bytes(uint64_t(n) + 1);
-            SECEDO_TRY(len.grow(size_t(n) + 1, 0, s));
-            SECEDO_TRY(off.grow(size_t(n) + 1, 0, s));
-            SECEDO_TRY(tmp.grow(tb, 0, s));
-            SECEDO_TRY(measure(i0, n, len.p));
-            SECEDO_TRY(bam::exclusive_sum64(tmp.p, tb, len.p, off.p, uint64_t(n) + 1, s));
-            uint64_t total = 0;
-            SECEDO_TRY(hipMemcpyAsync(&total, off.p + n, 8, hipMemcpyDeviceToHost, s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            SECEDO_TRY(text.grow(total + 2 * bz::kDeflateInSlack, 0, s));
-            uint8_t *d_text = text.p + bz::kDeflateInSlack;
-            SECEDO_TRY(hipMemsetAsync(text.p, 0, bz::kDeflateInSlack, s));
-            SECEDO_TRY(hipMemsetAsync(d_text + total, 0, bz::kDeflateInSlack, s));
-            SECEDO_TRY(write(i0, n, off.p, d_text));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            g_info.format_ms += ms_lap(t0);
-            g_info.ranges += 1;
-            SECEDO_CALL(out->device(d_text, total));
-        }
-        return SECEDO_OK;
-    }
 };
 
 // the per-cell counters and the drop counters of the front passes, kept over the chromosomes of one call
@@ -253,37 +73,18 @@ using PairChunks = std::vector<std::unique_ptr<Dev<bd::Pair>>>;
 int depth_chromosome(const Request &rq, const ChrInput &ci, uint32_t ln, uint64_t bin_base, int end_bit,
                      const bam::CellList *cells, Counters *cnt, PairChunks *chunks, hipStream_t s,
                      secedo_bam_times *t) {
-    Clock::time_point t0 = Clock::now();
     std::vector<uint64_t> in_off;
-    std::vector<uint16_t> in_file;
-    for (size_t f = 0; f < ci.roff.size(); ++f)
-        for (size_t k = 0; k < ci.roff[f].size(); ++k) {
-            in_off.push_back(ci.file_base[f] + ci.roff[f][k]);
-            in_file.push_back(uint16_t(f));
-        }
-    if (in_off.size() >= (1ull << 32)) return fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome");
-    const uint32_t n_in = uint32_t(in_off.size());
-    t->walk_ms += ms_lap(t0);
-    if (n_in == 0) return SECEDO_OK;
-
     Dev<uint8_t> d_bytes, tmp;
     Dev<uint64_t> d_in_off;
-    Dev<uint16_t> d_file;
-    SECEDO_TRY(d_bytes.alloc(ci.bytes.size() + 16));
-    SECEDO_TRY(d_in_off.alloc(n_in));
-    SECEDO_TRY(hipMemcpyAsync(d_bytes.p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
-    SECEDO_TRY(hipMemsetAsync(d_bytes.p + ci.bytes.size(), 0, 16, s));
-    SECEDO_TRY(hipMemcpyAsync(d_in_off.p, in_off.data(), n_in * 8ull, hipMemcpyHostToDevice, s));
-    if (!cells) {
-        SECEDO_TRY(d_file.alloc(n_in));
-        SECEDO_TRY(hipMemcpyAsync(d_file.p, in_file.data(), n_in * 2ull, hipMemcpyHostToDevice, s));
-    }
-    SECEDO_TRY(hipStreamSynchronize(s));
-    t->upload_ms += ms_lap(t0);
+    Dev<uint16_t> d_file;  // stays null in tag mode
+    SECEDO_CALL(upload_input_order(ci, s, &in_off, nullptr, &d_bytes, &d_in_off, cells ? nullptr : &d_file, t));
+    const uint32_t n_in = uint32_t(in_off.size());
+    if (n_in == 0) return SECEDO_OK;
+    Clock::time_point t0 = Clock::now();
 
     // steps 1 and 2, the compaction, and with duplicates the order rule 3d's passes need
     Dev<uint64_t> tag_key, key, kc, ks;
-    Dev<uint32_t> tag_sel, sel, scan, vc, vs, dup_keep;
+    Dev<uint32_t> tag_sel, sel, vc, vs, dup_keep;
     Dev<uint16_t> d_cell;
     SECEDO_TRY(key.alloc(n_in));
     SECEDO_TRY(sel.alloc(size_t(n_in) + 1));
@@ -295,32 +96,23 @@ int depth_chromosome(const Request &rq, const ChrInput &ci, uint32_t ln, uint64_
     }
     SECEDO_TRY(bd::depth_front(d_bytes.p, d_in_off.p, n_in, d_file.p, tag_key.p, tag_sel.p, rq.n_cells, rq.require,
                                rq.exclude, d_cell.p, sel.p, key.p, cnt->cell_records.p, cnt->stat.p, s));
-    size_t tb = bam::scan_bytes(uint64_t(n_in) + 1);
-    SECEDO_TRY(tmp.alloc(tb));
-    SECEDO_TRY(scan.alloc(size_t(n_in) + 1));
-    SECEDO_TRY(hipMemsetAsync(sel.p + n_in, 0, 4, s));
-    SECEDO_TRY(bam::exclusive_sum(tmp.p, tb, sel.p, scan.p, uint64_t(n_in) + 1, s));
     uint32_t m = 0;
-    SECEDO_TRY(hipMemcpyAsync(&m, scan.p + n_in, 4, hipMemcpyDeviceToHost, s));
-    SECEDO_TRY(hipStreamSynchronize(s));
+    SECEDO_CALL(compact_selected(key, sel, n_in, s, &m, &kc, &vc));
     if (m == 0) {
         g_info.order_ms += ms_lap(t0);
         return SECEDO_OK;
     }
-    SECEDO_TRY(kc.alloc(m));
-    SECEDO_TRY(vc.alloc(m));
-    SECEDO_TRY(bam::compact_keys(key.p, sel.p, scan.p, n_in, kc.p, vc.p, s));
     const uint32_t *d_val = vc.p;
     if (rq.dup != SECEDO_BAM_DUPLICATES_KEEP) {
         // Sorted by Position (stable over the input order) the records of a cell stand in the pileup's global order,
         // as in secedo_bam_split_clusters_select, so rule 3d's passes choose the pileup's set.
         SECEDO_TRY(ks.alloc(m));
         SECEDO_TRY(vs.alloc(m));
-        tb = bs::split_sort_bytes(m);
+        size_t tb = bs::split_sort_bytes(m);
         SECEDO_TRY(tmp.alloc(tb));
         SECEDO_TRY(bs::split_sort(tmp.p, tb, kc.p, ks.p, vc.p, vs.p, m, 32, s));
         SECEDO_TRY(hipStreamSynchronize(s));
-        key.reset(), sel.reset(), scan.reset(), kc.reset(), vc.reset(), ks.reset(), tmp.reset();
+        key.reset(), sel.reset(), kc.reset(), vc.reset(), ks.reset(), tmp.reset();
         SelStat stat;
         SECEDO_CALL(stat.init(s));
         Dev<uint64_t> v_off;
@@ -340,7 +132,7 @@ int depth_chromosome(const Request &rq, const ChrInput &ci, uint32_t ln, uint64_
     SECEDO_TRY(piece_off.alloc(size_t(m) + 1));
     SECEDO_TRY(bd::depth_count(d_bytes.p, d_in_off.p, d_val, m, d_cell.p, dup_keep.p, rq.min_mapq, ln, rq.S, rq.mode,
                                pieces.p, cnt->cell_counted.p, cnt->stat.p, s));
-    tb = bam::scan_bytes(uint64_t(m) + 1);
+    size_t tb = bam::scan_bytes(uint64_t(m) + 1);
     SECEDO_TRY(tmp.alloc(tb));
     SECEDO_TRY(bam::exclusive_sum64(tmp.p, tb, pieces.p, piece_off.p, uint64_t(m) + 1, s));
     uint64_t n_pieces64 = 0;
@@ -363,7 +155,7 @@ int depth_chromosome(const Request &rq, const ChrInput &ci, uint32_t ln, uint64_
                               bin_base, rq.n_cells, pk.p, pv.p, s));
     SECEDO_TRY(hipStreamSynchronize(s));
     d_bytes.reset(), d_in_off.reset(), d_file.reset(), tag_key.reset(), tag_sel.reset(), key.reset(), sel.reset();
-    scan.reset(), kc.reset(), vc.reset(), vs.reset(), dup_keep.reset(), d_cell.reset(), pieces.reset();
+    kc.reset(), vc.reset(), vs.reset(), dup_keep.reset(), d_cell.reset(), pieces.reset();
     piece_off.reset();
 
     // sort and reduce
@@ -416,48 +208,50 @@ int depth_chromosome(const Request &rq, const ChrInput &ci, uint32_t ln, uint64_
 
 int write_files(const Request &rq, const bd::Layout &lay, const std::vector<bs::Ref> &refs, const Result &res,
                 const bd::Pair *d_pairs, const bd::CellRow *d_rows, const uint64_t *d_table, OutFiles *of,
-                hipStream_t s) {
+                TextCounts *tc, hipStream_t s) {
     Clock::time_point t0 = Clock::now();
-    SECEDO_CALL(of->open());
+    SECEDO_CALL(out_error(of->open()));
     {  // the two host-written files
         std::string bed, samples;
         for (size_t g = 0; g < res.bin_chr.size(); ++g)
             bed += bd::bed_line(refs[res.bin_chr[g]].name, res.bin_start[g], res.bin_end[g]);
         for (const std::string &n : rq.names) samples += n + "\n";
-        SECEDO_CALL(of->append(0, bed.data(), bed.size()));
-        SECEDO_CALL(of->append(1, samples.data(), samples.size()));
+        SECEDO_CALL(out_error(of->append(0, bed.data(), bed.size())));
+        SECEDO_CALL(out_error(of->append(1, samples.data(), samples.size())));
     }
     g_info.write_ms += ms_lap(t0);
-    const uint64_t batch = std::min(env_u64("SECEDO_DEPTH_BATCH_BYTES", kDefaultBatchBytes), kMaxBatchBytes);
+    const uint64_t batch = text_batch_bytes("SECEDO_DEPTH_BATCH_BYTES");
+    const Scan64 scan{bam::scan_bytes, bam::exclusive_sum64};
     bz::Encoder enc(kSlice);
     Formatter fm;
     DevNames cell_names, chr_names;
     SECEDO_CALL(upload_names(rq.names, s, &cell_names));
     {
-        TextOut out{of, 2, rq.bgzf, &enc, s, {}, {}};
+        TextOut out{of, 2, rq.bgzf, &enc, s, tc, {}, {}};
         SECEDO_CALL(out.host(bd::mtx_header(lay.n_bins(), rq.n_cells, res.pairs.size())));
         SECEDO_CALL(fm.run(
-            res.pairs.size(), bd::lines_per_range(batch, bd::kMaxMtxLine),
+            res.pairs.size(), bd::lines_per_range(batch, bd::kMaxMtxLine), bd::kMaxMtxLine,
             [&](uint64_t i0, uint32_t n, uint64_t *len) { return bd::mtx_measure(d_pairs, i0, n, len, s); },
             [&](uint64_t i0, uint32_t n, const uint64_t *off, uint8_t *text) {
                 return bd::mtx_write(d_pairs, i0, n, off, text, s);
             },
-            &out, s));
+            scan, &out, s));
         SECEDO_CALL(out.finish());
     }
     {
-        TextOut out{of, 3, rq.bgzf, &enc, s, {}, {}};
+        TextOut out{of, 3, rq.bgzf, &enc, s, tc, {}, {}};
         SECEDO_CALL(out.host(bd::cells_header()));
         const bd::Names names = cell_names.view();
+        const uint64_t max_line = bd::max_cell_line(cell_names.longest);
         SECEDO_CALL(fm.run(
-            rq.n_cells, bd::lines_per_range(batch, bd::max_cell_line(cell_names.longest)),
+            rq.n_cells, bd::lines_per_range(batch, max_line), max_line,
             [&](uint64_t i0, uint32_t n, uint64_t *len) {
                 return bd::cells_measure(d_rows, names, uint32_t(i0), n, len, s);
             },
             [&](uint64_t i0, uint32_t n, const uint64_t *off, uint8_t *text) {
                 return bd::cells_write(d_rows, names, uint32_t(i0), n, off, text, s);
             },
-            &out, s));
+            scan, &out, s));
         SECEDO_CALL(out.finish());
     }
     if (rq.n_clusters) {
@@ -474,19 +268,20 @@ int write_files(const Request &rq, const bd::Layout &lay, const std::vector<bs::
         SECEDO_TRY(hipStreamSynchronize(s));
         const bd::BinTable bt{d_base.p, d_len.p, uint32_t(lay.chr.size()), rq.S, chr_names.view(), d_table,
                               rq.n_clusters};
-        TextOut out{of, 4, rq.bgzf, &enc, s, {}, {}};
+        const uint64_t max_line = bd::max_cluster_line(chr_names.longest, rq.n_clusters);
+        TextOut out{of, 4, rq.bgzf, &enc, s, tc, {}, {}};
         SECEDO_CALL(out.host(bd::clusters_header(rq.n_clusters)));
         SECEDO_CALL(fm.run(
-            lay.n_bins(), bd::lines_per_range(batch, bd::max_cluster_line(chr_names.longest, rq.n_clusters)),
+            lay.n_bins(), bd::lines_per_range(batch, max_line), max_line,
             [&](uint64_t i0, uint32_t n, uint64_t *len) { return bd::clusters_measure(bt, i0, n, len, s); },
             [&](uint64_t i0, uint32_t n, const uint64_t *off, uint8_t *text) {
                 return bd::clusters_write(bt, i0, n, off, text, s);
             },
-            &out, s));
+            scan, &out, s));
         SECEDO_CALL(out.finish());
     }
     (void)ms_lap(t0);
-    SECEDO_CALL(of->commit());
+    SECEDO_CALL(out_error(of->commit()));
     g_info.write_ms += ms_lap(t0);
     return SECEDO_OK;
 }
@@ -679,7 +474,15 @@ int depth(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     SECEDO_TRY(hipStreamSynchronize(s));
     g_info.count_ms += ms_lap(t0);
 
-    if (rq.write) SECEDO_CALL(write_files(rq, lay, refs, *res, d_pairs.p, d_rows.p, d_table.p, &of, s));
+    if (rq.write) {
+        TextCounts tc;  // what the text layer did, also where it failed
+        const int rc = write_files(rq, lay, refs, *res, d_pairs.p, d_rows.p, d_table.p, &of, &tc, s);
+        g_info.text_bytes += tc.text_bytes, g_info.compressed_bytes += tc.compressed_bytes;
+        g_info.members += tc.members, g_info.ranges += tc.ranges;
+        g_info.format_ms += tc.format_ms, g_info.deflate_ms += tc.deflate_ms;
+        g_info.download_ms += tc.download_ms, g_info.write_ms += tc.write_ms;
+        SECEDO_CALL(rc);
+    }
     delete g_result;
     g_result = res.release();
     tl.device_ms += g_info.order_ms + g_info.count_ms + g_info.format_ms + g_info.deflate_ms + g_info.download_ms;

@@ -157,6 +157,13 @@ DEPTH_HD void put_bytes(Sink &s, const uint8_t *p, uint32_t n) {
     for (uint32_t k = 0; k < n; ++k) s.put(char(p[k]));
 }
 
+// names one after the other, as the kernels of both table writers read them (text_out.hpp uploads them):
+// off[i] .. off[i + 1] is name i
+struct Names {
+    const uint8_t *bytes;
+    const uint32_t *off;
+};
+
 // depth.counts.mtx: "<bin + 1>\t<cell + 1>\t<value>\n"
 template <class Sink>
 DEPTH_HD void put_mtx_line(Sink &s, uint32_t bin, uint32_t cell, uint64_t value) {

@@ -80,12 +80,8 @@ hipError_t depth_summaries(const Pair *d_pair, uint64_t n, CellRow *d_rows, cons
                            uint32_t n_clusters, uint64_t *d_table, hipStream_t s);
 
 // ---- text, count then store (text_sink.hpp). The items [i0, i0 + n) of one file; measure gives d_len[k] (n + 1
-// entries, the last 0), write stores item k's line at d_out + d_off[k] (d_off = the exclusive sum of d_len).
-
-struct Names {  // names one after the other; off[i] .. off[i + 1] is name i
-    const uint8_t *bytes;
-    const uint32_t *off;
-};
+// entries, the last 0), write stores item k's line at d_out + d_off[k] (d_off = the exclusive sum of d_len). The host
+// loop over the ranges of a file is text_out.hpp's Formatter; Names is bam_depth.hpp's.
 
 // depth.counts.mtx: item = pair
 hipError_t mtx_measure(const Pair *d_pair, uint64_t i0, uint32_t n, uint64_t *d_len, hipStream_t s);

@@ -1,5 +1,8 @@
-// bam_host.hpp -- what the two host files of include/secedo_bam.h share: bam_input.cpp reads the BAM and SAM files
-// into one ChrInput per requested chromosome, bam_pileup.cpp turns those into the pileup. Internal, nothing exported.
+// bam_host.hpp -- what the host files of include/secedo_bam.h share: bam_input.cpp reads the BAM and SAM files
+// into one ChrInput per requested chromosome, bam_pileup.cpp turns those into the pileup, bam_split.cpp into the
+// per-cluster BAMs and bam_depth.cpp into the depth tables; the three take a chromosome's records to the device and
+// compact the selected ones through the functions declared here (bam_pileup.cpp defines them). Internal, nothing
+// exported.
 #pragma once
 
 #include "bam_batch.hpp"
@@ -85,7 +88,7 @@ int read_file_header(const std::string &path, FileHeader *h);
 int read_reference_lists(const std::vector<std::string> &files, std::vector<bamsplit::Ref> *first,
                          std::vector<uint8_t> *first_list, std::vector<std::string> *texts);
 
-// ---- what the calls of bam_pileup.cpp and bam_split.cpp share of tag mode and of their argument checks
+// ---- what the calls of bam_pileup.cpp, bam_split.cpp and bam_depth.cpp share of tag mode and of their argument checks
 
 // tag: two characters [A-Za-z][A-Za-z0-9] (SAM spec 1.5)
 int check_tag(const char *tag);
@@ -102,7 +105,8 @@ struct DevCells {
 };
 int upload_cells(const char tag[2], const std::vector<std::string> &values, hipStream_t s, DevCells *dc);
 
-// ---- rules 3c and 3d of bam_kernels.hip, shared by the pileup calls and secedo_bam_split_clusters_select
+// ---- rules 3c and 3d of bam_kernels.hip, shared by the pileup calls, secedo_bam_split_clusters_select and
+// secedo_bam_depth
 
 // The device counters of the front passes (bam::Sel slots), added to a call's secedo_bam_select_info when a
 // chromosome's passes are done. Stays unallocated, and adds nothing, with both rules off.
@@ -129,14 +133,47 @@ struct SelStat {
     }
 };
 
-// Selected (key, input ordinal) pairs of d_key / d_sel (n records; d_sel has n + 1 entries), sorted by key (stable):
-// -> *n_sel, d_ks, d_vs.
-int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
-                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs);
 // Rule 3d over the rs.n >= 1 records of rs, whose order within a cell is the global order: (*keep)[o] (rs.n + 1
 // entries allocated) = 0 for every record of a template that is not the best of its key, 1 elsewhere. d_stat: Sel
 // counters (kSelTemplates, kSelLarge, kSelDupTemplates, kSelDupRecords). The passes' arrays are freed on return.
 int duplicate_keep(const bam::Records &rs, unsigned long long *d_stat, hipStream_t s, Dev<uint32_t> *keep);
+
+// ---- what the pileup calls, bam_split.cpp and bam_depth.cpp share of a chromosome's way to the device
+
+// Where the records of the pileup's global order come from, for error messages and the .map.
+struct Order {
+    uint32_t n = 0, last_chunk = 0;
+    int32_t min_pos = INT32_MAX;
+    std::vector<uint64_t> ord_off;  // per-file mode: per ordinal byte offset, input file, record index
+    std::vector<uint16_t> ord_file;
+    std::vector<uint64_t> ord_idx;
+    std::vector<uint32_t> in_file;  // tag mode: per input ordinal; d_ord maps an ordinal to its input ordinal
+    std::vector<uint64_t> in_idx;
+    Dev<uint32_t> d_ord;  // per-file mode: null until rule 3c or 3d dropped a record, then the ordinal each had before
+};
+
+// a chromosome's records are numbered in 32 bits
+inline int check_record_count(uint64_t n) {
+    return n >= (1ull << 32) ? fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome") : SECEDO_OK;
+}
+
+// zero bytes behind the last record on the device: the split's gather reads whole aligned words
+constexpr size_t kRecordSlack = 16;
+
+// The chromosome's records on the device in input order (file, record): ci.bytes and kRecordSlack zero bytes ->
+// d_bytes, the byte offset of each record -> in_off / d_in_off (check_record_count holds). d_file (may be null) takes
+// the input file of each record; ord (may be null) the input file and record index of each, on the host. t (may be
+// null): walk_ms and upload_ms are added to. A chromosome without records is uploaded like any other.
+int upload_input_order(const ChrInput &ci, hipStream_t s, std::vector<uint64_t> *in_off, Order *ord,
+                       Dev<uint8_t> *d_bytes, Dev<uint64_t> *d_in_off, Dev<uint16_t> *d_file, secedo_bam_times *t);
+
+// The selected (key, input ordinal) pairs of d_key / d_sel (n records; d_sel has n + 1 entries, the last is zeroed
+// here) in input order: -> *n_sel, d_kc, d_vc.
+int compact_selected(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
+                     Dev<uint64_t> *d_kc, Dev<uint32_t> *d_vc);
+// compact_selected, then sorted by key (stable): -> *n_sel, d_ks, d_vs.
+int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
+                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs);
 
 // ---- what bam_input.cpp (host inflate, host walk) and bam_device_input.cpp (device inflate, device walk) share
 

@@ -170,28 +170,69 @@ int upload_cells(const char tag[2], const std::vector<std::string> &values, hipS
     return SECEDO_OK;
 }
 
-// Selected (key, input ordinal) pairs of d_key / d_sel (n records), sorted by key: -> *n_sel, d_ks, d_vs.
-int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
-                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs) {
+// The chromosome's records to the device in input order (bam_host.hpp), for the pileup, the split and the depth.
+int upload_input_order(const ChrInput &ci, hipStream_t s, std::vector<uint64_t> *in_off, Order *ord,
+                       Dev<uint8_t> *d_bytes, Dev<uint64_t> *d_in_off, Dev<uint16_t> *d_file, secedo_bam_times *t) {
+    Clock::time_point t0 = Clock::now();
+    std::vector<uint16_t> in_file;
+    for (size_t f = 0; f < ci.roff.size(); ++f)
+        for (size_t k = 0; k < ci.roff[f].size(); ++k) {
+            in_off->push_back(ci.file_base[f] + ci.roff[f][k]);
+            if (d_file) in_file.push_back(uint16_t(f));
+            if (ord) ord->in_file.push_back(uint32_t(f));
+            if (ord) ord->in_idx.push_back(ci.ridx[f][k]);
+        }
+    SECEDO_CALL(check_record_count(in_off->size()));
+    const uint32_t n_in = uint32_t(in_off->size());
+    if (t) t->walk_ms += ms_lap(t0);
+    SECEDO_TRY(d_bytes->alloc(ci.bytes.size() + kRecordSlack));
+    SECEDO_TRY(d_in_off->alloc(n_in));
+    if (!ci.bytes.empty())
+        SECEDO_TRY(hipMemcpyAsync(d_bytes->p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipMemsetAsync(d_bytes->p + ci.bytes.size(), 0, kRecordSlack, s));
+    if (n_in) SECEDO_TRY(hipMemcpyAsync(d_in_off->p, in_off->data(), n_in * 8ull, hipMemcpyHostToDevice, s));
+    if (d_file) {
+        SECEDO_TRY(d_file->alloc(n_in));
+        if (n_in) SECEDO_TRY(hipMemcpyAsync(d_file->p, in_file.data(), n_in * 2ull, hipMemcpyHostToDevice, s));
+    }
+    SECEDO_TRY(hipStreamSynchronize(s));
+    if (t) t->upload_ms += ms_lap(t0);
+    return SECEDO_OK;
+}
+
+// The selected (key, input ordinal) pairs of d_key / d_sel in input order (bam_host.hpp).
+int compact_selected(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
+                     Dev<uint64_t> *d_kc, Dev<uint32_t> *d_vc) {
     using namespace secedo::bam;
-    Dev<uint32_t> scan, vc;
-    Dev<uint64_t> kc;
+    Dev<uint32_t> scan;
     Dev<uint8_t> tmp;
-    size_t tb = scan_bytes(uint64_t(n) + 1);
+    const size_t tb = scan_bytes(uint64_t(n) + 1);
     SECEDO_TRY(tmp.alloc(tb));
-    SECEDO_TRY(scan.alloc(n + 1));
+    SECEDO_TRY(scan.alloc(size_t(n) + 1));
     SECEDO_TRY(hipMemsetAsync(d_sel.p + n, 0, 4, s));
     SECEDO_TRY(exclusive_sum(tmp.p, tb, d_sel.p, scan.p, uint64_t(n) + 1, s));
     *n_sel = 0;
     SECEDO_TRY(hipMemcpyAsync(n_sel, scan.p + n, 4, hipMemcpyDeviceToHost, s));
     SECEDO_TRY(hipStreamSynchronize(s));
+    SECEDO_TRY(d_kc->alloc(*n_sel));
+    SECEDO_TRY(d_vc->alloc(*n_sel));
+    SECEDO_TRY(compact_keys(d_key.p, d_sel.p, scan.p, n, d_kc->p, d_vc->p, s));
+    SECEDO_TRY(hipStreamSynchronize(s));  // scan and tmp go with this scope
+    return SECEDO_OK;
+}
+
+// compact_selected, then sorted by key: -> *n_sel, d_ks, d_vs.
+int compact_and_sort(const Dev<uint64_t> &d_key, Dev<uint32_t> &d_sel, uint32_t n, hipStream_t s, uint32_t *n_sel,
+                     Dev<uint64_t> *d_ks, Dev<uint32_t> *d_vs) {
+    using namespace secedo::bam;
+    Dev<uint32_t> vc;
+    Dev<uint64_t> kc;
+    Dev<uint8_t> tmp;
+    SECEDO_CALL(compact_selected(d_key, d_sel, n, s, n_sel, &kc, &vc));
     const uint32_t m = *n_sel;
-    SECEDO_TRY(kc.alloc(m));
-    SECEDO_TRY(vc.alloc(m));
     SECEDO_TRY(d_ks->alloc(m));
     SECEDO_TRY(d_vs->alloc(m));
-    SECEDO_TRY(compact_keys(d_key.p, d_sel.p, scan.p, n, kc.p, vc.p, s));
-    tb = sort_pairs_bytes(m);
+    const size_t tb = sort_pairs_bytes(m);
     SECEDO_TRY(tmp.alloc(tb));
     SECEDO_TRY(sort_pairs(tmp.p, tb, kc.p, d_ks->p, vc.p, d_vs->p, m, s));  // radix sort: stable
     SECEDO_TRY(hipStreamSynchronize(s));
@@ -256,47 +297,6 @@ int duplicate_keep(const bam::Records &rs, unsigned long long *d_stat, hipStream
 
 namespace {
 
-// Where the records of the global order come from, for error messages and the .map.
-struct Order {
-    uint32_t n = 0, last_chunk = 0;
-    int32_t min_pos = INT32_MAX;
-    std::vector<uint64_t> ord_off;  // per-file mode: per ordinal byte offset, input file, record index
-    std::vector<uint16_t> ord_file;
-    std::vector<uint64_t> ord_idx;
-    std::vector<uint32_t> in_file;  // tag mode: per input ordinal; d_ord maps an ordinal to its input ordinal
-    std::vector<uint64_t> in_idx;
-    Dev<uint32_t> d_ord;  // per-file mode: null until rule 3c or 3d dropped a record, then the ordinal each had before
-};
-
-int check_record_count(uint64_t n) {
-    return n >= (1ull << 32) ? fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome") : SECEDO_OK;
-}
-
-// The chromosome's records on the device in input order (file, record): ci.bytes -> d_bytes and the byte offset of
-// each record -> in_off / d_in_off; ord (may be null) takes the input file and record index of each.
-int upload_input_order(const ChrInput &ci, hipStream_t s, std::vector<uint64_t> *in_off, Order *ord,
-                       Dev<uint8_t> *d_bytes, Dev<uint64_t> *d_in_off, secedo_bam_times *t) {
-    Clock::time_point t0 = Clock::now();
-    for (size_t f = 0; f < ci.roff.size(); ++f)
-        for (size_t k = 0; k < ci.roff[f].size(); ++k) {
-            in_off->push_back(ci.file_base[f] + ci.roff[f][k]);
-            if (ord) ord->in_file.push_back(uint32_t(f));
-            if (ord) ord->in_idx.push_back(ci.ridx[f][k]);
-        }
-    SECEDO_CALL(check_record_count(in_off->size()));
-    const uint32_t n_in = uint32_t(in_off->size());
-    if (t) t->walk_ms += ms_since(t0);
-    t0 = Clock::now();
-    SECEDO_TRY(d_bytes->alloc(ci.bytes.size()));
-    SECEDO_TRY(d_in_off->alloc(n_in));
-    if (!ci.bytes.empty())
-        SECEDO_TRY(hipMemcpyAsync(d_bytes->p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
-    if (n_in) SECEDO_TRY(hipMemcpyAsync(d_in_off->p, in_off->data(), n_in * 8ull, hipMemcpyHostToDevice, s));
-    SECEDO_TRY(hipStreamSynchronize(s));
-    if (t) t->upload_ms += ms_since(t0);
-    return SECEDO_OK;
-}
-
 // Tag mode: the records in input order go up, the device selects the listed cells and sorts them into the global
 // order (chunk, cell, Position, file, record) -> d_off / d_cell of the selected records.
 int order_by_cell(const ChrInput &ci, const CellList &L, const Select &sl, unsigned long long *d_stat, hipStream_t s,
@@ -304,7 +304,7 @@ int order_by_cell(const ChrInput &ci, const CellList &L, const Select &sl, unsig
                   secedo_bam_times *t) {
     std::vector<uint64_t> in_off;
     Dev<uint64_t> d_in_off;
-    SECEDO_CALL(upload_input_order(ci, s, &in_off, ord, d_bytes, &d_in_off, t));
+    SECEDO_CALL(upload_input_order(ci, s, &in_off, ord, d_bytes, &d_in_off, nullptr, t));
     const uint32_t n_in = uint32_t(in_off.size());
     const Clock::time_point t0 = Clock::now();
     Dev<uint64_t> key, ks;
@@ -910,7 +910,7 @@ int count_values(const ChrInput &ci, const char *tag, const Select &sl, hipStrea
     Dev<uint8_t> d_bytes, tmp;
     Dev<uint64_t> d_in_off, key, ks, voff;
     Dev<uint32_t> sel, vs, run, cnt, vlen;
-    SECEDO_CALL(upload_input_order(ci, s, &in_off, nullptr, &d_bytes, &d_in_off, nullptr));
+    SECEDO_CALL(upload_input_order(ci, s, &in_off, nullptr, &d_bytes, &d_in_off, nullptr, nullptr));
     const uint32_t n_in = uint32_t(in_off.size());
     if (n_in == 0) return SECEDO_OK;
     SECEDO_TRY(key.alloc(n_in));

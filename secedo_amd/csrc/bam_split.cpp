@@ -2,8 +2,8 @@
 // cluster of a clustering. The inputs come through the pileup's input layer (bam_host.hpp: load_inputs, one ChrInput
 // per requested chromosome); per chromosome the records go up in input order and bam_split_kernels.hip turns them into
 // one stream, cluster after cluster, which the BGZF encoder (bgzf_deflate_kernels.hip) deflates member by member. Only
-// compressed bytes come back; they are appended to the clusters' temporary files. What decides bytes is in
-// bam_split.hpp. secedo_bam_split_clusters_rg is the same call with a gather that edits the records on
+// compressed bytes come back; they are appended to the clusters' temporary files (out_files.hpp, reopened per append).
+// The record upload and the compaction are bam_host.hpp's. What decides bytes is in bam_split.hpp. secedo_bam_split_clusters_rg is the same call with a gather that edits the records on
 // the way: every record gets RG:Z:<its cell's name>, the header one @RG line per cell of the cluster.
 // secedo_bam_split_clusters_select selects records on the way: the flag filter in front of the compaction,
 // rule 3d's passes (bam_host.hpp: duplicate_keep) over the sorted records, whose choice is removed before the lengths
@@ -12,13 +12,11 @@
 #include "bam_kernels.hpp"
 #include "bam_split.hpp"
 #include "bam_split_kernels.hpp"
-#include "bgzf_encoder.hpp"
+#include "text_out.hpp"
 
 #include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <cstdio>
 
 namespace {
 
@@ -31,8 +29,6 @@ thread_local secedo_bam_split_info g_split{};
 thread_local secedo_bam_split_rg_info g_rg{};
 thread_local secedo_bam_select_info g_sel{};
 
-// Members deflated per launch at the most: 256 MiB of slots, whatever the chromosome's size.
-constexpr size_t kSlice = 4096;
 // the gather's stream lies behind this much room (the encoder's 16-byte loads); keeps the stream 16-byte aligned
 constexpr uint64_t kFront = bz::kDeflateInSlack;
 static_assert(kFront % bs::kGatherVec == 0, "the gather stores whole aligned vectors");
@@ -41,48 +37,6 @@ bool exists(const std::string &path) {
     struct stat st;
     return stat(path.c_str(), &st) == 0;
 }
-
-// The clusters' files: written under a temporary name beside the target, renamed by commit(). Whatever is left
-// uncommitted is removed. No file stays open between appends: there may be more clusters than descriptors.
-struct OutFiles {
-    std::vector<std::string> target, tmp;
-    bool committed = false;
-    OutFiles() = default;
-    OutFiles(const OutFiles &) = delete;
-    OutFiles &operator=(const OutFiles &) = delete;
-    ~OutFiles() {
-        if (!committed)
-            for (const std::string &t : tmp) (void)unlink(t.c_str());
-    }
-    int write(size_t k, const char *mode, const uint8_t *p, size_t n) {
-        FILE *f = fopen(tmp[k].c_str(), mode);
-        const bool ok = f && fwrite(p, 1, n, f) == n;
-        if ((f && fclose(f) != 0) || !ok) return fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp[k]);
-        return SECEDO_OK;
-    }
-    int open() {
-        const std::string suffix = ".tmp." + std::to_string(long(getpid()));
-        for (const std::string &t : target) {
-            tmp.push_back(t + suffix);
-            SECEDO_CALL(write(tmp.size() - 1, "wb", nullptr, 0));
-        }
-        return SECEDO_OK;
-    }
-    int append(size_t k, const uint8_t *p, size_t n) {
-        SECEDO_CALL(write(k, "ab", p, n));
-        g_split.compressed_bytes += n;
-        return SECEDO_OK;
-    }
-    int commit() {
-        // nothing is renamed before every file is complete; a rename that fails leaves the targets before it, which
-        // are complete files, and removes the rest
-        for (size_t k = 0; k < tmp.size(); ++k)
-            if (rename(tmp[k].c_str(), target[k].c_str()) != 0)
-                return fail(SECEDO_E_INVALID_ARG, "Could not rename " + tmp[k] + " to " + target[k]);
-        committed = true;
-        return SECEDO_OK;
-    }
-};
 
 // The members desc of the text at d_text go through the encoder (kept over the header and the chromosomes of one
 // call) and member k is appended to file owner[k]; owners ascend, so every file gets its members in stream order.
@@ -100,9 +54,10 @@ int encode_to_files(bz::Encoder *enc, const uint8_t *d_text, const std::vector<b
             uint32_t e = k + 1;
             while (e < n && owner[b0 + e] == owner[b0 + k]) ++e;
             const uint64_t stop = e < n ? at[e] : end;
-            SECEDO_CALL(of->append(owner[b0 + k], enc->bytes.data() + at[k], stop - at[k]));
+            SECEDO_CALL(out_error(of->append(owner[b0 + k], enc->bytes.data() + at[k], stop - at[k])));
             k = e;
         }
+        g_split.compressed_bytes += end;
         g_split.write_ms += ms_since(t0);
         return SECEDO_OK;
     });
@@ -156,34 +111,14 @@ int upload_suffixes(const std::vector<std::string> &names, hipStream_t s, DevSuf
 // One chromosome: its records in HBM in input order -> the stream -> members appended to the clusters' files.
 int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList *cells, const uint16_t *d_cell_cluster,
                      const DevSuffixes *suffixes, bz::Encoder *enc, OutFiles *of, hipStream_t s, secedo_bam_times *t) {
-    Clock::time_point t0 = Clock::now();
     std::vector<uint64_t> in_off;
-    std::vector<uint16_t> in_file;
-    for (size_t f = 0; f < ci.roff.size(); ++f)
-        for (size_t k = 0; k < ci.roff[f].size(); ++k) {
-            in_off.push_back(ci.file_base[f] + ci.roff[f][k]);
-            in_file.push_back(uint16_t(f));
-        }
-    if (in_off.size() >= (1ull << 32)) return fail(SECEDO_E_LIMIT, "more than 2^32 records in one chromosome");
-    const uint32_t n_in = uint32_t(in_off.size());
-    t->walk_ms += ms_lap(t0);
-    if (n_in == 0) return SECEDO_OK;
-
-    // the gather reads whole aligned dwords: room behind the last record
     Dev<uint8_t> d_bytes, tmp;
     Dev<uint64_t> d_in_off;
-    Dev<uint16_t> d_file;
-    SECEDO_TRY(d_bytes.alloc(ci.bytes.size() + 16));
-    SECEDO_TRY(d_in_off.alloc(n_in));
-    SECEDO_TRY(hipMemcpyAsync(d_bytes.p, ci.bytes.data(), ci.bytes.size(), hipMemcpyHostToDevice, s));
-    SECEDO_TRY(hipMemsetAsync(d_bytes.p + ci.bytes.size(), 0, 16, s));
-    SECEDO_TRY(hipMemcpyAsync(d_in_off.p, in_off.data(), n_in * 8ull, hipMemcpyHostToDevice, s));
-    if (!cells) {
-        SECEDO_TRY(d_file.alloc(n_in));
-        SECEDO_TRY(hipMemcpyAsync(d_file.p, in_file.data(), n_in * 2ull, hipMemcpyHostToDevice, s));
-    }
-    SECEDO_TRY(hipStreamSynchronize(s));
-    t->upload_ms += ms_lap(t0);
+    Dev<uint16_t> d_file;  // stays null in tag mode
+    SECEDO_CALL(upload_input_order(ci, s, &in_off, nullptr, &d_bytes, &d_in_off, cells ? nullptr : &d_file, t));
+    const uint32_t n_in = uint32_t(in_off.size());
+    if (n_in == 0) return SECEDO_OK;
+    Clock::time_point t0 = Clock::now();
 
     // keys, compaction, order
     const uint32_t n_cells = uint32_t(rq.cell_cluster.size());
@@ -216,26 +151,17 @@ int split_chromosome(const Request &rq, const ChrInput &ci, const bam::CellList 
         SECEDO_TRY(bs::split_and(sel.p, pass.p, n_in, s));
         SECEDO_TRY(hipStreamSynchronize(s));  // pass goes with this scope
     }
-    size_t tb = bam::scan_bytes(uint64_t(n_in) + 1);
-    SECEDO_TRY(tmp.alloc(tb));
-    SECEDO_TRY(scan.alloc(size_t(n_in) + 1));
-    SECEDO_TRY(hipMemsetAsync(sel.p + n_in, 0, 4, s));
-    SECEDO_TRY(bam::exclusive_sum(tmp.p, tb, sel.p, scan.p, uint64_t(n_in) + 1, s));
     uint32_t m = 0;
-    SECEDO_TRY(hipMemcpyAsync(&m, scan.p + n_in, 4, hipMemcpyDeviceToHost, s));
-    SECEDO_TRY(hipStreamSynchronize(s));
+    SECEDO_CALL(compact_selected(key, sel, n_in, s, &m, &kc, &vc));
     g_split.dropped_records += n_in - m;
     if (m == 0) {
         SECEDO_CALL(take_stats());
         g_split.order_ms += ms_lap(t0);
         return SECEDO_OK;
     }
-    SECEDO_TRY(kc.alloc(m));
-    SECEDO_TRY(vc.alloc(m));
     SECEDO_TRY(ks.alloc(m));
     SECEDO_TRY(vs.alloc(m));
-    SECEDO_TRY(bam::compact_keys(key.p, sel.p, scan.p, n_in, kc.p, vc.p, s));
-    tb = bs::split_sort_bytes(m);
+    size_t tb = bs::split_sort_bytes(m);
     SECEDO_TRY(tmp.alloc(tb));
     SECEDO_TRY(bs::split_sort(tmp.p, tb, kc.p, ks.p, vc.p, vs.p, m, bs::key_bits(rq.n_clusters - 1), s));
     // Rule 2. Within a cell the sorted records stand in the pileup's global order, so rule 3d's passes over them choose
@@ -474,6 +400,7 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode))
         return fail(SECEDO_E_INVALID_ARG, dir + " is not a directory");
     OutFiles of;
+    of.keep_open = false;  // there may be more clusters than descriptors
     for (uint32_t k = 0; k < rq.n_clusters; ++k) {
         of.target.push_back(dir + "/cluster_" + std::to_string(k) + ".bam");
         if (!overwrite && exists(of.target.back()))
@@ -498,7 +425,7 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     if (rq.rg) SECEDO_CALL(upload_suffixes(rq.names, s, &ds));
     SECEDO_TRY(hipStreamSynchronize(s));
 
-    SECEDO_CALL(of.open());
+    SECEDO_CALL(out_error(of.open()));
     SECEDO_CALL(write_headers(headers, &enc, &of, s));
     for (uint32_t c = 0; c < n_chr; ++c) {
         SECEDO_CALL(split_chromosome(rq, in.chrs[c], tag ? &dc.list : nullptr, d_cc.p, rq.rg ? &ds : nullptr, &enc, &of,
@@ -507,8 +434,9 @@ int split(const char *const *bam_files, uint32_t n_files, const uint32_t *chromo
     }
     Clock::time_point t0 = Clock::now();
     const auto eof = bz::eof_member();
-    for (uint32_t k = 0; k < rq.n_clusters; ++k) SECEDO_CALL(of.append(k, eof.data(), eof.size()));
-    SECEDO_CALL(of.commit());
+    for (uint32_t k = 0; k < rq.n_clusters; ++k) SECEDO_CALL(out_error(of.append(k, eof.data(), eof.size())));
+    g_split.compressed_bytes += uint64_t(rq.n_clusters) * eof.size();
+    SECEDO_CALL(out_error(of.commit()));
     g_split.write_ms += ms_since(t0);
     tl.device_ms += g_split.order_ms + g_split.gather_ms + g_split.deflate_ms + g_split.download_ms;
     tl.write_ms += g_split.write_ms;

@@ -3,21 +3,21 @@
 // layer (fasta_source.cpp) and the double-buffered stager (fasta_stage.hpp); per range the scans of fasta_kernels.hip
 // give every chunk its entry state and sequence ordinal and the host its header slots, the host names the contigs and
 // builds the piece table, and k_compose (genome_bins_kernels.hip) counts the text into the bins x 6 table. The host
-// keeps what is serial and small: names, lengths, the selection. What decides numbers and bytes is in genome_bins.hpp.
+// keeps what is serial and small: names, lengths, the selection. The file's lines go out through text_out.hpp (the
+// ranged formatter, the way down, the name upload) into a temporary file of out_files.hpp. What decides numbers and
+// bytes is in genome_bins.hpp.
 //
 // Which contigs are selected, and so where a contig's bins begin in selection order, is known only at the end of the
 // file. The ranges therefore count into a table laid out in file order over the contigs that can still be selected
 // (all first-of-their-name ones, or the listed names): a contig's first bin there is known when its header is, since
 // every contig in front of it has ended. With a list of names the rows are moved into the listed order at the end,
 // one device copy per contig.
-#include "bgzf_encoder.hpp"
 #include "fasta_stage.hpp"
 #include "genome_bins_kernels.hpp"
+#include "text_out.hpp"
 
 #include <sys/stat.h>
-#include <unistd.h>
 
-#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <set>
@@ -39,108 +39,7 @@ struct Result {
 };
 thread_local std::unique_ptr<Result> g_result;
 
-constexpr size_t kSlice = 4096;  // members deflated per launch at the most
-constexpr uint64_t kDefaultBatchBytes = 256ull << 20;
-constexpr uint64_t kMaxBatchBytes = 1ull << 30;
 constexpr uint32_t kInitialSlots = 256;  // header slots of a range before the first range that has more
-
-// The output file: written under a temporary name beside the target, renamed by commit(), else removed.
-struct OutFile {
-    std::string target, tmp;
-    FILE *f = nullptr;
-    bool committed = false;
-    OutFile() = default;
-    OutFile(const OutFile &) = delete;
-    OutFile &operator=(const OutFile &) = delete;
-    ~OutFile() {
-        if (f) fclose(f);
-        if (!committed && !tmp.empty()) (void)unlink(tmp.c_str());
-    }
-    int open() {
-        tmp = target + ".tmp." + std::to_string(long(getpid()));
-        f = fopen(tmp.c_str(), "wb");
-        return f ? SECEDO_OK : fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp);
-    }
-    int append(const void *p, size_t n) {
-        if (n && fwrite(p, 1, n, f) != n) return fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp);
-        return SECEDO_OK;
-    }
-    int commit() {
-        const bool ok = fclose(f) == 0;
-        f = nullptr;
-        if (!ok) return fail(SECEDO_E_INVALID_ARG, "Could not write " + tmp);
-        if (rename(tmp.c_str(), target.c_str()) != 0)
-            return fail(SECEDO_E_INVALID_ARG, "Could not rename " + tmp + " to " + target);
-        committed = true;
-        return SECEDO_OK;
-    }
-};
-
-// Text on the device goes down as it is, or through the encoder with the member cuts of this piece of text.
-struct TextOut {
-    OutFile *of;
-    bool bgzf;
-    bz::Encoder *enc;
-    hipStream_t s;
-    std::vector<uint8_t> down;
-    Buf stage;
-
-    // d_text: `total` bytes with bz::kDeflateInSlack readable bytes around them
-    int device(const uint8_t *d_text, uint64_t total) {
-        if (total == 0) return SECEDO_OK;
-        Clock::time_point t0 = Clock::now();
-        g_info.text_bytes += total;
-        if (!bgzf) {
-            down.resize(total);
-            SECEDO_TRY(hipMemcpyAsync(down.data(), d_text, total, hipMemcpyDeviceToHost, s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            g_info.download_ms += ms_lap(t0);
-            SECEDO_CALL(of->append(down.data(), total));
-            g_info.write_ms += ms_lap(t0);
-            return SECEDO_OK;
-        }
-        std::vector<bz::DeflateDesc> desc;
-        bz::member_cuts(0, total, &desc);
-        const int rc = enc->run(d_text, desc, s, [&](size_t, uint32_t n, const uint32_t *bytes, uint64_t *at) -> int {
-            uint64_t end = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                at[i] = end;
-                end += bytes[i];
-            }
-            SECEDO_CALL(enc->fetch(end, &enc->bytes, 0));
-            Clock::time_point t1 = Clock::now();
-            SECEDO_CALL(of->append(enc->bytes.data(), end));
-            g_info.compressed_bytes += end;
-            g_info.write_ms += ms_since(t1);
-            return SECEDO_OK;
-        });
-        g_info.members += enc->counts.members;
-        g_info.deflate_ms += enc->counts.deflate_ms;
-        g_info.download_ms += enc->counts.download_ms;
-        enc->counts = bz::EncoderCounts{};  // taken
-        return rc;
-    }
-    // the header line, made on the host: the same way out
-    int host(const std::string &text) {
-        if (!bgzf) {
-            g_info.text_bytes += text.size();
-            return of->append(text.data(), text.size());
-        }
-        std::vector<uint8_t> all(bz::kDeflateInSlack, 0);
-        all.insert(all.end(), text.begin(), text.end());
-        all.resize(all.size() + bz::kDeflateInSlack, 0);
-        SECEDO_TRY(stage.alloc(all.size()));
-        SECEDO_TRY(hipMemcpyAsync(stage.p, all.data(), all.size(), hipMemcpyHostToDevice, s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        return device(stage.p + bz::kDeflateInSlack, text.size());
-    }
-    int finish() {
-        if (!bgzf) return SECEDO_OK;
-        const auto eof = bz::eof_member();
-        g_info.compressed_bytes += eof.size();
-        return of->append(eof.data(), eof.size());
-    }
-};
 
 // The names of the contigs, in file order, from the header slots of one range after the other. A header line that a
 // range boundary cuts is joined here: `raw` holds its first bytes until its end is seen.
@@ -401,6 +300,43 @@ int count_file(const Source &src, const Request &rq, hipStream_t s, Counted *out
     return SECEDO_OK;
 }
 
+// The file of the selected contigs' bins: the header line, then the lines formatted on the GPU from the table in
+// selection order.
+int write_file(const Request &rq, const bd::Layout &lay, const std::vector<std::string> &names,
+               const uint32_t *d_counts, OutFiles *of, TextCounts *tc, hipStream_t s) {
+    Clock::time_point t0 = Clock::now();
+    SECEDO_CALL(out_error(of->open()));
+    g_info.write_ms += ms_lap(t0);
+    DevNames dn;
+    SECEDO_CALL(upload_names(names, s, &dn));
+    Dev<uint32_t> d_len;
+    Dev<uint64_t> d_base;
+    SECEDO_TRY(d_base.alloc(lay.base.size()));
+    SECEDO_TRY(d_len.alloc(lay.len.size()));
+    SECEDO_TRY(hipMemcpyAsync(d_base.p, lay.base.data(), lay.base.size() * 8, hipMemcpyHostToDevice, s));
+    if (!lay.len.empty())
+        SECEDO_TRY(hipMemcpyAsync(d_len.p, lay.len.data(), lay.len.size() * 4, hipMemcpyHostToDevice, s));
+    SECEDO_TRY(hipStreamSynchronize(s));
+    const gb::Rows rows{d_base.p, d_len.p, uint32_t(lay.chr.size()), rq.S, dn.view(), d_counts};
+    bz::Encoder enc(kSlice);
+    Formatter fm;
+    TextOut out{of, 0, rq.bgzf, &enc, s, tc, {}, {}};
+    SECEDO_CALL(out.host(gb::header_line()));
+    const uint64_t max_line = gb::max_line(dn.longest);
+    SECEDO_CALL(fm.run(
+        lay.n_bins(), bd::lines_per_range(text_batch_bytes("SECEDO_GENOME_BINS_BATCH_BYTES"), max_line), max_line,
+        [&](uint64_t i0, uint32_t n, uint64_t *len) { return gb::lines_measure(rows, i0, n, len, s); },
+        [&](uint64_t i0, uint32_t n, const uint64_t *off, uint8_t *text) {
+            return gb::lines_write(rows, i0, n, off, text, s);
+        },
+        Scan64{gb::scan_bytes, gb::exclusive_sum64}, &out, s));
+    SECEDO_CALL(out.finish());
+    t0 = Clock::now();
+    SECEDO_CALL(out_error(of->commit()));
+    g_info.write_ms += ms_lap(t0);
+    return SECEDO_OK;
+}
+
 int genome_bins(const char *fasta, uint32_t bin_size, const char *const *names, const uint64_t *lengths,
                 uint32_t n_names, const char *out_path, int output, int overwrite) {
     // everything that needs no input, before any is read
@@ -420,13 +356,13 @@ int genome_bins(const char *fasta, uint32_t bin_size, const char *const *names, 
         if (lengths) rq.lengths.push_back(lengths[i]);
     }
     g_info.output = uint32_t(output);
-    OutFile of;
+    OutFiles of;
     if (out_path) {
         rq.write = true;
-        of.target = std::string(out_path) + (rq.bgzf ? ".gz" : "");
+        of.target = {std::string(out_path) + (rq.bgzf ? ".gz" : "")};
         struct stat st;
-        if (!rq.overwrite && stat(of.target.c_str(), &st) == 0)
-            return fail(SECEDO_E_INVALID_ARG, of.target + " exists; pass overwrite to replace it");
+        if (!rq.overwrite && stat(of.target[0].c_str(), &st) == 0)
+            return fail(SECEDO_E_INVALID_ARG, of.target[0] + " exists; pass overwrite to replace it");
     }
 
     Source src;
@@ -498,64 +434,12 @@ int genome_bins(const char *fasta, uint32_t bin_size, const char *const *names, 
     SECEDO_TRY(hipStreamSynchronize(s));
 
     if (rq.write) {
-        Clock::time_point t0 = Clock::now();
-        SECEDO_CALL(of.open());
-        g_info.write_ms += ms_lap(t0);
-        // names, layout
-        std::vector<uint8_t> bytes;
-        std::vector<uint32_t> off{0};
-        uint64_t longest = 0;
-        for (const std::string &n : res->names) {
-            bytes.insert(bytes.end(), n.begin(), n.end());
-            off.push_back(uint32_t(bytes.size()));
-            longest = std::max<uint64_t>(longest, n.size());
-        }
-        Dev<uint8_t> d_bytes, d_tmp, d_text;
-        Dev<uint32_t> d_off, d_len;
-        Dev<uint64_t> d_base, d_line, d_at;
-        SECEDO_TRY(d_bytes.alloc(bytes.size()));
-        SECEDO_TRY(d_off.alloc(off.size()));
-        SECEDO_TRY(d_base.alloc(lay.base.size()));
-        SECEDO_TRY(d_len.alloc(lay.len.size()));
-        if (!bytes.empty()) SECEDO_TRY(hipMemcpyAsync(d_bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
-        SECEDO_TRY(hipMemcpyAsync(d_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
-        SECEDO_TRY(hipMemcpyAsync(d_base.p, lay.base.data(), lay.base.size() * 8, hipMemcpyHostToDevice, s));
-        if (!lay.len.empty())
-            SECEDO_TRY(hipMemcpyAsync(d_len.p, lay.len.data(), lay.len.size() * 4, hipMemcpyHostToDevice, s));
-        SECEDO_TRY(hipStreamSynchronize(s));
-        const gb::Rows rows{d_base.p, d_len.p, uint32_t(lay.chr.size()), rq.S, gb::Names{d_bytes.p, d_off.p}, d_counts};
-        bz::Encoder enc(kSlice);
-        TextOut out{&of, rq.bgzf, &enc, s, {}, {}};
-        SECEDO_CALL(out.host(gb::header_line()));
-        const uint64_t batch = std::min(env_u64("SECEDO_GENOME_BINS_BATCH_BYTES", kDefaultBatchBytes), kMaxBatchBytes);
-        const uint64_t per_range = bd::lines_per_range(batch, gb::max_line(longest));
-        for (uint64_t i0 = 0; i0 < n_bins; i0 += per_range) {  // measure, scan, store, out
-            t0 = Clock::now();
-            const uint32_t n = uint32_t(std::min<uint64_t>(per_range, n_bins - i0));
-            const size_t tb = gb::scan_bytes(uint64_t(n) + 1);
-            SECEDO_TRY(d_line.grow(size_t(n) + 1, 0, s));
-            SECEDO_TRY(d_at.grow(size_t(n) + 1, 0, s));
-            SECEDO_TRY(d_tmp.grow(tb, 0, s));
-            SECEDO_TRY(gb::lines_measure(rows, i0, n, d_line.p, s));
-            SECEDO_TRY(gb::exclusive_sum64(d_tmp.p, tb, d_line.p, d_at.p, uint64_t(n) + 1, s));
-            uint64_t total = 0;
-            SECEDO_TRY(hipMemcpyAsync(&total, d_at.p + n, 8, hipMemcpyDeviceToHost, s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            if (total > uint64_t(n) * gb::max_line(longest))
-                return fail(SECEDO_E_HIP, "the line lengths add up to more than the lines can hold");
-            SECEDO_TRY(d_text.grow(total + 2 * bz::kDeflateInSlack, 0, s));
-            uint8_t *text = d_text.p + bz::kDeflateInSlack;
-            SECEDO_TRY(hipMemsetAsync(d_text.p, 0, bz::kDeflateInSlack, s));
-            SECEDO_TRY(hipMemsetAsync(text + total, 0, bz::kDeflateInSlack, s));
-            SECEDO_TRY(gb::lines_write(rows, i0, n, d_at.p, text, s));
-            SECEDO_TRY(hipStreamSynchronize(s));
-            g_info.format_ms += ms_lap(t0);
-            SECEDO_CALL(out.device(text, total));
-        }
-        SECEDO_CALL(out.finish());
-        t0 = Clock::now();
-        SECEDO_CALL(of.commit());
-        g_info.write_ms += ms_lap(t0);
+        TextCounts tc;  // what the text layer did, also where it failed
+        const int wrc = write_file(rq, lay, res->names, d_counts, &of, &tc, s);
+        g_info.text_bytes += tc.text_bytes, g_info.compressed_bytes += tc.compressed_bytes;
+        g_info.members += tc.members, g_info.format_ms += tc.format_ms, g_info.deflate_ms += tc.deflate_ms;
+        g_info.download_ms += tc.download_ms, g_info.write_ms += tc.write_ms;
+        SECEDO_CALL(wrc);
     }
     g_result = std::move(res);
     return SECEDO_OK;

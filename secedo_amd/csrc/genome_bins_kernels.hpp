@@ -22,11 +22,7 @@ hipError_t compose(const uint8_t *d_text, uint32_t len, uint32_t state, const fa
 size_t scan_bytes(uint64_t n);
 hipError_t exclusive_sum64(void *tmp, size_t bytes, const uint64_t *d_in, uint64_t *d_out, uint64_t n, hipStream_t s);
 
-// names one after the other; off[i] .. off[i + 1] is name i
-struct Names {
-    const uint8_t *bytes;
-    const uint32_t *off;
-};
+using Names = bd::Names;  // bam_depth.hpp: names one after the other
 
 // The file's lines, item = global bin: d_base[n + 1] and d_len[n] are the layout's, names those of the selected
 // contigs, counts the table in selection order.
@@ -38,7 +34,8 @@ struct Rows {
     const uint32_t *counts;
 };
 // count then store (text_sink.hpp): measure gives d_len[k] for the bins [i0, i0 + n) (n + 1 entries, the last 0),
-// write stores bin k's line at d_out + d_off[k] (d_off = the exclusive sum of d_len)
+// write stores bin k's line at d_out + d_off[k] (d_off = the exclusive sum of d_len); the host loop over the ranges
+// is text_out.hpp's Formatter, over the scan above
 hipError_t lines_measure(const Rows &r, uint64_t i0, uint32_t n, uint64_t *d_len, hipStream_t s);
 hipError_t lines_write(const Rows &r, uint64_t i0, uint32_t n, const uint64_t *d_off, uint8_t *d_out, hipStream_t s);
 
