@@ -297,6 +297,12 @@ uint32_t secedo_simmat_last_workgroups(const secedo_simmat_t *handle);
  * grp, rec, idx may be null. SECEDO_E_STATE when the lists have not been built. */
 int secedo_simmat_debug_flag_lists(secedo_simmat_t *handle, uint64_t *n_flagged, uint32_t *grp, uint32_t *rec,
                                    uint32_t *idx);
+/* Debugging aid: the locus ranges of the prepared pileup, copied to host memory (synchronises the device).
+ * num_ranges: their number; max_range_span: the loci of the longest, as the packing reported it; cap_loci: the limit
+ * they were cut for (a device packing cuts them inside segments of that many loci); range_off (num_ranges + 1 words,
+ * room for num_loci + 1): the first locus of every range and num_loci. range_off may be null. */
+int secedo_simmat_debug_ranges(secedo_simmat_t *handle, uint32_t *num_ranges, uint32_t *max_range_span,
+                               uint32_t *cap_loci, uint32_t *range_off);
 
 /* log-likelihood ratio D(x_s, x_d) = log P(x_s,x_d | different) - log P(x_s,x_d | same) as the
  * matrix path adds it (host-only, no device): what the reference's nested sums return

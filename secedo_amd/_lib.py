@@ -103,6 +103,7 @@ SIGNATURES = {
     "secedo_simmat_last_locus_words": (C.c_int, [_vp]),
     "secedo_simmat_last_workgroups": (C.c_uint32, [_vp]),
     "secedo_simmat_debug_flag_lists": (C.c_int, [_vp, _u64p, _vp, _vp, _vp]),
+    "secedo_simmat_debug_ranges": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "secedo_simmat_llr": (C.c_double, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double]),
     "secedo_simmat_llr_closed_form": (C.c_double, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double]),
     "secedo_simmat_pair_bound": (C.c_uint64, [_vp]),

@@ -97,9 +97,11 @@ struct Scalars {
     uint32_t max_read_entries;  // kept entries of the longest read id run
     uint32_t caps_wrong;        // the locus ranges were cut for the count tile, and the pair bound forbids it
     uint32_t n_multi_id;        // entries whose read id occurs more than once in its chromosome (k_compact_m)
-    uint32_t reads_total;       // reads of the whole pileup (k_arank_m)
+    uint32_t reads_total;       // reads of the whole pileup (k_ranks_runs)
     uint32_t n_wide;            // kept entries whose read reaches beyond their 8-locus windows (k_m_records / k_records)
     uint32_t max_range_span;    // loci of the longest locus range (k_ranges_compact; accumulate_counts' instance)
+    // ticket words of the kernels whose last workgroup finishes the job (last_workgroup): zero between launches
+    uint32_t ticket_ids, ticket_reads;
     unsigned long long id_space;  // sum over chromosomes of (largest - smallest read id + 1)
     unsigned long long multi_entries;
     unsigned long long pair_bound;
@@ -123,29 +125,100 @@ __global__ void k_publish(const Scalars *sc, const unsigned long long *totals, M
     }
 }
 
-// behind: launches that do not touch the scalars and whose results the caller wants whatever the scalars say. They
-// are enqueued behind the publishing kernel and in front of the wait: the host has the scalars as early as without
-// them, and the GPU has work while the host acts on them.
-hipError_t read_scalars(DevicePacked &pk, hipStream_t stream, const Scalars *sc, const unsigned long long *totals,
-                        Scalars *out, unsigned long long *out_totals, const std::function<void()> &behind = nullptr) {
-    static const bool plain = [] {
-        const char *e = std::getenv("SECEDO_PACK_READBACK");
-        return e && std::strcmp(e, "memcpy") == 0;
-    }();
-    hipError_t e;
-    if (!plain && !pk.mailbox && !pk.mailbox_failed) {
+// A word another workgroup of the same launch, or a kernel on the other stream, may have written: read at device scope
+template <class T>
+__device__ __forceinline__ T load_dev(const T *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <class T>
+__device__ __forceinline__ void store_dev(T *p, T v) {  // write-through: at the device's coherence point when it has left
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ---- the last workgroup finishes the job -------------------------------------------------------------------------
+// A serial step behind a grid (the id bases, the scan of the blocks' sums, the publishing of a read-back) without a
+// one-workgroup launch of its own: every workgroup ends with one relaxed fetch_add on a ticket word, and the workgroup
+// that draws the last ticket does the step and puts the ticket back to zero. Nobody waits for anybody. Two rules
+// keep it cheap (round 32 measured the other way: an agent-scope release per workgroup, +301 us on C3):
+//  * the few words that are handed over are written with atomics or store_dev (write-through), so no workgroup needs
+//    a release -- every wave only waits until its own stores have left, then the barrier, then the ticket; the last
+//    workgroup's first lane acquires once, and reads them with load_dev;
+//  * the grid is a few hundred workgroups at the most: the tickets are same-address atomics, tens of ns each.
+// All threads of every workgroup of the grid call it, once (it holds barriers).
+__device__ __forceinline__ bool last_workgroup(uint32_t *ticket) {
+    __shared__ uint32_t s_last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = drawn + 1u == gridDim.x;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            store_dev(ticket, 0u);
+        }
+        s_last = last ? 1u : 0u;
+    }
+    __syncthreads();
+    return s_last != 0u;
+}
+// A read-back whose publishing is folded into the kernel in front of it: one lane of that kernel copies the scalars
+// and releases the sequence word (k_publish's body). box == null: nothing is published here (the plain copies, or a
+// call site that launches k_publish).
+struct Publish {
+    Mailbox *box;
+    unsigned long long seq;
+    const unsigned long long *totals;
+};
+__device__ __forceinline__ void publish_scalars(const Scalars *sc, const Publish &pub) {  // (one lane)
+    static_assert(sizeof(Scalars) % 4 == 0, "copied word by word");
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(sc);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&pub.box->sc);
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(Scalars) / 4; ++i) dst[i] = load_dev(src + i);
+    pub.box->totals = pub.totals ? load_dev(pub.totals) : 0ull;
+    __hip_atomic_store(&pub.box->seq, pub.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+bool plain_readback() {  // (asked per packing, not once per process: a test takes both ways on one handle)
+    const char *e = std::getenv("SECEDO_PACK_READBACK");
+    return e && std::strcmp(e, "memcpy") == 0;
+}
+Mailbox *mailbox_of(DevicePacked &pk) {  // null: no mailbox wanted or to be had
+    if (plain_readback()) return nullptr;
+    if (!pk.mailbox && !pk.mailbox_failed) {
         if (hipHostMalloc(&pk.mailbox, sizeof(Mailbox), hipHostMallocCoherent) == hipSuccess) {
             std::memset(pk.mailbox, 0, sizeof(Mailbox));
-        } else {  // no pinned memory to be had: the plain copies below
+        } else {  // no pinned memory to be had: the plain copies
             (void)hipGetLastError();
             pk.mailbox = nullptr;
             pk.mailbox_failed = true;
         }
     }
-    if (!plain && pk.mailbox) {
-        Mailbox *box = static_cast<Mailbox *>(pk.mailbox);
-        const unsigned long long seq = ++pk.mailbox_seq;
-        hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, stream, sc, totals, box, seq);
+    return static_cast<Mailbox *>(pk.mailbox);
+}
+// the sequence number of the next read-back, for the kernel that publishes it; read_scalars(.., &folded) waits for it
+Publish fold_publish(DevicePacked &pk, const unsigned long long *totals) {
+    Mailbox *box = mailbox_of(pk);
+    return Publish{box, box ? ++pk.mailbox_seq : 0ull, totals};
+}
+
+// behind: launches that do not touch the scalars and whose results the caller wants whatever the scalars say. They
+// are enqueued behind the publishing kernel and in front of the wait: the host has the scalars as early as without
+// them, and the GPU has work while the host acts on them.
+// folded: the kernel last launched on `stream` publishes (fold_publish): nothing is launched here, only `behind` is
+// enqueued and the word polled. Without a mailbox (folded->box == null) the plain copies, as ever.
+hipError_t read_scalars(DevicePacked &pk, hipStream_t stream, const Scalars *sc, const unsigned long long *totals,
+                        Scalars *out, unsigned long long *out_totals, const std::function<void()> &behind = nullptr,
+                        const Publish *folded = nullptr) {
+    hipError_t e;
+    Mailbox *const mailbox = folded ? folded->box : mailbox_of(pk);
+    if (mailbox) {
+        Mailbox *box = mailbox;
+        unsigned long long seq;
+        if (folded) {
+            seq = folded->seq;
+        } else {
+            seq = ++pk.mailbox_seq;
+            hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, stream, sc, totals, box, seq);
+        }
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (behind) behind();
         // poll; every few thousand polls ask the runtime whether the stream died or drained without
@@ -262,7 +335,7 @@ __device__ __forceinline__ uint32_t chr_first_entry(const Raw &in, uint32_t c) {
 // It also checks that the positions increase strictly inside a chromosome (the reference asserts it,
 // similarity_matrix.cpp:398): a thread per locus, in front of the ids -- the single-entry path launches no
 // k_entry_locus, which checks the same.
-__global__ __launch_bounds__(TPB) void k_id_range(Raw in, uint32_t *id_max, uint32_t *id_negmin, int vec, Scalars *sc) {
+__device__ __forceinline__ void id_range_chunk(const Raw &in, uint32_t *id_max, uint32_t *id_negmin, int vec, Scalars *sc) {
     __shared__ uint32_t s_hi[TPB / 64], s_neg[TPB / 64];
     __shared__ uint32_t s_chr;
     for (uint32_t l = blockIdx.x * TPB + threadIdx.x; l + 1 < in.n_loci; l += gridDim.x * TPB) {
@@ -362,22 +435,24 @@ __global__ __launch_bounds__(TPB) void k_id_range(Raw in, uint32_t *id_max, uint
     }
 }
 
-// dense numbering of (chromosome, read id): id_base[c] + id - smallest id of c
-// (the other lanes: the chromosomes' first entries, chr_entry[0 .. n_chr], for the kernels that find an entry's
-// chromosome from its index)
-__global__ void k_id_bases(Raw in, const uint32_t *id_max, const uint32_t *id_negmin, uint32_t *id_base,
-                           uint32_t *chr_entry, unsigned long long assumed_space, Scalars *sc) {
+// ... and, by the last workgroup (the extremes are atomics: last_workgroup), the dense numbering of (chromosome, read
+// id): id_base[c] + id - smallest id of c; the other lanes write the chromosomes' first entries, chr_entry[0 .. n_chr],
+// for the kernels that find an entry's chromosome from its index. (A kernel of its own, k_id_bases, until round 32.)
+__global__ __launch_bounds__(TPB) void k_id_range(Raw in, uint32_t *id_max, uint32_t *id_negmin, int vec,
+                                                 uint32_t *id_base, uint32_t *chr_entry,
+                                                 unsigned long long assumed_space, Scalars *sc) {
+    id_range_chunk(in, id_max, id_negmin, vec, sc);
+    if (!last_workgroup(&sc->ticket_ids)) return;
     const uint32_t n_chr = in.n_chr;
-    if (blockIdx.x != 0) return;
-    for (uint32_t c = threadIdx.x; c <= n_chr; c += blockDim.x) chr_entry[c] = chr_first_entry(in, c);
+    for (uint32_t c = threadIdx.x; c <= n_chr; c += TPB) chr_entry[c] = chr_first_entry(in, c);
     if (threadIdx.x != 0) return;
     unsigned long long sum = 0;
     uint32_t top = 0;
     for (uint32_t c = 0; c < n_chr; ++c) {
         id_base[c] = (uint32_t)min(sum, 0xFFFFFFFFull);
-        const uint32_t lo = ~id_negmin[c];
-        if ((id_max[c] | id_negmin[c]) != 0u) sum += (unsigned long long)(id_max[c] - lo) + 1ull;  // has entries
-        top = max(top, id_max[c]);
+        const uint32_t hi = load_dev(id_max + c), neg = load_dev(id_negmin + c);
+        if ((hi | neg) != 0u) sum += (unsigned long long)(hi - ~neg) + 1ull;  // has entries
+        top = max(top, hi);
     }
     id_base[n_chr] = (uint32_t)min(sum, 0xFFFFFFFFull);
     sc->id_space = sum;
@@ -411,7 +486,7 @@ __global__ void k_sorted_locus(Raw in, const uint32_t *sval, const uint32_t *ent
 
 // The dense id of an entry: its chromosome, then two per-chromosome words. The chromosome is a search over the
 // chromosomes' first loci with the entry's locus as the key (`first` = chr_locus_off: the general path, which has the
-// entry -> locus table), or over their first ENTRIES with the entry's index (`first` = chr_entry, k_id_bases: the
+// entry -> locus table), or over their first ENTRIES with the entry's index (`first` = chr_entry, k_id_range: the
 // single-entry path, which has no such table -- the same search, no per-entry read in front of it). Empty chromosomes
 // share a start with their successor and last_le picks the last of them, the one that holds the key.
 // From LDS when the tables fit: from global memory the search is a chain of log2(C) dependent loads in front of
@@ -578,7 +653,40 @@ __global__ void k_id_check(Raw in, const uint32_t *chr_entry, const uint32_t *id
         }
     }
 }
+// exclusive offsets of n_blocks block sums by the THREADS threads of ONE workgroup (3000 blocks on C3); returns the
+// total in every thread. The sums are read at device scope: in a kernel's last workgroup other workgroups wrote them.
+constexpr int TPB_SCAN = 1024;
+template <int THREADS>
+__device__ __forceinline__ uint32_t scan_block_sums(const uint32_t *block_sum, uint32_t n_blocks, uint32_t *block_off) {
+    __shared__ uint32_t part[THREADS / 64];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint32_t carry = 0;  // (uniform)
+    for (uint32_t base = 0; base < n_blocks; base += THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < n_blocks ? load_dev(block_sum + i) : 0u;
+        uint32_t incl = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if (lane >= (uint32_t)off) incl += up;
+        }
+        __syncthreads();  // the previous round's partials have been read
+        if (lane == 63u) part[wv] = incl;
+        __syncthreads();
+        uint32_t before = carry;
+#pragma unroll
+        for (int w2 = 0; w2 < THREADS / 64; ++w2) {
+            const uint32_t pw = part[w2];
+            if ((uint32_t)w2 < wv) before += pw;
+            carry += pw;
+        }
+        if (i < n_blocks) block_off[i] = before + incl - v;
+    }
+    return carry;
+}
 // flags per block of kFlagBlock entries (the flag array is zero-padded to whole blocks)
+// (Round 32 measured the scan as this kernel's tail -- 256 workgroups, a wave per block, sums written through, the last
+// workgroup scans --: 22.8 us against 5.5 + 7.8 for the two kernels on C3. A kernel this short has nothing to hide
+// 256 tickets behind.)
 __global__ __launch_bounds__(TPB) void k_flag_count(const uint8_t *multi, uint32_t *block_sum) {
     __shared__ uint32_t part[TPB / 64];
     static_assert(kFlagBlock == TPB * 16, "a thread takes 16 consecutive flags");
@@ -593,36 +701,13 @@ __global__ __launch_bounds__(TPB) void k_flag_count(const uint8_t *multi, uint32
         block_sum[blockIdx.x] = n;
     }
 }
-// exclusive offsets of the blocks (one workgroup; 3000 blocks on C3), the number of M entries
-constexpr int TPB_SCAN = 1024;
+// the blocks' exclusive offsets as a kernel of its own, and the number of M entries
 __global__ __launch_bounds__(TPB_SCAN) void k_flag_scan(const uint32_t *block_sum, uint32_t n_blocks, uint32_t *block_off,
                                                        uint32_t *total_out, Scalars *sc) {
-    constexpr int TPB = TPB_SCAN;  // (this kernel's own)
-    __shared__ uint32_t part[TPB / 64];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0u) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    for (uint32_t base = 0; base < n_blocks; base += TPB) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_blocks ? block_sum[i] : 0u;
-        uint32_t incl = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off);
-            if (lane >= (uint32_t)off) incl += up;
-        }
-        if (lane == 63u) part[wv] = incl;
-        __syncthreads();
-        uint32_t before = carry;
-        for (uint32_t w2 = 0; w2 < wv; ++w2) before += part[w2];
-        if (i < n_blocks) block_off[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == TPB - 1) carry = before + incl;
-        __syncthreads();
-    }
+    const uint32_t total = scan_block_sums<TPB_SCAN>(block_sum, n_blocks, block_off);
     if (threadIdx.x == 0u) {
-        *total_out = carry;  // the prefix of the closing chunk
-        if (sc) sc->n_multi_id = carry;  // (null: the flagged entries' lists, pack_flag_lists)
+        *total_out = total;  // the prefix of the closing chunk
+        if (sc) sc->n_multi_id = total;  // (null: the flagged entries' lists, pack_flag_lists)
     }
 }
 // The numbering of the M entries, in the form the flagged entries' lists have below: per 64-entry chunk its flags
@@ -643,7 +728,7 @@ struct MIndex {
 // consecutive flags, so four neighbouring lanes hold a chunk. (k_flag_scan writes the closing chunk's prefix.)
 __global__ __launch_bounds__(TPB) void k_compact_m(Raw in, const uint8_t *multi, const uint32_t *block_off,
                                                   uint32_t *chunk_pre, unsigned long long *chunk_mask,
-                                                  uint32_t *m_entry) {
+                                                  uint32_t *m_entry, uint32_t *count_m, Scalars *sc, Publish pub) {
     __shared__ uint32_t part[TPB / 64];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint32_t e0 = blockIdx.x * kFlagBlock + threadIdx.x * 16u;
@@ -671,7 +756,20 @@ __global__ __launch_bounds__(TPB) void k_compact_m(Raw in, const uint8_t *multi,
         chunk_mask[chunk] = m;
     }
     if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0u) chunk_mask[gridDim.x * (kFlagBlock / 64u)] = 0ull;
-    for (uint32_t b = bits; b; b &= b - 1u) m_entry[j++] = e0 + (uint32_t)__ffs((int)b) - 1u;
+    // (count_m: the M entries' counters of k_m_fields, n_m + 1 of them, zeroed where the M entries are numbered
+    // instead of by a fill behind read-back 1b, which stood between the host's answer and k_m_fields)
+    for (uint32_t b = bits; b; b &= b - 1u) {
+        count_m[j] = 0u;
+        m_entry[j++] = e0 + (uint32_t)__ffs((int)b) - 1u;
+    }
+    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == TPB - 1) count_m[j] = 0u;  // (j: all M entries)
+    // Read-back 1b. What it carries (n_multi_id, the flags of the kernels in front) was complete before this kernel
+    // began: the first workgroup publishes when it is through. The host therefore has the scalars while other
+    // workgroups of this kernel still run -- a hand-over at read-back 1b (an error, a void attempt, the host packing)
+    // no longer finds the stream drained. That is sound because whatever follows is enqueued on this stream or goes
+    // through a synchronising hipFree, and this kernel writes scratch arenas only (M_ENTRY, M_CHUNKS, DENSE_M), which
+    // the host packing's uploads do not replace (compare close_attempt's note on read-back 3).
+    if (pub.box && blockIdx.x == 0u && threadIdx.x == 0u) publish_scalars(sc, pub);
 }
 // The same count -> scan -> compact chain numbers the FLAGGED entries of the packed pileup (C_TAIL | C_MULTI in
 // entry32: the read was never flushed, or has further kept entries) for the correction of the sparse-loci pair
@@ -793,11 +891,10 @@ void flag_groups(const FlagScratch &fs, const uint32_t *blk_off, size_t n_off, u
     const uint32_t blocks = (uint32_t)std::min<size_t>((n_off + TPB - 1) / TPB, 256 * 32);
     hipLaunchKernelGGL(k_pflag_groups, dim3(blocks), dim3(TPB), 0, stream, blk_off, n_off, fs.chunk_pre, fs.chunk_mask, grp);
 }
-// the lists behind a k_entry_records that has written fs.chunk_mask and fs.block_sum
+// the lists behind a k_entry_records that has written fs.chunk_mask and fs.block_sum, and a k_records_tail that has
+// scanned the sums
 void flag_lists_from_masks(const FlagScratch &fs, const uint4 *entry, const uint32_t *blk_off, size_t n_off,
                            uint32_t *grp, uint4 *rec, uint32_t *idx, hipStream_t stream) {
-    hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, fs.block_sum, fs.nb, fs.block_off,
-                       fs.chunk_pre + 64 * (size_t)fs.nb, static_cast<Scalars *>(nullptr));
     hipLaunchKernelGGL(k_pflag_compact_masks, dim3(fs.nb), dim3(TPB), 0, stream, fs.chunk_mask, entry, fs.block_off, rec,
                        idx, fs.chunk_pre);
     flag_groups(fs, blk_off, n_off, grp, stream);
@@ -888,17 +985,6 @@ struct UnmarkedM {  // input of the scan that gives unm
     uint32_t n_m;
     __device__ __forceinline__ uint32_t operator()(uint32_t j) const { return j < n_m ? 1u - mark_m[j] : 0u; }
 };
-// appearance ranks of the M entries (k_read_info reads the rank of a read's first entry), the number of reads
-__global__ void k_arank_m(const uint32_t *unm, const uint32_t *m_entry, uint32_t n_m, uint32_t n, uint32_t *arank_m,
-                          Scalars *sc) {
-    for (uint32_t j = blockIdx.x * TPB + threadIdx.x; j < n_m; j += gridDim.x * TPB) arank_m[j] = m_entry[j] - unm[j];
-    if (blockIdx.x == 0 && threadIdx.x == 0) sc->reads_total = n - unm[n_m];
-}
-// per chromosome the first appearance rank
-__global__ void k_rbeg(Raw in, Ranks rank, uint32_t *rbeg) {
-    for (uint32_t c = blockIdx.x * TPB + threadIdx.x; c <= in.n_chr; c += gridDim.x * TPB)
-        rbeg[c] = rank((uint32_t)in.locus_entry_off[in.chr_locus_off[c]]);
-}
 // Input of the one scan over the sorted order: low word = first entry of a read (head of a run of
 // equal keys), high word = the entry survives the duplicate rule. The inclusive sums give, per
 // position, the 1-based read number and the number of kept entries up to and including it.
@@ -958,13 +1044,37 @@ __global__ void k_runs_csr(Raw in, const unsigned long long *incl, const uint32_
         }
     }
 }
+// Single-entry route, one launch for three independent things that all stand behind the two scans (k_arank_m, k_rbeg
+// and k_runs_csr until round 32): the appearance ranks of the M entries (k_read_info reads the rank of a read's first
+// entry) and the number of reads; the run starts and per-read lists as in k_runs_csr; per chromosome the first
+// appearance rank. The grid is sized by the n_m M entries (`in` is the whole pileup) and walks the n_chr + 1
+// chromosomes with its first threads.
+__global__ void k_ranks_runs(Raw in, Ranks rank, const uint32_t *m_entry, uint32_t n_m, uint32_t *arank_m,
+                             uint32_t *rbeg, const unsigned long long *incl, const uint32_t *sloc,
+                             uint32_t *run_start, uint32_t *read_locus, uint8_t *read_base, Scalars *sc) {
+    const uint32_t *unm = rank.unm;
+    for (uint32_t s = blockIdx.x * TPB + threadIdx.x; s < n_m; s += gridDim.x * TPB) {
+        arank_m[s] = m_entry[s] - unm[s];
+        const unsigned long long cur = incl[s], prev = s ? incl[s - 1] : 0ull;
+        if (incl_reads(cur) != incl_reads(prev)) run_start[incl_reads(cur) - 1] = s;
+        if (s == n_m - 1) run_start[incl_reads(cur)] = n_m;
+        if (incl_kept(cur) != incl_kept(prev)) {
+            const uint32_t k = incl_kept(prev), v = sloc[s];
+            read_locus[k] = sloc_locus(v);
+            read_base[k] = (uint8_t)sloc_base(v);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) sc->reads_total = in.n_entries - unm[n_m];
+    for (uint32_t c = blockIdx.x * TPB + threadIdx.x; c <= in.n_chr; c += gridDim.x * TPB)
+        rbeg[c] = rank((uint32_t)in.locus_entry_off[in.chr_locus_off[c]]);
+}
 
 // per read: span check, offsets into the per-read lists, appearance rank, start position in rank
 // order, entries of multi-locus reads; per chromosome the first rank
 __global__ __launch_bounds__(TPB) void k_read_info(Raw in, const unsigned long long *incl, const uint32_t *run_start,
                                                   const uint32_t *sval, const uint32_t *sloc,
                                                   const uint32_t *arank, uint32_t mfl, uint32_t *run_rank,
-                                                  uint32_t *rbeg, uint32_t *read_off, Scalars *sc) {
+                                                  uint32_t *rbeg, uint32_t *read_off, Scalars *sc, Publish pub) {
     __shared__ unsigned long long part[TPB / 64];
     __shared__ uint32_t part_len[TPB / 64];
     const uint32_t n = in.n_entries;
@@ -977,8 +1087,8 @@ __global__ __launch_bounds__(TPB) void k_read_info(Raw in, const unsigned long l
         const uint32_t p0 = in.locus_pos[sloc_locus(sloc[s0])], p1 = in.locus_pos[sloc_locus(sloc[s1 - 1])];
         // a read whose entries reach start + mfl can be flushed before its last entry arrives and is
         // then re-opened as a new read (:368-371, :379-382): k_split_update finds where
-        if (p1 - p0 >= mfl) sc->long_reads = 1;
-        if ((unsigned long long)p1 + mfl > 0xFFFFFFFFull) sc->need_host = 1;
+        if (p1 - p0 >= mfl) store_dev(&sc->long_reads, 1u);  // (written through: the last workgroup publishes them)
+        if ((unsigned long long)p1 + mfl > 0xFFFFFFFFull) store_dev(&sc->need_host, 1u);
         const uint32_t rk = arank[e0];
         run_rank[r] = rk;
         const uint32_t k0 = s0 ? incl_kept(incl[s0 - 1]) : 0u, k1 = incl_kept(incl[s1 - 1]);
@@ -987,7 +1097,7 @@ __global__ __launch_bounds__(TPB) void k_read_info(Raw in, const unsigned long l
         if (k1 - k0 > 1) multi += k1 - k0;
         longest = max(longest, k1 - k0);
     }
-    if (rbeg) {  // (the single-entry fast path has the ranks of all entries elsewhere: k_rbeg)
+    if (rbeg) {  // (the single-entry fast path has the ranks of all entries elsewhere: k_ranks_runs)
         for (uint32_t c = blockIdx.x * TPB + threadIdx.x; c <= in.n_chr; c += gridDim.x * TPB)
             rbeg[c] = arank[(uint32_t)in.locus_entry_off[in.chr_locus_off[c]]];
     }
@@ -1011,6 +1121,8 @@ __global__ __launch_bounds__(TPB) void k_read_info(Raw in, const unsigned long l
         if (sum) atomicAdd(&sc->multi_entries, sum);
         if (len > 1) atomicMax(&sc->max_read_entries, len);  // reads of one entry are the rule: no atomic for them
     }
+    // the read-back behind the build, published by the last workgroup: every workgroup's flags and sums are in
+    if (pub.box && last_workgroup(&sc->ticket_reads) && threadIdx.x == 0) publish_scalars(sc, pub);
 }
 
 // completed-prefix count per locus (:348-352): reads of the chromosome with start + mfl <= position. A read
@@ -1581,7 +1693,7 @@ __global__ __launch_bounds__(TPB) void k_ranges_compact(const uint32_t *seg_ends
                                                        uint32_t n_cells_padded, int force_variant, Scalars *sc) {
     // force_variant < 0: the pair bound first (the largest per-cell sum of squares), then the limits it allows;
     // 0 / 1: the limits of the int64 tile / of the count tile, whatever the bound (the counting path cuts for
-    // the count tile before the bound is known, k_pair_bound checks afterwards)
+    // the count tile before the bound is known, k_records_tail checks afterwards)
     __shared__ unsigned long long s_best[TPB / 64];
     if (force_variant < 0) {
         unsigned long long best = 0;
@@ -1599,33 +1711,58 @@ __global__ __launch_bounds__(TPB) void k_ranges_compact(const uint32_t *seg_ends
     const uint32_t cap_loci = use_counts ? caps.loci_counts : caps.loci_plain;
     const uint32_t *seg_ends = seg_ends_both + (use_counts ? variant_stride : 0);
     const uint32_t *seg_count = seg_count_both + (use_counts ? variant_stride : 0);
-    __shared__ uint32_t s_base, s_span;
+    // A sweep takes TPB segments: a thread per segment loads its count, one prefix over the workgroup gives every
+    // segment its base, and all threads copy the sweep's ranges, a thread per range -- its segment by a search over
+    // the bases in LDS. (Until round 32 a loop over the segments, two barriers each: 27 us for C3's segments.)
+    __shared__ uint32_t s_first[TPB];  // ranges of the sweep before each of its segments
+    __shared__ uint32_t s_part[TPB / 64];
+    __shared__ uint32_t s_span;
     if (threadIdx.x == 0) {
-        s_base = 0;
         s_span = 0;
         range_off[0] = 0;
     }
-    __syncthreads();
+    // (no barrier here: the sweep below has some in front of the atomicMax, and L >= 1 gives at least one sweep)
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     uint32_t span = 0;  // the longest range this thread copies (a segment's first range begins with the segment)
-    for (uint32_t seg = 0; seg < n_seg; ++seg) {
-        const uint32_t base = s_base, cnt = seg_count[seg];
-        const uint32_t *ends = seg_ends + (size_t)seg * cap_loci;
-        for (uint32_t i = threadIdx.x; i < cnt; i += TPB) {
-            // (the range's begin is the neighbouring lane's end: one load per thread, all loads before the store)
+    uint32_t done = 0;  // ranges of the sweeps before (uniform)
+    for (uint32_t seg0 = 0; seg0 < n_seg; seg0 += TPB) {
+        const uint32_t n_here = min((uint32_t)TPB, n_seg - seg0);
+        const uint32_t cnt = threadIdx.x < n_here ? seg_count[seg0 + threadIdx.x] : 0u;
+        uint32_t incl = cnt;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if (lane >= (uint32_t)off) incl += up;
+        }
+        __syncthreads();  // the previous sweep's tables have been read
+        if (lane == 63u) s_part[wv] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < TPB / 64; ++w2) {
+            if ((uint32_t)w2 < wv) before += s_part[w2];
+            total += s_part[w2];
+        }
+        s_first[threadIdx.x] = before + incl - cnt;
+        __syncthreads();
+        for (uint32_t r = threadIdx.x; r < total; r += TPB) {
+            // the last segment that begins at or before r holds it (segments without ranges share a begin with their
+            // successor; those behind the last range begin at `total`)
+            const uint32_t sg = last_le<uint32_t>(s_first, n_here, r), i = r - s_first[sg];
+            const uint32_t seg = seg0 + sg;
+            const uint32_t *ends = seg_ends + (size_t)seg * cap_loci;
+            // (the range's begin is the neighbouring lane's end where that lane holds the range before in the segment)
             const uint32_t e = ends[i];
             uint32_t begin = __shfl_up(e, 1);
-            if ((threadIdx.x & 63u) == 0) begin = i ? ends[i - 1] : seg * cap_loci;
-            range_off[1 + base + i] = e;
+            if (lane == 0u || i == 0u) begin = i ? ends[i - 1] : seg * cap_loci;
+            range_off[1 + done + r] = e;
             span = max(span, e - begin);
         }
-        __syncthreads();
-        if (threadIdx.x == 0) s_base = base + cnt;
-        __syncthreads();
+        done += total;
     }
     atomicMax(&s_span, span);
     __syncthreads();
     if (threadIdx.x == 0) {
-        sc->num_ranges = s_base;
+        sc->num_ranges = done;
         sc->max_range_span = s_span;
     }
 }
@@ -1926,20 +2063,32 @@ __global__ __launch_bounds__(TPB_REC) void k_entry_records(const unsigned long l
             if (sq[i]) atomicAdd(&per_cell_sq[first_cell + i], sq[i]);
 }
 
-// the pair bound (largest per-cell sum of squares), and whether the locus ranges, cut for the count tile
-// before it was known, have to be cut again
-__global__ __launch_bounds__(TPB) void k_pair_bound(const unsigned long long *per_cell_sq, uint32_t n_cells_padded,
-                                                   CapChoice caps, uint32_t assumed_counts, Scalars *sc) {
-    __shared__ unsigned long long s_best[TPB / 64];
+// The serial tail of the records pass in ONE one-workgroup kernel (k_pair_bound, k_publish and k_flag_scan until round
+// 32): the pair bound (largest per-cell sum of squares) and whether the locus ranges, cut for the count tile before it
+// was known, have to be cut again; the publishing of read-back 3 (pub.box; null: the host copies); then, behind it so
+// that the host has the scalars first, the offsets of the list blocks (block_sum; null: no lists from this pass).
+__global__ __launch_bounds__(TPB_SCAN) void k_records_tail(const unsigned long long *per_cell_sq, uint32_t n_cells_padded,
+                                                          CapChoice caps, uint32_t assumed_counts, Scalars *sc,
+                                                          Publish pub, const uint32_t *block_sum, uint32_t n_blocks,
+                                                          uint32_t *block_off, uint32_t *total_out) {
+    __shared__ unsigned long long s_best[TPB_SCAN / 64];
     unsigned long long best = 0;
-    for (uint32_t i = threadIdx.x; i < n_cells_padded; i += TPB) best = max(best, per_cell_sq[i]);
+    for (uint32_t i = threadIdx.x; i < n_cells_padded; i += TPB_SCAN) best = max(best, per_cell_sq[i]);
     for (int off = 32; off > 0; off >>= 1) best = max(best, (unsigned long long)__shfl_down(best, off));
     if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < TPB / 64; ++w) best = max(best, s_best[w]);
+        for (int w = 1; w < TPB_SCAN / 64; ++w) best = max(best, s_best[w]);
         sc->pair_bound = max(sc->pair_bound, best);
         sc->caps_wrong = (assumed_counts && !caps.counts(sc)) ? 1u : 0u;
+        if (pub.box) {
+            __threadfence();  // (this lane's two words, in front of the copy's device-scope loads)
+            publish_scalars(sc, pub);
+        }
+    }
+    if (block_sum) {  // (uniform)
+        const uint32_t total = scan_block_sums<TPB_SCAN>(block_sum, n_blocks, block_off);
+        if (threadIdx.x == 0) *total_out = total;
     }
 }
 
@@ -2222,14 +2371,13 @@ struct PackAttempt {
     }
 
     Grouped group_by_read() {
-        hipLaunchKernelGGL(k_id_range, dim3(std::min<uint32_t>(256, (E + 4095) / 4096)), dim3(TPB), 0, stream, raw,
-                           m.id_max, m.id_negmin, ids_aligned, sc);
         // The size of the id space decides between the counting scheme and the radix sort and sizes the
         // histogram. A handle that has packed before assumes the size of the previous call and does not wait
-        // (k_id_bases raises Scalars::id_exceeded if that was too small: the attempt is then void and
+        // (k_id_range raises Scalars::id_exceeded if that was too small: the attempt is then void and
         // repeated with the read-back).
         const bool assume = !force_radix && !no_assumptions && pk.id_space_hint && pk.id_space_hint <= id_space_cap();
-        hipLaunchKernelGGL(k_id_bases, dim3(1), dim3(64), 0, stream, raw, m.id_max, m.id_negmin, m.id_base, m.chr_entry,
+        hipLaunchKernelGGL(k_id_range, dim3(std::min<uint32_t>(256, (E + 4095) / 4096)), dim3(TPB), 0, stream, raw,
+                           m.id_max, m.id_negmin, ids_aligned, m.id_base, m.chr_entry,
                            (unsigned long long)(assume ? pk.id_space_hint : 0), sc);
         Scalars hsc;
         std::memset(&hsc, 0, sizeof(hsc));
@@ -2282,11 +2430,13 @@ struct PackAttempt {
         hipLaunchKernelGGL(k_flag_count, dim3(n_flag_blocks), dim3(TPB), 0, stream, multi, sums.block_sum);
         hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(TPB_SCAN), 0, stream, sums.block_sum, n_flag_blocks, sums.block_off,
                            chunks.chunk_pre + (n_chunks - 1), sc);
+        // read-back 1b: how many entries take the general path (sizes every launch over them); k_compact_m's first
+        // workgroup publishes it. (count_m sits at the base of DENSE_M whatever the number of M entries: MReads)
+        const Publish pub = fold_publish(pk, nullptr);
         hipLaunchKernelGGL(k_compact_m, dim3(n_flag_blocks), dim3(TPB), 0, stream, raw, multi, sums.block_off,
-                           chunks.chunk_pre, chunks.chunk_mask, m_entry);
-        // read-back 1b: how many entries take the general path (sizes every launch over them)
+                           chunks.chunk_pre, chunks.chunk_mask, m_entry, MReads(S[Arena::DENSE_M].p, 0).count_m, sc, pub);
         Scalars hsc;
-        HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr));
+        HIP_OK(read_scalars(pk, stream, sc, nullptr, &hsc, nullptr, nullptr, &pub));
         STEP(scalar_verdict(hsc, false));
         Grouped g = whole_pileup(true);
         g.n_m = hsc.n_multi_id;
@@ -2304,7 +2454,6 @@ struct PackAttempt {
         if (g.n_m) {
             const uint32_t n_m = g.n_m;
             const MReads r(S[Arena::DENSE_M].p, n_m);
-            HIP_OK(hipMemsetAsync(r.count_m, 0, ((size_t)n_m + 1) * 4, stream));
             hipLaunchKernelGGL(k_m_fields, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, raw, m.chr_entry, m.id_base,
                                m.id_negmin, last, g.m_index, m_entry, n_m, rid_m, idb_m, eloc_m, r.winner_m, r.count_m);
             HIP_OK(exclusive_sum(r.count_m, r.goff, (size_t)n_m + 1));
@@ -2383,7 +2532,8 @@ struct PackAttempt {
     // Reads from the current `split` flags (cuts of reads that outlive max_fragment_length: none on the first build,
     // null), then completed counts and the flush chain. The chain is sequential (one lane per chromosome) and only
     // the final gather needs its result: it runs on a side stream, next to the grouping of the kept entries.
-    Attempt build_reads(const Grouped &g, const ReadViews &v, const uint32_t *split) {
+    // pub: where k_read_info publishes the read-back that follows the build (null, or no read: the caller's k_publish)
+    Attempt build_reads(const Grouped &g, const ReadViews &v, const uint32_t *split, Publish *pub = nullptr) {
         const uint32_t n_m = g.n_m;
         uint32_t *mark_sub = g.single_entry ? v.mark_sub : v.marks.mark, *arank = v.marks.arank;
         if (n_m) {
@@ -2401,19 +2551,25 @@ struct PackAttempt {
             hipcub::TransformInputIterator<uint32_t, UnmarkedM, hipcub::CountingInputIterator<uint32_t>> unmarked(
                     entries, UnmarkedM{mark_sub, n_m});
             HIP_OK(exclusive_sum(unmarked, arank, (size_t)n_m + 1));
-            hipLaunchKernelGGL(k_arank_m, dim3(blocks_for(std::max(n_m, 1u))), dim3(TPB), 0, stream, arank, g.m_entry, n_m,
-                               E, v.arank_m, sc);
+            hipLaunchKernelGGL(k_ranks_runs, dim3(blocks_for(std::max(n_m, 1u))), dim3(TPB), 0, stream, raw, v.ranks,
+                               g.m_entry, n_m, v.arank_m, m.rbeg, v.incl, g.sloc, v.runs.run_start, v.read_locus,
+                               v.read_base, sc);
             arank_sub = v.arank_m;
-            hipLaunchKernelGGL(k_rbeg, dim3(1), dim3(TPB), 0, stream, raw, v.ranks, m.rbeg);
         } else {
             HIP_OK(exclusive_sum(v.marks.mark, arank, (size_t)E + 1));
+            if (n_m)
+                hipLaunchKernelGGL(k_runs_csr, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, g.sub, v.incl, g.sval, g.sloc,
+                                   n_m, v.runs.run_start, v.read_locus, v.read_base);
         }
         if (n_m) {
-            hipLaunchKernelGGL(k_runs_csr, dim3(blocks_for(n_m)), dim3(TPB), 0, stream, g.sub, v.incl, g.sval, g.sloc, n_m,
-                               v.runs.run_start, v.read_locus, v.read_base);
-            hipLaunchKernelGGL(k_read_info, dim3(std::min<uint32_t>(blocks_for(n_m), 2048)), dim3(TPB), 0, stream, g.sub,
+            // The single-entry route's few reads (the M entries) take a grid of 512 workgroups at the most, and its last
+            // workgroup publishes (each draws a ticket; the scan's last sum rides along: reads | kept entries << 32).
+            // The whole pileup's reads (clustered loci: tens of millions) keep the large grid and the k_publish behind.
+            const bool fold = pub && g.single_entry;
+            const Publish folded = fold ? (*pub = fold_publish(pk, v.incl + (n_m - 1))) : Publish{nullptr, 0ull, nullptr};
+            hipLaunchKernelGGL(k_read_info, dim3(std::min<uint32_t>(blocks_for(n_m), fold ? 512 : 2048)), dim3(TPB), 0, stream, g.sub,
                                v.incl, v.runs.run_start, g.sval, g.sloc, arank_sub, mfl, v.runs.run_rank,
-                               g.single_entry ? nullptr : m.rbeg, v.read_off, sc);
+                               g.single_entry ? nullptr : m.rbeg, v.read_off, sc, folded);
         }
         HIP_OK(hipEventRecord(pk.ev_fork, stream));
         HIP_OK(hipStreamWaitEvent(pk.side, pk.ev_fork, 0));
@@ -2450,10 +2606,12 @@ struct PackAttempt {
         hipLaunchKernelGGL(k_ranges_segment, dim3(s.p.n_seg, s.p.caps.allow_counts ? 2u : 1u), dim3(TPB), 0, on, s.blk_off,
                            s.p.nb, L, s.p.caps, s.segs.seg_ends, s.segs.seg_count, s.p.variant_stride);
     }
-    Attempt cut_ranges_on_side(const Stage5 &s) {  // call when blk_off is complete on `stream`
+    // (call when blk_off is complete on `stream`; pick: the ranges are picked there as well, see bin_counting)
+    Attempt cut_ranges_on_side(const Stage5 &s, bool pick) {
         HIP_OK(hipEventRecord(pk.ev_offsets, stream));
         HIP_OK(hipStreamWaitEvent(pk.side, pk.ev_offsets, 0));
         launch_ranges_segment(s, pk.side);
+        if (pick) compact_ranges(s, 0u, assumed_variant(s.p), pk.side);
         HIP_OK(hipEventRecord(pk.ev_join, pk.side));
         return Attempt();
     }
@@ -2467,14 +2625,22 @@ struct PackAttempt {
     }
     // the locus ranges picked from the segments (assumed: 1 the count tile's limits, 0 the plain ones, -1 by the pair
     // bound of sq_rows rows) and what a record needs of its locus
-    void pick_ranges(const Stage5 &s, uint32_t sq_rows, int assumed, const uint8_t *dupflag) {
-        hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, stream, s.segs.seg_ends, s.segs.seg_count,
+    void compact_ranges(const Stage5 &s, uint32_t sq_rows, int assumed, hipStream_t on) {
+        hipLaunchKernelGGL(k_ranges_compact, dim3(1), dim3(TPB), 0, on, s.segs.seg_ends, s.segs.seg_count,
                            s.p.variant_stride, s.p.n_seg, s.p.caps, pk.range_off.as<uint32_t>(), s.per_cell_sq, sq_rows,
                            assumed, sc);
+    }
+    void locus_info(const Stage5 &s, const uint8_t *dupflag) {
         if (s.n_kept)
             hipLaunchKernelGGL(k_locus_info, dim3(blocks_for(L)), dim3(TPB), 0, stream, raw, pk.range_off.as<uint32_t>(),
                                sc, dupflag, m.locus_chr, m.locus_rel);
     }
+    void pick_ranges(const Stage5 &s, uint32_t sq_rows, int assumed, const uint8_t *dupflag) {
+        compact_ranges(s, sq_rows, assumed, stream);
+        locus_info(s, dupflag);
+    }
+    // the limits the counting route cuts the ranges for before the pair bound is known
+    static int assumed_variant(const TilePlan &p) { return p.caps.allow_counts ? 1 : 0; }
 
     // radix route: sort the kept entries by (block, locus, cell), count the groups
     Attempt bin_radix(const Stage5 &s) {
@@ -2488,7 +2654,7 @@ struct PackAttempt {
                                stream, b.key2_b, s.n_kept, s.p.B, L, s.p.lbits, s.blk_cnt, s.per_cell_sq);
         }
         HIP_OK(exclusive_sum(s.blk_cnt, s.blk_off, s.n_off));
-        return cut_ranges_on_side(s);
+        return cut_ranges_on_side(s, false);
     }
     // counting route: per-locus LDS histograms (hist_first: launched already, in front of k_keys2), scan, placement
     Attempt bin_counting(const Grouped &g, const ReadViews &v, const Stage5 &s, bool hist_first) {
@@ -2511,10 +2677,14 @@ struct PackAttempt {
         }
         HIP_OK(exclusive_sum(s.blk_cnt, s.blk_off, s.n_off));
         trace.mark("offset scan launched");
+        // The picking of the ranges (k_ranges_compact) needs the segments only, nothing the placing pass writes: it
+        // goes directly behind the cutting, beside the placing pass; k_locus_info, which wants the placing pass'
+        // duplicate flags, stays behind it on the main stream (records_counting).
         if (records_first) {
             launch_ranges_segment(s, stream);
+            compact_ranges(s, 0u, assumed_variant(p), stream);
         } else {
-            STEP(cut_ranges_on_side(s));
+            STEP(cut_ranges_on_side(s, true));
             if (s.kept_m) STEP(m_records_on_side(s, v));  // behind the flush chain and the range cutting
         }
         if (s.n_kept) {
@@ -2542,11 +2712,12 @@ struct PackAttempt {
     // are cut for the count tile if it is allowed at all; the pair bound comes out of the same pass, and if it forbids
     // the count tile the ranges are cut again and the records patched (deep pileups only: close_attempt).
     // Returns whether the records pass left the flags the flagged entries' lists are made of.
-    bool records_counting(const Stage5 &s) {
+    // pub: the read-back behind the records, published by the tail kernel (close_attempt launches nothing for it)
+    bool records_counting(const Stage5 &s, Publish *pub) {
         const TilePlan &p = s.p;
-        const int assumed = p.caps.allow_counts ? 1 : 0;
+        const int assumed = assumed_variant(p);
         bool lists_here = false;
-        pick_ranges(s, 0u, assumed, s.dupflag);
+        locus_info(s, s.dupflag);  // (the ranges were picked beside the placing pass: bin_counting)
         if (s.n_kept) {
             const RecordTables tables{s.m_rec, m.locus_rel, pk.entry.as<uint4>(), pk.entry32.as<uint32_t>(),
                                       pk.stage_masks ? pk.mask32.as<uint32_t>() : nullptr, pk.entry_read.as<uint32_t>()};
@@ -2560,8 +2731,11 @@ struct PackAttempt {
                                GroupedKept(S[Arena::KEY_B].p, E).p, s.blk_off, s.n_kept, p.nb, L, p.B, p.lbits, tables,
                                s.per_cell_sq, sc, lists_here ? fs.chunk_mask : nullptr, lists_here ? fs.block_sum : nullptr);
         }
-        hipLaunchKernelGGL(k_pair_bound, dim3(1), dim3(TPB), 0, stream, s.per_cell_sq, s.n_kept ? p.nb * p.B : 0u, p.caps,
-                           (uint32_t)assumed, sc);
+        const FlagScratch fs(lists_here ? pk.flag_lists.scratch : nullptr, s.n_kept);
+        *pub = fold_publish(pk, nullptr);
+        hipLaunchKernelGGL(k_records_tail, dim3(1), dim3(TPB_SCAN), 0, stream, s.per_cell_sq, s.n_kept ? p.nb * p.B : 0u,
+                           p.caps, (uint32_t)assumed, sc, *pub, lists_here ? fs.block_sum : nullptr, fs.nb,
+                           lists_here ? fs.block_off : nullptr, lists_here ? fs.chunk_pre + 64 * (size_t)fs.nb : nullptr);
         return lists_here;
     }
     // read-back 3: errors of the group mapping, pair bound (-> tile variant), number of ranges. The list chain goes
@@ -2569,7 +2743,7 @@ struct PackAttempt {
     // caller and launches the pair kernel. (In front of the publishing kernel the host learned the scalars 50 us
     // later and the GPU then stood idle for as long as the host needs from there to the pair kernel's launch: 74 us
     // under the profiler on C3, and C2, whose lists take 15 us, lost 20 us against the lists behind the read-back.)
-    Attempt close_attempt(const Stage5 &s, bool lists_launched) {
+    Attempt close_attempt(const Stage5 &s, bool lists_launched, const Publish *folded) {
         const TilePlan &p = s.p;
         Scalars hsc;
         trace.mark("records launched");
@@ -2577,7 +2751,7 @@ struct PackAttempt {
             if (lists_launched)
                 flag_lists_from_masks(FlagScratch(pk.flag_lists.scratch, s.n_kept), pk.entry.as<uint4>(), s.blk_off, s.n_off,
                                       pk.flag_lists.grp, pk.flag_lists.rec, pk.flag_lists.idx, stream);
-        }));
+        }, folded));
         trace.mark("read-back 3 arrived");
         if (!force_radix && hsc.caps_wrong && !hsc.regroup && hsc.error == 0) {
             pick_ranges(s, 0u, 0, nullptr);
@@ -2616,7 +2790,8 @@ struct PackAttempt {
 
         STEP(ensure_outputs());
         const ReadViews v = read_views(g);
-        STEP(build_reads(g, v, nullptr));
+        Publish pub2{nullptr, 0ull, nullptr};  // read-back 2 rides on k_read_info on the single-entry route (n_m > 0)
+        STEP(build_reads(g, v, nullptr, &pub2));
         struct SideJoin {  // every way out of this function leaves the side stream idle
             hipStream_t side;
             bool joined = false;
@@ -2627,7 +2802,8 @@ struct PackAttempt {
         Scalars hsc;
         unsigned long long totals = 0;  // reads | kept entries << 32
         trace.mark("reads built (launched)");
-        HIP_OK(read_scalars(pk, stream, sc, g.n_m ? v.incl + (g.n_m - 1) : nullptr, &hsc, &totals));
+        HIP_OK(read_scalars(pk, stream, sc, g.n_m ? v.incl + (g.n_m - 1) : nullptr, &hsc, &totals, nullptr,
+                            g.n_m && g.single_entry ? &pub2 : nullptr));
         trace.mark("read-back 2 arrived");
         const Attempt verdict = scalar_verdict(hsc, false);
         if (verdict.go() || verdict.kind == Attempt::RetryRadix || verdict.kind == Attempt::NeedHost)
@@ -2696,11 +2872,12 @@ struct PackAttempt {
         HIP_OK(hipStreamWaitEvent(stream, pk.ev_join, 0));
         side_join.joined = true;
         bool lists_launched = false;
+        Publish pub3{nullptr, 0ull, nullptr};
         if (force_radix)
             records_radix(v, s);
         else
-            lists_launched = records_counting(s);
-        return close_attempt(s, lists_launched);
+            lists_launched = records_counting(s, &pub3);
+        return close_attempt(s, lists_launched, force_radix ? nullptr : &pub3);
     }
 };
 

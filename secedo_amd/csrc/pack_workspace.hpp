@@ -74,7 +74,8 @@ struct One {
 
 // ---- MISC: the scalars and the per-chromosome / per-locus tables; one generation, alive over the whole attempt -----
 // (k_id_range writes, the closing read-back reads.) The attempt begins by clearing the prefix [0, zeroed): the
-// scalars, the id extremes k_id_range raises with atomics and the bases k_id_bases sums up.
+// scalars (among them the ticket words of the kernels whose last workgroup finishes the job), the id extremes
+// k_id_range raises with atomics and the bases its last workgroup sums up.
 template <class Scalars>
 struct MiscViews {
     Scalars *sc;
@@ -83,7 +84,7 @@ struct MiscViews {
     uint32_t *rbeg, *flushed;                // [C + 1] [C]
     uint32_t *cnt, *locus_chr, *locus_rel, *flush_loci;  // [L] each
     uint32_t *flush_count, *tail_begin;      // [C] [C]
-    uint32_t *chr_entry;  // [C + 1] first entry of every chromosome, and the number of entries (k_id_bases)
+    uint32_t *chr_entry;  // [C + 1] first entry of every chromosome, and the number of entries (k_id_range)
     size_t end;
     MiscViews(Carver c, const PackShape &s) {
         sc = c.take<Scalars>(1);
@@ -128,7 +129,7 @@ using KeptFlags = One<uint8_t>;  // [kept] base | multi flag per kept entry: k_k
 // ---- VAL_B, ELOC, ENTRY_KC, TMP ------------------------------------------------------------------------------------
 using SortedValues = One<uint32_t>;  // VAL_B [E] stage 1 -> k_keys2
 using EntryLocus = One<uint32_t>;    // ELOC [E] k_entry_locus -> k_id_rank / k_sorted_locus (no single-entry route)
-using SortedLoci = One<uint32_t>;    // ENTRY_KC [E] locus | base in sorted order: stage 1 -> k_split_update / k_runs_csr
+using SortedLoci = One<uint32_t>;    // ENTRY_KC [E] locus | base in sorted order: stage 1 -> k_split_update / k_runs_csr / k_ranks_runs
 using EntryKC = One<unsigned long long>;  // ENTRY_KC [E] counting route, (k, cell) per entry: k_bin_hist / k_keys2 -> k_bin_place
 using SplitFlags = One<uint32_t>;    // TMP [E] cuts of long reads: memset / k_split_update -> k_dup_mark of the last build
 using KeptRead = One<uint32_t>;      // TMP [E] read index per kept entry: k_keys2 -> k_records / k_m_records
@@ -138,7 +139,7 @@ using KeepFlags = One<uint32_t>; // WORK_A [E + 1] duplicate rule: k_dup_mark ->
 using KeptRank = One<uint32_t>;  // WORK_A [E] appearance rank per kept entry: k_keys2 -> k_records / k_m_records
 using IdOffsets = One<uint32_t>; // WORK_B [id_slots] the scan of the counts -> k_id_rank
 using InclSums = One<unsigned long long>;  // WORK_B [E + 1] reads | kept entries << 32 so far: the read scan -> k_keys2
-// ---- RUNS: k_runs_csr, k_read_info -> k_keys2 ----------------------------------------------------------------------
+// ---- RUNS: k_runs_csr / k_ranks_runs, k_read_info -> k_keys2 ----------------------------------------------------------------------
 struct Runs {
     uint32_t *run_start, *run_rank;  // [E + 1] [E] (reads R <= E)
     size_t end;
@@ -180,8 +181,10 @@ struct MChunks {  // M_CHUNKS: k_compact_m / k_flag_scan -> k_bin_hist (struct M
 };
 using MultiFlags = One<uint8_t>;  // MARK_M [flag_bytes] a byte per entry: memset / k_id_check -> k_compact_m
 using MarksOfM = One<uint32_t>;   // MARK_M [E + 2] the marks of the M entries: k_dup_mark -> the scan of UnmarkedM
-using PerM = One<uint32_t>;       // M_ENTRY, RID_M, IDB_M, ELOC_M (k_compact_m / k_m_fields -> k_keys2), ARANK_M (k_arank_m -> k_read_info): [E]
-struct MReads {  // DENSE_M, the reads of the n_m <= E / 2 M entries: k_m_fields -> k_group_rank
+using PerM = One<uint32_t>;       // M_ENTRY, RID_M, IDB_M, ELOC_M (k_compact_m / k_m_fields -> k_keys2), ARANK_M (k_ranks_runs -> k_read_info): [E]
+struct MReads {  // DENSE_M, the reads of the n_m <= E / 2 M entries: k_m_fields -> k_group_rank. count_m is zeroed by
+                 // k_compact_m, which does not know n_m yet: it is the FIRST view, at the arena's base whatever n_m is
+                 // (E + 1 words at the most, within the arena: a route given up at n_m > E / 2 has zeroed them too)
     uint32_t *count_m, *goff, *winner_m, *g_begin, *g_len, *members;  // [n_m + 1] [n_m + 1] [n_m] ...
     size_t end;
     MReads(Carver c, size_t n_m) {
@@ -192,7 +195,8 @@ struct MReads {  // DENSE_M, the reads of the n_m <= E / 2 M entries: k_m_fields
 };
 // ---- DUPF, SEGS (stage 5) ------------------------------------------------------------------------------------------
 using DupFlags = One<uint8_t>;  // DUPF [L] some cell has two kept entries at the locus: k_bin_place -> k_locus_info
-struct Segs {  // k_ranges_segment -> k_ranges_compact (the repair behind read-back 3 included); both variants of limits
+struct Segs {  // k_ranges_segment -> k_ranges_compact (on the side stream beside the placing pass; the repair behind
+               // read-back 3 included); both variants of limits
     uint32_t *seg_count, *seg_ends;  // [n_seg] [2 variant_stride - n_seg]
     size_t end;
     Segs(Carver c, size_t n_seg, size_t variant_stride) {

@@ -613,6 +613,20 @@ int secedo_simmat_debug_flag_lists(secedo_simmat_t *h, uint64_t *n_flagged, uint
     return SECEDO_OK;
 }
 
+int secedo_simmat_debug_ranges(secedo_simmat_t *h, uint32_t *num_ranges, uint32_t *max_range_span, uint32_t *cap_loci,
+                               uint32_t *range_off) {
+    if (!h || !num_ranges || !max_range_span || !cap_loci) return fail(SECEDO_E_INVALID_ARG, "null argument");
+    if (!h->prepared) return fail(SECEDO_E_STATE, "no pileup has been prepared");
+    SECEDO_TRY(hipSetDevice(h->device));
+    SECEDO_TRY(hipDeviceSynchronize());
+    *num_ranges = h->pk.num_ranges;
+    *max_range_span = h->pk.max_range_span;
+    *cap_loci = h->pk.cap_loci;
+    if (range_off)
+        SECEDO_TRY(hipMemcpy(range_off, h->pk.range_off.p, ((size_t)h->pk.num_ranges + 1) * 4, hipMemcpyDeviceToHost));
+    return SECEDO_OK;
+}
+
 int secedo_simmat_last_pair_kernel_ms(secedo_simmat_t *h, float *ms) {
     if (!h || !ms) return fail(SECEDO_E_INVALID_ARG, "null argument");
     if (!h->timed || !h->timed_mid) return fail(SECEDO_E_STATE, "the last accumulate did not run the sparse-loci kernels");
